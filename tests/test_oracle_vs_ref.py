@@ -1,109 +1,97 @@
-"""Pins the CPU oracle (oracle/vorbis_synth_oracle.c) against the REFERENCE ITSELF, compiled from its own
-sources into oracle/_ref/libref_shim.so (authoring container; the prebuilt .so travels to the GPU box).
-Bit-exact for everything: same arithmetic, same order.  Skipped only if oracle/_ref was never built.
+"""Pins the CPU oracle (oracle/vorbis_synth_oracle.c) against the REFERENCE ITSELF: the answers of the reference's own
+code (oracle/_ref/libref_shim.so, built from its sources by oracle/Makefile) on the seeded inputs below are stored in
+tests/golden/ref_shim.npz by oracle/make_ref_vectors.py, so the suite needs no reference tree.
+Bit-exact for everything: same arithmetic, same order.  Large outputs are stored as the sha256 of their bits.
 """
-import ctypes as C
+import hashlib
+import os
 
 import numpy as np
 import pytest
 
 from oracle import oracle_binding as ob
 
-pytestmark = pytest.mark.skipif(not ob.have_ref(), reason="oracle/_ref/libref_shim.so not built (make -C oracle)")
-
 SIZES = [64, 128, 256, 512, 1024, 2048, 4096, 8192]  # every Vorbis I blocksize, hpp:1294
+CLOSED_FORM_SIZES = [64, 256, 2048]
+WINDOW_PAIRS = [(256, 2048), (64, 64), (64, 8192), (512, 1024), (2048, 2048)]
+WINDOW_CASES = [(flag, prev, nxt) for flag in (0, 1) for prev in (0, 1) for nxt in (0, 1)]
+FLOOR_MULTS = [1, 2, 3, 4]
+FLOOR_SHAPES = [(2, 64), (9, 256), (29, 2048), (65, 8192), (17, 128)]
+FLOOR_TRIALS = 25
+OVERLAP_CONFIGS = [(256, 2048, 2), (64, 128, 1), (128, 128, 3), (64, 8192, 2)]
+OVERLAP_TRIALS = 4
+
+REF_VECTORS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_shim.npz")
+_vectors = None
 
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-@pytest.mark.parametrize("n", SIZES)
-def test_mdct_tables_and_backward_bit_exact(n):
-    orc, ref = ob.oracle(), ob.ref()
-    trig = np.zeros(n + n // 4, np.float32)
-    rev = np.zeros(n // 4, np.int32)
-    ref.ref_mdct_tables(n, ob.p(trig), ob.p(rev))
-    m = orc.orc_mdct_new(n)
-    ot = np.ctypeslib.as_array(orc.orc_mdct_trig(m), shape=(n + n // 4,))
-    orv = np.ctypeslib.as_array(orc.orc_mdct_bitrev(m), shape=(n // 4,))
-    assert np.array_equal(bits(ot), bits(trig))
-    assert np.array_equal(orv, rev)
-    orc.orc_mdct_free(m)
+def digest(a):
+    """sha256 of an array's dtype, shape and bytes: equal digests <=> equal arrays, bit for bit."""
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256()
+    h.update(("%s %s " % (a.dtype.str, a.shape)).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
 
+
+def ref_vector(key):
+    global _vectors
+    if _vectors is None:
+        _vectors = np.load(REF_VECTORS)
+    return _vectors[key]
+
+
+def assert_ref(key, got):
+    """got == the reference's answer stored under key (the array itself, or the digest of its bits)."""
+    want = ref_vector(key)
+    if want.dtype.kind == "U":
+        assert digest(got) == str(want), key
+    else:
+        assert got.dtype == want.dtype and np.array_equal(got, want), key
+
+
+# ---- seeded inputs (shared with oracle/make_ref_vectors.py, which stores the reference's answers to them) ----
+
+def mdct_input(n):
     rng = np.random.default_rng(n)
-    cnt = 16
-    x = rng.standard_normal((cnt, n // 2)).astype(np.float32)
+    x = rng.standard_normal((16, n // 2)).astype(np.float32)
     x[0] = 0
     x[1, :] = 0
     x[1, 3] = 1.0  # impulse
-    want = np.empty((cnt, n), np.float32)
-    ref.ref_mdct_backward_batch(n, cnt, ob.p(x), ob.p(want))
-    got = ob.imdct(n, x)
-    assert np.array_equal(bits(got), bits(want))
+    return x
 
 
-@pytest.mark.parametrize("n", [64, 256, 2048])
-def test_closed_form_agrees_with_reference(n):
+def closed_form_input(n):
     rng = np.random.default_rng(7)
-    x = (rng.standard_normal(n // 2) * 0.05).astype(np.float32)
-    want = np.empty(n, np.float32)
-    ob.ref().ref_mdct_backward(n, ob.p(x), ob.p(want))
-    cf = np.empty(n, np.float64)
-    ob.oracle().orc_imdct_closed_form(n, ob.p(x), ob.p(cf))
-    assert np.abs(cf - want).max() < 2e-6
-    # symmetries stated in SURVEY 8a-7
-    assert np.array_equal(want[: n // 2][::-1], -want[: n // 2])
-    assert np.array_equal(want[n // 2:][::-1], want[n // 2:])
+    return (rng.standard_normal(n // 2) * 0.05).astype(np.float32)
 
 
-@pytest.mark.parametrize("bs0,bs1", [(256, 2048), (64, 64), (64, 8192), (512, 1024), (2048, 2048)])
-def test_windows_bit_exact(bs0, bs1):
-    for flag in (0, 1):
-        n = bs1 if flag else bs0
-        for prev in (0, 1):
-            for nxt in (0, 1):
-                a = np.zeros(n, np.float32)
-                b = np.zeros(n, np.float32)
-                assert ob.ref().ref_window(bs0, bs1, flag, prev, nxt, ob.p(a)) == 0
-                ob.oracle().orc_window(bs0, bs1, flag, prev, nxt, ob.p(b))
-                assert np.array_equal(bits(a), bits(b)), (flag, prev, nxt)
-
-
-def test_inverse_db_table_bit_exact():
-    a = np.ctypeslib.as_array(ob.ref().ref_inverse_db_table(), shape=(256,))
-    b = np.ctypeslib.as_array(ob.oracle().orc_inverse_db_table(), shape=(256,))
-    assert np.array_equal(bits(a), bits(b))
-
-
-def test_render_helpers():
+def render_inputs():
+    """-> (render_point args [2000 x 5], render_line (x0, y0, x1, y1, len) [300], neighbor sets [200])"""
     rng = np.random.default_rng(3)
-    orc, ref = ob.oracle(), ob.ref()
+    points = []
     for _ in range(2000):
         x0 = int(rng.integers(0, 1000))
         x1 = x0 + int(rng.integers(1, 600))
         y0, y1 = int(rng.integers(0, 256)), int(rng.integers(0, 256))
         X = int(rng.integers(x0, x1 + 1))
-        assert orc.orc_render_point(x0, y0, x1, y1, X) == ref.ref_render_point(x0, y0, x1, y1, X)
+        points.append((x0, y0, x1, y1, X))
+    lines = []
     for _ in range(300):
         ln = int(rng.integers(8, 1200))
         x0 = int(rng.integers(0, ln + 20))
         x1 = x0 + int(rng.integers(1, 700))
         y0, y1 = int(rng.integers(0, 256)), int(rng.integers(0, 256))
-        a = np.full(ln, 7777, np.uint32)
-        b = a.copy()
-        orc.orc_render_line(x0, y0, x1, y1, ob.p(a), ln)
-        ref.ref_render_line(x0, y0, x1, y1, ob.p(b), ln)
-        assert np.array_equal(a, b)
-        # DDA == closed form per x (the identity the HIP kernel relies on)
-        for x in range(x0, min(x1, ln)):
-            assert a[x] == orc.orc_render_point(x0, y0, x1, y1, x)
+        lines.append((x0, y0, x1, y1, ln))
+    sets = []
     for _ in range(200):
         k = int(rng.integers(3, 66))
-        v = rng.permutation(5000)[:k].astype(np.uint32)
-        for idx in range(1, k):
-            assert orc.orc_low_neighbor(ob.p(v), idx) == ref.ref_low_neighbor(ob.p(v), k, idx)
-            assert orc.orc_high_neighbor(ob.p(v), idx) == ref.ref_high_neighbor(ob.p(v), k, idx)
+        sets.append(rng.permutation(5000)[:k].astype(np.uint32))
+    return np.array(points, np.uint32), lines, sets
 
 
 def random_xs(rng, posts, n2):
@@ -153,21 +141,15 @@ def valid_ys(rng, xs, mult, zero_frac=0.3):
     return ys
 
 
-@pytest.mark.parametrize("mult", [1, 2, 3, 4])
-@pytest.mark.parametrize("posts,n", [(2, 64), (9, 256), (29, 2048), (65, 8192), (17, 128)])
-def test_floor1_tail_vs_reference(mult, posts, n):
+def floor1_inputs(mult, posts, n):
+    """-> [(xs, ys)] of the trials"""
     rng = np.random.default_rng(1000 * mult + posts)
-    orc, ref = ob.oracle(), ob.ref()
-    for trial in range(25):
+    out = []
+    for trial in range(FLOOR_TRIALS):
         xs = random_xs(rng, posts, n // 2)
         ys = valid_ys(rng, xs, mult) if trial % 5 else rng.integers(0, 60, posts).astype(np.uint32)  # some wild ones
-        want = np.zeros(n, np.float32)
-        got = np.zeros(n, np.float32)
-        rr = ref.ref_floor1_synth(ob.p(xs), posts, mult, ob.p(ys), n, ob.p(want))
-        ro = orc.orc_floor1_synth(ob.p(xs), posts, mult, ob.p(ys), n, ob.p(got), None, None, None)
-        assert (rr != 0) == (ro != 0), (trial, rr, ro)
-        if rr == 0:
-            assert np.array_equal(bits(got), bits(want))
+        out.append((xs, ys))
+    return out
 
 
 def make_seq(rng, npk):
@@ -182,13 +164,12 @@ def make_seq(rng, npk):
     return flags, widx
 
 
-@pytest.mark.parametrize("bs0,bs1,channels", [(256, 2048, 2), (64, 128, 1), (128, 128, 3), (64, 8192, 2)])
-def test_overlap_add_state_vs_reference(bs0, bs1, channels):
-    """oracle decode state == reference VorbisStreamDecodeState on random mixed block sequences (incl. the
-    sliding-buffer moves) with a clipping granule on the last packet."""
-    from parseoggvorbis_amd.binding import SetupSpec, PACKET_DTYPE, SEGMENT_DTYPE
+def overlap_inputs(bs0, bs1, channels):
+    """-> [dict(flags, widx, sizes, blocks, gran, cap)] of the trials: random mixed block sequences with a clipping granule on
+    the last packet of every other trial"""
     rng = np.random.default_rng(bs0 + bs1 + channels)
-    for trial in range(4):
+    out = []
+    for trial in range(OVERLAP_TRIALS):
         npk = int(rng.integers(2, 40))
         flags, widx = make_seq(rng, npk)
         sizes = np.where(flags, bs1, bs0)
@@ -197,14 +178,97 @@ def test_overlap_add_state_vs_reference(bs0, bs1, channels):
         gran = np.full(npk, -1, np.int64)
         if trial % 2:
             gran[-1] = max(0, total - int(rng.integers(0, min(sizes[-1], sizes[-2]) // 4)))
-        cap = total + 16
-        want = np.zeros((channels, cap), np.float32)
-        emit_w = np.zeros(npk, np.uint32)
-        bad = C.c_int(-1)
-        flat = np.concatenate([b.ravel() for b in blocks])
-        rc = ob.ref().ref_overlap_add(channels, bs0, bs1, npk, ob.p(flags), ob.p(widx), ob.p(gran), ob.p(flat),
-                                      ob.p(want), cap, ob.p(emit_w), C.byref(bad))
-        assert rc == 0
+        out.append(dict(flags=flags, widx=widx, sizes=sizes, blocks=blocks, gran=gran, cap=total + 16))
+    return out
+
+
+def canonical_zero(a):
+    """-0.0 -> +0.0: the overlap test compares numerically, as the reference's PCM and the re-drive may differ in the zero's sign"""
+    return (np.asarray(a, np.float32) + np.float32(0.0)).astype(np.float32)
+
+
+# ---- the tests ----
+
+@pytest.mark.parametrize("n", SIZES)
+def test_mdct_tables_and_backward_bit_exact(n):
+    orc = ob.oracle()
+    m = orc.orc_mdct_new(n)
+    ot = np.ctypeslib.as_array(orc.orc_mdct_trig(m), shape=(n + n // 4,))
+    orv = np.ctypeslib.as_array(orc.orc_mdct_bitrev(m), shape=(n // 4,))
+    assert_ref("mdct_trig_%d" % n, bits(ot))
+    assert_ref("mdct_bitrev_%d" % n, orv.astype(np.int32))
+    orc.orc_mdct_free(m)
+    got = ob.imdct(n, mdct_input(n))
+    assert_ref("mdct_backward_%d" % n, bits(got))
+
+
+@pytest.mark.parametrize("n", CLOSED_FORM_SIZES)
+def test_closed_form_agrees_with_reference(n):
+    x = closed_form_input(n)
+    want = ref_vector("closed_form_%d" % n)
+    cf = np.empty(n, np.float64)
+    ob.oracle().orc_imdct_closed_form(n, ob.p(x), ob.p(cf))
+    assert np.abs(cf - want).max() < 2e-6
+    # symmetries stated in SURVEY 8a-7
+    assert np.array_equal(want[: n // 2][::-1], -want[: n // 2])
+    assert np.array_equal(want[n // 2:][::-1], want[n // 2:])
+
+
+@pytest.mark.parametrize("bs0,bs1", WINDOW_PAIRS)
+def test_windows_bit_exact(bs0, bs1):
+    for flag, prev, nxt in WINDOW_CASES:
+        n = bs1 if flag else bs0
+        b = np.zeros(n, np.float32)
+        ob.oracle().orc_window(bs0, bs1, flag, prev, nxt, ob.p(b))
+        assert_ref("window_%d_%d_%d%d%d" % (bs0, bs1, flag, prev, nxt), bits(b))
+
+
+def test_inverse_db_table_bit_exact():
+    b = np.ctypeslib.as_array(ob.oracle().orc_inverse_db_table(), shape=(256,))
+    assert_ref("inverse_db_table", bits(b))
+
+
+def test_render_helpers():
+    orc = ob.oracle()
+    points, lines, sets = render_inputs()
+    assert_ref("render_point", np.array([orc.orc_render_point(*(int(v) for v in pt)) for pt in points], np.uint32))
+    rendered = []
+    for x0, y0, x1, y1, ln in lines:
+        a = np.full(ln, 7777, np.uint32)
+        orc.orc_render_line(x0, y0, x1, y1, ob.p(a), ln)
+        # DDA == closed form per x (the identity the HIP kernel relies on)
+        for x in range(x0, min(x1, ln)):
+            assert a[x] == orc.orc_render_point(x0, y0, x1, y1, x)
+        rendered.append(a)
+    assert_ref("render_line", np.concatenate(rendered))
+    nb = [(orc.orc_low_neighbor(ob.p(v), idx), orc.orc_high_neighbor(ob.p(v), idx)) for v in sets for idx in range(1, len(v))]
+    assert_ref("neighbors", np.array(nb, np.int32))
+
+
+@pytest.mark.parametrize("mult", FLOOR_MULTS)
+@pytest.mark.parametrize("posts,n", FLOOR_SHAPES)
+def test_floor1_tail_vs_reference(mult, posts, n):
+    orc = ob.oracle()
+    key = "floor1_%d_%d_%d" % (mult, posts, n)
+    want_rc = ref_vector(key + "_failed")
+    decoded = []
+    for trial, (xs, ys) in enumerate(floor1_inputs(mult, posts, n)):
+        got = np.zeros(n, np.float32)
+        ro = orc.orc_floor1_synth(ob.p(xs), posts, mult, ob.p(ys), n, ob.p(got), None, None, None)
+        assert bool(want_rc[trial]) == (ro != 0), (trial, ro)
+        if ro == 0:
+            decoded.append(bits(got))
+    assert_ref(key, np.concatenate(decoded) if decoded else np.zeros(0, np.uint32))
+
+
+@pytest.mark.parametrize("bs0,bs1,channels", OVERLAP_CONFIGS)
+def test_overlap_add_state_vs_reference(bs0, bs1, channels):
+    """oracle decode state == reference VorbisStreamDecodeState on random mixed block sequences (incl. the
+    sliding-buffer moves) with a clipping granule on the last packet."""
+    for trial, t in enumerate(overlap_inputs(bs0, bs1, channels)):
+        flags, widx, sizes, blocks, gran, cap = t["flags"], t["widx"], t["sizes"], t["blocks"], t["gran"], t["cap"]
+        npk = len(flags)
+        key = "overlap_%d_%d_%d_%d" % (bs0, bs1, channels, trial)
         # oracle side: run only the state part by feeding identity "IMDCT": instead use the oracle's own
         # functions through a python re-drive of orc_window + the two-term overlap formula
         pos = 0
@@ -230,5 +294,5 @@ def test_overlap_add_state_vs_reference(bs0, bs1, channels):
             got[:, pos:pos + L] = chunk[:, :L]
             emit_g[i] = L
             pos += L
-        assert np.array_equal(emit_g, emit_w)
-        assert np.array_equal(got, want)  # numerically equal (-0.0 == 0.0)
+        assert_ref(key + "_emit", emit_g)
+        assert_ref(key + "_pcm", bits(canonical_zero(got)))  # numerically equal (-0.0 == 0.0); the stored PCM is finite
