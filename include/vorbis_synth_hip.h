@@ -46,7 +46,7 @@ enum {
   VSYN_ERR_STREAM = 4     /* the batch itself is bad (see vsyn_status.flags) */
 };
 
-/* vsyn_status.flags — conditions on which the reference fails a CHECK and aborts the read */
+/* vsyn_status.flags — conditions on which the reference fails a CHECK and aborts the read (VSYN_ST_WINDOW_FLAGS: see there) */
 enum {
   VSYN_ST_FLOOR_RANGE = 1u << 0,   /* predicted > range, hpp:536 */
   VSYN_ST_FLOOR_VALUE = 1u << 1,   /* rendered floor value >= 256, hpp:587 */
@@ -54,7 +54,12 @@ enum {
   VSYN_ST_PLANE_OVERFLOW = 1u << 3,/* a segment emits more than plane_stride samples (nothing is written out of bounds) */
   VSYN_ST_BAD_MODE = 1u << 4,      /* mode index >= num_modes */
   VSYN_ST_BAD_SEGMENT = 1u << 5,   /* segment out of range / unknown stream slot / unaligned residue_off */
-  VSYN_ST_BAD_VQ = 1u << 6         /* VQ stage: entry or classification number out of range, or entry count inconsistent with the classifications */
+  VSYN_ST_BAD_VQ = 1u << 6,        /* VQ stage: entry or classification number out of range, or entry count inconsistent with the classifications */
+  VSYN_ST_WINDOW_FLAGS = 1u << 7   /* a block smaller than the long block in front of it, whose next_long flag is set (only possible when
+                                      blocksize0 < blocksize1). Unlike the bits above, the reference ACCEPTS this input: it picks windows
+                                      from the flags alone (hpp:874-886) and keeps the long window's right slope beyond the smaller block
+                                      in its sliding buffer, where later packets add to it depending on when the buffer slides (hpp:1069-1109).
+                                      The device refuses the packet rather than return different PCM. Every other flag combination is exact. */
 };
 
 /* ---- stream setup: the part of VorbisStreamSetup (hpp:889-964) the synthesis half reads ---- */

@@ -93,6 +93,14 @@ def main():
             put(key + "_emit", emit)
             put(key + "_pcm", t.bits(t.canonical_zero(want)))
 
+    for bs0, bs1, channels in t.WINFLAG_CONFIGS:
+        for trial, c in enumerate(t.winflag_inputs(bs0, bs1, channels)):
+            rc, emit, want = t.overlap_ref_call(ref, "ref_overlap_add", bs0, bs1, channels, c)
+            assert rc == 0 and np.isfinite(want).all()
+            key = "winflags_%d_%d_%d_%d" % (bs0, bs1, channels, trial)
+            put(key + "_emit", emit)
+            put(key + "_pcm", t.bits(t.canonical_zero(want)))
+
     np.savez_compressed(t.REF_VECTORS, **out)
     print("wrote %s: %d entries, %d bytes" % (t.REF_VECTORS, len(out), os.path.getsize(t.REF_VECTORS)))
 

@@ -14,6 +14,17 @@ A stream the reference rejects (e.g. a floor curve that leaves the inverse-dB ta
 tried: every committed stream is one the reference decodes without error.
 
     python oracle/make_synth_ogg.py [count] [first_seed]
+
+With --winflags KIND the window flags of chosen long blocks are overridden instead of following the block sequence
+(a single stream, tests/golden/winflags_KIND.ogg / .npz, made by the same recipe):
+
+    python oracle/make_synth_ogg.py --winflags bcd [first_seed]   prev_long / next_long flipped at random on long blocks, so that
+                                                                  each of B (short, then long with prev_long set), C (long with
+                                                                  next_long clear, then long) and D (long, then long with prev_long
+                                                                  clear) occurs; never next_long set in front of a short block
+    python oracle/make_synth_ogg.py --winflags a [first_seed]     flags that agree, except ONE long block with next_long set in
+                                                                  front of a short block (class A: the reference accepts it, the
+                                                                  device refuses it with VSYN_ST_WINDOW_FLAGS)
 """
 import os
 import struct
@@ -514,7 +525,32 @@ def ogg_page(serial, seq, granule, packets, bos=False, eos=False):
     return bytes(page)
 
 
-def make_stream(seed):
+def window_flag_override(flags, rng, kind):
+    """-> (prev_long, next_long) per packet for --winflags KIND (see the module docstring), or None if the block sequence
+    cannot carry every class asked for"""
+    npk = len(flags)
+    prev = [flags[q - 1] if q else 1 for q in range(npk)]
+    nxt = [flags[q + 1] if q + 1 < npk else 1 for q in range(npk)]
+    if kind == "a":
+        at = [q for q in range(npk // 3, npk - 2) if flags[q] and not flags[q + 1]]
+        if not at:
+            return None
+        nxt[at[0]] = 1
+        return prev, nxt
+    cls = set()
+    for q in range(1, npk - 1):
+        if not flags[q]:
+            continue
+        if rng.random() < 0.5:
+            prev[q] ^= 1
+            cls.add("D" if flags[q - 1] else "B")
+        if flags[q + 1] and rng.random() < 0.5:
+            nxt[q] = 0
+            cls.add("C")
+    return (prev, nxt) if cls == {"B", "C", "D"} else None
+
+
+def make_stream(seed, winflags=None):
     rng = np.random.default_rng(seed)
     s = make_setup(rng)
     ident = b"\x01vorbis" + struct.pack("<IBIiiiB", 0, s.channels, s.rate, 0, 128000, 0, (ilog(s.bs0) - 1) | ((ilog(s.bs1) - 1) << 4)) + b"\x01"
@@ -522,14 +558,21 @@ def make_stream(seed):
     comment = b"\x03vorbis" + struct.pack("<I", len(vendor)) + vendor + struct.pack("<I", 1) + struct.pack("<I", 6) + b"SEED=%d" % (seed % 10) + b"\x01"
     comment = b"\x03vorbis" + struct.pack("<I", len(vendor)) + vendor + struct.pack("<I", 0) + b"\x01"
     setup = write_setup(s)
-    npk = int(os.environ.get("SYNTH_PACKETS", 0)) or int(rng.integers(8, 20))
+    npk = int(os.environ.get("SYNTH_PACKETS", 0)) or int(rng.integers(8, 20) if not winflags else rng.integers(24, 40))
     flags = [int(rng.random() < 0.55) for _ in range(npk)]
+    override = None
+    if winflags:
+        override = window_flag_override(flags, rng, winflags) if s.bs0 < s.bs1 else None
+        if override is None:
+            return None, s, npk
     pages = [ogg_page(77, 0, 0, [ident], bos=True), ogg_page(77, 1, 0, [comment, setup])]
     seq, pos, prev_n, batch = 2, 0, 0, []
     for q in range(npk):
         lng = flags[q]
         prev_long = flags[q - 1] if q else 1
         next_long = flags[q + 1] if q + 1 < npk else 1
+        if override:
+            prev_long, next_long = override[0][q], override[1][q]
         long_modes = [k for k, (bf, _) in enumerate(s.modes) if bf]
         mode = long_modes[int(rng.integers(0, len(long_modes)))] if lng else 0
         pkt = write_audio(s, rng, mode, prev_long, next_long)
@@ -546,6 +589,8 @@ def make_stream(seed):
             pages.append(ogg_page(77, seq, granule, batch, eos=last))
             seq += 1
             batch = []
+    if override:
+        s.win_flags = (np.asarray(flags, np.uint8), np.asarray(override[0], np.uint8), np.asarray(override[1], np.uint8))
     return b"".join(pages), s, npk
 
 
@@ -600,12 +645,22 @@ def reference_vectors(path):
 
 
 def main():
-    count = int(sys.argv[1]) if len(sys.argv) > 1 else 12
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    argv = sys.argv[1:]
+    winflags = None
+    if argv[:1] == ["--winflags"]:
+        winflags = argv[1]
+        assert winflags in ("a", "bcd"), winflags
+        argv = ["1"] + argv[2:]
+    count = int(argv[0]) if len(argv) > 0 else 12
+    seed = int(argv[1]) if len(argv) > 1 else 1
     made = 0
     while made < count:
-        data, s, npk = make_stream(seed)
-        path = os.path.join(OUT, "synth_%02d.ogg" % made)
+        data, s, npk = make_stream(seed, winflags)
+        if data is None:
+            print("seed %d skipped: the block sequence cannot carry --winflags %s" % (seed, winflags))
+            seed += 1
+            continue
+        path = os.path.join(OUT, ("winflags_%s.ogg" % winflags) if winflags else ("synth_%02d.ogg" % made))
         open(path, "wb").write(data)
         vec, why = reference_vectors(path)
         too_big = vec is not None and vec["pcm"].nbytes > int(os.environ.get("SYNTH_MAX_PCM_BYTES", "1000000000"))
@@ -624,9 +679,11 @@ def main():
             extra["floor%d_mult" % k] = np.int32(f.multiplier)
             extra["floor%d_xs" % k] = np.asarray(f.xs, np.int32)
         extra["num_floors"] = np.int32(len(s.floors))
-        np.savez_compressed(os.path.join(OUT, "synth_%02d.npz" % made), seed=np.int32(seed), **vec, **extra)
-        print("synth_%02d: seed %d, %d ch, blocks %d/%d, %d packets, %d frames, |pcm| <= %.3g, %d bytes"
-              % (made, seed, s.channels, s.bs0, s.bs1, npk, vec["pcm"].shape[1], float(np.abs(vec["pcm"]).max()), len(data)))
+        if winflags:  # per audio packet: block flag, and the window flags written into the packet
+            extra["block_long"], extra["win_prev"], extra["win_next"] = s.win_flags
+        np.savez_compressed(path[:-4] + ".npz", seed=np.int32(seed), **vec, **extra)
+        print("%s: seed %d, %d ch, blocks %d/%d, %d packets, %d frames, |pcm| <= %.3g, %d bytes"
+              % (os.path.basename(path)[:-4], seed, s.channels, s.bs0, s.bs1, npk, vec["pcm"].shape[1], float(np.abs(vec["pcm"]).max()), len(data)))
         made += 1
         seed += 1
 

@@ -70,6 +70,8 @@ def oracle():
         lib.orc_submit.argtypes = [vp, u32, vp, u32, vp, vp, vp, vp, u64, vp, C.POINTER(Taps), C.POINTER(Status)]
         lib.orc_pcm_interleave.argtypes = [C.c_int, u32, u32, vp, u64, vp]
         lib.orc_pcm_interleave.restype = None
+        lib.orc_overlap_add.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_uint64, vp,
+                                        C.POINTER(C.c_int)]
         lib.orc_residue_vq.argtypes = [C.POINTER(VqSetup), u32, u32, u32, u32, vp, C.c_size_t, vp, C.c_size_t, vp]
         _orc = lib
     return _orc

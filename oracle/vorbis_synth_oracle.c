@@ -401,6 +401,7 @@ typedef struct {
   uint32_t prev_win, cur_win;           /* hpp:986 */
   uint64_t abs_total_pos;               /* hpp:987 */
   int64_t expected_end;                 /* hpp:988 */
+  uint32_t tail; /* not upstream: the current block is long with its next_long flag set (orc_submit's VSYN_ST_WINDOW_FLAGS) */
 } orc_state;
 
 static void state_reset(orc_state* s, int channels) {
@@ -410,6 +411,7 @@ static void state_reset(orc_state* s, int channels) {
   s->prev_win = s->cur_win = 0;
   s->abs_total_pos = 0;
   s->expected_end = 0;
+  s->tail = 0;
 }
 
 /* hpp:1069-1109 */
@@ -473,6 +475,44 @@ static int64_t state_forward(orc_state* s, int channels, float* const* dst, uint
     s->abs_total_pos += frames;
   }
   return frames;
+}
+
+/* The decode state alone, with the signature of ref_overlap_add (oracle/ref_shim.cpp): blocks[p][c][n_p] (already IMDCT'ed) through
+ * state_begin_packet / state_add_frame / state_forward with the reference's buffer capacity (hpp:1354-1359), the window of each
+ * block picked from win_idx[p] = prev + 2*next alone (hpp:874-886), whatever the neighbouring block sizes. pcm [channels][cap]
+ * receives the forwarded frames in order. Returns 0, or 1 at packet *bad where the reference fails a CHECK. */
+int orc_overlap_add(int channels, int bs0, int bs1, int num_packets, const uint8_t* block_flag, const uint8_t* win_idx,
+                    const int64_t* granule, const float* blocks, float* pcm, uint64_t cap, uint32_t* emit_len, int* bad) {
+  orc_state st;
+  memset(&st, 0, sizeof(st));
+  st.cap = (uint32_t)bs0 * 5 + (uint32_t)bs1 * 5;
+  st.buf = (float**)malloc(sizeof(float*) * (size_t)channels);
+  for (int c = 0; c < channels; ++c) st.buf[c] = (float*)calloc(st.cap, sizeof(float));
+  float* win = (float*)malloc(sizeof(float) * (size_t)(bs0 > bs1 ? bs0 : bs1));
+  float* dst[VSYN_MAX_CHANNELS];
+  uint64_t written = 0;
+  size_t off = 0;
+  int rc = 0;
+  for (int p = 0; p < num_packets; ++p) {
+    const int lng = block_flag[p] ? 1 : 0;
+    const uint32_t n = (uint32_t)(lng ? bs1 : bs0);
+    orc_window(bs0, bs1, lng, win_idx[p] & 1, (win_idx[p] >> 1) & 1, win);
+    if (state_begin_packet(&st, channels, n)) { rc = 1; *bad = p; break; }
+    for (int c = 0; c < channels; ++c) {
+      state_add_frame(&st, c, blocks + off, win, n);
+      off += n;
+    }
+    st.expected_end = granule[p];
+    for (int c = 0; c < channels; ++c) dst[c] = pcm + (size_t)c * cap + written;
+    const int64_t frames = state_forward(&st, channels, dst, cap - written);
+    if (frames < 0) { rc = 1; *bad = p; break; }
+    emit_len[p] = (uint32_t)frames;
+    written += (uint64_t)frames;
+  }
+  for (int c = 0; c < channels; ++c) free(st.buf[c]);
+  free(st.buf);
+  free(win);
+  return rc;
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -603,7 +643,11 @@ int orc_submit(orc_handle* h, uint32_t num_packets, const vsyn_packet* packets, 
       const uint32_t n = h->bs[lng], n2 = n / 2;
       const int widx = lng ? ((pk->prev_long ? 1 : 0) | (pk->next_long ? 2 : 0)) : 0; /* hpp:874-886 */
       const float* window = h->win[lng][widx];
+      /* Not a reference CHECK: a block smaller than the long block in front of it whose next_long flag is set. The reference accepts it
+       * and keeps that window's right slope in its buffer past the smaller block; the device refuses it (VSYN_ST_WINDOW_FLAGS). */
+      if (st->tail && n < st->cur_win) { flag_status(status, VSYN_ST_WINDOW_FLAGS, p); break; }
       if (state_begin_packet(st, (int)C, n)) { flag_status(status, VSYN_ST_GRANULE, p); break; } /* hpp:1156 */
+      st->tail = (lng && pk->next_long) ? 1u : 0u;
 
       /* 4.3.2 floor curves, hpp:1159-1172 (floor_outputs is zero-initialised, n entries per channel) */
       uint32_t used = 0;

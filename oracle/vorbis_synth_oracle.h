@@ -45,6 +45,11 @@ void orc_imdct_closed_form(int n, const float* in, double* out);
 
 void orc_window(int blocksize0, int blocksize1, int block_flag, int prev, int next, float* out /* [blocksize] */);
 
+/* the overlap-add decode state alone, same signature and contract as ref_overlap_add (oracle/ref_shim.cpp) */
+int orc_overlap_add(int channels, int bs0, int bs1, int num_packets, const uint8_t* block_flag, const uint8_t* win_idx,
+                    const int64_t* granule, const float* blocks, float* pcm /* [channels][cap] */, uint64_t cap,
+                    uint32_t* emit_len, int* bad);
+
 /* ---- whole path, same batch contract as vsyn_submit_host ---- */
 typedef struct orc_handle orc_handle;
 orc_handle* orc_create(const vsyn_setup* setup, uint32_t max_streams);

@@ -16,6 +16,7 @@ VSYN_MAX_POSTS = 65
 VSYN_OK, VSYN_ERR_INVALID, VSYN_ERR_NO_DEVICE, VSYN_ERR_HIP, VSYN_ERR_STREAM = 0, 1, 2, 3, 4
 VSYN_ST_FLOOR_RANGE, VSYN_ST_FLOOR_VALUE, VSYN_ST_GRANULE, VSYN_ST_PLANE_OVERFLOW, VSYN_ST_BAD_MODE = 1, 2, 4, 8, 16
 VSYN_ST_BAD_SEGMENT, VSYN_ST_BAD_VQ = 32, 64
+VSYN_ST_WINDOW_FLAGS = 128  # accepted by the reference, refused by the device (include/vorbis_synth_hip.h)
 VSYN_SEG_RESET = 1
 VSYN_SUBMIT_STAGED = 1
 VSYN_SUBMIT_INPUTS_READY = 2

@@ -76,6 +76,7 @@ struct StreamState {              // VorbisStreamDecodeState (hpp:975-1115) redu
   uint64_t abs_total_pos;
   uint32_t has_prev, prev_n, parity;
   uint32_t tag;                   // submit number that wrote the record (0: never written)
+  uint32_t prev_tail;             // the last block is long with its next_long flag set (VSYN_ST_WINDOW_FLAGS on a smaller block behind it)
 };
 // Two records per stream slot. A submit READS the newer record written by an earlier submit and WRITES the other one, tagged with its
 // own number: every wave of a submit — whenever it starts, the segment's last wave may long have finished — finds the state the

@@ -327,9 +327,9 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
   extern __shared__ __attribute__((aligned(16))) uint32_t s_rows[];  // [posts of the longest floor, rounded up to 4][PREP_THREADS]: prep_unwrap_rows
   __shared__ AbsScan s_abs[PREP_WAVES];
   __shared__ uint64_t s_res[PREP_WAVES];
-  __shared__ uint32_t s_pk[PREP_THREADS];      // block size of each packet of the pass (a packet needs its predecessor's)
+  __shared__ uint32_t s_pk[PREP_THREADS];      // block size of each packet of the pass | prev_tail_of << 31 (a packet needs its predecessor's)
   __shared__ uint32_t s_longbits[PREP_MAX_SEG_PACKETS / 32 + 2];  // bit 0: the packet in front of the chunk, bit 1 + i: packet cs + i — set = a valid long block
-  __shared__ uint32_t s_last_n;
+  __shared__ uint32_t s_last_n;               // the pass's last block size | its prev_tail_of << 31
   const uint8_t* __restrict__ cb = A.cb;
   const ConstHeader* H = hdr_of(cb);
   const uint32_t t = threadIdx.x, lane = t & 63u, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -459,6 +459,7 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
   AbsScan cin = {0, 0};
   uint64_t cres = 0;
   uint32_t prev_n_in = carry_n;
+  uint32_t prev_tail_in = carry_n ? st0.prev_tail : 0u;  // the block in front is long with next_long set (pkt_step_core)
   bool halo_long = !carry_n;  // the block in front of the chunk is a valid long one (or there is none at all)
   if (cs > 0u) {
     const uint32_t per = (cs + NT - 1u) / NT;
@@ -491,6 +492,7 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
     const uint32_t hm = __builtin_amdgcn_readfirstlane((uint32_t)spk[cs - 1u].mode);
     prev_n_in = PREP_N_OF_MODE(hm);
     halo_long = PREP_IS_LONG(hm);
+    prev_tail_in = prev_tail_of(PREP_IS_LONG(hm), (uint8_t)__builtin_amdgcn_readfirstlane((uint32_t)spk[cs - 1u].next_long));
   }
   PSTAMP(1);  // scan in front of the chunk
 
@@ -523,9 +525,11 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
     const uint32_t n = lng ? bs1 : bs0;
     // block size in front of each packet: the previous thread's (across the wave boundary through LDS)
     __syncthreads();  // s_pk of the previous pass is no longer read
-    s_pk[t] = n;
+    const uint32_t tail = prev_tail_of(mode_ok && lng, k.next_long);
+    s_pk[t] = n | (tail << 31);
     __syncthreads();
-    const uint32_t prev_n = t == 0u ? prev_n_in : s_pk[t - 1u];
+    const uint32_t prev_n = t == 0u ? prev_n_in : (s_pk[t - 1u] & 0x7FFFFFFFu);
+    const uint32_t prev_tail = t == 0u ? prev_tail_in : (s_pk[t - 1u] >> 31);
     AbsScan inc = {0, 0};
     uint64_t rinc = 0;
     if (valid) {
@@ -586,9 +590,10 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
       }
     }
     if (valid) {
-      const PktStep ps = pkt_step_core(k, mode_ok, lng, mapping, n, prev_n, abs_before, abs0, res_off, A.plane_stride, own, used);
+      const PktStep ps = pkt_step_core(k, mode_ok, lng, mapping, n, prev_n, prev_tail, abs_before, abs0, res_off, A.plane_stride, own, used);
       if (ps.raise) {
         if (ps.raise & VSYN_ST_BAD_MODE) raise_status(A.status, VSYN_ST_BAD_MODE, p);
+        if (ps.raise & VSYN_ST_WINDOW_FLAGS) raise_status(A.status, VSYN_ST_WINDOW_FLAGS, p);
         if (ps.raise & VSYN_ST_GRANULE) raise_status(A.status, VSYN_ST_GRANULE, p);
         if (ps.raise & VSYN_ST_PLANE_OVERFLOW) raise_status(A.status, VSYN_ST_PLANE_OVERFLOW, p);
       }
@@ -602,19 +607,21 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
         ns.abs_total_pos = (uint64_t)ps.abs_after;
         ns.has_prev = 1;
         ns.prev_n = n;
+        ns.prev_tail = tail;
         ns.parity = si.parity_in ^ 1u;
         ns.tag = 0;
         state_write(A.state, sg.stream, st_slot, ns, A.epoch);
       }
       if (mode_ok && lng) atomicOr(&s_longbits[(q - cs + 1u) >> 5], 1u << ((q - cs + 1u) & 31u));
-      if (q == pe - 1u) s_last_n = n;
+      if (q == pe - 1u) s_last_n = n | (tail << 31);
     }
     __syncthreads();  // s_last_n is in place; everyone has read its predecessor's block size
     PSTAMP(2);  // descriptors, block scan, PktInfo
     // carry the scan into the next pass (s_last_n was written before the barriers above)
     cin = abs_combine(cin, tot);
     cres += rtot;
-    prev_n_in = s_last_n;
+    prev_n_in = s_last_n & 0x7FFFFFFFu;
+    prev_tail_in = s_last_n >> 31;
   }
   // ---- 4. which kernel takes each run of the chunk (vsyn_staged.h, run_class): 1 = every packet the run touches, its one-packet halo
   //         included, is a valid long block and there is no carry-in of another size; 2 = anything else a fused kernel covers ----------

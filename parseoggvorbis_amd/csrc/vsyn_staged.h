@@ -76,8 +76,13 @@ struct PktStep {
   uint32_t raise;  // VSYN_ST_* to raise for this packet (0: none)
 };
 // (own / used: floor_output_used before and after the nonzero propagate of hpp:1174-1180, see coupling_propagate)
+// prev_tail: the block in front is long and its next_long flag is set (prev_tail_of). A smaller block behind it is the one window-flag
+// disagreement whose reference result the two-term overlap cannot give (VSYN_ST_WINDOW_FLAGS): raised and skipped like a granule error.
+// Like VSYN_ST_BAD_MODE, the later checks of the packet (and the later packets of the segment) still run, so the flag word can hold
+// more bits than the oracle's, which stops at the first; the status code and first_bad_packet are the same.
 __device__ __forceinline__ PktStep pkt_step_core(const vsyn_packet& k, bool mode_ok, uint32_t lng, uint32_t mapping, uint32_t n, uint32_t prev_n,
-                                                 int64_t abs_before, int64_t abs0, uint64_t res_off, uint64_t plane_stride, uint32_t own, uint32_t used) {
+                                                 uint32_t prev_tail, int64_t abs_before, int64_t abs0, uint64_t res_off, uint64_t plane_stride,
+                                                 uint32_t own, uint32_t used) {
   PktStep r;
   PktInfo pi = {};
   r.raise = mode_ok ? 0u : (uint32_t)VSYN_ST_BAD_MODE;
@@ -85,6 +90,10 @@ __device__ __forceinline__ PktStep pkt_step_core(const vsyn_packet& k, bool mode
   int64_t abs_after = abs_before + L;
   uint32_t emit = L;
   bool bad = !mode_ok;
+  if (mode_ok && prev_tail && n < prev_n) {
+    r.raise |= VSYN_ST_WINDOW_FLAGS;
+    bad = true;
+  }
   if (k.granule >= 0) {
     // hpp:1029 (position already past the page granule) and hpp:1041 (packets cannot reach it)
     if (k.granule < abs_before || k.granule > abs_before + (int64_t)L) {
@@ -102,6 +111,7 @@ __device__ __forceinline__ PktStep pkt_step_core(const vsyn_packet& k, bool mode
     if (emit) bad = true;
     emit = 0;
   }
+  if (r.raise & VSYN_ST_WINDOW_FLAGS) emit = 0;
   pi.res_off = res_off;
   pi.out_pos = rel < 0 ? 0u : (uint32_t)rel;
   pi.emit = emit;
@@ -116,8 +126,11 @@ __device__ __forceinline__ PktStep pkt_step_core(const vsyn_packet& k, bool mode
   r.abs_after = abs_after;
   return r;
 }
+// the prev_tail of the block behind a packet: the packet is a valid long block whose next_long byte is non-zero (any non-zero byte is
+// true, as in the reference's getWindow(bool, bool))
+__device__ __forceinline__ uint32_t prev_tail_of(bool is_long, uint8_t next_long) { return (is_long && next_long) ? 1u : 0u; }
 __device__ __forceinline__ PktStep pkt_step(const MapConst* __restrict__ maps, const vsyn_packet& k, bool mode_ok, uint32_t lng, uint32_t mapping,
-                                            uint32_t n, uint32_t prev_n, int64_t abs_before, int64_t abs0, uint64_t res_off,
+                                            uint32_t n, uint32_t prev_n, uint32_t prev_tail, int64_t abs_before, int64_t abs0, uint64_t res_off,
                                             uint64_t plane_stride, uint32_t C) {
   const uint32_t chan_mask = C >= 32 ? 0xFFFFFFFFu : ((1u << C) - 1u);
   uint32_t own = k.floor_used & chan_mask, used = own;
@@ -126,7 +139,7 @@ __device__ __forceinline__ PktStep pkt_step(const MapConst* __restrict__ maps, c
     uint32_t m = mc->coup[2 * i], a = mc->coup[2 * i + 1];
     if (((used >> m) | (used >> a)) & 1u) used |= (1u << m) | (1u << a);
   }
-  return pkt_step_core(k, mode_ok, lng, mapping, n, prev_n, abs_before, abs0, res_off, plane_stride, own, used);
+  return pkt_step_core(k, mode_ok, lng, mapping, n, prev_n, prev_tail, abs_before, abs0, res_off, plane_stride, own, used);
 }
 
 // A segment is scanned in CHUNKS of chunk_packets packets (a multiple of the run length R, so that a run never straddles two
@@ -205,7 +218,7 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
   uint32_t* s_longbits = (uint32_t*)(s_dyn + (size_t)NT * (sizeof(AbsScan) + sizeof(uint64_t)));
   for (uint32_t w = t; w < (cn + 1u + 31u) / 32u; w += NT) s_longbits[w] = 0u;
   __shared__ int64_t s_abs_end;
-  __shared__ uint32_t s_last_n;
+  __shared__ uint32_t s_last_n, s_last_tail;
   __shared__ AbsScan s_chunk_ex;   // exclusive prefix of this chunk (everything before it in the segment)
   __shared__ uint64_t s_chunk_rex;
   __shared__ uint32_t s_chunk_lost;
@@ -227,7 +240,11 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
   vsyn_packet kq[KEEP];
   const uint32_t num_modes = H->num_modes, bs0 = H->bs[0], bs1 = H->bs[1];
   uint32_t carry_prev_mode = 0xFFFFFFFFu;  // mode of the packet before this thread's first one (for the block size in front of it)
-  if (cs + qb > 0 && qb < cn) carry_prev_mode = spk[cs + qb - 1].mode;
+  uint8_t carry_prev_next = 0;             // and its next_long byte
+  if (cs + qb > 0 && qb < cn) {
+    carry_prev_mode = spk[cs + qb - 1].mode;
+    carry_prev_next = spk[cs + qb - 1].next_long;
+  }
   __syncthreads();
   auto n_of_mode = [&](uint32_t m) -> uint32_t { return (m < num_modes && s_bf[m]) ? bs1 : bs0; };
   if (t == 0 && cs > 0) {  // the halo bit of the chunk's first run
@@ -235,6 +252,8 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
     if (m < num_modes && s_bf[m]) atomicOr(&s_longbits[0], 1u);
   }
   const uint32_t prev_n0 = cs + qb == 0 ? carry_n : (qb < cn ? n_of_mode(carry_prev_mode) : 0);
+  const uint32_t prev_tail0 = cs + qb == 0 ? (carry_n ? st0.prev_tail : 0u)
+                                           : (qb < cn ? prev_tail_of(carry_prev_mode < num_modes && s_bf[carry_prev_mode], carry_prev_next) : 0u);
 
   // pass A: per-thread aggregate
   AbsScan agg = {0, 0};
@@ -386,16 +405,18 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
     AbsScan pre = abs_combine(s_chunk_ex, s_abs[t]);
     int64_t abs_before = pre.set ? pre.val : abs0 + pre.val;
     uint64_t res_off = sg.residue_off + s_chunk_rex + s_res[t];
-    uint32_t prev_n = prev_n0;
+    uint32_t prev_n = prev_n0, prev_tail = prev_tail0;
     auto step_b = [&](uint32_t ql, const vsyn_packet& k) {  // ql: index inside the chunk
       const uint32_t q = cs + ql;
       const uint32_t p = sg.first_packet + q;
       const bool mode_ok = k.mode < num_modes;
       const uint32_t lng = mode_ok && s_bf[k.mode] ? 1u : 0u;
       const uint32_t n = lng ? bs1 : bs0;
-      const PktStep ps = pkt_step(map_of(cb, 0), k, mode_ok, lng, mode_ok ? s_mm[k.mode] : 0u, n, prev_n, abs_before, abs0, res_off, plane_stride, C);
+      const PktStep ps = pkt_step(map_of(cb, 0), k, mode_ok, lng, mode_ok ? s_mm[k.mode] : 0u, n, prev_n, prev_tail, abs_before, abs0, res_off,
+                                  plane_stride, C);
       // (one flag at a time, in the order the checks are made: first_bad_packet is a minimum over packets, the flags an OR)
       if (ps.raise & VSYN_ST_BAD_MODE) raise_status(status, VSYN_ST_BAD_MODE, p);
+      if (ps.raise & VSYN_ST_WINDOW_FLAGS) raise_status(status, VSYN_ST_WINDOW_FLAGS, p);
       if (ps.raise & VSYN_ST_GRANULE) raise_status(status, VSYN_ST_GRANULE, p);
       if (ps.raise & VSYN_ST_PLANE_OVERFLOW) raise_status(status, VSYN_ST_PLANE_OVERFLOW, p);
       info[p] = ps.pi;
@@ -405,10 +426,12 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
       if (q == num - 1) {
         s_abs_end = ps.abs_after;
         s_last_n = n;
+        s_last_tail = prev_tail_of(mode_ok && lng, k.next_long);
       }
       abs_before = ps.abs_after;
       res_off += (uint64_t)C * (n / 2);
       prev_n = n;
+      prev_tail = prev_tail_of(mode_ok && lng, k.next_long);
     };
     for (uint32_t base = qb; base < qe; base += KEEP) {
       if (!keep) {
@@ -459,6 +482,7 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
     ns.abs_total_pos = (uint64_t)s_abs_end;
     ns.has_prev = 1;
     ns.prev_n = s_last_n;
+    ns.prev_tail = s_last_tail;
     ns.parity = si.parity_in ^ 1u;
     ns.tag = 0;
     state_write(state, sg.stream, st_slot, ns, epoch);

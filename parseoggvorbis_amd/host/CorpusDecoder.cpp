@@ -210,6 +210,9 @@ std::string gpu_status_text(const vsyn_status& st) {
   if (st.flags & VSYN_ST_PLANE_OVERFLOW) s += " plane-overflow";
   if (st.flags & VSYN_ST_BAD_MODE) s += " bad-mode";
   if (st.flags & VSYN_ST_BAD_SEGMENT) s += " bad-segment";
+  if (st.flags & VSYN_ST_BAD_VQ) s += " bad-vq";
+  // accepted by the reference, refused here: a long block's next_long flag set in front of a short block
+  if (st.flags & VSYN_ST_WINDOW_FLAGS) s += " window-flags: next_long set on a long block before a short one";
   return s + ")";
 }
 

@@ -2,6 +2,10 @@
 // the synthesis half is batched onto the MI355X through include/vorbis_synth_hip.h.  See ParseOggVorbis.hpp.
 // Written from the Vorbis I specification (section numbers cited); behaviour on the public surface follows the
 // reference decoder (file:line cited where a reference convention is mirrored on purpose).
+// One deliberate divergence: a long block whose next_long window flag is set, followed by a short block. The reference accepts
+// it (rc 0) and leaves the long window's right slope, n/4 - s/4 samples past the short block, in its sliding buffer, where later
+// packets add to it depending on when the buffer slides; this decoder fails the read there instead (VSYN_ST_WINDOW_FLAGS,
+// DESIGN.md §7). Every other combination of window flags and block sizes decodes as the reference does.
 #include "ParseOggVorbis.hpp"
 
 #include <math.h>
@@ -1090,6 +1094,8 @@ static std::string status_text(const vsyn_status& st) {
   if (st.flags & VSYN_ST_BAD_MODE) s += " bad mode";
   if (st.flags & VSYN_ST_BAD_SEGMENT) s += " bad segment";
   if (st.flags & VSYN_ST_BAD_VQ) s += " residue entry / classification number out of range";
+  // (accepted by the reference, which keeps a long window's right slope past the smaller block: a deliberate divergence)
+  if (st.flags & VSYN_ST_WINDOW_FLAGS) s += " window flags disagree with the block sizes (next_long set on a long block before a short one)";
   return s;
 }
 

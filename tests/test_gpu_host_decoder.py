@@ -250,10 +250,11 @@ def test_synthetic_streams_pcm_matches_reference(vq, monkeypatch):
     monkeypatch.setenv("PARSEOGGVORBIS_VQ", vq)
     names = sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("synth_") and f.endswith(".ogg"))
     assert len(names) >= 16
+    names.append("winflags_bcd")  # window flags that disagree with the blocks around them (classes B, C, D)
     gold = [np.load(os.path.join(GOLDEN, n + ".npz")) for n in names]
     blobs = [open(os.path.join(GOLDEN, n + ".ogg"), "rb").read() for n in names]
     chans = [int(z["channels"]) for z in gold]
-    frames, sums, ok, pcm, stats = _run_corpus(blobs, chans, threads=3, feeders=2, files_per_submit=5, cap=16384)
+    frames, sums, ok, pcm, stats = _run_corpus(blobs, chans, threads=3, feeders=2, files_per_submit=5, cap=32768)  # winflags_bcd: 19037 frames
     for i, z in enumerate(gold):
         want = z["pcm"]
         assert ok[i], names[i]
@@ -267,7 +268,7 @@ def _synth_names():
     return sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("synth_") and f.endswith(".ogg"))
 
 
-@pytest.mark.parametrize("name", _synth_names())
+@pytest.mark.parametrize("name", _synth_names() + ["winflags_bcd"])
 def test_cli_dump_matches_reference_on_synthetic_streams(name, tmp_path):
     """ours_hip.bin --debug_out on the synthetic streams: the SAME hook stream as the reference decoder's — every entry name,
     channel and length in the same order (what tests/compare-debug-out.py of the reference walks, 154-198 / 380-401), integer
@@ -352,3 +353,38 @@ def test_error_in_mid_stream_still_delivers_the_packets_before_it(vq, tmp_path):
         got = np.concatenate([np.atleast_1d(v) for v in pcm[c]]) if len(pcm[c]) else np.zeros(0, np.float32)
         assert got.shape[0] == want
         assert np.abs(got - b["pcm"][c, :want]).max() < TOL
+
+
+def test_window_flag_tail_file_is_refused_by_name(tmp_path):
+    """tests/golden/winflags_a.ogg: one long block with next_long set in front of a short block — a file the reference decodes (rc 0)
+    with PCM the device cannot reproduce. ours_hip.bin fails the read and names the condition; the corpus decoder
+    fails that one file, names the condition too, and the other files of the same submit (same setup: winflags_bcd, the B/C/D
+    stream) still decode to the reference's PCM."""
+    import json
+    from tests.test_host_decoder import CORPUS_CLI
+    a = os.path.join(GOLDEN, "winflags_a.ogg")
+    r = subprocess.run(["timeout", "-k", "10", "120", CLI, "--in", a], capture_output=True, text=True)
+    assert r.returncode not in (0, 124, 137) and r.returncode > 0, (r.returncode, r.stderr[-400:])
+    assert "window flags disagree" in r.stdout + r.stderr, (r.stdout[-400:], r.stderr[-400:])
+    names = ["winflags_bcd", "winflags_a", "winflags_bcd", "winflags_bcd"]
+    gold = {n: np.load(os.path.join(GOLDEN, n + ".npz")) for n in set(names)}
+    assert all(gold["winflags_a"][k].tobytes() == gold["winflags_bcd"][k].tobytes() for k in ("blocksize0", "blocksize1", "channels"))
+    blobs = [open(os.path.join(GOLDEN, n + ".ogg"), "rb").read() for n in names]
+    frames, sums, ok, pcm, stats = _run_corpus(blobs, [int(gold[n]["channels"]) for n in names], threads=2, feeders=1,
+                                               files_per_submit=4, cap=32768)
+    assert stats[5] >= 1
+    for i, n in enumerate(names):
+        if n == "winflags_a":
+            assert ok[i] == 0
+            continue
+        want = gold[n]["pcm"]
+        assert ok[i] == 1 and frames[i] == want.shape[1], (i, frames[i])
+        assert np.abs(pcm[i][:, :frames[i]] - want).max() <= 4e-6 * max(1.0, float(np.abs(want).max())), i
+    r = subprocess.run(["timeout", "-k", "10", "120", CORPUS_CLI, "--threads", "2", "--files_per_submit", "4",
+                        os.path.join(GOLDEN, "winflags_bcd.ogg"), a, os.path.join(GOLDEN, "winflags_bcd.ogg")],
+                       capture_output=True, text=True)
+    assert r.returncode in (0, 1), (r.returncode, r.stderr[-800:])
+    assert "file 1 (%s)" % a in r.stderr and "window-flags" in r.stderr, r.stderr[-800:]
+    assert "file 0" not in r.stderr and "file 2" not in r.stderr, r.stderr[-800:]
+    out = json.loads(r.stdout)
+    assert (out["files"], out["failed"]) == (3, 1), out

@@ -9,7 +9,7 @@ import pytest
 from oracle import oracle_binding as ob
 from parseoggvorbis_amd import binding
 from parseoggvorbis_amd.binding import SetupSpec
-from tests.workloads import fixture_like_spec, load_golden, synth_batch
+from tests.workloads import disagreeing_window_flags, fixture_like_spec, load_golden, synth_batch, window_flag_classes
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -700,3 +700,195 @@ def test_preparation_kernel_geometries(run_len, C, monkeypatch):
     assert np.array_equal(pre["emit_len"], got["emit_len"])
     assert np.array_equal(pre["taps"]["floor_final"], got["taps"]["floor_final"])
     assert np.array_equal(bits(pre["pcm"]), bits(got["pcm"]))
+
+
+# ---- window flags that disagree with the block sequence (tests/workloads.py window_flag_classes: classes A-D) ----
+
+WINFLAG_SHAPES = [  # C, bs0, bs1, pattern, streams, packets per stream, run length (0: the library's choice), vsyn_fused_paths & 2
+    (2, 256, 2048, "mixed", 3, 60, 4, 2),
+    (2, 256, 2048, "long", 2, 40, 5, 2),     # all long: the tuned kernel's register-set path; only C and D can occur
+    (2, 128, 1024, "mixed", 2, 50, 4, 2),
+    (1, 512, 4096, "mixed", 2, 40, 0, 2),
+    (1, 64, 8192, "mixed", 1, 40, 4, 2),
+    (2, 1024, 2048, "mixed", 2, 40, 0, 2),
+    (2, 4096, 8192, "mixed", 1, 24, 0, 0),   # staged kernels
+    (2, 1024, 1024, "mixed", 2, 30, 4, 2),   # equal block sizes with the class-A pattern: nothing to refuse
+]
+
+
+def _winflag_blocks(rng, pattern, npk):
+    if pattern == "long":
+        return np.ones(npk, np.uint8)
+    blk = np.ones(npk, np.uint8)
+    q = 1
+    while q < npk:  # stretches: long 1..4, short 1..5
+        k = int(rng.integers(1, 6))
+        blk[q:q + k] = 0
+        q += k + int(rng.integers(1, 5))
+    return blk
+
+
+def _cut_submits(gpu, spec, b, npk, cuts, flags):
+    """stream 0 of batch b, submitted in pieces [cuts[i], cuts[i+1]) on stream slot 1 of gpu -> (pcm of the pieces concatenated, emit_len)"""
+    C = spec.channels
+    n_of = np.where(b["packets"]["mode"][:npk] == 1, spec.blocksize1, spec.blocksize0)
+    off = np.concatenate([[0], np.cumsum(C * (n_of // 2))])
+    parts, emits = [], []
+    for a, e in zip(cuts[:-1], cuts[1:]):
+        seg = b["segments"][:1].copy()
+        seg["stream"], seg["first_packet"], seg["num_packets"], seg["flags"], seg["residue_off"] = 1, 0, e - a, 1 if a == 0 else 0, 0
+        r = gpu.submit_host(b["packets"][a:e], seg, b["ys"][a:e], b["residue"][off[a]:off[e]], b["plane_stride"], flags=flags)
+        assert r["rc"] == 0, (a, e, r["flags"], r["first_bad"])
+        emits.append(r["emit_len"])
+        parts.append(r["pcm"][0][:, :int(r["emit_len"].sum())])
+    return np.concatenate(parts, axis=1), np.concatenate(emits)
+
+
+@pytest.mark.parametrize("flags", PATHS + [HIDDEN_PRE])
+@pytest.mark.parametrize("C,bs0,bs1,pattern,streams,npk,run_len,paths", WINFLAG_SHAPES)
+def test_window_flags_that_disagree_stay_exact(C, bs0, bs1, pattern, streams, npk, run_len, paths, flags, monkeypatch):
+    """Window flag bytes drawn at random (0, 1, 2, 0x80, 255) for every packet, short ones included, instead of from the blocks
+    around it: classes B, C and D occur (A too where the block sizes are equal), on a run's halo packet and on its first packet, and
+    on the last packet of one submit and the first of the next. The reference picks windows from the flags alone; so must every
+    kernel, its run halo and the carry across submits. One submit == oracle; the same stream cut into submits == uncut, bit for bit."""
+    if run_len:
+        monkeypatch.setenv("VSYN_RUN_LEN", str(run_len))
+    rng = np.random.default_rng(bs0 * 3 + bs1 + C + npk)
+    spec = fixture_like_spec(C, bs0, bs1)
+    blk = _winflag_blocks(rng, pattern, npk)
+    prev, nxt = [], []
+    for s in range(streams):
+        p, x = disagreeing_window_flags(rng, blk, bs0, bs1, allow_a=bs0 == bs1)
+        prev.append(p)
+        nxt.append(x)
+    prev, nxt = np.concatenate(prev), np.concatenate(nxt)
+    cl = window_flag_classes(blk, prev[:npk], nxt[:npk])
+    assert bool(cl["A"]) == (bs0 == bs1 and pattern == "mixed"), cl
+    assert cl["C"] and cl["D"] and (cl["B"] or pattern == "long"), cl
+    if pattern != "long":  # short blocks carry flags, to be ignored
+        assert set(prev[:npk][blk == 0]) - {0} and set(nxt[:npk][blk == 0]) - {0}
+    bad = sorted(set(cl["A"] + cl["B"] + cl["C"] + cl["D"]))
+    if run_len:  # disagreeing flags on a run's first packet and on its halo (the packet in front, recomputed by the run)
+        assert any(q % run_len == 0 and q for q in bad) and any(q % run_len == run_len - 1 for q in bad), (bad, run_len)
+    b = synth_batch(spec, streams, npk, blk, seed=bs1 + C, unused_frac=0.1, granule_last=True, prev_long=prev, next_long=nxt)
+    want = ob.OracleSynth(spec, streams).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
+    gpu = binding.Synth(spec, max_streams=max(2, streams))
+    print("%dx %d/%d %s: fused paths %d, flags %d, disagreeing packets %s" % (C, bs0, bs1, pattern, gpu.fused_paths, flags,
+                                                                            {k: len(v) for k, v in cl.items()}))
+    assert (gpu.fused_paths & 2) == paths, gpu.fused_paths
+    one = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=flags)
+    check(one, want)
+    d1, d2 = bad[len(bad) // 3], bad[2 * len(bad) // 3]
+    cuts = sorted(set([0, npk, d1 + 1, d2] + [int(c) for c in rng.integers(1, npk, 3)]))
+    gpu.reset()
+    got, emit = _cut_submits(gpu, spec, b, npk, cuts, flags)
+    assert np.array_equal(emit, one["emit_len"][:npk])
+    total = int(one["emit_len"][:npk].sum())
+    assert np.array_equal(bits(got), bits(one["pcm"][0][:, :total]))
+
+
+def _tail_batch(spec, npk, streams, a_at, seed):
+    """streams x npk packets, mixed blocks, window flags from disagreeing_window_flags (no class A), then class A forced in stream 0
+    at each packet of a_at (that packet short, the one in front long with next_long set)"""
+    rng = np.random.default_rng(seed)
+    blk = _winflag_blocks(rng, "mixed", npk)
+    for q in a_at:
+        blk[q - 1], blk[q] = 1, 0
+    prev, nxt = [], []
+    for s in range(streams):
+        p, x = disagreeing_window_flags(rng, blk, spec.blocksize0, spec.blocksize1)
+        prev.append(p)
+        nxt.append(x)
+    prev, nxt = np.concatenate(prev), np.concatenate(nxt)
+    for q in a_at:
+        nxt[q - 1] = (1, 2, 0x80, 255)[q % 4]
+    b = synth_batch(spec, streams, npk, blk, seed=seed, unused_frac=0.1, prev_long=prev, next_long=nxt)
+    assert window_flag_classes(blk, prev[:npk], nxt[:npk])["A"] == [q - 1 for q in a_at]  # (A names the long block)
+    return b
+
+
+def _assert_refused(r, w, first_bad):
+    # (the device goes on checking the refused packet and the rest of its segment, the oracle stops there: the flag words are equal
+    # here because these batches carry no page granules and no other fault; rc and first_bad agree in any case)
+    assert r["rc"] == w["rc"] == binding.VSYN_ERR_STREAM, (r["rc"], w["rc"])
+    assert r["flags"] == w["flags"] == binding.VSYN_ST_WINDOW_FLAGS, (r["flags"], w["flags"])
+    assert r["first_bad"] == w["first_bad"] == first_bad, (r["first_bad"], w["first_bad"])
+
+
+def _assert_segments_match(r, w, b, segs):
+    for g in segs:
+        sg = b["segments"][g]
+        sl = slice(int(sg["first_packet"]), int(sg["first_packet"] + sg["num_packets"]))
+        assert np.array_equal(r["emit_len"][sl], w["emit_len"][sl]), g
+        assert np.abs(r["pcm"][g] - w["pcm"][g]).max() < TOL * max(1.0, float(np.abs(w["pcm"][g]).max())), g
+
+
+@pytest.mark.parametrize("flags", PATHS + [HIDDEN_PRE])
+def test_window_flag_tail_is_refused(flags):
+    """Class A — a long block with next_long set (bytes 1, 2, 0x80, 255), then a short block — which the reference accepts with PCM
+    the two-term overlap cannot give (tests/test_oracle_vs_ref.py): device and oracle both refuse it with VSYN_ST_WINDOW_FLAGS at the
+    same packet, (1) in the middle of a segment, (2) on packet 0 of a submit whose previous submit ended on the long block, (3) past
+    the first chunk of a segment longer than the layout chunk (4096 packets), (4) on the first packet of the preparation kernel's
+    second pass over a chunk (PREP_THREADS / channels packets per pass: 128 in stereo, 256 in mono; the long block in front lies in the
+    first pass). The other segments of the batch still match the oracle, and after reset() the handle is exact again."""
+    spec = fixture_like_spec(2)
+    npk, S = 48, 3
+    # (1) mid-segment, stream 0; streams 1 and 2 carry disagreeing flags of classes B-D only
+    b = _tail_batch(spec, npk, S, [23], seed=71)
+    gpu = binding.Synth(spec, max_streams=S)
+    print("2x 256/2048: fused paths %d, flags %d" % (gpu.fused_paths, flags))
+    r = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=flags)
+    w = ob.OracleSynth(spec, S).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
+    _assert_refused(r, w, 23)
+    _assert_segments_match(r, w, b, [1, 2])
+    # after reset(): exact again on a clean batch (the same streams without the class-A packet's flag)
+    clean = b["packets"].copy()
+    clean["next_long"][22] = 0
+    gpu.reset()
+    check(gpu.submit_host(clean, b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=flags),
+          ob.OracleSynth(spec, S).submit_host(clean, b["segments"], b["ys"], b["residue"], b["plane_stride"]))
+
+    # (2) across submits: the first submit ends on the long block (accepted), the next one starts with the short block
+    b = _tail_batch(spec, npk, 1, [30], seed=72)
+    C = spec.channels
+    n_of = np.where(b["packets"]["mode"] == 1, spec.blocksize1, spec.blocksize0)
+    off = np.concatenate([[0], np.cumsum(C * (n_of // 2))])
+    gpu.reset()
+    orc = ob.OracleSynth(spec, S)
+    for a, e, want_bad in ((0, 30, None), (30, npk, 0)):
+        seg = b["segments"][:1].copy()
+        seg["stream"], seg["first_packet"], seg["num_packets"], seg["flags"], seg["residue_off"] = 2, 0, e - a, 1 if a == 0 else 0, 0
+        args = (b["packets"][a:e], seg, b["ys"][a:e], b["residue"][off[a]:off[e]], b["plane_stride"])
+        r = gpu.submit_host(*args, flags=flags)
+        w = orc.submit_host(*args)
+        if want_bad is None:
+            check(r, w)
+        else:
+            _assert_refused(r, w, want_bad)
+    gpu.reset()
+
+    # (3) a segment of 4700 packets (layout kernel, two chunks of 4096) with the class-A packet on the second chunk's first packet
+    #     (the long block in front of it lies in the first chunk), beside a clean one
+    big, at = 4700, 4096
+    b = _tail_batch(spec, big, 2, [at], seed=73)
+    gpu2 = binding.Synth(spec, max_streams=2)
+    r = gpu2.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=flags)
+    w = ob.OracleSynth(spec, 2).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
+    _assert_refused(r, w, at)
+    _assert_segments_match(r, w, b, [1])
+    gpu2.reset()
+    clean = b["packets"].copy()
+    clean["next_long"][at - 1] = 0
+    check(gpu2.submit_host(clean, b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=flags),
+          ob.OracleSynth(spec, 2).submit_host(clean, b["segments"], b["ys"], b["residue"], b["plane_stride"]))
+
+    # (4) the preparation kernel's pass boundary: the tail bit crosses from one pass to the next in LDS
+    for C, at in ((2, 128), (1, 256)):
+        sp = fixture_like_spec(C)
+        b = _tail_batch(sp, 300, 2, [at], seed=74 + C)
+        g = binding.Synth(sp, max_streams=2)
+        print("%dx 256/2048, class A at %d: fused paths %d, flags %d" % (C, at, g.fused_paths, flags))
+        r = g.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=flags)
+        w = ob.OracleSynth(sp, 2).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
+        _assert_refused(r, w, at)
+        _assert_segments_match(r, w, b, [1])

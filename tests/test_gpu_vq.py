@@ -11,7 +11,8 @@ import pytest
 from oracle import oracle_binding as ob
 from parseoggvorbis_amd.binding import (PACKET_DTYPE, SEGMENT_DTYPE, VQ_PACKET_DTYPE, VSYN_ERR_STREAM, VSYN_SEG_RESET,
                                         VSYN_ST_BAD_VQ, Synth, VsynError, VqSpec)
-from tests.workloads import GOLDEN, build_probe, load_golden, read_entropy_dump, synth_vq_packet
+from tests.workloads import (GOLDEN, build_probe, disagreeing_window_flags, load_golden, read_entropy_dump, synth_vq_packet,
+                             window_flag_classes)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -75,7 +76,8 @@ def test_vq_stage_reproduces_reference_residue_and_pcm(probe, name, tmp_path):
     assert np.abs(np.concatenate(got, axis=1) - b["pcm"]).max() < TOL
 
 
-def _random_vq_batch(spec, vq_spec, streams, per_stream, pattern, seed):
+def _random_vq_batch(spec, vq_spec, streams, per_stream, pattern, seed, flag_rng=None):
+    """flag_rng: window flags drawn by disagreeing_window_flags (random bytes, class A excluded) instead of the consistent ones"""
     rng = np.random.default_rng(seed)
     Cn = spec.channels
     long_mode = [i for i, (bf, _) in enumerate(spec.modes) if bf][0]
@@ -110,6 +112,10 @@ def _random_vq_batch(spec, vq_spec, streams, per_stream, pattern, seed):
             c_off += cls.size
             e_off += ent.size
             r_off += Cn * n2
+        if flag_rng is not None:
+            blocks = [pattern[q % len(pattern)] for q in range(per_stream)]
+            sl = slice(s * per_stream, (s + 1) * per_stream)
+            pk["prev_long"][sl], pk["next_long"][sl] = disagreeing_window_flags(flag_rng, blocks, spec.blocksize0, spec.blocksize1)
     return pk, seg, vqp, np.concatenate(cls_l), np.concatenate(ent_l), np.concatenate(want)
 
 
@@ -148,6 +154,32 @@ def test_vq_stage_tables_in_lds_and_in_global_memory(tables_in_lds, monkeypatch)
     assert out["rc"] == 0, out
     assert np.array_equal(out["residue"].view(np.uint32), want.view(np.uint32))
     assert np.abs(want).max() > 0
+
+
+def test_vq_stage_with_disagreeing_window_flags():
+    """The VQ stage's packets with window flag bytes that disagree with the block sequence (short-then-long with prev_long set,
+    long-then-long with either flag clear, bytes 2 / 0x80 / 255, random bytes on short blocks): residue bit for bit, PCM against the
+    oracle fed the same residue."""
+    from tests.workloads import fixture_like_spec, synthetic_vq_spec
+    spec = fixture_like_spec(2)
+    vqs = synthetic_vq_spec(2, spec.blocksize1)
+    pattern = [1, 1, 0, 1, 0, 0, 1, 1, 1, 0]
+    S, ppk = 6, 30
+    pk, seg, vqp, cls, ent, want = _random_vq_batch(spec, vqs, S, ppk, pattern, seed=41, flag_rng=np.random.default_rng(42))
+    blocks = [pattern[q % len(pattern)] for q in range(ppk)]
+    cl = window_flag_classes(blocks, pk["prev_long"][:ppk], pk["next_long"][:ppk])
+    assert cl["B"] and cl["C"] and cl["D"] and not cl["A"], cl
+    syn = Synth(spec, max_streams=S)
+    syn.attach_vq(vqs)
+    ys = np.zeros((len(pk), 2, syn.ys_stride), np.uint16)
+    plane = ppk * spec.blocksize1 // 2
+    out = syn.submit_host_vq(pk, seg, ys, vqp, cls, ent, want.size, plane)
+    assert out["rc"] == 0, out
+    assert np.array_equal(out["residue"].view(np.uint32), want.view(np.uint32))
+    w = ob.OracleSynth(spec, S).submit_host(pk, seg, ys, want, plane)
+    assert w["rc"] == 0
+    assert np.array_equal(out["emit_len"], w["emit_len"])
+    assert np.abs(out["pcm"] - w["pcm"]).max() < TOL * max(1.0, float(np.abs(w["pcm"]).max()))
 
 
 @pytest.mark.parametrize("variant", ["format0", "format1x2", "submaps"])

@@ -304,14 +304,15 @@ def test_packet_that_fails_half_way_leaves_the_batch_consistent(probe, tmp_path,
 SYNTH = sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("synth_") and f.endswith(".ogg"))
 
 
-@pytest.mark.parametrize("name", SYNTH)
+@pytest.mark.parametrize("name", SYNTH + ["winflags_bcd", "winflags_a"])
 def test_synthetic_streams_entropy_half_matches_reference(probe, name, tmp_path):
     """Streams written by oracle/make_synth_ogg.py from the Vorbis I specification — setups the two real fixtures do not have:
     1-3 channels, other block sizes, floor multipliers / post counts / subclass books, residue formats 0 / 1 / 2, vector lengths
     that are not powers of two, lookup types 1 and 2, sequence_p, sparse and ordered codebooks, two submaps, several coupling
     steps — with the REFERENCE decoder's hooks on them as golden vectors. The host's entropy half must reproduce the
     reference's 'floor1 ys' and 'after_residue' exactly, both as floats (PARSEOGGVORBIS_VQ=0) and as entry numbers pushed
-    through the oracle's accumulate stage (VQ mode)."""
+    through the oracle's accumulate stage (VQ mode). winflags_*: window flags that disagree with the blocks around them (classes
+    B, C, D; class A), handed to the synthesis half as they are in the packets."""
     from oracle import oracle_binding as ob
     z = np.load(os.path.join(GOLDEN, name + ".npz"))
     out = str(tmp_path / "e.bin")
@@ -323,6 +324,17 @@ def test_synthetic_streams_entropy_half_matches_reference(probe, name, tmp_path)
         Cn = d["channels"]
         assert d["P"] == int(z["packets"]) and Cn == int(z["channels"])
         assert (d["blocksize0"], d["blocksize1"]) == (int(z["blocksize0"]), int(z["blocksize1"]))
+        if name.startswith("winflags_"):
+            from tests.workloads import window_flag_classes
+            lg = z["mode_blockflag"][d["packets"]["mode"]]
+            assert np.array_equal(lg, z["block_long"])
+            for f, key in (("prev_long", "win_prev"), ("next_long", "win_next")):  # short blocks: the reference never reads them
+                assert np.array_equal(d["packets"][f][lg == 1], z[key][lg == 1]), f
+            cl = window_flag_classes(lg, d["packets"]["prev_long"], d["packets"]["next_long"])
+            if name == "winflags_a":
+                assert len(cl["A"]) == 1, cl
+            else:
+                assert cl["B"] and cl["C"] and cl["D"] and not cl["A"], cl
         off = 0
         for ln, where in zip(z["ys_len"], z["ys_where"]):
             p, c = divmod(int(where), 1000)

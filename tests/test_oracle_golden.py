@@ -97,13 +97,37 @@ def _synth_names():
     return sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("synth_") and f.endswith(".ogg"))
 
 
-@pytest.mark.parametrize("name", _synth_names())
+@pytest.mark.parametrize("name", _synth_names() + ["winflags_bcd"])
 def test_full_path_matches_reference_on_synthetic_streams(name, tmp_path_factory):
     """The oracle's whole synthesis path (floor unwrap + curve, propagate, coupling chains, product, IMDCT of every block size,
     windows, overlap, granule clipping) on the synthetic streams of oracle/make_synth_ogg.py — 2-6 channels, floor multipliers
     1-4, up to three coupling steps, three modes, block sizes 64 ... 4096: bit-identical to the REFERENCE decoder's PCM.
     Inputs are the host decoder's entropy output (tests/host_entropy_dump.cpp), itself checked against the reference's hooks
-    in tests/test_host_decoder.py."""
+    in tests/test_host_decoder.py. winflags_bcd: window flags that disagree with the blocks around them (classes B, C, D)."""
+    res, z, d = _oracle_on_stream(name, tmp_path_factory)
+    total = z["pcm"].shape[1]
+    assert res["rc"] == 0 and res["flags"] == 0, res
+    assert int(res["emit_len"].sum()) == total
+    assert np.array_equal(bits(res["pcm"][0][:, :total]), bits(z["pcm"]))
+
+
+def test_window_flag_tail_stream_is_refused(tmp_path_factory):
+    """winflags_a: a stream the reference decodes (rc 0) with one long block whose next_long flag is set in front of a short block.
+    The oracle refuses it at the short block with VSYN_ST_WINDOW_FLAGS, as the device does; the PCM in front of it is the
+    reference's, bit for bit."""
+    from parseoggvorbis_amd import binding
+    res, z, d = _oracle_on_stream("winflags_a", tmp_path_factory)
+    lg, nx = z["block_long"], z["win_next"]
+    at = [q + 1 for q in range(len(lg) - 1) if lg[q] and nx[q] and not lg[q + 1]]
+    assert len(at) == 1
+    assert (res["rc"], res["flags"], res["first_bad"]) == (binding.VSYN_ERR_STREAM, binding.VSYN_ST_WINDOW_FLAGS, at[0])
+    before = int(res["emit_len"][:at[0]].sum())
+    assert before > 0
+    assert np.array_equal(bits(res["pcm"][0][:, :before]), bits(z["pcm"][:, :before]))
+
+
+def _oracle_on_stream(name, tmp_path_factory):
+    """the host decoder's entropy output of tests/golden/<name>.ogg through the oracle -> (oracle result, golden npz, entropy dump)"""
     import os
     import subprocess
     from parseoggvorbis_amd.binding import SEGMENT_DTYPE, SetupSpec
@@ -127,7 +151,4 @@ def test_full_path_matches_reference_on_synthetic_streams(name, tmp_path_factory
     total = z["pcm"].shape[1]
     orc = ob.OracleSynth(spec, max_streams=1)
     assert orc.ys_stride == d["ys_stride"]
-    res = orc.submit_host(d["packets"], seg, d["ys"], d["residue"], total + 8)
-    assert res["rc"] == 0 and res["flags"] == 0, res
-    assert int(res["emit_len"].sum()) == total
-    assert np.array_equal(bits(res["pcm"][0][:, :total]), bits(z["pcm"]))
+    return orc.submit_host(d["packets"], seg, d["ys"], d["residue"], total + 8), z, d

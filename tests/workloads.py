@@ -91,11 +91,13 @@ def _encode_ys(xs, mult, target, rng, zero_frac):
 
 
 def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, ylo=28, yhi=88, unused_frac=0.0,
-                granule_last=False, roll=True):
+                granule_last=False, roll=True, prev_long=None, next_long=None):
     """Synthetic batch in the shape of BASELINE configs 3/4:
     residue = round(Laplace(b=1.5)) with 60 % zeros; floor amplitudes a random walk in [ylo,yhi] (step +-6)
     over the setup's X list, wrapped into coded ys.  pattern: 'long', 'short', 'mixed' (L L L S*8 repeating, rotated per
     stream) or an explicit sequence of block flags (1 = long), the same for every stream.
+    prev_long / next_long: window flag bytes of every packet of the batch ([streams * packets_per_stream], short packets included),
+    instead of the flags that agree with the block sequence (disagreeing_window_flags); the batch is otherwise the same.
     Returns dict(packets, segments, ys, residue, plane_stride)."""
     rng = np.random.default_rng(seed)
     C = spec.channels
@@ -148,6 +150,10 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
             r[rng.random((C, n // 2)) < 0.6] = 0
             res_parts.append(r.astype(np.float32).ravel())
             off += C * (n // 2)
+    if prev_long is not None:
+        pk["prev_long"] = np.asarray(prev_long, np.uint8)
+    if next_long is not None:
+        pk["next_long"] = np.asarray(next_long, np.uint8)
     if granule_last:
         for s in range(streams):
             fl = flags1 if (not roll or pattern != "mixed") else np.roll(flags1, s % 11)
@@ -157,6 +163,54 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
             pk[s * packets_per_stream + packets_per_stream - 1]["granule"] = total - min(37, last_l // 2)  # clipped last packet
     plane = packets_per_stream * (spec.blocksize1 // 2) + 64
     return dict(packets=pk, segments=seg, ys=ys, residue=np.concatenate(res_parts), plane_stride=plane)
+
+
+FLAG_BYTES = np.array([0, 1, 2, 0x80, 255], np.uint8)  # the reference treats any non-zero byte as true (getWindow(bool, bool))
+
+
+def disagreeing_window_flags(rng, blocks, bs0, bs1, allow_a=False):
+    """Window flag bytes drawn at random (0, 1, 2, 0x80, 255) for every packet of one stream, whatever the blocks around it.
+    blocks: block flags of the stream (1 = long). Each of classes B, C and D (window_flag_classes) is forced at least once where the
+    blocks allow it. Unless allow_a, a long block followed by a smaller one gets next_long = 0: that case (class A,
+    VSYN_ST_WINDOW_FLAGS) is refused by the device; the three others stay exact. -> (prev_long, next_long)"""
+    blocks = np.asarray(blocks, np.uint8)
+    n = len(blocks)
+    prev = FLAG_BYTES[rng.integers(0, len(FLAG_BYTES), n)]
+    nxt = FLAG_BYTES[rng.integers(0, len(FLAG_BYTES), n)]
+    lg = blocks == 1
+    at_b = np.flatnonzero(~lg[:-1] & lg[1:]) + 1  # long after short
+    at_c = np.flatnonzero(lg[:-1] & lg[1:])       # long before long
+    at_d = at_c + 1                               # long after long
+    if len(at_b):
+        prev[at_b[rng.integers(0, len(at_b))]] = FLAG_BYTES[rng.integers(1, len(FLAG_BYTES))]
+    if len(at_c):
+        nxt[at_c[rng.integers(0, len(at_c))]] = 0
+        prev[at_d[rng.integers(0, len(at_d))]] = 0
+    if bs0 < bs1 and not allow_a:
+        nxt[:-1][lg[:-1] & ~lg[1:]] = 0
+    return prev, nxt
+
+
+def window_flag_classes(blocks, prev, nxt):
+    """-> dict class -> packet indices of one stream where its window flags disagree with the block flags around it:
+    A long, next_long set, short block behind; B short, then long with prev_long set; C long with next_long clear, then long;
+    D long, then long with prev_long clear. (A and B disagree only in name when blocksize0 == blocksize1.)"""
+    b = np.asarray(blocks, np.uint8) == 1
+    p = np.asarray(prev) != 0
+    x = np.asarray(nxt) != 0
+    out = dict(A=[], B=[], C=[], D=[])
+    for i in range(len(b)):
+        if not b[i]:
+            continue
+        if i + 1 < len(b) and x[i] and not b[i + 1]:
+            out["A"].append(i)
+        if i > 0 and not b[i - 1] and p[i]:
+            out["B"].append(i)
+        if i + 1 < len(b) and b[i + 1] and not x[i]:
+            out["C"].append(i)
+        if i > 0 and b[i - 1] and not p[i]:
+            out["D"].append(i)
+    return out
 
 
 def read_entropy_dump(path):
