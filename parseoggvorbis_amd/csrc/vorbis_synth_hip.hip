@@ -90,10 +90,28 @@ uint32_t ilog2(uint32_t v) {
 }
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Knobs that tests and stress tools use to force cases (tools/README.md): read from the environment once per handle, in vsyn_create.
+struct Options {
+  uint32_t run_len = 0;           // VSYN_RUN_LEN=<R>: packets per run of the fused kernels (0: fused_pick_run_len plans it)
+  bool vq_no_lds_tables = false;  // VSYN_VQ_NO_LDS_TABLES=1: the residue VQ kernel keeps its value tables in global memory
+  bool debug = false;             // VSYN_DEBUG: the setup's kernel choices on stderr
+};
+
+Options options_from_env() {
+  Options o;
+  const char* e = getenv("VSYN_RUN_LEN");
+  if (e && atoi(e) > 0) o.run_len = (uint32_t)atoi(e);
+  e = getenv("VSYN_VQ_NO_LDS_TABLES");
+  o.vq_no_lds_tables = e && atoi(e);
+  o.debug = getenv("VSYN_DEBUG") != nullptr;
+  return o;
+}
+
 }  // namespace
 
 struct vsyn_handle {
   int device = 0;
+  Options opt;
   ConstHeader H{};
   std::vector<uint8_t> host_const;
   uint8_t* d_const = nullptr;
@@ -111,21 +129,21 @@ struct vsyn_handle {
   DevStatus* d_status = nullptr;
   FusedTables fused{};
   UTables utab{};
-  bool fused_ok = false;
   uint32_t fused_mask = 0;             // what the layout kernel classifies by: bit 0 long-run kernel usable, bit 1 mixed-block runs fused too
-  uint32_t tuned_mask = 0;             // the same without the size-generic kernel (used when a tap it cannot write is requested)
   bool u_mixed = false;                // class-2 runs go to the size-generic kernel (vsyn_fused_u.h) instead of fused_run<.., MIXED>
   int num_cus = 256;
   hipStream_t host_stream = nullptr;   // vsyn_submit_host: copies in, kernels, copies out
   hipStream_t side = nullptr;          // the (usually empty) staged work list runs beside the fused kernel
   hipStream_t pre = nullptr;           // layout + floor unwrap of submit i+1 run beside the fused kernel of submit i
   hipEvent_t ev_join = nullptr, ev_self = nullptr;
+  hipEvent_t ev_reset = nullptr;       // recorded behind the memset of vsyn_reset_streams
+  bool reset_pending = false;          // the next preparation waits for ev_reset
   // Workspace ring: submit i uses slot i % WS_RING. When its preparation kernels run on the internal stream `pre` (beside the previous
   // submit's synthesis kernel) the slot's previous user, submit i - WS_RING, must be done: known from an event recorded on the caller's
-  // stream behind every EV_EVERY-th submit whose preparation ran there. WS_RING = 2, EV_EVERY = 1 on purpose: a deeper ring lets the
-  // preparation run further ahead, but then its workgroups land in the MIDDLE of an exact-fit synthesis grid instead of at its start
-  // (measured with 8 / 4: config 3's synthesis kernel 0.258 instead of 0.242 ms).
-  static constexpr uint32_t WS_RING = 2, EV_EVERY = 1, EV_RING = 2, CNT_RING = 4;
+  // stream behind every submit whose preparation ran there. WS_RING = 2 on purpose: a deeper ring lets the preparation run further
+  // ahead, but then its workgroups land in the MIDDLE of an exact-fit synthesis grid instead of at its start (measured with a ring of 8
+  // and an event behind every 4th submit: config 3's synthesis kernel 0.258 instead of 0.242 ms).
+  static constexpr uint32_t WS_RING = 2, EV_RING = 2, CNT_RING = 4;
   hipEvent_t ev_pre_done[WS_RING] = {}, ev_ring[EV_RING] = {};
   uint64_t ev_ring_submit[EV_RING] = {~0ull, ~0ull};  // submit index each ring event was recorded behind
   bool pre_done_valid[WS_RING] = {};
@@ -365,6 +383,7 @@ int vsyn_create(const vsyn_setup* setup, int device, uint32_t max_streams, vsyn_
   if (device < 0 || device >= ndev) return fail(err, VSYN_ERR_NO_DEVICE, "device %d not in 0..%d", device, ndev - 1);
   vsyn_handle* h = new vsyn_handle();
   h->device = device;
+  h->opt = options_from_env();
   int rc = build_const(setup, max_streams, h, err);
   if (rc) {
     delete h;
@@ -407,6 +426,7 @@ int vsyn_create(const vsyn_setup* setup, int device, uint32_t max_streams, vsyn_
   const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
   HC(hipEventCreateWithFlags(&h->ev_join, evf));
   HC(hipEventCreateWithFlags(&h->ev_self, evf));
+  HC(hipEventCreateWithFlags(&h->ev_reset, evf));
   for (uint32_t k = 0; k < H.num_modes && k < 64; ++k)
     if (H.mode_blockflag[k]) h->long_modes |= 1ull << k;
   for (uint32_t b = 0; b < vsyn_handle::WS_RING; ++b) HC(hipEventCreateWithFlags(&h->ev_pre_done[b], evf));
@@ -415,31 +435,26 @@ int vsyn_create(const vsyn_setup* setup, int device, uint32_t max_streams, vsyn_
   HC(hipFuncSetAttribute((const void*)vsyn_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 68 * PREP_THREADS * 4));
   HC(h->ws_count.ensure(vsyn_handle::CNT_RING));
   HC(hipMemset(h->ws_count.p, 0, sizeof(uint32_t) * vsyn_handle::CNT_RING));
-  h->fused_mask = h->tuned_mask = fused_ok_mask(h->H, h->host_const.data());
-  if ((e = fused_tables_create(h->H, h->host_const.data(), &h->fused)) != hipSuccess) {
+  h->fused_mask = fused_ok_mask(h->H, h->host_const.data());
+  if ((e = fused_tables_create(h->H, h->host_const.data(), &h->fused, h->opt.debug)) != hipSuccess) {
     fail(err, VSYN_ERR_HIP, "fused table upload failed: %s", hipGetErrorString(e));
     return cleanup(VSYN_ERR_HIP);
   }
-  // The size-generic kernel takes the mixed-block runs of every setup it covers: all of them where the 256/2048 kernel has no
-  // mixed path, and (VSYN_U_MIXED=1) in its place where it has one.
-  if (u_supported(h->H, h->host_const.data()) && !getenv("VSYN_NO_U")) {
-    const bool want = !(h->fused_mask & 2u) || (getenv("VSYN_U_MIXED") && atoi(getenv("VSYN_U_MIXED")));
-    if (want) {
-      e = u_tables_create(h->H, h->host_const.data(), &h->utab);
-      if (e == hipSuccess) {
-        h->u_mixed = true;
-        h->fused_mask |= 2u;
-      } else if (e == hipErrorInvalidValue) {
-        // the setup does not fit (its channel waves plus the tables of an 8192-sample block exceed one CU's LDS): staged kernels
-        u_tables_destroy(&h->utab);
-        (void)hipGetLastError();
-      } else {
-        fail(err, VSYN_ERR_HIP, "generic fused table upload failed: %s", hipGetErrorString(e));
-        return cleanup(VSYN_ERR_HIP);
-      }
+  // The size-generic kernel takes the mixed-block runs of every setup it covers where the 256/2048 kernel has no mixed path.
+  if (!(h->fused_mask & 2u) && u_supported(h->H, h->host_const.data())) {
+    e = u_tables_create(h->H, h->host_const.data(), &h->utab, h->opt.debug);
+    if (e == hipSuccess) {
+      h->u_mixed = true;
+      h->fused_mask |= 2u;
+    } else if (e == hipErrorInvalidValue) {
+      // the setup does not fit (its channel waves plus the tables of an 8192-sample block exceed one CU's LDS): staged kernels
+      u_tables_destroy(&h->utab);
+      (void)hipGetLastError();
+    } else {
+      fail(err, VSYN_ERR_HIP, "generic fused table upload failed: %s", hipGetErrorString(e));
+      return cleanup(VSYN_ERR_HIP);
     }
   }
-  h->fused_ok = h->fused_mask != 0;
 #undef HC
   *out = h;
   return VSYN_OK;
@@ -530,6 +545,7 @@ void vsyn_destroy(vsyn_handle* h) {
   if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->ev_self) (void)hipEventDestroy(h->ev_self);
+  if (h->ev_reset) (void)hipEventDestroy(h->ev_reset);
   for (uint32_t b = 0; b < vsyn_handle::WS_RING; ++b)
     if (h->ev_pre_done[b]) (void)hipEventDestroy(h->ev_pre_done[b]);
   for (uint32_t b = 0; b < vsyn_handle::EV_RING; ++b)
@@ -609,8 +625,12 @@ static hipError_t profile_end(vsyn_handle* h, hipStream_t s) {
 
 int vsyn_reset_streams(vsyn_handle* h, void* hip_stream, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  std::lock_guard<std::mutex> lk(h->mu);
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemsetAsync(h->d_state, 0, sizeof(StreamState) * 2 * h->H.max_streams, (hipStream_t)hip_stream));
+  // the next preparation reads and writes these records on whichever stream it runs: it waits for the memset
+  HIPCHK(hipEventRecord(h->ev_reset, (hipStream_t)hip_stream));
+  h->reset_pending = true;
   return VSYN_OK;
 }
 
@@ -651,26 +671,56 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
   hipStream_t s = (hipStream_t)hip_stream;
   const ConstHeader& H = h->H;
   const uint32_t C = H.channels;
+
+  // ---- 1. plan -------------------------------------------------------------------------------------------------------------------
   // The intermediate-signal taps (after_envelope, pcm_after_mdct) exist only in the staged kernels. The feature taps — the rendered
   // floor curve and the unwrapped posts — do not force them: the posts come from the unwrap kernel either way and
   // the curve from the tap variant of the fused kernel.
   const bool want_taps = taps && (taps->after_envelope || taps->pcm_after_mdct);
   const bool use_u = h->u_mixed;  // (both fused kernels have a floor-curve tap variant)
-  const uint32_t fmask = use_u ? h->fused_mask : h->tuned_mask;
+  const uint32_t fmask = h->fused_mask;
   const bool force_staged = want_taps || (flags & VSYN_SUBMIT_STAGED) || !fmask;
   const uint32_t R = force_staged ? std::min<uint32_t>(max_seg_packets, 1024u)
-                                  : fused_pick_run_len((fmask & 1u) || !use_u ? h->fused.waves_per_cu : (int)h->utab.waves_per_cu, S, C,
-                                                       max_seg_packets, h->num_cus);
+                                  : fused_pick_run_len(h->opt.run_len, (fmask & 1u) || !use_u ? h->fused.waves_per_cu : (int)h->utab.waves_per_cu,
+                                                       S, C, max_seg_packets, h->num_cus);
+  const uint32_t runs_per_seg = (max_seg_packets + R - 1) / R;
 
-  // Workspace of this submit: slot i % WS_RING of a ring, so that the preparation of later submits can run ahead of the synthesis
-  // kernels (see vsyn_handle).
-  const uint64_t isub = h->nsub++;
+  // Preparation of the batch (layout scan, floor-1 step 1). The preparation kernel vsyn_prep_kernel (vsyn_prep.h: layout and floor
+  // workgroups side by side, no dependencies) runs on the caller's stream whenever it can: every run taken by a fused kernel, no residue
+  // VQ stage (its kernel needs the packets' offsets first), no segment longer than PREP_MAX_SEG_PACKETS, no VSYN_SUBMIT_PRE_KERNELS.
+  // Otherwise the chained layout and unwrap kernels (vsyn_staged.h) run. They go on the internal stream `pre`, beside the previous
+  // submit's synthesis kernel, when VSYN_SUBMIT_INPUTS_READY is set and the batch is not forced staged.
+  const bool prep_kernel = !force_staged && (fmask & 2u) && !d_vq && max_seg_packets <= PREP_MAX_SEG_PACKETS && !(flags & VSYN_SUBMIT_PRE_KERNELS);
+  hipStream_t ps = !prep_kernel && (flags & VSYN_SUBMIT_INPUTS_READY) && !force_staged ? h->pre : s;
+  // chained layout kernel: segments longer than LAYOUT_CHUNK_PACKETS are scanned in chunks (a multiple of R each) chained by a
+  // look-back; the usual batch has one chunk per segment
+  const uint32_t chunk_packets = max_seg_packets <= LAYOUT_CHUNK_PACKETS ? runs_per_seg * R : (LAYOUT_CHUNK_PACKETS + R - 1u) / R * R;
+  const uint32_t chunks_per_seg = (max_seg_packets + chunk_packets - 1u) / chunk_packets;
+  // preparation kernel: a workgroup takes whole runs, as many as give about one (packet, channel) row per thread; a batch of short
+  // segments (thousands of streams with a few packets each) gets smaller workgroups — whole waves — instead of 256 threads with a
+  // handful of rows. A layout workgroup and a floor workgroup per (segment, chunk), dealt in alternating groups of eight (vsyn_prep.h).
+  const uint32_t prep_nt = std::min<uint32_t>(PREP_THREADS, std::max<uint32_t>(64u, ((max_seg_packets * C + 63u) / 64u) * 64u));
+  const uint32_t prep_chunk_runs = std::max<uint32_t>(1u, std::max<uint32_t>(1u, prep_nt / C) / R);
+  const uint32_t prep_chunks_per_seg = (runs_per_seg + prep_chunk_runs - 1u) / prep_chunk_runs;
+  const uint64_t prep_wgs = (((uint64_t)S * prep_chunks_per_seg + 7u) / 8u) * 16u;
+  // Staged kernels walk the work list the layout kernel built: everything when forced, otherwise only the runs the fused kernel
+  // declines (short / mixed blocks, carry-in). In fused mode they run on a forked side stream beside the fused kernel (disjoint
+  // outputs) and exit at once when the list is empty. With the mixed-block kernel available every run is taken by one of the two fused
+  // kernels (run_class() never answers 0 then; packets with an invalid mode are skipped by both paths): the staged kernels are not
+  // launched at all.
+  const bool staged_may_work = force_staged || !(fmask & 2u);
+  hipStream_t ss = force_staged ? s : h->side;
+  // the fused kernels: one wave per (run, channel)
+  const uint64_t fused_units = (uint64_t)S * runs_per_seg * C;
+
+  // ---- 2. checks that can refuse the batch, then the allocations ----------------------------------------------------------------
+  if (!prep_kernel && (uint64_t)S * chunks_per_seg > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too many layout chunks");
+  if (prep_kernel && prep_wgs > 0x7FFFFFF0ull) return fail(err, VSYN_ERR_INVALID, "too many runs");
+  if (!force_staged && fused_units > (use_u ? U_MAX_UNITS : FUSED_MAX_UNITS)) return fail(err, VSYN_ERR_INVALID, "too many runs");
+  // workspace of this submit: slot i % WS_RING of a ring, so that the preparation of later submits can run ahead of the synthesis
+  // kernels (see vsyn_handle)
+  const uint64_t isub = h->nsub;
   const uint32_t wb = (uint32_t)(isub % vsyn_handle::WS_RING), wb_prev = (uint32_t)((isub + vsyn_handle::WS_RING - 1u) % vsyn_handle::WS_RING);
-  uint32_t* cnt = h->ws_count.p + (isub % vsyn_handle::CNT_RING);
-  uint32_t* cnt_next = h->ws_count.p + ((isub + 1u) % vsyn_handle::CNT_RING);
-  ++h->submit_count;
-  // the submit's number tags the stream-state records and the look-back records of the chunked scan; 0 means "never written"
-  const uint32_t epoch = (h->submit_count & 0x3FFFFFFFu) ? h->submit_count : ++h->submit_count;
   HIPCHK(h->ws_info[wb].ensure((size_t)P + 8));  // (slack: the generic kernel fetches descriptors eight at a time)
   HIPCHK(h->ws_seg[wb].ensure(S));
   HIPCHK(h->ws_segmap[wb].ensure(P));
@@ -680,42 +730,44 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
     HIPCHK(h->ws_fy[wb].ensure((size_t)P * C * H.ys_stride));
     fy = h->ws_fy[wb].p;
   }
-  const uint32_t runs_per_seg = (max_seg_packets + R - 1) / R;
   HIPCHK(h->ws_runcls[wb].ensure((size_t)S * runs_per_seg + 16));
+  bool clear_chunks = false;  // the look-back records are epoch-tagged: cleared once, when the buffer grows
+  if (!prep_kernel && chunks_per_seg > 1 && (size_t)S * chunks_per_seg > h->ws_chunks.cap) {
+    HIPCHK(h->ws_chunks.ensure((size_t)S * chunks_per_seg));
+    clear_chunks = true;
+  }
+  float* env = taps && taps->after_envelope ? taps->after_envelope : nullptr;
+  float* blk = taps && taps->pcm_after_mdct ? taps->pcm_after_mdct : nullptr;
+  if (staged_may_work) {
+    // residue floats upper bound (the descriptors are device resident, so the exact sum is not known here)
+    const size_t bound = (size_t)P * C * (H.bs[1] / 2);
+    if (!env) {
+      HIPCHK(h->ws_env.ensure(bound));
+      env = h->ws_env.p;
+    }
+    if (!blk) {
+      HIPCHK(h->ws_blk.ensure(2 * bound));
+      blk = h->ws_blk.p;
+    }
+  }
   PktInfo* info = h->ws_info[wb].p;
   SegInfo* sinfo = h->ws_seg[wb].p;
   uint32_t* segmap = h->ws_segmap[wb].p;
   uint32_t* list = h->ws_list[wb].p;
 
-  // Preparation of the batch (layout scan, floor-1 step 1): two ways.
-  //   (a) vsyn_prep_kernel (vsyn_prep.h): ONE dependency-free kernel — layout workgroups and floor workgroups side by side, ~17 us — in
-  //       front of the synthesis kernel on the caller's stream; no second queue, no events. The default whenever every run is taken by
-  //       a fused kernel and no segment is longer than PREP_MAX_SEG_PACKETS.
-  //   (b) The chained layout and unwrap kernels (vsyn_staged.h): for staged work lists, intermediate-signal taps, the residue VQ stage
-  //       (its kernel needs the packets' offsets first), very long segments, VSYN_SUBMIT_PRE_KERNELS. With VSYN_SUBMIT_INPUTS_READY
-  //       they run on the internal stream `pre`, beside the previous submit's synthesis kernel: their ~35 us of dependent latency are
-  //       hidden, at the price of one event record and one cross-queue wait per submit (~15 us between two synthesis kernels) and ~6 us
-  //       of interference with an exact-fit synthesis grid.
-  //   Until late in round 3 (b)-hidden was the default for VSYN_SUBMIT_INPUTS_READY: against a 20 us preparation kernel it tied on
-  //   config 3 (0.256-0.259 ms per step either way) and won config 4 by 3 %. With the preparation's two halves running side by side
-  //   (a) wins everywhere measured: config 3 0.2540 vs 0.2572 ms, config 4 0.0796 vs 0.0823, 128/1024 0.187 vs 0.195 (same box,
-  //   profiles/r03_experiments/batch_preparation_ab.txt). VSYN_PREP_SERIAL=0 brings (b)-hidden back for such submits, for A/B runs; the
-  //   preparation kernel on the internal stream (VSYN_PREP_OVERLAP=1) lost to both (0.266 ms).
-  static const bool env_no_prep_kernel = getenv("VSYN_NO_PREP_KERNEL") && atoi(getenv("VSYN_NO_PREP_KERNEL"));
-  static const int env_prep_serial_mode = getenv("VSYN_PREP_SERIAL") ? (atoi(getenv("VSYN_PREP_SERIAL")) ? 1 : 0) : -1;
-  const bool env_prep_serial = env_prep_serial_mode != 0;
-  static const bool env_prep_overlap = getenv("VSYN_PREP_OVERLAP") && atoi(getenv("VSYN_PREP_OVERLAP"));
-  const bool prep_ok = !force_staged && (fmask & 2u) && !d_vq && max_seg_packets <= PREP_MAX_SEG_PACKETS && !(flags & VSYN_SUBMIT_PRE_KERNELS) && !env_no_prep_kernel;
-  const bool overlap_pre = (flags & VSYN_SUBMIT_INPUTS_READY) && !force_staged && !(env_prep_serial && prep_ok);
-  const bool prep_kernel = prep_ok && (!overlap_pre || env_prep_overlap);
-  hipStream_t ps = overlap_pre ? h->pre : s;
+  // ---- 3. take the submit number, order the streams -----------------------------------------------------------------------------
+  ++h->nsub;
+  uint32_t* cnt = h->ws_count.p + (isub % vsyn_handle::CNT_RING);
+  uint32_t* cnt_next = h->ws_count.p + ((isub + 1u) % vsyn_handle::CNT_RING);
+  ++h->submit_count;
+  // the submit's number tags the stream-state records and the look-back records of the chunked scan; 0 means "never written"
+  const uint32_t epoch = (h->submit_count & 0x3FFFFFFFu) ? h->submit_count : ++h->submit_count;
   if (ps != s) {
-    // the slot's previous user, submit isub - WS_RING, has to be done: the first ring event recorded at or behind it says so
+    // the slot's previous user, submit isub - WS_RING, has to be done: the ring event recorded behind it says so
     if (isub >= vsyn_handle::WS_RING) {
       const uint64_t need = isub - vsyn_handle::WS_RING;
-      const uint64_t jstar = need + ((vsyn_handle::EV_EVERY - 1u) - need % vsyn_handle::EV_EVERY);  // first j >= need with j % EV_EVERY == EV_EVERY - 1
-      const uint32_t slot = (uint32_t)((jstar / vsyn_handle::EV_EVERY) % vsyn_handle::EV_RING);
-      if (h->ev_ring_submit[slot] == jstar) {
+      const uint32_t slot = (uint32_t)(need % vsyn_handle::EV_RING);
+      if (h->ev_ring_submit[slot] == need) {
         HIPCHK(hipStreamWaitEvent(ps, h->ev_ring[slot], 0));
       } else {  // that submit's preparation ran on the caller's stream (no record): order behind everything queued there so far
         HIPCHK(hipEventRecord(h->ev_self, s));
@@ -731,33 +783,20 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
   // Consecutive preparations chain through the stream state (abs position, carry parity) and the list-counter ring: when this one
   // runs on another stream than the previous one did (flags differ between submits), that order has to be stated.
   if (h->pre_done_valid[wb_prev] && h->last_pre_stream != ps) HIPCHK(hipStreamWaitEvent(ps, h->ev_pre_done[wb_prev], 0));
-  const bool staged_may_work_pre = force_staged || !(fmask & 2u);
+  if (h->reset_pending) HIPCHK(hipStreamWaitEvent(ps, h->ev_reset, 0));
+
+  // ---- 4. launch --------------------------------------------------------------------------------------------------------------
   if (!prep_kernel) {
     // the list-counter ring is cleared one submit ahead by the layout kernel; submits that ran none in between break that chain
     if (!h->last_ran_layout) HIPCHK(hipMemsetAsync(h->ws_count.p, 0, sizeof(uint32_t) * vsyn_handle::CNT_RING, ps));
-    {
-      // segments longer than LAYOUT_CHUNK_PACKETS are scanned in chunks (a multiple of R each) chained by a look-back; the usual batch
-      // has one chunk per segment
-      const uint32_t chunk_packets = max_seg_packets <= LAYOUT_CHUNK_PACKETS ? runs_per_seg * R : (LAYOUT_CHUNK_PACKETS + R - 1u) / R * R;
-      const uint32_t chunks_per_seg = (max_seg_packets + chunk_packets - 1u) / chunk_packets;
-      const uint32_t lt = std::min(chunk_packets, max_seg_packets) <= LAYOUT_SHORT_PACKETS ? LAYOUT_THREADS_SHORT : LAYOUT_THREADS;
-      if (chunks_per_seg > 1) {
-        const size_t need = (size_t)S * chunks_per_seg;
-        if (need > h->ws_chunks.cap) {
-          HIPCHK(h->ws_chunks.ensure(need));
-          HIPCHK(hipMemsetAsync(h->ws_chunks.p, 0, h->ws_chunks.cap * sizeof(LayoutChunk), ps));  // flags are epoch-tagged: cleared once
-        }
-      }
-      if ((uint64_t)S * chunks_per_seg > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too many layout chunks");
-      vsyn_layout_kernel<<<S * chunks_per_seg, lt, layout_lds_bytes(lt, chunk_packets), ps>>>(
-          h->d_const, P, d_packets, S, d_segments, plane_stride, info, sinfo, h->d_state, d_emit_len, h->d_status, R, force_staged ? 0u : fmask, list, cnt,
-          cnt_next, segmap, h->ws_runcls[wb].p, runs_per_seg, chunk_packets, chunks_per_seg, h->ws_chunks.p, epoch);
-    }
-    {
-      const uint32_t rows = P * C;
-      vsyn_floor_unwrap_kernel<<<(rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, UNWRAP_THREADS, 0, ps>>>(h->d_const, P, nullptr, nullptr, info,
-                                                                                                         d_ys, fy, h->d_status);
-    }
+    if (clear_chunks) HIPCHK(hipMemsetAsync(h->ws_chunks.p, 0, h->ws_chunks.cap * sizeof(LayoutChunk), ps));
+    const uint32_t lt = std::min(chunk_packets, max_seg_packets) <= LAYOUT_SHORT_PACKETS ? LAYOUT_THREADS_SHORT : LAYOUT_THREADS;
+    vsyn_layout_kernel<<<S * chunks_per_seg, lt, layout_lds_bytes(lt, chunk_packets), ps>>>(
+        h->d_const, P, d_packets, S, d_segments, plane_stride, info, sinfo, h->d_state, d_emit_len, h->d_status, R, force_staged ? 0u : fmask, list, cnt,
+        cnt_next, segmap, h->ws_runcls[wb].p, runs_per_seg, chunk_packets, chunks_per_seg, h->ws_chunks.p, epoch);
+    const uint32_t rows = P * C;
+    vsyn_floor_unwrap_kernel<<<(rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, UNWRAP_THREADS, 0, ps>>>(h->d_const, P, nullptr, nullptr, info,
+                                                                                                       d_ys, fy, h->d_status);
     if (d_vq) {
       if (h->profile_which == 3) HIPCHK(profile_begin(h, ps, "vsyn_residue_vq_kernel"));
       if (h->vq_tables_in_lds)
@@ -766,8 +805,8 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
       else
         vsyn_residue_vq_kernel<false><<<std::min<uint32_t>(P, h->vq_grid), VQ_THREADS, h->vq_lds_bytes, ps>>>(
             h->d_const, h->d_vq, P, info, d_vq->packets, d_vq->cls, d_vq->num_cls, d_vq->entries, d_vq->num_entries, d_residue, h->d_status);
+      if (h->profile_which == 3) HIPCHK(profile_end(h, ps));
     }
-    if (d_vq && h->profile_which == 3) HIPCHK(profile_end(h, ps));
   } else {
     PrepCtx pc;
     pc.cb = h->d_const;
@@ -789,36 +828,15 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
     pc.fused_ok = fmask;
     pc.P = P;
     pc.epoch = epoch;
-    // a workgroup takes whole runs, as many as give about one (packet, channel) row per thread; a batch of short segments (thousands of
-    // streams with a few packets each) gets smaller workgroups — whole waves — instead of 256 threads with a handful of rows
-    const uint32_t nt = std::min<uint32_t>(PREP_THREADS, std::max<uint32_t>(64u, ((max_seg_packets * C + 63u) / 64u) * 64u));
-    const uint32_t ppp = std::max<uint32_t>(1u, nt / C);
-    pc.chunk_runs = std::max<uint32_t>(1u, ppp / R);
-    pc.chunks_per_seg = (runs_per_seg + pc.chunk_runs - 1u) / pc.chunk_runs;
-    // a layout workgroup and a floor workgroup per (segment, chunk), dealt in alternating groups of eight (vsyn_prep.h)
-    const uint64_t wgs = (((uint64_t)S * pc.chunks_per_seg + 7u) / 8u) * 16u;
-    if (wgs > 0x7FFFFFF0ull) return fail(err, VSYN_ERR_INVALID, "too many runs");
-    vsyn_prep_kernel<<<(uint32_t)wgs, nt, h->prep_lds_bytes, ps>>>(pc);
+    pc.chunk_runs = prep_chunk_runs;
+    pc.chunks_per_seg = prep_chunks_per_seg;
+    vsyn_prep_kernel<<<(uint32_t)prep_wgs, prep_nt, h->prep_lds_bytes, ps>>>(pc);
   }
-  h->last_ran_layout = !prep_kernel;
-  h->last_prep_on_main = ps == s;
   if (ps != s) {
     HIPCHK(hipEventRecord(h->ev_pre_done[wb], ps));
-    h->pre_done_valid[wb] = true;
     HIPCHK(hipStreamWaitEvent(s, h->ev_pre_done[wb], 0));
-  } else {
-    h->pre_done_valid[wb] = false;  // (ordered by the caller's stream itself)
   }
-  h->last_pre_stream = ps;
-  (void)staged_may_work_pre;
 
-  // staged kernels walk the work list the layout kernel built: everything when forced, otherwise only the runs the
-  // fused kernel declines (short / mixed blocks, carry-in). In fused mode they run on a forked side stream beside the
-  // fused kernel (disjoint outputs) and exit at once when the list is empty.
-  // With the mixed-block kernel available every run is taken by one of the two fused kernels (run_class() never answers
-  // 0 then; packets with an invalid mode are skipped by both paths): the staged kernels are not launched at all.
-  const bool staged_may_work = force_staged || !(fmask & 2u);
-  hipStream_t ss = force_staged ? s : h->side;
   if (staged_may_work) {
     if (!force_staged) {  // the side stream starts behind the preparation
       if (ps != s) {
@@ -827,18 +845,6 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
         HIPCHK(hipEventRecord(h->ev_self, s));
         HIPCHK(hipStreamWaitEvent(h->side, h->ev_self, 0));
       }
-    }
-    // residue floats upper bound (the descriptors are device resident, so the exact sum is not known here)
-    const size_t bound = (size_t)P * C * (H.bs[1] / 2);
-    float* env = taps && taps->after_envelope ? taps->after_envelope : nullptr;
-    float* blk = taps && taps->pcm_after_mdct ? taps->pcm_after_mdct : nullptr;
-    if (!env) {
-      HIPCHK(h->ws_env.ensure(bound));
-      env = h->ws_env.p;
-    }
-    if (!blk) {
-      HIPCHK(h->ws_blk.ensure(2 * bound));
-      blk = h->ws_blk.p;
     }
     const uint32_t grid = force_staged ? std::min<uint32_t>(P * C, 256u * 32u) : 512u;
     vsyn_spectrum_kernel<<<std::min<uint32_t>(grid, P), 256, 0, ss>>>(h->d_const, list, cnt, info, d_residue, fy, env,
@@ -877,7 +883,7 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
     hipError_t e = hipSuccess;
     if (a.fused_ok) {
       if (!time_u && (h->profile_which == 1 || h->profile_which == 2)) HIPCHK(profile_begin(h, s, a.curve ? "vsyn_fused_tap_kernel" : fused_kernel_name(H)));
-      e = fused_launch(H, h->fused, a, max_seg_packets, s);
+      e = fused_launch(H, h->fused, a, s);
       if (e != hipSuccess) return fail(err, VSYN_ERR_HIP, "fused launch failed: %s", hipGetErrorString(e));
       if (!time_u && (h->profile_which == 1 || h->profile_which == 2)) HIPCHK(profile_end(h, s));
     }
@@ -891,8 +897,15 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
     }
     if (staged_may_work) HIPCHK(hipStreamWaitEvent(s, h->ev_join, 0));
   }
-  if (ps != s && isub % vsyn_handle::EV_EVERY == vsyn_handle::EV_EVERY - 1u) {  // (a record costs ~4.6 us between two synthesis kernels)
-    const uint32_t slot = (uint32_t)((isub / vsyn_handle::EV_EVERY) % vsyn_handle::EV_RING);
+
+  // ---- 5. record the ordering state for the next submit ------------------------------------------------------------------------
+  h->last_ran_layout = !prep_kernel;
+  h->last_prep_on_main = ps == s;
+  h->pre_done_valid[wb] = ps != s;  // (a preparation on the caller's stream is ordered by that stream itself)
+  h->last_pre_stream = ps;
+  h->reset_pending = false;
+  if (ps != s) {  // (a record costs ~4.6 us between two synthesis kernels)
+    const uint32_t slot = (uint32_t)(isub % vsyn_handle::EV_RING);
     HIPCHK(hipEventRecord(h->ev_ring[slot], s));
     h->ev_ring_submit[slot] = isub;
   }
@@ -926,65 +939,53 @@ int vsyn_attach_vq(vsyn_handle* h, const vsyn_vq_setup* vq, const char** err) {
   if (!why.empty()) return fail(err, VSYN_ERR_INVALID, "%s", why.c_str());
   std::lock_guard<std::mutex> lk(h->mu);
   HIPCHK(hipSetDevice(h->device));
+  // LDS budget of the value-table kernel: one workgroup per CU may take this much. The attribute belongs to the kernel on the current
+  // device, not to the handle: one fixed value for every handle, so that a later handle never lowers the limit under an earlier one
+  const uint32_t lds_budget = 156u * 1024u;
+  HIPCHK(hipFuncSetAttribute((const void*)vsyn_residue_vq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
   HIPCHK(hipDeviceSynchronize());  // a previously attached block may still be in use
   if (h->d_vq) (void)hipFree(h->d_vq);
   h->d_vq = nullptr;
   HIPCHK(hipMalloc((void**)&h->d_vq, block.size()));
   HIPCHK(hipMemcpy(h->d_vq, block.data(), block.size(), hipMemcpyHostToDevice));
-  {
-    const VqHeader* vh = (const VqHeader*)block.data();
-    uint32_t lds_off[7];
-    const uint32_t wave_bytes = vq_lds_layout(vh->max_slots, vh->max_classes, lds_off);
-    h->vq_tables_in_lds = false;
-    h->vq_waves = 1;
-    if (vh->img_floats && !(getenv("VSYN_VQ_NO_LDS_TABLES") && atoi(getenv("VSYN_VQ_NO_LDS_TABLES")))) {
-      // value tables in LDS, one copy per workgroup: k workgroups of w waves per CU, the pair that keeps most waves resident
-      const uint32_t tab_bytes = vq_align16(vh->img_floats * 4u);
-      hipFuncAttributes fa;
-      HIPCHK(hipFuncGetAttributes(&fa, (const void*)vsyn_residue_vq_kernel<true>));
-      const uint32_t regs = ((uint32_t)std::max(fa.numRegs, 1) + 7u) / 8u * 8u;  // allocation granule 8, 512 per SIMD lane
-      const uint32_t cu_waves = 4u * std::min<uint32_t>(8u, 512u / regs);
-      uint32_t best_k = 0, best_w = 0;
-      for (uint32_t k = 1; k <= 4; ++k) {
-        // (several workgroups per CU: measured co-resident up to 2 x 67 KB, not at 2 x 73 KB — plan those against 128 KB)
-        const uint32_t budget = k == 1 ? 156u * 1024u : 128u * 1024u;
-        if (budget / k <= tab_bytes + wave_bytes) break;
-        const uint32_t w = std::min<uint32_t>({16u, (budget / k - tab_bytes) / wave_bytes, cu_waves / k});
-        if (w && k * w > best_k * best_w) best_k = k, best_w = w;
-      }
-      if (const char* e = getenv("VSYN_VQ_WAVES_PER_WG")) best_w = (uint32_t)std::max(1, std::min(16, atoi(e)));
-      if (best_w) {
-        const uint32_t lds = tab_bytes + best_w * wave_bytes;
-        {
-          // the attribute belongs to the kernel, not to the handle: only ever raise it, or a handle with smaller tables would pull the
-          // limit below what an older handle still launches with
-          static std::mutex mu_attr;
-          static uint32_t cur_max = 0;
-          std::lock_guard<std::mutex> lk2(mu_attr);
-          if (lds > cur_max) {
-            HIPCHK(hipFuncSetAttribute((const void*)vsyn_residue_vq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            cur_max = lds;
-          }
-        }
-        int per_cu = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vsyn_residue_vq_kernel<true>, (int)(VQ_THREADS * best_w), lds));
-        if (per_cu > 0) {
-          h->vq_tables_in_lds = true;
-          h->vq_waves = best_w;
-          h->vq_lds_bytes = lds;
-          if (const char* e = getenv("VSYN_VQ_WG_PER_CU")) per_cu = atoi(e);
-          h->vq_grid = (uint32_t)h->num_cus * (uint32_t)std::max(per_cu, 1);
-          if (getenv("VSYN_DEBUG")) fprintf(stderr, "[vsyn] vq: tables in LDS (%u B), %u waves per workgroup, %d workgroups per CU, %u B LDS\n", tab_bytes, best_w, per_cu, lds);
-        }
-      }
+  const VqHeader* vh = (const VqHeader*)block.data();
+  uint32_t lds_off[7];
+  const uint32_t wave_bytes = vq_lds_layout(vh->max_slots, vh->max_classes, lds_off);
+  h->vq_tables_in_lds = false;
+  h->vq_waves = 1;
+  if (vh->img_floats && !h->opt.vq_no_lds_tables) {
+    // value tables in LDS, one copy per workgroup: k workgroups of w waves per CU, the pair that keeps most waves resident
+    const uint32_t tab_bytes = vq_align16(vh->img_floats * 4u);
+    hipFuncAttributes fa;
+    HIPCHK(hipFuncGetAttributes(&fa, (const void*)vsyn_residue_vq_kernel<true>));
+    const uint32_t regs = ((uint32_t)std::max(fa.numRegs, 1) + 7u) / 8u * 8u;  // allocation granule 8, 512 per SIMD lane
+    const uint32_t cu_waves = 4u * std::min<uint32_t>(8u, 512u / regs);
+    uint32_t best_k = 0, best_w = 0;
+    for (uint32_t k = 1; k <= 4; ++k) {
+      // (several workgroups per CU: measured co-resident up to 2 x 67 KB, not at 2 x 73 KB — plan those against 128 KB)
+      const uint32_t budget = k == 1 ? lds_budget : 128u * 1024u;
+      if (budget / k <= tab_bytes + wave_bytes) break;
+      const uint32_t w = std::min<uint32_t>({16u, (budget / k - tab_bytes) / wave_bytes, cu_waves / k});
+      if (w && k * w > best_k * best_w) best_k = k, best_w = w;
     }
-    if (!h->vq_tables_in_lds) {
-      h->vq_lds_bytes = wave_bytes;
+    if (best_w) {
+      const uint32_t lds = tab_bytes + best_w * wave_bytes;
       int per_cu = 0;
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vsyn_residue_vq_kernel<false>, VQ_THREADS, h->vq_lds_bytes));
-      if (const char* e = getenv("VSYN_VQ_WG_PER_CU")) per_cu = atoi(e);
-      h->vq_grid = (uint32_t)h->num_cus * (uint32_t)std::max(per_cu, 1);
+      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vsyn_residue_vq_kernel<true>, (int)(VQ_THREADS * best_w), lds));
+      if (per_cu > 0) {
+        h->vq_tables_in_lds = true;
+        h->vq_waves = best_w;
+        h->vq_lds_bytes = lds;
+        h->vq_grid = (uint32_t)h->num_cus * (uint32_t)per_cu;
+        if (h->opt.debug) fprintf(stderr, "[vsyn] vq: tables in LDS (%u B), %u waves per workgroup, %d workgroups per CU, %u B LDS\n", tab_bytes, best_w, per_cu, lds);
+      }
     }
+  }
+  if (!h->vq_tables_in_lds) {
+    h->vq_lds_bytes = wave_bytes;
+    int per_cu = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vsyn_residue_vq_kernel<false>, VQ_THREADS, h->vq_lds_bytes));
+    h->vq_grid = (uint32_t)h->num_cus * (uint32_t)std::max(per_cu, 1);
   }
   return VSYN_OK;
 }

@@ -128,40 +128,6 @@ __device__ __forceinline__ void dft8(float2 (&x)[8]) {
   x[7] = csub(d1, d3);
 }
 
-// Register-to-register forms of the two index exchanges (no LDS): a transposition of three register-index bits with three
-// lane bits is three swap stages; lane bits 5 and 4 have swap instructions (v_permlane32_swap / v_permlane16_swap), lane bits
-// 3 and 2 are DPP row shifts under a bank mask, lane bits 1 and 0 a DPP quad permutation plus a select.
-typedef unsigned xch_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void xch_swap32(float& a, float& b) {  // a[32..63] <-> b[0..31]
-  const xch_u32x2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void xch_swap16(float& a, float& b) {  // odd rows of a <-> even rows of b
-  const xch_u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  a = __uint_as_float(r[0]);
-  b = __uint_as_float(r[1]);
-}
-template <int SH>  // lane bit 3 (SH = 8) or 2 (SH = 4)
-__device__ __forceinline__ void xch_row(float& lo, float& hi) {
-  constexpr int shr = 0x110 + SH, shl = 0x100 + SH;
-  constexpr int up = SH == 8 ? 0xC : 0xA, dn = SH == 8 ? 0x3 : 0x5;
-  const unsigned l = __float_as_uint(lo), h = __float_as_uint(hi);
-  const unsigned nl = __builtin_amdgcn_update_dpp(l, h, shr, 0xF, up, false);  // lanes with the bit set: hi of lane - SH
-  const unsigned nh = __builtin_amdgcn_update_dpp(h, l, shl, 0xF, dn, false);  // lanes with the bit clear: lo of lane + SH
-  lo = __uint_as_float(nl);
-  hi = __uint_as_float(nh);
-}
-template <int BIT>  // lane bit 1 or 0
-__device__ __forceinline__ void xch_quad(float& lo, float& hi, bool bitset) {
-  constexpr int qp = BIT == 1 ? 0x4E : 0xB1;
-  const unsigned l = __float_as_uint(lo), h = __float_as_uint(hi);
-  const unsigned th = __builtin_amdgcn_mov_dpp(h, qp, 0xF, 0xF, false);
-  const unsigned tl = __builtin_amdgcn_mov_dpp(l, qp, 0xF, 0xF, false);
-  lo = __uint_as_float(bitset ? th : l);
-  hi = __uint_as_float(bitset ? h : tl);
-}
-
 // FFT-512 across one wave: in: lane l holds z[t] = point l + 64 t; out: lane l holds Z[c'] = bin swap3(l) + 64 c'.
 // xb = this wave's exchange image (FUSED_XSLOTS float2), w = W512^j table (LDS).
 __device__ __forceinline__ void fft512_wave(float2 (&z)[8], float2* __restrict__ xb, const FusedLdsImage* __restrict__ T, uint32_t lane) {
@@ -170,39 +136,18 @@ __device__ __forceinline__ void fft512_wave(float2 (&z)[8], float2* __restrict__
 #pragma unroll
   for (int t = 1; t < 8; ++t) z[t] = cmulf(z[t], T->tw1[t][lane]);
   // exchange 1: element (t', a, c): lane 8a+c reg t'  ->  lane 8t'+c reg a.   row stride 72: conflict-free both ways
-#if defined(VSYN_FFT_REGS) && (VSYN_FFT_REGS & 1)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { xch_swap32(z[i].x, z[i + 4].x); xch_swap32(z[i].y, z[i + 4].y); }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) if (!(i & 2)) { xch_swap16(z[i].x, z[i + 2].x); xch_swap16(z[i].y, z[i + 2].y); }
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) { xch_row<8>(z[i].x, z[i + 1].x); xch_row<8>(z[i].y, z[i + 1].y); }
-#else
 #pragma unroll
   for (int t = 0; t < 8; ++t) xb[t * 72 + lane] = z[t];
 #pragma unroll
   for (int a = 0; a < 8; ++a) z[a] = xb[hi * 72 + a * 8 + c];
-#endif
   dft8(z);  // over a -> a'
 #pragma unroll
   for (int a = 1; a < 8; ++a) z[a] = cmulf(z[a], T->tw2[a][c]);  // W64^(c a')
   // exchange 2: element (h, a', c): lane 8h+c reg a'  ->  lane 8h+a' reg c.   row stride 65
-#if defined(VSYN_FFT_REGS) && (VSYN_FFT_REGS & 2)
-  {
-    const bool b1 = (lane & 2u) != 0, b0 = (lane & 1u) != 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { xch_row<4>(z[i].x, z[i + 4].x); xch_row<4>(z[i].y, z[i + 4].y); }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) if (!(i & 2)) { xch_quad<1>(z[i].x, z[i + 2].x, b1); xch_quad<1>(z[i].y, z[i + 2].y, b1); }
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) { xch_quad<0>(z[i].x, z[i + 1].x, b0); xch_quad<0>(z[i].y, z[i + 1].y, b0); }
-  }
-#else
 #pragma unroll
   for (int a = 0; a < 8; ++a) xb[a * 65 + lane] = z[a];
 #pragma unroll
   for (int k = 0; k < 8; ++k) z[k] = xb[c * 65 + hi * 8 + k];
-#endif
   dft8(z);  // over c -> c'
 }
 
@@ -617,11 +562,7 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
   uint32_t bseg[8];  // LDS address of the segment entry of each of this lane's 16 bins, 16 bits each; until a floor is seen:
                      // entry 0, which is where a channel without a curve finds its constant entry
 #pragma unroll
-#ifdef VSYN_BSEG_PACK
-  for (int t = 0; t < 8; ++t) bseg[t] = 0u;
-#else
   for (int t = 0; t < 8; ++t) bseg[t] = seg_base | (seg_base << 16);
-#endif
   uint32_t sidx = 0, xsl = 0;       // header index / x of sorted post `lane`
   int cur_floor = -1;
   uint32_t vrow = 0;
@@ -637,8 +578,9 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
   const uint32_t q0 = qa ? qa - 1 : 0;
   const PktInfo* const ip = A.info + __builtin_amdgcn_readfirstlane(sg.first_packet);
   PktScalars pi = pkt_load(ip + q0);
-  float2 raw[8];  // own channel's residue, requested one packet ahead (mixed runs: when the next block is a long one, too)
-  bool raw_ahead = false;  // MIXED: raw[] already holds (or will hold) this packet's residue
+  float2 raw[8];  // own channel's residue (steady runs: requested one packet ahead)
+  bool raw_ahead = false;  // MIXED: raw[] already holds this packet's residue. Never set (the mixed look-ahead goes by LDS-DMA, below);
+                           // kept because removing it reorders the kernel's scalar moves
   // MIXED, long blocks: the residue rows come into the hand-off image by LDS-DMA (global_load_lds: no registers), and the NEXT long
   // block's rows are requested as soon as this block's FFT has released the image — the 128-VGPR mixed path has no registers for a
   // look-ahead, and without one every long block of a mixed run waited a full memory latency.
@@ -760,7 +702,6 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
     float2 r[8];
     // L = rows of the block: all 8 (long) or the first (short); called with a literal so that each copy is straight-line code
     auto residue_rows = [&](const bool L) {
-#ifndef VSYN_NO_MIXED_DMA
       if (MIXED && L) {
         if (!dma_ahead) {
           issue_dma(pi.res_off + (uint64_t)c * ML, lane);
@@ -785,7 +726,6 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
         }
         return;
       }
-#endif
       if (MIXED && !raw_ahead) {
         const float2* src = (const float2*)(A.residue + pi.res_off + (size_t)c * (L ? ML : 128u)) + lane;
 #pragma unroll
@@ -823,17 +763,6 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
       const float2* src = (const float2*)(A.residue + pin.res_off + (size_t)c * ML) + lane;  // one 64-bit add, immediate offsets
 #pragma unroll
       for (int t = 0; t < 8; ++t) raw[t] = stream_load2(src + 64 * t);
-    } else {
-#ifdef VSYN_MIXED_PREFETCH
-      // Measured (config 4): the 16 registers this keeps live across the floor product, FFT and overlap do not exist in the 128-VGPR
-      // mixed path — 224 B/lane of scratch, kernel 0.068 -> 0.121 ms. Off; it needs a launch of its own at 3 waves per SIMD.
-      raw_ahead = has_next && nlng && !pin.bad;  // (this point is only reached by long blocks: short ones take fused_short_pass)
-      if (raw_ahead) {
-        const float2* src = (const float2*)(A.residue + pin.res_off + (size_t)c * ML) + lane;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) raw[t] = src[64 * t];
-      }
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);
 
@@ -855,17 +784,10 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
         posts = __builtin_amdgcn_readfirstlane(fc->posts);
         const uint8_t* bs = A.binseg + (size_t)f * ML;
 #pragma unroll
-#ifdef VSYN_BSEG_PACK
-        for (int t = 0; t < 8; t += 2) {
-          const uint32_t two0 = *(const uint16_t*)(bs + 2u * (lane + 64u * t)), two1 = *(const uint16_t*)(bs + 2u * (lane + 64u * (t + 1)));
-          bseg[t >> 1] = two0 | (two1 << 16);
-        }
-#else
         for (int t = 0; t < 8; ++t) {
           const uint32_t two = *(const uint16_t*)(bs + 2u * (lane + 64u * t));  // intervals of bins 2k, 2k+1 (k = lane + 64 t)
           bseg[t] = (seg_base + 8u * (two & 0xFFu)) | ((seg_base + 8u * (two >> 8)) << 16);
         }
-#endif
         const bool in = lane < posts;
         sidx = in ? fc->sorted_idx[lane] : 0u;
         xsl = in ? fc->xs_sorted[lane] : 0u;
@@ -920,14 +842,7 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int b = 4 * grp + i;
-#ifdef VSYN_BSEG_PACK
-          // four interval numbers per register (half the registers, one more VALU op per bin): the steady path alone then needs 122
-          // VGPRs instead of 126 — still above the 120 at which a 32-VGPR pre-kernel wave could co-reside; off
-          const uint32_t w4 = (b & 2) ? (bseg[b >> 2] >> 16) : bseg[b >> 2];
-          const uint32_t addr = seg_base + 8u * ((b & 1) ? ((w4 >> 8) & 0xFFu) : (w4 & 0xFFu));
-#else
           const uint32_t addr = (b & 1) ? (bseg[b >> 1] >> 16) : (bseg[b >> 1] & 0xFFFFu);  // one VALU op per bin
-#endif
           typedef float lds_vf2 __attribute__((ext_vector_type(2)));
           const lds_vf2 ev = *(const __attribute__((address_space(3))) lds_vf2*)(uintptr_t)addr;
           sgm[i] = f2(ev.x, ev.y);
@@ -975,15 +890,8 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
       STAMP(4);  // mirror exchange + pre-rotation
       if (ROLE != 0 && !(VSYN_KNOCKOUT & 1)) pair_wait(&partner_flags[1], it + 1);  // the partner has read this wave's image: the FFT may reuse it
       STAMP(5);  // second partner wait
-#ifdef VSYN_EXP_SETPRIO
-      __builtin_amdgcn_s_setprio(VSYN_EXP_SETPRIO);
-#endif
       if (!(VSYN_KNOCKOUT & 4)) fft512_wave(z, xb, &T, lane);
-#ifdef VSYN_EXP_SETPRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
       STAMP(6);  // FFT-512
-#ifndef VSYN_NO_MIXED_DMA
       if (MIXED) {
         // the image is free until the next packet's hand-off (the partner finished with it before the FFT): request the next long
         // block's rows into it now
@@ -995,7 +903,6 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
           dma_younger = 0;
         }
       }
-#endif
 #pragma unroll
       for (int k = 0; k < 8; ++k) z[k] = cmulf(z[k], T.post[k][lane]);
 
@@ -1079,11 +986,7 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
       // Everything this wave has in flight here is LOADS issued long ago (residue and coded row of packet q+1): finish them before
       // the PCM stores go out, so that no later wait in the loop (the compiler places the loop-carried copies of those registers
       // behind the stores, where only vmcnt(0) is safe on every path) ever waits for a store. The stores are never waited for.
-#ifndef VSYN_NO_MIXED_DMA
       if (!MIXED) vmem_drain();  // (mixed runs: the next block's rows are in flight on purpose; they are waited for by count)
-#else
-      vmem_drain();
-#endif
       STAMP(7);  // post-rotation, window reads, overlap arithmetic, mirror exchange of the outputs
       // sample s = 2*kappa + 128*j of (lane, kh = 4 + j): two lane pointers, every store at an immediate offset
       if (VSYN_KNOCKOUT & 8) {
@@ -1310,7 +1213,7 @@ static inline uint32_t fused_ok_mask(const ConstHeader& H, const uint8_t* host_c
   return mask;
 }
 
-static inline hipError_t fused_tables_create(const ConstHeader& H, const uint8_t* host_const, FusedTables* ft) {
+static inline hipError_t fused_tables_create(const ConstHeader& H, const uint8_t* host_const, FusedTables* ft, bool debug) {
   const uint32_t half = H.bs[1] / 2;
   std::vector<uint8_t> tab((size_t)H.num_floors * half);
   const FloorConst* fl = (const FloorConst*)(host_const + H.off_floor);
@@ -1385,7 +1288,7 @@ static inline hipError_t fused_tables_create(const ConstHeader& H, const uint8_t
   int blocks = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, vsyn_fused_kernel, FUSED_WAVES * 64, 0) == hipSuccess && blocks > 0)
     ft->waves_per_cu = blocks * FUSED_WAVES;
-  if (getenv("VSYN_DEBUG")) fprintf(stderr, "vsyn: fused kernel %d workgroups/CU -> %d waves/CU\n", blocks, ft->waves_per_cu);
+  if (debug) fprintf(stderr, "vsyn: fused kernel %d workgroups/CU -> %d waves/CU\n", blocks, ft->waves_per_cu);
   return hipSuccess;
 }
 
@@ -1399,26 +1302,23 @@ static inline void fused_tables_destroy(FusedTables* ft) {
 static inline const char* fused_kernel_name(const ConstHeader&) { return "vsyn_fused_kernel"; }
 static inline const char* fused_imdct_kernel_name(uint32_t) { return "vsyn_imdct_wave_kernel"; }
 
-// run length: as few runs as fill the chip once (halo overhead is 1/R), never below 4
-static inline uint32_t fused_pick_run_len(int waves_per_cu, uint32_t S, uint32_t channels, uint32_t max_seg_packets, int num_cus) {
-  const char* env = getenv("VSYN_RUN_LEN");
-  if (env && atoi(env) > 0) return (uint32_t)atoi(env);
+// run length: as few runs as fill the chip once (halo overhead is 1/R), never below 4; run_len != 0 overrides it (VSYN_RUN_LEN)
+static inline uint32_t fused_pick_run_len(uint32_t run_len, int waves_per_cu, uint32_t S, uint32_t channels, uint32_t max_seg_packets, int num_cus) {
+  if (run_len) return run_len;
   const uint64_t slots = (uint64_t)num_cus * (uint64_t)waves_per_cu;
   uint32_t R = 4;
   while (R < max_seg_packets && (uint64_t)S * channels * ((max_seg_packets + R - 1) / R) > slots) ++R;
   return R;
 }
 
-static inline hipError_t fused_launch(const ConstHeader& H, const FusedTables& ft, FusedArgs a, uint32_t max_seg_packets, hipStream_t s) {
-  const uint64_t units = (uint64_t)a.S * a.runs_per_seg * H.channels;  // a.runs_per_seg = ceil(max_seg_packets / R)
-  (void)max_seg_packets;
-  if (units == 0 || units > 0x7FFFFFF8ull) return hipErrorInvalidValue;
+// one wave per (run, channel); the caller keeps the unit count at or below FUSED_MAX_UNITS
+#define FUSED_MAX_UNITS 0x7FFFFFF8ull
+static inline hipError_t fused_launch(const ConstHeader& H, const FusedTables& ft, FusedArgs a, hipStream_t s) {
+  const uint64_t units = (uint64_t)a.S * a.runs_per_seg * H.channels;
   dim3 grid((uint32_t)((units + FUSED_WAVES - 1) / FUSED_WAVES));
-  const char* xl = getenv("VSYN_EXTRA_LDS");  // experiment knob: extra dynamic LDS lowers the occupancy
-  const size_t dyn = xl ? (size_t)atoi(xl) : 0;
   a.coupling_mode = (uint32_t)ft.coupling_mode;
-  if (a.curve) vsyn_fused_tap_kernel<<<grid, FUSED_WAVES * 64, dyn, s>>>(a);
-  else vsyn_fused_kernel<<<grid, FUSED_WAVES * 64, dyn, s>>>(a);
+  if (a.curve) vsyn_fused_tap_kernel<<<grid, FUSED_WAVES * 64, 0, s>>>(a);
+  else vsyn_fused_kernel<<<grid, FUSED_WAVES * 64, 0, s>>>(a);
   return hipGetLastError();
 }
 

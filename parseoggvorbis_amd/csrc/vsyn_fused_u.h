@@ -1176,7 +1176,7 @@ static inline void u_fill_big(const ConstHeader& H, const uint8_t* host_const, U
     for (uint32_t c = 0; c < 8; ++c) F.tw2[a][c] = tw[((8 * c * a) & 511u) * NS];  // W64^(c a)
 }
 
-static inline hipError_t u_tables_create(const ConstHeader& H, const uint8_t* host_const, UTables* ut) {
+static inline hipError_t u_tables_create(const ConstHeader& H, const uint8_t* host_const, UTables* ut, bool debug) {
   const uint32_t ns = H.bs[1] > 2048 ? H.bs[1] / 2048 : 1;
   const uint32_t img_bytes = (uint32_t)((sizeof(ULdsImage) + 15u) & ~15u);
   const uint32_t big_bytes = ns == 2 ? (uint32_t)sizeof(UBig<2>) : (ns == 4 ? (uint32_t)sizeof(UBig<4>) : 0u);
@@ -1212,7 +1212,7 @@ static inline hipError_t u_tables_create(const ConstHeader& H, const uint8_t* ho
     const void* kft = ns == 1 ? (const void*)vsyn_fused_u_tap_kernel<1> : (ns == 2 ? (const void*)vsyn_fused_u_tap_kernel<2> : (const void*)vsyn_fused_u_tap_kernel<4>);
     e = hipFuncSetAttribute(kft, hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget);
   }
-  if (e != hipSuccess && getenv("VSYN_DEBUG"))
+  if (e != hipSuccess && debug)
     fprintf(stderr, "vsyn: hipFuncSetAttribute(%u B dynamic LDS) failed: %s\n", budget, hipGetErrorString(e));
   return e == hipSuccess ? hipSuccess : hipErrorInvalidValue;
 }
@@ -1222,9 +1222,10 @@ static inline void u_tables_destroy(UTables* ut) {
   ut->d_img = nullptr;
 }
 
+// one wave per (run, channel); the caller keeps the unit count at or below U_MAX_UNITS
+#define U_MAX_UNITS 0x7FFFFFF0ull
 static inline hipError_t u_launch(const ConstHeader& H, const UTables& ut, const FusedArgs& a, hipStream_t s) {
   const uint64_t units = (uint64_t)a.S * a.runs_per_seg * H.channels;
-  if (units == 0 || units > 0x7FFFFFF0ull) return hipErrorInvalidValue;
   UArgs u;
   u.f = a;
   u.img = ut.d_img;

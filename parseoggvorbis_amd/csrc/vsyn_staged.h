@@ -550,7 +550,6 @@ vsyn_floor_unwrap_kernel(const uint8_t* __restrict__ cb, uint32_t P, const uint3
     const bool fc_uniform = __all(fc_bits == fc_first);
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     typedef const __attribute__((address_space(4))) u32x4* const_pk;
-#ifndef VSYN_NO_UNWRAP_REGS
     // Up to 32 posts (every floor libvorbis writes for the common modes): the row lives in a per-thread register array
     // indexed by the wave-uniform neighbour indices (s_set_gpr_idx / v_movrel), so the serial chain over the posts is a
     // few dozen VALU cycles per post instead of three dependent LDS round trips. 32 is where the compiler still keeps the
@@ -613,7 +612,6 @@ vsyn_floor_unwrap_kernel(const uint8_t* __restrict__ cb, uint32_t P, const uint3
       }
       continue;
     }
-#endif
     {  // whole coded row up front (16-byte loads; rows are 8-byte aligned multiples of 4 posts), values parked in LDS
       const uint2* in8 = (const uint2*)(ys + (size_t)gid * stride);
       for (uint32_t j = 0; j * 4 < posts; ++j) {

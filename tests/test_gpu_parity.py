@@ -547,6 +547,43 @@ def test_submit_flags_may_alternate_between_submits():
             at += n
 
 
+def test_reset_orders_the_next_hidden_preparation():
+    """vsyn_reset_streams on the caller's stream between two submits whose chained pre-kernels run hidden on the internal stream
+    (HIDDEN_PRE), with delayed work queued in front of the reset. The second batch's segments do not set VSYN_SEG_RESET: it relies on the
+    reset alone, so its preparation has to wait for the memset — neither read the first batch's stream state nor have its record wiped."""
+    import torch
+    spec = fixture_like_spec(2)
+    S, ppk = 4, 24
+    gpu = binding.Synth(spec, max_streams=S)
+    stream = torch.cuda.current_stream().cuda_stream
+    busy = torch.zeros(64 << 20, device="cuda")
+    batches, keep = [], []
+    for i in range(2):
+        b = synth_batch(spec, S, ppk, "mixed", seed=40 + i)
+        if i == 1:
+            b["segments"]["flags"] = 0
+        d = dict(pk=torch.from_numpy(b["packets"].view(np.uint8)).cuda(), seg=torch.from_numpy(b["segments"].view(np.uint8)).cuda(),
+                 ys=torch.from_numpy(b["ys"].astype(np.int16)).cuda(), res=torch.from_numpy(b["residue"]).cuda(),
+                 pcm=torch.zeros((S, 2, b["plane_stride"]), device="cuda"), emit=torch.zeros(S * ppk, dtype=torch.int32, device="cuda"))
+        batches.append(b)
+        keep.append(d)
+    torch.cuda.synchronize()
+    for i, (b, d) in enumerate(zip(batches, keep)):
+        if i == 1:
+            for _ in range(4):
+                busy.add_(1.0)  # delayed work in front of the reset on the caller's stream
+            gpu.reset(stream)
+        gpu.submit_device(S * ppk, d["pk"].data_ptr(), S, d["seg"].data_ptr(), ppk, d["ys"].data_ptr(), d["res"].data_ptr(),
+                          d["pcm"].data_ptr(), b["plane_stride"], d["emit"].data_ptr(), None, HIDDEN_PRE, stream)
+    fl, bad = gpu.sync_status(stream)
+    assert fl == 0, (fl, bad)
+    b, d = batches[1], keep[1]
+    want = ob.OracleSynth(spec, S).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
+    assert want["rc"] == 0
+    assert np.array_equal(d["emit"].cpu().numpy().astype(np.uint32), want["emit_len"])
+    assert np.abs(d["pcm"].cpu().numpy() - want["pcm"]).max() < TOL * max(1.0, float(np.abs(want["pcm"]).max()))
+
+
 MULTI = [
     # C, bs0, bs1, couplings
     (6, 128, 1024, [(0, 1), (0, 2), (3, 4)]),   # 5.1-style: three steps, channel 0 in two of them (order matters)
