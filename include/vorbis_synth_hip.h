@@ -177,7 +177,10 @@ uint32_t vsyn_fused_paths(const vsyn_handle* h);
 size_t vsyn_const_block_bytes(const vsyn_handle* h);
 
 /* All pointers are DEVICE pointers on the handle's device; asynchronous on hip_stream (a hipStream_t, NULL = default stream).
- * max_seg_packets >= every segment's num_packets. Errors found on the device are reported by vsyn_sync_status. */
+ * max_seg_packets >= every segment's num_packets (0 = num_packets); a longer segment gets no rows and raises VSYN_ST_BAD_SEGMENT.
+ * Errors found on the device are reported by vsyn_sync_status. The features entry points of one handle share its feature
+ * workspace and its status word (with the synthesis submits): issue them on one stream, or serialise them; vsyn_sync_status and
+ * vsyn_features_host return every flag raised on the handle since the last read. */
 int vsyn_submit_device(vsyn_handle* h,
                        uint32_t num_packets, const vsyn_packet* d_packets,
                        uint32_t num_segments, const vsyn_segment* d_segments, uint32_t max_seg_packets,
@@ -321,6 +324,97 @@ int vsyn_profile_read(vsyn_handle* h, double* mean_ms, uint32_t* launches, const
 /* IMDCT-only entry (BASELINE config 2): in [count][n/2] -> out [count][n], device pointers, n = blocksize0 or blocksize1. */
 int vsyn_imdct_device(vsyn_handle* h, uint32_t n, uint32_t count, const float* d_in, float* d_out,
                       void* hip_stream, const char** err);
+
+/* ---- feature matrices: the reference's RETURNN features without synthesising PCM ----
+ *
+ * What returnn_import.py:74-115 (get_features_from_raw_bytes) computes: demo_live_extract.py read_floor_ys (262-416) and
+ * read_residue_ys (418-505) applied to the decoder's hook stream, filtered by name as returnn_import.py:84-113 does. One
+ * float32 row of output_dim columns per hook that makes a row, rows in hook order. The reference's quirks are the contract:
+ *
+ *  - Hook order per packet (hpp:1160-1211): for every channel c, "floor_number"; if c's floor is used (vsyn_packet.floor_used
+ *    bit c, before the nonzero propagate), "floor1 final_ys" (hpp:560) and "floor1 floor" (hpp:585). After all channels,
+ *    "after_residue" for EVERY channel, used floor or not. "floor1 final_ys" holds the posts BEFORE the multiplier (the
+ *    reader multiplies); "floor1 floor" has n entries, its second half flat.
+ *  - biggest floor = the first floor with the most posts.
+ *  - Floor kinds: one row per (packet, channel) with a used floor, in that order; with VSYN_FEAT_ONLY_BIGGEST_FLOOR only for
+ *    channels whose floor is the biggest (the floor-number column is then off). Column 0 (VSYN_FEAT_INCLUDE_FLOOR_NUMBER) is
+ *    (f + 1) / num_floors - 0.5 computed in double and rounded to float. Values: v / 255 (VSYN_FEAT_FLOOR_ALWAYS_POSITIVE) or
+ *    (v - 127.5) / 127.5 in float32, v = final_y * multiplier resp. the rendered curve gathered at xs; columns past the
+ *    data are 0.
+ *  - The rendered kind's xs: the floor's own xs (header order, ascending with VSYN_FEAT_SORTED_XS); with upscale_xs_factor
+ *    != 1 those xs through scipy.ndimage.zoom(order=1, mode="nearest") and numpy.round (restated on the host; a factor whose
+ *    output length is not len(xs) * factor fails like the reference's assert); with VSYN_FEAT_XS_FROM_BIGGEST_FLOOR the
+ *    biggest floor's (upscaled) xs, for another floor f floor-divided by factor = round(max xs_big / max xs_f) (Python's
+ *    round; 0 gives 0, as numpy does) and clipped to [0, n-1]. An unclipped index past the n entries fails the batch with
+ *    VSYN_ST_FEATURE_INDEX (the reference raises IndexError), whether or not its column is kept.
+ *  - Residue kinds: the reader's floor number at "after_residue" time is the LAST channel's: a packet gives one row per
+ *    channel (zeros for channels without residue) exactly when channel C-1's floor is the biggest. Row = after_residue
+ *    gathered at clip(xs_big[:output_dim], 0, n/2-1) (VSYN_FEAT_IGNORE_XS: bins 0..min(n/2, output_dim)-1); without
+ *    VSYN_FEAT_IGNORE_XS an output_dim below the biggest floor's post count is refused (the reference asserts,
+ *    demo_live_extract.py:484-485). VSYN_FEAT_RESIDUE_YS_WITH_FLOOR: floor_base = the most recent biggest-floor "floor1
+ *    floor" of the segment (carried over packets without one; none before the first) gathered the same way at clip(., 0, n-1)
+ *    and divided by 255; float32 order: log1p(|x|) (VSYN_FEAT_LOG1P_ABS_SPACE), then + floor_base * floor_base_factor resp.
+ *    * exp((floor_base - 1) * floor_base_factor) (log1p, exp rounded once from double), then * scale, then clip to +-clip_abs_max (VSYN_FEAT_CLIP). With
+ *    VSYN_FEAT_IGNORE_XS a floor_base whose length differs from the row's fails with VSYN_ST_FEATURE_INDEX (numpy cannot
+ *    broadcast them).
+ *  - The reference's floor_final_ys_rendered_concat_residue (scipy zoom order 3) is not provided.
+ *  - A segment is a whole stream from its first audio packet: nothing carries across calls, and the features entry points
+ *    neither read nor write the handle's overlap state or the PCM of the most recent submit. The checks are those of the
+ *    reference that concern floors and packets: VSYN_ST_FLOOR_RANGE, VSYN_ST_FLOOR_VALUE (any of the n floor entries >= 256),
+ *    VSYN_ST_BAD_MODE, VSYN_ST_BAD_SEGMENT, plus VSYN_ST_FEATURE_INDEX; a flagged batch's rows are unspecified.
+ */
+#define VSYN_ST_FEATURE_INDEX (1u << 8) /* feature entry points: a gather index past its vector, or floor_base / row lengths differ */
+
+enum {
+  VSYN_FEAT_FLOOR_FINAL_YS = 1,          /* kind "floor_final_ys" */
+  VSYN_FEAT_FLOOR_FINAL_YS_RENDERED = 2, /* kind "floor_final_ys_rendered" */
+  VSYN_FEAT_RESIDUE_YS = 3,              /* kind "residue_ys" */
+  VSYN_FEAT_RESIDUE_YS_WITH_FLOOR = 4    /* kind "residue_ys_with_floor" */
+};
+/* vsyn_feature_spec.options */
+#define VSYN_FEAT_INCLUDE_FLOOR_NUMBER 1u   /* floor kinds */
+#define VSYN_FEAT_ONLY_BIGGEST_FLOOR 2u     /* floor kinds; excludes VSYN_FEAT_INCLUDE_FLOOR_NUMBER */
+#define VSYN_FEAT_SORTED_XS 4u              /* all kinds */
+#define VSYN_FEAT_XS_FROM_BIGGEST_FLOOR 8u  /* floor kinds */
+#define VSYN_FEAT_FLOOR_ALWAYS_POSITIVE 16u /* floor kinds */
+#define VSYN_FEAT_LOG1P_ABS_SPACE 32u       /* residue kinds */
+#define VSYN_FEAT_IGNORE_XS 64u             /* residue kinds */
+#define VSYN_FEAT_CLIP 128u                 /* residue kinds: clip_abs_max is set and > 0 */
+
+typedef struct vsyn_feature_spec {
+  uint32_t kind;               /* VSYN_FEAT_* kind */
+  uint32_t output_dim;         /* columns per row, >= 1 */
+  uint32_t options;            /* VSYN_FEAT_* option bits */
+  uint32_t reserved0;
+  double upscale_xs_factor;    /* rendered kind: 1 = off */
+  float scale;                 /* residue kinds: 1 = off */
+  float clip_abs_max;          /* residue kinds, with VSYN_FEAT_CLIP */
+  float floor_base_factor;     /* residue_ys_with_floor: 1 = the reference's default */
+  uint32_t reserved1;
+} vsyn_feature_spec;
+
+/* Device pointers, asynchronous on hip_stream. vsyn_feature_rows_device writes d_seg_row_off[S+1] (uint64): segment g's rows
+ * are [d_seg_row_off[g], d_seg_row_off[g+1]). vsyn_features_device computes the same offsets (d_seg_row_off may be NULL) and
+ * writes the rows, d_rows[d_seg_row_off[S]][output_dim]; d_residue may be NULL for the floor kinds. No IMDCT, no PCM.
+ * max_seg_packets >= every segment's num_packets. Errors found on the device are reported by vsyn_sync_status. */
+int vsyn_feature_rows_device(vsyn_handle* h, const vsyn_feature_spec* spec,
+                             uint32_t num_packets, const vsyn_packet* d_packets,
+                             uint32_t num_segments, const vsyn_segment* d_segments, uint32_t max_seg_packets,
+                             uint64_t* d_seg_row_off, void* hip_stream, const char** err);
+int vsyn_features_device(vsyn_handle* h, const vsyn_feature_spec* spec,
+                         uint32_t num_packets, const vsyn_packet* d_packets,
+                         uint32_t num_segments, const vsyn_segment* d_segments, uint32_t max_seg_packets,
+                         const uint16_t* d_ys, const float* d_residue,
+                         float* d_rows, uint64_t* d_seg_row_off, void* hip_stream, const char** err);
+/* HOST pointers: stages, runs, copies back, synchronises. seg_rows[S] receives each segment's row count; rows (may be NULL
+ * when only the counts are wanted) receives the rows of all segments back to back, at most rows_capacity rows (num_packets *
+ * channels always suffices; VSYN_ERR_INVALID with the counts filled if it is too small). VSYN_ERR_STREAM if flagged. */
+int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec,
+                       uint32_t num_packets, const vsyn_packet* packets,
+                       uint32_t num_segments, const vsyn_segment* segments,
+                       const uint16_t* ys, const float* residue, size_t residue_floats,
+                       float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                       vsyn_status* status, const char** err);
 
 #ifdef __cplusplus
 }

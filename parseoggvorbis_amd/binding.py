@@ -54,6 +54,12 @@ class Taps(C.Structure):
                 ("floor_curve", C.c_void_p)]
 
 
+class FeatureSpec(C.Structure):  # vsyn_feature_spec
+    _fields_ = [("kind", C.c_uint32), ("output_dim", C.c_uint32), ("options", C.c_uint32), ("reserved0", C.c_uint32),
+                ("upscale_xs_factor", C.c_double), ("scale", C.c_float), ("clip_abs_max", C.c_float),
+                ("floor_base_factor", C.c_float), ("reserved1", C.c_uint32)]
+
+
 class Status(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("first_bad_packet", C.c_uint32)]
 
@@ -177,6 +183,7 @@ _SYMBOLS = [
     "vsyn_const_block_bytes", "vsyn_submit_device", "vsyn_submit_host", "vsyn_sync_status", "vsyn_reset_streams",
     "vsyn_profile_enable", "vsyn_profile_read", "vsyn_imdct_device", "vsyn_host_alloc", "vsyn_host_free",
     "vsyn_attach_vq", "vsyn_submit_device_vq", "vsyn_submit_host_vq", "vsyn_pcm_interleave_device", "vsyn_pcm_abs_sum_host", "vsyn_pcm_fetch_host",
+    "vsyn_feature_rows_device", "vsyn_features_device", "vsyn_features_host",
 ]
 
 
@@ -232,6 +239,10 @@ def load():
     lib.vsyn_pcm_interleave_device.argtypes = [vp, C.c_int, vp, u64, vp, u64, vp, vp, cpp]
     lib.vsyn_pcm_abs_sum_host.argtypes = [vp, C.POINTER(C.c_double), cpp]
     lib.vsyn_pcm_fetch_host.argtypes = [vp, C.c_int, vp, u64, vp, cpp]
+    lib.vsyn_feature_rows_device.argtypes = [vp, C.POINTER(FeatureSpec), u32, vp, u32, vp, u32, vp, vp, cpp]
+    lib.vsyn_features_device.argtypes = [vp, C.POINTER(FeatureSpec), u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_features_host.argtypes = [vp, C.POINTER(FeatureSpec), u32, vp, u32, vp, vp, vp, C.c_size_t, vp, u64, vp,
+                                       C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -306,6 +317,26 @@ class Synth:
         if rc not in (VSYN_OK, VSYN_ERR_STREAM):
             raise VsynError(rc, (err.value or b"").decode())
         return dict(rc=rc, pcm=pcm, emit_len=emit, taps=taps, flags=st.flags, first_bad=st.first_bad_packet)
+
+    def features_host(self, spec, packets, segments, ys, residue=None):
+        """vsyn_features_host with a FeatureSpec: returns dict(rc, rows [total][output_dim], seg_rows [S], flags, first_bad)."""
+        P, S, Cn = len(packets), len(segments), self.channels
+        packets = np.ascontiguousarray(packets, dtype=PACKET_DTYPE)
+        segments = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+        ys = np.ascontiguousarray(ys, dtype=np.uint16)
+        assert ys.size == P * Cn * self.ys_stride
+        if residue is not None:
+            residue = np.ascontiguousarray(residue, dtype=np.float32)
+        rows = np.zeros((max(1, P * Cn), spec.output_dim), np.float32)
+        seg_rows = np.zeros(max(1, S), np.uint64)
+        st, err = Status(), C.c_char_p()
+        rc = self.lib.vsyn_features_host(self.h, C.byref(spec), P, _ptr(packets), S, _ptr(segments), _ptr(ys), _ptr(residue),
+                                         0 if residue is None else residue.size, _ptr(rows), rows.shape[0], _ptr(seg_rows),
+                                         C.byref(st), C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum()) if rc == VSYN_OK else 0
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], flags=st.flags, first_bad=st.first_bad_packet)
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

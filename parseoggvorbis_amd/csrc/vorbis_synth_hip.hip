@@ -25,6 +25,7 @@
 #include "vsyn_fused_u.h"
 #include "vsyn_vq.h"
 #include "vsyn_pcm.h"
+#include "vsyn_features.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846264338327
@@ -176,6 +177,22 @@ struct vsyn_handle {
   DevBuf<uint8_t> st_conv;             // vsyn_pcm_fetch_host: interleaved output
   DevBuf<uint32_t> st_frames;
   uint64_t last_host_plane = 0;        // plane_stride of the most recent vsyn_submit_host* (0: none yet)
+  // feature matrices (vsyn_features.h): buffers of their own, so that a features call leaves every synthesis buffer alone
+  DevBuf<PktInfo> ft_info;
+  DevBuf<uint16_t> ft_fy;
+  DevBuf<uint32_t> ft_rowrel;
+  DevBuf<int32_t> ft_fbsrc;
+  DevBuf<uint8_t> ft_fbch;
+  DevBuf<uint64_t> ft_resoff, ft_segrows, ft_segoff;
+  DevBuf<uint8_t> ft_tab;
+  uint8_t* ft_tab_host = nullptr;      // page-locked copy of the gather table (the upload is asynchronous)
+  size_t ft_tab_host_cap = 0;
+  hipEvent_t ft_ev = nullptr;          // recorded behind the table upload: the host copy is reused only after it
+  bool ft_ev_valid = false;
+  DevBuf<vsyn_packet> fs_pk;           // vsyn_features_host staging
+  DevBuf<vsyn_segment> fs_seg;
+  DevBuf<uint16_t> fs_ys;
+  DevBuf<float> fs_res, fs_rows;
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -540,6 +557,8 @@ void vsyn_destroy(vsyn_handle* h) {
 #endif
   fused_tables_destroy(&h->fused);
   u_tables_destroy(&h->utab);
+  if (h->ft_ev) (void)hipEventDestroy(h->ft_ev);
+  if (h->ft_tab_host) (void)hipHostFree(h->ft_tab_host);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->pre) (void)hipStreamDestroy(h->pre);
   if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
@@ -1216,6 +1235,287 @@ int vsyn_imdct_device(vsyn_handle* h, uint32_t n, uint32_t count, const float* d
   }
   HIPCHK(profile_end(h, s));
   HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// feature matrices (vsyn_features.h; semantics in the header)
+// ------------------------------------------------------------------------------------------------
+// scipy.ndimage.zoom(xs as float32, z, order=1, mode="nearest") followed by numpy.round: output length round(L * z) (Python's round);
+// input coordinate k * (L - 1) / (out - 1) in double, clamped to [0, L - 1]; linear weights (1 - t, t) summed in double from 0 in
+// that order; the float32 result rounded half to even. False where the reference's assert (length == L * z) fails.
+static bool feat_zoom_round(const std::vector<uint32_t>& xs, double z, std::vector<uint32_t>& out) {
+  const size_t L = xs.size();
+  const double want = (double)L * z;
+  const double outn_d = nearbyint(want);
+  if (outn_d != want || outn_d < 1.0 || outn_d > 1e6) return false;
+  const size_t outn = (size_t)outn_d;
+  const double zf = outn > 1 ? (double)(L - 1) / (double)(outn - 1) : 1.0;
+  out.resize(outn);
+  for (size_t k = 0; k < outn; ++k) {
+    double cc = (double)k * zf;
+    cc = std::min(std::max(cc, 0.0), (double)(L - 1));
+    const double fl = floor(cc), t = cc - fl;
+    const size_t i0 = (size_t)fl, i1 = std::min(i0 + 1, L - 1);
+    double v = 0.0 + (1.0 - t) * (double)(float)xs[i0];
+    v = v + t * (double)(float)xs[i1];
+    const float r = nearbyintf((float)v);
+    out[k] = r <= 0.f ? 0u : (uint32_t)r;
+  }
+  return true;
+}
+
+// Validates the spec against the handle's setup and builds the gather table (FeatHeader, FeatFloor[], indices).
+static int feat_build_table(const vsyn_handle* h, const vsyn_feature_spec* sp, std::vector<uint8_t>& out, const char** err) {
+  if (!sp) return fail(err, VSYN_ERR_INVALID, "feature spec is NULL");
+  const bool floor_kind = sp->kind == VSYN_FEAT_FLOOR_FINAL_YS || sp->kind == VSYN_FEAT_FLOOR_FINAL_YS_RENDERED;
+  const bool res_kind = sp->kind == VSYN_FEAT_RESIDUE_YS || sp->kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
+  if (!floor_kind && !res_kind) return fail(err, VSYN_ERR_INVALID, "unknown feature kind %u", sp->kind);
+  if (sp->output_dim == 0 || sp->output_dim > (1u << 20)) return fail(err, VSYN_ERR_INVALID, "output_dim %u out of range", sp->output_dim);
+  const uint32_t floor_opts = VSYN_FEAT_INCLUDE_FLOOR_NUMBER | VSYN_FEAT_ONLY_BIGGEST_FLOOR | VSYN_FEAT_SORTED_XS | VSYN_FEAT_XS_FROM_BIGGEST_FLOOR |
+                              VSYN_FEAT_FLOOR_ALWAYS_POSITIVE;
+  const uint32_t res_opts = VSYN_FEAT_SORTED_XS | VSYN_FEAT_LOG1P_ABS_SPACE | VSYN_FEAT_IGNORE_XS | VSYN_FEAT_CLIP;
+  if (sp->options & ~(floor_kind ? floor_opts : res_opts)) return fail(err, VSYN_ERR_INVALID, "feature options 0x%x do not apply to kind %u", sp->options, sp->kind);
+  if ((sp->options & VSYN_FEAT_ONLY_BIGGEST_FLOOR) && (sp->options & VSYN_FEAT_INCLUDE_FLOOR_NUMBER))
+    return fail(err, VSYN_ERR_INVALID, "only_biggest_floor excludes include_floor_number");
+  if (res_kind && sp->upscale_xs_factor != 1.0) return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor applies to the floor kinds only");
+  if (!(sp->upscale_xs_factor > 0.0)) return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor must be > 0");
+  const ConstHeader& H = h->H;
+  const FloorConst* fcs = (const FloorConst*)(h->host_const.data() + H.off_floor);
+  const uint32_t F = H.num_floors, D = sp->output_dim;
+  uint32_t big = 0;
+  for (uint32_t f = 1; f < F; ++f)
+    if (fcs[f].posts > fcs[big].posts) big = f;  // the first of the largest (Python's max)
+  const bool sorted = (sp->options & VSYN_FEAT_SORTED_XS) != 0;
+  std::vector<std::vector<uint32_t>> xs(F), up(F);
+  for (uint32_t f = 0; f < F; ++f) {
+    xs[f].assign(fcs[f].xs, fcs[f].xs + fcs[f].posts);
+    if (sorted) std::sort(xs[f].begin(), xs[f].end());
+    if (floor_kind && sp->upscale_xs_factor != 1.0) {
+      if (!feat_zoom_round(xs[f], sp->upscale_xs_factor, up[f]))
+        return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor %g: floor %u's %u posts do not zoom to a whole length (the reference asserts)",
+                    sp->upscale_xs_factor, f, fcs[f].posts);
+    } else {
+      up[f] = xs[f];
+    }
+  }
+  if (res_kind && !(sp->options & VSYN_FEAT_IGNORE_XS) && D < fcs[big].posts)
+    return fail(err, VSYN_ERR_INVALID, "output_dim %u is below the biggest floor's %u posts: the reference asserts on such rows (use ignore_xs)", D,
+                fcs[big].posts);
+  FeatHeader T = {};
+  T.kind = sp->kind;
+  T.dim = D;
+  T.opts = sp->options;
+  T.big = big;
+  T.num_floors = F;
+  T.scale = sp->scale;
+  T.clip = sp->clip_abs_max;
+  T.fbf = sp->floor_base_factor;
+  std::vector<FeatFloor> ff(F);
+  std::vector<uint32_t> idx;
+  const uint32_t o = (sp->options & VSYN_FEAT_INCLUDE_FLOOR_NUMBER) ? 1u : 0u;
+  for (uint32_t f = 0; f < F; ++f) {
+    std::vector<uint32_t> l;
+    FeatFloor& e = ff[f];
+    e.fnum = (float)(((double)f + 1.0) / (double)F - 0.5);
+    if (sp->options & VSYN_FEAT_XS_FROM_BIGGEST_FLOOR) {
+      l = up[big];
+      if (f != big) {
+        const double mb = (double)*std::max_element(xs[big].begin(), xs[big].end());
+        const double mc = (double)*std::max_element(xs[f].begin(), xs[f].end());
+        const double factor = nearbyint(mb / mc);  // Python's round() of the ratio (mc == 0: inf, no usable floor)
+        for (uint32_t& v : l) v = (factor >= 1.0 && factor < 4294967296.0) ? (uint32_t)(v / (uint64_t)factor) : 0u;  // numpy: x // 0 == 0
+      }
+      e.clip = 1;
+    }
+    else l = up[f];
+    e.maxidx = l.empty() ? 0u : *std::max_element(l.begin(), l.end());
+    e.cnt = D > o ? (uint32_t)std::min<size_t>(l.size(), D - o) : 0u;
+    e.off = (uint32_t)idx.size();
+    idx.insert(idx.end(), l.begin(), l.begin() + e.cnt);
+  }
+  T.res_off = (uint32_t)idx.size();
+  T.res_cnt = std::min<uint32_t>(fcs[big].posts, D);
+  idx.insert(idx.end(), xs[big].begin(), xs[big].begin() + T.res_cnt);
+  out.resize(sizeof(FeatHeader) + sizeof(FeatFloor) * F + sizeof(uint32_t) * (idx.size() + 1));
+  memcpy(out.data(), &T, sizeof(T));
+  memcpy(out.data() + sizeof(T), ff.data(), sizeof(FeatFloor) * F);
+  memcpy(out.data() + sizeof(T) + sizeof(FeatFloor) * F, idx.data(), sizeof(uint32_t) * idx.size());
+  return VSYN_OK;
+}
+
+// The count / offsets kernels (and, with rows != nullptr, the floor unwrap and the rows kernel) on stream s. Caller holds h->mu.
+static int feat_launch(vsyn_handle* h, const vsyn_feature_spec* sp, uint32_t P, const vsyn_packet* d_pk, uint32_t S, const vsyn_segment* d_seg,
+                       uint32_t max_seg, const uint16_t* d_ys, const float* d_res, float* d_rows, uint64_t* d_segoff, hipStream_t s,
+                       const char** err) {
+  std::vector<uint8_t> tab;
+  int rc = feat_build_table(h, sp, tab, err);
+  if (rc) return rc;
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (max_seg == 0 || max_seg > P) max_seg = P;
+  const ConstHeader& H = h->H;
+  const uint32_t C = H.channels;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(h->ft_info.ensure(P));
+  HIPCHK(h->ft_fy.ensure((size_t)P * C * H.ys_stride));
+  HIPCHK(h->ft_rowrel.ensure(P));
+  HIPCHK(h->ft_fbsrc.ensure(P));
+  HIPCHK(h->ft_fbch.ensure(P));
+  HIPCHK(h->ft_resoff.ensure(P));
+  HIPCHK(h->ft_segrows.ensure(S));
+  HIPCHK(h->ft_segoff.ensure((size_t)S + 1));
+  HIPCHK(h->ft_tab.ensure(tab.size()));
+  if (!h->ft_ev) HIPCHK(hipEventCreateWithFlags(&h->ft_ev, hipEventDisableTiming));
+  if (h->ft_ev_valid) HIPCHK(hipEventSynchronize(h->ft_ev));  // the previous upload has read the host copy
+  if (h->ft_tab_host_cap < tab.size()) {
+    if (h->ft_tab_host) HIPCHK(hipHostFree(h->ft_tab_host));
+    h->ft_tab_host = nullptr;
+    h->ft_tab_host_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&h->ft_tab_host, tab.size() + 4096, hipHostMallocDefault));
+    h->ft_tab_host_cap = tab.size() + 4096;
+  }
+  memcpy(h->ft_tab_host, tab.data(), tab.size());
+  HIPCHK(hipMemcpyAsync(h->ft_tab.p, h->ft_tab_host, tab.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(h->ft_ev, s));
+  h->ft_ev_valid = true;
+  if (P) HIPCHK(hipMemsetAsync(h->ft_info.p, 0, sizeof(PktInfo) * P, s));  // packets outside every segment: no floor rows to unwrap
+  FeatCtx A;
+  A.cb = h->d_const;
+  A.tab = h->ft_tab.p;
+  A.pk = d_pk;
+  A.seg = d_seg;
+  A.fy = h->ft_fy.p;
+  A.res = d_res;
+  A.info = h->ft_info.p;
+  A.rowrel = h->ft_rowrel.p;
+  A.fbsrc = h->ft_fbsrc.p;
+  A.fbch = h->ft_fbch.p;
+  A.resoff = h->ft_resoff.p;
+  A.segrows = h->ft_segrows.p;
+  A.segoff = d_segoff ? d_segoff : h->ft_segoff.p;
+  A.rows = d_rows;
+  A.status = h->d_status;
+  A.P = P;
+  A.S = S;
+  A.max_seg = max_seg;
+  hipLaunchKernelGGL(vsyn_feat_count_kernel, dim3(S), dim3(FEAT_THREADS), 0, s, A);
+  hipLaunchKernelGGL(vsyn_feat_offsets_kernel, dim3(1), dim3(FEAT_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  if (!d_rows || P == 0 || max_seg == 0) return VSYN_OK;  // (no packet: every segment is empty or flagged by the count kernel)
+  const uint32_t rows = P * C;
+  hipLaunchKernelGGL(vsyn_floor_unwrap_kernel, dim3(std::min<uint32_t>((rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, 65535u)), dim3(UNWRAP_THREADS), 0, s,
+                     h->d_const, P, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const PktInfo*)h->ft_info.p, d_ys, h->ft_fy.p, h->d_status);
+  const uint64_t slots = (uint64_t)max_seg * C;
+  const uint64_t gx = (slots + FEAT_ROW_WAVES - 1) / FEAT_ROW_WAVES;
+  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  hipLaunchKernelGGL(vsyn_feat_rows_kernel, dim3((uint32_t)gx, S), dim3(FEAT_ROW_WAVES * 64), 0, s, A);
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}
+
+extern "C" {
+
+int vsyn_feature_rows_device(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P, const vsyn_packet* d_packets, uint32_t S,
+                             const vsyn_segment* d_segments, uint32_t max_seg_packets, uint64_t* d_seg_row_off, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (!d_seg_row_off) return fail(err, VSYN_ERR_INVALID, "d_seg_row_off is NULL");
+  if (S == 0) return VSYN_OK;
+  if ((P && !d_packets) || !d_segments) return fail(err, VSYN_ERR_INVALID, "NULL batch pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return feat_launch(h, spec, P, d_packets, S, d_segments, max_seg_packets, nullptr, nullptr, nullptr, d_seg_row_off, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_features_device(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P, const vsyn_packet* d_packets, uint32_t S,
+                         const vsyn_segment* d_segments, uint32_t max_seg_packets, const uint16_t* d_ys, const float* d_residue, float* d_rows,
+                         uint64_t* d_seg_row_off, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (!spec) return fail(err, VSYN_ERR_INVALID, "feature spec is NULL");
+  if (S == 0) return VSYN_OK;
+  const bool res_kind = spec->kind == VSYN_FEAT_RESIDUE_YS || spec->kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
+  if (!d_segments || (P && (!d_packets || !d_ys || !d_rows || (res_kind && !d_residue)))) return fail(err, VSYN_ERR_INVALID, "NULL batch pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return feat_launch(h, spec, P, d_packets, S, d_segments, max_seg_packets, d_ys, d_residue, d_rows, d_seg_row_off, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P, const vsyn_packet* packets, uint32_t S, const vsyn_segment* segments,
+                       const uint16_t* ys, const float* residue, size_t residue_floats, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                       vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (status) {
+    status->flags = 0;
+    status->first_bad_packet = 0xFFFFFFFFu;
+  }
+  if (!spec) return fail(err, VSYN_ERR_INVALID, "feature spec is NULL");
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  if (P == 0 || S == 0) return VSYN_OK;
+  const bool res_kind = spec->kind == VSYN_FEAT_RESIDUE_YS || spec->kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
+  if (!packets || !segments || !ys || (res_kind && !residue)) return fail(err, VSYN_ERR_INVALID, "NULL batch pointer");
+  {  // the checks of the spec first: they need no device
+    std::vector<uint8_t> tab;
+    const int rc = feat_build_table(h, spec, tab, err);
+    if (rc) return rc;
+  }
+  const ConstHeader& H = h->H;
+  const uint32_t C = H.channels;
+  uint32_t max_seg = 1;
+  for (uint32_t g = 0; g < S; ++g) {
+    const vsyn_segment& sg = segments[g];
+    if ((uint64_t)sg.first_packet + sg.num_packets > P || (sg.residue_off & 3)) return fail(err, VSYN_ERR_INVALID, "segment %u invalid", g);
+    for (uint32_t g2 = 0; g2 < g; ++g2) {
+      const vsyn_segment& o = segments[g2];
+      if (sg.num_packets && o.num_packets && sg.first_packet < o.first_packet + o.num_packets && o.first_packet < sg.first_packet + sg.num_packets)
+        return fail(err, VSYN_ERR_INVALID, "segments %u and %u overlap", g2, g);
+    }
+    if (res_kind) {
+      uint64_t need = sg.residue_off;
+      for (uint32_t q = 0; q < sg.num_packets; ++q) {
+        const uint8_t m = packets[sg.first_packet + q].mode;
+        need += (uint64_t)C * ((m < H.num_modes && H.mode_blockflag[m]) ? H.bs[1] : H.bs[0]) / 2;
+      }
+      if (need > residue_floats) return fail(err, VSYN_ERR_INVALID, "segment %u reads past the residue buffer", g);
+    }
+    max_seg = std::max(max_seg, sg.num_packets);
+  }
+  // the lock covers the whole call, copy-back included: the staging and row buffers are the handle's, and a second host thread on the
+  // same handle must not overwrite them before this call has read its rows
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t hs = h->host_stream;
+  const size_t ys_n = (size_t)P * C * H.ys_stride;
+  HIPCHK(h->fs_pk.ensure(P));
+  HIPCHK(h->fs_seg.ensure(S));
+  HIPCHK(h->fs_ys.ensure(ys_n));
+  HIPCHK(hipMemcpyAsync(h->fs_pk.p, packets, sizeof(vsyn_packet) * P, hipMemcpyHostToDevice, hs));
+  HIPCHK(hipMemcpyAsync(h->fs_seg.p, segments, sizeof(vsyn_segment) * S, hipMemcpyHostToDevice, hs));
+  HIPCHK(hipMemcpyAsync(h->fs_ys.p, ys, sizeof(uint16_t) * ys_n, hipMemcpyHostToDevice, hs));
+  if (res_kind) {
+    HIPCHK(h->fs_res.ensure(residue_floats + 4));
+    HIPCHK(hipMemcpyAsync(h->fs_res.p, residue, sizeof(float) * residue_floats, hipMemcpyHostToDevice, hs));
+  }
+  // rows: every (packet, channel) at most once
+  const uint64_t max_rows = (uint64_t)P * C, D = spec->output_dim;
+  HIPCHK(h->fs_rows.ensure(max_rows * D + 1));
+  int rc = feat_launch(h, spec, P, h->fs_pk.p, S, h->fs_seg.p, max_seg, h->fs_ys.p, res_kind ? h->fs_res.p : nullptr, h->fs_rows.p, nullptr, hs, err);
+  if (rc) return rc;
+  std::vector<uint64_t> off((size_t)S + 1);
+  HIPCHK(hipMemcpyAsync(off.data(), h->ft_segoff.p, sizeof(uint64_t) * (S + 1), hipMemcpyDeviceToHost, hs));
+  HIPCHK(hipStreamSynchronize(hs));
+  const uint64_t total = off[S];
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = off[g + 1] - off[g];
+  vsyn_status st;
+  rc = vsyn_sync_status(h, hs, &st, err);
+  if (status) *status = st;
+  if (rc) return rc;
+  if (total > max_rows) return fail(err, VSYN_ERR_HIP, "row count %llu exceeds packets x channels", (unsigned long long)total);
+  if (!rows) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (total) {
+    HIPCHK(hipMemcpyAsync(rows, h->fs_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipStreamSynchronize(hs));
+  }
   return VSYN_OK;
 }
 

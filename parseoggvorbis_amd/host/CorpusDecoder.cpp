@@ -1,6 +1,7 @@
 // CorpusDecoder.cpp — see CorpusDecoder.hpp.
 #include "CorpusDecoder.hpp"
 
+#include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
@@ -73,11 +74,17 @@ struct CollectSink : SynthSink {
 
 struct NullCallbacks : ParseCallbacks {};
 
-void entropy_decode_file(const CorpusItem& item, FileRecord& rec, SetupCache* cache) {
+bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
+bool feature_needs_residue(const CorpusOptions& o) {
+  return o.features.kind == VSYN_FEAT_RESIDUE_YS || o.features.kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
+}
+
+void entropy_decode_file(const CorpusItem& item, FileRecord& rec, SetupCache* cache, bool no_vq) {
   NullCallbacks cb;
   CollectSink sink(rec);
   OggReader reader(cb);
   reader.sink_ = &sink;
+  reader.no_vq_ = no_vq;
   reader.setup_cache_ = cache;
   reader.batch_limit_override_ = 0xffffffffu;  // the whole file is one batch; it is cut into runs on the GPU
   rec.status = reader.full_read_from_memory(item.data, item.len);
@@ -182,6 +189,8 @@ struct Group {
   PinnedArray<int16_t> pcm16;  // CorpusOptions::pcm_s16: [S][plane][C]
   PinnedArray<uint32_t> emit;
   bool vq = false;  // files of this group ship classification + entry numbers instead of residue floats
+  PinnedArray<float> rows;      // feature run: [P * C][output_dim]
+  PinnedArray<uint64_t> seg_rows;
   PinnedArray<vsyn_vq_packet> vq_pk;
   PinnedArray<uint8_t> cls;
   PinnedArray<uint16_t> entries;
@@ -213,6 +222,7 @@ std::string gpu_status_text(const vsyn_status& st) {
   if (st.flags & VSYN_ST_BAD_VQ) s += " bad-vq";
   // accepted by the reference, refused here: a long block's next_long flag set in front of a short block
   if (st.flags & VSYN_ST_WINDOW_FLAGS) s += " window-flags: next_long set on a long block before a short one";
+  if (st.flags & VSYN_ST_FEATURE_INDEX) s += " feature-index: a gather index past its vector";
   return s + ")";
 }
 
@@ -225,8 +235,104 @@ struct Feeder {
   std::mutex& callbacks_mu;
   std::map<std::string, std::unique_ptr<Group>> groups;
 
+  // Feature run: the pending files' batches through vsyn_features_host, rows delivered per file.
+  OkOrError submit_features(Group& g) {
+    const uint32_t C = g.channels, S = (uint32_t)g.pending.size(), D = opts.features.output_dim;
+    const bool want_res = feature_needs_residue(opts);
+    double t0 = now_s();
+    size_t P = 0, rfloats = 0;
+    for (const auto& r : g.pending) {
+      P += r->batch.pk.size();
+      rfloats += want_res ? r->batch.residue_floats : 0;
+    }
+    CHECK(P < 0xffffffffu);
+    CHECK_ERR(g.pk.ensure(P));
+    CHECK_ERR(g.seg.ensure(S));
+    CHECK_ERR(g.ys.ensure(P * C * g.ys_stride));
+    if (want_res) CHECK_ERR(g.residue.ensure(rfloats));
+    CHECK_ERR(g.rows.ensure(P * C * D));
+    CHECK_ERR(g.seg_rows.ensure(S));
+    size_t p0 = 0, r0 = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      const PacketBatch& b = g.pending[s]->batch;
+      CHECK(b.ys.size() == b.pk.size() * C * g.ys_stride);
+      memcpy(&g.pk[p0], b.pk.data(), b.pk.size() * sizeof(vsyn_packet));
+      memcpy(&g.ys[p0 * C * g.ys_stride], b.ys.data(), b.ys.size() * sizeof(uint16_t));
+      if (want_res) {
+        CHECK(!b.vq && b.residue.size() == b.residue_floats);
+        memcpy(&g.residue[r0], b.residue.data(), b.residue.size() * sizeof(float));
+      }
+      vsyn_segment& sg = g.seg[s];
+      memset(&sg, 0, sizeof(sg));
+      sg.stream = 0;  // (no stream state is read or written by a feature run)
+      sg.first_packet = (uint32_t)p0;
+      sg.num_packets = (uint32_t)b.pk.size();
+      sg.flags = VSYN_SEG_RESET;
+      sg.residue_off = want_res ? r0 : 0;
+      p0 += b.pk.size();
+      r0 += want_res ? b.residue_floats : 0;
+    }
+    double t1 = now_s();
+    stats.pack_s += t1 - t0;
+    vsyn_status st = {0, 0xffffffffu};
+    const char* err = nullptr;
+    const int rc = vsyn_features_host(g.handle, &opts.features, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, want_res ? g.residue.p : nullptr, rfloats,
+                                      g.rows.p, (uint64_t)P * C, g.seg_rows.p, &st, &err);
+    double t2 = now_s();
+    stats.gpu_call_s += t2 - t1;
+    stats.submits++;
+    if (rc == VSYN_ERR_INVALID) {  // the spec does not fit this setup (e.g. output_dim below the biggest floor's posts): the files' problem
+      const std::string msg = std::string("features: ") + (err ? err : "refused");
+      for (auto& r : g.pending) {
+        results[r->index].status = OkOrError(msg);
+        stats.files++;
+        queue.give_back(std::move(r));
+      }
+      g.pending.clear();
+      return OkOrError();
+    }
+    if (rc != VSYN_OK && rc != VSYN_ERR_STREAM) return OkOrError(std::string("GPU feature layer: ") + (err ? err : "features failed"));
+    if (rc == VSYN_ERR_STREAM && S > 1) {  // find the bad file(s): one by one
+      std::vector<std::unique_ptr<FileRecord>> files;
+      files.swap(g.pending);
+      for (auto& f : files) {
+        g.pending.clear();
+        g.pending.push_back(std::move(f));
+        CHECK_ERR(submit_features(g));
+      }
+      return OkOrError();
+    }
+    uint64_t row0 = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      FileRecord& r = *g.pending[s];
+      CorpusFileResult& out = results[r.index];
+      out.channels = C;
+      out.sample_rate = r.header.audio_sample_rate;
+      out.audio_packets = (uint32_t)r.batch.pk.size();
+      if (rc == VSYN_ERR_STREAM) {
+        out.status = OkOrError(gpu_status_text(st));
+      } else {
+        const uint64_t nr = g.seg_rows[s];
+        out.feature_rows = nr;
+        out.status = r.status;
+        if (callbacks && !r.status.is_error_) {
+          std::lock_guard<std::mutex> lk(callbacks_mu);
+          if (!callbacks->gotFileFeatures(r.index, r.header, &g.rows[row0 * D], nr, D)) return OkOrError("aborted by gotFileFeatures");
+        }
+        row0 += nr;
+      }
+      stats.audio_packets += r.batch.pk.size();
+      stats.files++;
+    }
+    for (auto& r : g.pending) queue.give_back(std::move(r));
+    g.pending.clear();
+    stats.deliver_s += now_s() - t2;
+    return OkOrError();
+  }
+
   OkOrError submit(Group& g) {
     if (g.pending.empty()) return OkOrError();
+    if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
     double t0 = now_s();
     size_t P = 0, rfloats = 0, ncls = 0, nent = 0;
@@ -417,7 +523,7 @@ struct Feeder {
         stats.files++;
         return OkOrError();
       }
-      if (rec->synth.has_vq && vsyn_attach_vq(gp->handle, &rec->synth.vq, &err) != VSYN_OK) {
+      if (rec->synth.has_vq && !feature_run(opts) && vsyn_attach_vq(gp->handle, &rec->synth.vq, &err) != VSYN_OK) {
         std::string msg = std::string("GPU synthesis layer: ") + (err ? err : "vsyn_attach_vq failed");
         groups.erase(rec->synth.key);
         return OkOrError(msg);
@@ -468,7 +574,7 @@ OkOrError decode_corpus(const std::vector<CorpusItem>& items, const CorpusOption
         std::unique_ptr<FileRecord> rec = queue.fresh();
         rec->index = i;
         const double t0 = now_s();
-        entropy_decode_file(items[i], *rec, opts.share_setups ? &setup_cache : nullptr);
+        entropy_decode_file(items[i], *rec, opts.share_setups ? &setup_cache : nullptr, feature_needs_residue(opts));
         worker_cpu[(size_t)t] += now_s() - t0;
         if (!queue.push(std::move(rec))) break;
       }
@@ -628,3 +734,80 @@ extern "C" int ogg_vorbis_decode_corpus_s16(const uint8_t* const* datas, const s
   }
   return 0;
 }
+
+extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
+                                          uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                          double* stats_out, const char** error_out) {
+  // per calling thread: loader threads may run feature passes side by side
+  static thread_local char error_buf[256];
+  static thread_local std::vector<std::string> file_errors;
+  if (rows_out)
+    for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
+  if (!spec || spec->kind == 0) {
+    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_features_corpus: no feature kind");
+    if (error_out) *error_out = error_buf;
+    return 1;
+  }
+  std::vector<CorpusItem> items(num_files);
+  for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
+  CorpusOptions opts;
+  opts.threads = threads;
+  opts.feeders = feeders;
+  opts.files_per_submit = files_per_submit;
+  opts.device = device;
+  opts.checksum = false;
+  opts.features = *spec;
+  std::vector<CorpusFileResult> results;
+  CorpusStats st;
+  struct CopyOut : CorpusCallbacks {  // gotFileFeatures calls never overlap (CorpusCallbacks)
+    float** out = nullptr;
+    std::vector<uint8_t> no_mem;
+    bool gotFileFeatures(size_t i, const VorbisIdHeader&, const float* rows, uint64_t n, uint32_t dim) override {
+      if (!n) return true;
+      float* p = (float*)malloc((size_t)n * dim * sizeof(float));
+      if (!p) {
+        no_mem[i] = 1;
+        return true;
+      }
+      memcpy(p, rows, (size_t)n * dim * sizeof(float));
+      out[i] = p;
+      return true;
+    }
+  } copy_out;
+  copy_out.out = rows_out;
+  copy_out.no_mem.assign(num_files, 0);
+  OkOrError r = decode_corpus(items, opts, rows_out ? &copy_out : nullptr, results, &st);
+  file_errors.assign(num_files, std::string());
+  for (size_t i = 0; i < results.size() && i < num_files; ++i) {
+    if (rows_count_out) rows_count_out[i] = results[i].feature_rows;
+    const bool bad = results[i].status.is_error_ || copy_out.no_mem[i];
+    if (bad && rows_out && rows_out[i]) {
+      free(rows_out[i]);
+      rows_out[i] = nullptr;
+    }
+    if (ok_out) ok_out[i] = bad ? 0 : 1;
+    if (error_out_per_file) {
+      file_errors[i] = results[i].status.is_error_ ? results[i].status.err_msg_ : (copy_out.no_mem[i] ? "features: out of host memory" : "");
+      error_out_per_file[i] = bad ? file_errors[i].c_str() : nullptr;
+    }
+  }
+  if (stats_out) {
+    const double v[8] = {st.wall_s, st.entropy_cpu_s, st.gpu_call_s, st.pack_s, st.deliver_s, (double)st.submits, (double)st.audio_packets, (double)st.frames};
+    for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+  }
+  if (r.is_error_) {
+    if (rows_out)
+      for (size_t i = 0; i < num_files; ++i) {
+        free(rows_out[i]);
+        rows_out[i] = nullptr;
+      }
+    snprintf(error_buf, sizeof(error_buf), "%s", r.err_msg_.c_str());
+    if (error_out) *error_out = error_buf;
+    return 1;
+  }
+  if (error_out) *error_out = nullptr;
+  return 0;
+}
+
+extern "C" void ogg_vorbis_features_free(float* rows) { free(rows); }

@@ -786,7 +786,7 @@ OkOrError VorbisStream::parse_setup(const uint8_t* data, uint32_t len, ParseCall
       if (f.floor_type == 1) maxp = std::max(maxp, f.floor1.xs.size());
     ys_stride_ = (uint32_t)((maxp + 3) & ~(size_t)3);
   }
-  vq_mode_ = stream_can_use_vq(*this);
+  vq_mode_ = !no_vq_ && stream_can_use_vq(*this);
   CHECK(cb.gotSetup(setup));
   return OkOrError();
 }
@@ -1311,6 +1311,7 @@ OkOrError OggReader::read_next_page(bool& reached_eof) {
     streams_[serial]->setup_cache_ = setup_cache_;
     if (sink_) sink_->prepare(*streams_[serial]);
     if (batch_limit_override_) streams_[serial]->batch_limit_ = batch_limit_override_;
+    streams_[serial]->no_vq_ = no_vq_;
   }
   auto it = streams_.find(serial);
   CHECK(it != streams_.end());

@@ -255,6 +255,7 @@ struct VorbisStream {
   // VQ mode: the residue leaves the host as classification + entry numbers (decided once per stream in parse_setup:
   // every VQ book <= 65536 entries, vector lengths dividing the partition sizes; PARSEOGGVORBIS_VQ=0 turns it off)
   bool vq_mode_ = false;
+  bool no_vq_ = false;  // set before the setup header: ship float residue whatever the setup (feature runs read "after_residue")
   uint64_t setup_hash_ = 0;  // FNV-1a of the setup header packet: identifies the codebooks when streams share a handle
   std::vector<vsyn_vq_packet> vq_pk_;
   std::vector<uint8_t> cls_;
@@ -272,6 +273,7 @@ struct OggReader {
   SynthSink* sink_ = nullptr;           // optional: where streams hand their batches (see SynthSink)
   SetupCache* setup_cache_ = nullptr;   // optional: parsed setup headers shared between readers (see SetupCache)
   uint32_t batch_limit_override_ = 0;   // optional: audio packets per batch (0: default / PARSEOGGVORBIS_BATCH)
+  bool no_vq_ = false;                  // optional: streams ship float residue (VorbisStream::no_vq_)
 
   explicit OggReader(ParseCallbacks& callbacks) : packet_counts_(0), callbacks_(callbacks) {}
   OkOrError open_file(const std::string& filename);
