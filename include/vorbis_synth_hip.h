@@ -416,6 +416,80 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec,
                        float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
                        vsyn_status* status, const char** err);
 
+/* ---- spectral features: mel filterbank, log-mel, dB-mel and MFCC of the decoded PCM, computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames (what ogg_vorbis_decode_corpus returns per file).
+ * Output: a float32 matrix (frames, dim), time-major like the feature matrices. The math follows librosa's documented defaults
+ * (librosa >= 0.10); it is written below as exact arithmetic, and the device is compared against a float64 model of it
+ * (tests/spectral_model.py). Parity with librosa itself has NOT been verified (librosa is not among the test dependencies).
+ *
+ *  1. Mono: y[t] = (1/C) * sum_c x[c][t]                                                     (librosa.to_mono)
+ *  2. Framing: VSYN_SPEC_CENTER pads n_fft/2 zeros on both sides; T_pad = T (+ 2 * (n_fft/2)). Frames
+ *     F = 1 + (T_pad - n_fft) / hop_length if T_pad >= n_fft, else 0; F = 0 whenever T = 0. Frame f starts at padded index
+ *     f * hop_length (vsyn_spectral_num_frames).
+ *  3. Window: periodic Hann of win_length, w[i] = 0.5 - 0.5 cos(2 pi i / win_length), zero-padded centred to n_fft at offset
+ *     (n_fft - win_length) / 2.
+ *  4. S[f][k] = |sum_j w[j] y_pad[f*hop + j] exp(-2 pi i j k / n_fft)|^power, k = 0 .. n_fft/2, power 1 or 2. Any n_fft in
+ *     [16, 8192], powers of two or not (int(0.025 * 44100) = 1102 is the usual 25 ms window).
+ *  5. Mel filterbank (librosa.filters.mel): bin frequencies k * sr / n_fft; n_mels + 2 edges equally spaced in mel between
+ *     mel(fmin) and mel(fmax) (fmax = 0: sr/2; fmax > sr/2 refused), mapped back to Hz: hz[0 .. n_mels+1]. Slaney mel scale:
+ *     f / (200/3) below 1000 Hz, 15 + ln(f / 1000) / (ln(6.4) / 27) above; VSYN_SPEC_HTK: 2595 log10(1 + f / 700).
+ *     W[m][k] = max(0, min((f_k - hz[m]) / (hz[m+1] - hz[m]), (hz[m+2] - f_k) / (hz[m+2] - hz[m+1]))), times
+ *     2 / (hz[m+2] - hz[m]) (Slaney area normalisation; VSYN_SPEC_NO_NORM turns it off). M[f][m] = sum_k W[m][k] S[f][k].
+ *     The table is built in double on the host, per distinct sample rate.
+ *  6. Kinds: VSYN_SPEC_MEL_POWER = M. VSYN_SPEC_LOG_MEL = log10(max(M, log_floor)) (RETURNN's log filterbank).
+ *     VSYN_SPEC_MEL_DB = librosa power_to_db(ref=1): D = 10 log10(max(M, amin)), then if top_db > 0,
+ *     D = max(D, max over the whole segment of D - top_db). VSYN_SPEC_MFCC = the orthonormal DCT-II of MEL_DB along the mel
+ *     axis, first n_mfcc coefficients (librosa.feature.mfcc, lifter 0). dim = n_mfcc for MFCC, n_mels otherwise.
+ *  7. Checks (VSYN_ERR_INVALID before anything runs): 1 <= hop_length; 1 <= win_length <= n_fft; 16 <= n_fft <= 8192;
+ *     1 <= n_mels <= 256; 1 <= n_mfcc <= n_mels (MFCC); 0 <= fmin < fmax <= sr/2 for every segment's rate; power 1 or 2;
+ *     log_floor > 0 (LOG_MEL); amin > 0 and top_db >= 0 (MEL_DB, MFCC).
+ *
+ * Precision: windowed samples, twiddles cos/sin(2 pi m / n_fft) (rounded from double) and mel weights are float32; the DFT
+ * and the mel sums accumulate in float32 in a fixed order, so the same PCM always gives the same bits. The error of the DFT
+ * chain grows with n_fft (DESIGN.md "Spectral features": at 8192 the log kinds lose digits on low, near-silent bands). The spectral entry
+ * points read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM, and a
+ * later vsyn_pcm_fetch_host returns the same PCM. One handle's spectral entry points share its spectral workspace. */
+enum {
+  VSYN_SPEC_MEL_POWER = 1,  /* "mel_power" */
+  VSYN_SPEC_LOG_MEL = 2,    /* "log_mel" */
+  VSYN_SPEC_MEL_DB = 3,     /* "mel_db" */
+  VSYN_SPEC_MFCC = 4        /* "mfcc" */
+};
+/* vsyn_spectral_spec.options */
+#define VSYN_SPEC_CENTER 1u   /* pad n_fft/2 zeros on both sides (librosa's center=True) */
+#define VSYN_SPEC_HTK 2u      /* HTK mel scale instead of Slaney's */
+#define VSYN_SPEC_NO_NORM 4u  /* no Slaney area normalisation of the filters */
+
+typedef struct vsyn_spectral_spec {
+  uint32_t kind;        /* VSYN_SPEC_* kind */
+  uint32_t options;     /* VSYN_SPEC_* option bits */
+  uint32_t n_fft, hop_length, win_length, n_mels;
+  uint32_t n_mfcc;      /* MFCC only */
+  uint32_t power;       /* 1 (magnitude) or 2 (power) */
+  double fmin, fmax;    /* Hz; fmax = 0: each segment's sr / 2 */
+  double log_floor;     /* LOG_MEL */
+  double amin, top_db;  /* MEL_DB, MFCC; top_db = 0: no clamp */
+} vsyn_spectral_spec;
+
+/* Frames of a segment of `frames` PCM frames under spec (step 2), 0 for an invalid spec. */
+uint64_t vsyn_spectral_num_frames(const vsyn_spectral_spec* spec, uint64_t frames);
+
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle (with or without VSYN_SUBMIT_KEEP_PCM), per segment of that
+ * submit. sample_rates[S] (host) is each segment's rate; a rate of 0 skips the segment (0 rows). seg_rows[S] receives each
+ * segment's row count; rows (may be NULL when only the counts are wanted) receives the rows of all segments back to back, dim
+ * columns each, at most rows_capacity rows (VSYN_ERR_INVALID with the counts filled if it is too small). status as for
+ * vsyn_features_host. Synchronous. */
+int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
+                           float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err);
+/* The caller's planar PCM: d_pcm[(g * channels + c) * plane_stride + t], d_frames[S] (device) PCM frames per segment (clamped to
+ * plane_stride). sample_rates[S] is a HOST array as above. Writes d_seg_row_off[S+1] (uint64, may be NULL): segment g's rows
+ * are [d_seg_row_off[g], d_seg_row_off[g+1]) of d_rows, which must hold sum_g vsyn_spectral_num_frames(spec, frames_g) rows of
+ * dim columns (S * vsyn_spectral_num_frames(spec, plane_stride) always suffices). Asynchronous on hip_stream. */
+int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
+                         const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames,
+                         float* d_rows, uint64_t* d_seg_row_off, void* hip_stream, const char** err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,12 @@ class FeatureSpec(C.Structure):  # vsyn_feature_spec
                 ("floor_base_factor", C.c_float), ("reserved1", C.c_uint32)]
 
 
+class SpectralSpec(C.Structure):  # vsyn_spectral_spec
+    _fields_ = [("kind", C.c_uint32), ("options", C.c_uint32), ("n_fft", C.c_uint32), ("hop_length", C.c_uint32),
+                ("win_length", C.c_uint32), ("n_mels", C.c_uint32), ("n_mfcc", C.c_uint32), ("power", C.c_uint32),
+                ("fmin", C.c_double), ("fmax", C.c_double), ("log_floor", C.c_double), ("amin", C.c_double), ("top_db", C.c_double)]
+
+
 class Status(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("first_bad_packet", C.c_uint32)]
 
@@ -184,6 +190,7 @@ _SYMBOLS = [
     "vsyn_profile_enable", "vsyn_profile_read", "vsyn_imdct_device", "vsyn_host_alloc", "vsyn_host_free",
     "vsyn_attach_vq", "vsyn_submit_device_vq", "vsyn_submit_host_vq", "vsyn_pcm_interleave_device", "vsyn_pcm_abs_sum_host", "vsyn_pcm_fetch_host",
     "vsyn_feature_rows_device", "vsyn_features_device", "vsyn_features_host",
+    "vsyn_spectral_num_frames", "vsyn_spectral_device", "vsyn_pcm_spectral_host",
 ]
 
 
@@ -243,6 +250,10 @@ def load():
     lib.vsyn_features_device.argtypes = [vp, C.POINTER(FeatureSpec), u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, cpp]
     lib.vsyn_features_host.argtypes = [vp, C.POINTER(FeatureSpec), u32, vp, u32, vp, vp, vp, C.c_size_t, vp, u64, vp,
                                        C.POINTER(Status), cpp]
+    lib.vsyn_spectral_num_frames.argtypes = [C.POINTER(SpectralSpec), u64]
+    lib.vsyn_spectral_num_frames.restype = u64
+    lib.vsyn_spectral_device.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_spectral_host.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, u64, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -337,6 +348,33 @@ class Synth:
             raise VsynError(rc, (err.value or b"").decode())
         total = int(seg_rows[:S].sum()) if rc == VSYN_OK else 0
         return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], flags=st.flags, first_bad=st.first_bad_packet)
+
+    def pcm_spectral_host(self, spec, sample_rates):
+        """vsyn_pcm_spectral_host over the last submit's segments: returns dict(rc, rows [total][dim], seg_rows [S], flags)."""
+        rates = np.ascontiguousarray(sample_rates, dtype=np.uint32)
+        S = len(rates)
+        dim = spec.n_mfcc if spec.kind == 4 else spec.n_mels
+        seg_rows = np.zeros(max(1, S), np.uint64)
+        st, err = Status(), C.c_char_p()
+        rc = self.lib.vsyn_pcm_spectral_host(self.h, C.byref(spec), S, _ptr(rates), None, 0, _ptr(seg_rows), C.byref(st), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum())
+        rows = np.zeros((max(1, total), dim), np.float32)
+        rc = self.lib.vsyn_pcm_spectral_host(self.h, C.byref(spec), S, _ptr(rates), _ptr(rows), total, _ptr(seg_rows), C.byref(st),
+                                             C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], flags=st.flags)
+
+    def spectral_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, stream=None):
+        """vsyn_spectral_device on device pointers (ints); sample_rates is a host sequence."""
+        rates = np.ascontiguousarray(sample_rates, dtype=np.uint32)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_spectral_device(self.h, C.byref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows,
+                                           d_seg_row_off, stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

@@ -26,6 +26,7 @@
 #include "vsyn_vq.h"
 #include "vsyn_pcm.h"
 #include "vsyn_features.h"
+#include "vsyn_spectral.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846264338327
@@ -193,6 +194,16 @@ struct vsyn_handle {
   DevBuf<vsyn_segment> fs_seg;
   DevBuf<uint16_t> fs_ys;
   DevBuf<float> fs_res, fs_rows;
+  // spectral features (vsyn_spectral.h): buffers of their own; the PCM is only read
+  DevBuf<uint8_t> sp_tab;
+  uint8_t* sp_tab_host = nullptr;      // page-locked copy of the tables (the upload is asynchronous)
+  size_t sp_tab_host_cap = 0;
+  hipEvent_t sp_ev = nullptr;          // recorded behind the table upload: the host copy is reused only after it
+  bool sp_ev_valid = false;
+  bool sp_lds_set = false;             // the STFT kernels' dynamic-LDS limit is raised on this handle's device
+  DevBuf<uint32_t> sp_segF, sp_segmax;
+  DevBuf<uint64_t> sp_segoff;
+  DevBuf<float> sp_db, sp_rows;
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -559,6 +570,8 @@ void vsyn_destroy(vsyn_handle* h) {
   u_tables_destroy(&h->utab);
   if (h->ft_ev) (void)hipEventDestroy(h->ft_ev);
   if (h->ft_tab_host) (void)hipHostFree(h->ft_tab_host);
+  if (h->sp_ev) (void)hipEventDestroy(h->sp_ev);
+  if (h->sp_tab_host) (void)hipHostFree(h->sp_tab_host);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->pre) (void)hipStreamDestroy(h->pre);
   if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
@@ -1517,6 +1530,264 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P
     HIPCHK(hipStreamSynchronize(hs));
   }
   return VSYN_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// spectral features (vsyn_spectral.h; semantics in the header)
+// ------------------------------------------------------------------------------------------------
+static const uint32_t SPEC_LDS_BUDGET = 160u * 1024u;  // gfx950: 160 KiB of LDS per CU, all of it available to one workgroup
+
+static double spec_hz_to_mel(double f, bool htk) {
+  if (htk) return 2595.0 * log10(1.0 + f / 700.0);
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+  return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
+}
+static double spec_mel_to_hz(double m, bool htk) {
+  if (htk) return 700.0 * (pow(10.0, m / 2595.0) - 1.0);
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+  return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+
+static uint32_t spec_dim(const vsyn_spectral_spec* sp) { return sp->kind == VSYN_SPEC_MFCC ? sp->n_mfcc : sp->n_mels; }
+
+// The checks of the spec and of every segment's rate (0 = skipped segment).
+static int spec_check(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const char** err) {
+  if (!sp) return fail(err, VSYN_ERR_INVALID, "spectral spec is NULL");
+  if (sp->kind < VSYN_SPEC_MEL_POWER || sp->kind > VSYN_SPEC_MFCC) return fail(err, VSYN_ERR_INVALID, "unknown spectral kind %u", sp->kind);
+  if (sp->options & ~(VSYN_SPEC_CENTER | VSYN_SPEC_HTK | VSYN_SPEC_NO_NORM)) return fail(err, VSYN_ERR_INVALID, "unknown spectral options 0x%x", sp->options);
+  if (sp->n_fft < 16 || sp->n_fft > 8192) return fail(err, VSYN_ERR_INVALID, "n_fft %u outside [16, 8192]", sp->n_fft);
+  if (sp->hop_length < 1) return fail(err, VSYN_ERR_INVALID, "hop_length must be >= 1");
+  if (sp->win_length < 1 || sp->win_length > sp->n_fft) return fail(err, VSYN_ERR_INVALID, "win_length %u outside [1, n_fft]", sp->win_length);
+  if (sp->n_mels < 1 || sp->n_mels > 256) return fail(err, VSYN_ERR_INVALID, "n_mels %u outside [1, 256]", sp->n_mels);
+  if (sp->kind == VSYN_SPEC_MFCC && (sp->n_mfcc < 1 || sp->n_mfcc > sp->n_mels)) return fail(err, VSYN_ERR_INVALID, "n_mfcc %u outside [1, n_mels]", sp->n_mfcc);
+  if (sp->power != 1 && sp->power != 2) return fail(err, VSYN_ERR_INVALID, "power must be 1 or 2");
+  if (!(sp->fmin >= 0.0) || !(sp->fmax >= 0.0)) return fail(err, VSYN_ERR_INVALID, "fmin / fmax must be >= 0");
+  if (sp->kind == VSYN_SPEC_LOG_MEL && !(sp->log_floor > 0.0)) return fail(err, VSYN_ERR_INVALID, "log_floor must be > 0");
+  if (sp->kind >= VSYN_SPEC_MEL_DB && (!(sp->amin > 0.0) || !(sp->top_db >= 0.0))) return fail(err, VSYN_ERR_INVALID, "amin must be > 0 and top_db >= 0");
+  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!rates[g]) continue;
+    const double ny = rates[g] / 2.0, fmax = sp->fmax > 0.0 ? sp->fmax : ny;
+    if (fmax > ny) return fail(err, VSYN_ERR_INVALID, "segment %u: fmax %g above sr/2 = %g", g, fmax, ny);
+    if (!(sp->fmin < fmax)) return fail(err, VSYN_ERR_INVALID, "segment %u: fmin %g not below fmax %g", g, sp->fmin, fmax);
+  }
+  return VSYN_OK;
+}
+
+static uint32_t spec_tile(const vsyn_spectral_spec* sp) {  // frames per STFT workgroup: the most that fit the LDS
+  for (uint32_t ft : {16u, 4u, 1u})
+    if (spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u <= SPEC_LDS_BUDGET) return ft;
+  return 0;
+}
+
+// SpecHeader, twiddles, window, per-rate bands and weights, DCT matrix, per-segment rate index. Call after spec_check.
+static void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, std::vector<uint8_t>& out) {
+  const uint32_t n = sp->n_fft, NM = sp->n_mels, nb = n / 2u + 1u;
+  const bool htk = (sp->options & VSYN_SPEC_HTK) != 0, norm = !(sp->options & VSYN_SPEC_NO_NORM);
+  std::vector<uint32_t> distinct, seg_rate(S, SPEC_SKIP);
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!rates[g]) continue;
+    auto it = std::find(distinct.begin(), distinct.end(), rates[g]);
+    seg_rate[g] = (uint32_t)(it - distinct.begin());
+    if (it == distinct.end()) distinct.push_back(rates[g]);
+  }
+  std::vector<SpecBand> bands;
+  std::vector<float> w;
+  std::vector<double> hz(NM + 2);
+  for (uint32_t sr : distinct) {
+    const double fmax = sp->fmax > 0.0 ? sp->fmax : sr / 2.0;
+    const double m0 = spec_hz_to_mel(sp->fmin, htk), m1 = spec_hz_to_mel(fmax, htk), step = (m1 - m0) / (double)(NM + 1);
+    for (uint32_t i = 0; i < NM + 2; ++i) hz[i] = spec_mel_to_hz(i == NM + 1 ? m1 : m0 + i * step, htk);  // numpy.linspace
+    for (uint32_t m = 0; m < NM; ++m) {
+      const double lo = hz[m], c = hz[m + 1], hi = hz[m + 2], enorm = norm ? 2.0 / (hi - lo) : 1.0;
+      SpecBand b = {0, 0, (uint32_t)w.size(), 0};
+      for (uint32_t k = 0; k < nb; ++k) {
+        const double fk = (double)k * sr / n;
+        const double v = std::max(0.0, std::min((fk - lo) / (c - lo), (hi - fk) / (hi - c))) * enorm;
+        if (v > 0.0) {
+          if (!b.cnt) b.first = k;
+          for (uint32_t z = b.first + b.cnt; z < k; ++z) w.push_back(0.f);  // (a triangle has no holes; kept general)
+          b.cnt = k - b.first + 1;
+          w.push_back((float)v);
+        }
+      }
+      bands.push_back(b);
+    }
+  }
+  SpecHeader T = {};
+  T.kind = sp->kind;
+  T.opts = sp->options;
+  T.n = n;
+  T.hop = sp->hop_length;
+  T.win = sp->win_length;
+  T.woff = (n - sp->win_length) / 2u;
+  T.nbins = nb;
+  T.n_mels = NM;
+  T.dim = spec_dim(sp);
+  T.n_mfcc = sp->kind == VSYN_SPEC_MFCC ? sp->n_mfcc : 0u;
+  T.power = sp->power;
+  T.num_rates = (uint32_t)distinct.size();
+  T.S = S;
+  T.log_floor = (float)sp->log_floor;
+  T.amin = (float)sp->amin;
+  T.top_db = (float)sp->top_db;
+  auto al = [](size_t v) { return (uint32_t)((v + 15) & ~(size_t)15); };
+  T.off_tw = al(sizeof(SpecHeader));
+  T.off_win = al(T.off_tw + 8ull * n);
+  T.off_band = al(T.off_win + 4ull * n);
+  T.off_w = al(T.off_band + sizeof(SpecBand) * bands.size());
+  T.off_dct = al(T.off_w + 4ull * w.size());
+  T.off_rate = al(T.off_dct + 4ull * T.n_mfcc * NM);
+  out.assign(T.off_rate + 4ull * S + 16, 0);
+  memcpy(out.data(), &T, sizeof(T));
+  float* tw = (float*)(out.data() + T.off_tw);
+  for (uint32_t m = 0; m < n; ++m) {
+    const double a = 2.0 * M_PI * (double)m / (double)n;
+    tw[2 * m] = (float)cos(a);
+    tw[2 * m + 1] = (float)sin(a);
+  }
+  float* wn = (float*)(out.data() + T.off_win);
+  for (uint32_t i = 0; i < sp->win_length; ++i) wn[T.woff + i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)sp->win_length));
+  if (!bands.empty()) memcpy(out.data() + T.off_band, bands.data(), sizeof(SpecBand) * bands.size());
+  if (!w.empty()) memcpy(out.data() + T.off_w, w.data(), 4 * w.size());
+  float* dct = (float*)(out.data() + T.off_dct);
+  for (uint32_t i = 0; i < T.n_mfcc; ++i)
+    for (uint32_t m = 0; m < NM; ++m)
+      dct[(size_t)i * NM + m] = (float)(sqrt((i ? 2.0 : 1.0) / NM) * cos(M_PI * (double)i * (2.0 * m + 1.0) / (2.0 * NM)));
+  if (S) memcpy(out.data() + T.off_rate, seg_rate.data(), 4ull * S);
+}
+
+// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s; frames from d_frames, else from si. f_max bounds every
+// segment's STFT frames, rows_bound the total rows. Caller holds h->mu and has run spec_check.
+static int spec_launch(vsyn_handle* h, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
+                       uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
+                       uint64_t* d_segoff, hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  const uint32_t ft = spec_tile(sp);
+  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", sp->n_fft, sp->hop_length);
+  std::vector<uint8_t> tab;
+  spec_build_table(sp, S, rates, tab);
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->sp_lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    h->sp_lds_set = true;
+  }
+  HIPCHK(h->sp_tab.ensure(tab.size()));
+  HIPCHK(h->sp_segF.ensure(S));
+  HIPCHK(h->sp_segmax.ensure(S));
+  HIPCHK(h->sp_segoff.ensure((size_t)S + 1));
+  if (sp->kind == VSYN_SPEC_MFCC) HIPCHK(h->sp_db.ensure(rows_bound * sp->n_mels + 1));
+  if (!h->sp_ev) HIPCHK(hipEventCreateWithFlags(&h->sp_ev, hipEventDisableTiming));
+  if (h->sp_ev_valid) HIPCHK(hipEventSynchronize(h->sp_ev));  // the previous upload has read the host copy
+  if (h->sp_tab_host_cap < tab.size()) {
+    if (h->sp_tab_host) HIPCHK(hipHostFree(h->sp_tab_host));
+    h->sp_tab_host = nullptr;
+    h->sp_tab_host_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&h->sp_tab_host, tab.size() + 4096, hipHostMallocDefault));
+    h->sp_tab_host_cap = tab.size() + 4096;
+  }
+  memcpy(h->sp_tab_host, tab.data(), tab.size());
+  HIPCHK(hipMemcpyAsync(h->sp_tab.p, h->sp_tab_host, tab.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(h->sp_ev, s));
+  h->sp_ev_valid = true;
+  SpecCtx A;
+  A.tab = h->sp_tab.p;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.segF = h->sp_segF.p;
+  A.segoff = d_segoff ? d_segoff : h->sp_segoff.p;
+  A.segmax = h->sp_segmax.p;
+  A.rows = d_rows;
+  A.db = sp->kind == VSYN_SPEC_MFCC ? h->sp_db.p : nullptr;
+  hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  if (f_max == 0 || S == 0) return VSYN_OK;
+  const uint64_t gx = (f_max + ft - 1) / ft;
+  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  const size_t lds = spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u;
+  const dim3 grid((uint32_t)gx, S);
+  if (ft == 16) hipLaunchKernelGGL(vsyn_spec_stft_kernel<16>, grid, dim3(SPEC_THREADS), lds, s, A);
+  else if (ft == 4) hipLaunchKernelGGL(vsyn_spec_stft_kernel<4>, grid, dim3(SPEC_THREADS), lds, s, A);
+  else hipLaunchKernelGGL(vsyn_spec_stft_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
+  HIPCHK(hipGetLastError());
+  if (sp->kind >= VSYN_SPEC_MEL_DB) {
+    hipLaunchKernelGGL(vsyn_spec_finish_kernel, dim3((uint32_t)((f_max + SPEC_FIN_ROWS - 1) / SPEC_FIN_ROWS), S), dim3(SPEC_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  return VSYN_OK;
+}
+
+extern "C" {
+
+uint64_t vsyn_spectral_num_frames(const vsyn_spectral_spec* spec, uint64_t frames) {
+  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
+  return spec_num_frames(spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, frames);
+}
+
+int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, const float* d_pcm,
+                         uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off,
+                         void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = spec_check(spec, S, sample_rates, err);
+  if (rc) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_rows || plane_stride == 0 || channels == 0 || channels > 255)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  const uint64_t f_max = spec_num_frames(spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, plane_stride);
+  std::lock_guard<std::mutex> lk(h->mu);
+  return spec_launch(h, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, (uint64_t)S * f_max, d_rows,
+                     d_seg_row_off, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
+                           uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (status) {
+    status->flags = 0;
+    status->first_bad_packet = 0xFFFFFFFFu;
+  }
+  int rc = spec_check(spec, S, sample_rates, err);
+  if (rc) return rc;
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  // the lock covers the whole call: the spectral workspace is the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->last_S == 0 || h->last_host_plane == 0) return fail(err, VSYN_ERR_INVALID, "no vsyn_submit_host on this handle yet");
+  if (S != h->last_S) return fail(err, VSYN_ERR_INVALID, "num_segments %u differs from the last submit's %u", S, h->last_S);
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t hs = h->host_stream;
+  const uint64_t plane = h->last_host_plane;
+  const SegInfo* d_si = h->ws_seg[h->last_wb].p;
+  std::vector<SegInfo> si(S);
+  HIPCHK(hipMemcpyAsync(si.data(), d_si, sizeof(SegInfo) * S, hipMemcpyDeviceToHost, hs));
+  HIPCHK(hipStreamSynchronize(hs));
+  const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
+  uint64_t total = 0, f_max = 0;
+  for (uint32_t g = 0; g < S; ++g) {
+    const uint64_t f = sample_rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, center, std::min<uint64_t>(si[g].total_emit, plane)) : 0;
+    seg_rows[g] = f;
+    total += f;
+    f_max = std::max(f_max, f);
+  }
+  if (!rows || total == 0) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  const uint64_t D = spec_dim(spec);
+  HIPCHK(h->sp_rows.ensure(total * D + 1));
+  rc = spec_launch(h, spec, S, sample_rates, h->st_pcm.p, plane, h->H.channels, nullptr, d_si, f_max, total, h->sp_rows.p, nullptr, hs, err);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+  vsyn_status st;
+  rc = vsyn_sync_status(h, hs, &st, err);
+  if (status) *status = st;
+  return rc;
 }
 
 }  // extern "C"

@@ -75,6 +75,7 @@ struct CollectSink : SynthSink {
 struct NullCallbacks : ParseCallbacks {};
 
 bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
+bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
 bool feature_needs_residue(const CorpusOptions& o) {
   return o.features.kind == VSYN_FEAT_RESIDUE_YS || o.features.kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
 }
@@ -358,8 +359,9 @@ struct Feeder {
       CHECK_ERR(g.residue.ensure(rfloats));
     }
     CHECK_ERR(g.emit.ensure(P));
+    const bool spectral = spectral_run(opts);  // the PCM stays on the device: only the spectral rows come back
     if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * C * plane));
-    else CHECK_ERR(g.pcm.ensure((size_t)S * C * plane));
+    else if (!spectral) CHECK_ERR(g.pcm.ensure((size_t)S * C * plane));
     size_t p0 = 0, r0 = 0, c0 = 0, e0 = 0;
     for (uint32_t s = 0; s < S; ++s) {
       const PacketBatch& b = g.pending[s]->batch;
@@ -400,7 +402,8 @@ struct Feeder {
     vsyn_status st = {0, 0xffffffffu};
     const char* err = nullptr;
     int rc;
-    const uint32_t sflags = opts.pcm_s16 ? VSYN_SUBMIT_KEEP_PCM : 0u;
+    const uint32_t sflags = (opts.pcm_s16 || spectral) ? VSYN_SUBMIT_KEEP_PCM : 0u;
+    float* pcm_out = (opts.pcm_s16 || spectral) ? nullptr : g.pcm.p;
     if (g.vq) {
       vsyn_vq_batch vqb;
       vqb.packets = g.vq_pk.p;
@@ -408,9 +411,9 @@ struct Feeder {
       vqb.entries = g.entries.p;
       vqb.num_cls = ncls;
       vqb.num_entries = nent;
-      rc = vsyn_submit_host_vq(g.handle, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, &vqb, nullptr, rfloats, opts.pcm_s16 ? nullptr : g.pcm.p, plane, g.emit.p, nullptr, sflags, &st, &err);
+      rc = vsyn_submit_host_vq(g.handle, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, &vqb, nullptr, rfloats, pcm_out, plane, g.emit.p, nullptr, sflags, &st, &err);
     } else {
-      rc = vsyn_submit_host(g.handle, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, g.residue.p, rfloats, opts.pcm_s16 ? nullptr : g.pcm.p, plane, g.emit.p, nullptr, sflags, &st, &err);
+      rc = vsyn_submit_host(g.handle, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, g.residue.p, rfloats, pcm_out, plane, g.emit.p, nullptr, sflags, &st, &err);
     }
     if (opts.pcm_s16 && rc == VSYN_OK) {
       const char* ferr = nullptr;
@@ -424,6 +427,43 @@ struct Feeder {
       const char* derr = nullptr;
       if (vsyn_pcm_abs_sum_host(g.handle, digest.data(), &derr) != VSYN_OK)
         return OkOrError(std::string("GPU synthesis layer: ") + (derr ? derr : "digest failed"));
+    }
+    // spectral run: each file's rows from the PCM still on the device (vsyn_pcm_spectral_host); a file whose rate the spec does not
+    // fit (fmax above its sr / 2) gets no rows and an error of its own
+    std::vector<std::string> spec_err;
+    uint64_t spec_rows = 0;
+    if (spectral && rc == VSYN_OK) {
+      std::vector<uint32_t> rates(S);
+      spec_err.assign(S, std::string());
+      size_t q0 = 0;
+      for (uint32_t s = 0; s < S; ++s) {
+        const FileRecord& r = *g.pending[s];
+        const double ny = r.header.audio_sample_rate / 2.0, fmax = opts.spectral.fmax > 0.0 ? opts.spectral.fmax : ny;
+        rates[s] = r.header.audio_sample_rate;
+        if (!(fmax <= ny && opts.spectral.fmin < fmax)) {
+          char buf[160];
+          snprintf(buf, sizeof(buf), "spectral: fmin %g / fmax %g do not fit sample rate %u (0 <= fmin < fmax <= sr/2)", opts.spectral.fmin, fmax,
+                   r.header.audio_sample_rate);
+          spec_err[s] = buf;
+          rates[s] = 0;
+        }
+        uint64_t frames = 0;
+        for (size_t q = 0; q < r.batch.pk.size(); ++q) frames += g.emit[q0 + q];
+        q0 += r.batch.pk.size();
+        if (rates[s]) spec_rows += vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(frames, plane));
+      }
+      const uint32_t D = opts.spectral.kind == VSYN_SPEC_MFCC ? opts.spectral.n_mfcc : opts.spectral.n_mels;
+      CHECK_ERR(g.rows.ensure(spec_rows * D + 1));
+      CHECK_ERR(g.seg_rows.ensure(S));
+      vsyn_status sst;
+      const char* serr = nullptr;
+      const int src = vsyn_pcm_spectral_host(g.handle, &opts.spectral, S, rates.data(), g.rows.p, spec_rows, g.seg_rows.p, &sst, &serr);
+      if (src == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
+        for (uint32_t s = 0; s < S; ++s) spec_err[s] = std::string("spectral: ") + (serr ? serr : "refused");
+        for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
+      } else if (src != VSYN_OK) {
+        return OkOrError(std::string("GPU spectral layer: ") + (serr ? serr : "spectral failed"));
+      }
     }
     double t2 = now_s();
     stats.gpu_call_s += t2 - t1;
@@ -444,6 +484,7 @@ struct Feeder {
     // deliver
     std::vector<DataRange<const float>> chans(C);
     p0 = 0;
+    uint64_t row0 = 0;
     for (uint32_t s = 0; s < S; ++s) {
       FileRecord& r = *g.pending[s];
       CorpusFileResult& out = results[r.index];
@@ -458,7 +499,7 @@ struct Feeder {
         CHECK(frames <= plane);
         double acc = 0;
         for (uint32_t c = 0; c < C; ++c) {
-          if (!opts.pcm_s16) {
+          if (!opts.pcm_s16 && !spectral) {
             const float* x = &g.pcm[((size_t)s * C + c) * plane];
             chans[c] = DataRange<const float>(x, frames);
             if (opts.checksum && digest.empty()) acc += abs_sum_f32(x, frames);
@@ -469,7 +510,17 @@ struct Feeder {
         out.abs_sum = acc;
         out.status = r.status;
         stats.frames += frames;
-        if (callbacks) {
+        if (spectral) {
+          const uint32_t D = opts.spectral.kind == VSYN_SPEC_MFCC ? opts.spectral.n_mfcc : opts.spectral.n_mels;
+          const uint64_t nr = g.seg_rows[s];
+          if (!spec_err[s].empty()) out.status = OkOrError(spec_err[s]);
+          out.feature_rows = nr;
+          if (callbacks && !out.status.is_error_) {
+            std::lock_guard<std::mutex> lk(callbacks_mu);
+            if (!callbacks->gotFileFeatures(r.index, r.header, &g.rows[row0 * D], nr, D)) return OkOrError("aborted by gotFileFeatures");
+          }
+          row0 += nr;
+        } else if (callbacks) {
           std::lock_guard<std::mutex> lk(callbacks_mu);
           if (opts.pcm_s16) {
             if (!callbacks->gotFilePcmS16(r.index, r.header, &g.pcm16[(size_t)s * plane * C], frames)) return OkOrError("aborted by gotFilePcmS16");
@@ -735,29 +786,20 @@ extern "C" int ogg_vorbis_decode_corpus_s16(const uint8_t* const* datas, const s
   return 0;
 }
 
-extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
-                                          uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
-                                          uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
-                                          double* stats_out, const char** error_out) {
-  // per calling thread: loader threads may run feature passes side by side
+namespace {
+
+// One pass of a rows run (features or spectral, as set in opts): each file's rows into a malloc'd buffer of its own.
+int rows_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts,
+                float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                const char** error_out) {
+  // per calling thread: loader threads may run passes side by side
   static thread_local char error_buf[256];
   static thread_local std::vector<std::string> file_errors;
+  (void)name;
   if (rows_out)
     for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
-  if (!spec || spec->kind == 0) {
-    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_features_corpus: no feature kind");
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
   std::vector<CorpusItem> items(num_files);
   for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
-  CorpusOptions opts;
-  opts.threads = threads;
-  opts.feeders = feeders;
-  opts.files_per_submit = files_per_submit;
-  opts.device = device;
-  opts.checksum = false;
-  opts.features = *spec;
   std::vector<CorpusFileResult> results;
   CorpusStats st;
   struct CopyOut : CorpusCallbacks {  // gotFileFeatures calls never overlap (CorpusCallbacks)
@@ -788,7 +830,7 @@ extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const siz
     }
     if (ok_out) ok_out[i] = bad ? 0 : 1;
     if (error_out_per_file) {
-      file_errors[i] = results[i].status.is_error_ ? results[i].status.err_msg_ : (copy_out.no_mem[i] ? "features: out of host memory" : "");
+      file_errors[i] = results[i].status.is_error_ ? results[i].status.err_msg_ : (copy_out.no_mem[i] ? std::string(name) + ": out of host memory" : "");
       error_out_per_file[i] = bad ? file_errors[i].c_str() : nullptr;
     }
   }
@@ -808,6 +850,52 @@ extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const siz
   }
   if (error_out) *error_out = nullptr;
   return 0;
+}
+
+CorpusOptions rows_options(int threads, int feeders, uint32_t files_per_submit, int device) {
+  CorpusOptions opts;
+  opts.threads = threads;
+  opts.feeders = feeders;
+  opts.files_per_submit = files_per_submit;
+  opts.device = device;
+  opts.checksum = false;
+  return opts;
+}
+
+}  // namespace
+
+extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
+                                          uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                          double* stats_out, const char** error_out) {
+  static thread_local char error_buf[256];
+  if (!spec || spec->kind == 0) {
+    if (rows_out)
+      for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
+    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_features_corpus: no feature kind");
+    if (error_out) *error_out = error_buf;
+    return 1;
+  }
+  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
+  opts.features = *spec;
+  return rows_corpus("features", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, float** rows_out,
+                                          uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                          double* stats_out, const char** error_out) {
+  static thread_local char error_buf[256];
+  if (!spec || spec->kind == 0) {
+    if (rows_out)
+      for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
+    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_spectral_corpus: no spectral kind");
+    if (error_out) *error_out = error_buf;
+    return 1;
+  }
+  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
+  opts.spectral = *spec;
+  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
 extern "C" void ogg_vorbis_features_free(float* rows) { free(rows); }

@@ -37,7 +37,7 @@ struct CorpusFileResult {
   uint32_t audio_packets = 0;
   uint64_t frames = 0;   // PCM frames (samples per channel) produced
   double abs_sum = 0;    // sum |x| over all channels, in double: a cheap content check that does not need the PCM kept
-  uint64_t feature_rows = 0;  // CorpusOptions::features: rows delivered
+  uint64_t feature_rows = 0;  // CorpusOptions::features / spectral: rows delivered
 };
 
 struct CorpusCallbacks {
@@ -53,8 +53,8 @@ struct CorpusCallbacks {
     (void)file_index; (void)header; (void)interleaved; (void)frames;
     return true;
   }
-  // CorpusOptions::features: the file's feature matrix, num_rows x dim float32 row-major (include/vorbis_synth_hip.h, "feature
-  // matrices"), valid during the call. Called instead of gotFilePcm; a failed file gets no call.
+  // CorpusOptions::features / spectral: the file's feature matrix, num_rows x dim float32 row-major (include/vorbis_synth_hip.h,
+  // "feature matrices" / "spectral features"), valid during the call. Called instead of gotFilePcm; a failed file gets no call.
   virtual bool gotFileFeatures(size_t file_index, const VorbisIdHeader& header, const float* rows, uint64_t num_rows, uint32_t dim) {
     (void)file_index; (void)header; (void)rows; (void)num_rows; (void)dim;
     return true;
@@ -74,6 +74,9 @@ struct CorpusOptions {
   // feature run (features.kind != 0): each file's feature matrix from vsyn_features_host (gotFileFeatures), no synthesis, no PCM.
   // Residue kinds make the workers ship float residue (the VQ stage is off for them).
   vsyn_feature_spec features = {0, 0, 0, 0, 1.0, 1.0f, 0.0f, 1.0f, 0};
+  // spectral run (spectral.kind != 0): synthesis as usual but VSYN_SUBMIT_KEEP_PCM, then each file's spectral rows from the PCM on
+  // the device (vsyn_pcm_spectral_host), delivered through gotFileFeatures; no PCM crosses the bus. Excludes features / pcm_s16.
+  vsyn_spectral_spec spectral = {0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 struct CorpusStats {
@@ -108,9 +111,16 @@ int ogg_vorbis_decode_corpus_s16(const uint8_t* const* datas, const size_t* lens
                                  const uint64_t* pcm_capacity_frames, double* stats_out, const char** error_out);
 // feature run (CorpusOptions::features = *spec), one pass: rows_out (may be NULL) receives per file NULL (failed, or no rows) or a
 // buffer of rows_count_out[i] * spec->output_dim floats allocated by the library, to be released with ogg_vorbis_features_free.
-// error_out_per_file (may be NULL): per file NULL or the file's error text, valid until the next call on the same thread.
+// error_out_per_file (may be NULL): per file NULL or the file's error text, valid until the next call of either corpus function
+// below on the same thread.
 int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
+                               uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                               double* stats_out, const char** error_out);
+// spectral run (CorpusOptions::spectral = *spec), same output contract as ogg_vorbis_features_corpus (dim = n_mfcc for MFCC,
+// n_mels otherwise); rows released with ogg_vorbis_features_free. A file whose rate the spec does not fit fails alone.
+int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                               uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, float** rows_out,
                                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
