@@ -490,6 +490,61 @@ int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_
                          const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames,
                          float* d_rows, uint64_t* d_seg_row_off, void* hip_stream, const char** err);
 
+/* ---- resampling: polyphase resampling of the decoded PCM to a target sample rate, computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, at rate r_in. Output: the same layout at rate r_out.
+ * The arithmetic is scipy.signal.resample_poly(x, up, down) with its defaults (window ('kaiser', 5.0), padtype 'constant'),
+ * which is also librosa's res_type="polyphase". It is NOT soxr (librosa's default res_type); parity with soxr is not a goal.
+ * The device is compared against a float64 model of the arithmetic below (tests/resample_model.py).
+ *
+ *  1. Ratio: g = gcd(r_in, r_out), up = r_out / g, down = r_in / g. If up == down the output is the input, bit for bit.
+ *  2. Filter: M = max(up, down), H = 10 M, N = 2 H + 1. For n in [0, N), m = n - H:
+ *       h[n] = up * w[n] * sinc(m / M) / S,   sinc(x) = sin(pi x) / (pi x), sinc(0) = 1,
+ *       w[n] = I0(5 sqrt(1 - (2 n / (N - 1) - 1)^2)) / I0(5)   (the symmetric Kaiser window, beta 5),
+ *       S    = sum_n w[n] sinc(m / M)                          (firwin's DC normalisation).
+ *     Built in double on the host, per distinct (r_in, r_out) pair, and rounded to float32.
+ *  3. Output: T_out = ceil(T * up / down) frames (vsyn_resample_num_frames), and
+ *       y[j] = sum_i x[i] h[j down - i up + H],   h = 0 outside [0, N), x = 0 outside [0, T)  (scipy's padtype 'constant').
+ *     Polyphase form, as the device computes it: c = j down + H, phi = c mod up, i0 = c div up, K = ceil(N / up),
+ *       y[j] = sum_{t < K} P[phi][t] x[i0 - t],   P[phi][t] = h[phi + t up].
+ *  4. Per segment, per channel: each segment is resampled on its own, zero-padded at both ends; nothing carries across submits.
+ *  5. Limits (VSYN_ERR_INVALID before anything runs): 1 <= r_in, 1 <= r_out, and the reduced M = max(up, down) <= 65536.
+ *
+ * Precision: the taps are float32; every output is one float32 FMA chain over t = 0, 1, ... in that order, so the same input
+ * always gives the same bits. The resample entry points read PCM only: they touch neither stream state, the overlap buffers nor
+ * the PCM kept by VSYN_SUBMIT_KEEP_PCM, and a later vsyn_pcm_fetch_host returns the same PCM. One handle's resample entry points
+ * share its resample workspace. */
+#define VSYN_RESAMPLE_MAX_M 65536u
+
+/* T_out for `frames` input frames (step 3), 0 for an invalid pair (step 5). */
+uint64_t vsyn_resample_num_frames(uint32_t r_in, uint32_t r_out, uint64_t frames);
+
+/* The caller's planar PCM: d_pcm[(g * channels + c) * plane_stride + t], d_frames[S] (device) input frames per segment (clamped
+ * to plane_stride). in_rates[S] is a HOST array of each segment's rate; a rate of 0 skips the segment (0 output frames). Writes
+ * d_out[(g * channels + c) * out_plane_stride + j] for j < T_out(g), and d_out_frames[S] (device) = T_out(g). out_plane_stride
+ * must be at least vsyn_resample_num_frames(in_rates[g], out_rate, plane_stride) for every resampled segment, and below 2^32.
+ * d_out and d_out_frames are in the input form of vsyn_spectral_device (sample rate out_rate). Asynchronous on hip_stream. */
+int vsyn_resample_device(vsyn_handle* h, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, const float* d_pcm,
+                         uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride,
+                         uint32_t* d_out_frames, void* hip_stream, const char** err);
+
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle (with or without VSYN_SUBMIT_KEEP_PCM), resampled per segment
+ * from in_rates[S] (host; 0 skips the segment) to out_rate and copied to the host. frames_out[S] (host) receives each
+ * segment's T_out. out (may be NULL when only the counts are wanted) receives, with out_stride_frames frames per segment:
+ *   VSYN_PCM_F32  float32 PLANAR, out[(g * channels + c) * out_stride_frames + j]
+ *   VSYN_PCM_S16  int16 interleaved, out[(g * out_stride_frames + j) * channels + c], converted as vsyn_pcm_interleave_device does
+ * Frames past a segment's T_out are zero. An out_stride_frames below some segment's T_out is VSYN_ERR_INVALID, with frames_out
+ * filled. Synchronous. */
+int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, int format, void* out,
+                           uint64_t out_stride_frames, uint64_t* frames_out, const char** err);
+
+/* vsyn_pcm_spectral_host on the PCM of the most recent submit resampled to out_rate (what vsyn_resample_device followed by
+ * vsyn_spectral_device at out_rate gives), without the PCM leaving the device. in_rates[S] as for vsyn_pcm_resample_host;
+ * the spec's fmin / fmax are checked against out_rate. Synchronous. */
+int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t num_segments, const uint32_t* in_rates,
+                                    uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status,
+                                    const char** err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,7 @@ _SYMBOLS = [
     "vsyn_attach_vq", "vsyn_submit_device_vq", "vsyn_submit_host_vq", "vsyn_pcm_interleave_device", "vsyn_pcm_abs_sum_host", "vsyn_pcm_fetch_host",
     "vsyn_feature_rows_device", "vsyn_features_device", "vsyn_features_host",
     "vsyn_spectral_num_frames", "vsyn_spectral_device", "vsyn_pcm_spectral_host",
+    "vsyn_resample_num_frames", "vsyn_resample_device", "vsyn_pcm_resample_host", "vsyn_pcm_resample_spectral_host",
 ]
 
 
@@ -254,6 +255,11 @@ def load():
     lib.vsyn_spectral_num_frames.restype = u64
     lib.vsyn_spectral_device.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_spectral_host.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, u64, vp, C.POINTER(Status), cpp]
+    lib.vsyn_resample_num_frames.argtypes = [u32, u32, u64]
+    lib.vsyn_resample_num_frames.restype = u64
+    lib.vsyn_resample_device.argtypes = [vp, u32, vp, u32, vp, u64, u32, vp, vp, u64, vp, vp, cpp]
+    lib.vsyn_pcm_resample_host.argtypes = [vp, u32, vp, u32, C.c_int, vp, u64, vp, cpp]
+    lib.vsyn_pcm_resample_spectral_host.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, u32, vp, u64, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -375,6 +381,34 @@ class Synth:
                                            d_seg_row_off, stream, C.byref(err))
         if rc != VSYN_OK:
             raise VsynError(rc, (err.value or b"").decode())
+
+    def resample_device(self, in_rates, out_rate, d_pcm, plane_stride, channels, d_frames, d_out, out_plane_stride, d_out_frames,
+                        stream=None):
+        """vsyn_resample_device on device pointers (ints); in_rates is a host sequence."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_resample_device(self.h, len(rates), _ptr(rates), out_rate, d_pcm, plane_stride, channels, d_frames, d_out,
+                                           out_plane_stride, d_out_frames, stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+
+    def pcm_resample_host(self, in_rates, out_rate, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_resample_host over the last submit's segments: returns (pcm, frames [S]); pcm is float32 [S][C][stride] (planar)
+        or int16 [S][stride][C] (interleaved), stride = the largest T_out."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S = len(rates)
+        frames = np.zeros(max(1, S), np.uint64)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pcm_resample_host(self.h, S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        stride = max(1, int(frames[:S].max()) if S else 1)
+        C_ = self.channels
+        out = np.zeros((S, C_, stride), np.float32) if fmt == VSYN_PCM_F32 else np.zeros((S, stride, C_), np.int16)
+        rc = self.lib.vsyn_pcm_resample_host(self.h, S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        return out, frames[:S]
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

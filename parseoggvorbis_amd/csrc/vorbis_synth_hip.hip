@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -27,6 +28,7 @@
 #include "vsyn_pcm.h"
 #include "vsyn_features.h"
 #include "vsyn_spectral.h"
+#include "vsyn_resample.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846264338327
@@ -204,6 +206,17 @@ struct vsyn_handle {
   DevBuf<uint32_t> sp_segF, sp_segmax;
   DevBuf<uint64_t> sp_segoff;
   DevBuf<float> sp_db, sp_rows;
+  // resampling (vsyn_resample.h): buffers of its own; the PCM is only read
+  DevBuf<uint8_t> rs_tab;
+  uint8_t* rs_tab_host = nullptr;      // page-locked copy of the tables (the upload is asynchronous)
+  size_t rs_tab_host_cap = 0;
+  hipEvent_t rs_ev = nullptr;          // recorded behind the table upload: the host copy is reused only after it
+  bool rs_ev_valid = false;
+  bool rs_lds_set = false;             // vsyn_rs_kernel<true>'s dynamic-LDS limit is raised on this handle's device
+  DevBuf<uint32_t> rs_inF, rs_outF;
+  DevBuf<uint64_t> rs_off;
+  DevBuf<float> rs_pcm;                // host forms: the resampled PCM
+  DevBuf<int16_t> rs_s16;              // vsyn_pcm_resample_host, VSYN_PCM_S16
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -572,6 +585,8 @@ void vsyn_destroy(vsyn_handle* h) {
   if (h->ft_tab_host) (void)hipHostFree(h->ft_tab_host);
   if (h->sp_ev) (void)hipEventDestroy(h->sp_ev);
   if (h->sp_tab_host) (void)hipHostFree(h->sp_tab_host);
+  if (h->rs_ev) (void)hipEventDestroy(h->rs_ev);
+  if (h->rs_tab_host) (void)hipHostFree(h->rs_tab_host);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->pre) (void)hipStreamDestroy(h->pre);
   if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
@@ -1782,6 +1797,324 @@ int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint3
   const uint64_t D = spec_dim(spec);
   HIPCHK(h->sp_rows.ensure(total * D + 1));
   rc = spec_launch(h, spec, S, sample_rates, h->st_pcm.p, plane, h->H.channels, nullptr, d_si, f_max, total, h->sp_rows.p, nullptr, hs, err);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+  vsyn_status st;
+  rc = vsyn_sync_status(h, hs, &st, err);
+  if (status) *status = st;
+  return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// resampling (vsyn_resample.h; semantics in the header)
+// ------------------------------------------------------------------------------------------------
+// vsyn_rs_kernel<true> holds one pair's table and one tile's input span in LDS. 80 KiB keeps two of its workgroups on a CU
+// (160 KiB) at worst and takes every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1 and 48 kHz but 11.025 <-> 32 kHz (115 / 122
+// KiB); 44.1 -> 16 kHz needs 46 KiB. Bigger tables (11.025 <-> 32 kHz; 44056 -> 16000 = 2000 / 5507, 448 KiB) use
+// vsyn_rs_kernel<false>.
+static const uint32_t RS_LDS_BUDGET = 80u * 1024u;
+
+// The reduced ratio of a pair; false for a pair the contract refuses (a rate of 0, or M above VSYN_RESAMPLE_MAX_M).
+static bool rs_ratio(uint32_t r_in, uint32_t r_out, uint32_t* up, uint32_t* down) {
+  if (!r_in || !r_out) return false;
+  const uint32_t g = std::gcd(r_in, r_out);
+  *up = r_out / g;
+  *down = r_in / g;
+  return std::max(*up, *down) <= VSYN_RESAMPLE_MAX_M;
+}
+
+static double rs_i0(double x) {  // modified Bessel function of the first kind, order 0: sum_k ((x/2)^k / k!)^2
+  const double q = 0.25 * x * x;
+  double s = 1.0, t = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    t *= q / ((double)k * (double)k);
+    s += t;
+    if (t < 1e-17 * s) break;
+  }
+  return s;
+}
+
+// h[0 .. N) of the header's step 2, in double.
+static void rs_taps(uint32_t up, uint32_t down, std::vector<double>& h) {
+  const uint32_t M = std::max(up, down), H = 10u * M, N = 2u * H + 1u;
+  h.assign(N, 0.0);
+  const double i0b = rs_i0(5.0);
+  double S = 0.0;
+  for (uint32_t n = 0; n < N; ++n) {
+    const double m = (double)n - (double)H, xs = M_PI * m / (double)M, r = 2.0 * n / (double)(N - 1u) - 1.0;
+    const double sinc = m == 0.0 ? 1.0 : sin(xs) / xs;
+    h[n] = rs_i0(5.0 * sqrt(std::max(0.0, 1.0 - r * r))) / i0b * sinc;
+    S += h[n];
+  }
+  for (uint32_t n = 0; n < N; ++n) h[n] = up * h[n] / S;
+}
+
+struct RsPlan {
+  std::vector<uint8_t> tab;
+  uint64_t chunks[2] = {0, 0};  // grid bounds of vsyn_rs_kernel<true> / <false>
+  uint32_t lds_bytes = 0;       // dynamic LDS of vsyn_rs_kernel<true>
+};
+
+// RsHeader, RsPair per distinct pair, seg_pair[S], the polyphase tables. rates[g] = 0 skips g; every other pair is valid (checked
+// by the caller). plane bounds every segment's input frames.
+static void rs_build_table(uint32_t S, const uint32_t* rates, uint32_t out_rate, uint32_t C, uint64_t plane, RsPlan& plan) {
+  std::vector<uint32_t> seg_pair(S, RS_SKIP), keys;
+  std::vector<RsPair> pairs;
+  uint64_t taps = 0;
+  const uint64_t T_max = std::min<uint64_t>(plane, 0xFFFFFFFFull);
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!rates[g]) continue;
+    auto it = std::find(keys.begin(), keys.end(), rates[g]);
+    seg_pair[g] = (uint32_t)(it - keys.begin());
+    if (it == keys.end()) {
+      keys.push_back(rates[g]);
+      RsPair p = {};
+      rs_ratio(rates[g], out_rate, &p.up, &p.down);
+      p.lds = 1;
+      if (p.up != p.down) {
+        const uint32_t M = std::max(p.up, p.down), N = 20u * M + 1u, K = (N + p.up - 1u) / p.up;
+        p.h = 10u * M;
+        p.k4 = (K + 3u) & ~3u;
+        p.span4 = rs_span4(p.up, p.down, p.k4);
+        p.tab = taps;
+        taps += (uint64_t)p.up * p.k4;
+        const uint64_t lds = 4ull * ((uint64_t)p.up * p.k4 + 4ull * p.span4);
+        p.lds = lds <= RS_LDS_BUDGET;
+        if (p.lds) plan.lds_bytes = std::max(plan.lds_bytes, (uint32_t)lds);
+      }
+      pairs.push_back(p);
+    }
+    const RsPair& p = pairs[seg_pair[g]];
+    plan.chunks[p.lds ? 0 : 1] += (uint64_t)C * ((rs_num_frames(T_max, p.up, p.down) + RS_CHUNK - 1u) / RS_CHUNK);
+  }
+  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  RsHeader hd = {(uint32_t)pairs.size(), S, 0, 0};
+  const size_t off_pairs = sizeof(RsHeader);
+  hd.off_seg = (uint32_t)al(off_pairs + sizeof(RsPair) * pairs.size());
+  const size_t off_taps = al(hd.off_seg + 4ull * S);
+  for (RsPair& p : pairs) p.tab += off_taps / 4u;
+  plan.tab.assign(off_taps + 4ull * taps + 16, 0);
+  uint8_t* o = plan.tab.data();
+  memcpy(o, &hd, sizeof(hd));
+  if (!pairs.empty()) memcpy(o + off_pairs, pairs.data(), sizeof(RsPair) * pairs.size());
+  if (S) memcpy(o + hd.off_seg, seg_pair.data(), 4ull * S);
+  std::vector<double> h;
+  for (const RsPair& p : pairs) {
+    if (p.up == p.down) continue;
+    rs_taps(p.up, p.down, h);
+    float* P = (float*)o + p.tab;
+    for (uint32_t phi = 0; phi < p.up; ++phi)
+      for (uint32_t t = 0; t < p.k4; ++t) {
+        const uint64_t n = phi + (uint64_t)t * p.up;
+        P[(size_t)phi * p.k4 + t] = n < h.size() ? (float)h[n] : 0.0f;
+      }
+  }
+}
+
+// The checks of every segment's pair (0 = skipped segment).
+static int rs_check(uint32_t S, const uint32_t* rates, uint32_t out_rate, const char** err) {
+  if (!out_rate) return fail(err, VSYN_ERR_INVALID, "out_rate must be >= 1");
+  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "in_rates is NULL");
+  for (uint32_t g = 0; g < S; ++g) {
+    uint32_t up, down;
+    if (rates[g] && !rs_ratio(rates[g], out_rate, &up, &down))
+      return fail(err, VSYN_ERR_INVALID, "segment %u: %u -> %u Hz reduces to %u / %u, above the limit max(up, down) <= %u", g, rates[g],
+                  out_rate, up, down, VSYN_RESAMPLE_MAX_M);
+  }
+  return VSYN_OK;
+}
+
+// Offsets and resample kernels on stream s; frames from d_frames, else from si. Caller holds h->mu and has run rs_check, and
+// out_plane holds every segment's T_out.
+static int rs_launch(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, const float* d_pcm, uint64_t plane, uint32_t C,
+                     const uint32_t* d_frames, const SegInfo* si, float* d_out, uint64_t out_plane, uint32_t* d_out_frames, hipStream_t s,
+                     const char** err) {
+  RsPlan plan;
+  rs_build_table(S, rates, out_rate, C, plane, plan);
+  if (plan.chunks[0] > 0x7FFFFFFFull || plan.chunks[1] > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too much output for one call");
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->rs_lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_rs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_LDS_BUDGET));
+    h->rs_lds_set = true;
+  }
+  const std::vector<uint8_t>& tab = plan.tab;
+  HIPCHK(h->rs_tab.ensure(tab.size()));
+  HIPCHK(h->rs_inF.ensure(S));
+  HIPCHK(h->rs_outF.ensure(S));
+  HIPCHK(h->rs_off.ensure(2ull * S + 2));
+  if (!h->rs_ev) HIPCHK(hipEventCreateWithFlags(&h->rs_ev, hipEventDisableTiming));
+  if (h->rs_ev_valid) HIPCHK(hipEventSynchronize(h->rs_ev));  // the previous upload has read the host copy
+  if (h->rs_tab_host_cap < tab.size()) {
+    if (h->rs_tab_host) HIPCHK(hipHostFree(h->rs_tab_host));
+    h->rs_tab_host = nullptr;
+    h->rs_tab_host_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&h->rs_tab_host, tab.size() + 4096, hipHostMallocDefault));
+    h->rs_tab_host_cap = tab.size() + 4096;
+  }
+  memcpy(h->rs_tab_host, tab.data(), tab.size());
+  HIPCHK(hipMemcpyAsync(h->rs_tab.p, h->rs_tab_host, tab.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(h->rs_ev, s));
+  h->rs_ev_valid = true;
+  RsCtx A;
+  A.tab = h->rs_tab.p;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.out = d_out;
+  A.out_plane = out_plane;
+  A.in_frames = h->rs_inF.p;
+  A.out_frames = d_out_frames ? d_out_frames : h->rs_outF.p;
+  A.off = h->rs_off.p;
+  hipLaunchKernelGGL(vsyn_rs_offsets_kernel, dim3(1), dim3(RS_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  if (plan.chunks[0]) {
+    hipLaunchKernelGGL(vsyn_rs_kernel<true>, dim3((uint32_t)plan.chunks[0]), dim3(RS_THREADS), plan.lds_bytes, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  if (plan.chunks[1]) {
+    hipLaunchKernelGGL(vsyn_rs_kernel<false>, dim3((uint32_t)plan.chunks[1]), dim3(RS_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  return VSYN_OK;
+}
+
+// The last submit's input frames per segment (clamped to its plane) and, for rates[g] != 0, T_out; the host copy of SegInfo.
+static int rs_last_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, std::vector<uint64_t>& T_out,
+                          const char** err) {
+  if (h->last_S == 0 || h->last_host_plane == 0) return fail(err, VSYN_ERR_INVALID, "no vsyn_submit_host on this handle yet");
+  if (S != h->last_S) return fail(err, VSYN_ERR_INVALID, "num_segments %u differs from the last submit's %u", S, h->last_S);
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<SegInfo> si(S);
+  HIPCHK(hipMemcpyAsync(si.data(), h->ws_seg[h->last_wb].p, sizeof(SegInfo) * S, hipMemcpyDeviceToHost, h->host_stream));
+  HIPCHK(hipStreamSynchronize(h->host_stream));
+  T_out.assign(S, 0);
+  for (uint32_t g = 0; g < S; ++g) {
+    uint32_t up, down;
+    if (rates[g] && rs_ratio(rates[g], out_rate, &up, &down))
+      T_out[g] = rs_num_frames(std::min<uint64_t>(si[g].total_emit, h->last_host_plane), up, down);
+  }
+  return VSYN_OK;
+}
+
+extern "C" {
+
+uint64_t vsyn_resample_num_frames(uint32_t r_in, uint32_t r_out, uint64_t frames) {
+  uint32_t up, down;
+  if (!rs_ratio(r_in, r_out, &up, &down)) return 0;
+  const unsigned __int128 n = ((unsigned __int128)frames * up + down - 1u) / down;
+  return n > (unsigned __int128)UINT64_MAX ? 0 : (uint64_t)n;
+}
+
+int vsyn_resample_device(vsyn_handle* h, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, const float* d_pcm, uint64_t plane_stride,
+                         uint32_t channels, const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride, uint32_t* d_out_frames,
+                         void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = rs_check(S, in_rates, out_rate, err);
+  if (rc) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_out || !d_out_frames || plane_stride == 0 || channels == 0 || channels > 255)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  if (out_plane_stride > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_plane_stride must be below 2^32");
+  const uint64_t T_max = std::min<uint64_t>(plane_stride, 0xFFFFFFFFull);
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!in_rates[g]) continue;
+    const uint64_t need = vsyn_resample_num_frames(in_rates[g], out_rate, T_max);
+    if (need > out_plane_stride)
+      return fail(err, VSYN_ERR_INVALID, "segment %u: out_plane_stride %llu below %llu frames", g, (unsigned long long)out_plane_stride,
+                  (unsigned long long)need);
+  }
+  std::lock_guard<std::mutex> lk(h->mu);
+  return rs_launch(h, S, in_rates, out_rate, d_pcm, plane_stride, channels, d_frames, nullptr, d_out, out_plane_stride, d_out_frames,
+                   (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, int format, void* out,
+                           uint64_t out_stride_frames, uint64_t* frames_out, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = rs_check(S, in_rates, out_rate, err);
+  if (rc) return rc;
+  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
+  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
+  // the lock covers the whole call: the resample workspace is the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T_out;
+  rc = rs_last_frames(h, S, in_rates, out_rate, T_out, err);
+  if (rc) return rc;
+  uint64_t t_max = 0;
+  for (uint32_t g = 0; g < S; ++g) {
+    frames_out[g] = T_out[g];
+    t_max = std::max(t_max, T_out[g]);
+  }
+  if (!out || S == 0) return VSYN_OK;
+  if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
+                                             (unsigned long long)out_stride_frames, (unsigned long long)t_max);
+  if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
+  const uint32_t C = h->H.channels;
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * C * out_stride_frames;
+  HIPCHK(h->rs_pcm.ensure(n + 1));
+  if (format == VSYN_PCM_F32) HIPCHK(hipMemsetAsync(h->rs_pcm.p, 0, sizeof(float) * n, hs));  // zeros past each segment's T_out
+  rc = rs_launch(h, S, in_rates, out_rate, h->st_pcm.p, h->last_host_plane, C, nullptr, h->ws_seg[h->last_wb].p, h->rs_pcm.p,
+                 out_stride_frames, h->rs_outF.p, hs, err);
+  if (rc) return rc;
+  if (format == VSYN_PCM_F32) {
+    HIPCHK(hipMemcpyAsync(out, h->rs_pcm.p, sizeof(float) * n, hipMemcpyDeviceToHost, hs));
+  } else {
+    HIPCHK(h->rs_s16.ensure(n + 1));
+    const dim3 grid((uint32_t)((out_stride_frames + 255) / 256), S);
+    hipLaunchKernelGGL(vsyn_rs_s16_kernel, grid, dim3(256), 0, hs, h->rs_pcm.p, out_stride_frames, C, h->rs_outF.p, h->rs_s16.p, out_stride_frames);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, h->rs_s16.p, sizeof(int16_t) * n, hipMemcpyDeviceToHost, hs));
+  }
+  HIPCHK(hipStreamSynchronize(hs));
+  return VSYN_OK;
+}
+
+int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
+                                    float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (status) {
+    status->flags = 0;
+    status->first_bad_packet = 0xFFFFFFFFu;
+  }
+  int rc = rs_check(S, in_rates, out_rate, err);
+  if (rc) return rc;
+  std::vector<uint32_t> sp_rates(S);  // the spectral pass sees every resampled segment at out_rate
+  for (uint32_t g = 0; g < S; ++g) sp_rates[g] = in_rates[g] ? out_rate : 0u;
+  rc = spec_check(spec, S, sp_rates.data(), err);
+  if (rc) return rc;
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T_out;
+  rc = rs_last_frames(h, S, in_rates, out_rate, T_out, err);
+  if (rc) return rc;
+  const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
+  uint64_t total = 0, f_max = 0, t_max = 1;
+  for (uint32_t g = 0; g < S; ++g) {
+    const uint64_t f = sp_rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, center, T_out[g]) : 0;
+    seg_rows[g] = f;
+    total += f;
+    f_max = std::max(f_max, f);
+    t_max = std::max(t_max, T_out[g]);
+  }
+  if (!rows || total == 0) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
+  const uint32_t C = h->H.channels;
+  hipStream_t hs = h->host_stream;
+  HIPCHK(h->rs_pcm.ensure((size_t)S * C * t_max + 1));
+  rc = rs_launch(h, S, in_rates, out_rate, h->st_pcm.p, h->last_host_plane, C, nullptr, h->ws_seg[h->last_wb].p, h->rs_pcm.p, t_max,
+                 h->rs_outF.p, hs, err);
+  if (rc) return rc;
+  const uint64_t D = spec_dim(spec);
+  HIPCHK(h->sp_rows.ensure(total * D + 1));
+  rc = spec_launch(h, spec, S, sp_rates.data(), h->rs_pcm.p, t_max, C, h->rs_outF.p, nullptr, f_max, total, h->sp_rows.p, nullptr, hs, err);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
   vsyn_status st;

@@ -10,6 +10,7 @@
 #include <deque>
 #include <map>
 #include <mutex>
+#include <numeric>
 #include <thread>
 
 namespace {
@@ -360,8 +361,9 @@ struct Feeder {
     }
     CHECK_ERR(g.emit.ensure(P));
     const bool spectral = spectral_run(opts);  // the PCM stays on the device: only the spectral rows come back
+    const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
     if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * C * plane));
-    else if (!spectral) CHECK_ERR(g.pcm.ensure((size_t)S * C * plane));
+    else if (!spectral && !resample) CHECK_ERR(g.pcm.ensure((size_t)S * C * plane));
     size_t p0 = 0, r0 = 0, c0 = 0, e0 = 0;
     for (uint32_t s = 0; s < S; ++s) {
       const PacketBatch& b = g.pending[s]->batch;
@@ -402,8 +404,8 @@ struct Feeder {
     vsyn_status st = {0, 0xffffffffu};
     const char* err = nullptr;
     int rc;
-    const uint32_t sflags = (opts.pcm_s16 || spectral) ? VSYN_SUBMIT_KEEP_PCM : 0u;
-    float* pcm_out = (opts.pcm_s16 || spectral) ? nullptr : g.pcm.p;
+    const uint32_t sflags = (opts.pcm_s16 || spectral || resample) ? VSYN_SUBMIT_KEEP_PCM : 0u;
+    float* pcm_out = (opts.pcm_s16 || spectral || resample) ? nullptr : g.pcm.p;
     if (g.vq) {
       vsyn_vq_batch vqb;
       vqb.packets = g.vq_pk.p;
@@ -415,18 +417,63 @@ struct Feeder {
     } else {
       rc = vsyn_submit_host(g.handle, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, g.residue.p, rfloats, pcm_out, plane, g.emit.p, nullptr, sflags, &st, &err);
     }
-    if (opts.pcm_s16 && rc == VSYN_OK) {
+    if (opts.pcm_s16 && !resample && rc == VSYN_OK) {
       const char* ferr = nullptr;
       if (vsyn_pcm_fetch_host(g.handle, VSYN_PCM_S16, g.pcm16.p, plane, nullptr, &ferr) != VSYN_OK)
         return OkOrError(std::string("GPU synthesis layer: ") + (ferr ? ferr : "pcm fetch failed"));
     }
     // per-(file, channel) digests from the device, where the PCM still is (a host pass over it cost more than the decode's GPU calls)
     std::vector<double> digest;
-    if (opts.checksum && rc == VSYN_OK) {
+    if (opts.checksum && !resample && rc == VSYN_OK) {
       digest.resize((size_t)S * C);
       const char* derr = nullptr;
       if (vsyn_pcm_abs_sum_host(g.handle, digest.data(), &derr) != VSYN_OK)
         return OkOrError(std::string("GPU synthesis layer: ") + (derr ? derr : "digest failed"));
+    }
+    // resampled run: each file's PCM resampled on the device from its own rate to resample_rate (vsyn_pcm_resample_host, or for a
+    // spectral run vsyn_pcm_resample_spectral_host below); a file whose ratio the contract refuses gets no output and an error of
+    // its own
+    std::vector<std::string> rs_err;
+    std::vector<uint32_t> rs_rates;
+    std::vector<uint64_t> rs_frames;
+    uint64_t rs_plane = 1;
+    if (resample && rc == VSYN_OK) {
+      rs_err.assign(S, std::string());
+      rs_rates.assign(S, 0u);
+      rs_frames.assign(S, 0u);
+      size_t q0 = 0;
+      for (uint32_t s = 0; s < S; ++s) {
+        const FileRecord& r = *g.pending[s];
+        const uint32_t sr = r.header.audio_sample_rate;
+        uint64_t frames = 0;
+        for (size_t q = 0; q < r.batch.pk.size(); ++q) frames += g.emit[q0 + q];
+        q0 += r.batch.pk.size();
+        if (vsyn_resample_num_frames(sr, opts.resample_rate, 1) == 0) {
+          const uint32_t gd = sr ? std::gcd(sr, opts.resample_rate) : 1u;
+          char buf[160];
+          snprintf(buf, sizeof(buf), "resample: %u -> %u Hz reduces to %u / %u, above the limit max(up, down) <= %u", sr, opts.resample_rate,
+                   opts.resample_rate / gd, sr / gd, VSYN_RESAMPLE_MAX_M);
+          rs_err[s] = buf;
+          continue;
+        }
+        rs_rates[s] = sr;
+        rs_frames[s] = vsyn_resample_num_frames(sr, opts.resample_rate, std::min<uint64_t>(frames, plane));
+        rs_plane = std::max(rs_plane, rs_frames[s]);
+      }
+      if (!spectral) {
+        const char* rerr = nullptr;
+        std::vector<uint64_t> got(S);
+        int rrc;
+        if (opts.pcm_s16) {
+          CHECK_ERR(g.pcm16.ensure((size_t)S * C * rs_plane));
+          rrc = vsyn_pcm_resample_host(g.handle, S, rs_rates.data(), opts.resample_rate, VSYN_PCM_S16, g.pcm16.p, rs_plane, got.data(), &rerr);
+        } else {
+          CHECK_ERR(g.pcm.ensure((size_t)S * C * rs_plane));
+          rrc = vsyn_pcm_resample_host(g.handle, S, rs_rates.data(), opts.resample_rate, VSYN_PCM_F32, g.pcm.p, rs_plane, got.data(), &rerr);
+        }
+        if (rrc != VSYN_OK) return OkOrError(std::string("GPU resample layer: ") + (rerr ? rerr : "resample failed"));
+        CHECK(got == rs_frames);
+      }
     }
     // spectral run: each file's rows from the PCM still on the device (vsyn_pcm_spectral_host); a file whose rate the spec does not
     // fit (fmax above its sr / 2) gets no rows and an error of its own
@@ -438,26 +485,34 @@ struct Feeder {
       size_t q0 = 0;
       for (uint32_t s = 0; s < S; ++s) {
         const FileRecord& r = *g.pending[s];
-        const double ny = r.header.audio_sample_rate / 2.0, fmax = opts.spectral.fmax > 0.0 ? opts.spectral.fmax : ny;
+        const uint32_t sr = resample ? opts.resample_rate : r.header.audio_sample_rate;  // the rate the rows are computed at
+        const double ny = sr / 2.0, fmax = opts.spectral.fmax > 0.0 ? opts.spectral.fmax : ny;
         rates[s] = r.header.audio_sample_rate;
         if (!(fmax <= ny && opts.spectral.fmin < fmax)) {
           char buf[160];
           snprintf(buf, sizeof(buf), "spectral: fmin %g / fmax %g do not fit sample rate %u (0 <= fmin < fmax <= sr/2)", opts.spectral.fmin, fmax,
-                   r.header.audio_sample_rate);
+                   sr);
           spec_err[s] = buf;
+          rates[s] = 0;
+        }
+        if (resample && !rs_err[s].empty()) {
+          spec_err[s] = rs_err[s];
           rates[s] = 0;
         }
         uint64_t frames = 0;
         for (size_t q = 0; q < r.batch.pk.size(); ++q) frames += g.emit[q0 + q];
         q0 += r.batch.pk.size();
-        if (rates[s]) spec_rows += vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(frames, plane));
+        if (resample) frames = rs_frames[s];
+        if (rates[s]) spec_rows += vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(frames, resample ? rs_plane : plane));
       }
       const uint32_t D = opts.spectral.kind == VSYN_SPEC_MFCC ? opts.spectral.n_mfcc : opts.spectral.n_mels;
       CHECK_ERR(g.rows.ensure(spec_rows * D + 1));
       CHECK_ERR(g.seg_rows.ensure(S));
       vsyn_status sst;
       const char* serr = nullptr;
-      const int src = vsyn_pcm_spectral_host(g.handle, &opts.spectral, S, rates.data(), g.rows.p, spec_rows, g.seg_rows.p, &sst, &serr);
+      const int src = resample ? vsyn_pcm_resample_spectral_host(g.handle, &opts.spectral, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
+                                                                 g.seg_rows.p, &sst, &serr)
+                               : vsyn_pcm_spectral_host(g.handle, &opts.spectral, S, rates.data(), g.rows.p, spec_rows, g.seg_rows.p, &sst, &serr);
       if (src == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
         for (uint32_t s = 0; s < S; ++s) spec_err[s] = std::string("spectral: ") + (serr ? serr : "refused");
         for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
@@ -497,10 +552,13 @@ struct Feeder {
         uint64_t frames = 0;
         for (size_t q = 0; q < r.batch.pk.size(); ++q) frames += g.emit[p0 + q];
         CHECK(frames <= plane);
+        const uint64_t pl = resample ? rs_plane : plane;  // the delivered PCM's plane
+        const bool rs_bad = resample && !rs_err[s].empty();
+        if (resample) frames = rs_frames[s];
         double acc = 0;
         for (uint32_t c = 0; c < C; ++c) {
           if (!opts.pcm_s16 && !spectral) {
-            const float* x = &g.pcm[((size_t)s * C + c) * plane];
+            const float* x = &g.pcm[((size_t)s * C + c) * pl];
             chans[c] = DataRange<const float>(x, frames);
             if (opts.checksum && digest.empty()) acc += abs_sum_f32(x, frames);
           }
@@ -509,6 +567,8 @@ struct Feeder {
         out.frames = frames;
         out.abs_sum = acc;
         out.status = r.status;
+        if (resample) out.sample_rate = opts.resample_rate;
+        if (rs_bad) out.status = OkOrError(rs_err[s]);
         stats.frames += frames;
         if (spectral) {
           const uint32_t D = opts.spectral.kind == VSYN_SPEC_MFCC ? opts.spectral.n_mfcc : opts.spectral.n_mels;
@@ -520,10 +580,10 @@ struct Feeder {
             if (!callbacks->gotFileFeatures(r.index, r.header, &g.rows[row0 * D], nr, D)) return OkOrError("aborted by gotFileFeatures");
           }
           row0 += nr;
-        } else if (callbacks) {
+        } else if (callbacks && !rs_bad) {
           std::lock_guard<std::mutex> lk(callbacks_mu);
           if (opts.pcm_s16) {
-            if (!callbacks->gotFilePcmS16(r.index, r.header, &g.pcm16[(size_t)s * plane * C], frames)) return OkOrError("aborted by gotFilePcmS16");
+            if (!callbacks->gotFilePcmS16(r.index, r.header, &g.pcm16[(size_t)s * pl * C], frames)) return OkOrError("aborted by gotFilePcmS16");
           } else if (!callbacks->gotFilePcm(r.index, r.header, chans)) {
             return OkOrError("aborted by gotFilePcm");
           }
@@ -896,6 +956,109 @@ extern "C" int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const siz
   CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
   opts.spectral = *spec;
   return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_sr(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                             uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                             float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                             double* stats_out, const char** error_out) {
+  static thread_local char error_buf[256];
+  if (!spec || spec->kind == 0) {
+    if (rows_out)
+      for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
+    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_spectral_corpus_sr: no spectral kind");
+    if (error_out) *error_out = error_buf;
+    return 1;
+  }
+  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
+  opts.spectral = *spec;
+  opts.resample_rate = target_rate;
+  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+extern "C" int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                     uint32_t files_per_submit, int device, uint32_t target_rate, int format, void** pcm_out, uint64_t* frames_out,
+                                     uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file,
+                                     double* stats_out, const char** error_out) {
+  static thread_local char error_buf[256];
+  static thread_local std::vector<std::string> file_errors;
+  if (pcm_out)
+    for (size_t i = 0; i < num_files; ++i) pcm_out[i] = nullptr;
+  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) {
+    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_pcm_corpus: unknown PCM format %d", format);
+    if (error_out) *error_out = error_buf;
+    return 1;
+  }
+  std::vector<CorpusItem> items(num_files);
+  for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
+  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
+  opts.pcm_s16 = format == VSYN_PCM_S16;
+  opts.resample_rate = target_rate;
+  std::vector<CorpusFileResult> results;
+  CorpusStats st;
+  struct CopyOut : CorpusCallbacks {  // the callbacks never overlap (CorpusCallbacks)
+    void** out = nullptr;
+    std::vector<uint8_t> no_mem;
+    bool gotFilePcm(size_t i, const VorbisIdHeader&, const std::vector<DataRange<const float>>& ch) override {
+      const size_t n = ch.empty() ? 0 : ch[0].size();
+      if (!n) return true;
+      float* p = (float*)malloc(n * ch.size() * sizeof(float));
+      if (!p) {
+        no_mem[i] = 1;
+        return true;
+      }
+      for (size_t c = 0; c < ch.size(); ++c) memcpy(p + c * n, ch[c].begin(), n * sizeof(float));
+      out[i] = p;
+      return true;
+    }
+    bool gotFilePcmS16(size_t i, const VorbisIdHeader& h, const int16_t* x, uint64_t frames) override {
+      if (!frames) return true;
+      const size_t bytes = (size_t)frames * h.audio_channels * sizeof(int16_t);
+      void* p = malloc(bytes);
+      if (!p) {
+        no_mem[i] = 1;
+        return true;
+      }
+      memcpy(p, x, bytes);
+      out[i] = p;
+      return true;
+    }
+  } copy_out;
+  copy_out.out = pcm_out;
+  copy_out.no_mem.assign(num_files, 0);
+  OkOrError r = decode_corpus(items, opts, pcm_out ? &copy_out : nullptr, results, &st);
+  file_errors.assign(num_files, std::string());
+  for (size_t i = 0; i < results.size() && i < num_files; ++i) {
+    const bool bad = results[i].status.is_error_ || copy_out.no_mem[i];
+    if (bad && pcm_out && pcm_out[i]) {
+      free(pcm_out[i]);
+      pcm_out[i] = nullptr;
+    }
+    if (frames_out) frames_out[i] = bad ? 0 : results[i].frames;
+    if (channels_out) channels_out[i] = results[i].channels;
+    if (rate_out) rate_out[i] = results[i].sample_rate;
+    if (ok_out) ok_out[i] = bad ? 0 : 1;
+    if (error_out_per_file) {
+      file_errors[i] = results[i].status.is_error_ ? results[i].status.err_msg_ : (copy_out.no_mem[i] ? "pcm: out of host memory" : "");
+      error_out_per_file[i] = bad ? file_errors[i].c_str() : nullptr;
+    }
+  }
+  if (stats_out) {
+    const double v[8] = {st.wall_s, st.entropy_cpu_s, st.gpu_call_s, st.pack_s, st.deliver_s, (double)st.submits, (double)st.audio_packets, (double)st.frames};
+    for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+  }
+  if (r.is_error_) {
+    if (pcm_out)
+      for (size_t i = 0; i < num_files; ++i) {
+        free(pcm_out[i]);
+        pcm_out[i] = nullptr;
+      }
+    snprintf(error_buf, sizeof(error_buf), "%s", r.err_msg_.c_str());
+    if (error_out) *error_out = error_buf;
+    return 1;
+  }
+  if (error_out) *error_out = nullptr;
+  return 0;
 }
 
 extern "C" void ogg_vorbis_features_free(float* rows) { free(rows); }

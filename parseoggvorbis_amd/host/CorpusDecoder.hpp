@@ -77,6 +77,11 @@ struct CorpusOptions {
   // spectral run (spectral.kind != 0): synthesis as usual but VSYN_SUBMIT_KEEP_PCM, then each file's spectral rows from the PCM on
   // the device (vsyn_pcm_spectral_host), delivered through gotFileFeatures; no PCM crosses the bus. Excludes features / pcm_s16.
   vsyn_spectral_spec spectral = {0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  // resample_rate != 0: the PCM (f32 or pcm_s16) and the spectral rows are those of each file's PCM resampled on the device from
+  // its own rate to resample_rate (include/vorbis_synth_hip.h, "resampling"); frames and sample_rate in the results are the
+  // resampled ones, and abs_sum is taken over the delivered f32 PCM (0 for pcm_s16). The mel table and the fmin / fmax check of a
+  // spectral run use resample_rate. A file whose reduced ratio exceeds the limit fails alone. Not for feature runs.
+  uint32_t resample_rate = 0;
 };
 
 struct CorpusStats {
@@ -123,6 +128,20 @@ int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const size_t* lens, 
                                uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, float** rows_out,
                                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                double* stats_out, const char** error_out);
+// spectral run of the PCM resampled to target_rate (CorpusOptions::resample_rate; 0 = each file's own rate, as
+// ogg_vorbis_spectral_corpus). Same output contract as ogg_vorbis_spectral_corpus.
+int ogg_vorbis_spectral_corpus_sr(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                  uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                  float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                  double* stats_out, const char** error_out);
+// PCM run: pcm_out (may be NULL) receives per file NULL (failed, or no frames) or a buffer allocated by the library, released
+// with ogg_vorbis_features_free: format VSYN_PCM_F32 float32 planar [channels][frames], VSYN_PCM_S16 int16 interleaved
+// [frames][channels]. target_rate: 0 = each file's own rate, else CorpusOptions::resample_rate. frames_out, channels_out and
+// rate_out (any may be NULL) receive what was delivered; ok_out / error_out_per_file as for ogg_vorbis_features_corpus.
+int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                          uint32_t files_per_submit, int device, uint32_t target_rate, int format, void** pcm_out, uint64_t* frames_out,
+                          uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                          const char** error_out);
 void ogg_vorbis_features_free(float* rows);
 }
 

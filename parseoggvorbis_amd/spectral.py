@@ -4,7 +4,9 @@ libparseoggvorbis_amd.so (ogg_vorbis_spectral_corpus); the semantics are documen
 features"). They follow librosa's documented defaults (librosa >= 0.10); parity with librosa itself has not been verified, the
 float64 model in tests/spectral_model.py is the contract the device is tested against.
 
-Every argument is checked before the library is loaded. 25 ms / 10 ms at 44.1 kHz: n_fft=1102, hop_length=441."""
+Every argument is checked before the library is loaded. 25 ms / 10 ms at 44.1 kHz: n_fft=1102, hop_length=441. sr=None computes
+each file's matrix at its own rate; an integer sr resamples every file's PCM to it on the device first (parseoggvorbis_amd/pcm.py,
+scipy.signal.resample_poly's arithmetic), so that one mel table serves the whole batch."""
 import ctypes as C
 import math
 import os
@@ -94,6 +96,9 @@ def _load():
     lib.ogg_vorbis_spectral_corpus.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(binding.SpectralSpec),
                                                vp, vp, vp, vp, vp, C.POINTER(C.c_char_p)]
     lib.ogg_vorbis_spectral_corpus.restype = C.c_int
+    lib.ogg_vorbis_spectral_corpus_sr.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_int,
+                                                  C.POINTER(binding.SpectralSpec), C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(C.c_char_p)]
+    lib.ogg_vorbis_spectral_corpus_sr.restype = C.c_int
     lib.ogg_vorbis_features_free.argtypes = [vp]
     lib.ogg_vorbis_features_free.restype = None
     _lib = lib
@@ -102,12 +107,15 @@ def _load():
 
 def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n_mels=128, fmin=0.0, fmax=None,
                        htk=False, norm="slaney", center=True, power=2.0, log_floor=1e-3, amin=1e-10, top_db=80.0, n_mfcc=20,
-                       threads=0, feeders=0, device=0, errors="raise", files_per_submit=64, stats=None):
+                       threads=0, feeders=0, device=0, errors="raise", files_per_submit=64, stats=None, sr=None):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels otherwise. errors="raise": the first failed file raises SpectralError naming it; errors="return": its entry
-    is the SpectralError. stats (optional list) receives the run's 8 corpus statistics."""
+    is the SpectralError. stats (optional list) receives the run's 8 corpus statistics. sr=None: each file at its own rate;
+    an integer: every file resampled to sr on the device, and the mel table and the fmin / fmax check use sr."""
     if errors not in ("raise", "return"):
         raise ValueError("errors must be 'raise' or 'return'")
+    from .pcm import check_sr
+    target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
     lib = _load()
@@ -124,8 +132,12 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     rows = (C.c_void_p * n)()
     st = (C.c_double * 8)()
     err = C.c_char_p()
-    rc = lib.ogg_vorbis_spectral_corpus(datas, lens, n, threads, feeders, files_per_submit, device, C.byref(spec), rows,
-                                        counts.ctypes.data, ok.ctypes.data, ferr, st, C.byref(err))
+    if target:
+        rc = lib.ogg_vorbis_spectral_corpus_sr(datas, lens, n, threads, feeders, files_per_submit, device, C.byref(spec), target, rows,
+                                               counts.ctypes.data, ok.ctypes.data, ferr, st, C.byref(err))
+    else:
+        rc = lib.ogg_vorbis_spectral_corpus(datas, lens, n, threads, feeders, files_per_submit, device, C.byref(spec), rows,
+                                            counts.ctypes.data, ok.ctypes.data, ferr, st, C.byref(err))
     if rc != 0:
         raise SpectralError("spectral corpus run failed: %s" % (err.value or b"").decode())
     if stats is not None:
