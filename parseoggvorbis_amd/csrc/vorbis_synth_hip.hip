@@ -86,6 +86,37 @@ struct DevBuf {  // grow-only device buffer
   DevBuf& operator=(const DevBuf&) = delete;
 };
 
+// A table built on the host per call and uploaded asynchronously from a page-locked copy. One instance per front-end: each keeps
+// buffers of its own.
+struct TableUpload {
+  DevBuf<uint8_t> dev;
+  uint8_t* host = nullptr;  // page-locked copy of the table (the upload is asynchronous)
+  size_t host_cap = 0;
+  hipEvent_t ev = nullptr;  // recorded behind the upload: the host copy is reused only after it
+  bool ev_valid = false;
+  int upload(const std::vector<uint8_t>& tab, hipStream_t s, const char** err) {
+    HIPCHK(dev.ensure(tab.size()));
+    if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (ev_valid) HIPCHK(hipEventSynchronize(ev));  // the previous upload has read the host copy
+    if (host_cap < tab.size()) {
+      if (host) HIPCHK(hipHostFree(host));
+      host = nullptr;
+      host_cap = 0;
+      HIPCHK(hipHostMalloc((void**)&host, tab.size() + 4096, hipHostMallocDefault));
+      host_cap = tab.size() + 4096;
+    }
+    memcpy(host, tab.data(), tab.size());
+    HIPCHK(hipMemcpyAsync(dev.p, host, tab.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ev, s));
+    ev_valid = true;
+    return VSYN_OK;
+  }
+  ~TableUpload() {  // (as DevBuf's: vsyn_destroy selects the device before the handle goes away; not copyable, as DevBuf is not)
+    if (ev) (void)hipEventDestroy(ev);
+    if (host) (void)hipHostFree(host);
+  }
+};
+
 bool is_pow2(uint32_t v) { return v && !(v & (v - 1)); }
 uint32_t ilog2(uint32_t v) {
   uint32_t r = 0;
@@ -187,31 +218,19 @@ struct vsyn_handle {
   DevBuf<int32_t> ft_fbsrc;
   DevBuf<uint8_t> ft_fbch;
   DevBuf<uint64_t> ft_resoff, ft_segrows, ft_segoff;
-  DevBuf<uint8_t> ft_tab;
-  uint8_t* ft_tab_host = nullptr;      // page-locked copy of the gather table (the upload is asynchronous)
-  size_t ft_tab_host_cap = 0;
-  hipEvent_t ft_ev = nullptr;          // recorded behind the table upload: the host copy is reused only after it
-  bool ft_ev_valid = false;
+  TableUpload ft_tab;                  // the gather table
   DevBuf<vsyn_packet> fs_pk;           // vsyn_features_host staging
   DevBuf<vsyn_segment> fs_seg;
   DevBuf<uint16_t> fs_ys;
   DevBuf<float> fs_res, fs_rows;
   // spectral features (vsyn_spectral.h): buffers of their own; the PCM is only read
-  DevBuf<uint8_t> sp_tab;
-  uint8_t* sp_tab_host = nullptr;      // page-locked copy of the tables (the upload is asynchronous)
-  size_t sp_tab_host_cap = 0;
-  hipEvent_t sp_ev = nullptr;          // recorded behind the table upload: the host copy is reused only after it
-  bool sp_ev_valid = false;
+  TableUpload sp_tab;
   bool sp_lds_set = false;             // the STFT kernels' dynamic-LDS limit is raised on this handle's device
   DevBuf<uint32_t> sp_segF, sp_segmax;
   DevBuf<uint64_t> sp_segoff;
   DevBuf<float> sp_db, sp_rows;
   // resampling (vsyn_resample.h): buffers of its own; the PCM is only read
-  DevBuf<uint8_t> rs_tab;
-  uint8_t* rs_tab_host = nullptr;      // page-locked copy of the tables (the upload is asynchronous)
-  size_t rs_tab_host_cap = 0;
-  hipEvent_t rs_ev = nullptr;          // recorded behind the table upload: the host copy is reused only after it
-  bool rs_ev_valid = false;
+  TableUpload rs_tab;
   bool rs_lds_set = false;             // vsyn_rs_kernel<true>'s dynamic-LDS limit is raised on this handle's device
   DevBuf<uint32_t> rs_inF, rs_outF;
   DevBuf<uint64_t> rs_off;
@@ -581,12 +600,6 @@ void vsyn_destroy(vsyn_handle* h) {
 #endif
   fused_tables_destroy(&h->fused);
   u_tables_destroy(&h->utab);
-  if (h->ft_ev) (void)hipEventDestroy(h->ft_ev);
-  if (h->ft_tab_host) (void)hipHostFree(h->ft_tab_host);
-  if (h->sp_ev) (void)hipEventDestroy(h->sp_ev);
-  if (h->sp_tab_host) (void)hipHostFree(h->sp_tab_host);
-  if (h->rs_ev) (void)hipEventDestroy(h->rs_ev);
-  if (h->rs_tab_host) (void)hipHostFree(h->rs_tab_host);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->pre) (void)hipStreamDestroy(h->pre);
   if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
@@ -1269,6 +1282,24 @@ int vsyn_imdct_device(vsyn_handle* h, uint32_t n, uint32_t count, const float* d
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
+// the front-ends after synthesis: features, spectral, resampling
+// ------------------------------------------------------------------------------------------------
+static void status_reset(vsyn_status* status) {
+  if (status) {
+    status->flags = 0;
+    status->first_bad_packet = 0xFFFFFFFFu;
+  }
+}
+
+// The end of a *_host call: vsyn_sync_status on the host stream (which waits for it), the batch's status into *status.
+static int sync_status_into(vsyn_handle* h, vsyn_status* status, const char** err) {
+  vsyn_status st;
+  const int rc = vsyn_sync_status(h, h->host_stream, &st, err);
+  if (status) *status = st;
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
 // feature matrices (vsyn_features.h; semantics in the header)
 // ------------------------------------------------------------------------------------------------
 // scipy.ndimage.zoom(xs as float32, z, order=1, mode="nearest") followed by numpy.round: output length round(L * z) (Python's round);
@@ -1394,24 +1425,11 @@ static int feat_launch(vsyn_handle* h, const vsyn_feature_spec* sp, uint32_t P, 
   HIPCHK(h->ft_resoff.ensure(P));
   HIPCHK(h->ft_segrows.ensure(S));
   HIPCHK(h->ft_segoff.ensure((size_t)S + 1));
-  HIPCHK(h->ft_tab.ensure(tab.size()));
-  if (!h->ft_ev) HIPCHK(hipEventCreateWithFlags(&h->ft_ev, hipEventDisableTiming));
-  if (h->ft_ev_valid) HIPCHK(hipEventSynchronize(h->ft_ev));  // the previous upload has read the host copy
-  if (h->ft_tab_host_cap < tab.size()) {
-    if (h->ft_tab_host) HIPCHK(hipHostFree(h->ft_tab_host));
-    h->ft_tab_host = nullptr;
-    h->ft_tab_host_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&h->ft_tab_host, tab.size() + 4096, hipHostMallocDefault));
-    h->ft_tab_host_cap = tab.size() + 4096;
-  }
-  memcpy(h->ft_tab_host, tab.data(), tab.size());
-  HIPCHK(hipMemcpyAsync(h->ft_tab.p, h->ft_tab_host, tab.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(h->ft_ev, s));
-  h->ft_ev_valid = true;
+  if (int rc = h->ft_tab.upload(tab, s, err)) return rc;
   if (P) HIPCHK(hipMemsetAsync(h->ft_info.p, 0, sizeof(PktInfo) * P, s));  // packets outside every segment: no floor rows to unwrap
   FeatCtx A;
   A.cb = h->d_const;
-  A.tab = h->ft_tab.p;
+  A.tab = h->ft_tab.dev.p;
   A.pk = d_pk;
   A.seg = d_seg;
   A.fy = h->ft_fy.p;
@@ -1471,10 +1489,7 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P
                        const uint16_t* ys, const float* residue, size_t residue_floats, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
                        vsyn_status* status, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-  if (status) {
-    status->flags = 0;
-    status->first_bad_packet = 0xFFFFFFFFu;
-  }
+  status_reset(status);
   if (!spec) return fail(err, VSYN_ERR_INVALID, "feature spec is NULL");
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
@@ -1533,9 +1548,7 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P
   HIPCHK(hipStreamSynchronize(hs));
   const uint64_t total = off[S];
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = off[g + 1] - off[g];
-  vsyn_status st;
-  rc = vsyn_sync_status(h, hs, &st, err);
-  if (status) *status = st;
+  rc = sync_status_into(h, status, err);
   if (rc) return rc;
   if (total > max_rows) return fail(err, VSYN_ERR_HIP, "row count %llu exceeds packets x channels", (unsigned long long)total);
   if (!rows) return VSYN_OK;
@@ -1691,26 +1704,13 @@ static int spec_launch(vsyn_handle* h, const vsyn_spectral_spec* sp, uint32_t S,
     HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
     h->sp_lds_set = true;
   }
-  HIPCHK(h->sp_tab.ensure(tab.size()));
   HIPCHK(h->sp_segF.ensure(S));
   HIPCHK(h->sp_segmax.ensure(S));
   HIPCHK(h->sp_segoff.ensure((size_t)S + 1));
   if (sp->kind == VSYN_SPEC_MFCC) HIPCHK(h->sp_db.ensure(rows_bound * sp->n_mels + 1));
-  if (!h->sp_ev) HIPCHK(hipEventCreateWithFlags(&h->sp_ev, hipEventDisableTiming));
-  if (h->sp_ev_valid) HIPCHK(hipEventSynchronize(h->sp_ev));  // the previous upload has read the host copy
-  if (h->sp_tab_host_cap < tab.size()) {
-    if (h->sp_tab_host) HIPCHK(hipHostFree(h->sp_tab_host));
-    h->sp_tab_host = nullptr;
-    h->sp_tab_host_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&h->sp_tab_host, tab.size() + 4096, hipHostMallocDefault));
-    h->sp_tab_host_cap = tab.size() + 4096;
-  }
-  memcpy(h->sp_tab_host, tab.data(), tab.size());
-  HIPCHK(hipMemcpyAsync(h->sp_tab.p, h->sp_tab_host, tab.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(h->sp_ev, s));
-  h->sp_ev_valid = true;
+  if (int rc = h->sp_tab.upload(tab, s, err)) return rc;
   SpecCtx A;
-  A.tab = h->sp_tab.p;
+  A.tab = h->sp_tab.dev.p;
   A.pcm = d_pcm;
   A.plane = plane;
   A.C = C;
@@ -1760,49 +1760,6 @@ int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_
   std::lock_guard<std::mutex> lk(h->mu);
   return spec_launch(h, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, (uint64_t)S * f_max, d_rows,
                      d_seg_row_off, (hipStream_t)hip_stream, err);
-}
-
-int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
-                           uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
-  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-  if (status) {
-    status->flags = 0;
-    status->first_bad_packet = 0xFFFFFFFFu;
-  }
-  int rc = spec_check(spec, S, sample_rates, err);
-  if (rc) return rc;
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
-  // the lock covers the whole call: the spectral workspace is the handle's, and the PCM must stay that of the last submit
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (h->last_S == 0 || h->last_host_plane == 0) return fail(err, VSYN_ERR_INVALID, "no vsyn_submit_host on this handle yet");
-  if (S != h->last_S) return fail(err, VSYN_ERR_INVALID, "num_segments %u differs from the last submit's %u", S, h->last_S);
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t hs = h->host_stream;
-  const uint64_t plane = h->last_host_plane;
-  const SegInfo* d_si = h->ws_seg[h->last_wb].p;
-  std::vector<SegInfo> si(S);
-  HIPCHK(hipMemcpyAsync(si.data(), d_si, sizeof(SegInfo) * S, hipMemcpyDeviceToHost, hs));
-  HIPCHK(hipStreamSynchronize(hs));
-  const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
-  uint64_t total = 0, f_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    const uint64_t f = sample_rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, center, std::min<uint64_t>(si[g].total_emit, plane)) : 0;
-    seg_rows[g] = f;
-    total += f;
-    f_max = std::max(f_max, f);
-  }
-  if (!rows || total == 0) return VSYN_OK;
-  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
-  const uint64_t D = spec_dim(spec);
-  HIPCHK(h->sp_rows.ensure(total * D + 1));
-  rc = spec_launch(h, spec, S, sample_rates, h->st_pcm.p, plane, h->H.channels, nullptr, d_si, f_max, total, h->sp_rows.p, nullptr, hs, err);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
-  vsyn_status st;
-  rc = vsyn_sync_status(h, hs, &st, err);
-  if (status) *status = st;
-  return rc;
 }
 
 }  // extern "C"
@@ -1940,25 +1897,12 @@ static int rs_launch(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t
     h->rs_lds_set = true;
   }
   const std::vector<uint8_t>& tab = plan.tab;
-  HIPCHK(h->rs_tab.ensure(tab.size()));
   HIPCHK(h->rs_inF.ensure(S));
   HIPCHK(h->rs_outF.ensure(S));
   HIPCHK(h->rs_off.ensure(2ull * S + 2));
-  if (!h->rs_ev) HIPCHK(hipEventCreateWithFlags(&h->rs_ev, hipEventDisableTiming));
-  if (h->rs_ev_valid) HIPCHK(hipEventSynchronize(h->rs_ev));  // the previous upload has read the host copy
-  if (h->rs_tab_host_cap < tab.size()) {
-    if (h->rs_tab_host) HIPCHK(hipHostFree(h->rs_tab_host));
-    h->rs_tab_host = nullptr;
-    h->rs_tab_host_cap = 0;
-    HIPCHK(hipHostMalloc((void**)&h->rs_tab_host, tab.size() + 4096, hipHostMallocDefault));
-    h->rs_tab_host_cap = tab.size() + 4096;
-  }
-  memcpy(h->rs_tab_host, tab.data(), tab.size());
-  HIPCHK(hipMemcpyAsync(h->rs_tab.p, h->rs_tab_host, tab.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(h->rs_ev, s));
-  h->rs_ev_valid = true;
+  if (int rc = h->rs_tab.upload(tab, s, err)) return rc;
   RsCtx A;
-  A.tab = h->rs_tab.p;
+  A.tab = h->rs_tab.dev.p;
   A.pcm = d_pcm;
   A.plane = plane;
   A.C = C;
@@ -1983,22 +1927,82 @@ static int rs_launch(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t
   return VSYN_OK;
 }
 
-// The last submit's input frames per segment (clamped to its plane) and, for rates[g] != 0, T_out; the host copy of SegInfo.
-static int rs_last_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, std::vector<uint64_t>& T_out,
-                          const char** err) {
+// The last host submit's frames per segment: SegInfo::total_emit clamped to its plane; with out_rate != 0, what segment g has once
+// resampled from rates[g] to out_rate (0 for rates[g] = 0; the caller has run rs_check). Caller holds h->mu.
+static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, std::vector<uint64_t>& T, const char** err) {
   if (h->last_S == 0 || h->last_host_plane == 0) return fail(err, VSYN_ERR_INVALID, "no vsyn_submit_host on this handle yet");
   if (S != h->last_S) return fail(err, VSYN_ERR_INVALID, "num_segments %u differs from the last submit's %u", S, h->last_S);
   HIPCHK(hipSetDevice(h->device));
   std::vector<SegInfo> si(S);
   HIPCHK(hipMemcpyAsync(si.data(), h->ws_seg[h->last_wb].p, sizeof(SegInfo) * S, hipMemcpyDeviceToHost, h->host_stream));
   HIPCHK(hipStreamSynchronize(h->host_stream));
-  T_out.assign(S, 0);
+  T.resize(S);
   for (uint32_t g = 0; g < S; ++g) {
+    T[g] = std::min<uint64_t>(si[g].total_emit, h->last_host_plane);
     uint32_t up, down;
-    if (rates[g] && rs_ratio(rates[g], out_rate, &up, &down))
-      T_out[g] = rs_num_frames(std::min<uint64_t>(si[g].total_emit, h->last_host_plane), up, down);
+    if (out_rate) T[g] = rates[g] && rs_ratio(rates[g], out_rate, &up, &down) ? rs_num_frames(T[g], up, down) : 0;
   }
   return VSYN_OK;
+}
+
+// vsyn_pcm_spectral_host, and with out_rate != 0 vsyn_pcm_resample_spectral_host: the rows of the last host submit's PCM, each
+// segment resampled from rates[g] to out_rate first when out_rate != 0.
+static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* rates, uint32_t out_rate,
+                             float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  status_reset(status);
+  int rc;
+  std::vector<uint32_t> sp_rates;  // resampled: the spectral pass sees every resampled segment at out_rate
+  if (out_rate) {
+    rc = rs_check(S, rates, out_rate, err);
+    if (rc) return rc;
+    sp_rates.resize(S);
+    for (uint32_t g = 0; g < S; ++g) sp_rates[g] = rates[g] ? out_rate : 0u;
+  }
+  const uint32_t* spec_rates = out_rate ? sp_rates.data() : rates;
+  rc = spec_check(spec, S, spec_rates, err);
+  if (rc) return rc;
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  // the lock covers the whole call: the spectral and resample workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T;
+  rc = last_submit_frames(h, S, rates, out_rate, T, err);
+  if (rc) return rc;
+  const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
+  uint64_t total = 0, f_max = 0, t_max = 1;
+  for (uint32_t g = 0; g < S; ++g) {
+    const uint64_t f = spec_rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, center, T[g]) : 0;
+    seg_rows[g] = f;
+    total += f;
+    f_max = std::max(f_max, f);
+    t_max = std::max(t_max, T[g]);
+  }
+  if (!rows || total == 0) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  const uint32_t C = h->H.channels;
+  hipStream_t hs = h->host_stream;
+  // the spectral pass reads the synthesis PCM with the last submit's SegInfo, or the resampled PCM with its frames
+  const float* pcm = h->st_pcm.p;
+  uint64_t plane = h->last_host_plane;
+  const SegInfo* si = h->ws_seg[h->last_wb].p;
+  const uint32_t* d_frames = nullptr;
+  if (out_rate) {
+    if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
+    HIPCHK(h->rs_pcm.ensure((size_t)S * C * t_max + 1));
+    rc = rs_launch(h, S, rates, out_rate, pcm, plane, C, nullptr, si, h->rs_pcm.p, t_max, h->rs_outF.p, hs, err);
+    if (rc) return rc;
+    pcm = h->rs_pcm.p;
+    plane = t_max;
+    si = nullptr;
+    d_frames = h->rs_outF.p;
+  }
+  const uint64_t D = spec_dim(spec);
+  HIPCHK(h->sp_rows.ensure(total * D + 1));
+  rc = spec_launch(h, spec, S, spec_rates, pcm, plane, C, d_frames, si, f_max, total, h->sp_rows.p, nullptr, hs, err);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+  return sync_status_into(h, status, err);
 }
 
 extern "C" {
@@ -2043,7 +2047,7 @@ int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates,
   // the lock covers the whole call: the resample workspace is the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
   std::vector<uint64_t> T_out;
-  rc = rs_last_frames(h, S, in_rates, out_rate, T_out, err);
+  rc = last_submit_frames(h, S, in_rates, out_rate, T_out, err);
   if (rc) return rc;
   uint64_t t_max = 0;
   for (uint32_t g = 0; g < S; ++g) {
@@ -2075,52 +2079,18 @@ int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates,
   return VSYN_OK;
 }
 
+int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
+                           uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
+  return pcm_spectral_host(h, spec, S, sample_rates, 0, rows, rows_capacity, seg_rows, status, err);
+}
+
 int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
                                     float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
-  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-  if (status) {
-    status->flags = 0;
-    status->first_bad_packet = 0xFFFFFFFFu;
+  if (h && !out_rate) {  // out_rate 0 would mean no resampling to the shared body: rs_check refuses it here
+    status_reset(status);
+    return rs_check(S, in_rates, out_rate, err);
   }
-  int rc = rs_check(S, in_rates, out_rate, err);
-  if (rc) return rc;
-  std::vector<uint32_t> sp_rates(S);  // the spectral pass sees every resampled segment at out_rate
-  for (uint32_t g = 0; g < S; ++g) sp_rates[g] = in_rates[g] ? out_rate : 0u;
-  rc = spec_check(spec, S, sp_rates.data(), err);
-  if (rc) return rc;
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
-  std::lock_guard<std::mutex> lk(h->mu);
-  std::vector<uint64_t> T_out;
-  rc = rs_last_frames(h, S, in_rates, out_rate, T_out, err);
-  if (rc) return rc;
-  const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
-  uint64_t total = 0, f_max = 0, t_max = 1;
-  for (uint32_t g = 0; g < S; ++g) {
-    const uint64_t f = sp_rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, center, T_out[g]) : 0;
-    seg_rows[g] = f;
-    total += f;
-    f_max = std::max(f_max, f);
-    t_max = std::max(t_max, T_out[g]);
-  }
-  if (!rows || total == 0) return VSYN_OK;
-  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
-  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
-  const uint32_t C = h->H.channels;
-  hipStream_t hs = h->host_stream;
-  HIPCHK(h->rs_pcm.ensure((size_t)S * C * t_max + 1));
-  rc = rs_launch(h, S, in_rates, out_rate, h->st_pcm.p, h->last_host_plane, C, nullptr, h->ws_seg[h->last_wb].p, h->rs_pcm.p, t_max,
-                 h->rs_outF.p, hs, err);
-  if (rc) return rc;
-  const uint64_t D = spec_dim(spec);
-  HIPCHK(h->sp_rows.ensure(total * D + 1));
-  rc = spec_launch(h, spec, S, sp_rates.data(), h->rs_pcm.p, t_max, C, h->rs_outF.p, nullptr, f_max, total, h->sp_rows.p, nullptr, hs, err);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
-  vsyn_status st;
-  rc = vsyn_sync_status(h, hs, &st, err);
-  if (status) *status = st;
-  return rc;
+  return pcm_spectral_host(h, spec, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err);
 }
 
 }  // extern "C"

@@ -141,4 +141,36 @@ __device__ __forceinline__ void state_write(StreamState* __restrict__ st, uint32
   ns.tag = epoch;
   st[2u * stream + (read_slot ^ 1u)] = ns;
 }
+
+// Exclusive scans of K per-segment counts at once by one workgroup of N threads: Hillis–Steele over each block of N segments, a
+// carry from block to block. count(g, v) sets v[0 .. K) for segment g < S (called once per segment, by the thread that owns it).
+// out[k * (S + 1) + g] = the sum of v[k] over the segments in front of g, out[k * (S + 1) + S] = the total. Integer sums: the
+// result does not depend on the order of the additions. Every thread of the workgroup calls it.
+template <uint32_t N, uint32_t K, typename Count>
+__device__ __forceinline__ void wg_exclusive_scan(uint32_t S, uint64_t* __restrict__ out, Count count) {
+  __shared__ uint64_t s[K][N];
+  const uint32_t t = threadIdx.x;
+  uint64_t carry[K] = {};
+  for (uint32_t base = 0; base < S; base += N) {
+    const uint32_t g = base + t;
+    uint64_t v[K] = {};
+    if (g < S) count(g, v);
+    for (uint32_t k = 0; k < K; ++k) s[k][t] = v[k];
+    __syncthreads();
+    for (uint32_t d = 1; d < N; d <<= 1) {
+      uint64_t o[K];
+      for (uint32_t k = 0; k < K; ++k) o[k] = t >= d ? s[k][t - d] : 0ull;
+      __syncthreads();
+      for (uint32_t k = 0; k < K; ++k) s[k][t] += o[k];
+      __syncthreads();
+    }
+    for (uint32_t k = 0; k < K; ++k) {
+      if (g < S) out[k * (S + 1u) + g] = carry[k] + s[k][t] - v[k];
+      carry[k] += s[k][N - 1];
+    }
+    __syncthreads();
+  }
+  if (t == 0)
+    for (uint32_t k = 0; k < K; ++k) out[k * (S + 1u) + S] = carry[k];
+}
 #endif

@@ -162,25 +162,7 @@ __global__ void __launch_bounds__(FEAT_THREADS) vsyn_feat_count_kernel(const Fea
 }
 
 __global__ void __launch_bounds__(FEAT_THREADS) vsyn_feat_offsets_kernel(const FeatCtx A) {
-  __shared__ uint64_t s[FEAT_THREADS];
-  const uint32_t t = threadIdx.x;
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < A.S; base += FEAT_THREADS) {
-    const uint32_t g = base + t;
-    const uint64_t v = g < A.S ? A.segrows[g] : 0ull;
-    s[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < FEAT_THREADS; d <<= 1) {
-      const uint64_t o = t >= d ? s[t - d] : 0ull;
-      __syncthreads();
-      s[t] += o;
-      __syncthreads();
-    }
-    if (g < A.S) A.segoff[g] = carry + s[t] - v;
-    carry += s[FEAT_THREADS - 1];
-    __syncthreads();
-  }
-  if (t == 0) A.segoff[A.S] = carry;
+  wg_exclusive_scan<FEAT_THREADS, 1>(A.S, A.segoff, [&](uint32_t g, uint64_t* v) { v[0] = A.segrows[g]; });
 }
 
 // The reference's CHECK(floor[i] < 256) over all n entries of a decoded floor (hpp:586-588): the curve is piecewise linear between the

@@ -64,49 +64,21 @@ __device__ __forceinline__ const RsPair* rs_pairs(const uint8_t* t) { return (co
 __device__ __forceinline__ const uint32_t* rs_seg_pair(const uint8_t* t) { return (const uint32_t*)(t + ((const RsHeader*)t)->off_seg); }
 
 __global__ void __launch_bounds__(RS_THREADS) vsyn_rs_offsets_kernel(const RsCtx A) {
-  __shared__ uint64_t s0[RS_THREADS], s1[RS_THREADS];
   const RsPair* P = rs_pairs(A.tab);
   const uint32_t* sp = rs_seg_pair(A.tab);
-  const uint32_t t = threadIdx.x;
-  uint64_t carry0 = 0, carry1 = 0;
-  for (uint32_t base = 0; base < A.S; base += RS_THREADS) {
-    const uint32_t g = base + t;
-    uint64_t v0 = 0, v1 = 0;
-    if (g < A.S) {
-      const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
-      uint64_t To = 0;
-      if (sp[g] != RS_SKIP) {
-        const RsPair p = P[sp[g]];
-        To = rs_num_frames(T, p.up, p.down);
-        const uint64_t n = (uint64_t)A.C * ((To + RS_CHUNK - 1u) / RS_CHUNK);
-        if (p.lds) v0 = n;
-        else v1 = n;
-      }
-      A.in_frames[g] = (uint32_t)T;
-      A.out_frames[g] = (uint32_t)To;  // < 2^32: checked against out_plane on the host
+  wg_exclusive_scan<RS_THREADS, 2>(A.S, A.off, [&](uint32_t g, uint64_t* v) {
+    const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
+    uint64_t To = 0;
+    if (sp[g] != RS_SKIP) {
+      const RsPair p = P[sp[g]];
+      To = rs_num_frames(T, p.up, p.down);
+      const uint64_t n = (uint64_t)A.C * ((To + RS_CHUNK - 1u) / RS_CHUNK);
+      if (p.lds) v[0] = n;
+      else v[1] = n;
     }
-    s0[t] = v0;
-    s1[t] = v1;
-    __syncthreads();
-    for (uint32_t d = 1; d < RS_THREADS; d <<= 1) {
-      const uint64_t o0 = t >= d ? s0[t - d] : 0ull, o1 = t >= d ? s1[t - d] : 0ull;
-      __syncthreads();
-      s0[t] += o0;
-      s1[t] += o1;
-      __syncthreads();
-    }
-    if (g < A.S) {
-      A.off[g] = carry0 + s0[t] - v0;
-      A.off[A.S + 1u + g] = carry1 + s1[t] - v1;
-    }
-    carry0 += s0[RS_THREADS - 1];
-    carry1 += s1[RS_THREADS - 1];
-    __syncthreads();
-  }
-  if (t == 0) {
-    A.off[A.S] = carry0;
-    A.off[2u * A.S + 1u] = carry1;
-  }
+    A.in_frames[g] = (uint32_t)T;
+    A.out_frames[g] = (uint32_t)To;  // < 2^32: checked against out_plane on the host
+  });
 }
 
 template <bool LDS>

@@ -62,33 +62,14 @@ __device__ __forceinline__ uint32_t spec_key(float x) {
 __device__ __forceinline__ float spec_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_offsets_kernel(const SpecCtx A) {
-  __shared__ uint64_t s[SPEC_THREADS];
   const SpecHeader* H = spec_hdr(A.tab);
   const uint32_t* rate = (const uint32_t*)(A.tab + H->off_rate);
-  const uint32_t t = threadIdx.x;
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < A.S; base += SPEC_THREADS) {
-    const uint32_t g = base + t;
-    uint64_t v = 0;
-    if (g < A.S) {
-      const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
-      v = rate[g] == SPEC_SKIP ? 0ull : spec_num_frames(H->n, H->hop, (H->opts & VSYN_SPEC_CENTER) != 0, T);
-      A.segF[g] = (uint32_t)v;
-      A.segmax[g] = 0u;  // below every key
-    }
-    s[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < SPEC_THREADS; d <<= 1) {
-      const uint64_t o = t >= d ? s[t - d] : 0ull;
-      __syncthreads();
-      s[t] += o;
-      __syncthreads();
-    }
-    if (g < A.S) A.segoff[g] = carry + s[t] - v;
-    carry += s[SPEC_THREADS - 1];
-    __syncthreads();
-  }
-  if (t == 0) A.segoff[A.S] = carry;
+  wg_exclusive_scan<SPEC_THREADS, 1>(A.S, A.segoff, [&](uint32_t g, uint64_t* v) {
+    const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
+    v[0] = rate[g] == SPEC_SKIP ? 0ull : spec_num_frames(H->n, H->hop, (H->opts & VSYN_SPEC_CENTER) != 0, T);
+    A.segF[g] = (uint32_t)v[0];
+    A.segmax[g] = 0u;  // below every key
+  });
 }
 
 // LDS image of the STFT kernel, in floats: twiddles [2n] | window [n] | span [(FT-1) hop + n] | |X|^power [FT][256] | M [FT][n_mels]

@@ -6,12 +6,11 @@ Drop-in for RETURNN code: replace the reference's import of ParseOggVorbisLib wi
 get_features_from_raw_bytes(raw_bytes, output_dim, kind, **kwargs) keep the reference's names, kinds and keyword arguments.
 Kind and keyword arguments are checked before the library is loaded."""
 import ctypes as C
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HOST_LIB_PATH = os.path.join(_HERE, "host", "libparseoggvorbis_amd.so")
+from . import _corpus
+from ._corpus import HOST_LIB_PATH  # noqa: F401
 
 KINDS = {"floor_final_ys": 1, "floor_final_ys_rendered": 2, "residue_ys": 3, "residue_ys_with_floor": 4}
 NOT_PROVIDED = ("floor_final_ys_rendered_concat_residue",)
@@ -77,70 +76,21 @@ def feature_spec(output_dim, kind="floor_final_ys", **kwargs):
     return FeatureSpec(KINDS[kind], output_dim, opts, 0, up, scale, clip, fbf, 0)
 
 
-_lib = None
-
-
-def _load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    from . import binding
-    binding.load()  # the HIP runtime (torch's, when torch is importable) before the host library
-    if not os.path.exists(HOST_LIB_PATH):
-        raise RuntimeError("host library missing: %s — run __graft_entry__.build() (there is no CPU fallback)" % HOST_LIB_PATH)
-    lib = C.CDLL(HOST_LIB_PATH)
-    vp = C.c_void_p
-    lib.ogg_vorbis_features_corpus.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(binding.FeatureSpec),
-                                               vp, vp, vp, vp, vp, C.POINTER(C.c_char_p)]
-    lib.ogg_vorbis_features_corpus.restype = C.c_int
-    lib.ogg_vorbis_features_free.argtypes = [vp]
-    lib.ogg_vorbis_features_free.restype = None
-    _lib = lib
-    return lib
+_load = _corpus.load
 
 
 def get_features_batch(list_of_bytes, output_dim, kind="floor_final_ys", threads=0, feeders=0, device=0, errors="raise",
                        files_per_submit=64, **kwargs):
     """Feature matrices of many Ogg Vorbis files in one corpus run. Returns a list of float32 arrays (rows, output_dim);
     errors="raise": the first failed file raises FeatureError naming it; errors="return": its entry is the FeatureError."""
-    if errors not in ("raise", "return"):
-        raise ValueError("errors must be 'raise' or 'return'")
+    _corpus.check_errors(errors)
     spec = feature_spec(output_dim, kind, **kwargs)
     lib = _load()
-    n = len(list_of_bytes)
-    if n == 0:
-        return []
-    bufs = [np.frombuffer(bytes(b), np.uint8) if len(b) else np.zeros(1, np.uint8) for b in list_of_bytes]
-    datas = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in list_of_bytes])
+    counts = np.zeros(len(list_of_bytes), np.uint64)
     # one pass: the library hands each file's rows over in a buffer of its own, copied here and released
-    counts = np.zeros(n, np.uint64)
-    ok = np.zeros(n, np.uint8)
-    ferr = (C.c_char_p * n)()
-    rows = (C.c_void_p * n)()
-    err = C.c_char_p()
-    rc = lib.ogg_vorbis_features_corpus(datas, lens, n, threads, feeders, files_per_submit, device, C.byref(spec), rows,
-                                        counts.ctypes.data, ok.ctypes.data, ferr, None, C.byref(err))
-    if rc != 0:
-        raise FeatureError("features corpus run failed: %s" % (err.value or b"").decode())
-    res = []
-    try:
-        for i in range(n):
-            if not ok[i]:
-                e = FeatureError("file %d: %s" % (i, (ferr[i] or b"failed").decode(errors="replace")))
-                if errors == "raise":
-                    raise e
-                res.append(e)
-                continue
-            m = np.zeros((int(counts[i]), spec.output_dim), np.float32)
-            if m.size:
-                C.memmove(m.ctypes.data, rows[i], m.nbytes)
-            res.append(m)
-    finally:
-        for i in range(n):
-            if rows[i]:
-                lib.ogg_vorbis_features_free(rows[i])
-    return res
+    return _corpus.run(lib, lib.ogg_vorbis_features_corpus, list_of_bytes, (threads, feeders, files_per_submit, device, C.byref(spec)),
+                       (counts,), lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), spec.output_dim), np.float32), p),
+                       FeatureError, errors, "features")
 
 
 def get_features_from_raw_bytes(raw_bytes, output_dim, kind="floor_final_ys", **kwargs):

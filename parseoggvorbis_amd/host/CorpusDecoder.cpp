@@ -77,6 +77,7 @@ struct NullCallbacks : ParseCallbacks {};
 
 bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
 bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
+uint32_t spectral_dim(const CorpusOptions& o) { return o.spectral.kind == VSYN_SPEC_MFCC ? o.spectral.n_mfcc : o.spectral.n_mels; }
 bool feature_needs_residue(const CorpusOptions& o) {
   return o.features.kind == VSYN_FEAT_RESIDUE_YS || o.features.kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
 }
@@ -237,49 +238,135 @@ struct Feeder {
   std::mutex& callbacks_mu;
   std::map<std::string, std::unique_ptr<Group>> groups;
 
-  // Feature run: the pending files' batches through vsyn_features_host, rows delivered per file.
-  OkOrError submit_features(Group& g) {
-    const uint32_t C = g.channels, S = (uint32_t)g.pending.size(), D = opts.features.output_dim;
-    const bool want_res = feature_needs_residue(opts);
-    double t0 = now_s();
-    size_t P = 0, rfloats = 0;
+  // Totals of the pending files' batches.
+  struct Packed {
+    size_t P = 0, rfloats = 0, ncls = 0, nent = 0;
+    uint32_t max_p = 0;
+  };
+
+  // The pending files' batches into the group's submit buffers, one segment per file (VSYN_SEG_RESET). A synthesis run gives each
+  // file a stream slot of its own and ships residue floats, or a VQ group's classifications and entry numbers; a feature run reads
+  // no stream state (stream 0) and residue only for the residue kinds (with_res).
+  OkOrError pack(Group& g, bool synthesis, bool with_res, Packed& k) {
+    const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
+    const bool vq = synthesis && g.vq;
     for (const auto& r : g.pending) {
-      P += r->batch.pk.size();
-      rfloats += want_res ? r->batch.residue_floats : 0;
+      k.P += r->batch.pk.size();
+      k.rfloats += with_res ? r->batch.residue_floats : 0;
+      k.ncls += r->batch.cls.size();
+      k.nent += r->batch.entries.size();
+      k.max_p = std::max<uint32_t>(k.max_p, (uint32_t)r->batch.pk.size());
     }
-    CHECK(P < 0xffffffffu);
-    CHECK_ERR(g.pk.ensure(P));
+    CHECK(k.ncls < 0xffffffffu);
+    CHECK(k.P < 0xffffffffu);
+    CHECK_ERR(g.pk.ensure(k.P));
     CHECK_ERR(g.seg.ensure(S));
-    CHECK_ERR(g.ys.ensure(P * C * g.ys_stride));
-    if (want_res) CHECK_ERR(g.residue.ensure(rfloats));
-    CHECK_ERR(g.rows.ensure(P * C * D));
-    CHECK_ERR(g.seg_rows.ensure(S));
-    size_t p0 = 0, r0 = 0;
+    CHECK_ERR(g.ys.ensure(k.P * C * g.ys_stride));
+    if (vq) {
+      CHECK_ERR(g.vq_pk.ensure(k.P));
+      CHECK_ERR(g.cls.ensure(k.ncls));
+      CHECK_ERR(g.entries.ensure(k.nent));
+    } else if (with_res) {
+      CHECK_ERR(g.residue.ensure(k.rfloats));
+    }
+    size_t p0 = 0, r0 = 0, c0 = 0, e0 = 0;
     for (uint32_t s = 0; s < S; ++s) {
       const PacketBatch& b = g.pending[s]->batch;
+      if (synthesis) CHECK(b.vq == g.vq);
+      // the staging arrays were sized from pk / residue_floats: a batch whose per-packet vectors disagree with them (a packet
+      // that failed half way and was not rolled back) must not be copied
       CHECK(b.ys.size() == b.pk.size() * C * g.ys_stride);
       memcpy(&g.pk[p0], b.pk.data(), b.pk.size() * sizeof(vsyn_packet));
       memcpy(&g.ys[p0 * C * g.ys_stride], b.ys.data(), b.ys.size() * sizeof(uint16_t));
-      if (want_res) {
+      if (vq) {
+        CHECK(b.vq_pk.size() == b.pk.size());
+        for (size_t q = 0; q < b.vq_pk.size(); ++q) {  // rebase the file's offsets into the merged arrays
+          vsyn_vq_packet v = b.vq_pk[q];
+          v.entry_off += e0;
+          v.cls_off += (uint32_t)c0;
+          g.vq_pk[p0 + q] = v;
+        }
+        memcpy(&g.cls[c0], b.cls.data(), b.cls.size());
+        memcpy(&g.entries[e0], b.entries.data(), b.entries.size() * sizeof(uint16_t));
+        c0 += b.cls.size();
+        e0 += b.entries.size();
+      } else if (with_res) {
         CHECK(!b.vq && b.residue.size() == b.residue_floats);
         memcpy(&g.residue[r0], b.residue.data(), b.residue.size() * sizeof(float));
       }
       vsyn_segment& sg = g.seg[s];
       memset(&sg, 0, sizeof(sg));
-      sg.stream = 0;  // (no stream state is read or written by a feature run)
+      sg.stream = synthesis ? s : 0;  // (no stream state is read or written by a feature run)
       sg.first_packet = (uint32_t)p0;
       sg.num_packets = (uint32_t)b.pk.size();
       sg.flags = VSYN_SEG_RESET;
-      sg.residue_off = want_res ? r0 : 0;
+      sg.residue_off = with_res ? r0 : 0;
       p0 += b.pk.size();
-      r0 += want_res ? b.residue_floats : 0;
+      r0 += with_res ? b.residue_floats : 0;
     }
+    return OkOrError();
+  }
+
+  // A batch the device flagged: the status does not say which file beyond the first. Re-run the files one by one so that every
+  // good file still gets its output and every bad one its own message.
+  OkOrError submit_one_by_one(Group& g) {
+    std::vector<std::unique_ptr<FileRecord>> files;
+    files.swap(g.pending);
+    for (auto& f : files) {
+      g.pending.clear();
+      g.pending.push_back(std::move(f));
+      CHECK_ERR(submit(g));
+    }
+    return OkOrError();
+  }
+
+  // Every pending file's result: the batch's status text when the device flagged it (rc VSYN_ERR_STREAM), else what
+  // deliver_file(s, record, result) sets and delivers. The records then go back to the queue.
+  template <typename DeliverFile>
+  OkOrError deliver(Group& g, int rc, const vsyn_status& st, double t2, DeliverFile deliver_file) {
+    for (uint32_t s = 0; s < g.pending.size(); ++s) {
+      FileRecord& r = *g.pending[s];
+      CorpusFileResult& out = results[r.index];
+      out.channels = g.channels;
+      out.sample_rate = r.header.audio_sample_rate;
+      out.audio_packets = (uint32_t)r.batch.pk.size();
+      if (rc == VSYN_ERR_STREAM) out.status = OkOrError(gpu_status_text(st));
+      else CHECK_ERR(deliver_file(s, r, out));
+      stats.audio_packets += r.batch.pk.size();
+      stats.files++;
+    }
+    for (auto& r : g.pending) queue.give_back(std::move(r));
+    g.pending.clear();
+    stats.deliver_s += now_s() - t2;
+    return OkOrError();
+  }
+
+  // A rows run's file: rows [row0, row0 + nr) of g.rows to gotFileFeatures, unless its result is an error.
+  OkOrError deliver_rows(Group& g, const FileRecord& r, CorpusFileResult& out, uint64_t& row0, uint64_t nr, uint32_t D) {
+    out.feature_rows = nr;
+    if (callbacks && !out.status.is_error_) {
+      std::lock_guard<std::mutex> lk(callbacks_mu);
+      if (!callbacks->gotFileFeatures(r.index, r.header, &g.rows[row0 * D], nr, D)) return OkOrError("aborted by gotFileFeatures");
+    }
+    row0 += nr;
+    return OkOrError();
+  }
+
+  // Feature run: the pending files' batches through vsyn_features_host, rows delivered per file.
+  OkOrError submit_features(Group& g) {
+    const uint32_t C = g.channels, S = (uint32_t)g.pending.size(), D = opts.features.output_dim;
+    const bool want_res = feature_needs_residue(opts);
+    double t0 = now_s();
+    Packed k;
+    CHECK_ERR(pack(g, false, want_res, k));
+    CHECK_ERR(g.rows.ensure(k.P * C * D));
+    CHECK_ERR(g.seg_rows.ensure(S));
     double t1 = now_s();
     stats.pack_s += t1 - t0;
     vsyn_status st = {0, 0xffffffffu};
     const char* err = nullptr;
-    const int rc = vsyn_features_host(g.handle, &opts.features, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, want_res ? g.residue.p : nullptr, rfloats,
-                                      g.rows.p, (uint64_t)P * C, g.seg_rows.p, &st, &err);
+    const int rc = vsyn_features_host(g.handle, &opts.features, (uint32_t)k.P, g.pk.p, S, g.seg.p, g.ys.p, want_res ? g.residue.p : nullptr,
+                                      k.rfloats, g.rows.p, (uint64_t)k.P * C, g.seg_rows.p, &st, &err);
     double t2 = now_s();
     stats.gpu_call_s += t2 - t1;
     stats.submits++;
@@ -294,41 +381,155 @@ struct Feeder {
       return OkOrError();
     }
     if (rc != VSYN_OK && rc != VSYN_ERR_STREAM) return OkOrError(std::string("GPU feature layer: ") + (err ? err : "features failed"));
-    if (rc == VSYN_ERR_STREAM && S > 1) {  // find the bad file(s): one by one
-      std::vector<std::unique_ptr<FileRecord>> files;
-      files.swap(g.pending);
-      for (auto& f : files) {
-        g.pending.clear();
-        g.pending.push_back(std::move(f));
-        CHECK_ERR(submit_features(g));
-      }
-      return OkOrError();
-    }
+    if (rc == VSYN_ERR_STREAM && S > 1) return submit_one_by_one(g);
     uint64_t row0 = 0;
-    for (uint32_t s = 0; s < S; ++s) {
-      FileRecord& r = *g.pending[s];
-      CorpusFileResult& out = results[r.index];
-      out.channels = C;
-      out.sample_rate = r.header.audio_sample_rate;
-      out.audio_packets = (uint32_t)r.batch.pk.size();
-      if (rc == VSYN_ERR_STREAM) {
-        out.status = OkOrError(gpu_status_text(st));
-      } else {
-        const uint64_t nr = g.seg_rows[s];
-        out.feature_rows = nr;
-        out.status = r.status;
-        if (callbacks && !r.status.is_error_) {
-          std::lock_guard<std::mutex> lk(callbacks_mu);
-          if (!callbacks->gotFileFeatures(r.index, r.header, &g.rows[row0 * D], nr, D)) return OkOrError("aborted by gotFileFeatures");
-        }
-        row0 += nr;
-      }
-      stats.audio_packets += r.batch.pk.size();
-      stats.files++;
+    return deliver(g, rc, st, t2, [&](uint32_t s, FileRecord& r, CorpusFileResult& out) {
+      out.status = r.status;
+      return deliver_rows(g, r, out, row0, g.seg_rows[s], D);
+    });
+  }
+
+  // What a synthesis run leaves per file after its device stages: frames (the resampled ones in a resampled run), an error of its
+  // own (a ratio the resampler refuses, a rate the spectral spec does not fit), and the plane of the PCM the later stages and the
+  // delivery read (the synthesis plane, or the resampled one).
+  struct Outcome {
+    std::vector<uint64_t> frames;
+    std::vector<std::string> err;
+    std::vector<double> digest;  // per (file, channel), from the device
+    uint64_t plane = 0;
+  };
+
+  // Synthesis of the packed batch. The PCM comes back as f32 planes unless a later stage reads it on the device (VSYN_SUBMIT_KEEP_PCM).
+  int synthesize(Group& g, const Packed& k, uint64_t plane, bool keep_pcm, vsyn_status* st, const char** err) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    const uint32_t sflags = keep_pcm ? VSYN_SUBMIT_KEEP_PCM : 0u;
+    float* pcm_out = keep_pcm ? nullptr : g.pcm.p;
+    if (!g.vq)
+      return vsyn_submit_host(g.handle, (uint32_t)k.P, g.pk.p, S, g.seg.p, g.ys.p, g.residue.p, k.rfloats, pcm_out, plane, g.emit.p, nullptr,
+                              sflags, st, err);
+    vsyn_vq_batch vqb;
+    vqb.packets = g.vq_pk.p;
+    vqb.cls = g.cls.p;
+    vqb.entries = g.entries.p;
+    vqb.num_cls = k.ncls;
+    vqb.num_entries = k.nent;
+    return vsyn_submit_host_vq(g.handle, (uint32_t)k.P, g.pk.p, S, g.seg.p, g.ys.p, &vqb, nullptr, k.rfloats, pcm_out, plane, g.emit.p,
+                               nullptr, sflags, st, err);
+  }
+
+  // Without resampling: the int16 PCM (pcm_s16), and the per-(file, channel) digests from the device, where the PCM still is (a
+  // host pass over it cost more than the decode's GPU calls).
+  OkOrError fetch(Group& g, Outcome& o) {
+    const char* err = nullptr;
+    if (opts.pcm_s16 && vsyn_pcm_fetch_host(g.handle, VSYN_PCM_S16, g.pcm16.p, o.plane, nullptr, &err) != VSYN_OK)
+      return OkOrError(std::string("GPU synthesis layer: ") + (err ? err : "pcm fetch failed"));
+    if (opts.checksum) {
+      o.digest.resize(g.pending.size() * g.channels);
+      if (vsyn_pcm_abs_sum_host(g.handle, o.digest.data(), &err) != VSYN_OK)
+        return OkOrError(std::string("GPU synthesis layer: ") + (err ? err : "digest failed"));
     }
-    for (auto& r : g.pending) queue.give_back(std::move(r));
-    g.pending.clear();
-    stats.deliver_s += now_s() - t2;
+    return OkOrError();
+  }
+
+  // Resampled run: each file's PCM resampled on the device from its own rate to resample_rate (vsyn_pcm_resample_host, or for a
+  // spectral run vsyn_pcm_resample_spectral_host in spectral_stage); a file whose ratio the contract refuses gets no output and an error
+  // of its own.
+  OkOrError resample_stage(Group& g, bool spectral, Outcome& o) {
+    const uint32_t C = g.channels, S = (uint32_t)g.pending.size(), out_rate = opts.resample_rate;
+    std::vector<uint32_t> rates(S, 0u);  // 0: a refused file
+    uint64_t rs_plane = 1;
+    for (uint32_t s = 0; s < S; ++s) {
+      const uint32_t sr = g.pending[s]->header.audio_sample_rate;
+      if (vsyn_resample_num_frames(sr, out_rate, 1) == 0) {
+        const uint32_t gd = sr ? std::gcd(sr, out_rate) : 1u;
+        char buf[160];
+        snprintf(buf, sizeof(buf), "resample: %u -> %u Hz reduces to %u / %u, above the limit max(up, down) <= %u", sr, out_rate,
+                 out_rate / gd, sr / gd, VSYN_RESAMPLE_MAX_M);
+        o.err[s] = buf;
+        o.frames[s] = 0;
+        continue;
+      }
+      rates[s] = sr;
+      o.frames[s] = vsyn_resample_num_frames(sr, out_rate, std::min<uint64_t>(o.frames[s], o.plane));
+      rs_plane = std::max(rs_plane, o.frames[s]);
+    }
+    o.plane = rs_plane;
+    if (spectral) return OkOrError();
+    if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * C * rs_plane));
+    else CHECK_ERR(g.pcm.ensure((size_t)S * C * rs_plane));
+    const char* err = nullptr;
+    std::vector<uint64_t> got(S);
+    const int rc = vsyn_pcm_resample_host(g.handle, S, rates.data(), out_rate, opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32,
+                                          opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, rs_plane, got.data(), &err);
+    if (rc != VSYN_OK) return OkOrError(std::string("GPU resample layer: ") + (err ? err : "resample failed"));
+    CHECK(got == o.frames);
+    return OkOrError();
+  }
+
+  // Spectral run: each file's rows from the PCM still on the device (vsyn_pcm_spectral_host, or resampled first); a file whose rate
+  // the spec does not fit (fmax above its sr / 2) gets no rows and an error of its own, unless it has one already.
+  OkOrError spectral_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    const bool resample = opts.resample_rate != 0;
+    std::vector<uint32_t> rates(S);
+    uint64_t spec_rows = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      const FileRecord& r = *g.pending[s];
+      const uint32_t sr = resample ? opts.resample_rate : r.header.audio_sample_rate;  // the rate the rows are computed at
+      const double ny = sr / 2.0, fmax = opts.spectral.fmax > 0.0 ? opts.spectral.fmax : ny;
+      if (o.err[s].empty() && !(fmax <= ny && opts.spectral.fmin < fmax)) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "spectral: fmin %g / fmax %g do not fit sample rate %u (0 <= fmin < fmax <= sr/2)", opts.spectral.fmin, fmax,
+                 sr);
+        o.err[s] = buf;
+      }
+      rates[s] = o.err[s].empty() ? r.header.audio_sample_rate : 0;
+      if (rates[s]) spec_rows += vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(o.frames[s], o.plane));
+    }
+    CHECK_ERR(g.rows.ensure(spec_rows * spectral_dim(opts) + 1));
+    CHECK_ERR(g.seg_rows.ensure(S));
+    vsyn_status st;
+    const char* err = nullptr;
+    const int rc = resample ? vsyn_pcm_resample_spectral_host(g.handle, &opts.spectral, S, rates.data(), opts.resample_rate, g.rows.p,
+                                                              spec_rows, g.seg_rows.p, &st, &err)
+                            : vsyn_pcm_spectral_host(g.handle, &opts.spectral, S, rates.data(), g.rows.p, spec_rows, g.seg_rows.p, &st, &err);
+    if (rc == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
+      for (uint32_t s = 0; s < S; ++s) o.err[s] = std::string("spectral: ") + (err ? err : "refused");
+      for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
+    } else if (rc != VSYN_OK) {
+      return OkOrError(std::string("GPU spectral layer: ") + (err ? err : "spectral failed"));
+    }
+    return OkOrError();
+  }
+
+  // A synthesis run's file: its PCM (or, for a spectral run, its rows) to the callbacks.
+  OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
+    const uint32_t C = g.channels;
+    const bool spectral = spectral_run(opts);
+    const uint64_t frames = o.frames[s], pl = o.plane;
+    std::vector<DataRange<const float>> chans(C);
+    double acc = 0;
+    for (uint32_t c = 0; c < C; ++c) {
+      if (!opts.pcm_s16 && !spectral) {
+        const float* x = &g.pcm[((size_t)s * C + c) * pl];
+        chans[c] = DataRange<const float>(x, frames);
+        if (opts.checksum && o.digest.empty()) acc += abs_sum_f32(x, frames);
+      }
+      if (opts.checksum && !o.digest.empty()) acc += o.digest[(size_t)s * C + c];
+    }
+    out.frames = frames;
+    out.abs_sum = acc;
+    out.status = o.err[s].empty() ? r.status : OkOrError(o.err[s]);
+    if (opts.resample_rate) out.sample_rate = opts.resample_rate;
+    stats.frames += frames;
+    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], spectral_dim(opts));
+    if (!callbacks || !o.err[s].empty()) return OkOrError();
+    std::lock_guard<std::mutex> lk(callbacks_mu);
+    if (opts.pcm_s16) {
+      if (!callbacks->gotFilePcmS16(r.index, r.header, &g.pcm16[(size_t)s * pl * C], frames)) return OkOrError("aborted by gotFilePcmS16");
+    } else if (!callbacks->gotFilePcm(r.index, r.header, chans)) {
+      return OkOrError("aborted by gotFilePcm");
+    }
     return OkOrError();
   }
 
@@ -336,267 +537,43 @@ struct Feeder {
     if (g.pending.empty()) return OkOrError();
     if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
-    double t0 = now_s();
-    size_t P = 0, rfloats = 0, ncls = 0, nent = 0;
-    uint32_t max_p = 0;
-    for (const auto& r : g.pending) {
-      P += r->batch.pk.size();
-      rfloats += r->batch.residue_floats;
-      ncls += r->batch.cls.size();
-      nent += r->batch.entries.size();
-      max_p = std::max<uint32_t>(max_p, (uint32_t)r->batch.pk.size());
-    }
-    CHECK(ncls < 0xffffffffu);
-    CHECK(P < 0xffffffffu);
-    const uint64_t plane = (uint64_t)max_p * (g.bs1 / 2);
-    CHECK_ERR(g.pk.ensure(P));
-    CHECK_ERR(g.seg.ensure(S));
-    CHECK_ERR(g.ys.ensure(P * C * g.ys_stride));
-    if (g.vq) {
-      CHECK_ERR(g.vq_pk.ensure(P));
-      CHECK_ERR(g.cls.ensure(ncls));
-      CHECK_ERR(g.entries.ensure(nent));
-    } else {
-      CHECK_ERR(g.residue.ensure(rfloats));
-    }
-    CHECK_ERR(g.emit.ensure(P));
     const bool spectral = spectral_run(opts);  // the PCM stays on the device: only the spectral rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
+    double t0 = now_s();
+    Packed k;
+    CHECK_ERR(pack(g, true, true, k));
+    const uint64_t plane = (uint64_t)k.max_p * (g.bs1 / 2);
+    CHECK_ERR(g.emit.ensure(k.P));
     if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * C * plane));
     else if (!spectral && !resample) CHECK_ERR(g.pcm.ensure((size_t)S * C * plane));
-    size_t p0 = 0, r0 = 0, c0 = 0, e0 = 0;
-    for (uint32_t s = 0; s < S; ++s) {
-      const PacketBatch& b = g.pending[s]->batch;
-      CHECK(b.vq == g.vq);
-      // the staging arrays were sized from pk / residue_floats: a batch whose per-packet vectors disagree with them (a packet
-      // that failed half way and was not rolled back) must not be copied
-      CHECK(b.ys.size() == b.pk.size() * C * g.ys_stride);
-      CHECK(b.vq || b.residue.size() == b.residue_floats);
-      memcpy(&g.pk[p0], b.pk.data(), b.pk.size() * sizeof(vsyn_packet));
-      memcpy(&g.ys[p0 * C * g.ys_stride], b.ys.data(), b.ys.size() * sizeof(uint16_t));
-      if (g.vq) {
-        CHECK(b.vq_pk.size() == b.pk.size());
-        for (size_t q = 0; q < b.vq_pk.size(); ++q) {  // rebase the file's offsets into the merged arrays
-          vsyn_vq_packet v = b.vq_pk[q];
-          v.entry_off += e0;
-          v.cls_off += (uint32_t)c0;
-          g.vq_pk[p0 + q] = v;
-        }
-        memcpy(&g.cls[c0], b.cls.data(), b.cls.size());
-        memcpy(&g.entries[e0], b.entries.data(), b.entries.size() * sizeof(uint16_t));
-        c0 += b.cls.size();
-        e0 += b.entries.size();
-      } else {
-        memcpy(&g.residue[r0], b.residue.data(), b.residue.size() * sizeof(float));
-      }
-      vsyn_segment& sg = g.seg[s];
-      memset(&sg, 0, sizeof(sg));
-      sg.stream = s;
-      sg.first_packet = (uint32_t)p0;
-      sg.num_packets = (uint32_t)b.pk.size();
-      sg.flags = VSYN_SEG_RESET;
-      sg.residue_off = r0;
-      p0 += b.pk.size();
-      r0 += b.residue_floats;
-    }
     double t1 = now_s();
     stats.pack_s += t1 - t0;
     vsyn_status st = {0, 0xffffffffu};
     const char* err = nullptr;
-    int rc;
-    const uint32_t sflags = (opts.pcm_s16 || spectral || resample) ? VSYN_SUBMIT_KEEP_PCM : 0u;
-    float* pcm_out = (opts.pcm_s16 || spectral || resample) ? nullptr : g.pcm.p;
-    if (g.vq) {
-      vsyn_vq_batch vqb;
-      vqb.packets = g.vq_pk.p;
-      vqb.cls = g.cls.p;
-      vqb.entries = g.entries.p;
-      vqb.num_cls = ncls;
-      vqb.num_entries = nent;
-      rc = vsyn_submit_host_vq(g.handle, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, &vqb, nullptr, rfloats, pcm_out, plane, g.emit.p, nullptr, sflags, &st, &err);
-    } else {
-      rc = vsyn_submit_host(g.handle, (uint32_t)P, g.pk.p, S, g.seg.p, g.ys.p, g.residue.p, rfloats, pcm_out, plane, g.emit.p, nullptr, sflags, &st, &err);
-    }
-    if (opts.pcm_s16 && !resample && rc == VSYN_OK) {
-      const char* ferr = nullptr;
-      if (vsyn_pcm_fetch_host(g.handle, VSYN_PCM_S16, g.pcm16.p, plane, nullptr, &ferr) != VSYN_OK)
-        return OkOrError(std::string("GPU synthesis layer: ") + (ferr ? ferr : "pcm fetch failed"));
-    }
-    // per-(file, channel) digests from the device, where the PCM still is (a host pass over it cost more than the decode's GPU calls)
-    std::vector<double> digest;
-    if (opts.checksum && !resample && rc == VSYN_OK) {
-      digest.resize((size_t)S * C);
-      const char* derr = nullptr;
-      if (vsyn_pcm_abs_sum_host(g.handle, digest.data(), &derr) != VSYN_OK)
-        return OkOrError(std::string("GPU synthesis layer: ") + (derr ? derr : "digest failed"));
-    }
-    // resampled run: each file's PCM resampled on the device from its own rate to resample_rate (vsyn_pcm_resample_host, or for a
-    // spectral run vsyn_pcm_resample_spectral_host below); a file whose ratio the contract refuses gets no output and an error of
-    // its own
-    std::vector<std::string> rs_err;
-    std::vector<uint32_t> rs_rates;
-    std::vector<uint64_t> rs_frames;
-    uint64_t rs_plane = 1;
-    if (resample && rc == VSYN_OK) {
-      rs_err.assign(S, std::string());
-      rs_rates.assign(S, 0u);
-      rs_frames.assign(S, 0u);
+    const int rc = synthesize(g, k, plane, opts.pcm_s16 || spectral || resample, &st, &err);
+    Outcome o;
+    if (rc == VSYN_OK) {
+      o.plane = plane;
+      o.err.assign(S, std::string());
+      o.frames.assign(S, 0);
       size_t q0 = 0;
-      for (uint32_t s = 0; s < S; ++s) {
-        const FileRecord& r = *g.pending[s];
-        const uint32_t sr = r.header.audio_sample_rate;
-        uint64_t frames = 0;
-        for (size_t q = 0; q < r.batch.pk.size(); ++q) frames += g.emit[q0 + q];
-        q0 += r.batch.pk.size();
-        if (vsyn_resample_num_frames(sr, opts.resample_rate, 1) == 0) {
-          const uint32_t gd = sr ? std::gcd(sr, opts.resample_rate) : 1u;
-          char buf[160];
-          snprintf(buf, sizeof(buf), "resample: %u -> %u Hz reduces to %u / %u, above the limit max(up, down) <= %u", sr, opts.resample_rate,
-                   opts.resample_rate / gd, sr / gd, VSYN_RESAMPLE_MAX_M);
-          rs_err[s] = buf;
-          continue;
-        }
-        rs_rates[s] = sr;
-        rs_frames[s] = vsyn_resample_num_frames(sr, opts.resample_rate, std::min<uint64_t>(frames, plane));
-        rs_plane = std::max(rs_plane, rs_frames[s]);
+      for (uint32_t s = 0; s < S; ++s) {  // each file's frames: the sum of its packets' emit
+        const size_t np = g.pending[s]->batch.pk.size();
+        for (size_t q = 0; q < np; ++q) o.frames[s] += g.emit[q0 + q];
+        q0 += np;
+        CHECK(o.frames[s] <= plane);
       }
-      if (!spectral) {
-        const char* rerr = nullptr;
-        std::vector<uint64_t> got(S);
-        int rrc;
-        if (opts.pcm_s16) {
-          CHECK_ERR(g.pcm16.ensure((size_t)S * C * rs_plane));
-          rrc = vsyn_pcm_resample_host(g.handle, S, rs_rates.data(), opts.resample_rate, VSYN_PCM_S16, g.pcm16.p, rs_plane, got.data(), &rerr);
-        } else {
-          CHECK_ERR(g.pcm.ensure((size_t)S * C * rs_plane));
-          rrc = vsyn_pcm_resample_host(g.handle, S, rs_rates.data(), opts.resample_rate, VSYN_PCM_F32, g.pcm.p, rs_plane, got.data(), &rerr);
-        }
-        if (rrc != VSYN_OK) return OkOrError(std::string("GPU resample layer: ") + (rerr ? rerr : "resample failed"));
-        CHECK(got == rs_frames);
-      }
-    }
-    // spectral run: each file's rows from the PCM still on the device (vsyn_pcm_spectral_host); a file whose rate the spec does not
-    // fit (fmax above its sr / 2) gets no rows and an error of its own
-    std::vector<std::string> spec_err;
-    uint64_t spec_rows = 0;
-    if (spectral && rc == VSYN_OK) {
-      std::vector<uint32_t> rates(S);
-      spec_err.assign(S, std::string());
-      size_t q0 = 0;
-      for (uint32_t s = 0; s < S; ++s) {
-        const FileRecord& r = *g.pending[s];
-        const uint32_t sr = resample ? opts.resample_rate : r.header.audio_sample_rate;  // the rate the rows are computed at
-        const double ny = sr / 2.0, fmax = opts.spectral.fmax > 0.0 ? opts.spectral.fmax : ny;
-        rates[s] = r.header.audio_sample_rate;
-        if (!(fmax <= ny && opts.spectral.fmin < fmax)) {
-          char buf[160];
-          snprintf(buf, sizeof(buf), "spectral: fmin %g / fmax %g do not fit sample rate %u (0 <= fmin < fmax <= sr/2)", opts.spectral.fmin, fmax,
-                   sr);
-          spec_err[s] = buf;
-          rates[s] = 0;
-        }
-        if (resample && !rs_err[s].empty()) {
-          spec_err[s] = rs_err[s];
-          rates[s] = 0;
-        }
-        uint64_t frames = 0;
-        for (size_t q = 0; q < r.batch.pk.size(); ++q) frames += g.emit[q0 + q];
-        q0 += r.batch.pk.size();
-        if (resample) frames = rs_frames[s];
-        if (rates[s]) spec_rows += vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(frames, resample ? rs_plane : plane));
-      }
-      const uint32_t D = opts.spectral.kind == VSYN_SPEC_MFCC ? opts.spectral.n_mfcc : opts.spectral.n_mels;
-      CHECK_ERR(g.rows.ensure(spec_rows * D + 1));
-      CHECK_ERR(g.seg_rows.ensure(S));
-      vsyn_status sst;
-      const char* serr = nullptr;
-      const int src = resample ? vsyn_pcm_resample_spectral_host(g.handle, &opts.spectral, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
-                                                                 g.seg_rows.p, &sst, &serr)
-                               : vsyn_pcm_spectral_host(g.handle, &opts.spectral, S, rates.data(), g.rows.p, spec_rows, g.seg_rows.p, &sst, &serr);
-      if (src == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
-        for (uint32_t s = 0; s < S; ++s) spec_err[s] = std::string("spectral: ") + (serr ? serr : "refused");
-        for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
-      } else if (src != VSYN_OK) {
-        return OkOrError(std::string("GPU spectral layer: ") + (serr ? serr : "spectral failed"));
-      }
+      if (!resample) CHECK_ERR(fetch(g, o));
+      else CHECK_ERR(resample_stage(g, spectral, o));
+      if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
     double t2 = now_s();
     stats.gpu_call_s += t2 - t1;
     stats.submits++;
     if (rc != VSYN_OK && rc != VSYN_ERR_STREAM) return OkOrError(std::string("GPU synthesis layer: ") + (err ? err : "submit failed"));
-    if (rc == VSYN_ERR_STREAM && S > 1) {
-      // Some file of the batch is bad; the status does not say which beyond the first. Re-run the files one by one so that
-      // every good file still gets its PCM and every bad one its own message.
-      std::vector<std::unique_ptr<FileRecord>> files;
-      files.swap(g.pending);
-      for (auto& f : files) {
-        g.pending.clear();
-        g.pending.push_back(std::move(f));
-        CHECK_ERR(submit(g));
-      }
-      return OkOrError();
-    }
-    // deliver
-    std::vector<DataRange<const float>> chans(C);
-    p0 = 0;
+    if (rc == VSYN_ERR_STREAM && S > 1) return submit_one_by_one(g);
     uint64_t row0 = 0;
-    for (uint32_t s = 0; s < S; ++s) {
-      FileRecord& r = *g.pending[s];
-      CorpusFileResult& out = results[r.index];
-      out.channels = C;
-      out.sample_rate = r.header.audio_sample_rate;
-      out.audio_packets = (uint32_t)r.batch.pk.size();
-      if (rc == VSYN_ERR_STREAM) {
-        out.status = OkOrError(gpu_status_text(st));
-      } else {
-        uint64_t frames = 0;
-        for (size_t q = 0; q < r.batch.pk.size(); ++q) frames += g.emit[p0 + q];
-        CHECK(frames <= plane);
-        const uint64_t pl = resample ? rs_plane : plane;  // the delivered PCM's plane
-        const bool rs_bad = resample && !rs_err[s].empty();
-        if (resample) frames = rs_frames[s];
-        double acc = 0;
-        for (uint32_t c = 0; c < C; ++c) {
-          if (!opts.pcm_s16 && !spectral) {
-            const float* x = &g.pcm[((size_t)s * C + c) * pl];
-            chans[c] = DataRange<const float>(x, frames);
-            if (opts.checksum && digest.empty()) acc += abs_sum_f32(x, frames);
-          }
-          if (opts.checksum && !digest.empty()) acc += digest[(size_t)s * C + c];
-        }
-        out.frames = frames;
-        out.abs_sum = acc;
-        out.status = r.status;
-        if (resample) out.sample_rate = opts.resample_rate;
-        if (rs_bad) out.status = OkOrError(rs_err[s]);
-        stats.frames += frames;
-        if (spectral) {
-          const uint32_t D = opts.spectral.kind == VSYN_SPEC_MFCC ? opts.spectral.n_mfcc : opts.spectral.n_mels;
-          const uint64_t nr = g.seg_rows[s];
-          if (!spec_err[s].empty()) out.status = OkOrError(spec_err[s]);
-          out.feature_rows = nr;
-          if (callbacks && !out.status.is_error_) {
-            std::lock_guard<std::mutex> lk(callbacks_mu);
-            if (!callbacks->gotFileFeatures(r.index, r.header, &g.rows[row0 * D], nr, D)) return OkOrError("aborted by gotFileFeatures");
-          }
-          row0 += nr;
-        } else if (callbacks && !rs_bad) {
-          std::lock_guard<std::mutex> lk(callbacks_mu);
-          if (opts.pcm_s16) {
-            if (!callbacks->gotFilePcmS16(r.index, r.header, &g.pcm16[(size_t)s * pl * C], frames)) return OkOrError("aborted by gotFilePcmS16");
-          } else if (!callbacks->gotFilePcm(r.index, r.header, chans)) {
-            return OkOrError("aborted by gotFilePcm");
-          }
-        }
-      }
-      stats.audio_packets += r.batch.pk.size();
-      stats.files++;
-      p0 += r.batch.pk.size();
-    }
-    for (auto& r : g.pending) queue.give_back(std::move(r));
-    g.pending.clear();
-    stats.deliver_s += now_s() - t2;
-    return OkOrError();
+    return deliver(g, rc, st, t2, [&](uint32_t s, FileRecord& r, CorpusFileResult& out) { return deliver_pcm(g, s, r, out, o, row0); });
   }
 
   OkOrError take(std::unique_ptr<FileRecord> rec) {
@@ -738,19 +715,48 @@ OkOrError decode_corpus(const std::vector<CorpusItem>& items, const CorpusOption
   return run_status;
 }
 
-extern "C" int ogg_vorbis_decode_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
-                                        uint32_t files_per_submit, int device, uint64_t* frames_out, double* abs_sum_out, uint8_t* ok_out, float* const* pcm_out,
-                                        const uint64_t* pcm_capacity, double* stats_out, const char** error_out) {
-  static char error_buf[256];
-  std::vector<CorpusItem> items(num_files);
-  for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
+namespace {
+
+CorpusOptions call_options(int threads, int feeders, uint32_t files_per_submit, int device) {
   CorpusOptions opts;
   opts.threads = threads;
   opts.feeders = feeders;
   opts.files_per_submit = files_per_submit;
   opts.device = device;
-  std::vector<CorpusFileResult> results;
+  return opts;
+}
+
+// decode_corpus over the C form's arrays; stats_out (may be NULL) receives the 8 doubles the header lists.
+OkOrError run_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts, CorpusCallbacks* callbacks,
+                     std::vector<CorpusFileResult>& results, double* stats_out) {
+  std::vector<CorpusItem> items(num_files);
+  for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
   CorpusStats st;
+  OkOrError r = decode_corpus(items, opts, callbacks, results, &st);
+  if (stats_out) {
+    const double v[8] = {st.wall_s, st.entropy_cpu_s, st.gpu_call_s, st.pack_s, st.deliver_s, (double)st.submits, (double)st.audio_packets, (double)st.frames};
+    for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+  }
+  return r;
+}
+
+// The C form's return: 0 with *error_out = NULL, or 1 with *error_out pointing at the run's error text in buf.
+int call_result(const OkOrError& r, char (&buf)[256], const char** error_out) {
+  if (!r.is_error_) {
+    if (error_out) *error_out = nullptr;
+    return 0;
+  }
+  snprintf(buf, sizeof(buf), "%s", r.err_msg_.c_str());
+  if (error_out) *error_out = buf;
+  return 1;
+}
+
+}  // namespace
+
+extern "C" int ogg_vorbis_decode_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                        uint32_t files_per_submit, int device, uint64_t* frames_out, double* abs_sum_out, uint8_t* ok_out, float* const* pcm_out,
+                                        const uint64_t* pcm_capacity, double* stats_out, const char** error_out) {
+  static char error_buf[256];
   struct CopyOut : CorpusCallbacks {
     float* const* pcm_out;
     const uint64_t* cap;
@@ -770,30 +776,15 @@ extern "C" int ogg_vorbis_decode_corpus(const uint8_t* const* datas, const size_
   copy_out.pcm_out = pcm_out;
   copy_out.cap = pcm_capacity;
   copy_out.too_long.assign(num_files, 0);
-  OkOrError r = decode_corpus(items, opts, pcm_out && pcm_capacity ? &copy_out : nullptr, results, &st);
+  std::vector<CorpusFileResult> results;
+  const OkOrError r = run_corpus(datas, lens, num_files, call_options(threads, feeders, files_per_submit, device),
+                                 pcm_out && pcm_capacity ? &copy_out : nullptr, results, stats_out);
   for (size_t i = 0; i < results.size() && i < num_files; ++i) {
     if (frames_out) frames_out[i] = results[i].frames;
     if (abs_sum_out) abs_sum_out[i] = results[i].abs_sum;
     if (ok_out) ok_out[i] = results[i].status.is_error_ || copy_out.too_long[i] ? 0 : 1;
   }
-  if (stats_out) {
-    stats_out[0] = st.wall_s;
-    stats_out[1] = st.entropy_cpu_s;
-    stats_out[2] = st.gpu_call_s;
-    stats_out[3] = st.pack_s;
-    stats_out[4] = st.deliver_s;
-    stats_out[5] = (double)st.submits;
-    stats_out[6] = (double)st.audio_packets;
-    stats_out[7] = (double)st.frames;
-  }
-  if (r.is_error_) {
-    strncpy(error_buf, r.err_msg_.c_str(), sizeof(error_buf) - 1);
-    error_buf[sizeof(error_buf) - 1] = 0;
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
-  if (error_out) *error_out = nullptr;
-  return 0;
+  return call_result(r, error_buf, error_out);
 }
 
 // The same with int16 output (CorpusOptions::pcm_s16): pcm16_out[i] (may be NULL) receives the file's interleaved frames,
@@ -802,16 +793,8 @@ extern "C" int ogg_vorbis_decode_corpus_s16(const uint8_t* const* datas, const s
                                             uint32_t files_per_submit, int device, uint64_t* frames_out, uint8_t* ok_out, int16_t* const* pcm16_out,
                                             const uint64_t* pcm_capacity_frames, double* stats_out, const char** error_out) {
   static char error_buf[256];
-  std::vector<CorpusItem> items(num_files);
-  for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
-  CorpusOptions opts;
-  opts.threads = threads;
-  opts.feeders = feeders;
-  opts.files_per_submit = files_per_submit;
-  opts.device = device;
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
   opts.pcm_s16 = true;
-  std::vector<CorpusFileResult> results;
-  CorpusStats st;
   struct CopyOut : CorpusCallbacks {
     int16_t* const* out;
     const uint64_t* cap;
@@ -829,97 +812,98 @@ extern "C" int ogg_vorbis_decode_corpus_s16(const uint8_t* const* datas, const s
   copy_out.out = pcm16_out;
   copy_out.cap = pcm_capacity_frames;
   copy_out.too_long.assign(num_files, 0);
-  OkOrError r = decode_corpus(items, opts, pcm16_out && pcm_capacity_frames ? &copy_out : nullptr, results, &st);
+  std::vector<CorpusFileResult> results;
+  const OkOrError r = run_corpus(datas, lens, num_files, opts, pcm16_out && pcm_capacity_frames ? &copy_out : nullptr, results, stats_out);
   for (size_t i = 0; i < results.size() && i < num_files; ++i) {
     if (frames_out) frames_out[i] = results[i].frames;
     if (ok_out) ok_out[i] = results[i].status.is_error_ || copy_out.too_long[i] ? 0 : 1;
   }
-  if (stats_out) {
-    const double v[8] = {st.wall_s, st.entropy_cpu_s, st.gpu_call_s, st.pack_s, st.deliver_s, (double)st.submits, (double)st.audio_packets, (double)st.frames};
-    for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
-  }
-  if (r.is_error_) {
-    snprintf(error_buf, sizeof(error_buf), "%s", r.err_msg_.c_str());
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
-  return 0;
+  return call_result(r, error_buf, error_out);
 }
 
 namespace {
 
-// One pass of a rows run (features or spectral, as set in opts): each file's rows into a malloc'd buffer of its own.
-int rows_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts,
-                float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
-                const char** error_out) {
-  // per calling thread: loader threads may run passes side by side
-  static thread_local char error_buf[256];
-  static thread_local std::vector<std::string> file_errors;
-  (void)name;
-  if (rows_out)
-    for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
-  std::vector<CorpusItem> items(num_files);
-  for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
-  std::vector<CorpusFileResult> results;
-  CorpusStats st;
-  struct CopyOut : CorpusCallbacks {  // gotFileFeatures calls never overlap (CorpusCallbacks)
-    float** out = nullptr;
-    std::vector<uint8_t> no_mem;
-    bool gotFileFeatures(size_t i, const VorbisIdHeader&, const float* rows, uint64_t n, uint32_t dim) override {
-      if (!n) return true;
-      float* p = (float*)malloc((size_t)n * dim * sizeof(float));
-      if (!p) {
-        no_mem[i] = 1;
-        return true;
-      }
-      memcpy(p, rows, (size_t)n * dim * sizeof(float));
-      out[i] = p;
-      return true;
-    }
-  } copy_out;
-  copy_out.out = rows_out;
-  copy_out.no_mem.assign(num_files, 0);
-  OkOrError r = decode_corpus(items, opts, rows_out ? &copy_out : nullptr, results, &st);
-  file_errors.assign(num_files, std::string());
-  for (size_t i = 0; i < results.size() && i < num_files; ++i) {
-    if (rows_count_out) rows_count_out[i] = results[i].feature_rows;
-    const bool bad = results[i].status.is_error_ || copy_out.no_mem[i];
-    if (bad && rows_out && rows_out[i]) {
-      free(rows_out[i]);
-      rows_out[i] = nullptr;
-    }
-    if (ok_out) ok_out[i] = bad ? 0 : 1;
-    if (error_out_per_file) {
-      file_errors[i] = results[i].status.is_error_ ? results[i].status.err_msg_ : (copy_out.no_mem[i] ? std::string(name) + ": out of host memory" : "");
-      error_out_per_file[i] = bad ? file_errors[i].c_str() : nullptr;
-    }
+// Per calling thread (loader threads may run passes side by side): the error texts of the corpus calls below.
+thread_local char corpus_error_buf[256];
+thread_local std::vector<std::string> corpus_file_errors;
+
+// Each file's output (rows, or PCM) into a malloc'd buffer of its own: the callbacks never overlap (CorpusCallbacks).
+struct MallocOut : CorpusCallbacks {
+  void** out = nullptr;
+  std::vector<uint8_t> no_mem;
+  void* alloc(size_t i, size_t bytes) {  // out[i], or NULL with no_mem[i] set
+    void* p = malloc(bytes);
+    if (!p) no_mem[i] = 1;
+    return out[i] = p;
   }
-  if (stats_out) {
-    const double v[8] = {st.wall_s, st.entropy_cpu_s, st.gpu_call_s, st.pack_s, st.deliver_s, (double)st.submits, (double)st.audio_packets, (double)st.frames};
-    for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
+  bool gotFileFeatures(size_t i, const VorbisIdHeader&, const float* rows, uint64_t n, uint32_t dim) override {
+    const size_t bytes = (size_t)n * dim * sizeof(float);
+    if (n && alloc(i, bytes)) memcpy(out[i], rows, bytes);
+    return true;
   }
-  if (r.is_error_) {
-    if (rows_out)
-      for (size_t i = 0; i < num_files; ++i) {
-        free(rows_out[i]);
-        rows_out[i] = nullptr;
-      }
-    snprintf(error_buf, sizeof(error_buf), "%s", r.err_msg_.c_str());
-    if (error_out) *error_out = error_buf;
-    return 1;
+  bool gotFilePcm(size_t i, const VorbisIdHeader&, const std::vector<DataRange<const float>>& ch) override {
+    const size_t n = ch.empty() ? 0 : ch[0].size();
+    if (n && alloc(i, n * ch.size() * sizeof(float)))
+      for (size_t c = 0; c < ch.size(); ++c) memcpy((float*)out[i] + c * n, ch[c].begin(), n * sizeof(float));
+    return true;
   }
-  if (error_out) *error_out = nullptr;
-  return 0;
+  bool gotFilePcmS16(size_t i, const VorbisIdHeader& h, const int16_t* x, uint64_t frames) override {
+    const size_t bytes = (size_t)frames * h.audio_channels * sizeof(int16_t);
+    if (frames && alloc(i, bytes)) memcpy(out[i], x, bytes);
+    return true;
+  }
+};
+
+// A call refused before the run: every out[i] NULL, 1 with *error_out = msg.
+int refuse_call(void** out, size_t num_files, const std::string& msg, const char** error_out) {
+  if (out)
+    for (size_t i = 0; i < num_files; ++i) out[i] = nullptr;
+  return call_result(OkOrError(msg), corpus_error_buf, error_out);
 }
 
-CorpusOptions rows_options(int threads, int feeders, uint32_t files_per_submit, int device) {
-  CorpusOptions opts;
-  opts.threads = threads;
-  opts.feeders = feeders;
-  opts.files_per_submit = files_per_submit;
-  opts.device = device;
+// One pass of a run whose files' outputs each come back in a malloc'd buffer (ogg_vorbis_features_free): out[i] NULL for a failed
+// file or one without output; ok_out and error_out_per_file per file, and per_file(i, result, bad) for the caller's other arrays.
+// name prefixes the out-of-memory error of a file.
+template <typename PerFile>
+int malloc_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, CorpusOptions opts, void** out,
+                  uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out, PerFile per_file) {
   opts.checksum = false;
-  return opts;
+  if (out)
+    for (size_t i = 0; i < num_files; ++i) out[i] = nullptr;
+  MallocOut copy_out;
+  copy_out.out = out;
+  copy_out.no_mem.assign(num_files, 0);
+  std::vector<CorpusFileResult> results;
+  const OkOrError r = run_corpus(datas, lens, num_files, opts, out ? &copy_out : nullptr, results, stats_out);
+  corpus_file_errors.assign(num_files, std::string());
+  for (size_t i = 0; i < results.size() && i < num_files; ++i) {
+    const bool bad = results[i].status.is_error_ || copy_out.no_mem[i];
+    if (bad && out && out[i]) {
+      free(out[i]);
+      out[i] = nullptr;
+    }
+    per_file(i, results[i], bad);
+    if (ok_out) ok_out[i] = bad ? 0 : 1;
+    if (error_out_per_file) {
+      corpus_file_errors[i] = results[i].status.is_error_ ? results[i].status.err_msg_ : (copy_out.no_mem[i] ? std::string(name) + ": out of host memory" : "");
+      error_out_per_file[i] = bad ? corpus_file_errors[i].c_str() : nullptr;
+    }
+  }
+  if (r.is_error_ && out)
+    for (size_t i = 0; i < num_files; ++i) {
+      free(out[i]);
+      out[i] = nullptr;
+    }
+  return call_result(r, corpus_error_buf, error_out);
+}
+
+// A rows run (features or spectral, as set in opts).
+int rows_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts, float** rows_out,
+                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
+  return malloc_corpus(name, datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool) {
+                         if (rows_count_out) rows_count_out[i] = res.feature_rows;
+                       });
 }
 
 }  // namespace
@@ -928,137 +912,58 @@ extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const siz
                                           uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
                                           uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                           double* stats_out, const char** error_out) {
-  static thread_local char error_buf[256];
-  if (!spec || spec->kind == 0) {
-    if (rows_out)
-      for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
-    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_features_corpus: no feature kind");
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
-  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
+  if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_features_corpus: no feature kind", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
   opts.features = *spec;
   return rows_corpus("features", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
+
+namespace {
+
+// ogg_vorbis_spectral_corpus (target_rate 0) and ogg_vorbis_spectral_corpus_sr; fn: the entry point, for its refusal text.
+int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate, float** rows_out,
+                    uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
+  if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  opts.spectral = *spec;
+  opts.resample_rate = target_rate;
+  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+}  // namespace
 
 extern "C" int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                           uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, float** rows_out,
                                           uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                           double* stats_out, const char** error_out) {
-  static thread_local char error_buf[256];
-  if (!spec || spec->kind == 0) {
-    if (rows_out)
-      for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
-    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_spectral_corpus: no spectral kind");
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
-  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
-  opts.spectral = *spec;
-  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+  return spectral_corpus("ogg_vorbis_spectral_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, 0, rows_out,
+                         rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_sr(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                              uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                                              float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                              double* stats_out, const char** error_out) {
-  static thread_local char error_buf[256];
-  if (!spec || spec->kind == 0) {
-    if (rows_out)
-      for (size_t i = 0; i < num_files; ++i) rows_out[i] = nullptr;
-    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_spectral_corpus_sr: no spectral kind");
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
-  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
-  opts.spectral = *spec;
-  opts.resample_rate = target_rate;
-  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+  return spectral_corpus("ogg_vorbis_spectral_corpus_sr", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
+                         rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
 extern "C" int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                      uint32_t files_per_submit, int device, uint32_t target_rate, int format, void** pcm_out, uint64_t* frames_out,
                                      uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file,
                                      double* stats_out, const char** error_out) {
-  static thread_local char error_buf[256];
-  static thread_local std::vector<std::string> file_errors;
-  if (pcm_out)
-    for (size_t i = 0; i < num_files; ++i) pcm_out[i] = nullptr;
-  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) {
-    snprintf(error_buf, sizeof(error_buf), "ogg_vorbis_pcm_corpus: unknown PCM format %d", format);
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
-  std::vector<CorpusItem> items(num_files);
-  for (size_t i = 0; i < num_files; ++i) items[i] = CorpusItem{datas[i], lens[i]};
-  CorpusOptions opts = rows_options(threads, feeders, files_per_submit, device);
+  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
+    return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
   opts.pcm_s16 = format == VSYN_PCM_S16;
   opts.resample_rate = target_rate;
-  std::vector<CorpusFileResult> results;
-  CorpusStats st;
-  struct CopyOut : CorpusCallbacks {  // the callbacks never overlap (CorpusCallbacks)
-    void** out = nullptr;
-    std::vector<uint8_t> no_mem;
-    bool gotFilePcm(size_t i, const VorbisIdHeader&, const std::vector<DataRange<const float>>& ch) override {
-      const size_t n = ch.empty() ? 0 : ch[0].size();
-      if (!n) return true;
-      float* p = (float*)malloc(n * ch.size() * sizeof(float));
-      if (!p) {
-        no_mem[i] = 1;
-        return true;
-      }
-      for (size_t c = 0; c < ch.size(); ++c) memcpy(p + c * n, ch[c].begin(), n * sizeof(float));
-      out[i] = p;
-      return true;
-    }
-    bool gotFilePcmS16(size_t i, const VorbisIdHeader& h, const int16_t* x, uint64_t frames) override {
-      if (!frames) return true;
-      const size_t bytes = (size_t)frames * h.audio_channels * sizeof(int16_t);
-      void* p = malloc(bytes);
-      if (!p) {
-        no_mem[i] = 1;
-        return true;
-      }
-      memcpy(p, x, bytes);
-      out[i] = p;
-      return true;
-    }
-  } copy_out;
-  copy_out.out = pcm_out;
-  copy_out.no_mem.assign(num_files, 0);
-  OkOrError r = decode_corpus(items, opts, pcm_out ? &copy_out : nullptr, results, &st);
-  file_errors.assign(num_files, std::string());
-  for (size_t i = 0; i < results.size() && i < num_files; ++i) {
-    const bool bad = results[i].status.is_error_ || copy_out.no_mem[i];
-    if (bad && pcm_out && pcm_out[i]) {
-      free(pcm_out[i]);
-      pcm_out[i] = nullptr;
-    }
-    if (frames_out) frames_out[i] = bad ? 0 : results[i].frames;
-    if (channels_out) channels_out[i] = results[i].channels;
-    if (rate_out) rate_out[i] = results[i].sample_rate;
-    if (ok_out) ok_out[i] = bad ? 0 : 1;
-    if (error_out_per_file) {
-      file_errors[i] = results[i].status.is_error_ ? results[i].status.err_msg_ : (copy_out.no_mem[i] ? "pcm: out of host memory" : "");
-      error_out_per_file[i] = bad ? file_errors[i].c_str() : nullptr;
-    }
-  }
-  if (stats_out) {
-    const double v[8] = {st.wall_s, st.entropy_cpu_s, st.gpu_call_s, st.pack_s, st.deliver_s, (double)st.submits, (double)st.audio_packets, (double)st.frames};
-    for (int i = 0; i < 8; ++i) stats_out[i] = v[i];
-  }
-  if (r.is_error_) {
-    if (pcm_out)
-      for (size_t i = 0; i < num_files; ++i) {
-        free(pcm_out[i]);
-        pcm_out[i] = nullptr;
-      }
-    snprintf(error_buf, sizeof(error_buf), "%s", r.err_msg_.c_str());
-    if (error_out) *error_out = error_buf;
-    return 1;
-  }
-  if (error_out) *error_out = nullptr;
-  return 0;
+  return malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (channels_out) channels_out[i] = res.channels;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                       });
 }
 
 extern "C" void ogg_vorbis_features_free(float* rows) { free(rows); }

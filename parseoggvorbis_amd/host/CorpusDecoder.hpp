@@ -116,8 +116,8 @@ int ogg_vorbis_decode_corpus_s16(const uint8_t* const* datas, const size_t* lens
                                  const uint64_t* pcm_capacity_frames, double* stats_out, const char** error_out);
 // feature run (CorpusOptions::features = *spec), one pass: rows_out (may be NULL) receives per file NULL (failed, or no rows) or a
 // buffer of rows_count_out[i] * spec->output_dim floats allocated by the library, to be released with ogg_vorbis_features_free.
-// error_out_per_file (may be NULL): per file NULL or the file's error text, valid until the next call of either corpus function
-// below on the same thread.
+// error_out_per_file (may be NULL): per file NULL or the file's error text, valid until the next call, on the same thread, of this
+// function or of the spectral or PCM corpus functions below.
 int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
                                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,

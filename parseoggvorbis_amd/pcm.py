@@ -4,13 +4,10 @@ res_type="polyphase", not its default soxr), computed on the device before the P
 in include/vorbis_synth_hip.h ("resampling") and the float64 model in tests/resample_model.py is the contract.
 
 Every argument is checked before the library is loaded."""
-import ctypes as C
-import os
-
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HOST_LIB_PATH = os.path.join(_HERE, "host", "libparseoggvorbis_amd.so")
+from . import _corpus
+from ._corpus import HOST_LIB_PATH  # noqa: F401
 
 FORMATS = {"float32": 2, "int16": 1}  # VSYN_PCM_F32, VSYN_PCM_S16
 MAX_RATE = 0xFFFFFFFF
@@ -40,26 +37,7 @@ def _format(dtype):
     return name
 
 
-_lib = None
-
-
-def _load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    from . import binding
-    binding.load()  # the HIP runtime (torch's, when torch is importable) before the host library
-    if not os.path.exists(HOST_LIB_PATH):
-        raise RuntimeError("host library missing: %s — run __graft_entry__.build() (there is no CPU fallback)" % HOST_LIB_PATH)
-    lib = C.CDLL(HOST_LIB_PATH)
-    vp = C.c_void_p
-    lib.ogg_vorbis_pcm_corpus.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp,
-                                          vp, vp, vp, C.POINTER(C.c_char_p)]
-    lib.ogg_vorbis_pcm_corpus.restype = C.c_int
-    lib.ogg_vorbis_features_free.argtypes = [vp]
-    lib.ogg_vorbis_features_free.restype = None
-    _lib = lib
-    return lib
+_load = _corpus.load
 
 
 def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0, device=0, errors="raise", files_per_submit=64,
@@ -69,50 +47,22 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     PCM is bit for bit that of ogg_vorbis_decode_corpus); an integer resamples every file to it on the GPU. errors="raise": the
     first failed file raises PcmError naming it; errors="return": its entry is the PcmError. stats (optional list) receives
     the run's 8 corpus statistics."""
-    if errors not in ("raise", "return"):
-        raise ValueError("errors must be 'raise' or 'return'")
+    _corpus.check_errors(errors)
     target = check_sr(sr)
     name = _format(dtype)
     lib = _load()
     n = len(list_of_bytes)
-    if n == 0:
-        return []
-    bufs = [np.frombuffer(bytes(b), np.uint8) if len(b) else np.zeros(1, np.uint8) for b in list_of_bytes]
-    datas = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in list_of_bytes])
     frames = np.zeros(n, np.uint64)
     chans = np.zeros(n, np.uint32)
     rates = np.zeros(n, np.uint32)
-    ok = np.zeros(n, np.uint8)
-    ferr = (C.c_char_p * n)()
-    pcm = (C.c_void_p * n)()
-    st = (C.c_double * 8)()
-    err = C.c_char_p()
-    rc = lib.ogg_vorbis_pcm_corpus(datas, lens, n, threads, feeders, files_per_submit, device, target, FORMATS[name], pcm,
-                                   frames.ctypes.data, chans.ctypes.data, rates.ctypes.data, ok.ctypes.data, ferr, st, C.byref(err))
-    if rc != 0:
-        raise PcmError("pcm corpus run failed: %s" % (err.value or b"").decode())
-    if stats is not None:
-        stats[:] = list(st)
-    res = []
-    try:
-        for i in range(n):
-            if not ok[i]:
-                e = PcmError("file %d: %s" % (i, (ferr[i] or b"failed").decode(errors="replace")))
-                if errors == "raise":
-                    raise e
-                res.append(e)
-                continue
-            T, Cn = int(frames[i]), int(chans[i])
-            a = np.zeros((Cn, T), np.float32) if name == "float32" else np.zeros((T, Cn), np.int16)
-            if a.size and pcm[i]:
-                C.memmove(a.ctypes.data, pcm[i], a.nbytes)
-            res.append((a, int(rates[i])))
-    finally:
-        for i in range(n):
-            if pcm[i]:
-                lib.ogg_vorbis_features_free(pcm[i])
-    return res
+
+    def build(i, p):
+        T, Cn = int(frames[i]), int(chans[i])
+        a = np.zeros((Cn, T), np.float32) if name == "float32" else np.zeros((T, Cn), np.int16)
+        return _corpus.copy_into(a, p), int(rates[i])
+
+    return _corpus.run(lib, lib.ogg_vorbis_pcm_corpus, list_of_bytes, (threads, feeders, files_per_submit, device, target, FORMATS[name]),
+                       (frames, chans, rates), build, PcmError, errors, "pcm", stats)
 
 
 def get_pcm_from_raw_bytes(raw_bytes, sr=None, dtype="float32", **kwargs):

@@ -1,6 +1,6 @@
 """Spectral front-end features computed on the GPU from Ogg bytes: mel power, log-mel, dB-mel and MFCC matrices
 (frames, dim) float32, from the decoded PCM while it is still on the device (no PCM crosses the bus). ctypes onto
-libparseoggvorbis_amd.so (ogg_vorbis_spectral_corpus); the semantics are documented in include/vorbis_synth_hip.h ("spectral
+libparseoggvorbis_amd.so (ogg_vorbis_spectral_corpus_sr); the semantics are documented in include/vorbis_synth_hip.h ("spectral
 features"). They follow librosa's documented defaults (librosa >= 0.10); parity with librosa itself has not been verified, the
 float64 model in tests/spectral_model.py is the contract the device is tested against.
 
@@ -9,12 +9,11 @@ each file's matrix at its own rate; an integer sr resamples every file's PCM to 
 scipy.signal.resample_poly's arithmetic), so that one mel table serves the whole batch."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HOST_LIB_PATH = os.path.join(_HERE, "host", "libparseoggvorbis_amd.so")
+from . import _corpus
+from ._corpus import HOST_LIB_PATH  # noqa: F401
 
 KINDS = {"mel_power": 1, "log_mel": 2, "mel_db": 3, "mfcc": 4}
 OPT_CENTER, OPT_HTK, OPT_NO_NORM = 1, 2, 4
@@ -80,29 +79,7 @@ def spec_dim(spec):
     return spec.n_mfcc if spec.kind == KINDS["mfcc"] else spec.n_mels
 
 
-_lib = None
-
-
-def _load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    from . import binding
-    binding.load()  # the HIP runtime (torch's, when torch is importable) before the host library
-    if not os.path.exists(HOST_LIB_PATH):
-        raise RuntimeError("host library missing: %s — run __graft_entry__.build() (there is no CPU fallback)" % HOST_LIB_PATH)
-    lib = C.CDLL(HOST_LIB_PATH)
-    vp = C.c_void_p
-    lib.ogg_vorbis_spectral_corpus.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(binding.SpectralSpec),
-                                               vp, vp, vp, vp, vp, C.POINTER(C.c_char_p)]
-    lib.ogg_vorbis_spectral_corpus.restype = C.c_int
-    lib.ogg_vorbis_spectral_corpus_sr.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_int,
-                                                  C.POINTER(binding.SpectralSpec), C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(C.c_char_p)]
-    lib.ogg_vorbis_spectral_corpus_sr.restype = C.c_int
-    lib.ogg_vorbis_features_free.argtypes = [vp]
-    lib.ogg_vorbis_features_free.restype = None
-    _lib = lib
-    return lib
+_load = _corpus.load
 
 
 def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n_mels=128, fmin=0.0, fmax=None,
@@ -112,54 +89,18 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     "mfcc", n_mels otherwise. errors="raise": the first failed file raises SpectralError naming it; errors="return": its entry
     is the SpectralError. stats (optional list) receives the run's 8 corpus statistics. sr=None: each file at its own rate;
     an integer: every file resampled to sr on the device, and the mel table and the fmin / fmax check use sr."""
-    if errors not in ("raise", "return"):
-        raise ValueError("errors must be 'raise' or 'return'")
+    _corpus.check_errors(errors)
     from .pcm import check_sr
     target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
     lib = _load()
-    n = len(list_of_bytes)
-    if n == 0:
-        return []
     dim = spec_dim(spec)
-    bufs = [np.frombuffer(bytes(b), np.uint8) if len(b) else np.zeros(1, np.uint8) for b in list_of_bytes]
-    datas = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[len(b) for b in list_of_bytes])
-    counts = np.zeros(n, np.uint64)
-    ok = np.zeros(n, np.uint8)
-    ferr = (C.c_char_p * n)()
-    rows = (C.c_void_p * n)()
-    st = (C.c_double * 8)()
-    err = C.c_char_p()
-    if target:
-        rc = lib.ogg_vorbis_spectral_corpus_sr(datas, lens, n, threads, feeders, files_per_submit, device, C.byref(spec), target, rows,
-                                               counts.ctypes.data, ok.ctypes.data, ferr, st, C.byref(err))
-    else:
-        rc = lib.ogg_vorbis_spectral_corpus(datas, lens, n, threads, feeders, files_per_submit, device, C.byref(spec), rows,
-                                            counts.ctypes.data, ok.ctypes.data, ferr, st, C.byref(err))
-    if rc != 0:
-        raise SpectralError("spectral corpus run failed: %s" % (err.value or b"").decode())
-    if stats is not None:
-        stats[:] = list(st)
-    res = []
-    try:
-        for i in range(n):
-            if not ok[i]:
-                e = SpectralError("file %d: %s" % (i, (ferr[i] or b"failed").decode(errors="replace")))
-                if errors == "raise":
-                    raise e
-                res.append(e)
-                continue
-            m = np.zeros((int(counts[i]), dim), np.float32)
-            if m.size:
-                C.memmove(m.ctypes.data, rows[i], m.nbytes)
-            res.append(m)
-    finally:
-        for i in range(n):
-            if rows[i]:
-                lib.ogg_vorbis_features_free(rows[i])
-    return res
+    counts = np.zeros(len(list_of_bytes), np.uint64)
+    return _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_sr, list_of_bytes,
+                       (threads, feeders, files_per_submit, device, C.byref(spec), target), (counts,),
+                       lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors, "spectral",
+                       stats)
 
 
 def get_spectral_from_raw_bytes(raw_bytes, kind="log_mel", **kwargs):

@@ -79,22 +79,42 @@ def test_output_dim_below_the_biggest_floor_is_refused_for_residue_kinds(feats):
     assert "below the biggest floor" in str(ei.value)
 
 
+def _submits(feats, datas, entry):
+    """GPU submits of one corpus run (one feeder, three files per submit): the run's statistics, from the corpus call itself."""
+    import ctypes as C
+    from parseoggvorbis_amd import _corpus
+    kind, dim, kw = entry
+    spec, lib, stats = feats.feature_spec(dim, kind, **kw), feats._load(), []
+    counts = np.zeros(len(datas), np.uint64)
+    _corpus.run(lib, lib.ogg_vorbis_features_corpus, datas, (4, 1, 3, 0, C.byref(spec)), (counts,), lambda i, p: None, feats.FeatureError,
+                "return", "features", stats)
+    return stats[5]
+
+
 @pytest.mark.parametrize("feeders", [1, 3])
 def test_corpus_replicated_with_a_damaged_file(feats, feeders):
-    names = ["test.stereo44khz", "synth_03", "test.mono44khz", "winflags_bcd"] * 3
+    """A replicated corpus with one damaged file (file 7: a page checksum broken half way). Grid entry 15 is refused on the device
+    for synth_04 and synth_11 (feature-index, as the reference raises): their replicas share a setup each, so with one feeder
+    their submits of three are flagged and re-run file by file, and each replica fails alone."""
+    names = ["test.stereo44khz", "synth_03", "test.mono44khz", "winflags_bcd", "synth_04", "synth_11"] * 3
     datas = [_ogg(n) for n in names]
-    bad = bytearray(datas[5])
+    bad = bytearray(datas[7])
     bad[len(bad) // 2:len(bad) // 2 + 64] = bytes(64)  # breaks a page checksum half way
-    datas[5] = bytes(bad)
+    datas[7] = bytes(bad)
     grid, _ = _golden(names[0])
-    for i in (1, 7, 14):
+    if feeders == 1:  # entry 15 re-runs the two flagged submits of three file by file: six submits more than entry 14
+        assert _submits(feats, datas, grid[15]) - _submits(feats, datas, grid[14]) == 6
+    for i in (1, 7, 14, 15):
         kind, dim, kw = grid[i]
         res = feats.get_features_batch(datas, dim, kind, threads=4, feeders=feeders, files_per_submit=3, errors="return", **kw)
         for j, (name, got) in enumerate(zip(names, res)):
-            if j == 5:
-                assert isinstance(got, feats.FeatureError) and "file 5" in str(got), str(got)
+            z = _golden(name)[1]
+            if j == 7:
+                assert isinstance(got, feats.FeatureError) and "file 7" in str(got), str(got)
+            elif "e%d" % i in z.files:
+                assert isinstance(got, feats.FeatureError) and "feature-index" in str(got), (j, name, i, str(got))
             else:
-                assert_close(got, _golden(name)[1]["c%d" % i], kind, (j, name, i), kw)
+                assert_close(got, z["c%d" % i], kind, (j, name, i), kw)
 
 
 def test_features_between_submits_leave_the_pcm_alone(feats):

@@ -311,3 +311,34 @@ def test_spectral_with_resampling(mods, product_pcm):
     bad = spec_mod.get_spectral_batch(blobs[:2], sr=16000, errors="return", kind="log_mel", n_fft=400, hop_length=160, n_mels=40,
                                       fmax=11025.0)
     assert all(isinstance(r, spec_mod.SpectralError) and "16000" in str(r) for r in bad)
+
+
+@pytest.mark.parametrize("run", ["pcm-float32", "pcm-int16", "spectral"])
+@pytest.mark.parametrize("sr", [None, 16000])
+def test_refused_file_fails_alone_in_a_batch(run, sr):
+    """winflags_a is refused by the synthesis layer; in one submit with three winflags_bcd files (same setup, one
+    feeder, so all four share the submit) the flagged batch is re-run file by file: five submits. Only file 1 fails, naming the
+    condition; every other entry is bit for bit that file's result alone."""
+    from parseoggvorbis_amd import pcm, spectral
+    names = ["winflags_bcd", "winflags_a", "winflags_bcd", "winflags_bcd"]
+    blobs = [_ogg(n) for n in names]
+    stats = []
+    if run == "spectral":
+        err_cls = spectral.SpectralError
+        res = spectral.get_spectral_batch(blobs, sr=sr, feeders=1, files_per_submit=4, errors="return", stats=stats)
+        alone = [spectral.get_spectral_batch([b], sr=sr, errors="return")[0] for b in blobs]
+        arrays = lambda r: [r]  # noqa: E731
+    else:
+        err_cls = pcm.PcmError
+        dtype = run.split("-")[1]
+        res = pcm.get_pcm_batch(blobs, sr=sr, dtype=dtype, feeders=1, files_per_submit=4, errors="return", stats=stats)
+        alone = [pcm.get_pcm_batch([b], sr=sr, dtype=dtype, errors="return")[0] for b in blobs]
+        arrays = lambda r: [r[0], np.int64(r[1])]  # noqa: E731
+    assert stats[5] == 5, stats  # the flagged 4-file submit, then one per file
+    for i, (got, want) in enumerate(zip(res, alone)):
+        if i == 1:
+            assert isinstance(got, err_cls) and "file 1" in str(got) and "window-flags" in str(got), str(got)
+            continue
+        assert not isinstance(got, Exception) and not isinstance(want, Exception), (i, str(got), str(want))
+        for a, b in zip(arrays(got), arrays(want)):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), i
