@@ -188,6 +188,7 @@ struct vsyn_handle {
   uint64_t long_modes = 0;             // bit m: mode m selects a long block
   uint64_t nsub = 0;                   // submits so far
   uint32_t prep_lds_bytes = 0;         // dynamic LDS of vsyn_prep_kernel: one 32-bit column of the longest floor's posts per thread
+  uint32_t unwrap_lds_bytes = 0;       // the same for vsyn_floor_unwrap_kernel
   uint32_t submit_count = 0;
   // workspace
   // per-batch workspace, a ring indexed by the submit number so that the preparation of later submits can run ahead
@@ -356,6 +357,7 @@ static int build_const(const vsyn_setup* su, uint32_t max_streams, vsyn_handle* 
   }
   H.ys_stride = (maxp + 3u) & ~3u;
   h->prep_lds_bytes = maxp > 32 ? H.ys_stride * PREP_THREADS * (uint32_t)sizeof(uint32_t) : 16u;  // (floors of <= 32 posts stay in registers)
+  h->unwrap_lds_bytes = maxp > 32 ? H.ys_stride * UNWRAP_THREADS * (uint32_t)sizeof(uint32_t) : 16u;
 
   std::vector<MapConst> maps(su->num_mappings);
   for (uint32_t m = 0; m < su->num_mappings; ++m) {
@@ -855,8 +857,8 @@ static int submit_device_impl(vsyn_handle* h, uint32_t P, const vsyn_packet* d_p
         h->d_const, P, d_packets, S, d_segments, plane_stride, info, sinfo, h->d_state, d_emit_len, h->d_status, R, force_staged ? 0u : fmask, list, cnt,
         cnt_next, segmap, h->ws_runcls[wb].p, runs_per_seg, chunk_packets, chunks_per_seg, h->ws_chunks.p, epoch);
     const uint32_t rows = P * C;
-    vsyn_floor_unwrap_kernel<<<(rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, UNWRAP_THREADS, 0, ps>>>(h->d_const, P, nullptr, nullptr, info,
-                                                                                                       d_ys, fy, h->d_status);
+    vsyn_floor_unwrap_kernel<<<(rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, UNWRAP_THREADS, h->unwrap_lds_bytes, ps>>>(h->d_const, P, info, d_ys, fy,
+                                                                                                                          h->d_status);
     if (d_vq) {
       if (h->profile_which == 3) HIPCHK(profile_begin(h, ps, "vsyn_residue_vq_kernel"));
       if (h->vq_tables_in_lds)
@@ -1451,8 +1453,8 @@ static int feat_launch(vsyn_handle* h, const vsyn_feature_spec* sp, uint32_t P, 
   HIPCHK(hipGetLastError());
   if (!d_rows || P == 0 || max_seg == 0) return VSYN_OK;  // (no packet: every segment is empty or flagged by the count kernel)
   const uint32_t rows = P * C;
-  hipLaunchKernelGGL(vsyn_floor_unwrap_kernel, dim3(std::min<uint32_t>((rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, 65535u)), dim3(UNWRAP_THREADS), 0, s,
-                     h->d_const, P, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const PktInfo*)h->ft_info.p, d_ys, h->ft_fy.p, h->d_status);
+  hipLaunchKernelGGL(vsyn_floor_unwrap_kernel, dim3(std::min<uint32_t>((rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, 65535u)), dim3(UNWRAP_THREADS), h->unwrap_lds_bytes, s,
+                     h->d_const, P, (const PktInfo*)h->ft_info.p, d_ys, h->ft_fy.p, h->d_status);
   const uint64_t slots = (uint64_t)max_seg * C;
   const uint64_t gx = (slots + FEAT_ROW_WAVES - 1) / FEAT_ROW_WAVES;
   if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");

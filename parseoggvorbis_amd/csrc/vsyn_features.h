@@ -8,7 +8,7 @@
 //                                last packet at or before this one, inside the segment, with a used biggest-floor channel: a max scan).
 //                                Also the PktInfo fields the floor unwrap reads (own, mapping, bad).
 //   2. vsyn_feat_offsets_kernel  one workgroup: seg_row_off[S+1] from the per-segment totals.
-//   3. vsyn_floor_unwrap_kernel  (vsyn_staged.h, unchanged) floor-1 step 1 of every used (packet, channel) row.
+//   3. vsyn_floor_unwrap_kernel  (vsyn_staged.h, floor1_unwrap_rows) floor-1 step 1 of every used (packet, channel) row.
 //   4. vsyn_feat_rows_kernel     one wave64 per (packet, channel) slot, lanes across the output columns: the floor-value check of the
 //                                row (the reference's CHECK(floor[i] < 256) over all n entries), then the row itself — posts, the
 //                                integer curve evaluated at the gathered x only (floor1_curve_at, the per-bin closed form), or the

@@ -1,4 +1,5 @@
-// vsyn_staged.h — layout / floor-unwrap kernels (used by every path) and the STAGED synthesis kernels:
+// vsyn_staged.h — the layout and floor-unwrap pre-kernels (the chained preparation; vsyn_prep.h does both in one kernel; the floor-1
+// arithmetic is vsyn_floor1.h's) and the STAGED synthesis kernels:
 // any blocksize 64..8192, any channel count / coupling list, every intermediate materialised in HBM so it
 // can be handed out as a debug tap (the reference's push_data_* hooks).  Correctness-first; the fused
 // kernels in vsyn_fused.h are the speed path.  Compiled with -ffp-contract=off: every a*b+c below is two
@@ -7,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "vsyn_device.h"
+#include "vsyn_floor1.h"
 
 // ------------------------------------------------------------------------------------------------
 // K0  layout: one workgroup per segment.  Restates the integer bookkeeping of
@@ -490,215 +492,29 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
 }
 
 // ------------------------------------------------------------------------------------------------
-// K1  floor-1 step 1 (amplitude value synthesis), hpp:521-559, one thread per (packet, channel).
-// Serial over <=65 posts, parallel over the batch. Neighbour indices come precomputed from the setup
-// (Utils.hpp:60-118 depend on xs only).  uint32 wrap-around semantics as in the reference (y_t = uint32_t).
-// Output row: final_y * multiplier (saturated to 15 bits) | step2_flag << 15, header order.
+// K1  floor-1 step 1 (hpp:521-559): one thread per (packet, channel) row, floor1_unwrap_rows (vsyn_floor1.h) as in
+// vsyn_prep_kernel. Dynamic LDS: vsyn_handle::unwrap_lds_bytes (a column of the longest floor per thread when it has more than 32 posts).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t render_point_u32(uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t X) {
-  // Utils.hpp:122-137
-  uint32_t adx = x1 - x0;
-  bool up = y1 >= y0;
-  uint32_t ady = up ? y1 - y0 : y0 - y1;
-  uint32_t off = (ady * (X - x0)) / adx;
-  return up ? y0 + off : y0 - off;
-}
-
-// predicted = render_point(xs[lo], fy[lo], xs[hi], fy[hi], xs[i]) with the post geometry folded into the
-// per-floor constants dxi = xs[i]-xs[lo] and inv = 1/(xs[hi]-xs[lo]):  off = (|dy| * dxi) / adx  exactly, via
-// floor((|dy|*dxi + 0.5) * inv) while |dy|*dxi < 2^24 (always, for in-range amplitudes); else the integer divide.
-__device__ __forceinline__ uint32_t predict_post(uint32_t ylo, uint32_t yhi, uint32_t dxi, uint32_t adx, float inv) {
-  const bool up = yhi >= ylo;
-  const uint32_t ady = up ? yhi - ylo : ylo - yhi;
-  uint32_t off;
-  const uint32_t prod = ady * dxi;
-  // float path only where it is provably the integer quotient: prod + 0.5 exact (< 2^23) and the rounding of the
-  // product (<= 2.4e-7 * prod/adx) stays inside the 0.5/adx guard band (prod < 2^21); in-range amplitudes give
-  // prod <= 255 * 4096
-  if (ady < 65536u && prod < (1u << 21)) off = (uint32_t)(((float)prod + 0.5f) * inv);
-  else off = prod / adx;
-  return up ? ylo + off : ylo - off;
-}
-
 #define UNWRAP_THREADS 128
-#define UNWRAP_REG_POSTS 32
 __global__ void __launch_bounds__(UNWRAP_THREADS)
-vsyn_floor_unwrap_kernel(const uint8_t* __restrict__ cb, uint32_t P, const uint32_t* __restrict__ list, const uint32_t* __restrict__ count,
-                         const PktInfo* __restrict__ info, const uint16_t* __restrict__ ys, uint16_t* __restrict__ fy_out,
-                         DevStatus* __restrict__ status) {
-  // list == nullptr: rows are all (packet, channel) pairs; else rows come from the staged work list
-  __shared__ uint32_t s_fy[VSYN_MAX_POSTS][UNWRAP_THREADS];  // post-major: thread-contiguous, conflict-free
+vsyn_floor_unwrap_kernel(const uint8_t* __restrict__ cb, uint32_t P, const PktInfo* __restrict__ info, const uint16_t* __restrict__ ys,
+                         uint16_t* __restrict__ fy_out, DevStatus* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_rows[];  // [posts of the longest floor, rounded up to 4][UNWRAP_THREADS]
   const ConstHeader* H = hdr_of(cb);
-  const uint32_t C = H->channels, stride = H->ys_stride, t = threadIdx.x;
-  const uint32_t rows = (list ? *count : P) * C;
+  const uint32_t C = H->channels, stride = __builtin_amdgcn_readfirstlane(H->ys_stride), t = threadIdx.x;
+  const uint32_t rows = P * C;
+  // (the trip count is the same for the whole workgroup: floor1_unwrap_rows votes across the wave, rows past the end take part inactive)
   for (uint32_t base = blockIdx.x * UNWRAP_THREADS; base < rows; base += gridDim.x * UNWRAP_THREADS) {
-    const uint32_t row = base + t;
-    if (row >= rows) continue;
-    const uint32_t p = list ? (list[row / C] & 0x7FFFFFFFu) : row / C, c = row % C;
-    const uint32_t gid = p * C + c;
-    const PktInfo pi = info[p];
-    if (pi.bad || !((pi.own >> c) & 1u)) continue;
-    const FloorConst* fc = floor_of(cb, map_of(cb, pi.mapping)->chfloor[c]);
-    uint16_t* out = fy_out + (size_t)gid * stride;
-    const uint32_t posts = fc->posts, range = fc->range, mult = fc->mult;
-    // When every active row of the wavefront uses the same floor (always, unless block sizes alternate inside the 64 rows) the
-    // per-post constants are wave-uniform: read them through the scalar unit (constant address space -> s_load, scalar cache)
-    // instead of 64 identical per-lane loads per post.
-    const uint64_t fc_bits = (uint64_t)(uintptr_t)fc;
-    const uint64_t fc_first = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)fc_bits) |
-                              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(fc_bits >> 32)) << 32);
-    const bool fc_uniform = __all(fc_bits == fc_first);
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef const __attribute__((address_space(4))) u32x4* const_pk;
-    // Up to 32 posts (every floor libvorbis writes for the common modes): the row lives in a per-thread register array
-    // indexed by the wave-uniform neighbour indices (s_set_gpr_idx / v_movrel), so the serial chain over the posts is a
-    // few dozen VALU cycles per post instead of three dependent LDS round trips. 32 is where the compiler still keeps the
-    // array in registers; longer floors take the LDS path below.
-    if (fc_uniform && __builtin_amdgcn_readfirstlane(posts) <= UNWRAP_REG_POSTS) {
-      const FloorConst* fcu = (const FloorConst*)(uintptr_t)fc_first;
-      const uint32_t posts_u = __builtin_amdgcn_readfirstlane(posts);
-      uint32_t f[UNWRAP_REG_POSTS];
-      const uint2* in8 = (const uint2*)(ys + (size_t)gid * stride);
-#pragma unroll
-      for (uint32_t j = 0; j < UNWRAP_REG_POSTS / 4; ++j) {
-        uint2 w = make_uint2(0u, 0u);
-        if (j * 4 < posts_u) w = in8[j];
-        f[4 * j + 0] = w.x & 0xFFFFu;
-        f[4 * j + 1] = w.x >> 16;
-        f[4 * j + 2] = w.y & 0xFFFFu;
-        f[4 * j + 3] = w.y >> 16;
-      }
-      uint32_t flags = 3;
-      bool bad = false;
-      u32x4 kn = *(const_pk)(uintptr_t)&fcu->pk[2];
-      for (uint32_t i = 2; i < posts_u; ++i) {
-        const u32x4 kq = kn;
-        kn = *(const_pk)(uintptr_t)&fcu->pk[i + 1];  // next post's constants while this one computes (pk[] has 65 entries)
-        const uint32_t lo = kq.x & 0xFFFFu, hi = kq.x >> 16;
-        const uint32_t val = f[i], ylo = f[lo], yhi = f[hi];
-        const uint32_t dxi = kq.y & 0xFFFFu, adx = kq.y >> 16;
-        const bool up = yhi >= ylo;
-        const uint32_t ady = up ? yhi - ylo : ylo - yhi;
-        const uint32_t prod = ady * dxi;
-        uint32_t off = (uint32_t)(((float)prod + 0.5f) * __uint_as_float(kq.z));
-        if (__any(prod >= (1u << 21))) off = prod >= (1u << 21) ? prod / adx : off;
-        const uint32_t predicted = up ? ylo + off : ylo - off;
-        const bool ok = predicted <= range;  // hpp:536
-        const uint32_t pr = ok ? predicted : 0u;
-        const uint32_t high_room = range - pr, low_room = pr;
-        const uint32_t room = min(high_room, low_room) * 2;
-        const uint32_t big = high_room > low_room ? val - low_room + pr : pr - val + high_room - 1;
-        const uint32_t small = (val & 1u) ? pr - (val + 1) / 2 : pr + val / 2;
-        const uint32_t fn = val == 0 ? pr : (val >= room ? big : small);
-        const uint32_t touched = (1u << lo) | (1u << hi) | (1u << i);  // lo, hi < i < 32
-        flags |= val != 0 ? touched : 0u;
-        bad = bad || !ok;
-        f[i] = bad ? 0u : fn;  // after the first out-of-range prediction the row is dropped; keep the chain tame
-      }
-      uint2* out8 = (uint2*)out;
-      if (bad) raise_status(status, VSYN_ST_FLOOR_RANGE, p);
-#pragma unroll
-      for (uint32_t j = 0; j < UNWRAP_REG_POSTS / 4; ++j) {
-        if (j * 4 >= posts_u) break;
-        uint32_t w[4];
-#pragma unroll
-        for (uint32_t e = 0; e < 4; ++e) {
-          const uint32_t i = 4 * j + e;
-          uint32_t v = f[i] * mult;  // hpp:573,578
-          if (v > 0x7FFFu || f[i] > 0x7FFFu) v = 0x7FFFu;
-          w[e] = i < posts_u ? (bad ? 0x8000u : (v | (((flags >> i) & 1u) << 15))) : 0u;
-        }
-        out8[j] = make_uint2(w[0] | (w[1] << 16), w[2] | (w[3] << 16));
-      }
-      continue;
+    const uint32_t row = base + t, p = row / C, c = row - p * C;
+    bool act = false;
+    uint32_t fl_id = 0xFFFFFFFFu;
+    if (row < rows) {
+      const PktInfo pi = info[p];
+      act = !pi.bad && ((pi.own >> c) & 1u);
+      if (act) fl_id = map_of(cb, pi.mapping)->chfloor[c];
     }
-    {  // whole coded row up front (16-byte loads; rows are 8-byte aligned multiples of 4 posts), values parked in LDS
-      const uint2* in8 = (const uint2*)(ys + (size_t)gid * stride);
-      for (uint32_t j = 0; j * 4 < posts; ++j) {
-        const uint2 w = in8[j];
-        s_fy[4 * j + 0][t] = w.x & 0xFFFFu;
-        if (4 * j + 1 < VSYN_MAX_POSTS) s_fy[4 * j + 1][t] = w.x >> 16;
-        if (4 * j + 2 < VSYN_MAX_POSTS) s_fy[4 * j + 2][t] = w.y & 0xFFFFu;
-        if (4 * j + 3 < VSYN_MAX_POSTS) s_fy[4 * j + 3][t] = w.y >> 16;
-      }
-    }
-    uint64_t flags_lo = 3;
-    uint32_t flag_64 = 0;
-    bool bad = false;
-    // one post: kq = its constants (neighbour indices, dx, 1/adx). Selects, no branches (the body ran as ~120 instructions
-    // of exec-mask juggling per post; at two waves per SIMD every instruction of it costs ~8 cycles).
-    auto step = [&](uint32_t i, const uint4 kq) -> bool {
-      const uint32_t lo = kq.x & 0xFFFFu, hi = kq.x >> 16;
-      const uint32_t val = s_fy[i][t];  // coded value; overwritten below by the amplitude
-      const uint32_t ylo = s_fy[lo][t], yhi = s_fy[hi][t];
-      const uint32_t dxi = kq.y & 0xFFFFu, adx = kq.y >> 16;
-      // predict_post() with its rare integer-divide path taken only if some lane needs it (wave-uniform branch)
-      const bool up = yhi >= ylo;
-      const uint32_t ady = up ? yhi - ylo : ylo - yhi;
-      const uint32_t prod = ady * dxi;
-      uint32_t off = (uint32_t)(((float)prod + 0.5f) * __uint_as_float(kq.z));
-      if (__any(prod >= (1u << 21))) off = prod >= (1u << 21) ? prod / adx : off;
-      const uint32_t predicted = up ? ylo + off : ylo - off;
-      const bool ok = predicted <= range;  // hpp:536
-      const uint32_t pr = ok ? predicted : 0u;
-      const uint32_t high_room = range - pr, low_room = pr;
-      const uint32_t room = min(high_room, low_room) * 2;
-      const uint32_t big = high_room > low_room ? val - low_room + pr : pr - val + high_room - 1;
-      const uint32_t small = (val & 1u) ? pr - (val + 1) / 2 : pr + val / 2;
-      const uint32_t f = val == 0 ? pr : (val >= room ? big : small);
-      const uint64_t touched = (1ull << lo) | (1ull << hi) | (i < 64 ? 1ull << i : 0ull);  // lo, hi < i <= 64
-      flags_lo |= val != 0 ? touched : 0ull;
-      flag_64 |= (val != 0 && i >= 64) ? 1u : 0u;
-      s_fy[i][t] = f;
-      return ok;
-    };
-    if (fc_uniform) {
-      const FloorConst* fcu = (const FloorConst*)(uintptr_t)fc_first;
-      const uint32_t posts_u = __builtin_amdgcn_readfirstlane(posts);
-      for (uint32_t i = 2; i < posts_u && !bad; ++i) {
-        const u32x4 w = *(const_pk)(uintptr_t)&fcu->pk[i];
-        if (!step(i, make_uint4(w.x, w.y, w.z, w.w))) bad = true;
-      }
-    } else {
-      for (uint32_t i = 2; i < posts && !bad; ++i)
-        if (!step(i, *(const uint4*)&fc->pk[i])) bad = true;
-    }
-    if (bad) {
-      raise_status(status, VSYN_ST_FLOOR_RANGE, p);
-      for (uint32_t i = 0; i < posts; ++i) out[i] = 0x8000;  // flat zero curve, all flagged: harmless
-      continue;
-    }
-    uint2* out8 = (uint2*)out;
-    for (uint32_t j = 0; j * 4 < posts; ++j) {  // 8-byte stores, 4 posts each (row stride is a multiple of 4)
-      uint32_t w[4];
-#pragma unroll
-      for (uint32_t e = 0; e < 4; ++e) {
-        const uint32_t i = 4 * j + e;
-        const uint32_t f = i < posts ? s_fy[i < VSYN_MAX_POSTS ? i : 0][t] : 0u;
-        uint32_t v = f * mult;  // hpp:573,578
-        if (v > 0x7FFFu || f > 0x7FFFu) v = 0x7FFFu;  // wrapped / absurd amplitude: renders >= 256 -> FLOOR_VALUE later
-        const uint32_t fl = i < 64 ? (uint32_t)((flags_lo >> i) & 1ull) : (i == 64 ? flag_64 : 0u);
-        w[e] = i < posts ? (v | (fl << 15)) : 0u;
-      }
-      out8[j] = make_uint2(w[0] | (w[1] << 16), w[2] | (w[3] << 16));
-    }
+    floor1_unwrap_rows(cb, ys, fy_out, status, act, fl_id, p, row, stride, (floor1_lds_u32*)s_rows + t, UNWRAP_THREADS);
   }
-}
-
-// floor-1 step 2 for ONE bin (hpp:563-589): value of the piecewise-linear integer curve at x.
-// render_line's DDA (Utils.hpp:143-183) equals render_point per x (tests/test_oracle_vs_ref.py::test_render_helpers).
-// Generic linear walk over the sorted posts; the fused kernels use a precomputed segment table instead.
-__device__ __forceinline__ uint32_t floor1_curve_at(const FloorConst* fc, const uint16_t* __restrict__ fyrow, uint32_t x) {
-  uint32_t lx = 0, ly = fyrow[fc->sorted_idx[0]] & 0x7FFFu;
-  for (uint32_t s = 1; s < fc->posts; ++s) {
-    const uint32_t v = fyrow[fc->sorted_idx[s]];
-    if (!(v >> 15)) continue;
-    const uint32_t hx = fc->xs_sorted[s], hy = v & 0x7FFFu;
-    if (x < hx) return render_point_u32(lx, ly, hx, hy, x);
-    lx = hx;
-    ly = hy;
-  }
-  return ly;  // flat extension, hpp:583-584
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -352,10 +352,11 @@ def test_garbage_descriptors_and_posts(flags):
 
 @pytest.mark.parametrize("bs0,bs1", [(256, 2048), (128, 1024)])
 def test_absurd_coded_posts_unwrap_alike_on_every_preparation(bs0, bs1):
-    """Coded floor values far outside a valid stream's range (up to 65535: |dy| * dx beyond 2^21, where the preparation kernel's float
-    form of hpp:533's division is no longer exact and the row is redone with the integer division): `floor_final` of the
-    dependency-free preparation kernel == the chained pre-kernels == the staged path, bit for bit, flagged rows included; and equal
-    to the oracle's rows wherever the oracle raises nothing."""
+    """Coded floor values far outside a valid stream's range (up to 65535: |dy| * dx beyond 2^21, where the float form of hpp:533's
+    division is no longer exact and floor1_unwrap_rows redoes the row with the integer division): `floor_final` of the
+    dependency-free preparation kernel == the chained pre-kernels == the staged path, bit for bit, flagged rows included (both
+    kernels run floor1_unwrap_rows; each picks its rows, their floors and its LDS itself); and equal to the oracle's rows wherever
+    the oracle raises nothing."""
     spec = fixture_like_spec(2, bs0, bs1)
     b = synth_batch(spec, 3, 40, "mixed", seed=31)
     rng = np.random.default_rng(5)
