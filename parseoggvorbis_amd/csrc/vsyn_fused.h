@@ -12,8 +12,9 @@
 //   * after the post rotation lane `l` holds points m = kappa + 64 c' (kappa = swap3(l)), and
 //     point m of consecutive packets produces the SAME output samples (s, 1023-s): the overlap carry is
 //     kept in 8 registers per channel for the whole run; the window is applied on the fly.
-//   * the first packet of a run whose predecessor belongs to another wave is recomputed (one-packet halo,
-//     1/R extra work) instead of communicated.
+//   * ring mode (a workgroup of 8 steady runs x 2 channels): slot j takes every 8th packet of the 8 runs, and a packet's overlap
+//     carry comes from the slot in front of it through LDS; only the chunk's first packet recomputes its predecessor (one halo per
+//     8 runs). Otherwise a wave owns a run and recomputes the packet in front of it (one-packet halo, 1/R extra work).
 //
 // Everything the reference rounds separately is rounded separately here (file is built -ffp-contract=off;
 // FMAs are explicit): coupling and floor product are bit-exact, `pcm += block*window` is mul-then-add.
@@ -23,7 +24,7 @@
 #include "vsyn_device.h"
 
 #ifndef FUSED_WAVES
-#define FUSED_WAVES 8     // waves per workgroup (tables are shared per workgroup)
+#define FUSED_WAVES 16    // waves per workgroup (tables are shared per workgroup): 8 runs x 2 channels in ring mode
 #endif
 #ifndef FUSED_MIN_WAVES_PER_SIMD
 #define FUSED_MIN_WAVES_PER_SIMD 4
@@ -182,6 +183,33 @@ __device__ __forceinline__ void pair_post(lds_u32* flag, uint32_t v) {
 __device__ __forceinline__ void pair_wait(const lds_u32* flag, uint32_t v) {
   asm volatile("" ::: "memory");
   while (*(const volatile lds_u32*)flag < v) __builtin_amdgcn_s_sleep(1);
+  asm volatile("" ::: "memory");
+}
+
+// Ring mode (fused_kernel_body): the LDS a slot wave uses to hand its packets' overlap carry to the next slot. Counters are tags
+// q - chunk start + 2 (the halo, one packet before the chunk, is 1): flags[0] "my carry slot holds packet #tag", flags[1] "I have read
+// my predecessor's packet #tag". A packet's P (8 floats per lane, lane-major: conflict-free) is published right after its
+// post-rotation, before the wave waits for its predecessor's: every wait is on a neighbour's same or previous step, nothing chains.
+struct RingLds {
+  lds_f32* mine = nullptr;            // this wave's carry slot [8][64]
+  const lds_f32* pred = nullptr;      // the predecessor slot's (same channel)
+  lds_u32* flags = nullptr;           // this wave's [posted, consumed]
+  const lds_u32* pred_flags = nullptr;
+  const lds_u32* succ_flags = nullptr;
+  uint32_t slot = 0;
+};
+// Bounded: the slots of a ring always reach the counts they wait for, so the bound is never met — but a wave that waited for ever
+// would hold a shared device, so after ~2 s it flags the batch (VSYN_ST_BAD_SEGMENT) and goes on; `dead` then skips its later waits.
+__device__ __forceinline__ void ring_wait(const lds_u32* flag, uint32_t v, DevStatus* status, bool& dead) {
+  asm volatile("" ::: "memory");
+  uint32_t spins = 0;
+  while (!dead && *(const volatile lds_u32*)flag < v) {
+    __builtin_amdgcn_s_sleep(2);
+    if (++spins > (1u << 24)) {
+      if ((threadIdx.x & 63u) == 0) atomicOr(&status->flags, VSYN_ST_BAD_SEGMENT);
+      dead = true;
+    }
+  }
   asm volatile("" ::: "memory");
 }
 
@@ -539,10 +567,17 @@ __device__ __forceinline__ uint32_t fused_short_pass(const FusedArgs& A, const F
 //   K_CARRY   from the stream's carry buffer (windowed right half in natural order) for a long block after a long carry-in.
 // `buf = 0; buf += prev*w; buf += cur*w` (hpp:1008-1017) with the same two roundings in every case.
 
-template <int ROLE, bool MIXED, bool TAPC>
+//
+// RING (steady runs only): [qa, qb) is the chunk of the workgroup's 8 runs and the wave is slot rl.slot of its ring: it takes the
+// packets qa + slot, qa + slot + 8, ... and the chunk's halo qa - 1 is slot 7's first packet. The overlap carry P of a packet is
+// published to the next slot and the predecessor's is read from LDS (RingLds) — the same f32 values the wave would have kept.
+template <int ROLE, bool MIXED, bool TAPC, bool RING = false>
 __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImage& T, float2* __restrict__ xb, const float2* __restrict__ pxb, float4* __restrict__ seg,
                                           lds_f32* cbuf, lds_u32* my_flags, const lds_u32* partner_flags, const uint32_t lane0, const uint32_t g,
-                                          const vsyn_segment sg, const SegInfo si, const uint32_t qa, const uint32_t qb, const uint32_t C, const uint32_t c) {
+                                          const vsyn_segment sg, const SegInfo si, const uint32_t qa, const uint32_t qb, const uint32_t C, const uint32_t c,
+                                          const RingLds& rl = RingLds()) {
+  static_assert(!(RING && MIXED), "ring mode is a steady-run mode");
+  constexpr uint32_t STEP = RING ? 8u : 1u;  // packets between two iterations of the wave
   constexpr uint32_t ML = 1024;
   const uint8_t* __restrict__ cb = A.cb;
   const ConstHeader* H = hdr_of(cb);
@@ -575,7 +610,9 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
   const FloorConst* const floors = (const FloorConst*)(cb + H->off_floor);
   uint32_t cur_map = 0xFFFFFFFFu, map_floor = 0, posts = 0;
 
-  const uint32_t q0 = qa ? qa - 1 : 0;
+  const uint32_t q0 = RING ? ((rl.slot == 7u && qa) ? qa - 1u : qa + rl.slot) : (qa ? qa - 1 : 0);
+  if (RING && q0 >= qb) return;  // a chunk shorter than one round of slots: nothing for this one
+  bool ring_dead = false;
   const PktInfo* const ip = A.info + __builtin_amdgcn_readfirstlane(sg.first_packet);
   PktScalars pi = pkt_load(ip + q0);
   float2 raw[8];  // own channel's residue (steady runs: requested one packet ahead)
@@ -630,7 +667,7 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
   // FETCH_SIZE x2 = 1.10 GB vs 0.55 GB per launch). my_flags[0] = "my image holds packet #n's residue",
   // my_flags[1] = "I have read the partner's image of packet #n".
   uint32_t q = q0;
-  for (uint32_t it = 0; q < qb; ++it, ++q) {  // (a packed short pass advances q by more than one: `it` counts hand-off epochs)
+  for (uint32_t it = 0; q < qb; ++it, q += STEP) {  // (a packed short pass advances q by more than one: `it` counts hand-off epochs)
     STAMP(0);  // loop overhead / previous iteration's tail
     // launder the lane id once per packet: keeps the lane-derived LDS/global addresses from being hoisted out of
     // the loop and pinned in VGPRs for its whole duration (recomputing them costs a few VALU ops)
@@ -638,8 +675,10 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
     const uint32_t lane = lane_v;
     const uint32_t kappa = ((lane & 7u) << 3) | (lane >> 3);
     const uint32_t p = sg.first_packet + q;
-    const bool halo = q < qa, has_next = q + 1 < qb;
-    const PktScalars pin = pkt_load(ip + (has_next ? q + 1 : q));  // one packet ahead
+    const bool halo = q < qa, has_next = q + STEP < qb;
+    const PktScalars pin = pkt_load(ip + (has_next ? q + STEP : q));  // one packet ahead (ring: this slot's next packet)
+    // ring: the window flag of the packet in front comes from its descriptor (the register copy belongs to another slot)
+    if (RING) prev_next_long = q ? (pkt_load(ip + q - 1u).widx >> 1) & 1u : 1u;
     const bool lng = !MIXED || pi.lng != 0u;
     const bool nlng = !MIXED || pin.lng != 0u;
     const uint32_t M = lng ? ML : 128u;
@@ -825,7 +864,7 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
     STAMP(2);  // next packet's loads issued, floor set-up (coded row arrival, ballot, two bpermutes, entry write)
     // coded posts of packet q+1, one packet ahead (valid if the floor does not change)
     vrow_ok = has_next && pin.mapping == pi.mapping && cur_floor >= 0;
-    vrow = (A.fy + ((size_t)(has_next ? p + 1 : p) * C + c) * ys_stride)[sidx];
+    vrow = (A.fy + ((size_t)(has_next ? p + STEP : p) * C + c) * ys_stride)[sidx];
 
     // ---- floor curve at this lane's 16 bins + product (hpp:585-589, 1243-1255) -----------------------------
     // (a channel without a curve was given a constant x1.0 / x0.0 entry above: no branch here)
@@ -905,6 +944,23 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) z[k] = cmulf(z[k], T.post[k][lane]);
+      if (RING) {
+        // publish this packet's carry (once the next slot has read this slot's previous one), then take the predecessor's
+        const uint32_t tag = q + 2u - qa;
+        if (q != q0) ring_wait(&rl.succ_flags[1], tag - 8u, A.status, ring_dead);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) rl.mine[64 * k + lane] = k >= 4 ? z[k].y : -z[k].x;
+        pair_post(&rl.flags[0], tag);
+        if (!halo && q != 0u) {
+          ring_wait(&rl.pred_flags[0], tag - 1u, A.status, ring_dead);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) P[k] = rl.pred[64 * k + lane];
+          pair_post(&rl.flags[1], tag - 1u);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) P[k] = 0.f;
+        }
+      }
 
       // ---- window + overlap-add + PCM store (hpp:1008-1059) --------------------------------------------------
       // point m = kappa + 64k gives samples s and 1023-s of this packet's output:
@@ -1090,18 +1146,19 @@ static_assert(FUSED_WAVES % 2 == 0, "the two channel waves of a run must share a
 template <bool TAPC>
 __device__ __forceinline__ void fused_kernel_body(const FusedArgs& A) {
   // one LDS block with a fixed member order: the floor entry tables come first so that their addresses fit the 16 bits
-  // fused_run packs them into (the whole block is 72 KB)
+  // fused_run packs them into (the whole block is 147 KB: one workgroup of 16 waves per CU)
   struct Lds {
     float4 seg[FUSED_WAVES][64];
-    uint32_t flag[FUSED_WAVES][2];
+    uint32_t flag[FUSED_WAVES][4];  // [0], [1]: channel-pair hand-off; [2], [3]: ring (RingLds::flags)
     FusedLdsImage t;
     float2 x[FUSED_WAVES][FUSED_XSLOTS];
+    float ring[FUSED_WAVES][8 * 64];  // ring mode: each wave's carry slot
   };
   __shared__ Lds s_lds;
   FusedLdsImage& s_t = s_lds.t;
   float2 (&s_x)[FUSED_WAVES][FUSED_XSLOTS] = s_lds.x;
   float4 (&s_seg)[FUSED_WAVES][64] = s_lds.seg;
-  uint32_t (&s_flag)[FUSED_WAVES][2] = s_lds.flag;
+  uint32_t (&s_flag)[FUSED_WAVES][4] = s_lds.flag;
   static_assert(sizeof(s_lds.seg) + sizeof(s_lds.flag) < 65536, "floor entry addresses are packed into 16 bits");
   const ConstHeader* H = hdr_of(A.cb);
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1118,9 +1175,11 @@ __device__ __forceinline__ void fused_kernel_body(const FusedArgs& A) {
   vsyn_segment sg = {};
   SegInfo si = {};
   uint32_t cls = 0xFFu;
+  bool seg_ok = false;
   if (g < A.S) {
     sg = A.segs[g];
     if (sg.stream < H->max_streams && !(sg.residue_off & 3)) {  // (otherwise the layout kernel flagged the segment)
+      seg_ok = true;
       si = A.sinfo[g];
       cls = __builtin_amdgcn_readfirstlane((uint32_t)A.run_cls[(size_t)g * A.runs_per_seg + run]);
     }
@@ -1133,10 +1192,20 @@ __device__ __forceinline__ void fused_kernel_body(const FusedArgs& A) {
     const uint4* src = (const uint4*)A.lds_image;
     uint4* dst = (uint4*)&s_t;
     for (uint32_t i = threadIdx.x; i < sizeof(FusedLdsImage) / 16; i += FUSED_WAVES * 64) dst[i] = src[i];
-    if (threadIdx.x < FUSED_WAVES * 2) (&s_flag[0][0])[threadIdx.x] = 0u;
+    if (threadIdx.x < FUSED_WAVES * 4) (&s_flag[0][0])[threadIdx.x] = 0u;
   }
-  __syncthreads();  // the only workgroup-wide barrier: from here on a wave meets nobody but its coupling partner (pair_post/pair_wait)
-  if (!active) return;  // a run is active for all its channels or for none: no partner is left waiting
+  // Ring mode: the workgroup holds 8 consecutive runs x 2 channels of one segment and every run of them that has packets is a steady
+  // long run. Then the 8 channel pairs become the slots of a ring over the chunk of the 8 runs (fused_run<.., RING>): the halo is paid
+  // once per chunk, and each step of the workgroup reads one contiguous block of 8 packets and writes 8 contiguous blocks per channel
+  // plane. Otherwise every wave takes its own run as below.
+  static_assert(FUSED_WAVES == 16, "ring mode: 8 slots x 2 channels");
+  const uint32_t unit0 = blockIdx.x * FUSED_WAVES;
+  const bool one_seg = unit0 / per_seg == (unit0 + FUSED_WAVES - 1u) / per_seg;
+  const bool ring_ok = C == 2u && one_seg && g < A.S && (A.fused_ok & 1u) && seg_ok && (cls == 1u || qa >= sg.num_packets);
+  // the only workgroup-wide barrier: from here on a wave meets nobody but its coupling partner (pair_post/pair_wait) and, in ring mode,
+  // the slots beside it
+  const bool ring = __syncthreads_and(ring_ok ? 1 : 0);
+  if (!ring && !active) return;  // a run is active for all its channels or for none: no partner is left waiting
   const uint32_t mag = A.coupling_mode == 1 ? 0u : 1u;  // the magnitude channel of the (single) coupling step
   const int role = (A.coupling_mode == 0 || C < 2) ? 0 : (c == mag ? 1 : 2);
   const uint32_t pw = role ? (wave ^ 1u) : wave;  // partner wave
@@ -1145,7 +1214,20 @@ __device__ __forceinline__ void fused_kernel_body(const FusedArgs& A) {
   // mixed runs: the 128 overlap frames that change hands when the block size changes live in the second half of the wave's
   // floor-entry block (the entries are 8 bytes: 64 of them fill the first 512 bytes)
   lds_f32* cbw = (lds_f32*)((float*)s_seg[wave] + 128);
-  if (cls == 1u) {
+  if (ring) {
+    const uint32_t slot = wave >> 1, pred = ((slot + 7u) & 7u) * 2u + c, succ = ((slot + 1u) & 7u) * 2u + c;
+    RingLds rl;
+    rl.mine = (lds_f32*)s_lds.ring[wave];
+    rl.pred = (const lds_f32*)s_lds.ring[pred];
+    rl.flags = (lds_u32*)&s_flag[wave][2];
+    rl.pred_flags = (const lds_u32*)&s_flag[pred][2];
+    rl.succ_flags = (const lds_u32*)&s_flag[succ][2];
+    rl.slot = slot;
+    const uint32_t ca = qa - slot * A.R, ce = min(sg.num_packets, ca + 8u * A.R);  // the chunk of the workgroup's 8 runs
+    if (role == 0) fused_run<0, false, TAPC, true>(A, s_t, s_x[wave], s_x[pw], s_seg[wave], cbw, mf, pf, lane, g, sg, si, ca, ce, C, c, rl);
+    else if (role == 1) fused_run<1, false, TAPC, true>(A, s_t, s_x[wave], s_x[pw], s_seg[wave], cbw, mf, pf, lane, g, sg, si, ca, ce, C, c, rl);
+    else fused_run<2, false, TAPC, true>(A, s_t, s_x[wave], s_x[pw], s_seg[wave], cbw, mf, pf, lane, g, sg, si, ca, ce, C, c, rl);
+  } else if (cls == 1u) {
     if (role == 0) fused_run<0, false, TAPC>(A, s_t, s_x[wave], s_x[pw], s_seg[wave], cbw, mf, pf, lane, g, sg, si, qa, qb, C, c);
     else if (role == 1) fused_run<1, false, TAPC>(A, s_t, s_x[wave], s_x[pw], s_seg[wave], cbw, mf, pf, lane, g, sg, si, qa, qb, C, c);
     else fused_run<2, false, TAPC>(A, s_t, s_x[wave], s_x[pw], s_seg[wave], cbw, mf, pf, lane, g, sg, si, qa, qb, C, c);
@@ -1303,6 +1385,8 @@ static inline const char* fused_kernel_name(const ConstHeader&) { return "vsyn_f
 static inline const char* fused_imdct_kernel_name(uint32_t) { return "vsyn_imdct_wave_kernel"; }
 
 // run length: as few runs as fill the chip once (halo overhead is 1/R), never below 4; run_len != 0 overrides it (VSYN_RUN_LEN)
+// Ring mode takes chunks of 8 runs: the exact fit makes them one round of workgroups, which is where the ring pattern streams best
+// (measured: chunks of 256 packets 5.42 TB/s, 128 5.34, 64 5.26 on the bare pattern), so the rule serves both modes unchanged.
 static inline uint32_t fused_pick_run_len(uint32_t run_len, int waves_per_cu, uint32_t S, uint32_t channels, uint32_t max_seg_packets, int num_cus) {
   if (run_len) return run_len;
   const uint64_t slots = (uint64_t)num_cus * (uint64_t)waves_per_cu;

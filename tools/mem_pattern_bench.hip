@@ -4,6 +4,7 @@
 // 16 waves per CU — exactly the fused kernel's geometry (64 streams x 32 runs x 2 channels = 4096 waves). Variants:
 //   width   8 or 16 bytes per lane per instruction (global_load/store_dwordx2 vs dwordx4)
 //   layout  "runs": the kernel's geometry;  "linear": the same bytes as one flat copy (wave w handles blocks w, w + W, ...)
+//   ring    `mem_pattern_bench ring`: the interleaved ring of 16-wave workgroups (walk_ring) beside the runs
 //   pace    0: as fast as memory allows;  N > 0: N dependent FMAs per lane between load and store (a wave then issues its next
 //           request only every ~N*4 cycles, as a computing wave does)
 //   hipcc --offload-arch=gfx950 -O3 -o tools/mem_pattern_bench tools/mem_pattern_bench.hip
@@ -241,6 +242,101 @@ static void run_pair(const char* name, const float* in, float* out, uint32_t str
   printf("%-44s: %.3f ms  %.2f TB/s (read + write)\n", name, best, bytes / best / 1e9);
 }
 
+
+// Interleaved ring (the geometry of the fused kernel's ring mode): one 16-wave workgroup per chunk of K consecutive packets of one
+// stream, 8 slots x 2 channels. Slot j takes packets j, j + 8, j + 16, ... of the chunk (one 4 KiB block of its channel each, one
+// packet ahead), so a step of the workgroup reads one contiguous 8 x 8 KiB block and writes 8 x 4 KiB contiguous per channel plane.
+// Each packet hands a 2 KiB carry (8 floats per lane) to the next slot through LDS with two monotonic counters per wave ("my slot
+// holds packet #n", "I have read my predecessor's #n"): the wave publishes its own carry first, then waits for its predecessor's
+// (slot 0: slot 7's of the previous step) — nearest-neighbour dependencies, nothing chains. Waits are bounded: a wait that runs
+// past its limit sets *timeout and the wave goes on.
+__device__ __forceinline__ bool ring_wait(const __attribute__((address_space(3))) uint32_t* f, uint32_t v) {
+  for (uint32_t n = 0; *(const volatile __attribute__((address_space(3))) uint32_t*)f < v; ++n) {
+    if (n > (1u << 20)) return false;
+    __builtin_amdgcn_s_sleep(1);
+  }
+  return true;
+}
+__global__ void __launch_bounds__(1024) walk_ring(const float* __restrict__ in, float* __restrict__ out, uint32_t streams, uint32_t K,
+                                                   uint32_t ppk, uint64_t plane, uint32_t* timeout) {
+  typedef __attribute__((address_space(3))) uint32_t lu32;
+  typedef float v2 __attribute__((ext_vector_type(2)));
+  __shared__ float carry[16][8][64];
+  __shared__ uint32_t flags[16][2];  // [wave][0: posted, 1: consumed from the predecessor]
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t c = wave & 1u, j = wave >> 1;
+  const uint32_t chunks = ppk / K, s = blockIdx.x / chunks, qa = (blockIdx.x % chunks) * K;
+  if (threadIdx.x < 32) (&flags[0][0])[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint32_t me = wave, pred = ((j + 7u) & 7u) * 2u + c, succ = ((j + 1u) & 7u) * 2u + c;
+  lu32* my = (lu32*)&flags[me][0];
+  const lu32* pf = (const lu32*)&flags[pred][0];
+  const lu32* sf = (const lu32*)&flags[succ][0];
+  auto src_of = [&](uint32_t q) { return (const v2*)(in + (((size_t)s * ppk + qa + q) * 2 + c) * BLK) + lane; };
+  auto dst_of = [&](uint32_t q) { return (v2*)(out + ((size_t)s * 2 + c) * plane + (qa + q) * BLK) + lane; };
+  const uint32_t steps = K / 8;
+  v2 cur[8], nxt[8];
+  {
+    const v2* p = src_of(j);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) cur[i] = __builtin_nontemporal_load(p + 64 * i);
+  }
+  bool ok = true;
+  for (uint32_t i = 0; i < steps; ++i) {
+    const uint32_t q = j + 8 * i;
+    const v2* p = src_of(i + 1 < steps ? q + 8 : q);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) nxt[t] = __builtin_nontemporal_load(p + 64 * t);
+    // publish this packet's carry (the successor must have read the previous one)
+    if (i) ok &= ring_wait(sf + 1, i);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) carry[me][t][lane] = cur[t].y;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    *(volatile lu32*)(my + 0) = i + 1;
+    // the predecessor's carry: same step (slot j - 1), or the previous step (slot 0 from slot 7); none for the chunk's first packet
+    float pv[8];
+    const uint32_t need = j ? i + 1 : i;
+    if (need) {
+      ok &= ring_wait(pf, need);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) pv[t] = carry[pred][t][lane];
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      *(volatile lu32*)(my + 1) = need;
+    } else {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) pv[t] = 0.f;
+    }
+    v2* d = dst_of(q);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) __builtin_nontemporal_store(v2{cur[t].x + pv[t] * 1e-30f, cur[t].y}, d + 64 * t);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) cur[t] = nxt[t];
+  }
+  if (!ok && lane == 0) atomicAdd(timeout, 1u);
+}
+static void run_ring(const char* name, const float* in, float* out, uint32_t streams, uint32_t ppk, uint32_t K, uint64_t plane, uint32_t* d_to) {
+  const uint32_t blocks = streams * (ppk / K);
+  hipEvent_t e0, e1;
+  CHECK(hipEventCreate(&e0));
+  CHECK(hipEventCreate(&e1));
+  CHECK(hipMemset(d_to, 0, 4));
+  float best = 1e30f;
+  for (int rep = 0; rep < 5; ++rep) {
+    CHECK(hipEventRecord(e0, 0));
+    walk_ring<<<blocks, 1024>>>(in, out, streams, K, ppk, plane, d_to);
+    CHECK(hipEventRecord(e1, 0));
+    CHECK(hipEventSynchronize(e1));
+    float ms;
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    if (rep && ms < best) best = ms;
+  }
+  uint32_t to = 0;
+  CHECK(hipMemcpy(&to, d_to, 4, hipMemcpyDeviceToHost));
+  const double bytes = (double)streams * ppk * 2 * BLK * 4 * 2;
+  printf("%-44s: %.3f ms  %.2f TB/s (read + write)%s\n", name, best, bytes / best / 1e9, to ? "  WAIT TIME-OUT" : "");
+  if (to) exit(3);
+}
+
 template <int WIDTH, bool LINEAR, bool WRITE, int NT = 0, int ORDER = 0>
 static void run(const char* name, const float* in, float* out, uint32_t streams, uint32_t runs, uint32_t R, uint64_t plane, int pace) {
   const uint32_t ppk = runs * R, nwaves = streams * runs * 2;
@@ -273,6 +369,29 @@ int main(int argc, char** argv) {
   if (argc > 1) {
     // counter mode (round 3): `mem_pattern_bench <run length>` launches ONLY the streaming pattern at that run length (same bytes, 32 / R
     // times the waves) so that a `rocprofv3 --pmc TCC_EA0_RDREQ_DRAM_sum ...` pass sees one kernel shape; "flat" = the linear sweep
+    if (!strcmp(argv[1], "ring")) {
+      // the interleaved ring beside the kernel's runs and the shorter runs, same bytes, same run (`mem_pattern_bench ring`); three passes
+      // in alternating order so that a drift of the clock shows as spread rather than as a difference
+      uint32_t* d_to;
+      CHECK(hipMalloc((void**)&d_to, 4));
+      for (int pass = 0; pass < 3; ++pass) {
+        run<8, false, true, 3>("runs (R = 32, the kernel), nt both", in, out, streams, runs, R, plane, 0);
+        run<8, false, true, 3>("runs of 8 (x4 waves), nt both", in, out, streams, 4 * runs, R / 4, plane, 0);
+        run_ring("ring 8 slots x 2 ch, K = 64 (4 rounds)", in, out, streams, runs * R, 64, plane, d_to);
+        run_ring("ring 8 slots x 2 ch, K = 128 (2 rounds)", in, out, streams, runs * R, 128, plane, d_to);
+        run_ring("ring 8 slots x 2 ch, K = 256 (1 round)", in, out, streams, runs * R, 256, plane, d_to);
+        run_ring("ring 8 slots x 2 ch, K = 32 (8 rounds)", in, out, streams, runs * R, 32, plane, d_to);
+      }
+      return 0;
+    }
+    if (!strncmp(argv[1], "ring", 4)) {  // counter mode of one ring length: `mem_pattern_bench ring64`
+      uint32_t* d_to;
+      CHECK(hipMalloc((void**)&d_to, 4));
+      const uint32_t K = (uint32_t)atoi(argv[1] + 4);
+      if (K < 8 || K % 8 || (runs * R) % K) return 2;
+      run_ring("ring 8 slots x 2 ch", in, out, streams, runs * R, K, plane, d_to);
+      return 0;
+    }
     if (!strcmp(argv[1], "flat")) {
       run<16, true, true, 3>("linear, 16 B/lane, nt both", in, out, streams, runs, R, plane, 0);
       return 0;
