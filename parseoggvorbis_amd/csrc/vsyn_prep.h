@@ -72,9 +72,7 @@ __device__ unsigned long long g_prep_stamps[8192][PREP_NSTAMPS];
 __device__ __forceinline__ void prep_wave_scan(AbsScan& inc, uint64_t& rinc, const uint32_t lane) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
-    AbsScan o;
-    o.val = __shfl_up(inc.val, d);
-    o.set = __shfl_up(inc.set, d);
+    const AbsScan o = abs_shfl_up(inc, d);
     const uint64_t ro = __shfl_up(rinc, d);
     if ((int)lane >= d) {
       inc = abs_combine(o, inc);
@@ -278,10 +276,7 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
           const uint32_t md = kq[j].x & 0xFFu;
           const uint32_t n = PREP_N_OF_MODE(md);
           const int64_t gran = (int64_t)((uint64_t)kq[j].z | ((uint64_t)kq[j].w << 32));
-          AbsScan el;
-          el.set = gran >= 0;
-          el.val = el.set ? gran : (prev_n ? (int64_t)(prev_n / 4 + n / 4) : 0);
-          agg = abs_combine(agg, el);
+          agg = abs_combine(agg, abs_element(gran, prev_n ? (int64_t)(prev_n / 4 + n / 4) : 0));
           res += (uint64_t)C * (n / 2);
           prev_n = n;
         }
@@ -331,8 +326,7 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
     AbsScan inc = {0, 0};
     uint64_t rinc = 0;
     if (valid) {
-      inc.set = k.granule >= 0;
-      inc.val = inc.set ? k.granule : (prev_n ? (int64_t)(prev_n / 4 + n / 4) : 0);
+      inc = abs_element(k.granule, prev_n ? (int64_t)(prev_n / 4 + n / 4) : 0);
       rinc = (uint64_t)C * (n / 2);
     }
     const AbsScan own_el = inc;
@@ -347,8 +341,7 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
     {
       // the inclusive value of thread t - 1: shuffle inside the wave, LDS across the wave boundary (s_abs holds the wave totals, and
       // prep_block_scan's result already includes the earlier waves)
-      ex.val = __shfl_up(inc.val, 1);
-      ex.set = __shfl_up(inc.set, 1);
+      ex = abs_shfl_up(inc, 1);
       if (lane == 0u) {
         AbsScan pre = {0, 0};
         for (uint32_t w = 0; w < wave; ++w) pre = abs_combine(pre, s_abs[w]);
@@ -357,7 +350,7 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
     }
     (void)own_el;
     ex = abs_combine(cin, ex);
-    const int64_t abs_before = ex.set ? ex.val : abs0 + ex.val;
+    const int64_t abs_before = abs_eval(ex, abs0);
     const uint64_t res_off = sg.residue_off + cres + rex;
     const uint32_t p = sg.first_packet + q;
     // mode -> mapping and the nonzero propagate over the mapping's coupling steps (hpp:1174-1180), one DISTINCT mode of the wave at a

@@ -14,19 +14,42 @@
 // K0  layout: one workgroup per segment.  Restates the integer bookkeeping of
 // VorbisStreamDecodeState::advancePcmOffsetBeginAudioPacket / forwardReadyPcm (hpp:1019-1067) as a scan:
 //   natural frames L_q = n_{q-1}/4 + n_q/4 (0 for a stream's first packet, hpp:1021-1027)
-//   abs_after_q = granule_q if granule_q >= 0 (hpp:1028-1044,1056-1057) else abs_before_q + L_q
+//   abs_after_q = max(granule_q, abs_before_q) if granule_q >= 0 (hpp:1028-1044,1056-1057) else abs_before_q + L_q
 // plus the residue offset prefix sum and the nonzero propagate (hpp:1174-1180).
+// A granule at or ahead of the position is where the reference puts it. One BEHIND the position is refused (VSYN_ST_GRANULE, hpp:1029);
+// the max keeps it from moving the position back, so that the packets behind a refused one, which the device still lays out, land
+// behind the PCM in front of it instead of over it.
+// One packet's step is the map x -> max(lo, x + val) (set: a granule, lo = granule, val = 0) or x -> x + val (no granule, val = L_q);
+// such maps compose into the same form: max(lo2, max(lo1, x + v1) + v2) = max(max(lo2, lo1 + v2), x + v1 + v2).
 // ------------------------------------------------------------------------------------------------
 struct AbsScan {
   int64_t val;
   int set;
+  int64_t lo;
 };
-__device__ __forceinline__ AbsScan abs_combine(AbsScan a, AbsScan b) {
+__device__ __forceinline__ AbsScan abs_combine(AbsScan a, AbsScan b) {  // b after a
   AbsScan r;
-  if (b.set) return b;
-  r.set = a.set;
   r.val = a.val + b.val;
+  r.set = a.set | b.set;
+  r.lo = b.set ? (a.set ? max(b.lo, a.lo + b.val) : b.lo) : a.lo + b.val;
   return r;
+}
+// the step of one packet: its page granule (or -1) and its natural frames L
+__device__ __forceinline__ AbsScan abs_element(int64_t granule, int64_t L) {
+  AbsScan e;
+  e.set = granule >= 0;
+  e.val = e.set ? 0 : L;
+  e.lo = e.set ? granule : 0;
+  return e;
+}
+// the position behind the packets of e, starting at x
+__device__ __forceinline__ int64_t abs_eval(const AbsScan& e, int64_t x) { return e.set ? max(e.lo, x + e.val) : x + e.val; }
+__device__ __forceinline__ AbsScan abs_shfl_up(const AbsScan& e, int d) {
+  AbsScan o;
+  o.val = __shfl_up(e.val, d);
+  o.set = __shfl_up(e.set, d);
+  o.lo = __shfl_up(e.lo, d);
+  return o;
 }
 
 // Shared by the layout kernel (which builds the staged list) and the fused kernel (which skips non-fast runs):
@@ -105,7 +128,7 @@ __device__ __forceinline__ PktStep pkt_step_core(const vsyn_packet& k, bool mode
     } else {
       emit = (uint32_t)(k.granule - abs_before);
     }
-    abs_after = k.granule;
+    abs_after = k.granule < abs_before ? abs_before : k.granule;  // (a granule behind the position does not move it back: AbsScan)
   }
   const int64_t rel = abs_before - abs0;
   if (rel < 0 || (uint64_t)rel + emit > plane_stride) {
@@ -157,12 +180,13 @@ __device__ __forceinline__ PktStep pkt_step(const MapConst* __restrict__ maps, c
 #define LAYOUT_THREADS_SHORT 64
 #define LAYOUT_SHORT_PACKETS 256u
 #define LAYOUT_CHUNK_PACKETS 4096u
-struct LayoutChunk {          // look-back record of one (segment, chunk); 48 bytes
+struct LayoutChunk {          // look-back record of one (segment, chunk); 64 bytes
   uint32_t flag;              // (epoch & 2^30-1) * 4 + 1: aggregate valid, + 2: inclusive prefix valid, + 3: chain lost (no clearing between submits)
   uint32_t pad;
   int64_t agg_val, inc_val;   // AbsScan of the chunk's own packets / of everything up to its end
   uint64_t agg_res, inc_res;  // residue floats likewise
   uint32_t agg_set, inc_set;
+  int64_t agg_lo, inc_lo;
 };
 static inline __host__ __device__ size_t layout_lds_bytes(uint32_t threads, uint32_t chunk_packets) {
   return (size_t)threads * (sizeof(AbsScan) + sizeof(uint64_t)) + (size_t)((chunk_packets + 1u + 31u) / 32u) * 4u + 16u;
@@ -264,10 +288,7 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
     uint32_t prev_n = prev_n0;
     auto step_a = [&](const vsyn_packet& k) {
       const uint32_t n = n_of_mode(k.mode);
-      AbsScan e;
-      e.set = k.granule >= 0;
-      e.val = e.set ? k.granule : (prev_n ? (int64_t)(prev_n / 4 + n / 4) : 0);
-      agg = abs_combine(agg, e);
+      agg = abs_combine(agg, abs_element(k.granule, prev_n ? (int64_t)(prev_n / 4 + n / 4) : 0));
       res += (uint64_t)C * (n / 2);
       prev_n = n;
     };
@@ -290,9 +311,7 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
     uint64_t rinc = res;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-      AbsScan o;
-      o.val = __shfl_up(inc.val, d);
-      o.set = __shfl_up(inc.set, d);
+      const AbsScan o = abs_shfl_up(inc, d);
       const uint64_t ro = __shfl_up(rinc, d);
       if ((int)lane >= d) {
         inc = abs_combine(o, inc);
@@ -317,13 +336,10 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
       chunk_res += s_res[w];
     }
     // exclusive = (prefix of earlier waves) o (inclusive of lane-1)
-    AbsScan ex;
-    ex.val = __shfl_up(inc.val, 1);
-    ex.set = __shfl_up(inc.set, 1);
+    AbsScan ex = abs_shfl_up(inc, 1);
     uint64_t rex = __shfl_up(rinc, 1);
     if (lane == 0) {
-      ex.val = 0;
-      ex.set = 0;
+      ex = AbsScan{0, 0, 0};
       rex = 0;
     }
     ex = abs_combine(pre, ex);
@@ -343,6 +359,7 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
       if (ch > 0) {
         mine->agg_val = chunk_agg.val;
         mine->agg_set = (uint32_t)chunk_agg.set;
+        mine->agg_lo = chunk_agg.lo;
         mine->agg_res = chunk_res;
         __hip_atomic_store(&mine->flag, ep * 4u + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         AbsScan run = {0, 0};  // aggregate of the chunks between the record in hand and this chunk
@@ -361,12 +378,12 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
           if ((f & 3u) == 3u) lost = true;  // a predecessor gave up: so does everything behind it, at once
           if (lost) break;
           if ((f & 3u) == 2u) {
-            AbsScan a = {pr->inc_val, (int)pr->inc_set};
+            AbsScan a = {pr->inc_val, (int)pr->inc_set, pr->inc_lo};
             ex = abs_combine(a, run);
             rex = pr->inc_res + rrun;
             break;
           }
-          AbsScan a = {pr->agg_val, (int)pr->agg_set};
+          AbsScan a = {pr->agg_val, (int)pr->agg_set, pr->agg_lo};
           run = abs_combine(a, run);
           rrun += pr->agg_res;
         }
@@ -376,6 +393,7 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
       const AbsScan incl = abs_combine(ex, chunk_agg);
       mine->inc_val = incl.val;
       mine->inc_set = (uint32_t)incl.set;
+      mine->inc_lo = incl.lo;
       mine->inc_res = rex + chunk_res;
       __hip_atomic_store(&mine->flag, ep * 4u + (lost ? 3u : 2u), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       s_chunk_ex = ex;
@@ -405,7 +423,7 @@ vsyn_layout_kernel(const uint8_t* __restrict__ cb, uint32_t P, const vsyn_packet
   // pass B
   {
     AbsScan pre = abs_combine(s_chunk_ex, s_abs[t]);
-    int64_t abs_before = pre.set ? pre.val : abs0 + pre.val;
+    int64_t abs_before = abs_eval(pre, abs0);
     uint64_t res_off = sg.residue_off + s_chunk_rex + s_res[t];
     uint32_t prev_n = prev_n0, prev_tail = prev_tail0;
     auto step_b = [&](uint32_t ql, const vsyn_packet& k) {  // ql: index inside the chunk

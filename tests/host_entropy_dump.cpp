@@ -4,6 +4,9 @@
 // classification and entry numbers plus the VQ setup — and dumps it, so that tests can compare it with the reference
 // decoder's hooks in tests/golden/ and feed the same tensors to the oracle / the GPU.
 // Usage: host_entropy_dump in.ogg out.bin
+//        host_entropy_dump --prefix in.ogg out.bin   (damaged files: on a read error, dump the complete packets the reader flushed
+//                                                     in front of it and exit with status 4; 5 if it flushed none, 6 for a
+//                                                     stream without audio packets; nothing written in those two cases)
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -60,21 +63,9 @@ static int check_mode(const char* path) {
   return ok ? 0 : 3;
 }
 
-int main(int argc, char** argv) {
-  if (argc == 3 && std::string(argv[1]) == "--check") return check_mode(argv[2]);
-  if (argc != 3) return 2;
-  ParseCallbacks cb;
-  Collect sink;
-  OggReader reader(cb);
-  reader.sink_ = &sink;
-  reader.batch_limit_override_ = 0xffffffffu;  // the whole stream in one batch
-  const OkOrError r = reader.full_read(argv[1]);
-  if (r.is_error_ || sink.batches != 1) {
-    fprintf(stderr, "expected one batch (%u), result: %s\n", sink.batches, r.err_msg_.c_str());
-    return 1;
-  }
+static int write_dump(const Collect& sink, const char* path) {
   const PacketBatch& b = sink.batch;
-  FILE* f = fopen(argv[2], "wb");
+  FILE* f = fopen(path, "wb");
   if (!f) return 1;
   auto u32 = [f](uint32_t v) { fwrite(&v, 4, 1, f); };
   const uint32_t hdr[6] = {(uint32_t)b.pk.size(), sink.header.audio_channels, sink.ys_stride, (uint32_t)b.residue.size(),
@@ -117,6 +108,32 @@ int main(int argc, char** argv) {
     }
   }
   fclose(f);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc == 3 && std::string(argv[1]) == "--check") return check_mode(argv[2]);
+  const bool prefix = argc == 4 && std::string(argv[1]) == "--prefix";
+  if (argc != 3 && !prefix) return 2;
+  const char* in = argv[prefix ? 2 : 1];
+  const char* out = argv[prefix ? 3 : 2];
+  ParseCallbacks cb;
+  Collect sink;
+  OggReader reader(cb);
+  reader.sink_ = &sink;
+  reader.batch_limit_override_ = 0xffffffffu;  // the whole stream in one batch
+  const OkOrError r = reader.full_read(in);
+  if (prefix && !r.is_error_ && !sink.batches) return 6;  // a stream without audio packets
+  if (prefix && r.is_error_ && sink.batches <= 1) {
+    printf("error: %s\n", r.err_msg_.c_str());
+    if (!sink.batches) return 5;
+    return write_dump(sink, out) ? 1 : 4;
+  }
+  if (r.is_error_ || sink.batches != 1) {
+    fprintf(stderr, "expected one batch (%u), result: %s\n", sink.batches, r.err_msg_.c_str());
+    return 1;
+  }
+  if (write_dump(sink, out)) return 1;
   printf("ok\n");
   return 0;
 }

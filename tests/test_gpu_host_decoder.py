@@ -157,29 +157,8 @@ def test_corpus_survives_damaged_files(tmp_path):
     import json
     import subprocess
     from tests.test_host_decoder import CORPUS_CLI  # noqa: F401
+    from tests.workloads import fix_page_crcs as fix_crcs
     rng = np.random.default_rng(77)
-    tab = []
-    for i in range(256):
-        r = i << 24
-        for _ in range(8):
-            r = ((r << 1) ^ 0x04C11DB7) & 0xFFFFFFFF if r & 0x80000000 else (r << 1) & 0xFFFFFFFF
-        tab.append(r)
-
-    def fix_crcs(b):
-        o = 0
-        while o + 27 <= len(b) and b[o:o + 4] == b"OggS":
-            ns = b[o + 26]
-            if o + 27 + ns > len(b):
-                break
-            ln = 27 + ns + sum(b[o + 27:o + 27 + ns])
-            if o + ln > len(b):
-                break
-            b[o + 22:o + 26] = b"\0\0\0\0"
-            c = 0
-            for x in b[o:o + ln]:
-                c = ((c << 8) & 0xFFFFFFFF) ^ tab[((c >> 24) & 0xFF) ^ x]
-            b[o + 22:o + 26] = c.to_bytes(4, "little")
-            o += ln
 
     names = ["test.stereo44khz", "test.mono44khz"]
     base = [open(os.path.join(GOLDEN, n + ".ogg"), "rb").read() for n in names]

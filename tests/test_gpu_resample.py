@@ -14,6 +14,7 @@ import pytest
 
 from tests import resample_model as rm
 from tests import spectral_model as sm
+from tests.workloads import ogg_crc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -37,15 +38,6 @@ def _rate(data):
     return struct.unpack_from("<I", data, 27 + nseg + 12)[0]
 
 
-def _ogg_crc(page):
-    crc = 0
-    for b in page:
-        crc ^= b << 24
-        for _ in range(8):
-            crc = ((crc << 1) ^ 0x04C11DB7) & 0xFFFFFFFF if crc & 0x80000000 else (crc << 1) & 0xFFFFFFFF
-    return crc
-
-
 def _rehead(data, rate):
     """The same stream with the id header's sample rate rewritten and the first page's CRC recomputed."""
     d = bytearray(data)
@@ -53,7 +45,7 @@ def _rehead(data, rate):
     plen = 27 + nseg + sum(d[27:27 + nseg])
     struct.pack_into("<I", d, 27 + nseg + 12, rate)
     d[22:26] = b"\0\0\0\0"
-    struct.pack_into("<I", d, 22, _ogg_crc(bytes(d[:plen])))
+    struct.pack_into("<I", d, 22, ogg_crc(bytes(d[:plen])))
     return bytes(d)
 
 

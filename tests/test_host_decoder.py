@@ -192,33 +192,7 @@ def test_mutated_files_never_crash_the_front_end(built, tmp_path):
     (tools/fuzz_host.cpp is the sanitizer-instrumented long-running version of this.)"""
     import json
     import zlib  # noqa: F401  (only to make sure the interpreter's C extensions load before the subprocess storm)
-
-    def crc_tab():
-        t = []
-        for i in range(256):
-            r = i << 24
-            for _ in range(8):
-                r = ((r << 1) ^ 0x04C11DB7) & 0xFFFFFFFF if r & 0x80000000 else (r << 1) & 0xFFFFFFFF
-            t.append(r)
-        return t
-
-    tab = crc_tab()
-
-    def fix_crcs(b):
-        o = 0
-        while o + 27 <= len(b) and b[o:o + 4] == b"OggS":
-            ns = b[o + 26]
-            if o + 27 + ns > len(b):
-                break
-            ln = 27 + ns + sum(b[o + 27:o + 27 + ns])
-            if o + ln > len(b):
-                break
-            b[o + 22:o + 26] = b"\0\0\0\0"
-            c = 0
-            for x in b[o:o + ln]:
-                c = ((c << 8) & 0xFFFFFFFF) ^ tab[((c >> 24) & 0xFF) ^ x]
-            b[o + 22:o + 26] = c.to_bytes(4, "little")
-            o += ln
+    from tests.workloads import fix_page_crcs as fix_crcs
 
     rng = np.random.default_rng(2024)
     base = [open(os.path.join(GOLDEN, n + ".ogg"), "rb").read() for n in ("test.stereo44khz", "test.mono44khz")]
@@ -251,26 +225,7 @@ def test_packet_that_fails_half_way_leaves_the_batch_consistent(probe, tmp_path,
     appended floor rows / residue / entry numbers. The batch it then hands over (the reader delivers the good packets in front of
     the error, as the reference does packet by packet, hpp:1045-1054) must account for every row: ys, floor numbers, residue or
     entries exactly as long as the packet list says. (CorpusDecoder's feeders size their staging buffers from the packet list.)"""
-    tab = []
-    for i in range(256):
-        r = i << 24
-        for _ in range(8):
-            r = ((r << 1) ^ 0x04C11DB7) & 0xFFFFFFFF if r & 0x80000000 else (r << 1) & 0xFFFFFFFF
-        tab.append(r)
-
-    def fix_crcs(b):
-        o = 0
-        while o + 27 <= len(b) and b[o:o + 4] == b"OggS":
-            ns = b[o + 26]
-            ln = 27 + ns + sum(b[o + 27:o + 27 + ns])
-            if o + ln > len(b):
-                break
-            b[o + 22:o + 26] = b"\0\0\0\0"
-            c = 0
-            for x in b[o:o + ln]:
-                c = ((c << 8) & 0xFFFFFFFF) ^ tab[((c >> 24) & 0xFF) ^ x]
-            b[o + 22:o + 26] = c.to_bytes(4, "little")
-            o += ln
+    from tests.workloads import fix_page_crcs as fix_crcs
 
     # deterministic first: the 20th audio packet fails after its floor rows and residue were appended (fault injection in
     # VorbisStream::parse_audio) — the reader must deliver exactly the 20 packets in front of it, consistently

@@ -213,6 +213,136 @@ def window_flag_classes(blocks, prev, nxt):
     return out
 
 
+def _ogg_crc_table():
+    t = []
+    for i in range(256):
+        r = i << 24
+        for _ in range(8):
+            r = ((r << 1) ^ 0x04C11DB7) & 0xFFFFFFFF if r & 0x80000000 else (r << 1) & 0xFFFFFFFF
+        t.append(r)
+    return t
+
+
+_OGG_CRC = _ogg_crc_table()
+
+
+def ogg_crc(data):
+    """Ogg page CRC (polynomial 0x04C11DB7, no reflection, initial value 0) of `data`, its CRC field zeroed by the caller."""
+    c = 0
+    for x in data:
+        c = ((c << 8) & 0xFFFFFFFF) ^ _OGG_CRC[((c >> 24) & 0xFF) ^ x]
+    return c
+
+
+def fix_page_crcs(b):
+    """Recompute, in place, the CRC of every complete page of the bytearray b, walking the pages as their segment tables lay them
+    out, so that damage to a file reaches the codec layer instead of its CRC check. A torn page at the end is left as it is."""
+    o = 0
+    while o + 27 <= len(b) and b[o:o + 4] == b"OggS":
+        ns = b[o + 26]
+        if o + 27 + ns > len(b):
+            break
+        ln = 27 + ns + sum(b[o + 27:o + 27 + ns])
+        if o + ln > len(b):
+            break
+        b[o + 22:o + 26] = b"\0\0\0\0"
+        b[o + 22:o + 26] = ogg_crc(b[o:o + ln]).to_bytes(4, "little")
+        o += ln
+    return b
+
+
+def ogg_pages(data):
+    """-> [(offset, length, number of packets that end on the page)] of the complete pages at the start of data, in the walk of
+    fix_page_crcs."""
+    out = []
+    o = 0
+    while o + 27 <= len(data) and data[o:o + 4] == b"OggS":
+        ns = data[o + 26]
+        if o + 27 + ns > len(data):
+            break
+        lace = data[o + 27:o + 27 + ns]
+        ln = 27 + ns + sum(lace)
+        if o + ln > len(data):
+            break
+        out.append((o, ln, sum(1 for v in lace if v < 255)))
+        o += ln
+    return out
+
+
+def sha256_bits(a):
+    """sha256 hex digest of the bits of a float32 array (C order; callers keep the shape alongside)."""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a, np.float32).view(np.uint32).tobytes()).hexdigest()
+
+
+def fixture_setup(name):
+    """SetupSpec of a committed .ogg fixture: test.stereo44khz / test.mono44khz (load_golden) or a stream of
+    oracle/make_synth_ogg.py (synth_NN, winflags_*), whose .npz carries its synthesis-side setup."""
+    if name.startswith("test."):
+        return load_golden(name)[0]
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    floors = [(int(z["floor%d_mult" % k]), [int(x) for x in z["floor%d_xs" % k]]) for k in range(int(z["num_floors"]))]
+    nmap = int(z["mode_mapping"].max()) + 1
+    mappings = [([(int(a), int(b)) for a, b in z["coupling_m%d" % k]], [int(f) for f in z["chfloor_m%d" % k]]) for k in range(nmap)]
+    modes = [(int(bf), int(mp)) for bf, mp in zip(z["mode_blockflag"], z["mode_mapping"])]
+    return SetupSpec(int(z["channels"]), int(z["blocksize0"]), int(z["blocksize1"]), floors, mappings, modes)
+
+
+def entropy_hook_digests(spec, d, upto):
+    """sha256 of the "floor1 ys" and "after_residue" hooks of packets [0, upto) of an entropy dump (read_entropy_dump, float
+    residue), in the form oracle/make_damaged_goldens.py records the reference's: per used channel (packet, channel, posts) + ys;
+    per channel (packet, channel, n/2) + residue bits."""
+    import hashlib
+    ys, res = hashlib.sha256(), hashlib.sha256()
+    C = spec.channels
+    off = 0
+    for p in range(min(upto, d["P"])):
+        mode = int(d["packets"]["mode"][p])
+        bf, mapping = spec.modes[mode]
+        n2 = (spec.blocksize1 if bf else spec.blocksize0) // 2
+        used = int(d["packets"]["floor_used"][p])
+        for c in range(C):
+            if (used >> c) & 1:
+                posts = len(spec.floors[spec.mappings[mapping][1][c]][1])
+                ys.update(np.asarray([p, c, posts], np.int32).tobytes() + d["ys"][p, c, :posts].astype(np.uint32).tobytes())
+        for c in range(C):
+            res.update(np.asarray([p, c, n2], np.int32).tobytes() + np.ascontiguousarray(d["residue"][off + c * n2:off + (c + 1) * n2]).tobytes())
+        off += C * n2
+    return ys.hexdigest(), res.hexdigest()
+
+
+def load_damaged():
+    """tests/golden/damaged.npz (oracle/make_damaged_goldens.py) -> list of dict per record."""
+    z = np.load(os.path.join(GOLDEN, "damaged.npz"))
+    names = [str(n) for n in z["base_names"]]
+    recs = []
+    for i in range(len(z["base"])):
+        e0, e1 = int(z["edit_off"][i]), int(z["edit_off"][i + 1])
+        recs.append(dict(index=i, seed=int(z["seed"][i]), draw=int(z["draw"][i]), base=names[int(z["base"][i])], kind=str(z["kind"][i]),
+                         edit_pos=z["edit_pos"][e0:e1], edit_val=z["edit_val"][e0:e1], trunc=int(z["trunc"][i]),
+                         sha=str(z["sha"][i]), ref_rc=int(z["ref_rc"][i]), ref_err=str(z["ref_err"][i]), ref_packets=int(z["ref_packets"][i]),
+                         ref_frames=int(z["ref_frames"][i]), ref_pcm=str(z["ref_pcm"][i]), ref_ys=str(z["ref_ys"][i]),
+                         ref_res=str(z["ref_res"][i]), expect_ok=bool(z["expect_ok"][i]), expect_flags=int(z["expect_flags"][i]),
+                         expect_bad=int(z["expect_bad"][i]), hook_sha=str(z["hook_sha"][i]), hook_off=int(z["hook_off"][i]),
+                         hook_num=int(z["hook_num"][i])))
+    return recs, z
+
+
+def damaged_bytes(rec):
+    """Rebuild one damaged file of tests/golden/damaged.npz from its base fixture and recipe: byte edits, truncation, then every
+    complete page's CRC recomputed. Asserts the sha256 the generator recorded."""
+    import hashlib
+    b = bytearray(open(os.path.join(GOLDEN, rec["base"] + ".ogg"), "rb").read())
+    for p, v in zip(rec["edit_pos"], rec["edit_val"]):
+        b[int(p)] = int(v)
+    if rec["trunc"] >= 0:
+        del b[rec["trunc"]:]
+    fix_page_crcs(b)
+    data = bytes(b)
+    assert hashlib.sha256(data).hexdigest() == rec["sha"], (rec["base"], rec["seed"], rec["draw"])
+    return data
+
+
 def read_entropy_dump(path):
     """Parse the file written by tests/host_entropy_dump.cpp -> dict (packets, ys, residue, and in VQ mode vq_packets,
     cls, entries, residue_floats, vq_spec)."""

@@ -3,7 +3,9 @@
 and through the host entropy half (tests/host_entropy_dump.cpp). Counts: both accept with identical hooks / both reject / one
 accepts. Round 1: 600 files — 364 both accept, always identical; 208 both reject; 0 where the reference accepts and the host
 rejects; 19 that only the reference rejects, all in its synthesis half (hpp:536 / 1041 / Utils.hpp:145), which the full CLI
-rejects on the GPU with the matching reason; 9 skipped (memory error inside the reference)."""
+rejects on the GPU with the matching reason; 9 skipped (memory error inside the reference).
+Superseded for the suite by oracle/make_damaged_goldens.py, which stores seeded damaged files with the reference's verdict, hooks and
+PCM digests in tests/golden/damaged.npz for tests/test_damaged_files.py (CPU) and tests/test_gpu_damaged_files.py (every GPU path)."""
 import sys, os, subprocess, tempfile, struct
 sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/oracle')
 import numpy as np
