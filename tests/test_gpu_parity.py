@@ -9,6 +9,7 @@ import pytest
 from oracle import oracle_binding as ob
 from parseoggvorbis_amd import binding
 from parseoggvorbis_amd.binding import SetupSpec
+from tests import synth_model
 from tests.workloads import disagreeing_window_flags, fixture_like_spec, load_golden, synth_batch, window_flag_classes
 
 pytestmark = pytest.mark.gpu
@@ -21,12 +22,15 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def check(got, want, scale_tol=True):
+def check(got, want, scale_tol=True, model=None):
+    """model=(spec, batch): also the per-packet gate against the float64 model of the batch (synth_model.py)."""
     assert got["rc"] == want["rc"] == 0, (got["rc"], got["flags"], want["rc"])
     assert np.array_equal(got["emit_len"], want["emit_len"])
     scale = max(1.0, float(np.abs(want["pcm"]).max())) if scale_tol else 1.0
     err = float(np.abs(got["pcm"] - want["pcm"]).max())
     assert err < TOL * scale, (err, scale)
+    if model is not None:
+        synth_model.check_model(got, *model)
     return err
 
 
@@ -43,6 +47,7 @@ def test_reference_fixture_dumps(name, flags):
     assert int(r["emit_len"].sum()) == total
     assert np.abs(r["pcm"][0][:, :total] - b["pcm"]).max() < TOL
     assert not r["pcm"][0][:, total:].any()
+    synth_model.check_model(r, spec, dict(b, plane_stride=total + 8))
 
 
 @pytest.mark.parametrize("name", ["test.stereo44khz", "test.mono44khz"])
@@ -113,7 +118,7 @@ def test_synthetic_vs_oracle(C, bs0, bs1, pattern, streams, npk, flags):
     want = ob.OracleSynth(spec, streams).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
     got = binding.Synth(spec, max_streams=streams).submit_host(b["packets"], b["segments"], b["ys"], b["residue"],
                                                              b["plane_stride"], flags=flags)
-    check(got, want)
+    check(got, want, model=(spec, b))
 
 
 def test_many_channels_chained_couplings():
@@ -126,7 +131,7 @@ def test_many_channels_chained_couplings():
     b = synth_batch(spec, 2, 16, "mixed", seed=11, unused_frac=0.3)
     want = ob.OracleSynth(spec, 2).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps=True)
     got = binding.Synth(spec, max_streams=2).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps=True)
-    check(got, want)
+    check(got, want, model=(spec, b))
     assert np.array_equal(bits(got["taps"]["after_envelope"]), bits(want["taps"]["after_envelope"]))
     assert np.array_equal(got["taps"]["floor_final"], want["taps"]["floor_final"])
 
@@ -177,7 +182,7 @@ def test_random_block_patterns_runs_and_cuts(seed, run_len, monkeypatch):
     b = synth_batch(spec, 3, npk, flags, seed=seed, unused_frac=0.15, granule_last=True)
     want = ob.OracleSynth(spec, 3).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
     one = binding.Synth(spec, max_streams=3).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
-    check(one, want)
+    check(one, want, model=(spec, b))
     # stream 0 again, cut at random places (every kind of size pair occurs at some cut)
     n_of = np.where(b["packets"]["mode"][:npk] == 1, spec.blocksize1, spec.blocksize0)
     off = np.concatenate([[0], np.cumsum(2 * n_of // 2)])
@@ -281,6 +286,12 @@ def test_imdct_only(n):
     for r in (0, count - 1):
         ob.oracle().orc_imdct_closed_form(n, ob.p(x[r]), ob.p(cf))
         assert np.abs(got[r] - cf).max() < TOL * max(1.0, peak)
+    # every row against the float64 IMDCT, per row: within G * 2^-24 * rms(row) (synth_model.py)
+    y = synth_model.imdct(n, x)
+    rms = np.sqrt(np.mean(y * y, axis=1))
+    ratio = np.abs(got - y).max(axis=1) / (synth_model.ULP * rms)
+    print("imdct_only n=%d: worst row %.1f x 2^-24 rms (gate %g)" % (n, ratio.max(), synth_model.G))
+    assert ratio.max() <= synth_model.G, (n, int(np.argmax(ratio)), ratio.max())
 
 
 @pytest.mark.parametrize("flags", [binding.VSYN_SUBMIT_INPUTS_READY, binding.VSYN_SUBMIT_INPUTS_READY | binding.VSYN_SUBMIT_PRE_KERNELS])
@@ -390,7 +401,7 @@ def test_feature_taps_from_the_fused_kernel(pattern, C, bs0, bs1):
     gpu = binding.Synth(spec, max_streams=4)
     assert gpu.fused_paths & 2, gpu.fused_paths  # every run of this setup is taken by a fused kernel
     got = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps="features")
-    check(got, want)
+    check(got, want, model=(spec, b))
     assert np.array_equal(got["taps"]["floor_curve"], want["taps"]["floor_curve"])
     assert np.array_equal(got["taps"]["floor_final"], want["taps"]["floor_final"])
     gpu.reset()
@@ -441,7 +452,7 @@ def test_fused_path_limits(C, posts, ml, ms, coupled, pattern, paths):
     assert gpu.fused_paths == paths, (gpu.fused_paths, paths)
     want = ob.OracleSynth(spec, 3).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps=True)
     got = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps="features")
-    check(got, want)
+    check(got, want, model=(spec, b))
     assert np.array_equal(got["taps"]["floor_final"], want["taps"]["floor_final"])
     assert np.array_equal(got["taps"]["floor_curve"], want["taps"]["floor_curve"])
     gpu.reset()
@@ -449,7 +460,7 @@ def test_fused_path_limits(C, posts, ml, ms, coupled, pattern, paths):
     assert np.array_equal(bits(plain["pcm"]), bits(got["pcm"]))
     gpu.reset()
     staged = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=binding.VSYN_SUBMIT_STAGED)
-    check(staged, want)
+    check(staged, want, model=(spec, b))
 
 
 @pytest.mark.parametrize("bs0,bs1,posts_short,posts_long", [(256, 2048, 65, 65), (128, 1024, 65, 40), (512, 4096, 30, 65), (1024, 8192, 65, 65)])
@@ -468,7 +479,7 @@ def test_65_post_floors_stay_fused(bs0, bs1, posts_short, posts_long):
     assert gpu.fused_paths & 2, gpu.fused_paths
     want = ob.OracleSynth(spec, 3).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps=True)
     got = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps="features")
-    check(got, want)
+    check(got, want, model=(spec, b))
     assert np.array_equal(got["taps"]["floor_final"], want["taps"]["floor_final"])
     assert np.array_equal(got["taps"]["floor_curve"], want["taps"]["floor_curve"])
     gpu.reset()
@@ -476,7 +487,7 @@ def test_65_post_floors_stay_fused(bs0, bs1, posts_short, posts_long):
     assert np.array_equal(bits(plain["pcm"]), bits(got["pcm"]))
     gpu.reset()
     staged = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=binding.VSYN_SUBMIT_STAGED)
-    check(staged, want)
+    check(staged, want, model=(spec, b))
 
 
 @pytest.mark.parametrize("pattern", ["long", "mixed"])
@@ -610,10 +621,10 @@ def test_multichannel_and_chained_couplings_stay_fused(C, bs0, bs1, coup):
     assert gpu.fused_paths & 2, gpu.fused_paths
     want = ob.OracleSynth(spec, 3).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
     got = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
-    check(got, want)
+    check(got, want, model=(spec, b))
     gpu.reset()
     staged = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=binding.VSYN_SUBMIT_STAGED)
-    check(staged, want)
+    check(staged, want, model=(spec, b))
 
 
 @pytest.mark.parametrize("C,bs,pattern", [(2, 4096, "mixed"), (2, 8192, "mixed"), (1, 8192, "short"), (3, 4096, "long")])
@@ -626,14 +637,14 @@ def test_equal_block_sizes_above_2048_stay_fused(C, bs, pattern):
     assert gpu.fused_paths & 2, gpu.fused_paths
     want = ob.OracleSynth(spec, 2).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps=True)
     got = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], want_taps="features")
-    check(got, want)
+    check(got, want, model=(spec, b))
     assert np.array_equal(got["taps"]["floor_final"], want["taps"]["floor_final"])
     assert np.array_equal(got["taps"]["floor_curve"], want["taps"]["floor_curve"])
     gpu.reset()
     plain = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
     assert np.array_equal(bits(plain["pcm"]), bits(got["pcm"]))
     gpu.reset()
-    check(gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=binding.VSYN_SUBMIT_STAGED), want)
+    check(gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=binding.VSYN_SUBMIT_STAGED), want, model=(spec, b))
 
 
 @pytest.mark.parametrize("C,bs0,bs1,paths", [(14, 128, 1024, 2), (16, 256, 2048, 2), (17, 128, 1024, 0), (14, 512, 4096, 0)])
@@ -648,7 +659,7 @@ def test_many_coupled_channels(C, bs0, bs1, paths):
     gpu = binding.Synth(spec, max_streams=2)
     assert gpu.fused_paths == paths, gpu.fused_paths
     want = ob.OracleSynth(spec, 2).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"])
-    check(gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"]), want)
+    check(gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"]), want, model=(spec, b))
 
 
 MIXED_MAPPINGS = [
@@ -674,7 +685,7 @@ def test_mappings_with_different_coupling_lists_stay_fused(C, bs0, bs1, coup0, c
     for flags in (0, binding.VSYN_SUBMIT_PRE_KERNELS, binding.VSYN_SUBMIT_STAGED):
         gpu.reset()
         got = gpu.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=flags)
-        check(got, want)
+        check(got, want, model=(spec, b))
 
 
 @pytest.mark.parametrize("streams,npk", [(1, 10007), (2, 9000)])

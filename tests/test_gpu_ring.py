@@ -8,7 +8,8 @@ import pytest
 from oracle import oracle_binding as ob
 from parseoggvorbis_amd import binding
 from parseoggvorbis_amd.binding import SetupSpec
-from tests.workloads import fixture_like_spec, synth_batch
+from tests import synth_model
+from tests.workloads import concat_batches as _concat, fixture_like_spec, synth_batch
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -27,25 +28,6 @@ def _spec(kind):
     return SetupSpec(2, f.blocksize0, f.blocksize1, f.floors, [(coup, [0, 0]), (coup, [1, 1])], [(0, 0), (1, 1)])
 
 
-def _concat(parts):
-    """One batch from several synth_batch results (segments renumbered onto consecutive streams)."""
-    pk = np.concatenate([p["packets"] for p in parts])
-    ys = np.concatenate([p["ys"] for p in parts])
-    res = np.concatenate([p["residue"] for p in parts])
-    segs = np.concatenate([p["segments"] for p in parts]).copy()
-    first = res_off = 0
-    i = 0
-    for p in parts:
-        for s in range(len(p["segments"])):
-            segs[i]["stream"] = i
-            segs[i]["first_packet"] = first + p["segments"][s]["first_packet"]
-            segs[i]["residue_off"] = res_off + p["segments"][s]["residue_off"]
-            i += 1
-        first += len(p["packets"])
-        res_off += len(p["residue"])
-    return dict(packets=pk, segments=segs, ys=ys, residue=res, plane_stride=max(p["plane_stride"] for p in parts))
-
-
 def _submit(spec, b, run_len, monkeypatch, want_taps=False):
     if run_len:
         monkeypatch.setenv("VSYN_RUN_LEN", str(run_len))
@@ -57,11 +39,14 @@ def _submit(spec, b, run_len, monkeypatch, want_taps=False):
     return got
 
 
-def _check(got, want):
+def _check(got, want, spec=None, b=None):
+    """spec, b: also the per-packet gate against the float64 model of batch b (synth_model.py)."""
     assert got["rc"] == want["rc"] == 0, (got["rc"], got["flags"], want["rc"])
     assert np.array_equal(got["emit_len"], want["emit_len"])
     scale = max(1.0, float(np.abs(want["pcm"]).max()))
     assert float(np.abs(got["pcm"] - want["pcm"]).max()) < TOL * scale
+    if b is not None:
+        synth_model.check_model(got, spec, b)
 
 
 # segment lengths: shorter than one round of slots (1-7), one round, chunks that 8R does not divide, several chunks
@@ -77,7 +62,7 @@ def test_ring_chunks_every_length_same_bits_for_every_run_length(kind, monkeypat
     ref = None
     for rl in RUN_LENS:
         got = _submit(spec, b, rl, monkeypatch)
-        _check(got, want)
+        _check(got, want, spec, b)
         if ref is None:
             ref = got
         else:
@@ -97,7 +82,7 @@ def test_group_with_one_mixed_run_falls_back_with_the_same_bits(at, monkeypatch)
     ref = None
     for rl in RUN_LENS:
         got = _submit(spec, b, rl, monkeypatch)
-        _check(got, want)
+        _check(got, want, spec, b)
         if ref is None:
             ref = got
         else:
@@ -138,7 +123,7 @@ def test_feature_tap_kernel_in_ring_mode(run_len, monkeypatch):
     want = ob.OracleSynth(spec, len(b["segments"])).submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"],
                                                                 want_taps=True)
     got = _submit(spec, b, run_len, monkeypatch, want_taps="features")
-    _check(got, want)
+    _check(got, want, spec, b)
     assert np.array_equal(got["taps"]["floor_curve"], want["taps"]["floor_curve"])
     assert np.array_equal(got["taps"]["floor_final"], want["taps"]["floor_final"])
     plain = _submit(spec, b, run_len, monkeypatch)

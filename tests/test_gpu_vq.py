@@ -11,6 +11,7 @@ import pytest
 from oracle import oracle_binding as ob
 from parseoggvorbis_amd.binding import (PACKET_DTYPE, SEGMENT_DTYPE, VQ_PACKET_DTYPE, VSYN_ERR_STREAM, VSYN_SEG_RESET,
                                         VSYN_ST_BAD_VQ, Synth, VsynError, VqSpec)
+from tests import synth_model
 from tests.workloads import (GOLDEN, build_probe, disagreeing_window_flags, load_golden, read_entropy_dump, synth_vq_packet,
                              window_flag_classes)
 
@@ -54,6 +55,9 @@ def test_vq_stage_reproduces_reference_residue_and_pcm(probe, name, tmp_path):
     total = b["pcm"].shape[1]
     assert int(out["emit_len"].sum()) == total
     assert np.abs(out["pcm"][0][:, :total] - b["pcm"]).max() < TOL
+    # and per packet against the float64 model fed the same residue (tests/synth_model.py)
+    synth_model.check_model(out, spec, dict(packets=d["packets"], segments=seg, ys=d["ys"], residue=out["residue"],
+                                            plane_stride=P * spec.blocksize1 // 2))
     # same batch cut into two submits (overlap carried on the device) gives the same PCM
     syn.reset()
     cut = 41

@@ -34,8 +34,8 @@ def load_golden(name):
                       emit_len=z["emit_len"]), z
 
 
-def fixture_like_spec(channels=2, bs0=256, bs1=2048):
-    """The fixtures' stream setup, generalised to other blocksizes by scaling the X lists."""
+def fixture_like_spec(channels=2, bs0=256, bs1=2048, coupled=True):
+    """The fixtures' stream setup, generalised to other blocksizes by scaling the X lists (coupled=False: no coupling step)."""
     def scale(xs, n2, base):
         out = sorted({min(n2, max(0, (x * n2) // base)) for x in xs})
         if len(out) < 2:
@@ -48,7 +48,7 @@ def fixture_like_spec(channels=2, bs0=256, bs1=2048):
     inner = long_sorted[2:]
     rng.shuffle(inner)  # header order is not sorted in real streams
     long_ = [0, bs1 // 2] + [int(v) for v in inner]
-    coup = [(0, 1)] if channels >= 2 else []
+    coup = [(0, 1)] if channels >= 2 and coupled else []
     return SetupSpec(channels, bs0, bs1, [(4, short), (2, long_)],
                      [(coup, [0] * channels), (coup, [1] * channels)], [(0, 0), (1, 1)])
 
@@ -90,15 +90,26 @@ def _encode_ys(xs, mult, target, rng, zero_frac):
     return ys
 
 
+QUIET_YS = (0, 8)      # floor range of quiet packets: peak |pcm| about 5e-5 with the default residue
+LOUD_YS = (150, 250)   # floor range of loud packets: peak |pcm| about 150
+
+
 def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, ylo=28, yhi=88, unused_frac=0.0,
-                granule_last=False, roll=True, prev_long=None, next_long=None):
+                granule_last=False, roll=True, prev_long=None, next_long=None, residue="laplace", residue_scale=1.0,
+                floor_ranges=None, alternate=0):
     """Synthetic batch in the shape of BASELINE configs 3/4:
     residue = round(Laplace(b=1.5)) with 60 % zeros; floor amplitudes a random walk in [ylo,yhi] (step +-6)
     over the setup's X list, wrapped into coded ys.  pattern: 'long', 'short', 'mixed' (L L L S*8 repeating, rotated per
     stream) or an explicit sequence of block flags (1 = long), the same for every stream.
     prev_long / next_long: window flag bytes of every packet of the batch ([streams * packets_per_stream], short packets included),
     instead of the flags that agree with the block sequence (disagreeing_window_flags); the batch is otherwise the same.
+    Precision probes (the defaults leave the batch unchanged, byte for byte):
+    residue: 'laplace' (the above) or 'gauss' (standard normal: dense, non-integer, no zeros, more cancellation in the IMDCT),
+    times residue_scale; floor_ranges: one (ylo, yhi) per stream instead of (ylo, yhi); alternate=k: packets alternate between
+    k quiet packets (floor range QUIET_YS) and k loud ones (LOUD_YS) within each segment, loud first, so that overlap carries run
+    from loud blocks into quiet ones.
     Returns dict(packets, segments, ys, residue, plane_stride)."""
+    assert residue in ("laplace", "gauss"), residue
     rng = np.random.default_rng(seed)
     C = spec.channels
     if not isinstance(pattern, str):
@@ -134,6 +145,9 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
                 pk[p]["prev_long"] = flags[q - 1] if q > 0 else 1
                 pk[p]["next_long"] = flags[q + 1] if q + 1 < packets_per_stream else 1
             pk[p]["granule"] = -1
+            lo, hi = (ylo, yhi) if floor_ranges is None else floor_ranges[s]
+            if alternate:
+                lo, hi = QUIET_YS if (q // alternate) % 2 else LOUD_YS
             used = 0
             for c in range(C):
                 if rng.random() < unused_frac:
@@ -141,13 +155,18 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
                 used |= 1 << c
                 mult, xs = spec.floors[spec.mappings[spec.modes[mode][1]][1][c]]
                 order = np.argsort(xs)
-                walk = np.clip(np.cumsum(rng.integers(-6, 7, len(xs))) + rng.integers(ylo, yhi), ylo, yhi)
+                walk = np.clip(np.cumsum(rng.integers(-6, 7, len(xs))) + rng.integers(lo, hi), lo, hi)
                 target = np.zeros(len(xs), np.int64)
                 target[order] = walk * 2 // mult  # same dB range whatever the multiplier
                 ys[p, c, :len(xs)] = _encode_ys(xs, mult, target, rng, 0.25)
             pk[p]["floor_used"] = used
-            r = np.round(rng.laplace(0.0, 1.5, (C, n // 2)))
-            r[rng.random((C, n // 2)) < 0.6] = 0
+            if residue == "laplace":
+                r = np.round(rng.laplace(0.0, 1.5, (C, n // 2)))
+                r[rng.random((C, n // 2)) < 0.6] = 0
+            else:
+                r = rng.standard_normal((C, n // 2))
+            if residue_scale != 1.0:
+                r = r * residue_scale
             res_parts.append(r.astype(np.float32).ravel())
             off += C * (n // 2)
     if prev_long is not None:
@@ -163,6 +182,66 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
             pk[s * packets_per_stream + packets_per_stream - 1]["granule"] = total - min(37, last_l // 2)  # clipped last packet
     plane = packets_per_stream * (spec.blocksize1 // 2) + 64
     return dict(packets=pk, segments=seg, ys=ys, residue=np.concatenate(res_parts), plane_stride=plane)
+
+
+def concat_batches(parts):
+    """One batch from several synth_batch results (segments renumbered onto consecutive streams)."""
+    pk = np.concatenate([p["packets"] for p in parts])
+    ys = np.concatenate([p["ys"] for p in parts])
+    res = np.concatenate([p["residue"] for p in parts])
+    segs = np.concatenate([p["segments"] for p in parts]).copy()
+    first = res_off = 0
+    i = 0
+    for p in parts:
+        for s in range(len(p["segments"])):
+            segs[i]["stream"] = i
+            segs[i]["first_packet"] = first + p["segments"][s]["first_packet"]
+            segs[i]["residue_off"] = res_off + p["segments"][s]["residue_off"]
+            i += 1
+        first += len(p["packets"])
+        res_off += len(p["residue"])
+    return dict(packets=pk, segments=segs, ys=ys, residue=res, plane_stride=max(p["plane_stride"] for p in parts))
+
+
+def packet_blocks(spec, packets, segments):
+    """-> (n [P], residue offset [P]) of a batch: every packet's block size and the float index of its first residue value."""
+    n = np.array([spec.blocksize1 if spec.modes[int(m)][0] else spec.blocksize0 for m in packets["mode"]], np.int64)
+    off = np.zeros(len(packets), np.int64)
+    for sg in segments:
+        a, k = int(sg["first_packet"]), int(sg["num_packets"])
+        sizes = n[a:a + k] // 2 * spec.channels
+        off[a:a + k] = int(sg["residue_off"]) + np.concatenate([[0], np.cumsum(sizes)[:-1]]) if k else []
+    return n, off
+
+
+def silence(spec, b, packets, channels=None):
+    """Make channels (default: all) of the given packets silent in place, as a real decoder delivers an unused channel: floor_used
+    cleared and the residue zeroed."""
+    n, off = packet_blocks(spec, b["packets"], b["segments"])
+    chans = range(spec.channels) if channels is None else channels
+    for p in packets:
+        for c in chans:
+            b["packets"][p]["floor_used"] &= ~np.uint32(1 << c)
+            b["residue"][off[p] + c * n[p] // 2: off[p] + (c + 1) * n[p] // 2] = 0
+    return b
+
+
+def loudness_profiles(spec, npk=24, seed=1):
+    """The loudness profiles of the precision tests, one batch each for spec's block sizes: quiet (peak about 5e-5), loud (about
+    1e5), a quiet and a loud stream in one submit, alternating loud and quiet packets, Gaussian residue, silent channels."""
+    pat = "long" if spec.blocksize0 == spec.blocksize1 else "mixed"
+    quiet = synth_batch(spec, 2, npk, pat, seed=seed, ylo=0, yhi=8, granule_last=True)  # no unused channel: its residue is loud
+    loud = synth_batch(spec, 2, npk, pat, seed=seed + 1, ylo=150, yhi=250, residue_scale=1000.0, granule_last=True)
+    both = synth_batch(spec, 2, npk, pat, seed=seed + 2, floor_ranges=[(0, 8), (150, 250)], granule_last=True)
+    alt = concat_batches([synth_batch(spec, 1, npk, pat, seed=seed + 3, alternate=1),
+                          synth_batch(spec, 1, npk, "long", seed=seed + 4, alternate=3, granule_last=True)])
+    gauss = synth_batch(spec, 2, npk, pat, seed=seed + 5, residue="gauss", granule_last=True)
+    sil = synth_batch(spec, 3, npk, pat, seed=seed + 6, alternate=2)
+    silence(spec, sil, [q for q in range(npk) if q % 5 in (1, 2)])              # every channel, after and before loud packets
+    if not any(m[0] for m in spec.mappings):  # one whole channel of stream 1 (a coupled partner would bring it back to life)
+        silence(spec, sil, range(npk, 2 * npk), channels=[spec.channels - 1])
+    silence(spec, sil, range(2 * npk, 3 * npk))                                 # a whole stream
+    return dict(quiet=quiet, loud=loud, both=both, alternate=alt, gauss=gauss, silent=sil)
 
 
 FLAG_BYTES = np.array([0, 1, 2, 0x80, 255], np.uint8)  # the reference treats any non-zero byte as true (getWindow(bool, bool))
