@@ -545,6 +545,78 @@ int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* sp
                                     uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status,
                                     const char** err);
 
+/* ---- spectral post-processing: delta columns and mean / variance normalisation of spectral rows, computed where the rows are ----
+ *
+ * Input: one segment's spectral matrix X[f][d], F rows, D = dim columns (any of the four kinds). Output: a float32 matrix
+ * (F, D_out), D_out = D * (1 + order). These are the options with_delta / norm_mean / norm_std_dev of RETURNN's
+ * ExtractAudioFeatures; the deltas are librosa.feature.delta's. Neither is among the test dependencies: the device is compared
+ * against a float64 model of the arithmetic below (tests/spectral_post_model.py), and the model's deltas against
+ * scipy.signal.savgol_filter.
+ *
+ *  1. Deltas. width odd in [3, 65], h = (width - 1) / 2, k = -h .. h, S2 = sum k^2, S4 = sum k^4.
+ *       c1[k] = k / S2;   c2[k] = 2 (width k^2 - S2) / (width S4 - S2^2).
+ *     For h <= f <= F-1-h: D_o[f][d] = sum_k c_o[k] X[f+k][d], k ascending. For the h rows at either end:
+ *     D_o[f] = D_o[clamp(f, h, F-1-h)]. This is scipy.signal.savgol_filter(X, width, deriv=o, polyorder=o, axis=0,
+ *     mode="interp"), i.e. librosa.feature.delta(order=o): with polyorder equal to the derivative order the edge polynomial's
+ *     o-th derivative is a constant, so the edge rows repeat the first / last interior row. Order 2 is the second derivative of
+ *     X, not a delta of the delta. Y = [X | D_1 | D_2] up to `order`. A segment with 0 < F < width and order > 0 is an error (as
+ *     in librosa); F = 0 gives (0, D_out).
+ *  2. Normalisation, on Y, column by column, after the deltas (RETURNN's order).
+ *     VSYN_POST_STATS_SEGMENT: mu[j] = (1/F) sum_f Y[f][j], sigma[j] = sqrt((1/F) sum_f (Y[f][j] - mu[j])^2) (numpy's std).
+ *     VSYN_POST_STATS_GIVEN: mu = mean, sigma = std, the caller's float32 vectors of D_out entries (HOST arrays, read during the
+ *     call; their length is the caller's word).
+ *     VSYN_POST_NORM_MEAN: Z = Y - mu. VSYN_POST_NORM_MEAN_VAR: Z = (Y - mu) / max(sigma, std_floor): a constant column becomes zeros.
+ *  3. Precision. The coefficients are rounded from double to float32; a delta is one float32 FMA chain in the order written. mu
+ *     and sigma are accumulated in float64 in a fixed order: the sums of blocks of 16 rows of the segment, rows ascending; then
+ *     16 chains, chain i adding the sums of blocks i, i + 16, ... in ascending order; then the chains in ascending order (no
+ *     floating-point atomics). The order is a function of the segment's rows alone, so the result depends on neither the launch
+ *     geometry nor the segment's place in the batch, and the same rows always give the same bits. Z = float32((double(Y) - mu) * r),
+ *     r = 1 / max(sigma, std_floor) in float64 (1 for NORM_MEAN): one rounding to float32.
+ *  4. Checks (VSYN_ERR_INVALID before anything runs): order <= 2; width odd in [3, 65] (whatever the order); norm and stats
+ *     among the enums; std_floor finite and > 0; with given statistics and norm != none, mean non-NULL and finite, and for
+ *     MEAN_VAR std non-NULL and finite.
+ *
+ * order = 0 with VSYN_POST_NORM_NONE launches nothing: the rows are those of the spectral entry points, bit for bit. The post
+ * entry points read rows (and through vsyn_pcm_spectral_post_host, PCM) only: they touch neither stream state, the overlap buffers
+ * nor the PCM kept by VSYN_SUBMIT_KEEP_PCM. One handle's post entry points share its post workspace. */
+enum {
+  VSYN_POST_NORM_NONE = 0,
+  VSYN_POST_NORM_MEAN = 1,     /* "mean" */
+  VSYN_POST_NORM_MEAN_VAR = 2  /* "mean_var" */
+};
+enum {
+  VSYN_POST_STATS_SEGMENT = 0, /* per segment (RETURNN's "per_seq") */
+  VSYN_POST_STATS_GIVEN = 1    /* the caller's mean / std */
+};
+#define VSYN_POST_MAX_WIDTH 65u
+
+typedef struct vsyn_spectral_post {
+  uint32_t order;     /* 0, 1 or 2 delta orders */
+  uint32_t width;     /* odd, in [3, 65]; librosa's default is 9 */
+  uint32_t norm;      /* VSYN_POST_NORM_* */
+  uint32_t stats;     /* VSYN_POST_STATS_* */
+  double std_floor;   /* > 0 */
+  const float* mean;  /* VSYN_POST_STATS_GIVEN: [D_out], host */
+  const float* std;   /* VSYN_POST_STATS_GIVEN with MEAN_VAR: [D_out], host */
+} vsyn_spectral_post;
+
+/* D_out = dim * (1 + order) for spec's dim; 0 for an invalid spec or post. */
+uint32_t vsyn_spectral_post_dim(const vsyn_spectral_spec* spec, const vsyn_spectral_post* post);
+
+/* The post stage alone on rows the caller has on the device (what vsyn_spectral_device wrote): d_in holds the segments' rows back
+ * to back, dim columns (1 <= dim <= 256); seg_rows[S] is a HOST array of each segment's row count, so a segment with
+ * 0 < F < width (order > 0) is refused by name before anything is launched. Writes d_out, the same rows with dim * (1 + order)
+ * columns; d_out may be d_in only when order = 0. Asynchronous on hip_stream. */
+int vsyn_spectral_post_device(vsyn_handle* h, const vsyn_spectral_post* post, uint32_t dim, uint32_t num_segments,
+                              const uint64_t* seg_rows, const float* d_in, float* d_out, void* hip_stream, const char** err);
+
+/* vsyn_pcm_spectral_host (out_rate = 0: each segment at its own rate) or vsyn_pcm_resample_spectral_host (out_rate != 0) followed
+ * by the post stage, without rows or PCM leaving the device in between: rows receives D_out columns per row. A segment with
+ * 0 < F < width (order > 0) makes the call VSYN_ERR_INVALID, with seg_rows filled. Synchronous. */
+int vsyn_pcm_spectral_post_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t num_segments,
+                                const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                                vsyn_status* status, const char** err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ def load():
     for name, args in (("ogg_vorbis_features_corpus", [C.POINTER(binding.FeatureSpec), vp, vp, vp]),
                        ("ogg_vorbis_spectral_corpus", [C.POINTER(binding.SpectralSpec), vp, vp, vp]),
                        ("ogg_vorbis_spectral_corpus_sr", [C.POINTER(binding.SpectralSpec), u32, vp, vp, vp]),
+                       ("ogg_vorbis_spectral_corpus_post", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPost), vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus", [u32, C.c_int, vp, vp, vp, vp, vp])):
         fn = getattr(lib, name)
         fn.argtypes = head + args + tail

@@ -66,6 +66,11 @@ class SpectralSpec(C.Structure):  # vsyn_spectral_spec
                 ("fmin", C.c_double), ("fmax", C.c_double), ("log_floor", C.c_double), ("amin", C.c_double), ("top_db", C.c_double)]
 
 
+class SpectralPost(C.Structure):  # vsyn_spectral_post
+    _fields_ = [("order", C.c_uint32), ("width", C.c_uint32), ("norm", C.c_uint32), ("stats", C.c_uint32), ("std_floor", C.c_double),
+                ("mean", C.c_void_p), ("std", C.c_void_p)]
+
+
 class Status(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("first_bad_packet", C.c_uint32)]
 
@@ -192,6 +197,7 @@ _SYMBOLS = [
     "vsyn_feature_rows_device", "vsyn_features_device", "vsyn_features_host",
     "vsyn_spectral_num_frames", "vsyn_spectral_device", "vsyn_pcm_spectral_host",
     "vsyn_resample_num_frames", "vsyn_resample_device", "vsyn_pcm_resample_host", "vsyn_pcm_resample_spectral_host",
+    "vsyn_spectral_post_dim", "vsyn_spectral_post_device", "vsyn_pcm_spectral_post_host",
 ]
 
 
@@ -260,6 +266,11 @@ def load():
     lib.vsyn_resample_device.argtypes = [vp, u32, vp, u32, vp, u64, u32, vp, vp, u64, vp, vp, cpp]
     lib.vsyn_pcm_resample_host.argtypes = [vp, u32, vp, u32, C.c_int, vp, u64, vp, cpp]
     lib.vsyn_pcm_resample_spectral_host.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, u32, vp, u64, vp, C.POINTER(Status), cpp]
+    lib.vsyn_spectral_post_dim.argtypes = [C.POINTER(SpectralSpec), C.POINTER(SpectralPost)]
+    lib.vsyn_spectral_post_dim.restype = u32
+    lib.vsyn_spectral_post_device.argtypes = [vp, C.POINTER(SpectralPost), u32, u32, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_spectral_post_host.argtypes = [vp, C.POINTER(SpectralSpec), C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp,
+                                                C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -381,6 +392,33 @@ class Synth:
                                            d_seg_row_off, stream, C.byref(err))
         if rc != VSYN_OK:
             raise VsynError(rc, (err.value or b"").decode())
+
+    def spectral_post_device(self, post, dim, seg_rows, d_in, d_out, stream=None):
+        """vsyn_spectral_post_device on device pointers (ints); seg_rows is a host sequence of each segment's row count."""
+        nrows = np.ascontiguousarray(seg_rows, dtype=np.uint64)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_spectral_post_device(self.h, C.byref(post), dim, len(nrows), _ptr(nrows), d_in, d_out, stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+
+    def pcm_spectral_post_host(self, spec, post, in_rates, out_rate=0):
+        """vsyn_pcm_spectral_post_host over the last submit's segments: returns dict(rc, rows [total][D_out], seg_rows [S], flags)."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S = len(rates)
+        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + post.order)
+        seg_rows = np.zeros(max(S, 1), np.uint64)
+        st, err = Status(), C.c_char_p()
+        rc = self.lib.vsyn_pcm_spectral_post_host(self.h, C.byref(spec), C.byref(post), S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows),
+                                                  C.byref(st), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum())
+        rows = np.zeros((max(total, 1), dout), np.float32)
+        rc = self.lib.vsyn_pcm_spectral_post_host(self.h, C.byref(spec), C.byref(post), S, _ptr(rates), out_rate, _ptr(rows), total,
+                                                  _ptr(seg_rows), C.byref(st), C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], flags=st.flags)
 
     def resample_device(self, in_rates, out_rate, d_pcm, plane_stride, channels, d_frames, d_out, out_plane_stride, d_out_frames,
                         stream=None):

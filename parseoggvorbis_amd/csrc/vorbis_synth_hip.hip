@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <numeric>
 #include <string>
@@ -28,6 +29,7 @@
 #include "vsyn_pcm.h"
 #include "vsyn_features.h"
 #include "vsyn_spectral.h"
+#include "vsyn_spectral_post.h"
 #include "vsyn_resample.h"
 
 #ifndef M_PI
@@ -230,6 +232,11 @@ struct vsyn_handle {
   DevBuf<uint32_t> sp_segF, sp_segmax;
   DevBuf<uint64_t> sp_segoff;
   DevBuf<float> sp_db, sp_rows;
+  // spectral post-processing (vsyn_spectral_post.h): a second row buffer (the output rows are wider) and the statistics
+  TableUpload pp_tab;
+  bool pp_lds_set = false;             // vsyn_post_delta_kernel's dynamic-LDS limit is raised on this handle's device
+  DevBuf<float> pp_rows;
+  DevBuf<double> pp_part, pp_stat;     // per-block partial sums; mu | rinv per (segment, column)
   // resampling (vsyn_resample.h): buffers of its own; the PCM is only read
   TableUpload rs_tab;
   bool rs_lds_set = false;             // vsyn_rs_kernel<true>'s dynamic-LDS limit is raised on this handle's device
@@ -1767,6 +1774,165 @@ int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
+// spectral post-processing (vsyn_spectral_post.h; semantics in the header)
+// ------------------------------------------------------------------------------------------------
+static bool post_on(const vsyn_spectral_post* p) { return p->order != 0 || p->norm != VSYN_POST_NORM_NONE; }
+static bool post_given(const vsyn_spectral_post* p) { return p->norm != VSYN_POST_NORM_NONE && p->stats == VSYN_POST_STATS_GIVEN; }
+
+// The checks of the post spec that need no row counts; the given vectors are read for finiteness only when dout != 0.
+static int post_check(const vsyn_spectral_post* p, const char** err, uint32_t dout = 0) {
+  if (!p) return fail(err, VSYN_ERR_INVALID, "spectral post spec is NULL");
+  if (p->order > 2) return fail(err, VSYN_ERR_INVALID, "delta order %u outside [0, 2]", p->order);
+  if (p->width < 3 || p->width > VSYN_POST_MAX_WIDTH || !(p->width & 1u))
+    return fail(err, VSYN_ERR_INVALID, "delta width %u must be odd and in [3, %u]", p->width, VSYN_POST_MAX_WIDTH);
+  if (p->norm > VSYN_POST_NORM_MEAN_VAR) return fail(err, VSYN_ERR_INVALID, "unknown normalisation %u", p->norm);
+  if (p->stats > VSYN_POST_STATS_GIVEN) return fail(err, VSYN_ERR_INVALID, "unknown statistics source %u", p->stats);
+  if (!(p->std_floor > 0.0) || !std::isfinite(p->std_floor)) return fail(err, VSYN_ERR_INVALID, "std_floor must be finite and > 0");
+  if (post_given(p)) {
+    const bool var = p->norm == VSYN_POST_NORM_MEAN_VAR;
+    if (!p->mean || (var && !p->std)) return fail(err, VSYN_ERR_INVALID, "given statistics: %s is NULL", p->mean ? "std" : "mean");
+    for (uint32_t j = 0; j < dout; ++j)
+      if (!std::isfinite(p->mean[j]) || (var && !std::isfinite(p->std[j])))
+        return fail(err, VSYN_ERR_INVALID, "given statistics: column %u is not finite", j);
+  }
+  return VSYN_OK;
+}
+
+// A segment shorter than the delta window is refused by name.
+static int post_check_rows(const vsyn_spectral_post* p, uint32_t S, const uint64_t* seg_rows, const char** err) {
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) {
+    if (seg_rows[g] > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment %u: too many rows", g);
+    if (p->order && seg_rows[g] && seg_rows[g] < p->width)
+      return fail(err, VSYN_ERR_INVALID, "segment %u: delta width %u needs %u frames, segment has %llu", g, p->width, p->width,
+                  (unsigned long long)seg_rows[g]);
+  }
+  return VSYN_OK;
+}
+
+// The stage's kernels on stream s: d_in [rows][D] -> d_out [rows][D * (1 + order)]. Caller holds h->mu, has run post_check (with
+// dout) and post_check_rows, and post_on(p) holds.
+static int post_launch(vsyn_handle* h, const vsyn_spectral_post* p, uint32_t D, uint32_t S, const uint64_t* seg_rows, const float* d_in,
+                       float* d_out, hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  const uint32_t W = p->width, Dout = D * (1u + p->order), hh = p->order ? (W - 1u) / 2u : 0u;
+  const bool norm = p->norm != VSYN_POST_NORM_NONE, given = post_given(p), var = p->norm == VSYN_POST_NORM_MEAN_VAR;
+  // table: PostSeg[S] | given mu[Dout], rinv[Dout] (double) | c1[W], c2[W] (float)
+  const size_t off_stat = sizeof(PostSeg) * S, off_coef = off_stat + (given ? 16ull * Dout : 0ull);
+  std::vector<uint8_t> tab(off_coef + 8ull * W);
+  PostSeg* seg = (PostSeg*)tab.data();
+  uint64_t rows = 0, blocks = 0, f_max = 0;
+  for (uint32_t g = 0; g < S; ++g) {
+    seg[g] = PostSeg{rows, blocks, (uint32_t)seg_rows[g], 0u};
+    rows += seg_rows[g];
+    blocks += (seg_rows[g] + POST_BLK - 1u) / POST_BLK;
+    f_max = std::max(f_max, seg_rows[g]);
+  }
+  if (f_max == 0) return VSYN_OK;
+  if (given) {
+    double* st = (double*)(tab.data() + off_stat);
+    for (uint32_t j = 0; j < Dout; ++j) {
+      st[j] = (double)p->mean[j];
+      st[Dout + j] = var ? 1.0 / std::max((double)p->std[j], p->std_floor) : 1.0;
+    }
+  }
+  float* coef = (float*)(tab.data() + off_coef);
+  double S2 = 0, S4 = 0;
+  for (int k = -(int)hh; k <= (int)hh; ++k) {
+    S2 += (double)k * k;
+    S4 += (double)k * k * k * k;
+  }
+  for (uint32_t i = 0; i < W && hh; ++i) {
+    const double k = (double)i - (double)hh;
+    coef[i] = (float)(k / S2);
+    coef[W + i] = (float)(2.0 * (W * k * k - S2) / (W * S4 - S2 * S2));
+  }
+  // the tile: every row group of the workgroup gets a block, at least four blocks, and the LDS image fits
+  const uint32_t G = POST_THREADS / std::min<uint32_t>(Dout, POST_THREADS);
+  uint32_t nb = G * ((4u + G - 1u) / G);
+  const auto lds_of = [&](uint32_t blocks) { return ((size_t)(blocks * POST_BLK + 2u * hh) * D + POST_COEF_FLOATS) * 4u; };
+  while (nb > 1u && lds_of(nb) > SPEC_LDS_BUDGET) --nb;
+  const uint32_t tile = nb * POST_BLK;
+  const size_t lds = lds_of(nb);
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->pp_lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_post_delta_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    h->pp_lds_set = true;
+  }
+  const bool seg_stats = norm && !given;
+  if (seg_stats) {
+    HIPCHK(h->pp_part.ensure(blocks * Dout));
+    HIPCHK(h->pp_stat.ensure(2ull * S * Dout));
+  }
+  if (int rc = h->pp_tab.upload(tab, s, err)) return rc;
+  PostCtx A;
+  A.seg = (const PostSeg*)h->pp_tab.dev.p;
+  A.coef = (const float*)(h->pp_tab.dev.p + off_coef);
+  A.in = d_in;
+  A.out = d_out;
+  A.part = seg_stats ? h->pp_part.p : nullptr;
+  A.mu = given ? (double*)(h->pp_tab.dev.p + off_stat) : h->pp_stat.p;
+  A.rinv = given ? A.mu + Dout : h->pp_stat.p + (size_t)S * Dout;
+  A.stat_stride = given ? 0u : Dout;
+  A.D = D;
+  A.Dout = Dout;
+  A.order = p->order;
+  A.width = W;
+  A.tile = tile;
+  A.std_floor = p->std_floor;
+  const uint64_t gx = (f_max + tile - 1u) / tile;
+  const dim3 grid((uint32_t)gx, S), rgrid((Dout + POST_RED_COLS - 1u) / POST_RED_COLS, S);
+  hipLaunchKernelGGL(vsyn_post_delta_kernel, grid, dim3(POST_THREADS), lds, s, A);
+  HIPCHK(hipGetLastError());
+  if (seg_stats) {
+    hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 0u);
+    HIPCHK(hipGetLastError());
+    if (var) {
+      hipLaunchKernelGGL(vsyn_post_moment_kernel, grid, dim3(POST_THREADS), 0, s, A);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 1u);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if (norm) {
+    hipLaunchKernelGGL(vsyn_post_norm_kernel, grid, dim3(POST_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  return VSYN_OK;
+}
+
+extern "C" {
+
+uint32_t vsyn_spectral_post_dim(const vsyn_spectral_spec* spec, const vsyn_spectral_post* post) {
+  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK || post_check(post, nullptr) != VSYN_OK) return 0;
+  return spec_dim(spec) * (1u + post->order);
+}
+
+int vsyn_spectral_post_device(vsyn_handle* h, const vsyn_spectral_post* post, uint32_t dim, uint32_t S, const uint64_t* seg_rows,
+                              const float* d_in, float* d_out, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (dim < 1 || dim > 256) return fail(err, VSYN_ERR_INVALID, "dim %u outside [1, 256]", dim);
+  int rc = post_check(post, err, dim * (1u + (post && post->order <= 2 ? post->order : 0u)));
+  if (rc) return rc;
+  rc = post_check_rows(post, S, seg_rows, err);
+  if (rc) return rc;
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  if (total == 0) return VSYN_OK;
+  if (!d_in || !d_out) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
+  if (d_in == d_out && post->order) return fail(err, VSYN_ERR_INVALID, "d_out may be d_in only when order = 0");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!post_on(post)) {  // nothing to compute: the rows as they are
+    HIPCHK(hipSetDevice(h->device));
+    if (d_in != d_out) HIPCHK(hipMemcpyAsync(d_out, d_in, sizeof(float) * total * dim, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+    return VSYN_OK;
+  }
+  return post_launch(h, post, dim, S, seg_rows, d_in, d_out, (hipStream_t)hip_stream, err);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
 // resampling (vsyn_resample.h; semantics in the header)
 // ------------------------------------------------------------------------------------------------
 // vsyn_rs_kernel<true> holds one pair's table and one tile's input span in LDS. 80 KiB keeps two of its workgroups on a CU
@@ -1949,8 +2115,9 @@ static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates,
 
 // vsyn_pcm_spectral_host, and with out_rate != 0 vsyn_pcm_resample_spectral_host: the rows of the last host submit's PCM, each
 // segment resampled from rates[g] to out_rate first when out_rate != 0.
-static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* rates, uint32_t out_rate,
-                             float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
+static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S,
+                             const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                             vsyn_status* status, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   status_reset(status);
   int rc;
@@ -1964,6 +2131,11 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uin
   const uint32_t* spec_rates = out_rate ? sp_rates.data() : rates;
   rc = spec_check(spec, S, spec_rates, err);
   if (rc) return rc;
+  if (post) {
+    rc = post_check(post, err, post->order <= 2 ? spec_dim(spec) * (1u + post->order) : 0u);
+    if (rc) return rc;
+    if (!post_on(post)) post = nullptr;  // off: the rows of the spectral pass, bit for bit
+  }
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
   // the lock covers the whole call: the spectral and resample workspaces are the handle's, and the PCM must stay that of the last submit
@@ -1979,6 +2151,10 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uin
     total += f;
     f_max = std::max(f_max, f);
     t_max = std::max(t_max, T[g]);
+  }
+  if (post) {
+    rc = post_check_rows(post, S, seg_rows, err);
+    if (rc) return rc;
   }
   if (!rows || total == 0) return VSYN_OK;
   if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
@@ -2003,7 +2179,15 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uin
   HIPCHK(h->sp_rows.ensure(total * D + 1));
   rc = spec_launch(h, spec, S, spec_rates, pcm, plane, C, d_frames, si, f_max, total, h->sp_rows.p, nullptr, hs, err);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+  if (post) {  // the rows go on to the post stage in their place, and its wider rows come back
+    const uint64_t Dout = D * (1u + post->order);
+    HIPCHK(h->pp_rows.ensure(total * Dout + 1));
+    rc = post_launch(h, post, (uint32_t)D, S, seg_rows, h->sp_rows.p, h->pp_rows.p, hs, err);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(rows, h->pp_rows.p, sizeof(float) * total * Dout, hipMemcpyDeviceToHost, hs));
+  } else {
+    HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+  }
   return sync_status_into(h, status, err);
 }
 
@@ -2083,7 +2267,14 @@ int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates,
 
 int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
                            uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
-  return pcm_spectral_host(h, spec, S, sample_rates, 0, rows, rows_capacity, seg_rows, status, err);
+  return pcm_spectral_host(h, spec, nullptr, S, sample_rates, 0, rows, rows_capacity, seg_rows, status, err);
+}
+
+int vsyn_pcm_spectral_post_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S,
+                                const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                                vsyn_status* status, const char** err) {
+  if (!post) return fail(err, VSYN_ERR_INVALID, "spectral post spec is NULL");
+  return pcm_spectral_host(h, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err);
 }
 
 int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
@@ -2092,7 +2283,7 @@ int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* sp
     status_reset(status);
     return rs_check(S, in_rates, out_rate, err);
   }
-  return pcm_spectral_host(h, spec, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err);
+  return pcm_spectral_host(h, spec, nullptr, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err);
 }
 
 }  // extern "C"

@@ -1,0 +1,178 @@
+// vsyn_spectral_post.h — delta / delta-delta columns and per-column mean / variance normalisation of spectral rows already on the
+// device. Semantics: include/vorbis_synth_hip.h, "spectral post-processing".
+//
+// The host knows every segment's row count, so it uploads one PostSeg per segment (row offset, offset of its 16-row blocks, rows)
+// with the float32 delta coefficients and, for given statistics, the columns' mu and 1 / max(sigma, std_floor) in double
+// (vorbis_synth_hip.hip post_launch). Up to five launches on one stream:
+//   1. vsyn_post_delta_kernel   one workgroup per (segment, tile of `tile` rows). The tile's rows of X plus the halo of the
+//                               clamped window go through (dynamic) LDS once; a thread owns one output column j of one 16-row block at a
+//                               time and walks the block's rows in ascending order: lanes run along j, so a wave's loads and
+//                               stores are contiguous, and for D_out < 256 the workgroup's 256 / D_out row groups take different
+//                               blocks instead of idling. Writes Y = [X | D_1 | D_2] at pitch D_out and, when statistics are
+//                               wanted, the block's float64 column sum.
+//   2. vsyn_post_reduce_kernel  per (segment, column): the blocks' partials added in a fixed two-level order (16 interleaved chains,
+//                               each in ascending block order, then the chains in order) -> mu, or (second call, on the partials
+//                               of 3) sigma -> 1 / max(sigma, std_floor). No atomics: the order is a function of the rows alone.
+//   3. vsyn_post_moment_kernel  mean + variance per segment: the blocks' float64 sums of (Y - mu)^2, a second pass over Y (exact on
+//                               columns with a large mean and a small spread, which sum(Y^2) - F mu^2 is not).
+//   4. vsyn_post_norm_kernel    Y = float((double(Y) - mu) * rinv) in place.
+// A block is always 16 rows of its segment, whatever the tile, the grid or the segment's place in the batch: the same rows give
+// the same bits. Nothing here reads or writes stream state, the overlap carry or PCM.
+#pragma once
+#include "vsyn_device.h"
+
+#define POST_THREADS 256
+#define POST_BLK 16u  // rows per block of partial sums
+#define POST_RED_CHAINS 16u  // vsyn_post_reduce_kernel: interleaved chains of block partials per column ...
+#define POST_RED_COLS 16u    // ... and columns per workgroup (POST_RED_CHAINS * POST_RED_COLS = POST_THREADS)
+#define POST_COEF_FLOATS 132u  // LDS floats in front of the tile's rows: two coefficient vectors of up to 65
+
+struct PostSeg {
+  uint64_t off;  // first row of the segment in the row buffers
+  uint64_t blk;  // first block of the segment in the partials
+  uint32_t F, pad;
+};
+
+struct PostCtx {  // launch arguments
+  const PostSeg* seg;
+  const float* coef;  // c1[width] | c2[width]
+  const float* in;    // [rows][D]
+  float* out;         // [rows][Dout]
+  double* part;       // [blocks][Dout], or NULL
+  double* mu;         // [S or 1][Dout]
+  double* rinv;       // [S or 1][Dout]
+  uint32_t stat_stride;  // Dout per segment, 0 for given statistics
+  uint32_t D, Dout, order, width, tile;
+  double std_floor;
+};
+
+// Thread layout over a tile: wd lanes along the columns, G = POST_THREADS / wd row groups; group ty takes blocks ty, ty + G, ...
+struct PostLane {
+  uint32_t wd, G, ty, tx;
+};
+__device__ __forceinline__ PostLane post_lane(uint32_t Dout) {
+  PostLane L;
+  L.wd = min(Dout, (uint32_t)POST_THREADS);
+  L.G = POST_THREADS / L.wd;
+  L.ty = threadIdx.x / L.wd;
+  L.tx = threadIdx.x - L.ty * L.wd;
+  return L;
+}
+__device__ __forceinline__ uint32_t post_clamp(uint32_t f, uint32_t lo, uint32_t hi) { return min(max(f, lo), hi); }
+
+__global__ void __launch_bounds__(POST_THREADS) vsyn_post_delta_kernel(const PostCtx A) {
+  extern __shared__ float s_c[];  // c1, c2 [POST_COEF_FLOATS] | the tile's rows of X
+  float* s_x = s_c + POST_COEF_FLOATS;
+  const PostSeg sg = A.seg[blockIdx.y];
+  const uint32_t F = sg.F, f0 = blockIdx.x * A.tile, tid = threadIdx.x;
+  if (f0 >= F) return;
+  const uint32_t D = A.D, Dout = A.Dout, W = A.width;
+  const uint32_t nrows = min(A.tile, F - f0);
+  const uint32_t h = A.order ? (W - 1u) / 2u : 0u;  // the host has refused 0 < F < width when order > 0
+  // rows of X the tile reads: its own, and the windows of its rows clamped to [h, F - 1 - h]
+  const uint32_t lo = post_clamp(f0, h, F - 1u - h) - h, hi = post_clamp(f0 + nrows - 1u, h, F - 1u - h) + h + 1u;
+  const float* x = A.in + (sg.off + lo) * D;
+  for (uint32_t i = tid; i < (hi - lo) * D; i += POST_THREADS) s_x[i] = x[i];
+  if (A.order)
+    for (uint32_t i = tid; i < A.order * W; i += POST_THREADS) s_c[i] = A.coef[i];
+  __syncthreads();
+  const PostLane L = post_lane(Dout);
+  if (L.ty >= L.G) return;
+  const uint32_t nblk = (nrows + POST_BLK - 1u) / POST_BLK;
+  for (uint32_t b = L.ty; b < nblk; b += L.G) {
+    const uint32_t fb = f0 + b * POST_BLK, fe = min(fb + POST_BLK, f0 + nrows);
+    for (uint32_t j = L.tx; j < Dout; j += L.wd) {
+      const uint32_t o = j / D, d = j - o * D;
+      const float* c = s_c + (o ? o - 1u : 0u) * W;
+      float* y = A.out + (sg.off + fb) * Dout + j;
+      double sum = 0.0;
+      for (uint32_t f = fb; f < fe; ++f, y += Dout) {
+        float v;
+        if (o == 0) {
+          v = s_x[(f - lo) * D + d];
+        } else {
+          const float* p = s_x + (post_clamp(f, h, F - 1u - h) - h - lo) * D + d;
+          v = 0.f;
+          for (uint32_t k = 0; k < W; ++k) v = fmaf(c[k], p[k * D], v);
+        }
+        *y = v;
+        sum += (double)v;
+      }
+      if (A.part) A.part[(sg.blk + fb / POST_BLK) * Dout + j] = sum;
+    }
+  }
+}
+
+// part[block][j] = sum over the block's rows of (Y - mu)^2, rows ascending
+__global__ void __launch_bounds__(POST_THREADS) vsyn_post_moment_kernel(const PostCtx A) {
+  const PostSeg sg = A.seg[blockIdx.y];
+  const uint32_t F = sg.F, f0 = blockIdx.x * A.tile, Dout = A.Dout;
+  if (f0 >= F) return;
+  const uint32_t nrows = min(A.tile, F - f0);
+  const PostLane L = post_lane(Dout);
+  if (L.ty >= L.G) return;
+  const double* mu = A.mu + (size_t)blockIdx.y * A.stat_stride;
+  const uint32_t nblk = (nrows + POST_BLK - 1u) / POST_BLK;
+  for (uint32_t b = L.ty; b < nblk; b += L.G) {
+    const uint32_t fb = f0 + b * POST_BLK, fe = min(fb + POST_BLK, f0 + nrows);
+    for (uint32_t j = L.tx; j < Dout; j += L.wd) {
+      const double m = mu[j];
+      const float* y = A.out + (sg.off + fb) * Dout + j;
+      double sum = 0.0;
+      for (uint32_t f = fb; f < fe; ++f, y += Dout) {
+        const double t = (double)*y - m;
+        sum += t * t;
+      }
+      A.part[(sg.blk + fb / POST_BLK) * Dout + j] = sum;
+    }
+  }
+}
+
+// One workgroup per (segment, POST_RED_COLS columns), a fixed two-level order: chain i of POST_RED_CHAINS adds the partials of
+// blocks i, i + POST_RED_CHAINS, ... in ascending order, then the chains are added in ascending order (a chain without a block adds
+// 0). second = 0: mu = sum / F, rinv = 1. second = 1: rinv = 1 / max(sqrt(sum / F), std_floor).
+__global__ void __launch_bounds__(POST_THREADS) vsyn_post_reduce_kernel(const PostCtx A, const uint32_t second) {
+  __shared__ double s_sum[POST_RED_CHAINS][POST_RED_COLS];
+  const PostSeg sg = A.seg[blockIdx.y];
+  const uint32_t cy = threadIdx.x / POST_RED_COLS, cx = threadIdx.x % POST_RED_COLS;
+  const uint32_t j = blockIdx.x * POST_RED_COLS + cx, Dout = A.Dout;
+  if (sg.F == 0) return;
+  const uint32_t nblk = (sg.F + POST_BLK - 1u) / POST_BLK;
+  double sum = 0.0;
+  if (j < Dout) {
+    const double* p = A.part + sg.blk * Dout + j;
+    for (uint32_t b = cy; b < nblk; b += POST_RED_CHAINS) sum += p[(size_t)b * Dout];
+  }
+  s_sum[cy][cx] = sum;
+  __syncthreads();
+  if (cy != 0 || j >= Dout) return;
+  sum = s_sum[0][cx];
+  for (uint32_t i = 1; i < POST_RED_CHAINS; ++i) sum += s_sum[i][cx];
+  const size_t q = (size_t)blockIdx.y * A.stat_stride + j;
+  const double v = sum / (double)sg.F;
+  if (!second) {
+    A.mu[q] = v;
+    A.rinv[q] = 1.0;
+  } else {
+    A.rinv[q] = 1.0 / fmax(sqrt(v), A.std_floor);
+  }
+}
+
+__global__ void __launch_bounds__(POST_THREADS) vsyn_post_norm_kernel(const PostCtx A) {
+  const PostSeg sg = A.seg[blockIdx.y];
+  const uint32_t F = sg.F, f0 = blockIdx.x * A.tile, Dout = A.Dout;
+  if (f0 >= F) return;
+  const uint32_t nrows = min(A.tile, F - f0);
+  const PostLane L = post_lane(Dout);
+  if (L.ty >= L.G) return;
+  const size_t s0 = (size_t)blockIdx.y * A.stat_stride;
+  const uint32_t nblk = (nrows + POST_BLK - 1u) / POST_BLK;
+  for (uint32_t b = L.ty; b < nblk; b += L.G) {
+    const uint32_t fb = f0 + b * POST_BLK, fe = min(fb + POST_BLK, f0 + nrows);
+    for (uint32_t j = L.tx; j < Dout; j += L.wd) {
+      const double m = A.mu[s0 + j], r = A.rinv[s0 + j];
+      float* y = A.out + (sg.off + fb) * Dout + j;
+      for (uint32_t f = fb; f < fe; ++f, y += Dout) *y = (float)(((double)*y - m) * r);
+    }
+  }
+}

@@ -77,7 +77,11 @@ struct NullCallbacks : ParseCallbacks {};
 
 bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
 bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
-uint32_t spectral_dim(const CorpusOptions& o) { return o.spectral.kind == VSYN_SPEC_MFCC ? o.spectral.n_mfcc : o.spectral.n_mels; }
+bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
+// columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
+uint32_t spectral_dim(const CorpusOptions& o) {
+  return (o.spectral.kind == VSYN_SPEC_MFCC ? o.spectral.n_mfcc : o.spectral.n_mels) * (1u + o.post.order);
+}
 bool feature_needs_residue(const CorpusOptions& o) {
   return o.features.kind == VSYN_FEAT_RESIDUE_YS || o.features.kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
 }
@@ -483,14 +487,24 @@ struct Feeder {
                  sr);
         o.err[s] = buf;
       }
+      uint64_t F = o.err[s].empty() ? vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(o.frames[s], o.plane)) : 0;
+      if (opts.post.order && F && F < opts.post.width) {  // fewer frames than the delta window: this file's error, not the submit's
+        char buf[96];
+        snprintf(buf, sizeof(buf), "spectral: delta width %u needs %u frames, file has %llu", opts.post.width, opts.post.width,
+                 (unsigned long long)F);
+        o.err[s] = buf;
+        F = 0;
+      }
       rates[s] = o.err[s].empty() ? r.header.audio_sample_rate : 0;
-      if (rates[s]) spec_rows += vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(o.frames[s], o.plane));
+      spec_rows += F;
     }
     CHECK_ERR(g.rows.ensure(spec_rows * spectral_dim(opts) + 1));
     CHECK_ERR(g.seg_rows.ensure(S));
     vsyn_status st;
     const char* err = nullptr;
-    const int rc = resample ? vsyn_pcm_resample_spectral_host(g.handle, &opts.spectral, S, rates.data(), opts.resample_rate, g.rows.p,
+    const int rc = post_run(opts) ? vsyn_pcm_spectral_post_host(g.handle, &opts.spectral, &opts.post, S, rates.data(), opts.resample_rate,
+                                                                g.rows.p, spec_rows, g.seg_rows.p, &st, &err)
+                   : resample     ? vsyn_pcm_resample_spectral_host(g.handle, &opts.spectral, S, rates.data(), opts.resample_rate, g.rows.p,
                                                               spec_rows, g.seg_rows.p, &st, &err)
                             : vsyn_pcm_spectral_host(g.handle, &opts.spectral, S, rates.data(), g.rows.p, spec_rows, g.seg_rows.p, &st, &err);
     if (rc == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
@@ -922,12 +936,16 @@ namespace {
 
 // ogg_vorbis_spectral_corpus (target_rate 0) and ogg_vorbis_spectral_corpus_sr; fn: the entry point, for its refusal text.
 int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
-                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate, float** rows_out,
-                    uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
+                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                    const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
+                    const char** error_out_per_file, double* stats_out, const char** error_out) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
+  if (post && !vsyn_spectral_post_dim(spec, post))
+    return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
   CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
   opts.spectral = *spec;
   opts.resample_rate = target_rate;
+  if (post) opts.post = *post;
   return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
@@ -937,8 +955,8 @@ extern "C" int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const siz
                                           uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, float** rows_out,
                                           uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                           double* stats_out, const char** error_out) {
-  return spectral_corpus("ogg_vorbis_spectral_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, 0, rows_out,
-                         rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+  return spectral_corpus("ogg_vorbis_spectral_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, 0, nullptr,
+                         rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_sr(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -946,7 +964,16 @@ extern "C" int ogg_vorbis_spectral_corpus_sr(const uint8_t* const* datas, const 
                                              float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                              double* stats_out, const char** error_out) {
   return spectral_corpus("ogg_vorbis_spectral_corpus_sr", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
-                         rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+                         nullptr, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_post(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                               uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                               const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
+                                               const char** error_out_per_file, double* stats_out, const char** error_out) {
+  if (!post) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_spectral_corpus_post: no post spec", error_out);
+  return spectral_corpus("ogg_vorbis_spectral_corpus_post", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
+                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
 extern "C" int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

@@ -82,6 +82,10 @@ struct CorpusOptions {
   // resampled ones, and abs_sum is taken over the delivered f32 PCM (0 for pcm_s16). The mel table and the fmin / fmax check of a
   // spectral run use resample_rate. A file whose reduced ratio exceeds the limit fails alone. Not for feature runs.
   uint32_t resample_rate = 0;
+  // spectral run with the post stage (post.order != 0 or post.norm != VSYN_POST_NORM_NONE): delta columns and mean / variance
+  // normalisation of each file's rows on the device (include/vorbis_synth_hip.h, "spectral post-processing"); the rows delivered have
+  // dim * (1 + order) columns. A file with fewer frames than the delta width fails alone. The default is off: today's rows.
+  vsyn_spectral_post post = {0, 9, VSYN_POST_NORM_NONE, VSYN_POST_STATS_SEGMENT, 1e-5, nullptr, nullptr};
 };
 
 struct CorpusStats {
@@ -134,6 +138,12 @@ int ogg_vorbis_spectral_corpus_sr(const uint8_t* const* datas, const size_t* len
                                   uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                                   float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                   double* stats_out, const char** error_out);
+// spectral run followed by the post stage (CorpusOptions::post = *post; target_rate as for ogg_vorbis_spectral_corpus_sr): rows of
+// vsyn_spectral_post_dim(spec, post) columns. A file with 0 < frames < post->width (order > 0) fails alone. Same output contract.
+int ogg_vorbis_spectral_corpus_post(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                    const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
+                                    const char** error_out_per_file, double* stats_out, const char** error_out);
 // PCM run: pcm_out (may be NULL) receives per file NULL (failed, or no frames) or a buffer allocated by the library, released
 // with ogg_vorbis_features_free: format VSYN_PCM_F32 float32 planar [channels][frames], VSYN_PCM_S16 int16 interleaved
 // [frames][channels]. target_rate: 0 = each file's own rate, else CorpusOptions::resample_rate. frames_out, channels_out and

@@ -6,7 +6,9 @@ float64 model in tests/spectral_model.py is the contract the device is tested ag
 
 Every argument is checked before the library is loaded. 25 ms / 10 ms at 44.1 kHz: n_fft=1102, hop_length=441. sr=None computes
 each file's matrix at its own rate; an integer sr resamples every file's PCM to it on the device first (parseoggvorbis_amd/pcm.py,
-scipy.signal.resample_poly's arithmetic), so that one mel table serves the whole batch."""
+scipy.signal.resample_poly's arithmetic), so that one mel table serves the whole batch. delta / normalize finish the rows on the
+device as well (include/vorbis_synth_hip.h, "spectral post-processing"): librosa.feature.delta's columns, then per-column mean or
+mean / variance normalisation; tests/spectral_post_model.py is their float64 model."""
 import ctypes as C
 import math
 
@@ -79,26 +81,84 @@ def spec_dim(spec):
     return spec.n_mfcc if spec.kind == KINDS["mfcc"] else spec.n_mels
 
 
+NORM_NONE, NORM_MEAN, NORM_MEAN_VAR = 0, 1, 2
+STATS_SEGMENT, STATS_GIVEN = 0, 1
+MAX_DELTA_WIDTH = 65
+
+
+def post_spec(dim, delta=0, delta_width=9, normalize=None, std_floor=1e-5):
+    """Checks the post-processing arguments (include/vorbis_synth_hip.h, "spectral post-processing", step 4) for rows of dim columns.
+    Returns (C post spec, D_out, arrays the spec points into: keep them alive during the call), or (None, dim, ()) when the stage is
+    off (delta=0, normalize=None). normalize: None, "mean", "mean_var" (per file), or (mean, std) of D_out entries each, std None
+    for the mean alone."""
+    from .binding import SpectralPost
+    delta = _int("delta", delta)
+    delta_width = _int("delta_width", delta_width)
+    if not 0 <= delta <= 2:
+        raise SpectralError("delta must be 0, 1 or 2, got %d" % delta)
+    if not 3 <= delta_width <= MAX_DELTA_WIDTH or delta_width % 2 == 0:
+        raise SpectralError("delta_width must be odd and in [3, %d], got %d" % (MAX_DELTA_WIDTH, delta_width))
+    if isinstance(std_floor, bool) or not isinstance(std_floor, (int, float, np.integer, np.floating)):
+        raise SpectralError("std_floor must be a number, got %r" % (std_floor,))
+    std_floor = float(std_floor)
+    if not (math.isfinite(std_floor) and std_floor > 0.0):
+        raise SpectralError("std_floor must be finite and > 0, got %r" % std_floor)
+    dout = dim * (1 + delta)
+    norm, stats, keep = NORM_NONE, STATS_SEGMENT, ()
+    if isinstance(normalize, str) and normalize in ("mean", "mean_var"):
+        norm = NORM_MEAN if normalize == "mean" else NORM_MEAN_VAR
+    elif isinstance(normalize, tuple) and len(normalize) == 2 and normalize[0] is not None:
+        stats = STATS_GIVEN
+        norm = NORM_MEAN if normalize[1] is None else NORM_MEAN_VAR
+        vecs = []
+        for name, v in (("mean", normalize[0]), ("std", normalize[1])):
+            if v is None:
+                continue
+            try:
+                a = np.ascontiguousarray(v, dtype=np.float32)
+            except (TypeError, ValueError):
+                raise SpectralError("normalize: %s must be an array of %d numbers" % (name, dout))
+            if a.shape != (dout,):
+                raise SpectralError("normalize: %s must have %d entries (dim %d x (1 + delta %d)), got shape %r"
+                                    % (name, dout, dim, delta, a.shape))
+            if not np.isfinite(a).all():
+                raise SpectralError("normalize: %s must be finite" % name)
+            vecs.append(a)
+        keep = tuple(vecs)
+    elif normalize is not None:
+        raise SpectralError("normalize must be None, 'mean', 'mean_var' or a tuple (mean, std), got %r" % (normalize,))
+    if delta == 0 and norm == NORM_NONE:
+        return None, dim, ()
+    post = SpectralPost(delta, delta_width, norm, stats, std_floor, keep[0].ctypes.data if keep else None,
+                        keep[1].ctypes.data if len(keep) > 1 else None)
+    return post, dout, keep
+
+
 _load = _corpus.load
 
 
 def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n_mels=128, fmin=0.0, fmax=None,
                        htk=False, norm="slaney", center=True, power=2.0, log_floor=1e-3, amin=1e-10, top_db=80.0, n_mfcc=20,
-                       threads=0, feeders=0, device=0, errors="raise", files_per_submit=64, stats=None, sr=None):
+                       threads=0, feeders=0, device=0, errors="raise", files_per_submit=64, stats=None, sr=None, delta=0, delta_width=9,
+                       normalize=None, std_floor=1e-5):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels otherwise. errors="raise": the first failed file raises SpectralError naming it; errors="return": its entry
     is the SpectralError. stats (optional list) receives the run's 8 corpus statistics. sr=None: each file at its own rate;
-    an integer: every file resampled to sr on the device, and the mel table and the fmin / fmax check use sr."""
+    an integer: every file resampled to sr on the device, and the mel table and the fmin / fmax check use sr.
+    delta = 1 or 2 appends librosa.feature.delta's columns of that many orders (Savitzky-Golay over delta_width frames; a file
+    with fewer frames than delta_width fails alone); normalize = "mean" / "mean_var" normalises every column per file, a tuple
+    (mean, std) with the caller's vectors (std None: mean only), dividing by max(std, std_floor). The arrays are then
+    (frames, dim * (1 + delta)); with the defaults the stage is off and the rows are those of the spectral kernels."""
     _corpus.check_errors(errors)
     from .pcm import check_sr
     target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
+    post, dim, keep = post_spec(spec_dim(spec), delta, delta_width, normalize, std_floor)
     lib = _load()
-    dim = spec_dim(spec)
     counts = np.zeros(len(list_of_bytes), np.uint64)
-    return _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_sr, list_of_bytes,
-                       (threads, feeders, files_per_submit, device, C.byref(spec), target), (counts,),
+    fn, extra = (lib.ogg_vorbis_spectral_corpus_sr, ()) if post is None else (lib.ogg_vorbis_spectral_corpus_post, (C.byref(post),))
+    return _corpus.run(lib, fn, list_of_bytes, (threads, feeders, files_per_submit, device, C.byref(spec), target) + extra, (counts,),
                        lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors, "spectral",
                        stats)
 
