@@ -30,7 +30,8 @@ extern "C" {
 
 #define VSYN_ABI_VERSION 5 /* 2: + residue VQ stage (vsyn_attach_vq, vsyn_vq_batch), page-locked host buffers; 3: + vsyn_pcm_abs_sum_host,
                               vsyn_pcm_fetch_host, VSYN_SUBMIT_KEEP_PCM (additive; the feature taps no longer force the staged kernels);
-                              4: + vsyn_fused_paths (additive); 5: + VSYN_SUBMIT_PRE_KERNELS (additive) */
+                              4: + vsyn_fused_paths (additive); 5: + VSYN_SUBMIT_PRE_KERNELS (additive); still 5: + the PCM
+                              conditioning entry points (vsyn_pcm_cond, vsyn_pcm_condition_*, vsyn_pcm_cond_spectral_host; additive) */
 
 #define VSYN_MAX_CHANNELS 32 /* floor_used is a 32-bit mask (reference: uint8_t audio_channels) */
 #define VSYN_MAX_POSTS 65    /* Vorbis I: 2 + 31 partitions x <=8 dims, capped at 65 by the spec */
@@ -616,6 +617,73 @@ int vsyn_spectral_post_device(vsyn_handle* h, const vsyn_spectral_post* post, ui
 int vsyn_pcm_spectral_post_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t num_segments,
                                 const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
                                 vsyn_status* status, const char** err);
+
+/* ---- PCM conditioning: mono downmix, peak normalisation and pre-emphasis of the decoded PCM, computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames. Output: ONE float32 plane z[t] of the same T. This is
+ * what the consumers of the spectral rows do to the waveform in front of the STFT: librosa.load(mono=True), and the options
+ * peak_normalization / preemphasis of RETURNN's ExtractAudioFeatures. Neither is among the test dependencies: the device is
+ * compared against a float64 model of the arithmetic below (tests/condition_model.py), and the model's pre-emphasis against
+ * scipy.signal.lfilter.
+ *
+ *  1. Downmix. y[t] = the float32 sum of x[c][t] over the channels in ascending order, times float32(1 / C) when C > 1. It is the
+ *     expression of step 1 of the spectral features, one device function shared by both: a mono plane from this stage, given to
+ *     vsyn_spectral_device with channels = 1, gives the rows the C-channel PCM gives, bit for bit.
+ *  2. Peak (VSYN_COND_PEAK). p = max_t |y[t]| over the segment's T frames. y1[t] = y[t] / p, the correctly rounded float32
+ *     division, when p > 0: the peak sample becomes exactly +-1. y1 = y when p = 0 (silence, T = 0). A peak that is not finite
+ *     (an Inf or NaN sample) refuses that segment alone: its plane is zeros and its entry of the peaks array holds the value that
+ *     is not finite; the other segments of the call are not affected. Without the option y1 = y and nothing is checked.
+ *  3. Pre-emphasis (VSYN_COND_PREEMPH, coefficient a, 0 < a < 1, rounded once to float32). z[0] = y1[0], and
+ *     z[t] = fmaf(-a, y1[t-1], y1[t]) for t > 0: scipy.signal.lfilter([1, -a], [1], y1) with zero initial state. Without the
+ *     option z = y1.
+ *  4. Order in the pipeline: decode, resample per channel (if asked), condition, then PCM out or STFT, then the post stage. The
+ *     peak is the peak of what the STFT sees.
+ *  5. Checks (VSYN_ERR_INVALID before anything runs): unknown option bits; VSYN_COND_PREEMPH with a coefficient that is not
+ *     finite, or that as a double or rounded to float32 is outside (0, 1); channels = 0.
+ *
+ * Precision: p is a maximum, taken on the absolute values' bit patterns as unsigned integers (no floating-point atomics), so it
+ * depends on neither the order nor the launch geometry nor the segment's place in the batch; every z[t] is a function of x[.][t-1],
+ * x[.][t] and p alone. The same input always gives the same bits. A NULL vsyn_pcm_cond means the stage is off: nothing is launched
+ * and every entry point that takes one returns what its counterpart without the stage returns, bit for bit; options = 0 is the
+ * downmix alone. The conditioning entry points read PCM only: they touch neither stream state, the overlap buffers nor the PCM
+ * kept by VSYN_SUBMIT_KEEP_PCM, and a later vsyn_pcm_fetch_host returns the same PCM. One handle's conditioning entry points share
+ * its conditioning workspace. */
+#define VSYN_COND_PEAK 1u     /* peak normalisation (step 2) */
+#define VSYN_COND_PREEMPH 2u  /* pre-emphasis with the coefficient `preemphasis` (step 3) */
+
+typedef struct vsyn_pcm_cond {
+  uint32_t options;    /* VSYN_COND_* option bits; the downmix is implied by the stage */
+  uint32_t reserved;
+  double preemphasis;  /* a, with VSYN_COND_PREEMPH */
+} vsyn_pcm_cond;
+
+/* The caller's planar PCM: d_pcm[(g * channels + c) * plane_stride + t], d_frames[S] (device) frames per segment (clamped to
+ * plane_stride and to out_plane_stride). Writes d_out[g * out_plane_stride + t] for t < T(g), nothing past it. d_peaks[S] (device,
+ * may be NULL): with VSYN_COND_PEAK each segment's p (step 2: a value that is not finite marks a refused segment), not written
+ * without the option. d_out with d_frames is in the input form of vsyn_spectral_device with channels = 1. Asynchronous on
+ * hip_stream. */
+int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t num_segments, const float* d_pcm, uint64_t plane_stride,
+                              uint32_t channels, const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride, float* d_peaks,
+                              void* hip_stream, const char** err);
+
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle (with or without VSYN_SUBMIT_KEEP_PCM), per segment resampled from
+ * in_rates[S] (host; 0 skips the segment) to out_rate when out_rate != 0 (out_rate = 0: no resampling, in_rates is not read and
+ * may be NULL), conditioned, and copied to the host. frames_out[S] (host) receives each segment's T. out (may be NULL when only
+ * the counts are wanted) receives the mono planes, out[g * out_stride_frames + t]: VSYN_PCM_F32 float32, or VSYN_PCM_S16 int16
+ * converted as vsyn_pcm_interleave_device does. Frames past a segment's T are zero. peaks_out[S] (host, may be NULL): each
+ * segment's p with VSYN_COND_PEAK (not finite: the segment is refused, step 2), 0 without. An out_stride_frames below some
+ * segment's T is VSYN_ERR_INVALID, with frames_out filled. Synchronous. */
+int vsyn_pcm_condition_host(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                            int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err);
+
+/* The whole front end on the PCM of the most recent submit without anything leaving the device in between: resample (out_rate != 0;
+ * in_rates as for vsyn_pcm_spectral_post_host), condition (cond != NULL), spectral rows, post stage (post != NULL). With cond and
+ * post NULL this is vsyn_pcm_spectral_host resp. vsyn_pcm_resample_spectral_host, with cond NULL vsyn_pcm_spectral_post_host.
+ * peaks_out[S] (host, may be NULL) as for vsyn_pcm_condition_host: a refused segment's rows are those of its plane of zeros, to be
+ * discarded by the caller. Synchronous. */
+int vsyn_pcm_cond_spectral_host(vsyn_handle* h, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post,
+                                uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
+                                uint64_t* seg_rows, float* peaks_out, vsyn_status* status, const char** err);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,7 @@ VSYN_SUBMIT_INPUTS_READY = 2
 VSYN_SUBMIT_KEEP_PCM = 4
 VSYN_SUBMIT_PRE_KERNELS = 8
 VSYN_PCM_S16, VSYN_PCM_F32 = 1, 2
+VSYN_COND_PEAK, VSYN_COND_PREEMPH = 1, 2
 
 
 class Floor1(C.Structure):
@@ -69,6 +70,10 @@ class SpectralSpec(C.Structure):  # vsyn_spectral_spec
 class SpectralPost(C.Structure):  # vsyn_spectral_post
     _fields_ = [("order", C.c_uint32), ("width", C.c_uint32), ("norm", C.c_uint32), ("stats", C.c_uint32), ("std_floor", C.c_double),
                 ("mean", C.c_void_p), ("std", C.c_void_p)]
+
+
+class PcmCond(C.Structure):  # vsyn_pcm_cond
+    _fields_ = [("options", C.c_uint32), ("reserved", C.c_uint32), ("preemphasis", C.c_double)]
 
 
 class Status(C.Structure):
@@ -198,6 +203,7 @@ _SYMBOLS = [
     "vsyn_spectral_num_frames", "vsyn_spectral_device", "vsyn_pcm_spectral_host",
     "vsyn_resample_num_frames", "vsyn_resample_device", "vsyn_pcm_resample_host", "vsyn_pcm_resample_spectral_host",
     "vsyn_spectral_post_dim", "vsyn_spectral_post_device", "vsyn_pcm_spectral_post_host",
+    "vsyn_pcm_condition_device", "vsyn_pcm_condition_host", "vsyn_pcm_cond_spectral_host",
 ]
 
 
@@ -271,6 +277,10 @@ def load():
     lib.vsyn_spectral_post_device.argtypes = [vp, C.POINTER(SpectralPost), u32, u32, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_spectral_post_host.argtypes = [vp, C.POINTER(SpectralSpec), C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp,
                                                 C.POINTER(Status), cpp]
+    lib.vsyn_pcm_condition_device.argtypes = [vp, C.POINTER(PcmCond), u32, vp, u64, u32, vp, vp, u64, vp, vp, cpp]
+    lib.vsyn_pcm_condition_host.argtypes = [vp, C.POINTER(PcmCond), u32, vp, u32, C.c_int, vp, u64, vp, vp, cpp]
+    lib.vsyn_pcm_cond_spectral_host.argtypes = [vp, C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPost), u32, vp, u32, vp,
+                                                u64, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -447,6 +457,57 @@ class Synth:
         if rc != VSYN_OK:
             raise VsynError(rc, (err.value or b"").decode())
         return out, frames[:S]
+
+    def pcm_condition_device(self, cond, d_pcm, plane_stride, channels, num_segments, d_frames, d_out, out_plane_stride, d_peaks=None,
+                             stream=None):
+        """vsyn_pcm_condition_device on device pointers (ints)."""
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pcm_condition_device(self.h, C.byref(cond), num_segments, d_pcm, plane_stride, channels, d_frames, d_out,
+                                                out_plane_stride, d_peaks, stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+
+    def pcm_condition_host(self, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_condition_host over the last submit's segments: returns (pcm [S][stride] float32 or int16, frames [S], peaks [S]),
+        stride = the largest T."""
+        S = num_segments
+        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
+        frames = np.zeros(max(1, S), np.uint64)
+        peaks = np.zeros(max(1, S), np.float32)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pcm_condition_host(self.h, C.byref(cond), S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), None, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        stride = max(1, int(frames[:S].max()) if S else 1)
+        out = np.zeros((S, stride), np.float32 if fmt == VSYN_PCM_F32 else np.int16)
+        rc = self.lib.vsyn_pcm_condition_host(self.h, C.byref(cond), S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames),
+                                              _ptr(peaks), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        return out, frames[:S], peaks[:S]
+
+    def pcm_cond_spectral_host(self, cond, spec, post, in_rates, out_rate=0):
+        """vsyn_pcm_cond_spectral_host over the last submit's segments (cond / post may be None): returns dict(rc, rows [total][D_out],
+        seg_rows [S], peaks [S], flags)."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S = len(rates)
+        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + (post.order if post is not None else 0))
+        seg_rows = np.zeros(max(S, 1), np.uint64)
+        peaks = np.zeros(max(S, 1), np.float32)
+        st, err = Status(), C.c_char_p()
+        cp = None if cond is None else C.byref(cond)
+        pp = None if post is None else C.byref(post)
+        rc = self.lib.vsyn_pcm_cond_spectral_host(self.h, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None,
+                                                  C.byref(st), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum())
+        rows = np.zeros((max(total, 1), dout), np.float32)
+        rc = self.lib.vsyn_pcm_cond_spectral_host(self.h, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows),
+                                                  _ptr(peaks), C.byref(st), C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], peaks=peaks[:S], flags=st.flags)
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

@@ -31,6 +31,7 @@
 #include "vsyn_spectral.h"
 #include "vsyn_spectral_post.h"
 #include "vsyn_resample.h"
+#include "vsyn_condition.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846264338327
@@ -244,6 +245,10 @@ struct vsyn_handle {
   DevBuf<uint64_t> rs_off;
   DevBuf<float> rs_pcm;                // host forms: the resampled PCM
   DevBuf<int16_t> rs_s16;              // vsyn_pcm_resample_host, VSYN_PCM_S16
+  // PCM conditioning (vsyn_condition.h): buffers of its own; the PCM is only read
+  DevBuf<float> cd_pcm;                // host forms: the conditioned mono planes
+  DevBuf<uint32_t> cd_peak, cd_frames; // per segment: max |bits| of the downmix; frames written
+  DevBuf<int16_t> cd_s16;              // vsyn_pcm_condition_host, VSYN_PCM_S16
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -2095,6 +2100,76 @@ static int rs_launch(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t
   return VSYN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// PCM conditioning (vsyn_condition.h; semantics in the header)
+// ------------------------------------------------------------------------------------------------
+static int cond_check(const vsyn_pcm_cond* c, const char** err) {
+  if (!c) return fail(err, VSYN_ERR_INVALID, "PCM conditioning spec is NULL");
+  if (c->options & ~(VSYN_COND_PEAK | VSYN_COND_PREEMPH)) return fail(err, VSYN_ERR_INVALID, "unknown conditioning options 0x%x", c->options);
+  if (c->options & VSYN_COND_PREEMPH) {
+    const double a = c->preemphasis;
+    if (!std::isfinite(a) || !(a > 0.0 && a < 1.0) || !((float)a > 0.0f && (float)a < 1.0f))
+      return fail(err, VSYN_ERR_INVALID, "pre-emphasis coefficient %g outside (0, 1)", a);
+  }
+  return VSYN_OK;
+}
+
+// A NULL handle: without a usable device there is nothing to make one from, and that is what the caller has to hear.
+static int cond_no_handle(const char** err) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(err, VSYN_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
+  return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+}
+
+// The stage's kernels on stream s: frames from d_frames, else from si; t_max bounds every segment's frames. d_peak [S] (uint32
+// view of the float peaks; NULL: the handle's) is cleared and filled with VSYN_COND_PEAK only. The frames written go to
+// h->cd_frames. Caller holds h->mu and has run cond_check.
+static int cond_launch(vsyn_handle* h, const vsyn_pcm_cond* c, uint32_t S, const float* d_pcm, uint64_t plane, uint32_t C,
+                       const uint32_t* d_frames, const SegInfo* si, uint64_t t_max, float* d_out, uint64_t out_plane, uint32_t* d_peak,
+                       hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_out & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM pointers must be 4-byte aligned");
+  const uint64_t gx = (std::min(std::min(t_max, plane), out_plane) + 3u + COND_TILE - 1u) / COND_TILE;
+  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(h->cd_frames.ensure(S));
+  const bool peak = (c->options & VSYN_COND_PEAK) != 0;
+  if (peak && !d_peak) {
+    HIPCHK(h->cd_peak.ensure(S));
+    d_peak = h->cd_peak.p;
+  }
+  CondCtx A;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.out = d_out;
+  A.out_plane = out_plane;
+  A.peak = peak ? d_peak : nullptr;
+  A.out_frames = h->cd_frames.p;
+  A.opts = c->options;
+  A.a = (c->options & VSYN_COND_PREEMPH) ? (float)c->preemphasis : 0.0f;
+  const dim3 grid((uint32_t)gx, S);
+  if (peak) {
+    HIPCHK(hipMemsetAsync(d_peak, 0, sizeof(uint32_t) * S, s));
+    hipLaunchKernelGGL(vsyn_cond_peak_kernel, grid, dim3(COND_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(vsyn_cond_apply_kernel, grid, dim3(COND_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}
+
+// peaks_out[S] (may be NULL) from the handle's peak words behind the kernels on stream s; zeros without VSYN_COND_PEAK.
+static int cond_fetch_peaks(vsyn_handle* h, const vsyn_pcm_cond* c, uint32_t S, float* peaks_out, hipStream_t s, const char** err) {
+  if (!peaks_out || !S) return VSYN_OK;
+  if (c->options & VSYN_COND_PEAK) HIPCHK(hipMemcpyAsync(peaks_out, h->cd_peak.p, sizeof(float) * S, hipMemcpyDeviceToHost, s));
+  else memset(peaks_out, 0, sizeof(float) * S);
+  return VSYN_OK;
+}
+
 // The last host submit's frames per segment: SegInfo::total_emit clamped to its plane; with out_rate != 0, what segment g has once
 // resampled from rates[g] to out_rate (0 for rates[g] = 0; the caller has run rs_check). Caller holds h->mu.
 static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, std::vector<uint64_t>& T, const char** err) {
@@ -2114,13 +2189,17 @@ static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates,
 }
 
 // vsyn_pcm_spectral_host, and with out_rate != 0 vsyn_pcm_resample_spectral_host: the rows of the last host submit's PCM, each
-// segment resampled from rates[g] to out_rate first when out_rate != 0.
+// segment resampled from rates[g] to out_rate first when out_rate != 0, then conditioned into a mono plane when cond != NULL.
 static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S,
                              const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
-                             vsyn_status* status, const char** err) {
+                             vsyn_status* status, const char** err, const vsyn_pcm_cond* cond = nullptr, float* peaks_out = nullptr) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   status_reset(status);
   int rc;
+  if (cond) {
+    rc = cond_check(cond, err);
+    if (rc) return rc;
+  }
   std::vector<uint32_t> sp_rates;  // resampled: the spectral pass sees every resampled segment at out_rate
   if (out_rate) {
     rc = rs_check(S, rates, out_rate, err);
@@ -2138,7 +2217,8 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   }
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
-  // the lock covers the whole call: the spectral and resample workspaces are the handle's, and the PCM must stay that of the last submit
+  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
+  // the lock covers the whole call: the spectral, resample and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
   std::vector<uint64_t> T;
   rc = last_submit_frames(h, S, rates, out_rate, T, err);
@@ -2175,9 +2255,22 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, con
     si = nullptr;
     d_frames = h->rs_outF.p;
   }
+  uint32_t spec_C = C;
+  if (cond) {  // the spectral pass reads the conditioned mono plane as 1-channel PCM, with the frames the stage wrote
+    HIPCHK(h->cd_pcm.ensure((size_t)S * t_max + 1));
+    rc = cond_launch(h, cond, S, pcm, plane, C, d_frames, si, t_max, h->cd_pcm.p, t_max, nullptr, hs, err);
+    if (rc) return rc;
+    rc = cond_fetch_peaks(h, cond, S, peaks_out, hs, err);
+    if (rc) return rc;
+    pcm = h->cd_pcm.p;
+    plane = t_max;
+    si = nullptr;
+    d_frames = h->cd_frames.p;
+    spec_C = 1;
+  }
   const uint64_t D = spec_dim(spec);
   HIPCHK(h->sp_rows.ensure(total * D + 1));
-  rc = spec_launch(h, spec, S, spec_rates, pcm, plane, C, d_frames, si, f_max, total, h->sp_rows.p, nullptr, hs, err);
+  rc = spec_launch(h, spec, S, spec_rates, pcm, plane, spec_C, d_frames, si, f_max, total, h->sp_rows.p, nullptr, hs, err);
   if (rc) return rc;
   if (post) {  // the rows go on to the post stage in their place, and its wider rows come back
     const uint64_t Dout = D * (1u + post->order);
@@ -2284,6 +2377,91 @@ int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* sp
     return rs_check(S, in_rates, out_rate, err);
   }
   return pcm_spectral_host(h, spec, nullptr, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err);
+}
+
+int vsyn_pcm_cond_spectral_host(vsyn_handle* h, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post,
+                                uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
+                                uint64_t* seg_rows, float* peaks_out, vsyn_status* status, const char** err) {
+  if (!h) return cond_no_handle(err);
+  return pcm_spectral_host(h, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err, cond, peaks_out);
+}
+
+int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t S, const float* d_pcm, uint64_t plane_stride,
+                              uint32_t channels, const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride, float* d_peaks,
+                              void* hip_stream, const char** err) {
+  if (!h) return cond_no_handle(err);
+  int rc = cond_check(cond, err);
+  if (rc) return rc;
+  if (channels == 0 || channels > 255) return fail(err, VSYN_ERR_INVALID, "channels %u outside [1, 255]", channels);
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_out || plane_stride == 0 || out_plane_stride == 0)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer or zero stride");
+  if (plane_stride > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return cond_launch(h, cond, S, d_pcm, plane_stride, channels, d_frames, nullptr, plane_stride, d_out, out_plane_stride, (uint32_t*)d_peaks,
+                     (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_condition_host(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, int format,
+                            void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err) {
+  if (!h) return cond_no_handle(err);
+  int rc = cond_check(cond, err);
+  if (rc) return rc;
+  if (out_rate) {
+    rc = rs_check(S, in_rates, out_rate, err);
+    if (rc) return rc;
+  }
+  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
+  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
+  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
+  // the lock covers the whole call: the resample and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T;
+  rc = last_submit_frames(h, S, in_rates, out_rate, T, err);
+  if (rc) return rc;
+  uint64_t t_max = 0;
+  for (uint32_t g = 0; g < S; ++g) {
+    frames_out[g] = T[g];
+    t_max = std::max(t_max, T[g]);
+  }
+  if (!out || S == 0) return VSYN_OK;
+  if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
+                                             (unsigned long long)out_stride_frames, (unsigned long long)t_max);
+  if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
+  const uint32_t C = h->H.channels;
+  hipStream_t hs = h->host_stream;
+  const float* pcm = h->st_pcm.p;
+  uint64_t plane = h->last_host_plane;
+  const SegInfo* si = h->ws_seg[h->last_wb].p;
+  const uint32_t* d_frames = nullptr;
+  if (out_rate) {
+    const uint64_t rs_plane = std::max<uint64_t>(t_max, 1);
+    HIPCHK(h->rs_pcm.ensure((size_t)S * C * rs_plane + 1));
+    rc = rs_launch(h, S, in_rates, out_rate, pcm, plane, C, nullptr, si, h->rs_pcm.p, rs_plane, h->rs_outF.p, hs, err);
+    if (rc) return rc;
+    pcm = h->rs_pcm.p;
+    plane = rs_plane;
+    si = nullptr;
+    d_frames = h->rs_outF.p;
+  }
+  const size_t n = (size_t)S * out_stride_frames;
+  HIPCHK(h->cd_pcm.ensure(n + 1));
+  if (format == VSYN_PCM_F32) HIPCHK(hipMemsetAsync(h->cd_pcm.p, 0, sizeof(float) * n, hs));  // zeros past each segment's T
+  rc = cond_launch(h, cond, S, pcm, plane, C, d_frames, si, t_max, h->cd_pcm.p, out_stride_frames, nullptr, hs, err);
+  if (rc) return rc;
+  rc = cond_fetch_peaks(h, cond, S, peaks_out, hs, err);
+  if (rc) return rc;
+  if (format == VSYN_PCM_F32) {
+    HIPCHK(hipMemcpyAsync(out, h->cd_pcm.p, sizeof(float) * n, hipMemcpyDeviceToHost, hs));
+  } else {  // one channel: planar is interleaved, and the conversion is vsyn_pcm_interleave_device's (pcm_s16)
+    HIPCHK(h->cd_s16.ensure(n + 1));
+    const dim3 grid((uint32_t)((out_stride_frames + 255) / 256), S);
+    hipLaunchKernelGGL(vsyn_rs_s16_kernel, grid, dim3(256), 0, hs, h->cd_pcm.p, out_stride_frames, 1u, h->cd_frames.p, h->cd_s16.p, out_stride_frames);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, h->cd_s16.p, sizeof(int16_t) * n, hipMemcpyDeviceToHost, hs));
+  }
+  HIPCHK(hipStreamSynchronize(hs));
+  return VSYN_OK;
 }
 
 }  // extern "C"

@@ -119,6 +119,16 @@ __device__ __forceinline__ const float* win_of(const uint8_t* cb, int b, int wid
   return (const float*)(cb + hdr_of(cb)->off_win[b]) + (size_t)widx * hdr_of(cb)->bs[b];
 }
 
+// The mono downmix of frame t of one segment's planar PCM (x = the segment's first plane, C planes `plane` floats apart): the
+// float32 sum of the channels in ascending order, times inv_c = 1.0f / (float)C when C > 1. The STFT span load (vsyn_spectral.h)
+// and the conditioning kernels (vsyn_condition.h) both call this, so that a mono plane made by the one feeds the other the bits
+// it would have computed itself.
+__device__ __forceinline__ float pcm_downmix(const float* x, uint64_t plane, uint32_t C, float inv_c, uint64_t t) {
+  float s = x[t];
+  for (uint32_t c = 1; c < C; ++c) s += x[(size_t)c * plane + t];
+  return C == 1 ? s : s * inv_c;
+}
+
 __device__ __forceinline__ void raise_status(DevStatus* st, uint32_t flag, uint32_t pkt) {
   atomicOr(&st->flags, flag);
   atomicMin(&st->first_bad_packet, pkt);

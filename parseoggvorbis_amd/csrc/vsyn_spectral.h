@@ -113,13 +113,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_stft_kernel(const Spec
   const float* x = A.pcm + (size_t)g * C * A.plane;
   for (uint32_t i = tid; i < span; i += SPEC_THREADS) {
     const int64_t t = p0 + (int64_t)i;
-    float v = 0.f;
-    if (t >= 0 && (uint64_t)t < T) {
-      float s = x[t];
-      for (uint32_t c = 1; c < C; ++c) s += x[(size_t)c * A.plane + (uint64_t)t];
-      v = C == 1 ? s : s * invC;
-    }
-    s_span[i] = v;
+    s_span[i] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, invC, (uint64_t)t) : 0.f;
   }
   for (uint32_t i = tid; i < FT * NM; i += SPEC_THREADS) s_M[i] = 0.f;
   __syncthreads();

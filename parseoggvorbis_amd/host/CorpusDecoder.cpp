@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <map>
@@ -470,6 +471,36 @@ struct Feeder {
     return OkOrError();
   }
 
+  // A file the conditioning stage refused (include/vorbis_synth_hip.h, "PCM conditioning", step 2) gets an error of its own.
+  void refuse_peaks(const std::vector<float>& peaks, Outcome& o) {
+    for (size_t s = 0; s < peaks.size(); ++s)
+      if (o.err[s].empty() && !std::isfinite(peaks[s])) o.err[s] = "condition: the peak of the downmixed PCM is not finite";
+  }
+
+  // Conditioned PCM run: each file's PCM, resampled first in a resampled run (resample_stage has set the frames and refused what
+  // the resampler refuses), through vsyn_pcm_condition_host: one mono plane per file comes back.
+  OkOrError condition_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    std::vector<uint32_t> rates(S);
+    uint64_t pl = 1;
+    for (uint32_t s = 0; s < S; ++s) {
+      rates[s] = o.err[s].empty() ? g.pending[s]->header.audio_sample_rate : 0;
+      pl = std::max(pl, o.frames[s]);
+    }
+    if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * pl));
+    else CHECK_ERR(g.pcm.ensure((size_t)S * pl));
+    const char* err = nullptr;
+    std::vector<uint64_t> got(S);
+    std::vector<float> peaks(S);
+    const int rc = vsyn_pcm_condition_host(g.handle, &opts.cond, S, rates.data(), opts.resample_rate, opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32,
+                                           opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, pl, got.data(), peaks.data(), &err);
+    if (rc != VSYN_OK) return OkOrError(std::string("GPU conditioning layer: ") + (err ? err : "conditioning failed"));
+    CHECK(got == o.frames);
+    refuse_peaks(peaks, o);
+    o.plane = pl;
+    return OkOrError();
+  }
+
   // Spectral run: each file's rows from the PCM still on the device (vsyn_pcm_spectral_host, or resampled first); a file whose rate
   // the spec does not fit (fmax above its sr / 2) gets no rows and an error of its own, unless it has one already.
   OkOrError spectral_stage(Group& g, Outcome& o) {
@@ -502,7 +533,11 @@ struct Feeder {
     CHECK_ERR(g.seg_rows.ensure(S));
     vsyn_status st;
     const char* err = nullptr;
-    const int rc = post_run(opts) ? vsyn_pcm_spectral_post_host(g.handle, &opts.spectral, &opts.post, S, rates.data(), opts.resample_rate,
+    std::vector<float> peaks(S);
+    const int rc = opts.condition ? vsyn_pcm_cond_spectral_host(g.handle, &opts.cond, &opts.spectral, post_run(opts) ? &opts.post : nullptr, S,
+                                                                rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p,
+                                                                peaks.data(), &st, &err)
+                   : post_run(opts) ? vsyn_pcm_spectral_post_host(g.handle, &opts.spectral, &opts.post, S, rates.data(), opts.resample_rate,
                                                                 g.rows.p, spec_rows, g.seg_rows.p, &st, &err)
                    : resample     ? vsyn_pcm_resample_spectral_host(g.handle, &opts.spectral, S, rates.data(), opts.resample_rate, g.rows.p,
                                                               spec_rows, g.seg_rows.p, &st, &err)
@@ -513,14 +548,16 @@ struct Feeder {
     } else if (rc != VSYN_OK) {
       return OkOrError(std::string("GPU spectral layer: ") + (err ? err : "spectral failed"));
     }
+    if (opts.condition) refuse_peaks(peaks, o);
     return OkOrError();
   }
 
   // A synthesis run's file: its PCM (or, for a spectral run, its rows) to the callbacks.
   OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
-    const uint32_t C = g.channels;
+    const uint32_t C = opts.condition ? 1u : g.channels;  // channels delivered
     const bool spectral = spectral_run(opts);
     const uint64_t frames = o.frames[s], pl = o.plane;
+    if (opts.condition) out.channels = 1;
     std::vector<DataRange<const float>> chans(C);
     double acc = 0;
     for (uint32_t c = 0; c < C; ++c) {
@@ -553,18 +590,19 @@ struct Feeder {
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
     const bool spectral = spectral_run(opts);  // the PCM stays on the device: only the spectral rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
+    const bool cond = opts.condition;               // ... and until it is conditioned
     double t0 = now_s();
     Packed k;
     CHECK_ERR(pack(g, true, true, k));
     const uint64_t plane = (uint64_t)k.max_p * (g.bs1 / 2);
     CHECK_ERR(g.emit.ensure(k.P));
     if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * C * plane));
-    else if (!spectral && !resample) CHECK_ERR(g.pcm.ensure((size_t)S * C * plane));
+    else if (!spectral && !resample && !cond) CHECK_ERR(g.pcm.ensure((size_t)S * C * plane));
     double t1 = now_s();
     stats.pack_s += t1 - t0;
     vsyn_status st = {0, 0xffffffffu};
     const char* err = nullptr;
-    const int rc = synthesize(g, k, plane, opts.pcm_s16 || spectral || resample, &st, &err);
+    const int rc = synthesize(g, k, plane, opts.pcm_s16 || spectral || resample || cond, &st, &err);
     Outcome o;
     if (rc == VSYN_OK) {
       o.plane = plane;
@@ -577,8 +615,9 @@ struct Feeder {
         q0 += np;
         CHECK(o.frames[s] <= plane);
       }
-      if (!resample) CHECK_ERR(fetch(g, o));
-      else CHECK_ERR(resample_stage(g, spectral, o));
+      if (resample) CHECK_ERR(resample_stage(g, spectral || cond, o));
+      else if (!cond) CHECK_ERR(fetch(g, o));
+      if (cond && !spectral) CHECK_ERR(condition_stage(g, o));
       if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
     double t2 = now_s();
@@ -861,8 +900,9 @@ struct MallocOut : CorpusCallbacks {
       for (size_t c = 0; c < ch.size(); ++c) memcpy((float*)out[i] + c * n, ch[c].begin(), n * sizeof(float));
     return true;
   }
+  uint32_t s16_channels = 0;  // channels of the int16 frames delivered; 0: the header's (CorpusOptions::condition delivers one)
   bool gotFilePcmS16(size_t i, const VorbisIdHeader& h, const int16_t* x, uint64_t frames) override {
-    const size_t bytes = (size_t)frames * h.audio_channels * sizeof(int16_t);
+    const size_t bytes = (size_t)frames * (s16_channels ? s16_channels : h.audio_channels) * sizeof(int16_t);
     if (frames && alloc(i, bytes)) memcpy(out[i], x, bytes);
     return true;
   }
@@ -886,6 +926,7 @@ int malloc_corpus(const char* name, const uint8_t* const* datas, const size_t* l
     for (size_t i = 0; i < num_files; ++i) out[i] = nullptr;
   MallocOut copy_out;
   copy_out.out = out;
+  copy_out.s16_channels = opts.condition ? 1u : 0u;
   copy_out.no_mem.assign(num_files, 0);
   std::vector<CorpusFileResult> results;
   const OkOrError r = run_corpus(datas, lens, num_files, opts, out ? &copy_out : nullptr, results, stats_out);
@@ -938,7 +979,7 @@ namespace {
 int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                     const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
-                    const char** error_out_per_file, double* stats_out, const char** error_out) {
+                    const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
@@ -946,6 +987,10 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
   opts.spectral = *spec;
   opts.resample_rate = target_rate;
   if (post) opts.post = *post;
+  if (cond) {
+    opts.condition = true;
+    opts.cond = *cond;
+  }
   return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
@@ -976,15 +1021,36 @@ extern "C" int ogg_vorbis_spectral_corpus_post(const uint8_t* const* datas, cons
                          target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
+extern "C" int ogg_vorbis_spectral_corpus_cond(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                               uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                               const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, float** rows_out,
+                                               uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                                               const char** error_out) {
+  return spectral_corpus("ogg_vorbis_spectral_corpus_cond", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
+                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond);
+}
+
 extern "C" int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                      uint32_t files_per_submit, int device, uint32_t target_rate, int format, void** pcm_out, uint64_t* frames_out,
                                      uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file,
                                      double* stats_out, const char** error_out) {
+  return ogg_vorbis_pcm_corpus_cond(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, nullptr, pcm_out,
+                                    frames_out, channels_out, rate_out, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+extern "C" int ogg_vorbis_pcm_corpus_cond(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                          void** pcm_out, uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out,
+                                          const char** error_out_per_file, double* stats_out, const char** error_out) {
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
     return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
   CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
   opts.pcm_s16 = format == VSYN_PCM_S16;
   opts.resample_rate = target_rate;
+  if (cond) {
+    opts.condition = true;
+    opts.cond = *cond;
+  }
   return malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
                        [&](size_t i, const CorpusFileResult& res, bool bad) {
                          if (frames_out) frames_out[i] = bad ? 0 : res.frames;

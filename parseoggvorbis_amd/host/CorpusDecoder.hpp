@@ -86,6 +86,13 @@ struct CorpusOptions {
   // normalisation of each file's rows on the device (include/vorbis_synth_hip.h, "spectral post-processing"); the rows delivered have
   // dim * (1 + order) columns. A file with fewer frames than the delta width fails alone. The default is off: today's rows.
   vsyn_spectral_post post = {0, 9, VSYN_POST_NORM_NONE, VSYN_POST_STATS_SEGMENT, 1e-5, nullptr, nullptr};
+  // condition: each file's PCM (resampled first with resample_rate) goes through the conditioning stage on the device
+  // (include/vorbis_synth_hip.h, "PCM conditioning": mono downmix, and per cond.options peak normalisation and pre-emphasis). A PCM
+  // run then delivers ONE channel (gotFilePcm with one range; gotFilePcmS16 with mono frames whatever the header's channel count;
+  // channels = 1 in the results, abs_sum over the delivered plane), a spectral run computes its rows from that plane. A file
+  // whose peak is not finite fails alone. Not for feature runs. The default is off: today's output.
+  bool condition = false;
+  vsyn_pcm_cond cond = {0, 0, 0.0};
 };
 
 struct CorpusStats {
@@ -152,6 +159,19 @@ int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_
                           uint32_t files_per_submit, int device, uint32_t target_rate, int format, void** pcm_out, uint64_t* frames_out,
                           uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
                           const char** error_out);
+// ogg_vorbis_pcm_corpus through the conditioning stage (CorpusOptions::cond = *cond): pcm_out receives ONE plane per file,
+// float32 [frames] or int16 [frames], and channels_out 1. cond = NULL is ogg_vorbis_pcm_corpus.
+int ogg_vorbis_pcm_corpus_cond(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                               uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                               void** pcm_out, uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out,
+                               const char** error_out_per_file, double* stats_out, const char** error_out);
+// spectral run whose rows are computed from the conditioned plane: resample (target_rate != 0), condition (cond != NULL), spectral
+// rows, post stage (post != NULL). cond = NULL is ogg_vorbis_spectral_corpus_post resp. ogg_vorbis_spectral_corpus_sr. A file whose
+// peak is not finite (VSYN_COND_PEAK) fails alone. Same output contract.
+int ogg_vorbis_spectral_corpus_cond(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                    const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, float** rows_out, uint64_t* rows_count_out,
+                                    uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
 }
 

@@ -3,7 +3,14 @@ libparseoggvorbis_amd.so (ogg_vorbis_pcm_corpus). Resampling is scipy.signal.res
 res_type="polyphase", not its default soxr), computed on the device before the PCM is copied back; the arithmetic is written out
 in include/vorbis_synth_hip.h ("resampling") and the float64 model in tests/resample_model.py is the contract.
 
+mono=True returns ONE plane per file, made on the device by the conditioning stage (include/vorbis_synth_hip.h, "PCM
+conditioning"; float64 model: tests/condition_model.py): the channels' float32 mean like librosa.load's default, optionally
+divided by its peak (peak_normalize) and pre-emphasised (preemphasis), after the resampling and before the copy to the host.
+
 Every argument is checked before the library is loaded."""
+import ctypes as C
+import math
+
 import numpy as np
 
 from . import _corpus
@@ -37,19 +44,48 @@ def _format(dtype):
     return name
 
 
+COND_PEAK, COND_PREEMPH = 1, 2  # VSYN_COND_PEAK, VSYN_COND_PREEMPH
+
+
+def cond_spec(peak_normalize=False, preemphasis=None, error=PcmError):
+    """Checks the conditioning arguments (include/vorbis_synth_hip.h, "PCM conditioning", step 5) and returns the C spec
+    (binding.PcmCond): peak_normalize a bool; preemphasis None or a real number whose float32 rounding lies in (0, 1)."""
+    from .binding import PcmCond
+    if not isinstance(peak_normalize, (bool, np.bool_)):
+        raise error("peak_normalize must be a bool, got %r" % (peak_normalize,))
+    opts, a = (COND_PEAK if peak_normalize else 0), 0.0
+    if preemphasis is not None:
+        if isinstance(preemphasis, (bool, np.bool_)) or not isinstance(preemphasis, (int, float, np.integer, np.floating)):
+            raise error("preemphasis must be None or a number in (0, 1), got %r" % (preemphasis,))
+        a = float(np.float32(preemphasis))  # rounded once to float32: the coefficient the device uses
+        if not (math.isfinite(a) and 0.0 < float(preemphasis) < 1.0 and 0.0 < a < 1.0):
+            raise error("preemphasis must be in (0, 1), got %r" % (preemphasis,))
+        opts |= COND_PREEMPH
+    return PcmCond(opts, 0, a)
+
+
 _load = _corpus.load
 
 
 def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0, device=0, errors="raise", files_per_submit=64,
-                  stats=None):
+                  stats=None, mono=False, peak_normalize=False, preemphasis=None):
     """PCM of many Ogg Vorbis files in one corpus run: a list of (pcm, sr) tuples. pcm is float32 (channels, frames), or int16
     (frames, channels) with ov_read's conversion; sr is the rate of the returned PCM. sr=None keeps each file's own rate (the
     PCM is bit for bit that of ogg_vorbis_decode_corpus); an integer resamples every file to it on the GPU. errors="raise": the
     first failed file raises PcmError naming it; errors="return": its entry is the PcmError. stats (optional list) receives
-    the run's 8 corpus statistics."""
+    the run's 8 corpus statistics.
+    mono=True: pcm is 1-D (frames,), float32 or int16, the channels' mean computed on the device (half the bytes come back for
+    stereo files); with peak_normalize=True divided by its largest magnitude, so that the peak is exactly +-1 (a file with an Inf
+    or NaN sample fails alone; silence stays silence); with preemphasis=a, 0 < a < 1, then filtered as z[t] = y[t] - a y[t-1].
+    peak_normalize and preemphasis need mono=True."""
     _corpus.check_errors(errors)
     target = check_sr(sr)
     name = _format(dtype)
+    if not isinstance(mono, (bool, np.bool_)):
+        raise PcmError("mono must be a bool, got %r" % (mono,))
+    cond = cond_spec(peak_normalize, preemphasis)
+    if not mono and cond.options:
+        raise PcmError("peak_normalize and preemphasis act on the mono signal: pass mono=True")
     lib = _load()
     n = len(list_of_bytes)
     frames = np.zeros(n, np.uint64)
@@ -58,11 +94,15 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
 
     def build(i, p):
         T, Cn = int(frames[i]), int(chans[i])
-        a = np.zeros((Cn, T), np.float32) if name == "float32" else np.zeros((T, Cn), np.int16)
+        if mono:
+            a = np.zeros(T, np.float32 if name == "float32" else np.int16)
+        else:
+            a = np.zeros((Cn, T), np.float32) if name == "float32" else np.zeros((T, Cn), np.int16)
         return _corpus.copy_into(a, p), int(rates[i])
 
-    return _corpus.run(lib, lib.ogg_vorbis_pcm_corpus, list_of_bytes, (threads, feeders, files_per_submit, device, target, FORMATS[name]),
-                       (frames, chans, rates), build, PcmError, errors, "pcm", stats)
+    args = (threads, feeders, files_per_submit, device, target, FORMATS[name])
+    fn, extra = (lib.ogg_vorbis_pcm_corpus_cond, (C.byref(cond),)) if mono else (lib.ogg_vorbis_pcm_corpus, ())
+    return _corpus.run(lib, fn, list_of_bytes, args + extra, (frames, chans, rates), build, PcmError, errors, "pcm", stats)
 
 
 def get_pcm_from_raw_bytes(raw_bytes, sr=None, dtype="float32", **kwargs):

@@ -8,7 +8,8 @@ Every argument is checked before the library is loaded. 25 ms / 10 ms at 44.1 kH
 each file's matrix at its own rate; an integer sr resamples every file's PCM to it on the device first (parseoggvorbis_amd/pcm.py,
 scipy.signal.resample_poly's arithmetic), so that one mel table serves the whole batch. delta / normalize finish the rows on the
 device as well (include/vorbis_synth_hip.h, "spectral post-processing"): librosa.feature.delta's columns, then per-column mean or
-mean / variance normalisation; tests/spectral_post_model.py is their float64 model."""
+mean / variance normalisation; tests/spectral_post_model.py is their float64 model. peak_normalize / preemphasis condition the mono
+waveform on the device in front of the STFT (include/vorbis_synth_hip.h, "PCM conditioning"; model: tests/condition_model.py)."""
 import ctypes as C
 import math
 
@@ -140,7 +141,7 @@ _load = _corpus.load
 def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n_mels=128, fmin=0.0, fmax=None,
                        htk=False, norm="slaney", center=True, power=2.0, log_floor=1e-3, amin=1e-10, top_db=80.0, n_mfcc=20,
                        threads=0, feeders=0, device=0, errors="raise", files_per_submit=64, stats=None, sr=None, delta=0, delta_width=9,
-                       normalize=None, std_floor=1e-5):
+                       normalize=None, std_floor=1e-5, peak_normalize=False, preemphasis=None):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels otherwise. errors="raise": the first failed file raises SpectralError naming it; errors="return": its entry
     is the SpectralError. stats (optional list) receives the run's 8 corpus statistics. sr=None: each file at its own rate;
@@ -148,16 +149,23 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     delta = 1 or 2 appends librosa.feature.delta's columns of that many orders (Savitzky-Golay over delta_width frames; a file
     with fewer frames than delta_width fails alone); normalize = "mean" / "mean_var" normalises every column per file, a tuple
     (mean, std) with the caller's vectors (std None: mean only), dividing by max(std, std_floor). The arrays are then
-    (frames, dim * (1 + delta)); with the defaults the stage is off and the rows are those of the spectral kernels."""
+    (frames, dim * (1 + delta)); with the defaults the stage is off and the rows are those of the spectral kernels.
+    peak_normalize=True divides the mono signal (after the resampling) by its largest magnitude before the STFT, preemphasis=a
+    (0 < a < 1) then filters it as z[t] = y[t] - a y[t-1] (get_pcm_batch(mono=True, ...) returns that signal); a file with an Inf
+    or NaN sample fails alone under peak_normalize. With the defaults nothing is launched."""
     _corpus.check_errors(errors)
-    from .pcm import check_sr
+    from .pcm import check_sr, cond_spec
     target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
     post, dim, keep = post_spec(spec_dim(spec), delta, delta_width, normalize, std_floor)
+    cond = cond_spec(peak_normalize, preemphasis, SpectralError)
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
-    fn, extra = (lib.ogg_vorbis_spectral_corpus_sr, ()) if post is None else (lib.ogg_vorbis_spectral_corpus_post, (C.byref(post),))
+    if cond.options:
+        fn, extra = lib.ogg_vorbis_spectral_corpus_cond, (None if post is None else C.byref(post), C.byref(cond))
+    else:
+        fn, extra = (lib.ogg_vorbis_spectral_corpus_sr, ()) if post is None else (lib.ogg_vorbis_spectral_corpus_post, (C.byref(post),))
     return _corpus.run(lib, fn, list_of_bytes, (threads, feeders, files_per_submit, device, C.byref(spec), target) + extra, (counts,),
                        lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors, "spectral",
                        stats)
