@@ -6,20 +6,12 @@
 // floor neighbour tables), which the reference also builds once per stream (mdct.cpp:88-127, hpp:837-862).
 #include <hip/hip_runtime.h>
 
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <cmath>
 #include <mutex>
-#include <numeric>
 #include <string>
-#include <vector>
 
 #include <stdlib.h>
 
+#include "vsyn_host.h"
 #include "vsyn_device.h"
 #include "vsyn_staged.h"
 #include "vsyn_prep.h"
@@ -33,100 +25,9 @@
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
 
-#ifndef M_PI
-#define M_PI 3.14159265358979323846264338327
-#endif
-#ifndef M_PI_2
-#define M_PI_2 1.57079632679489661923
-#endif
-
 static const uint32_t k_inverse_db_bits[256] = {
 #include "vorbis_floor1_inverse_db.inc"
 };
-
-namespace {
-
-thread_local char g_err[512];
-
-int fail(const char** err, int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  if (err) *err = g_err;
-  return code;
-}
-
-#define HIPCHK(call)                                                                                      \
-  do {                                                                                                    \
-    hipError_t e_ = (call);                                                                               \
-    if (e_ != hipSuccess)                                                                                 \
-      return fail(err, VSYN_ERR_HIP, "%s:%d: %s failed: %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-  } while (0)
-
-template <typename T>
-struct DevBuf {  // grow-only device buffer
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 8 + 64;
-    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  ~DevBuf() { release(); }  // (vsyn_destroy selects the device before the handle goes away)
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
-// A table built on the host per call and uploaded asynchronously from a page-locked copy. One instance per front-end: each keeps
-// buffers of its own.
-struct TableUpload {
-  DevBuf<uint8_t> dev;
-  uint8_t* host = nullptr;  // page-locked copy of the table (the upload is asynchronous)
-  size_t host_cap = 0;
-  hipEvent_t ev = nullptr;  // recorded behind the upload: the host copy is reused only after it
-  bool ev_valid = false;
-  int upload(const std::vector<uint8_t>& tab, hipStream_t s, const char** err) {
-    HIPCHK(dev.ensure(tab.size()));
-    if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    if (ev_valid) HIPCHK(hipEventSynchronize(ev));  // the previous upload has read the host copy
-    if (host_cap < tab.size()) {
-      if (host) HIPCHK(hipHostFree(host));
-      host = nullptr;
-      host_cap = 0;
-      HIPCHK(hipHostMalloc((void**)&host, tab.size() + 4096, hipHostMallocDefault));
-      host_cap = tab.size() + 4096;
-    }
-    memcpy(host, tab.data(), tab.size());
-    HIPCHK(hipMemcpyAsync(dev.p, host, tab.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ev, s));
-    ev_valid = true;
-    return VSYN_OK;
-  }
-  ~TableUpload() {  // (as DevBuf's: vsyn_destroy selects the device before the handle goes away; not copyable, as DevBuf is not)
-    if (ev) (void)hipEventDestroy(ev);
-    if (host) (void)hipHostFree(host);
-  }
-};
-
-bool is_pow2(uint32_t v) { return v && !(v & (v - 1)); }
-uint32_t ilog2(uint32_t v) {
-  uint32_t r = 0;
-  while ((1u << r) < v) ++r;
-  return r;
-}
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Knobs that tests and stress tools use to force cases (tools/README.md): read from the environment once per handle, in vsyn_create.
 struct Options {
@@ -135,7 +36,7 @@ struct Options {
   bool debug = false;             // VSYN_DEBUG: the setup's kernel choices on stderr
 };
 
-Options options_from_env() {
+static Options options_from_env() {
   Options o;
   const char* e = getenv("VSYN_RUN_LEN");
   if (e && atoi(e) > 0) o.run_len = (uint32_t)atoi(e);
@@ -144,8 +45,6 @@ Options options_from_env() {
   o.debug = getenv("VSYN_DEBUG") != nullptr;
   return o;
 }
-
-}  // namespace
 
 struct vsyn_handle {
   int device = 0;
@@ -215,40 +114,12 @@ struct vsyn_handle {
   DevBuf<uint8_t> st_conv;             // vsyn_pcm_fetch_host: interleaved output
   DevBuf<uint32_t> st_frames;
   uint64_t last_host_plane = 0;        // plane_stride of the most recent vsyn_submit_host* (0: none yet)
-  // feature matrices (vsyn_features.h): buffers of their own, so that a features call leaves every synthesis buffer alone
-  DevBuf<PktInfo> ft_info;
-  DevBuf<uint16_t> ft_fy;
-  DevBuf<uint32_t> ft_rowrel;
-  DevBuf<int32_t> ft_fbsrc;
-  DevBuf<uint8_t> ft_fbch;
-  DevBuf<uint64_t> ft_resoff, ft_segrows, ft_segoff;
-  TableUpload ft_tab;                  // the gather table
-  DevBuf<vsyn_packet> fs_pk;           // vsyn_features_host staging
-  DevBuf<vsyn_segment> fs_seg;
-  DevBuf<uint16_t> fs_ys;
-  DevBuf<float> fs_res, fs_rows;
-  // spectral features (vsyn_spectral.h): buffers of their own; the PCM is only read
-  TableUpload sp_tab;
-  bool sp_lds_set = false;             // the STFT kernels' dynamic-LDS limit is raised on this handle's device
-  DevBuf<uint32_t> sp_segF, sp_segmax;
-  DevBuf<uint64_t> sp_segoff;
-  DevBuf<float> sp_db, sp_rows;
-  // spectral post-processing (vsyn_spectral_post.h): a second row buffer (the output rows are wider) and the statistics
-  TableUpload pp_tab;
-  bool pp_lds_set = false;             // vsyn_post_delta_kernel's dynamic-LDS limit is raised on this handle's device
-  DevBuf<float> pp_rows;
-  DevBuf<double> pp_part, pp_stat;     // per-block partial sums; mu | rinv per (segment, column)
-  // resampling (vsyn_resample.h): buffers of its own; the PCM is only read
-  TableUpload rs_tab;
-  bool rs_lds_set = false;             // vsyn_rs_kernel<true>'s dynamic-LDS limit is raised on this handle's device
-  DevBuf<uint32_t> rs_inF, rs_outF;
-  DevBuf<uint64_t> rs_off;
-  DevBuf<float> rs_pcm;                // host forms: the resampled PCM
-  DevBuf<int16_t> rs_s16;              // vsyn_pcm_resample_host, VSYN_PCM_S16
-  // PCM conditioning (vsyn_condition.h): buffers of its own; the PCM is only read
-  DevBuf<float> cd_pcm;                // host forms: the conditioned mono planes
-  DevBuf<uint32_t> cd_peak, cd_frames; // per segment: max |bits| of the downmix; frames written
-  DevBuf<int16_t> cd_s16;              // vsyn_pcm_condition_host, VSYN_PCM_S16
+  // the stages behind synthesis: each owns its workspace, and its launch code sees nothing else of the handle
+  FeatureWs ft;                        // vsyn_features.h
+  SpectralWs sp;                       // vsyn_spectral.h
+  PostWs pp;                           // vsyn_spectral_post.h
+  ResampleWs rs;                       // vsyn_resample.h
+  CondWs cd;                           // vsyn_condition.h
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -538,80 +409,9 @@ void vsyn_destroy(vsyn_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-#ifdef VQ_STAMPS
-  {  // diagnostic build: the residue VQ kernel's cycles per phase and packet (last launch), averaged over its waves
-    static unsigned long long host[8192][VQ_NSTAMPS];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_vq_stamps), sizeof(host)) == hipSuccess) {
-      double sum[VQ_NSTAMPS] = {0};
-      unsigned long long pk = 0, waves = 0;
-      for (int u = 0; u < 8192; ++u) {
-        if (!host[u][VQ_NSTAMPS - 1]) continue;
-        ++waves;
-        pk += host[u][VQ_NSTAMPS - 1];
-        for (int i = 0; i + 1 < VQ_NSTAMPS; ++i) sum[i] += (double)host[u][i];
-      }
-      if (pk) {
-        fprintf(stderr, "[vq stamps] %llu waves, %.1f packets each; s_memtime ticks per packet:", waves, (double)pk / waves);
-        for (int i = 0; i + 1 < VQ_NSTAMPS; ++i) fprintf(stderr, " %d:%.0f", i, sum[i] / pk);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
-#endif
-#ifdef PREP_STAMPS
-  {  // diagnostic build: cycles per phase of vsyn_prep_kernel (last launch), averaged over the waves of each role, and when the waves
-     // of each role started / ended relative to the first wave of the launch (100 MHz clock)
-    static unsigned long long host[8192][PREP_NSTAMPS];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_prep_stamps), sizeof(host)) == hipSuccess) {
-      unsigned long long t_first = ~0ull;
-      for (int u = 0; u < 8192; ++u)
-        if (host[u][7] && host[u][5] < t_first) t_first = host[u][5];
-      for (unsigned role = 0; role < 2; ++role) {
-        double sum[5] = {0}, st = 0, en = 0, en_max = 0, st_max = 0;
-        unsigned long long waves = 0;
-        for (int u = 0; u < 8192; ++u) {
-          if (host[u][7] != 1ull + role) continue;
-          ++waves;
-          for (int i = 0; i < 5; ++i) sum[i] += (double)host[u][i];
-          const double a = (double)(host[u][5] - t_first) / 100.0, b = (double)(host[u][6] - t_first) / 100.0;
-          st += a;
-          en += b;
-          if (a > st_max) st_max = a;
-          if (b > en_max) en_max = b;
-        }
-        if (!waves) continue;
-        static const char* nm[5] = {"header + stream state", "scan in front of the chunk", "descriptors, scan, PktInfo", "floor role: descriptors, floor ids", "floor role: chains"};
-        fprintf(stderr, "prep stamps, %s role: %llu waves; start %.2f us (latest %.2f), end %.2f us (latest %.2f) after the launch's first wave\n",
-                role ? "floor" : "layout", waves, st / waves, st_max, en / waves, en_max);
-        for (int i = 0; i < 5; ++i)
-          if (sum[i] > 0) fprintf(stderr, "  %-36s %8.0f cycles\n", nm[i], sum[i] / waves);
-      }
-    }
-  }
-#endif
-#ifdef VSYN_STAMPS
-  {  // diagnostic build: per-phase cycles of the LAST launch's steady runs, averaged over the waves that ran one
-    static unsigned long long host[8192][VSYN_NSTAMPS];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_vsyn_stamps), sizeof(host)) == hipSuccess) {
-      double sum[VSYN_NSTAMPS] = {0};
-      unsigned long long waves = 0, pk = 0;
-      for (int u = 0; u < 8192; ++u) {
-        if (!host[u][VSYN_NSTAMPS - 1]) continue;
-        ++waves;
-        pk += host[u][VSYN_NSTAMPS - 1];
-        for (int i = 0; i + 1 < VSYN_NSTAMPS; ++i) sum[i] += (double)host[u][i];
-      }
-      if (pk) {
-        static const char* nm[VSYN_NSTAMPS - 1] = {"loop", "residue+handoff+couple", "loads+floor setup", "floor product", "mirror+pre-rot", "partner wait 2",
-                                                   "fft512", "post+window+overlap", "stores / short pass: stores", "short: descriptors", "short: rows", "short: couple+floor", "short: fft+window", "-", "-"};
-        double tot = 0;
-        for (int i = 0; i + 1 < VSYN_NSTAMPS; ++i) tot += sum[i];
-        fprintf(stderr, "vsyn stamps: %llu waves, %llu wave-packets, %.0f cycles per wave-packet\n", waves, pk, tot / pk);
-        for (int i = 0; i + 1 < VSYN_NSTAMPS; ++i) fprintf(stderr, "  %-26s %8.0f cycles  %5.1f %%\n", nm[i], sum[i] / pk, 100.0 * sum[i] / tot);
-      }
-    }
-  }
-#endif
+  vq_stamps_dump();
+  prep_stamps_dump();
+  fused_stamps_dump();
   fused_tables_destroy(&h->fused);
   u_tables_destroy(&h->utab);
   if (h->side) (void)hipStreamDestroy(h->side);
@@ -626,24 +426,14 @@ void vsyn_destroy(vsyn_handle* h) {
     if (h->ev_ring[b]) (void)hipEventDestroy(h->ev_ring[b]);
   if (h->d_const) (void)hipFree(h->d_const);
   if (h->d_vq) (void)hipFree(h->d_vq);
-  h->st_curve.release(); h->st_vqpk.release(); h->st_cls.release(); h->st_ent.release();
   if (h->d_state) (void)hipFree(h->d_state);
   if (h->d_carry) (void)hipFree(h->d_carry);
   if (h->d_status) (void)hipFree(h->d_status);
-  h->ws_count.release();
-  h->ws_chunks.release();
-  for (uint32_t b = 0; b < vsyn_handle::WS_RING; ++b) {
-    h->ws_list[b].release(); h->ws_info[b].release(); h->ws_seg[b].release(); h->ws_segmap[b].release(); h->ws_fy[b].release(); h->ws_runcls[b].release();
-  }
-  h->ws_env.release(); h->ws_blk.release();
-  h->st_pk.release(); h->st_seg.release(); h->st_ys.release(); h->st_fy.release(); h->st_res.release(); h->st_pcm.release();
-  h->st_env.release(); h->st_blk.release(); h->st_emit.release();
-  h->st_sum.release(); h->st_conv.release(); h->st_frames.release();
   for (auto& ev : h->events) {
     (void)hipEventDestroy(ev.first);
     (void)hipEventDestroy(ev.second);
   }
-  delete h;
+  delete h;  // (frees every DevBuf: the device is selected and idle)
 }
 
 uint32_t vsyn_ys_stride(const vsyn_handle* h) { return h ? h->H.ys_stride : 0; }
@@ -1296,183 +1086,14 @@ int vsyn_imdct_device(vsyn_handle* h, uint32_t n, uint32_t count, const float* d
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
-// the front-ends after synthesis: features, spectral, resampling
+// the front-ends after synthesis: the entry points. Each stage's checks, tables, workspace and launch are the host side of its header.
 // ------------------------------------------------------------------------------------------------
-static void status_reset(vsyn_status* status) {
-  if (status) {
-    status->flags = 0;
-    status->first_bad_packet = 0xFFFFFFFFu;
-  }
-}
-
 // The end of a *_host call: vsyn_sync_status on the host stream (which waits for it), the batch's status into *status.
 static int sync_status_into(vsyn_handle* h, vsyn_status* status, const char** err) {
   vsyn_status st;
   const int rc = vsyn_sync_status(h, h->host_stream, &st, err);
   if (status) *status = st;
   return rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// feature matrices (vsyn_features.h; semantics in the header)
-// ------------------------------------------------------------------------------------------------
-// scipy.ndimage.zoom(xs as float32, z, order=1, mode="nearest") followed by numpy.round: output length round(L * z) (Python's round);
-// input coordinate k * (L - 1) / (out - 1) in double, clamped to [0, L - 1]; linear weights (1 - t, t) summed in double from 0 in
-// that order; the float32 result rounded half to even. False where the reference's assert (length == L * z) fails.
-static bool feat_zoom_round(const std::vector<uint32_t>& xs, double z, std::vector<uint32_t>& out) {
-  const size_t L = xs.size();
-  const double want = (double)L * z;
-  const double outn_d = nearbyint(want);
-  if (outn_d != want || outn_d < 1.0 || outn_d > 1e6) return false;
-  const size_t outn = (size_t)outn_d;
-  const double zf = outn > 1 ? (double)(L - 1) / (double)(outn - 1) : 1.0;
-  out.resize(outn);
-  for (size_t k = 0; k < outn; ++k) {
-    double cc = (double)k * zf;
-    cc = std::min(std::max(cc, 0.0), (double)(L - 1));
-    const double fl = floor(cc), t = cc - fl;
-    const size_t i0 = (size_t)fl, i1 = std::min(i0 + 1, L - 1);
-    double v = 0.0 + (1.0 - t) * (double)(float)xs[i0];
-    v = v + t * (double)(float)xs[i1];
-    const float r = nearbyintf((float)v);
-    out[k] = r <= 0.f ? 0u : (uint32_t)r;
-  }
-  return true;
-}
-
-// Validates the spec against the handle's setup and builds the gather table (FeatHeader, FeatFloor[], indices).
-static int feat_build_table(const vsyn_handle* h, const vsyn_feature_spec* sp, std::vector<uint8_t>& out, const char** err) {
-  if (!sp) return fail(err, VSYN_ERR_INVALID, "feature spec is NULL");
-  const bool floor_kind = sp->kind == VSYN_FEAT_FLOOR_FINAL_YS || sp->kind == VSYN_FEAT_FLOOR_FINAL_YS_RENDERED;
-  const bool res_kind = sp->kind == VSYN_FEAT_RESIDUE_YS || sp->kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
-  if (!floor_kind && !res_kind) return fail(err, VSYN_ERR_INVALID, "unknown feature kind %u", sp->kind);
-  if (sp->output_dim == 0 || sp->output_dim > (1u << 20)) return fail(err, VSYN_ERR_INVALID, "output_dim %u out of range", sp->output_dim);
-  const uint32_t floor_opts = VSYN_FEAT_INCLUDE_FLOOR_NUMBER | VSYN_FEAT_ONLY_BIGGEST_FLOOR | VSYN_FEAT_SORTED_XS | VSYN_FEAT_XS_FROM_BIGGEST_FLOOR |
-                              VSYN_FEAT_FLOOR_ALWAYS_POSITIVE;
-  const uint32_t res_opts = VSYN_FEAT_SORTED_XS | VSYN_FEAT_LOG1P_ABS_SPACE | VSYN_FEAT_IGNORE_XS | VSYN_FEAT_CLIP;
-  if (sp->options & ~(floor_kind ? floor_opts : res_opts)) return fail(err, VSYN_ERR_INVALID, "feature options 0x%x do not apply to kind %u", sp->options, sp->kind);
-  if ((sp->options & VSYN_FEAT_ONLY_BIGGEST_FLOOR) && (sp->options & VSYN_FEAT_INCLUDE_FLOOR_NUMBER))
-    return fail(err, VSYN_ERR_INVALID, "only_biggest_floor excludes include_floor_number");
-  if (res_kind && sp->upscale_xs_factor != 1.0) return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor applies to the floor kinds only");
-  if (!(sp->upscale_xs_factor > 0.0)) return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor must be > 0");
-  const ConstHeader& H = h->H;
-  const FloorConst* fcs = (const FloorConst*)(h->host_const.data() + H.off_floor);
-  const uint32_t F = H.num_floors, D = sp->output_dim;
-  uint32_t big = 0;
-  for (uint32_t f = 1; f < F; ++f)
-    if (fcs[f].posts > fcs[big].posts) big = f;  // the first of the largest (Python's max)
-  const bool sorted = (sp->options & VSYN_FEAT_SORTED_XS) != 0;
-  std::vector<std::vector<uint32_t>> xs(F), up(F);
-  for (uint32_t f = 0; f < F; ++f) {
-    xs[f].assign(fcs[f].xs, fcs[f].xs + fcs[f].posts);
-    if (sorted) std::sort(xs[f].begin(), xs[f].end());
-    if (floor_kind && sp->upscale_xs_factor != 1.0) {
-      if (!feat_zoom_round(xs[f], sp->upscale_xs_factor, up[f]))
-        return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor %g: floor %u's %u posts do not zoom to a whole length (the reference asserts)",
-                    sp->upscale_xs_factor, f, fcs[f].posts);
-    } else {
-      up[f] = xs[f];
-    }
-  }
-  if (res_kind && !(sp->options & VSYN_FEAT_IGNORE_XS) && D < fcs[big].posts)
-    return fail(err, VSYN_ERR_INVALID, "output_dim %u is below the biggest floor's %u posts: the reference asserts on such rows (use ignore_xs)", D,
-                fcs[big].posts);
-  FeatHeader T = {};
-  T.kind = sp->kind;
-  T.dim = D;
-  T.opts = sp->options;
-  T.big = big;
-  T.num_floors = F;
-  T.scale = sp->scale;
-  T.clip = sp->clip_abs_max;
-  T.fbf = sp->floor_base_factor;
-  std::vector<FeatFloor> ff(F);
-  std::vector<uint32_t> idx;
-  const uint32_t o = (sp->options & VSYN_FEAT_INCLUDE_FLOOR_NUMBER) ? 1u : 0u;
-  for (uint32_t f = 0; f < F; ++f) {
-    std::vector<uint32_t> l;
-    FeatFloor& e = ff[f];
-    e.fnum = (float)(((double)f + 1.0) / (double)F - 0.5);
-    if (sp->options & VSYN_FEAT_XS_FROM_BIGGEST_FLOOR) {
-      l = up[big];
-      if (f != big) {
-        const double mb = (double)*std::max_element(xs[big].begin(), xs[big].end());
-        const double mc = (double)*std::max_element(xs[f].begin(), xs[f].end());
-        const double factor = nearbyint(mb / mc);  // Python's round() of the ratio (mc == 0: inf, no usable floor)
-        for (uint32_t& v : l) v = (factor >= 1.0 && factor < 4294967296.0) ? (uint32_t)(v / (uint64_t)factor) : 0u;  // numpy: x // 0 == 0
-      }
-      e.clip = 1;
-    }
-    else l = up[f];
-    e.maxidx = l.empty() ? 0u : *std::max_element(l.begin(), l.end());
-    e.cnt = D > o ? (uint32_t)std::min<size_t>(l.size(), D - o) : 0u;
-    e.off = (uint32_t)idx.size();
-    idx.insert(idx.end(), l.begin(), l.begin() + e.cnt);
-  }
-  T.res_off = (uint32_t)idx.size();
-  T.res_cnt = std::min<uint32_t>(fcs[big].posts, D);
-  idx.insert(idx.end(), xs[big].begin(), xs[big].begin() + T.res_cnt);
-  out.resize(sizeof(FeatHeader) + sizeof(FeatFloor) * F + sizeof(uint32_t) * (idx.size() + 1));
-  memcpy(out.data(), &T, sizeof(T));
-  memcpy(out.data() + sizeof(T), ff.data(), sizeof(FeatFloor) * F);
-  memcpy(out.data() + sizeof(T) + sizeof(FeatFloor) * F, idx.data(), sizeof(uint32_t) * idx.size());
-  return VSYN_OK;
-}
-
-// The count / offsets kernels (and, with rows != nullptr, the floor unwrap and the rows kernel) on stream s. Caller holds h->mu.
-static int feat_launch(vsyn_handle* h, const vsyn_feature_spec* sp, uint32_t P, const vsyn_packet* d_pk, uint32_t S, const vsyn_segment* d_seg,
-                       uint32_t max_seg, const uint16_t* d_ys, const float* d_res, float* d_rows, uint64_t* d_segoff, hipStream_t s,
-                       const char** err) {
-  std::vector<uint8_t> tab;
-  int rc = feat_build_table(h, sp, tab, err);
-  if (rc) return rc;
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  if (max_seg == 0 || max_seg > P) max_seg = P;
-  const ConstHeader& H = h->H;
-  const uint32_t C = H.channels;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(h->ft_info.ensure(P));
-  HIPCHK(h->ft_fy.ensure((size_t)P * C * H.ys_stride));
-  HIPCHK(h->ft_rowrel.ensure(P));
-  HIPCHK(h->ft_fbsrc.ensure(P));
-  HIPCHK(h->ft_fbch.ensure(P));
-  HIPCHK(h->ft_resoff.ensure(P));
-  HIPCHK(h->ft_segrows.ensure(S));
-  HIPCHK(h->ft_segoff.ensure((size_t)S + 1));
-  if (int rc = h->ft_tab.upload(tab, s, err)) return rc;
-  if (P) HIPCHK(hipMemsetAsync(h->ft_info.p, 0, sizeof(PktInfo) * P, s));  // packets outside every segment: no floor rows to unwrap
-  FeatCtx A;
-  A.cb = h->d_const;
-  A.tab = h->ft_tab.dev.p;
-  A.pk = d_pk;
-  A.seg = d_seg;
-  A.fy = h->ft_fy.p;
-  A.res = d_res;
-  A.info = h->ft_info.p;
-  A.rowrel = h->ft_rowrel.p;
-  A.fbsrc = h->ft_fbsrc.p;
-  A.fbch = h->ft_fbch.p;
-  A.resoff = h->ft_resoff.p;
-  A.segrows = h->ft_segrows.p;
-  A.segoff = d_segoff ? d_segoff : h->ft_segoff.p;
-  A.rows = d_rows;
-  A.status = h->d_status;
-  A.P = P;
-  A.S = S;
-  A.max_seg = max_seg;
-  hipLaunchKernelGGL(vsyn_feat_count_kernel, dim3(S), dim3(FEAT_THREADS), 0, s, A);
-  hipLaunchKernelGGL(vsyn_feat_offsets_kernel, dim3(1), dim3(FEAT_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  if (!d_rows || P == 0 || max_seg == 0) return VSYN_OK;  // (no packet: every segment is empty or flagged by the count kernel)
-  const uint32_t rows = P * C;
-  hipLaunchKernelGGL(vsyn_floor_unwrap_kernel, dim3(std::min<uint32_t>((rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, 65535u)), dim3(UNWRAP_THREADS), h->unwrap_lds_bytes, s,
-                     h->d_const, P, (const PktInfo*)h->ft_info.p, d_ys, h->ft_fy.p, h->d_status);
-  const uint64_t slots = (uint64_t)max_seg * C;
-  const uint64_t gx = (slots + FEAT_ROW_WAVES - 1) / FEAT_ROW_WAVES;
-  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  hipLaunchKernelGGL(vsyn_feat_rows_kernel, dim3((uint32_t)gx, S), dim3(FEAT_ROW_WAVES * 64), 0, s, A);
-  HIPCHK(hipGetLastError());
-  return VSYN_OK;
 }
 
 extern "C" {
@@ -1484,7 +1105,8 @@ int vsyn_feature_rows_device(vsyn_handle* h, const vsyn_feature_spec* spec, uint
   if (S == 0) return VSYN_OK;
   if ((P && !d_packets) || !d_segments) return fail(err, VSYN_ERR_INVALID, "NULL batch pointer");
   std::lock_guard<std::mutex> lk(h->mu);
-  return feat_launch(h, spec, P, d_packets, S, d_segments, max_seg_packets, nullptr, nullptr, nullptr, d_seg_row_off, (hipStream_t)hip_stream, err);
+  return feat_launch(h->ft, h->device, h->H, h->host_const.data(), h->d_const, h->d_status, h->unwrap_lds_bytes, spec, P, d_packets, S, d_segments,
+                     max_seg_packets, nullptr, nullptr, nullptr, d_seg_row_off, (hipStream_t)hip_stream, err);
 }
 
 int vsyn_features_device(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P, const vsyn_packet* d_packets, uint32_t S,
@@ -1496,7 +1118,8 @@ int vsyn_features_device(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t
   const bool res_kind = spec->kind == VSYN_FEAT_RESIDUE_YS || spec->kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
   if (!d_segments || (P && (!d_packets || !d_ys || !d_rows || (res_kind && !d_residue)))) return fail(err, VSYN_ERR_INVALID, "NULL batch pointer");
   std::lock_guard<std::mutex> lk(h->mu);
-  return feat_launch(h, spec, P, d_packets, S, d_segments, max_seg_packets, d_ys, d_residue, d_rows, d_seg_row_off, (hipStream_t)hip_stream, err);
+  return feat_launch(h->ft, h->device, h->H, h->host_const.data(), h->d_const, h->d_status, h->unwrap_lds_bytes, spec, P, d_packets, S, d_segments,
+                     max_seg_packets, d_ys, d_residue, d_rows, d_seg_row_off, (hipStream_t)hip_stream, err);
 }
 
 int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P, const vsyn_packet* packets, uint32_t S, const vsyn_segment* segments,
@@ -1512,7 +1135,7 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P
   if (!packets || !segments || !ys || (res_kind && !residue)) return fail(err, VSYN_ERR_INVALID, "NULL batch pointer");
   {  // the checks of the spec first: they need no device
     std::vector<uint8_t> tab;
-    const int rc = feat_build_table(h, spec, tab, err);
+    const int rc = feat_build_table(h->H, h->host_const.data(), spec, tab, err);
     if (rc) return rc;
   }
   const ConstHeader& H = h->H;
@@ -1542,23 +1165,24 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P
   HIPCHK(hipSetDevice(h->device));
   hipStream_t hs = h->host_stream;
   const size_t ys_n = (size_t)P * C * H.ys_stride;
-  HIPCHK(h->fs_pk.ensure(P));
-  HIPCHK(h->fs_seg.ensure(S));
-  HIPCHK(h->fs_ys.ensure(ys_n));
-  HIPCHK(hipMemcpyAsync(h->fs_pk.p, packets, sizeof(vsyn_packet) * P, hipMemcpyHostToDevice, hs));
-  HIPCHK(hipMemcpyAsync(h->fs_seg.p, segments, sizeof(vsyn_segment) * S, hipMemcpyHostToDevice, hs));
-  HIPCHK(hipMemcpyAsync(h->fs_ys.p, ys, sizeof(uint16_t) * ys_n, hipMemcpyHostToDevice, hs));
+  HIPCHK(h->ft.st_pk.ensure(P));
+  HIPCHK(h->ft.st_seg.ensure(S));
+  HIPCHK(h->ft.st_ys.ensure(ys_n));
+  HIPCHK(hipMemcpyAsync(h->ft.st_pk.p, packets, sizeof(vsyn_packet) * P, hipMemcpyHostToDevice, hs));
+  HIPCHK(hipMemcpyAsync(h->ft.st_seg.p, segments, sizeof(vsyn_segment) * S, hipMemcpyHostToDevice, hs));
+  HIPCHK(hipMemcpyAsync(h->ft.st_ys.p, ys, sizeof(uint16_t) * ys_n, hipMemcpyHostToDevice, hs));
   if (res_kind) {
-    HIPCHK(h->fs_res.ensure(residue_floats + 4));
-    HIPCHK(hipMemcpyAsync(h->fs_res.p, residue, sizeof(float) * residue_floats, hipMemcpyHostToDevice, hs));
+    HIPCHK(h->ft.st_res.ensure(residue_floats + 4));
+    HIPCHK(hipMemcpyAsync(h->ft.st_res.p, residue, sizeof(float) * residue_floats, hipMemcpyHostToDevice, hs));
   }
   // rows: every (packet, channel) at most once
   const uint64_t max_rows = (uint64_t)P * C, D = spec->output_dim;
-  HIPCHK(h->fs_rows.ensure(max_rows * D + 1));
-  int rc = feat_launch(h, spec, P, h->fs_pk.p, S, h->fs_seg.p, max_seg, h->fs_ys.p, res_kind ? h->fs_res.p : nullptr, h->fs_rows.p, nullptr, hs, err);
+  HIPCHK(h->ft.st_rows.ensure(max_rows * D + 1));
+  int rc = feat_launch(h->ft, h->device, h->H, h->host_const.data(), h->d_const, h->d_status, h->unwrap_lds_bytes, spec, P, h->ft.st_pk.p, S, h->ft.st_seg.p,
+                       max_seg, h->ft.st_ys.p, res_kind ? h->ft.st_res.p : nullptr, h->ft.st_rows.p, nullptr, hs, err);
   if (rc) return rc;
   std::vector<uint64_t> off((size_t)S + 1);
-  HIPCHK(hipMemcpyAsync(off.data(), h->ft_segoff.p, sizeof(uint64_t) * (S + 1), hipMemcpyDeviceToHost, hs));
+  HIPCHK(hipMemcpyAsync(off.data(), h->ft.segoff.p, sizeof(uint64_t) * (S + 1), hipMemcpyDeviceToHost, hs));
   HIPCHK(hipStreamSynchronize(hs));
   const uint64_t total = off[S];
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = off[g + 1] - off[g];
@@ -1568,193 +1192,11 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec, uint32_t P
   if (!rows) return VSYN_OK;
   if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
   if (total) {
-    HIPCHK(hipMemcpyAsync(rows, h->fs_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipMemcpyAsync(rows, h->ft.st_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
     HIPCHK(hipStreamSynchronize(hs));
   }
   return VSYN_OK;
 }
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// spectral features (vsyn_spectral.h; semantics in the header)
-// ------------------------------------------------------------------------------------------------
-static const uint32_t SPEC_LDS_BUDGET = 160u * 1024u;  // gfx950: 160 KiB of LDS per CU, all of it available to one workgroup
-
-static double spec_hz_to_mel(double f, bool htk) {
-  if (htk) return 2595.0 * log10(1.0 + f / 700.0);
-  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-  return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
-}
-static double spec_mel_to_hz(double m, bool htk) {
-  if (htk) return 700.0 * (pow(10.0, m / 2595.0) - 1.0);
-  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-  return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
-}
-
-static uint32_t spec_dim(const vsyn_spectral_spec* sp) { return sp->kind == VSYN_SPEC_MFCC ? sp->n_mfcc : sp->n_mels; }
-
-// The checks of the spec and of every segment's rate (0 = skipped segment).
-static int spec_check(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const char** err) {
-  if (!sp) return fail(err, VSYN_ERR_INVALID, "spectral spec is NULL");
-  if (sp->kind < VSYN_SPEC_MEL_POWER || sp->kind > VSYN_SPEC_MFCC) return fail(err, VSYN_ERR_INVALID, "unknown spectral kind %u", sp->kind);
-  if (sp->options & ~(VSYN_SPEC_CENTER | VSYN_SPEC_HTK | VSYN_SPEC_NO_NORM)) return fail(err, VSYN_ERR_INVALID, "unknown spectral options 0x%x", sp->options);
-  if (sp->n_fft < 16 || sp->n_fft > 8192) return fail(err, VSYN_ERR_INVALID, "n_fft %u outside [16, 8192]", sp->n_fft);
-  if (sp->hop_length < 1) return fail(err, VSYN_ERR_INVALID, "hop_length must be >= 1");
-  if (sp->win_length < 1 || sp->win_length > sp->n_fft) return fail(err, VSYN_ERR_INVALID, "win_length %u outside [1, n_fft]", sp->win_length);
-  if (sp->n_mels < 1 || sp->n_mels > 256) return fail(err, VSYN_ERR_INVALID, "n_mels %u outside [1, 256]", sp->n_mels);
-  if (sp->kind == VSYN_SPEC_MFCC && (sp->n_mfcc < 1 || sp->n_mfcc > sp->n_mels)) return fail(err, VSYN_ERR_INVALID, "n_mfcc %u outside [1, n_mels]", sp->n_mfcc);
-  if (sp->power != 1 && sp->power != 2) return fail(err, VSYN_ERR_INVALID, "power must be 1 or 2");
-  if (!(sp->fmin >= 0.0) || !(sp->fmax >= 0.0)) return fail(err, VSYN_ERR_INVALID, "fmin / fmax must be >= 0");
-  if (sp->kind == VSYN_SPEC_LOG_MEL && !(sp->log_floor > 0.0)) return fail(err, VSYN_ERR_INVALID, "log_floor must be > 0");
-  if (sp->kind >= VSYN_SPEC_MEL_DB && (!(sp->amin > 0.0) || !(sp->top_db >= 0.0))) return fail(err, VSYN_ERR_INVALID, "amin must be > 0 and top_db >= 0");
-  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
-  for (uint32_t g = 0; g < S; ++g) {
-    if (!rates[g]) continue;
-    const double ny = rates[g] / 2.0, fmax = sp->fmax > 0.0 ? sp->fmax : ny;
-    if (fmax > ny) return fail(err, VSYN_ERR_INVALID, "segment %u: fmax %g above sr/2 = %g", g, fmax, ny);
-    if (!(sp->fmin < fmax)) return fail(err, VSYN_ERR_INVALID, "segment %u: fmin %g not below fmax %g", g, sp->fmin, fmax);
-  }
-  return VSYN_OK;
-}
-
-static uint32_t spec_tile(const vsyn_spectral_spec* sp) {  // frames per STFT workgroup: the most that fit the LDS
-  for (uint32_t ft : {16u, 4u, 1u})
-    if (spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u <= SPEC_LDS_BUDGET) return ft;
-  return 0;
-}
-
-// SpecHeader, twiddles, window, per-rate bands and weights, DCT matrix, per-segment rate index. Call after spec_check.
-static void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, std::vector<uint8_t>& out) {
-  const uint32_t n = sp->n_fft, NM = sp->n_mels, nb = n / 2u + 1u;
-  const bool htk = (sp->options & VSYN_SPEC_HTK) != 0, norm = !(sp->options & VSYN_SPEC_NO_NORM);
-  std::vector<uint32_t> distinct, seg_rate(S, SPEC_SKIP);
-  for (uint32_t g = 0; g < S; ++g) {
-    if (!rates[g]) continue;
-    auto it = std::find(distinct.begin(), distinct.end(), rates[g]);
-    seg_rate[g] = (uint32_t)(it - distinct.begin());
-    if (it == distinct.end()) distinct.push_back(rates[g]);
-  }
-  std::vector<SpecBand> bands;
-  std::vector<float> w;
-  std::vector<double> hz(NM + 2);
-  for (uint32_t sr : distinct) {
-    const double fmax = sp->fmax > 0.0 ? sp->fmax : sr / 2.0;
-    const double m0 = spec_hz_to_mel(sp->fmin, htk), m1 = spec_hz_to_mel(fmax, htk), step = (m1 - m0) / (double)(NM + 1);
-    for (uint32_t i = 0; i < NM + 2; ++i) hz[i] = spec_mel_to_hz(i == NM + 1 ? m1 : m0 + i * step, htk);  // numpy.linspace
-    for (uint32_t m = 0; m < NM; ++m) {
-      const double lo = hz[m], c = hz[m + 1], hi = hz[m + 2], enorm = norm ? 2.0 / (hi - lo) : 1.0;
-      SpecBand b = {0, 0, (uint32_t)w.size(), 0};
-      for (uint32_t k = 0; k < nb; ++k) {
-        const double fk = (double)k * sr / n;
-        const double v = std::max(0.0, std::min((fk - lo) / (c - lo), (hi - fk) / (hi - c))) * enorm;
-        if (v > 0.0) {
-          if (!b.cnt) b.first = k;
-          for (uint32_t z = b.first + b.cnt; z < k; ++z) w.push_back(0.f);  // (a triangle has no holes; kept general)
-          b.cnt = k - b.first + 1;
-          w.push_back((float)v);
-        }
-      }
-      bands.push_back(b);
-    }
-  }
-  SpecHeader T = {};
-  T.kind = sp->kind;
-  T.opts = sp->options;
-  T.n = n;
-  T.hop = sp->hop_length;
-  T.win = sp->win_length;
-  T.woff = (n - sp->win_length) / 2u;
-  T.nbins = nb;
-  T.n_mels = NM;
-  T.dim = spec_dim(sp);
-  T.n_mfcc = sp->kind == VSYN_SPEC_MFCC ? sp->n_mfcc : 0u;
-  T.power = sp->power;
-  T.num_rates = (uint32_t)distinct.size();
-  T.S = S;
-  T.log_floor = (float)sp->log_floor;
-  T.amin = (float)sp->amin;
-  T.top_db = (float)sp->top_db;
-  auto al = [](size_t v) { return (uint32_t)((v + 15) & ~(size_t)15); };
-  T.off_tw = al(sizeof(SpecHeader));
-  T.off_win = al(T.off_tw + 8ull * n);
-  T.off_band = al(T.off_win + 4ull * n);
-  T.off_w = al(T.off_band + sizeof(SpecBand) * bands.size());
-  T.off_dct = al(T.off_w + 4ull * w.size());
-  T.off_rate = al(T.off_dct + 4ull * T.n_mfcc * NM);
-  out.assign(T.off_rate + 4ull * S + 16, 0);
-  memcpy(out.data(), &T, sizeof(T));
-  float* tw = (float*)(out.data() + T.off_tw);
-  for (uint32_t m = 0; m < n; ++m) {
-    const double a = 2.0 * M_PI * (double)m / (double)n;
-    tw[2 * m] = (float)cos(a);
-    tw[2 * m + 1] = (float)sin(a);
-  }
-  float* wn = (float*)(out.data() + T.off_win);
-  for (uint32_t i = 0; i < sp->win_length; ++i) wn[T.woff + i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)sp->win_length));
-  if (!bands.empty()) memcpy(out.data() + T.off_band, bands.data(), sizeof(SpecBand) * bands.size());
-  if (!w.empty()) memcpy(out.data() + T.off_w, w.data(), 4 * w.size());
-  float* dct = (float*)(out.data() + T.off_dct);
-  for (uint32_t i = 0; i < T.n_mfcc; ++i)
-    for (uint32_t m = 0; m < NM; ++m)
-      dct[(size_t)i * NM + m] = (float)(sqrt((i ? 2.0 : 1.0) / NM) * cos(M_PI * (double)i * (2.0 * m + 1.0) / (2.0 * NM)));
-  if (S) memcpy(out.data() + T.off_rate, seg_rate.data(), 4ull * S);
-}
-
-// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s; frames from d_frames, else from si. f_max bounds every
-// segment's STFT frames, rows_bound the total rows. Caller holds h->mu and has run spec_check.
-static int spec_launch(vsyn_handle* h, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
-                       uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
-                       uint64_t* d_segoff, hipStream_t s, const char** err) {
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  const uint32_t ft = spec_tile(sp);
-  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", sp->n_fft, sp->hop_length);
-  std::vector<uint8_t> tab;
-  spec_build_table(sp, S, rates, tab);
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->sp_lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    h->sp_lds_set = true;
-  }
-  HIPCHK(h->sp_segF.ensure(S));
-  HIPCHK(h->sp_segmax.ensure(S));
-  HIPCHK(h->sp_segoff.ensure((size_t)S + 1));
-  if (sp->kind == VSYN_SPEC_MFCC) HIPCHK(h->sp_db.ensure(rows_bound * sp->n_mels + 1));
-  if (int rc = h->sp_tab.upload(tab, s, err)) return rc;
-  SpecCtx A;
-  A.tab = h->sp_tab.dev.p;
-  A.pcm = d_pcm;
-  A.plane = plane;
-  A.C = C;
-  A.S = S;
-  A.frames = d_frames;
-  A.si = si;
-  A.segF = h->sp_segF.p;
-  A.segoff = d_segoff ? d_segoff : h->sp_segoff.p;
-  A.segmax = h->sp_segmax.p;
-  A.rows = d_rows;
-  A.db = sp->kind == VSYN_SPEC_MFCC ? h->sp_db.p : nullptr;
-  hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  if (f_max == 0 || S == 0) return VSYN_OK;
-  const uint64_t gx = (f_max + ft - 1) / ft;
-  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  const size_t lds = spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u;
-  const dim3 grid((uint32_t)gx, S);
-  if (ft == 16) hipLaunchKernelGGL(vsyn_spec_stft_kernel<16>, grid, dim3(SPEC_THREADS), lds, s, A);
-  else if (ft == 4) hipLaunchKernelGGL(vsyn_spec_stft_kernel<4>, grid, dim3(SPEC_THREADS), lds, s, A);
-  else hipLaunchKernelGGL(vsyn_spec_stft_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
-  HIPCHK(hipGetLastError());
-  if (sp->kind >= VSYN_SPEC_MEL_DB) {
-    hipLaunchKernelGGL(vsyn_spec_finish_kernel, dim3((uint32_t)((f_max + SPEC_FIN_ROWS - 1) / SPEC_FIN_ROWS), S), dim3(SPEC_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
-  }
-  return VSYN_OK;
-}
-
-extern "C" {
 
 uint64_t vsyn_spectral_num_frames(const vsyn_spectral_spec* spec, uint64_t frames) {
   if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
@@ -1772,141 +1214,10 @@ int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_
     return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
   const uint64_t f_max = spec_num_frames(spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, plane_stride);
   std::lock_guard<std::mutex> lk(h->mu);
-  return spec_launch(h, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, (uint64_t)S * f_max, d_rows,
+  return spec_launch(h->sp, h->device, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, (uint64_t)S * f_max, d_rows,
                      d_seg_row_off, (hipStream_t)hip_stream, err);
 }
 
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// spectral post-processing (vsyn_spectral_post.h; semantics in the header)
-// ------------------------------------------------------------------------------------------------
-static bool post_on(const vsyn_spectral_post* p) { return p->order != 0 || p->norm != VSYN_POST_NORM_NONE; }
-static bool post_given(const vsyn_spectral_post* p) { return p->norm != VSYN_POST_NORM_NONE && p->stats == VSYN_POST_STATS_GIVEN; }
-
-// The checks of the post spec that need no row counts; the given vectors are read for finiteness only when dout != 0.
-static int post_check(const vsyn_spectral_post* p, const char** err, uint32_t dout = 0) {
-  if (!p) return fail(err, VSYN_ERR_INVALID, "spectral post spec is NULL");
-  if (p->order > 2) return fail(err, VSYN_ERR_INVALID, "delta order %u outside [0, 2]", p->order);
-  if (p->width < 3 || p->width > VSYN_POST_MAX_WIDTH || !(p->width & 1u))
-    return fail(err, VSYN_ERR_INVALID, "delta width %u must be odd and in [3, %u]", p->width, VSYN_POST_MAX_WIDTH);
-  if (p->norm > VSYN_POST_NORM_MEAN_VAR) return fail(err, VSYN_ERR_INVALID, "unknown normalisation %u", p->norm);
-  if (p->stats > VSYN_POST_STATS_GIVEN) return fail(err, VSYN_ERR_INVALID, "unknown statistics source %u", p->stats);
-  if (!(p->std_floor > 0.0) || !std::isfinite(p->std_floor)) return fail(err, VSYN_ERR_INVALID, "std_floor must be finite and > 0");
-  if (post_given(p)) {
-    const bool var = p->norm == VSYN_POST_NORM_MEAN_VAR;
-    if (!p->mean || (var && !p->std)) return fail(err, VSYN_ERR_INVALID, "given statistics: %s is NULL", p->mean ? "std" : "mean");
-    for (uint32_t j = 0; j < dout; ++j)
-      if (!std::isfinite(p->mean[j]) || (var && !std::isfinite(p->std[j])))
-        return fail(err, VSYN_ERR_INVALID, "given statistics: column %u is not finite", j);
-  }
-  return VSYN_OK;
-}
-
-// A segment shorter than the delta window is refused by name.
-static int post_check_rows(const vsyn_spectral_post* p, uint32_t S, const uint64_t* seg_rows, const char** err) {
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  for (uint32_t g = 0; g < S; ++g) {
-    if (seg_rows[g] > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment %u: too many rows", g);
-    if (p->order && seg_rows[g] && seg_rows[g] < p->width)
-      return fail(err, VSYN_ERR_INVALID, "segment %u: delta width %u needs %u frames, segment has %llu", g, p->width, p->width,
-                  (unsigned long long)seg_rows[g]);
-  }
-  return VSYN_OK;
-}
-
-// The stage's kernels on stream s: d_in [rows][D] -> d_out [rows][D * (1 + order)]. Caller holds h->mu, has run post_check (with
-// dout) and post_check_rows, and post_on(p) holds.
-static int post_launch(vsyn_handle* h, const vsyn_spectral_post* p, uint32_t D, uint32_t S, const uint64_t* seg_rows, const float* d_in,
-                       float* d_out, hipStream_t s, const char** err) {
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  const uint32_t W = p->width, Dout = D * (1u + p->order), hh = p->order ? (W - 1u) / 2u : 0u;
-  const bool norm = p->norm != VSYN_POST_NORM_NONE, given = post_given(p), var = p->norm == VSYN_POST_NORM_MEAN_VAR;
-  // table: PostSeg[S] | given mu[Dout], rinv[Dout] (double) | c1[W], c2[W] (float)
-  const size_t off_stat = sizeof(PostSeg) * S, off_coef = off_stat + (given ? 16ull * Dout : 0ull);
-  std::vector<uint8_t> tab(off_coef + 8ull * W);
-  PostSeg* seg = (PostSeg*)tab.data();
-  uint64_t rows = 0, blocks = 0, f_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    seg[g] = PostSeg{rows, blocks, (uint32_t)seg_rows[g], 0u};
-    rows += seg_rows[g];
-    blocks += (seg_rows[g] + POST_BLK - 1u) / POST_BLK;
-    f_max = std::max(f_max, seg_rows[g]);
-  }
-  if (f_max == 0) return VSYN_OK;
-  if (given) {
-    double* st = (double*)(tab.data() + off_stat);
-    for (uint32_t j = 0; j < Dout; ++j) {
-      st[j] = (double)p->mean[j];
-      st[Dout + j] = var ? 1.0 / std::max((double)p->std[j], p->std_floor) : 1.0;
-    }
-  }
-  float* coef = (float*)(tab.data() + off_coef);
-  double S2 = 0, S4 = 0;
-  for (int k = -(int)hh; k <= (int)hh; ++k) {
-    S2 += (double)k * k;
-    S4 += (double)k * k * k * k;
-  }
-  for (uint32_t i = 0; i < W && hh; ++i) {
-    const double k = (double)i - (double)hh;
-    coef[i] = (float)(k / S2);
-    coef[W + i] = (float)(2.0 * (W * k * k - S2) / (W * S4 - S2 * S2));
-  }
-  // the tile: every row group of the workgroup gets a block, at least four blocks, and the LDS image fits
-  const uint32_t G = POST_THREADS / std::min<uint32_t>(Dout, POST_THREADS);
-  uint32_t nb = G * ((4u + G - 1u) / G);
-  const auto lds_of = [&](uint32_t blocks) { return ((size_t)(blocks * POST_BLK + 2u * hh) * D + POST_COEF_FLOATS) * 4u; };
-  while (nb > 1u && lds_of(nb) > SPEC_LDS_BUDGET) --nb;
-  const uint32_t tile = nb * POST_BLK;
-  const size_t lds = lds_of(nb);
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->pp_lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_post_delta_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    h->pp_lds_set = true;
-  }
-  const bool seg_stats = norm && !given;
-  if (seg_stats) {
-    HIPCHK(h->pp_part.ensure(blocks * Dout));
-    HIPCHK(h->pp_stat.ensure(2ull * S * Dout));
-  }
-  if (int rc = h->pp_tab.upload(tab, s, err)) return rc;
-  PostCtx A;
-  A.seg = (const PostSeg*)h->pp_tab.dev.p;
-  A.coef = (const float*)(h->pp_tab.dev.p + off_coef);
-  A.in = d_in;
-  A.out = d_out;
-  A.part = seg_stats ? h->pp_part.p : nullptr;
-  A.mu = given ? (double*)(h->pp_tab.dev.p + off_stat) : h->pp_stat.p;
-  A.rinv = given ? A.mu + Dout : h->pp_stat.p + (size_t)S * Dout;
-  A.stat_stride = given ? 0u : Dout;
-  A.D = D;
-  A.Dout = Dout;
-  A.order = p->order;
-  A.width = W;
-  A.tile = tile;
-  A.std_floor = p->std_floor;
-  const uint64_t gx = (f_max + tile - 1u) / tile;
-  const dim3 grid((uint32_t)gx, S), rgrid((Dout + POST_RED_COLS - 1u) / POST_RED_COLS, S);
-  hipLaunchKernelGGL(vsyn_post_delta_kernel, grid, dim3(POST_THREADS), lds, s, A);
-  HIPCHK(hipGetLastError());
-  if (seg_stats) {
-    hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 0u);
-    HIPCHK(hipGetLastError());
-    if (var) {
-      hipLaunchKernelGGL(vsyn_post_moment_kernel, grid, dim3(POST_THREADS), 0, s, A);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 1u);
-      HIPCHK(hipGetLastError());
-    }
-  }
-  if (norm) {
-    hipLaunchKernelGGL(vsyn_post_norm_kernel, grid, dim3(POST_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
-  }
-  return VSYN_OK;
-}
-
-extern "C" {
 
 uint32_t vsyn_spectral_post_dim(const vsyn_spectral_spec* spec, const vsyn_spectral_post* post) {
   if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK || post_check(post, nullptr) != VSYN_OK) return 0;
@@ -1932,259 +1243,83 @@ int vsyn_spectral_post_device(vsyn_handle* h, const vsyn_spectral_post* post, ui
     if (d_in != d_out) HIPCHK(hipMemcpyAsync(d_out, d_in, sizeof(float) * total * dim, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
     return VSYN_OK;
   }
-  return post_launch(h, post, dim, S, seg_rows, d_in, d_out, (hipStream_t)hip_stream, err);
+  return post_launch(h->pp, h->device, post, dim, S, seg_rows, d_in, d_out, (hipStream_t)hip_stream, err);
 }
 
 }  // extern "C"
 
-// ------------------------------------------------------------------------------------------------
-// resampling (vsyn_resample.h; semantics in the header)
-// ------------------------------------------------------------------------------------------------
-// vsyn_rs_kernel<true> holds one pair's table and one tile's input span in LDS. 80 KiB keeps two of its workgroups on a CU
-// (160 KiB) at worst and takes every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1 and 48 kHz but 11.025 <-> 32 kHz (115 / 122
-// KiB); 44.1 -> 16 kHz needs 46 KiB. Bigger tables (11.025 <-> 32 kHz; 44056 -> 16000 = 2000 / 5507, 448 KiB) use
-// vsyn_rs_kernel<false>.
-static const uint32_t RS_LDS_BUDGET = 80u * 1024u;
 
-// The reduced ratio of a pair; false for a pair the contract refuses (a rate of 0, or M above VSYN_RESAMPLE_MAX_M).
-static bool rs_ratio(uint32_t r_in, uint32_t r_out, uint32_t* up, uint32_t* down) {
-  if (!r_in || !r_out) return false;
-  const uint32_t g = std::gcd(r_in, r_out);
-  *up = r_out / g;
-  *down = r_in / g;
-  return std::max(*up, *down) <= VSYN_RESAMPLE_MAX_M;
-}
-
-static double rs_i0(double x) {  // modified Bessel function of the first kind, order 0: sum_k ((x/2)^k / k!)^2
-  const double q = 0.25 * x * x;
-  double s = 1.0, t = 1.0;
-  for (int k = 1; k < 500; ++k) {
-    t *= q / ((double)k * (double)k);
-    s += t;
-    if (t < 1e-17 * s) break;
-  }
-  return s;
-}
-
-// h[0 .. N) of the header's step 2, in double.
-static void rs_taps(uint32_t up, uint32_t down, std::vector<double>& h) {
-  const uint32_t M = std::max(up, down), H = 10u * M, N = 2u * H + 1u;
-  h.assign(N, 0.0);
-  const double i0b = rs_i0(5.0);
-  double S = 0.0;
-  for (uint32_t n = 0; n < N; ++n) {
-    const double m = (double)n - (double)H, xs = M_PI * m / (double)M, r = 2.0 * n / (double)(N - 1u) - 1.0;
-    const double sinc = m == 0.0 ? 1.0 : sin(xs) / xs;
-    h[n] = rs_i0(5.0 * sqrt(std::max(0.0, 1.0 - r * r))) / i0b * sinc;
-    S += h[n];
-  }
-  for (uint32_t n = 0; n < N; ++n) h[n] = up * h[n] / S;
-}
-
-struct RsPlan {
-  std::vector<uint8_t> tab;
-  uint64_t chunks[2] = {0, 0};  // grid bounds of vsyn_rs_kernel<true> / <false>
-  uint32_t lds_bytes = 0;       // dynamic LDS of vsyn_rs_kernel<true>
+// The stages chained behind the last host submit. The PCM the next stage reads: planar [S][C][plane]; each segment's frames from d_frames, else from si.
+struct PcmView {
+  const float* pcm;
+  uint64_t plane;
+  uint32_t C;
+  const SegInfo* si;
+  const uint32_t* d_frames;
 };
 
-// RsHeader, RsPair per distinct pair, seg_pair[S], the polyphase tables. rates[g] = 0 skips g; every other pair is valid (checked
-// by the caller). plane bounds every segment's input frames.
-static void rs_build_table(uint32_t S, const uint32_t* rates, uint32_t out_rate, uint32_t C, uint64_t plane, RsPlan& plan) {
-  std::vector<uint32_t> seg_pair(S, RS_SKIP), keys;
-  std::vector<RsPair> pairs;
-  uint64_t taps = 0;
-  const uint64_t T_max = std::min<uint64_t>(plane, 0xFFFFFFFFull);
-  for (uint32_t g = 0; g < S; ++g) {
-    if (!rates[g]) continue;
-    auto it = std::find(keys.begin(), keys.end(), rates[g]);
-    seg_pair[g] = (uint32_t)(it - keys.begin());
-    if (it == keys.end()) {
-      keys.push_back(rates[g]);
-      RsPair p = {};
-      rs_ratio(rates[g], out_rate, &p.up, &p.down);
-      p.lds = 1;
-      if (p.up != p.down) {
-        const uint32_t M = std::max(p.up, p.down), N = 20u * M + 1u, K = (N + p.up - 1u) / p.up;
-        p.h = 10u * M;
-        p.k4 = (K + 3u) & ~3u;
-        p.span4 = rs_span4(p.up, p.down, p.k4);
-        p.tab = taps;
-        taps += (uint64_t)p.up * p.k4;
-        const uint64_t lds = 4ull * ((uint64_t)p.up * p.k4 + 4ull * p.span4);
-        p.lds = lds <= RS_LDS_BUDGET;
-        if (p.lds) plan.lds_bytes = std::max(plan.lds_bytes, (uint32_t)lds);
-      }
-      pairs.push_back(p);
-    }
-    const RsPair& p = pairs[seg_pair[g]];
-    plan.chunks[p.lds ? 0 : 1] += (uint64_t)C * ((rs_num_frames(T_max, p.up, p.down) + RS_CHUNK - 1u) / RS_CHUNK);
-  }
-  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  RsHeader hd = {(uint32_t)pairs.size(), S, 0, 0};
-  const size_t off_pairs = sizeof(RsHeader);
-  hd.off_seg = (uint32_t)al(off_pairs + sizeof(RsPair) * pairs.size());
-  const size_t off_taps = al(hd.off_seg + 4ull * S);
-  for (RsPair& p : pairs) p.tab += off_taps / 4u;
-  plan.tab.assign(off_taps + 4ull * taps + 16, 0);
-  uint8_t* o = plan.tab.data();
-  memcpy(o, &hd, sizeof(hd));
-  if (!pairs.empty()) memcpy(o + off_pairs, pairs.data(), sizeof(RsPair) * pairs.size());
-  if (S) memcpy(o + hd.off_seg, seg_pair.data(), 4ull * S);
-  std::vector<double> h;
-  for (const RsPair& p : pairs) {
-    if (p.up == p.down) continue;
-    rs_taps(p.up, p.down, h);
-    float* P = (float*)o + p.tab;
-    for (uint32_t phi = 0; phi < p.up; ++phi)
-      for (uint32_t t = 0; t < p.k4; ++t) {
-        const uint64_t n = phi + (uint64_t)t * p.up;
-        P[(size_t)phi * p.k4 + t] = n < h.size() ? (float)h[n] : 0.0f;
-      }
-  }
-}
-
-// The checks of every segment's pair (0 = skipped segment).
-static int rs_check(uint32_t S, const uint32_t* rates, uint32_t out_rate, const char** err) {
-  if (!out_rate) return fail(err, VSYN_ERR_INVALID, "out_rate must be >= 1");
-  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "in_rates is NULL");
-  for (uint32_t g = 0; g < S; ++g) {
-    uint32_t up, down;
-    if (rates[g] && !rs_ratio(rates[g], out_rate, &up, &down))
-      return fail(err, VSYN_ERR_INVALID, "segment %u: %u -> %u Hz reduces to %u / %u, above the limit max(up, down) <= %u", g, rates[g],
-                  out_rate, up, down, VSYN_RESAMPLE_MAX_M);
-  }
-  return VSYN_OK;
-}
-
-// Offsets and resample kernels on stream s; frames from d_frames, else from si. Caller holds h->mu and has run rs_check, and
-// out_plane holds every segment's T_out.
-static int rs_launch(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, const float* d_pcm, uint64_t plane, uint32_t C,
-                     const uint32_t* d_frames, const SegInfo* si, float* d_out, uint64_t out_plane, uint32_t* d_out_frames, hipStream_t s,
-                     const char** err) {
-  RsPlan plan;
-  rs_build_table(S, rates, out_rate, C, plane, plan);
-  if (plan.chunks[0] > 0x7FFFFFFFull || plan.chunks[1] > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too much output for one call");
-  HIPCHK(hipSetDevice(h->device));
-  if (!h->rs_lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_rs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_LDS_BUDGET));
-    h->rs_lds_set = true;
-  }
-  const std::vector<uint8_t>& tab = plan.tab;
-  HIPCHK(h->rs_inF.ensure(S));
-  HIPCHK(h->rs_outF.ensure(S));
-  HIPCHK(h->rs_off.ensure(2ull * S + 2));
-  if (int rc = h->rs_tab.upload(tab, s, err)) return rc;
-  RsCtx A;
-  A.tab = h->rs_tab.dev.p;
-  A.pcm = d_pcm;
-  A.plane = plane;
-  A.C = C;
-  A.S = S;
-  A.frames = d_frames;
-  A.si = si;
-  A.out = d_out;
-  A.out_plane = out_plane;
-  A.in_frames = h->rs_inF.p;
-  A.out_frames = d_out_frames ? d_out_frames : h->rs_outF.p;
-  A.off = h->rs_off.p;
-  hipLaunchKernelGGL(vsyn_rs_offsets_kernel, dim3(1), dim3(RS_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  if (plan.chunks[0]) {
-    hipLaunchKernelGGL(vsyn_rs_kernel<true>, dim3((uint32_t)plan.chunks[0]), dim3(RS_THREADS), plan.lds_bytes, s, A);
-    HIPCHK(hipGetLastError());
-  }
-  if (plan.chunks[1]) {
-    hipLaunchKernelGGL(vsyn_rs_kernel<false>, dim3((uint32_t)plan.chunks[1]), dim3(RS_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
-  }
-  return VSYN_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// PCM conditioning (vsyn_condition.h; semantics in the header)
-// ------------------------------------------------------------------------------------------------
-static int cond_check(const vsyn_pcm_cond* c, const char** err) {
-  if (!c) return fail(err, VSYN_ERR_INVALID, "PCM conditioning spec is NULL");
-  if (c->options & ~(VSYN_COND_PEAK | VSYN_COND_PREEMPH)) return fail(err, VSYN_ERR_INVALID, "unknown conditioning options 0x%x", c->options);
-  if (c->options & VSYN_COND_PREEMPH) {
-    const double a = c->preemphasis;
-    if (!std::isfinite(a) || !(a > 0.0 && a < 1.0) || !((float)a > 0.0f && (float)a < 1.0f))
-      return fail(err, VSYN_ERR_INVALID, "pre-emphasis coefficient %g outside (0, 1)", a);
-  }
-  return VSYN_OK;
-}
-
-// A NULL handle: without a usable device there is nothing to make one from, and that is what the caller has to hear.
-static int cond_no_handle(const char** err) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(err, VSYN_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
-  return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-}
-
-// The stage's kernels on stream s: frames from d_frames, else from si; t_max bounds every segment's frames. d_peak [S] (uint32
-// view of the float peaks; NULL: the handle's) is cleared and filled with VSYN_COND_PEAK only. The frames written go to
-// h->cd_frames. Caller holds h->mu and has run cond_check.
-static int cond_launch(vsyn_handle* h, const vsyn_pcm_cond* c, uint32_t S, const float* d_pcm, uint64_t plane, uint32_t C,
-                       const uint32_t* d_frames, const SegInfo* si, uint64_t t_max, float* d_out, uint64_t out_plane, uint32_t* d_peak,
-                       hipStream_t s, const char** err) {
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_out & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM pointers must be 4-byte aligned");
-  const uint64_t gx = (std::min(std::min(t_max, plane), out_plane) + 3u + COND_TILE - 1u) / COND_TILE;
-  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(h->cd_frames.ensure(S));
-  const bool peak = (c->options & VSYN_COND_PEAK) != 0;
-  if (peak && !d_peak) {
-    HIPCHK(h->cd_peak.ensure(S));
-    d_peak = h->cd_peak.p;
-  }
-  CondCtx A;
-  A.pcm = d_pcm;
-  A.plane = plane;
-  A.C = C;
-  A.S = S;
-  A.frames = d_frames;
-  A.si = si;
-  A.out = d_out;
-  A.out_plane = out_plane;
-  A.peak = peak ? d_peak : nullptr;
-  A.out_frames = h->cd_frames.p;
-  A.opts = c->options;
-  A.a = (c->options & VSYN_COND_PREEMPH) ? (float)c->preemphasis : 0.0f;
-  const dim3 grid((uint32_t)gx, S);
-  if (peak) {
-    HIPCHK(hipMemsetAsync(d_peak, 0, sizeof(uint32_t) * S, s));
-    hipLaunchKernelGGL(vsyn_cond_peak_kernel, grid, dim3(COND_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(vsyn_cond_apply_kernel, grid, dim3(COND_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  return VSYN_OK;
-}
-
-// peaks_out[S] (may be NULL) from the handle's peak words behind the kernels on stream s; zeros without VSYN_COND_PEAK.
-static int cond_fetch_peaks(vsyn_handle* h, const vsyn_pcm_cond* c, uint32_t S, float* peaks_out, hipStream_t s, const char** err) {
-  if (!peaks_out || !S) return VSYN_OK;
-  if (c->options & VSYN_COND_PEAK) HIPCHK(hipMemcpyAsync(peaks_out, h->cd_peak.p, sizeof(float) * S, hipMemcpyDeviceToHost, s));
-  else memset(peaks_out, 0, sizeof(float) * S);
-  return VSYN_OK;
-}
-
-// The last host submit's frames per segment: SegInfo::total_emit clamped to its plane; with out_rate != 0, what segment g has once
-// resampled from rates[g] to out_rate (0 for rates[g] = 0; the caller has run rs_check). Caller holds h->mu.
-static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, std::vector<uint64_t>& T, const char** err) {
+// The last host submit's frames per segment into T[S], their maximum into *t_max: SegInfo::total_emit clamped to its plane; with
+// out_rate != 0, what segment g has once resampled from rates[g] to out_rate (0 for rates[g] = 0; the caller has run rs_check).
+// Caller holds h->mu.
+static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, uint64_t* T, uint64_t* t_max, const char** err) {
   if (h->last_S == 0 || h->last_host_plane == 0) return fail(err, VSYN_ERR_INVALID, "no vsyn_submit_host on this handle yet");
   if (S != h->last_S) return fail(err, VSYN_ERR_INVALID, "num_segments %u differs from the last submit's %u", S, h->last_S);
   HIPCHK(hipSetDevice(h->device));
   std::vector<SegInfo> si(S);
   HIPCHK(hipMemcpyAsync(si.data(), h->ws_seg[h->last_wb].p, sizeof(SegInfo) * S, hipMemcpyDeviceToHost, h->host_stream));
   HIPCHK(hipStreamSynchronize(h->host_stream));
-  T.resize(S);
+  *t_max = 0;
   for (uint32_t g = 0; g < S; ++g) {
     T[g] = std::min<uint64_t>(si[g].total_emit, h->last_host_plane);
     uint32_t up, down;
     if (out_rate) T[g] = rates[g] && rs_ratio(rates[g], out_rate, &up, &down) ? rs_num_frames(T[g], up, down) : 0;
+    *t_max = std::max(*t_max, T[g]);
   }
+  return VSYN_OK;
+}
+
+// The chain on the host stream, from the last host submit's PCM to *v: with out_rate != 0 every segment resampled from rates[g] to
+// out_rate into h->rs's plane of rs_plane frames; with cond != NULL conditioned into h->cd's mono plane of cd_plane frames, the peaks
+// on their way to peaks_out. t_max bounds every segment's frames; zero clears the last plane first: zeros past each segment's
+// frames. Caller holds h->mu and has run rs_check / cond_check; its checks of its own buffers sit between last_submit_frames and this.
+static int pcm_chain(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, uint64_t rs_plane, const vsyn_pcm_cond* cond,
+                     uint64_t cd_plane, uint64_t t_max, bool zero, float* peaks_out, PcmView* v, const char** err) {
+  const uint32_t C = h->H.channels;
+  hipStream_t hs = h->host_stream;
+  *v = PcmView{h->st_pcm.p, h->last_host_plane, C, h->ws_seg[h->last_wb].p, nullptr};
+  if (out_rate) {
+    const size_t n = (size_t)S * C * rs_plane;
+    HIPCHK(h->rs.pcm.ensure(n + 1));
+    if (zero && !cond) HIPCHK(hipMemsetAsync(h->rs.pcm.p, 0, sizeof(float) * n, hs));
+    if (int rc = rs_launch(h->rs, h->device, S, rates, out_rate, v->pcm, v->plane, C, nullptr, v->si, h->rs.pcm.p, rs_plane, nullptr, hs, err)) return rc;
+    *v = PcmView{h->rs.pcm.p, rs_plane, C, nullptr, h->rs.outF.p};
+  }
+  if (cond) {  // the next stage reads the conditioned mono plane as 1-channel PCM, with the frames the stage wrote
+    const size_t n = (size_t)S * cd_plane;
+    HIPCHK(h->cd.pcm.ensure(n + 1));
+    if (zero) HIPCHK(hipMemsetAsync(h->cd.pcm.p, 0, sizeof(float) * n, hs));
+    if (int rc = cond_launch(h->cd, h->device, cond, S, v->pcm, v->plane, C, v->d_frames, v->si, t_max, h->cd.pcm.p, cd_plane, nullptr, hs, err)) return rc;
+    if (int rc = cond_fetch_peaks(h->cd, cond, S, peaks_out, hs, err)) return rc;
+    *v = PcmView{h->cd.pcm.p, cd_plane, 1u, nullptr, h->cd.frames.p};
+  }
+  return VSYN_OK;
+}
+
+// The end of a PCM host form: the view's planes to out as they are (VSYN_PCM_F32: the chain cleared them first), or interleaved
+// and converted into s16 (vsyn_pcm_interleave_device's conversion, zeros past each segment's frames) and that; then the call's one wait.
+static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format, DevBuf<int16_t>& s16, void* out, const char** err) {
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * v.C * v.plane;
+  if (format == VSYN_PCM_F32) {
+    HIPCHK(hipMemcpyAsync(out, v.pcm, sizeof(float) * n, hipMemcpyDeviceToHost, hs));
+  } else {
+    HIPCHK(s16.ensure(n + 1));
+    const dim3 grid((uint32_t)((v.plane + 255) / 256), S);
+    hipLaunchKernelGGL(vsyn_rs_s16_kernel, grid, dim3(256), 0, hs, v.pcm, v.plane, v.C, v.d_frames, s16.p, v.plane);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, s16.p, sizeof(int16_t) * n, hipMemcpyDeviceToHost, hs));
+  }
+  HIPCHK(hipStreamSynchronize(hs));
   return VSYN_OK;
 }
 
@@ -2220,17 +1355,17 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
   // the lock covers the whole call: the spectral, resample and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
-  std::vector<uint64_t> T;
-  rc = last_submit_frames(h, S, rates, out_rate, T, err);
+  std::vector<uint64_t> T(S);
+  uint64_t total = 0, f_max = 0, t_max;
+  rc = last_submit_frames(h, S, rates, out_rate, T.data(), &t_max, err);
   if (rc) return rc;
+  t_max = std::max<uint64_t>(t_max, 1);
   const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
-  uint64_t total = 0, f_max = 0, t_max = 1;
   for (uint32_t g = 0; g < S; ++g) {
     const uint64_t f = spec_rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, center, T[g]) : 0;
     seg_rows[g] = f;
     total += f;
     f_max = std::max(f_max, f);
-    t_max = std::max(t_max, T[g]);
   }
   if (post) {
     rc = post_check_rows(post, S, seg_rows, err);
@@ -2238,48 +1373,23 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   }
   if (!rows || total == 0) return VSYN_OK;
   if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
-  const uint32_t C = h->H.channels;
+  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
   hipStream_t hs = h->host_stream;
-  // the spectral pass reads the synthesis PCM with the last submit's SegInfo, or the resampled PCM with its frames
-  const float* pcm = h->st_pcm.p;
-  uint64_t plane = h->last_host_plane;
-  const SegInfo* si = h->ws_seg[h->last_wb].p;
-  const uint32_t* d_frames = nullptr;
-  if (out_rate) {
-    if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
-    HIPCHK(h->rs_pcm.ensure((size_t)S * C * t_max + 1));
-    rc = rs_launch(h, S, rates, out_rate, pcm, plane, C, nullptr, si, h->rs_pcm.p, t_max, h->rs_outF.p, hs, err);
-    if (rc) return rc;
-    pcm = h->rs_pcm.p;
-    plane = t_max;
-    si = nullptr;
-    d_frames = h->rs_outF.p;
-  }
-  uint32_t spec_C = C;
-  if (cond) {  // the spectral pass reads the conditioned mono plane as 1-channel PCM, with the frames the stage wrote
-    HIPCHK(h->cd_pcm.ensure((size_t)S * t_max + 1));
-    rc = cond_launch(h, cond, S, pcm, plane, C, d_frames, si, t_max, h->cd_pcm.p, t_max, nullptr, hs, err);
-    if (rc) return rc;
-    rc = cond_fetch_peaks(h, cond, S, peaks_out, hs, err);
-    if (rc) return rc;
-    pcm = h->cd_pcm.p;
-    plane = t_max;
-    si = nullptr;
-    d_frames = h->cd_frames.p;
-    spec_C = 1;
-  }
+  PcmView v;  // the spectral pass reads the synthesis PCM with the last submit's SegInfo, or what the chain made of it
+  rc = pcm_chain(h, S, rates, out_rate, t_max, cond, t_max, t_max, false, peaks_out, &v, err);
+  if (rc) return rc;
   const uint64_t D = spec_dim(spec);
-  HIPCHK(h->sp_rows.ensure(total * D + 1));
-  rc = spec_launch(h, spec, S, spec_rates, pcm, plane, spec_C, d_frames, si, f_max, total, h->sp_rows.p, nullptr, hs, err);
+  HIPCHK(h->sp.rows.ensure(total * D + 1));
+  rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err);
   if (rc) return rc;
   if (post) {  // the rows go on to the post stage in their place, and its wider rows come back
     const uint64_t Dout = D * (1u + post->order);
-    HIPCHK(h->pp_rows.ensure(total * Dout + 1));
-    rc = post_launch(h, post, (uint32_t)D, S, seg_rows, h->sp_rows.p, h->pp_rows.p, hs, err);
+    HIPCHK(h->pp.rows.ensure(total * Dout + 1));
+    rc = post_launch(h->pp, h->device, post, (uint32_t)D, S, seg_rows, h->sp.rows.p, h->pp.rows.p, hs, err);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(rows, h->pp_rows.p, sizeof(float) * total * Dout, hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipMemcpyAsync(rows, h->pp.rows.p, sizeof(float) * total * Dout, hipMemcpyDeviceToHost, hs));
   } else {
-    HIPCHK(hipMemcpyAsync(rows, h->sp_rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipMemcpyAsync(rows, h->sp.rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
   }
   return sync_status_into(h, status, err);
 }
@@ -2312,7 +1422,7 @@ int vsyn_resample_device(vsyn_handle* h, uint32_t S, const uint32_t* in_rates, u
                   (unsigned long long)need);
   }
   std::lock_guard<std::mutex> lk(h->mu);
-  return rs_launch(h, S, in_rates, out_rate, d_pcm, plane_stride, channels, d_frames, nullptr, d_out, out_plane_stride, d_out_frames,
+  return rs_launch(h->rs, h->device, S, in_rates, out_rate, d_pcm, plane_stride, channels, d_frames, nullptr, d_out, out_plane_stride, d_out_frames,
                    (hipStream_t)hip_stream, err);
 }
 
@@ -2325,37 +1435,17 @@ int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates,
   if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
   // the lock covers the whole call: the resample workspace is the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
-  std::vector<uint64_t> T_out;
-  rc = last_submit_frames(h, S, in_rates, out_rate, T_out, err);
+  uint64_t t_max;
+  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
   if (rc) return rc;
-  uint64_t t_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    frames_out[g] = T_out[g];
-    t_max = std::max(t_max, T_out[g]);
-  }
   if (!out || S == 0) return VSYN_OK;
   if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
                                              (unsigned long long)out_stride_frames, (unsigned long long)t_max);
   if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
-  const uint32_t C = h->H.channels;
-  hipStream_t hs = h->host_stream;
-  const size_t n = (size_t)S * C * out_stride_frames;
-  HIPCHK(h->rs_pcm.ensure(n + 1));
-  if (format == VSYN_PCM_F32) HIPCHK(hipMemsetAsync(h->rs_pcm.p, 0, sizeof(float) * n, hs));  // zeros past each segment's T_out
-  rc = rs_launch(h, S, in_rates, out_rate, h->st_pcm.p, h->last_host_plane, C, nullptr, h->ws_seg[h->last_wb].p, h->rs_pcm.p,
-                 out_stride_frames, h->rs_outF.p, hs, err);
+  PcmView v;
+  rc = pcm_chain(h, S, in_rates, out_rate, out_stride_frames, nullptr, 0, t_max, format == VSYN_PCM_F32, nullptr, &v, err);
   if (rc) return rc;
-  if (format == VSYN_PCM_F32) {
-    HIPCHK(hipMemcpyAsync(out, h->rs_pcm.p, sizeof(float) * n, hipMemcpyDeviceToHost, hs));
-  } else {
-    HIPCHK(h->rs_s16.ensure(n + 1));
-    const dim3 grid((uint32_t)((out_stride_frames + 255) / 256), S);
-    hipLaunchKernelGGL(vsyn_rs_s16_kernel, grid, dim3(256), 0, hs, h->rs_pcm.p, out_stride_frames, C, h->rs_outF.p, h->rs_s16.p, out_stride_frames);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, h->rs_s16.p, sizeof(int16_t) * n, hipMemcpyDeviceToHost, hs));
-  }
-  HIPCHK(hipStreamSynchronize(hs));
-  return VSYN_OK;
+  return pcm_copy_out(h, v, S, format, h->rs.s16, out, err);
 }
 
 int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
@@ -2398,7 +1488,7 @@ int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_
     return fail(err, VSYN_ERR_INVALID, "NULL pointer or zero stride");
   if (plane_stride > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
   std::lock_guard<std::mutex> lk(h->mu);
-  return cond_launch(h, cond, S, d_pcm, plane_stride, channels, d_frames, nullptr, plane_stride, d_out, out_plane_stride, (uint32_t*)d_peaks,
+  return cond_launch(h->cd, h->device, cond, S, d_pcm, plane_stride, channels, d_frames, nullptr, plane_stride, d_out, out_plane_stride, (uint32_t*)d_peaks,
                      (hipStream_t)hip_stream, err);
 }
 
@@ -2416,52 +1506,17 @@ int vsyn_pcm_condition_host(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t 
   if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
   // the lock covers the whole call: the resample and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
-  std::vector<uint64_t> T;
-  rc = last_submit_frames(h, S, in_rates, out_rate, T, err);
+  uint64_t t_max;
+  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
   if (rc) return rc;
-  uint64_t t_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    frames_out[g] = T[g];
-    t_max = std::max(t_max, T[g]);
-  }
   if (!out || S == 0) return VSYN_OK;
   if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
                                              (unsigned long long)out_stride_frames, (unsigned long long)t_max);
   if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
-  const uint32_t C = h->H.channels;
-  hipStream_t hs = h->host_stream;
-  const float* pcm = h->st_pcm.p;
-  uint64_t plane = h->last_host_plane;
-  const SegInfo* si = h->ws_seg[h->last_wb].p;
-  const uint32_t* d_frames = nullptr;
-  if (out_rate) {
-    const uint64_t rs_plane = std::max<uint64_t>(t_max, 1);
-    HIPCHK(h->rs_pcm.ensure((size_t)S * C * rs_plane + 1));
-    rc = rs_launch(h, S, in_rates, out_rate, pcm, plane, C, nullptr, si, h->rs_pcm.p, rs_plane, h->rs_outF.p, hs, err);
-    if (rc) return rc;
-    pcm = h->rs_pcm.p;
-    plane = rs_plane;
-    si = nullptr;
-    d_frames = h->rs_outF.p;
-  }
-  const size_t n = (size_t)S * out_stride_frames;
-  HIPCHK(h->cd_pcm.ensure(n + 1));
-  if (format == VSYN_PCM_F32) HIPCHK(hipMemsetAsync(h->cd_pcm.p, 0, sizeof(float) * n, hs));  // zeros past each segment's T
-  rc = cond_launch(h, cond, S, pcm, plane, C, d_frames, si, t_max, h->cd_pcm.p, out_stride_frames, nullptr, hs, err);
+  PcmView v;  // resampled into a plane as long as the longest segment, conditioned into the caller's stride
+  rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err);
   if (rc) return rc;
-  rc = cond_fetch_peaks(h, cond, S, peaks_out, hs, err);
-  if (rc) return rc;
-  if (format == VSYN_PCM_F32) {
-    HIPCHK(hipMemcpyAsync(out, h->cd_pcm.p, sizeof(float) * n, hipMemcpyDeviceToHost, hs));
-  } else {  // one channel: planar is interleaved, and the conversion is vsyn_pcm_interleave_device's (pcm_s16)
-    HIPCHK(h->cd_s16.ensure(n + 1));
-    const dim3 grid((uint32_t)((out_stride_frames + 255) / 256), S);
-    hipLaunchKernelGGL(vsyn_rs_s16_kernel, grid, dim3(256), 0, hs, h->cd_pcm.p, out_stride_frames, 1u, h->cd_frames.p, h->cd_s16.p, out_stride_frames);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, h->cd_s16.p, sizeof(int16_t) * n, hipMemcpyDeviceToHost, hs));
-  }
-  HIPCHK(hipStreamSynchronize(hs));
-  return VSYN_OK;
+  return pcm_copy_out(h, v, S, format, h->cd.s16, out, err);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_host.h"
 
 #define COND_THREADS 256
 #define COND_PER_THREAD 4
@@ -176,4 +177,80 @@ __global__ void __launch_bounds__(COND_THREADS) vsyn_cond_apply_kernel(const Con
       z[t] = r;
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct CondWs {  // the stage's buffers: its own; the PCM is only read
+  DevBuf<float> pcm;                   // host forms: the conditioned mono planes
+  DevBuf<uint32_t> peak, frames;       // per segment: max |bits| of the downmix; frames written
+  DevBuf<int16_t> s16;                 // vsyn_pcm_condition_host, VSYN_PCM_S16
+};
+
+static inline int cond_check(const vsyn_pcm_cond* c, const char** err) {
+  if (!c) return fail(err, VSYN_ERR_INVALID, "PCM conditioning spec is NULL");
+  if (c->options & ~(VSYN_COND_PEAK | VSYN_COND_PREEMPH)) return fail(err, VSYN_ERR_INVALID, "unknown conditioning options 0x%x", c->options);
+  if (c->options & VSYN_COND_PREEMPH) {
+    const double a = c->preemphasis;
+    if (!std::isfinite(a) || !(a > 0.0 && a < 1.0) || !((float)a > 0.0f && (float)a < 1.0f))
+      return fail(err, VSYN_ERR_INVALID, "pre-emphasis coefficient %g outside (0, 1)", a);
+  }
+  return VSYN_OK;
+}
+
+// A NULL handle: without a usable device there is nothing to make one from, and that is what the caller has to hear.
+static inline int cond_no_handle(const char** err) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(err, VSYN_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
+  return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+}
+
+// The stage's kernels on stream s: frames from d_frames, else from si; t_max bounds every segment's frames. d_peak [S] (uint32
+// view of the float peaks; NULL: ws.peak) is cleared and filled with VSYN_COND_PEAK only. The frames written go to
+// ws.frames. Caller holds the handle's lock and has run cond_check.
+static inline int cond_launch(CondWs& ws, int device, const vsyn_pcm_cond* c, uint32_t S, const float* d_pcm, uint64_t plane, uint32_t C,
+                       const uint32_t* d_frames, const SegInfo* si, uint64_t t_max, float* d_out, uint64_t out_plane, uint32_t* d_peak,
+                       hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_out & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM pointers must be 4-byte aligned");
+  const uint64_t gx = (std::min(std::min(t_max, plane), out_plane) + 3u + COND_TILE - 1u) / COND_TILE;
+  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(ws.frames.ensure(S));
+  const bool peak = (c->options & VSYN_COND_PEAK) != 0;
+  if (peak && !d_peak) {
+    HIPCHK(ws.peak.ensure(S));
+    d_peak = ws.peak.p;
+  }
+  CondCtx A;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.out = d_out;
+  A.out_plane = out_plane;
+  A.peak = peak ? d_peak : nullptr;
+  A.out_frames = ws.frames.p;
+  A.opts = c->options;
+  A.a = (c->options & VSYN_COND_PREEMPH) ? (float)c->preemphasis : 0.0f;
+  const dim3 grid((uint32_t)gx, S);
+  if (peak) {
+    HIPCHK(hipMemsetAsync(d_peak, 0, sizeof(uint32_t) * S, s));
+    hipLaunchKernelGGL(vsyn_cond_peak_kernel, grid, dim3(COND_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(vsyn_cond_apply_kernel, grid, dim3(COND_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}
+
+// peaks_out[S] (may be NULL) from the workspace's peak words behind the kernels on stream s; zeros without VSYN_COND_PEAK.
+static inline int cond_fetch_peaks(const CondWs& ws, const vsyn_pcm_cond* c, uint32_t S, float* peaks_out, hipStream_t s, const char** err) {
+  if (!peaks_out || !S) return VSYN_OK;
+  if (c->options & VSYN_COND_PEAK) HIPCHK(hipMemcpyAsync(peaks_out, ws.peak.p, sizeof(float) * S, hipMemcpyDeviceToHost, s));
+  else memset(peaks_out, 0, sizeof(float) * S);
+  return VSYN_OK;
 }

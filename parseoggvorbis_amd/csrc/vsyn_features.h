@@ -15,6 +15,7 @@
 //                                residue at the gathered bins.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_host.h"
 #include "vsyn_staged.h"
 
 // Per-floor gather table, built on the host per call (vorbis_synth_hip.hip, feat_build_table) and read by the rows kernel.
@@ -269,4 +270,180 @@ __global__ void __launch_bounds__(FEAT_ROW_WAVES * 64) vsyn_feat_rows_kernel(con
     }
     out[j] = v;
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct FeatureWs {  // the stage's buffers: its own, so that a features call leaves every synthesis buffer alone
+  DevBuf<PktInfo> info;
+  DevBuf<uint16_t> fy;
+  DevBuf<uint32_t> rowrel;
+  DevBuf<int32_t> fbsrc;
+  DevBuf<uint8_t> fbch;
+  DevBuf<uint64_t> resoff, segrows, segoff;
+  TableUpload tab;                     // the gather table
+  DevBuf<vsyn_packet> st_pk;           // vsyn_features_host staging
+  DevBuf<vsyn_segment> st_seg;
+  DevBuf<uint16_t> st_ys;
+  DevBuf<float> st_res, st_rows;
+};
+
+// scipy.ndimage.zoom(xs as float32, z, order=1, mode="nearest") followed by numpy.round: output length round(L * z) (Python's round);
+// input coordinate k * (L - 1) / (out - 1) in double, clamped to [0, L - 1]; linear weights (1 - t, t) summed in double from 0 in
+// that order; the float32 result rounded half to even. False where the reference's assert (length == L * z) fails.
+static inline bool feat_zoom_round(const std::vector<uint32_t>& xs, double z, std::vector<uint32_t>& out) {
+  const size_t L = xs.size();
+  const double want = (double)L * z;
+  const double outn_d = nearbyint(want);
+  if (outn_d != want || outn_d < 1.0 || outn_d > 1e6) return false;
+  const size_t outn = (size_t)outn_d;
+  const double zf = outn > 1 ? (double)(L - 1) / (double)(outn - 1) : 1.0;
+  out.resize(outn);
+  for (size_t k = 0; k < outn; ++k) {
+    double cc = (double)k * zf;
+    cc = std::min(std::max(cc, 0.0), (double)(L - 1));
+    const double fl = floor(cc), t = cc - fl;
+    const size_t i0 = (size_t)fl, i1 = std::min(i0 + 1, L - 1);
+    double v = 0.0 + (1.0 - t) * (double)(float)xs[i0];
+    v = v + t * (double)(float)xs[i1];
+    const float r = nearbyintf((float)v);
+    out[k] = r <= 0.f ? 0u : (uint32_t)r;
+  }
+  return true;
+}
+
+// Validates the spec against the setup (the constant block's header and host copy) and builds the gather table (FeatHeader, FeatFloor[], indices).
+static inline int feat_build_table(const ConstHeader& H, const uint8_t* host_const, const vsyn_feature_spec* sp, std::vector<uint8_t>& out, const char** err) {
+  if (!sp) return fail(err, VSYN_ERR_INVALID, "feature spec is NULL");
+  const bool floor_kind = sp->kind == VSYN_FEAT_FLOOR_FINAL_YS || sp->kind == VSYN_FEAT_FLOOR_FINAL_YS_RENDERED;
+  const bool res_kind = sp->kind == VSYN_FEAT_RESIDUE_YS || sp->kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
+  if (!floor_kind && !res_kind) return fail(err, VSYN_ERR_INVALID, "unknown feature kind %u", sp->kind);
+  if (sp->output_dim == 0 || sp->output_dim > (1u << 20)) return fail(err, VSYN_ERR_INVALID, "output_dim %u out of range", sp->output_dim);
+  const uint32_t floor_opts = VSYN_FEAT_INCLUDE_FLOOR_NUMBER | VSYN_FEAT_ONLY_BIGGEST_FLOOR | VSYN_FEAT_SORTED_XS | VSYN_FEAT_XS_FROM_BIGGEST_FLOOR |
+                              VSYN_FEAT_FLOOR_ALWAYS_POSITIVE;
+  const uint32_t res_opts = VSYN_FEAT_SORTED_XS | VSYN_FEAT_LOG1P_ABS_SPACE | VSYN_FEAT_IGNORE_XS | VSYN_FEAT_CLIP;
+  if (sp->options & ~(floor_kind ? floor_opts : res_opts)) return fail(err, VSYN_ERR_INVALID, "feature options 0x%x do not apply to kind %u", sp->options, sp->kind);
+  if ((sp->options & VSYN_FEAT_ONLY_BIGGEST_FLOOR) && (sp->options & VSYN_FEAT_INCLUDE_FLOOR_NUMBER))
+    return fail(err, VSYN_ERR_INVALID, "only_biggest_floor excludes include_floor_number");
+  if (res_kind && sp->upscale_xs_factor != 1.0) return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor applies to the floor kinds only");
+  if (!(sp->upscale_xs_factor > 0.0)) return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor must be > 0");
+  const FloorConst* fcs = (const FloorConst*)(host_const + H.off_floor);
+  const uint32_t F = H.num_floors, D = sp->output_dim;
+  uint32_t big = 0;
+  for (uint32_t f = 1; f < F; ++f)
+    if (fcs[f].posts > fcs[big].posts) big = f;  // the first of the largest (Python's max)
+  const bool sorted = (sp->options & VSYN_FEAT_SORTED_XS) != 0;
+  std::vector<std::vector<uint32_t>> xs(F), up(F);
+  for (uint32_t f = 0; f < F; ++f) {
+    xs[f].assign(fcs[f].xs, fcs[f].xs + fcs[f].posts);
+    if (sorted) std::sort(xs[f].begin(), xs[f].end());
+    if (floor_kind && sp->upscale_xs_factor != 1.0) {
+      if (!feat_zoom_round(xs[f], sp->upscale_xs_factor, up[f]))
+        return fail(err, VSYN_ERR_INVALID, "upscale_xs_factor %g: floor %u's %u posts do not zoom to a whole length (the reference asserts)",
+                    sp->upscale_xs_factor, f, fcs[f].posts);
+    } else {
+      up[f] = xs[f];
+    }
+  }
+  if (res_kind && !(sp->options & VSYN_FEAT_IGNORE_XS) && D < fcs[big].posts)
+    return fail(err, VSYN_ERR_INVALID, "output_dim %u is below the biggest floor's %u posts: the reference asserts on such rows (use ignore_xs)", D,
+                fcs[big].posts);
+  FeatHeader T = {};
+  T.kind = sp->kind;
+  T.dim = D;
+  T.opts = sp->options;
+  T.big = big;
+  T.num_floors = F;
+  T.scale = sp->scale;
+  T.clip = sp->clip_abs_max;
+  T.fbf = sp->floor_base_factor;
+  std::vector<FeatFloor> ff(F);
+  std::vector<uint32_t> idx;
+  const uint32_t o = (sp->options & VSYN_FEAT_INCLUDE_FLOOR_NUMBER) ? 1u : 0u;
+  for (uint32_t f = 0; f < F; ++f) {
+    std::vector<uint32_t> l;
+    FeatFloor& e = ff[f];
+    e.fnum = (float)(((double)f + 1.0) / (double)F - 0.5);
+    if (sp->options & VSYN_FEAT_XS_FROM_BIGGEST_FLOOR) {
+      l = up[big];
+      if (f != big) {
+        const double mb = (double)*std::max_element(xs[big].begin(), xs[big].end());
+        const double mc = (double)*std::max_element(xs[f].begin(), xs[f].end());
+        const double factor = nearbyint(mb / mc);  // Python's round() of the ratio (mc == 0: inf, no usable floor)
+        for (uint32_t& v : l) v = (factor >= 1.0 && factor < 4294967296.0) ? (uint32_t)(v / (uint64_t)factor) : 0u;  // numpy: x // 0 == 0
+      }
+      e.clip = 1;
+    }
+    else l = up[f];
+    e.maxidx = l.empty() ? 0u : *std::max_element(l.begin(), l.end());
+    e.cnt = D > o ? (uint32_t)std::min<size_t>(l.size(), D - o) : 0u;
+    e.off = (uint32_t)idx.size();
+    idx.insert(idx.end(), l.begin(), l.begin() + e.cnt);
+  }
+  T.res_off = (uint32_t)idx.size();
+  T.res_cnt = std::min<uint32_t>(fcs[big].posts, D);
+  idx.insert(idx.end(), xs[big].begin(), xs[big].begin() + T.res_cnt);
+  out.resize(sizeof(FeatHeader) + sizeof(FeatFloor) * F + sizeof(uint32_t) * (idx.size() + 1));
+  memcpy(out.data(), &T, sizeof(T));
+  memcpy(out.data() + sizeof(T), ff.data(), sizeof(FeatFloor) * F);
+  memcpy(out.data() + sizeof(T) + sizeof(FeatFloor) * F, idx.data(), sizeof(uint32_t) * idx.size());
+  return VSYN_OK;
+}
+
+// The count / offsets kernels (and, with rows != nullptr, the floor unwrap and the rows kernel) on stream s. Of the handle: the
+// constant block (header, host copy, device copy), the status words and the floor unwrap's dynamic LDS. Caller holds the handle's lock.
+static inline int feat_launch(FeatureWs& ws, int device, const ConstHeader& H, const uint8_t* host_const, const uint8_t* d_const,
+                              DevStatus* d_status, uint32_t unwrap_lds_bytes, const vsyn_feature_spec* sp, uint32_t P, const vsyn_packet* d_pk, uint32_t S, const vsyn_segment* d_seg,
+                       uint32_t max_seg, const uint16_t* d_ys, const float* d_res, float* d_rows, uint64_t* d_segoff, hipStream_t s,
+                       const char** err) {
+  std::vector<uint8_t> tab;
+  int rc = feat_build_table(H, host_const, sp, tab, err);
+  if (rc) return rc;
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (max_seg == 0 || max_seg > P) max_seg = P;
+  const uint32_t C = H.channels;
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(ws.info.ensure(P));
+  HIPCHK(ws.fy.ensure((size_t)P * C * H.ys_stride));
+  HIPCHK(ws.rowrel.ensure(P));
+  HIPCHK(ws.fbsrc.ensure(P));
+  HIPCHK(ws.fbch.ensure(P));
+  HIPCHK(ws.resoff.ensure(P));
+  HIPCHK(ws.segrows.ensure(S));
+  HIPCHK(ws.segoff.ensure((size_t)S + 1));
+  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+  if (P) HIPCHK(hipMemsetAsync(ws.info.p, 0, sizeof(PktInfo) * P, s));  // packets outside every segment: no floor rows to unwrap
+  FeatCtx A;
+  A.cb = d_const;
+  A.tab = ws.tab.dev.p;
+  A.pk = d_pk;
+  A.seg = d_seg;
+  A.fy = ws.fy.p;
+  A.res = d_res;
+  A.info = ws.info.p;
+  A.rowrel = ws.rowrel.p;
+  A.fbsrc = ws.fbsrc.p;
+  A.fbch = ws.fbch.p;
+  A.resoff = ws.resoff.p;
+  A.segrows = ws.segrows.p;
+  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
+  A.rows = d_rows;
+  A.status = d_status;
+  A.P = P;
+  A.S = S;
+  A.max_seg = max_seg;
+  hipLaunchKernelGGL(vsyn_feat_count_kernel, dim3(S), dim3(FEAT_THREADS), 0, s, A);
+  hipLaunchKernelGGL(vsyn_feat_offsets_kernel, dim3(1), dim3(FEAT_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  if (!d_rows || P == 0 || max_seg == 0) return VSYN_OK;  // (no packet: every segment is empty or flagged by the count kernel)
+  const uint32_t rows = P * C;
+  hipLaunchKernelGGL(vsyn_floor_unwrap_kernel, dim3(std::min<uint32_t>((rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, 65535u)), dim3(UNWRAP_THREADS), unwrap_lds_bytes, s,
+                     d_const, P, (const PktInfo*)ws.info.p, d_ys, ws.fy.p, d_status);
+  const uint64_t slots = (uint64_t)max_seg * C;
+  const uint64_t gx = (slots + FEAT_ROW_WAVES - 1) / FEAT_ROW_WAVES;
+  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  hipLaunchKernelGGL(vsyn_feat_rows_kernel, dim3((uint32_t)gx, S), dim3(FEAT_ROW_WAVES * 64), 0, s, A);
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
 }

@@ -1498,3 +1498,28 @@ static inline hipError_t fused_imdct_launch(const ConstHeader& H, const uint8_t*
   *done = true;
   return hipGetLastError();
 }
+
+// Diagnostic build (-DVSYN_STAMPS): per-phase cycles of the LAST launch's steady runs, averaged over the waves that ran one.
+static inline void fused_stamps_dump() {
+#ifdef VSYN_STAMPS
+  static unsigned long long host[8192][VSYN_NSTAMPS];
+  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_vsyn_stamps), sizeof(host)) == hipSuccess) {
+    double sum[VSYN_NSTAMPS] = {0};
+    unsigned long long waves = 0, pk = 0;
+    for (int u = 0; u < 8192; ++u) {
+      if (!host[u][VSYN_NSTAMPS - 1]) continue;
+      ++waves;
+      pk += host[u][VSYN_NSTAMPS - 1];
+      for (int i = 0; i + 1 < VSYN_NSTAMPS; ++i) sum[i] += (double)host[u][i];
+    }
+    if (pk) {
+      static const char* nm[VSYN_NSTAMPS - 1] = {"loop", "residue+handoff+couple", "loads+floor setup", "floor product", "mirror+pre-rot", "partner wait 2",
+                                                 "fft512", "post+window+overlap", "stores / short pass: stores", "short: descriptors", "short: rows", "short: couple+floor", "short: fft+window", "-", "-"};
+      double tot = 0;
+      for (int i = 0; i + 1 < VSYN_NSTAMPS; ++i) tot += sum[i];
+      fprintf(stderr, "vsyn stamps: %llu waves, %llu wave-packets, %.0f cycles per wave-packet\n", waves, pk, tot / pk);
+      for (int i = 0; i + 1 < VSYN_NSTAMPS; ++i) fprintf(stderr, "  %-26s %8.0f cycles  %5.1f %%\n", nm[i], sum[i] / pk, 100.0 * sum[i] / tot);
+    }
+  }
+#endif
+}

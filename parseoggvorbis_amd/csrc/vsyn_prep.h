@@ -439,3 +439,41 @@ __global__ void __launch_bounds__(PREP_THREADS) vsyn_prep_kernel(const PrepCtx A
 #undef PREP_IS_LONG
 #undef PREP_N_OF_MODE
 }
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+#include <stdio.h>
+
+// Diagnostic build (-DPREP_STAMPS): cycles per phase of vsyn_prep_kernel (last launch), averaged over the waves of each role, and when
+// the waves of each role started / ended relative to the first wave of the launch (100 MHz clock).
+static inline void prep_stamps_dump() {
+#ifdef PREP_STAMPS
+  static unsigned long long host[8192][PREP_NSTAMPS];
+  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_prep_stamps), sizeof(host)) == hipSuccess) {
+    unsigned long long t_first = ~0ull;
+    for (int u = 0; u < 8192; ++u)
+      if (host[u][7] && host[u][5] < t_first) t_first = host[u][5];
+    for (unsigned role = 0; role < 2; ++role) {
+      double sum[5] = {0}, st = 0, en = 0, en_max = 0, st_max = 0;
+      unsigned long long waves = 0;
+      for (int u = 0; u < 8192; ++u) {
+        if (host[u][7] != 1ull + role) continue;
+        ++waves;
+        for (int i = 0; i < 5; ++i) sum[i] += (double)host[u][i];
+        const double a = (double)(host[u][5] - t_first) / 100.0, b = (double)(host[u][6] - t_first) / 100.0;
+        st += a;
+        en += b;
+        if (a > st_max) st_max = a;
+        if (b > en_max) en_max = b;
+      }
+      if (!waves) continue;
+      static const char* nm[5] = {"header + stream state", "scan in front of the chunk", "descriptors, scan, PktInfo", "floor role: descriptors, floor ids", "floor role: chains"};
+      fprintf(stderr, "prep stamps, %s role: %llu waves; start %.2f us (latest %.2f), end %.2f us (latest %.2f) after the launch's first wave\n",
+              role ? "floor" : "layout", waves, st / waves, st_max, en / waves, en_max);
+      for (int i = 0; i < 5; ++i)
+        if (sum[i] > 0) fprintf(stderr, "  %-36s %8.0f cycles\n", nm[i], sum[i] / waves);
+    }
+  }
+#endif
+}

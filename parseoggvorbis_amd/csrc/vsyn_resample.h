@@ -16,6 +16,7 @@
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_host.h"
 #include "vsyn_pcm.h"
 
 #define RS_THREADS 256
@@ -198,4 +199,176 @@ __global__ void __launch_bounds__(256) vsyn_rs_s16_kernel(const float* __restric
   const bool in = t < frames[g];
   for (uint32_t c = 0; c < C; ++c)
     out[((size_t)g * out_stride + t) * C + c] = in ? (int16_t)pcm_s16(pcm[((size_t)g * C + c) * plane + t]) : (int16_t)0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct ResampleWs {  // the stage's buffers: its own; the PCM is only read
+  TableUpload tab;
+  bool lds_set = false;                // vsyn_rs_kernel<true>'s dynamic-LDS limit is raised on this handle's device
+  DevBuf<uint32_t> inF, outF;
+  DevBuf<uint64_t> off;
+  DevBuf<float> pcm;                   // host forms: the resampled PCM
+  DevBuf<int16_t> s16;                 // vsyn_pcm_resample_host, VSYN_PCM_S16
+};
+
+// vsyn_rs_kernel<true> holds one pair's table and one tile's input span in LDS. 80 KiB keeps two of its workgroups on a CU
+// (160 KiB) at worst and takes every pair among 8, 11.025, 16, 22.05, 24, 32, 44.1 and 48 kHz but 11.025 <-> 32 kHz (115 / 122
+// KiB); 44.1 -> 16 kHz needs 46 KiB. Bigger tables (11.025 <-> 32 kHz; 44056 -> 16000 = 2000 / 5507, 448 KiB) use
+// vsyn_rs_kernel<false>.
+static const uint32_t RS_LDS_BUDGET = 80u * 1024u;
+
+// The reduced ratio of a pair; false for a pair the contract refuses (a rate of 0, or M above VSYN_RESAMPLE_MAX_M).
+static inline bool rs_ratio(uint32_t r_in, uint32_t r_out, uint32_t* up, uint32_t* down) {
+  if (!r_in || !r_out) return false;
+  const uint32_t g = std::gcd(r_in, r_out);
+  *up = r_out / g;
+  *down = r_in / g;
+  return std::max(*up, *down) <= VSYN_RESAMPLE_MAX_M;
+}
+
+static inline double rs_i0(double x) {  // modified Bessel function of the first kind, order 0: sum_k ((x/2)^k / k!)^2
+  const double q = 0.25 * x * x;
+  double s = 1.0, t = 1.0;
+  for (int k = 1; k < 500; ++k) {
+    t *= q / ((double)k * (double)k);
+    s += t;
+    if (t < 1e-17 * s) break;
+  }
+  return s;
+}
+
+// h[0 .. N) of the header's step 2, in double.
+static inline void rs_taps(uint32_t up, uint32_t down, std::vector<double>& h) {
+  const uint32_t M = std::max(up, down), H = 10u * M, N = 2u * H + 1u;
+  h.assign(N, 0.0);
+  const double i0b = rs_i0(5.0);
+  double S = 0.0;
+  for (uint32_t n = 0; n < N; ++n) {
+    const double m = (double)n - (double)H, xs = M_PI * m / (double)M, r = 2.0 * n / (double)(N - 1u) - 1.0;
+    const double sinc = m == 0.0 ? 1.0 : sin(xs) / xs;
+    h[n] = rs_i0(5.0 * sqrt(std::max(0.0, 1.0 - r * r))) / i0b * sinc;
+    S += h[n];
+  }
+  for (uint32_t n = 0; n < N; ++n) h[n] = up * h[n] / S;
+}
+
+struct RsPlan {
+  std::vector<uint8_t> tab;
+  uint64_t chunks[2] = {0, 0};  // grid bounds of vsyn_rs_kernel<true> / <false>
+  uint32_t lds_bytes = 0;       // dynamic LDS of vsyn_rs_kernel<true>
+};
+
+// RsHeader, RsPair per distinct pair, seg_pair[S], the polyphase tables. rates[g] = 0 skips g; every other pair is valid (checked
+// by the caller). plane bounds every segment's input frames.
+static inline void rs_build_table(uint32_t S, const uint32_t* rates, uint32_t out_rate, uint32_t C, uint64_t plane, RsPlan& plan) {
+  std::vector<uint32_t> seg_pair(S, RS_SKIP), keys;
+  std::vector<RsPair> pairs;
+  uint64_t taps = 0;
+  const uint64_t T_max = std::min<uint64_t>(plane, 0xFFFFFFFFull);
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!rates[g]) continue;
+    auto it = std::find(keys.begin(), keys.end(), rates[g]);
+    seg_pair[g] = (uint32_t)(it - keys.begin());
+    if (it == keys.end()) {
+      keys.push_back(rates[g]);
+      RsPair p = {};
+      rs_ratio(rates[g], out_rate, &p.up, &p.down);
+      p.lds = 1;
+      if (p.up != p.down) {
+        const uint32_t M = std::max(p.up, p.down), N = 20u * M + 1u, K = (N + p.up - 1u) / p.up;
+        p.h = 10u * M;
+        p.k4 = (K + 3u) & ~3u;
+        p.span4 = rs_span4(p.up, p.down, p.k4);
+        p.tab = taps;
+        taps += (uint64_t)p.up * p.k4;
+        const uint64_t lds = 4ull * ((uint64_t)p.up * p.k4 + 4ull * p.span4);
+        p.lds = lds <= RS_LDS_BUDGET;
+        if (p.lds) plan.lds_bytes = std::max(plan.lds_bytes, (uint32_t)lds);
+      }
+      pairs.push_back(p);
+    }
+    const RsPair& p = pairs[seg_pair[g]];
+    plan.chunks[p.lds ? 0 : 1] += (uint64_t)C * ((rs_num_frames(T_max, p.up, p.down) + RS_CHUNK - 1u) / RS_CHUNK);
+  }
+  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  RsHeader hd = {(uint32_t)pairs.size(), S, 0, 0};
+  const size_t off_pairs = sizeof(RsHeader);
+  hd.off_seg = (uint32_t)al(off_pairs + sizeof(RsPair) * pairs.size());
+  const size_t off_taps = al(hd.off_seg + 4ull * S);
+  for (RsPair& p : pairs) p.tab += off_taps / 4u;
+  plan.tab.assign(off_taps + 4ull * taps + 16, 0);
+  uint8_t* o = plan.tab.data();
+  memcpy(o, &hd, sizeof(hd));
+  if (!pairs.empty()) memcpy(o + off_pairs, pairs.data(), sizeof(RsPair) * pairs.size());
+  if (S) memcpy(o + hd.off_seg, seg_pair.data(), 4ull * S);
+  std::vector<double> h;
+  for (const RsPair& p : pairs) {
+    if (p.up == p.down) continue;
+    rs_taps(p.up, p.down, h);
+    float* P = (float*)o + p.tab;
+    for (uint32_t phi = 0; phi < p.up; ++phi)
+      for (uint32_t t = 0; t < p.k4; ++t) {
+        const uint64_t n = phi + (uint64_t)t * p.up;
+        P[(size_t)phi * p.k4 + t] = n < h.size() ? (float)h[n] : 0.0f;
+      }
+  }
+}
+
+// The checks of every segment's pair (0 = skipped segment).
+static inline int rs_check(uint32_t S, const uint32_t* rates, uint32_t out_rate, const char** err) {
+  if (!out_rate) return fail(err, VSYN_ERR_INVALID, "out_rate must be >= 1");
+  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "in_rates is NULL");
+  for (uint32_t g = 0; g < S; ++g) {
+    uint32_t up, down;
+    if (rates[g] && !rs_ratio(rates[g], out_rate, &up, &down))
+      return fail(err, VSYN_ERR_INVALID, "segment %u: %u -> %u Hz reduces to %u / %u, above the limit max(up, down) <= %u", g, rates[g],
+                  out_rate, up, down, VSYN_RESAMPLE_MAX_M);
+  }
+  return VSYN_OK;
+}
+
+// Offsets and resample kernels on stream s; frames from d_frames, else from si; the frames written go to d_out_frames (NULL:
+// ws.outF). Caller holds the handle's lock and has run rs_check, and out_plane holds every segment's T_out.
+static inline int rs_launch(ResampleWs& ws, int device, uint32_t S, const uint32_t* rates, uint32_t out_rate, const float* d_pcm, uint64_t plane, uint32_t C,
+                     const uint32_t* d_frames, const SegInfo* si, float* d_out, uint64_t out_plane, uint32_t* d_out_frames, hipStream_t s,
+                     const char** err) {
+  RsPlan plan;
+  rs_build_table(S, rates, out_rate, C, plane, plan);
+  if (plan.chunks[0] > 0x7FFFFFFFull || plan.chunks[1] > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too much output for one call");
+  HIPCHK(hipSetDevice(device));
+  if (!ws.lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_rs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_LDS_BUDGET));
+    ws.lds_set = true;
+  }
+  const std::vector<uint8_t>& tab = plan.tab;
+  HIPCHK(ws.inF.ensure(S));
+  HIPCHK(ws.outF.ensure(S));
+  HIPCHK(ws.off.ensure(2ull * S + 2));
+  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+  RsCtx A;
+  A.tab = ws.tab.dev.p;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.out = d_out;
+  A.out_plane = out_plane;
+  A.in_frames = ws.inF.p;
+  A.out_frames = d_out_frames ? d_out_frames : ws.outF.p;
+  A.off = ws.off.p;
+  hipLaunchKernelGGL(vsyn_rs_offsets_kernel, dim3(1), dim3(RS_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  if (plan.chunks[0]) {
+    hipLaunchKernelGGL(vsyn_rs_kernel<true>, dim3((uint32_t)plan.chunks[0]), dim3(RS_THREADS), plan.lds_bytes, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  if (plan.chunks[1]) {
+    hipLaunchKernelGGL(vsyn_rs_kernel<false>, dim3((uint32_t)plan.chunks[1]), dim3(RS_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  return VSYN_OK;
 }

@@ -16,6 +16,7 @@
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_host.h"
 
 struct SpecHeader {
   uint32_t kind, opts, n, hop, win, woff, nbins, n_mels;
@@ -211,4 +212,190 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_finish_kernel(const Sp
     for (uint32_t m = 0; m < NM; ++m) acc = fmaf(c[m], row[m], acc);
     A.rows[(r0 + f) * D + i] = acc;
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+static const uint32_t SPEC_LDS_BUDGET = 160u * 1024u;  // gfx950: 160 KiB of LDS per CU, all of it available to one workgroup
+
+struct SpectralWs {  // the stage's buffers: its own; the PCM is only read
+  TableUpload tab;
+  bool lds_set = false;                // the STFT kernels' dynamic-LDS limit is raised on this handle's device
+  DevBuf<uint32_t> segF, segmax;
+  DevBuf<uint64_t> segoff;
+  DevBuf<float> db, rows;
+};
+
+static inline double spec_hz_to_mel(double f, bool htk) {
+  if (htk) return 2595.0 * log10(1.0 + f / 700.0);
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+  return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
+}
+static inline double spec_mel_to_hz(double m, bool htk) {
+  if (htk) return 700.0 * (pow(10.0, m / 2595.0) - 1.0);
+  const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+  return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+
+static inline uint32_t spec_dim(const vsyn_spectral_spec* sp) { return sp->kind == VSYN_SPEC_MFCC ? sp->n_mfcc : sp->n_mels; }
+
+// The checks of the spec and of every segment's rate (0 = skipped segment).
+static inline int spec_check(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const char** err) {
+  if (!sp) return fail(err, VSYN_ERR_INVALID, "spectral spec is NULL");
+  if (sp->kind < VSYN_SPEC_MEL_POWER || sp->kind > VSYN_SPEC_MFCC) return fail(err, VSYN_ERR_INVALID, "unknown spectral kind %u", sp->kind);
+  if (sp->options & ~(VSYN_SPEC_CENTER | VSYN_SPEC_HTK | VSYN_SPEC_NO_NORM)) return fail(err, VSYN_ERR_INVALID, "unknown spectral options 0x%x", sp->options);
+  if (sp->n_fft < 16 || sp->n_fft > 8192) return fail(err, VSYN_ERR_INVALID, "n_fft %u outside [16, 8192]", sp->n_fft);
+  if (sp->hop_length < 1) return fail(err, VSYN_ERR_INVALID, "hop_length must be >= 1");
+  if (sp->win_length < 1 || sp->win_length > sp->n_fft) return fail(err, VSYN_ERR_INVALID, "win_length %u outside [1, n_fft]", sp->win_length);
+  if (sp->n_mels < 1 || sp->n_mels > 256) return fail(err, VSYN_ERR_INVALID, "n_mels %u outside [1, 256]", sp->n_mels);
+  if (sp->kind == VSYN_SPEC_MFCC && (sp->n_mfcc < 1 || sp->n_mfcc > sp->n_mels)) return fail(err, VSYN_ERR_INVALID, "n_mfcc %u outside [1, n_mels]", sp->n_mfcc);
+  if (sp->power != 1 && sp->power != 2) return fail(err, VSYN_ERR_INVALID, "power must be 1 or 2");
+  if (!(sp->fmin >= 0.0) || !(sp->fmax >= 0.0)) return fail(err, VSYN_ERR_INVALID, "fmin / fmax must be >= 0");
+  if (sp->kind == VSYN_SPEC_LOG_MEL && !(sp->log_floor > 0.0)) return fail(err, VSYN_ERR_INVALID, "log_floor must be > 0");
+  if (sp->kind >= VSYN_SPEC_MEL_DB && (!(sp->amin > 0.0) || !(sp->top_db >= 0.0))) return fail(err, VSYN_ERR_INVALID, "amin must be > 0 and top_db >= 0");
+  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!rates[g]) continue;
+    const double ny = rates[g] / 2.0, fmax = sp->fmax > 0.0 ? sp->fmax : ny;
+    if (fmax > ny) return fail(err, VSYN_ERR_INVALID, "segment %u: fmax %g above sr/2 = %g", g, fmax, ny);
+    if (!(sp->fmin < fmax)) return fail(err, VSYN_ERR_INVALID, "segment %u: fmin %g not below fmax %g", g, sp->fmin, fmax);
+  }
+  return VSYN_OK;
+}
+
+static inline uint32_t spec_tile(const vsyn_spectral_spec* sp) {  // frames per STFT workgroup: the most that fit the LDS
+  for (uint32_t ft : {16u, 4u, 1u})
+    if (spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u <= SPEC_LDS_BUDGET) return ft;
+  return 0;
+}
+
+// SpecHeader, twiddles, window, per-rate bands and weights, DCT matrix, per-segment rate index. Call after spec_check.
+static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, std::vector<uint8_t>& out) {
+  const uint32_t n = sp->n_fft, NM = sp->n_mels, nb = n / 2u + 1u;
+  const bool htk = (sp->options & VSYN_SPEC_HTK) != 0, norm = !(sp->options & VSYN_SPEC_NO_NORM);
+  std::vector<uint32_t> distinct, seg_rate(S, SPEC_SKIP);
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!rates[g]) continue;
+    auto it = std::find(distinct.begin(), distinct.end(), rates[g]);
+    seg_rate[g] = (uint32_t)(it - distinct.begin());
+    if (it == distinct.end()) distinct.push_back(rates[g]);
+  }
+  std::vector<SpecBand> bands;
+  std::vector<float> w;
+  std::vector<double> hz(NM + 2);
+  for (uint32_t sr : distinct) {
+    const double fmax = sp->fmax > 0.0 ? sp->fmax : sr / 2.0;
+    const double m0 = spec_hz_to_mel(sp->fmin, htk), m1 = spec_hz_to_mel(fmax, htk), step = (m1 - m0) / (double)(NM + 1);
+    for (uint32_t i = 0; i < NM + 2; ++i) hz[i] = spec_mel_to_hz(i == NM + 1 ? m1 : m0 + i * step, htk);  // numpy.linspace
+    for (uint32_t m = 0; m < NM; ++m) {
+      const double lo = hz[m], c = hz[m + 1], hi = hz[m + 2], enorm = norm ? 2.0 / (hi - lo) : 1.0;
+      SpecBand b = {0, 0, (uint32_t)w.size(), 0};
+      for (uint32_t k = 0; k < nb; ++k) {
+        const double fk = (double)k * sr / n;
+        const double v = std::max(0.0, std::min((fk - lo) / (c - lo), (hi - fk) / (hi - c))) * enorm;
+        if (v > 0.0) {
+          if (!b.cnt) b.first = k;
+          for (uint32_t z = b.first + b.cnt; z < k; ++z) w.push_back(0.f);  // (a triangle has no holes; kept general)
+          b.cnt = k - b.first + 1;
+          w.push_back((float)v);
+        }
+      }
+      bands.push_back(b);
+    }
+  }
+  SpecHeader T = {};
+  T.kind = sp->kind;
+  T.opts = sp->options;
+  T.n = n;
+  T.hop = sp->hop_length;
+  T.win = sp->win_length;
+  T.woff = (n - sp->win_length) / 2u;
+  T.nbins = nb;
+  T.n_mels = NM;
+  T.dim = spec_dim(sp);
+  T.n_mfcc = sp->kind == VSYN_SPEC_MFCC ? sp->n_mfcc : 0u;
+  T.power = sp->power;
+  T.num_rates = (uint32_t)distinct.size();
+  T.S = S;
+  T.log_floor = (float)sp->log_floor;
+  T.amin = (float)sp->amin;
+  T.top_db = (float)sp->top_db;
+  auto al = [](size_t v) { return (uint32_t)((v + 15) & ~(size_t)15); };
+  T.off_tw = al(sizeof(SpecHeader));
+  T.off_win = al(T.off_tw + 8ull * n);
+  T.off_band = al(T.off_win + 4ull * n);
+  T.off_w = al(T.off_band + sizeof(SpecBand) * bands.size());
+  T.off_dct = al(T.off_w + 4ull * w.size());
+  T.off_rate = al(T.off_dct + 4ull * T.n_mfcc * NM);
+  out.assign(T.off_rate + 4ull * S + 16, 0);
+  memcpy(out.data(), &T, sizeof(T));
+  float* tw = (float*)(out.data() + T.off_tw);
+  for (uint32_t m = 0; m < n; ++m) {
+    const double a = 2.0 * M_PI * (double)m / (double)n;
+    tw[2 * m] = (float)cos(a);
+    tw[2 * m + 1] = (float)sin(a);
+  }
+  float* wn = (float*)(out.data() + T.off_win);
+  for (uint32_t i = 0; i < sp->win_length; ++i) wn[T.woff + i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)sp->win_length));
+  if (!bands.empty()) memcpy(out.data() + T.off_band, bands.data(), sizeof(SpecBand) * bands.size());
+  if (!w.empty()) memcpy(out.data() + T.off_w, w.data(), 4 * w.size());
+  float* dct = (float*)(out.data() + T.off_dct);
+  for (uint32_t i = 0; i < T.n_mfcc; ++i)
+    for (uint32_t m = 0; m < NM; ++m)
+      dct[(size_t)i * NM + m] = (float)(sqrt((i ? 2.0 : 1.0) / NM) * cos(M_PI * (double)i * (2.0 * m + 1.0) / (2.0 * NM)));
+  if (S) memcpy(out.data() + T.off_rate, seg_rate.data(), 4ull * S);
+}
+
+// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s; frames from d_frames, else from si. f_max bounds every
+// segment's STFT frames, rows_bound the total rows. Caller holds the handle's lock and has run spec_check.
+static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
+                       uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
+                       uint64_t* d_segoff, hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  const uint32_t ft = spec_tile(sp);
+  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", sp->n_fft, sp->hop_length);
+  std::vector<uint8_t> tab;
+  spec_build_table(sp, S, rates, tab);
+  HIPCHK(hipSetDevice(device));
+  if (!ws.lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    ws.lds_set = true;
+  }
+  HIPCHK(ws.segF.ensure(S));
+  HIPCHK(ws.segmax.ensure(S));
+  HIPCHK(ws.segoff.ensure((size_t)S + 1));
+  if (sp->kind == VSYN_SPEC_MFCC) HIPCHK(ws.db.ensure(rows_bound * sp->n_mels + 1));
+  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+  SpecCtx A;
+  A.tab = ws.tab.dev.p;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.segF = ws.segF.p;
+  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
+  A.segmax = ws.segmax.p;
+  A.rows = d_rows;
+  A.db = sp->kind == VSYN_SPEC_MFCC ? ws.db.p : nullptr;
+  hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  if (f_max == 0 || S == 0) return VSYN_OK;
+  const uint64_t gx = (f_max + ft - 1) / ft;
+  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  const size_t lds = spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u;
+  const dim3 grid((uint32_t)gx, S);
+  if (ft == 16) hipLaunchKernelGGL(vsyn_spec_stft_kernel<16>, grid, dim3(SPEC_THREADS), lds, s, A);
+  else if (ft == 4) hipLaunchKernelGGL(vsyn_spec_stft_kernel<4>, grid, dim3(SPEC_THREADS), lds, s, A);
+  else hipLaunchKernelGGL(vsyn_spec_stft_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
+  HIPCHK(hipGetLastError());
+  if (sp->kind >= VSYN_SPEC_MEL_DB) {
+    hipLaunchKernelGGL(vsyn_spec_finish_kernel, dim3((uint32_t)((f_max + SPEC_FIN_ROWS - 1) / SPEC_FIN_ROWS), S), dim3(SPEC_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  return VSYN_OK;
 }

@@ -20,6 +20,8 @@
 // the same bits. Nothing here reads or writes stream state, the overlap carry or PCM.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_host.h"
+#include "vsyn_spectral.h"  // SPEC_LDS_BUDGET
 
 #define POST_THREADS 256
 #define POST_BLK 16u  // rows per block of partial sums
@@ -175,4 +177,139 @@ __global__ void __launch_bounds__(POST_THREADS) vsyn_post_norm_kernel(const Post
       for (uint32_t f = fb; f < fe; ++f, y += Dout) *y = (float)(((double)*y - m) * r);
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct PostWs {  // the stage's buffers: a second row buffer (the output rows are wider) and the statistics
+  TableUpload tab;
+  bool lds_set = false;                // vsyn_post_delta_kernel's dynamic-LDS limit is raised on this handle's device
+  DevBuf<float> rows;
+  DevBuf<double> part, stat;           // per-block partial sums; mu | rinv per (segment, column)
+};
+
+static inline bool post_on(const vsyn_spectral_post* p) { return p->order != 0 || p->norm != VSYN_POST_NORM_NONE; }
+static inline bool post_given(const vsyn_spectral_post* p) { return p->norm != VSYN_POST_NORM_NONE && p->stats == VSYN_POST_STATS_GIVEN; }
+
+// The checks of the post spec that need no row counts; the given vectors are read for finiteness only when dout != 0.
+static inline int post_check(const vsyn_spectral_post* p, const char** err, uint32_t dout = 0) {
+  if (!p) return fail(err, VSYN_ERR_INVALID, "spectral post spec is NULL");
+  if (p->order > 2) return fail(err, VSYN_ERR_INVALID, "delta order %u outside [0, 2]", p->order);
+  if (p->width < 3 || p->width > VSYN_POST_MAX_WIDTH || !(p->width & 1u))
+    return fail(err, VSYN_ERR_INVALID, "delta width %u must be odd and in [3, %u]", p->width, VSYN_POST_MAX_WIDTH);
+  if (p->norm > VSYN_POST_NORM_MEAN_VAR) return fail(err, VSYN_ERR_INVALID, "unknown normalisation %u", p->norm);
+  if (p->stats > VSYN_POST_STATS_GIVEN) return fail(err, VSYN_ERR_INVALID, "unknown statistics source %u", p->stats);
+  if (!(p->std_floor > 0.0) || !std::isfinite(p->std_floor)) return fail(err, VSYN_ERR_INVALID, "std_floor must be finite and > 0");
+  if (post_given(p)) {
+    const bool var = p->norm == VSYN_POST_NORM_MEAN_VAR;
+    if (!p->mean || (var && !p->std)) return fail(err, VSYN_ERR_INVALID, "given statistics: %s is NULL", p->mean ? "std" : "mean");
+    for (uint32_t j = 0; j < dout; ++j)
+      if (!std::isfinite(p->mean[j]) || (var && !std::isfinite(p->std[j])))
+        return fail(err, VSYN_ERR_INVALID, "given statistics: column %u is not finite", j);
+  }
+  return VSYN_OK;
+}
+
+// A segment shorter than the delta window is refused by name.
+static inline int post_check_rows(const vsyn_spectral_post* p, uint32_t S, const uint64_t* seg_rows, const char** err) {
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) {
+    if (seg_rows[g] > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment %u: too many rows", g);
+    if (p->order && seg_rows[g] && seg_rows[g] < p->width)
+      return fail(err, VSYN_ERR_INVALID, "segment %u: delta width %u needs %u frames, segment has %llu", g, p->width, p->width,
+                  (unsigned long long)seg_rows[g]);
+  }
+  return VSYN_OK;
+}
+
+// The stage's kernels on stream s: d_in [rows][D] -> d_out [rows][D * (1 + order)]. Caller holds the handle's lock, has run post_check (with
+// dout) and post_check_rows, and post_on(p) holds.
+static inline int post_launch(PostWs& ws, int device, const vsyn_spectral_post* p, uint32_t D, uint32_t S, const uint64_t* seg_rows, const float* d_in,
+                       float* d_out, hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  const uint32_t W = p->width, Dout = D * (1u + p->order), hh = p->order ? (W - 1u) / 2u : 0u;
+  const bool norm = p->norm != VSYN_POST_NORM_NONE, given = post_given(p), var = p->norm == VSYN_POST_NORM_MEAN_VAR;
+  // table: PostSeg[S] | given mu[Dout], rinv[Dout] (double) | c1[W], c2[W] (float)
+  const size_t off_stat = sizeof(PostSeg) * S, off_coef = off_stat + (given ? 16ull * Dout : 0ull);
+  std::vector<uint8_t> tab(off_coef + 8ull * W);
+  PostSeg* seg = (PostSeg*)tab.data();
+  uint64_t rows = 0, blocks = 0, f_max = 0;
+  for (uint32_t g = 0; g < S; ++g) {
+    seg[g] = PostSeg{rows, blocks, (uint32_t)seg_rows[g], 0u};
+    rows += seg_rows[g];
+    blocks += (seg_rows[g] + POST_BLK - 1u) / POST_BLK;
+    f_max = std::max(f_max, seg_rows[g]);
+  }
+  if (f_max == 0) return VSYN_OK;
+  if (given) {
+    double* st = (double*)(tab.data() + off_stat);
+    for (uint32_t j = 0; j < Dout; ++j) {
+      st[j] = (double)p->mean[j];
+      st[Dout + j] = var ? 1.0 / std::max((double)p->std[j], p->std_floor) : 1.0;
+    }
+  }
+  float* coef = (float*)(tab.data() + off_coef);
+  double S2 = 0, S4 = 0;
+  for (int k = -(int)hh; k <= (int)hh; ++k) {
+    S2 += (double)k * k;
+    S4 += (double)k * k * k * k;
+  }
+  for (uint32_t i = 0; i < W && hh; ++i) {
+    const double k = (double)i - (double)hh;
+    coef[i] = (float)(k / S2);
+    coef[W + i] = (float)(2.0 * (W * k * k - S2) / (W * S4 - S2 * S2));
+  }
+  // the tile: every row group of the workgroup gets a block, at least four blocks, and the LDS image fits
+  const uint32_t G = POST_THREADS / std::min<uint32_t>(Dout, POST_THREADS);
+  uint32_t nb = G * ((4u + G - 1u) / G);
+  const auto lds_of = [&](uint32_t blocks) { return ((size_t)(blocks * POST_BLK + 2u * hh) * D + POST_COEF_FLOATS) * 4u; };
+  while (nb > 1u && lds_of(nb) > SPEC_LDS_BUDGET) --nb;
+  const uint32_t tile = nb * POST_BLK;
+  const size_t lds = lds_of(nb);
+  HIPCHK(hipSetDevice(device));
+  if (!ws.lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_post_delta_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    ws.lds_set = true;
+  }
+  const bool seg_stats = norm && !given;
+  if (seg_stats) {
+    HIPCHK(ws.part.ensure(blocks * Dout));
+    HIPCHK(ws.stat.ensure(2ull * S * Dout));
+  }
+  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+  PostCtx A;
+  A.seg = (const PostSeg*)ws.tab.dev.p;
+  A.coef = (const float*)(ws.tab.dev.p + off_coef);
+  A.in = d_in;
+  A.out = d_out;
+  A.part = seg_stats ? ws.part.p : nullptr;
+  A.mu = given ? (double*)(ws.tab.dev.p + off_stat) : ws.stat.p;
+  A.rinv = given ? A.mu + Dout : ws.stat.p + (size_t)S * Dout;
+  A.stat_stride = given ? 0u : Dout;
+  A.D = D;
+  A.Dout = Dout;
+  A.order = p->order;
+  A.width = W;
+  A.tile = tile;
+  A.std_floor = p->std_floor;
+  const uint64_t gx = (f_max + tile - 1u) / tile;
+  const dim3 grid((uint32_t)gx, S), rgrid((Dout + POST_RED_COLS - 1u) / POST_RED_COLS, S);
+  hipLaunchKernelGGL(vsyn_post_delta_kernel, grid, dim3(POST_THREADS), lds, s, A);
+  HIPCHK(hipGetLastError());
+  if (seg_stats) {
+    hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 0u);
+    HIPCHK(hipGetLastError());
+    if (var) {
+      hipLaunchKernelGGL(vsyn_post_moment_kernel, grid, dim3(POST_THREADS), 0, s, A);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 1u);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if (norm) {
+    hipLaunchKernelGGL(vsyn_post_norm_kernel, grid, dim3(POST_THREADS), 0, s, A);
+    HIPCHK(hipGetLastError());
+  }
+  return VSYN_OK;
 }

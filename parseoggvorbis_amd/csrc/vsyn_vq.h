@@ -705,3 +705,25 @@ static inline std::string vq_build_block(const vsyn_vq_setup* vq, const ConstHea
   if (!img.empty()) memcpy(block.data() + vh.off_img, img.data(), img.size() * sizeof(float));
   return std::string();
 }
+
+// Diagnostic build (-DVQ_STAMPS): the residue VQ kernel's cycles per phase and packet (last launch), averaged over its waves.
+static inline void vq_stamps_dump() {
+#ifdef VQ_STAMPS
+  static unsigned long long host[8192][VQ_NSTAMPS];
+  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_vq_stamps), sizeof(host)) == hipSuccess) {
+    double sum[VQ_NSTAMPS] = {0};
+    unsigned long long pk = 0, waves = 0;
+    for (int u = 0; u < 8192; ++u) {
+      if (!host[u][VQ_NSTAMPS - 1]) continue;
+      ++waves;
+      pk += host[u][VQ_NSTAMPS - 1];
+      for (int i = 0; i + 1 < VQ_NSTAMPS; ++i) sum[i] += (double)host[u][i];
+    }
+    if (pk) {
+      fprintf(stderr, "[vq stamps] %llu waves, %.1f packets each; s_memtime ticks per packet:", waves, (double)pk / waves);
+      for (int i = 0; i + 1 < VQ_NSTAMPS; ++i) fprintf(stderr, " %d:%.0f", i, sum[i] / pk);
+      fprintf(stderr, "\n");
+    }
+  }
+#endif
+}

@@ -420,3 +420,80 @@ def test_host_entries_leave_the_pcm_and_the_next_submit_alone(mods, synth):
         g.close()
     assert np.array_equal(outs[0][0], outs[1][0])
     assert np.array_equal(outs[0][1], outs[1][1]) and np.array_equal(outs[0][2], outs[1][2])
+
+
+def test_full_chain_equals_the_stages_one_by_one(mods, synth):
+    """Stage chaining, no tolerance: the rows, seg_rows and peaks of one vsyn_pcm_cond_spectral_host call (resample, condition, STFT /
+    mel, post) equal those of vsyn_resample_device -> vsyn_pcm_condition_device -> vsyn_spectral_device -> vsyn_spectral_post_device
+    run one by one on the fetched PCM, on planes of another stride (t_max + 5) than the host form's (t_max); and the PCM of
+    vsyn_pcm_condition_host, F32 and S16, equals that run's conditioned plane. Three segments at 8000 (resampled 1:2), 16000 (ratio 1)
+    and 0 Hz (skipped: 0 frames, 0 rows, peak 0); the longest segment is the one resampled 1:2, so that a plane of t_max + 5 frames
+    holds every input plane resampled, which vsyn_resample_device asks for."""
+    import torch
+    from parseoggvorbis_amd.binding import Synth, VSYN_PCM_F32, VSYN_PCM_S16
+    from tests.workloads import fixture_like_spec, synth_batch
+    _, spectral = mods
+    spec = fixture_like_spec(2)
+    b = synth_batch(spec, streams=3, packets_per_stream=12, pattern="mixed", seed=21)
+    S, Cn, rates, out_rate = len(b["segments"]), 2, [16000, 0, 8000], 16000
+    assert S == 3
+    cond = _cond(True, A)
+    s = spectral.spectral_spec(kind="mel_db", n_fft=64, hop_length=32, n_mels=8)
+    dim = spectral.spec_dim(s)
+    post, dout, _ = spectral.post_spec(dim, delta=1, delta_width=3, normalize="mean_var")
+    g = Synth(spec, device=0, max_streams=4)
+    try:
+        assert g.submit_host(b["packets"], b["segments"], b["ys"], b["residue"], b["plane_stride"], flags=4)["rc"] == 0  # KEEP_PCM
+        f1, fr = g.pcm_fetch_host(VSYN_PCM_F32, S, b["plane_stride"])
+        host = g.pcm_cond_spectral_host(cond, s, post, rates, out_rate)
+        out32, frames32, peaks32 = g.pcm_condition_host(cond, S, rates, out_rate)
+        out16, frames16, peaks16 = g.pcm_condition_host(cond, S, rates, out_rate, fmt=VSYN_PCM_S16)
+    finally:
+        g.close()
+    assert host["rc"] == 0
+    T = [int(t) * out_rate // r if r else 0 for t, r in zip(fr, rates)]
+    t_max = max(T)
+    assert T[0] > 0 and T[2] == 2 * int(fr[2]) and list(frames32) == T and list(frames16) == T
+    plane = t_max + 5                # of the resampled and of the conditioned planes
+    in_plane = plane // 2            # vsyn_resample_device wants room for a whole input plane resampled
+    assert int(fr.max()) <= in_plane
+    x = np.zeros((S, Cn, in_plane), np.float32)
+    for gi in range(S):
+        x[gi, :, :int(fr[gi])] = f1[gi, :int(fr[gi])].T
+    st = torch.cuda.current_stream().cuda_stream
+    d_x = torch.from_numpy(x).cuda()
+    d_fr = torch.from_numpy(fr.astype(np.int32)).cuda()
+    d_rs = torch.full((S * Cn * plane,), float("nan"), dtype=torch.float32, device="cuda")
+    d_rsf = torch.full((S,), -1, dtype=torch.int32, device="cuda")
+    synth.resample_device(rates, out_rate, d_x.data_ptr(), in_plane, Cn, d_fr.data_ptr(), d_rs.data_ptr(), plane, d_rsf.data_ptr(), st)
+    d_cd = torch.full((S * plane,), float("nan"), dtype=torch.float32, device="cuda")
+    d_pk = torch.full((S,), float("nan"), dtype=torch.float32, device="cuda")
+    synth.pcm_condition_device(cond, d_rs.data_ptr(), plane, Cn, S, d_rsf.data_ptr(), d_cd.data_ptr(), plane, d_pk.data_ptr(), st)
+    n_rows = [int(synth.lib.vsyn_spectral_num_frames(C.byref(s), t)) if r else 0 for t, r in zip(T, rates)]
+    total = sum(n_rows)
+    d_rows = torch.full((total + 2, dim), float("nan"), dtype=torch.float32, device="cuda")
+    d_off = torch.full((S + 1,), -1, dtype=torch.int64, device="cuda")
+    synth.spectral_device(s, [out_rate if r else 0 for r in rates], d_cd.data_ptr(), plane, 1, d_rsf.data_ptr(), d_rows.data_ptr(),
+                          d_off.data_ptr(), st)
+    d_post = torch.full((total + 2, dout), float("nan"), dtype=torch.float32, device="cuda")
+    synth.spectral_post_device(post, dim, n_rows, d_rows.data_ptr(), d_post.data_ptr(), st)
+    torch.cuda.synchronize()
+    assert list(d_rsf.cpu().numpy()) == T
+    off = d_off.cpu().numpy()
+    assert list(np.diff(off)) == n_rows and off[0] == 0
+    # the rows, seg_rows and peaks of the one host call
+    assert list(host["seg_rows"]) == n_rows and n_rows[1] == 0 and min(n_rows[0], n_rows[2]) >= 3
+    want_rows = d_post.cpu().numpy()
+    assert np.isnan(want_rows[total:]).all() and not np.isnan(want_rows[:total]).any()
+    assert host["rows"].shape == (total, dout) and np.array_equal(_bits(host["rows"]), _bits(want_rows[:total]))
+    pk = d_pk.cpu().numpy()
+    assert pk[1] == 0 and pk[0] > 0 and pk[2] > 0
+    assert np.array_equal(_bits(host["peaks"]), _bits(pk))
+    # the PCM of vsyn_pcm_condition_host
+    cd = d_cd.cpu().numpy().reshape(S, plane)
+    assert np.array_equal(_bits(peaks32), _bits(pk)) and np.array_equal(_bits(peaks16), _bits(pk))
+    assert out32.shape == (S, t_max) and out16.shape == (S, t_max)
+    for gi in range(S):
+        assert np.isnan(cd[gi, T[gi]:]).all() and not np.isnan(cd[gi, :T[gi]]).any(), gi
+        assert np.array_equal(_bits(out32[gi, :T[gi]]), _bits(cd[gi, :T[gi]])) and not out32[gi, T[gi]:].any(), gi
+        assert np.array_equal(out16[gi, :T[gi]], _s16(cd[gi, :T[gi]])) and not out16[gi, T[gi]:].any(), gi
