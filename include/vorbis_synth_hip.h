@@ -685,6 +685,88 @@ int vsyn_pcm_cond_spectral_host(vsyn_handle* h, const vsyn_pcm_cond* cond, const
                                 uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
                                 uint64_t* seg_rows, float* peaks_out, vsyn_status* status, const char** err);
 
+/* ---- PCM trimming: the silent head and tail of the decoded PCM cut off, computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames. Parameters: frame_length L, 1 <= L <= 8192; hop_length H,
+ * H >= 1; top_db, finite, 0 < top_db <= 200. Output: ONE mono float32 plane, out_frames, and (start, end). This is
+ * librosa.effects.trim(y, top_db, ref=np.max, frame_length=L, hop_length=H) on the mono signal. librosa is not among the test
+ * dependencies: the device is compared against a float64 model of the arithmetic below (tests/trim_model.py), and the model against
+ * a restatement in librosa's own words (tests/test_trim_cpu.py).
+ *
+ *  1. Downmix. y[t] is step 1 of the conditioning stage, the one device function the STFT and the conditioning stage use. The
+ *     decision and the output are taken on the mono signal: for a mono file that is librosa's decision. librosa's per-channel
+ *     aggregate (aggregate=np.max over the channels' frame energies) for multichannel input is NOT built.
+ *  2. Frame energies: librosa.feature.rms(center=True, pad_mode="constant"). For T >= 1, F = 1 + (T + 2 (L / 2) - L) / H frames
+ *     (integer divisions), F = 0 when that numerator is negative or T = 0. ms[f] = (1 / L) sum_{i < L} y[f H - L / 2 + i]^2, with
+ *     zeros outside [0, T). The squares and the sums are float64: a float32 squared is exact in float64, so only the summation
+ *     rounds. The order of a frame's sum is a function of L alone: lane l of 64 adds the samples l, l + 64, ... in ascending
+ *     order, the 64 partial sums are joined by a butterfly over the lane offsets 32, 16, 8, 4, 2, 1, and the sum is divided by L.
+ *     It depends on neither the tile, the grid nor the segment's place in the batch.
+ *  3. Decision: amplitude_to_db(rms, ref=np.max, amin=1e-5, top_db=None) > -top_db, written without logarithms.
+ *     E[f] = max(ms[f], 1e-10); R = max(max_f ms[f], 1e-10); k = 10^(-top_db / 10), computed once on the host in double. Frame f
+ *     is non-silent iff E[f] > R * k (one float64 product) or E[f] >= R. In real numbers the second clause adds nothing (k < 1)
+ *     and this is librosa's predicate; in float64 it keeps a loudest frame non-silent for a top_db so small that R * k rounds
+ *     to R. Parity with librosa at a rounding distance from the threshold is not claimed.
+ *  4. Bounds. f0 and f1 are the first and the last non-silent frame: start = f0 * H, end = min(T, (f1 + 1) * H). With F = 0,
+ *     start = end = 0. The frame that holds the maximum is always non-silent (k < 1), so a segment with F >= 1 is never trimmed
+ *     to nothing. For all-zero PCM, or any signal below amin, every E[f] = R: nothing is cut and (start, end) = (0, T).
+ *  5. Output: out[t] = y[start + t] for t < end - start; out_frames = end - start; nothing is written past it.
+ *  6. Not finite. A segment with an Inf or NaN sample among its T frames (in any channel's contribution to y, whether or not a
+ *     frame covers it) is refused alone: it gets (0, 0), out_frames 0, and its entry of the ref array (R) is not finite. The
+ *     other segments of the call are not affected.
+ *  7. Order in the pipeline: decode, resample per channel (if asked), downmix and trim, peak, pre-emphasis, then PCM out or STFT,
+ *     then the post stage. The peak is the peak of the trimmed signal, the pre-emphasis starts at z[0] = y1[start], "fewer frames
+ *     than the delta width" applies to the trimmed rows, and (start, end) are in samples of the resampled signal.
+ *  8. Checks (VSYN_ERR_INVALID before anything runs): L or H out of range; top_db not finite or outside (0, 200]; channels = 0.
+ *
+ * Not built: librosa.effects.split, the per-channel aggregate, a ref other than the maximum. No floating-point atomics and no
+ * atomics at all: the same PCM gives the same bits, alone, in any slot of a batch and at any alignment. A NULL vsyn_pcm_trim means
+ * the stage is off: nothing is launched and every entry point that takes one returns what its counterpart without the stage
+ * returns, bit for bit. The trim entry points read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept
+ * by VSYN_SUBMIT_KEEP_PCM, and a later vsyn_pcm_fetch_host returns the same PCM. One handle's trim entry points share its trim
+ * workspace. */
+#define VSYN_TRIM_MAX_FRAME 8192u
+
+typedef struct vsyn_pcm_trim {
+  uint32_t frame_length; /* L */
+  uint32_t hop_length;   /* H */
+  double top_db;         /* in (0, 200] */
+} vsyn_pcm_trim;
+
+/* F of step 2 for a segment of `frames` PCM frames, 0 for an invalid spec. */
+uint64_t vsyn_pcm_trim_num_frames(const vsyn_pcm_trim* trim, uint64_t frames);
+
+/* The caller's planar PCM: d_pcm[(g * channels + c) * plane_stride + t], d_frames[S] (device) frames per segment (clamped to
+ * plane_stride and to out_plane_stride). Writes d_out[g * out_plane_stride + t] for t < out_frames(g), nothing past it;
+ * d_out_frames[S] (device, uint32); d_bounds[S][2] (device, uint32: start, end); d_ref[S] (device, double, may be NULL): R, not
+ * finite for a refused segment; d_ms (device, double, may be NULL): d_ms[g * ms_stride + f] = ms[f] for f < F(g), ms_stride at
+ * least vsyn_pcm_trim_num_frames(trim, min(plane_stride, out_plane_stride)). d_out with d_out_frames is in the input form of
+ * vsyn_pcm_condition_device and vsyn_spectral_device with channels = 1. Asynchronous on hip_stream. */
+int vsyn_pcm_trim_device(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t num_segments, const float* d_pcm, uint64_t plane_stride,
+                         uint32_t channels, const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride, uint32_t* d_out_frames,
+                         uint32_t* d_bounds, double* d_ref, double* d_ms, uint64_t ms_stride, void* hip_stream, const char** err);
+
+/* vsyn_pcm_condition_host with the trim in front of the conditioning: resample (out_rate != 0), downmix and trim, condition (cond
+ * may be NULL with a trim: the trimmed downmix as it is; peaks_out then holds zeros), PCM out as one mono plane per segment.
+ * frames_out[S] receives each segment's out_frames; bounds_out[S][2] (uint32, may be NULL) its (start, end); refs_out[S] (double,
+ * may be NULL) its R (not finite: refused, step 6); peaks_out as for vsyn_pcm_condition_host. out_stride_frames is checked against
+ * the UNTRIMMED T, which is known before the launch and bounds the result; with out = NULL nothing is launched and frames_out
+ * receives that untrimmed T. trim = NULL is vsyn_pcm_condition_host (bounds_out and refs_out are not written). Synchronous. */
+int vsyn_pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t num_segments, const uint32_t* in_rates,
+                       uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
+                       float* peaks_out, double* refs_out, const char** err);
+
+/* vsyn_pcm_cond_spectral_host with the trim in it: resample, downmix and trim, condition (cond != NULL), spectral rows, post stage
+ * (post != NULL). The row counts of the later stages are the host's to give, so this form reads the bounds back once between the
+ * trim and the spectral launches (S * 8 bytes and one wait). seg_rows are the rows of the trimmed segments; a refused segment
+ * (refs_out not finite) and, with post->order > 0, a segment trimmed to 0 < F < post->width get 0 rows and fail alone: the caller
+ * sees the latter from bounds_out. With rows = NULL the resampler and the trim still run, for the counts. trim = NULL is
+ * vsyn_pcm_cond_spectral_host (bounds_out and refs_out are not written). Synchronous. */
+int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                const vsyn_spectral_post* post, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                                float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out,
+                                double* refs_out, vsyn_status* status, const char** err);
+
 #ifdef __cplusplus
 }
 #endif

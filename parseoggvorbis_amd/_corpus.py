@@ -31,7 +31,11 @@ def load():
                        ("ogg_vorbis_spectral_corpus_cond", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPost),
                                                             C.POINTER(binding.PcmCond), vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus", [u32, C.c_int, vp, vp, vp, vp, vp]),
-                       ("ogg_vorbis_pcm_corpus_cond", [u32, C.c_int, C.POINTER(binding.PcmCond), vp, vp, vp, vp, vp])):
+                       ("ogg_vorbis_spectral_corpus_trim", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPost),
+                                                            C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), vp, vp, vp, vp]),
+                       ("ogg_vorbis_pcm_corpus_cond", [u32, C.c_int, C.POINTER(binding.PcmCond), vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_pcm_corpus_trim", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), vp, vp, vp, vp,
+                                                       vp, vp])):
         fn = getattr(lib, name)
         fn.argtypes = head + args + tail
         fn.restype = C.c_int

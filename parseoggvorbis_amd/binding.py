@@ -76,6 +76,10 @@ class PcmCond(C.Structure):  # vsyn_pcm_cond
     _fields_ = [("options", C.c_uint32), ("reserved", C.c_uint32), ("preemphasis", C.c_double)]
 
 
+class PcmTrim(C.Structure):  # vsyn_pcm_trim
+    _fields_ = [("frame_length", C.c_uint32), ("hop_length", C.c_uint32), ("top_db", C.c_double)]
+
+
 class Status(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("first_bad_packet", C.c_uint32)]
 
@@ -204,6 +208,7 @@ _SYMBOLS = [
     "vsyn_resample_num_frames", "vsyn_resample_device", "vsyn_pcm_resample_host", "vsyn_pcm_resample_spectral_host",
     "vsyn_spectral_post_dim", "vsyn_spectral_post_device", "vsyn_pcm_spectral_post_host",
     "vsyn_pcm_condition_device", "vsyn_pcm_condition_host", "vsyn_pcm_cond_spectral_host",
+    "vsyn_pcm_trim_num_frames", "vsyn_pcm_trim_device", "vsyn_pcm_trim_host", "vsyn_pcm_trim_spectral_host",
 ]
 
 
@@ -281,6 +286,12 @@ def load():
     lib.vsyn_pcm_condition_host.argtypes = [vp, C.POINTER(PcmCond), u32, vp, u32, C.c_int, vp, u64, vp, vp, cpp]
     lib.vsyn_pcm_cond_spectral_host.argtypes = [vp, C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPost), u32, vp, u32, vp,
                                                 u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_pcm_trim_num_frames.argtypes = [C.POINTER(PcmTrim), u64]
+    lib.vsyn_pcm_trim_num_frames.restype = u64
+    lib.vsyn_pcm_trim_device.argtypes = [vp, C.POINTER(PcmTrim), u32, vp, u64, u32, vp, vp, u64, vp, vp, vp, vp, u64, vp, cpp]
+    lib.vsyn_pcm_trim_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), u32, vp, u32, C.c_int, vp, u64, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_trim_spectral_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPost),
+                                                u32, vp, u32, vp, u64, vp, vp, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -508,6 +519,64 @@ class Synth:
         if rc not in (VSYN_OK, VSYN_ERR_STREAM):
             raise VsynError(rc, (err.value or b"").decode())
         return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], peaks=peaks[:S], flags=st.flags)
+
+    def pcm_trim_device(self, trim, d_pcm, plane_stride, channels, num_segments, d_frames, d_out, out_plane_stride, d_out_frames, d_bounds,
+                        d_ref=None, d_ms=None, ms_stride=0, stream=None):
+        """vsyn_pcm_trim_device on device pointers (ints)."""
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pcm_trim_device(self.h, None if trim is None else C.byref(trim), num_segments, d_pcm, plane_stride, channels, d_frames,
+                                           d_out, out_plane_stride, d_out_frames, d_bounds, d_ref, d_ms, ms_stride, stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+
+    def pcm_trim_host(self, trim, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_trim_host over the last submit's segments (trim / cond may be None): returns dict(pcm [S][stride] float32 or
+        int16, frames [S], bounds [S][2], peaks [S], refs [S]), stride = the largest untrimmed T."""
+        S = num_segments
+        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
+        frames = np.zeros(max(1, S), np.uint64)
+        peaks = np.zeros(max(1, S), np.float32)
+        bounds = np.zeros((max(1, S), 2), np.uint32)
+        refs = np.zeros(max(1, S), np.float64)
+        err = C.c_char_p()
+        tp = None if trim is None else C.byref(trim)
+        cp = None if cond is None else C.byref(cond)
+        rc = self.lib.vsyn_pcm_trim_host(self.h, tp, cp, S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), None, None, None, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        stride = max(1, int(frames[:S].max()) if S else 1)
+        out = np.zeros((S, stride), np.float32 if fmt == VSYN_PCM_F32 else np.int16)
+        rc = self.lib.vsyn_pcm_trim_host(self.h, tp, cp, S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames), _ptr(bounds),
+                                         _ptr(peaks), _ptr(refs), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(pcm=out, frames=frames[:S], bounds=bounds[:S], peaks=peaks[:S], refs=refs[:S])
+
+    def pcm_trim_spectral_host(self, trim, cond, spec, post, in_rates, out_rate=0):
+        """vsyn_pcm_trim_spectral_host over the last submit's segments (trim / cond / post may be None): returns dict(rc, rows
+        [total][D_out], seg_rows [S], bounds [S][2], peaks [S], refs [S], flags)."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S = len(rates)
+        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + (post.order if post is not None else 0))
+        seg_rows = np.zeros(max(S, 1), np.uint64)
+        peaks = np.zeros(max(S, 1), np.float32)
+        bounds = np.zeros((max(1, S), 2), np.uint32)
+        refs = np.zeros(max(1, S), np.float64)
+        st, err = Status(), C.c_char_p()
+        tp = None if trim is None else C.byref(trim)
+        cp = None if cond is None else C.byref(cond)
+        pp = None if post is None else C.byref(post)
+        rc = self.lib.vsyn_pcm_trim_spectral_host(self.h, tp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None,
+                                                  None, None, C.byref(st), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum())
+        rows = np.zeros((max(total, 1), dout), np.float32)
+        rc = self.lib.vsyn_pcm_trim_spectral_host(self.h, tp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows),
+                                                  _ptr(bounds), _ptr(peaks), _ptr(refs), C.byref(st), C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], bounds=bounds[:S], peaks=peaks[:S], refs=refs[:S], flags=st.flags)
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

@@ -24,6 +24,7 @@
 #include "vsyn_spectral_post.h"
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
+#include "vsyn_trim.h"
 
 static const uint32_t k_inverse_db_bits[256] = {
 #include "vorbis_floor1_inverse_db.inc"
@@ -120,6 +121,7 @@ struct vsyn_handle {
   PostWs pp;                           // vsyn_spectral_post.h
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
+  TrimWs tr;                           // vsyn_trim.h
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -1278,29 +1280,50 @@ static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates,
   return VSYN_OK;
 }
 
+// The trim stage of a chain: its spec and where its bounds and refs go (host, either may be NULL).
+struct TrimArgs {
+  const vsyn_pcm_trim* spec;
+  uint32_t* bounds_out;
+  double* refs_out;
+};
+
 // The chain on the host stream, from the last host submit's PCM to *v: with out_rate != 0 every segment resampled from rates[g] to
-// out_rate into h->rs's plane of rs_plane frames; with cond != NULL conditioned into h->cd's mono plane of cd_plane frames, the peaks
-// on their way to peaks_out. t_max bounds every segment's frames; zero clears the last plane first: zeros past each segment's
-// frames. Caller holds h->mu and has run rs_check / cond_check; its checks of its own buffers sit between last_submit_frames and this.
+// out_rate into h->rs's plane of rs_plane frames; with trim != NULL downmixed and trimmed into h->tr's mono plane (of mono_plane
+// frames when it is the last stage, of t_max frames in front of the conditioning), the bounds and refs on their way to the host;
+// with cond != NULL conditioned into h->cd's mono plane of mono_plane frames, the peaks on their way to peaks_out. t_max bounds
+// every segment's frames; zero clears the last plane first: zeros past each segment's frames. Caller holds h->mu and has run
+// rs_check / trim_check / cond_check; its checks of its own buffers sit between last_submit_frames and this.
 static int pcm_chain(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, uint64_t rs_plane, const vsyn_pcm_cond* cond,
-                     uint64_t cd_plane, uint64_t t_max, bool zero, float* peaks_out, PcmView* v, const char** err) {
+                     uint64_t mono_plane, uint64_t t_max, bool zero, float* peaks_out, PcmView* v, const char** err,
+                     const TrimArgs* trim = nullptr) {
   const uint32_t C = h->H.channels;
   hipStream_t hs = h->host_stream;
   *v = PcmView{h->st_pcm.p, h->last_host_plane, C, h->ws_seg[h->last_wb].p, nullptr};
   if (out_rate) {
     const size_t n = (size_t)S * C * rs_plane;
     HIPCHK(h->rs.pcm.ensure(n + 1));
-    if (zero && !cond) HIPCHK(hipMemsetAsync(h->rs.pcm.p, 0, sizeof(float) * n, hs));
+    if (zero && !cond && !trim) HIPCHK(hipMemsetAsync(h->rs.pcm.p, 0, sizeof(float) * n, hs));
     if (int rc = rs_launch(h->rs, h->device, S, rates, out_rate, v->pcm, v->plane, C, nullptr, v->si, h->rs.pcm.p, rs_plane, nullptr, hs, err)) return rc;
     *v = PcmView{h->rs.pcm.p, rs_plane, C, nullptr, h->rs.outF.p};
   }
+  if (trim) {  // the next stage reads the trimmed mono plane as 1-channel PCM, with the frames the stage wrote
+    const uint64_t tr_plane = cond ? std::max<uint64_t>(t_max, 1) : mono_plane;
+    const size_t n = (size_t)S * tr_plane;
+    HIPCHK(h->tr.pcm.ensure(n + 1));
+    if (zero && !cond) HIPCHK(hipMemsetAsync(h->tr.pcm.p, 0, sizeof(float) * n, hs));
+    if (int rc = trim_launch(h->tr, h->device, trim->spec, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, h->tr.pcm.p, tr_plane, nullptr,
+                             nullptr, nullptr, nullptr, 0, hs, err))
+      return rc;
+    if (int rc = trim_fetch_bounds(h->tr, S, trim->bounds_out, trim->refs_out, hs, err)) return rc;
+    *v = PcmView{h->tr.pcm.p, tr_plane, 1u, nullptr, h->tr.frames.p};
+  }
   if (cond) {  // the next stage reads the conditioned mono plane as 1-channel PCM, with the frames the stage wrote
-    const size_t n = (size_t)S * cd_plane;
+    const size_t n = (size_t)S * mono_plane;
     HIPCHK(h->cd.pcm.ensure(n + 1));
     if (zero) HIPCHK(hipMemsetAsync(h->cd.pcm.p, 0, sizeof(float) * n, hs));
-    if (int rc = cond_launch(h->cd, h->device, cond, S, v->pcm, v->plane, C, v->d_frames, v->si, t_max, h->cd.pcm.p, cd_plane, nullptr, hs, err)) return rc;
+    if (int rc = cond_launch(h->cd, h->device, cond, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, h->cd.pcm.p, mono_plane, nullptr, hs, err)) return rc;
     if (int rc = cond_fetch_peaks(h->cd, cond, S, peaks_out, hs, err)) return rc;
-    *v = PcmView{h->cd.pcm.p, cd_plane, 1u, nullptr, h->cd.frames.p};
+    *v = PcmView{h->cd.pcm.p, mono_plane, 1u, nullptr, h->cd.frames.p};
   }
   return VSYN_OK;
 }
@@ -1321,6 +1344,29 @@ static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format
   }
   HIPCHK(hipStreamSynchronize(hs));
   return VSYN_OK;
+}
+
+// The end of a spectral host form: the rows of the view's PCM on the host stream (post != NULL: on to the post stage in their
+// place, and its wider rows come back), copied to rows, then the call's wait and status. seg_rows, f_max and total are the host's
+// row counts. Caller holds h->mu.
+static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S, const uint32_t* spec_rates,
+                             const PcmView& v, const uint64_t* seg_rows, uint64_t f_max, uint64_t total, float* rows, vsyn_status* status,
+                             const char** err) {
+  hipStream_t hs = h->host_stream;
+  const uint64_t D = spec_dim(spec);
+  HIPCHK(h->sp.rows.ensure(total * D + 1));
+  int rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err);
+  if (rc) return rc;
+  if (post) {
+    const uint64_t Dout = D * (1u + post->order);
+    HIPCHK(h->pp.rows.ensure(total * Dout + 1));
+    rc = post_launch(h->pp, h->device, post, (uint32_t)D, S, seg_rows, h->sp.rows.p, h->pp.rows.p, hs, err);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(rows, h->pp.rows.p, sizeof(float) * total * Dout, hipMemcpyDeviceToHost, hs));
+  } else {
+    HIPCHK(hipMemcpyAsync(rows, h->sp.rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+  }
+  return sync_status_into(h, status, err);
 }
 
 // vsyn_pcm_spectral_host, and with out_rate != 0 vsyn_pcm_resample_spectral_host: the rows of the last host submit's PCM, each
@@ -1378,20 +1424,81 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   PcmView v;  // the spectral pass reads the synthesis PCM with the last submit's SegInfo, or what the chain made of it
   rc = pcm_chain(h, S, rates, out_rate, t_max, cond, t_max, t_max, false, peaks_out, &v, err);
   if (rc) return rc;
-  const uint64_t D = spec_dim(spec);
-  HIPCHK(h->sp.rows.ensure(total * D + 1));
-  rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err);
+  return spectral_rows_out(h, spec, post, S, spec_rates, v, seg_rows, f_max, total, rows, status, err);
+}
+
+// vsyn_pcm_trim_spectral_host with a trim: the chain up to the trimmed plane, the bounds back to the host (the later stages take
+// their row counts from there), then conditioning, spectral rows and the post stage on the trimmed plane.
+static int pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                  const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows,
+                                  uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out, double* refs_out,
+                                  vsyn_status* status, const char** err) {
+  status_reset(status);
+  int rc = trim_check(trim, err);
   if (rc) return rc;
-  if (post) {  // the rows go on to the post stage in their place, and its wider rows come back
-    const uint64_t Dout = D * (1u + post->order);
-    HIPCHK(h->pp.rows.ensure(total * Dout + 1));
-    rc = post_launch(h->pp, h->device, post, (uint32_t)D, S, seg_rows, h->sp.rows.p, h->pp.rows.p, hs, err);
+  if (cond) {
+    rc = cond_check(cond, err);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(rows, h->pp.rows.p, sizeof(float) * total * Dout, hipMemcpyDeviceToHost, hs));
-  } else {
-    HIPCHK(hipMemcpyAsync(rows, h->sp.rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
   }
-  return sync_status_into(h, status, err);
+  std::vector<uint32_t> sp_rates(S);  // the rates the spectral pass sees: 0 skips a segment
+  if (out_rate) {
+    rc = rs_check(S, rates, out_rate, err);
+    if (rc) return rc;
+    for (uint32_t g = 0; g < S; ++g) sp_rates[g] = rates[g] ? out_rate : 0u;
+  } else {
+    for (uint32_t g = 0; g < S; ++g) sp_rates[g] = rates ? rates[g] : 0u;
+  }
+  rc = spec_check(spec, S, sp_rates.data(), err);
+  if (rc) return rc;
+  if (post) {
+    rc = post_check(post, err, post->order <= 2 ? spec_dim(spec) * (1u + post->order) : 0u);
+    if (rc) return rc;
+    if (!post_on(post)) post = nullptr;
+  }
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
+  if (bounds_out) memset(bounds_out, 0, sizeof(uint32_t) * 2u * S);
+  if (refs_out) memset(refs_out, 0, sizeof(double) * S);
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T(S);
+  uint64_t t_max;
+  rc = last_submit_frames(h, S, rates, out_rate, T.data(), &t_max, err);
+  if (rc) return rc;
+  if (S == 0) return VSYN_OK;
+  t_max = std::max<uint64_t>(t_max, 1);
+  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  hipStream_t hs = h->host_stream;
+  std::vector<uint32_t> bounds(2u * (size_t)S);
+  std::vector<double> refs(S);
+  const TrimArgs ta{trim, bounds.data(), refs.data()};
+  PcmView v;
+  rc = pcm_chain(h, S, rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err, &ta);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(hs));  // the one read-back of this form: S * 8 bytes of bounds (and the refs)
+  if (bounds_out) memcpy(bounds_out, bounds.data(), sizeof(uint32_t) * bounds.size());
+  if (refs_out) memcpy(refs_out, refs.data(), sizeof(double) * S);
+  const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
+  uint64_t total = 0, f_max = 0;
+  for (uint32_t g = 0; g < S; ++g) {
+    uint64_t f = sp_rates[g] && std::isfinite(refs[g]) ? spec_num_frames(spec->n_fft, spec->hop_length, center, bounds[2u * g + 1u] - bounds[2u * g]) : 0;
+    if (post && post->order && f && f < post->width) f = 0;  // trimmed below the delta width: fails alone
+    if (!f) sp_rates[g] = 0u;
+    seg_rows[g] = f;
+    total += f;
+    f_max = std::max(f_max, f);
+  }
+  if (!rows || total == 0) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (cond) {
+    HIPCHK(h->cd.pcm.ensure((size_t)S * t_max + 1));
+    rc = cond_launch(h->cd, h->device, cond, S, v.pcm, v.plane, 1u, v.d_frames, nullptr, t_max, h->cd.pcm.p, t_max, nullptr, hs, err);
+    if (rc) return rc;
+    rc = cond_fetch_peaks(h->cd, cond, S, peaks_out, hs, err);
+    if (rc) return rc;
+    v = PcmView{h->cd.pcm.p, t_max, 1u, nullptr, h->cd.frames.p};
+  }
+  return spectral_rows_out(h, spec, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err);
 }
 
 extern "C" {
@@ -1517,6 +1624,76 @@ int vsyn_pcm_condition_host(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t 
   rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err);
   if (rc) return rc;
   return pcm_copy_out(h, v, S, format, h->cd.s16, out, err);
+}
+
+uint64_t vsyn_pcm_trim_num_frames(const vsyn_pcm_trim* trim, uint64_t frames) {
+  if (trim_check(trim, nullptr) != VSYN_OK) return 0;
+  return trim_num_frames(frames, trim->frame_length, trim->hop_length);
+}
+
+int vsyn_pcm_trim_device(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t S, const float* d_pcm, uint64_t plane_stride, uint32_t channels,
+                         const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride, uint32_t* d_out_frames, uint32_t* d_bounds,
+                         double* d_ref, double* d_ms, uint64_t ms_stride, void* hip_stream, const char** err) {
+  if (!h) return cond_no_handle(err);
+  int rc = trim_check(trim, err);
+  if (rc) return rc;
+  if (channels == 0 || channels > 255) return fail(err, VSYN_ERR_INVALID, "channels %u outside [1, 255]", channels);
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_out || !d_out_frames || !d_bounds || plane_stride == 0 || out_plane_stride == 0)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer or zero stride");
+  if (plane_stride > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return trim_launch(h->tr, h->device, trim, S, d_pcm, plane_stride, channels, d_frames, nullptr, plane_stride, d_out, out_plane_stride, d_out_frames,
+                     d_bounds, d_ref, d_ms, ms_stride, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
+                       uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
+                       float* peaks_out, double* refs_out, const char** err) {
+  if (!trim) return vsyn_pcm_condition_host(h, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
+  if (!h) return cond_no_handle(err);
+  int rc = trim_check(trim, err);
+  if (rc) return rc;
+  if (cond) {
+    rc = cond_check(cond, err);
+    if (rc) return rc;
+  }
+  if (out_rate) {
+    rc = rs_check(S, in_rates, out_rate, err);
+    if (rc) return rc;
+  }
+  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
+  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
+  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
+  // the lock covers the whole call: the resample, trim and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t t_max;
+  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
+  if (rc) return rc;
+  if (!out || S == 0) return VSYN_OK;
+  if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
+                                             (unsigned long long)out_stride_frames, (unsigned long long)t_max);
+  if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
+  std::vector<uint32_t> bounds(2u * (size_t)S);
+  const TrimArgs ta{trim, bounds.data(), refs_out};
+  PcmView v;  // resampled into a plane as long as the longest segment, trimmed, conditioned into the caller's stride
+  rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err, &ta);
+  if (rc) return rc;
+  rc = pcm_copy_out(h, v, S, format, cond ? h->cd.s16 : h->tr.s16, out, err);
+  if (rc) return rc;
+  for (uint32_t g = 0; g < S; ++g) frames_out[g] = bounds[2u * g + 1u] - bounds[2u * g];
+  if (bounds_out) memcpy(bounds_out, bounds.data(), sizeof(uint32_t) * bounds.size());
+  return VSYN_OK;
+}
+
+int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                                uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out, double* refs_out,
+                                vsyn_status* status, const char** err) {
+  if (!trim) return vsyn_pcm_cond_spectral_host(h, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, peaks_out, status, err);
+  if (!h) return cond_no_handle(err);
+  return pcm_trim_spectral_host(h, trim, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, bounds_out, peaks_out, refs_out,
+                                status, err);
 }
 
 }  // extern "C"

@@ -401,6 +401,7 @@ struct Feeder {
     std::vector<uint64_t> frames;
     std::vector<std::string> err;
     std::vector<double> digest;  // per (file, channel), from the device
+    std::vector<uint32_t> bounds;  // trim run: per file (start, end)
     uint64_t plane = 0;
   };
 
@@ -477,6 +478,15 @@ struct Feeder {
       if (o.err[s].empty() && !std::isfinite(peaks[s])) o.err[s] = "condition: the peak of the downmixed PCM is not finite";
   }
 
+  // A file the trim stage refused (include/vorbis_synth_hip.h, "PCM trimming", step 6) gets an error of its own.
+  void refuse_refs(const std::vector<double>& refs, Outcome& o) {
+    for (size_t s = 0; s < refs.size(); ++s)
+      if (o.err[s].empty() && !std::isfinite(refs[s])) o.err[s] = "trim: the PCM holds a sample that is not finite";
+  }
+
+  // the conditioning spec of a trim run: NULL when the trimmed downmix is delivered as it is
+  const vsyn_pcm_cond* trim_cond() const { return opts.cond.options ? &opts.cond : nullptr; }
+
   // Conditioned PCM run: each file's PCM, resampled first in a resampled run (resample_stage has set the frames and refused what
   // the resampler refuses), through vsyn_pcm_condition_host: one mono plane per file comes back.
   OkOrError condition_stage(Group& g, Outcome& o) {
@@ -492,6 +502,22 @@ struct Feeder {
     const char* err = nullptr;
     std::vector<uint64_t> got(S);
     std::vector<float> peaks(S);
+    if (opts.trim) {  // the trim in front: the frames delivered are the trimmed ones
+      std::vector<double> refs(S);
+      o.bounds.assign(2u * (size_t)S, 0u);
+      const int rc = vsyn_pcm_trim_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate,
+                                        opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32, opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, pl,
+                                        got.data(), o.bounds.data(), peaks.data(), refs.data(), &err);
+      if (rc != VSYN_OK) return OkOrError(std::string("GPU trim layer: ") + (err ? err : "trim failed"));
+      for (uint32_t s = 0; s < S; ++s) {
+        CHECK(got[s] <= o.frames[s]);
+        o.frames[s] = got[s];
+      }
+      refuse_refs(refs, o);
+      refuse_peaks(peaks, o);
+      o.plane = pl;
+      return OkOrError();
+    }
     const int rc = vsyn_pcm_condition_host(g.handle, &opts.cond, S, rates.data(), opts.resample_rate, opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32,
                                            opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, pl, got.data(), peaks.data(), &err);
     if (rc != VSYN_OK) return OkOrError(std::string("GPU conditioning layer: ") + (err ? err : "conditioning failed"));
@@ -519,7 +545,7 @@ struct Feeder {
         o.err[s] = buf;
       }
       uint64_t F = o.err[s].empty() ? vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(o.frames[s], o.plane)) : 0;
-      if (opts.post.order && F && F < opts.post.width) {  // fewer frames than the delta window: this file's error, not the submit's
+      if (!opts.trim && opts.post.order && F && F < opts.post.width) {  // fewer frames than the delta window: this file's error, not the submit's
         char buf[96];
         snprintf(buf, sizeof(buf), "spectral: delta width %u needs %u frames, file has %llu", opts.post.width, opts.post.width,
                  (unsigned long long)F);
@@ -534,7 +560,12 @@ struct Feeder {
     vsyn_status st;
     const char* err = nullptr;
     std::vector<float> peaks(S);
-    const int rc = opts.condition ? vsyn_pcm_cond_spectral_host(g.handle, &opts.cond, &opts.spectral, post_run(opts) ? &opts.post : nullptr, S,
+    std::vector<double> refs(S);
+    if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);  // spec_rows, from the untrimmed frames, bounds the trimmed rows
+    const int rc = opts.trim    ? vsyn_pcm_trim_spectral_host(g.handle, &opts.trim_spec, trim_cond(), &opts.spectral, post_run(opts) ? &opts.post : nullptr,
+                                                              S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(),
+                                                              peaks.data(), refs.data(), &st, &err)
+                   : opts.condition ? vsyn_pcm_cond_spectral_host(g.handle, &opts.cond, &opts.spectral, post_run(opts) ? &opts.post : nullptr, S,
                                                                 rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p,
                                                                 peaks.data(), &st, &err)
                    : post_run(opts) ? vsyn_pcm_spectral_post_host(g.handle, &opts.spectral, &opts.post, S, rates.data(), opts.resample_rate,
@@ -547,6 +578,20 @@ struct Feeder {
       for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
     } else if (rc != VSYN_OK) {
       return OkOrError(std::string("GPU spectral layer: ") + (err ? err : "spectral failed"));
+    }
+    if (opts.trim && rc == VSYN_OK) {
+      refuse_refs(refs, o);
+      for (uint32_t s = 0; s < S; ++s) {
+        if (!o.err[s].empty()) continue;
+        o.frames[s] = o.bounds[2u * s + 1u] - o.bounds[2u * s];
+        const uint64_t F = vsyn_spectral_num_frames(&opts.spectral, o.frames[s]);
+        if (opts.post.order && F && F < opts.post.width) {  // trimmed to fewer frames than the delta window
+          char buf[96];
+          snprintf(buf, sizeof(buf), "spectral: delta width %u needs %u frames, file has %llu", opts.post.width, opts.post.width,
+                   (unsigned long long)F);
+          o.err[s] = buf;
+        }
+      }
     }
     if (opts.condition) refuse_peaks(peaks, o);
     return OkOrError();
@@ -569,6 +614,10 @@ struct Feeder {
       if (opts.checksum && !o.digest.empty()) acc += o.digest[(size_t)s * C + c];
     }
     out.frames = frames;
+    if (!o.bounds.empty()) {
+      out.trim_start = o.bounds[2u * s];
+      out.trim_end = o.bounds[2u * s + 1u];
+    }
     out.abs_sum = acc;
     out.status = o.err[s].empty() ? r.status : OkOrError(o.err[s]);
     if (opts.resample_rate) out.sample_rate = opts.resample_rate;
@@ -952,12 +1001,21 @@ int malloc_corpus(const char* name, const uint8_t* const* datas, const size_t* l
   return call_result(r, corpus_error_buf, error_out);
 }
 
+// A file's (start, end) of a trim run into bounds_out[i][2] (zeros for a failed file, and without the stage).
+void give_bounds(uint64_t* bounds_out, size_t i, const CorpusFileResult& res, bool bad) {
+  if (!bounds_out) return;
+  bounds_out[2 * i] = bad ? 0 : res.trim_start;
+  bounds_out[2 * i + 1] = bad ? 0 : res.trim_end;
+}
+
 // A rows run (features or spectral, as set in opts).
 int rows_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts, float** rows_out,
-                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
+                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out,
+                uint64_t* bounds_out = nullptr) {
   return malloc_corpus(name, datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
-                       [&](size_t i, const CorpusFileResult& res, bool) {
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
                          if (rows_count_out) rows_count_out[i] = res.feature_rows;
+                         give_bounds(bounds_out, i, res, bad);
                        });
 }
 
@@ -979,7 +1037,8 @@ namespace {
 int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                     const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
-                    const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr) {
+                    const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr,
+                    const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
@@ -991,7 +1050,13 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
     opts.condition = true;
     opts.cond = *cond;
   }
-  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+  if (trim) {
+    if (!vsyn_pcm_trim_num_frames(trim, 1)) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid trim spec", error_out);
+    opts.condition = opts.trim = true;  // the rows come from the trimmed mono plane
+    opts.trim_spec = *trim;
+  }
+  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out,
+                     bounds_out);
 }
 
 }  // namespace
@@ -1030,6 +1095,15 @@ extern "C" int ogg_vorbis_spectral_corpus_cond(const uint8_t* const* datas, cons
                          target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond);
 }
 
+extern "C" int ogg_vorbis_spectral_corpus_trim(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                               uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                               const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim,
+                                               float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out, uint8_t* ok_out,
+                                               const char** error_out_per_file, double* stats_out, const char** error_out) {
+  return spectral_corpus("ogg_vorbis_spectral_corpus_trim", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
+                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, trim, bounds_out);
+}
+
 extern "C" int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                      uint32_t files_per_submit, int device, uint32_t target_rate, int format, void** pcm_out, uint64_t* frames_out,
                                      uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file,
@@ -1042,6 +1116,15 @@ extern "C" int ogg_vorbis_pcm_corpus_cond(const uint8_t* const* datas, const siz
                                           uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
                                           void** pcm_out, uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint8_t* ok_out,
                                           const char** error_out_per_file, double* stats_out, const char** error_out) {
+  return ogg_vorbis_pcm_corpus_trim(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, nullptr,
+                                    pcm_out, frames_out, channels_out, rate_out, nullptr, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+extern "C" int ogg_vorbis_pcm_corpus_trim(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                          const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out,
+                                          uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
+                                          double* stats_out, const char** error_out) {
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
     return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
   CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
@@ -1051,11 +1134,17 @@ extern "C" int ogg_vorbis_pcm_corpus_cond(const uint8_t* const* datas, const siz
     opts.condition = true;
     opts.cond = *cond;
   }
+  if (trim) {
+    if (!vsyn_pcm_trim_num_frames(trim, 1)) return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus_trim: invalid trim spec", error_out);
+    opts.condition = opts.trim = true;  // one mono plane per file
+    opts.trim_spec = *trim;
+  }
   return malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
                        [&](size_t i, const CorpusFileResult& res, bool bad) {
                          if (frames_out) frames_out[i] = bad ? 0 : res.frames;
                          if (channels_out) channels_out[i] = res.channels;
                          if (rate_out) rate_out[i] = res.sample_rate;
+                         give_bounds(bounds_out, i, res, bad);
                        });
 }
 

@@ -38,6 +38,7 @@ struct CorpusFileResult {
   uint64_t frames = 0;   // PCM frames (samples per channel) produced
   double abs_sum = 0;    // sum |x| over all channels, in double: a cheap content check that does not need the PCM kept
   uint64_t feature_rows = 0;  // CorpusOptions::features / spectral: rows delivered
+  uint64_t trim_start = 0, trim_end = 0;  // CorpusOptions::trim: the samples kept, [trim_start, trim_end) of the (resampled) signal
 };
 
 struct CorpusCallbacks {
@@ -93,6 +94,12 @@ struct CorpusOptions {
   // whose peak is not finite fails alone. Not for feature runs. The default is off: today's output.
   bool condition = false;
   vsyn_pcm_cond cond = {0, 0, 0.0};
+  // trim (needs condition: the output is the mono plane): the silent head and tail of each file's downmix are cut on the device in
+  // front of the peak and the pre-emphasis (include/vorbis_synth_hip.h, "PCM trimming"). frames in the results are the trimmed
+  // ones, trim_start / trim_end the samples kept; a spectral run computes its rows (and "fewer frames than the delta width") from
+  // the trimmed plane. A file with a sample that is not finite fails alone. The default is off: today's output.
+  bool trim = false;
+  vsyn_pcm_trim trim_spec = {2048, 512, 60.0};
 };
 
 struct CorpusStats {
@@ -172,6 +179,22 @@ int ogg_vorbis_spectral_corpus_cond(const uint8_t* const* datas, const size_t* l
                                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                                     const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, float** rows_out, uint64_t* rows_count_out,
                                     uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
+// ogg_vorbis_pcm_corpus_cond with the trim in front of the conditioning (CorpusOptions::trim_spec = *trim): one mono plane per file,
+// cond = NULL: the trimmed downmix as it is. bounds_out (may be NULL) receives per file (start, end), two uint64 each: the samples
+// of the (resampled) signal that were kept; frames_out their count. trim = NULL is ogg_vorbis_pcm_corpus_cond (bounds_out: zeros).
+int ogg_vorbis_pcm_corpus_trim(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                               uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                               const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out,
+                               uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                               const char** error_out);
+// ogg_vorbis_spectral_corpus_cond with the trim in it: resample, trim, condition (cond != NULL), spectral rows, post stage. A file
+// trimmed to fewer frames than post->width (order > 0) fails alone. bounds_out as above. trim = NULL is
+// ogg_vorbis_spectral_corpus_cond (bounds_out: zeros).
+int ogg_vorbis_spectral_corpus_trim(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                    const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, float** rows_out,
+                                    uint64_t* rows_count_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
+                                    double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
 }
 

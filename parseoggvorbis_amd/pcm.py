@@ -6,6 +6,8 @@ in include/vorbis_synth_hip.h ("resampling") and the float64 model in tests/resa
 mono=True returns ONE plane per file, made on the device by the conditioning stage (include/vorbis_synth_hip.h, "PCM
 conditioning"; float64 model: tests/condition_model.py): the channels' float32 mean like librosa.load's default, optionally
 divided by its peak (peak_normalize) and pre-emphasised (preemphasis), after the resampling and before the copy to the host.
+trim_db cuts the silent head and tail of that plane first, as librosa.effects.trim does on a mono signal (include/vorbis_synth_hip.h,
+"PCM trimming"; float64 model: tests/trim_model.py).
 
 Every argument is checked before the library is loaded."""
 import ctypes as C
@@ -64,11 +66,46 @@ def cond_spec(peak_normalize=False, preemphasis=None, error=PcmError):
     return PcmCond(opts, 0, a)
 
 
+TRIM_MAX_FRAME = 8192  # VSYN_TRIM_MAX_FRAME
+U32_MAX = 0xFFFFFFFF   # vsyn_pcm_trim's fields are uint32
+
+
+def trim_spec(trim_db=None, trim_frame_length=2048, trim_hop_length=512, trim_index=None, error=PcmError):
+    """Checks the trim arguments (include/vorbis_synth_hip.h, "PCM trimming", step 8) and returns the C spec (binding.PcmTrim), or
+    None for trim_db=None: the stage is off and its other arguments are not looked at. trim_db a finite number in (0, 200],
+    trim_frame_length an integer in [1, 8192], trim_hop_length an integer >= 1 (that the C spec's uint32 holds), trim_index None
+    or a list."""
+    from .binding import PcmTrim
+    if trim_index is not None and not isinstance(trim_index, list):
+        raise error("trim_index must be None or a list, got %r" % (trim_index,))
+    if trim_db is None:
+        return None
+    if isinstance(trim_db, (bool, np.bool_)) or not isinstance(trim_db, (int, float, np.integer, np.floating)):
+        raise error("trim_db must be None or a number in (0, 200], got %r" % (trim_db,))
+    if not (math.isfinite(float(trim_db)) and 0.0 < float(trim_db) <= 200.0):
+        raise error("trim_db must be in (0, 200], got %r" % (trim_db,))
+    for name, v, hi in (("trim_frame_length", trim_frame_length, TRIM_MAX_FRAME), ("trim_hop_length", trim_hop_length, U32_MAX)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise error("%s must be an integer, got %r" % (name, v))
+        if not 1 <= int(v) <= hi:
+            raise error("%s must be in [1, %d], got %d" % (name, hi, int(v)))
+    return PcmTrim(int(trim_frame_length), int(trim_hop_length), float(trim_db))
+
+
+def give_trim_index(trim_index, bounds, results):
+    """trim_index[:] = one (start, end) per file from the run's bounds array; None for a file that failed, and for every file
+    with the stage off (bounds None)."""
+    if trim_index is not None:
+        trim_index[:] = [None if bounds is None or isinstance(r, Exception) else (int(bounds[i][0]), int(bounds[i][1]))
+                         for i, r in enumerate(results)]
+
+
 _load = _corpus.load
 
 
 def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0, device=0, errors="raise", files_per_submit=64,
-                  stats=None, mono=False, peak_normalize=False, preemphasis=None):
+                  stats=None, mono=False, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048, trim_hop_length=512,
+                  trim_index=None):
     """PCM of many Ogg Vorbis files in one corpus run: a list of (pcm, sr) tuples. pcm is float32 (channels, frames), or int16
     (frames, channels) with ov_read's conversion; sr is the rate of the returned PCM. sr=None keeps each file's own rate (the
     PCM is bit for bit that of ogg_vorbis_decode_corpus); an integer resamples every file to it on the GPU. errors="raise": the
@@ -77,7 +114,12 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     mono=True: pcm is 1-D (frames,), float32 or int16, the channels' mean computed on the device (half the bytes come back for
     stereo files); with peak_normalize=True divided by its largest magnitude, so that the peak is exactly +-1 (a file with an Inf
     or NaN sample fails alone; silence stays silence); with preemphasis=a, 0 < a < 1, then filtered as z[t] = y[t] - a y[t-1].
-    peak_normalize and preemphasis need mono=True."""
+    peak_normalize and preemphasis need mono=True.
+    trim_db=d (0 < d <= 200, needs mono=True): the leading and trailing frames of the mono signal whose RMS over trim_frame_length
+    samples, every trim_hop_length samples, lies more than d dB below the loudest frame's are cut off first, as
+    librosa.effects.trim(y, top_db=d) does; the peak and the pre-emphasis are those of what is kept. trim_index (optional list)
+    receives one (start, end) per file, in samples of the returned rate (None for a failed file, and for every file with the stage off). A
+    file with an Inf or NaN sample fails alone."""
     _corpus.check_errors(errors)
     target = check_sr(sr)
     name = _format(dtype)
@@ -86,6 +128,9 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     cond = cond_spec(peak_normalize, preemphasis)
     if not mono and cond.options:
         raise PcmError("peak_normalize and preemphasis act on the mono signal: pass mono=True")
+    trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index)
+    if not mono and trim is not None:
+        raise PcmError("trim_db acts on the mono signal: pass mono=True")
     lib = _load()
     n = len(list_of_bytes)
     frames = np.zeros(n, np.uint64)
@@ -101,8 +146,16 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
         return _corpus.copy_into(a, p), int(rates[i])
 
     args = (threads, feeders, files_per_submit, device, target, FORMATS[name])
+    if trim is not None:
+        bounds = np.zeros((max(n, 1), 2), np.uint64)
+        res = _corpus.run(lib, lib.ogg_vorbis_pcm_corpus_trim, list_of_bytes, args + (C.byref(cond) if cond.options else None, C.byref(trim)),
+                          (frames, chans, rates, bounds), build, PcmError, errors, "pcm", stats)
+        give_trim_index(trim_index, bounds[:n], res)
+        return res
     fn, extra = (lib.ogg_vorbis_pcm_corpus_cond, (C.byref(cond),)) if mono else (lib.ogg_vorbis_pcm_corpus, ())
-    return _corpus.run(lib, fn, list_of_bytes, args + extra, (frames, chans, rates), build, PcmError, errors, "pcm", stats)
+    res = _corpus.run(lib, fn, list_of_bytes, args + extra, (frames, chans, rates), build, PcmError, errors, "pcm", stats)
+    give_trim_index(trim_index, None, res)
+    return res
 
 
 def get_pcm_from_raw_bytes(raw_bytes, sr=None, dtype="float32", **kwargs):
