@@ -719,7 +719,7 @@ int vsyn_pcm_cond_spectral_host(vsyn_handle* h, const vsyn_pcm_cond* cond, const
  *     than the delta width" applies to the trimmed rows, and (start, end) are in samples of the resampled signal.
  *  8. Checks (VSYN_ERR_INVALID before anything runs): L or H out of range; top_db not finite or outside (0, 200]; channels = 0.
  *
- * Not built: librosa.effects.split, the per-channel aggregate, a ref other than the maximum. No floating-point atomics and no
+ * Not built: the per-channel aggregate, a ref other than the maximum (librosa.effects.split: "PCM splitting" below). No floating-point atomics and no
  * atomics at all: the same PCM gives the same bits, alone, in any slot of a batch and at any alignment. A NULL vsyn_pcm_trim means
  * the stage is off: nothing is launched and every entry point that takes one returns what its counterpart without the stage
  * returns, bit for bit. The trim entry points read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept
@@ -766,6 +766,80 @@ int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const
                                 const vsyn_spectral_post* post, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
                                 float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out,
                                 double* refs_out, vsyn_status* status, const char** err);
+
+/* ---- PCM splitting: the non-silent intervals of the decoded PCM, and the signal with its silent stretches removed ----
+ *
+ * Input and parameters as for "PCM trimming": one segment's planar float32 PCM x[c][t], C channels, T frames; frame_length L,
+ * hop_length H and top_db in a vsyn_pcm_trim, with the same checks. Output: n intervals (start_k, end_k), uint32 pairs in ascending
+ * order; optionally ONE mono float32 plane, the joined signal, and out_frames. This is librosa.effects.split(y, top_db, ref=np.max,
+ * frame_length=L, hop_length=H) on the mono signal. The device is compared against tests/split_model.py, and that model against a
+ * restatement in librosa's own words (tests/test_split_cpu.py).
+ *
+ *  1. Downmix, frame energies, decision: steps 1 to 3 of "PCM trimming", by the same kernel and the same device functions: the
+ *     same y, the same ms[f] in the same summation order, the same predicate E[f] > R * k || E[f] >= R with the same k.
+ *  2. Intervals. A maximal run of non-silent frames [a, b) is the interval (a * H, min(b * H, T)). n <= (F + 1) / 2. Only the last
+ *     interval can be clipped by T; when the last frame alone is non-silent and (F - 1) * H = T it is (T, T), listed as librosa lists
+ *     it, and contributes no samples. The first start and the last end are (start, end) of "PCM trimming".
+ *  3. Joined signal: out = y[start_0 : end_0] ++ y[start_1 : end_1] ++ ..., out_frames = sum_k (end_k - start_k); nothing is written
+ *     past it. Equivalently: the hops y[f * H : min((f + 1) * H, T)] of the non-silent frames f in order, which is how it is gathered.
+ *  4. F = 0: no intervals, out_frames = 0. All-zero PCM, or PCM below amin: one interval (0, T).
+ *  5. Not finite (step 6 of "PCM trimming"): the segment is refused alone: n = 0, out_frames = 0, and its R is not finite.
+ *  6. Order in the pipeline: decode, resample per channel (if asked), downmix and split, peak, pre-emphasis, then PCM out or STFT,
+ *     then the post stage: the peak, the pre-emphasis, the frames and "fewer frames than the delta width" are those of the joined
+ *     signal, and the intervals are in samples of the resampled signal. A call either trims or splits.
+ *  7. Checks (VSYN_ERR_INVALID before anything runs): those of "PCM trimming", and an intervals_stride below
+ *     vsyn_pcm_split_max_intervals for the longest segment the call can hold.
+ *
+ * Integer scans and reductions only behind the energies, no atomics: the same PCM gives the same intervals and the same bits, alone,
+ * in any slot of a batch and at any alignment. Entries of an interval array past a segment's count are not written by the device
+ * entry and unspecified in the host entries. A NULL vsyn_pcm_trim means the stage is off, as for the trim entry points. The split
+ * entry points read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM. One
+ * handle's split entry points share its split workspace, which is not the trim stage's. */
+
+/* (F + 1) / 2 for a segment of `frames` PCM frames: the most intervals it can have. 0 for an invalid spec. */
+uint64_t vsyn_pcm_split_max_intervals(const vsyn_pcm_trim* trim, uint64_t frames);
+
+/* The caller's planar PCM as for vsyn_pcm_trim_device. Writes d_out[g * out_plane_stride + t] for t < out_frames(g), nothing past
+ * it; d_out_frames[S] (device, uint32); d_counts[S] (device, uint32): n; d_intervals (device, uint32):
+ * d_intervals[(g * intervals_stride + k) * 2 + {0, 1}] = start_k, end_k for k < n(g), intervals_stride at least
+ * vsyn_pcm_split_max_intervals(trim, min(plane_stride, out_plane_stride)); d_ref and d_ms as for vsyn_pcm_trim_device. d_out with
+ * d_out_frames is in the input form of vsyn_pcm_condition_device and vsyn_spectral_device with channels = 1. Asynchronous on
+ * hip_stream. */
+int vsyn_pcm_split_device(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t num_segments, const float* d_pcm, uint64_t plane_stride,
+                          uint32_t channels, const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride, uint32_t* d_out_frames,
+                          uint32_t* d_counts, uint32_t* d_intervals, uint64_t intervals_stride, double* d_ref, double* d_ms,
+                          uint64_t ms_stride, void* hip_stream, const char** err);
+
+/* vsyn_pcm_trim_host with the split in the trim's place: resample (out_rate != 0), downmix and split, condition (cond may be NULL:
+ * the joined downmix as it is), PCM out as one mono plane per segment. frames_out[S] receives each segment's out_frames;
+ * counts_out[S] (uint32, may be NULL) its n; intervals_out (uint32, may be NULL) its intervals,
+ * intervals_out[(g * intervals_stride + k) * 2 + {0, 1}], intervals_stride at least vsyn_pcm_split_max_intervals of the longest
+ * unsplit T; refs_out and peaks_out as for vsyn_pcm_trim_host. out_stride_frames is checked against the UNSPLIT T; with out = NULL
+ * nothing is launched and frames_out receives that unsplit T. trim = NULL is vsyn_pcm_condition_host (counts_out, intervals_out
+ * and refs_out are not written). Synchronous. */
+int vsyn_pcm_split_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t num_segments, const uint32_t* in_rates,
+                        uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* counts_out,
+                        uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out, const char** err);
+
+/* The intervals alone of the PCM of the most recent submit: resample (out_rate != 0), frame energies, intervals. The joined signal
+ * is not made and no PCM is copied back. frames_out[S] receives each segment's (resampled, unsplit) T; counts_out, intervals_out
+ * with intervals_stride, and refs_out as for vsyn_pcm_split_host. With counts_out = NULL nothing is launched: frames_out alone, from
+ * which the caller sizes intervals_out. Synchronous. */
+int vsyn_pcm_split_intervals_host(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t num_segments, const uint32_t* in_rates,
+                                  uint32_t out_rate, uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out,
+                                  uint64_t intervals_stride, double* refs_out, const char** err);
+
+/* vsyn_pcm_trim_spectral_host with the split in the trim's place. This form reads out_frames back once between the split and the
+ * spectral launches (with the counts, the intervals and the refs; one wait). frames_out[S] (may be NULL) receives each segment's
+ * out_frames; seg_rows are the rows of the joined segments; a refused segment and, with post->order > 0, a segment joined to
+ * 0 < F < post->width get 0 rows and fail alone: the caller sees the latter from frames_out. With rows = NULL the resampler and the
+ * split still run, for the counts. trim = NULL is vsyn_pcm_cond_spectral_host (frames_out, counts_out, intervals_out and refs_out
+ * are not written). Synchronous. */
+int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                 const vsyn_spectral_post* post, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                                 float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* counts_out,
+                                 uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                 vsyn_status* status, const char** err);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,12 @@ def load():
                                                             C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), vp, vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus_cond", [u32, C.c_int, C.POINTER(binding.PcmCond), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus_trim", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), vp, vp, vp, vp,
-                                                       vp, vp])):
+                                                       vp, vp]),
+                       ("ogg_vorbis_pcm_corpus_split", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), vp, vp, vp, vp,
+                                                        vp, vp, vp]),
+                       ("ogg_vorbis_spectral_corpus_split", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPost),
+                                                             C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), vp, vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_intervals_corpus", [u32, C.POINTER(binding.PcmTrim), vp, vp, vp, vp, vp])):
         fn = getattr(lib, name)
         fn.argtypes = head + args + tail
         fn.restype = C.c_int
@@ -52,7 +57,7 @@ def check_errors(errors):
 
 def run(lib, fn, list_of_bytes, args, arrays, build, error, errors, what, stats=None):
     """One corpus run of the C entry point fn over list_of_bytes: fn(datas, lens, n, *args, out, *arrays, ok, error_out_per_file,
-    stats_out, error_out), arrays being the caller's per-file numpy outputs. build(i, ptr) makes file i's entry from the buffer the
+    stats_out, error_out), arrays being the caller's per-file numpy outputs (or ctypes arrays). build(i, ptr) makes file i's entry from the buffer the
     library handed over (released here afterwards). A failed file raises error("file i: ...") (errors="raise") or is returned as
     one (errors="return"); a failed run raises error("<what> corpus run failed: ..."). stats (optional list) receives the run's 8
     corpus statistics."""
@@ -67,7 +72,8 @@ def run(lib, fn, list_of_bytes, args, arrays, build, error, errors, what, stats=
     ferr = (C.c_char_p * n)()
     st = (C.c_double * 8)()
     err = C.c_char_p()
-    if fn(datas, lens, n, *args, out, *[a.ctypes.data for a in arrays], ok.ctypes.data, ferr, st, C.byref(err)) != 0:
+    if fn(datas, lens, n, *args, out, *[a.ctypes.data if isinstance(a, np.ndarray) else a for a in arrays], ok.ctypes.data, ferr, st,
+          C.byref(err)) != 0:
         raise error("%s corpus run failed: %s" % (what, (err.value or b"").decode()))
     if stats is not None:
         stats[:] = list(st)
@@ -86,6 +92,26 @@ def run(lib, fn, list_of_bytes, args, arrays, build, error, errors, what, stats=
             if out[i]:
                 lib.ogg_vorbis_features_free(out[i])
     return res
+
+
+class IntervalBuffers:
+    """The per-file interval buffers of a split run: `ptrs` and `counts` go to the entry point (after its per-file output, or as
+    it); take(i) is file i's (n, 2) int64 array; free() releases what the library handed over."""
+
+    def __init__(self, lib, n):
+        self.lib = lib
+        self.ptrs = (C.c_void_p * max(n, 1))()
+        self.counts = np.zeros(max(n, 1), np.uint64)
+
+    def take(self, i):
+        a = np.zeros((int(self.counts[i]), 2), np.uint32)
+        return copy_into(a, self.ptrs[i]).astype(np.int64)
+
+    def free(self):
+        for i in range(len(self.ptrs)):
+            if self.ptrs[i]:
+                self.lib.ogg_vorbis_features_free(self.ptrs[i])
+                self.ptrs[i] = None
 
 
 def copy_into(a, ptr):

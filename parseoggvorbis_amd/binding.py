@@ -209,6 +209,8 @@ _SYMBOLS = [
     "vsyn_spectral_post_dim", "vsyn_spectral_post_device", "vsyn_pcm_spectral_post_host",
     "vsyn_pcm_condition_device", "vsyn_pcm_condition_host", "vsyn_pcm_cond_spectral_host",
     "vsyn_pcm_trim_num_frames", "vsyn_pcm_trim_device", "vsyn_pcm_trim_host", "vsyn_pcm_trim_spectral_host",
+    "vsyn_pcm_split_max_intervals", "vsyn_pcm_split_device", "vsyn_pcm_split_host", "vsyn_pcm_split_intervals_host",
+    "vsyn_pcm_split_spectral_host",
 ]
 
 
@@ -292,6 +294,13 @@ def load():
     lib.vsyn_pcm_trim_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), u32, vp, u32, C.c_int, vp, u64, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_trim_spectral_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPost),
                                                 u32, vp, u32, vp, u64, vp, vp, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_pcm_split_max_intervals.argtypes = [C.POINTER(PcmTrim), u64]
+    lib.vsyn_pcm_split_max_intervals.restype = u64
+    lib.vsyn_pcm_split_device.argtypes = [vp, C.POINTER(PcmTrim), u32, vp, u64, u32, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, cpp]
+    lib.vsyn_pcm_split_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), u32, vp, u32, C.c_int, vp, u64, vp, vp, vp, u64, vp, vp, cpp]
+    lib.vsyn_pcm_split_intervals_host.argtypes = [vp, C.POINTER(PcmTrim), u32, vp, u32, vp, vp, vp, u64, vp, cpp]
+    lib.vsyn_pcm_split_spectral_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPost),
+                                                 u32, vp, u32, vp, u64, vp, vp, vp, vp, u64, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -577,6 +586,102 @@ class Synth:
         if rc not in (VSYN_OK, VSYN_ERR_STREAM):
             raise VsynError(rc, (err.value or b"").decode())
         return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], bounds=bounds[:S], peaks=peaks[:S], refs=refs[:S], flags=st.flags)
+
+    def pcm_split_device(self, split, d_pcm, plane_stride, channels, num_segments, d_frames, d_out, out_plane_stride, d_out_frames, d_counts,
+                         d_intervals, intervals_stride, d_ref=None, d_ms=None, ms_stride=0, stream=None):
+        """vsyn_pcm_split_device on device pointers (ints)."""
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pcm_split_device(self.h, None if split is None else C.byref(split), num_segments, d_pcm, plane_stride, channels, d_frames,
+                                            d_out, out_plane_stride, d_out_frames, d_counts, d_intervals, intervals_stride, d_ref, d_ms, ms_stride,
+                                            stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+
+    def _split_sizes(self, split, S, rates, out_rate):
+        """The unsplit frames [S] of the last submit's segments and the interval stride that holds the longest one's intervals."""
+        frames = np.zeros(max(1, S), np.uint64)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pcm_split_intervals_host(self.h, C.byref(split), S, _ptr(rates), out_rate, _ptr(frames), None, None, 0, None, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        t_max = int(frames[:S].max()) if S else 0
+        return frames, max(1, int(self.lib.vsyn_pcm_split_max_intervals(C.byref(split), t_max)))
+
+    @staticmethod
+    def _intervals(counts, iv, S):
+        return [iv[g, :int(counts[g])].astype(np.int64) for g in range(S)]
+
+    def pcm_split_intervals_host(self, split, num_segments, in_rates=None, out_rate=0):
+        """vsyn_pcm_split_intervals_host over the last submit's segments: returns dict(frames [S] (unsplit), counts [S], intervals (a
+        list of (n, 2) int64 arrays), refs [S])."""
+        S = num_segments
+        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
+        frames, stride = self._split_sizes(split, S, rates, out_rate)
+        counts = np.zeros(max(1, S), np.uint32)
+        iv = np.zeros((max(1, S), stride, 2), np.uint32)
+        refs = np.zeros(max(1, S), np.float64)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pcm_split_intervals_host(self.h, C.byref(split), S, _ptr(rates), out_rate, _ptr(frames), _ptr(counts), _ptr(iv), stride,
+                                                    _ptr(refs), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(frames=frames[:S], counts=counts[:S], intervals=self._intervals(counts, iv, S), refs=refs[:S])
+
+    def pcm_split_host(self, split, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_split_host over the last submit's segments (split / cond may be None): returns dict(pcm [S][stride] float32 or
+        int16, frames [S], counts [S], intervals (a list of (n, 2) int64 arrays), peaks [S], refs [S]), stride = the largest unsplit T."""
+        S = num_segments
+        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
+        frames = np.zeros(max(1, S), np.uint64)
+        peaks = np.zeros(max(1, S), np.float32)
+        counts = np.zeros(max(1, S), np.uint32)
+        refs = np.zeros(max(1, S), np.float64)
+        err = C.c_char_p()
+        sp = None if split is None else C.byref(split)
+        cp = None if cond is None else C.byref(cond)
+        rc = self.lib.vsyn_pcm_split_host(self.h, sp, cp, S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), None, None, 0, None, None, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        t_max = int(frames[:S].max()) if S else 0
+        stride = max(1, t_max)
+        ivs = 1 if split is None else max(1, int(self.lib.vsyn_pcm_split_max_intervals(sp, t_max)))
+        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
+        out = np.zeros((S, stride), np.float32 if fmt == VSYN_PCM_F32 else np.int16)
+        rc = self.lib.vsyn_pcm_split_host(self.h, sp, cp, S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames), _ptr(counts), _ptr(iv), ivs,
+                                          _ptr(peaks), _ptr(refs), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(pcm=out, frames=frames[:S], counts=counts[:S], intervals=self._intervals(counts, iv, S), peaks=peaks[:S], refs=refs[:S])
+
+    def pcm_split_spectral_host(self, split, cond, spec, post, in_rates, out_rate=0):
+        """vsyn_pcm_split_spectral_host over the last submit's segments (split / cond / post may be None): returns dict(rc, rows
+        [total][D_out], seg_rows [S], frames [S], counts [S], intervals, peaks [S], refs [S], flags)."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S = len(rates)
+        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + (post.order if post is not None else 0))
+        seg_rows = np.zeros(max(S, 1), np.uint64)
+        frames = np.zeros(max(S, 1), np.uint64)
+        peaks = np.zeros(max(S, 1), np.float32)
+        counts = np.zeros(max(1, S), np.uint32)
+        refs = np.zeros(max(1, S), np.float64)
+        st, err = Status(), C.c_char_p()
+        sp = None if split is None else C.byref(split)
+        cp = None if cond is None else C.byref(cond)
+        pp = None if post is None else C.byref(post)
+        ivs = 1 if split is None else self._split_sizes(split, S, rates if out_rate else None, out_rate)[1]
+        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
+        rc = self.lib.vsyn_pcm_split_spectral_host(self.h, sp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None, None,
+                                                   None, 0, None, None, C.byref(st), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum())
+        rows = np.zeros((max(total, 1), dout), np.float32)
+        rc = self.lib.vsyn_pcm_split_spectral_host(self.h, sp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows),
+                                                   _ptr(frames), _ptr(counts), _ptr(iv), ivs, _ptr(peaks), _ptr(refs), C.byref(st), C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], frames=frames[:S], counts=counts[:S], intervals=self._intervals(counts, iv, S),
+                    peaks=peaks[:S], refs=refs[:S], flags=st.flags)
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

@@ -25,6 +25,7 @@
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
 #include "vsyn_trim.h"
+#include "vsyn_split.h"
 
 static const uint32_t k_inverse_db_bits[256] = {
 #include "vorbis_floor1_inverse_db.inc"
@@ -122,6 +123,7 @@ struct vsyn_handle {
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
   TrimWs tr;                           // vsyn_trim.h
+  SplitWs sl;                          // vsyn_split.h
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -1287,22 +1289,35 @@ struct TrimArgs {
   double* refs_out;
 };
 
+// The split stage of a chain, in the trim stage's place: its spec and where its results go (host, each may be NULL): the joined
+// frames, the interval counts, the intervals [S][stride][2], the refs. gather = false: the intervals alone, no joined plane.
+struct SplitArgs {
+  const vsyn_pcm_trim* spec;
+  uint32_t* frames_out;
+  uint32_t* counts_out;
+  uint32_t* intervals_out;
+  uint64_t stride;
+  double* refs_out;
+  bool gather;
+};
+
 // The chain on the host stream, from the last host submit's PCM to *v: with out_rate != 0 every segment resampled from rates[g] to
 // out_rate into h->rs's plane of rs_plane frames; with trim != NULL downmixed and trimmed into h->tr's mono plane (of mono_plane
 // frames when it is the last stage, of t_max frames in front of the conditioning), the bounds and refs on their way to the host;
+// with split != NULL (never with a trim) downmixed and joined into h->sl's mono plane in the same way, its results on their way;
 // with cond != NULL conditioned into h->cd's mono plane of mono_plane frames, the peaks on their way to peaks_out. t_max bounds
 // every segment's frames; zero clears the last plane first: zeros past each segment's frames. Caller holds h->mu and has run
 // rs_check / trim_check / cond_check; its checks of its own buffers sit between last_submit_frames and this.
 static int pcm_chain(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, uint64_t rs_plane, const vsyn_pcm_cond* cond,
                      uint64_t mono_plane, uint64_t t_max, bool zero, float* peaks_out, PcmView* v, const char** err,
-                     const TrimArgs* trim = nullptr) {
+                     const TrimArgs* trim = nullptr, const SplitArgs* split = nullptr) {
   const uint32_t C = h->H.channels;
   hipStream_t hs = h->host_stream;
   *v = PcmView{h->st_pcm.p, h->last_host_plane, C, h->ws_seg[h->last_wb].p, nullptr};
   if (out_rate) {
     const size_t n = (size_t)S * C * rs_plane;
     HIPCHK(h->rs.pcm.ensure(n + 1));
-    if (zero && !cond && !trim) HIPCHK(hipMemsetAsync(h->rs.pcm.p, 0, sizeof(float) * n, hs));
+    if (zero && !cond && !trim && !split) HIPCHK(hipMemsetAsync(h->rs.pcm.p, 0, sizeof(float) * n, hs));
     if (int rc = rs_launch(h->rs, h->device, S, rates, out_rate, v->pcm, v->plane, C, nullptr, v->si, h->rs.pcm.p, rs_plane, nullptr, hs, err)) return rc;
     *v = PcmView{h->rs.pcm.p, rs_plane, C, nullptr, h->rs.outF.p};
   }
@@ -1316,6 +1331,23 @@ static int pcm_chain(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t
       return rc;
     if (int rc = trim_fetch_bounds(h->tr, S, trim->bounds_out, trim->refs_out, hs, err)) return rc;
     *v = PcmView{h->tr.pcm.p, tr_plane, 1u, nullptr, h->tr.frames.p};
+  }
+  if (split) {  // the next stage reads the joined mono plane as 1-channel PCM, with the frames the stage wrote
+    const uint64_t sl_plane = cond ? std::max<uint64_t>(t_max, 1) : mono_plane;
+    const size_t n = (size_t)S * sl_plane;
+    float* joined = nullptr;
+    if (split->gather) {
+      HIPCHK(h->sl.e.pcm.ensure(n + 1));
+      if (zero && !cond) HIPCHK(hipMemsetAsync(h->sl.e.pcm.p, 0, sizeof(float) * n, hs));
+      joined = h->sl.e.pcm.p;
+    }
+    uint64_t ws_stride = 0;
+    if (int rc = split_launch(h->sl, h->device, split->spec, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, joined, sl_plane, nullptr, nullptr,
+                              nullptr, 0, &ws_stride, nullptr, nullptr, 0, hs, err))
+      return rc;
+    if (int rc = split_fetch(h->sl, S, split->counts_out, split->intervals_out, split->stride, ws_stride, split->refs_out, hs, err)) return rc;
+    if (split->frames_out) HIPCHK(hipMemcpyAsync(split->frames_out, h->sl.e.frames.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
+    *v = PcmView{joined, sl_plane, 1u, nullptr, h->sl.e.frames.p};
   }
   if (cond) {  // the next stage reads the conditioned mono plane as 1-channel PCM, with the frames the stage wrote
     const size_t n = (size_t)S * mono_plane;
@@ -1427,12 +1459,30 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   return spectral_rows_out(h, spec, post, S, spec_rates, v, seg_rows, f_max, total, rows, status, err);
 }
 
+// What the split forms of the host entries hand back where the trim forms hand back bounds (host, each may be NULL): the joined
+// frames, the interval counts, the intervals [S][stride][2].
+struct SplitOut {
+  uint64_t* frames_out;
+  uint32_t* counts_out;
+  uint32_t* intervals_out;
+  uint64_t stride;
+};
+
+// intervals_out must hold what a segment of t_max frames can have
+static int split_check_stride(const vsyn_pcm_trim* trim, const SplitOut* so, uint64_t t_max, const char** err) {
+  const uint64_t need = split_max_intervals(t_max, trim->frame_length, trim->hop_length);
+  if (so->intervals_out && so->stride < need)
+    return fail(err, VSYN_ERR_INVALID, "intervals_stride %llu below %llu intervals", (unsigned long long)so->stride, (unsigned long long)need);
+  return VSYN_OK;
+}
+
 // vsyn_pcm_trim_spectral_host with a trim: the chain up to the trimmed plane, the bounds back to the host (the later stages take
-// their row counts from there), then conditioning, spectral rows and the post stage on the trimmed plane.
+// their row counts from there), then conditioning, spectral rows and the post stage on the trimmed plane. so != NULL:
+// vsyn_pcm_split_spectral_host, the joined plane in the trimmed one's place and its frames, counts and intervals back.
 static int pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
                                   const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows,
                                   uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out, double* refs_out,
-                                  vsyn_status* status, const char** err) {
+                                  vsyn_status* status, const char** err, const SplitOut* so = nullptr) {
   status_reset(status);
   int rc = trim_check(trim, err);
   if (rc) return rc;
@@ -1466,16 +1516,33 @@ static int pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, con
   rc = last_submit_frames(h, S, rates, out_rate, T.data(), &t_max, err);
   if (rc) return rc;
   if (S == 0) return VSYN_OK;
+  if (so) {
+    rc = split_check_stride(trim, so, t_max, err);
+    if (rc) return rc;
+  }
   t_max = std::max<uint64_t>(t_max, 1);
   if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
   hipStream_t hs = h->host_stream;
-  std::vector<uint32_t> bounds(2u * (size_t)S);
+  std::vector<uint32_t> bounds(2u * (size_t)S);  // split: (0, joined frames)
   std::vector<double> refs(S);
   const TrimArgs ta{trim, bounds.data(), refs.data()};
   PcmView v;
-  rc = pcm_chain(h, S, rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err, &ta);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(hs));  // the one read-back of this form: S * 8 bytes of bounds (and the refs)
+  if (so) {
+    std::vector<uint32_t> joined(S);
+    const SplitArgs sa{trim, joined.data(), so->counts_out, so->intervals_out, so->stride, refs.data(), true};
+    rc = pcm_chain(h, S, rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err, nullptr, &sa);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(hs));  // the one read-back of this form: the joined frames, with the counts, intervals and refs
+    for (uint32_t g = 0; g < S; ++g) {
+      bounds[2u * g] = 0u;
+      bounds[2u * g + 1u] = joined[g];
+      if (so->frames_out) so->frames_out[g] = joined[g];
+    }
+  } else {
+    rc = pcm_chain(h, S, rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err, &ta);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(hs));  // the one read-back of this form: S * 8 bytes of bounds (and the refs)
+  }
   if (bounds_out) memcpy(bounds_out, bounds.data(), sizeof(uint32_t) * bounds.size());
   if (refs_out) memcpy(refs_out, refs.data(), sizeof(double) * S);
   const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
@@ -1500,6 +1567,10 @@ static int pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, con
   }
   return spectral_rows_out(h, spec, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err);
 }
+
+static int pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
+                         uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
+                         float* peaks_out, double* refs_out, const char** err, const SplitOut* so = nullptr);
 
 extern "C" {
 
@@ -1651,6 +1722,16 @@ int vsyn_pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm
                        uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
                        float* peaks_out, double* refs_out, const char** err) {
   if (!trim) return vsyn_pcm_condition_host(h, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
+  return pcm_trim_host(h, trim, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, bounds_out, peaks_out, refs_out, err);
+}
+
+}  // extern "C"
+
+// vsyn_pcm_trim_host with a trim; so != NULL: vsyn_pcm_split_host, the joined plane in the trimmed one's place, its counts and
+// intervals back.
+static int pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
+                         uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
+                         float* peaks_out, double* refs_out, const char** err, const SplitOut* so) {
   if (!h) return cond_no_handle(err);
   int rc = trim_check(trim, err);
   if (rc) return rc;
@@ -1674,9 +1755,22 @@ int vsyn_pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm
   if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
                                              (unsigned long long)out_stride_frames, (unsigned long long)t_max);
   if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
+  PcmView v;  // resampled into a plane as long as the longest segment, trimmed or joined, conditioned into the caller's stride
+  if (so) {
+    rc = split_check_stride(trim, so, t_max, err);
+    if (rc) return rc;
+    std::vector<uint32_t> joined(S);
+    const SplitArgs sa{trim, joined.data(), so->counts_out, so->intervals_out, so->stride, refs_out, true};
+    rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err,
+                   nullptr, &sa);
+    if (rc) return rc;
+    rc = pcm_copy_out(h, v, S, format, cond ? h->cd.s16 : h->sl.e.s16, out, err);
+    if (rc) return rc;
+    for (uint32_t g = 0; g < S; ++g) frames_out[g] = joined[g];
+    return VSYN_OK;
+  }
   std::vector<uint32_t> bounds(2u * (size_t)S);
   const TrimArgs ta{trim, bounds.data(), refs_out};
-  PcmView v;  // resampled into a plane as long as the longest segment, trimmed, conditioned into the caller's stride
   rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err, &ta);
   if (rc) return rc;
   rc = pcm_copy_out(h, v, S, format, cond ? h->cd.s16 : h->tr.s16, out, err);
@@ -1686,6 +1780,8 @@ int vsyn_pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm
   return VSYN_OK;
 }
 
+extern "C" {
+
 int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
                                 const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
                                 uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out, double* refs_out,
@@ -1694,6 +1790,76 @@ int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const
   if (!h) return cond_no_handle(err);
   return pcm_trim_spectral_host(h, trim, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, bounds_out, peaks_out, refs_out,
                                 status, err);
+}
+
+uint64_t vsyn_pcm_split_max_intervals(const vsyn_pcm_trim* trim, uint64_t frames) {
+  if (trim_check(trim, nullptr) != VSYN_OK) return 0;
+  return split_max_intervals(frames, trim->frame_length, trim->hop_length);
+}
+
+int vsyn_pcm_split_device(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t S, const float* d_pcm, uint64_t plane_stride, uint32_t channels,
+                          const uint32_t* d_frames, float* d_out, uint64_t out_plane_stride, uint32_t* d_out_frames, uint32_t* d_counts,
+                          uint32_t* d_intervals, uint64_t intervals_stride, double* d_ref, double* d_ms, uint64_t ms_stride, void* hip_stream,
+                          const char** err) {
+  if (!h) return cond_no_handle(err);
+  int rc = trim_check(trim, err);
+  if (rc) return rc;
+  if (channels == 0 || channels > 255) return fail(err, VSYN_ERR_INVALID, "channels %u outside [1, 255]", channels);
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_out || !d_out_frames || !d_counts || !d_intervals || plane_stride == 0 || out_plane_stride == 0)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer or zero stride");
+  if (plane_stride > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return split_launch(h->sl, h->device, trim, S, d_pcm, plane_stride, channels, d_frames, nullptr, plane_stride, d_out, out_plane_stride, d_out_frames,
+                      d_counts, d_intervals, intervals_stride, nullptr, d_ref, d_ms, ms_stride, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_split_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
+                        uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* counts_out,
+                        uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out, const char** err) {
+  if (!trim) return vsyn_pcm_condition_host(h, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
+  const SplitOut so{nullptr, counts_out, intervals_out, intervals_stride};
+  return pcm_trim_host(h, trim, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, nullptr, peaks_out, refs_out, err, &so);
+}
+
+int vsyn_pcm_split_intervals_host(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
+                                  uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
+                                  double* refs_out, const char** err) {
+  if (!h) return cond_no_handle(err);
+  int rc = trim_check(trim, err);
+  if (rc) return rc;
+  if (out_rate) {
+    rc = rs_check(S, in_rates, out_rate, err);
+    if (rc) return rc;
+  }
+  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
+  // the lock covers the whole call: the resample and split workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t t_max;
+  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
+  if (rc) return rc;
+  if (!counts_out || S == 0) return VSYN_OK;
+  const SplitOut so{nullptr, counts_out, intervals_out, intervals_stride};
+  rc = split_check_stride(trim, &so, t_max, err);
+  if (rc) return rc;
+  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  const SplitArgs sa{trim, nullptr, counts_out, intervals_out, intervals_stride, refs_out, false};
+  PcmView v;  // resampled into a plane as long as the longest segment, marked there: nothing but the counts, intervals and refs comes back
+  rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), nullptr, 0, t_max, false, nullptr, &v, err, nullptr, &sa);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->host_stream));
+  return VSYN_OK;
+}
+
+int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                 const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                                 uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out,
+                                 uint64_t intervals_stride, float* peaks_out, double* refs_out, vsyn_status* status, const char** err) {
+  if (!trim) return vsyn_pcm_cond_spectral_host(h, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, peaks_out, status, err);
+  if (!h) return cond_no_handle(err);
+  const SplitOut so{frames_out, counts_out, intervals_out, intervals_stride};
+  return pcm_trim_spectral_host(h, trim, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, refs_out, status,
+                                err, &so);
 }
 
 }  // extern "C"

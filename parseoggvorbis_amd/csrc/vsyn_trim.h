@@ -22,6 +22,7 @@
 // channel plane sit on a 16-byte boundary too differs per segment; it is uniform per workgroup: 16-byte loads (cond_downmix4)
 // when they do, four 4-byte loads per plane when not. Both forms do the same float32 operations per frame.
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
+// The split stage (vsyn_split.h) launches the energy kernel as it is and shares the bounds kernel's reference and predicate.
 #pragma once
 #include "vsyn_condition.h"
 #include "vsyn_device.h"
@@ -145,14 +146,12 @@ __device__ __forceinline__ uint64_t trim_wave_min(uint64_t v) {
   return v;
 }
 
-__global__ void __launch_bounds__(TRIM_THREADS) vsyn_trim_bounds_kernel(const TrimCtx A) {
-  __shared__ uint64_t s_a[TRIM_WAVES], s_b[TRIM_WAVES];
-  const uint32_t g = blockIdx.x, tid = threadIdx.x;
-  const uint64_t T = trim_frames(A, g);
-  const uint64_t F = trim_num_frames(T, A.L, A.H);
-  const double* ms = A.ms + (size_t)g * A.F_max;
+// The reference of segment g behind its finished ms array, for a whole workgroup of TRIM_THREADS (s_a: TRIM_WAVES words of LDS, free
+// again on return): the maximum of ms on its bit patterns (ms >= 0, or not finite and then above every finite one); a flagged tile
+// counts as a NaN. trim_refused / trim_ref / trim_loud read the decision off it; the split stage (vsyn_split.h) shares all four.
+__device__ __forceinline__ uint64_t trim_segment_max(const TrimCtx& A, uint32_t g, uint64_t F, const double* ms, uint64_t* s_a) {
+  const uint32_t tid = threadIdx.x;
   const uint32_t tiles = (uint32_t)((F + A.FT - 1u) / A.FT);
-  // the maximum of ms on its bit patterns (ms >= 0, or not finite and then above every finite one); a flagged tile counts as a NaN
   uint64_t mx = 0ull;
   for (uint64_t f = tid; f < F; f += TRIM_THREADS) mx = trim_max64(mx, (uint64_t)__double_as_longlong(ms[f]) & TRIM_ABS64);
   for (uint32_t i = tid; i < tiles; i += TRIM_THREADS)
@@ -162,14 +161,32 @@ __global__ void __launch_bounds__(TRIM_THREADS) vsyn_trim_bounds_kernel(const Tr
   __syncthreads();
   mx = trim_max64(trim_max64(s_a[0], s_a[1]), trim_max64(s_a[2], s_a[3]));
   __syncthreads();
-  const bool refused = mx >= TRIM_NOT_FINITE64;
-  const double R = refused ? __longlong_as_double((long long)mx) : fmax(__longlong_as_double((long long)mx), TRIM_AMIN_SQ);
+  return mx;
+}
+__device__ __forceinline__ bool trim_refused(uint64_t mx) { return mx >= TRIM_NOT_FINITE64; }
+__device__ __forceinline__ double trim_ref(uint64_t mx) {
+  return trim_refused(mx) ? __longlong_as_double((long long)mx) : fmax(__longlong_as_double((long long)mx), TRIM_AMIN_SQ);
+}
+// is a frame of mean square m non-silent under R and thr = R k? (E >= R: a loudest frame, also where R k rounds up to R)
+__device__ __forceinline__ bool trim_loud(double m, double R, double thr) {
+  const double E = fmax(m, TRIM_AMIN_SQ);
+  return E > thr || E >= R;
+}
+
+__global__ void __launch_bounds__(TRIM_THREADS) vsyn_trim_bounds_kernel(const TrimCtx A) {
+  __shared__ uint64_t s_a[TRIM_WAVES], s_b[TRIM_WAVES];
+  const uint32_t g = blockIdx.x, tid = threadIdx.x;
+  const uint64_t T = trim_frames(A, g);
+  const uint64_t F = trim_num_frames(T, A.L, A.H);
+  const double* ms = A.ms + (size_t)g * A.F_max;
+  const uint64_t mx = trim_segment_max(A, g, F, ms, s_a);
+  const bool refused = trim_refused(mx);
+  const double R = trim_ref(mx);
   uint64_t first = ~0ull, lastf = 0ull;  // first non-silent frame; last non-silent frame + 1
   if (!refused) {
     const double thr = R * A.k;
     for (uint64_t f = tid; f < F; f += TRIM_THREADS) {
-      const double E = fmax(ms[f], TRIM_AMIN_SQ);
-      if (E > thr || E >= R) {  // (E >= R: a loudest frame, also where R k rounds up to R)
+      if (trim_loud(ms[f], R, thr)) {
         first = trim_min64(first, f);
         lastf = trim_max64(lastf, f + 1u);
       }
@@ -259,12 +276,13 @@ static inline uint32_t trim_tile(uint32_t L, uint32_t H) {
   return ft;
 }
 
-// The stage's kernels on stream s: frames from d_frames, else from si; t_max bounds every segment's frames. d_bounds [S][2],
-// d_out_frames [S], d_ref [S] (NULL: the workspace's); d_ms with ms_stride optional. Caller holds the handle's lock and has run
-// trim_check.
-static inline int trim_launch(TrimWs& ws, int device, const vsyn_pcm_trim* tr, uint32_t S, const float* d_pcm, uint64_t plane, uint32_t C,
-                       const uint32_t* d_frames, const SegInfo* si, uint64_t t_max, float* d_out, uint64_t out_plane, uint32_t* d_out_frames,
-                       uint32_t* d_bounds, double* d_ref, double* d_ms, uint64_t ms_stride, hipStream_t s, const char** err) {
+// The stage's checks, workspace and launch arguments, and the energy kernel on stream s: frames from d_frames, else from si; t_max
+// bounds every segment's frames. *A receives the arguments the kernels behind the energy kernel take (bounds as given; d_ref NULL:
+// the workspace's). The split stage (vsyn_split.h) starts here too, on a workspace of its own. Caller holds the handle's lock and
+// has run trim_check.
+static inline int trim_energy_launch(TrimWs& ws, int device, const vsyn_pcm_trim* tr, uint32_t S, const float* d_pcm, uint64_t plane, uint32_t C,
+                              const uint32_t* d_frames, const SegInfo* si, uint64_t t_max, float* d_out, uint64_t out_plane, uint32_t* d_out_frames,
+                              uint32_t* d_bounds, double* d_ref, double* d_ms, uint64_t ms_stride, hipStream_t s, TrimCtx* ctx, const char** err) {
   if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
   if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_out & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM pointers must be 4-byte aligned");
   if ((uintptr_t)d_ms & 7u) return fail(err, VSYN_ERR_INVALID, "d_ms must be 8-byte aligned");
@@ -274,21 +292,17 @@ static inline int trim_launch(TrimWs& ws, int device, const vsyn_pcm_trim* tr, u
   const uint64_t F_max = std::max<uint64_t>(trim_num_frames(T, L, H), 1);
   if (d_ms && ms_stride < F_max) return fail(err, VSYN_ERR_INVALID, "ms_stride %llu below %llu frames", (unsigned long long)ms_stride, (unsigned long long)F_max);
   const uint32_t ft = trim_tile(L, H);
-  const uint64_t tiles = (F_max + ft - 1u) / ft, gx = (T + 3u + TRIM_CUT_TILE - 1u) / TRIM_CUT_TILE;
+  const uint64_t tiles = (F_max + ft - 1u) / ft;
   if (tiles > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
   HIPCHK(hipSetDevice(device));
   HIPCHK(ws.ms.ensure((size_t)S * F_max));
   HIPCHK(ws.flags.ensure((size_t)S * tiles));
   HIPCHK(ws.frames.ensure(S));
-  if (!d_bounds) {
-    HIPCHK(ws.bounds.ensure(2u * (size_t)S));
-    d_bounds = ws.bounds.p;
-  }
   if (!d_ref) {
     HIPCHK(ws.ref.ensure(S));
     d_ref = ws.ref.p;
   }
-  TrimCtx A;
+  TrimCtx& A = *ctx;
   A.pcm = d_pcm;
   A.plane = plane;
   A.C = C;
@@ -314,6 +328,25 @@ static inline int trim_launch(TrimWs& ws, int device, const vsyn_pcm_trim* tr, u
   const size_t lds = sizeof(float) * ((size_t)(ft - 1u) * fstep + L);
   hipLaunchKernelGGL(vsyn_trim_energy_kernel, dim3((uint32_t)tiles, S), dim3(TRIM_THREADS), lds, s, A);
   HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}
+
+// The stage's kernels on stream s: frames from d_frames, else from si; t_max bounds every segment's frames. d_bounds [S][2],
+// d_out_frames [S], d_ref [S] (NULL: the workspace's); d_ms with ms_stride optional. Caller holds the handle's lock and has run
+// trim_check.
+static inline int trim_launch(TrimWs& ws, int device, const vsyn_pcm_trim* tr, uint32_t S, const float* d_pcm, uint64_t plane, uint32_t C,
+                       const uint32_t* d_frames, const SegInfo* si, uint64_t t_max, float* d_out, uint64_t out_plane, uint32_t* d_out_frames,
+                       uint32_t* d_bounds, double* d_ref, double* d_ms, uint64_t ms_stride, hipStream_t s, const char** err) {
+  if (!d_bounds) {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(ws.bounds.ensure(2u * (size_t)S));
+    d_bounds = ws.bounds.p;
+  }
+  TrimCtx A;
+  if (int rc = trim_energy_launch(ws, device, tr, S, d_pcm, plane, C, d_frames, si, t_max, d_out, out_plane, d_out_frames, d_bounds, d_ref, d_ms,
+                                  ms_stride, s, &A, err))
+    return rc;
+  const uint64_t gx = (A.t_cap + 3u + TRIM_CUT_TILE - 1u) / TRIM_CUT_TILE;
   hipLaunchKernelGGL(vsyn_trim_bounds_kernel, dim3(S), dim3(TRIM_THREADS), 0, s, A);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(vsyn_trim_cut_kernel, dim3((uint32_t)gx, S), dim3(TRIM_THREADS), 0, s, A);

@@ -402,6 +402,8 @@ struct Feeder {
     std::vector<std::string> err;
     std::vector<double> digest;  // per (file, channel), from the device
     std::vector<uint32_t> bounds;  // trim run: per file (start, end)
+    std::vector<uint32_t> counts, iv;  // split run: per file its intervals, iv[(s * iv_stride + k) * 2 + {0, 1}]
+    uint64_t iv_stride = 0;
     uint64_t plane = 0;
   };
 
@@ -484,6 +486,15 @@ struct Feeder {
       if (o.err[s].empty() && !std::isfinite(refs[s])) o.err[s] = "trim: the PCM holds a sample that is not finite";
   }
 
+  // A split run's interval arrays, sized for the longest file of the submit (its unsplit frames).
+  void size_intervals(uint32_t S, Outcome& o) {
+    uint64_t t_max = 0;
+    for (uint32_t s = 0; s < S; ++s) t_max = std::max(t_max, o.frames[s]);
+    o.iv_stride = std::max<uint64_t>(vsyn_pcm_split_max_intervals(&opts.trim_spec, t_max), 1);
+    o.counts.assign(S, 0u);
+    o.iv.assign((size_t)S * o.iv_stride * 2u, 0u);
+  }
+
   // the conditioning spec of a trim run: NULL when the trimmed downmix is delivered as it is
   const vsyn_pcm_cond* trim_cond() const { return opts.cond.options ? &opts.cond : nullptr; }
 
@@ -498,10 +509,29 @@ struct Feeder {
       pl = std::max(pl, o.frames[s]);
     }
     if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * pl));
-    else CHECK_ERR(g.pcm.ensure((size_t)S * pl));
+    else if (!opts.intervals_only) CHECK_ERR(g.pcm.ensure((size_t)S * pl));  // (intervals_only: no PCM comes back)
     const char* err = nullptr;
     std::vector<uint64_t> got(S);
-    std::vector<float> peaks(S);
+    std::vector<float> peaks(S, 0.f);
+    if (opts.split) {  // the split in front: the frames delivered are those of the joined signal, or with intervals_only nothing is
+      std::vector<double> refs(S);
+      size_intervals(S, o);
+      const int rc = opts.intervals_only
+                         ? vsyn_pcm_split_intervals_host(g.handle, &opts.trim_spec, S, rates.data(), opts.resample_rate, got.data(), o.counts.data(),
+                                                         o.iv.data(), o.iv_stride, refs.data(), &err)
+                         : vsyn_pcm_split_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate,
+                                               opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32, opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, pl,
+                                               got.data(), o.counts.data(), o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &err);
+      if (rc != VSYN_OK) return OkOrError(std::string("GPU split layer: ") + (err ? err : "split failed"));
+      for (uint32_t s = 0; s < S; ++s) {
+        CHECK(got[s] <= o.frames[s]);
+        o.frames[s] = got[s];
+      }
+      refuse_refs(refs, o);
+      refuse_peaks(peaks, o);
+      o.plane = pl;
+      return OkOrError();
+    }
     if (opts.trim) {  // the trim in front: the frames delivered are the trimmed ones
       std::vector<double> refs(S);
       o.bounds.assign(2u * (size_t)S, 0u);
@@ -545,7 +575,7 @@ struct Feeder {
         o.err[s] = buf;
       }
       uint64_t F = o.err[s].empty() ? vsyn_spectral_num_frames(&opts.spectral, std::min<uint64_t>(o.frames[s], o.plane)) : 0;
-      if (!opts.trim && opts.post.order && F && F < opts.post.width) {  // fewer frames than the delta window: this file's error, not the submit's
+      if (!opts.trim && !opts.split && opts.post.order && F && F < opts.post.width) {  // fewer frames than the delta window: this file's error, not the submit's
         char buf[96];
         snprintf(buf, sizeof(buf), "spectral: delta width %u needs %u frames, file has %llu", opts.post.width, opts.post.width,
                  (unsigned long long)F);
@@ -562,7 +592,12 @@ struct Feeder {
     std::vector<float> peaks(S);
     std::vector<double> refs(S);
     if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);  // spec_rows, from the untrimmed frames, bounds the trimmed rows
-    const int rc = opts.trim    ? vsyn_pcm_trim_spectral_host(g.handle, &opts.trim_spec, trim_cond(), &opts.spectral, post_run(opts) ? &opts.post : nullptr,
+    std::vector<uint64_t> joined(S, 0);
+    if (opts.split) size_intervals(S, o);
+    const int rc = opts.split   ? vsyn_pcm_split_spectral_host(g.handle, &opts.trim_spec, trim_cond(), &opts.spectral, post_run(opts) ? &opts.post : nullptr,
+                                                               S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(),
+                                                               o.counts.data(), o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &st, &err)
+                   : opts.trim  ? vsyn_pcm_trim_spectral_host(g.handle, &opts.trim_spec, trim_cond(), &opts.spectral, post_run(opts) ? &opts.post : nullptr,
                                                               S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(),
                                                               peaks.data(), refs.data(), &st, &err)
                    : opts.condition ? vsyn_pcm_cond_spectral_host(g.handle, &opts.cond, &opts.spectral, post_run(opts) ? &opts.post : nullptr, S,
@@ -579,13 +614,13 @@ struct Feeder {
     } else if (rc != VSYN_OK) {
       return OkOrError(std::string("GPU spectral layer: ") + (err ? err : "spectral failed"));
     }
-    if (opts.trim && rc == VSYN_OK) {
+    if ((opts.trim || opts.split) && rc == VSYN_OK) {
       refuse_refs(refs, o);
       for (uint32_t s = 0; s < S; ++s) {
         if (!o.err[s].empty()) continue;
-        o.frames[s] = o.bounds[2u * s + 1u] - o.bounds[2u * s];
+        o.frames[s] = opts.split ? joined[s] : o.bounds[2u * s + 1u] - o.bounds[2u * s];
         const uint64_t F = vsyn_spectral_num_frames(&opts.spectral, o.frames[s]);
-        if (opts.post.order && F && F < opts.post.width) {  // trimmed to fewer frames than the delta window
+        if (opts.post.order && F && F < opts.post.width) {  // trimmed or joined to fewer frames than the delta window
           char buf[96];
           snprintf(buf, sizeof(buf), "spectral: delta width %u needs %u frames, file has %llu", opts.post.width, opts.post.width,
                    (unsigned long long)F);
@@ -606,7 +641,7 @@ struct Feeder {
     std::vector<DataRange<const float>> chans(C);
     double acc = 0;
     for (uint32_t c = 0; c < C; ++c) {
-      if (!opts.pcm_s16 && !spectral) {
+      if (!opts.pcm_s16 && !spectral && !opts.intervals_only) {
         const float* x = &g.pcm[((size_t)s * C + c) * pl];
         chans[c] = DataRange<const float>(x, frames);
         if (opts.checksum && o.digest.empty()) acc += abs_sum_f32(x, frames);
@@ -618,12 +653,16 @@ struct Feeder {
       out.trim_start = o.bounds[2u * s];
       out.trim_end = o.bounds[2u * s + 1u];
     }
+    if (!o.counts.empty() && o.err[s].empty()) {
+      const uint32_t* iv = &o.iv[(size_t)s * o.iv_stride * 2u];
+      out.intervals.assign(iv, iv + 2u * (size_t)std::min<uint64_t>(o.counts[s], o.iv_stride));
+    }
     out.abs_sum = acc;
     out.status = o.err[s].empty() ? r.status : OkOrError(o.err[s]);
     if (opts.resample_rate) out.sample_rate = opts.resample_rate;
     stats.frames += frames;
     if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], spectral_dim(opts));
-    if (!callbacks || !o.err[s].empty()) return OkOrError();
+    if (!callbacks || !o.err[s].empty() || opts.intervals_only) return OkOrError();
     std::lock_guard<std::mutex> lk(callbacks_mu);
     if (opts.pcm_s16) {
       if (!callbacks->gotFilePcmS16(r.index, r.header, &g.pcm16[(size_t)s * pl * C], frames)) return OkOrError("aborted by gotFilePcmS16");
@@ -1008,15 +1047,49 @@ void give_bounds(uint64_t* bounds_out, size_t i, const CorpusFileResult& res, bo
   bounds_out[2 * i + 1] = bad ? 0 : res.trim_end;
 }
 
+// A file's intervals of a split run into a buffer of its own, intervals_out[i] (NULL for a failed file, and without intervals).
+void give_intervals(uint32_t** intervals_out, uint64_t* intervals_count_out, size_t i, const CorpusFileResult& res, bool bad) {
+  const size_t n = bad ? 0 : res.intervals.size() / 2u;
+  if (intervals_count_out) intervals_count_out[i] = n;
+  if (!intervals_out) return;
+  intervals_out[i] = nullptr;
+  if (!n) return;
+  intervals_out[i] = (uint32_t*)malloc(res.intervals.size() * sizeof(uint32_t));
+  if (intervals_out[i]) memcpy(intervals_out[i], res.intervals.data(), res.intervals.size() * sizeof(uint32_t));
+  else if (intervals_count_out) intervals_count_out[i] = 0;
+}
+
+// Where a split run's per-file results go (any may be NULL): the joined frames, the interval buffers and their counts.
+struct SplitOuts {
+  uint64_t* frames_out = nullptr;
+  uint32_t** intervals_out = nullptr;
+  uint64_t* intervals_count_out = nullptr;
+  void clear(size_t num_files) const {  // before the run, and behind a run that failed: no buffer is handed over
+    for (size_t i = 0; intervals_out && i < num_files; ++i) {
+      free(intervals_out[i]);
+      intervals_out[i] = nullptr;
+    }
+  }
+  void begin(size_t num_files) const {
+    for (size_t i = 0; intervals_out && i < num_files; ++i) intervals_out[i] = nullptr;
+    for (size_t i = 0; intervals_count_out && i < num_files; ++i) intervals_count_out[i] = 0;
+  }
+};
+
 // A rows run (features or spectral, as set in opts).
 int rows_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts, float** rows_out,
                 uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out,
-                uint64_t* bounds_out = nullptr) {
-  return malloc_corpus(name, datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
-                       [&](size_t i, const CorpusFileResult& res, bool bad) {
-                         if (rows_count_out) rows_count_out[i] = res.feature_rows;
-                         give_bounds(bounds_out, i, res, bad);
-                       });
+                uint64_t* bounds_out = nullptr, const SplitOuts* so = nullptr) {
+  if (so) so->begin(num_files);
+  const int rc = malloc_corpus(name, datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                               [&](size_t i, const CorpusFileResult& res, bool bad) {
+                                 if (rows_count_out) rows_count_out[i] = res.feature_rows;
+                                 give_bounds(bounds_out, i, res, bad);
+                                 if (so && so->frames_out) so->frames_out[i] = bad ? 0 : res.frames;
+                                 if (so) give_intervals(so->intervals_out, so->intervals_count_out, i, res, bad);
+                               });
+  if (rc && so) so->clear(num_files);
+  return rc;
 }
 
 }  // namespace
@@ -1038,7 +1111,8 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                     const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
                     const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr,
-                    const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr) {
+                    const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr, const vsyn_pcm_trim* split = nullptr,
+                    const SplitOuts* so = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
@@ -1055,8 +1129,13 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
     opts.condition = opts.trim = true;  // the rows come from the trimmed mono plane
     opts.trim_spec = *trim;
   }
+  if (split) {
+    if (!vsyn_pcm_trim_num_frames(split, 1)) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid split spec", error_out);
+    opts.condition = opts.split = true;  // the rows come from the joined mono plane
+    opts.trim_spec = *split;
+  }
   return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out,
-                     bounds_out);
+                     bounds_out, split ? so : nullptr);
 }
 
 }  // namespace
@@ -1120,11 +1199,74 @@ extern "C" int ogg_vorbis_pcm_corpus_cond(const uint8_t* const* datas, const siz
                                     pcm_out, frames_out, channels_out, rate_out, nullptr, ok_out, error_out_per_file, stats_out, error_out);
 }
 
+namespace {
+
+// ogg_vorbis_pcm_corpus_trim, and with split != NULL ogg_vorbis_pcm_corpus_split (intervals_only: ogg_vorbis_intervals_corpus).
+int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders, uint32_t files_per_submit, int device,
+               uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
+               uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
+               double* stats_out, const char** error_out, const vsyn_pcm_trim* split = nullptr, bool intervals_only = false,
+               const SplitOuts* so = nullptr);
+
+}  // namespace
+
 extern "C" int ogg_vorbis_pcm_corpus_trim(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                           uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
                                           const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out,
                                           uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                                           double* stats_out, const char** error_out) {
+  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, trim, pcm_out, frames_out,
+                    channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out);
+}
+
+extern "C" int ogg_vorbis_pcm_corpus_split(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                           uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                           const vsyn_pcm_trim* split, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out,
+                                           uint32_t* rate_out, uint32_t** intervals_out, uint64_t* intervals_count_out, uint8_t* ok_out,
+                                           const char** error_out_per_file, double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, nullptr, pcm_out, frames_out,
+                    channels_out, rate_out, nullptr, ok_out, error_out_per_file, stats_out, error_out, split, false, &so);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_split(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                                uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                                const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* split,
+                                                float** rows_out, uint64_t* rows_count_out, uint64_t* frames_out, uint32_t** intervals_out,
+                                                uint64_t* intervals_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                                double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.frames_out = frames_out;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  so.begin(num_files);
+  return spectral_corpus("ogg_vorbis_spectral_corpus_split", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
+                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, nullptr, nullptr,
+                         split, &so);
+}
+
+extern "C" int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                           uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pcm_trim* split,
+                                           uint32_t** intervals_out, uint64_t* intervals_count_out, uint64_t* frames_out, uint32_t* rate_out,
+                                           uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  so.begin(num_files);
+  if (!split) return refuse_call(nullptr, num_files, "ogg_vorbis_intervals_corpus: no split spec", error_out);
+  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, VSYN_PCM_F32, nullptr, nullptr, nullptr,
+                    frames_out, nullptr, rate_out, nullptr, ok_out, error_out_per_file, stats_out, error_out, split, true, &so);
+}
+
+namespace {
+
+int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders, uint32_t files_per_submit, int device,
+               uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
+               uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
+               double* stats_out, const char** error_out, const vsyn_pcm_trim* split, bool intervals_only, const SplitOuts* so) {
+  if (so) so->begin(num_files);
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
     return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
   CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
@@ -1139,13 +1281,24 @@ extern "C" int ogg_vorbis_pcm_corpus_trim(const uint8_t* const* datas, const siz
     opts.condition = opts.trim = true;  // one mono plane per file
     opts.trim_spec = *trim;
   }
-  return malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
-                       [&](size_t i, const CorpusFileResult& res, bool bad) {
-                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
-                         if (channels_out) channels_out[i] = res.channels;
-                         if (rate_out) rate_out[i] = res.sample_rate;
-                         give_bounds(bounds_out, i, res, bad);
-                       });
+  if (split) {
+    if (!vsyn_pcm_trim_num_frames(split, 1)) return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus_split: invalid split spec", error_out);
+    opts.condition = opts.split = true;  // one mono plane per file, or with intervals_only none
+    opts.intervals_only = intervals_only;
+    opts.trim_spec = *split;
+  }
+  const int rc = malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
+                               [&](size_t i, const CorpusFileResult& res, bool bad) {
+                                 if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                                 if (channels_out) channels_out[i] = res.channels;
+                                 if (rate_out) rate_out[i] = res.sample_rate;
+                                 give_bounds(bounds_out, i, res, bad);
+                                 if (so && split) give_intervals(so->intervals_out, so->intervals_count_out, i, res, bad);
+                               });
+  if (rc && so) so->clear(num_files);
+  return rc;
 }
+
+}  // namespace
 
 extern "C" void ogg_vorbis_features_free(float* rows) { free(rows); }

@@ -39,6 +39,7 @@ struct CorpusFileResult {
   double abs_sum = 0;    // sum |x| over all channels, in double: a cheap content check that does not need the PCM kept
   uint64_t feature_rows = 0;  // CorpusOptions::features / spectral: rows delivered
   uint64_t trim_start = 0, trim_end = 0;  // CorpusOptions::trim: the samples kept, [trim_start, trim_end) of the (resampled) signal
+  std::vector<uint32_t> intervals;        // CorpusOptions::split: (start, end) of every non-silent interval, in samples of that signal
 };
 
 struct CorpusCallbacks {
@@ -100,6 +101,12 @@ struct CorpusOptions {
   // the trimmed plane. A file with a sample that is not finite fails alone. The default is off: today's output.
   bool trim = false;
   vsyn_pcm_trim trim_spec = {2048, 512, 60.0};
+  // split (needs condition, excludes trim; its parameters are trim_spec's): every silent stretch of each file's downmix is removed on
+  // the device, not the head and the tail alone (include/vorbis_synth_hip.h, "PCM splitting"). frames in the results are those of
+  // the joined signal, intervals the non-silent intervals; a spectral run computes its rows from the joined plane. intervals_only
+  // (a PCM run with split): the intervals alone; the joined signal is not made, no PCM is delivered, and frames are the unsplit
+  // ones. A file with a sample that is not finite fails alone. The default is off: today's output.
+  bool split = false, intervals_only = false;
 };
 
 struct CorpusStats {
@@ -195,6 +202,29 @@ int ogg_vorbis_spectral_corpus_trim(const uint8_t* const* datas, const size_t* l
                                     const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, float** rows_out,
                                     uint64_t* rows_count_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                                     double* stats_out, const char** error_out);
+// ogg_vorbis_pcm_corpus_trim with the split in the trim's place (CorpusOptions::split): pcm_out receives each file's joined mono
+// plane, frames_out its length. intervals_out (may be NULL) receives per file NULL (failed, or no intervals) or a buffer of
+// intervals_count_out[i] (start, end) pairs of uint32 allocated by the library, released with ogg_vorbis_features_free. split =
+// NULL is ogg_vorbis_pcm_corpus_cond (no intervals).
+int ogg_vorbis_pcm_corpus_split(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                const vsyn_pcm_trim* split, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out,
+                                uint32_t** intervals_out, uint64_t* intervals_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                double* stats_out, const char** error_out);
+// ogg_vorbis_spectral_corpus_trim with the split in the trim's place: the rows of the joined plane. A file joined to fewer frames
+// than post->width (order > 0) fails alone. frames_out (may be NULL): each file's joined length; intervals_out / intervals_count_out
+// as above. split = NULL is ogg_vorbis_spectral_corpus_cond.
+int ogg_vorbis_spectral_corpus_split(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                     const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* split, float** rows_out,
+                                     uint64_t* rows_count_out, uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
+                                     uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
+// The intervals alone (CorpusOptions::intervals_only): decode, resample (target_rate != 0), frame energies, intervals; no PCM comes
+// back from the device. frames_out / rate_out: each file's (resampled) length and rate; intervals_out / intervals_count_out as above.
+int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pcm_trim* split, uint32_t** intervals_out,
+                                uint64_t* intervals_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                                const char** error_out_per_file, double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
 }
 

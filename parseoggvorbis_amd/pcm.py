@@ -7,7 +7,9 @@ mono=True returns ONE plane per file, made on the device by the conditioning sta
 conditioning"; float64 model: tests/condition_model.py): the channels' float32 mean like librosa.load's default, optionally
 divided by its peak (peak_normalize) and pre-emphasised (preemphasis), after the resampling and before the copy to the host.
 trim_db cuts the silent head and tail of that plane first, as librosa.effects.trim does on a mono signal (include/vorbis_synth_hip.h,
-"PCM trimming"; float64 model: tests/trim_model.py).
+"PCM trimming"; float64 model: tests/trim_model.py). split_db removes every silent stretch instead, as joining the slices of
+librosa.effects.split does, and get_intervals_batch returns those intervals alone, without any PCM coming back ("PCM splitting";
+model: tests/split_model.py).
 
 Every argument is checked before the library is loaded."""
 import ctypes as C
@@ -100,12 +102,35 @@ def give_trim_index(trim_index, bounds, results):
                          for i, r in enumerate(results)]
 
 
+def split_spec(split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None, trim=None, error=PcmError):
+    """Checks the split arguments as trim_spec checks the trim's (the stage takes the same C spec) and returns it, or None for
+    split_db=None: the stage is off. trim: the call's trim spec; a call either trims or splits."""
+    if split_index is not None and not isinstance(split_index, list):
+        raise error("split_index must be None or a list, got %r" % (split_index,))
+    if split_db is None:
+        return None
+
+    def renamed(msg):
+        return error(str(msg).replace("trim_", "split_"))
+    spec = trim_spec(split_db, split_frame_length, split_hop_length, None, renamed)
+    if trim is not None:
+        raise error("split_db and trim_db exclude each other: the split's first start and last end are the trim's bounds")
+    return spec
+
+
+def give_split_index(split_index, buffers, results):
+    """split_index[:] = one (n, 2) int64 array per file from the run's interval buffers; None for a file that failed, and for every
+    file with the stage off (buffers None)."""
+    if split_index is not None:
+        split_index[:] = [None if buffers is None or isinstance(r, Exception) else buffers.take(i) for i, r in enumerate(results)]
+
+
 _load = _corpus.load
 
 
 def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0, device=0, errors="raise", files_per_submit=64,
                   stats=None, mono=False, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048, trim_hop_length=512,
-                  trim_index=None):
+                  trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None):
     """PCM of many Ogg Vorbis files in one corpus run: a list of (pcm, sr) tuples. pcm is float32 (channels, frames), or int16
     (frames, channels) with ov_read's conversion; sr is the rate of the returned PCM. sr=None keeps each file's own rate (the
     PCM is bit for bit that of ogg_vorbis_decode_corpus); an integer resamples every file to it on the GPU. errors="raise": the
@@ -119,7 +144,11 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     samples, every trim_hop_length samples, lies more than d dB below the loudest frame's are cut off first, as
     librosa.effects.trim(y, top_db=d) does; the peak and the pre-emphasis are those of what is kept. trim_index (optional list)
     receives one (start, end) per file, in samples of the returned rate (None for a failed file, and for every file with the stage off). A
-    file with an Inf or NaN sample fails alone."""
+    file with an Inf or NaN sample fails alone.
+    split_db=d (instead of trim_db, with split_frame_length and split_hop_length; needs mono=True): every stretch of such frames is
+    removed, not the head and the tail alone: pcm is the concatenation of y[start:end] over librosa.effects.split(y, top_db=d)'s
+    intervals, and the peak and the pre-emphasis are those of that joined signal. split_index (optional list) receives one (n, 2)
+    int64 array of (start, end) per file (None for a failed file, and for every file with the stage off)."""
     _corpus.check_errors(errors)
     target = check_sr(sr)
     name = _format(dtype)
@@ -131,6 +160,9 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index)
     if not mono and trim is not None:
         raise PcmError("trim_db acts on the mono signal: pass mono=True")
+    split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim)
+    if not mono and split is not None:
+        raise PcmError("split_db acts on the mono signal: pass mono=True")
     lib = _load()
     n = len(list_of_bytes)
     frames = np.zeros(n, np.uint64)
@@ -146,6 +178,17 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
         return _corpus.copy_into(a, p), int(rates[i])
 
     args = (threads, feeders, files_per_submit, device, target, FORMATS[name])
+    if split is not None:
+        ib = _corpus.IntervalBuffers(lib, n)
+        try:
+            res = _corpus.run(lib, lib.ogg_vorbis_pcm_corpus_split, list_of_bytes, args + (C.byref(cond) if cond.options else None, C.byref(split)),
+                              (frames, chans, rates, ib.ptrs, ib.counts), build, PcmError, errors, "pcm", stats)
+            give_split_index(split_index, ib, res)
+        finally:
+            ib.free()
+        give_trim_index(trim_index, None, res)
+        return res
+    give_split_index(split_index, None, [None] * n)
     if trim is not None:
         bounds = np.zeros((max(n, 1), 2), np.uint64)
         res = _corpus.run(lib, lib.ogg_vorbis_pcm_corpus_trim, list_of_bytes, args + (C.byref(cond) if cond.options else None, C.byref(trim)),
@@ -156,6 +199,41 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     res = _corpus.run(lib, fn, list_of_bytes, args + extra, (frames, chans, rates), build, PcmError, errors, "pcm", stats)
     give_trim_index(trim_index, None, res)
     return res
+
+
+def get_intervals_batch(list_of_bytes, top_db=60.0, frame_length=2048, hop_length=512, sr=None, threads=0, feeders=0, device=0, errors="raise",
+                        files_per_submit=64, stats=None):
+    """The non-silent intervals of many Ogg Vorbis files in one corpus run: a list of (intervals, sr, frames) tuples. intervals is
+    an (n, 2) int64 array of (start, end) in samples, what librosa.effects.split(y, top_db=top_db, frame_length=frame_length,
+    hop_length=hop_length) returns for the mono signal y = get_pcm_batch(mono=True, sr=sr); sr is the rate they are counted at and
+    frames the length of y. The frame energies and the intervals are computed on the device and no PCM is copied back. sr, errors
+    and stats as for get_pcm_batch; a file with an Inf or NaN sample fails alone."""
+    _corpus.check_errors(errors)
+    target = check_sr(sr)
+
+    def renamed(msg):
+        return PcmError(str(msg).replace("trim_db", "top_db").replace("trim_", ""))
+    if top_db is None:
+        raise PcmError("top_db must be a number in (0, 200], got None")
+    split = trim_spec(top_db, frame_length, hop_length, None, renamed)
+    lib = _load()
+    n = len(list_of_bytes)
+    counts = np.zeros(max(n, 1), np.uint64)
+    frames = np.zeros(max(n, 1), np.uint64)
+    rates = np.zeros(max(n, 1), np.uint32)
+
+    def build(i, p):
+        return _corpus.copy_into(np.zeros((int(counts[i]), 2), np.uint32), p).astype(np.int64), int(rates[i]), int(frames[i])
+
+    return _corpus.run(lib, lib.ogg_vorbis_intervals_corpus, list_of_bytes, (threads, feeders, files_per_submit, device, target, C.byref(split)),
+                       (counts, frames, rates), build, PcmError, errors, "intervals", stats)
+
+
+def get_intervals_from_raw_bytes(raw_bytes, top_db=60.0, **kwargs):
+    """One file's (intervals, sr, frames), as get_intervals_batch."""
+    kwargs.setdefault("threads", 1)
+    kwargs.setdefault("feeders", 1)
+    return get_intervals_batch([raw_bytes], top_db, **kwargs)[0]
 
 
 def get_pcm_from_raw_bytes(raw_bytes, sr=None, dtype="float32", **kwargs):

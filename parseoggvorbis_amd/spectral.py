@@ -10,7 +10,8 @@ scipy.signal.resample_poly's arithmetic), so that one mel table serves the whole
 device as well (include/vorbis_synth_hip.h, "spectral post-processing"): librosa.feature.delta's columns, then per-column mean or
 mean / variance normalisation; tests/spectral_post_model.py is their float64 model. peak_normalize / preemphasis condition the mono
 waveform on the device in front of the STFT (include/vorbis_synth_hip.h, "PCM conditioning"; model: tests/condition_model.py), and
-trim_db cuts its silent head and tail in front of both ("PCM trimming"; model: tests/trim_model.py)."""
+trim_db cuts its silent head and tail in front of both ("PCM trimming"; model: tests/trim_model.py), or split_db every silent
+stretch ("PCM splitting"; model: tests/split_model.py)."""
 import ctypes as C
 import math
 
@@ -143,7 +144,7 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                        htk=False, norm="slaney", center=True, power=2.0, log_floor=1e-3, amin=1e-10, top_db=80.0, n_mfcc=20,
                        threads=0, feeders=0, device=0, errors="raise", files_per_submit=64, stats=None, sr=None, delta=0, delta_width=9,
                        normalize=None, std_floor=1e-5, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048,
-                       trim_hop_length=512, trim_index=None):
+                       trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels otherwise. errors="raise": the first failed file raises SpectralError naming it; errors="return": its entry
     is the SpectralError. stats (optional list) receives the run's 8 corpus statistics. sr=None: each file at its own rate;
@@ -157,17 +158,36 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     or NaN sample fails alone under peak_normalize. With the defaults nothing is launched.
     trim_db=d cuts the silent head and tail of the mono signal first, as get_pcm_batch(mono=True, trim_db=d, ...) does (the peak, the
     pre-emphasis, the frames and "fewer frames than delta_width" are those of what is kept); trim_index (optional list) receives
-    one (start, end) per file in samples of the (resampled) signal, None for a failed file and for every file with the stage off."""
+    one (start, end) per file in samples of the (resampled) signal, None for a failed file and for every file with the stage off.
+    split_db=d (instead of trim_db) removes every silent stretch of the mono signal first, as get_pcm_batch(mono=True, split_db=d,
+    ...) does: the rows are those of the joined signal; split_index (optional list) receives one (n, 2) int64 array of (start, end)
+    per file, None for a failed file and for every file with the stage off."""
     _corpus.check_errors(errors)
-    from .pcm import check_sr, cond_spec, give_trim_index, trim_spec
+    from .pcm import check_sr, cond_spec, give_split_index, give_trim_index, split_spec, trim_spec
     target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
     post, dim, keep = post_spec(spec_dim(spec), delta, delta_width, normalize, std_floor)
     cond = cond_spec(peak_normalize, preemphasis, SpectralError)
     trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index, SpectralError)
+    split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
+    if split is not None:
+        ib = _corpus.IntervalBuffers(lib, len(list_of_bytes))
+        joined = np.zeros(max(len(list_of_bytes), 1), np.uint64)
+        try:
+            res = _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_split, list_of_bytes,
+                              (threads, feeders, files_per_submit, device, C.byref(spec), target, None if post is None else C.byref(post),
+                               C.byref(cond) if cond.options else None, C.byref(split)), (counts, joined, ib.ptrs, ib.counts),
+                              lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors,
+                              "spectral", stats)
+            give_split_index(split_index, ib, res)
+        finally:
+            ib.free()
+        give_trim_index(trim_index, None, res)
+        return res
+    give_split_index(split_index, None, [None] * len(list_of_bytes))
     if trim is not None:
         bounds = np.zeros((max(len(list_of_bytes), 1), 2), np.uint64)
         res = _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_trim, list_of_bytes,
