@@ -841,6 +841,80 @@ int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, cons
                                  uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                  vsyn_status* status, const char** err);
 
+/* ---- pitch: the fundamental frequency of the decoded PCM per frame (YIN), computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, and its sample rate sr. Parameters: frame_length L,
+ * hop_length H, fmin, fmax, trough_threshold, VSYN_PITCH_CENTER. Output: a float32 matrix (F, 2), one row per frame: f0 in Hz, and
+ * the cumulative-mean-normalised difference at the chosen lag (the aperiodicity that librosa.yin discards and that a caller
+ * thresholds for voicing). This is librosa.yin(y, fmin, fmax, sr, frame_length=L, win_length=L / 2, hop_length=H,
+ * trough_threshold, center, pad_mode="constant") (librosa >= 0.10) on the mono signal. librosa is not among the test dependencies
+ * and parity with it is not claimed: the device is compared against a float64 model of the arithmetic below (tests/pitch_model.py),
+ * and the model against a restatement in librosa's own words (tests/test_pitch_cpu.py).
+ *
+ *  1. Mono. y[t] is step 1 of the conditioning stage, the one device function every stage uses.
+ *  2. Framing. W = L / 2 (integer division). VSYN_PITCH_CENTER pads L / 2 zeros on both sides. The frame count F is that of
+ *     "spectral features" step 2 with n_fft = L and the same hop (vsyn_pitch_num_frames), so that row f lines up with row f of the
+ *     spectral rows. z[i] = y_pad[f H + i] for i < L.
+ *  3. Periods, per segment rate: p_min = max(floor(sr / fmax), 1), p_max = min(ceil(sr / fmin), L - W - 1), computed in double on the
+ *     host per call. n = p_max - p_min + 1 lags.
+ *  4. Difference function: d[tau] = sum_{j = 1 .. W} (z[j] - z[j + tau])^2 for tau = 1 .. p_max: librosa's sum, including its start
+ *     at j = 1, in direct form and not through an FFT. Each difference is formed in float64 (exact for float32 samples) and each
+ *     sum is ONE float64 fma chain with j ascending. librosa zeroes autocorrelation values below 1e-6 in magnitude; that guards the
+ *     cancellation of its FFT route, which the direct form does not have, and is NOT reproduced: quiet frames keep their d.
+ *  5. Cumulative mean normalisation: S[tau] = sum_{u = 1 .. tau} d[u] in float64; c[i] = d[p_min + i] / (S[p_min + i] / (p_min + i)
+ *     + tiny) for i < n, tiny = 2.2250738585072014e-308. S comes from a scan in a fixed order, a function of p_max alone
+ *     (csrc/vsyn_pitch.h states it); its terms are >= 0, so its relative error is at most (terms) * 2^-53.
+ *  6. Troughs: trough[i] = c[i] < c[i-1] and c[i] <= c[i+1] for 0 < i < n - 1; trough[0] = c[0] < c[1]; trough[n-1] = c[n-1] <
+ *     c[n-2]. i* is the first i with trough[i] and c[i] < trough_threshold; without one, the first index of the minimum of c.
+ *     Integer "first index" reductions, no atomics.
+ *  7. Parabolic shift, for 0 < i* < n - 1: a = (c[i*+1] + c[i*-1]) - 2 c[i*], b = (c[i*+1] - c[i*-1]) / 2, shift = -b / a if
+ *     |b| < |a|, else 0; shift = 0 at either end.
+ *  8. Row f: column 0 = float32(sr / (p_min + i* + shift)), computed in float64 and rounded once; column 1 = float32(c[i*]). An
+ *     all-zero frame gives (sr / p_min, 0) exactly.
+ *  9. Not finite. A segment with an Inf or NaN sample among its T frames (the trim stage's test, whether or not a frame covers the
+ *     sample) is refused alone: every value of its F rows is NaN and its entry of the refused array is 1. The other segments of
+ *     the call are not affected.
+ * 10. Checks (VSYN_ERR_INVALID before anything runs): 4 <= L <= 8192; 1 <= H; unknown option bits; fmin, fmax and
+ *     trough_threshold finite; 0 < fmin < fmax <= sr / 2 and n >= 2 for every segment's rate; 0 < trough_threshold <= 1. A rate
+ *     of 0 skips the segment (0 rows).
+ *
+ * Not built: pYIN, a win_length other than L / 2, composition with the trim, split and conditioning stages. The same PCM gives the
+ * same bits, alone, in any slot of a batch and at any alignment. The pitch entry points read PCM only: they touch neither stream
+ * state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM, and a later vsyn_pcm_fetch_host returns the same PCM. One
+ * handle's pitch entry points share its pitch workspace, which is no other stage's. */
+#define VSYN_PITCH_CENTER 1u /* pad frame_length/2 zeros on both sides (librosa's center=True) */
+
+typedef struct vsyn_pitch_spec {
+  uint32_t frame_length; /* L */
+  uint32_t hop_length;   /* H */
+  uint32_t options;      /* VSYN_PITCH_* bits */
+  uint32_t reserved;     /* 0 */
+  double fmin, fmax;     /* Hz */
+  double trough_threshold;
+} vsyn_pitch_spec;
+
+/* F of step 2 for a segment of `frames` PCM frames, 0 for an invalid spec (the checks of step 10 that need no rate). */
+uint64_t vsyn_pitch_num_frames(const vsyn_pitch_spec* spec, uint64_t frames);
+
+/* The caller's planar PCM: d_pcm[(g * channels + c) * plane_stride + t], d_frames[S] (device) PCM frames per segment (clamped to
+ * plane_stride). sample_rates[S] is a HOST array; a rate of 0 skips the segment. Writes d_seg_row_off[S+1] (uint64, may be NULL):
+ * segment g's rows are [d_seg_row_off[g], d_seg_row_off[g+1]) of d_rows, which must hold sum_g vsyn_pitch_num_frames(spec,
+ * frames_g) rows of 2 columns (S * vsyn_pitch_num_frames(spec, plane_stride) always suffices); d_refused[S] (device, uint32, may
+ * be NULL): 1 for a refused segment (step 9), else 0. Asynchronous on hip_stream. */
+int vsyn_pitch_device(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
+                      const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows,
+                      uint64_t* d_seg_row_off, uint32_t* d_refused, void* hip_stream, const char** err);
+
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle, per segment of that submit, each segment resampled from in_rates[g]
+ * to out_rate first when out_rate != 0 (0: at its own rate in_rates[g]; the periods are those of the rate the rows are computed
+ * at). in_rates[S] (host); a rate of 0 skips the segment. seg_rows[S] receives each segment's row count; rows (may be NULL when only
+ * the counts are wanted: nothing is launched) receives the rows of all segments back to back, 2 columns each, at most
+ * rows_capacity rows (VSYN_ERR_INVALID with the counts filled if it is too small); refused_out[S] (uint32, may be NULL) as
+ * d_refused. status as for vsyn_pcm_spectral_host. Synchronous. */
+int vsyn_pcm_pitch_host(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                        float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
+                        const char** err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ VSYN_SUBMIT_KEEP_PCM = 4
 VSYN_SUBMIT_PRE_KERNELS = 8
 VSYN_PCM_S16, VSYN_PCM_F32 = 1, 2
 VSYN_COND_PEAK, VSYN_COND_PREEMPH = 1, 2
+VSYN_PITCH_CENTER = 1
 
 
 class Floor1(C.Structure):
@@ -78,6 +79,11 @@ class PcmCond(C.Structure):  # vsyn_pcm_cond
 
 class PcmTrim(C.Structure):  # vsyn_pcm_trim
     _fields_ = [("frame_length", C.c_uint32), ("hop_length", C.c_uint32), ("top_db", C.c_double)]
+
+
+class PitchSpec(C.Structure):  # vsyn_pitch_spec
+    _fields_ = [("frame_length", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32), ("reserved", C.c_uint32),
+                ("fmin", C.c_double), ("fmax", C.c_double), ("trough_threshold", C.c_double)]
 
 
 class Status(C.Structure):
@@ -211,6 +217,7 @@ _SYMBOLS = [
     "vsyn_pcm_trim_num_frames", "vsyn_pcm_trim_device", "vsyn_pcm_trim_host", "vsyn_pcm_trim_spectral_host",
     "vsyn_pcm_split_max_intervals", "vsyn_pcm_split_device", "vsyn_pcm_split_host", "vsyn_pcm_split_intervals_host",
     "vsyn_pcm_split_spectral_host",
+    "vsyn_pitch_num_frames", "vsyn_pitch_device", "vsyn_pcm_pitch_host",
 ]
 
 
@@ -301,6 +308,10 @@ def load():
     lib.vsyn_pcm_split_intervals_host.argtypes = [vp, C.POINTER(PcmTrim), u32, vp, u32, vp, vp, vp, u64, vp, cpp]
     lib.vsyn_pcm_split_spectral_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPost),
                                                  u32, vp, u32, vp, u64, vp, vp, vp, vp, u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_pitch_num_frames.argtypes = [C.POINTER(PitchSpec), u64]
+    lib.vsyn_pitch_num_frames.restype = u64
+    lib.vsyn_pitch_device.argtypes = [vp, C.POINTER(PitchSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_pitch_host.argtypes = [vp, C.POINTER(PitchSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -682,6 +693,33 @@ class Synth:
             raise VsynError(rc, (err.value or b"").decode())
         return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], frames=frames[:S], counts=counts[:S], intervals=self._intervals(counts, iv, S),
                     peaks=peaks[:S], refs=refs[:S], flags=st.flags)
+
+    def pitch_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, d_refused=None, stream=None):
+        """vsyn_pitch_device on device pointers (ints); sample_rates is a host sequence."""
+        rates = np.ascontiguousarray(sample_rates, dtype=np.uint32)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_pitch_device(self.h, None if spec is None else C.byref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels,
+                                        d_frames, d_rows, d_seg_row_off, d_refused, stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+
+    def pcm_pitch_host(self, spec, in_rates, out_rate=0):
+        """vsyn_pcm_pitch_host over the last submit's segments: returns dict(rc, rows [total][2], seg_rows [S], refused [S], flags)."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S = len(rates)
+        seg_rows = np.zeros(max(S, 1), np.uint64)
+        refused = np.zeros(max(S, 1), np.uint32)
+        st, err = Status(), C.c_char_p()
+        rc = self.lib.vsyn_pcm_pitch_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None, C.byref(st), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum())
+        rows = np.zeros((max(total, 1), 2), np.float32)
+        rc = self.lib.vsyn_pcm_pitch_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows), _ptr(refused),
+                                          C.byref(st), C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], refused=refused[:S], flags=st.flags)
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

@@ -26,6 +26,7 @@
 #include "vsyn_condition.h"
 #include "vsyn_trim.h"
 #include "vsyn_split.h"
+#include "vsyn_pitch.h"
 
 static const uint32_t k_inverse_db_bits[256] = {
 #include "vorbis_floor1_inverse_db.inc"
@@ -124,6 +125,7 @@ struct vsyn_handle {
   CondWs cd;                           // vsyn_condition.h
   TrimWs tr;                           // vsyn_trim.h
   SplitWs sl;                          // vsyn_split.h
+  PitchWs pt;                          // vsyn_pitch.h
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -1860,6 +1862,77 @@ int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, cons
   const SplitOut so{frames_out, counts_out, intervals_out, intervals_stride};
   return pcm_trim_spectral_host(h, trim, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, refs_out, status,
                                 err, &so);
+}
+
+// ---- pitch (vsyn_pitch.h) ----
+
+static bool pitch_center(const vsyn_pitch_spec* spec) { return (spec->options & VSYN_PITCH_CENTER) != 0; }
+
+uint64_t vsyn_pitch_num_frames(const vsyn_pitch_spec* spec, uint64_t frames) {
+  if (pitch_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
+  return spec_num_frames(spec->frame_length, spec->hop_length, pitch_center(spec), frames);
+}
+
+int vsyn_pitch_device(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t S, const uint32_t* sample_rates, const float* d_pcm,
+                      uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off,
+                      uint32_t* d_refused, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = pitch_check(spec, S, sample_rates, err);
+  if (rc) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_rows || plane_stride == 0 || channels == 0 || channels > 255)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  const uint64_t f_max = spec_num_frames(spec->frame_length, spec->hop_length, pitch_center(spec), plane_stride);
+  std::lock_guard<std::mutex> lk(h->mu);
+  return pitch_launch(h->pt, h->device, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, d_rows, d_seg_row_off,
+                      d_refused, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_pitch_host(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                        uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  status_reset(status);
+  int rc;
+  std::vector<uint32_t> pt_rates;  // resampled: the pitch pass sees every resampled segment at out_rate
+  if (out_rate) {
+    rc = rs_check(S, in_rates, out_rate, err);
+    if (rc) return rc;
+    pt_rates.resize(S);
+    for (uint32_t g = 0; g < S; ++g) pt_rates[g] = in_rates[g] ? out_rate : 0u;
+  }
+  const uint32_t* rates = out_rate ? pt_rates.data() : in_rates;
+  rc = pitch_check(spec, S, rates, err);
+  if (rc) return rc;
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  if (refused_out) memset(refused_out, 0, sizeof(uint32_t) * S);
+  // the lock covers the whole call: the resample and pitch workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T(S);
+  uint64_t total = 0, f_max = 0, t_max;
+  rc = last_submit_frames(h, S, in_rates, out_rate, T.data(), &t_max, err);
+  if (rc) return rc;
+  t_max = std::max<uint64_t>(t_max, 1);
+  for (uint32_t g = 0; g < S; ++g) {
+    const uint64_t f = rates[g] ? spec_num_frames(spec->frame_length, spec->hop_length, pitch_center(spec), T[g]) : 0;
+    seg_rows[g] = f;
+    total += f;
+    f_max = std::max(f_max, f);
+  }
+  if (!rows || S == 0) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
+  hipStream_t hs = h->host_stream;
+  PcmView v;  // the synthesis PCM with the last submit's SegInfo, or the resampler's planes with its frames
+  rc = pcm_chain(h, S, in_rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err);
+  if (rc) return rc;
+  HIPCHK(h->pt.rows.ensure(total * 2u + 1));
+  HIPCHK(h->pt.refused.ensure(S));
+  rc = pitch_launch(h->pt, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->pt.rows.p, nullptr, h->pt.refused.p, hs, err);
+  if (rc) return rc;
+  if (total) HIPCHK(hipMemcpyAsync(rows, h->pt.rows.p, sizeof(float) * total * 2u, hipMemcpyDeviceToHost, hs));
+  if (refused_out) HIPCHK(hipMemcpyAsync(refused_out, h->pt.refused.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
+  return sync_status_into(h, status, err);
 }
 
 }  // extern "C"

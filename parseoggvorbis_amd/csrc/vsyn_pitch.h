@@ -1,0 +1,342 @@
+// vsyn_pitch.h — pitch: per frame the fundamental frequency (YIN) and the normalised difference at the chosen lag, from planar
+// float32 PCM already on the device (librosa.yin on the mono signal). Semantics: include/vorbis_synth_hip.h, "pitch".
+//
+// Three kernels on one stream (the per-segment periods are built on the host in double, pitch_periods):
+//   1. vsyn_pitch_offsets_kernel  one workgroup: per segment its PCM frames, its frame count (spec_num_frames), the exclusive row
+//                                 scan seg_off[S+1] (the spectral stage's offsets kernel, without its dB maxima).
+//   2. vsyn_pitch_kernel          grid (tile of FT frames, segment). LDS: the tile's span of the mono signal as float32 (the downmix
+//                                 is done while loading, zeros outside [0, T); H > L: the frames back to back, as the trim stage
+//                                 stages them), then d[FT][p_max] as float64.
+//                                 Difference function: the (frame, lag) pairs of the tile are dealt to the threads in order, lag
+//                                 fastest, PITCH_ILP pairs per thread PITCH_THREADS apart. A thread owns its lag tau and walks j =
+//                                 1 .. W: z[j] is one address per frame (a broadcast read), z[j + tau] consecutive across the lanes
+//                                 (ds_read_b32, 32 banks, no conflict inside a frame). Both are widened to float64, the difference
+//                                 is exact, and the sum is ONE fma chain with j ascending, whatever the tile and the thread: the
+//                                 PITCH_ILP chains of a thread are independent and only hide the fma latency (the workgroup is one
+//                                 wave per SIMD, two workgroups per CU at the LDS budget).
+//                                 Then per frame, by the whole workgroup: the cumulative sum S (order below), c in place of d,
+//                                 the first trough below the threshold and the first minimum by 64-bit integer minima through the
+//                                 wave (__shfl_xor) and the four waves (LDS), and thread 0 writes the row. No atomics.
+//                                 The workgroup also looks at every sample of its share of the segment for an Inf or a NaN
+//                                 (trim_not_finite, the trim stage's test) and stores one flag word per tile.
+//   3. vsyn_pitch_finish_kernel   one workgroup per segment: a segment with a flagged tile is refused: its rows become NaN and its
+//                                 word of the refused array 1.
+// Order of S: with K = ceil(p_max / PITCH_THREADS), thread t owns the lags t K + 1 .. (t + 1) K. It adds its d in ascending order
+// (its total), the totals are scanned inside each wave by Hillis-Steele over the lane offsets 1, 2, .. 32, a wave's offset is the sum
+// of the earlier waves' totals in ascending order, and S[tau] = (wave offset + the exclusive lane prefix) + d[first] + .. + d[tau],
+// added left to right. A function of p_max alone. Every term is >= 0: the relative error is at most (terms) * 2^-53.
+// Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
+#pragma once
+#include "vsyn_device.h"
+#include "vsyn_host.h"
+#include "vsyn_spectral.h"
+#include "vsyn_trim.h"
+
+#define PITCH_THREADS 256
+#define PITCH_WAVES (PITCH_THREADS / 64)
+#define PITCH_ILP 4u                        // independent fma chains per thread
+#define PITCH_FT_MAX 64u                    // frames per workgroup, at most
+#define PITCH_LDS_BUDGET (79u * 1024u)      // dynamic LDS of a workgroup: two fit a CU's 160 KiB beside their static words
+#define PITCH_TINY 2.2250738585072014e-308  // numpy.finfo(float64).tiny
+#define PITCH_NONE 0xFFFFFFFFFFFFFFFFull
+
+struct PitchSeg {  // one segment's periods (host, double): p_max = 0 skips the segment
+  double sr;
+  uint32_t p_min, p_max;
+};
+
+struct PitchCtx {  // launch arguments
+  const PitchSeg* seg;
+  const float* pcm;
+  uint64_t plane;
+  uint32_t C, S;
+  const uint32_t* frames;  // PCM frames per segment (caller's, or the resampler's), or
+  const SegInfo* si;       // the last submit's SegInfo (total_emit)
+  uint32_t L, H, FT;       // frame_length, hop_length, frames per workgroup
+  uint32_t center;
+  uint32_t tiles;          // workgroups per segment (grid.x): the flags' stride
+  double thr;              // trough_threshold
+  uint32_t* segF;          // [S] frames
+  uint64_t* segoff;        // [S+1]
+  uint32_t* flags;         // [S][tiles] a sample of the tile's share is not finite
+  uint32_t* refused;       // [S]
+  float* rows;             // [segoff[S]][2]
+};
+
+__device__ __forceinline__ uint64_t pitch_frames(const PitchCtx& A, uint32_t g) {
+  return trim_min64(A.frames ? A.frames[g] : A.si[g].total_emit, A.plane);
+}
+
+__global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_offsets_kernel(const PitchCtx A) {
+  wg_exclusive_scan<PITCH_THREADS, 1>(A.S, A.segoff, [&](uint32_t g, uint64_t* v) {
+    v[0] = A.seg[g].p_max ? spec_num_frames(A.L, A.H, A.center != 0, pitch_frames(A, g)) : 0ull;
+    A.segF[g] = (uint32_t)v[0];
+  });
+}
+
+// the minimum of v over the workgroup, for every thread (s_r: PITCH_WAVES words of LDS, free again on return)
+__device__ __forceinline__ uint64_t pitch_wg_min(uint64_t v, uint64_t* s_r) {
+  v = trim_wave_min(v);
+  if ((threadIdx.x & 63u) == 0) s_r[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = trim_min64(trim_min64(s_r[0], s_r[1]), trim_min64(s_r[2], s_r[3]));
+  __syncthreads();
+  return v;
+}
+
+__global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCtx A) {
+  extern __shared__ double s_pitch[];
+  __shared__ uint64_t s_r[PITCH_WAVES];
+  __shared__ double s_w[PITCH_WAVES];
+  const uint32_t g = blockIdx.y, tid = threadIdx.x;
+  const PitchSeg sg = A.seg[g];
+  uint32_t* flag = A.flags + (size_t)g * A.tiles + blockIdx.x;
+  const uint64_t F = A.segF[g];
+  const uint64_t f0 = (uint64_t)blockIdx.x * A.FT;
+  if (sg.p_max == 0u || (f0 >= F && blockIdx.x != 0u)) {  // (workgroup-uniform) nothing here: the flag word is still this workgroup's to write
+    if (tid == 0) *flag = 0u;
+    return;
+  }
+  const uint64_t T = pitch_frames(A, g);
+  const uint32_t L = A.L, H = A.H, W = L / 2u, PL = sg.p_max;
+  const uint32_t nf = f0 < F ? (uint32_t)trim_min64(A.FT, F - f0) : 0u;  // (F = 0, T > 0: tile 0 still looks at the samples)
+  const bool last = f0 + A.FT >= F;
+  const uint32_t C = A.C;
+  const float inv_c = 1.0f / (float)C;
+  const float* x = A.pcm + (size_t)g * C * A.plane;
+  const int64_t pad = A.center ? (int64_t)W : 0;
+  const bool apart = H > L;  // frames that do not touch: staged back to back
+  const uint32_t fstep = apart ? L : H, staged = nf ? (nf - 1u) * fstep + L : 0u;
+  const int64_t base = (int64_t)(f0 * H) - pad;  // sample index of the first staged float
+  float* s_y = (float*)s_pitch;
+  double* s_d = s_pitch + (((size_t)(A.FT - 1u) * fstep + L + 1u) >> 1);
+  for (uint32_t u = tid; u < staged; u += PITCH_THREADS) {
+    const int64_t t = apart ? base + (int64_t)(u / L) * H + (u % L) : base + u;
+    s_y[u] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t) : 0.f;
+  }
+  // the workgroup's share of the segment, [its first frame's start, the next tile's), the first tile from 0 and the last up to T
+  {
+    const int64_t lo = blockIdx.x == 0u ? 0 : (base > 0 ? base : 0);
+    int64_t hi = last ? (int64_t)T : (int64_t)((f0 + A.FT) * H) - pad;
+    if (hi > (int64_t)T) hi = (int64_t)T;
+    bool bad = false;
+    for (int64_t t = lo + tid; t < hi; t += PITCH_THREADS) bad |= trim_not_finite(pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t));
+    const int any = __syncthreads_or(bad ? 1 : 0);  // (also the barrier behind the staging)
+    if (tid == 0) *flag = any ? 1u : 0u;
+  }
+  if (nf == 0u) return;
+
+  // d[f][tau - 1], tau = 1 .. PL: one fma chain per (f, tau), j ascending
+  const uint32_t items = nf * PL;
+  for (uint32_t q0 = 0; q0 < items; q0 += PITCH_ILP * PITCH_THREADS) {
+    const float* zf[PITCH_ILP];
+    uint32_t tau[PITCH_ILP];
+    double acc[PITCH_ILP];
+#pragma unroll
+    for (uint32_t r = 0; r < PITCH_ILP; ++r) {
+      const uint32_t q = q0 + r * PITCH_THREADS + tid;
+      const uint32_t qq = q < items ? q : 0u;  // (an idle chain repeats pair 0 and is not stored)
+      const uint32_t f = qq / PL;
+      tau[r] = qq - f * PL + 1u;
+      zf[r] = s_y + (size_t)f * fstep;
+      acc[r] = 0.0;
+    }
+    for (uint32_t j = 1; j <= W; ++j) {
+#pragma unroll
+      for (uint32_t r = 0; r < PITCH_ILP; ++r) {
+        const double df = (double)zf[r][j] - (double)zf[r][j + tau[r]];  // (j + tau <= W + p_max <= L - 1)
+        acc[r] = fma(df, df, acc[r]);
+      }
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < PITCH_ILP; ++r) {
+      const uint32_t q = q0 + r * PITCH_THREADS + tid;
+      if (q < items) s_d[q] = acc[r];
+    }
+  }
+  __syncthreads();
+
+  const uint32_t p_min = sg.p_min, n = PL - p_min + 1u;
+  const uint32_t K = (PL + PITCH_THREADS - 1u) / PITCH_THREADS;
+  const uint32_t b0 = tid * K < PL ? tid * K : PL, b1 = b0 + K < PL ? b0 + K : PL;  // this thread's lags, as indices tau - 1
+  const uint32_t wave = tid >> 6, lane = tid & 63u;
+  const uint64_t r0 = A.segoff[g] + f0;
+  for (uint32_t f = 0; f < nf; ++f) {
+    double* d = s_d + (size_t)f * PL;
+    // S, and c in place of d from p_min on
+    double tot = 0.0;
+    for (uint32_t k = b0; k < b1; ++k) tot += d[k];
+    double inc = tot;
+    for (int o = 1; o < 64; o <<= 1) {
+      const double up = __shfl_up(inc, o);
+      if ((int)lane >= o) inc += up;
+    }
+    if (lane == 63u) s_w[wave] = inc;
+    double exc = __shfl_up(inc, 1);
+    if (lane == 0u) exc = 0.0;
+    __syncthreads();
+    double woff = 0.0;
+    for (uint32_t w = 0; w < wave; ++w) woff += s_w[w];
+    double run = woff + exc;
+    for (uint32_t k = b0; k < b1; ++k) {
+      const double dk = d[k];
+      run += dk;
+      if (k + 1u >= p_min) d[k] = dk / (run / (double)(k + 1u) + PITCH_TINY);
+    }
+    __syncthreads();
+    // i*: the first trough below the threshold, else the first minimum (c >= 0: its bit pattern orders as its value)
+    const double* c = d + (p_min - 1u);
+    uint64_t first = PITCH_NONE, low = PITCH_NONE;
+    for (uint32_t i = tid; i < n; i += PITCH_THREADS) {
+      const double ci = c[i];
+      const bool tr = i == 0u ? ci < c[1] : i == n - 1u ? ci < c[i - 1u] : (ci < c[i - 1u] && ci <= c[i + 1u]);
+      if (tr && ci < A.thr) first = trim_min64(first, i);
+      low = trim_min64(low, (uint64_t)__double_as_longlong(ci));
+    }
+    first = pitch_wg_min(first, s_r);
+    if (first == PITCH_NONE) {  // (workgroup-uniform)
+      low = pitch_wg_min(low, s_r);
+      for (uint32_t i = tid; i < n; i += PITCH_THREADS)
+        if ((uint64_t)__double_as_longlong(c[i]) == low) first = trim_min64(first, i);
+      first = pitch_wg_min(first, s_r);
+      if (first == PITCH_NONE) first = 0ull;  // (a NaN among the c of a segment that is refused anyway)
+    }
+    if (tid == 0) {
+      const uint32_t is = (uint32_t)first;
+      double shift = 0.0;
+      if (is > 0u && is < n - 1u) {
+        const double a = (c[is + 1u] + c[is - 1u]) - 2.0 * c[is];
+        const double b = (c[is + 1u] - c[is - 1u]) * 0.5;
+        if (fabs(b) < fabs(a)) shift = -b / a;
+      }
+      float* row = A.rows + 2u * (r0 + f);
+      row[0] = (float)(sg.sr / ((double)(p_min + is) + shift));
+      row[1] = (float)c[is];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_finish_kernel(const PitchCtx A) {
+  const uint32_t g = blockIdx.x, tid = threadIdx.x;
+  bool bad = false;
+  for (uint32_t i = tid; i < A.tiles; i += PITCH_THREADS) bad |= A.flags[(size_t)g * A.tiles + i] != 0u;
+  const int refused = __syncthreads_or(bad ? 1 : 0);
+  if (tid == 0 && A.refused) A.refused[g] = refused ? 1u : 0u;
+  if (!refused) return;
+  float* rows = A.rows + 2u * A.segoff[g];
+  const uint64_t nv = 2ull * A.segF[g];
+  for (uint64_t i = tid; i < nv; i += PITCH_THREADS) rows[i] = __uint_as_float(0x7FC00000u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct PitchWs {  // the stage's buffers: its own; the PCM is only read
+  TableUpload tab;
+  bool lds_set = false;  // the kernel's dynamic-LDS limit is raised on this handle's device
+  DevBuf<uint32_t> segF, flags, refused;
+  DevBuf<uint64_t> segoff;
+  DevBuf<float> rows;    // host form: the rows
+};
+
+// p_min and p_max of step 3 for rate sr, in double; false: fewer than two lags
+static inline bool pitch_periods(const vsyn_pitch_spec* sp, uint32_t sr, uint32_t* p_min, uint32_t* p_max) {
+  const uint32_t L = sp->frame_length, W = L / 2u;
+  const double lo = std::max(floor((double)sr / sp->fmax), 1.0);
+  const double hi = std::min(ceil((double)sr / sp->fmin), (double)(L - W - 1u));
+  if (!(hi - lo + 1.0 >= 2.0)) return false;
+  *p_min = (uint32_t)lo;
+  *p_max = (uint32_t)hi;
+  return true;
+}
+
+// The checks of the spec and of every segment's rate (0 = skipped segment).
+static inline int pitch_check(const vsyn_pitch_spec* sp, uint32_t S, const uint32_t* rates, const char** err) {
+  if (!sp) return fail(err, VSYN_ERR_INVALID, "pitch spec is NULL");
+  if (sp->options & ~VSYN_PITCH_CENTER) return fail(err, VSYN_ERR_INVALID, "unknown pitch options 0x%x", sp->options);
+  if (sp->frame_length < 4 || sp->frame_length > TRIM_MAX_FRAME)
+    return fail(err, VSYN_ERR_INVALID, "pitch frame_length %u outside [4, %u]", sp->frame_length, TRIM_MAX_FRAME);
+  if (sp->hop_length < 1) return fail(err, VSYN_ERR_INVALID, "pitch hop_length must be >= 1");
+  if (!std::isfinite(sp->fmin) || !std::isfinite(sp->fmax) || !(sp->fmin > 0.0 && sp->fmin < sp->fmax))
+    return fail(err, VSYN_ERR_INVALID, "pitch fmin %g / fmax %g: need 0 < fmin < fmax", sp->fmin, sp->fmax);
+  if (!std::isfinite(sp->trough_threshold) || !(sp->trough_threshold > 0.0 && sp->trough_threshold <= 1.0))
+    return fail(err, VSYN_ERR_INVALID, "pitch trough_threshold %g outside (0, 1]", sp->trough_threshold);
+  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
+  for (uint32_t g = 0; g < S; ++g) {
+    if (!rates[g]) continue;
+    uint32_t p_min, p_max;
+    if (sp->fmax > rates[g] / 2.0) return fail(err, VSYN_ERR_INVALID, "segment %u: fmax %g above sr/2 = %g", g, sp->fmax, rates[g] / 2.0);
+    if (!pitch_periods(sp, rates[g], &p_min, &p_max))
+      return fail(err, VSYN_ERR_INVALID, "segment %u: fewer than two lags between sr/fmax and min(sr/fmin, frame_length - frame_length/2 - 1)", g);
+  }
+  return VSYN_OK;
+}
+
+static inline size_t pitch_lds_bytes(uint32_t ft, uint32_t L, uint32_t H, uint32_t pl) {
+  return 8u * ((((size_t)(ft - 1u) * std::min(L, H) + L + 1u) >> 1) + (size_t)ft * pl);
+}
+
+// frames per workgroup: the most whose span and difference functions fit the LDS budget (as spec_tile chooses FT); one always fits
+static inline uint32_t pitch_tile(uint32_t L, uint32_t H, uint32_t pl) {
+  uint32_t ft = PITCH_FT_MAX;
+  while (ft > 1u && pitch_lds_bytes(ft, L, H, pl) > PITCH_LDS_BUDGET) --ft;
+  return ft;
+}
+
+// Offsets, pitch and finishing kernels on stream s; frames from d_frames, else from si. f_max bounds every segment's frames.
+// d_refused [S] may be NULL. Caller holds the handle's lock and has run pitch_check.
+static inline int pitch_launch(PitchWs& ws, int device, const vsyn_pitch_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
+                               uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
+                               uint64_t* d_segoff, uint32_t* d_refused, hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_rows & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM and row pointers must be 4-byte aligned");
+  if (plane > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
+  const uint32_t L = sp->frame_length, H = sp->hop_length;
+  std::vector<uint8_t> tab(sizeof(PitchSeg) * (size_t)S);
+  PitchSeg* seg = (PitchSeg*)tab.data();
+  uint32_t pl = 2u;
+  for (uint32_t g = 0; g < S; ++g) {
+    seg[g] = PitchSeg{(double)rates[g], 0u, 0u};
+    if (rates[g]) pitch_periods(sp, rates[g], &seg[g].p_min, &seg[g].p_max);
+    pl = std::max(pl, seg[g].p_max);
+  }
+  const uint32_t ft = pitch_tile(L, H, pl);
+  const uint64_t tiles = std::max<uint64_t>((f_max + ft - 1u) / ft, 1);
+  if (tiles > 0x7FFFFFFFull || f_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  HIPCHK(hipSetDevice(device));
+  if (!ws.lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_pitch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PITCH_LDS_BUDGET));
+    ws.lds_set = true;
+  }
+  HIPCHK(ws.segF.ensure(S));
+  HIPCHK(ws.segoff.ensure((size_t)S + 1));
+  HIPCHK(ws.flags.ensure((size_t)S * tiles));
+  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+  PitchCtx A;
+  A.seg = (const PitchSeg*)ws.tab.dev.p;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.L = L;
+  A.H = H;
+  A.FT = ft;
+  A.center = (sp->options & VSYN_PITCH_CENTER) ? 1u : 0u;
+  A.tiles = (uint32_t)tiles;
+  A.thr = sp->trough_threshold;
+  A.segF = ws.segF.p;
+  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
+  A.flags = ws.flags.p;
+  A.refused = d_refused;
+  A.rows = d_rows;
+  hipLaunchKernelGGL(vsyn_pitch_offsets_kernel, dim3(1), dim3(PITCH_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(vsyn_pitch_kernel, dim3((uint32_t)tiles, S), dim3(PITCH_THREADS), pitch_lds_bytes(ft, L, H, pl), s, A);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(vsyn_pitch_finish_kernel, dim3(S), dim3(PITCH_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}

@@ -78,6 +78,7 @@ struct NullCallbacks : ParseCallbacks {};
 
 bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
 bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
+bool pitch_run(const CorpusOptions& o) { return o.pitch.frame_length != 0; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
 uint32_t spectral_dim(const CorpusOptions& o) {
@@ -632,10 +633,43 @@ struct Feeder {
     return OkOrError();
   }
 
-  // A synthesis run's file: its PCM (or, for a spectral run, its rows) to the callbacks.
+  // Pitch run: each file's (f0, normalised difference) rows from the PCM still on the device (vsyn_pcm_pitch_host, resampled first in
+  // a resampled run); a file whose rate the spec does not fit gets no rows and an error of its own, and so does a file the stage
+  // refuses (a sample that is not finite).
+  OkOrError pitch_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    std::vector<uint32_t> rates(S);
+    uint64_t rows = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      const uint32_t in = g.pending[s]->header.audio_sample_rate;
+      const uint32_t sr = opts.resample_rate ? opts.resample_rate : in;  // the rate the rows are computed at
+      const uint32_t L = opts.pitch.frame_length;
+      const double lo = std::max(std::floor(sr / opts.pitch.fmax), 1.0), hi = std::min(std::ceil(sr / opts.pitch.fmin), (double)(L - L / 2u - 1u));
+      if (o.err[s].empty() && !(opts.pitch.fmax <= sr / 2.0 && hi - lo + 1.0 >= 2.0)) {  // "pitch", steps 3 and 10
+        char buf[200];
+        snprintf(buf, sizeof(buf), "pitch: fmin %g / fmax %g do not fit sample rate %u and frame_length %u (fmax <= sr/2, two lags or more)",
+                 opts.pitch.fmin, opts.pitch.fmax, sr, L);
+        o.err[s] = buf;
+      }
+      rates[s] = o.err[s].empty() ? in : 0;
+      if (rates[s]) rows += vsyn_pitch_num_frames(&opts.pitch, std::min<uint64_t>(o.frames[s], o.plane));
+    }
+    CHECK_ERR(g.rows.ensure(rows * 2u + 1));
+    CHECK_ERR(g.seg_rows.ensure(S));
+    std::vector<uint32_t> refused(S, 0u);
+    vsyn_status st;
+    const char* err = nullptr;
+    const int rc = vsyn_pcm_pitch_host(g.handle, &opts.pitch, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused.data(), &st, &err);
+    if (rc != VSYN_OK) return OkOrError(std::string("GPU pitch layer: ") + (err ? err : "pitch failed"));
+    for (uint32_t s = 0; s < S; ++s)
+      if (o.err[s].empty() && refused[s]) o.err[s] = "pitch: the PCM holds a sample that is not finite";
+    return OkOrError();
+  }
+
+  // A synthesis run's file: its PCM (or, for a spectral or pitch run, its rows) to the callbacks.
   OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
     const uint32_t C = opts.condition ? 1u : g.channels;  // channels delivered
-    const bool spectral = spectral_run(opts);
+    const bool spectral = spectral_run(opts) || pitch_run(opts);
     const uint64_t frames = o.frames[s], pl = o.plane;
     if (opts.condition) out.channels = 1;
     std::vector<DataRange<const float>> chans(C);
@@ -661,7 +695,7 @@ struct Feeder {
     out.status = o.err[s].empty() ? r.status : OkOrError(o.err[s]);
     if (opts.resample_rate) out.sample_rate = opts.resample_rate;
     stats.frames += frames;
-    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], spectral_dim(opts));
+    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : spectral_dim(opts));
     if (!callbacks || !o.err[s].empty() || opts.intervals_only) return OkOrError();
     std::lock_guard<std::mutex> lk(callbacks_mu);
     if (opts.pcm_s16) {
@@ -676,7 +710,8 @@ struct Feeder {
     if (g.pending.empty()) return OkOrError();
     if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
-    const bool spectral = spectral_run(opts);  // the PCM stays on the device: only the spectral rows come back
+    const bool pitch = pitch_run(opts);
+    const bool spectral = spectral_run(opts) || pitch;  // the PCM stays on the device: only the spectral (or pitch) rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
     const bool cond = opts.condition;               // ... and until it is conditioned
     double t0 = now_s();
@@ -706,7 +741,8 @@ struct Feeder {
       if (resample) CHECK_ERR(resample_stage(g, spectral || cond, o));
       else if (!cond) CHECK_ERR(fetch(g, o));
       if (cond && !spectral) CHECK_ERR(condition_stage(g, o));
-      if (spectral) CHECK_ERR(spectral_stage(g, o));
+      if (pitch) CHECK_ERR(pitch_stage(g, o));
+      else if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
     double t2 = now_s();
     stats.gpu_call_s += t2 - t1;
@@ -1300,5 +1336,22 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
 }
 
 }  // namespace
+
+extern "C" int ogg_vorbis_pitch_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                       uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pitch_spec* spec, float** rows_out,
+                                       uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                                       const char** error_out_per_file, double* stats_out, const char** error_out) {
+  if (!spec || !vsyn_pitch_num_frames(spec, 0x7FFFFFFFu))
+    return refuse_call((void**)rows_out, num_files, "ogg_vorbis_pitch_corpus: invalid pitch spec", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  opts.pitch = *spec;
+  opts.resample_rate = target_rate;
+  return malloc_corpus("pitch", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                       });
+}
 
 extern "C" void ogg_vorbis_features_free(float* rows) { free(rows); }

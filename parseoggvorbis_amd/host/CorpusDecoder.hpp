@@ -107,6 +107,11 @@ struct CorpusOptions {
   // (a PCM run with split): the intervals alone; the joined signal is not made, no PCM is delivered, and frames are the unsplit
   // ones. A file with a sample that is not finite fails alone. The default is off: today's output.
   bool split = false, intervals_only = false;
+  // pitch run (pitch.frame_length != 0): synthesis as usual but VSYN_SUBMIT_KEEP_PCM, then each file's (f0, normalised difference)
+  // rows from the PCM on the device (include/vorbis_synth_hip.h, "pitch": vsyn_pcm_pitch_host, resampled first with resample_rate),
+  // delivered through gotFileFeatures with dim 2; no PCM crosses the bus. A file whose rate the spec does not fit, and a file with
+  // a sample that is not finite, fails alone. Excludes features, spectral, pcm_s16 and the conditioning, trim and split stages.
+  vsyn_pitch_spec pitch = {0, 0, 0, 0, 0.0, 0.0, 0.0};
 };
 
 struct CorpusStats {
@@ -225,6 +230,13 @@ int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens,
                                 uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pcm_trim* split, uint32_t** intervals_out,
                                 uint64_t* intervals_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
                                 const char** error_out_per_file, double* stats_out, const char** error_out);
+// pitch run (CorpusOptions::pitch = *spec; target_rate as for ogg_vorbis_spectral_corpus_sr): rows_out receives per file NULL
+// (failed, or no rows) or a buffer of rows_count_out[i] * 2 floats, (f0 in Hz, normalised difference) per frame, released with
+// ogg_vorbis_features_free. frames_out / rate_out: each file's (resampled) length and the rate its rows are computed at.
+int ogg_vorbis_pitch_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                            uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pitch_spec* spec, float** rows_out,
+                            uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                            const char** error_out_per_file, double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
 }
 
