@@ -915,6 +915,86 @@ int vsyn_pcm_pitch_host(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t nu
                         float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
                         const char** err);
 
+/* ---- frame descriptors: energy, zero-crossing rate and spectral shape of the decoded PCM per frame, computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, and its sample rate sr. Parameters: n_fft, hop_length,
+ * win_length, roll_percent, zcr_threshold, amin, VSYN_FDESC_CENTER. Output: a float32 matrix (F, 6), one row per frame, the columns
+ * in this order: rms, zcr, centroid, bandwidth, rolloff, flatness, as librosa.feature.rms (pad_mode="constant"),
+ * zero_crossing_rate (edge padding, threshold=zcr_threshold), spectral_centroid, spectral_bandwidth (p=2), spectral_rolloff and
+ * spectral_flatness (power=2) define them on the mono signal. librosa is not among the test dependencies and parity with it is not
+ * claimed: the device is compared against a float64 model of the arithmetic below (tests/fdesc_model.py), and the model against a
+ * restatement with numpy.fft.rfft (tests/test_fdesc_cpu.py).
+ *
+ *  1. Mono and framing. y[t] is step 1 of the conditioning stage, the one device function every stage uses. The frame count F is
+ *     that of "spectral features" step 2 with the same n_fft, hop and centring (vsyn_fdesc_num_frames), so that row f lines up with
+ *     row f of the spectral rows and with frame f of the pitch stage at frame_length = n_fft. P = n_fft / 2 (integer division) with
+ *     VSYN_FDESC_CENTER, else 0; frame f covers the samples t = f hop - P + j, j < n_fft.
+ *  2. rms. y_j = y[t] inside [0, T) and 0 outside. E = sum_j y_j^2: every sample is widened to float64, the squares are added by
+ *     fma in the order below (the samples dealt as the bins are, K = ceil(n_fft / 256)), and rms = sqrt(E / n_fft), rounded once to
+ *     float32.
+ *  3. zcr. Here a sample outside [0, T) is the nearest valid one (t clamped to [0, T - 1]). s_j = (y_j < 0 and |y_j| >
+ *     zcr_threshold), compared in float64. zcr = #{1 <= j < n_fft: s_j != s_(j-1)} / n_fft, rounded once: the count is an integer
+ *     and the column is exact.
+ *  4. STFT. The window w is the spectral stage's: float32(0.5 - 0.5 cos(2 pi i / win_length)), i < win_length, placed at
+ *     (n_fft - win_length) / 2 and 0 elsewhere; padding is zero as in step 2. v_j = (double)w_j * (double)y_j (exact). The twiddle
+ *     table is float64, built on the host: (cos(a_m), sin(a_m)), a_m = 2.0 * pi * m / n_fft evaluated left to right in double,
+ *     m < n_fft. For k = 0 .. n_fft / 2: re_k = sum_j v_j cos(a_(j k mod n_fft)), im_k likewise with sin, each ONE float64 fma chain
+ *     with j ascending from 0.0; S_k = sqrt(fma(re_k, re_k, im_k im_k)). NB = n_fft / 2 + 1 bins.
+ *  5. Ordered sums over k. With K = ceil(NB / 256), thread t of 256 owns the bins t K .. min((t + 1) K, NB) - 1 and adds its terms
+ *     in ascending order from 0.0; the 256 totals are scanned in four groups of 64 (Hillis-Steele over the offsets 1, 2, .. 32),
+ *     a group's offset is the sum of the earlier groups' totals in ascending order, and the sum over all bins is ((g0 + g1) + g2) +
+ *     g3. c_k = (group offset + the exclusive prefix of the thread) + S_first + .. + S_k, left to right. A = c_(NB-1).
+ *     f_k = (k * sr) / n_fft in double. A function of n_fft alone; every sum below is taken in this order, in float64.
+ *  6. centroid = (sum_k fma(f_k, S_k, .)) / A. bandwidth = sqrt((sum_k fma(S_k d_k, d_k, .)) / A), d_k = f_k - centroid. If
+ *     A < 1.1754944e-38 both are 0.
+ *  7. rolloff. theta = roll_percent * A. k* is the first k with c_k >= theta (an integer minimum, no atomics); rolloff = f_(k*). A
+ *     silent frame gives k* = 0.
+ *  8. flatness. P_k = max(amin, S_k S_k). flatness = exp((sum_k ln P_k) / NB) / ((sum_k P_k) / NB).
+ *  9. Not finite. A segment with an Inf or NaN sample among its T frames (the trim stage's test, whether or not a frame covers the
+ *     sample) is refused alone: every value of its F rows is NaN and its entry of the refused array is 1. The other segments of
+ *     the call are not affected.
+ * 10. A rate of 0 skips the segment (0 rows); T = 0 gives 0 rows.
+ * 11. Checks (VSYN_ERR_INVALID before anything runs): 16 <= n_fft <= 8192; 1 <= hop_length; 1 <= win_length <= n_fft;
+ *     0 < roll_percent < 1; zcr_threshold finite and >= 0; amin finite and > 0; unknown option bits; channels >= 1; sample_rates
+ *     non-NULL when there are segments.
+ *
+ * Every column is rounded to float32 once, from float64. Not built: composition with the trim, split and conditioning stages,
+ * p != 2, selectable columns. The same PCM gives the same bits, alone, in any slot of a batch and at any alignment. The entry
+ * points read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM, and a later
+ * vsyn_pcm_fetch_host returns the same PCM. One handle's frame descriptor entry points share its frame descriptor workspace,
+ * which is no other stage's. */
+#define VSYN_FDESC_CENTER 1u /* pad n_fft/2 on both sides (librosa's center=True) */
+
+typedef struct vsyn_fdesc_spec {
+  uint32_t n_fft;
+  uint32_t hop_length;
+  uint32_t win_length;
+  uint32_t options;     /* VSYN_FDESC_* bits */
+  double roll_percent;  /* step 7 */
+  double zcr_threshold; /* step 3 */
+  double amin;          /* step 8 */
+} vsyn_fdesc_spec;
+
+/* F of step 1 for a segment of `frames` PCM frames, 0 for an invalid spec. */
+uint64_t vsyn_fdesc_num_frames(const vsyn_fdesc_spec* spec, uint64_t frames);
+
+/* The caller's planar PCM, as for vsyn_pitch_device: d_pcm[(g * channels + c) * plane_stride + t], d_frames[S] (device) PCM frames
+ * per segment (clamped to plane_stride), sample_rates[S] a HOST array (0 skips the segment). Writes d_seg_row_off[S+1] (uint64, may
+ * be NULL) and d_rows, which must hold sum_g vsyn_fdesc_num_frames(spec, frames_g) rows of 6 columns; d_refused[S] (device, uint32,
+ * may be NULL): 1 for a refused segment (step 9), else 0. Asynchronous on hip_stream. */
+int vsyn_fdesc_device(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
+                      const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows,
+                      uint64_t* d_seg_row_off, uint32_t* d_refused, void* hip_stream, const char** err);
+
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle, as for vsyn_pcm_pitch_host: each segment resampled from in_rates[g]
+ * to out_rate first when out_rate != 0 (f_k then uses out_rate). seg_rows[S] receives each segment's row count; rows (may be NULL
+ * when only the counts are wanted: nothing is launched) receives the rows of all segments back to back, 6 columns each, at most
+ * rows_capacity rows (VSYN_ERR_INVALID with the counts filled if it is too small); refused_out[S] (uint32, may be NULL) as
+ * d_refused. status as for vsyn_pcm_spectral_host. Synchronous. */
+int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                        float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
+                        const char** err);
+
 #ifdef __cplusplus
 }
 #endif

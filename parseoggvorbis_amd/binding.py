@@ -25,6 +25,7 @@ VSYN_SUBMIT_PRE_KERNELS = 8
 VSYN_PCM_S16, VSYN_PCM_F32 = 1, 2
 VSYN_COND_PEAK, VSYN_COND_PREEMPH = 1, 2
 VSYN_PITCH_CENTER = 1
+VSYN_FDESC_CENTER = 1
 
 
 class Floor1(C.Structure):
@@ -84,6 +85,11 @@ class PcmTrim(C.Structure):  # vsyn_pcm_trim
 class PitchSpec(C.Structure):  # vsyn_pitch_spec
     _fields_ = [("frame_length", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32), ("reserved", C.c_uint32),
                 ("fmin", C.c_double), ("fmax", C.c_double), ("trough_threshold", C.c_double)]
+
+
+class FdescSpec(C.Structure):  # vsyn_fdesc_spec
+    _fields_ = [("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("win_length", C.c_uint32), ("options", C.c_uint32),
+                ("roll_percent", C.c_double), ("zcr_threshold", C.c_double), ("amin", C.c_double)]
 
 
 class Status(C.Structure):
@@ -218,6 +224,7 @@ _SYMBOLS = [
     "vsyn_pcm_split_max_intervals", "vsyn_pcm_split_device", "vsyn_pcm_split_host", "vsyn_pcm_split_intervals_host",
     "vsyn_pcm_split_spectral_host",
     "vsyn_pitch_num_frames", "vsyn_pitch_device", "vsyn_pcm_pitch_host",
+    "vsyn_fdesc_num_frames", "vsyn_fdesc_device", "vsyn_pcm_fdesc_host",
 ]
 
 
@@ -312,6 +319,10 @@ def load():
     lib.vsyn_pitch_num_frames.restype = u64
     lib.vsyn_pitch_device.argtypes = [vp, C.POINTER(PitchSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_pitch_host.argtypes = [vp, C.POINTER(PitchSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_fdesc_num_frames.argtypes = [C.POINTER(FdescSpec), u64]
+    lib.vsyn_fdesc_num_frames.restype = u64
+    lib.vsyn_fdesc_device.argtypes = [vp, C.POINTER(FdescSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_fdesc_host.argtypes = [vp, C.POINTER(FdescSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -716,6 +727,34 @@ class Synth:
         total = int(seg_rows[:S].sum())
         rows = np.zeros((max(total, 1), 2), np.float32)
         rc = self.lib.vsyn_pcm_pitch_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows), _ptr(refused),
+                                          C.byref(st), C.byref(err))
+        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
+            raise VsynError(rc, (err.value or b"").decode())
+        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], refused=refused[:S], flags=st.flags)
+
+    def fdesc_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, d_refused=None, stream=None):
+        """vsyn_fdesc_device on device pointers (ints); sample_rates is a host sequence (None: NULL)."""
+        rates = None if sample_rates is None else np.ascontiguousarray(sample_rates, dtype=np.uint32)
+        err = C.c_char_p()
+        rc = self.lib.vsyn_fdesc_device(self.h, None if spec is None else C.byref(spec), 0 if rates is None else len(rates),
+                                        None if rates is None else _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off,
+                                        d_refused, stream, C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+
+    def pcm_fdesc_host(self, spec, in_rates, out_rate=0):
+        """vsyn_pcm_fdesc_host over the last submit's segments: returns dict(rc, rows [total][6], seg_rows [S], refused [S], flags)."""
+        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S = len(rates)
+        seg_rows = np.zeros(max(S, 1), np.uint64)
+        refused = np.zeros(max(S, 1), np.uint32)
+        st, err = Status(), C.c_char_p()
+        rc = self.lib.vsyn_pcm_fdesc_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None, C.byref(st), C.byref(err))
+        if rc != VSYN_OK:
+            raise VsynError(rc, (err.value or b"").decode())
+        total = int(seg_rows[:S].sum())
+        rows = np.zeros((max(total, 1), 6), np.float32)
+        rc = self.lib.vsyn_pcm_fdesc_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows), _ptr(refused),
                                           C.byref(st), C.byref(err))
         if rc not in (VSYN_OK, VSYN_ERR_STREAM):
             raise VsynError(rc, (err.value or b"").decode())

@@ -27,6 +27,7 @@
 #include "vsyn_trim.h"
 #include "vsyn_split.h"
 #include "vsyn_pitch.h"
+#include "vsyn_fdesc.h"
 
 static const uint32_t k_inverse_db_bits[256] = {
 #include "vorbis_floor1_inverse_db.inc"
@@ -126,6 +127,7 @@ struct vsyn_handle {
   TrimWs tr;                           // vsyn_trim.h
   SplitWs sl;                          // vsyn_split.h
   PitchWs pt;                          // vsyn_pitch.h
+  FdescWs fd;                          // vsyn_fdesc.h
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -1932,6 +1934,76 @@ int vsyn_pcm_pitch_host(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t S,
   if (rc) return rc;
   if (total) HIPCHK(hipMemcpyAsync(rows, h->pt.rows.p, sizeof(float) * total * 2u, hipMemcpyDeviceToHost, hs));
   if (refused_out) HIPCHK(hipMemcpyAsync(refused_out, h->pt.refused.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
+  return sync_status_into(h, status, err);
+}
+
+// ---- frame descriptors (vsyn_fdesc.h) ----
+
+static bool fdesc_center(const vsyn_fdesc_spec* spec) { return (spec->options & VSYN_FDESC_CENTER) != 0; }
+
+uint64_t vsyn_fdesc_num_frames(const vsyn_fdesc_spec* spec, uint64_t frames) {
+  if (fdesc_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
+  return spec_num_frames(spec->n_fft, spec->hop_length, fdesc_center(spec), frames);
+}
+
+int vsyn_fdesc_device(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t S, const uint32_t* sample_rates, const float* d_pcm,
+                      uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off,
+                      uint32_t* d_refused, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = fdesc_check(spec, S, sample_rates, err);
+  if (rc) return rc;
+  if (channels == 0 || channels > 255) return fail(err, VSYN_ERR_INVALID, "channels %u outside [1, 255]", channels);
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_rows || plane_stride == 0) return fail(err, VSYN_ERR_INVALID, "NULL pointer or zero stride");
+  const uint64_t f_max = spec_num_frames(spec->n_fft, spec->hop_length, fdesc_center(spec), plane_stride);
+  std::lock_guard<std::mutex> lk(h->mu);
+  return fdesc_launch(h->fd, h->device, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, d_rows, d_seg_row_off,
+                      d_refused, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                        uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = fdesc_check(spec, S, in_rates, err);  // (first: an invalid spec writes nothing, the status included)
+  if (rc) return rc;
+  status_reset(status);
+  std::vector<uint32_t> fd_rates;  // resampled: the descriptor pass sees every resampled segment at out_rate
+  if (out_rate) {
+    rc = rs_check(S, in_rates, out_rate, err);
+    if (rc) return rc;
+    fd_rates.resize(S);
+    for (uint32_t g = 0; g < S; ++g) fd_rates[g] = in_rates[g] ? out_rate : 0u;
+  }
+  const uint32_t* rates = out_rate ? fd_rates.data() : in_rates;
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  if (refused_out) memset(refused_out, 0, sizeof(uint32_t) * S);
+  // the lock covers the whole call: the resample and descriptor workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T(S);
+  uint64_t total = 0, f_max = 0, t_max;
+  rc = last_submit_frames(h, S, in_rates, out_rate, T.data(), &t_max, err);
+  if (rc) return rc;
+  t_max = std::max<uint64_t>(t_max, 1);
+  for (uint32_t g = 0; g < S; ++g) {
+    const uint64_t f = rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, fdesc_center(spec), T[g]) : 0;
+    seg_rows[g] = f;
+    total += f;
+    f_max = std::max(f_max, f);
+  }
+  if (!rows || S == 0) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
+  hipStream_t hs = h->host_stream;
+  PcmView v;  // the synthesis PCM with the last submit's SegInfo, or the resampler's planes with its frames
+  rc = pcm_chain(h, S, in_rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err);
+  if (rc) return rc;
+  HIPCHK(h->fd.rows.ensure(total * FDESC_COLS + 1));
+  HIPCHK(h->fd.refused.ensure(S));
+  rc = fdesc_launch(h->fd, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->fd.rows.p, nullptr, h->fd.refused.p, hs, err);
+  if (rc) return rc;
+  if (total) HIPCHK(hipMemcpyAsync(rows, h->fd.rows.p, sizeof(float) * total * FDESC_COLS, hipMemcpyDeviceToHost, hs));
+  if (refused_out) HIPCHK(hipMemcpyAsync(refused_out, h->fd.refused.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
   return sync_status_into(h, status, err);
 }
 

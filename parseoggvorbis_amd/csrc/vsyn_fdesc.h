@@ -1,0 +1,429 @@
+// vsyn_fdesc.h — frame descriptors: per frame rms, zero-crossing rate, spectral centroid, bandwidth, roll-off and flatness, from
+// planar float32 PCM already on the device. Semantics: include/vorbis_synth_hip.h, "frame descriptors".
+//
+// Three kernels on one stream (the table — per-segment rates, float64 twiddles, float32 window — is built on the host per call):
+//   1. vsyn_fdesc_offsets_kernel  one workgroup: per segment its frame count (spec_num_frames) and the exclusive row scan seg_off[S+1]
+//                                 (the pitch stage's offsets kernel).
+//   2. vsyn_fdesc_kernel<TWL>     grid (tile of FT frames, segment), 256 threads. Dynamic LDS, declared 16-byte aligned, in this order:
+//                                   twiddles (cos, sin)[n_fft] float64, TWL only
+//                                   S[FT][NB] float64, NB = n_fft / 2 + 1: the magnitudes of the tile's frames
+//                                   26 words of 8 bytes for the reductions
+//                                   window[n_fft] float32
+//                                   the tile's span of the mono signal as float32 (the downmix is done while loading, zeros outside
+//                                   [0, T); hop > n_fft: the frames back to back, as the pitch and trim stages stage them).
+//                                 DFT: the tile's frames are taken in groups of FDESC_ILP, and the (group, bin) items are dealt to
+//                                 the threads in order, bin fastest. A thread owns its bin k for the frames of its group and walks
+//                                 j = 0 .. n_fft - 1: window[j] and each frame's y[j] are one address per wave (broadcast reads),
+//                                 widened to float64 and multiplied (exact); one twiddle read serves the group's frames; re and im
+//                                 of every (frame, bin) are ONE fma chain each with j ascending, whatever the tile, the group and the
+//                                 thread; the twiddle index (j k) mod n_fft is walked by adding k and subtracting n_fft once when it
+//                                 is reached.
+//                                 TWL = true reads the twiddles from LDS, TWL = false from the table in global memory (every workgroup
+//                                 re-reads the same 16 n_fft bytes: L2). Both read the same table: the bits do not depend on the path.
+//                                 Then per frame, by the whole workgroup: the ordered sums below, the roll-off bin by an integer
+//                                 minimum through the wave (__shfl_xor) and the four waves (LDS), the zero-crossing count by an integer
+//                                 sum, and thread 0 writes the row. No atomics.
+//                                 The workgroup also looks at every sample of its share of the segment for an Inf or a NaN
+//                                 (trim_not_finite) and stores one flag word per tile.
+//   3. vsyn_fdesc_finish_kernel   one workgroup per segment: a segment with a flagged tile is refused: its rows become NaN and its
+//                                 word of the refused array 1.
+// Order of the sums over the bins: with K = ceil(NB / 256), thread t owns the bins t K .. min((t + 1) K, NB) - 1 and adds its terms in
+// ascending order from 0.0 (its total). The totals are scanned inside each wave by Hillis-Steele over the lane offsets 1, 2, .. 32; a
+// wave's offset is the sum of the earlier waves' totals in ascending order; a sum over all bins is ((w0 + w1) + w2) + w3 of the four
+// waves' totals; and c_k = (wave offset + the exclusive lane prefix) + S[first] + .. + S[k], added left to right. A = c_(NB-1). The
+// frame's energy (rms) is summed the same way over the samples, K = ceil(n_fft / 256). A function of n_fft alone.
+// LDS budget: FDESC_LDS_BUDGET = 79 KiB (80,896 B) of dynamic LDS, so that two workgroups share a CU's 160 KiB beside the
+// static LDS of __syncthreads_or; with the twiddles in LDS one frame takes 28 n_fft + 216 bytes, which fits up to n_fft = 2881. Above that the twiddles
+// stay in global memory and the workgroup may take FDESC_LDS_WIDE = 156 KiB (159,744 B), one workgroup per CU: one frame at
+// n_fft = 8192 takes 8 * (4097 + 26) + 4 * 8192 + 4 * 8192 = 98,520 B. FT is the most frames (at most 64) whose image fits the budget.
+// Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
+#pragma once
+#include "vsyn_device.h"
+#include "vsyn_host.h"
+#include "vsyn_pitch.h"
+#include "vsyn_spectral.h"
+#include "vsyn_trim.h"
+
+#define FDESC_THREADS 256
+#define FDESC_WAVES (FDESC_THREADS / 64)
+#define FDESC_ILP 4u                         // frames per thread and twiddle read: 8 independent fma chains
+#define FDESC_FT_MAX 64u                     // frames per workgroup, at most
+#define FDESC_LDS_BUDGET (79u * 1024u)       // dynamic LDS of a workgroup, twiddles in LDS: two workgroups fit a CU
+#define FDESC_LDS_WIDE (156u * 1024u)        // dynamic LDS of a workgroup, twiddles in global memory: one workgroup per CU
+#define FDESC_COLS 6u
+#define FDESC_TINY 1.1754944e-38             // step 6: below this sum of magnitudes the centroid and the bandwidth are 0
+#define FDESC_MIN_FFT 16u
+#define FDESC_SUMS 5u                        // sums of the first ordered pass: S, f S, P, ln P, y^2
+#define FDESC_WORDS 26u                      // 8-byte words of the reductions in the image: the sums' waves, A, the integer minima, one spare
+
+struct FdescCtx {  // launch arguments
+  const double* sr;        // [S] the segment's rate; 0 skips the segment
+  const double2* tw;       // [n_fft] (cos, sin)(2 pi m / n_fft)
+  const float* win;        // [n_fft]
+  const float* pcm;
+  uint64_t plane;
+  uint32_t C, S;
+  const uint32_t* frames;  // PCM frames per segment (caller's, or the resampler's), or
+  const SegInfo* si;       // the last submit's SegInfo (total_emit)
+  uint32_t N, H, FT;       // n_fft, hop_length, frames per workgroup
+  uint32_t center;
+  uint32_t tiles;          // workgroups per segment (grid.x): the flags' stride
+  double roll, zthr, amin;
+  uint32_t* segF;          // [S] frames
+  uint64_t* segoff;        // [S+1]
+  uint32_t* flags;         // [S][tiles] a sample of the tile's share is not finite
+  uint32_t* refused;       // [S]
+  float* rows;             // [segoff[S]][6]
+};
+
+__device__ __forceinline__ uint64_t fdesc_frames(const FdescCtx& A, uint32_t g) {
+  return trim_min64(A.frames ? A.frames[g] : A.si[g].total_emit, A.plane);
+}
+
+__global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_offsets_kernel(const FdescCtx A) {
+  wg_exclusive_scan<FDESC_THREADS, 1>(A.S, A.segoff, [&](uint32_t g, uint64_t* v) {
+    v[0] = A.sr[g] != 0.0 ? spec_num_frames(A.N, A.H, A.center != 0, fdesc_frames(A, g)) : 0ull;
+    A.segF[g] = (uint32_t)v[0];
+  });
+}
+
+// M sums over the workgroup in the order of the header: v = this thread's totals; exc = the sum of the totals of the threads in front
+// of it, tot = the sum of all of them, for every thread (s_w: M * FDESC_WAVES doubles of LDS, free again on return)
+template <uint32_t M>
+__device__ __forceinline__ void fdesc_scan(const double (&v)[M], double (&exc)[M], double (&tot)[M], double* s_w) {
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t m = 0; m < M; ++m) {
+    double inc = v[m];
+    for (int o = 1; o < 64; o <<= 1) {
+      const double up = __shfl_up(inc, o);
+      if ((int)lane >= o) inc += up;
+    }
+    if (lane == 63u) s_w[m * FDESC_WAVES + wave] = inc;
+    const double e = __shfl_up(inc, 1);
+    exc[m] = lane == 0u ? 0.0 : e;
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t m = 0; m < M; ++m) {
+    const double* w = s_w + m * FDESC_WAVES;
+    double woff = 0.0;
+    for (uint32_t i = 0; i < wave; ++i) woff += w[i];
+    exc[m] = woff + exc[m];
+    tot[m] = ((w[0] + w[1]) + w[2]) + w[3];
+  }
+  __syncthreads();
+}
+
+// the sum of v over the workgroup, for every thread (s_r: FDESC_WAVES words of LDS, free again on return)
+__device__ __forceinline__ uint32_t fdesc_wg_count(uint32_t v, uint64_t* s_r) {
+  for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+  if ((threadIdx.x & 63u) == 0) s_r[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = (uint32_t)(s_r[0] + s_r[1] + s_r[2] + s_r[3]);
+  __syncthreads();
+  return v;
+}
+
+// Bin k of NR frames a tile step apart (z0: the first one's samples): S into out[0], out[NB], .. One twiddle read serves the NR
+// frames; every (frame, bin) is still ONE fma chain per component with j ascending.
+template <bool TWL, uint32_t NR>
+__device__ __forceinline__ void fdesc_dft(const double2* s_tw, const double2* g_tw, const float* s_win, const float* z0, uint32_t fstep,
+                                          uint32_t N, uint32_t k, double* out, uint32_t NB) {
+  double re[NR], im[NR];
+#pragma unroll
+  for (uint32_t r = 0; r < NR; ++r) re[r] = im[r] = 0.0;
+  uint32_t idx = 0u;
+#pragma unroll 2
+  for (uint32_t j = 0; j < N; ++j) {
+    const double w = (double)s_win[j];
+    const double2 cs = TWL ? s_tw[idx] : g_tw[idx];
+    idx += k;  // (k <= n_fft / 2: one subtraction brings it back below n_fft)
+    if (idx >= N) idx -= N;
+#pragma unroll
+    for (uint32_t r = 0; r < NR; ++r) {
+      const double v = w * (double)z0[(size_t)r * fstep + j];  // (exact: two float32 factors)
+      re[r] = fma(v, cs.x, re[r]);
+      im[r] = fma(v, cs.y, im[r]);
+    }
+  }
+#pragma unroll
+  for (uint32_t r = 0; r < NR; ++r) out[(size_t)r * NB] = sqrt(fma(re[r], re[r], im[r] * im[r]));
+}
+
+template <bool TWL>
+__global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCtx A) {
+  extern __shared__ __attribute__((aligned(16))) double s_fdesc[];
+  const uint32_t g = blockIdx.y, tid = threadIdx.x;
+  const double sr = A.sr[g];
+  uint32_t* flag = A.flags + (size_t)g * A.tiles + blockIdx.x;
+  const uint64_t F = A.segF[g];
+  const uint64_t f0 = (uint64_t)blockIdx.x * A.FT;
+  if (sr == 0.0 || (f0 >= F && blockIdx.x != 0u)) {  // (workgroup-uniform) nothing here: the flag word is still this workgroup's to write
+    if (tid == 0) *flag = 0u;
+    return;
+  }
+  const uint64_t T = fdesc_frames(A, g);
+  const uint32_t N = A.N, H = A.H, NB = N / 2u + 1u;
+  const uint32_t nf = f0 < F ? (uint32_t)trim_min64(A.FT, F - f0) : 0u;  // (F = 0, T > 0: tile 0 still looks at the samples)
+  const bool last = f0 + A.FT >= F;
+  const uint32_t C = A.C;
+  const float inv_c = 1.0f / (float)C;
+  const float* x = A.pcm + (size_t)g * C * A.plane;
+  const int64_t pad = A.center ? (int64_t)(N / 2u) : 0;
+  const bool apart = H > N;  // frames that do not touch: staged back to back
+  const uint32_t fstep = apart ? N : H, staged = nf ? (nf - 1u) * fstep + N : 0u;
+  const int64_t base = (int64_t)(f0 * H) - pad;  // sample index of the first staged float
+  const double2* s_tw = (const double2*)s_fdesc;  // (first: the image is declared 16-byte aligned, for the 16-byte twiddle reads)
+  double* s_S = s_fdesc + (TWL ? 2u * (size_t)N : 0u);
+  double* s_w = s_S + (size_t)A.FT * NB;  // the reductions' words
+  double* s_a = s_w + FDESC_SUMS * FDESC_WAVES;
+  uint64_t* s_r = (uint64_t*)(s_a + 1);
+  float* s_win = (float*)(s_w + FDESC_WORDS);
+  float* s_y = s_win + N;
+  if (nf) {
+    if (TWL)
+      for (uint32_t u = tid; u < N; u += FDESC_THREADS) ((double2*)s_tw)[u] = A.tw[u];
+    for (uint32_t u = tid; u < N; u += FDESC_THREADS) s_win[u] = A.win[u];
+  }
+  for (uint32_t u = tid; u < staged; u += FDESC_THREADS) {
+    const int64_t t = apart ? base + (int64_t)(u / N) * H + (u % N) : base + u;
+    s_y[u] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t) : 0.f;
+  }
+  // the workgroup's share of the segment, [its first frame's start, the next tile's), the first tile from 0 and the last up to T
+  {
+    const int64_t lo = blockIdx.x == 0u ? 0 : (base > 0 ? base : 0);
+    int64_t hi = last ? (int64_t)T : (int64_t)((f0 + A.FT) * H) - pad;
+    if (hi > (int64_t)T) hi = (int64_t)T;
+    bool bad = false;
+    for (int64_t t = lo + tid; t < hi; t += FDESC_THREADS) bad |= trim_not_finite(pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t));
+    const int any = __syncthreads_or(bad ? 1 : 0);  // (also the barrier behind the staging)
+    if (tid == 0) *flag = any ? 1u : 0u;
+  }
+  if (nf == 0u) return;
+
+  // S[f][k]: one fma chain per component of (f, k), j ascending. An item is (group of up to FDESC_ILP frames, bin); a wave without one
+  // skips the pass (the CU's other workgroup has the SIMD meanwhile).
+  const uint32_t items = ((nf + FDESC_ILP - 1u) / FDESC_ILP) * NB;
+  for (uint32_t q0 = 0; q0 < items; q0 += FDESC_THREADS) {
+    if (q0 + (tid & ~63u) >= items) continue;  // (wave-uniform; no barrier inside the loop)
+    const uint32_t q = q0 + tid;
+    if (q >= items) continue;
+    const uint32_t grp = q / NB, k = q - grp * NB, fa = grp * FDESC_ILP;
+    const float* z0 = s_y + (size_t)fa * fstep;
+    double* out = s_S + (size_t)fa * NB + k;
+    switch (nf - fa) {
+      case 1u: fdesc_dft<TWL, 1u>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
+      case 2u: fdesc_dft<TWL, 2u>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
+      case 3u: fdesc_dft<TWL, 3u>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
+      default: fdesc_dft<TWL, FDESC_ILP>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
+    }
+  }
+  __syncthreads();
+
+  const uint32_t K = (NB + FDESC_THREADS - 1u) / FDESC_THREADS;
+  const uint32_t b0 = tid * K < NB ? tid * K : NB, b1 = b0 + K < NB ? b0 + K : NB;  // this thread's bins
+  const uint32_t KJ = (N + FDESC_THREADS - 1u) / FDESC_THREADS;
+  const uint32_t j0 = tid * KJ < N ? tid * KJ : N, j1 = j0 + KJ < N ? j0 + KJ : N;  // this thread's samples
+  const double y_first = (double)pcm_downmix(x, A.plane, C, inv_c, 0ull);           // (F > 0: T > 0) zcr's edge padding
+  const double y_last = (double)pcm_downmix(x, A.plane, C, inv_c, T - 1u);
+  const double dn = (double)N, dnb = (double)NB;
+  const uint64_t r0 = A.segoff[g] + f0;
+  for (uint32_t f = 0; f < nf; ++f) {
+    const double* S = s_S + (size_t)f * NB;
+    const float* z = s_y + (size_t)f * fstep;
+    const int64_t t0 = (int64_t)((f0 + f) * H) - pad;  // the frame's first sample
+    // the sums of the first pass, and the zero crossings of this thread's samples
+    double v[FDESC_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0}, exc[FDESC_SUMS], tot[FDESC_SUMS];
+    for (uint32_t kk = b0; kk < b1; ++kk) {
+      const double s = S[kk], fk = (double)kk * sr / dn, p = fmax(A.amin, s * s);
+      v[0] += s;
+      v[1] = fma(fk, s, v[1]);
+      v[2] += p;
+      v[3] += log(p);
+    }
+    uint32_t cross = 0u;
+    for (uint32_t j = j0; j < j1; ++j) {
+      const double y = (double)z[j];
+      v[4] = fma(y, y, v[4]);
+      if (j == 0u) continue;
+      const int64_t ta = t0 + (int64_t)j - 1, tb = ta + 1;
+      const double ya = ta < 0 ? y_first : (uint64_t)ta >= T ? y_last : (double)z[j - 1u];
+      const double yb = tb < 0 ? y_first : (uint64_t)tb >= T ? y_last : y;
+      const bool sa = ya < 0.0 && fabs(ya) > A.zthr, sb = yb < 0.0 && fabs(yb) > A.zthr;
+      cross += sa != sb ? 1u : 0u;
+    }
+    fdesc_scan<FDESC_SUMS>(v, exc, tot, s_w);
+    cross = fdesc_wg_count(cross, s_r);
+    // A = c_(NB-1), from the thread that owns the last bin
+    {
+      double run = exc[0];
+      for (uint32_t kk = b0; kk < b1; ++kk) run += S[kk];
+      if (b0 < b1 && b1 == NB) *s_a = run;
+    }
+    __syncthreads();
+    const double a = *s_a;
+    // k*: the first bin whose cumulative sum reaches theta
+    const double theta = A.roll * a;
+    uint64_t first = PITCH_NONE;
+    {
+      double run = exc[0];
+      for (uint32_t kk = b0; kk < b1; ++kk) {
+        run += S[kk];
+        if (run >= theta && first == PITCH_NONE) first = kk;
+      }
+    }
+    first = pitch_wg_min(first, s_r);
+    if (first == PITCH_NONE) first = 0ull;  // (a NaN among the S of a segment that is refused anyway)
+    const bool silent = a < FDESC_TINY;
+    const double cent = silent ? 0.0 : tot[1] / a;
+    double v2[1] = {0.0}, e2[1], t2[1];
+    for (uint32_t kk = b0; kk < b1; ++kk) {
+      const double d = (double)kk * sr / dn - cent;
+      v2[0] = fma(S[kk] * d, d, v2[0]);
+    }
+    fdesc_scan<1>(v2, e2, t2, s_w);
+    if (tid == 0) {
+      float* row = A.rows + (size_t)FDESC_COLS * (r0 + f);
+      row[0] = (float)sqrt(tot[4] / dn);
+      row[1] = (float)((double)cross / dn);
+      row[2] = (float)cent;
+      row[3] = (float)(silent ? 0.0 : sqrt(t2[0] / a));
+      row[4] = (float)((double)first * sr / dn);
+      row[5] = (float)(exp(tot[3] / dnb) / (tot[2] / dnb));
+    }
+  }
+}
+
+__global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_finish_kernel(const FdescCtx A) {
+  const uint32_t g = blockIdx.x, tid = threadIdx.x;
+  bool bad = false;
+  for (uint32_t i = tid; i < A.tiles; i += FDESC_THREADS) bad |= A.flags[(size_t)g * A.tiles + i] != 0u;
+  const int refused = __syncthreads_or(bad ? 1 : 0);
+  if (tid == 0 && A.refused) A.refused[g] = refused ? 1u : 0u;
+  if (!refused) return;
+  float* rows = A.rows + (size_t)FDESC_COLS * A.segoff[g];
+  const uint64_t nv = (uint64_t)FDESC_COLS * A.segF[g];
+  for (uint64_t i = tid; i < nv; i += FDESC_THREADS) rows[i] = __uint_as_float(0x7FC00000u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct FdescWs {  // the stage's buffers: its own; the PCM is only read
+  TableUpload tab;
+  std::vector<uint8_t> fixed;  // the spec's part of the table, (cos, sin)[n] as double | window [n] as float, kept from call to call
+  uint32_t fixed_n = 0, fixed_win = 0;
+  bool lds_set = false;  // the kernels' dynamic-LDS limits are raised on this handle's device
+  DevBuf<uint32_t> segF, flags, refused;
+  DevBuf<uint64_t> segoff;
+  DevBuf<float> rows;    // host form: the rows
+};
+
+// The checks of step 11 that need no launch arguments.
+static inline int fdesc_check(const vsyn_fdesc_spec* sp, uint32_t S, const uint32_t* rates, const char** err) {
+  if (!sp) return fail(err, VSYN_ERR_INVALID, "frame descriptor spec is NULL");
+  if (sp->options & ~VSYN_FDESC_CENTER) return fail(err, VSYN_ERR_INVALID, "unknown frame descriptor options 0x%x", sp->options);
+  if (sp->n_fft < FDESC_MIN_FFT || sp->n_fft > TRIM_MAX_FRAME)
+    return fail(err, VSYN_ERR_INVALID, "frame descriptor n_fft %u outside [%u, %u]", sp->n_fft, FDESC_MIN_FFT, TRIM_MAX_FRAME);
+  if (sp->hop_length < 1) return fail(err, VSYN_ERR_INVALID, "frame descriptor hop_length must be >= 1");
+  if (sp->win_length < 1 || sp->win_length > sp->n_fft) return fail(err, VSYN_ERR_INVALID, "win_length %u outside [1, n_fft]", sp->win_length);
+  if (!(sp->roll_percent > 0.0 && sp->roll_percent < 1.0)) return fail(err, VSYN_ERR_INVALID, "roll_percent %g outside (0, 1)", sp->roll_percent);
+  if (!std::isfinite(sp->zcr_threshold) || !(sp->zcr_threshold >= 0.0))
+    return fail(err, VSYN_ERR_INVALID, "zcr_threshold %g must be finite and >= 0", sp->zcr_threshold);
+  if (!std::isfinite(sp->amin) || !(sp->amin > 0.0)) return fail(err, VSYN_ERR_INVALID, "amin %g must be finite and > 0", sp->amin);
+  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
+  return VSYN_OK;
+}
+
+static inline size_t fdesc_lds_bytes(uint32_t ft, uint32_t n, uint32_t h, bool twl) {
+  return 8u * ((size_t)ft * (n / 2u + 1u) + FDESC_WORDS) + (twl ? 16u * (size_t)n : 0u) + 4u * (size_t)n + 4u * ((size_t)(ft - 1u) * std::min(n, h) + n);
+}
+
+// twiddles in LDS: when one frame then fits FDESC_LDS_BUDGET
+static inline bool fdesc_twiddles_in_lds(uint32_t n, uint32_t h) { return fdesc_lds_bytes(1u, n, h, true) <= FDESC_LDS_BUDGET; }
+
+// frames per workgroup: the most whose image fits the path's LDS budget (as pitch_tile chooses FT); one always fits
+static inline uint32_t fdesc_tile(uint32_t n, uint32_t h, bool twl) {
+  const size_t budget = twl ? FDESC_LDS_BUDGET : FDESC_LDS_WIDE;
+  uint32_t ft = FDESC_FT_MAX;
+  while (ft > 1u && fdesc_lds_bytes(ft, n, h, twl) > budget) --ft;
+  return ft;
+}
+
+// Offsets, descriptor and finishing kernels on stream s; frames from d_frames, else from si. f_max bounds every segment's frames.
+// d_refused [S] may be NULL. Caller holds the handle's lock and has run fdesc_check.
+static inline int fdesc_launch(FdescWs& ws, int device, const vsyn_fdesc_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
+                               uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
+                               uint64_t* d_segoff, uint32_t* d_refused, hipStream_t s, const char** err) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_rows & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM and row pointers must be 4-byte aligned");
+  if (plane > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
+  const uint32_t n = sp->n_fft, h = sp->hop_length;
+  // the table: (cos, sin)[n] as double | window [n] as float (rebuilt only when n_fft or win_length change) | rates [S] as double
+  const size_t off_win = 16u * (size_t)n, off_sr = align_up(off_win + 4u * (size_t)n, 16);
+  if (ws.fixed_n != n || ws.fixed_win != sp->win_length) {
+    ws.fixed.assign(off_sr, 0);
+    double* tw = (double*)ws.fixed.data();
+    for (uint32_t m = 0; m < n; ++m) {
+      const double a = 2.0 * M_PI * (double)m / (double)n;
+      tw[2u * m] = cos(a);
+      tw[2u * m + 1u] = sin(a);
+    }
+    float* wn = (float*)(ws.fixed.data() + off_win);  // the spectral stage's window: periodic Hann of win_length, centred in n_fft
+    const uint32_t woff = (n - sp->win_length) / 2u;
+    for (uint32_t i = 0; i < sp->win_length; ++i) wn[woff + i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)sp->win_length));
+    ws.fixed_n = n;
+    ws.fixed_win = sp->win_length;
+  }
+  std::vector<uint8_t> tab(off_sr + 8u * (size_t)S);
+  memcpy(tab.data(), ws.fixed.data(), off_sr);
+  double* sr = (double*)(tab.data() + off_sr);
+  for (uint32_t g = 0; g < S; ++g) sr[g] = (double)rates[g];
+  const bool twl = fdesc_twiddles_in_lds(n, h);
+  const uint32_t ft = fdesc_tile(n, h, twl);
+  const uint64_t tiles = std::max<uint64_t>((f_max + ft - 1u) / ft, 1);
+  if (tiles > 0x7FFFFFFFull || f_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  HIPCHK(hipSetDevice(device));
+  if (!ws.lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_fdesc_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FDESC_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_fdesc_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FDESC_LDS_WIDE));
+    ws.lds_set = true;
+  }
+  HIPCHK(ws.segF.ensure(S));
+  HIPCHK(ws.segoff.ensure((size_t)S + 1));
+  HIPCHK(ws.flags.ensure((size_t)S * tiles));
+  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+  FdescCtx A;
+  A.sr = (const double*)(ws.tab.dev.p + off_sr);
+  A.tw = (const double2*)ws.tab.dev.p;
+  A.win = (const float*)(ws.tab.dev.p + off_win);
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.N = n;
+  A.H = h;
+  A.FT = ft;
+  A.center = (sp->options & VSYN_FDESC_CENTER) ? 1u : 0u;
+  A.tiles = (uint32_t)tiles;
+  A.roll = sp->roll_percent;
+  A.zthr = sp->zcr_threshold;
+  A.amin = sp->amin;
+  A.segF = ws.segF.p;
+  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
+  A.flags = ws.flags.p;
+  A.refused = d_refused;
+  A.rows = d_rows;
+  hipLaunchKernelGGL(vsyn_fdesc_offsets_kernel, dim3(1), dim3(FDESC_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  const size_t lds = fdesc_lds_bytes(ft, n, h, twl);
+  if (twl) hipLaunchKernelGGL(vsyn_fdesc_kernel<true>, dim3((uint32_t)tiles, S), dim3(FDESC_THREADS), lds, s, A);
+  else hipLaunchKernelGGL(vsyn_fdesc_kernel<false>, dim3((uint32_t)tiles, S), dim3(FDESC_THREADS), lds, s, A);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(vsyn_fdesc_finish_kernel, dim3(S), dim3(FDESC_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}

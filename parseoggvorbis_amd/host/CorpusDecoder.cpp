@@ -79,6 +79,7 @@ struct NullCallbacks : ParseCallbacks {};
 bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
 bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
 bool pitch_run(const CorpusOptions& o) { return o.pitch.frame_length != 0; }
+bool fdesc_run(const CorpusOptions& o) { return o.fdesc.n_fft != 0; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
 uint32_t spectral_dim(const CorpusOptions& o) {
@@ -666,10 +667,33 @@ struct Feeder {
     return OkOrError();
   }
 
-  // A synthesis run's file: its PCM (or, for a spectral or pitch run, its rows) to the callbacks.
+  // Frame descriptor run: each file's (rms, zcr, centroid, bandwidth, rolloff, flatness) rows from the PCM still on the device
+  // (vsyn_pcm_fdesc_host, resampled first in a resampled run); a file the stage refuses (a sample that is not finite) gets an error
+  // of its own.
+  OkOrError fdesc_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    std::vector<uint32_t> rates(S);
+    uint64_t rows = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      rates[s] = o.err[s].empty() ? g.pending[s]->header.audio_sample_rate : 0;
+      if (rates[s]) rows += vsyn_fdesc_num_frames(&opts.fdesc, std::min<uint64_t>(o.frames[s], o.plane));
+    }
+    CHECK_ERR(g.rows.ensure(rows * 6u + 1));
+    CHECK_ERR(g.seg_rows.ensure(S));
+    std::vector<uint32_t> refused(S, 0u);
+    vsyn_status st;
+    const char* err = nullptr;
+    const int rc = vsyn_pcm_fdesc_host(g.handle, &opts.fdesc, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused.data(), &st, &err);
+    if (rc != VSYN_OK) return OkOrError(std::string("GPU frame descriptor layer: ") + (err ? err : "frame descriptors failed"));
+    for (uint32_t s = 0; s < S; ++s)
+      if (o.err[s].empty() && refused[s]) o.err[s] = "frame descriptors: the PCM holds a sample that is not finite";
+    return OkOrError();
+  }
+
+  // A synthesis run's file: its PCM (or, for a spectral, pitch or frame descriptor run, its rows) to the callbacks.
   OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
     const uint32_t C = opts.condition ? 1u : g.channels;  // channels delivered
-    const bool spectral = spectral_run(opts) || pitch_run(opts);
+    const bool spectral = spectral_run(opts) || pitch_run(opts) || fdesc_run(opts);
     const uint64_t frames = o.frames[s], pl = o.plane;
     if (opts.condition) out.channels = 1;
     std::vector<DataRange<const float>> chans(C);
@@ -695,7 +719,7 @@ struct Feeder {
     out.status = o.err[s].empty() ? r.status : OkOrError(o.err[s]);
     if (opts.resample_rate) out.sample_rate = opts.resample_rate;
     stats.frames += frames;
-    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : spectral_dim(opts));
+    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : fdesc_run(opts) ? 6u : spectral_dim(opts));
     if (!callbacks || !o.err[s].empty() || opts.intervals_only) return OkOrError();
     std::lock_guard<std::mutex> lk(callbacks_mu);
     if (opts.pcm_s16) {
@@ -710,8 +734,8 @@ struct Feeder {
     if (g.pending.empty()) return OkOrError();
     if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
-    const bool pitch = pitch_run(opts);
-    const bool spectral = spectral_run(opts) || pitch;  // the PCM stays on the device: only the spectral (or pitch) rows come back
+    const bool pitch = pitch_run(opts), fdesc = fdesc_run(opts);
+    const bool spectral = spectral_run(opts) || pitch || fdesc;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
     const bool cond = opts.condition;               // ... and until it is conditioned
     double t0 = now_s();
@@ -742,6 +766,7 @@ struct Feeder {
       else if (!cond) CHECK_ERR(fetch(g, o));
       if (cond && !spectral) CHECK_ERR(condition_stage(g, o));
       if (pitch) CHECK_ERR(pitch_stage(g, o));
+      else if (fdesc) CHECK_ERR(fdesc_stage(g, o));
       else if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
     double t2 = now_s();
@@ -1347,6 +1372,23 @@ extern "C" int ogg_vorbis_pitch_corpus(const uint8_t* const* datas, const size_t
   opts.pitch = *spec;
   opts.resample_rate = target_rate;
   return malloc_corpus("pitch", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                       });
+}
+
+extern "C" int ogg_vorbis_fdesc_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                       uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_fdesc_spec* spec, float** rows_out,
+                                       uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                                       const char** error_out_per_file, double* stats_out, const char** error_out) {
+  if (!spec || !vsyn_fdesc_num_frames(spec, 0x7FFFFFFFu))
+    return refuse_call((void**)rows_out, num_files, "ogg_vorbis_fdesc_corpus: invalid frame descriptor spec", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  opts.fdesc = *spec;
+  opts.resample_rate = target_rate;
+  return malloc_corpus("fdesc", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
                        [&](size_t i, const CorpusFileResult& res, bool bad) {
                          if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
                          if (frames_out) frames_out[i] = bad ? 0 : res.frames;

@@ -112,6 +112,10 @@ struct CorpusOptions {
   // delivered through gotFileFeatures with dim 2; no PCM crosses the bus. A file whose rate the spec does not fit, and a file with
   // a sample that is not finite, fails alone. Excludes features, spectral, pcm_s16 and the conditioning, trim and split stages.
   vsyn_pitch_spec pitch = {0, 0, 0, 0, 0.0, 0.0, 0.0};
+  // frame descriptor run (fdesc.n_fft != 0): as a pitch run, but each file's (rms, zcr, centroid, bandwidth, rolloff, flatness) rows
+  // (include/vorbis_synth_hip.h, "frame descriptors": vsyn_pcm_fdesc_host), delivered through gotFileFeatures with dim 6. A file with
+  // a sample that is not finite fails alone. Excludes what a pitch run excludes, and pitch.
+  vsyn_fdesc_spec fdesc = {0, 0, 0, 0, 0.0, 0.0, 0.0};
 };
 
 struct CorpusStats {
@@ -235,6 +239,13 @@ int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens,
 // ogg_vorbis_features_free. frames_out / rate_out: each file's (resampled) length and the rate its rows are computed at.
 int ogg_vorbis_pitch_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                             uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pitch_spec* spec, float** rows_out,
+                            uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                            const char** error_out_per_file, double* stats_out, const char** error_out);
+// frame descriptor run (CorpusOptions::fdesc = *spec; target_rate as for ogg_vorbis_pitch_corpus): rows_out receives per file NULL
+// (failed, or no rows) or a buffer of rows_count_out[i] * 6 floats, (rms, zcr, centroid, bandwidth, rolloff, flatness) per frame,
+// released with ogg_vorbis_features_free. An invalid spec refuses the call before any file is touched.
+int ogg_vorbis_fdesc_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                            uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_fdesc_spec* spec, float** rows_out,
                             uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
                             const char** error_out_per_file, double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
