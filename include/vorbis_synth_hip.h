@@ -465,12 +465,12 @@ enum {
 typedef struct vsyn_spectral_spec {
   uint32_t kind;        /* VSYN_SPEC_* kind */
   uint32_t options;     /* VSYN_SPEC_* option bits */
-  uint32_t n_fft, hop_length, win_length, n_mels;
+  uint32_t n_fft, hop_length, win_length, n_mels;  /* n_mels: the mel kinds only */
   uint32_t n_mfcc;      /* MFCC only */
   uint32_t power;       /* 1 (magnitude) or 2 (power) */
   double fmin, fmax;    /* Hz; fmax = 0: each segment's sr / 2 */
   double log_floor;     /* LOG_MEL */
-  double amin, top_db;  /* MEL_DB, MFCC; top_db = 0: no clamp */
+  double amin, top_db;  /* MEL_DB, MFCC, LIN_DB; top_db = 0: no clamp */
 } vsyn_spectral_spec;
 
 /* Frames of a segment of `frames` PCM frames under spec (step 2), 0 for an invalid spec. */
@@ -490,6 +490,51 @@ int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint3
 int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
                          const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames,
                          float* d_rows, uint64_t* d_seg_row_off, void* hip_stream, const char** err);
+
+/* ---- linear spectra: magnitude / power, their dB image and the complex STFT of the decoded PCM, computed where the PCM is ----
+ *
+ * Three more kinds of vsyn_spectral_spec, served by every spectral entry point above and below (vsyn_spectral_device, the
+ * vsyn_pcm_*spectral*_host forms, the corpus runs): the linear-frequency spectrum that the mel kinds are built from, without a
+ * filterbank. Input, output layout and frame count are those of "spectral features"; the device is compared against a float64
+ * model of the arithmetic below (tests/spectral_lin_model.py) under a per-frame error bound.
+ *
+ *  1. Mono, framing and window: steps 1 - 3 of "spectral features", unchanged. vsyn_spectral_num_frames gives F; row f lines up
+ *     with row f of the mel kinds, of the pitch frames and of the frame descriptors at the same n_fft, hop and centring.
+ *  2. v[j] = w[j] * y_pad[f * hop_length + j], j < n_fft (0 outside the window's support), and
+ *     X[k] = sum_j v[j] exp(-2 pi i j k / n_fft), k = 0 .. NB - 1, NB = n_fft / 2 + 1.
+ *  3. Kinds. VSYN_SPEC_LIN_POWER: S[k] = |X[k]|^power, power 1 or 2; dim = NB.
+ *     VSYN_SPEC_LIN_DB: D[k] = 10 log10(max(S[k], amin)), then if top_db > 0, D = max(D, max over the whole segment of D - top_db):
+ *     step 6's MEL_DB with S in M's place; dim = NB. librosa.amplitude_to_db(|X|, amin=a) is this kind with power = 2, amin = a^2.
+ *     VSYN_SPEC_STFT: re_0, im_0, re_1, im_1, ... with re_k = sum_j v[j] cos(2 pi j k / n_fft), im_k = -sum_j v[j] sin(2 pi j k /
+ *     n_fft) (numpy.fft.rfft's sign); dim = 2 NB; power, amin and top_db are not read.
+ *  4. Not read by these kinds, and not checked: n_mels, n_mfcc, fmin, fmax, VSYN_SPEC_HTK, VSYN_SPEC_NO_NORM, log_floor. A
+ *     segment's rate only decides whether it is skipped (rate 0: 0 rows); no mel table is built. Checked (VSYN_ERR_INVALID before
+ *     anything runs): the option bits, n_fft, hop_length, win_length as in step 7 there; power 1 or 2 (LIN_POWER, LIN_DB); amin > 0
+ *     and top_db >= 0 (LIN_DB).
+ *  5. The post stage ("spectral post-processing") holds rows of at most 256 columns and is refused for these kinds: every entry
+ *     point given a vsyn_spectral_post with the stage on (order != 0 or a normalisation) returns VSYN_ERR_INVALID before anything
+ *     runs, and vsyn_spectral_post_dim returns 0. A post spec with the stage off is accepted and does nothing, as for the mel kinds.
+ *  6. Inf and NaN samples propagate through the sums as they do for the mel kinds (a frame that holds one is Inf / NaN, other
+ *     frames are not touched); nothing is refused.
+ *
+ * Arithmetic: float32 throughout, in a fixed order per frame, so that the same PCM gives the same bits alone, in any slot of a
+ * batch, at any alignment of the plane and wherever the frame falls in its workgroup's tile. n_fft a power of two: v[j] is one
+ * rounded product, then a real-input radix-2 FFT per frame (a half-size complex transform of the even and odd samples and an
+ * untangling pass) with the twiddles cos/sin(2 pi m / n_fft) rounded from double; each of re_k, im_k is within
+ * 4 (log2 n_fft + 2) 2^-24 sum_j |v[j]| of the exact sum. Any other n_fft: the direct sum of "spectral features", one fma chain
+ * per component, j ascending over the window's support; within (win_length + 3) 2^-24 sum_j |v[j]|. A row of these kinds has up to
+ * 8194 floats: size rows buffers by vsyn_spectral_dim. */
+enum {
+  VSYN_SPEC_LIN_POWER = 5,  /* "lin_power" */
+  VSYN_SPEC_LIN_DB = 6,     /* "lin_db" */
+  VSYN_SPEC_STFT = 7        /* "stft" */
+};
+
+/* Columns of a row under spec (n_mels; n_mfcc for MFCC; NB for LIN_POWER and LIN_DB; 2 NB for STFT), 0 for an invalid spec. */
+uint32_t vsyn_spectral_dim(const vsyn_spectral_spec* spec);
+/* Frames that one workgroup of the linear kinds' kernel computes under spec (a tuning fact, exposed for tests that place frame
+ * counts around it); 0 for an invalid spec or a mel kind. */
+uint32_t vsyn_spectral_lin_tile(const vsyn_spectral_spec* spec);
 
 /* ---- resampling: polyphase resampling of the decoded PCM to a target sample rate, computed where the PCM is ----
  *

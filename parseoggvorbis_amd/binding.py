@@ -26,6 +26,8 @@ VSYN_PCM_S16, VSYN_PCM_F32 = 1, 2
 VSYN_COND_PEAK, VSYN_COND_PREEMPH = 1, 2
 VSYN_PITCH_CENTER = 1
 VSYN_FDESC_CENTER = 1
+VSYN_SPEC_MEL_POWER, VSYN_SPEC_LOG_MEL, VSYN_SPEC_MEL_DB, VSYN_SPEC_MFCC = 1, 2, 3, 4
+VSYN_SPEC_LIN_POWER, VSYN_SPEC_LIN_DB, VSYN_SPEC_STFT = 5, 6, 7  # include/vorbis_synth_hip.h, "linear spectra"
 
 
 class Floor1(C.Structure):
@@ -216,7 +218,7 @@ _SYMBOLS = [
     "vsyn_profile_enable", "vsyn_profile_read", "vsyn_imdct_device", "vsyn_host_alloc", "vsyn_host_free",
     "vsyn_attach_vq", "vsyn_submit_device_vq", "vsyn_submit_host_vq", "vsyn_pcm_interleave_device", "vsyn_pcm_abs_sum_host", "vsyn_pcm_fetch_host",
     "vsyn_feature_rows_device", "vsyn_features_device", "vsyn_features_host",
-    "vsyn_spectral_num_frames", "vsyn_spectral_device", "vsyn_pcm_spectral_host",
+    "vsyn_spectral_num_frames", "vsyn_spectral_device", "vsyn_pcm_spectral_host", "vsyn_spectral_dim", "vsyn_spectral_lin_tile",
     "vsyn_resample_num_frames", "vsyn_resample_device", "vsyn_pcm_resample_host", "vsyn_pcm_resample_spectral_host",
     "vsyn_spectral_post_dim", "vsyn_spectral_post_device", "vsyn_pcm_spectral_post_host",
     "vsyn_pcm_condition_device", "vsyn_pcm_condition_host", "vsyn_pcm_cond_spectral_host",
@@ -226,6 +228,11 @@ _SYMBOLS = [
     "vsyn_pitch_num_frames", "vsyn_pitch_device", "vsyn_pcm_pitch_host",
     "vsyn_fdesc_num_frames", "vsyn_fdesc_device", "vsyn_pcm_fdesc_host",
 ]
+
+
+def _spec_dim(spec):
+    from .spectral import spec_dim  # the one formula (spectral imports this module lazily as well)
+    return spec_dim(spec)
 
 
 def declared_symbols():
@@ -286,6 +293,10 @@ def load():
                                        C.POINTER(Status), cpp]
     lib.vsyn_spectral_num_frames.argtypes = [C.POINTER(SpectralSpec), u64]
     lib.vsyn_spectral_num_frames.restype = u64
+    lib.vsyn_spectral_dim.argtypes = [C.POINTER(SpectralSpec)]
+    lib.vsyn_spectral_dim.restype = u32
+    lib.vsyn_spectral_lin_tile.argtypes = [C.POINTER(SpectralSpec)]
+    lib.vsyn_spectral_lin_tile.restype = u32
     lib.vsyn_spectral_device.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_spectral_host.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, u64, vp, C.POINTER(Status), cpp]
     lib.vsyn_resample_num_frames.argtypes = [u32, u32, u64]
@@ -422,7 +433,7 @@ class Synth:
         """vsyn_pcm_spectral_host over the last submit's segments: returns dict(rc, rows [total][dim], seg_rows [S], flags)."""
         rates = np.ascontiguousarray(sample_rates, dtype=np.uint32)
         S = len(rates)
-        dim = spec.n_mfcc if spec.kind == 4 else spec.n_mels
+        dim = _spec_dim(spec)
         seg_rows = np.zeros(max(1, S), np.uint64)
         st, err = Status(), C.c_char_p()
         rc = self.lib.vsyn_pcm_spectral_host(self.h, C.byref(spec), S, _ptr(rates), None, 0, _ptr(seg_rows), C.byref(st), C.byref(err))
@@ -457,7 +468,7 @@ class Synth:
         """vsyn_pcm_spectral_post_host over the last submit's segments: returns dict(rc, rows [total][D_out], seg_rows [S], flags)."""
         rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
         S = len(rates)
-        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + post.order)
+        dout = _spec_dim(spec) * (1 + post.order)
         seg_rows = np.zeros(max(S, 1), np.uint64)
         st, err = Status(), C.c_char_p()
         rc = self.lib.vsyn_pcm_spectral_post_host(self.h, C.byref(spec), C.byref(post), S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows),
@@ -533,7 +544,7 @@ class Synth:
         seg_rows [S], peaks [S], flags)."""
         rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
         S = len(rates)
-        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + (post.order if post is not None else 0))
+        dout = _spec_dim(spec) * (1 + (post.order if post is not None else 0))
         seg_rows = np.zeros(max(S, 1), np.uint64)
         peaks = np.zeros(max(S, 1), np.float32)
         st, err = Status(), C.c_char_p()
@@ -588,7 +599,7 @@ class Synth:
         [total][D_out], seg_rows [S], bounds [S][2], peaks [S], refs [S], flags)."""
         rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
         S = len(rates)
-        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + (post.order if post is not None else 0))
+        dout = _spec_dim(spec) * (1 + (post.order if post is not None else 0))
         seg_rows = np.zeros(max(S, 1), np.uint64)
         peaks = np.zeros(max(S, 1), np.float32)
         bounds = np.zeros((max(1, S), 2), np.uint32)
@@ -680,7 +691,7 @@ class Synth:
         [total][D_out], seg_rows [S], frames [S], counts [S], intervals, peaks [S], refs [S], flags)."""
         rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
         S = len(rates)
-        dout = (spec.n_mfcc if spec.kind == 4 else spec.n_mels) * (1 + (post.order if post is not None else 0))
+        dout = _spec_dim(spec) * (1 + (post.order if post is not None else 0))
         seg_rows = np.zeros(max(S, 1), np.uint64)
         frames = np.zeros(max(S, 1), np.uint64)
         peaks = np.zeros(max(S, 1), np.float32)

@@ -21,6 +21,7 @@
 #include "vsyn_pcm.h"
 #include "vsyn_features.h"
 #include "vsyn_spectral.h"
+#include "vsyn_spectral_lin.h"
 #include "vsyn_spectral_post.h"
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
@@ -1211,6 +1212,16 @@ uint64_t vsyn_spectral_num_frames(const vsyn_spectral_spec* spec, uint64_t frame
   return spec_num_frames(spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, frames);
 }
 
+uint32_t vsyn_spectral_dim(const vsyn_spectral_spec* spec) {
+  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
+  return spec_dim(spec);
+}
+
+uint32_t vsyn_spectral_lin_tile(const vsyn_spectral_spec* spec) {
+  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK || !spec_is_lin(spec)) return 0;
+  return spec_lin_tile(spec);
+}
+
 int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, const float* d_pcm,
                          uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off,
                          void* hip_stream, const char** err) {
@@ -1229,6 +1240,7 @@ int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_
 
 uint32_t vsyn_spectral_post_dim(const vsyn_spectral_spec* spec, const vsyn_spectral_post* post) {
   if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK || post_check(post, nullptr) != VSYN_OK) return 0;
+  if (spec_is_lin(spec) && post_on(post)) return 0;  // refused: spec_post_check
   return spec_dim(spec) * (1u + post->order);
 }
 
@@ -1255,7 +1267,6 @@ int vsyn_spectral_post_device(vsyn_handle* h, const vsyn_spectral_post* post, ui
 }
 
 }  // extern "C"
-
 
 // The stages chained behind the last host submit. The PCM the next stage reads: planar [S][C][plane]; each segment's frames from d_frames, else from si.
 struct PcmView {
@@ -1428,7 +1439,7 @@ static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   rc = spec_check(spec, S, spec_rates, err);
   if (rc) return rc;
   if (post) {
-    rc = post_check(post, err, post->order <= 2 ? spec_dim(spec) * (1u + post->order) : 0u);
+    rc = spec_post_check(spec, post, err);
     if (rc) return rc;
     if (!post_on(post)) post = nullptr;  // off: the rows of the spectral pass, bit for bit
   }
@@ -1505,7 +1516,7 @@ static int pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, con
   rc = spec_check(spec, S, sp_rates.data(), err);
   if (rc) return rc;
   if (post) {
-    rc = post_check(post, err, post->order <= 2 ? spec_dim(spec) * (1u + post->order) : 0u);
+    rc = spec_post_check(spec, post, err);
     if (rc) return rc;
     if (!post_on(post)) post = nullptr;
   }

@@ -222,6 +222,7 @@ static const uint32_t SPEC_LDS_BUDGET = 160u * 1024u;  // gfx950: 160 KiB of LDS
 struct SpectralWs {  // the stage's buffers: its own; the PCM is only read
   TableUpload tab;
   bool lds_set = false;                // the STFT kernels' dynamic-LDS limit is raised on this handle's device
+  bool lin_lds_set = false;            // and that of the linear kinds' kernels (vsyn_spectral_lin.h)
   DevBuf<uint32_t> segF, segmax;
   DevBuf<uint64_t> segoff;
   DevBuf<float> db, rows;
@@ -238,16 +239,37 @@ static inline double spec_mel_to_hz(double m, bool htk) {
   return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
 
-static inline uint32_t spec_dim(const vsyn_spectral_spec* sp) { return sp->kind == VSYN_SPEC_MFCC ? sp->n_mfcc : sp->n_mels; }
+// The linear kinds (include/vorbis_synth_hip.h, "linear spectra") read no mel field of the spec.
+static inline bool spec_is_lin(const vsyn_spectral_spec* sp) { return sp->kind >= VSYN_SPEC_LIN_POWER && sp->kind <= VSYN_SPEC_STFT; }
+
+// Columns of a row (vsyn_spectral_dim): the one formula on the C side; 0 for an unknown kind.
+static inline uint32_t spec_dim(const vsyn_spectral_spec* sp) {
+  switch (sp->kind) {
+    case VSYN_SPEC_MEL_POWER:
+    case VSYN_SPEC_LOG_MEL:
+    case VSYN_SPEC_MEL_DB: return sp->n_mels;
+    case VSYN_SPEC_MFCC: return sp->n_mfcc;
+    case VSYN_SPEC_LIN_POWER:
+    case VSYN_SPEC_LIN_DB: return sp->n_fft / 2u + 1u;
+    case VSYN_SPEC_STFT: return 2u * (sp->n_fft / 2u + 1u);
+    default: return 0u;
+  }
+}
 
 // The checks of the spec and of every segment's rate (0 = skipped segment).
 static inline int spec_check(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const char** err) {
   if (!sp) return fail(err, VSYN_ERR_INVALID, "spectral spec is NULL");
-  if (sp->kind < VSYN_SPEC_MEL_POWER || sp->kind > VSYN_SPEC_MFCC) return fail(err, VSYN_ERR_INVALID, "unknown spectral kind %u", sp->kind);
+  if (sp->kind < VSYN_SPEC_MEL_POWER || sp->kind > VSYN_SPEC_STFT) return fail(err, VSYN_ERR_INVALID, "unknown spectral kind %u", sp->kind);
   if (sp->options & ~(VSYN_SPEC_CENTER | VSYN_SPEC_HTK | VSYN_SPEC_NO_NORM)) return fail(err, VSYN_ERR_INVALID, "unknown spectral options 0x%x", sp->options);
   if (sp->n_fft < 16 || sp->n_fft > 8192) return fail(err, VSYN_ERR_INVALID, "n_fft %u outside [16, 8192]", sp->n_fft);
   if (sp->hop_length < 1) return fail(err, VSYN_ERR_INVALID, "hop_length must be >= 1");
   if (sp->win_length < 1 || sp->win_length > sp->n_fft) return fail(err, VSYN_ERR_INVALID, "win_length %u outside [1, n_fft]", sp->win_length);
+  if (spec_is_lin(sp)) {  // no mel field is read, and a rate only decides whether its segment is skipped
+    if (sp->kind != VSYN_SPEC_STFT && sp->power != 1 && sp->power != 2) return fail(err, VSYN_ERR_INVALID, "power must be 1 or 2");
+    if (sp->kind == VSYN_SPEC_LIN_DB && (!(sp->amin > 0.0) || !(sp->top_db >= 0.0))) return fail(err, VSYN_ERR_INVALID, "amin must be > 0 and top_db >= 0");
+    if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
+    return VSYN_OK;
+  }
   if (sp->n_mels < 1 || sp->n_mels > 256) return fail(err, VSYN_ERR_INVALID, "n_mels %u outside [1, 256]", sp->n_mels);
   if (sp->kind == VSYN_SPEC_MFCC && (sp->n_mfcc < 1 || sp->n_mfcc > sp->n_mels)) return fail(err, VSYN_ERR_INVALID, "n_mfcc %u outside [1, n_mels]", sp->n_mfcc);
   if (sp->power != 1 && sp->power != 2) return fail(err, VSYN_ERR_INVALID, "power must be 1 or 2");
@@ -272,7 +294,7 @@ static inline uint32_t spec_tile(const vsyn_spectral_spec* sp) {  // frames per 
 
 // SpecHeader, twiddles, window, per-rate bands and weights, DCT matrix, per-segment rate index. Call after spec_check.
 static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, std::vector<uint8_t>& out) {
-  const uint32_t n = sp->n_fft, NM = sp->n_mels, nb = n / 2u + 1u;
+  const uint32_t n = sp->n_fft, NM = spec_is_lin(sp) ? 0u : sp->n_mels, nb = n / 2u + 1u;  // a linear kind: no mel table
   const bool htk = (sp->options & VSYN_SPEC_HTK) != 0, norm = !(sp->options & VSYN_SPEC_NO_NORM);
   std::vector<uint32_t> distinct, seg_rate(S, SPEC_SKIP);
   for (uint32_t g = 0; g < S; ++g) {
@@ -347,12 +369,17 @@ static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, co
   if (S) memcpy(out.data() + T.off_rate, seg_rate.data(), 4ull * S);
 }
 
-// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s; frames from d_frames, else from si. f_max bounds every
+static inline int spec_lin_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
+                                  uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
+                                  uint64_t* d_segoff, hipStream_t s, const char** err);  // vsyn_spectral_lin.h
+
+// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s (a linear kind: spec_lin_launch); frames from d_frames, else from si. f_max bounds every
 // segment's STFT frames, rows_bound the total rows. Caller holds the handle's lock and has run spec_check.
 static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
                        uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
                        uint64_t* d_segoff, hipStream_t s, const char** err) {
   if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (spec_is_lin(sp)) return spec_lin_launch(ws, device, sp, S, rates, d_pcm, plane, C, d_frames, si, f_max, d_rows, d_segoff, s, err);
   const uint32_t ft = spec_tile(sp);
   if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", sp->n_fft, sp->hop_length);
   std::vector<uint8_t> tab;

@@ -83,7 +83,7 @@ bool fdesc_run(const CorpusOptions& o) { return o.fdesc.n_fft != 0; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
 uint32_t spectral_dim(const CorpusOptions& o) {
-  return (o.spectral.kind == VSYN_SPEC_MFCC ? o.spectral.n_mfcc : o.spectral.n_mels) * (1u + o.post.order);
+  return vsyn_spectral_dim(&o.spectral) * (1u + o.post.order);
 }
 bool feature_needs_residue(const CorpusOptions& o) {
   return o.features.kind == VSYN_FEAT_RESIDUE_YS || o.features.kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
@@ -570,7 +570,8 @@ struct Feeder {
       const FileRecord& r = *g.pending[s];
       const uint32_t sr = resample ? opts.resample_rate : r.header.audio_sample_rate;  // the rate the rows are computed at
       const double ny = sr / 2.0, fmax = opts.spectral.fmax > 0.0 ? opts.spectral.fmax : ny;
-      if (o.err[s].empty() && !(fmax <= ny && opts.spectral.fmin < fmax)) {
+      const bool lin = opts.spectral.kind >= VSYN_SPEC_LIN_POWER;  // a linear kind reads neither fmin nor fmax
+      if (o.err[s].empty() && !lin && !(fmax <= ny && opts.spectral.fmin < fmax)) {
         char buf[160];
         snprintf(buf, sizeof(buf), "spectral: fmin %g / fmax %g do not fit sample rate %u (0 <= fmin < fmax <= sr/2)", opts.spectral.fmin, fmax,
                  sr);

@@ -156,8 +156,9 @@ int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, 
                                uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
                                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                double* stats_out, const char** error_out);
-// spectral run (CorpusOptions::spectral = *spec), same output contract as ogg_vorbis_features_corpus (dim = n_mfcc for MFCC,
-// n_mels otherwise); rows released with ogg_vorbis_features_free. A file whose rate the spec does not fit fails alone.
+// spectral run (CorpusOptions::spectral = *spec), same output contract as ogg_vorbis_features_corpus (dim =
+// vsyn_spectral_dim(spec): n_mfcc for MFCC, n_fft / 2 + 1 for LIN_POWER and LIN_DB, twice that for STFT, n_mels otherwise); rows
+// released with ogg_vorbis_features_free. A file whose rate the spec does not fit fails alone (a linear kind fits every rate).
 int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, float** rows_out,
                                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,

@@ -1,5 +1,5 @@
 """Spectral front-end features computed on the GPU from Ogg bytes: mel power, log-mel, dB-mel and MFCC matrices
-(frames, dim) float32, from the decoded PCM while it is still on the device (no PCM crosses the bus). ctypes onto
+(frames, dim) float32, and the linear spectra they are built from (magnitude / power, dB, complex STFT), from the decoded PCM while it is still on the device (no PCM crosses the bus). ctypes onto
 libparseoggvorbis_amd.so (ogg_vorbis_spectral_corpus_sr); the semantics are documented in include/vorbis_synth_hip.h ("spectral
 features"). They follow librosa's documented defaults (librosa >= 0.10); parity with librosa itself has not been verified, the
 float64 model in tests/spectral_model.py is the contract the device is tested against.
@@ -20,7 +20,8 @@ import numpy as np
 from . import _corpus
 from ._corpus import HOST_LIB_PATH  # noqa: F401
 
-KINDS = {"mel_power": 1, "log_mel": 2, "mel_db": 3, "mfcc": 4}
+KINDS = {"mel_power": 1, "log_mel": 2, "mel_db": 3, "mfcc": 4, "lin_power": 5, "lin_db": 6, "stft": 7}
+LINEAR_KINDS = (5, 6, 7)  # include/vorbis_synth_hip.h, "linear spectra": no filterbank, rows of n_fft / 2 + 1 bins
 OPT_CENTER, OPT_HTK, OPT_NO_NORM = 1, 2, 4
 MAX_N_FFT, MAX_N_MELS = 8192, 256
 
@@ -38,7 +39,8 @@ def _int(name, v):
 def spectral_spec(kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n_mels=128, fmin=0.0, fmax=None, htk=False,
                   norm="slaney", center=True, power=2.0, log_floor=1e-3, amin=1e-10, top_db=80.0, n_mfcc=20):
     """Checks the arguments (include/vorbis_synth_hip.h, "spectral features", step 7; fmax against each file's rate happens per
-    file) and returns the C spec (binding.SpectralSpec)."""
+    file) and returns the C spec (binding.SpectralSpec). Every argument is checked for every kind, the linear kinds ("lin_power",
+    "lin_db", "stft": "linear spectra" there) included, although the device reads no mel argument for those."""
     from .binding import SpectralSpec
     if kind not in KINDS:
         raise SpectralError("invalid spectral kind %r; supported kinds: %s" % (kind, ", ".join(sorted(KINDS))))
@@ -71,9 +73,9 @@ def spectral_spec(kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n
     top_db = 0.0 if top_db is None else float(top_db)
     if kind == "log_mel" and not log_floor > 0:
         raise SpectralError("log_floor must be > 0, got %r" % log_floor)
-    if kind in ("mel_db", "mfcc") and not amin > 0:
+    if kind in ("mel_db", "mfcc", "lin_db") and not amin > 0:
         raise SpectralError("amin must be > 0, got %r" % amin)
-    if kind in ("mel_db", "mfcc") and not top_db >= 0:
+    if kind in ("mel_db", "mfcc", "lin_db") and not top_db >= 0:
         raise SpectralError("top_db must be >= 0 (or None), got %r" % top_db)
     opts = (OPT_CENTER if center else 0) | (OPT_HTK if htk else 0) | (OPT_NO_NORM if norm is None else 0)
     return SpectralSpec(KINDS[kind], opts, n_fft, hop_length, win_length, n_mels, n_mfcc if kind == "mfcc" else 0, int(power),
@@ -81,7 +83,14 @@ def spectral_spec(kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n
 
 
 def spec_dim(spec):
-    return spec.n_mfcc if spec.kind == KINDS["mfcc"] else spec.n_mels
+    """Columns of a row under spec (vsyn_spectral_dim; the one formula on the Python side, usable before the library loads):
+    n_mfcc for "mfcc", n_fft / 2 + 1 for "lin_power" and "lin_db", twice that for "stft" (re, im interleaved), n_mels otherwise;
+    0 for an unknown kind."""
+    if spec.kind == KINDS["mfcc"]:
+        return spec.n_mfcc
+    if spec.kind in LINEAR_KINDS:
+        return (spec.n_fft // 2 + 1) * (2 if spec.kind == KINDS["stft"] else 1)
+    return spec.n_mels if spec.kind in KINDS.values() else 0
 
 
 NORM_NONE, NORM_MEAN, NORM_MEAN_VAR = 0, 1, 2
@@ -146,7 +155,11 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                        normalize=None, std_floor=1e-5, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048,
                        trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
-    "mfcc", n_mels otherwise. errors="raise": the first failed file raises SpectralError naming it; errors="return": its entry
+    "mfcc", n_mels for the other mel kinds. The linear kinds have no filterbank: "lin_power" is |X|^power and "lin_db" its dB image
+    (amin, top_db as for "mel_db"; librosa.amplitude_to_db(|X|, amin=a) is power=2, amin=a*a), both (frames, n_fft / 2 + 1);
+    "stft" is the complex STFT itself, complex64 arrays (frames, n_fft / 2 + 1) with numpy.fft.rfft's sign. They take neither
+    delta nor normalize (SpectralError before anything is loaded) and compose with sr, peak_normalize / preemphasis, trim_db and
+    split_db like the mel kinds; their rows are n_fft / 2 + 1 floats wide, so files_per_submit bounds the memory of a run. errors="raise": the first failed file raises SpectralError naming it; errors="return": its entry
     is the SpectralError. stats (optional list) receives the run's 8 corpus statistics. sr=None: each file at its own rate;
     an integer: every file resampled to sr on the device, and the mel table and the fmin / fmax check use sr.
     delta = 1 or 2 appends librosa.feature.delta's columns of that many orders (Savitzky-Golay over delta_width frames; a file
@@ -168,6 +181,9 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
     post, dim, keep = post_spec(spec_dim(spec), delta, delta_width, normalize, std_floor)
+    if post is not None and spec.kind in LINEAR_KINDS:
+        raise SpectralError("delta / normalize are not available for the linear kind %r (rows of %d columns; the post stage holds 256)"
+                            % (kind, dim))
     cond = cond_spec(peak_normalize, preemphasis, SpectralError)
     trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index, SpectralError)
     split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
@@ -186,7 +202,7 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
         finally:
             ib.free()
         give_trim_index(trim_index, None, res)
-        return res
+        return _finish(spec, res)
     give_split_index(split_index, None, [None] * len(list_of_bytes))
     if trim is not None:
         bounds = np.zeros((max(len(list_of_bytes), 1), 2), np.uint64)
@@ -196,7 +212,7 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                           lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors, "spectral",
                           stats)
         give_trim_index(trim_index, bounds[:len(list_of_bytes)], res)
-        return res
+        return _finish(spec, res)
     if cond.options:
         fn, extra = lib.ogg_vorbis_spectral_corpus_cond, (None if post is None else C.byref(post), C.byref(cond))
     else:
@@ -205,6 +221,15 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                       lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors, "spectral",
                       stats)
     give_trim_index(trim_index, None, res)
+    return _finish(spec, res)
+
+
+def _finish(spec, res):
+    """"stft": each float32 matrix (frames, 2 NB) as its complex64 view (frames, NB); every other kind as it is."""
+    if spec.kind == KINDS["stft"]:
+        for i, a in enumerate(res):
+            if isinstance(a, np.ndarray):
+                res[i] = a.view(np.complex64)
     return res
 
 
