@@ -347,21 +347,45 @@ class VsynError(RuntimeError):
         self.code, self.status = code, status
 
 
+def _check(rc, err, ok=(VSYN_OK,)):
+    if rc not in ok:
+        raise VsynError(rc, (err.value or b"").decode())
+
+
 def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _ref(x):
+    return None if x is None else C.byref(x)
+
+
+def _rates(r):
+    return None if r is None else np.ascontiguousarray(r, dtype=np.uint32)
+
+
+_PER_SEGMENT = dict(frames=(np.uint64,), seg_rows=(np.uint64,), peaks=(np.float32,), refs=(np.float64,), counts=(np.uint32,),
+                    refused=(np.uint32,), bounds=(np.uint32, 2))
+
+
+def _per_segment(S, *names):
+    """The named per-segment outputs of a host entry, zeroed and never empty (C gets their pointers)."""
+    return {n: np.zeros((max(1, S),) + _PER_SEGMENT[n][1:], _PER_SEGMENT[n][0]) for n in names}
+
+
+def _post_dim(spec, post):
+    return _spec_dim(spec) * (1 + (post.order if post is not None else 0))
+
+
 class Synth:
-    """Owns one vsyn_handle. Thin: every method is one C-ABI call."""
+    """Owns one vsyn_handle. Thin: every method is one C-ABI call (a host entry that sizes its own output: two, _sized_call)."""
 
     def __init__(self, spec, device=0, max_streams=64):
         self.lib = load()
         self.spec = spec
         self._su = spec.c_setup()
         h, err = C.c_void_p(), C.c_char_p()
-        rc = self.lib.vsyn_create(C.byref(self._su), device, max_streams, C.byref(h), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_create(C.byref(self._su), device, max_streams, C.byref(h), C.byref(err)), err)
         self.h = h
         self.channels = spec.channels
         self.ys_stride = self.lib.vsyn_ys_stride(h)
@@ -376,9 +400,7 @@ class Synth:
 
     def reset(self, stream=None):
         err = C.c_char_p()
-        rc = self.lib.vsyn_reset_streams(self.h, stream, C.byref(err))
-        if rc:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_reset_streams(self.h, stream, C.byref(err)), err)
 
     def submit_host(self, packets, segments, ys, residue, plane_stride, want_taps=False, flags=0):
         """numpy in, numpy out: returns dict(pcm [S][C][plane_stride], emit_len [P], taps..., status)."""
@@ -405,8 +427,7 @@ class Synth:
         rc = self.lib.vsyn_submit_host(self.h, P, _ptr(packets), S, _ptr(segments), _ptr(ys), _ptr(residue),
                                        residue.size, _ptr(pcm), plane_stride, _ptr(emit),
                                        C.byref(tp) if tp else None, flags, C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(rc, err, (VSYN_OK, VSYN_ERR_STREAM))
         return dict(rc=rc, pcm=pcm, emit_len=emit, taps=taps, flags=st.flags, first_bad=st.first_bad_packet)
 
     def features_host(self, spec, packets, segments, ys, residue=None):
@@ -424,221 +445,146 @@ class Synth:
         rc = self.lib.vsyn_features_host(self.h, C.byref(spec), P, _ptr(packets), S, _ptr(segments), _ptr(ys), _ptr(residue),
                                          0 if residue is None else residue.size, _ptr(rows), rows.shape[0], _ptr(seg_rows),
                                          C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(rc, err, (VSYN_OK, VSYN_ERR_STREAM))
         total = int(seg_rows[:S].sum()) if rc == VSYN_OK else 0
         return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], flags=st.flags, first_bad=st.first_bad_packet)
 
+    def _sized_call(self, fn, head, sizes, alloc, st=None, ok=(VSYN_OK,)):
+        """The two calls of a host entry fn(h, *head, buffer, its capacity or stride, sizes, further outputs ..., [status,] err): with
+        a NULL buffer (and every further output NULL or 0) for sizes [S], the frames or the row counts; then (buffer, n, outs) =
+        alloc() and the call that fills them. Returns (rc of the second call, buffer)."""
+        err = C.c_char_p()
+        tail = ([] if st is None else [C.byref(st)]) + [C.byref(err)]
+        nulls = [0] * (len(fn.argtypes) - len(head) - len(tail) - 4)
+        _check(fn(self.h, *head, None, 0, _ptr(sizes), *nulls, *tail), err)
+        buf, n, outs = alloc()
+        rc = fn(self.h, *head, _ptr(buf), n, _ptr(sizes), *[_ptr(o) if isinstance(o, np.ndarray) else o for o in outs], *tail)
+        _check(rc, err, ok)
+        return rc, buf
+
+    def _rows_host(self, fn, head, S, cols, outs=(), named={}):
+        """A host entry that returns rows: dict(rc, rows [total][cols], seg_rows [S], flags) and the named per-segment outputs; outs
+        are its further outputs in the order of the C arguments."""
+        seg_rows, st = np.zeros(max(1, S), np.uint64), Status()
+        rc, rows = self._sized_call(fn, head, seg_rows, lambda: (np.zeros((max(1, int(seg_rows[:S].sum())), cols), np.float32),
+                                                                 int(seg_rows[:S].sum()), outs), st, (VSYN_OK, VSYN_ERR_STREAM))
+        return dict(rc=rc, rows=rows[:int(seg_rows[:S].sum())], seg_rows=seg_rows[:S], flags=st.flags, **{k: v[:S] for k, v in named.items()})
+
+    def _pcm_host(self, fn, head, S, fmt, chans, outs):
+        """A host entry that returns PCM: (pcm, frames [S]); pcm is float32 [S][chans][stride] (planar) or int16 [S][stride][chans]
+        (interleaved), for chans = None (mono) [S][stride] of either, stride = the largest of the frames the size query gives.
+        outs(t_max): its further outputs in the order of the C arguments."""
+        frames = np.zeros(max(1, S), np.uint64)
+
+        def alloc():
+            t_max = int(frames[:S].max()) if S else 0
+            stride = max(1, t_max)
+            shape = (S, stride) if chans is None else (S, chans, stride) if fmt == VSYN_PCM_F32 else (S, stride, chans)
+            return np.zeros(shape, np.float32 if fmt == VSYN_PCM_F32 else np.int16), stride, outs(t_max)
+        return self._sized_call(fn, head, frames, alloc)[1], frames[:S]
+
     def pcm_spectral_host(self, spec, sample_rates):
         """vsyn_pcm_spectral_host over the last submit's segments: returns dict(rc, rows [total][dim], seg_rows [S], flags)."""
-        rates = np.ascontiguousarray(sample_rates, dtype=np.uint32)
-        S = len(rates)
-        dim = _spec_dim(spec)
-        seg_rows = np.zeros(max(1, S), np.uint64)
-        st, err = Status(), C.c_char_p()
-        rc = self.lib.vsyn_pcm_spectral_host(self.h, C.byref(spec), S, _ptr(rates), None, 0, _ptr(seg_rows), C.byref(st), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        total = int(seg_rows[:S].sum())
-        rows = np.zeros((max(1, total), dim), np.float32)
-        rc = self.lib.vsyn_pcm_spectral_host(self.h, C.byref(spec), S, _ptr(rates), _ptr(rows), total, _ptr(seg_rows), C.byref(st),
-                                             C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], flags=st.flags)
+        rates = _rates(sample_rates)
+        return self._rows_host(self.lib.vsyn_pcm_spectral_host, (C.byref(spec), len(rates), _ptr(rates)), len(rates), _spec_dim(spec))
 
     def spectral_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, stream=None):
         """vsyn_spectral_device on device pointers (ints); sample_rates is a host sequence."""
-        rates = np.ascontiguousarray(sample_rates, dtype=np.uint32)
+        rates = _rates(sample_rates)
         err = C.c_char_p()
-        rc = self.lib.vsyn_spectral_device(self.h, C.byref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows,
-                                           d_seg_row_off, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_spectral_device(self.h, C.byref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows,
+                                             d_seg_row_off, stream, C.byref(err)), err)
 
     def spectral_post_device(self, post, dim, seg_rows, d_in, d_out, stream=None):
         """vsyn_spectral_post_device on device pointers (ints); seg_rows is a host sequence of each segment's row count."""
         nrows = np.ascontiguousarray(seg_rows, dtype=np.uint64)
         err = C.c_char_p()
-        rc = self.lib.vsyn_spectral_post_device(self.h, C.byref(post), dim, len(nrows), _ptr(nrows), d_in, d_out, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_spectral_post_device(self.h, C.byref(post), dim, len(nrows), _ptr(nrows), d_in, d_out, stream, C.byref(err)), err)
 
     def pcm_spectral_post_host(self, spec, post, in_rates, out_rate=0):
         """vsyn_pcm_spectral_post_host over the last submit's segments: returns dict(rc, rows [total][D_out], seg_rows [S], flags)."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
-        S = len(rates)
-        dout = _spec_dim(spec) * (1 + post.order)
-        seg_rows = np.zeros(max(S, 1), np.uint64)
-        st, err = Status(), C.c_char_p()
-        rc = self.lib.vsyn_pcm_spectral_post_host(self.h, C.byref(spec), C.byref(post), S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows),
-                                                  C.byref(st), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        total = int(seg_rows[:S].sum())
-        rows = np.zeros((max(total, 1), dout), np.float32)
-        rc = self.lib.vsyn_pcm_spectral_post_host(self.h, C.byref(spec), C.byref(post), S, _ptr(rates), out_rate, _ptr(rows), total,
-                                                  _ptr(seg_rows), C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], flags=st.flags)
+        rates = _rates(in_rates)
+        return self._rows_host(self.lib.vsyn_pcm_spectral_post_host, (C.byref(spec), C.byref(post), len(rates), _ptr(rates), out_rate), len(rates),
+                               _post_dim(spec, post))
 
     def resample_device(self, in_rates, out_rate, d_pcm, plane_stride, channels, d_frames, d_out, out_plane_stride, d_out_frames,
                         stream=None):
         """vsyn_resample_device on device pointers (ints); in_rates is a host sequence."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
+        rates = _rates(in_rates)
         err = C.c_char_p()
-        rc = self.lib.vsyn_resample_device(self.h, len(rates), _ptr(rates), out_rate, d_pcm, plane_stride, channels, d_frames, d_out,
-                                           out_plane_stride, d_out_frames, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_resample_device(self.h, len(rates), _ptr(rates), out_rate, d_pcm, plane_stride, channels, d_frames, d_out,
+                                             out_plane_stride, d_out_frames, stream, C.byref(err)), err)
 
     def pcm_resample_host(self, in_rates, out_rate, fmt=VSYN_PCM_F32):
         """vsyn_pcm_resample_host over the last submit's segments: returns (pcm, frames [S]); pcm is float32 [S][C][stride] (planar)
         or int16 [S][stride][C] (interleaved), stride = the largest T_out."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
-        S = len(rates)
-        frames = np.zeros(max(1, S), np.uint64)
-        err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_resample_host(self.h, S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        stride = max(1, int(frames[:S].max()) if S else 1)
-        C_ = self.channels
-        out = np.zeros((S, C_, stride), np.float32) if fmt == VSYN_PCM_F32 else np.zeros((S, stride, C_), np.int16)
-        rc = self.lib.vsyn_pcm_resample_host(self.h, S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        return out, frames[:S]
+        rates = _rates(in_rates)
+        return self._pcm_host(self.lib.vsyn_pcm_resample_host, (len(rates), _ptr(rates), out_rate, fmt), len(rates), fmt, self.channels,
+                              lambda t_max: [])
 
     def pcm_condition_device(self, cond, d_pcm, plane_stride, channels, num_segments, d_frames, d_out, out_plane_stride, d_peaks=None,
                              stream=None):
         """vsyn_pcm_condition_device on device pointers (ints)."""
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_condition_device(self.h, C.byref(cond), num_segments, d_pcm, plane_stride, channels, d_frames, d_out,
-                                                out_plane_stride, d_peaks, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_pcm_condition_device(self.h, C.byref(cond), num_segments, d_pcm, plane_stride, channels, d_frames, d_out,
+                                                  out_plane_stride, d_peaks, stream, C.byref(err)), err)
 
     def pcm_condition_host(self, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
         """vsyn_pcm_condition_host over the last submit's segments: returns (pcm [S][stride] float32 or int16, frames [S], peaks [S]),
         stride = the largest T."""
-        S = num_segments
-        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
-        frames = np.zeros(max(1, S), np.uint64)
-        peaks = np.zeros(max(1, S), np.float32)
-        err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_condition_host(self.h, C.byref(cond), S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), None, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        stride = max(1, int(frames[:S].max()) if S else 1)
-        out = np.zeros((S, stride), np.float32 if fmt == VSYN_PCM_F32 else np.int16)
-        rc = self.lib.vsyn_pcm_condition_host(self.h, C.byref(cond), S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames),
-                                              _ptr(peaks), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        return out, frames[:S], peaks[:S]
+        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "peaks")
+        out, frames = self._pcm_host(self.lib.vsyn_pcm_condition_host, (C.byref(cond), S, _ptr(rates), out_rate, fmt), S, fmt, None,
+                                     lambda t_max: [o["peaks"]])
+        return out, frames, o["peaks"][:S]
 
     def pcm_cond_spectral_host(self, cond, spec, post, in_rates, out_rate=0):
         """vsyn_pcm_cond_spectral_host over the last submit's segments (cond / post may be None): returns dict(rc, rows [total][D_out],
         seg_rows [S], peaks [S], flags)."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
-        S = len(rates)
-        dout = _spec_dim(spec) * (1 + (post.order if post is not None else 0))
-        seg_rows = np.zeros(max(S, 1), np.uint64)
-        peaks = np.zeros(max(S, 1), np.float32)
-        st, err = Status(), C.c_char_p()
-        cp = None if cond is None else C.byref(cond)
-        pp = None if post is None else C.byref(post)
-        rc = self.lib.vsyn_pcm_cond_spectral_host(self.h, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None,
-                                                  C.byref(st), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        total = int(seg_rows[:S].sum())
-        rows = np.zeros((max(total, 1), dout), np.float32)
-        rc = self.lib.vsyn_pcm_cond_spectral_host(self.h, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows),
-                                                  _ptr(peaks), C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], peaks=peaks[:S], flags=st.flags)
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "peaks")
+        return self._rows_host(self.lib.vsyn_pcm_cond_spectral_host, (_ref(cond), C.byref(spec), _ref(post), S, _ptr(rates), out_rate), S,
+                               _post_dim(spec, post), [o["peaks"]], o)
 
     def pcm_trim_device(self, trim, d_pcm, plane_stride, channels, num_segments, d_frames, d_out, out_plane_stride, d_out_frames, d_bounds,
                         d_ref=None, d_ms=None, ms_stride=0, stream=None):
         """vsyn_pcm_trim_device on device pointers (ints)."""
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_trim_device(self.h, None if trim is None else C.byref(trim), num_segments, d_pcm, plane_stride, channels, d_frames,
-                                           d_out, out_plane_stride, d_out_frames, d_bounds, d_ref, d_ms, ms_stride, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_pcm_trim_device(self.h, _ref(trim), num_segments, d_pcm, plane_stride, channels, d_frames, d_out, out_plane_stride,
+                                             d_out_frames, d_bounds, d_ref, d_ms, ms_stride, stream, C.byref(err)), err)
 
     def pcm_trim_host(self, trim, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
         """vsyn_pcm_trim_host over the last submit's segments (trim / cond may be None): returns dict(pcm [S][stride] float32 or
         int16, frames [S], bounds [S][2], peaks [S], refs [S]), stride = the largest untrimmed T."""
-        S = num_segments
-        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
-        frames = np.zeros(max(1, S), np.uint64)
-        peaks = np.zeros(max(1, S), np.float32)
-        bounds = np.zeros((max(1, S), 2), np.uint32)
-        refs = np.zeros(max(1, S), np.float64)
-        err = C.c_char_p()
-        tp = None if trim is None else C.byref(trim)
-        cp = None if cond is None else C.byref(cond)
-        rc = self.lib.vsyn_pcm_trim_host(self.h, tp, cp, S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), None, None, None, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        stride = max(1, int(frames[:S].max()) if S else 1)
-        out = np.zeros((S, stride), np.float32 if fmt == VSYN_PCM_F32 else np.int16)
-        rc = self.lib.vsyn_pcm_trim_host(self.h, tp, cp, S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames), _ptr(bounds),
-                                         _ptr(peaks), _ptr(refs), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(pcm=out, frames=frames[:S], bounds=bounds[:S], peaks=peaks[:S], refs=refs[:S])
+        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "bounds", "peaks", "refs")
+        out, frames = self._pcm_host(self.lib.vsyn_pcm_trim_host, (_ref(trim), _ref(cond), S, _ptr(rates), out_rate, fmt), S, fmt, None,
+                                     lambda t_max: [o["bounds"], o["peaks"], o["refs"]])
+        return dict(pcm=out, frames=frames, **{k: v[:S] for k, v in o.items()})
 
     def pcm_trim_spectral_host(self, trim, cond, spec, post, in_rates, out_rate=0):
         """vsyn_pcm_trim_spectral_host over the last submit's segments (trim / cond / post may be None): returns dict(rc, rows
         [total][D_out], seg_rows [S], bounds [S][2], peaks [S], refs [S], flags)."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
-        S = len(rates)
-        dout = _spec_dim(spec) * (1 + (post.order if post is not None else 0))
-        seg_rows = np.zeros(max(S, 1), np.uint64)
-        peaks = np.zeros(max(S, 1), np.float32)
-        bounds = np.zeros((max(1, S), 2), np.uint32)
-        refs = np.zeros(max(1, S), np.float64)
-        st, err = Status(), C.c_char_p()
-        tp = None if trim is None else C.byref(trim)
-        cp = None if cond is None else C.byref(cond)
-        pp = None if post is None else C.byref(post)
-        rc = self.lib.vsyn_pcm_trim_spectral_host(self.h, tp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None,
-                                                  None, None, C.byref(st), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        total = int(seg_rows[:S].sum())
-        rows = np.zeros((max(total, 1), dout), np.float32)
-        rc = self.lib.vsyn_pcm_trim_spectral_host(self.h, tp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows),
-                                                  _ptr(bounds), _ptr(peaks), _ptr(refs), C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], bounds=bounds[:S], peaks=peaks[:S], refs=refs[:S], flags=st.flags)
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "bounds", "peaks", "refs")
+        return self._rows_host(self.lib.vsyn_pcm_trim_spectral_host, (_ref(trim), _ref(cond), C.byref(spec), _ref(post), S, _ptr(rates), out_rate), S,
+                               _post_dim(spec, post), [o["bounds"], o["peaks"], o["refs"]], o)
 
     def pcm_split_device(self, split, d_pcm, plane_stride, channels, num_segments, d_frames, d_out, out_plane_stride, d_out_frames, d_counts,
                          d_intervals, intervals_stride, d_ref=None, d_ms=None, ms_stride=0, stream=None):
         """vsyn_pcm_split_device on device pointers (ints)."""
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_split_device(self.h, None if split is None else C.byref(split), num_segments, d_pcm, plane_stride, channels, d_frames,
-                                            d_out, out_plane_stride, d_out_frames, d_counts, d_intervals, intervals_stride, d_ref, d_ms, ms_stride,
-                                            stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_pcm_split_device(self.h, _ref(split), num_segments, d_pcm, plane_stride, channels, d_frames, d_out, out_plane_stride,
+                                              d_out_frames, d_counts, d_intervals, intervals_stride, d_ref, d_ms, ms_stride, stream, C.byref(err)), err)
+
+    def _max_intervals(self, split, t_max):
+        return 1 if split is None else max(1, int(self.lib.vsyn_pcm_split_max_intervals(C.byref(split), t_max)))
 
     def _split_sizes(self, split, S, rates, out_rate):
         """The unsplit frames [S] of the last submit's segments and the interval stride that holds the longest one's intervals."""
         frames = np.zeros(max(1, S), np.uint64)
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_split_intervals_host(self.h, C.byref(split), S, _ptr(rates), out_rate, _ptr(frames), None, None, 0, None, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        t_max = int(frames[:S].max()) if S else 0
-        return frames, max(1, int(self.lib.vsyn_pcm_split_max_intervals(C.byref(split), t_max)))
+        _check(self.lib.vsyn_pcm_split_intervals_host(self.h, C.byref(split), S, _ptr(rates), out_rate, _ptr(frames), None, None, 0, None,
+                                                      C.byref(err)), err)
+        return frames, self._max_intervals(split, int(frames[:S].max()) if S else 0)
 
     @staticmethod
     def _intervals(counts, iv, S):
@@ -647,137 +593,69 @@ class Synth:
     def pcm_split_intervals_host(self, split, num_segments, in_rates=None, out_rate=0):
         """vsyn_pcm_split_intervals_host over the last submit's segments: returns dict(frames [S] (unsplit), counts [S], intervals (a
         list of (n, 2) int64 arrays), refs [S])."""
-        S = num_segments
-        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
+        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "counts", "refs")
         frames, stride = self._split_sizes(split, S, rates, out_rate)
-        counts = np.zeros(max(1, S), np.uint32)
         iv = np.zeros((max(1, S), stride, 2), np.uint32)
-        refs = np.zeros(max(1, S), np.float64)
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_split_intervals_host(self.h, C.byref(split), S, _ptr(rates), out_rate, _ptr(frames), _ptr(counts), _ptr(iv), stride,
-                                                    _ptr(refs), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(frames=frames[:S], counts=counts[:S], intervals=self._intervals(counts, iv, S), refs=refs[:S])
+        _check(self.lib.vsyn_pcm_split_intervals_host(self.h, C.byref(split), S, _ptr(rates), out_rate, _ptr(frames), _ptr(o["counts"]), _ptr(iv),
+                                                      stride, _ptr(o["refs"]), C.byref(err)), err)
+        return dict(frames=frames[:S], counts=o["counts"][:S], intervals=self._intervals(o["counts"], iv, S), refs=o["refs"][:S])
 
     def pcm_split_host(self, split, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
         """vsyn_pcm_split_host over the last submit's segments (split / cond may be None): returns dict(pcm [S][stride] float32 or
         int16, frames [S], counts [S], intervals (a list of (n, 2) int64 arrays), peaks [S], refs [S]), stride = the largest unsplit T."""
-        S = num_segments
-        rates = None if in_rates is None else np.ascontiguousarray(in_rates, dtype=np.uint32)
-        frames = np.zeros(max(1, S), np.uint64)
-        peaks = np.zeros(max(1, S), np.float32)
-        counts = np.zeros(max(1, S), np.uint32)
-        refs = np.zeros(max(1, S), np.float64)
-        err = C.c_char_p()
-        sp = None if split is None else C.byref(split)
-        cp = None if cond is None else C.byref(cond)
-        rc = self.lib.vsyn_pcm_split_host(self.h, sp, cp, S, _ptr(rates), out_rate, fmt, None, 0, _ptr(frames), None, None, 0, None, None, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        t_max = int(frames[:S].max()) if S else 0
-        stride = max(1, t_max)
-        ivs = 1 if split is None else max(1, int(self.lib.vsyn_pcm_split_max_intervals(sp, t_max)))
-        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
-        out = np.zeros((S, stride), np.float32 if fmt == VSYN_PCM_F32 else np.int16)
-        rc = self.lib.vsyn_pcm_split_host(self.h, sp, cp, S, _ptr(rates), out_rate, fmt, _ptr(out), stride, _ptr(frames), _ptr(counts), _ptr(iv), ivs,
-                                          _ptr(peaks), _ptr(refs), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(pcm=out, frames=frames[:S], counts=counts[:S], intervals=self._intervals(counts, iv, S), peaks=peaks[:S], refs=refs[:S])
+        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "counts", "peaks", "refs")
+        iv = []
+
+        def outs(t_max):  # the intervals are sized once the frames are known
+            ivs = self._max_intervals(split, t_max)
+            iv.append(np.zeros((max(1, S), ivs, 2), np.uint32))
+            return [o["counts"], iv[0], ivs, o["peaks"], o["refs"]]
+        out, frames = self._pcm_host(self.lib.vsyn_pcm_split_host, (_ref(split), _ref(cond), S, _ptr(rates), out_rate, fmt), S, fmt, None, outs)
+        return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), **{k: v[:S] for k, v in o.items()})
 
     def pcm_split_spectral_host(self, split, cond, spec, post, in_rates, out_rate=0):
         """vsyn_pcm_split_spectral_host over the last submit's segments (split / cond / post may be None): returns dict(rc, rows
         [total][D_out], seg_rows [S], frames [S], counts [S], intervals, peaks [S], refs [S], flags)."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
-        S = len(rates)
-        dout = _spec_dim(spec) * (1 + (post.order if post is not None else 0))
-        seg_rows = np.zeros(max(S, 1), np.uint64)
-        frames = np.zeros(max(S, 1), np.uint64)
-        peaks = np.zeros(max(S, 1), np.float32)
-        counts = np.zeros(max(1, S), np.uint32)
-        refs = np.zeros(max(1, S), np.float64)
-        st, err = Status(), C.c_char_p()
-        sp = None if split is None else C.byref(split)
-        cp = None if cond is None else C.byref(cond)
-        pp = None if post is None else C.byref(post)
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "frames", "counts", "peaks", "refs")
         ivs = 1 if split is None else self._split_sizes(split, S, rates if out_rate else None, out_rate)[1]
         iv = np.zeros((max(1, S), ivs, 2), np.uint32)
-        rc = self.lib.vsyn_pcm_split_spectral_host(self.h, sp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None, None,
-                                                   None, 0, None, None, C.byref(st), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        total = int(seg_rows[:S].sum())
-        rows = np.zeros((max(total, 1), dout), np.float32)
-        rc = self.lib.vsyn_pcm_split_spectral_host(self.h, sp, cp, C.byref(spec), pp, S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows),
-                                                   _ptr(frames), _ptr(counts), _ptr(iv), ivs, _ptr(peaks), _ptr(refs), C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], frames=frames[:S], counts=counts[:S], intervals=self._intervals(counts, iv, S),
-                    peaks=peaks[:S], refs=refs[:S], flags=st.flags)
+        r = self._rows_host(self.lib.vsyn_pcm_split_spectral_host, (_ref(split), _ref(cond), C.byref(spec), _ref(post), S, _ptr(rates), out_rate), S,
+                            _post_dim(spec, post), [o["frames"], o["counts"], iv, ivs, o["peaks"], o["refs"]], o)
+        return dict(r, intervals=self._intervals(o["counts"], iv, S))
 
     def pitch_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, d_refused=None, stream=None):
         """vsyn_pitch_device on device pointers (ints); sample_rates is a host sequence."""
-        rates = np.ascontiguousarray(sample_rates, dtype=np.uint32)
+        rates = _rates(sample_rates)
         err = C.c_char_p()
-        rc = self.lib.vsyn_pitch_device(self.h, None if spec is None else C.byref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels,
-                                        d_frames, d_rows, d_seg_row_off, d_refused, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_pitch_device(self.h, _ref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows,
+                                          d_seg_row_off, d_refused, stream, C.byref(err)), err)
 
     def pcm_pitch_host(self, spec, in_rates, out_rate=0):
         """vsyn_pcm_pitch_host over the last submit's segments: returns dict(rc, rows [total][2], seg_rows [S], refused [S], flags)."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
-        S = len(rates)
-        seg_rows = np.zeros(max(S, 1), np.uint64)
-        refused = np.zeros(max(S, 1), np.uint32)
-        st, err = Status(), C.c_char_p()
-        rc = self.lib.vsyn_pcm_pitch_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None, C.byref(st), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        total = int(seg_rows[:S].sum())
-        rows = np.zeros((max(total, 1), 2), np.float32)
-        rc = self.lib.vsyn_pcm_pitch_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows), _ptr(refused),
-                                          C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], refused=refused[:S], flags=st.flags)
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "refused")
+        return self._rows_host(self.lib.vsyn_pcm_pitch_host, (C.byref(spec), S, _ptr(rates), out_rate), S, 2, [o["refused"]], o)
 
     def fdesc_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, d_refused=None, stream=None):
         """vsyn_fdesc_device on device pointers (ints); sample_rates is a host sequence (None: NULL)."""
-        rates = None if sample_rates is None else np.ascontiguousarray(sample_rates, dtype=np.uint32)
+        rates = _rates(sample_rates)
         err = C.c_char_p()
-        rc = self.lib.vsyn_fdesc_device(self.h, None if spec is None else C.byref(spec), 0 if rates is None else len(rates),
-                                        None if rates is None else _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off,
-                                        d_refused, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_fdesc_device(self.h, _ref(spec), 0 if rates is None else len(rates), _ptr(rates), d_pcm, plane_stride, channels,
+                                          d_frames, d_rows, d_seg_row_off, d_refused, stream, C.byref(err)), err)
 
     def pcm_fdesc_host(self, spec, in_rates, out_rate=0):
         """vsyn_pcm_fdesc_host over the last submit's segments: returns dict(rc, rows [total][6], seg_rows [S], refused [S], flags)."""
-        rates = np.ascontiguousarray(in_rates, dtype=np.uint32)
-        S = len(rates)
-        seg_rows = np.zeros(max(S, 1), np.uint64)
-        refused = np.zeros(max(S, 1), np.uint32)
-        st, err = Status(), C.c_char_p()
-        rc = self.lib.vsyn_pcm_fdesc_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, None, 0, _ptr(seg_rows), None, C.byref(st), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
-        total = int(seg_rows[:S].sum())
-        rows = np.zeros((max(total, 1), 6), np.float32)
-        rc = self.lib.vsyn_pcm_fdesc_host(self.h, C.byref(spec), S, _ptr(rates), out_rate, _ptr(rows), total, _ptr(seg_rows), _ptr(refused),
-                                          C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
-        return dict(rc=rc, rows=rows[:total], seg_rows=seg_rows[:S], refused=refused[:S], flags=st.flags)
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "refused")
+        return self._rows_host(self.lib.vsyn_pcm_fdesc_host, (C.byref(spec), S, _ptr(rates), out_rate), S, 6, [o["refused"]], o)
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""
         self._vq = vq_spec.c_setup()
         err = C.c_char_p()
-        rc = self.lib.vsyn_attach_vq(self.h, C.byref(self._vq), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_attach_vq(self.h, C.byref(self._vq), C.byref(err)), err)
         self.fused_paths = self.lib.vsyn_fused_paths(self.h)  # (+ bit 8: the VQ kernel keeps this setup's value tables in LDS)
 
     def submit_host_vq(self, packets, segments, ys, vq_packets, cls, entries, residue_floats, plane_stride,
@@ -800,8 +678,7 @@ class Synth:
         rc = self.lib.vsyn_submit_host_vq(self.h, P, _ptr(packets), S, _ptr(segments), _ptr(ys), C.byref(vb), _ptr(res),
                                           residue_floats, _ptr(pcm), plane_stride, _ptr(emit), None, flags,
                                           C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(rc, err, (VSYN_OK, VSYN_ERR_STREAM))
         return dict(rc=rc, pcm=pcm, emit_len=emit, residue=res, flags=st.flags, first_bad=st.first_bad_packet)
 
     def submit_device_vq(self, P, d_packets, S, d_segments, max_seg_packets, d_ys, d_vq_packets, d_cls, num_cls, d_entries,
@@ -809,60 +686,46 @@ class Synth:
         """All pointers are raw device addresses (ints)."""
         err = C.c_char_p()
         vb = VqBatch(d_vq_packets, d_cls, d_entries, num_cls, num_entries)
-        rc = self.lib.vsyn_submit_device_vq(self.h, P, d_packets, S, d_segments, max_seg_packets, d_ys, C.byref(vb),
-                                            d_residue, d_pcm, plane_stride, d_emit, None, flags, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_submit_device_vq(self.h, P, d_packets, S, d_segments, max_seg_packets, d_ys, C.byref(vb),
+                                              d_residue, d_pcm, plane_stride, d_emit, None, flags, stream, C.byref(err)), err)
 
     def submit_device(self, P, d_packets, S, d_segments, max_seg_packets, d_ys, d_residue, d_pcm, plane_stride,
                       d_emit=None, taps=None, flags=0, stream=None):
         """All arguments are raw device addresses (ints)."""
         err = C.c_char_p()
         tp = C.byref(Taps(*taps)) if taps else None
-        rc = self.lib.vsyn_submit_device(self.h, P, d_packets, S, d_segments, max_seg_packets, d_ys, d_residue,
-                                         d_pcm, plane_stride, d_emit, tp, flags, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_submit_device(self.h, P, d_packets, S, d_segments, max_seg_packets, d_ys, d_residue,
+                                           d_pcm, plane_stride, d_emit, tp, flags, stream, C.byref(err)), err)
 
     def pcm_interleave_device(self, fmt, d_pcm, plane_stride, d_out, out_stride_frames, d_frames=None, stream=None):
         """Interleave / convert the PCM of the most recent submit_device* (raw device addresses)."""
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_interleave_device(self.h, fmt, d_pcm, plane_stride, d_out, out_stride_frames, d_frames, stream,
-                                                 C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_pcm_interleave_device(self.h, fmt, d_pcm, plane_stride, d_out, out_stride_frames, d_frames, stream,
+                                                   C.byref(err)), err)
 
     def pcm_fetch_host(self, fmt, num_segments, out_stride_frames):
         """The PCM of the most recent submit_host*, converted on the device -> ([S][out_stride_frames][C] int16 / float32, frames [S])."""
         out = np.zeros((num_segments, out_stride_frames, self.channels), np.int16 if fmt == VSYN_PCM_S16 else np.float32)
         frames = np.zeros(num_segments, np.uint32)
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_fetch_host(self.h, fmt, out.ctypes.data, out_stride_frames, frames.ctypes.data, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_pcm_fetch_host(self.h, fmt, out.ctypes.data, out_stride_frames, frames.ctypes.data, C.byref(err)), err)
         return out, frames
 
     def pcm_abs_sum_host(self, num_segments):
         """Per-(segment, channel) sum |x| of the PCM of the most recent submit_host*, computed on the device -> [S][C] float64."""
         out = np.zeros((num_segments, self.channels), np.float64)
         err = C.c_char_p()
-        rc = self.lib.vsyn_pcm_abs_sum_host(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_pcm_abs_sum_host(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(err)), err)
         return out
 
     def sync_status(self, stream=None):
         st, err = Status(), C.c_char_p()
-        rc = self.lib.vsyn_sync_status(self.h, stream, C.byref(st), C.byref(err))
-        if rc not in (VSYN_OK, VSYN_ERR_STREAM):
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_sync_status(self.h, stream, C.byref(st), C.byref(err)), err, (VSYN_OK, VSYN_ERR_STREAM))
         return st.flags, st.first_bad_packet
 
     def imdct_device(self, n, count, d_in, d_out, stream=None):
         err = C.c_char_p()
-        rc = self.lib.vsyn_imdct_device(self.h, n, count, d_in, d_out, stream, C.byref(err))
-        if rc != VSYN_OK:
-            raise VsynError(rc, (err.value or b"").decode())
+        _check(self.lib.vsyn_imdct_device(self.h, n, count, d_in, d_out, stream, C.byref(err)), err)
 
     def profile(self, on=1):
         """0/False off, 1/True long-run fused kernel, 2 mixed-block fused kernel."""

@@ -1297,85 +1297,119 @@ static int last_submit_frames(vsyn_handle* h, uint32_t S, const uint32_t* rates,
   return VSYN_OK;
 }
 
-// The trim stage of a chain: its spec and where its bounds and refs go (host, either may be NULL).
-struct TrimArgs {
+// The gate of a chain: the trim stage, or with split the split stage in its place, and where its read-backs go (host; NULL: not
+// wanted). Trim fills bounds [S][2] and refs; split fills frames (the joined ones), counts, intervals [S][stride][2] and refs.
+// gather = false (split): the intervals alone, no joined plane.
+struct Gate {
   const vsyn_pcm_trim* spec;
-  uint32_t* bounds_out;
-  double* refs_out;
-};
-
-// The split stage of a chain, in the trim stage's place: its spec and where its results go (host, each may be NULL): the joined
-// frames, the interval counts, the intervals [S][stride][2], the refs. gather = false: the intervals alone, no joined plane.
-struct SplitArgs {
-  const vsyn_pcm_trim* spec;
-  uint32_t* frames_out;
-  uint32_t* counts_out;
-  uint32_t* intervals_out;
+  bool split, gather;
+  uint32_t* frames;
+  uint32_t* bounds;
+  uint32_t* counts;
+  uint32_t* intervals;
   uint64_t stride;
-  double* refs_out;
-  bool gather;
+  double* refs;
 };
 
-// The chain on the host stream, from the last host submit's PCM to *v: with out_rate != 0 every segment resampled from rates[g] to
-// out_rate into h->rs's plane of rs_plane frames; with trim != NULL downmixed and trimmed into h->tr's mono plane (of mono_plane
-// frames when it is the last stage, of t_max frames in front of the conditioning), the bounds and refs on their way to the host;
-// with split != NULL (never with a trim) downmixed and joined into h->sl's mono plane in the same way, its results on their way;
-// with cond != NULL conditioned into h->cd's mono plane of mono_plane frames, the peaks on their way to peaks_out. t_max bounds
-// every segment's frames; zero clears the last plane first: zeros past each segment's frames. Caller holds h->mu and has run
-// rs_check / trim_check / cond_check; its checks of its own buffers sit between last_submit_frames and this.
-static int pcm_chain(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, uint64_t rs_plane, const vsyn_pcm_cond* cond,
-                     uint64_t mono_plane, uint64_t t_max, bool zero, float* peaks_out, PcmView* v, const char** err,
-                     const TrimArgs* trim = nullptr, const SplitArgs* split = nullptr) {
-  const uint32_t C = h->H.channels;
-  hipStream_t hs = h->host_stream;
-  *v = PcmView{h->st_pcm.p, h->last_host_plane, C, h->ws_seg[h->last_wb].p, nullptr};
-  if (out_rate) {
-    const size_t n = (size_t)S * C * rs_plane;
-    HIPCHK(h->rs.pcm.ensure(n + 1));
-    if (zero && !cond && !trim && !split) HIPCHK(hipMemsetAsync(h->rs.pcm.p, 0, sizeof(float) * n, hs));
-    if (int rc = rs_launch(h->rs, h->device, S, rates, out_rate, v->pcm, v->plane, C, nullptr, v->si, h->rs.pcm.p, rs_plane, nullptr, hs, err)) return rc;
-    *v = PcmView{h->rs.pcm.p, rs_plane, C, nullptr, h->rs.outF.p};
+// The specs of the stages a chain has (gate, cond: NULL, out_rate: 0 when it has none), in the order every entry checks them.
+static int chain_check(const Gate* gate, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, uint32_t out_rate, const char** err) {
+  if (gate)
+    if (int rc = trim_check(gate->spec, err)) return rc;
+  if (cond)
+    if (int rc = cond_check(cond, err)) return rc;
+  return out_rate ? rs_check(S, rates, out_rate, err) : VSYN_OK;
+}
+
+// The rates the stage behind the chain sees: out_rate for every resampled segment, else the caller's; 0 skips a segment.
+static std::vector<uint32_t> stage_rates(uint32_t S, const uint32_t* rates, uint32_t out_rate) {
+  std::vector<uint32_t> r(S, 0u);
+  for (uint32_t g = 0; g < S && rates; ++g) r[g] = out_rate && rates[g] ? out_rate : rates[g];
+  return r;
+}
+
+// The rows of a framing (frame length n, hop, centred or not) over each segment's frames T[g], none where rates[g] = 0: into
+// seg_rows, their sum and their maximum. A segment of fewer than min_rows rows gets none.
+static void count_rows(uint32_t n, uint32_t hop, bool center, uint32_t S, const uint32_t* rates, const uint64_t* T, uint64_t min_rows,
+                       uint64_t* seg_rows, uint64_t* total, uint64_t* f_max) {
+  *total = *f_max = 0;
+  for (uint32_t g = 0; g < S; ++g) {
+    seg_rows[g] = rates[g] ? spec_num_frames(n, hop, center, T[g]) : 0;
+    if (seg_rows[g] < min_rows) seg_rows[g] = 0;
+    *total += seg_rows[g];
+    *f_max = std::max(*f_max, seg_rows[g]);
   }
-  if (trim) {  // the next stage reads the trimmed mono plane as 1-channel PCM, with the frames the stage wrote
-    const uint64_t tr_plane = cond ? std::max<uint64_t>(t_max, 1) : mono_plane;
-    const size_t n = (size_t)S * tr_plane;
-    HIPCHK(h->tr.pcm.ensure(n + 1));
-    if (zero && !cond) HIPCHK(hipMemsetAsync(h->tr.pcm.p, 0, sizeof(float) * n, hs));
-    if (int rc = trim_launch(h->tr, h->device, trim->spec, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, h->tr.pcm.p, tr_plane, nullptr,
-                             nullptr, nullptr, nullptr, 0, hs, err))
-      return rc;
-    if (int rc = trim_fetch_bounds(h->tr, S, trim->bounds_out, trim->refs_out, hs, err)) return rc;
-    *v = PcmView{h->tr.pcm.p, tr_plane, 1u, nullptr, h->tr.frames.p};
-  }
-  if (split) {  // the next stage reads the joined mono plane as 1-channel PCM, with the frames the stage wrote
-    const uint64_t sl_plane = cond ? std::max<uint64_t>(t_max, 1) : mono_plane;
-    const size_t n = (size_t)S * sl_plane;
-    float* joined = nullptr;
-    if (split->gather) {
-      HIPCHK(h->sl.e.pcm.ensure(n + 1));
-      if (zero && !cond) HIPCHK(hipMemsetAsync(h->sl.e.pcm.p, 0, sizeof(float) * n, hs));
-      joined = h->sl.e.pcm.p;
-    }
-    uint64_t ws_stride = 0;
-    if (int rc = split_launch(h->sl, h->device, split->spec, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, joined, sl_plane, nullptr, nullptr,
-                              nullptr, 0, &ws_stride, nullptr, nullptr, 0, hs, err))
-      return rc;
-    if (int rc = split_fetch(h->sl, S, split->counts_out, split->intervals_out, split->stride, ws_stride, split->refs_out, hs, err)) return rc;
-    if (split->frames_out) HIPCHK(hipMemcpyAsync(split->frames_out, h->sl.e.frames.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
-    *v = PcmView{joined, sl_plane, 1u, nullptr, h->sl.e.frames.p};
-  }
-  if (cond) {  // the next stage reads the conditioned mono plane as 1-channel PCM, with the frames the stage wrote
-    const size_t n = (size_t)S * mono_plane;
-    HIPCHK(h->cd.pcm.ensure(n + 1));
-    if (zero) HIPCHK(hipMemsetAsync(h->cd.pcm.p, 0, sizeof(float) * n, hs));
-    if (int rc = cond_launch(h->cd, h->device, cond, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, h->cd.pcm.p, mono_plane, nullptr, hs, err)) return rc;
-    if (int rc = cond_fetch_peaks(h->cd, cond, S, peaks_out, hs, err)) return rc;
-    *v = PcmView{h->cd.pcm.p, mono_plane, 1u, nullptr, h->cd.frames.p};
-  }
+}
+
+// intervals must hold what a segment of t_max frames can have
+static int split_check_stride(const Gate& g, uint64_t t_max, const char** err) {
+  const uint64_t need = split_max_intervals(t_max, g.spec->frame_length, g.spec->hop_length);
+  if (g.intervals && g.stride < need)
+    return fail(err, VSYN_ERR_INVALID, "intervals_stride %llu below %llu intervals", (unsigned long long)g.stride, (unsigned long long)need);
   return VSYN_OK;
 }
 
-// The end of a PCM host form: the view's planes to out as they are (VSYN_PCM_F32: the chain cleared them first), or interleaved
+// A chain starts at the last host submit's PCM and advances *v one step per stage, all on the host stream. Every step writes its
+// workspace's plane of `plane` frames per segment and channel; clear zeroes that plane first (the step whose plane goes to the
+// caller as float: zeros past each segment's frames). t_max bounds every segment's frames. Caller holds h->mu, has run chain_check
+// and, between last_submit_frames and the first step, the checks of its own buffers.
+static PcmView last_submit_view(vsyn_handle* h) { return PcmView{h->st_pcm.p, h->last_host_plane, h->H.channels, h->ws_seg[h->last_wb].p, nullptr}; }
+
+// every segment from rates[g] to out_rate, into h->rs's planes
+static int step_resample(vsyn_handle* h, uint32_t S, const uint32_t* rates, uint32_t out_rate, uint64_t plane, bool clear, PcmView* v, const char** err) {
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * v->C * plane;
+  HIPCHK(h->rs.pcm.ensure(n + 1));
+  if (clear) HIPCHK(hipMemsetAsync(h->rs.pcm.p, 0, sizeof(float) * n, hs));
+  if (int rc = rs_launch(h->rs, h->device, S, rates, out_rate, v->pcm, v->plane, v->C, nullptr, v->si, h->rs.pcm.p, plane, nullptr, hs, err)) return rc;
+  *v = PcmView{h->rs.pcm.p, plane, v->C, nullptr, h->rs.outF.p};
+  return VSYN_OK;
+}
+
+// downmixed and trimmed into h->tr's mono plane, or split and joined into h->sl's; g's read-backs on their way to the host (the
+// caller waits before it reads them). The next stage reads the mono plane as 1-channel PCM, with the frames the stage wrote.
+static int step_gate(vsyn_handle* h, uint32_t S, const Gate& g, uint64_t plane, uint64_t t_max, bool clear, PcmView* v, const char** err) {
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * plane;
+  if (!g.split) {
+    HIPCHK(h->tr.pcm.ensure(n + 1));
+    if (clear) HIPCHK(hipMemsetAsync(h->tr.pcm.p, 0, sizeof(float) * n, hs));
+    if (int rc = trim_launch(h->tr, h->device, g.spec, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, h->tr.pcm.p, plane, nullptr, nullptr,
+                             nullptr, nullptr, 0, hs, err))
+      return rc;
+    if (int rc = trim_fetch_bounds(h->tr, S, g.bounds, g.refs, hs, err)) return rc;
+    *v = PcmView{h->tr.pcm.p, plane, 1u, nullptr, h->tr.frames.p};
+    return VSYN_OK;
+  }
+  float* joined = nullptr;
+  if (g.gather) {
+    HIPCHK(h->sl.e.pcm.ensure(n + 1));
+    if (clear) HIPCHK(hipMemsetAsync(h->sl.e.pcm.p, 0, sizeof(float) * n, hs));
+    joined = h->sl.e.pcm.p;
+  }
+  uint64_t ws_stride = 0;
+  if (int rc = split_launch(h->sl, h->device, g.spec, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, joined, plane, nullptr, nullptr, nullptr,
+                            0, &ws_stride, nullptr, nullptr, 0, hs, err))
+    return rc;
+  if (int rc = split_fetch(h->sl, S, g.counts, g.intervals, g.stride, ws_stride, g.refs, hs, err)) return rc;
+  if (g.frames) HIPCHK(hipMemcpyAsync(g.frames, h->sl.e.frames.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
+  *v = PcmView{joined, plane, 1u, nullptr, h->sl.e.frames.p};
+  return VSYN_OK;
+}
+
+// conditioned into h->cd's mono plane, the peaks on their way to peaks_out; read on as the gate's plane is
+static int step_condition(vsyn_handle* h, uint32_t S, const vsyn_pcm_cond* cond, uint64_t plane, uint64_t t_max, bool clear, float* peaks_out,
+                          PcmView* v, const char** err) {
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * plane;
+  HIPCHK(h->cd.pcm.ensure(n + 1));
+  if (clear) HIPCHK(hipMemsetAsync(h->cd.pcm.p, 0, sizeof(float) * n, hs));
+  if (int rc = cond_launch(h->cd, h->device, cond, S, v->pcm, v->plane, v->C, v->d_frames, v->si, t_max, h->cd.pcm.p, plane, nullptr, hs, err)) return rc;
+  if (int rc = cond_fetch_peaks(h->cd, cond, S, peaks_out, hs, err)) return rc;
+  *v = PcmView{h->cd.pcm.p, plane, 1u, nullptr, h->cd.frames.p};
+  return VSYN_OK;
+}
+
+// The end of a PCM host form: the view's planes to out as they are (VSYN_PCM_F32: the last step cleared them first), or interleaved
 // and converted into s16 (vsyn_pcm_interleave_device's conversion, zeros past each segment's frames) and that; then the call's one wait.
 static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format, DevBuf<int16_t>& s16, void* out, const char** err) {
   hipStream_t hs = h->host_stream;
@@ -1390,6 +1424,54 @@ static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format
     HIPCHK(hipMemcpyAsync(out, s16.p, sizeof(int16_t) * n, hipMemcpyDeviceToHost, hs));
   }
   HIPCHK(hipStreamSynchronize(hs));
+  return VSYN_OK;
+}
+
+// The PCM host forms (vsyn_pcm_resample_host, vsyn_pcm_condition_host, vsyn_pcm_trim_host, vsyn_pcm_split_host): the stages present
+// (gate, cond: NULL, out_rate: 0 for none), the last one into a plane of the caller's stride, the ones in front of it into planes
+// as long as the longest segment; that plane to out, and the frames behind the gate to frames_out.
+static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, uint32_t out_rate, int format,
+                        void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err) {
+  if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
+  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
+  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
+  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
+  // the lock covers the whole call: the stages' workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t t_max;
+  if (int rc = last_submit_frames(h, S, rates, out_rate, frames_out, &t_max, err)) return rc;
+  if (!out || S == 0) return VSYN_OK;
+  if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
+                                             (unsigned long long)out_stride_frames, (unsigned long long)t_max);
+  if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
+  std::vector<uint32_t> bounds(gate ? 2u * (size_t)S : 0), joined(gate ? S : 0);
+  Gate g{};
+  if (gate) {
+    g = *gate;
+    if (g.split)
+      if (int rc = split_check_stride(g, t_max, err)) return rc;
+    g.frames = joined.data();
+    g.bounds = bounds.data();
+  }
+  const bool f32 = format == VSYN_PCM_F32;
+  const uint64_t inner = std::max<uint64_t>(t_max, 1);
+  PcmView v = last_submit_view(h);
+  DevBuf<int16_t>* s16 = &h->rs.s16;  // the last stage's
+  if (out_rate)
+    if (int rc = step_resample(h, S, rates, out_rate, gate || cond ? inner : out_stride_frames, f32 && !gate && !cond, &v, err)) return rc;
+  if (gate) {
+    if (int rc = step_gate(h, S, g, cond ? inner : out_stride_frames, t_max, f32 && !cond, &v, err)) return rc;
+    s16 = g.split ? &h->sl.e.s16 : &h->tr.s16;
+  }
+  if (cond) {
+    if (int rc = step_condition(h, S, cond, out_stride_frames, t_max, f32, peaks_out, &v, err)) return rc;
+    s16 = &h->cd.s16;
+  }
+  if (int rc = pcm_copy_out(h, v, S, format, *s16, out, err)) return rc;
+  if (gate) {
+    for (uint32_t s = 0; s < S; ++s) frames_out[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
+    if (gate->bounds) memcpy(gate->bounds, bounds.data(), sizeof(uint32_t) * bounds.size());
+  }
   return VSYN_OK;
 }
 
@@ -1416,176 +1498,133 @@ static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   return sync_status_into(h, status, err);
 }
 
-// vsyn_pcm_spectral_host, and with out_rate != 0 vsyn_pcm_resample_spectral_host: the rows of the last host submit's PCM, each
-// segment resampled from rates[g] to out_rate first when out_rate != 0, then conditioned into a mono plane when cond != NULL.
-static int pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S,
-                             const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
-                             vsyn_status* status, const char** err, const vsyn_pcm_cond* cond = nullptr, float* peaks_out = nullptr) {
+// The spectral host forms: the rows of the last host submit's PCM behind the stages present (gate, cond, post: NULL, out_rate: 0
+// for none). Without a gate the rows are counted on the host and nothing runs for a NULL rows. With one the chain runs up to the
+// gated plane and waits once for the gate's read-backs, the row counts come from those (frames_out: the frames behind the gate),
+// and conditioning, spectral rows and the post stage follow on the gated plane.
+static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post,
+                         uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                         uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   status_reset(status);
-  int rc;
-  if (cond) {
-    rc = cond_check(cond, err);
-    if (rc) return rc;
-  }
-  std::vector<uint32_t> sp_rates;  // resampled: the spectral pass sees every resampled segment at out_rate
-  if (out_rate) {
-    rc = rs_check(S, rates, out_rate, err);
-    if (rc) return rc;
-    sp_rates.resize(S);
-    for (uint32_t g = 0; g < S; ++g) sp_rates[g] = rates[g] ? out_rate : 0u;
-  }
-  const uint32_t* spec_rates = out_rate ? sp_rates.data() : rates;
-  rc = spec_check(spec, S, spec_rates, err);
-  if (rc) return rc;
+  if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
+  std::vector<uint32_t> sp_rates = stage_rates(S, rates, out_rate);
+  // (NULL rates without a gate are spec_check's to refuse; behind a gate they skip every segment)
+  if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err)) return rc;
   if (post) {
-    rc = spec_post_check(spec, post, err);
-    if (rc) return rc;
+    if (int rc = spec_post_check(spec, post, err)) return rc;
     if (!post_on(post)) post = nullptr;  // off: the rows of the spectral pass, bit for bit
   }
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
   if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
-  // the lock covers the whole call: the spectral, resample and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
+  if (gate && gate->bounds) memset(gate->bounds, 0, sizeof(uint32_t) * 2u * S);
+  if (gate && gate->refs) memset(gate->refs, 0, sizeof(double) * S);
+  // the lock covers the whole call: the stages' workspaces are the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
   std::vector<uint64_t> T(S);
-  uint64_t total = 0, f_max = 0, t_max;
-  rc = last_submit_frames(h, S, rates, out_rate, T.data(), &t_max, err);
-  if (rc) return rc;
+  uint64_t total, f_max, t_max;
+  if (int rc = last_submit_frames(h, S, rates, out_rate, T.data(), &t_max, err)) return rc;
+  if (gate && S == 0) return VSYN_OK;
+  if (gate && gate->split)
+    if (int rc = split_check_stride(*gate, t_max, err)) return rc;
   t_max = std::max<uint64_t>(t_max, 1);
-  const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    const uint64_t f = spec_rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, center, T[g]) : 0;
-    seg_rows[g] = f;
-    total += f;
-    f_max = std::max(f_max, f);
-  }
-  if (post) {
-    rc = post_check_rows(post, S, seg_rows, err);
-    if (rc) return rc;
-  }
-  if (!rows || total == 0) return VSYN_OK;
-  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
-  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
-  hipStream_t hs = h->host_stream;
-  PcmView v;  // the spectral pass reads the synthesis PCM with the last submit's SegInfo, or what the chain made of it
-  rc = pcm_chain(h, S, rates, out_rate, t_max, cond, t_max, t_max, false, peaks_out, &v, err);
-  if (rc) return rc;
-  return spectral_rows_out(h, spec, post, S, spec_rates, v, seg_rows, f_max, total, rows, status, err);
-}
-
-// What the split forms of the host entries hand back where the trim forms hand back bounds (host, each may be NULL): the joined
-// frames, the interval counts, the intervals [S][stride][2].
-struct SplitOut {
-  uint64_t* frames_out;
-  uint32_t* counts_out;
-  uint32_t* intervals_out;
-  uint64_t stride;
-};
-
-// intervals_out must hold what a segment of t_max frames can have
-static int split_check_stride(const vsyn_pcm_trim* trim, const SplitOut* so, uint64_t t_max, const char** err) {
-  const uint64_t need = split_max_intervals(t_max, trim->frame_length, trim->hop_length);
-  if (so->intervals_out && so->stride < need)
-    return fail(err, VSYN_ERR_INVALID, "intervals_stride %llu below %llu intervals", (unsigned long long)so->stride, (unsigned long long)need);
-  return VSYN_OK;
-}
-
-// vsyn_pcm_trim_spectral_host with a trim: the chain up to the trimmed plane, the bounds back to the host (the later stages take
-// their row counts from there), then conditioning, spectral rows and the post stage on the trimmed plane. so != NULL:
-// vsyn_pcm_split_spectral_host, the joined plane in the trimmed one's place and its frames, counts and intervals back.
-static int pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
-                                  const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows,
-                                  uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out, double* refs_out,
-                                  vsyn_status* status, const char** err, const SplitOut* so = nullptr) {
-  status_reset(status);
-  int rc = trim_check(trim, err);
-  if (rc) return rc;
-  if (cond) {
-    rc = cond_check(cond, err);
-    if (rc) return rc;
-  }
-  std::vector<uint32_t> sp_rates(S);  // the rates the spectral pass sees: 0 skips a segment
-  if (out_rate) {
-    rc = rs_check(S, rates, out_rate, err);
-    if (rc) return rc;
-    for (uint32_t g = 0; g < S; ++g) sp_rates[g] = rates[g] ? out_rate : 0u;
-  } else {
-    for (uint32_t g = 0; g < S; ++g) sp_rates[g] = rates ? rates[g] : 0u;
-  }
-  rc = spec_check(spec, S, sp_rates.data(), err);
-  if (rc) return rc;
-  if (post) {
-    rc = spec_post_check(spec, post, err);
-    if (rc) return rc;
-    if (!post_on(post)) post = nullptr;
-  }
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
-  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
-  if (bounds_out) memset(bounds_out, 0, sizeof(uint32_t) * 2u * S);
-  if (refs_out) memset(refs_out, 0, sizeof(double) * S);
-  std::lock_guard<std::mutex> lk(h->mu);
-  std::vector<uint64_t> T(S);
-  uint64_t t_max;
-  rc = last_submit_frames(h, S, rates, out_rate, T.data(), &t_max, err);
-  if (rc) return rc;
-  if (S == 0) return VSYN_OK;
-  if (so) {
-    rc = split_check_stride(trim, so, t_max, err);
-    if (rc) return rc;
-  }
-  t_max = std::max<uint64_t>(t_max, 1);
-  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  hipStream_t hs = h->host_stream;
-  std::vector<uint32_t> bounds(2u * (size_t)S);  // split: (0, joined frames)
-  std::vector<double> refs(S);
-  const TrimArgs ta{trim, bounds.data(), refs.data()};
-  PcmView v;
-  if (so) {
-    std::vector<uint32_t> joined(S);
-    const SplitArgs sa{trim, joined.data(), so->counts_out, so->intervals_out, so->stride, refs.data(), true};
-    rc = pcm_chain(h, S, rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err, nullptr, &sa);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(hs));  // the one read-back of this form: the joined frames, with the counts, intervals and refs
-    for (uint32_t g = 0; g < S; ++g) {
-      bounds[2u * g] = 0u;
-      bounds[2u * g + 1u] = joined[g];
-      if (so->frames_out) so->frames_out[g] = joined[g];
+  if (gate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  PcmView v = last_submit_view(h);  // the spectral pass reads the synthesis PCM with the last submit's SegInfo, or what the chain made of it
+  if (gate) {
+    std::vector<uint32_t> bounds(2u * (size_t)S), joined(S);
+    std::vector<double> refs(S);
+    Gate g = *gate;
+    g.frames = joined.data();
+    g.bounds = bounds.data();
+    g.refs = refs.data();
+    if (out_rate)
+      if (int rc = step_resample(h, S, rates, out_rate, t_max, false, &v, err)) return rc;
+    if (int rc = step_gate(h, S, g, t_max, t_max, false, &v, err)) return rc;
+    HIPCHK(hipStreamSynchronize(h->host_stream));  // the one read-back of a gated form: the bounds or the joined frames, with the refs (counts, intervals)
+    for (uint32_t s = 0; s < S; ++s) {
+      T[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
+      if (frames_out) frames_out[s] = T[s];
+      if (!std::isfinite(refs[s])) sp_rates[s] = 0u;
     }
-  } else {
-    rc = pcm_chain(h, S, rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err, &ta);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(hs));  // the one read-back of this form: S * 8 bytes of bounds (and the refs)
+    if (gate->bounds) memcpy(gate->bounds, bounds.data(), sizeof(uint32_t) * bounds.size());
+    if (gate->refs) memcpy(gate->refs, refs.data(), sizeof(double) * S);
   }
-  if (bounds_out) memcpy(bounds_out, bounds.data(), sizeof(uint32_t) * bounds.size());
-  if (refs_out) memcpy(refs_out, refs.data(), sizeof(double) * S);
   const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
-  uint64_t total = 0, f_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    uint64_t f = sp_rates[g] && std::isfinite(refs[g]) ? spec_num_frames(spec->n_fft, spec->hop_length, center, bounds[2u * g + 1u] - bounds[2u * g]) : 0;
-    if (post && post->order && f && f < post->width) f = 0;  // trimmed below the delta width: fails alone
-    if (!f) sp_rates[g] = 0u;
-    seg_rows[g] = f;
-    total += f;
-    f_max = std::max(f_max, f);
+  count_rows(spec->n_fft, spec->hop_length, center, S, sp_rates.data(), T.data(), gate && post && post->order ? post->width : 0u, seg_rows, &total,
+             &f_max);
+  if (gate) {  // gated to nothing, or below the delta width: that segment fails alone
+    for (uint32_t s = 0; s < S; ++s)
+      if (!seg_rows[s]) sp_rates[s] = 0u;
+  } else if (post) {  // ungated, a segment below the delta width refuses the call
+    if (int rc = post_check_rows(post, S, seg_rows, err)) return rc;
   }
   if (!rows || total == 0) return VSYN_OK;
   if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
-  if (cond) {
-    HIPCHK(h->cd.pcm.ensure((size_t)S * t_max + 1));
-    rc = cond_launch(h->cd, h->device, cond, S, v.pcm, v.plane, 1u, v.d_frames, nullptr, t_max, h->cd.pcm.p, t_max, nullptr, hs, err);
-    if (rc) return rc;
-    rc = cond_fetch_peaks(h->cd, cond, S, peaks_out, hs, err);
-    if (rc) return rc;
-    v = PcmView{h->cd.pcm.p, t_max, 1u, nullptr, h->cd.frames.p};
+  if (!gate && out_rate) {
+    if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
+    if (int rc = step_resample(h, S, rates, out_rate, t_max, false, &v, err)) return rc;
   }
+  if (cond)
+    if (int rc = step_condition(h, S, cond, t_max, t_max, false, peaks_out, &v, err)) return rc;
   return spectral_rows_out(h, spec, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err);
 }
 
-static int pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
-                         uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
-                         float* peaks_out, double* refs_out, const char** err, const SplitOut* so = nullptr);
+// vsyn_pcm_split_intervals_host: the chain up to the split stage's marks; nothing but the frames in front of the stage, the
+// counts, the intervals and the refs comes back.
+static int split_intervals_host(vsyn_handle* h, const Gate& g, uint32_t S, const uint32_t* rates, uint32_t out_rate, uint64_t* frames_out,
+                                const char** err) {
+  if (int rc = chain_check(&g, nullptr, S, rates, out_rate, err)) return rc;
+  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
+  // the lock covers the whole call: the resample and split workspaces are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t t_max;
+  if (int rc = last_submit_frames(h, S, rates, out_rate, frames_out, &t_max, err)) return rc;
+  if (!g.counts || S == 0) return VSYN_OK;
+  if (int rc = split_check_stride(g, t_max, err)) return rc;
+  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  PcmView v = last_submit_view(h);  // resampled into a plane as long as the longest segment, marked there
+  if (out_rate)
+    if (int rc = step_resample(h, S, rates, out_rate, std::max<uint64_t>(t_max, 1), false, &v, err)) return rc;
+  if (int rc = step_gate(h, S, g, 0, t_max, false, &v, err)) return rc;
+  HIPCHK(hipStreamSynchronize(h->host_stream));
+  return VSYN_OK;
+}
+
+static bool pitch_center(const vsyn_pitch_spec* spec) { return (spec->options & VSYN_PITCH_CENTER) != 0; }
+static bool fdesc_center(const vsyn_fdesc_spec* spec) { return (spec->options & VSYN_FDESC_CENTER) != 0; }
+
+// The host forms whose rows come from a framing of the PCM as the resampler leaves it (vsyn_pcm_pitch_host, vsyn_pcm_fdesc_host),
+// behind their spec checks: frames of n samples every hop, cols columns a row; launch(v, f_max, stream) runs the stage's kernels
+// over the view into d_rows and d_refused. rates: what the stage sees (stage_rates, or the caller's own).
+template <class Launch>
+static int framed_rows_host(vsyn_handle* h, uint32_t n, uint32_t hop, bool center, uint32_t cols, DevBuf<float>& d_rows, DevBuf<uint32_t>& d_refused,
+                            Launch launch, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, const uint32_t* rates, float* rows,
+                            uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status, const char** err) {
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
+  if (refused_out) memset(refused_out, 0, sizeof(uint32_t) * S);
+  // the lock covers the whole call: the resample workspace and the stage's are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T(S);
+  uint64_t total, f_max, t_max;
+  if (int rc = last_submit_frames(h, S, in_rates, out_rate, T.data(), &t_max, err)) return rc;
+  t_max = std::max<uint64_t>(t_max, 1);
+  count_rows(n, hop, center, S, rates, T.data(), 0, seg_rows, &total, &f_max);
+  if (!rows || S == 0) return VSYN_OK;
+  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
+  hipStream_t hs = h->host_stream;
+  PcmView v = last_submit_view(h);  // the synthesis PCM with the last submit's SegInfo, or the resampler's planes with its frames
+  if (out_rate)
+    if (int rc = step_resample(h, S, in_rates, out_rate, t_max, false, &v, err)) return rc;
+  HIPCHK(d_rows.ensure(total * cols + 1));
+  HIPCHK(d_refused.ensure(S));
+  if (int rc = launch(v, f_max, hs)) return rc;
+  if (total) HIPCHK(hipMemcpyAsync(rows, d_rows.p, sizeof(float) * total * cols, hipMemcpyDeviceToHost, hs));
+  if (refused_out) HIPCHK(hipMemcpyAsync(refused_out, d_refused.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
+  return sync_status_into(h, status, err);
+}
 
 extern "C" {
 
@@ -1622,35 +1661,20 @@ int vsyn_resample_device(vsyn_handle* h, uint32_t S, const uint32_t* in_rates, u
 int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, int format, void* out,
                            uint64_t out_stride_frames, uint64_t* frames_out, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-  int rc = rs_check(S, in_rates, out_rate, err);
-  if (rc) return rc;
-  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
-  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
-  // the lock covers the whole call: the resample workspace is the handle's, and the PCM must stay that of the last submit
-  std::lock_guard<std::mutex> lk(h->mu);
-  uint64_t t_max;
-  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
-  if (rc) return rc;
-  if (!out || S == 0) return VSYN_OK;
-  if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
-                                             (unsigned long long)out_stride_frames, (unsigned long long)t_max);
-  if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
-  PcmView v;
-  rc = pcm_chain(h, S, in_rates, out_rate, out_stride_frames, nullptr, 0, t_max, format == VSYN_PCM_F32, nullptr, &v, err);
-  if (rc) return rc;
-  return pcm_copy_out(h, v, S, format, h->rs.s16, out, err);
+  if (!out_rate) return rs_check(S, in_rates, out_rate, err);  // (0 would mean no resampling to the shared body)
+  return pcm_out_host(h, nullptr, nullptr, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, nullptr, err);
 }
 
 int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
                            uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
-  return pcm_spectral_host(h, spec, nullptr, S, sample_rates, 0, rows, rows_capacity, seg_rows, status, err);
+  return spectral_host(h, nullptr, nullptr, spec, nullptr, S, sample_rates, 0, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
 }
 
 int vsyn_pcm_spectral_post_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S,
                                 const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
                                 vsyn_status* status, const char** err) {
   if (!post) return fail(err, VSYN_ERR_INVALID, "spectral post spec is NULL");
-  return pcm_spectral_host(h, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err);
+  return spectral_host(h, nullptr, nullptr, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
 }
 
 int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
@@ -1659,14 +1683,14 @@ int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* sp
     status_reset(status);
     return rs_check(S, in_rates, out_rate, err);
   }
-  return pcm_spectral_host(h, spec, nullptr, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err);
+  return spectral_host(h, nullptr, nullptr, spec, nullptr, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
 }
 
 int vsyn_pcm_cond_spectral_host(vsyn_handle* h, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post,
                                 uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
                                 uint64_t* seg_rows, float* peaks_out, vsyn_status* status, const char** err) {
   if (!h) return cond_no_handle(err);
-  return pcm_spectral_host(h, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, status, err, cond, peaks_out);
+  return spectral_host(h, nullptr, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status, err);
 }
 
 int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t S, const float* d_pcm, uint64_t plane_stride,
@@ -1685,31 +1709,12 @@ int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_
                      (hipStream_t)hip_stream, err);
 }
 
+// A PCM host form without a gate is vsyn_pcm_condition_host, which needs its spec.
 int vsyn_pcm_condition_host(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, int format,
                             void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err) {
   if (!h) return cond_no_handle(err);
-  int rc = cond_check(cond, err);
-  if (rc) return rc;
-  if (out_rate) {
-    rc = rs_check(S, in_rates, out_rate, err);
-    if (rc) return rc;
-  }
-  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
-  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
-  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
-  // the lock covers the whole call: the resample and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
-  std::lock_guard<std::mutex> lk(h->mu);
-  uint64_t t_max;
-  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
-  if (rc) return rc;
-  if (!out || S == 0) return VSYN_OK;
-  if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
-                                             (unsigned long long)out_stride_frames, (unsigned long long)t_max);
-  if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
-  PcmView v;  // resampled into a plane as long as the longest segment, conditioned into the caller's stride
-  rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err);
-  if (rc) return rc;
-  return pcm_copy_out(h, v, S, format, h->cd.s16, out, err);
+  if (!cond) return cond_check(cond, err);
+  return pcm_out_host(h, nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
 }
 
 uint64_t vsyn_pcm_trim_num_frames(const vsyn_pcm_trim* trim, uint64_t frames) {
@@ -1737,74 +1742,18 @@ int vsyn_pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm
                        uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
                        float* peaks_out, double* refs_out, const char** err) {
   if (!trim) return vsyn_pcm_condition_host(h, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
-  return pcm_trim_host(h, trim, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, bounds_out, peaks_out, refs_out, err);
-}
-
-}  // extern "C"
-
-// vsyn_pcm_trim_host with a trim; so != NULL: vsyn_pcm_split_host, the joined plane in the trimmed one's place, its counts and
-// intervals back.
-static int pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
-                         uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
-                         float* peaks_out, double* refs_out, const char** err, const SplitOut* so) {
   if (!h) return cond_no_handle(err);
-  int rc = trim_check(trim, err);
-  if (rc) return rc;
-  if (cond) {
-    rc = cond_check(cond, err);
-    if (rc) return rc;
-  }
-  if (out_rate) {
-    rc = rs_check(S, in_rates, out_rate, err);
-    if (rc) return rc;
-  }
-  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
-  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
-  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
-  // the lock covers the whole call: the resample, trim and conditioning workspaces are the handle's, and the PCM must stay that of the last submit
-  std::lock_guard<std::mutex> lk(h->mu);
-  uint64_t t_max;
-  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
-  if (rc) return rc;
-  if (!out || S == 0) return VSYN_OK;
-  if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
-                                             (unsigned long long)out_stride_frames, (unsigned long long)t_max);
-  if (out_stride_frames > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "out_stride_frames must be below 2^32");
-  PcmView v;  // resampled into a plane as long as the longest segment, trimmed or joined, conditioned into the caller's stride
-  if (so) {
-    rc = split_check_stride(trim, so, t_max, err);
-    if (rc) return rc;
-    std::vector<uint32_t> joined(S);
-    const SplitArgs sa{trim, joined.data(), so->counts_out, so->intervals_out, so->stride, refs_out, true};
-    rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err,
-                   nullptr, &sa);
-    if (rc) return rc;
-    rc = pcm_copy_out(h, v, S, format, cond ? h->cd.s16 : h->sl.e.s16, out, err);
-    if (rc) return rc;
-    for (uint32_t g = 0; g < S; ++g) frames_out[g] = joined[g];
-    return VSYN_OK;
-  }
-  std::vector<uint32_t> bounds(2u * (size_t)S);
-  const TrimArgs ta{trim, bounds.data(), refs_out};
-  rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), cond, out_stride_frames, t_max, format == VSYN_PCM_F32, peaks_out, &v, err, &ta);
-  if (rc) return rc;
-  rc = pcm_copy_out(h, v, S, format, cond ? h->cd.s16 : h->tr.s16, out, err);
-  if (rc) return rc;
-  for (uint32_t g = 0; g < S; ++g) frames_out[g] = bounds[2u * g + 1u] - bounds[2u * g];
-  if (bounds_out) memcpy(bounds_out, bounds.data(), sizeof(uint32_t) * bounds.size());
-  return VSYN_OK;
+  const Gate g{trim, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return pcm_out_host(h, &g, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
 }
-
-extern "C" {
 
 int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
                                 const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
                                 uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out, double* refs_out,
                                 vsyn_status* status, const char** err) {
-  if (!trim) return vsyn_pcm_cond_spectral_host(h, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, peaks_out, status, err);
   if (!h) return cond_no_handle(err);
-  return pcm_trim_spectral_host(h, trim, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, bounds_out, peaks_out, refs_out,
-                                status, err);
+  const Gate g{trim, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return spectral_host(h, trim ? &g : nullptr, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status, err);
 }
 
 uint64_t vsyn_pcm_split_max_intervals(const vsyn_pcm_trim* trim, uint64_t frames) {
@@ -1833,53 +1782,30 @@ int vsyn_pcm_split_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pc
                         uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* counts_out,
                         uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out, const char** err) {
   if (!trim) return vsyn_pcm_condition_host(h, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
-  const SplitOut so{nullptr, counts_out, intervals_out, intervals_stride};
-  return pcm_trim_host(h, trim, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, nullptr, peaks_out, refs_out, err, &so);
+  if (!h) return cond_no_handle(err);
+  const Gate g{trim, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out};
+  return pcm_out_host(h, &g, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
 }
 
 int vsyn_pcm_split_intervals_host(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
                                   uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
                                   double* refs_out, const char** err) {
   if (!h) return cond_no_handle(err);
-  int rc = trim_check(trim, err);
-  if (rc) return rc;
-  if (out_rate) {
-    rc = rs_check(S, in_rates, out_rate, err);
-    if (rc) return rc;
-  }
-  if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
-  // the lock covers the whole call: the resample and split workspaces are the handle's, and the PCM must stay that of the last submit
-  std::lock_guard<std::mutex> lk(h->mu);
-  uint64_t t_max;
-  rc = last_submit_frames(h, S, in_rates, out_rate, frames_out, &t_max, err);
-  if (rc) return rc;
-  if (!counts_out || S == 0) return VSYN_OK;
-  const SplitOut so{nullptr, counts_out, intervals_out, intervals_stride};
-  rc = split_check_stride(trim, &so, t_max, err);
-  if (rc) return rc;
-  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  const SplitArgs sa{trim, nullptr, counts_out, intervals_out, intervals_stride, refs_out, false};
-  PcmView v;  // resampled into a plane as long as the longest segment, marked there: nothing but the counts, intervals and refs comes back
-  rc = pcm_chain(h, S, in_rates, out_rate, std::max<uint64_t>(t_max, 1), nullptr, 0, t_max, false, nullptr, &v, err, nullptr, &sa);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(h->host_stream));
-  return VSYN_OK;
+  return split_intervals_host(h, Gate{trim, true, false, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}, S, in_rates, out_rate,
+                              frames_out, err);
 }
 
 int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
                                  const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
                                  uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out,
                                  uint64_t intervals_stride, float* peaks_out, double* refs_out, vsyn_status* status, const char** err) {
-  if (!trim) return vsyn_pcm_cond_spectral_host(h, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, peaks_out, status, err);
   if (!h) return cond_no_handle(err);
-  const SplitOut so{frames_out, counts_out, intervals_out, intervals_stride};
-  return pcm_trim_spectral_host(h, trim, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, refs_out, status,
-                                err, &so);
+  const Gate g{trim, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out};
+  return spectral_host(h, trim ? &g : nullptr, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, trim ? frames_out : nullptr,
+                       peaks_out, status, err);
 }
 
 // ---- pitch (vsyn_pitch.h) ----
-
-static bool pitch_center(const vsyn_pitch_spec* spec) { return (spec->options & VSYN_PITCH_CENTER) != 0; }
 
 uint64_t vsyn_pitch_num_frames(const vsyn_pitch_spec* spec, uint64_t frames) {
   if (pitch_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
@@ -1905,52 +1831,19 @@ int vsyn_pcm_pitch_host(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t S,
                         uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   status_reset(status);
-  int rc;
-  std::vector<uint32_t> pt_rates;  // resampled: the pitch pass sees every resampled segment at out_rate
-  if (out_rate) {
-    rc = rs_check(S, in_rates, out_rate, err);
-    if (rc) return rc;
-    pt_rates.resize(S);
-    for (uint32_t g = 0; g < S; ++g) pt_rates[g] = in_rates[g] ? out_rate : 0u;
-  }
+  if (int rc = chain_check(nullptr, nullptr, S, in_rates, out_rate, err)) return rc;
+  const std::vector<uint32_t> pt_rates = stage_rates(S, in_rates, out_rate);
   const uint32_t* rates = out_rate ? pt_rates.data() : in_rates;
-  rc = pitch_check(spec, S, rates, err);
-  if (rc) return rc;
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
-  if (refused_out) memset(refused_out, 0, sizeof(uint32_t) * S);
-  // the lock covers the whole call: the resample and pitch workspaces are the handle's, and the PCM must stay that of the last submit
-  std::lock_guard<std::mutex> lk(h->mu);
-  std::vector<uint64_t> T(S);
-  uint64_t total = 0, f_max = 0, t_max;
-  rc = last_submit_frames(h, S, in_rates, out_rate, T.data(), &t_max, err);
-  if (rc) return rc;
-  t_max = std::max<uint64_t>(t_max, 1);
-  for (uint32_t g = 0; g < S; ++g) {
-    const uint64_t f = rates[g] ? spec_num_frames(spec->frame_length, spec->hop_length, pitch_center(spec), T[g]) : 0;
-    seg_rows[g] = f;
-    total += f;
-    f_max = std::max(f_max, f);
-  }
-  if (!rows || S == 0) return VSYN_OK;
-  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
-  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
-  hipStream_t hs = h->host_stream;
-  PcmView v;  // the synthesis PCM with the last submit's SegInfo, or the resampler's planes with its frames
-  rc = pcm_chain(h, S, in_rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err);
-  if (rc) return rc;
-  HIPCHK(h->pt.rows.ensure(total * 2u + 1));
-  HIPCHK(h->pt.refused.ensure(S));
-  rc = pitch_launch(h->pt, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->pt.rows.p, nullptr, h->pt.refused.p, hs, err);
-  if (rc) return rc;
-  if (total) HIPCHK(hipMemcpyAsync(rows, h->pt.rows.p, sizeof(float) * total * 2u, hipMemcpyDeviceToHost, hs));
-  if (refused_out) HIPCHK(hipMemcpyAsync(refused_out, h->pt.refused.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
-  return sync_status_into(h, status, err);
+  if (int rc = pitch_check(spec, S, rates, err)) return rc;
+  return framed_rows_host(
+      h, spec->frame_length, spec->hop_length, pitch_center(spec), 2u, h->pt.rows, h->pt.refused,
+      [&](const PcmView& v, uint64_t f_max, hipStream_t hs) {
+        return pitch_launch(h->pt, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->pt.rows.p, nullptr, h->pt.refused.p, hs, err);
+      },
+      S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
 }
 
 // ---- frame descriptors (vsyn_fdesc.h) ----
-
-static bool fdesc_center(const vsyn_fdesc_spec* spec) { return (spec->options & VSYN_FDESC_CENTER) != 0; }
 
 uint64_t vsyn_fdesc_num_frames(const vsyn_fdesc_spec* spec, uint64_t frames) {
   if (fdesc_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
@@ -1975,47 +1868,17 @@ int vsyn_fdesc_device(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t S, c
 int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
                         uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-  int rc = fdesc_check(spec, S, in_rates, err);  // (first: an invalid spec writes nothing, the status included)
-  if (rc) return rc;
+  if (int rc = fdesc_check(spec, S, in_rates, err)) return rc;  // (first: an invalid spec writes nothing, the status included)
   status_reset(status);
-  std::vector<uint32_t> fd_rates;  // resampled: the descriptor pass sees every resampled segment at out_rate
-  if (out_rate) {
-    rc = rs_check(S, in_rates, out_rate, err);
-    if (rc) return rc;
-    fd_rates.resize(S);
-    for (uint32_t g = 0; g < S; ++g) fd_rates[g] = in_rates[g] ? out_rate : 0u;
-  }
+  if (int rc = chain_check(nullptr, nullptr, S, in_rates, out_rate, err)) return rc;
+  const std::vector<uint32_t> fd_rates = stage_rates(S, in_rates, out_rate);
   const uint32_t* rates = out_rate ? fd_rates.data() : in_rates;
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
-  if (refused_out) memset(refused_out, 0, sizeof(uint32_t) * S);
-  // the lock covers the whole call: the resample and descriptor workspaces are the handle's, and the PCM must stay that of the last submit
-  std::lock_guard<std::mutex> lk(h->mu);
-  std::vector<uint64_t> T(S);
-  uint64_t total = 0, f_max = 0, t_max;
-  rc = last_submit_frames(h, S, in_rates, out_rate, T.data(), &t_max, err);
-  if (rc) return rc;
-  t_max = std::max<uint64_t>(t_max, 1);
-  for (uint32_t g = 0; g < S; ++g) {
-    const uint64_t f = rates[g] ? spec_num_frames(spec->n_fft, spec->hop_length, fdesc_center(spec), T[g]) : 0;
-    seg_rows[g] = f;
-    total += f;
-    f_max = std::max(f_max, f);
-  }
-  if (!rows || S == 0) return VSYN_OK;
-  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
-  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
-  hipStream_t hs = h->host_stream;
-  PcmView v;  // the synthesis PCM with the last submit's SegInfo, or the resampler's planes with its frames
-  rc = pcm_chain(h, S, in_rates, out_rate, t_max, nullptr, t_max, t_max, false, nullptr, &v, err);
-  if (rc) return rc;
-  HIPCHK(h->fd.rows.ensure(total * FDESC_COLS + 1));
-  HIPCHK(h->fd.refused.ensure(S));
-  rc = fdesc_launch(h->fd, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->fd.rows.p, nullptr, h->fd.refused.p, hs, err);
-  if (rc) return rc;
-  if (total) HIPCHK(hipMemcpyAsync(rows, h->fd.rows.p, sizeof(float) * total * FDESC_COLS, hipMemcpyDeviceToHost, hs));
-  if (refused_out) HIPCHK(hipMemcpyAsync(refused_out, h->fd.refused.p, sizeof(uint32_t) * S, hipMemcpyDeviceToHost, hs));
-  return sync_status_into(h, status, err);
+  return framed_rows_host(
+      h, spec->n_fft, spec->hop_length, fdesc_center(spec), FDESC_COLS, h->fd.rows, h->fd.refused,
+      [&](const PcmView& v, uint64_t f_max, hipStream_t hs) {
+        return fdesc_launch(h->fd, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->fd.rows.p, nullptr, h->fd.refused.p, hs, err);
+      },
+      S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
 }
 
 }  // extern "C"

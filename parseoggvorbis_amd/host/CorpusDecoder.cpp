@@ -515,45 +515,35 @@ struct Feeder {
     const char* err = nullptr;
     std::vector<uint64_t> got(S);
     std::vector<float> peaks(S, 0.f);
-    if (opts.split) {  // the split in front: the frames delivered are those of the joined signal, or with intervals_only nothing is
+    const int fmt = opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32;
+    void* out = opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p;
+    if (opts.split || opts.trim) {  // a gate in front: the frames delivered are the joined or trimmed ones, or with intervals_only nothing is
       std::vector<double> refs(S);
-      size_intervals(S, o);
-      const int rc = opts.intervals_only
-                         ? vsyn_pcm_split_intervals_host(g.handle, &opts.trim_spec, S, rates.data(), opts.resample_rate, got.data(), o.counts.data(),
-                                                         o.iv.data(), o.iv_stride, refs.data(), &err)
-                         : vsyn_pcm_split_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate,
-                                               opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32, opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, pl,
-                                               got.data(), o.counts.data(), o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &err);
-      if (rc != VSYN_OK) return OkOrError(std::string("GPU split layer: ") + (err ? err : "split failed"));
+      int rc;
+      if (opts.split) {
+        size_intervals(S, o);
+        rc = opts.intervals_only
+                 ? vsyn_pcm_split_intervals_host(g.handle, &opts.trim_spec, S, rates.data(), opts.resample_rate, got.data(), o.counts.data(),
+                                                 o.iv.data(), o.iv_stride, refs.data(), &err)
+                 : vsyn_pcm_split_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate, fmt, out, pl, got.data(),
+                                       o.counts.data(), o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &err);
+        if (rc != VSYN_OK) return OkOrError(std::string("GPU split layer: ") + (err ? err : "split failed"));
+      } else {
+        o.bounds.assign(2u * (size_t)S, 0u);
+        rc = vsyn_pcm_trim_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate, fmt, out, pl, got.data(),
+                                o.bounds.data(), peaks.data(), refs.data(), &err);
+        if (rc != VSYN_OK) return OkOrError(std::string("GPU trim layer: ") + (err ? err : "trim failed"));
+      }
       for (uint32_t s = 0; s < S; ++s) {
         CHECK(got[s] <= o.frames[s]);
         o.frames[s] = got[s];
       }
       refuse_refs(refs, o);
-      refuse_peaks(peaks, o);
-      o.plane = pl;
-      return OkOrError();
+    } else {
+      const int rc = vsyn_pcm_condition_host(g.handle, &opts.cond, S, rates.data(), opts.resample_rate, fmt, out, pl, got.data(), peaks.data(), &err);
+      if (rc != VSYN_OK) return OkOrError(std::string("GPU conditioning layer: ") + (err ? err : "conditioning failed"));
+      CHECK(got == o.frames);
     }
-    if (opts.trim) {  // the trim in front: the frames delivered are the trimmed ones
-      std::vector<double> refs(S);
-      o.bounds.assign(2u * (size_t)S, 0u);
-      const int rc = vsyn_pcm_trim_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate,
-                                        opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32, opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, pl,
-                                        got.data(), o.bounds.data(), peaks.data(), refs.data(), &err);
-      if (rc != VSYN_OK) return OkOrError(std::string("GPU trim layer: ") + (err ? err : "trim failed"));
-      for (uint32_t s = 0; s < S; ++s) {
-        CHECK(got[s] <= o.frames[s]);
-        o.frames[s] = got[s];
-      }
-      refuse_refs(refs, o);
-      refuse_peaks(peaks, o);
-      o.plane = pl;
-      return OkOrError();
-    }
-    const int rc = vsyn_pcm_condition_host(g.handle, &opts.cond, S, rates.data(), opts.resample_rate, opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32,
-                                           opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p, pl, got.data(), peaks.data(), &err);
-    if (rc != VSYN_OK) return OkOrError(std::string("GPU conditioning layer: ") + (err ? err : "conditioning failed"));
-    CHECK(got == o.frames);
     refuse_peaks(peaks, o);
     o.plane = pl;
     return OkOrError();
@@ -597,27 +587,23 @@ struct Feeder {
     if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);  // spec_rows, from the untrimmed frames, bounds the trimmed rows
     std::vector<uint64_t> joined(S, 0);
     if (opts.split) size_intervals(S, o);
-    const int rc = opts.split   ? vsyn_pcm_split_spectral_host(g.handle, &opts.trim_spec, trim_cond(), &opts.spectral, post_run(opts) ? &opts.post : nullptr,
-                                                               S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(),
-                                                               o.counts.data(), o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &st, &err)
-                   : opts.trim  ? vsyn_pcm_trim_spectral_host(g.handle, &opts.trim_spec, trim_cond(), &opts.spectral, post_run(opts) ? &opts.post : nullptr,
-                                                              S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(),
-                                                              peaks.data(), refs.data(), &st, &err)
-                   : opts.condition ? vsyn_pcm_cond_spectral_host(g.handle, &opts.cond, &opts.spectral, post_run(opts) ? &opts.post : nullptr, S,
-                                                                rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p,
-                                                                peaks.data(), &st, &err)
-                   : post_run(opts) ? vsyn_pcm_spectral_post_host(g.handle, &opts.spectral, &opts.post, S, rates.data(), opts.resample_rate,
-                                                                g.rows.p, spec_rows, g.seg_rows.p, &st, &err)
-                   : resample     ? vsyn_pcm_resample_spectral_host(g.handle, &opts.spectral, S, rates.data(), opts.resample_rate, g.rows.p,
-                                                              spec_rows, g.seg_rows.p, &st, &err)
-                            : vsyn_pcm_spectral_host(g.handle, &opts.spectral, S, rates.data(), g.rows.p, spec_rows, g.seg_rows.p, &st, &err);
+    // one entry per gate: a stage that is off is a NULL spec, and the entry then gives the bits of the entry without that stage
+    const bool gated = opts.trim || opts.split;
+    const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
+    const vsyn_spectral_post* post = post_run(opts) ? &opts.post : nullptr;
+    const int rc = opts.split ? vsyn_pcm_split_spectral_host(g.handle, &opts.trim_spec, cond, &opts.spectral, post, S, rates.data(), opts.resample_rate,
+                                                             g.rows.p, spec_rows, g.seg_rows.p, joined.data(), o.counts.data(), o.iv.data(), o.iv_stride,
+                                                             peaks.data(), refs.data(), &st, &err)
+                              : vsyn_pcm_trim_spectral_host(g.handle, opts.trim ? &opts.trim_spec : nullptr, cond, &opts.spectral, post, S, rates.data(),
+                                                            opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(), peaks.data(),
+                                                            refs.data(), &st, &err);
     if (rc == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
       for (uint32_t s = 0; s < S; ++s) o.err[s] = std::string("spectral: ") + (err ? err : "refused");
       for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
     } else if (rc != VSYN_OK) {
       return OkOrError(std::string("GPU spectral layer: ") + (err ? err : "spectral failed"));
     }
-    if ((opts.trim || opts.split) && rc == VSYN_OK) {
+    if (gated && rc == VSYN_OK) {
       refuse_refs(refs, o);
       for (uint32_t s = 0; s < S; ++s) {
         if (!o.err[s].empty()) continue;
@@ -632,6 +618,22 @@ struct Feeder {
       }
     }
     if (opts.condition) refuse_peaks(peaks, o);
+    return OkOrError();
+  }
+
+  // What a pitch and a frame descriptor run share behind their rates: room for rows rows of cols columns, the call, and an error of
+  // its own for a file the stage refuses (a sample that is not finite).
+  template <class Call>
+  OkOrError framed_rows(Group& g, Outcome& o, uint64_t rows, uint32_t cols, const char* layer, const char* name, Call call) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    CHECK_ERR(g.rows.ensure(rows * cols + 1));
+    CHECK_ERR(g.seg_rows.ensure(S));
+    std::vector<uint32_t> refused(S, 0u);
+    vsyn_status st;
+    const char* err = nullptr;
+    if (call(refused.data(), &st, &err) != VSYN_OK) return OkOrError("GPU " + std::string(layer) + " layer: " + (err ? err : std::string(name) + " failed"));
+    for (uint32_t s = 0; s < S; ++s)
+      if (o.err[s].empty() && refused[s]) o.err[s] = std::string(name) + ": the PCM holds a sample that is not finite";
     return OkOrError();
   }
 
@@ -656,16 +658,9 @@ struct Feeder {
       rates[s] = o.err[s].empty() ? in : 0;
       if (rates[s]) rows += vsyn_pitch_num_frames(&opts.pitch, std::min<uint64_t>(o.frames[s], o.plane));
     }
-    CHECK_ERR(g.rows.ensure(rows * 2u + 1));
-    CHECK_ERR(g.seg_rows.ensure(S));
-    std::vector<uint32_t> refused(S, 0u);
-    vsyn_status st;
-    const char* err = nullptr;
-    const int rc = vsyn_pcm_pitch_host(g.handle, &opts.pitch, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused.data(), &st, &err);
-    if (rc != VSYN_OK) return OkOrError(std::string("GPU pitch layer: ") + (err ? err : "pitch failed"));
-    for (uint32_t s = 0; s < S; ++s)
-      if (o.err[s].empty() && refused[s]) o.err[s] = "pitch: the PCM holds a sample that is not finite";
-    return OkOrError();
+    return framed_rows(g, o, rows, 2u, "pitch", "pitch", [&](uint32_t* refused, vsyn_status* st, const char** err) {
+      return vsyn_pcm_pitch_host(g.handle, &opts.pitch, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused, st, err);
+    });
   }
 
   // Frame descriptor run: each file's (rms, zcr, centroid, bandwidth, rolloff, flatness) rows from the PCM still on the device
@@ -679,16 +674,9 @@ struct Feeder {
       rates[s] = o.err[s].empty() ? g.pending[s]->header.audio_sample_rate : 0;
       if (rates[s]) rows += vsyn_fdesc_num_frames(&opts.fdesc, std::min<uint64_t>(o.frames[s], o.plane));
     }
-    CHECK_ERR(g.rows.ensure(rows * 6u + 1));
-    CHECK_ERR(g.seg_rows.ensure(S));
-    std::vector<uint32_t> refused(S, 0u);
-    vsyn_status st;
-    const char* err = nullptr;
-    const int rc = vsyn_pcm_fdesc_host(g.handle, &opts.fdesc, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused.data(), &st, &err);
-    if (rc != VSYN_OK) return OkOrError(std::string("GPU frame descriptor layer: ") + (err ? err : "frame descriptors failed"));
-    for (uint32_t s = 0; s < S; ++s)
-      if (o.err[s].empty() && refused[s]) o.err[s] = "frame descriptors: the PCM holds a sample that is not finite";
-    return OkOrError();
+    return framed_rows(g, o, rows, 6u, "frame descriptor", "frame descriptors", [&](uint32_t* refused, vsyn_status* st, const char** err) {
+      return vsyn_pcm_fdesc_host(g.handle, &opts.fdesc, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused, st, err);
+    });
   }
 
   // A synthesis run's file: its PCM (or, for a spectral, pitch or frame descriptor run, its rows) to the callbacks.
