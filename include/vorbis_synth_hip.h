@@ -886,6 +886,78 @@ int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, cons
                                  uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                  vsyn_status* status, const char** err);
 
+/* ---- PCEN: per-channel energy normalisation of spectral rows, computed where the rows are ----
+ *
+ * Input: one segment's rows X[f][j], F rows, D columns, float32, non-negative: the rows of VSYN_SPEC_MEL_POWER or VSYN_SPEC_LIN_POWER
+ * (power 1 or 2). Output: a float32 matrix (F, D). This is librosa.pcen(S.T * scale, sr=sr, hop_length=hop, gain, bias, power,
+ * time_constant, eps, b, max_size=1).T (librosa >= 0.10): an adaptive gain control along time in place of a fixed log compression.
+ * librosa is not among the test dependencies and parity with it is not claimed: the device is compared against a float64 model of the
+ * arithmetic below (tests/pcen_model.py), and the model against a restatement in librosa's own words with scipy.signal.lfilter and
+ * lfilter_zi (tests/test_pcen_cpu.py).
+ *
+ *  1. Scale. S = float32(X * float32(scale)): one rounding, exact for a power of two. librosa's documentation uses 2^31 for float
+ *     PCM; the default of the Python layer is 1.
+ *  2. Coefficient. b as given, or for b = 0: t = time_constant * sr / hop_length, b = (sqrt(1 + 4 t^2) - 1) / (2 t^2), in double on
+ *     the host. sr is the rate the segment's rows were computed at (the resample target, else the segment's own), so b is per
+ *     segment. q = 1 - b.
+ *  3. Smoother. M[f] = b S[f] + q M[f-1], M[-1] = 1, per column, in float64. This is scipy.signal.lfilter([b], [1, b - 1], S,
+ *     zi=lfilter_zi([b], [1, b - 1])), whose zi is 1 - b and is not scaled by S[0], exactly as librosa does it.
+ *  4. Gain and compression, in float64, in librosa's log-space form: G = exp(-gain * (log(eps) + log1p(M / eps))), then
+ *       power = 0:              Y = log1p(S * G)
+ *       power != 0, bias = 0:   Y = exp(power * (log(S) + log(G)))     (S = 0 gives 0)
+ *       otherwise:              Y = bias^power * expm1(power * log1p(S * G / bias))
+ *     and one rounding to float32.
+ *  5. Order in the pipeline: ..., STFT and filterbank, PCEN, delta / normalisation.
+ *  6. Checks (VSYN_ERR_INVALID before anything runs): gain, bias, power finite and >= 0; eps, time_constant, scale finite and > 0;
+ *     b = 0 (derive it) or in (0, 1]; with b = 0, hop_length >= 1 and a non-NULL rate array; dim >= 1. Through the spectral entry
+ *     points a kind other than VSYN_SPEC_MEL_POWER or VSYN_SPEC_LIN_POWER is refused by name: its rows can be negative. librosa's
+ *     max_size > 1, ref, zi and return_zf are not built.
+ *  7. The device entry does not look at signs: a NaN or a negative input propagates as IEEE arithmetic and the model say, and a NaN
+ *     poisons the rest of its column, as in librosa.
+ *
+ * Precision and order. The smoother is a blocked scan whose decomposition is a function of the segment's rows alone: blocks of 64
+ * rows counted from the segment's first row. Per (block, column) the block's zero-state response at its last row (the recurrence
+ * from 0, rows ascending); per column over the blocks in ascending order carry[0] = 1, carry[k+1] = part[k] + q^64 carry[k] (q^64
+ * in double from the host); then every block from its carry, rows ascending. All in float64, no atomics, and every term is
+ * non-negative, so nothing cancels. The result depends on neither the launch geometry nor the segment's place in the batch: the
+ * same rows give the same bits. The PCEN entry points read rows (and through the host forms, PCM) only: they touch neither stream
+ * state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM. One handle's PCEN entry points share its PCEN workspace. */
+typedef struct vsyn_spectral_pcen { /* 56 bytes */
+  double gain;          /* >= 0; librosa's default is 0.98 */
+  double bias;          /* >= 0; 2 */
+  double power;         /* >= 0; 0.5 */
+  double time_constant; /* > 0, seconds; 0.4. Read only when b = 0 */
+  double eps;           /* > 0; 1e-6 */
+  double b;             /* 0: derived from time_constant, the rate and the hop; else in (0, 1] */
+  double scale;         /* > 0; the rows are multiplied by float32(scale) first */
+} vsyn_spectral_pcen;
+
+/* The coefficient b of step 2 for rows computed at sample_rate every hop_length samples (pcen->b itself when it is not 0). 0 for an
+ * invalid spec, and for b = 0 with sample_rate = 0 or hop_length = 0. */
+double vsyn_spectral_pcen_b(const vsyn_spectral_pcen* pcen, uint32_t sample_rate, uint32_t hop_length);
+
+/* The stage alone on rows the caller has on the device (what vsyn_spectral_device wrote): d_in holds the segments' rows back to
+ * back, dim columns; seg_rows[S] is a HOST array of each segment's row count; sample_rates[S] (HOST; may be NULL when b != 0) the
+ * rate each segment's rows were computed at, 0 skips the segment (its rows are neither read nor written). Writes d_out, the same
+ * rows, and nothing past them; d_out may be d_in. Asynchronous on hip_stream. */
+int vsyn_spectral_pcen_device(vsyn_handle* h, const vsyn_spectral_pcen* pcen, uint32_t dim, uint32_t num_segments, const uint64_t* seg_rows,
+                              const uint32_t* sample_rates, uint32_t hop_length, const float* d_in, float* d_out, void* hip_stream,
+                              const char** err);
+
+/* vsyn_pcm_trim_spectral_host and vsyn_pcm_split_spectral_host with the PCEN stage between the spectral rows and the post stage, in
+ * place on the rows, without rows or PCM leaving the device: b is derived (b = 0) from the rate the spectral stage sees and
+ * spec->hop_length. pcen = NULL is the entry without the stage, bit for bit; trim = NULL, cond = NULL and post = NULL mean what they
+ * mean there. A spec->kind other than VSYN_SPEC_MEL_POWER or VSYN_SPEC_LIN_POWER with pcen != NULL is VSYN_ERR_INVALID. Synchronous. */
+int vsyn_pcm_trim_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                     const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t num_segments,
+                                     const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                                     uint32_t* bounds_out, float* peaks_out, double* refs_out, vsyn_status* status, const char** err);
+int vsyn_pcm_split_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                      const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t num_segments,
+                                      const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                                      uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
+                                      float* peaks_out, double* refs_out, vsyn_status* status, const char** err);
+
 /* ---- pitch: the fundamental frequency of the decoded PCM per frame (YIN), computed where the PCM is ----
  *
  * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, and its sample rate sr. Parameters: frame_length L,

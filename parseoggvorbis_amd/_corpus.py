@@ -40,6 +40,9 @@ def load():
                                                         vp, vp, vp]),
                        ("ogg_vorbis_spectral_corpus_split", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPost),
                                                              C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), vp, vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_spectral_corpus_pcen", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPcen),
+                                                            C.POINTER(binding.SpectralPost), C.POINTER(binding.PcmCond),
+                                                            C.POINTER(binding.PcmTrim), C.c_int, vp, vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_intervals_corpus", [u32, C.POINTER(binding.PcmTrim), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pitch_corpus", [u32, C.POINTER(binding.PitchSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_fdesc_corpus", [u32, C.POINTER(binding.FdescSpec), vp, vp, vp, vp, vp])):

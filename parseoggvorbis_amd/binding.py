@@ -76,6 +76,11 @@ class SpectralPost(C.Structure):  # vsyn_spectral_post
                 ("mean", C.c_void_p), ("std", C.c_void_p)]
 
 
+class SpectralPcen(C.Structure):  # vsyn_spectral_pcen
+    _fields_ = [("gain", C.c_double), ("bias", C.c_double), ("power", C.c_double), ("time_constant", C.c_double), ("eps", C.c_double),
+                ("b", C.c_double), ("scale", C.c_double)]
+
+
 class PcmCond(C.Structure):  # vsyn_pcm_cond
     _fields_ = [("options", C.c_uint32), ("reserved", C.c_uint32), ("preemphasis", C.c_double)]
 
@@ -225,6 +230,7 @@ _SYMBOLS = [
     "vsyn_pcm_trim_num_frames", "vsyn_pcm_trim_device", "vsyn_pcm_trim_host", "vsyn_pcm_trim_spectral_host",
     "vsyn_pcm_split_max_intervals", "vsyn_pcm_split_device", "vsyn_pcm_split_host", "vsyn_pcm_split_intervals_host",
     "vsyn_pcm_split_spectral_host",
+    "vsyn_spectral_pcen_b", "vsyn_spectral_pcen_device", "vsyn_pcm_trim_spectral_pcen_host", "vsyn_pcm_split_spectral_pcen_host",
     "vsyn_pitch_num_frames", "vsyn_pitch_device", "vsyn_pcm_pitch_host",
     "vsyn_fdesc_num_frames", "vsyn_fdesc_device", "vsyn_pcm_fdesc_host",
 ]
@@ -326,6 +332,14 @@ def load():
     lib.vsyn_pcm_split_intervals_host.argtypes = [vp, C.POINTER(PcmTrim), u32, vp, u32, vp, vp, vp, u64, vp, cpp]
     lib.vsyn_pcm_split_spectral_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPost),
                                                  u32, vp, u32, vp, u64, vp, vp, vp, vp, u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_spectral_pcen_b.argtypes = [C.POINTER(SpectralPcen), u32, u32]
+    lib.vsyn_spectral_pcen_b.restype = C.c_double
+    lib.vsyn_spectral_pcen_device.argtypes = [vp, C.POINTER(SpectralPcen), u32, u32, vp, vp, u32, vp, vp, vp, cpp]
+    lib.vsyn_pcm_trim_spectral_pcen_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPcen),
+                                                     C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_pcm_split_spectral_pcen_host.argtypes = [vp, C.POINTER(PcmTrim), C.POINTER(PcmCond), C.POINTER(SpectralSpec), C.POINTER(SpectralPcen),
+                                                      C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, u64, vp, vp,
+                                                      C.POINTER(Status), cpp]
     lib.vsyn_pitch_num_frames.argtypes = [C.POINTER(PitchSpec), u64]
     lib.vsyn_pitch_num_frames.restype = u64
     lib.vsyn_pitch_device.argtypes = [vp, C.POINTER(PitchSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
@@ -567,6 +581,34 @@ class Synth:
         S, o = len(rates), _per_segment(len(rates), "bounds", "peaks", "refs")
         return self._rows_host(self.lib.vsyn_pcm_trim_spectral_host, (_ref(trim), _ref(cond), C.byref(spec), _ref(post), S, _ptr(rates), out_rate), S,
                                _post_dim(spec, post), [o["bounds"], o["peaks"], o["refs"]], o)
+
+    def spectral_pcen_device(self, pcen, dim, seg_rows, sample_rates, hop_length, d_in, d_out, stream=None):
+        """vsyn_spectral_pcen_device on device pointers (ints); seg_rows and sample_rates (None: NULL) are host sequences."""
+        nrows, rates = np.ascontiguousarray(seg_rows, dtype=np.uint64), _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_spectral_pcen_device(self.h, _ref(pcen), dim, len(nrows), _ptr(nrows), _ptr(rates), hop_length, d_in, d_out, stream,
+                                                  C.byref(err)), err)
+
+    def pcm_trim_spectral_pcen_host(self, trim, cond, spec, pcen, post, in_rates, out_rate=0):
+        """vsyn_pcm_trim_spectral_pcen_host over the last submit's segments (trim / cond / pcen / post may be None): returns what
+        pcm_trim_spectral_host returns."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "bounds", "peaks", "refs")
+        return self._rows_host(self.lib.vsyn_pcm_trim_spectral_pcen_host,
+                               (_ref(trim), _ref(cond), C.byref(spec), _ref(pcen), _ref(post), S, _ptr(rates), out_rate), S, _post_dim(spec, post),
+                               [o["bounds"], o["peaks"], o["refs"]], o)
+
+    def pcm_split_spectral_pcen_host(self, split, cond, spec, pcen, post, in_rates, out_rate=0):
+        """vsyn_pcm_split_spectral_pcen_host over the last submit's segments (split / cond / pcen / post may be None): returns what
+        pcm_split_spectral_host returns."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "frames", "counts", "peaks", "refs")
+        ivs = 1 if split is None else self._split_sizes(split, S, rates if out_rate else None, out_rate)[1]
+        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
+        r = self._rows_host(self.lib.vsyn_pcm_split_spectral_pcen_host,
+                            (_ref(split), _ref(cond), C.byref(spec), _ref(pcen), _ref(post), S, _ptr(rates), out_rate), S, _post_dim(spec, post),
+                            [o["frames"], o["counts"], iv, ivs, o["peaks"], o["refs"]], o)
+        return dict(r, intervals=self._intervals(o["counts"], iv, S))
 
     def pcm_split_device(self, split, d_pcm, plane_stride, channels, num_segments, d_frames, d_out, out_plane_stride, d_out_frames, d_counts,
                          d_intervals, intervals_stride, d_ref=None, d_ms=None, ms_stride=0, stream=None):

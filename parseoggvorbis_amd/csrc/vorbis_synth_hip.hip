@@ -23,6 +23,7 @@
 #include "vsyn_spectral.h"
 #include "vsyn_spectral_lin.h"
 #include "vsyn_spectral_post.h"
+#include "vsyn_pcen.h"
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
 #include "vsyn_trim.h"
@@ -123,6 +124,7 @@ struct vsyn_handle {
   FeatureWs ft;                        // vsyn_features.h
   SpectralWs sp;                       // vsyn_spectral.h
   PostWs pp;                           // vsyn_spectral_post.h
+  PcenWs pc;                           // vsyn_pcen.h
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
   TrimWs tr;                           // vsyn_trim.h
@@ -1266,6 +1268,24 @@ int vsyn_spectral_post_device(vsyn_handle* h, const vsyn_spectral_post* post, ui
   return post_launch(h->pp, h->device, post, dim, S, seg_rows, d_in, d_out, (hipStream_t)hip_stream, err);
 }
 
+double vsyn_spectral_pcen_b(const vsyn_spectral_pcen* pcen, uint32_t sample_rate, uint32_t hop_length) {
+  if (pcen_check(pcen, nullptr) != VSYN_OK) return 0.0;
+  return pcen_b(pcen, sample_rate, hop_length);
+}
+
+int vsyn_spectral_pcen_device(vsyn_handle* h, const vsyn_spectral_pcen* pcen, uint32_t dim, uint32_t S, const uint64_t* seg_rows,
+                              const uint32_t* sample_rates, uint32_t hop_length, const float* d_in, float* d_out, void* hip_stream,
+                              const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = pcen_check_call(pcen, dim, S, seg_rows, sample_rates, hop_length, err)) return rc;
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  if (total == 0) return VSYN_OK;
+  if (!d_in || !d_out) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return pcen_launch(h->pc, h->device, pcen, dim, S, seg_rows, sample_rates, hop_length, d_in, d_out, (hipStream_t)hip_stream, err);
+}
+
 }  // extern "C"
 
 // The stages chained behind the last host submit. The PCM the next stage reads: planar [S][C][plane]; each segment's frames from d_frames, else from si.
@@ -1475,10 +1495,11 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   return VSYN_OK;
 }
 
-// The end of a spectral host form: the rows of the view's PCM on the host stream (post != NULL: on to the post stage in their
-// place, and its wider rows come back), copied to rows, then the call's wait and status. seg_rows, f_max and total are the host's
-// row counts. Caller holds h->mu.
-static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S, const uint32_t* spec_rates,
+// The end of a spectral host form: the rows of the view's PCM on the host stream (pcen != NULL: through the PCEN stage in place;
+// post != NULL: on to the post stage in their place, and its wider rows come back), copied to rows, then the call's wait and
+// status. seg_rows, f_max and total are the host's row counts. Caller holds h->mu.
+static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S,
+                             const uint32_t* spec_rates,
                              const PcmView& v, const uint64_t* seg_rows, uint64_t f_max, uint64_t total, float* rows, vsyn_status* status,
                              const char** err) {
   hipStream_t hs = h->host_stream;
@@ -1486,6 +1507,10 @@ static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   HIPCHK(h->sp.rows.ensure(total * D + 1));
   int rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err);
   if (rc) return rc;
+  if (pcen) {
+    rc = pcen_launch(h->pc, h->device, pcen, (uint32_t)D, S, seg_rows, spec_rates, spec->hop_length, h->sp.rows.p, h->sp.rows.p, hs, err);
+    if (rc) return rc;
+  }
   if (post) {
     const uint64_t Dout = D * (1u + post->order);
     HIPCHK(h->pp.rows.ensure(total * Dout + 1));
@@ -1498,12 +1523,13 @@ static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   return sync_status_into(h, status, err);
 }
 
-// The spectral host forms: the rows of the last host submit's PCM behind the stages present (gate, cond, post: NULL, out_rate: 0
+// The spectral host forms: the rows of the last host submit's PCM behind the stages present (gate, cond, pcen, post: NULL, out_rate: 0
 // for none). Without a gate the rows are counted on the host and nothing runs for a NULL rows. With one the chain runs up to the
 // gated plane and waits once for the gate's read-backs, the row counts come from those (frames_out: the frames behind the gate),
 // and conditioning, spectral rows and the post stage follow on the gated plane.
-static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post,
-                         uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen,
+                         const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
+                         uint64_t* seg_rows,
                          uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   status_reset(status);
@@ -1511,6 +1537,15 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
   std::vector<uint32_t> sp_rates = stage_rates(S, rates, out_rate);
   // (NULL rates without a gate are spec_check's to refuse; behind a gate they skip every segment)
   if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err)) return rc;
+  if (pcen) {
+    if (int rc = pcen_check(pcen, err)) return rc;
+    if (spec->kind != VSYN_SPEC_MEL_POWER && spec->kind != VSYN_SPEC_LIN_POWER)
+      return fail(err, VSYN_ERR_INVALID, "pcen takes the rows of mel_power or lin_power, not of kind %u (they can be negative)", spec->kind);
+    for (uint32_t g = 0; g < S; ++g)
+      if (sp_rates[g] && pcen_b(pcen, sp_rates[g], spec->hop_length) == 0.0)
+        return fail(err, VSYN_ERR_INVALID, "segment %u: pcen: no coefficient in (0, 1] from time_constant %g at rate %u, hop %u", g,
+                    pcen->time_constant, sp_rates[g], spec->hop_length);
+  }
   if (post) {
     if (int rc = spec_post_check(spec, post, err)) return rc;
     if (!post_on(post)) post = nullptr;  // off: the rows of the spectral pass, bit for bit
@@ -1567,7 +1602,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
   }
   if (cond)
     if (int rc = step_condition(h, S, cond, t_max, t_max, false, peaks_out, &v, err)) return rc;
-  return spectral_rows_out(h, spec, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err);
+  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err);
 }
 
 // vsyn_pcm_split_intervals_host: the chain up to the split stage's marks; nothing but the frames in front of the stage, the
@@ -1667,14 +1702,14 @@ int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates,
 
 int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
                            uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
-  return spectral_host(h, nullptr, nullptr, spec, nullptr, S, sample_rates, 0, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
+  return spectral_host(h, nullptr, nullptr, spec, nullptr, nullptr, S, sample_rates, 0, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
 }
 
 int vsyn_pcm_spectral_post_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S,
                                 const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
                                 vsyn_status* status, const char** err) {
   if (!post) return fail(err, VSYN_ERR_INVALID, "spectral post spec is NULL");
-  return spectral_host(h, nullptr, nullptr, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
+  return spectral_host(h, nullptr, nullptr, spec, nullptr, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
 }
 
 int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
@@ -1683,14 +1718,14 @@ int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* sp
     status_reset(status);
     return rs_check(S, in_rates, out_rate, err);
   }
-  return spectral_host(h, nullptr, nullptr, spec, nullptr, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
+  return spectral_host(h, nullptr, nullptr, spec, nullptr, nullptr, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
 }
 
 int vsyn_pcm_cond_spectral_host(vsyn_handle* h, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post,
                                 uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
                                 uint64_t* seg_rows, float* peaks_out, vsyn_status* status, const char** err) {
   if (!h) return cond_no_handle(err);
-  return spectral_host(h, nullptr, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status, err);
+  return spectral_host(h, nullptr, cond, spec, nullptr, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status, err);
 }
 
 int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t S, const float* d_pcm, uint64_t plane_stride,
@@ -1751,9 +1786,18 @@ int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const
                                 const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
                                 uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out, float* peaks_out, double* refs_out,
                                 vsyn_status* status, const char** err) {
+  return vsyn_pcm_trim_spectral_pcen_host(h, trim, cond, spec, nullptr, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, bounds_out, peaks_out,
+                                          refs_out, status, err);
+}
+
+int vsyn_pcm_trim_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                     const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates,
+                                     uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out,
+                                     float* peaks_out, double* refs_out, vsyn_status* status, const char** err) {
   if (!h) return cond_no_handle(err);
   const Gate g{trim, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return spectral_host(h, trim ? &g : nullptr, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status, err);
+  return spectral_host(h, trim ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status,
+                       err);
 }
 
 uint64_t vsyn_pcm_split_max_intervals(const vsyn_pcm_trim* trim, uint64_t frames) {
@@ -1799,9 +1843,18 @@ int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, cons
                                  const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
                                  uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out,
                                  uint64_t intervals_stride, float* peaks_out, double* refs_out, vsyn_status* status, const char** err) {
+  return vsyn_pcm_split_spectral_pcen_host(h, trim, cond, spec, nullptr, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, frames_out,
+                                           counts_out, intervals_out, intervals_stride, peaks_out, refs_out, status, err);
+}
+
+int vsyn_pcm_split_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
+                                      const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates,
+                                      uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out,
+                                      uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                      vsyn_status* status, const char** err) {
   if (!h) return cond_no_handle(err);
   const Gate g{trim, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out};
-  return spectral_host(h, trim ? &g : nullptr, cond, spec, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, trim ? frames_out : nullptr,
+  return spectral_host(h, trim ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, trim ? frames_out : nullptr,
                        peaks_out, status, err);
 }
 

@@ -591,12 +591,21 @@ struct Feeder {
     const bool gated = opts.trim || opts.split;
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
     const vsyn_spectral_post* post = post_run(opts) ? &opts.post : nullptr;
-    const int rc = opts.split ? vsyn_pcm_split_spectral_host(g.handle, &opts.trim_spec, cond, &opts.spectral, post, S, rates.data(), opts.resample_rate,
-                                                             g.rows.p, spec_rows, g.seg_rows.p, joined.data(), o.counts.data(), o.iv.data(), o.iv_stride,
-                                                             peaks.data(), refs.data(), &st, &err)
-                              : vsyn_pcm_trim_spectral_host(g.handle, opts.trim ? &opts.trim_spec : nullptr, cond, &opts.spectral, post, S, rates.data(),
-                                                            opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(), peaks.data(),
-                                                            refs.data(), &st, &err);
+    int rc;
+    if (opts.pcen)  // the two forms with the PCEN stage in them; off, today's entries
+      rc = opts.split ? vsyn_pcm_split_spectral_pcen_host(g.handle, &opts.trim_spec, cond, &opts.spectral, &opts.pcen_spec, post, S, rates.data(),
+                                                          opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(), o.counts.data(),
+                                                          o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &st, &err)
+                      : vsyn_pcm_trim_spectral_pcen_host(g.handle, opts.trim ? &opts.trim_spec : nullptr, cond, &opts.spectral, &opts.pcen_spec, post, S,
+                                                         rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(),
+                                                         peaks.data(), refs.data(), &st, &err);
+    else
+      rc = opts.split ? vsyn_pcm_split_spectral_host(g.handle, &opts.trim_spec, cond, &opts.spectral, post, S, rates.data(), opts.resample_rate,
+                                                     g.rows.p, spec_rows, g.seg_rows.p, joined.data(), o.counts.data(), o.iv.data(), o.iv_stride,
+                                                     peaks.data(), refs.data(), &st, &err)
+                      : vsyn_pcm_trim_spectral_host(g.handle, opts.trim ? &opts.trim_spec : nullptr, cond, &opts.spectral, post, S, rates.data(),
+                                                    opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(), peaks.data(),
+                                                    refs.data(), &st, &err);
     if (rc == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
       for (uint32_t s = 0; s < S; ++s) o.err[s] = std::string("spectral: ") + (err ? err : "refused");
       for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
@@ -1162,7 +1171,7 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
                     const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
                     const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr,
                     const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr, const vsyn_pcm_trim* split = nullptr,
-                    const SplitOuts* so = nullptr) {
+                    const SplitOuts* so = nullptr, const vsyn_spectral_pcen* pcen = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
@@ -1170,6 +1179,10 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
   opts.spectral = *spec;
   opts.resample_rate = target_rate;
   if (post) opts.post = *post;
+  if (pcen) {
+    opts.pcen = true;
+    opts.pcen_spec = *pcen;
+  }
   if (cond) {
     opts.condition = true;
     opts.cond = *cond;
@@ -1295,6 +1308,25 @@ extern "C" int ogg_vorbis_spectral_corpus_split(const uint8_t* const* datas, con
   return spectral_corpus("ogg_vorbis_spectral_corpus_split", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
                          target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, nullptr, nullptr,
                          split, &so);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_pcen(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                               uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                               const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_pcm_cond* cond,
+                                               const vsyn_pcm_trim* gate, int gate_is_split, float** rows_out, uint64_t* rows_count_out,
+                                               uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
+                                               uint64_t* intervals_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                               double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.frames_out = frames_out;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  so.begin(num_files);
+  const bool split = gate && gate_is_split;
+  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
+  return spectral_corpus("ogg_vorbis_spectral_corpus_pcen", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
+                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
+                         split ? gate : nullptr, &so, pcen);
 }
 
 extern "C" int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

@@ -107,6 +107,12 @@ struct CorpusOptions {
   // (a PCM run with split): the intervals alone; the joined signal is not made, no PCM is delivered, and frames are the unsplit
   // ones. A file with a sample that is not finite fails alone. The default is off: today's output.
   bool split = false, intervals_only = false;
+  // pcen (a spectral run of kind mel_power or lin_power): each file's rows go through the PCEN stage on the device between the
+  // spectral rows and the post stage (include/vorbis_synth_hip.h, "PCEN"); with pcen_spec.b = 0 the coefficient comes from the rate
+  // the rows are computed at (resample_rate, else the file's own) and spectral.hop_length. A spec the stage refuses (another kind
+  // among them) is every file's error. The default is off: today's rows and today's entry points.
+  bool pcen = false;
+  vsyn_spectral_pcen pcen_spec = {0.98, 2.0, 0.5, 0.4, 1e-6, 0.0, 1.0};
   // pitch run (pitch.frame_length != 0): synthesis as usual but VSYN_SUBMIT_KEEP_PCM, then each file's (f0, normalised difference)
   // rows from the PCM on the device (include/vorbis_synth_hip.h, "pitch": vsyn_pcm_pitch_host, resampled first with resample_rate),
   // delivered through gotFileFeatures with dim 2; no PCM crosses the bus. A file whose rate the spec does not fit, and a file with
@@ -229,6 +235,17 @@ int ogg_vorbis_spectral_corpus_split(const uint8_t* const* datas, const size_t* 
                                      const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* split, float** rows_out,
                                      uint64_t* rows_count_out, uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
                                      uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
+// The spectral run with every stage's spec in one call: resample (target_rate != 0), the gate (gate != NULL: a trim, or with
+// gate_is_split != 0 a split), condition (cond != NULL), spectral rows, PCEN (pcen != NULL: CorpusOptions::pcen_spec = *pcen), post
+// stage (post != NULL). NULL means off. The outputs are those of ogg_vorbis_spectral_corpus_trim (bounds_out) and of
+// ogg_vorbis_spectral_corpus_split (frames_out, intervals_out, intervals_count_out); each may be NULL, and those of the gate that is
+// off are zeroed. A PCEN spec the stage refuses is every file's error. Same output contract.
+int ogg_vorbis_spectral_corpus_pcen(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                    const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_pcm_cond* cond,
+                                    const vsyn_pcm_trim* gate, int gate_is_split, float** rows_out, uint64_t* rows_count_out,
+                                    uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
+                                    uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
 // The intervals alone (CorpusOptions::intervals_only): decode, resample (target_rate != 0), frame energies, intervals; no PCM comes
 // back from the device. frames_out / rate_out: each file's (resampled) length and rate; intervals_out / intervals_count_out as above.
 int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

@@ -11,7 +11,8 @@ device as well (include/vorbis_synth_hip.h, "spectral post-processing"): librosa
 mean / variance normalisation; tests/spectral_post_model.py is their float64 model. peak_normalize / preemphasis condition the mono
 waveform on the device in front of the STFT (include/vorbis_synth_hip.h, "PCM conditioning"; model: tests/condition_model.py), and
 trim_db cuts its silent head and tail in front of both ("PCM trimming"; model: tests/trim_model.py), or split_db every silent
-stretch ("PCM splitting"; model: tests/split_model.py)."""
+stretch ("PCM splitting"; model: tests/split_model.py). pcen=True turns the rows of "mel_power" or "lin_power" into librosa.pcen's
+on the device, between the spectral rows and delta / normalize ("PCEN"; model: tests/pcen_model.py)."""
 import ctypes as C
 import math
 
@@ -146,6 +147,32 @@ def post_spec(dim, delta=0, delta_width=9, normalize=None, std_floor=1e-5):
     return post, dout, keep
 
 
+PCEN_KINDS = ("mel_power", "lin_power")  # include/vorbis_synth_hip.h, "PCEN": the kinds whose rows cannot be negative
+
+
+def _number(name, v, positive):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise SpectralError("%s must be a number, got %r" % (name, v))
+    v = float(v)
+    if not (math.isfinite(v) and (v > 0.0 if positive else v >= 0.0)):
+        raise SpectralError("%s must be finite and %s 0, got %r" % (name, ">" if positive else ">=", v))
+    return v
+
+
+def pcen_spec(gain=0.98, bias=2.0, power=0.5, time_constant=0.4, eps=1e-6, b=None, scale=1.0):
+    """Checks the PCEN arguments (include/vorbis_synth_hip.h, "PCEN", step 6) and returns the C spec (binding.SpectralPcen). b=None:
+    the coefficient is derived per file from time_constant, the rate its rows are computed at and hop_length (encoded as 0)."""
+    from .binding import SpectralPcen
+    gain, bias, power = _number("pcen_gain", gain, False), _number("pcen_bias", bias, False), _number("pcen_power", power, False)
+    time_constant, eps = _number("pcen_time_constant", time_constant, True), _number("pcen_eps", eps, True)
+    scale = _number("pcen_scale", scale, True)
+    if b is not None:
+        b = _number("pcen_b", b, True)
+        if b > 1.0:
+            raise SpectralError("pcen_b must be in (0, 1] (or None), got %r" % b)
+    return SpectralPcen(gain, bias, power, time_constant, eps, 0.0 if b is None else b, scale)
+
+
 _load = _corpus.load
 
 
@@ -153,7 +180,9 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                        htk=False, norm="slaney", center=True, power=2.0, log_floor=1e-3, amin=1e-10, top_db=80.0, n_mfcc=20,
                        threads=0, feeders=0, device=0, errors="raise", files_per_submit=64, stats=None, sr=None, delta=0, delta_width=9,
                        normalize=None, std_floor=1e-5, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048,
-                       trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None):
+                       trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None,
+                       pcen=False, pcen_gain=0.98, pcen_bias=2.0, pcen_power=0.5, pcen_time_constant=0.4, pcen_eps=1e-6, pcen_b=None,
+                       pcen_scale=1.0):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels for the other mel kinds. The linear kinds have no filterbank: "lin_power" is |X|^power and "lin_db" its dB image
     (amin, top_db as for "mel_db"; librosa.amplitude_to_db(|X|, amin=a) is power=2, amin=a*a), both (frames, n_fft / 2 + 1);
@@ -174,7 +203,13 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     one (start, end) per file in samples of the (resampled) signal, None for a failed file and for every file with the stage off.
     split_db=d (instead of trim_db) removes every silent stretch of the mono signal first, as get_pcm_batch(mono=True, split_db=d,
     ...) does: the rows are those of the joined signal; split_index (optional list) receives one (n, 2) int64 array of (start, end)
-    per file, None for a failed file and for every file with the stage off."""
+    per file, None for a failed file and for every file with the stage off.
+    pcen=True (kind "mel_power" or "lin_power" only; SpectralError before anything is loaded otherwise) replaces the rows by
+    librosa.pcen(rows.T * pcen_scale, sr, hop_length, gain=pcen_gain, bias=pcen_bias, power=pcen_power,
+    time_constant=pcen_time_constant, eps=pcen_eps, b=pcen_b, max_size=1).T on the device, in front of delta / normalize; sr is
+    the rate the rows are computed at, so with sr=None the derived coefficient differs between files of different rates.
+    librosa's documentation uses pcen_scale=2**31 for float PCM. With pcen=False the pcen_* arguments are still checked, nothing is
+    launched and the call takes the entry points it took without them."""
     _corpus.check_errors(errors)
     from .pcm import check_sr, cond_spec, give_split_index, give_trim_index, split_spec, trim_spec
     target = check_sr(sr, SpectralError)
@@ -184,11 +219,33 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     if post is not None and spec.kind in LINEAR_KINDS:
         raise SpectralError("delta / normalize are not available for the linear kind %r (rows of %d columns; the post stage holds 256)"
                             % (kind, dim))
+    pc = pcen_spec(pcen_gain, pcen_bias, pcen_power, pcen_time_constant, pcen_eps, pcen_b, pcen_scale)
+    if not isinstance(pcen, (bool, np.bool_)):
+        raise SpectralError("pcen must be True or False, got %r" % (pcen,))
+    if pcen and kind not in PCEN_KINDS:
+        raise SpectralError("pcen is not available for kind %r: it takes the rows of %s" % (kind, " or ".join(PCEN_KINDS)))
     cond = cond_spec(peak_normalize, preemphasis, SpectralError)
     trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index, SpectralError)
     split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
+    if pcen:  # the one entry with every stage's spec (NULL: off)
+        n = len(list_of_bytes)
+        ib = _corpus.IntervalBuffers(lib, n)
+        joined, bounds = np.zeros(max(n, 1), np.uint64), np.zeros((max(n, 1), 2), np.uint64)
+        gate = split if split is not None else trim
+        try:
+            res = _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_pcen, list_of_bytes,
+                              (threads, feeders, files_per_submit, device, C.byref(spec), target, C.byref(pc), None if post is None else C.byref(post),
+                               C.byref(cond) if cond.options else None, None if gate is None else C.byref(gate), int(split is not None)),
+                              (counts, bounds, joined, ib.ptrs, ib.counts),
+                              lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors,
+                              "spectral", stats)
+            give_split_index(split_index, ib if split is not None else None, res)
+        finally:
+            ib.free()
+        give_trim_index(trim_index, bounds[:n] if trim is not None else None, res)
+        return _finish(spec, res)
     if split is not None:
         ib = _corpus.IntervalBuffers(lib, len(list_of_bytes))
         joined = np.zeros(max(len(list_of_bytes), 1), np.uint64)
