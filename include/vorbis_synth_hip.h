@@ -1112,6 +1112,143 @@ int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t nu
                         float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
                         const char** err);
 
+/* ---- loudness: the integrated loudness of the decoded PCM (ITU-R BS.1770-4 / EBU R 128) and the gain to a target, computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, at rate fs. The measured signal is the C planes
+ * (VSYN_LOUD_SUM, Cs = C) or their mono downmix, the float32 expression of "PCM conditioning" step 1 (VSYN_LOUD_MONO, Cs = 1).
+ * This is what pyloudnorm.Meter(fs).integrated_loudness and ffmpeg's ebur128 "I" compute for one and two channels; neither is among
+ * the test dependencies and parity with them is not claimed: the device is compared against a float64 model of the arithmetic below
+ * (tests/loudness_model.py), and the model against the standard's coefficient table, its 997 Hz calibration and EBU Tech 3341's
+ * cases 1 to 5 (tests/test_loudness_cpu.py).
+ *
+ *  1. K-weighting. Two biquads in cascade, a high shelf and then a high pass, coefficients in double on the host from fs:
+ *       shelf      G = 3.999843853973347 dB, Q = 0.7071752369554196, fc = 1681.974450955533,
+ *                  K = tan(pi fc / fs), Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *                  b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0],
+ *                  a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *       high pass  Q = 0.5003270373238773, fc = 38.13547087602444, b = [1, -2, 1], a by the same two expressions.
+ *     At 48 kHz these are the standard's table to 8.9e-16. Each biquad runs in direct form II transposed in float64 from a zero
+ *     state: scipy.signal.lfilter per section. vsyn_loudness_coefficients returns the ten numbers the device is given.
+ *  2. Hops and blocks, in integers. Hop i covers the samples [(i fs) / 10, ((i + 1) fs) / 10) (integer division); Nh = (10 T) / fs
+ *     whole hops. Block j is hops j .. j + 3, j < Nh - 3, and its mean square is z_j = (((s_j + s_j+1) + s_j+2) + s_j+3) / n_j with
+ *     n_j its own sample count and s_i the float64 sum of the squared K-weighted samples of hop i, summed over the channels in
+ *     ascending order with unit weights. With fs a multiple of 10 these are BS.1770-4's 400 ms blocks at 75 % overlap; at 11 025 and
+ *     22 050 Hz the hop length alternates by one sample.
+ *  3. Gating, on z with no logarithm on the device. Absolute gate: z_j > Z_abs = 10^((-70 + 0.691) / 10), a host double. zbar_a is
+ *     the mean of the blocks kept. Relative gate: of those, z_j > zbar_a / 10.0. zbar is the mean of what is left; the integrated
+ *     loudness is -0.691 + 10 log10(zbar), formed by the caller from zbar.
+ *  4. Gain to a target L_t in LUFS (VSYN_LOUD_NORMALIZE): g = float32(sqrt(Z_t / zbar)), Z_t = 10^((L_t + 0.691) / 10) a host
+ *     double; the division and the square root are the correctly rounded float64 ones, so float32(sqrt(Z_t / zbar)) formed from the
+ *     record's zbar anywhere else is g bit for bit. y[t] = x[t] * g: one float32 multiplication, not clipped.
+ *  5. The record per segment: zbar, zbar_a, the three block counts (all, above the absolute gate, above both), g (0 without a target
+ *     or a measurement) and a status: VSYN_LOUD_OK; VSYN_LOUD_NOT_FINITE, a sample of the segment is Inf or NaN, the tail behind the
+ *     last whole hop included; VSYN_LOUD_TOO_SHORT, Nh < 4; VSYN_LOUD_SILENT, no block passes the absolute gate;
+ *     VSYN_LOUD_RATE_REFUSED, fs < 4000 (0 included): nothing of the segment is read. Where several hold the order is rate refused,
+ *     not finite, too short, silent. A segment that is not VSYN_LOUD_OK has zbar = zbar_a = g = 0 and a scaled plane of zeros, as a
+ *     refused segment has under VSYN_COND_PEAK.
+ *  6. Checks (VSYN_ERR_INVALID before anything runs, outputs untouched): unknown option bits or channel mode, with
+ *     VSYN_LOUD_NORMALIZE a target that is not finite or outside [-70, 0], NULL records, a scaled plane without VSYN_LOUD_NORMALIZE.
+ *
+ * Deliberately not built: BS.1770's surround weights (1.41) and its LFE exclusion, every channel has weight 1, so the result is the
+ * standard's for one and two channels exactly; true peak, loudness range and short-term (3 s) or momentary loudness; any limiter.
+ *  7. Order in the pipeline: resample, the gate (trim or split), loudness normalisation, conditioning (pre-emphasis), spectral rows,
+ *     PCEN, delta / normalisation. As a step of a chain (vsyn_pcm_chain_host, vsyn_pcm_chain_spectral_host) the stage measures the
+ *     mono plane the chain has at that point (the gated plane, else the downmix: VSYN_LOUD_MONO) at the rate the chain has there,
+ *     and hands on y = x * g as 1-channel PCM. It excludes VSYN_COND_PEAK (VSYN_ERR_INVALID): two level controls. A segment that
+ *     is not VSYN_LOUD_OK, a silent one included, hands on zeros and its record says why.
+ *     Measured afresh the scaled signal need not be at L_t: the absolute gate does not move with the gain, so a block it cut can
+ *     pass it afterwards. Over the blocks the measurement kept it is at L_t, up to float32.
+ *
+ * Precision and order. The filter is a blocked scan whose decomposition is a function of the segment's samples alone: chunks of 32
+ * samples counted from the segment's first one, 256 chunks to a tile; the chunks' zero-state responses are combined with the powers
+ * A^(32 2^k) of the cascade's 4x4 state-transition matrix, formed in double on the host, in a fixed order; tiles are chained in
+ * ascending order. Sums of squares run per chunk in ascending order, per hop over its chunks in a fixed order, per gate over the
+ * blocks in a fixed order. Float64 throughout, no atomics: the same PCM gives the same bits alone and anywhere in a batch. The
+ * K-weighted samples differ from the float64 model's by rounding that leaves through the all-pole parts of the sections, whose
+ * double pole near z = 1 amplifies it by about 1 / (1 - rho)^2; DESIGN.md 6m derives the bound the tests gate at. The entry points
+ * read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM. One handle's
+ * loudness entry points share its loudness workspace. */
+#define VSYN_LOUD_NORMALIZE 1u /* form g for spec.target (step 4) */
+enum {
+  VSYN_LOUD_SUM = 0, /* the C planes, unit weights */
+  VSYN_LOUD_MONO = 1 /* their mono downmix */
+};
+enum {
+  VSYN_LOUD_OK = 0,
+  VSYN_LOUD_NOT_FINITE = 1,
+  VSYN_LOUD_TOO_SHORT = 2,
+  VSYN_LOUD_SILENT = 3,
+  VSYN_LOUD_RATE_REFUSED = 4
+};
+typedef struct vsyn_loudness_spec { /* 16 bytes */
+  uint32_t options;      /* VSYN_LOUD_* bits */
+  uint32_t channel_mode; /* VSYN_LOUD_SUM or VSYN_LOUD_MONO */
+  double target;         /* L_t in LUFS, in [-70, 0]; read only with VSYN_LOUD_NORMALIZE */
+} vsyn_loudness_spec;
+typedef struct vsyn_loudness_record { /* 40 bytes */
+  double zbar;         /* step 3; the integrated loudness is -0.691 + 10 log10(zbar) */
+  double zbar_a;       /* the mean behind the absolute gate alone */
+  uint32_t blocks;     /* Nh - 3, or 0 */
+  uint32_t blocks_abs; /* of those, above the absolute gate */
+  uint32_t blocks_rel; /* of those, above the relative gate too */
+  float gain;          /* g of step 4 */
+  uint32_t status;     /* VSYN_LOUD_OK ... */
+  uint32_t reserved;
+} vsyn_loudness_record;
+
+/* The blocks of step 2 for a segment of `frames` frames at sample_rate: Nh - 3, 0 for Nh < 4 or a refused rate. */
+uint64_t vsyn_loudness_num_blocks(uint32_t sample_rate, uint64_t frames);
+
+/* The ten coefficients of step 1 at sample_rate as the device gets them: b0 b1 b2 a1 a2 of the shelf, then of the high pass.
+ * VSYN_ERR_INVALID for a NULL out or a rate below 4000. */
+int vsyn_loudness_coefficients(uint32_t sample_rate, double* out);
+
+/* The nine 4x4 matrices A^(32 2^k), k = 0 .. 8, row-major, 144 doubles, of the cascade's state transition at sample_rate as the
+ * device gets them ("Precision and order"). VSYN_ERR_INVALID for a NULL out or a rate below 4000. */
+int vsyn_loudness_powers(uint32_t sample_rate, double* out);
+
+/* The stage alone on the caller's planar PCM on the device: d_pcm[(g * channels + c) * plane_stride + t]; sample_rates[S] and
+ * frames[S] are HOST arrays (frames clamped to plane_stride). Writes d_records[S]; d_z (may be NULL) receives the z_j of all
+ * segments back to back, vsyn_loudness_num_blocks of them each (also for a segment that is not finite); d_weighted (may be NULL)
+ * the K-weighted samples as float64, [(g * Cs + c) * weighted_plane_stride + t] (not written for a rate-refused segment);
+ * d_scaled (may be NULL; needs VSYN_LOUD_NORMALIZE) the planes of step 4, [(g * Cs + c) * scaled_plane_stride + t], frames clamped
+ * to the stride, nothing written past a segment's frames. Asynchronous on hip_stream. */
+int vsyn_loudness_device(vsyn_handle* h, const vsyn_loudness_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
+                         const uint64_t* frames, const float* d_pcm, uint64_t plane_stride, uint32_t channels,
+                         vsyn_loudness_record* d_records, double* d_z, double* d_weighted, uint64_t weighted_plane_stride, float* d_scaled,
+                         uint64_t scaled_plane_stride, void* hip_stream, const char** err);
+
+/* The measurement of the PCM of the MOST RECENT vsyn_submit_host* on this handle, as for vsyn_pcm_pitch_host: each segment resampled
+ * from in_rates[g] to out_rate first when out_rate != 0 (fs is then out_rate). records[S] receives the records (NULL: nothing is launched,
+ * only seg_blocks is filled); seg_blocks[S] (may be NULL with records given) each segment's block count; z (may be NULL) the z_j of
+ * all segments back to back, at most z_capacity of them (VSYN_ERR_INVALID with seg_blocks filled if it is too small). No PCM leaves the device. status as for vsyn_pcm_spectral_host.
+ * Synchronous. */
+int vsyn_pcm_loudness_host(vsyn_handle* h, const vsyn_loudness_spec* spec, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                           vsyn_loudness_record* records, double* z, uint64_t z_capacity, uint64_t* seg_blocks, vsyn_status* status,
+                           const char** err);
+
+/* The most general PCM host form: vsyn_pcm_trim_host (gate_is_split = 0: bounds_out) or vsyn_pcm_split_host (gate_is_split != 0:
+ * counts_out, intervals_out, intervals_stride) with the loudness step of "loudness" step 7 between the gate and conditioning. Every
+ * stage's spec may be NULL (gate, loud, cond) and out_rate 0: that stage is off; loud = NULL is the entry without the argument, bit
+ * for bit. With loud the output is one mono plane per segment, as with a gate or conditioning; loud needs VSYN_LOUD_NORMALIZE,
+ * VSYN_LOUD_MONO and in_rates, and excludes VSYN_COND_PEAK (VSYN_ERR_INVALID, nothing written). records_out[S] (may be NULL)
+ * receives the records. Behind a gate the call waits once more, for the gated frame counts. Synchronous. */
+int vsyn_pcm_chain_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond,
+                        uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, int format, void* out, uint64_t out_stride_frames,
+                        uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
+                        float* peaks_out, double* refs_out, vsyn_loudness_record* records_out, const char** err);
+
+/* The most general spectral host form: vsyn_pcm_trim_spectral_pcen_host (gate_is_split = 0) or vsyn_pcm_split_spectral_pcen_host
+ * (gate_is_split != 0) with the loudness step between the gate and conditioning; the rows are those of the normalised plane. NULL
+ * specs, loud = NULL, the checks and records_out as for vsyn_pcm_chain_host; frames_out (may be NULL) the frames behind the gate. A
+ * refused loudness spec leaves every output untouched, status included. Synchronous. */
+int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                                 const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen,
+                                 const vsyn_spectral_post* post, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                                 uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
+                                 uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                 vsyn_loudness_record* records_out, vsyn_status* status, const char** err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""ctypes plumbing of the corpus front-ends (features.py, spectral.py, pcm.py, pitch.py, frame_descriptors.py): the corpus entry points of libparseoggvorbis_amd.so
+"""ctypes plumbing of the corpus front-ends (features.py, spectral.py, pcm.py, pitch.py, frame_descriptors.py, loudness.py): the corpus entry points of libparseoggvorbis_amd.so
 and the per-file loop over the buffers they hand back (include/vorbis_synth_hip.h documents what they compute)."""
 import ctypes as C
 import os
@@ -45,7 +45,14 @@ def load():
                                                             C.POINTER(binding.PcmTrim), C.c_int, vp, vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_intervals_corpus", [u32, C.POINTER(binding.PcmTrim), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pitch_corpus", [u32, C.POINTER(binding.PitchSpec), vp, vp, vp, vp, vp]),
-                       ("ogg_vorbis_fdesc_corpus", [u32, C.POINTER(binding.FdescSpec), vp, vp, vp, vp, vp])):
+                       ("ogg_vorbis_fdesc_corpus", [u32, C.POINTER(binding.FdescSpec), vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_pcm_corpus_loud", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
+                                                       C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_spectral_corpus_loud", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPcen),
+                                                            C.POINTER(binding.SpectralPost), C.POINTER(binding.PcmCond),
+                                                            C.POINTER(binding.PcmTrim), C.c_int, C.POINTER(binding.LoudnessSpec), vp, vp, vp,
+                                                            vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_loudness_corpus", [u32, C.POINTER(binding.LoudnessSpec), C.c_int, vp, vp, vp, vp, vp, vp])):
         fn = getattr(lib, name)
         fn.argtypes = head + args + tail
         fn.restype = C.c_int

@@ -99,6 +99,18 @@ class FdescSpec(C.Structure):  # vsyn_fdesc_spec
                 ("roll_percent", C.c_double), ("zcr_threshold", C.c_double), ("amin", C.c_double)]
 
 
+class LoudnessSpec(C.Structure):  # vsyn_loudness_spec
+    _fields_ = [("options", C.c_uint32), ("channel_mode", C.c_uint32), ("target", C.c_double)]
+
+
+# vsyn_loudness_record
+LOUDNESS_RECORD_DTYPE = np.dtype([("zbar", "<f8"), ("zbar_a", "<f8"), ("blocks", "<u4"), ("blocks_abs", "<u4"), ("blocks_rel", "<u4"),
+                                  ("gain", "<f4"), ("status", "<u4"), ("reserved", "<u4")])
+VSYN_LOUD_NORMALIZE = 1
+VSYN_LOUD_SUM, VSYN_LOUD_MONO = 0, 1
+VSYN_LOUD_OK, VSYN_LOUD_NOT_FINITE, VSYN_LOUD_TOO_SHORT, VSYN_LOUD_SILENT, VSYN_LOUD_RATE_REFUSED = 0, 1, 2, 3, 4
+
+
 class Status(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("first_bad_packet", C.c_uint32)]
 
@@ -233,6 +245,8 @@ _SYMBOLS = [
     "vsyn_spectral_pcen_b", "vsyn_spectral_pcen_device", "vsyn_pcm_trim_spectral_pcen_host", "vsyn_pcm_split_spectral_pcen_host",
     "vsyn_pitch_num_frames", "vsyn_pitch_device", "vsyn_pcm_pitch_host",
     "vsyn_fdesc_num_frames", "vsyn_fdesc_device", "vsyn_pcm_fdesc_host",
+    "vsyn_loudness_num_blocks", "vsyn_loudness_coefficients", "vsyn_loudness_powers", "vsyn_loudness_device", "vsyn_pcm_loudness_host",
+    "vsyn_pcm_chain_host", "vsyn_pcm_chain_spectral_host",
 ]
 
 
@@ -348,6 +362,17 @@ def load():
     lib.vsyn_fdesc_num_frames.restype = u64
     lib.vsyn_fdesc_device.argtypes = [vp, C.POINTER(FdescSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_fdesc_host.argtypes = [vp, C.POINTER(FdescSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_loudness_num_blocks.argtypes = [u32, u64]
+    lib.vsyn_loudness_num_blocks.restype = u64
+    lib.vsyn_loudness_coefficients.argtypes = [u32, vp]
+    lib.vsyn_loudness_powers.argtypes = [u32, vp]
+    lib.vsyn_loudness_device.argtypes = [vp, C.POINTER(LoudnessSpec), u32, vp, vp, vp, u64, u32, vp, vp, vp, u64, vp, u64, vp, cpp]
+    lib.vsyn_pcm_loudness_host.argtypes = [vp, C.POINTER(LoudnessSpec), u32, vp, u32, vp, vp, u64, vp, C.POINTER(Status), cpp]
+    lib.vsyn_pcm_chain_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond), u32, vp, u32, C.c_int, vp,
+                                        u64, vp, vp, vp, vp, u64, vp, vp, vp, cpp]
+    lib.vsyn_pcm_chain_spectral_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
+                                                 C.POINTER(SpectralSpec), C.POINTER(SpectralPcen), C.POINTER(SpectralPost), u32, vp, u32, vp, u64,
+                                                 vp, vp, vp, vp, vp, u64, vp, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -692,6 +717,57 @@ class Synth:
         rates = _rates(in_rates)
         S, o = len(rates), _per_segment(len(rates), "refused")
         return self._rows_host(self.lib.vsyn_pcm_fdesc_host, (C.byref(spec), S, _ptr(rates), out_rate), S, 6, [o["refused"]], o)
+
+    def loudness_device(self, spec, sample_rates, frames, d_pcm, plane_stride, channels, d_records, d_z=None, d_weighted=None,
+                        weighted_plane_stride=0, d_scaled=None, scaled_plane_stride=0, stream=None):
+        """vsyn_loudness_device on device pointers (ints); sample_rates and frames are host sequences."""
+        rates, fr = _rates(sample_rates), np.ascontiguousarray(frames, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_loudness_device(self.h, _ref(spec), len(rates), _ptr(rates), _ptr(fr), d_pcm, plane_stride, channels, d_records, d_z,
+                                             d_weighted, weighted_plane_stride, d_scaled, scaled_plane_stride, stream, C.byref(err)), err)
+
+    def pcm_loudness_host(self, spec, in_rates, out_rate=0, blocks=False):
+        """vsyn_pcm_loudness_host over the last submit's segments: returns dict(rc, records [S] (LOUDNESS_RECORD_DTYPE), seg_blocks [S],
+        z (blocks=True: the block means back to back, else None), flags)."""
+        rates = _rates(in_rates)
+        S = len(rates)
+        rec, nb = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), np.zeros(max(1, S), np.uint64)
+        st, err = Status(), C.c_char_p()
+        head = (self.h, _ref(spec), S, _ptr(rates), out_rate)
+        z = None
+        if blocks:  # the size query first: nothing is launched for NULL records
+            _check(self.lib.vsyn_pcm_loudness_host(*head, None, None, 0, _ptr(nb), C.byref(st), C.byref(err)), err)
+            z = np.zeros(max(1, int(nb[:S].sum())), np.float64)
+        rc = self.lib.vsyn_pcm_loudness_host(*head, _ptr(rec), _ptr(z), 0 if z is None else len(z), _ptr(nb), C.byref(st), C.byref(err))
+        _check(rc, err, (VSYN_OK, VSYN_ERR_STREAM))
+        return dict(rc=rc, records=rec[:S], seg_blocks=nb[:S], z=None if z is None else z[:int(nb[:S].sum())], flags=st.flags)
+
+    def pcm_chain_host(self, gate, gate_is_split, loud, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_chain_host over the last submit's segments (gate / loud / cond may be None, but not all three): returns dict(pcm
+        [S][stride], frames [S], bounds [S][2], counts [S], intervals, peaks [S], refs [S], records [S])."""
+        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "bounds", "counts", "peaks", "refs")
+        rec, iv = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), []
+
+        def outs(t_max):
+            ivs = self._max_intervals(gate, t_max) if gate is not None and gate_is_split else 1
+            iv.append(np.zeros((max(1, S), ivs, 2), np.uint32))
+            return [o["bounds"], o["counts"], iv[0], ivs, o["peaks"], o["refs"], rec]
+        out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_host,
+                                     (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), S, _ptr(rates), out_rate, fmt), S, fmt, None, outs)
+        return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
+
+    def pcm_chain_spectral_host(self, gate, gate_is_split, loud, cond, spec, pcen, post, in_rates, out_rate=0):
+        """vsyn_pcm_chain_spectral_host over the last submit's segments (gate / loud / cond / pcen / post may be None): returns what
+        pcm_split_spectral_host returns, with bounds [S][2] and records [S]."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "frames", "bounds", "counts", "peaks", "refs")
+        rec = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE)
+        ivs = self._split_sizes(gate, S, rates if out_rate else None, out_rate)[1] if gate is not None and gate_is_split else 1
+        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
+        r = self._rows_host(self.lib.vsyn_pcm_chain_spectral_host,
+                            (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), C.byref(spec), _ref(pcen), _ref(post), S, _ptr(rates),
+                             out_rate), S, _post_dim(spec, post), [o["frames"], o["bounds"], o["counts"], iv, ivs, o["peaks"], o["refs"], rec], o)
+        return dict(r, intervals=self._intervals(o["counts"], iv, S), records=rec[:S])
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

@@ -24,6 +24,7 @@
 #include "vsyn_spectral_lin.h"
 #include "vsyn_spectral_post.h"
 #include "vsyn_pcen.h"
+#include "vsyn_loudness.h"
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
 #include "vsyn_trim.h"
@@ -131,6 +132,7 @@ struct vsyn_handle {
   SplitWs sl;                          // vsyn_split.h
   PitchWs pt;                          // vsyn_pitch.h
   FdescWs fd;                          // vsyn_fdesc.h
+  LoudWs ld;                           // vsyn_loudness.h
   // profiling
   bool profile = false;
   int profile_which = 1;  // 1 / 2: the fused kernel (steady / mixed workloads: same kernel), 3: residue VQ kernel
@@ -1429,6 +1431,32 @@ static int step_condition(vsyn_handle* h, uint32_t S, const vsyn_pcm_cond* cond,
   return VSYN_OK;
 }
 
+// The normaliser of a chain (loud != NULL): what the chain forms ask of its spec beyond loud_check, before anything is written.
+static int chain_loud_check(const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, const char** err) {
+  if (int rc = loud_check(loud, err)) return rc;
+  if (!(loud->options & VSYN_LOUD_NORMALIZE)) return fail(err, VSYN_ERR_INVALID, "the loudness step of a chain needs VSYN_LOUD_NORMALIZE and a target");
+  if (loud->channel_mode != VSYN_LOUD_MONO) return fail(err, VSYN_ERR_INVALID, "the loudness step of a chain measures the mono downmix (VSYN_LOUD_MONO)");
+  if (cond && (cond->options & VSYN_COND_PEAK)) return fail(err, VSYN_ERR_INVALID, "loudness normalisation and VSYN_COND_PEAK exclude each other");
+  if (S && !rates) return fail(err, VSYN_ERR_INVALID, "the loudness step needs the segments' sample rates");
+  return VSYN_OK;
+}
+
+// measured (the view's mono downmix, T[g] frames at rates[g]) and scaled to the target into h->ld's mono plane, the records on their
+// way to records_out; read on as the gate's plane is, with the frames the view had
+static int step_loudness(vsyn_handle* h, uint32_t S, const vsyn_loudness_spec* loud, const uint32_t* rates, const uint64_t* T, uint64_t plane,
+                         bool clear, vsyn_loudness_record* records_out, PcmView* v, const char** err) {
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * plane;
+  HIPCHK(h->ld.pcm.ensure(n + 1));
+  HIPCHK(h->ld.rec.ensure(S));
+  if (clear) HIPCHK(hipMemsetAsync(h->ld.pcm.p, 0, sizeof(float) * n, hs));
+  if (int rc = loud_launch(h->ld, h->device, loud, S, rates, T, v->pcm, v->plane, v->C, h->ld.rec.p, nullptr, nullptr, 0, h->ld.pcm.p, plane, hs, err))
+    return rc;
+  if (records_out) HIPCHK(hipMemcpyAsync(records_out, h->ld.rec.p, sizeof(vsyn_loudness_record) * S, hipMemcpyDeviceToHost, hs));
+  *v = PcmView{h->ld.pcm.p, plane, 1u, v->si, v->d_frames};
+  return VSYN_OK;
+}
+
 // The end of a PCM host form: the view's planes to out as they are (VSYN_PCM_F32: the last step cleared them first), or interleaved
 // and converted into s16 (vsyn_pcm_interleave_device's conversion, zeros past each segment's frames) and that; then the call's one wait.
 static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format, DevBuf<int16_t>& s16, void* out, const char** err) {
@@ -1451,11 +1479,15 @@ static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format
 // (gate, cond: NULL, out_rate: 0 for none), the last one into a plane of the caller's stride, the ones in front of it into planes
 // as long as the longest segment; that plane to out, and the frames behind the gate to frames_out.
 static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, uint32_t out_rate, int format,
-                        void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err) {
+                        void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err,
+                        const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr) {
+  if (loud)
+    if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
   if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
   if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
   if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
+  if (records_out) memset(records_out, 0, sizeof(vsyn_loudness_record) * S);
   // the lock covers the whole call: the stages' workspaces are the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
   uint64_t t_max;
@@ -1478,10 +1510,20 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   PcmView v = last_submit_view(h);
   DevBuf<int16_t>* s16 = &h->rs.s16;  // the last stage's
   if (out_rate)
-    if (int rc = step_resample(h, S, rates, out_rate, gate || cond ? inner : out_stride_frames, f32 && !gate && !cond, &v, err)) return rc;
+    if (int rc = step_resample(h, S, rates, out_rate, gate || cond || loud ? inner : out_stride_frames, f32 && !gate && !cond && !loud, &v, err)) return rc;
   if (gate) {
-    if (int rc = step_gate(h, S, g, cond ? inner : out_stride_frames, t_max, f32 && !cond, &v, err)) return rc;
+    if (int rc = step_gate(h, S, g, cond || loud ? inner : out_stride_frames, t_max, f32 && !cond && !loud, &v, err)) return rc;
     s16 = g.split ? &h->sl.e.s16 : &h->tr.s16;
+  }
+  if (loud) {  // the stage's table needs each segment's frames: behind a gate the chain waits here for the gate's read-backs
+    std::vector<uint64_t> T(frames_out, frames_out + S);
+    if (gate) {
+      HIPCHK(hipStreamSynchronize(h->host_stream));
+      for (uint32_t s = 0; s < S; ++s) T[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
+    }
+    const std::vector<uint32_t> ld_rates = stage_rates(S, rates, out_rate);
+    if (int rc = step_loudness(h, S, loud, ld_rates.data(), T.data(), cond ? inner : out_stride_frames, f32 && !cond, records_out, &v, err)) return rc;
+    s16 = &h->ld.s16;
   }
   if (cond) {
     if (int rc = step_condition(h, S, cond, out_stride_frames, t_max, f32, peaks_out, &v, err)) return rc;
@@ -1530,8 +1572,11 @@ static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, con
 static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen,
                          const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
                          uint64_t* seg_rows,
-                         uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err) {
+                         uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err, const vsyn_loudness_spec* loud = nullptr,
+                         vsyn_loudness_record* records_out = nullptr) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (loud)  // (first: a refused loudness spec writes nothing, the status included)
+    if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
   status_reset(status);
   if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
   std::vector<uint32_t> sp_rates = stage_rates(S, rates, out_rate);
@@ -1553,6 +1598,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
   if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
+  if (records_out) memset(records_out, 0, sizeof(vsyn_loudness_record) * S);
   if (gate && gate->bounds) memset(gate->bounds, 0, sizeof(uint32_t) * 2u * S);
   if (gate && gate->refs) memset(gate->refs, 0, sizeof(double) * S);
   // the lock covers the whole call: the stages' workspaces are the handle's, and the PCM must stay that of the last submit
@@ -1600,6 +1646,8 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
     if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
     if (int rc = step_resample(h, S, rates, out_rate, t_max, false, &v, err)) return rc;
   }
+  if (loud)
+    if (int rc = step_loudness(h, S, loud, sp_rates.data(), T.data(), t_max, false, records_out, &v, err)) return rc;
   if (cond)
     if (int rc = step_condition(h, S, cond, t_max, t_max, false, peaks_out, &v, err)) return rc;
   return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err);
@@ -1858,6 +1906,43 @@ int vsyn_pcm_split_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim,
                        peaks_out, status, err);
 }
 
+// The most general PCM and spectral host forms: every stage's spec, NULL for a stage that is off; the gate is a trim, or with
+// gate_is_split != 0 a split. With loud = NULL they are the entries without the argument.
+int vsyn_pcm_chain_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond,
+                        uint32_t S, const uint32_t* in_rates, uint32_t out_rate, int format, void* out, uint64_t out_stride_frames,
+                        uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
+                        float* peaks_out, double* refs_out, vsyn_loudness_record* records_out, const char** err) {
+  if (!loud)
+    return gate && gate_is_split ? vsyn_pcm_split_host(h, gate, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, counts_out,
+                                                       intervals_out, intervals_stride, peaks_out, refs_out, err)
+                                 : vsyn_pcm_trim_host(h, gate, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, bounds_out,
+                                                      peaks_out, refs_out, err);
+  if (!h) return cond_no_handle(err);
+  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
+                      records_out);
+}
+
+int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                                 const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen,
+                                 const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                                 uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
+                                 uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                 vsyn_loudness_record* records_out, vsyn_status* status, const char** err) {
+  if (!loud)
+    return gate && gate_is_split
+               ? vsyn_pcm_split_spectral_pcen_host(h, gate, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, frames_out,
+                                                   counts_out, intervals_out, intervals_stride, peaks_out, refs_out, status, err)
+               : vsyn_pcm_trim_spectral_pcen_host(h, gate, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, bounds_out,
+                                                  peaks_out, refs_out, status, err);
+  if (!h) return cond_no_handle(err);
+  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
+                       gate ? frames_out : nullptr, peaks_out, status, err, loud, records_out);
+}
+
 // ---- pitch (vsyn_pitch.h) ----
 
 uint64_t vsyn_pitch_num_frames(const vsyn_pitch_spec* spec, uint64_t frames) {
@@ -1932,6 +2017,80 @@ int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t S,
         return fdesc_launch(h->fd, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->fd.rows.p, nullptr, h->fd.refused.p, hs, err);
       },
       S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
+}
+
+// ---- loudness (vsyn_loudness.h) ----
+
+uint64_t vsyn_loudness_num_blocks(uint32_t sample_rate, uint64_t frames) { return loud_num_blocks(sample_rate, frames); }
+
+int vsyn_loudness_coefficients(uint32_t sample_rate, double* out) {
+  if (!out || sample_rate < LOUD_MIN_RATE) return VSYN_ERR_INVALID;
+  loud_coefficients(sample_rate, out);
+  return VSYN_OK;
+}
+
+int vsyn_loudness_powers(uint32_t sample_rate, double* out) {
+  if (!out || sample_rate < LOUD_MIN_RATE) return VSYN_ERR_INVALID;
+  double k[10], M[LOUD_LEVELS + 1u][16];
+  loud_coefficients(sample_rate, k);
+  loud_powers(k, M);
+  memcpy(out, M, sizeof(M));
+  return VSYN_OK;
+}
+
+int vsyn_loudness_device(vsyn_handle* h, const vsyn_loudness_spec* spec, uint32_t S, const uint32_t* sample_rates, const uint64_t* frames,
+                         const float* d_pcm, uint64_t plane_stride, uint32_t channels, vsyn_loudness_record* d_records, double* d_z,
+                         double* d_weighted, uint64_t weighted_plane_stride, float* d_scaled, uint64_t scaled_plane_stride, void* hip_stream,
+                         const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = loud_check(spec, err)) return rc;
+  if (d_scaled && !(spec->options & VSYN_LOUD_NORMALIZE)) return fail(err, VSYN_ERR_INVALID, "a scaled plane needs VSYN_LOUD_NORMALIZE and a target");
+  if (S == 0) return VSYN_OK;
+  if (!sample_rates || !frames || !d_pcm || !d_records || plane_stride == 0 || channels == 0 || channels > 255)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  if ((d_weighted && weighted_plane_stride == 0) || (d_scaled && scaled_plane_stride == 0))
+    return fail(err, VSYN_ERR_INVALID, "an output plane has a zero stride");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return loud_launch(h->ld, h->device, spec, S, sample_rates, frames, d_pcm, plane_stride, channels, d_records, d_z, d_weighted,
+                     weighted_plane_stride, d_scaled, scaled_plane_stride, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_loudness_host(vsyn_handle* h, const vsyn_loudness_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
+                           vsyn_loudness_record* records, double* z, uint64_t z_capacity, uint64_t* seg_blocks, vsyn_status* status,
+                           const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = loud_check(spec, err)) return rc;  // (first: an invalid spec writes nothing, the status included)
+  if (S && !in_rates) return fail(err, VSYN_ERR_INVALID, "in_rates is NULL");
+  if (S && !records && !seg_blocks) return fail(err, VSYN_ERR_INVALID, "records and seg_blocks are both NULL");
+  status_reset(status);
+  if (int rc = chain_check(nullptr, nullptr, S, in_rates, out_rate, err)) return rc;
+  const std::vector<uint32_t> rates = stage_rates(S, in_rates, out_rate);
+  // the lock covers the whole call: the resample workspace and the stage's are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T(S);
+  uint64_t t_max, total = 0;
+  if (int rc = last_submit_frames(h, S, in_rates, out_rate, T.data(), &t_max, err)) return rc;
+  for (uint32_t g = 0; g < S; ++g) {
+    const uint64_t nb = loud_num_blocks(rates[g], T[g]);
+    if (seg_blocks) seg_blocks[g] = nb;
+    total += nb;
+  }
+  if (S == 0 || !records) return VSYN_OK;
+  if (z && total > z_capacity) return fail(err, VSYN_ERR_INVALID, "z buffer too small: %llu blocks", (unsigned long long)total);
+  t_max = std::max<uint64_t>(t_max, 1);
+  if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  hipStream_t hs = h->host_stream;
+  PcmView v = last_submit_view(h);
+  if (out_rate)
+    if (int rc = step_resample(h, S, in_rates, out_rate, t_max, false, &v, err)) return rc;
+  HIPCHK(h->ld.rec.ensure(S));
+  if (z) HIPCHK(h->ld.z.ensure(total + 1));
+  if (int rc = loud_launch(h->ld, h->device, spec, S, rates.data(), T.data(), v.pcm, v.plane, v.C, h->ld.rec.p, z ? h->ld.z.p : nullptr, nullptr, 0,
+                           nullptr, 0, hs, err))
+    return rc;
+  HIPCHK(hipMemcpyAsync(records, h->ld.rec.p, sizeof(vsyn_loudness_record) * S, hipMemcpyDeviceToHost, hs));
+  if (z && total) HIPCHK(hipMemcpyAsync(z, h->ld.z.p, sizeof(double) * total, hipMemcpyDeviceToHost, hs));
+  return sync_status_into(h, status, err);
 }
 
 }  // extern "C"

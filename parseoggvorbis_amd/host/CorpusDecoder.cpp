@@ -80,6 +80,7 @@ bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
 bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
 bool pitch_run(const CorpusOptions& o) { return o.pitch.frame_length != 0; }
 bool fdesc_run(const CorpusOptions& o) { return o.fdesc.n_fft != 0; }
+bool loudness_run(const CorpusOptions& o) { return o.loudness; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
 uint32_t spectral_dim(const CorpusOptions& o) {
@@ -407,6 +408,9 @@ struct Feeder {
     std::vector<uint32_t> counts, iv;  // split run: per file its intervals, iv[(s * iv_stride + k) * 2 + {0, 1}]
     uint64_t iv_stride = 0;
     uint64_t plane = 0;
+    std::vector<vsyn_loudness_record> loud;  // loudness run: per file its record,
+    std::vector<uint64_t> loud_nb;           // its blocks
+    std::vector<double> loud_z;              // and with loudness_blocks the block means of all files back to back
   };
 
   // Synthesis of the packed batch. The PCM comes back as f32 planes unless a later stage reads it on the device (VSYN_SUBMIT_KEEP_PCM).
@@ -488,6 +492,32 @@ struct Feeder {
       if (o.err[s].empty() && !std::isfinite(refs[s])) o.err[s] = "trim: the PCM holds a sample that is not finite";
   }
 
+  // A file the loudness stage refused (include/vorbis_synth_hip.h, "loudness", step 5) gets an error of its own, by name. A silent
+  // file is measured, but cannot be normalised.
+  void refuse_loud(Outcome& o, bool normalise, const std::vector<uint32_t>& rates) {
+    for (size_t s = 0; s < o.loud.size(); ++s) {
+      if (!o.err[s].empty()) continue;
+      const uint32_t sr = opts.resample_rate && rates[s] ? opts.resample_rate : rates[s];
+      char buf[160];
+      switch (o.loud[s].status) {
+        case VSYN_LOUD_NOT_FINITE: o.err[s] = "loudness: the PCM holds a sample that is not finite"; break;
+        case VSYN_LOUD_TOO_SHORT:
+          snprintf(buf, sizeof(buf), "loudness: too short: %llu frames at %u Hz are fewer than four hops of 100 ms",
+                   (unsigned long long)o.frames[s], sr);
+          o.err[s] = buf;
+          break;
+        case VSYN_LOUD_RATE_REFUSED:
+          snprintf(buf, sizeof(buf), "loudness: sample rate %u below 4000 Hz", sr);
+          o.err[s] = buf;
+          break;
+        case VSYN_LOUD_SILENT:
+          if (normalise) o.err[s] = "loudness: silent: no block above -70 LUFS, nothing to normalise";
+          break;
+        default: break;
+      }
+    }
+  }
+
   // A split run's interval arrays, sized for the longest file of the submit (its unsplit frames).
   void size_intervals(uint32_t S, Outcome& o) {
     uint64_t t_max = 0;
@@ -517,7 +547,28 @@ struct Feeder {
     std::vector<float> peaks(S, 0.f);
     const int fmt = opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32;
     void* out = opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p;
-    if (opts.split || opts.trim) {  // a gate in front: the frames delivered are the joined or trimmed ones, or with intervals_only nothing is
+    if (opts.loudness_norm) {  // the one form with every stage's spec: a gate or none, the normaliser, conditioning or none
+      std::vector<double> refs(S);
+      const bool gated = opts.split || opts.trim;
+      if (opts.split) size_intervals(S, o);
+      if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);
+      o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+      const int rc = vsyn_pcm_chain_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.loudness_spec, trim_cond(), S,
+                                         rates.data(), opts.resample_rate, fmt, out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr,
+                                         opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(),
+                                         refs.data(), o.loud.data(), &err);
+      if (rc != VSYN_OK) return OkOrError(std::string("GPU loudness layer: ") + (err ? err : "normalisation failed"));
+      if (gated) {
+        for (uint32_t s = 0; s < S; ++s) {
+          CHECK(got[s] <= o.frames[s]);
+          o.frames[s] = got[s];
+        }
+        refuse_refs(refs, o);
+      } else {
+        CHECK(got == o.frames);
+      }
+      refuse_loud(o, true, rates);
+    } else if (opts.split || opts.trim) {  // a gate in front: the frames delivered are the joined or trimmed ones, or with intervals_only nothing is
       std::vector<double> refs(S);
       int rc;
       if (opts.split) {
@@ -592,7 +643,13 @@ struct Feeder {
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
     const vsyn_spectral_post* post = post_run(opts) ? &opts.post : nullptr;
     int rc;
-    if (opts.pcen)  // the two forms with the PCEN stage in them; off, today's entries
+    if (opts.loudness_norm) {  // the one form with every stage's spec
+      o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+      rc = vsyn_pcm_chain_spectral_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.loudness_spec, cond, &opts.spectral,
+                                        opts.pcen ? &opts.pcen_spec : nullptr, post, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
+                                        g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
+                                        opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(), o.loud.data(), &st, &err);
+    } else if (opts.pcen)  // the two forms with the PCEN stage in them; off, today's entries
       rc = opts.split ? vsyn_pcm_split_spectral_pcen_host(g.handle, &opts.trim_spec, cond, &opts.spectral, &opts.pcen_spec, post, S, rates.data(),
                                                           opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(), o.counts.data(),
                                                           o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &st, &err)
@@ -627,6 +684,7 @@ struct Feeder {
       }
     }
     if (opts.condition) refuse_peaks(peaks, o);
+    if (opts.loudness_norm && rc == VSYN_OK) refuse_loud(o, true, rates);
     return OkOrError();
   }
 
@@ -688,10 +746,35 @@ struct Feeder {
     });
   }
 
+  // Loudness run: each file's record (and block means) from the PCM still on the device (vsyn_pcm_loudness_host, resampled first in
+  // a resampled run). A silent file is measured; a file the stage refuses gets an error of its own, by name.
+  OkOrError loudness_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    std::vector<uint32_t> rates(S);
+    for (uint32_t s = 0; s < S; ++s) rates[s] = o.err[s].empty() ? g.pending[s]->header.audio_sample_rate : 0;
+    o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+    o.loud_nb.assign(S, 0);
+    vsyn_status st;
+    const char* err = nullptr;
+    if (opts.loudness_blocks) {  // the size query first: nothing is launched for NULL records
+      if (vsyn_pcm_loudness_host(g.handle, &opts.loudness_spec, S, rates.data(), opts.resample_rate, nullptr, nullptr, 0, o.loud_nb.data(), &st, &err) !=
+          VSYN_OK)
+        return OkOrError(std::string("GPU loudness layer: ") + (err ? err : "loudness failed"));
+      uint64_t total = 0;
+      for (uint32_t s = 0; s < S; ++s) total += o.loud_nb[s];
+      o.loud_z.assign(total + 1, 0.0);
+    }
+    if (vsyn_pcm_loudness_host(g.handle, &opts.loudness_spec, S, rates.data(), opts.resample_rate, o.loud.data(),
+                               opts.loudness_blocks ? o.loud_z.data() : nullptr, o.loud_z.size(), o.loud_nb.data(), &st, &err) != VSYN_OK)
+      return OkOrError(std::string("GPU loudness layer: ") + (err ? err : "loudness failed"));
+    refuse_loud(o, false, rates);
+    return OkOrError();
+  }
+
   // A synthesis run's file: its PCM (or, for a spectral, pitch or frame descriptor run, its rows) to the callbacks.
   OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
     const uint32_t C = opts.condition ? 1u : g.channels;  // channels delivered
-    const bool spectral = spectral_run(opts) || pitch_run(opts) || fdesc_run(opts);
+    const bool spectral = spectral_run(opts) || pitch_run(opts) || fdesc_run(opts) || loudness_run(opts);
     const uint64_t frames = o.frames[s], pl = o.plane;
     if (opts.condition) out.channels = 1;
     std::vector<DataRange<const float>> chans(C);
@@ -717,6 +800,14 @@ struct Feeder {
     out.status = o.err[s].empty() ? r.status : OkOrError(o.err[s]);
     if (opts.resample_rate) out.sample_rate = opts.resample_rate;
     stats.frames += frames;
+    if (o.err[s].empty() && s < o.loud.size()) out.loudness = o.loud[s];
+    if (loudness_run(opts)) {  // the record and the block means: nothing goes to the callbacks; row0 counts the blocks in front
+      if (o.err[s].empty() && s < o.loud.size()) {
+        if (opts.loudness_blocks) out.loudness_blocks.assign(o.loud_z.begin() + row0, o.loud_z.begin() + row0 + o.loud_nb[s]);
+      }
+      if (s < o.loud_nb.size()) row0 += o.loud_nb[s];
+      return OkOrError();
+    }
     if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : fdesc_run(opts) ? 6u : spectral_dim(opts));
     if (!callbacks || !o.err[s].empty() || opts.intervals_only) return OkOrError();
     std::lock_guard<std::mutex> lk(callbacks_mu);
@@ -732,8 +823,8 @@ struct Feeder {
     if (g.pending.empty()) return OkOrError();
     if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
-    const bool pitch = pitch_run(opts), fdesc = fdesc_run(opts);
-    const bool spectral = spectral_run(opts) || pitch || fdesc;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
+    const bool pitch = pitch_run(opts), fdesc = fdesc_run(opts), loud = loudness_run(opts);
+    const bool spectral = spectral_run(opts) || pitch || fdesc || loud;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
     const bool cond = opts.condition;               // ... and until it is conditioned
     double t0 = now_s();
@@ -763,7 +854,8 @@ struct Feeder {
       if (resample) CHECK_ERR(resample_stage(g, spectral || cond, o));
       else if (!cond) CHECK_ERR(fetch(g, o));
       if (cond && !spectral) CHECK_ERR(condition_stage(g, o));
-      if (pitch) CHECK_ERR(pitch_stage(g, o));
+      if (loud) CHECK_ERR(loudness_stage(g, o));
+      else if (pitch) CHECK_ERR(pitch_stage(g, o));
       else if (fdesc) CHECK_ERR(fdesc_stage(g, o));
       else if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
@@ -1138,11 +1230,12 @@ struct SplitOuts {
 // A rows run (features or spectral, as set in opts).
 int rows_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts, float** rows_out,
                 uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out,
-                uint64_t* bounds_out = nullptr, const SplitOuts* so = nullptr) {
+                uint64_t* bounds_out = nullptr, const SplitOuts* so = nullptr, vsyn_loudness_record* records_out = nullptr) {
   if (so) so->begin(num_files);
   const int rc = malloc_corpus(name, datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
                                [&](size_t i, const CorpusFileResult& res, bool bad) {
                                  if (rows_count_out) rows_count_out[i] = res.feature_rows;
+                                 if (records_out) records_out[i] = bad ? vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u} : res.loudness;
                                  give_bounds(bounds_out, i, res, bad);
                                  if (so && so->frames_out) so->frames_out[i] = bad ? 0 : res.frames;
                                  if (so) give_intervals(so->intervals_out, so->intervals_count_out, i, res, bad);
@@ -1165,13 +1258,20 @@ extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const siz
 
 namespace {
 
+// What a run with the normaliser asks of its spec (include/vorbis_synth_hip.h, "loudness", step 7).
+bool loud_norm_spec_ok(const vsyn_loudness_spec* l, const vsyn_pcm_cond* cond) {
+  return l->options == VSYN_LOUD_NORMALIZE && l->channel_mode == VSYN_LOUD_MONO && l->target >= -70.0 && l->target <= 0.0 &&
+         !(cond && (cond->options & VSYN_COND_PEAK));
+}
+
 // ogg_vorbis_spectral_corpus (target_rate 0) and ogg_vorbis_spectral_corpus_sr; fn: the entry point, for its refusal text.
 int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                     const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
                     const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr,
                     const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr, const vsyn_pcm_trim* split = nullptr,
-                    const SplitOuts* so = nullptr, const vsyn_spectral_pcen* pcen = nullptr) {
+                    const SplitOuts* so = nullptr, const vsyn_spectral_pcen* pcen = nullptr, const vsyn_loudness_spec* loud = nullptr,
+                    vsyn_loudness_record* records_out = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
@@ -1197,8 +1297,14 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
     opts.condition = opts.split = true;  // the rows come from the joined mono plane
     opts.trim_spec = *split;
   }
+  if (loud) {
+    if (!loud_norm_spec_ok(loud, opts.condition ? &opts.cond : nullptr))
+      return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid loudness spec (a target in [-70, 0], the mono downmix, no peak)", error_out);
+    opts.loudness_norm = true;
+    opts.loudness_spec = *loud;
+  }
   return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out,
-                     bounds_out, split ? so : nullptr);
+                     bounds_out, split ? so : nullptr, records_out);
 }
 
 }  // namespace
@@ -1269,7 +1375,7 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
                uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
                uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                double* stats_out, const char** error_out, const vsyn_pcm_trim* split = nullptr, bool intervals_only = false,
-               const SplitOuts* so = nullptr);
+               const SplitOuts* so = nullptr, const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr);
 
 }  // namespace
 
@@ -1347,7 +1453,8 @@ namespace {
 int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders, uint32_t files_per_submit, int device,
                uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
                uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
-               double* stats_out, const char** error_out, const vsyn_pcm_trim* split, bool intervals_only, const SplitOuts* so) {
+               double* stats_out, const char** error_out, const vsyn_pcm_trim* split, bool intervals_only, const SplitOuts* so,
+               const vsyn_loudness_spec* loud, vsyn_loudness_record* records_out) {
   if (so) so->begin(num_files);
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
     return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
@@ -1369,9 +1476,17 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
     opts.intervals_only = intervals_only;
     opts.trim_spec = *split;
   }
+  if (loud) {
+    if (!loud_norm_spec_ok(loud, cond) || intervals_only)
+      return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus_loud: invalid loudness spec (a target in [-70, 0], the mono downmix, no peak)",
+                         error_out);
+    opts.condition = opts.loudness_norm = true;  // one mono plane per file
+    opts.loudness_spec = *loud;
+  }
   const int rc = malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
                                [&](size_t i, const CorpusFileResult& res, bool bad) {
                                  if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                                 if (records_out) records_out[i] = bad ? vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u} : res.loudness;
                                  if (channels_out) channels_out[i] = res.channels;
                                  if (rate_out) rate_out[i] = res.sample_rate;
                                  give_bounds(bounds_out, i, res, bad);
@@ -1414,6 +1529,69 @@ extern "C" int ogg_vorbis_fdesc_corpus(const uint8_t* const* datas, const size_t
                          if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
                          if (frames_out) frames_out[i] = bad ? 0 : res.frames;
                          if (rate_out) rate_out[i] = res.sample_rate;
+                       });
+}
+
+extern "C" int ogg_vorbis_pcm_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                          const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, void** pcm_out,
+                                          uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out,
+                                          uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out,
+                                          uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  const bool split = gate && gate_is_split;
+  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
+                    frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
+                    &so, loud, records_out);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                               uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                               const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_pcm_cond* cond,
+                                               const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, float** rows_out,
+                                               uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
+                                               uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                               const char** error_out_per_file, double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.frames_out = frames_out;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  so.begin(num_files);
+  const bool split = gate && gate_is_split;
+  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
+  return spectral_corpus("ogg_vorbis_spectral_corpus_loud", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
+                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
+                         split ? gate : nullptr, &so, pcen, loud, records_out);
+}
+
+extern "C" int ogg_vorbis_loudness_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_loudness_spec* spec,
+                                          int want_blocks, double** blocks_out, uint64_t* blocks_count_out, vsyn_loudness_record* records_out,
+                                          uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file,
+                                          double* stats_out, const char** error_out) {
+  if (!spec || (spec->options & ~VSYN_LOUD_NORMALIZE) || spec->channel_mode > VSYN_LOUD_MONO ||
+      ((spec->options & VSYN_LOUD_NORMALIZE) && !(spec->target >= -70.0 && spec->target <= 0.0)))
+    return refuse_call((void**)blocks_out, num_files, "ogg_vorbis_loudness_corpus: invalid loudness spec", error_out);
+  if (want_blocks && !blocks_out) return refuse_call(nullptr, num_files, "ogg_vorbis_loudness_corpus: blocks wanted, blocks_out NULL", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  opts.loudness = true;
+  opts.loudness_blocks = want_blocks != 0;
+  opts.loudness_spec = *spec;
+  opts.resample_rate = target_rate;
+  return malloc_corpus("loudness", datas, lens, num_files, opts, (void**)blocks_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (records_out) records_out[i] = bad ? vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u} : res.loudness;
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                         const size_t n = bad || !want_blocks ? 0 : res.loudness_blocks.size();
+                         if (blocks_count_out) blocks_count_out[i] = n;
+                         if (n && blocks_out) {
+                           blocks_out[i] = (double*)malloc(n * sizeof(double));
+                           if (blocks_out[i]) memcpy(blocks_out[i], res.loudness_blocks.data(), n * sizeof(double));
+                           else if (blocks_count_out) blocks_count_out[i] = 0;
+                         }
                        });
 }
 

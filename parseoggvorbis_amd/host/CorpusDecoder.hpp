@@ -40,6 +40,8 @@ struct CorpusFileResult {
   uint64_t feature_rows = 0;  // CorpusOptions::features / spectral: rows delivered
   uint64_t trim_start = 0, trim_end = 0;  // CorpusOptions::trim: the samples kept, [trim_start, trim_end) of the (resampled) signal
   std::vector<uint32_t> intervals;        // CorpusOptions::split: (start, end) of every non-silent interval, in samples of that signal
+  vsyn_loudness_record loudness = {0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u};  // CorpusOptions::loudness: the file's record
+  std::vector<double> loudness_blocks;    // ... and with loudness_blocks its block means z_j
 };
 
 struct CorpusCallbacks {
@@ -122,6 +124,17 @@ struct CorpusOptions {
   // (include/vorbis_synth_hip.h, "frame descriptors": vsyn_pcm_fdesc_host), delivered through gotFileFeatures with dim 6. A file with
   // a sample that is not finite fails alone. Excludes what a pitch run excludes, and pitch.
   vsyn_fdesc_spec fdesc = {0, 0, 0, 0, 0.0, 0.0, 0.0};
+  // loudness run (loudness): as a pitch run, but each file's integrated loudness record (include/vorbis_synth_hip.h, "loudness":
+  // vsyn_pcm_loudness_host, resampled first with resample_rate; loudness_spec.channel_mode picks the planes or their downmix) into
+  // CorpusFileResult::loudness, and with loudness_blocks the block means into CorpusFileResult::loudness_blocks; nothing goes to the
+  // callbacks and no PCM crosses the bus. A silent file is measured (status VSYN_LOUD_SILENT); a file that is too short, holds a
+  // sample that is not finite or has a rate below 4000 Hz fails alone, by name. Excludes what a pitch run excludes, pitch and fdesc.
+  // loudness_norm (a PCM run with condition, or a spectral run): each file's mono plane is normalised to loudness_spec.target on
+  // the device between the gate and conditioning ("loudness", step 7: VSYN_LOUD_NORMALIZE, VSYN_LOUD_MONO; excludes VSYN_COND_PEAK);
+  // the record goes to CorpusFileResult::loudness. A file the stage refuses, a silent one included, fails alone, by name. The
+  // default is off: today's output and today's entry points.
+  bool loudness = false, loudness_blocks = false, loudness_norm = false;
+  vsyn_loudness_spec loudness_spec = {0u, VSYN_LOUD_SUM, 0.0};
 };
 
 struct CorpusStats {
@@ -246,6 +259,31 @@ int ogg_vorbis_spectral_corpus_pcen(const uint8_t* const* datas, const size_t* l
                                     const vsyn_pcm_trim* gate, int gate_is_split, float** rows_out, uint64_t* rows_count_out,
                                     uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
                                     uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
+// The loudness run (CorpusOptions::loudness): decode, resample (target_rate != 0), measure; no PCM comes back from the device.
+// records_out[num_files] each file's record (zeros for a failed file); with want_blocks != 0 blocks_out[i] is a malloc'd array of
+// blocks_count_out[i] block means (ogg_vorbis_features_free; NULL for none), else blocks_out may be NULL; frames_out / rate_out: each
+// file's (resampled) length and rate. Same output contract.
+int ogg_vorbis_loudness_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                               uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_loudness_spec* spec, int want_blocks,
+                               double** blocks_out, uint64_t* blocks_count_out, vsyn_loudness_record* records_out, uint64_t* frames_out,
+                               uint32_t* rate_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
+// The PCM run and the spectral run with every stage's spec in one call, the loudness normaliser among them (loud != NULL:
+// CorpusOptions::loudness_norm; NULL means off, as for every other spec): the arguments of ogg_vorbis_pcm_corpus_trim / _split and of
+// ogg_vorbis_spectral_corpus_pcen, the gate a trim or with gate_is_split != 0 a split, plus records_out[num_files] (may be NULL),
+// each file's loudness record in front of the gain (zeros for a failed file). Same output contract.
+int ogg_vorbis_pcm_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                               uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                               const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, void** pcm_out, uint64_t* frames_out,
+                               uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint32_t** intervals_out,
+                               uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                               const char** error_out_per_file, double* stats_out, const char** error_out);
+int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
+                                    const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_pcm_cond* cond,
+                                    const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, float** rows_out,
+                                    uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
+                                    uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                    const char** error_out_per_file, double* stats_out, const char** error_out);
 // The intervals alone (CorpusOptions::intervals_only): decode, resample (target_rate != 0), frame energies, intervals; no PCM comes
 // back from the device. frames_out / rate_out: each file's (resampled) length and rate; intervals_out / intervals_count_out as above.
 int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

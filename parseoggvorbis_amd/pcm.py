@@ -94,6 +94,29 @@ def trim_spec(trim_db=None, trim_frame_length=2048, trim_hop_length=512, trim_in
     return PcmTrim(int(trim_frame_length), int(trim_hop_length), float(trim_db))
 
 
+def loudness_args(loudness_normalize, loudness, cond, error=PcmError):
+    """Checks the normaliser's arguments (include/vorbis_synth_hip.h, "loudness", steps 6 and 7) and returns the C spec
+    (binding.LoudnessSpec: the mono downmix, the target), or None for loudness_normalize=None: the stage is off. loudness None or a
+    list; cond: the call's conditioning spec, whose peak normalisation the normaliser excludes."""
+    from .loudness import loudness_spec
+    if loudness is not None and not isinstance(loudness, list):
+        raise error("loudness must be None or a list, got %r" % (loudness,))
+    if loudness_normalize is None:
+        return None
+    spec = loudness_spec("mono", loudness_normalize, lambda msg: error(str(msg).replace("target", "loudness_normalize")))
+    if cond.options & COND_PEAK:
+        raise error("loudness_normalize and peak_normalize exclude each other: two level controls")
+    return spec
+
+
+def give_loudness(loudness, records, results):
+    """loudness[:] = each file's measured LUFS (in front of the gain) from the run's records; None for a failed file, and for every
+    file with the stage off (records None)."""
+    if loudness is not None:
+        from .loudness import lufs_of
+        loudness[:] = [None if records is None or isinstance(r, Exception) else float(lufs_of(records[i]["zbar"])) for i, r in enumerate(results)]
+
+
 def give_trim_index(trim_index, bounds, results):
     """trim_index[:] = one (start, end) per file from the run's bounds array; None for a file that failed, and for every file
     with the stage off (bounds None)."""
@@ -130,7 +153,8 @@ _load = _corpus.load
 
 def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0, device=0, errors="raise", files_per_submit=64,
                   stats=None, mono=False, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048, trim_hop_length=512,
-                  trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None):
+                  trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None, loudness_normalize=None,
+                  loudness=None):
     """PCM of many Ogg Vorbis files in one corpus run: a list of (pcm, sr) tuples. pcm is float32 (channels, frames), or int16
     (frames, channels) with ov_read's conversion; sr is the rate of the returned PCM. sr=None keeps each file's own rate (the
     PCM is bit for bit that of ogg_vorbis_decode_corpus); an integer resamples every file to it on the GPU. errors="raise": the
@@ -148,7 +172,13 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     split_db=d (instead of trim_db, with split_frame_length and split_hop_length; needs mono=True): every stretch of such frames is
     removed, not the head and the tail alone: pcm is the concatenation of y[start:end] over librosa.effects.split(y, top_db=d)'s
     intervals, and the peak and the pre-emphasis are those of that joined signal. split_index (optional list) receives one (n, 2)
-    int64 array of (start, end) per file (None for a failed file, and for every file with the stage off)."""
+    int64 array of (start, end) per file (None for a failed file, and for every file with the stage off).
+    loudness_normalize=L (a number of LUFS in [-70, 0]; needs mono=True, excludes peak_normalize): the mono signal, behind the
+    resampler and trim_db / split_db and in front of the pre-emphasis, is scaled by one gain so that its integrated loudness (ITU-R
+    BS.1770-4, as get_loudness_batch(channels="mono") measures it on that signal) is L; it is not clipped. loudness (optional list)
+    receives the measured LUFS per file, in front of the gain (None for a failed file, and for every file with the stage off). A
+    file that is shorter than 400 ms, silent (nothing above -70 LUFS), not finite or below 4000 Hz fails alone, by name. With
+    loudness_normalize=None nothing is launched and the call takes the entry points it took without the argument."""
     _corpus.check_errors(errors)
     target = check_sr(sr)
     name = _format(dtype)
@@ -163,6 +193,9 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim)
     if not mono and split is not None:
         raise PcmError("split_db acts on the mono signal: pass mono=True")
+    loud = loudness_args(loudness_normalize, loudness, cond)
+    if not mono and loud is not None:
+        raise PcmError("loudness_normalize acts on the mono signal: pass mono=True")
     lib = _load()
     n = len(list_of_bytes)
     frames = np.zeros(n, np.uint64)
@@ -178,6 +211,23 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
         return _corpus.copy_into(a, p), int(rates[i])
 
     args = (threads, feeders, files_per_submit, device, target, FORMATS[name])
+    if loud is not None:  # the one entry with every stage's spec (NULL: off)
+        from .binding import LOUDNESS_RECORD_DTYPE
+        ib = _corpus.IntervalBuffers(lib, n)
+        bounds, records = np.zeros((max(n, 1), 2), np.uint64), np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
+        gate = split if split is not None else trim
+        try:
+            res = _corpus.run(lib, lib.ogg_vorbis_pcm_corpus_loud, list_of_bytes,
+                              args + (C.byref(cond) if cond.options else None, None if gate is None else C.byref(gate), int(split is not None),
+                                      C.byref(loud)), (frames, chans, rates, bounds, ib.ptrs, ib.counts, records), build, PcmError, errors, "pcm",
+                              stats)
+            give_split_index(split_index, ib if split is not None else None, res)
+        finally:
+            ib.free()
+        give_trim_index(trim_index, bounds[:n] if trim is not None else None, res)
+        give_loudness(loudness, records, res)
+        return res
+    give_loudness(loudness, None, [None] * n)
     if split is not None:
         ib = _corpus.IntervalBuffers(lib, n)
         try:

@@ -182,7 +182,7 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                        normalize=None, std_floor=1e-5, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048,
                        trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None,
                        pcen=False, pcen_gain=0.98, pcen_bias=2.0, pcen_power=0.5, pcen_time_constant=0.4, pcen_eps=1e-6, pcen_b=None,
-                       pcen_scale=1.0):
+                       pcen_scale=1.0, loudness_normalize=None, loudness=None):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels for the other mel kinds. The linear kinds have no filterbank: "lin_power" is |X|^power and "lin_db" its dB image
     (amin, top_db as for "mel_db"; librosa.amplitude_to_db(|X|, amin=a) is power=2, amin=a*a), both (frames, n_fft / 2 + 1);
@@ -209,9 +209,13 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     time_constant=pcen_time_constant, eps=pcen_eps, b=pcen_b, max_size=1).T on the device, in front of delta / normalize; sr is
     the rate the rows are computed at, so with sr=None the derived coefficient differs between files of different rates.
     librosa's documentation uses pcen_scale=2**31 for float PCM. With pcen=False the pcen_* arguments are still checked, nothing is
-    launched and the call takes the entry points it took without them."""
+    launched and the call takes the entry points it took without them.
+    loudness_normalize=L (LUFS in [-70, 0]; excludes peak_normalize) scales the mono signal to the integrated loudness L behind
+    trim_db / split_db and in front of the pre-emphasis, as get_pcm_batch(mono=True, loudness_normalize=L, ...) does, and the rows are
+    those of that signal; loudness (optional list) receives the measured LUFS per file. A file the measurement refuses (shorter than
+    400 ms, silent, not finite, below 4000 Hz) fails alone. With loudness_normalize=None nothing is launched."""
     _corpus.check_errors(errors)
-    from .pcm import check_sr, cond_spec, give_split_index, give_trim_index, split_spec, trim_spec
+    from .pcm import check_sr, cond_spec, give_loudness, give_split_index, give_trim_index, loudness_args, split_spec, trim_spec
     target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
@@ -227,8 +231,31 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     cond = cond_spec(peak_normalize, preemphasis, SpectralError)
     trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index, SpectralError)
     split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
+    loud = loudness_args(loudness_normalize, loudness, cond, SpectralError)
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
+    if loud is not None:  # the one entry with every stage's spec, the normaliser's among them (NULL: off)
+        from .binding import LOUDNESS_RECORD_DTYPE
+        n = len(list_of_bytes)
+        ib = _corpus.IntervalBuffers(lib, n)
+        joined, bounds = np.zeros(max(n, 1), np.uint64), np.zeros((max(n, 1), 2), np.uint64)
+        records = np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
+        gate = split if split is not None else trim
+        try:
+            res = _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_loud, list_of_bytes,
+                              (threads, feeders, files_per_submit, device, C.byref(spec), target, C.byref(pc) if pcen else None,
+                               None if post is None else C.byref(post), C.byref(cond) if cond.options else None,
+                               None if gate is None else C.byref(gate), int(split is not None), C.byref(loud)),
+                              (counts, bounds, joined, ib.ptrs, ib.counts, records),
+                              lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors,
+                              "spectral", stats)
+            give_split_index(split_index, ib if split is not None else None, res)
+        finally:
+            ib.free()
+        give_trim_index(trim_index, bounds[:n] if trim is not None else None, res)
+        give_loudness(loudness, records, res)
+        return _finish(spec, res)
+    give_loudness(loudness, None, [None] * len(list_of_bytes))
     if pcen:  # the one entry with every stage's spec (NULL: off)
         n = len(list_of_bytes)
         ib = _corpus.IntervalBuffers(lib, n)
