@@ -530,11 +530,95 @@ enum {
   VSYN_SPEC_STFT = 7        /* "stft" */
 };
 
-/* Columns of a row under spec (n_mels; n_mfcc for MFCC; NB for LIN_POWER and LIN_DB; 2 NB for STFT), 0 for an invalid spec. */
+/* Columns of a row under spec (n_mels; n_mfcc for MFCC; NB for LIN_POWER and LIN_DB; 2 NB for STFT), 0 for an invalid spec and for
+ * the kinds of "chroma" below (vsyn_spectral_chroma_dim answers for those). */
 uint32_t vsyn_spectral_dim(const vsyn_spectral_spec* spec);
 /* Frames that one workgroup of the linear kinds' kernel computes under spec (a tuning fact, exposed for tests that place frame
  * counts around it); 0 for an invalid spec or a mel kind. */
 uint32_t vsyn_spectral_lin_tile(const vsyn_spectral_spec* spec);
+
+/* ---- chroma: pitch-class rows (librosa.feature.chroma_stft) and the tonnetz rows computed from them, where the PCM is ----
+ *
+ * Two more kinds of vsyn_spectral_spec, served by every spectral entry point above and below with the default chroma parameters,
+ * and by the entry points of this section with a vsyn_spectral_chroma of the caller's (vsyn_spectral_dim alone still answers 0 for
+ * them: vsyn_spectral_chroma_dim sizes their rows). librosa is not among the test dependencies
+ * and parity with it is not claimed: the contract is the exact arithmetic below, and the device is compared against a float64
+ * model of it (tests/chroma_model.py) under a per-frame error bound.
+ *
+ *  1. Mono, framing, window and X[k]: steps 1 - 3 of "spectral features" and step 2 of "linear spectra", unchanged.
+ *     S[k] = |X[k]|^power, power 1 or 2 (chroma_stft's is 2), k < NB = n_fft / 2 + 1. Row f lines up with row f of every other kind
+ *     at the same n_fft, hop and centring.
+ *  2. Filterbank (librosa.filters.chroma with its inner norm = 2), built in double on the host, once per distinct sample rate sr:
+ *       fr[j] = j sr / n_fft, j = 1 .. n_fft - 1;  A = 440 * 2^(tuning / n_chroma);  q[j] = n_chroma log2(fr[j] / (A / 16));
+ *       q[0] = q[1] - 1.5 n_chroma;  bw[j] = max(q[j+1] - q[j], 1) for j < n_fft - 1, bw[n_fft-1] = 1;
+ *       h = rint(n_chroma / 2) with ties to even (numpy.round);  D[c][j] = mod(q[j] - c + h + 10 n_chroma, n_chroma) - h with a
+ *       non-negative mod;  W[c][j] = exp(-0.5 (2 D[c][j] / bw[j])^2).
+ *     Every column j is divided by its L2 norm over c (a norm below DBL_MIN counts as 1); unless VSYN_CHROMA_NO_OCT it is then
+ *     multiplied by exp(-0.5 ((q[j] / n_chroma - ctroct) / octwidth)^2); with VSYN_CHROMA_BASE_C the rows are rotated so that new
+ *     row c is old row (c + 3 (n_chroma / 12)) mod n_chroma (integer division): row 0 is C instead of A. Columns 0 .. NB - 1 are
+ *     kept and cast to float32; a value whose magnitude is below FLT_MIN is stored as 0, so no weight is denormal.
+ *     vsyn_chroma_filterbank returns this table.
+ *  3. VSYN_SPEC_CHROMA: R[c] = sum_k W[c][k] S[k]; N = the norm of R over c chosen by vsyn_spectral_chroma.norm (L1: sum |R|, L2:
+ *     sqrt(sum R^2), max: max |R|). The row is R[c] / N, or R itself when N < FLT_MIN (librosa.util.normalize's fill = None) and
+ *     with norm none. dim = n_chroma.
+ *  4. VSYN_SPEC_TONNETZ (librosa.feature.tonnetz(chroma = the rows of step 3)): u = the chroma row after its own norm, L1-normalised
+ *     again with the same FLT_MIN rule; out[i] = sum_c phi[i][c] u[c], i < 6, phi[i][c] = r_i cos(pi (s_i 12 c / n_chroma - o_i)),
+ *     s = (7/6, 7/6, 3/2, 3/2, 2/3, 2/3), o = (1/2, 0, 1/2, 0, 1/2, 0), r = (1, 1, 1, 1, 1/2, 1/2); phi is built in double on the
+ *     host and rounded to float32. dim = 6.
+ *  5. If any R[c] of a frame is not finite (an Inf or NaN sample inside the frame, or an overflow), every value of that frame's
+ *     row is NaN, for both kinds and every norm; other frames are not touched.
+ *  6. Checked (VSYN_ERR_INVALID before anything runs): the option bits, n_fft, hop_length, win_length and power as for "linear
+ *     spectra"; 1 <= n_chroma <= 256; norm in 0 .. 3; no unknown chroma option bits; tuning and ctroct finite; octwidth finite and
+ *     > 0 unless VSYN_CHROMA_NO_OCT. Not read and not checked: the mel fields, amin, top_db, log_floor. A rate of 0 skips its
+ *     segment. tuning is always a number: librosa's tuning = None (estimate_tuning) is not built.
+ *  7. PCEN is refused for both kinds. The post stage ("spectral post-processing") is accepted for both: their rows are at most 256
+ *     columns wide.
+ *
+ * Arithmetic: float32 in a fixed order, so that the same PCM gives the same bits alone, in any slot of a batch, at any alignment of
+ * the plane and wherever the frame falls in its workgroup's tile. n_fft a power of two: the FFT of "linear spectra", S[k] kept in
+ * LDS; R[c] by one wave per (frame, c): lane l runs one fma chain over k = l, l + 64, ... ascending, then the 64 partial sums are
+ * added in an xor-shuffle tree (lane distance 32, 16, 8, 4, 2, 1). Any other n_fft: the direct sum of "spectral features" in chunks
+ * of 256 bins; per chunk the same chain and tree over the chunk's bins, the chunks' sums added to R[c] in ascending order. The norm's
+ * sum (L1: |R|, L2: (R / m)^2, max) runs per frame in one wave: lane l over c = l, l + 64, ... ascending, then the same tree; L2 is
+ * m sqrtf(sum (R / m)^2) with m = max |R| (and N = m when m < FLT_MIN), so that the squares neither overflow nor vanish. Tonnetz: the second L1 sum likewise, then one fma chain per i over c ascending. The linear rows never
+ * leave the workgroup. */
+enum {
+  VSYN_SPEC_CHROMA = 8,  /* "chroma" */
+  VSYN_SPEC_TONNETZ = 9  /* "tonnetz" */
+};
+/* vsyn_spectral_chroma.norm */
+enum { VSYN_CHROMA_NORM_NONE = 0, VSYN_CHROMA_NORM_L1 = 1, VSYN_CHROMA_NORM_L2 = 2, VSYN_CHROMA_NORM_MAX = 3 };
+/* vsyn_spectral_chroma.options */
+#define VSYN_CHROMA_BASE_C 1u  /* row 0 is pitch class C (librosa's base_c=True); without it, A */
+#define VSYN_CHROMA_NO_OCT 2u  /* no Gaussian octave weighting (librosa's octwidth=None); ctroct and octwidth are not read */
+
+typedef struct vsyn_spectral_chroma {
+  uint32_t n_chroma;  /* 1 .. 256 */
+  uint32_t norm;      /* VSYN_CHROMA_NORM_* */
+  uint32_t options;   /* VSYN_CHROMA_* option bits */
+  uint32_t reserved;  /* 0 */
+  double tuning;      /* deviation from A440 in fractions of a chroma bin */
+  double ctroct, octwidth;  /* centre and width of the octave weighting, in octaves (units of q / n_chroma) */
+} vsyn_spectral_chroma;
+/* The defaults, which a NULL vsyn_spectral_chroma means everywhere: {12, VSYN_CHROMA_NORM_MAX, VSYN_CHROMA_BASE_C, 0, 0.0, 5.0, 2.0}. */
+
+/* The columns of a row of every kind. vsyn_spectral_dim predates the chroma kinds and keeps answering 0 for kinds 8 and 9, as it did
+ * when they were unknown: a row's width is a chroma parameter, which it does not take. Size rows buffers of these kinds with this
+ * function. With the chroma parameters (NULL: the defaults): n_chroma for CHROMA, 6 for TONNETZ, vsyn_spectral_dim(spec) for
+ * every other kind (chroma is then neither read nor checked); 0 for an invalid spec or chroma. */
+uint32_t vsyn_spectral_chroma_dim(const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma);
+/* The float32 filterbank of step 2 at sample_rate, as the device gets it: out[c * NB + k], n_chroma rows of NB = n_fft / 2 + 1. Host
+ * only: no device is needed. VSYN_ERR_INVALID for a NULL out, sample_rate 0, or a spec / chroma that step 6 refuses (spec->kind must
+ * be CHROMA or TONNETZ). */
+int vsyn_chroma_filterbank(uint32_t sample_rate, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma, float* out);
+/* Frames that one workgroup of the chroma kernels computes under spec (a tuning fact, exposed for tests that place frame counts
+ * around it); 0 for an invalid spec or another kind. */
+uint32_t vsyn_spectral_chroma_tile(const vsyn_spectral_spec* spec);
+/* vsyn_spectral_device with the chroma parameters (NULL: the defaults; with a kind other than CHROMA and TONNETZ chroma is not read and
+ * the call is vsyn_spectral_device). */
+int vsyn_spectral_chroma_device(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma, uint32_t num_segments,
+                                const uint32_t* sample_rates, const float* d_pcm, uint64_t plane_stride, uint32_t channels,
+                                const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off, void* hip_stream, const char** err);
 
 /* ---- resampling: polyphase resampling of the decoded PCM to a target sample rate, computed where the PCM is ----
  *
@@ -1248,6 +1332,15 @@ int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int 
                                  uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
                                  uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                  vsyn_loudness_record* records_out, vsyn_status* status, const char** err);
+
+/* vsyn_pcm_chain_spectral_host with the chroma parameters of "chroma" (NULL: the defaults) between spec and pcen. It runs through the
+ * same chain body; with chroma = NULL and a kind other than CHROMA and TONNETZ it is that entry, bit for bit. */
+int vsyn_pcm_chain_chroma_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                               const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                               const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t num_segments, const uint32_t* in_rates,
+                               uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out,
+                               uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out,
+                               double* refs_out, vsyn_loudness_record* records_out, vsyn_status* status, const char** err);
 
 #ifdef __cplusplus
 }

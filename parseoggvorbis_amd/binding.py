@@ -28,6 +28,9 @@ VSYN_PITCH_CENTER = 1
 VSYN_FDESC_CENTER = 1
 VSYN_SPEC_MEL_POWER, VSYN_SPEC_LOG_MEL, VSYN_SPEC_MEL_DB, VSYN_SPEC_MFCC = 1, 2, 3, 4
 VSYN_SPEC_LIN_POWER, VSYN_SPEC_LIN_DB, VSYN_SPEC_STFT = 5, 6, 7  # include/vorbis_synth_hip.h, "linear spectra"
+VSYN_SPEC_CHROMA, VSYN_SPEC_TONNETZ = 8, 9  # include/vorbis_synth_hip.h, "chroma"
+VSYN_CHROMA_NORM_NONE, VSYN_CHROMA_NORM_L1, VSYN_CHROMA_NORM_L2, VSYN_CHROMA_NORM_MAX = 0, 1, 2, 3
+VSYN_CHROMA_BASE_C, VSYN_CHROMA_NO_OCT = 1, 2
 
 
 class Floor1(C.Structure):
@@ -69,6 +72,11 @@ class SpectralSpec(C.Structure):  # vsyn_spectral_spec
     _fields_ = [("kind", C.c_uint32), ("options", C.c_uint32), ("n_fft", C.c_uint32), ("hop_length", C.c_uint32),
                 ("win_length", C.c_uint32), ("n_mels", C.c_uint32), ("n_mfcc", C.c_uint32), ("power", C.c_uint32),
                 ("fmin", C.c_double), ("fmax", C.c_double), ("log_floor", C.c_double), ("amin", C.c_double), ("top_db", C.c_double)]
+
+
+class SpectralChroma(C.Structure):  # vsyn_spectral_chroma
+    _fields_ = [("n_chroma", C.c_uint32), ("norm", C.c_uint32), ("options", C.c_uint32), ("reserved", C.c_uint32),
+                ("tuning", C.c_double), ("ctroct", C.c_double), ("octwidth", C.c_double)]
 
 
 class SpectralPost(C.Structure):  # vsyn_spectral_post
@@ -247,12 +255,16 @@ _SYMBOLS = [
     "vsyn_fdesc_num_frames", "vsyn_fdesc_device", "vsyn_pcm_fdesc_host",
     "vsyn_loudness_num_blocks", "vsyn_loudness_coefficients", "vsyn_loudness_powers", "vsyn_loudness_device", "vsyn_pcm_loudness_host",
     "vsyn_pcm_chain_host", "vsyn_pcm_chain_spectral_host",
+    "vsyn_spectral_chroma_dim", "vsyn_chroma_filterbank", "vsyn_spectral_chroma_tile", "vsyn_spectral_chroma_device",
+    "vsyn_pcm_chain_chroma_host",
 ]
 
 
-def _spec_dim(spec):
-    from .spectral import spec_dim  # the one formula (spectral imports this module lazily as well)
-    return spec_dim(spec)
+def _spec_dim(spec, chroma=None):
+    from .spectral import CHROMA_KINDS, chroma_spec, spec_dim  # the one formula (spectral imports this module lazily as well)
+    if chroma is None and spec.kind in CHROMA_KINDS.values():
+        chroma = chroma_spec()  # an entry without the chroma argument serves these kinds with the defaults
+    return spec_dim(spec, chroma)
 
 
 def declared_symbols():
@@ -373,6 +385,16 @@ def load():
     lib.vsyn_pcm_chain_spectral_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
                                                  C.POINTER(SpectralSpec), C.POINTER(SpectralPcen), C.POINTER(SpectralPost), u32, vp, u32, vp, u64,
                                                  vp, vp, vp, vp, vp, u64, vp, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_spectral_chroma_dim.argtypes = [C.POINTER(SpectralSpec), C.POINTER(SpectralChroma)]
+    lib.vsyn_spectral_chroma_dim.restype = u32
+    lib.vsyn_chroma_filterbank.argtypes = [u32, C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), vp]
+    lib.vsyn_spectral_chroma_tile.argtypes = [C.POINTER(SpectralSpec)]
+    lib.vsyn_spectral_chroma_tile.restype = u32
+    lib.vsyn_spectral_chroma_device.argtypes = [vp, C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), u32, vp, vp, u64, u32, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_chain_chroma_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
+                                               C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralPcen),
+                                               C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp,
+                                               C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -533,6 +555,13 @@ class Synth:
         err = C.c_char_p()
         _check(self.lib.vsyn_spectral_device(self.h, C.byref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows,
                                              d_seg_row_off, stream, C.byref(err)), err)
+
+    def spectral_chroma_device(self, spec, chroma, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, stream=None):
+        """vsyn_spectral_chroma_device on device pointers (ints); chroma (a SpectralChroma) may be None for the defaults."""
+        rates = _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_spectral_chroma_device(self.h, C.byref(spec), _ref(chroma), len(rates), _ptr(rates), d_pcm, plane_stride, channels,
+                                                    d_frames, d_rows, d_seg_row_off, stream, C.byref(err)), err)
 
     def spectral_post_device(self, post, dim, seg_rows, d_in, d_out, stream=None):
         """vsyn_spectral_post_device on device pointers (ints); seg_rows is a host sequence of each segment's row count."""

@@ -22,6 +22,7 @@
 #include "vsyn_features.h"
 #include "vsyn_spectral.h"
 #include "vsyn_spectral_lin.h"
+#include "vsyn_chroma.h"
 #include "vsyn_spectral_post.h"
 #include "vsyn_pcen.h"
 #include "vsyn_loudness.h"
@@ -1217,7 +1218,8 @@ uint64_t vsyn_spectral_num_frames(const vsyn_spectral_spec* spec, uint64_t frame
 }
 
 uint32_t vsyn_spectral_dim(const vsyn_spectral_spec* spec) {
-  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
+  // (the chroma kinds' width is a chroma parameter, which this function does not take: vsyn_spectral_chroma_dim answers for them)
+  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK || spec_is_chroma(spec)) return 0;
   return spec_dim(spec);
 }
 
@@ -1226,11 +1228,34 @@ uint32_t vsyn_spectral_lin_tile(const vsyn_spectral_spec* spec) {
   return spec_lin_tile(spec);
 }
 
+uint32_t vsyn_spectral_chroma_dim(const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma) {
+  if (spec_check(spec, 0, nullptr, nullptr, chroma) != VSYN_OK) return 0;
+  return spec_dim(spec, chroma);
+}
+
+uint32_t vsyn_spectral_chroma_tile(const vsyn_spectral_spec* spec) {
+  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK || !spec_is_chroma(spec)) return 0;
+  return spec_chroma_tile(spec);
+}
+
+int vsyn_chroma_filterbank(uint32_t sample_rate, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma, float* out) {
+  if (!out || !sample_rate || spec_check(spec, 0, nullptr, nullptr, chroma) != VSYN_OK || !spec_is_chroma(spec)) return VSYN_ERR_INVALID;
+  chroma_filterbank(sample_rate, spec->n_fft, spec_chroma_or_defaults(chroma), out);
+  return VSYN_OK;
+}
+
 int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, const float* d_pcm,
                          uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off,
                          void* hip_stream, const char** err) {
+  return vsyn_spectral_chroma_device(h, spec, nullptr, S, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off, hip_stream,
+                                     err);
+}
+
+int vsyn_spectral_chroma_device(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma, uint32_t S,
+                                const uint32_t* sample_rates, const float* d_pcm, uint64_t plane_stride, uint32_t channels,
+                                const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off, void* hip_stream, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-  int rc = spec_check(spec, S, sample_rates, err);
+  int rc = spec_check(spec, S, sample_rates, err, chroma);
   if (rc) return rc;
   if (S == 0) return VSYN_OK;
   if (!d_pcm || !d_frames || !d_rows || plane_stride == 0 || channels == 0 || channels > 255)
@@ -1238,7 +1263,7 @@ int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_
   const uint64_t f_max = spec_num_frames(spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, plane_stride);
   std::lock_guard<std::mutex> lk(h->mu);
   return spec_launch(h->sp, h->device, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, (uint64_t)S * f_max, d_rows,
-                     d_seg_row_off, (hipStream_t)hip_stream, err);
+                     d_seg_row_off, (hipStream_t)hip_stream, err, chroma);
 }
 
 
@@ -1543,11 +1568,12 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
 static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S,
                              const uint32_t* spec_rates,
                              const PcmView& v, const uint64_t* seg_rows, uint64_t f_max, uint64_t total, float* rows, vsyn_status* status,
-                             const char** err) {
+                             const char** err, const vsyn_spectral_chroma* chroma) {
   hipStream_t hs = h->host_stream;
-  const uint64_t D = spec_dim(spec);
+  const uint64_t D = spec_dim(spec, chroma);
   HIPCHK(h->sp.rows.ensure(total * D + 1));
-  int rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err);
+  int rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err,
+                       chroma);
   if (rc) return rc;
   if (pcen) {
     rc = pcen_launch(h->pc, h->device, pcen, (uint32_t)D, S, seg_rows, spec_rates, spec->hop_length, h->sp.rows.p, h->sp.rows.p, hs, err);
@@ -1573,7 +1599,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
                          const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
                          uint64_t* seg_rows,
                          uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err, const vsyn_loudness_spec* loud = nullptr,
-                         vsyn_loudness_record* records_out = nullptr) {
+                         vsyn_loudness_record* records_out = nullptr, const vsyn_spectral_chroma* chroma = nullptr) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   if (loud)  // (first: a refused loudness spec writes nothing, the status included)
     if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
@@ -1581,7 +1607,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
   if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
   std::vector<uint32_t> sp_rates = stage_rates(S, rates, out_rate);
   // (NULL rates without a gate are spec_check's to refuse; behind a gate they skip every segment)
-  if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err)) return rc;
+  if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err, chroma)) return rc;
   if (pcen) {
     if (int rc = pcen_check(pcen, err)) return rc;
     if (spec->kind != VSYN_SPEC_MEL_POWER && spec->kind != VSYN_SPEC_LIN_POWER)
@@ -1592,7 +1618,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
                     pcen->time_constant, sp_rates[g], spec->hop_length);
   }
   if (post) {
-    if (int rc = spec_post_check(spec, post, err)) return rc;
+    if (int rc = spec_post_check(spec, post, err, chroma)) return rc;
     if (!post_on(post)) post = nullptr;  // off: the rows of the spectral pass, bit for bit
   }
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
@@ -1650,7 +1676,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
     if (int rc = step_loudness(h, S, loud, sp_rates.data(), T.data(), t_max, false, records_out, &v, err)) return rc;
   if (cond)
     if (int rc = step_condition(h, S, cond, t_max, t_max, false, peaks_out, &v, err)) return rc;
-  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err);
+  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err, chroma);
 }
 
 // vsyn_pcm_split_intervals_host: the chain up to the split stage's marks; nothing but the frames in front of the stage, the
@@ -1941,6 +1967,25 @@ int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int 
                                : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
   return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
                        gate ? frames_out : nullptr, peaks_out, status, err, loud, records_out);
+}
+
+// vsyn_pcm_chain_spectral_host with the chroma parameters: the same chain body. Without a loudness spec the gate decides, as there, which
+// of frames_out and the outputs of the other gate the body is given.
+int vsyn_pcm_chain_chroma_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                               const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                               const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates,
+                               uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out,
+                               uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out,
+                               double* refs_out, vsyn_loudness_record* records_out, vsyn_status* status, const char** err) {
+  if (!spec || !spec_is_chroma(spec) || !h)  // chroma is not read: the entry without it (which also words the refusal of a NULL handle)
+    return vsyn_pcm_chain_spectral_host(h, gate, gate_is_split, loud, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
+                                        frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, status,
+                                        err);
+  const bool split = gate && gate_is_split;
+  const Gate g = split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                       : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
+                       gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma);
 }
 
 // ---- pitch (vsyn_pitch.h) ----

@@ -1,0 +1,387 @@
+// vsyn_chroma.h — chroma rows (librosa.feature.chroma_stft's arithmetic) and the tonnetz rows computed from them, from planar float32
+// PCM already on the device. Semantics: include/vorbis_synth_hip.h, "chroma". Design, bound and measurements: DESIGN.md 6n.
+//
+// The offsets kernel, the table of the linear kinds (header, twiddles, window, per-segment rate index) and the workspace are those of
+// vsyn_spectral.h; behind the rate index the table carries a ChromaHeader, the dense float32 filterbank [rate][n_chroma][NB] and
+// phi [6][n_chroma] (SpecHeader.pad holds the ChromaHeader's offset; it is 0 in every other kind's table). Behind the offsets kernel,
+// one workgroup of 256 threads (4 waves) per (segment, tile of frames), by n_fft alone:
+//   vsyn_chroma_fft_kernel         n_fft a power of two: spec_lin_fft_tile_run (vsyn_spectral_lin.h), then S[f][k] = |X[k]|^power into
+//                                  the spare ping-pong buffer instead of a store of the bins.
+//   vsyn_chroma_direct_kernel<FT>  any other n_fft: the loop of vsyn_spec_stft_kernel in chunks of 256 bins, S of a chunk in LDS.
+// Both project with chroma_dot, one wave per (frame, c): lane l runs one fma chain over the bins l, l + 64, ... (ascending) of the
+// whole row (FFT kernel) or of the chunk (direct kernel, the chunks' sums added to R[f][c] in ascending order), W read from global
+// memory along k, S from LDS, then an xor-shuffle tree over lane distances 32 ... 1. chroma_finish then takes each frame's norm, the
+// non-finite rule and, for tonnetz, the 6 x n_chroma product, one wave per frame. No atomics; S and R never leave the workgroup.
+// Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
+#pragma once
+#include <cfloat>
+
+#include "vsyn_spectral_lin.h"
+
+#define CHROMA_DIRECT_FT 8
+#define CHROMA_MAX 256  // n_chroma's limit; the LDS images reserve a row of it per frame, so that the tile depends on the spec alone
+
+struct ChromaHeader {
+  uint32_t n_chroma, norm, off_w, off_phi;  // byte offsets into the table
+};
+
+__device__ __forceinline__ const ChromaHeader* chroma_hdr(const uint8_t* t) { return (const ChromaHeader*)(t + spec_hdr(t)->pad); }
+
+// LDS images in floats: the FFT kernel's of vsyn_spectral_lin.h | R [ft][CHROMA_MAX]; the direct kernel's twiddles [2n] | window [n] |
+// span [(ft-1) hop + n] | S [ft][256] | R [ft][CHROMA_MAX]
+__host__ __device__ __forceinline__ uint64_t chroma_fft_lds_floats(uint32_t ft, uint32_t n) { return spec_lin_fft_lds_floats(ft, n) + (uint64_t)ft * CHROMA_MAX; }
+__host__ __device__ __forceinline__ uint64_t chroma_direct_lds_floats(uint32_t ft, uint32_t n, uint32_t hop) {
+  return 3ull * n + spec_span_len(ft, n, hop) + (uint64_t)ft * SPEC_THREADS + (uint64_t)ft * CHROMA_MAX;
+}
+
+// sum_k w[k] s[k] over k < cnt by one wave: lane l's fma chain over k = l, l + 64, ... ascending, then the tree; every lane returns the sum.
+__device__ __forceinline__ float chroma_dot(const float* __restrict__ w, const float* s, uint32_t cnt, uint32_t lane) {
+  float acc = 0.f;
+  for (uint32_t k0 = lane; k0 < cnt; k0 += 64u * 6u) {  // six loads of each operand in flight, then their fmas in the chain's order
+    float wv[6], sv[6];
+#pragma unroll
+    for (uint32_t u = 0; u < 6u; ++u) {
+      const uint32_t k = k0 + 64u * u;
+      wv[u] = k < cnt ? w[k] : 0.f;
+      sv[u] = k < cnt ? s[k] : 0.f;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < 6u; ++u)
+      if (k0 + 64u * u < cnt) acc = fmaf(wv[u], sv[u], acc);
+  }
+  for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
+  return acc;
+}
+
+__device__ __forceinline__ float chroma_tree_sum(float v) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// Rows f0 .. f0 + nf - 1 from R [nf][NC] in LDS, one wave per frame: the norm, the division, the non-finite rule, and for tonnetz the
+// second L1 norm and the product with phi (u goes back to the frame's row of s_R). Called by the whole workgroup behind a barrier.
+__device__ __forceinline__ void chroma_finish(const SpecHeader* H, const ChromaHeader* CH, const uint8_t* tab, float* s_R, uint32_t nf, uint64_t r0,
+                                              float* rows) {
+  const uint32_t NC = CH->n_chroma, norm = CH->norm, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const bool tonnetz = H->kind == VSYN_SPEC_TONNETZ;
+  const float* phi = (const float*)(tab + CH->off_phi);
+  const float qnan = __uint_as_float(0x7FC00000u);
+  for (uint32_t fb = 0; fb < nf; fb += SPEC_THREADS / 64u) {
+    const uint32_t f = fb + wave;
+    const bool act = f < nf;  // wave-uniform
+    float* R = s_R + (size_t)f * NC;
+    bool bad = false;
+    if (act) {
+      float v[CHROMA_MAX / 64];
+      float s = 0.f, mx = 0.f;
+#pragma unroll
+      for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) {
+        const uint32_t c = lane + 64u * j;
+        v[j] = c < NC ? R[c] : 0.f;
+        const float a = fabsf(v[j]);
+        bad |= !(a <= FLT_MAX);  // Inf or NaN (fmaxf would drop a NaN)
+        mx = fmaxf(mx, a);
+        s = s + a;
+      }
+      bad = __any(bad) != 0;
+      for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+      float N = mx;
+      if (norm == VSYN_CHROMA_NORM_L1) {
+        N = chroma_tree_sum(s);
+      } else if (norm == VSYN_CHROMA_NORM_L2 && !(mx < FLT_MIN)) {  // mx sqrt(sum (R / mx)^2): the squares neither overflow nor vanish
+        s = 0.f;
+#pragma unroll
+        for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) {
+          const float t = v[j] / mx;
+          s = fmaf(t, t, s);
+        }
+        N = mx * sqrtf(chroma_tree_sum(s));
+      }
+      if (norm != VSYN_CHROMA_NORM_NONE && !bad && !(N < FLT_MIN)) {
+#pragma unroll
+        for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) v[j] = v[j] / N;
+      }
+      if (tonnetz && !bad) {
+        float s1 = 0.f;
+#pragma unroll
+        for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) s1 = s1 + fabsf(v[j]);
+        s1 = chroma_tree_sum(s1);
+        if (!(s1 < FLT_MIN)) {
+#pragma unroll
+          for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) v[j] = v[j] / s1;
+        }
+      }
+#pragma unroll
+      for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) {
+        const uint32_t c = lane + 64u * j;
+        if (c < NC) {
+          if (tonnetz) R[c] = v[j];
+          else rows[(r0 + f) * NC + c] = bad ? qnan : v[j];
+        }
+      }
+    }
+    if (tonnetz) {  // (uniform over the workgroup)
+      __syncthreads();
+      if (act && lane < 6u) {
+        const float* ph = phi + (size_t)lane * NC;
+        float acc = 0.f;
+        for (uint32_t c = 0; c < NC; ++c) acc = fmaf(ph[c], R[c], acc);
+        rows[(r0 + f) * 6u + lane] = bad ? qnan : acc;
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(SPEC_THREADS) vsyn_chroma_fft_kernel(const SpecCtx A, const uint32_t ft, const uint32_t lgM) {
+  extern __shared__ float lds[];
+  const SpecHeader* H = spec_hdr(A.tab);
+  const ChromaHeader* CH = chroma_hdr(A.tab);
+  const uint32_t g = blockIdx.y, tid = threadIdx.x;
+  const uint32_t F = A.segF[g];
+  const uint32_t f0 = blockIdx.x * ft;
+  if (f0 >= F) return;
+  const uint32_t n = H->n, nb = H->nbins, M = n >> 1, NC = CH->n_chroma;
+  const uint32_t nf = min(ft, F - f0);
+  const SpecLinFft T = spec_lin_fft_tile_run(A, H, lds, ft, lgM, g, f0, nf);
+  float* s_S = (float*)T.spare;                       // [nf][nb]: nf nb <= ft n floats, the buffer's size
+  float* s_R = lds + spec_lin_fft_lds_floats(ft, n);  // [nf][NC]
+  for (uint32_t q = tid; q < nf * nb; q += SPEC_THREADS) {
+    const uint32_t f = q / nb, k = q - f * nb;
+    float re, im;
+    spec_lin_untangle(T.Z + (size_t)f * M, T.un, M, k, re, im);
+    const float p = fmaf(re, re, im * im);
+    s_S[q] = H->power == 1 ? sqrtf(p) : p;
+  }
+  __syncthreads();
+  const uint32_t ri = ((const uint32_t*)(A.tab + H->off_rate))[g];
+  const float* W = (const float*)(A.tab + CH->off_w) + (size_t)ri * NC * nb;
+  const uint32_t wave = tid >> 6, lane = tid & 63u;
+  for (uint32_t p = wave; p < nf * NC; p += SPEC_THREADS / 64u) {
+    const uint32_t f = p / NC, c = p - f * NC;
+    const float r = chroma_dot(W + (size_t)c * nb, s_S + (size_t)f * nb, nb, lane);
+    if (lane == 0) s_R[p] = r;
+  }
+  __syncthreads();
+  chroma_finish(H, CH, A.tab, s_R, nf, A.segoff[g] + f0, A.rows);
+}
+
+template <int FT>
+__global__ void __launch_bounds__(SPEC_THREADS) vsyn_chroma_direct_kernel(const SpecCtx A) {
+  extern __shared__ float lds[];
+  const SpecHeader* H = spec_hdr(A.tab);
+  const ChromaHeader* CH = chroma_hdr(A.tab);
+  const uint32_t g = blockIdx.y, tid = threadIdx.x;
+  const uint32_t F = A.segF[g];
+  const uint32_t f0 = blockIdx.x * FT;
+  if (f0 >= F) return;
+  const uint32_t n = H->n, hop = H->hop, nb = H->nbins, win = H->win, woff = H->woff, NC = CH->n_chroma;
+  const uint32_t nf = min((uint32_t)FT, F - f0);
+  float2* s_tw = (float2*)lds;
+  float* s_win = lds + 2u * n;
+  float* s_span = s_win + n;
+  const uint32_t span = (uint32_t)spec_span_len(FT, n, hop);
+  float* s_S = s_span + span;             // [FT][256]
+  float* s_R = s_S + FT * SPEC_THREADS;  // [nf][NC]
+  const float2* g_tw = (const float2*)(A.tab + H->off_tw);
+  const float* g_win = (const float*)(A.tab + H->off_win);
+  for (uint32_t i = tid; i < n; i += SPEC_THREADS) {
+    s_tw[i] = g_tw[i];
+    s_win[i] = g_win[i];
+  }
+  // the tile's span of the padded mono signal, as in vsyn_spec_stft_kernel
+  const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
+  const int64_t pad = (H->opts & VSYN_SPEC_CENTER) ? (int64_t)(n / 2u) : 0;
+  const int64_t p0 = (int64_t)f0 * hop - pad;
+  const uint32_t C = A.C;
+  const float invC = 1.0f / (float)C;
+  const float* x = A.pcm + (size_t)g * C * A.plane;
+  for (uint32_t i = tid; i < span; i += SPEC_THREADS) {
+    const int64_t t = p0 + (int64_t)i;
+    s_span[i] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, invC, (uint64_t)t) : 0.f;
+  }
+  for (uint32_t i = tid; i < nf * NC; i += SPEC_THREADS) s_R[i] = 0.f;
+  __syncthreads();
+  const uint32_t ri = ((const uint32_t*)(A.tab + H->off_rate))[g];
+  const float* W = (const float*)(A.tab + CH->off_w) + (size_t)ri * NC * nb;
+  const uint32_t wave = tid >> 6, lane = tid & 63u;
+  for (uint32_t k0 = 0; k0 < nb; k0 += SPEC_THREADS) {
+    const uint32_t k = k0 + tid;
+    float re[FT], im[FT];
+#pragma unroll
+    for (int f = 0; f < FT; ++f) re[f] = im[f] = 0.f;
+    if (k < nb) {
+      uint32_t idx = (uint32_t)(((uint64_t)woff * k) % n);
+      for (uint32_t j = woff; j < woff + win; ++j) {
+        const float2 tw = s_tw[idx];
+        const float w = s_win[j];
+        const float a = w * tw.x, b = w * tw.y;
+        const float* sp = s_span + j;
+#pragma unroll
+        for (int f = 0; f < FT; ++f) {
+          const float v = sp[f * hop];
+          re[f] = fmaf(v, a, re[f]);
+          im[f] = fmaf(v, b, im[f]);
+        }
+        idx += k;
+        if (idx >= n) idx -= n;
+      }
+    }
+#pragma unroll
+    for (int f = 0; f < FT; ++f) {
+      const float p = fmaf(re[f], re[f], im[f] * im[f]);
+      s_S[f * SPEC_THREADS + tid] = H->power == 1 ? sqrtf(p) : p;
+    }
+    __syncthreads();
+    const uint32_t cnt = min((uint32_t)SPEC_THREADS, nb - k0);
+    for (uint32_t p = wave; p < nf * NC; p += SPEC_THREADS / 64u) {  // (pair p stays with its wave over the chunks)
+      const uint32_t f = p / NC, c = p - f * NC;
+      const float r = chroma_dot(W + (size_t)c * nb + k0, s_S + f * SPEC_THREADS, cnt, lane);
+      if (lane == 0) s_R[p] = s_R[p] + r;
+    }
+    __syncthreads();
+  }
+  chroma_finish(H, CH, A.tab, s_R, nf, A.segoff[g] + f0, A.rows);
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+
+// The filterbank of "chroma" step 2 at rate sr: out[c * NB + k] float32, n_chroma rows of NB = n_fft / 2 + 1. ch is checked.
+static inline void chroma_filterbank(uint32_t sr, uint32_t n, const vsyn_spectral_chroma* ch, float* out) {
+  const uint32_t NC = ch->n_chroma, nb = n / 2u + 1u;
+  const double nc = (double)NC;
+  std::vector<double> q(n), bw(n), col(NC);
+  const double a16 = 440.0 * exp2(ch->tuning / nc) / 16.0;
+  for (uint32_t j = 1; j < n; ++j) q[j] = nc * log2(((double)j * (double)sr / (double)n) / a16);
+  q[0] = q[1] - 1.5 * nc;
+  for (uint32_t j = 0; j + 1u < n; ++j) bw[j] = std::max(q[j + 1] - q[j], 1.0);
+  bw[n - 1u] = 1.0;
+  const double h = nearbyint(nc / 2.0);  // ties to even, as numpy.round
+  const uint32_t rot = (ch->options & VSYN_CHROMA_BASE_C) ? 3u * (NC / 12u) : 0u;
+  for (uint32_t j = 0; j < nb; ++j) {
+    double ss = 0.0;
+    for (uint32_t c = 0; c < NC; ++c) {
+      double d = fmod((q[j] - (double)c) + h + 10.0 * nc, nc);
+      if (d < 0.0) d += nc;
+      d -= h;
+      const double t = 2.0 * d / bw[j];
+      col[c] = exp(-0.5 * (t * t));
+      ss += col[c] * col[c];
+    }
+    double nrm = sqrt(ss);
+    if (nrm < DBL_MIN) nrm = 1.0;
+    double oct = 1.0;
+    if (!(ch->options & VSYN_CHROMA_NO_OCT)) {
+      const double t = (q[j] / nc - ch->ctroct) / ch->octwidth;
+      oct = exp(-0.5 * (t * t));
+    }
+    for (uint32_t c = 0; c < NC; ++c) {
+      const float v = (float)(col[(c + rot) % NC] / nrm * oct);
+      out[(size_t)c * nb + j] = fabsf(v) < FLT_MIN ? 0.f : v;
+    }
+  }
+}
+
+// phi of "chroma" step 4: out[i * n_chroma + c] float32
+static inline void chroma_phi(uint32_t NC, float* out) {
+  static const double sc[6] = {7.0 / 6.0, 7.0 / 6.0, 3.0 / 2.0, 3.0 / 2.0, 2.0 / 3.0, 2.0 / 3.0};
+  static const double of[6] = {0.5, 0.0, 0.5, 0.0, 0.5, 0.0};
+  static const double rd[6] = {1.0, 1.0, 1.0, 1.0, 0.5, 0.5};
+  for (uint32_t i = 0; i < 6u; ++i)
+    for (uint32_t c = 0; c < NC; ++c) out[(size_t)i * NC + c] = (float)(rd[i] * cos(M_PI * (sc[i] * (12.0 * (double)c / (double)NC) - of[i])));
+}
+
+// Frames per workgroup under sp (a chroma kind, checked): the FFT kernel's for a power-of-two n_fft, else the most of the direct
+// kernel's that fit the LDS; 0 when nothing fits.
+static inline uint32_t spec_chroma_tile(const vsyn_spectral_spec* sp) {
+  if (spec_lin_pow2(sp->n_fft)) {
+    const uint32_t ft = spec_lin_fft_tile(sp->n_fft);
+    return chroma_fft_lds_floats(ft, sp->n_fft) * 4u <= SPEC_LDS_BUDGET ? ft : 0u;
+  }
+  for (uint32_t ft : {(uint32_t)CHROMA_DIRECT_FT, 1u})
+    if (chroma_direct_lds_floats(ft, sp->n_fft, sp->hop_length) * 4u <= SPEC_LDS_BUDGET) return ft;
+  return 0;
+}
+
+// spec_launch for the chroma kinds (it dispatches here): the linear kinds' table with the chroma block behind it, offsets, and the
+// FFT or direct kernel.
+static inline int spec_chroma_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, const vsyn_spectral_chroma* ch, uint32_t S,
+                                     const uint32_t* rates, const float* d_pcm, uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si,
+                                     uint64_t f_max, float* d_rows, uint64_t* d_segoff, hipStream_t s, const char** err) {
+  ch = spec_chroma_or_defaults(ch);
+  const uint32_t ft = spec_chroma_tile(sp), n = sp->n_fft, nb = n / 2u + 1u, NC = ch->n_chroma;
+  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", n, sp->hop_length);
+  std::vector<uint8_t> tab;
+  spec_build_table(sp, S, rates, tab);
+  {  // the chroma block: one filterbank per distinct rate, in the order of the table's rate indices (first appearance)
+    SpecHeader T;
+    memcpy(&T, tab.data(), sizeof(T));
+    std::vector<uint32_t> distinct;
+    for (uint32_t g = 0; g < S; ++g)
+      if (rates[g] && std::find(distinct.begin(), distinct.end(), rates[g]) == distinct.end()) distinct.push_back(rates[g]);
+    const size_t off_ch = (tab.size() + 15) & ~(size_t)15;
+    const size_t off_w = off_ch + sizeof(ChromaHeader);
+    const size_t off_phi = off_w + 4ull * distinct.size() * NC * nb;
+    const size_t total = off_phi + 4ull * 6u * NC + 16;
+    if (total > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too many distinct sample rates (%zu) for one chroma table", distinct.size());
+    tab.resize(total, 0);
+    T.pad = (uint32_t)off_ch;
+    T.dim = spec_dim(sp, ch);
+    memcpy(tab.data(), &T, sizeof(T));
+    const ChromaHeader CH = {NC, ch->norm, (uint32_t)off_w, (uint32_t)off_phi};
+    memcpy(tab.data() + off_ch, &CH, sizeof(CH));
+    // the filterbanks of the last call are kept: a corpus run asks for the same ones submit after submit
+    std::vector<double> key = {(double)n, (double)NC, (double)ch->options, ch->tuning, ch->ctroct, ch->octwidth};
+    for (uint32_t r : distinct) key.push_back((double)r);
+    if (key != ws.chroma_key) {
+      ws.chroma_key.clear();  // (a throw below leaves no stale bank behind a matching key)
+      ws.chroma_bank.resize(distinct.size() * NC * nb);
+      for (size_t r = 0; r < distinct.size(); ++r) chroma_filterbank(distinct[r], n, ch, ws.chroma_bank.data() + r * NC * nb);
+      ws.chroma_key = key;
+    }
+    if (!ws.chroma_bank.empty()) memcpy(tab.data() + off_w, ws.chroma_bank.data(), 4 * ws.chroma_bank.size());
+    chroma_phi(NC, (float*)(tab.data() + off_phi));
+  }
+  HIPCHK(hipSetDevice(device));
+  if (!ws.chroma_lds_set) {
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_chroma_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute((const void*)vsyn_chroma_direct_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+    ws.chroma_lds_set = true;
+  }
+  HIPCHK(ws.segF.ensure(S));
+  HIPCHK(ws.segmax.ensure(S));
+  HIPCHK(ws.segoff.ensure((size_t)S + 1));
+  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+  SpecCtx A;
+  A.tab = ws.tab.dev.p;
+  A.pcm = d_pcm;
+  A.plane = plane;
+  A.C = C;
+  A.S = S;
+  A.frames = d_frames;
+  A.si = si;
+  A.segF = ws.segF.p;
+  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
+  A.segmax = ws.segmax.p;
+  A.rows = d_rows;
+  A.db = nullptr;
+  hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
+  HIPCHK(hipGetLastError());
+  if (f_max == 0 || S == 0) return VSYN_OK;
+  const uint64_t gx = (f_max + ft - 1) / ft;
+  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+  const dim3 grid((uint32_t)gx, S);
+  if (spec_lin_pow2(n)) {
+    uint32_t lgM = 0;
+    while ((2u << lgM) < n) ++lgM;
+    hipLaunchKernelGGL(vsyn_chroma_fft_kernel, grid, dim3(SPEC_THREADS), chroma_fft_lds_floats(ft, n) * 4u, s, A, ft, lgM);
+  } else {
+    const size_t lds = chroma_direct_lds_floats(ft, n, sp->hop_length) * 4u;
+    if (ft == CHROMA_DIRECT_FT) hipLaunchKernelGGL(vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
+    else hipLaunchKernelGGL(vsyn_chroma_direct_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
+  }
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}

@@ -223,6 +223,9 @@ struct SpectralWs {  // the stage's buffers: its own; the PCM is only read
   TableUpload tab;
   bool lds_set = false;                // the STFT kernels' dynamic-LDS limit is raised on this handle's device
   bool lin_lds_set = false;            // and that of the linear kinds' kernels (vsyn_spectral_lin.h)
+  bool chroma_lds_set = false;         // and that of the chroma kernels (vsyn_chroma.h)
+  std::vector<double> chroma_key;      // what the kept chroma filterbanks were built from (n_fft, the chroma parameters, the distinct rates)
+  std::vector<float> chroma_bank;      // [rate][n_chroma][NB]
   DevBuf<uint32_t> segF, segmax;
   DevBuf<uint64_t> segoff;
   DevBuf<float> db, rows;
@@ -242,9 +245,17 @@ static inline double spec_mel_to_hz(double m, bool htk) {
 // The linear kinds (include/vorbis_synth_hip.h, "linear spectra") read no mel field of the spec.
 static inline bool spec_is_lin(const vsyn_spectral_spec* sp) { return sp->kind >= VSYN_SPEC_LIN_POWER && sp->kind <= VSYN_SPEC_STFT; }
 
-// Columns of a row (vsyn_spectral_dim): the one formula on the C side; 0 for an unknown kind.
-static inline uint32_t spec_dim(const vsyn_spectral_spec* sp) {
+// The chroma kinds (include/vorbis_synth_hip.h, "chroma") read the framing fields and power of the spec and a vsyn_spectral_chroma.
+static inline bool spec_is_chroma(const vsyn_spectral_spec* sp) { return sp->kind == VSYN_SPEC_CHROMA || sp->kind == VSYN_SPEC_TONNETZ; }
+static const vsyn_spectral_chroma SPEC_CHROMA_DEFAULTS = {12u, VSYN_CHROMA_NORM_MAX, VSYN_CHROMA_BASE_C, 0u, 0.0, 5.0, 2.0};
+static inline const vsyn_spectral_chroma* spec_chroma_or_defaults(const vsyn_spectral_chroma* ch) { return ch ? ch : &SPEC_CHROMA_DEFAULTS; }
+
+// Columns of a row (vsyn_spectral_dim, vsyn_spectral_chroma_dim): the one formula on the C side; 0 for an unknown kind. ch (NULL:
+// the defaults) is read for the chroma kinds only.
+static inline uint32_t spec_dim(const vsyn_spectral_spec* sp, const vsyn_spectral_chroma* ch = nullptr) {
   switch (sp->kind) {
+    case VSYN_SPEC_CHROMA: return spec_chroma_or_defaults(ch)->n_chroma;
+    case VSYN_SPEC_TONNETZ: return 6u;
     case VSYN_SPEC_MEL_POWER:
     case VSYN_SPEC_LOG_MEL:
     case VSYN_SPEC_MEL_DB: return sp->n_mels;
@@ -256,10 +267,10 @@ static inline uint32_t spec_dim(const vsyn_spectral_spec* sp) {
   }
 }
 
-// The checks of the spec and of every segment's rate (0 = skipped segment).
-static inline int spec_check(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const char** err) {
+// The checks of the spec and of every segment's rate (0 = skipped segment); ch (NULL: the defaults) is read for the chroma kinds only.
+static inline int spec_check(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const char** err, const vsyn_spectral_chroma* ch = nullptr) {
   if (!sp) return fail(err, VSYN_ERR_INVALID, "spectral spec is NULL");
-  if (sp->kind < VSYN_SPEC_MEL_POWER || sp->kind > VSYN_SPEC_STFT) return fail(err, VSYN_ERR_INVALID, "unknown spectral kind %u", sp->kind);
+  if (sp->kind < VSYN_SPEC_MEL_POWER || sp->kind > VSYN_SPEC_TONNETZ) return fail(err, VSYN_ERR_INVALID, "unknown spectral kind %u", sp->kind);
   if (sp->options & ~(VSYN_SPEC_CENTER | VSYN_SPEC_HTK | VSYN_SPEC_NO_NORM)) return fail(err, VSYN_ERR_INVALID, "unknown spectral options 0x%x", sp->options);
   if (sp->n_fft < 16 || sp->n_fft > 8192) return fail(err, VSYN_ERR_INVALID, "n_fft %u outside [16, 8192]", sp->n_fft);
   if (sp->hop_length < 1) return fail(err, VSYN_ERR_INVALID, "hop_length must be >= 1");
@@ -267,6 +278,18 @@ static inline int spec_check(const vsyn_spectral_spec* sp, uint32_t S, const uin
   if (spec_is_lin(sp)) {  // no mel field is read, and a rate only decides whether its segment is skipped
     if (sp->kind != VSYN_SPEC_STFT && sp->power != 1 && sp->power != 2) return fail(err, VSYN_ERR_INVALID, "power must be 1 or 2");
     if (sp->kind == VSYN_SPEC_LIN_DB && (!(sp->amin > 0.0) || !(sp->top_db >= 0.0))) return fail(err, VSYN_ERR_INVALID, "amin must be > 0 and top_db >= 0");
+    if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
+    return VSYN_OK;
+  }
+  if (spec_is_chroma(sp)) {  // the framing and power as for a linear kind, then the chroma parameters; no mel field is read
+    ch = spec_chroma_or_defaults(ch);
+    if (sp->power != 1 && sp->power != 2) return fail(err, VSYN_ERR_INVALID, "power must be 1 or 2");
+    if (ch->n_chroma < 1 || ch->n_chroma > 256) return fail(err, VSYN_ERR_INVALID, "n_chroma %u outside [1, 256]", ch->n_chroma);
+    if (ch->norm > VSYN_CHROMA_NORM_MAX) return fail(err, VSYN_ERR_INVALID, "unknown chroma norm %u", ch->norm);
+    if (ch->options & ~(VSYN_CHROMA_BASE_C | VSYN_CHROMA_NO_OCT)) return fail(err, VSYN_ERR_INVALID, "unknown chroma options 0x%x", ch->options);
+    if (!std::isfinite(ch->tuning) || !std::isfinite(ch->ctroct)) return fail(err, VSYN_ERR_INVALID, "chroma tuning and ctroct must be finite");
+    if (!(ch->options & VSYN_CHROMA_NO_OCT) && !(std::isfinite(ch->octwidth) && ch->octwidth > 0.0))
+      return fail(err, VSYN_ERR_INVALID, "chroma octwidth must be finite and > 0");
     if (S && !rates) return fail(err, VSYN_ERR_INVALID, "sample_rates is NULL");
     return VSYN_OK;
   }
@@ -294,7 +317,7 @@ static inline uint32_t spec_tile(const vsyn_spectral_spec* sp) {  // frames per 
 
 // SpecHeader, twiddles, window, per-rate bands and weights, DCT matrix, per-segment rate index. Call after spec_check.
 static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, std::vector<uint8_t>& out) {
-  const uint32_t n = sp->n_fft, NM = spec_is_lin(sp) ? 0u : sp->n_mels, nb = n / 2u + 1u;  // a linear kind: no mel table
+  const uint32_t n = sp->n_fft, NM = spec_is_lin(sp) || spec_is_chroma(sp) ? 0u : sp->n_mels, nb = n / 2u + 1u;  // a linear or chroma kind: no mel table
   const bool htk = (sp->options & VSYN_SPEC_HTK) != 0, norm = !(sp->options & VSYN_SPEC_NO_NORM);
   std::vector<uint32_t> distinct, seg_rate(S, SPEC_SKIP);
   for (uint32_t g = 0; g < S; ++g) {
@@ -372,14 +395,18 @@ static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, co
 static inline int spec_lin_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
                                   uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
                                   uint64_t* d_segoff, hipStream_t s, const char** err);  // vsyn_spectral_lin.h
+static inline int spec_chroma_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, const vsyn_spectral_chroma* ch, uint32_t S,
+                                     const uint32_t* rates, const float* d_pcm, uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si,
+                                     uint64_t f_max, float* d_rows, uint64_t* d_segoff, hipStream_t s, const char** err);  // vsyn_chroma.h
 
-// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s (a linear kind: spec_lin_launch); frames from d_frames, else from si. f_max bounds every
+// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s (a linear kind: spec_lin_launch; a chroma kind: spec_chroma_launch with ch, NULL for the defaults); frames from d_frames, else from si. f_max bounds every
 // segment's STFT frames, rows_bound the total rows. Caller holds the handle's lock and has run spec_check.
 static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
                        uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
-                       uint64_t* d_segoff, hipStream_t s, const char** err) {
+                       uint64_t* d_segoff, hipStream_t s, const char** err, const vsyn_spectral_chroma* ch = nullptr) {
   if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
   if (spec_is_lin(sp)) return spec_lin_launch(ws, device, sp, S, rates, d_pcm, plane, C, d_frames, si, f_max, d_rows, d_segoff, s, err);
+  if (spec_is_chroma(sp)) return spec_chroma_launch(ws, device, sp, ch, S, rates, d_pcm, plane, C, d_frames, si, f_max, d_rows, d_segoff, s, err);
   const uint32_t ft = spec_tile(sp);
   if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", sp->n_fft, sp->hop_length);
   std::vector<uint8_t> tab;

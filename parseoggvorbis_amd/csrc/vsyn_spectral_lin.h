@@ -9,7 +9,9 @@
 //                                    untangling pass X[k] = E + w_k O with E, O from Z[k] and conj Z[M - k]. A frame owns its M
 //                                    complex words: nothing of one frame enters another's sums. The twiddles sit in LDS twice: per
 //                                    pass a compact run of Ns entries (so a pass reads them at stride 1, whatever its span), and
-//                                    the n_fft / 2 + 1 entries of the untangling pass.
+//                                    the n_fft / 2 + 1 entries of the untangling pass. The tile's transforms and one bin's
+//                                    untangling are the __device__ helpers spec_lin_fft_tile_run and spec_lin_untangle, which
+//                                    the chroma kernel (vsyn_chroma.h) calls as well.
 //   vsyn_spec_lin_direct_kernel<FT>  any other n_fft: the loop of vsyn_spec_stft_kernel (twiddle index walked by (j k) mod n_fft, one
 //                                    fma chain per component, j ascending over the window's support), its sums stored as bins.
 //   vsyn_spec_lin_clamp_kernel       LIN_DB with top_db > 0, after either: the clamp against the segment's maximum, elementwise.
@@ -53,16 +55,38 @@ __device__ __forceinline__ void spec_lin_seg_max(const SpecCtx& A, uint32_t g, f
   if ((threadIdx.x & 63u) == 0 && mx > -INFINITY) atomicMax(A.segmax + g, spec_key(mx));
 }
 
-__global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_lin_fft_kernel(const SpecCtx A, const uint32_t ft, const uint32_t lgM) {
-  extern __shared__ float lds[];
-  const SpecHeader* H = spec_hdr(A.tab);
-  const uint32_t g = blockIdx.y, tid = threadIdx.x;
-  const uint32_t F = A.segF[g];
-  const uint32_t f0 = blockIdx.x * ft;
-  if (f0 >= F) return;
-  const uint32_t n = H->n, hop = H->hop, nb = H->nbins, win = H->win, woff = H->woff;
+// The transforms of one tile, shared by vsyn_spec_lin_fft_kernel and the chroma kernel (vsyn_chroma.h): what spec_lin_fft_tile_run
+// leaves in LDS. Z[f * M + m] is frame f's half-size transform, un its untangling twiddles, and spare the other ping-pong buffer
+// ([ft][M] float2), free behind the last pass.
+struct SpecLinFft {
+  const float2* Z;
+  const float2* un;
+  float2* spare;
+};
+
+// Bin k <= M of one frame from its half-size transform Z: X[k] = E + w_k O, E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i,
+// Z[M] = Z[0]; X[M] = Re Z[0] - Im Z[0]
+__device__ __forceinline__ void spec_lin_untangle(const float2* Z, const float2* s_un, uint32_t M, uint32_t k, float& re, float& im) {
+  const float2 a = Z[k & (M - 1u)], b = Z[(M - k) & (M - 1u)];
+  if (k == M) {
+    re = a.x - a.y;
+    im = 0.f;
+  } else {
+    const float er = 0.5f * (a.x + b.x), ei = 0.5f * (a.y - b.y);
+    const float qr = 0.5f * (a.y + b.y), qi = 0.5f * (b.x - a.x);
+    const float2 w = s_un[k];
+    re = er + (w.x * qr + w.y * qi);
+    im = ei + (w.x * qi - w.y * qr);
+  }
+}
+
+// The twiddles, the windowed frames f0 .. f0 + nf - 1 of segment g and their Stockham passes, by the whole workgroup; ends behind a
+// barrier. LDS image: spec_lin_fft_lds_floats.
+__device__ __forceinline__ SpecLinFft spec_lin_fft_tile_run(const SpecCtx& A, const SpecHeader* H, float* lds, uint32_t ft, uint32_t lgM, uint32_t g,
+                                                            uint32_t f0, uint32_t nf) {
+  const uint32_t tid = threadIdx.x;
+  const uint32_t n = H->n, hop = H->hop, win = H->win, woff = H->woff;
   const uint32_t M = n >> 1, half = M >> 1;
-  const uint32_t nf = min(ft, F - f0);
   float2* s_st = (float2*)lds;  // pass Ns reads s_st[Ns - 1 + k] = exp(-2 pi i k / (2 Ns)) as (cos, sin), k < Ns
   float2* s_un = s_st + M;      // s_un[k] = (cos, sin)(2 pi k / n), k <= M
   float2* src = s_un + M + 1u;
@@ -116,24 +140,25 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_lin_fft_kernel(const S
     dst = sw;
   }
   __syncthreads();
-  // untangling: X[k] = E + w_k O, E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i, Z[M] = Z[0]; X[M] = Re Z[0] - Im Z[0]
+  return SpecLinFft{src, s_un, dst};
+}
+
+__global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_lin_fft_kernel(const SpecCtx A, const uint32_t ft, const uint32_t lgM) {
+  extern __shared__ float lds[];
+  const SpecHeader* H = spec_hdr(A.tab);
+  const uint32_t g = blockIdx.y, tid = threadIdx.x;
+  const uint32_t F = A.segF[g];
+  const uint32_t f0 = blockIdx.x * ft;
+  if (f0 >= F) return;
+  const uint32_t nb = H->nbins, M = H->n >> 1;
+  const uint32_t nf = min(ft, F - f0);
+  const SpecLinFft T = spec_lin_fft_tile_run(A, H, lds, ft, lgM, g, f0, nf);
   const uint64_t r0 = A.segoff[g] + f0;
   float mx = -INFINITY;
   for (uint32_t q = tid; q < nf * nb; q += SPEC_THREADS) {
     const uint32_t f = q / nb, k = q - f * nb;
-    const float2* Z = src + (size_t)f * M;
-    const float2 a = Z[k & (M - 1u)], b = Z[(M - k) & (M - 1u)];
     float re, im;
-    if (k == M) {
-      re = a.x - a.y;
-      im = 0.f;
-    } else {
-      const float er = 0.5f * (a.x + b.x), ei = 0.5f * (a.y - b.y);
-      const float qr = 0.5f * (a.y + b.y), qi = 0.5f * (b.x - a.x);
-      const float2 w = s_un[k];
-      re = er + (w.x * qr + w.y * qi);
-      im = ei + (w.x * qi - w.y * qr);
-    }
+    spec_lin_untangle(T.Z + (size_t)f * M, T.un, M, k, re, im);
     mx = fmaxf(mx, spec_lin_emit(H, A.rows, r0 + f, k, re, im));
   }
   if (H->kind == VSYN_SPEC_LIN_DB) spec_lin_seg_max(A, g, mx);

@@ -213,10 +213,11 @@ static inline int post_check(const vsyn_spectral_post* p, const char** err, uint
 
 // The post spec of a spectral entry point against its (checked) spectral spec: post_check with the rows' width, after the refusal
 // of the stage on rows of a linear kind (its layout holds 256 columns), which comes before the given vectors are read.
-static inline int spec_post_check(const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, const char** err) {
+static inline int spec_post_check(const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, const char** err,
+                                  const vsyn_spectral_chroma* chroma = nullptr) {
   if (int rc = post_check(post, err)) return rc;
   if (spec_is_lin(spec) && post_on(post)) return fail(err, VSYN_ERR_INVALID, "the post stage does not take rows of a linear kind (kind %u)", spec->kind);
-  return post_check(post, err, spec_dim(spec) * (1u + post->order));
+  return post_check(post, err, spec_dim(spec, chroma) * (1u + post->order));
 }
 
 // A segment shorter than the delta window is refused by name.

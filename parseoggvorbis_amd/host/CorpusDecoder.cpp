@@ -84,7 +84,7 @@ bool loudness_run(const CorpusOptions& o) { return o.loudness; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
 uint32_t spectral_dim(const CorpusOptions& o) {
-  return vsyn_spectral_dim(&o.spectral) * (1u + o.post.order);
+  return vsyn_spectral_chroma_dim(&o.spectral, o.chroma_entry && o.chroma_given ? &o.chroma_spec : nullptr) * (1u + o.post.order);
 }
 bool feature_needs_residue(const CorpusOptions& o) {
   return o.features.kind == VSYN_FEAT_RESIDUE_YS || o.features.kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
@@ -643,7 +643,15 @@ struct Feeder {
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
     const vsyn_spectral_post* post = post_run(opts) ? &opts.post : nullptr;
     int rc;
-    if (opts.loudness_norm) {  // the one form with every stage's spec
+    if (opts.chroma_entry) {  // the form with every stage's spec and the chroma parameters; a NULL spec is a stage that is off
+      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+      rc = vsyn_pcm_chain_chroma_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
+                                      cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr, post,
+                                      S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(),
+                                      opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
+                                      opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
+                                      opts.loudness_norm ? o.loud.data() : nullptr, &st, &err);
+    } else if (opts.loudness_norm) {  // the one form with every stage's spec
       o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
       rc = vsyn_pcm_chain_spectral_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.loudness_spec, cond, &opts.spectral,
                                         opts.pcen ? &opts.pcen_spec : nullptr, post, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
@@ -1271,12 +1279,19 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
                     const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr,
                     const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr, const vsyn_pcm_trim* split = nullptr,
                     const SplitOuts* so = nullptr, const vsyn_spectral_pcen* pcen = nullptr, const vsyn_loudness_spec* loud = nullptr,
-                    vsyn_loudness_record* records_out = nullptr) {
+                    vsyn_loudness_record* records_out = nullptr, bool chroma_entry = false, const vsyn_spectral_chroma* chroma = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
+  if (chroma_entry && !vsyn_spectral_chroma_dim(spec, chroma))
+    return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or chroma spec", error_out);
   CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
   opts.spectral = *spec;
+  opts.chroma_entry = chroma_entry;
+  if (chroma) {
+    opts.chroma_given = true;
+    opts.chroma_spec = *chroma;
+  }
   opts.resample_rate = target_rate;
   if (post) opts.post = *post;
   if (pcen) {
@@ -1564,6 +1579,26 @@ extern "C" int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, cons
   return spectral_corpus("ogg_vorbis_spectral_corpus_loud", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
                          post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
                          split ? gate : nullptr, &so, pcen, loud, records_out);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                                 uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec,
+                                                 const vsyn_spectral_chroma* chroma, uint32_t target_rate, const vsyn_spectral_pcen* pcen,
+                                                 const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* gate,
+                                                 int gate_is_split, const vsyn_loudness_spec* loud, float** rows_out, uint64_t* rows_count_out,
+                                                 uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
+                                                 uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                                 const char** error_out_per_file, double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.frames_out = frames_out;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  so.begin(num_files);
+  const bool split = gate && gate_is_split;
+  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
+  return spectral_corpus("ogg_vorbis_spectral_corpus_chroma", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
+                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
+                         split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma);
 }
 
 extern "C" int ogg_vorbis_loudness_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

@@ -135,6 +135,11 @@ struct CorpusOptions {
   // default is off: today's output and today's entry points.
   bool loudness = false, loudness_blocks = false, loudness_norm = false;
   vsyn_loudness_spec loudness_spec = {0u, VSYN_LOUD_SUM, 0.0};
+  // chroma_entry (a spectral run): the rows come through vsyn_pcm_chain_chroma_host, whatever stages are on, with chroma_spec
+  // (chroma_given) or NULL for the defaults (include/vorbis_synth_hip.h, "chroma"). The kinds VSYN_SPEC_CHROMA and VSYN_SPEC_TONNETZ
+  // without it run with the default chroma parameters through today's entry points, as every spectral entry point serves them.
+  bool chroma_entry = false, chroma_given = false;
+  vsyn_spectral_chroma chroma_spec = {12u, VSYN_CHROMA_NORM_MAX, VSYN_CHROMA_BASE_C, 0u, 0.0, 5.0, 2.0};
 };
 
 struct CorpusStats {
@@ -284,6 +289,17 @@ int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* l
                                     uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
                                     uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                     const char** error_out_per_file, double* stats_out, const char** error_out);
+// ogg_vorbis_spectral_corpus_loud with every stage's spec NULL-able (loud = NULL: no normaliser, records_out zeroed) and the chroma
+// parameters of the kinds VSYN_SPEC_CHROMA and VSYN_SPEC_TONNETZ (chroma = NULL: the defaults; not read for another kind): the rows
+// come through vsyn_pcm_chain_chroma_host (CorpusOptions::chroma_entry), dim = vsyn_spectral_chroma_dim(spec, chroma), times
+// 1 + post->order with the post stage. A chroma spec the stage refuses refuses the call. Same output contract.
+int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                      uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                                      uint32_t target_rate, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post,
+                                      const vsyn_pcm_cond* cond, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                                      float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out,
+                                      uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                      const char** error_out_per_file, double* stats_out, const char** error_out);
 // The intervals alone (CorpusOptions::intervals_only): decode, resample (target_rate != 0), frame energies, intervals; no PCM comes
 // back from the device. frames_out / rate_out: each file's (resampled) length and rate; intervals_out / intervals_count_out as above.
 int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

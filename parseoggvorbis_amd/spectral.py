@@ -12,7 +12,9 @@ mean / variance normalisation; tests/spectral_post_model.py is their float64 mod
 waveform on the device in front of the STFT (include/vorbis_synth_hip.h, "PCM conditioning"; model: tests/condition_model.py), and
 trim_db cuts its silent head and tail in front of both ("PCM trimming"; model: tests/trim_model.py), or split_db every silent
 stretch ("PCM splitting"; model: tests/split_model.py). pcen=True turns the rows of "mel_power" or "lin_power" into librosa.pcen's
-on the device, between the spectral rows and delta / normalize ("PCEN"; model: tests/pcen_model.py)."""
+on the device, between the spectral rows and delta / normalize ("PCEN"; model: tests/pcen_model.py). kind="chroma" / "tonnetz" give
+librosa.feature.chroma_stft's pitch-class rows and librosa.feature.tonnetz's coordinates from them ("chroma"; model:
+tests/chroma_model.py; ogg_vorbis_spectral_corpus_chroma)."""
 import ctypes as C
 import math
 
@@ -23,6 +25,13 @@ from ._corpus import HOST_LIB_PATH  # noqa: F401
 
 KINDS = {"mel_power": 1, "log_mel": 2, "mel_db": 3, "mfcc": 4, "lin_power": 5, "lin_db": 6, "stft": 7}
 LINEAR_KINDS = (5, 6, 7)  # include/vorbis_synth_hip.h, "linear spectra": no filterbank, rows of n_fft / 2 + 1 bins
+# include/vorbis_synth_hip.h, "chroma": rows of n_chroma pitch classes, and the 6 tonnetz coordinates from them. A table of their own:
+# KINDS holds the kinds whose row width the spectral spec alone decides (vsyn_spectral_dim), these need the chroma arguments as well
+CHROMA_KINDS = {"chroma": 8, "tonnetz": 9}
+ALL_KINDS = dict(KINDS, **CHROMA_KINDS)  # what kind= accepts
+CHROMA_NORMS = {None: 0, 1: 1, 2: 2, math.inf: 3}  # chroma_norm -> vsyn_spectral_chroma.norm
+CHROMA_BASE_C, CHROMA_NO_OCT = 1, 2
+MAX_N_CHROMA = 256
 OPT_CENTER, OPT_HTK, OPT_NO_NORM = 1, 2, 4
 MAX_N_FFT, MAX_N_MELS = 8192, 256
 
@@ -43,8 +52,8 @@ def spectral_spec(kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n
     file) and returns the C spec (binding.SpectralSpec). Every argument is checked for every kind, the linear kinds ("lin_power",
     "lin_db", "stft": "linear spectra" there) included, although the device reads no mel argument for those."""
     from .binding import SpectralSpec
-    if kind not in KINDS:
-        raise SpectralError("invalid spectral kind %r; supported kinds: %s" % (kind, ", ".join(sorted(KINDS))))
+    if kind not in ALL_KINDS:
+        raise SpectralError("invalid spectral kind %r; supported kinds: %s" % (kind, ", ".join(sorted(ALL_KINDS))))
     n_fft = _int("n_fft", n_fft)
     hop_length = _int("hop_length", hop_length)
     win_length = n_fft if win_length is None else _int("win_length", win_length)
@@ -79,16 +88,47 @@ def spectral_spec(kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n
     if kind in ("mel_db", "mfcc", "lin_db") and not top_db >= 0:
         raise SpectralError("top_db must be >= 0 (or None), got %r" % top_db)
     opts = (OPT_CENTER if center else 0) | (OPT_HTK if htk else 0) | (OPT_NO_NORM if norm is None else 0)
-    return SpectralSpec(KINDS[kind], opts, n_fft, hop_length, win_length, n_mels, n_mfcc if kind == "mfcc" else 0, int(power),
+    return SpectralSpec(ALL_KINDS[kind], opts, n_fft, hop_length, win_length, n_mels, n_mfcc if kind == "mfcc" else 0, int(power),
                         fmin, fmax, log_floor, amin, top_db)
 
 
-def spec_dim(spec):
-    """Columns of a row under spec (vsyn_spectral_dim; the one formula on the Python side, usable before the library loads):
-    n_mfcc for "mfcc", n_fft / 2 + 1 for "lin_power" and "lin_db", twice that for "stft" (re, im interleaved), n_mels otherwise;
-    0 for an unknown kind."""
+def chroma_spec(n_chroma=12, tuning=0.0, chroma_norm=math.inf, ctroct=5.0, octwidth=2.0, base_c=True):
+    """Checks the chroma arguments (include/vorbis_synth_hip.h, "chroma", step 6) and returns the C struct (binding.SpectralChroma).
+    chroma_norm: numpy.inf (max), 1, 2 or None; octwidth=None: no octave weighting. tuning is a number: librosa's tuning=None
+    (estimate_tuning) is not available."""
+    from .binding import SpectralChroma
+    n_chroma = _int("n_chroma", n_chroma)
+    if not 1 <= n_chroma <= MAX_N_CHROMA:
+        raise SpectralError("n_chroma must be in [1, %d], got %d" % (MAX_N_CHROMA, n_chroma))
+    if isinstance(chroma_norm, bool) or not (chroma_norm is None or (isinstance(chroma_norm, (int, float, np.integer, np.floating))
+                                                                     and chroma_norm in (1, 2, math.inf))):
+        raise SpectralError("chroma_norm must be numpy.inf, 1, 2 or None, got %r" % (chroma_norm,))
+    norm = CHROMA_NORMS[None if chroma_norm is None else (math.inf if chroma_norm == math.inf else int(chroma_norm))]
+    vals = {}
+    for name, v in (("tuning", tuning), ("ctroct", ctroct), ("octwidth", octwidth)):
+        if name == "octwidth" and v is None:
+            vals[name] = 0.0
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+            raise SpectralError("%s must be a finite number%s, got %r" % (name, " (or None)" if name == "octwidth" else "", v))
+        vals[name] = float(v)
+    if octwidth is not None and not vals["octwidth"] > 0.0:
+        raise SpectralError("octwidth must be > 0 (or None), got %r" % (octwidth,))
+    if not isinstance(base_c, (bool, np.bool_)):
+        raise SpectralError("base_c must be True or False, got %r" % (base_c,))
+    opts = (CHROMA_BASE_C if base_c else 0) | (CHROMA_NO_OCT if octwidth is None else 0)
+    return SpectralChroma(n_chroma, norm, opts, 0, vals["tuning"], vals["ctroct"], vals["octwidth"])
+
+
+def spec_dim(spec, chroma=None):
+    """Columns of a row under spec (the one formula on the Python side, usable before the library loads): n_mfcc for "mfcc",
+    n_fft / 2 + 1 for "lin_power" and "lin_db", twice that for "stft" (re, im interleaved), n_mels for the other mel kinds; 0 for an
+    unknown kind. Without chroma it is vsyn_spectral_dim, which answers 0 for "chroma" and "tonnetz" (their width is a chroma
+    argument); with chroma (chroma_spec(...); chroma_spec() for the defaults) it is vsyn_spectral_chroma_dim: n_chroma and 6."""
     if spec.kind == KINDS["mfcc"]:
         return spec.n_mfcc
+    if spec.kind in CHROMA_KINDS.values():
+        return 0 if chroma is None else chroma.n_chroma if spec.kind == CHROMA_KINDS["chroma"] else 6
     if spec.kind in LINEAR_KINDS:
         return (spec.n_fft // 2 + 1) * (2 if spec.kind == KINDS["stft"] else 1)
     return spec.n_mels if spec.kind in KINDS.values() else 0
@@ -182,7 +222,8 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                        normalize=None, std_floor=1e-5, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048,
                        trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None,
                        pcen=False, pcen_gain=0.98, pcen_bias=2.0, pcen_power=0.5, pcen_time_constant=0.4, pcen_eps=1e-6, pcen_b=None,
-                       pcen_scale=1.0, loudness_normalize=None, loudness=None):
+                       pcen_scale=1.0, loudness_normalize=None, loudness=None, n_chroma=12, tuning=0.0, chroma_norm=math.inf, ctroct=5.0,
+                       octwidth=2.0, base_c=True):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels for the other mel kinds. The linear kinds have no filterbank: "lin_power" is |X|^power and "lin_db" its dB image
     (amin, top_db as for "mel_db"; librosa.amplitude_to_db(|X|, amin=a) is power=2, amin=a*a), both (frames, n_fft / 2 + 1);
@@ -213,13 +254,20 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     loudness_normalize=L (LUFS in [-70, 0]; excludes peak_normalize) scales the mono signal to the integrated loudness L behind
     trim_db / split_db and in front of the pre-emphasis, as get_pcm_batch(mono=True, loudness_normalize=L, ...) does, and the rows are
     those of that signal; loudness (optional list) receives the measured LUFS per file. A file the measurement refuses (shorter than
-    400 ms, silent, not finite, below 4000 Hz) fails alone. With loudness_normalize=None nothing is launched."""
+    400 ms, silent, not finite, below 4000 Hz) fails alone. With loudness_normalize=None nothing is launched.
+    kind="chroma" gives librosa.feature.chroma_stft's arithmetic (include/vorbis_synth_hip.h, "chroma"; model: tests/chroma_model.py):
+    (frames, n_chroma) rows of the |X|^power spectrum (power=2 is chroma_stft's) projected on librosa.filters.chroma(sr, n_fft,
+    n_chroma, tuning, ctroct, octwidth, base_c) and normalised per frame by chroma_norm (numpy.inf, 1, 2 or None); octwidth=None turns
+    the octave weighting off. tuning must be a number (librosa's tuning=None estimation is not available). kind="tonnetz" gives
+    librosa.feature.tonnetz(chroma=those rows): (frames, 6). A frame that holds an Inf or NaN sample is all NaN. Both take delta /
+    normalize and every PCM stage like the mel kinds, and refuse pcen. The chroma arguments are checked for every kind."""
     _corpus.check_errors(errors)
     from .pcm import check_sr, cond_spec, give_loudness, give_split_index, give_trim_index, loudness_args, split_spec, trim_spec
     target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
-    post, dim, keep = post_spec(spec_dim(spec), delta, delta_width, normalize, std_floor)
+    chroma = chroma_spec(n_chroma, tuning, chroma_norm, ctroct, octwidth, base_c)
+    post, dim, keep = post_spec(spec_dim(spec, chroma), delta, delta_width, normalize, std_floor)
     if post is not None and spec.kind in LINEAR_KINDS:
         raise SpectralError("delta / normalize are not available for the linear kind %r (rows of %d columns; the post stage holds 256)"
                             % (kind, dim))
@@ -234,7 +282,8 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     loud = loudness_args(loudness_normalize, loudness, cond, SpectralError)
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
-    if loud is not None:  # the one entry with every stage's spec, the normaliser's among them (NULL: off)
+    is_chroma = kind in CHROMA_KINDS
+    if loud is not None or is_chroma:  # the entries with every stage's spec, the normaliser's among them (NULL: off); a chroma kind: with the chroma parameters
         from .binding import LOUDNESS_RECORD_DTYPE
         n = len(list_of_bytes)
         ib = _corpus.IntervalBuffers(lib, n)
@@ -242,10 +291,11 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
         records = np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
         gate = split if split is not None else trim
         try:
-            res = _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_loud, list_of_bytes,
-                              (threads, feeders, files_per_submit, device, C.byref(spec), target, C.byref(pc) if pcen else None,
+            res = _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_chroma if is_chroma else lib.ogg_vorbis_spectral_corpus_loud, list_of_bytes,
+                              (threads, feeders, files_per_submit, device, C.byref(spec)) + ((C.byref(chroma),) if is_chroma else ()) +
+                              (target, C.byref(pc) if pcen else None,
                                None if post is None else C.byref(post), C.byref(cond) if cond.options else None,
-                               None if gate is None else C.byref(gate), int(split is not None), C.byref(loud)),
+                               None if gate is None else C.byref(gate), int(split is not None), None if loud is None else C.byref(loud)),
                               (counts, bounds, joined, ib.ptrs, ib.counts, records),
                               lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors,
                               "spectral", stats)
@@ -253,7 +303,7 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
         finally:
             ib.free()
         give_trim_index(trim_index, bounds[:n] if trim is not None else None, res)
-        give_loudness(loudness, records, res)
+        give_loudness(loudness, records if loud is not None else None, res)
         return _finish(spec, res)
     give_loudness(loudness, None, [None] * len(list_of_bytes))
     if pcen:  # the one entry with every stage's spec (NULL: off)
