@@ -285,7 +285,10 @@ int vsyn_submit_host_vq(vsyn_handle* h,
  * total emitted frames (the sum of its emit_len), also written to d_frames[g] if d_frames != NULL.
  *   VSYN_PCM_S16  int16, host endian, val = round-to-nearest-even(x * 32768.f) clamped to [-32768, 32767] — ov_read's
  *                 conversion (reference tree: tests/libvorbis-standalone/vorbis_vorbisfile.c:2026-2029 with vorbis_ftoi of
- *                 os.h:156-158); halves the output bytes
+ *                 os.h:156-158); halves the output bytes. +Inf and every product above 32767 give 32767, -Inf and every product
+ *                 below -32768 give -32768, and a NaN gives -32768 (ov_read's own value: its conversion of a NaN is INT_MIN, which
+ *                 the clamp cuts), at every site that writes int16: both forms of this entry, vsyn_pcm_fetch_host and
+ *                 vsyn_pcm_resample_host
  *   VSYN_PCM_F32  float32, values unchanged */
 #define VSYN_PCM_S16 1
 #define VSYN_PCM_F32 2
@@ -445,6 +448,15 @@ int vsyn_features_host(vsyn_handle* h, const vsyn_feature_spec* spec,
  *  7. Checks (VSYN_ERR_INVALID before anything runs): 1 <= hop_length; 1 <= win_length <= n_fft; 16 <= n_fft <= 8192;
  *     1 <= n_mels <= 256; 1 <= n_mfcc <= n_mels (MFCC); 0 <= fmin < fmax <= sr/2 for every segment's rate; power 1 or 2;
  *     log_floor > 0 (LOG_MEL); amin > 0 and top_db >= 0 (MEL_DB, MFCC).
+ *  8. Not finite. Nothing is refused and no status is raised. Frame f reads the samples of its window's support alone, PCM frames
+ *     [f hop - pad + woff, f hop - pad + woff + win_length), pad = n_fft / 2 with VSYN_SPEC_CENTER else 0,
+ *     woff = (n_fft - win_length) / 2. If one of them is Inf or NaN in any channel (under a window value of zero as well), every
+ *     value of row f is Inf or NaN, for every kind: the floors of step 6 keep a NaN (max(NaN, floor) is NaN here, as numpy.maximum
+ *     has it). Every other row has the bits it has without that sample, with one exception that is a rule of its own: with
+ *     top_db > 0 the segment's maximum is taken over its finite D values only, so a value that is not finite takes no part in it,
+ *     and the clamp leaves such a value as it is. Rows outside the footprint are therefore clamped against the maximum of the
+ *     finite values, and a segment without a finite value is not clamped. Samples behind a segment's frames, or that no
+ *     frame's support holds, are never read. Other segments are not touched.
  *
  * Precision: windowed samples, twiddles cos/sin(2 pi m / n_fft) (rounded from double) and mel weights are float32; the DFT
  * and the mel sums accumulate in float32 in a fixed order, so the same PCM always gives the same bits. The error of the DFT
@@ -514,8 +526,11 @@ int vsyn_spectral_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_
  *  5. The post stage ("spectral post-processing") holds rows of at most 256 columns and is refused for these kinds: every entry
  *     point given a vsyn_spectral_post with the stage on (order != 0 or a normalisation) returns VSYN_ERR_INVALID before anything
  *     runs, and vsyn_spectral_post_dim returns 0. A post spec with the stage off is accepted and does nothing, as for the mel kinds.
- *  6. Inf and NaN samples propagate through the sums as they do for the mel kinds (a frame that holds one is Inf / NaN, other
- *     frames are not touched); nothing is refused.
+ *  6. Inf and NaN samples: step 8 of "spectral features", word for word, with S in M's place for LIN_DB (the amin floor keeps a
+ *     NaN; the segment's maximum is over its finite D values; the clamp leaves a value that is not finite as it is). A frame whose
+ *     window's support holds such a sample is Inf / NaN in every bin, other frames are not touched, nothing is refused. For
+ *     VSYN_SPEC_STFT a value is the complex bin: at least one of re_k, im_k is Inf or NaN (im_0 and, for an even n_fft, the last
+ *     bin's im may be the 0 that a real transform gives them, as in numpy.fft.rfft).
  *
  * Arithmetic: float32 throughout, in a fixed order per frame, so that the same PCM gives the same bits alone, in any slot of a
  * batch, at any alignment of the plane and wherever the frame falls in its workgroup's tile. n_fft a power of two: v[j] is one
@@ -636,7 +651,12 @@ int vsyn_spectral_chroma_device(vsyn_handle* h, const vsyn_spectral_spec* spec, 
  *  3. Output: T_out = ceil(T * up / down) frames (vsyn_resample_num_frames), and
  *       y[j] = sum_i x[i] h[j down - i up + H],   h = 0 outside [0, N), x = 0 outside [0, T)  (scipy's padtype 'constant').
  *     Polyphase form, as the device computes it: c = j down + H, phi = c mod up, i0 = c div up, K = ceil(N / up),
- *       y[j] = sum_{t < K} P[phi][t] x[i0 - t],   P[phi][t] = h[phi + t up].
+ *       y[j] = sum_{t < K4} P[phi][t] x[i0 - t],   P[phi][t] = h[phi + t up],   K4 = K rounded up to a multiple of 4.
+ *     The taps with phi + t up >= N, those in [K, K4) among them, are +0: on finite input they add nothing and the sum is the one
+ *     over t < K. They are read all the same, so the rule for Inf and NaN is by K4: output j of a channel is Inf or NaN exactly
+ *     when one of x[i0 - K4 + 1 .. i0] of that channel, inside [0, T), is (0 * Inf and 0 * NaN are NaN), and has the bits it has
+ *     without that sample otherwise. Nothing is refused; the other channel, other segments and T_out are not touched, and
+ *     samples behind a segment's T frames are never read. The rule is the same whether a pair's table is kept in LDS or not.
  *  4. Per segment, per channel: each segment is resampled on its own, zero-padded at both ends; nothing carries across submits.
  *  5. Limits (VSYN_ERR_INVALID before anything runs): 1 <= r_in, 1 <= r_out, and the reduced M = max(up, down) <= 65536.
  *
@@ -705,6 +725,11 @@ int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* sp
  *  4. Checks (VSYN_ERR_INVALID before anything runs): order <= 2; width odd in [3, 65] (whatever the order); norm and stats
  *     among the enums; std_floor finite and > 0; with given statistics and norm != none, mean non-NULL and finite, and for
  *     MEAN_VAR std non-NULL and finite.
+ *  5. Not finite; nothing is refused. An Inf or NaN X[f][d] makes Y[f][d] and D_o[r][d] of every row r whose (clamped) window reads
+ *     row f Inf or NaN (a coefficient of 0 as well: 0 * Inf is NaN); the h edge rows at either end have the window of the first /
+ *     last interior row and go with it. Every other value of Y has the bits it has without it. With VSYN_POST_STATS_SEGMENT the mean and the deviation of
+ *     each column of Y that holds such a value are not finite, and every row of that column of that segment is Inf or NaN (column
+ *     d, and D + d, 2 D + d up to `order`); the other columns and the other segments are not touched.
  *
  * order = 0 with VSYN_POST_NORM_NONE launches nothing: the rows are those of the spectral entry points, bit for bit. The post
  * entry points read rows (and through vsyn_pcm_spectral_post_host, PCM) only: they touch neither stream state, the overlap buffers
@@ -997,7 +1022,10 @@ int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, cons
  *     points a kind other than VSYN_SPEC_MEL_POWER or VSYN_SPEC_LIN_POWER is refused by name: its rows can be negative. librosa's
  *     max_size > 1, ref, zi and return_zf are not built.
  *  7. The device entry does not look at signs: a NaN or a negative input propagates as IEEE arithmetic and the model say, and a NaN
- *     poisons the rest of its column, as in librosa.
+ *     poisons the rest of its column, as in librosa: Y is NaN from its row on, rows before it and the other columns keep their
+ *     bits. A -Inf does the same (M = -Inf, log1p of it is NaN). A +Inf does not: its own row is NaN (S G = Inf * 0), but M stays
+ *     +Inf behind it, so with gain > 0 the gain G is 0 and every later row of the column is the value of step 4 at G = 0, a finite
+ *     0, again as in librosa; with gain = 0, G = exp(-0 * Inf) is NaN and the column is NaN from the row on.
  *
  * Precision and order. The smoother is a blocked scan whose decomposition is a function of the segment's rows alone: blocks of 64
  * rows counted from the segment's first row. Per (block, column) the block's zero-state response at its last row (the recurrence

@@ -12,7 +12,8 @@
 //                              needs, with 16-byte loads and zeros outside [0, T). LDS = false (table + span above RS_LDS_BUDGET,
 //                              e.g. 44056 -> 16000 = 2000 / 5507, a 448 KiB table): P and x come from global memory (L2).
 //                              Both compute y[j] = sum_{t < K4} P[phi][t] x[i0 - t] as one fmaf chain, t ascending: the padded
-//                              taps are +0 and add nothing, and both variants give the same bits. up == down copies.
+//                              taps are +0 and add nothing to finite input (under an Inf or NaN sample they give NaN, which is why
+//                              the header states the sum over K4), and both variants give the same bits. up == down copies.
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include "vsyn_device.h"

@@ -55,7 +55,12 @@ __host__ __device__ __forceinline__ uint64_t spec_num_frames(uint32_t n, uint32_
   return tp < n ? 0ull : 1ull + (tp - n) / hop;
 }
 
-// float -> uint32 with the same order (no NaN here: every dB value is a finite log of a value >= amin > 0)
+// max(x, floor) that keeps a NaN: fmaxf(NaN, floor) is floor, which would turn a frame that holds a NaN sample into a silent one
+__device__ __forceinline__ float spec_floor(float x, float floor) { return x < floor ? floor : x; }
+// A dB value as a candidate for its segment's maximum: a value that is not finite takes no part in it (-inf is below every key).
+__device__ __forceinline__ float spec_max_term(float d) { return fabsf(d) < INFINITY ? d : -INFINITY; }
+
+// float -> uint32 with the same order (no NaN here: only finite dB values get a key, spec_max_term)
 __device__ __forceinline__ uint32_t spec_key(float x) {
   const uint32_t b = __float_as_uint(x);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
@@ -169,10 +174,10 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_stft_kernel(const Spec
     if (kind == VSYN_SPEC_MEL_POWER) {
       A.rows[r * NM + m] = M;
     } else if (kind == VSYN_SPEC_LOG_MEL) {
-      A.rows[r * NM + m] = log10f(fmaxf(M, H->log_floor));
+      A.rows[r * NM + m] = log10f(spec_floor(M, H->log_floor));
     } else {
-      const float d = 10.0f * log10f(fmaxf(M, H->amin));
-      mx = fmaxf(mx, d);
+      const float d = 10.0f * log10f(spec_floor(M, H->amin));
+      mx = fmaxf(mx, spec_max_term(d));
       if (kind == VSYN_SPEC_MEL_DB) A.rows[r * NM + m] = d;
       else A.db[r * NM + m] = d;
     }
@@ -183,7 +188,8 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_stft_kernel(const Spec
   }
 }
 
-// MEL_DB: the top_db clamp in place. MFCC: out[r][i] = sum_m dct[i][m] * max(D[r][m], thr), m ascending.
+// MEL_DB: the top_db clamp in place. MFCC: out[r][i] = sum_m dct[i][m] * max(D[r][m], thr), m ascending. The clamp leaves a value
+// that is not finite as it is, and so does a threshold that is none (a segment without a finite value).
 __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_finish_kernel(const SpecCtx A) {
   __shared__ float s_d[SPEC_FIN_ROWS * 256];
   const SpecHeader* H = spec_hdr(A.tab);
@@ -196,11 +202,11 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_finish_kernel(const Sp
   if (H->kind == VSYN_SPEC_MEL_DB) {
     for (uint32_t q = tid; q < nf * NM; q += SPEC_THREADS) {
       float* p = A.rows + r0 * NM + q;
-      *p = fmaxf(*p, thr);
+      *p = spec_floor(*p, thr);
     }
     return;
   }
-  for (uint32_t q = tid; q < nf * NM; q += SPEC_THREADS) s_d[q] = fmaxf(A.db[r0 * NM + q], thr);
+  for (uint32_t q = tid; q < nf * NM; q += SPEC_THREADS) s_d[q] = spec_floor(A.db[r0 * NM + q], thr);
   __syncthreads();
   const uint32_t D = H->n_mfcc;
   const float* dct = (const float*)(A.tab + H->off_dct);

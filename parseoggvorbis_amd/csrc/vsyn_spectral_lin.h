@@ -30,7 +30,8 @@ __host__ __device__ __forceinline__ uint64_t spec_lin_fft_lds_floats(uint32_t ft
 // LDS image of the direct kernel, in floats: twiddles [2n] | window [n] | span [(ft-1) hop + n]
 __host__ __device__ __forceinline__ uint64_t spec_lin_direct_lds_floats(uint32_t ft, uint32_t n, uint32_t hop) { return 3ull * n + spec_span_len(ft, n, hop); }
 
-// One bin of row r into the kind's layout; returns the dB value of LIN_DB (for the segment's maximum), -inf otherwise.
+// One bin of row r into the kind's layout; returns the dB value of LIN_DB where it is finite (for the segment's maximum), -inf
+// otherwise.
 __device__ __forceinline__ float spec_lin_emit(const SpecHeader* H, float* rows, uint64_t r, uint32_t k, float re, float im) {
   const uint32_t nb = H->nbins;
   if (H->kind == VSYN_SPEC_STFT) {
@@ -45,9 +46,9 @@ __device__ __forceinline__ float spec_lin_emit(const SpecHeader* H, float* rows,
     rows[r * nb + k] = S;
     return -INFINITY;
   }
-  const float d = 10.0f * log10f(fmaxf(S, H->amin));
+  const float d = 10.0f * log10f(spec_floor(S, H->amin));
   rows[r * nb + k] = d;
-  return d;
+  return spec_max_term(d);
 }
 
 __device__ __forceinline__ void spec_lin_seg_max(const SpecCtx& A, uint32_t g, float mx) {
@@ -224,7 +225,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_lin_direct_kernel(cons
   if (H->kind == VSYN_SPEC_LIN_DB) spec_lin_seg_max(A, g, mx);
 }
 
-// LIN_DB: D = max(D, segment's maximum - top_db), over the segment's F * nbins values.
+// LIN_DB: D = max(D, segment's maximum - top_db), over the segment's F * nbins values; a value that is not finite stays.
 __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_lin_clamp_kernel(const SpecCtx A) {
   const SpecHeader* H = spec_hdr(A.tab);
   const uint32_t g = blockIdx.y;
@@ -232,7 +233,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_lin_clamp_kernel(const
   if (total == 0) return;
   const float thr = spec_unkey(A.segmax[g]) - H->top_db;
   float* p = A.rows + A.segoff[g] * H->dim;
-  for (uint64_t i = (uint64_t)blockIdx.x * SPEC_THREADS + threadIdx.x; i < total; i += (uint64_t)gridDim.x * SPEC_THREADS) p[i] = fmaxf(p[i], thr);
+  for (uint64_t i = (uint64_t)blockIdx.x * SPEC_THREADS + threadIdx.x; i < total; i += (uint64_t)gridDim.x * SPEC_THREADS) p[i] = spec_floor(p[i], thr);
 }
 
 // ------------------------------------------------------------------------------------------------

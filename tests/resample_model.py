@@ -50,11 +50,18 @@ def taps(up, down):
     return up * h / h.sum()
 
 
+def padded_taps(N, up):
+    """K4 of step 3: the taps every phase reads, K = ceil(N / up) rounded up to a multiple of 4."""
+    K = -(-N // up)
+    return 4 * (-(-K // 4))
+
+
 def polyphase(up, down, h=None):
-    """P[phi][t] = h[phi + t up], t < K = ceil(N / up), zero past N."""
+    """P[phi][t] = h[phi + t up], t < K4 = K = ceil(N / up) rounded up to a multiple of 4 (step 3), zero past N. The padded taps add
+    nothing to a finite signal; an Inf or NaN sample under one makes the sum NaN, as the header says."""
     h = taps(up, down) if h is None else h
     N = len(h)
-    K = -(-N // up)
+    K = padded_taps(N, up)
     hp = np.zeros(K * up)
     hp[:N] = h
     return hp.reshape(K, up).T.copy()

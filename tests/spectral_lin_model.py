@@ -86,7 +86,9 @@ def frames(x, n_fft, hop_length, win_length=None, center=True):
     p = n_fft // 2 if center else 0
     w = window32(n_fft, win_length).astype(np.float64)
     idx = np.arange(F)[:, None] * hop_length + np.arange(n_fft)[None, :]
-    return np.pad(y, (p, p))[idx] * w[None, :], (np.pad(dmix, (p, p))[idx] * w[None, :]).sum(axis=1)
+    v = np.pad(y, (p, p))[idx] * w[None, :]
+    v[:, ~sm.support(n_fft, win_length)] = 0.0  # v is 0 outside the window's support whatever the sample there is, an Inf or NaN too
+    return v, (np.pad(dmix, (p, p))[idx] * w[None, :]).sum(axis=1)
 
 
 def stft(x, n_fft, hop_length, win_length=None, center=True, extra=None):
@@ -119,9 +121,10 @@ def db_interval(S, dS, amin=1e-10, top_db=80.0):
     want, lo, hi = _db(S, amin), _db(S - dS, amin), _db(S + dS, amin)
     lo = lo - (4.0 * U * np.abs(lo) + 5.2e-7)
     hi = hi + (4.0 * U * np.abs(hi) + 5.2e-7)
-    if top_db and want.size:
-        want = np.maximum(want, want.max() - top_db)
-        tl, th = lo.max() - top_db, hi.max() - top_db
+    if top_db and np.isfinite(want).any():  # the maximum is over the finite values (sm.clamp_top_db); lo and hi are NaN where want is
+        want = sm.clamp_top_db(want, top_db)
+        fin = np.isfinite(want)
+        tl, th = lo[fin].max() - top_db, hi[fin].max() - top_db
         lo = np.maximum(lo, tl - U * abs(tl))
         hi = np.maximum(hi, th + U * abs(th))
     return want, lo, hi

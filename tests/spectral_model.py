@@ -49,6 +49,13 @@ def window(n_fft, win_length=None):
     return w
 
 
+def support(n_fft, win_length=None):
+    """bool [n_fft]: the window's support, [woff, woff + win_length) (a window value of 0 inside it included)."""
+    win_length = n_fft if win_length is None else win_length
+    j = np.arange(n_fft) - (n_fft - win_length) // 2
+    return (j >= 0) & (j < win_length)
+
+
 def num_frames(T, n_fft, hop_length, center=True):
     if T == 0:
         return 0
@@ -69,6 +76,7 @@ def spectrum(x, n_fft=2048, hop_length=512, win_length=None, center=True, power=
     w = window(n_fft, win_length)
     idx = np.arange(F)[:, None] * hop_length + np.arange(n_fft)[None, :]
     frames = yp[idx] * w[None, :]
+    frames[:, ~support(n_fft, win_length)] = 0.0  # a frame reads its window's support alone: an Inf or NaN outside it is not seen
     # the DFT as a matrix product in float64 (any n_fft), exact twiddles from (j * k) mod n_fft
     jk = np.outer(np.arange(n_fft), np.arange(nb)) % n_fft
     ang = 2.0 * np.pi * jk / n_fft
@@ -87,6 +95,15 @@ def dct_ortho(n_mfcc, n_mels):
     return D
 
 
+def clamp_top_db(D, top_db):
+    """Step 6's clamp of one segment's dB values: D = max(D, max of the segment's finite D - top_db). A value that is not finite
+    (a frame that holds an Inf or NaN sample) takes no part in the maximum and stays as it is; top_db 0 or None: no clamp."""
+    fin = np.isfinite(D)
+    if not top_db or not fin.any():
+        return D
+    return np.where(fin, np.maximum(D, D[fin].max() - top_db), D)
+
+
 def spectral(x, sr, kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n_mels=128, fmin=0.0, fmax=None, htk=False,
              norm="slaney", center=True, power=2.0, log_floor=1e-3, amin=1e-10, top_db=80.0, n_mfcc=20):
     """The (frames, dim) matrix of one file in float64, plus the mel power M it was made from."""
@@ -97,8 +114,7 @@ def spectral(x, sr, kind="log_mel", n_fft=2048, hop_length=512, win_length=None,
     if kind == "log_mel":
         return np.log10(np.maximum(M, log_floor)), M
     D = 10.0 * np.log10(np.maximum(M, amin))
-    if top_db and D.size:
-        D = np.maximum(D, D.max() - top_db)
+    D = clamp_top_db(D, top_db)
     if kind == "mel_db":
         return D, M
     return D @ dct_ortho(n_mfcc, n_mels).T, M
