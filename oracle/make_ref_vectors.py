@@ -66,18 +66,24 @@ def main():
     put("neighbors", np.array([(ref.ref_low_neighbor(ob.p(v), len(v), idx), ref.ref_high_neighbor(ob.p(v), len(v), idx))
                                for v in sets for idx in range(1, len(v))], np.int32))
 
+    def floor1(key, cases, accepted=False):
+        failed, decoded = [], []
+        for xs, mult, ys, n in cases:
+            want = np.zeros(n, np.float32)
+            rr = ref.ref_floor1_synth(ob.p(xs), len(xs), mult, ob.p(ys), n, ob.p(want))
+            assert not (accepted and rr), "%s: the reference rejects a case of the table (fix its generator)" % key
+            failed.append(rr != 0)
+            if rr == 0:
+                decoded.append(t.bits(want))
+        out[key + "_failed"] = np.array(failed, bool)
+        put(key, np.concatenate(decoded) if decoded else np.zeros(0, np.uint32))
+
     for mult in t.FLOOR_MULTS:
         for posts, n in t.FLOOR_SHAPES:
-            key = "floor1_%d_%d_%d" % (mult, posts, n)
-            failed, decoded = [], []
-            for xs, ys in t.floor1_inputs(mult, posts, n):
-                want = np.zeros(n, np.float32)
-                rr = ref.ref_floor1_synth(ob.p(xs), posts, mult, ob.p(ys), n, ob.p(want))
-                failed.append(rr != 0)
-                if rr == 0:
-                    decoded.append(t.bits(want))
-            out[key + "_failed"] = np.array(failed, bool)
-            put(key, np.concatenate(decoded) if decoded else np.zeros(0, np.uint32))
+            floor1("floor1_%d_%d_%d" % (mult, posts, n), [(xs, mult, ys, n) for xs, ys in t.floor1_inputs(mult, posts, n)])
+    for geom in t.fg.GEOMETRIES:  # x[1] above / below half the block size, floors shared by both block sizes
+        for bs0, bs1 in t.fg.PAIRS:
+            floor1(*t.geometry_floor1_inputs(geom, bs0, bs1), accepted=True)
 
     for bs0, bs1, channels in t.OVERLAP_CONFIGS:
         for trial, c in enumerate(t.overlap_inputs(bs0, bs1, channels)):

@@ -25,6 +25,18 @@ With --winflags KIND the window flags of chosen long blocks are overridden inste
     python oracle/make_synth_ogg.py --winflags a [first_seed]     flags that agree, except ONE long block with next_long set in
                                                                   front of a short block (class A: the reference accepts it, the
                                                                   device refuses it with VSYN_ST_WINDOW_FLAGS)
+
+With --geometry KIND the floors' x[1] = 1 << rangebits (hpp:447-450) is chosen apart from half the block size (the default recipe
+always writes rangebits = log2(n/2)); one stream of 20 packets with both block sizes, written as tests/golden/synth_NN:
+
+    python oracle/make_synth_ogg.py --geometry beyond2 NN [first_seed]    a floor per block size with x[1] = n (twice the half block):
+                                                                          12..20 posts, posts at n/2 - 1, n/2, n/2 + 1 and at least
+                                                                          three more beyond
+    python oracle/make_synth_ogg.py --geometry shared15 NN [first_seed]   ONE floor with rangebits = 15 (x[1] = 32768) for both block
+                                                                          sizes: a third of its posts inside the short block, a third
+                                                                          up to the long one, the rest in 20000..32767
+
+The committed synth_16 is `--geometry beyond2 16 9` (stereo, 256/2048), synth_17 is `--geometry shared15 17 11` (stereo, 128/1024).
 """
 import os
 import struct
@@ -195,7 +207,7 @@ class Setup:
     pass
 
 
-def make_setup(rng):
+def make_setup(rng, geometry=None):
     s = Setup()
     s.channels = int(rng.choice([1, 2, 2, 2, 3, 3, 4, 6]))
     if os.environ.get("SYNTH_CHANNELS"):  # stress knobs (one-off runs; the committed set uses none)
@@ -204,6 +216,8 @@ def make_setup(rng):
     if os.environ.get("SYNTH_BLOCKS"):
         s.bs0, s.bs1 = (int(v) for v in os.environ["SYNTH_BLOCKS"].split("/"))
     s.rate = 44100
+    if geometry and s.bs0 == s.bs1:  # a geometry stream has both block sizes: the caller tries the next seed
+        return None
     books = []
 
     def add(b):
@@ -212,11 +226,13 @@ def make_setup(rng):
 
     # ---- floors: one per block size ----
     s.floors = []
-    for n in (s.bs0, s.bs1):
+    for n in ((s.bs1,) if geometry == "shared15" else (s.bs0, s.bs1)):
         f = Setup()
         n2 = n // 2
-        f.rangebits = ilog(n2 - 1) if n2 > 1 else 1
-        assert (1 << f.rangebits) == n2
+        # x[1] = 1 << rangebits, whatever the block size (hpp:447-450): log2(n/2) by default, one more for beyond2, 15 for shared15
+        f.rangebits = {None: ilog(n2 - 1) if n2 > 1 else 1, "beyond2": ilog(n2 - 1) + 1, "shared15": 15}[geometry]
+        x1 = 1 << f.rangebits
+        minposts = 12 if geometry else 0
         f.multiplier = int(rng.integers(1, 5))
         rng_y = [256, 128, 86, 64][f.multiplier - 1]
         nclasses = int(rng.integers(1, 4))
@@ -230,7 +246,7 @@ def make_setup(rng):
             c.subbooks = [add(Book(rng, 1, int(rng.integers(4, 13)), 0)) if rng.random() < 0.85 else -1 for _ in range(nsub)]
             c.masterbook = add(Book(rng, 1, nsub ** c.dims if nsub ** c.dims >= 2 else 2, 0)) if c.subclass else 0
             f.classes.append(c)
-        maxposts = min(40, n2 - 1)
+        maxposts = 20 if geometry else min(40, x1 - 1)
         f.part_classes = []
         posts = 2
         while True:
@@ -239,13 +255,26 @@ def make_setup(rng):
                 break
             f.part_classes.append(c)
             posts += f.classes[c].dims
-            if rng.random() < 0.12 and len(f.part_classes) >= 2:
+            if rng.random() < 0.12 and len(f.part_classes) >= 2 and posts >= minposts:
                 break
         # every class index up to the largest one used must exist: the header declares max+1 classes
         used_max = max(f.part_classes) if f.part_classes else -1
         f.classes = f.classes[:used_max + 1]
-        xs_inner = rng.choice(np.arange(1, n2), posts - 2, replace=False).tolist() if posts > 2 else []
-        f.xs = [0, n2] + [int(x) for x in xs_inner]
+        def draw(lo, hi, k):
+            return rng.choice(np.arange(lo, hi), k, replace=False).tolist()
+
+        if geometry == "beyond2":
+            beyond = int(rng.integers(3, 6))
+            xs_inner = [n2 - 1, n2, n2 + 1] + draw(n2 + 2, x1, beyond) + draw(1, n2 - 1, posts - 5 - beyond)
+            rng.shuffle(xs_inner)
+        elif geometry == "shared15":
+            k = (posts - 2) // 3
+            xs_inner = draw(1, s.bs0 // 2, k) + draw(s.bs0 // 2, n2, k) + draw(20000, x1, posts - 2 - 2 * k)
+            rng.shuffle(xs_inner)
+        else:  # inner posts anywhere below x[1]
+            xs_inner = draw(1, x1, posts - 2) if posts > 2 else []
+        f.xs = [0, x1] + [int(x) for x in xs_inner]
+        assert len(set(f.xs)) == posts and max(f.xs) == x1
         f.range = rng_y
         s.floors.append(f)
 
@@ -291,6 +320,7 @@ def make_setup(rng):
     s.residues = []
     s.mappings = []
     blocks = [(0, s.bs0), (1, s.bs1)]
+    floor_of = (lambda blk: 0) if geometry == "shared15" else (lambda blk: blk)
     if rng.random() < 0.35:
         blocks.append((1, s.bs1))  # a second long-block mode with its own mapping (other coupling / submaps / residue)
     for blk, n in blocks:
@@ -310,7 +340,7 @@ def make_setup(rng):
         for sm in range(m.submaps):
             nch = sum(1 for c in range(s.channels) if m.mux[c] == sm)
             s.residues.append(make_residue(n, max(1, nch)))
-            m.sub.append((blk, len(s.residues) - 1))  # (floor, residue)
+            m.sub.append((floor_of(blk), len(s.residues) - 1))  # (floor, residue)
         s.mappings.append(m)
     s.modes = [(blk, k) for k, (blk, _) in enumerate(blocks)]  # (blockflag, mapping)
     s.books = books
@@ -550,16 +580,22 @@ def window_flag_override(flags, rng, kind):
     return (prev, nxt) if cls == {"B", "C", "D"} else None
 
 
-def make_stream(seed, winflags=None):
+def make_stream(seed, winflags=None, geometry=None):
     rng = np.random.default_rng(seed)
-    s = make_setup(rng)
+    s = make_setup(rng, geometry)
+    if s is None:
+        return None, s, 0
     ident = b"\x01vorbis" + struct.pack("<IBIiiiB", 0, s.channels, s.rate, 0, 128000, 0, (ilog(s.bs0) - 1) | ((ilog(s.bs1) - 1) << 4)) + b"\x01"
     vendor = b"synthetic stream for differential tests"
     comment = b"\x03vorbis" + struct.pack("<I", len(vendor)) + vendor + struct.pack("<I", 1) + struct.pack("<I", 6) + b"SEED=%d" % (seed % 10) + b"\x01"
     comment = b"\x03vorbis" + struct.pack("<I", len(vendor)) + vendor + struct.pack("<I", 0) + b"\x01"
     setup = write_setup(s)
     npk = int(os.environ.get("SYNTH_PACKETS", 0)) or int(rng.integers(8, 20) if not winflags else rng.integers(24, 40))
+    if geometry:
+        npk = 20
     flags = [int(rng.random() < 0.55) for _ in range(npk)]
+    if geometry and len(set(flags)) < 2:  # packets of both block sizes
+        return None, s, npk
     override = None
     if winflags:
         override = window_flag_override(flags, rng, winflags) if s.bs0 < s.bs1 else None
@@ -651,16 +687,22 @@ def main():
         winflags = argv[1]
         assert winflags in ("a", "bcd"), winflags
         argv = ["1"] + argv[2:]
+    geometry, index = None, 0
+    if argv[:1] == ["--geometry"]:
+        geometry, index = argv[1], int(argv[2])
+        assert geometry in ("beyond2", "shared15"), geometry
+        argv = ["1"] + argv[3:]
     count = int(argv[0]) if len(argv) > 0 else 12
     seed = int(argv[1]) if len(argv) > 1 else 1
     made = 0
     while made < count:
-        data, s, npk = make_stream(seed, winflags)
+        data, s, npk = make_stream(seed, winflags, geometry)
         if data is None:
-            print("seed %d skipped: the block sequence cannot carry --winflags %s" % (seed, winflags))
+            print("seed %d skipped: %s" % (seed, ("the block sequence cannot carry --winflags %s" % winflags) if winflags else
+                                           "equal block sizes, or packets of one size only"))
             seed += 1
             continue
-        path = os.path.join(OUT, ("winflags_%s.ogg" % winflags) if winflags else ("synth_%02d.ogg" % made))
+        path = os.path.join(OUT, ("winflags_%s.ogg" % winflags) if winflags else ("synth_%02d.ogg" % (index + made)))
         open(path, "wb").write(data)
         vec, why = reference_vectors(path)
         too_big = vec is not None and vec["pcm"].nbytes > int(os.environ.get("SYNTH_MAX_PCM_BYTES", "1000000000"))

@@ -394,13 +394,16 @@ int vsyn_create(const vsyn_setup* setup, int device, uint32_t max_streams, vsyn_
   HC(hipFuncSetAttribute((const void*)vsyn_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 68 * PREP_THREADS * 4));
   HC(h->ws_count.ensure(vsyn_handle::CNT_RING));
   HC(hipMemset(h->ws_count.p, 0, sizeof(uint32_t) * vsyn_handle::CNT_RING));
-  h->fused_mask = fused_ok_mask(h->H, h->host_const.data());
+  // A floor whose posts lie outside the domain in which the fused kernels' float32 curve is proven exact (floor_closed_form_ok,
+  // vsyn_fused.h: x[1] far beyond the half block) keeps the whole setup on the staged kernels, whose curve is integer.
+  const bool curve_ok = floor_closed_form_ok(h->H, h->host_const.data());
+  h->fused_mask = curve_ok ? fused_ok_mask(h->H, h->host_const.data()) : 0u;
   if ((e = fused_tables_create(h->H, h->host_const.data(), &h->fused, h->opt.debug)) != hipSuccess) {
     fail(err, VSYN_ERR_HIP, "fused table upload failed: %s", hipGetErrorString(e));
     return cleanup(VSYN_ERR_HIP);
   }
   // The size-generic kernel takes the mixed-block runs of every setup it covers where the 256/2048 kernel has no mixed path.
-  if (!(h->fused_mask & 2u) && u_supported(h->H, h->host_const.data())) {
+  if (curve_ok && !(h->fused_mask & 2u) && u_supported(h->H, h->host_const.data())) {
     e = u_tables_create(h->H, h->host_const.data(), &h->utab, h->opt.debug);
     if (e == hipSuccess) {
       h->u_mixed = true;

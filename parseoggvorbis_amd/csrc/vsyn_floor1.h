@@ -25,7 +25,8 @@ __device__ __forceinline__ uint32_t render_point_u32(uint32_t x0, uint32_t y0, u
 // (hpp:536) raises VSYN_ST_FLOOR_RANGE and is written as 0x8000 in every post (flat zero curve, all flagged: harmless).
 // The prediction render_point(xs[lo], fy[lo], xs[hi], fy[hi], xs[i]) has the post geometry folded into the per-floor constants
 // dxi = xs[i] - xs[lo] and inv = 1 / (xs[hi] - xs[lo]): off = (|dy| * dxi) / adx exactly, as floor((prod + 0.5) * inv) while
-// prod = |dy| * dxi < 2^21 (always, for in-range amplitudes: prod <= 255 * 4096), where prod + 0.5 is exact and the rounding of the
+// prod = |dy| * dxi < 2^21 (in-range amplitudes on posts up to 8192: prod <= 255 * 8191; the format allows posts up to 32767, whose
+// larger products take the integer division like absurd coded values do), where prod + 0.5 is exact and the rounding of the
 // product (<= 2.4e-7 * prod / adx) stays inside the 0.5 / adx guard band; else the integer division.
 // Floors of more than 32 posts: the row's posts live in LDS, col[post * NT] (32-bit amplitudes, the thread's own column of NT threads:
 // conflict-free, no synchronisation), and are worked on in GROUPS of four mutually independent posts (FloorConst::sched): twelve LDS

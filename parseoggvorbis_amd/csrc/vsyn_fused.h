@@ -851,7 +851,8 @@ __device__ __forceinline__ void fused_run(const FusedArgs& A, const FusedLdsImag
       // A = |dy|/adx, B = (0.5 - |dy| x0)/adx  ==  y0 +- (|dy| (x - x0)) / adx  in integers (Utils.hpp:122-137).
       // u is an odd multiple of 1/(2 adx), never an integer, so -floor(u) = floor(-u) + 1 and both directions fold into
       //   curve(x) = floor(x * A' + B'),  rising: A' = A, B' = B + y0;  falling: A' = -A, B' = y0 + 1 - B
-      // (one fma + one conversion per bin, 8-byte entries). The 0.5/adx guard band dwarfs the f32 rounding, DESIGN.md
+      // (one fma + one conversion per bin, 8-byte entries). The 0.5/adx guard band dwarfs the f32 rounding for the setups that reach
+      // this kernel: floor_closed_form_ok below states the bound, vsyn_create keeps every other setup on the staged kernels
       floor_bad = (v & 0x7FFFu) > 255u;  // a post above 255 can only render >= 256 (hpp:587)
       const float x0 = (float)(plo >> 16), y0 = fminf((float)(plo & 0xFFFFu), 255.f);
       const float x1 = (float)(phi >> 16), y1 = fminf((float)(phi & 0xFFFFu), 255.f);
@@ -1276,6 +1277,36 @@ static inline bool fused_setup_ok(const ConstHeader& H, const uint8_t* host_cons
   for (uint32_t f = 0; f < H.num_floors; ++f)
     if (fl[f].posts > 64) return false;  // one ballot covers the sorted posts
   return fused_coupling_mode(H, host_const) >= 0;
+}
+
+// Both fused kernels (this one and vsyn_fused_u.h) render the floor curve in float32, index = floor(x * A' + B') (see the set-up in the
+// long-block loop). The true argument lies 0.5 / adx or more from an integer, so the index is exact while the rounding of the
+// argument stays below that. To first order, with u = 2^-24, |dy| <= 255, x0 <= x <= xm the bins the segment renders and
+// adx = x1 - x0:   1/adx by v_rcp_f32 (1 ulp = 2 u) on both terms:  2 u (|dy| (x - x0) + 0.5) / adx
+//                  A = fl(|dy| inv):  u x |dy| / adx       B = fl(fl(0.5 - |dy| x0) inv), the fma exact (|dy| x0 < 2^23):  u |dy| x0 / adx
+//                  B' = fl(B + y0) resp. fl(y0 + 1 - B):  u (|dy| x0 / adx + 257)       the final fma, a value below 256:  128 u
+// Times adx, the sum is at most u (765 xm + 385 adx + 1), which has to stay below 0.5: 765 xm + 385 adx + 1 < 2^23.
+// Any two sorted posts can become a segment (the posts between them unflagged), so the bound is checked for every pair whose left
+// post lies inside a block that uses the floor, xm = min(x1, n/2) - 1. With x[1] = n/2, the only X lists libvorbis writes, it holds
+// for every block size (n/2 = 4096: 4.7e6); the format allows x[1] = 1 << rangebits up to 32768 whatever the block size
+// (hpp:447-450), and from adx of about 2^14 on it does not: measured on an MI355X, x[1] = 32768 with 512/4096 blocks gave index 256
+// (the 0.0 entry: a silenced bin) where the integer rule gives 255. Such a setup is kept off the fused kernels by vsyn_create
+// (vsyn_fused_paths & 3 == 0); the staged kernels' floor1_curve_at is integer.
+static inline bool floor_closed_form_ok(const ConstHeader& H, const uint8_t* host_const) {
+  const FloorConst* fl = (const FloorConst*)(host_const + H.off_floor);
+  const MapConst* mp = (const MapConst*)(host_const + H.off_map);
+  for (uint32_t k = 0; k < H.num_modes; ++k) {
+    const uint32_t n2 = H.bs[H.mode_blockflag[k] ? 1 : 0] / 2;
+    for (uint32_t c = 0; c < H.channels; ++c) {
+      const FloorConst& f = fl[mp[H.mode_mapping[k]].chfloor[c]];
+      for (uint32_t i = 0; i + 1 < f.posts && f.xs_sorted[i] < n2; ++i)
+        for (uint32_t j = i + 1; j < f.posts; ++j) {
+          const uint64_t x0 = f.xs_sorted[i], x1 = f.xs_sorted[j], xm = std::min<uint64_t>(x1, n2) - 1;
+          if (765u * xm + 385u * (x1 - x0) + 1u >= (1u << 23)) return false;
+        }
+    }
+  }
+  return true;
 }
 
 static inline uint32_t fused_ok_mask(const ConstHeader& H, const uint8_t* host_const) {

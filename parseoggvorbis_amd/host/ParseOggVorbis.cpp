@@ -1207,15 +1207,31 @@ OkOrError VorbisStream::flush(ParseCallbacks& cb) {
           push_data_u32(this, "floor1 ys", -1, y32.data(), posts);
           push_data_u32(this, "floor1 final_ys", -1, fy.data(), posts);
           push_data_bool(this, "floor1 step2_flag", -1, flag);
-          // "floor1 floor" (hpp:585): n values upstream; the device tap holds the first n/2. The rest is flat (hpp:583-584
-          // extends the last flagged post's y to the end of the vector): the y of the post at x = n/2 (header index 1) if it
-          // is flagged, else the extension began earlier and bin n/2-1 already carries it
+          // "floor1 floor" (hpp:585): n values upstream; the device tap holds the first n/2. The rest is the same integer curve
+          // (hpp:563-584) continued from the unwrapped posts: x[1] = 1 << rangebits is not tied to the block size, so flagged posts
+          // may lie in [n/2, n) and a segment may run past n (cut there, Utils.hpp:159-161); behind the last flagged post — x[1]
+          // itself is always flagged — the vector is flat. With x[1] <= n/2 that is the flat tail at post 1's y.
           {
             std::vector<uint32_t> curve(n);
             const uint16_t* crow = &fcurve[roff + (size_t)ch * n2];
             for (uint32_t i = 0; i < n2; ++i) curve[i] = crow[i];
-            const uint32_t tail = (frow[1] >> 15) ? (uint32_t)(frow[1] & 0x7fffu) : (uint32_t)crow[n2 - 1];
-            for (uint32_t i = n2; i < n; ++i) curve[i] = tail;
+            std::vector<size_t> order(posts);
+            for (size_t i = 0; i < posts; ++i) order[i] = i;
+            std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return f1.xs[a] < f1.xs[b]; });
+            uint32_t lx = 0, ly = (uint32_t)(frow[order[0]] & 0x7fffu), hx = 0, hy = 0;
+            for (size_t s = 1; s < posts; ++s) {
+              const size_t i = order[s];
+              if (!flag[i]) continue;
+              hx = f1.xs[i];
+              hy = (uint32_t)(frow[i] & 0x7fffu);
+              for (uint32_t x = std::max(lx, n2); x < hx && x < n; ++x) {  // render_point per bin == render_line's walk (Utils.hpp:122-183)
+                const uint32_t off = ((hy >= ly ? hy - ly : ly - hy) * (x - lx)) / (hx - lx);
+                curve[x] = hy >= ly ? ly + off : ly - off;
+              }
+              lx = hx;
+              ly = hy;
+            }
+            for (uint32_t x = std::max(hx, n2); x < n; ++x) curve[x] = hy;
             push_data_u32(this, "floor1 floor", -1, curve.data(), n);
             // "floor_outputs" (hpp:1171): the curve through the inverse-dB table (Vorbis I 10.1, hpp:588)
             std::vector<float> fo(n);

@@ -221,14 +221,14 @@ def test_bench_config5_full_size():
 
 @pytest.mark.parametrize("vq", ["1", "0"])
 def test_synthetic_streams_pcm_matches_reference(vq, monkeypatch):
-    """The 16 synthetic streams of tests/golden (oracle/make_synth_ogg.py: setups the real fixtures do not have, golden PCM from
+    """The 18 synthetic streams of tests/golden (oracle/make_synth_ogg.py: setups the real fixtures do not have, golden PCM from
     the reference decoder) end to end through the corpus decoder — host entropy half, device VQ stage or float residue,
     synthesis kernels (most of these shapes take the staged kernels: 3 channels, other block sizes, chained couplings).
     Frame counts equal the reference's; PCM within 4e-6 of the stream's peak (the reference's own harness allows 1e-5 at
     |pcm| <= 1, compare-debug-out.py:90; these streams peak between 0.2 and 160)."""
     monkeypatch.setenv("PARSEOGGVORBIS_VQ", vq)
     names = sorted(f[:-4] for f in os.listdir(GOLDEN) if f.startswith("synth_") and f.endswith(".ogg"))
-    assert len(names) >= 16
+    assert len(names) >= 18  # synth_16 / synth_17: floors whose x[1] is not half the block size (make_synth_ogg.py --geometry)
     names.append("winflags_bcd")  # window flags that disagree with the blocks around them (classes B, C, D)
     gold = [np.load(os.path.join(GOLDEN, n + ".npz")) for n in names]
     blobs = [open(os.path.join(GOLDEN, n + ".ogg"), "rb").read() for n in names]

@@ -415,7 +415,8 @@ def test_feature_taps_from_the_fused_kernel(pattern, C, bs0, bs1):
 # ---- the fused path at its limits (hpp:484-492 multipliers/ranges, hpp:521-589 floor decode) -----------------------------------
 def _limit_spec(C, posts_long, mult_long, mult_short, coupled, posts_short=9, seed=5):
     """256/2048 setup whose long-block floor has `posts_long` posts at random distinct x (header order shuffled, x[0] = 0 and
-    x[1] = n/2 as the format requires) and the given multipliers."""
+    x[1] = n/2 as libvorbis writes it; the format only requires a power of two, see test_gpu_floor_geometry.py) and the given
+    multipliers."""
     rng = np.random.default_rng(seed)
 
     def xs(n2, posts):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_binding as ob
+from tests import floor_geometry_cases as fg
 
 SIZES = [64, 128, 256, 512, 1024, 2048, 4096, 8192]  # every Vorbis I blocksize, hpp:1294
 CLOSED_FORM_SIZES = [64, 256, 2048]
@@ -349,20 +350,42 @@ def test_render_helpers():
     assert_ref("neighbors", np.array(nb, np.int32))
 
 
-@pytest.mark.parametrize("mult", FLOOR_MULTS)
-@pytest.mark.parametrize("posts,n", FLOOR_SHAPES)
-def test_floor1_tail_vs_reference(mult, posts, n):
+def floor1_tail(key, cases, accepted=False):
+    """orc_floor1_synth on (xs, mult, ys, n) cases against the reference's verdicts (key + "_failed") and curves (key: the inverse-dB
+    values of the accepted ones, all n of a block). accepted: every case is one that both decode."""
     orc = ob.oracle()
-    key = "floor1_%d_%d_%d" % (mult, posts, n)
     want_rc = ref_vector(key + "_failed")
+    assert len(want_rc) == len(cases), key
     decoded = []
-    for trial, (xs, ys) in enumerate(floor1_inputs(mult, posts, n)):
+    for trial, (xs, mult, ys, n) in enumerate(cases):
         got = np.zeros(n, np.float32)
-        ro = orc.orc_floor1_synth(ob.p(xs), posts, mult, ob.p(ys), n, ob.p(got), None, None, None)
-        assert bool(want_rc[trial]) == (ro != 0), (trial, ro)
+        ro = orc.orc_floor1_synth(ob.p(xs), len(xs), mult, ob.p(ys), n, ob.p(got), None, None, None)
+        assert bool(want_rc[trial]) == (ro != 0), (key, trial, ro)
+        assert not (accepted and ro), (key, trial, ro)
         if ro == 0:
             decoded.append(bits(got))
     assert_ref(key, np.concatenate(decoded) if decoded else np.zeros(0, np.uint32))
+
+
+def geometry_floor1_inputs(geom, bs0, bs1):
+    """-> (key, [(xs, mult, ys, n)]) of a geometry of floor_geometry_cases.py: X lists whose x[1] is not half the block size"""
+    return "floorgeo_%s_%d_%d" % (geom, bs0, bs1), [(c["xs"], c["mult"], c["ys"], c["n"]) for c in fg.floor_cases(geom, bs0, bs1)]
+
+
+@pytest.mark.parametrize("mult", FLOOR_MULTS)
+@pytest.mark.parametrize("posts,n", FLOOR_SHAPES)
+def test_floor1_tail_vs_reference(mult, posts, n):
+    floor1_tail("floor1_%d_%d_%d" % (mult, posts, n), [(xs, mult, ys, n) for xs, ys in floor1_inputs(mult, posts, n)])
+
+
+@pytest.mark.parametrize("bs0,bs1", fg.PAIRS)
+@pytest.mark.parametrize("geom", fg.GEOMETRIES)
+def test_floor1_tail_vs_reference_on_floor_geometries(geom, bs0, bs1):
+    """The same on X lists with x[1] above and below half the block size and on floors that both block sizes use (random_xs above
+    only draws x[1] == n / 2): the reference decodes every case, the oracle gives its curve over the whole floor vector."""
+    key, cases = geometry_floor1_inputs(geom, bs0, bs1)
+    assert not ref_vector(key + "_failed").any(), key
+    floor1_tail(key, cases, accepted=True)
 
 
 @pytest.mark.parametrize("bs0,bs1,channels", OVERLAP_CONFIGS)
