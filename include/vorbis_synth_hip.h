@@ -1372,6 +1372,71 @@ int vsyn_pcm_chain_chroma_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
                                uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out,
                                double* refs_out, vsyn_loudness_record* records_out, vsyn_status* status, const char** err);
 
+/* ---- HPSS: harmonic-percussive separation of spectral rows by median filtering, computed where the rows are ----
+ *
+ * Input: one segment's rows X[f][j], F rows (time), D columns (bins), float32: the rows of VSYN_SPEC_MEL_POWER or
+ * VSYN_SPEC_LIN_POWER. Output: a float32 matrix (F, D). This is librosa.decompose.hpss(S.T, kernel_size=(kh, kp), power=power,
+ * mask=..., margin=(margin_h, margin_p)) transposed, with scipy.ndimage.median_filter(mode="reflect") behind it. librosa is not among
+ * the test dependencies and parity with it is not claimed: the contract is the arithmetic below, the device is compared against a
+ * float64 model of it (tests/hpss_model.py), and the model against restatements in numpy's, scipy's and librosa's own words
+ * (tests/test_hpss_cpu.py).
+ *
+ *  1. Medians. H[f][j] is the median of the kh values X[f - kh/2 .. f + kh/2][j] (along time), P[f][j] the median of the kp values
+ *     X[f][j - kp/2 .. j + kp/2] (along bins); kh and kp are odd, k/2 is the integer quotient. An index outside the segment (or the
+ *     row) is reflected as numpy.pad(mode="symmetric") does it, as often as needed: i mod 2n, and if that is >= n then 2n - 1 - that.
+ *     F = 1 with kh = 63 is defined. Reflection is per segment: no value of a neighbouring segment is ever read. The median is a
+ *     selection, not arithmetic: the element of rank k/2 of the window. H and P are therefore exact: equal as values to the model's
+ *     (which of -0 and +0 comes back is not pinned). A window that holds a NaN gives NaN: sorting leaves that case undefined, so this
+ *     is the rule here. -Inf and +Inf sort as numbers.
+ *  2. Soft masks, in float64 (librosa.util.softmask). Harmonic: A = H, B = double(P) * margin_h. Percussive: A = P,
+ *     B = double(H) * margin_p. Z = max(A, B) (a NaN operand gives NaN). Z < FLT_MIN: the element is "bad" and its mask is 0.5
+ *     when both margins are 1, else 0. Otherwise, with a = (A / Z)^power and b = (B / Z)^power, the mask is a / (a + b).
+ *     power = +Inf is the hard mask A > B (1 or 0). Non-finite values go through as IEEE arithmetic and the model say.
+ *  3. Output, one of (each with one rounding to float32): the component X * mask; the mask; the median itself (H for the harmonic
+ *     component, P for the percussive one), useful on its own as a noise-floor estimate.
+ *  4. Order in the pipeline: ..., STFT and filterbank, HPSS, PCEN, delta / normalisation.
+ *  5. Checks (VSYN_ERR_INVALID before anything runs, the output untouched): kh, kp odd and in [1, 63]; component and output known;
+ *     margins finite and >= 1; power > 0, finite or +Inf; dim >= 1. Through the spectral entry points a kind other than
+ *     VSYN_SPEC_MEL_POWER or VSYN_SPEC_LIN_POWER is refused by name, and so is PCEN together with the mask or the median output.
+ *  6. Not built: even kernel sizes; the residual X - (harmonic + percussive); complex input with phase; both components from one
+ *     call; HPSS in front of the chroma kinds, whose bins never leave the FFT workgroup.
+ *
+ * Precision and order. Step 1 selects out of LDS on order-preserving integer images of the floats, so denormals are neither flushed
+ * nor reordered. Steps 2 and 3 are per element. Nothing is accumulated and no atomics are used: the result depends on neither the
+ * launch geometry nor the segment's place in the batch, the same rows give the same bits. The HPSS entry points read rows (and
+ * through the host form, PCM) only: they touch neither stream state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM.
+ * One handle's HPSS entry points share its HPSS workspace. */
+enum { VSYN_HPSS_HARMONIC = 0, VSYN_HPSS_PERCUSSIVE = 1 };                            /* vsyn_spectral_hpss.component */
+enum { VSYN_HPSS_OUT_COMPONENT = 0, VSYN_HPSS_OUT_MASK = 1, VSYN_HPSS_OUT_MEDIAN = 2 }; /* vsyn_spectral_hpss.output */
+
+typedef struct vsyn_spectral_hpss { /* 40 bytes */
+  uint32_t kh;        /* median length along time (harmonic), odd, 1 .. 63; librosa's default is 31 */
+  uint32_t kp;        /* median length along bins (percussive), odd, 1 .. 63; 31 */
+  uint32_t component; /* VSYN_HPSS_HARMONIC or VSYN_HPSS_PERCUSSIVE */
+  uint32_t output;    /* VSYN_HPSS_OUT_* */
+  double power;       /* > 0, finite or +Inf (hard mask); 2 */
+  double margin_h;    /* finite, >= 1; 1 */
+  double margin_p;    /* finite, >= 1; 1 */
+} vsyn_spectral_hpss;
+
+/* The stage alone on rows the caller has on the device (what vsyn_spectral_device wrote): d_in holds the segments' rows back to
+ * back, dim columns; seg_rows[S] is a HOST array of each segment's row count. Writes d_out, the same rows, and nothing past them.
+ * d_out may be d_in (the output then goes through the handle's HPSS workspace, grown on demand, and is copied back on the stream);
+ * any other overlap of the two is not allowed. Asynchronous on hip_stream. */
+int vsyn_spectral_hpss_device(vsyn_handle* h, const vsyn_spectral_hpss* hpss, uint32_t dim, uint32_t num_segments, const uint64_t* seg_rows,
+                              const float* d_in, float* d_out, void* hip_stream, const char** err);
+
+/* vsyn_pcm_chain_chroma_host with the HPSS stage between the spectral rows and PCEN, through the same chain body, without rows or
+ * PCM leaving the device. hpss = NULL is that entry, bit for bit. With hpss != NULL a spec->kind other than VSYN_SPEC_MEL_POWER or
+ * VSYN_SPEC_LIN_POWER, and pcen != NULL with an output other than VSYN_HPSS_OUT_COMPONENT, are VSYN_ERR_INVALID. Synchronous. */
+int vsyn_pcm_chain_hpss_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                             const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                             const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post,
+                             uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
+                             uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out,
+                             uint64_t intervals_stride, float* peaks_out, double* refs_out, vsyn_loudness_record* records_out,
+                             vsyn_status* status, const char** err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,11 @@ class SpectralPcen(C.Structure):  # vsyn_spectral_pcen
                 ("b", C.c_double), ("scale", C.c_double)]
 
 
+class SpectralHpss(C.Structure):  # vsyn_spectral_hpss
+    _fields_ = [("kh", C.c_uint32), ("kp", C.c_uint32), ("component", C.c_uint32), ("output", C.c_uint32), ("power", C.c_double),
+                ("margin_h", C.c_double), ("margin_p", C.c_double)]
+
+
 class PcmCond(C.Structure):  # vsyn_pcm_cond
     _fields_ = [("options", C.c_uint32), ("reserved", C.c_uint32), ("preemphasis", C.c_double)]
 
@@ -257,6 +262,7 @@ _SYMBOLS = [
     "vsyn_pcm_chain_host", "vsyn_pcm_chain_spectral_host",
     "vsyn_spectral_chroma_dim", "vsyn_chroma_filterbank", "vsyn_spectral_chroma_tile", "vsyn_spectral_chroma_device",
     "vsyn_pcm_chain_chroma_host",
+    "vsyn_spectral_hpss_device", "vsyn_pcm_chain_hpss_host",
 ]
 
 
@@ -395,6 +401,11 @@ def load():
                                                C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralPcen),
                                                C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp,
                                                C.POINTER(Status), cpp]
+    lib.vsyn_spectral_hpss_device.argtypes = [vp, C.POINTER(SpectralHpss), u32, u32, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_chain_hpss_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
+                                             C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralHpss),
+                                             C.POINTER(SpectralPcen), C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64,
+                                             vp, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -434,8 +445,8 @@ def _per_segment(S, *names):
     return {n: np.zeros((max(1, S),) + _PER_SEGMENT[n][1:], _PER_SEGMENT[n][0]) for n in names}
 
 
-def _post_dim(spec, post):
-    return _spec_dim(spec) * (1 + (post.order if post is not None else 0))
+def _post_dim(spec, post, chroma=None):
+    return _spec_dim(spec, chroma) * (1 + (post.order if post is not None else 0))
 
 
 class Synth:
@@ -643,6 +654,13 @@ class Synth:
         _check(self.lib.vsyn_spectral_pcen_device(self.h, _ref(pcen), dim, len(nrows), _ptr(nrows), _ptr(rates), hop_length, d_in, d_out, stream,
                                                   C.byref(err)), err)
 
+    def spectral_hpss_device(self, hpss, dim, seg_rows, d_in, d_out, stream=None):
+        """vsyn_spectral_hpss_device on device pointers (ints); seg_rows is a host sequence of each segment's row count. d_out may
+        be d_in."""
+        nrows = np.ascontiguousarray(seg_rows, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_spectral_hpss_device(self.h, _ref(hpss), dim, len(nrows), _ptr(nrows), d_in, d_out, stream, C.byref(err)), err)
+
     def pcm_trim_spectral_pcen_host(self, trim, cond, spec, pcen, post, in_rates, out_rate=0):
         """vsyn_pcm_trim_spectral_pcen_host over the last submit's segments (trim / cond / pcen / post may be None): returns what
         pcm_trim_spectral_host returns."""
@@ -797,6 +815,30 @@ class Synth:
                             (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), C.byref(spec), _ref(pcen), _ref(post), S, _ptr(rates),
                              out_rate), S, _post_dim(spec, post), [o["frames"], o["bounds"], o["counts"], iv, ivs, o["peaks"], o["refs"], rec], o)
         return dict(r, intervals=self._intervals(o["counts"], iv, S), records=rec[:S])
+
+    def _chain_rows_host(self, fn, gate, gate_is_split, loud, cond, spec, chroma, stages, post, in_rates, out_rate):
+        """The chain entries that take the chroma parameters: stages are the row stages' specs between chroma and post."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "frames", "bounds", "counts", "peaks", "refs")
+        rec = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE)
+        ivs = self._split_sizes(gate, S, rates if out_rate else None, out_rate)[1] if gate is not None and gate_is_split else 1
+        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
+        r = self._rows_host(fn, (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), C.byref(spec), _ref(chroma)) +
+                            tuple(_ref(st) for st in stages) + (_ref(post), S, _ptr(rates), out_rate), S, _post_dim(spec, post, chroma),
+                            [o["frames"], o["bounds"], o["counts"], iv, ivs, o["peaks"], o["refs"], rec], o)
+        return dict(r, intervals=self._intervals(o["counts"], iv, S), records=rec[:S])
+
+    def pcm_chain_chroma_host(self, gate, gate_is_split, loud, cond, spec, chroma, pcen, post, in_rates, out_rate=0):
+        """vsyn_pcm_chain_chroma_host over the last submit's segments (every spec but spec may be None): returns what
+        pcm_chain_spectral_host returns."""
+        return self._chain_rows_host(self.lib.vsyn_pcm_chain_chroma_host, gate, gate_is_split, loud, cond, spec, chroma, (pcen,), post, in_rates,
+                                     out_rate)
+
+    def pcm_chain_hpss_host(self, gate, gate_is_split, loud, cond, spec, chroma, hpss, pcen, post, in_rates, out_rate=0):
+        """vsyn_pcm_chain_hpss_host over the last submit's segments (every spec but spec may be None): returns what
+        pcm_chain_spectral_host returns."""
+        return self._chain_rows_host(self.lib.vsyn_pcm_chain_hpss_host, gate, gate_is_split, loud, cond, spec, chroma, (hpss, pcen), post,
+                                     in_rates, out_rate)
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

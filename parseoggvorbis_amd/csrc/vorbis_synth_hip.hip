@@ -25,6 +25,7 @@
 #include "vsyn_chroma.h"
 #include "vsyn_spectral_post.h"
 #include "vsyn_pcen.h"
+#include "vsyn_hpss.h"
 #include "vsyn_loudness.h"
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
@@ -127,6 +128,7 @@ struct vsyn_handle {
   SpectralWs sp;                       // vsyn_spectral.h
   PostWs pp;                           // vsyn_spectral_post.h
   PcenWs pc;                           // vsyn_pcen.h
+  HpssWs hp;                           // vsyn_hpss.h
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
   TrimWs tr;                           // vsyn_trim.h
@@ -1316,6 +1318,18 @@ int vsyn_spectral_pcen_device(vsyn_handle* h, const vsyn_spectral_pcen* pcen, ui
   return pcen_launch(h->pc, h->device, pcen, dim, S, seg_rows, sample_rates, hop_length, d_in, d_out, (hipStream_t)hip_stream, err);
 }
 
+int vsyn_spectral_hpss_device(vsyn_handle* h, const vsyn_spectral_hpss* hpss, uint32_t dim, uint32_t S, const uint64_t* seg_rows, const float* d_in,
+                              float* d_out, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = hpss_check_call(hpss, dim, S, seg_rows, err)) return rc;
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  if (total == 0) return VSYN_OK;
+  if (!d_in || !d_out) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return hpss_launch_any(h->hp, h->device, hpss, dim, S, seg_rows, d_in, d_out, (hipStream_t)hip_stream, err);
+}
+
 }  // extern "C"
 
 // The stages chained behind the last host submit. The PCM the next stage reads: planar [S][C][plane]; each segment's frames from d_frames, else from si.
@@ -1565,31 +1579,41 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   return VSYN_OK;
 }
 
-// The end of a spectral host form: the rows of the view's PCM on the host stream (pcen != NULL: through the PCEN stage in place;
+// The end of a spectral host form: the rows of the view's PCM on the host stream (hpss != NULL: through the HPSS stage into its
+// workspace, where the later stages find them; pcen != NULL: through the PCEN stage in place;
 // post != NULL: on to the post stage in their place, and its wider rows come back), copied to rows, then the call's wait and
 // status. seg_rows, f_max and total are the host's row counts. Caller holds h->mu.
 static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S,
                              const uint32_t* spec_rates,
                              const PcmView& v, const uint64_t* seg_rows, uint64_t f_max, uint64_t total, float* rows, vsyn_status* status,
-                             const char** err, const vsyn_spectral_chroma* chroma) {
+                             const char** err, const vsyn_spectral_chroma* chroma, const vsyn_spectral_hpss* hpss) {
   hipStream_t hs = h->host_stream;
   const uint64_t D = spec_dim(spec, chroma);
+  if (hpss)
+    if (int rc = hpss_check_call(hpss, (uint32_t)D, S, seg_rows, err)) return rc;
   HIPCHK(h->sp.rows.ensure(total * D + 1));
   int rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err,
                        chroma);
   if (rc) return rc;
+  float* cur = h->sp.rows.p;  // where the rows are
+  if (hpss) {
+    HIPCHK(h->hp.rows.ensure(total * D + 1));
+    rc = hpss_launch(h->hp, h->device, hpss, (uint32_t)D, S, seg_rows, spec_rates, cur, h->hp.rows.p, hs, err);
+    if (rc) return rc;
+    cur = h->hp.rows.p;
+  }
   if (pcen) {
-    rc = pcen_launch(h->pc, h->device, pcen, (uint32_t)D, S, seg_rows, spec_rates, spec->hop_length, h->sp.rows.p, h->sp.rows.p, hs, err);
+    rc = pcen_launch(h->pc, h->device, pcen, (uint32_t)D, S, seg_rows, spec_rates, spec->hop_length, cur, cur, hs, err);
     if (rc) return rc;
   }
   if (post) {
     const uint64_t Dout = D * (1u + post->order);
     HIPCHK(h->pp.rows.ensure(total * Dout + 1));
-    rc = post_launch(h->pp, h->device, post, (uint32_t)D, S, seg_rows, h->sp.rows.p, h->pp.rows.p, hs, err);
+    rc = post_launch(h->pp, h->device, post, (uint32_t)D, S, seg_rows, cur, h->pp.rows.p, hs, err);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(rows, h->pp.rows.p, sizeof(float) * total * Dout, hipMemcpyDeviceToHost, hs));
   } else {
-    HIPCHK(hipMemcpyAsync(rows, h->sp.rows.p, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipMemcpyAsync(rows, cur, sizeof(float) * total * D, hipMemcpyDeviceToHost, hs));
   }
   return sync_status_into(h, status, err);
 }
@@ -1602,7 +1626,8 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
                          const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
                          uint64_t* seg_rows,
                          uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err, const vsyn_loudness_spec* loud = nullptr,
-                         vsyn_loudness_record* records_out = nullptr, const vsyn_spectral_chroma* chroma = nullptr) {
+                         vsyn_loudness_record* records_out = nullptr, const vsyn_spectral_chroma* chroma = nullptr,
+                         const vsyn_spectral_hpss* hpss = nullptr) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   if (loud)  // (first: a refused loudness spec writes nothing, the status included)
     if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
@@ -1611,6 +1636,13 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
   std::vector<uint32_t> sp_rates = stage_rates(S, rates, out_rate);
   // (NULL rates without a gate are spec_check's to refuse; behind a gate they skip every segment)
   if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err, chroma)) return rc;
+  if (hpss) {
+    if (int rc = hpss_check(hpss, err)) return rc;
+    if (spec->kind != VSYN_SPEC_MEL_POWER && spec->kind != VSYN_SPEC_LIN_POWER)
+      return fail(err, VSYN_ERR_INVALID, "hpss takes the rows of mel_power or lin_power, not of kind %u", spec->kind);
+    if (pcen && hpss->output != VSYN_HPSS_OUT_COMPONENT)
+      return fail(err, VSYN_ERR_INVALID, "pcen takes the hpss component, not its %s", hpss->output == VSYN_HPSS_OUT_MASK ? "mask" : "median");
+  }
   if (pcen) {
     if (int rc = pcen_check(pcen, err)) return rc;
     if (spec->kind != VSYN_SPEC_MEL_POWER && spec->kind != VSYN_SPEC_LIN_POWER)
@@ -1679,7 +1711,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
     if (int rc = step_loudness(h, S, loud, sp_rates.data(), T.data(), t_max, false, records_out, &v, err)) return rc;
   if (cond)
     if (int rc = step_condition(h, S, cond, t_max, t_max, false, peaks_out, &v, err)) return rc;
-  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err, chroma);
+  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err, chroma, hpss);
 }
 
 // vsyn_pcm_split_intervals_host: the chain up to the split stage's marks; nothing but the frames in front of the stage, the
@@ -1989,6 +2021,24 @@ int vsyn_pcm_chain_chroma_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
                        : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
   return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
                        gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma);
+}
+
+// vsyn_pcm_chain_chroma_host with the HPSS stage: the same chain body, and the same choice of the outputs it is given.
+int vsyn_pcm_chain_hpss_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                             const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                             const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S,
+                             const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                             uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
+                             float* peaks_out, double* refs_out, vsyn_loudness_record* records_out, vsyn_status* status, const char** err) {
+  if (!hpss || !spec || !h)  // the entry without the stage (which also words the refusal of a NULL handle or spec)
+    return vsyn_pcm_chain_chroma_host(h, gate, gate_is_split, loud, cond, spec, chroma, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
+                                      frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, status,
+                                      err);
+  const bool split = gate && gate_is_split;
+  const Gate g = split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                       : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
+                       gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma, hpss);
 }
 
 // ---- pitch (vsyn_pitch.h) ----

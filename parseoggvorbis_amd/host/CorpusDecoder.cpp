@@ -643,7 +643,15 @@ struct Feeder {
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
     const vsyn_spectral_post* post = post_run(opts) ? &opts.post : nullptr;
     int rc;
-    if (opts.chroma_entry) {  // the form with every stage's spec and the chroma parameters; a NULL spec is a stage that is off
+    if (opts.hpss) {  // the chroma form with the HPSS stage in it
+      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+      rc = vsyn_pcm_chain_hpss_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
+                                    cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, &opts.hpss_spec,
+                                    opts.pcen ? &opts.pcen_spec : nullptr, post, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
+                                    g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
+                                    opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
+                                    opts.loudness_norm ? o.loud.data() : nullptr, &st, &err);
+    } else if (opts.chroma_entry) {  // the form with every stage's spec and the chroma parameters; a NULL spec is a stage that is off
       if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
       rc = vsyn_pcm_chain_chroma_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
                                       cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr, post,
@@ -1279,7 +1287,8 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
                     const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr,
                     const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr, const vsyn_pcm_trim* split = nullptr,
                     const SplitOuts* so = nullptr, const vsyn_spectral_pcen* pcen = nullptr, const vsyn_loudness_spec* loud = nullptr,
-                    vsyn_loudness_record* records_out = nullptr, bool chroma_entry = false, const vsyn_spectral_chroma* chroma = nullptr) {
+                    vsyn_loudness_record* records_out = nullptr, bool chroma_entry = false, const vsyn_spectral_chroma* chroma = nullptr,
+                    const vsyn_spectral_hpss* hpss = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
@@ -1297,6 +1306,10 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
   if (pcen) {
     opts.pcen = true;
     opts.pcen_spec = *pcen;
+  }
+  if (hpss) {
+    opts.hpss = true;
+    opts.hpss_spec = *hpss;
   }
   if (cond) {
     opts.condition = true;
@@ -1599,6 +1612,26 @@ extern "C" int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, co
   return spectral_corpus("ogg_vorbis_spectral_corpus_chroma", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
                          post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
                          split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma);
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                               uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec,
+                                               const vsyn_spectral_chroma* chroma, uint32_t target_rate, const vsyn_spectral_hpss* hpss,
+                                               const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_pcm_cond* cond,
+                                               const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, float** rows_out,
+                                               uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
+                                               uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                               const char** error_out_per_file, double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.frames_out = frames_out;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  so.begin(num_files);
+  const bool split = gate && gate_is_split;
+  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
+  return spectral_corpus("ogg_vorbis_spectral_corpus_hpss", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
+                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
+                         split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma, hpss);
 }
 
 extern "C" int ogg_vorbis_loudness_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

@@ -140,6 +140,11 @@ struct CorpusOptions {
   // without it run with the default chroma parameters through today's entry points, as every spectral entry point serves them.
   bool chroma_entry = false, chroma_given = false;
   vsyn_spectral_chroma chroma_spec = {12u, VSYN_CHROMA_NORM_MAX, VSYN_CHROMA_BASE_C, 0u, 0.0, 5.0, 2.0};
+  // hpss (a spectral run of kind mel_power or lin_power): each file's rows go through the HPSS stage on the device between the
+  // spectral rows and PCEN (include/vorbis_synth_hip.h, "HPSS"), through vsyn_pcm_chain_hpss_host. A spec the stage refuses (another
+  // kind, or PCEN on the mask or the median) is every file's error. The default is off: today's rows and today's entry points.
+  bool hpss = false;
+  vsyn_spectral_hpss hpss_spec = {31u, 31u, VSYN_HPSS_HARMONIC, VSYN_HPSS_OUT_COMPONENT, 2.0, 1.0, 1.0};
 };
 
 struct CorpusStats {
@@ -300,6 +305,16 @@ int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, const size_t*
                                       float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out,
                                       uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                       const char** error_out_per_file, double* stats_out, const char** error_out);
+// ogg_vorbis_spectral_corpus_chroma with the HPSS stage (hpss != NULL: CorpusOptions::hpss_spec = *hpss) between the spectral rows
+// and PCEN; hpss = NULL is that entry. An HPSS spec the stage refuses is every file's error. Same output contract.
+int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                                    uint32_t target_rate, const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen,
+                                    const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* gate, int gate_is_split,
+                                    const vsyn_loudness_spec* loud, float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out,
+                                    uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
+                                    vsyn_loudness_record* records_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                                    const char** error_out);
 // The intervals alone (CorpusOptions::intervals_only): decode, resample (target_rate != 0), frame energies, intervals; no PCM comes
 // back from the device. frames_out / rate_out: each file's (resampled) length and rate; intervals_out / intervals_count_out as above.
 int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

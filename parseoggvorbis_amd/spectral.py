@@ -14,7 +14,9 @@ trim_db cuts its silent head and tail in front of both ("PCM trimming"; model: t
 stretch ("PCM splitting"; model: tests/split_model.py). pcen=True turns the rows of "mel_power" or "lin_power" into librosa.pcen's
 on the device, between the spectral rows and delta / normalize ("PCEN"; model: tests/pcen_model.py). kind="chroma" / "tonnetz" give
 librosa.feature.chroma_stft's pitch-class rows and librosa.feature.tonnetz's coordinates from them ("chroma"; model:
-tests/chroma_model.py; ogg_vorbis_spectral_corpus_chroma)."""
+tests/chroma_model.py; ogg_vorbis_spectral_corpus_chroma). hpss="harmonic" / "percussive" turns the rows of "mel_power" or
+"lin_power" into librosa.decompose.hpss's component (or its mask, or the median itself) on the device, between the spectral rows and
+PCEN ("HPSS"; model: tests/hpss_model.py; ogg_vorbis_spectral_corpus_hpss)."""
 import ctypes as C
 import math
 
@@ -213,6 +215,43 @@ def pcen_spec(gain=0.98, bias=2.0, power=0.5, time_constant=0.4, eps=1e-6, b=Non
     return SpectralPcen(gain, bias, power, time_constant, eps, 0.0 if b is None else b, scale)
 
 
+HPSS_KINDS = PCEN_KINDS  # include/vorbis_synth_hip.h, "HPSS": the same two kinds
+HPSS_COMPONENTS = {"harmonic": 0, "percussive": 1}
+HPSS_OUTPUTS = {"component": 0, "mask": 1, "median": 2}
+MAX_HPSS_KERNEL = 63
+
+
+def _pair(name, v):
+    """A number, or a (harmonic, percussive) pair of them."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise SpectralError("%s must be one value or a (harmonic, percussive) pair, got %r" % (name, v))
+        return v[0], v[1]
+    return v, v
+
+
+def hpss_spec(component="harmonic", kernel_size=31, power=2.0, margin=1.0, output="component"):
+    """Checks the HPSS arguments (include/vorbis_synth_hip.h, "HPSS", step 5) and returns the C spec (binding.SpectralHpss).
+    kernel_size and margin: one value or a (harmonic, percussive) pair; kernel sizes odd and in [1, 63]; margins finite and >= 1;
+    power > 0, numpy.inf for the hard mask."""
+    from .binding import SpectralHpss
+    if not isinstance(component, str) or component not in HPSS_COMPONENTS:
+        raise SpectralError("hpss must be None, %s, got %r" % (" or ".join(repr(k) for k in HPSS_COMPONENTS), component))
+    if not isinstance(output, str) or output not in HPSS_OUTPUTS:
+        raise SpectralError("hpss_output must be %s, got %r" % (" or ".join(repr(k) for k in HPSS_OUTPUTS), output))
+    ks = [_int("hpss_kernel_size", k) for k in _pair("hpss_kernel_size", kernel_size)]
+    for k in ks:
+        if not (1 <= k <= MAX_HPSS_KERNEL and k % 2 == 1):
+            raise SpectralError("hpss_kernel_size must be odd and in [1, %d], got %r" % (MAX_HPSS_KERNEL, k))
+    ms = [_number("hpss_margin", m, True) for m in _pair("hpss_margin", margin)]
+    for m in ms:
+        if m < 1.0:
+            raise SpectralError("hpss_margin must be >= 1, got %r" % m)
+    if isinstance(power, bool) or not isinstance(power, (int, float, np.integer, np.floating)) or not float(power) > 0.0:
+        raise SpectralError("hpss_power must be a number > 0 (numpy.inf: the hard mask), got %r" % (power,))
+    return SpectralHpss(ks[0], ks[1], HPSS_COMPONENTS[component], HPSS_OUTPUTS[output], float(power), ms[0], ms[1])
+
+
 _load = _corpus.load
 
 
@@ -223,7 +262,7 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                        trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None,
                        pcen=False, pcen_gain=0.98, pcen_bias=2.0, pcen_power=0.5, pcen_time_constant=0.4, pcen_eps=1e-6, pcen_b=None,
                        pcen_scale=1.0, loudness_normalize=None, loudness=None, n_chroma=12, tuning=0.0, chroma_norm=math.inf, ctroct=5.0,
-                       octwidth=2.0, base_c=True):
+                       octwidth=2.0, base_c=True, hpss=None, hpss_kernel_size=31, hpss_power=2.0, hpss_margin=1.0, hpss_output="component"):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels for the other mel kinds. The linear kinds have no filterbank: "lin_power" is |X|^power and "lin_db" its dB image
     (amin, top_db as for "mel_db"; librosa.amplitude_to_db(|X|, amin=a) is power=2, amin=a*a), both (frames, n_fft / 2 + 1);
@@ -260,7 +299,15 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     n_chroma, tuning, ctroct, octwidth, base_c) and normalised per frame by chroma_norm (numpy.inf, 1, 2 or None); octwidth=None turns
     the octave weighting off. tuning must be a number (librosa's tuning=None estimation is not available). kind="tonnetz" gives
     librosa.feature.tonnetz(chroma=those rows): (frames, 6). A frame that holds an Inf or NaN sample is all NaN. Both take delta /
-    normalize and every PCM stage like the mel kinds, and refuse pcen. The chroma arguments are checked for every kind."""
+    normalize and every PCM stage like the mel kinds, and refuse pcen. The chroma arguments are checked for every kind.
+    hpss="harmonic" / "percussive" (kind "mel_power" or "lin_power" only; SpectralError before anything is loaded otherwise) replaces
+    the rows by that component of librosa.decompose.hpss(rows.T, kernel_size=hpss_kernel_size, power=hpss_power, margin=hpss_margin).T
+    on the device (include/vorbis_synth_hip.h, "HPSS"; model: tests/hpss_model.py), in front of pcen and delta / normalize:
+    hpss_kernel_size and hpss_margin are one value or a (harmonic, percussive) pair, the sizes odd and in [1, 63], the medians
+    reflect at a file's first and last frame and at bin 0 and the last bin. hpss_output="mask" returns the soft mask instead and
+    "median" the median-filtered rows themselves (along time for "harmonic", along bins for "percussive"); pcen takes neither of
+    those two. With hpss=None the hpss_* arguments are still checked, nothing is launched and the call takes the entry points it took
+    without them."""
     _corpus.check_errors(errors)
     from .pcm import check_sr, cond_spec, give_loudness, give_split_index, give_trim_index, loudness_args, split_spec, trim_spec
     target = check_sr(sr, SpectralError)
@@ -276,6 +323,11 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
         raise SpectralError("pcen must be True or False, got %r" % (pcen,))
     if pcen and kind not in PCEN_KINDS:
         raise SpectralError("pcen is not available for kind %r: it takes the rows of %s" % (kind, " or ".join(PCEN_KINDS)))
+    hp = hpss_spec("harmonic" if hpss is None else hpss, hpss_kernel_size, hpss_power, hpss_margin, hpss_output)
+    if hpss is not None and kind not in HPSS_KINDS:
+        raise SpectralError("hpss is not available for kind %r: it takes the rows of %s" % (kind, " or ".join(HPSS_KINDS)))
+    if hpss is not None and pcen and hpss_output != "component":
+        raise SpectralError("pcen takes the hpss component, not hpss_output=%r" % (hpss_output,))
     cond = cond_spec(peak_normalize, preemphasis, SpectralError)
     trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index, SpectralError)
     split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
@@ -283,7 +335,7 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
     is_chroma = kind in CHROMA_KINDS
-    if loud is not None or is_chroma:  # the entries with every stage's spec, the normaliser's among them (NULL: off); a chroma kind: with the chroma parameters
+    if loud is not None or is_chroma or hpss is not None:  # the entries with every stage's spec, the normaliser's among them (NULL: off); a chroma kind: with the chroma parameters
         from .binding import LOUDNESS_RECORD_DTYPE
         n = len(list_of_bytes)
         ib = _corpus.IntervalBuffers(lib, n)
@@ -291,9 +343,15 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
         records = np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
         gate = split if split is not None else trim
         try:
-            res = _corpus.run(lib, lib.ogg_vorbis_spectral_corpus_chroma if is_chroma else lib.ogg_vorbis_spectral_corpus_loud, list_of_bytes,
-                              (threads, feeders, files_per_submit, device, C.byref(spec)) + ((C.byref(chroma),) if is_chroma else ()) +
-                              (target, C.byref(pc) if pcen else None,
+            if hpss is not None:  # the chroma entry with the HPSS spec behind the rate (its kinds read no chroma parameters)
+                fn, head, mid = lib.ogg_vorbis_spectral_corpus_hpss, (None,), (C.byref(hp),)
+            elif is_chroma:
+                fn, head, mid = lib.ogg_vorbis_spectral_corpus_chroma, (C.byref(chroma),), ()
+            else:
+                fn, head, mid = lib.ogg_vorbis_spectral_corpus_loud, (), ()
+            res = _corpus.run(lib, fn, list_of_bytes,
+                              (threads, feeders, files_per_submit, device, C.byref(spec)) + head + (target,) + mid +
+                              (C.byref(pc) if pcen else None,
                                None if post is None else C.byref(post), C.byref(cond) if cond.options else None,
                                None if gate is None else C.byref(gate), int(split is not None), None if loud is None else C.byref(loud)),
                               (counts, bounds, joined, ib.ptrs, ib.counts, records),
