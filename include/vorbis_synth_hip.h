@@ -260,7 +260,8 @@ typedef struct vsyn_vq_batch {        /* host or device pointers, like the other
 
 /* Uploads the codebook value tables and residue descriptions. VSYN_ERR_INVALID (with the reason in *err) if the setup
  * is outside what the stage handles — a book with more than 65536 entries, a vector length that does not divide the
- * partition size, more than 8192 (pass, partition, channel) slots per packet; the caller then keeps feeding floats. */
+ * partition size, more than 8192 (pass, partition, channel) slots per packet, a residue vector longer than 65535 or a
+ * submap that can hold more than 65535 entry numbers in one pass; the caller then keeps feeding floats. */
 int vsyn_attach_vq(vsyn_handle* h, const vsyn_vq_setup* vq, const char** err);
 
 /* vsyn_submit_device / vsyn_submit_host with the residue given as VQ entries: `residue` becomes an OUTPUT of

@@ -42,6 +42,7 @@ static const uint32_t k_inverse_db_bits[256] = {
 struct Options {
   uint32_t run_len = 0;           // VSYN_RUN_LEN=<R>: packets per run of the fused kernels (0: fused_pick_run_len plans it)
   bool vq_no_lds_tables = false;  // VSYN_VQ_NO_LDS_TABLES=1: the residue VQ kernel keeps its value tables in global memory
+  uint32_t vq_grid = 0;           // VSYN_VQ_GRID=<n>: at most n workgroups of the residue VQ kernel (0: as many as are resident at once)
   bool debug = false;             // VSYN_DEBUG: the setup's kernel choices on stderr
 };
 
@@ -51,6 +52,8 @@ static Options options_from_env() {
   if (e && atoi(e) > 0) o.run_len = (uint32_t)atoi(e);
   e = getenv("VSYN_VQ_NO_LDS_TABLES");
   o.vq_no_lds_tables = e && atoi(e);
+  e = getenv("VSYN_VQ_GRID");
+  if (e && atoi(e) > 0) o.vq_grid = (uint32_t)atoi(e);
   o.debug = getenv("VSYN_DEBUG") != nullptr;
   return o;
 }
@@ -870,6 +873,11 @@ int vsyn_attach_vq(vsyn_handle* h, const vsyn_vq_setup* vq, const char** err) {
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vsyn_residue_vq_kernel<false>, VQ_THREADS, h->vq_lds_bytes));
     h->vq_grid = (uint32_t)h->num_cus * (uint32_t)std::max(per_cu, 1);
   }
+  if (h->opt.vq_grid) h->vq_grid = std::min(h->vq_grid, h->opt.vq_grid);
+  // the launch shape of either variant, in one form (tests read it)
+  if (h->opt.debug)
+    fprintf(stderr, "[vsyn] vq launch: %u workgroups, %u waves per workgroup, %u B LDS, tables in %s\n", h->vq_grid, h->vq_waves, h->vq_lds_bytes,
+            h->vq_tables_in_lds ? "LDS" : "global memory");
   return VSYN_OK;
 }
 

@@ -39,6 +39,11 @@
 // one scalar unit), not by memory: per-wave time grows linearly with the waves per CU. Measured and dropped in round 2: a two-stage
 // packet pipeline with double-buffered LDS, descriptors one packet ahead by vector load, several groups per lane before any store,
 // lattice books as half vectors in LDS (-DVQ_STAMPS and profiles/r02_experiments/vq_* hold the phase times and A/B runs).
+// Verified (tests/test_gpu_vq_shapes.py, residue bit for bit; DESIGN.md f-1 lists the cases): 1 to 15 channels per submap in formats
+// 0 / 1 / 2, two submaps, chained couplings, block sizes 64 to 8192, 0 partitions to 8192 slots, both store fallbacks, both table
+// homes, entry counts around VQ_ENT_CAP at every shift, 61 440 entries per pass in both halves of a scan word, and the packet walk
+// itself: with VSYN_VQ_GRID capping the grid every wave decodes a tour of packets that changes block size, residue, mapping, submap
+// count and the home of its entries from one packet to the next, with a flagged packet in between.
 #pragma once
 #include "vsyn_device.h"
 
@@ -473,8 +478,9 @@ __global__ void __launch_bounds__(TLDS ? 1024 : VQ_THREADS) vsyn_residue_vq_kern
           if ((pused >> s_chan[j]) & 1u) vused |= 1u << j;
 
       // ---- entries per slot + exclusive scan in decode order (pass, partition, vector) ----
-      // A lane takes one (partition, vector) pair and its 8 passes; two passes share a 32-bit word (a pass holds at most
-      // len <= 65535 entries: 16 bits each), so four DPP scans cover the eight per-pass prefix sums. A row of s_pp is
+      // A lane takes one (partition, vector) pair and its 8 passes; two passes share a 32-bit word (a pass of the submap holds at
+      // most 65535 entries, all its vectors together — vq_build_block refuses setups that can exceed it —: 16 bits each), so four
+      // DPP scans cover the eight per-pass prefix sums. A row of s_pp is
       // exactly the lane's four packed counts.
       uint32_t carry[4] = {0, 0, 0, 0};
       bool bad_cls = false;
@@ -671,6 +677,11 @@ static inline std::string vq_build_block(const vsyn_vq_setup* vq, const ConstHea
       const uint32_t parts = (std::min(r.end, len) - std::min(r.begin, len)) / r.psize;
       if ((uint64_t)8 * parts * vch > VQ_MAX_SLOTS) return "vq setup: more than 8192 (pass, partition, channel) slots per packet";
       if (len > 65535u) return "vq setup: residue vector longer than 65535";  // per-pass entry counts are scanned as 16-bit halves
+      // ... and a pass of formats 0 / 1 holds the entries of all vch vectors: parts * vch slots of at most psize / (shortest vector) each
+      uint32_t min_dims = r.psize;
+      for (uint32_t i = 0; i < r.nclass * 8u; ++i)
+        if (r.books[i] >= 0) min_dims = std::min(min_dims, books[r.books[i]].dims);
+      if ((uint64_t)parts * vch * (r.psize / min_dims) > 65535u) return "vq setup: more than 65535 entries in one pass of a submap";
       max_slots = std::max(max_slots, 8u * parts * vch);
     }
   }

@@ -496,10 +496,29 @@ def build_probe(tmpdir, testing=False):
     return out
 
 
-def synth_vq_packet(vq_spec, mapping, channels, n2, used_mask, rng):
-    """Random but well-formed (cls, entries) of one packet for `mapping`, in the decode order of hpp:708-760."""
+def vq_submap_shapes(vq_spec, mapping, channels, n2):
+    """-> [(vectors, partitions)] of one packet with n2 bins per channel, one pair per submap that has channels, in submap order:
+    the shape of the classification array each of them reads (format 2: one interleaved vector)."""
+    mux, sres = vq_spec.mappings[mapping]
+    out = []
+    for s in range(len(sres)):
+        nch = sum(1 for c in range(channels) if mux[c] == s)
+        if not nch:
+            continue
+        r = vq_spec.residues[sres[s]]
+        fmt2 = r["type"] == 2
+        ln = nch * n2 if fmt2 else n2
+        out.append((1 if fmt2 else nch, (min(r["end"], ln) - min(r["begin"], ln)) // r["partition_size"]))
+    return out
+
+
+def synth_vq_packet(vq_spec, mapping, channels, n2, used_mask, rng, classes=None):
+    """Random but well-formed (cls, entries) of one packet for `mapping`, in the decode order of hpp:708-760.
+    classes: chosen classifications instead of random ones, one array [vectors][partitions] (vq_submap_shapes) per submap that has
+    channels - the way to hit an exact entry count; the entry numbers stay random."""
     mux, sres = vq_spec.mappings[mapping]
     cls_all, ent_all = [], []
+    k = 0
     for s in range(len(sres)):
         chans = [c for c in range(channels) if mux[c] == s]
         if not chans:
@@ -509,7 +528,12 @@ def synth_vq_packet(vq_spec, mapping, channels, n2, used_mask, rng):
         vch = 1 if fmt2 else len(chans)
         ln = len(chans) * n2 if fmt2 else n2
         parts = (min(r["end"], ln) - min(r["begin"], ln)) // r["partition_size"]
-        cls = rng.integers(0, r["num_classifications"], (vch, parts)).astype(np.uint8)
+        if classes is None:
+            cls = rng.integers(0, r["num_classifications"], (vch, parts)).astype(np.uint8)
+        else:
+            cls = np.asarray(classes[k], np.uint8).reshape(vch, parts)
+            assert int(cls.max(initial=0)) < r["num_classifications"]
+        k += 1
         used = [True] if fmt2 else [bool((used_mask >> c) & 1) for c in chans]
         for ps in range(8):
             for pc in range(parts):
@@ -596,3 +620,104 @@ def exotic_vq_spec(variant, channels=2, bs0=256, bs1=2048, seed=9):
         maps = [(mux, [0, 1]), (mux, [0, 1])]
     # the class codebook's vector length only matters to the host's bit reader; books here always have a value table
     return VqSpec(books, res, maps)
+
+
+def build_vq_spec(channels, mux, residues, submap_residues, seed=17):
+    """A residue VQ setup from its shape, beside synthetic_vq_spec / exotic_vq_spec (whose outputs it leaves alone).
+    mux: submap of every channel - one list for every mapping, or one list per mapping.
+    residues: list of dict(type, partition_size, begin, end, dims=[vector length, ...]) with optional nclass (6), density (0.35: the
+        chance that a (class, pass) pair has a book; class 0 has none) or cascade (an int [nclass][8] array of indices into dims,
+        -1: no book, instead of a drawn one). Every residue gets books of its own, one per entry of dims.
+    submap_residues: per mapping, the residue of each submap ([[0], [0]]: both mappings share residue 0).
+    Value tables are float32 normal deviates scaled by powers of two that differ from book to book, so that every addition of the
+    accumulation rounds and a sum taken in another order, or with a pass left out, differs in its bits."""
+    from parseoggvorbis_amd.binding import VqSpec
+    rng = np.random.default_rng(seed)
+    books, res = [], []
+    for r in residues:
+        first = len(books)
+        for k, dims in enumerate(r["dims"]):
+            n = int(rng.integers(9, 140))
+            tab = (rng.standard_normal((n, dims)) * 2.0 ** (k % 5 - 1)).astype(np.float32)
+            books.append((dims, n, tab.ravel()))
+        nclass = int(r.get("nclass", 6))
+        if "cascade" in r:
+            cas = np.asarray(r["cascade"], np.int64).reshape(nclass, 8)
+        else:
+            cas = np.full((nclass, 8), -1, np.int64)
+            for c in range(1, nclass):
+                for ps in range(8):
+                    if rng.random() < r.get("density", 0.35):
+                        cas[c, ps] = int(rng.integers(0, len(r["dims"])))
+        cas = np.where(cas >= 0, cas + first, -1).astype(np.int16)
+        res.append(dict(type=r["type"], begin=r["begin"], end=r["end"], partition_size=r["partition_size"], num_classifications=nclass,
+                        classwords=2, books=cas.ravel()))
+    per_map = mux if isinstance(mux[0], (list, tuple)) else [mux] * len(submap_residues)
+    assert all(len(m) == channels for m in per_map)
+    return VqSpec(books, res, [(list(m), list(sr)) for m, sr in zip(per_map, submap_residues)])
+
+
+def propagated_used(spec, mode, own):
+    """floor_used after the coupling step has brought both channels of a pair to life where either is (hpp:1174-1180)."""
+    used = int(own)
+    for mag, ang in spec.mappings[spec.modes[mode][1]][0]:
+        if (used >> mag) & 1 or (used >> ang) & 1:
+            used |= (1 << mag) | (1 << ang)
+    return used
+
+
+def vq_pool_packet(spec, vq_spec, mode, own, rng, classes=None):
+    """One packet of mode `mode` for assemble_vq_batch: dict(long, mode, mapping, own, used, n2, cls, ent). own: the packet's
+    floor_used; classes: see synth_vq_packet."""
+    n2 = spec.blocksize_of_mode(mode) // 2
+    used = propagated_used(spec, mode, own)
+    mapping = spec.modes[mode][1]
+    cls, ent = synth_vq_packet(vq_spec, mapping, spec.channels, n2, used, rng, classes)
+    return dict(long=int(bool(spec.modes[mode][0])), mode=mode, mapping=mapping, own=int(own), used=used, n2=n2, cls=cls, ent=ent)
+
+
+def random_own_mask(rng, channels, partial=0.3):
+    """floor_used of a random packet: every channel, or (with probability `partial`) a random subset - the draw of
+    tests/test_gpu_vq.py's batches."""
+    return int(rng.integers(0, 1 << channels)) if rng.random() < partial else (1 << channels) - 1
+
+
+def assemble_vq_batch(spec, pkts, streams, ent_mod8=None, bad_mode=()):
+    """The VQ stage's batch from a list of pool packets (vq_pool_packet; the same dict may appear many times) in submit order, cut
+    into `streams` equal segments that each start a stream. Window flags agree with the block sequence.
+    ent_mod8[p]: packet p's entry_off modulo 8 (-1: wherever it falls), reached by putting entry numbers that no packet reads
+        (0xFFFF) in front of its own.
+    bad_mode: packets whose mode byte is replaced by one the setup does not have; the layout takes them for short blocks.
+    -> dict(packets, segments, vq_packets, cls, entries, res_off [P + 1] (float index of every packet's residue), plane_stride)"""
+    P = len(pkts)
+    assert P % streams == 0
+    per = P // streams
+    pk = np.zeros(P, PACKET_DTYPE)
+    from parseoggvorbis_amd.binding import VQ_PACKET_DTYPE
+    vqp = np.zeros(P, VQ_PACKET_DTYPE)
+    seg = np.zeros(streams, SEGMENT_DTYPE)
+    res_off = np.zeros(P + 1, np.int64)
+    cls_l, ent_l = [], []
+    c_off = e_off = 0
+    lng = [0 if p in bad_mode else k["long"] for p, k in enumerate(pkts)]
+    for p, k in enumerate(pkts):
+        q = p % per
+        if q == 0:
+            seg[p // per] = (p // per, p, per, VSYN_SEG_RESET, res_off[p])
+        pk[p]["mode"], pk[p]["granule"], pk[p]["floor_used"] = (len(spec.modes) + 3 if p in bad_mode else k["mode"]), -1, k["own"]
+        pk[p]["prev_long"] = lng[p - 1] if q else 1
+        pk[p]["next_long"] = lng[p + 1] if q + 1 < per else 1
+        if not lng[p]:
+            pk[p]["prev_long"] = pk[p]["next_long"] = 1
+        npad = (int(ent_mod8[p]) - e_off) % 8 if ent_mod8 is not None and ent_mod8[p] >= 0 else 0
+        if npad:
+            ent_l.append(np.full(npad, 0xFFFF, np.uint16))
+            e_off += npad
+        vqp[p] = (e_off, k["ent"].size, c_off)
+        cls_l.append(k["cls"])
+        ent_l.append(k["ent"])
+        c_off += k["cls"].size
+        e_off += k["ent"].size
+        res_off[p + 1] = res_off[p] + spec.channels * (spec.blocksize0 // 2 if p in bad_mode else k["n2"])
+    return dict(packets=pk, segments=seg, vq_packets=vqp, cls=np.concatenate(cls_l + [np.zeros(0, np.uint8)]),
+                entries=np.concatenate(ent_l + [np.zeros(0, np.uint16)]), res_off=res_off, plane_stride=per * (spec.blocksize1 // 2) + 64)

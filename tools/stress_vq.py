@@ -1,7 +1,8 @@
-"""tools/stress_vq.py [first_seed] [count] — one-off stress of the residue VQ kernel on the GPU box: random residue setups (format
-0 / 1 / 2, partition sizes that are and are not multiples of 8, vector lengths 1..16 incl. non powers of two, 1-2 submaps, begin /
-end anywhere, 2..14 classes, random cascades) with random well-formed entry streams over long and short blocks: device == oracle
-bit for bit (same helper as tests/test_gpu_vq.py)."""
+"""tools/stress_vq.py [first_seed] [count] [channels] [bs0] [bs1] — one-off stress of the residue VQ kernel on the GPU box: random
+residue setups (format 0 / 1 / 2, partition sizes that are and are not multiples of 8, vector lengths 1..16 incl. non powers of two,
+1 to 3 submaps with a random mux over the channels, begin / end anywhere, 2..14 classes, random cascades) with random well-formed
+entry streams over long and short blocks: device == oracle bit for bit (same helper as tests/test_gpu_vq.py). Default: stereo
+256/2048. Setups outside the stage's limits (slots, entries per pass) are refused by vsyn_attach_vq and skipped."""
 import os
 import sys
 
@@ -45,10 +46,14 @@ def random_spec(rng, channels=2, bs1=2048):
         return dict(type=t, begin=begin, end=end, partition_size=ps, num_classifications=nclass, classwords=int(rng.integers(1, 4)),
                     books=cascade(nclass, float(rng.uniform(0.1, 0.5))))
 
-    if rng.random() < 0.3:
+    if channels >= 2 and rng.random() < 0.3:
         res = [residue(), residue()]
         mux = [i % 2 for i in range(channels)]
         maps = [(mux, [0, 1]), (mux, [1, 0])]
+    elif channels >= 3 and rng.random() < 0.5:  # up to three submaps, channels dealt at random (a submap may stay empty)
+        nsub = int(rng.integers(2, 4))
+        res = [residue() for _ in range(nsub)]
+        maps = [([int(v) for v in rng.integers(0, nsub, channels)], [int(v) for v in rng.permutation(nsub)]) for _ in range(2)]
     else:
         res = [residue()]
         maps = [([0] * channels, [0]), ([0] * channels, [0])]
@@ -57,11 +62,14 @@ def random_spec(rng, channels=2, bs1=2048):
 
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 0
 count = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-spec = fixture_like_spec(2)
+channels = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+bs0 = int(sys.argv[4]) if len(sys.argv) > 4 else 256
+bs1 = int(sys.argv[5]) if len(sys.argv) > 5 else 2048
+spec = fixture_like_spec(channels, bs0, bs1)
 done = 0
 for seed in range(first, first + count):
     rng = np.random.default_rng(7000 + seed)
-    vqs = random_spec(rng)
+    vqs = random_spec(rng, channels, bs1)
     syn = Synth(spec, max_streams=4)
     try:
         syn.attach_vq(vqs)
@@ -69,7 +77,7 @@ for seed in range(first, first + count):
         print("seed", seed, "refused:", str(e)[:80], flush=True)
         continue
     pk, seg, vqp, cls, ent, want = _random_vq_batch(spec, vqs, 4, 10, [1, 0, 1, 1, 0], seed=seed)
-    ys = np.zeros((len(pk), 2, syn.ys_stride), np.uint16)
+    ys = np.zeros((len(pk), channels, syn.ys_stride), np.uint16)
     out = syn.submit_host_vq(pk, seg, ys, vqp, cls, ent, want.size, 10 * spec.blocksize1 // 2)
     assert out["rc"] == 0, (seed, out)
     assert np.array_equal(out["residue"].view(np.uint32), want.view(np.uint32)), seed
