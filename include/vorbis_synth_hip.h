@@ -1438,6 +1438,169 @@ int vsyn_pcm_chain_hpss_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate
                              uint64_t intervals_stride, float* peaks_out, double* refs_out, vsyn_loudness_record* records_out,
                              vsyn_status* status, const char** err);
 
+/* ---- rhythm: onset strength, onset frames, tempogram and tempo, computed where the rows are ----
+ *
+ * Three stages behind the spectral rows: librosa.onset.onset_strength (aggregate = mean), librosa.onset.onset_detect through
+ * util.peak_pick (backtrack = False), librosa.feature.tempogram (autocorrelation, window = "hann") and, on its mean,
+ * librosa.feature.tempo (aggregate = mean, log-normal prior). librosa is not among the test dependencies and parity with it is not
+ * claimed: the contract is the arithmetic below, the device is compared against a float64 model of it (tests/rhythm_model.py), and
+ * the model against restatements in numpy's and scipy's own words (tests/test_rhythm_cpu.py).
+ *
+ * A. Onset strength. Input: one segment's rows S[f][j], F rows, D columns, 1 <= D <= 256, float32 (any kind; mel_db is what
+ *    onset_strength(y, sr) feeds itself). Output: a float32 vector of exactly F entries.
+ *  1. Reference rows. R = S when max_size = 1. Otherwise R[f][j] is the maximum of S[f][k], k in [j - m/2, j - m/2 + m), m = max_size,
+ *     m/2 the integer quotient (scipy.ndimage.maximum_filter1d; even sizes are not centred). An index outside the row is reflected as
+ *     numpy.pad(mode="symmetric") does it, as often as needed. A window that holds a NaN gives NaN.
+ *  2. Envelope. p = n_fft / (2 hop_length) (integer quotient) with VSYN_ONSET_CENTER, else 0; g = f - p. env[f] = 0 when g < lag,
+ *     else (1/D) sum_j max(0, double(S[g][j]) - double(R[g - lag][j])), where max(0, NaN) is NaN (numpy.maximum) and +-Inf go through
+ *     as IEEE arithmetic says. F <= lag + p gives all zeros: the vector has F entries whatever librosa's center=False length would be.
+ *  3. Order of the sum, a function of nothing at all: 64 partial sums, partial i adding its terms j = i, i + 64, i + 128, i + 192
+ *     (those below D) in that order to 0.0, then six rounds o = 32, 16, 8, 4, 2, 1 in which partial i becomes partial i +
+ *     partial (i xor o); partial 0 is the sum. It is divided by D in float64 and rounded once to float32.
+ *  4. Checks (VSYN_ERR_INVALID before anything runs, outputs untouched): lag and max_size in [1, 64]; dim in [1, 256]; n_fft >= 1 and
+ *     hop_length >= 1; no unknown option bit.
+ *  5. Not built: aggregate = median, detrend, a caller's ref, onset_strength_multi's channels.
+ *
+ * B. Onset frames. Input: an envelope x of F float32 values per segment, that segment's sample rate. Output: the ascending list of
+ *    onset frame indices, its count, and a refusal word.
+ *  1. Window lengths in frames, per segment, on the host in double: w(t) = floor((t * rate) / hop_length); pre_max = w(pre_max
+ *     seconds), post_max = w(post_max seconds) + 1, pre_avg = w(pre_avg seconds), post_avg = w(post_avg seconds) + 1, wait = w(wait
+ *     seconds). librosa's defaults 0.03, 0.0, 0.10, 0.10, 0.03 give 1, 1, 4, 5, 1 at 22050 / 512. vsyn_onset_peak_windows returns them.
+ *  2. Normalisation (VSYN_PEAKS_NORMALIZE): u[n] = (double(x[n]) - mn) / ((mx - mn) + FLT_MIN) in float64, mn and mx the segment's
+ *     float32 minimum and maximum; otherwise u = double(x).
+ *  3. Frame n is a candidate when (a) no x[k], k in [max(0, n - pre_max), min(F, n + post_max)), is greater than x[n] (on the float32
+ *     values), and (b) u[n] >= sum / count + delta, the sum adding u[k], k in [max(0, n - pre_avg), min(F, n + post_avg)) in
+ *     ascending order to 0.0 in float64, count the number of its terms.
+ *  4. Walking n upwards, a candidate is accepted when none has been accepted yet or when n - last > wait (librosa >= 0.10.2's
+ *     clipped-window loop). No special case for a constant envelope: the rule decides.
+ *  5. A segment whose envelope holds an Inf or a NaN is refused: its word of the refusal array is 1 and its count 0.
+ *  6. Checks: the five times finite and >= 0, delta finite, hop_length >= 1, every derived window <= 4096 frames, a rate of 0 skips
+ *     the segment (count 0). At most ceil(F / (wait + 1)) frames are accepted.
+ *
+ * C. Tempogram. Input: an envelope e of F float32 values per segment. Output: float32 rows (F', W), time-major, and / or their
+ *    mean over time g[W] in float64. W = win_length when that is not 0, else floor(ac_size * rate / hop_length) per segment (344 at
+ *    22050 / 512 for librosa.feature.tempo's ac_size = 8 s), which vsyn_tempogram_win_length returns; W in [2, 2048].
+ *  1. Padding. With VSYN_TG_CENTER e is padded by w = W/2 on both sides as numpy.pad(mode="linear_ramp", end_values=0) does it:
+ *     left sample i is float(double(i) * (double(e[0]) / w)), right sample k counted from the edge outward float(double(w - 1 - k) *
+ *     (double(e[F-1]) / w)). F' = F (0 when F = 0). Without it F' = max(0, F - W + 1).
+ *  2. y_f[n] = double(win[n]) * double(e_pad[f + n]), exact in float64; win[n] = float(0.5 - 0.5 cos(2 pi n / W)) is built on the host
+ *     in double (scipy.signal.get_window("hann", W, fftbins=True)). ac[f][l] = sum_{n = 0}^{W-1-l} y_f[n] y_f[n + l], one fma chain
+ *     from 0.0 with n ascending, in float64.
+ *  3. VSYN_TG_NORM_INF divides a row by mx = max_l |ac[f][l]| (a NaN among them makes mx NaN) unless mx <= FLT_MIN; without it the
+ *     row is left as it is. Each output is rounded once to float32. Non-finite envelopes flow through as IEEE arithmetic says; with
+ *     the norm a row whose window holds a NaN is NaN.
+ *  4. Mean. g[l] = (sum over the F' rows of double(the float32 output)) / F'. With FT = vsyn_tempogram_tile(W) rows per tile, T =
+ *     ceil(F' / FT) tiles, tpb = ceil(T / 128) tiles per block: a block's rows are added in ascending order to 0.0, then the blocks'
+ *     sums in ascending order to 0.0; a function of W and F' alone. F' = 0 gives NaN.
+ *  5. Tempo, on the host in double (vsyn_tempo_from_mean): bpm[0] = +Inf, bpm[l] = 60 rate / (hop_length l); logprior[l] = -0.5
+ *     ((log2 bpm[l] - log2 start_bpm) / std_bpm)^2; with max_tempo > 0 the entries in front of the first lag whose bpm is below
+ *     max_tempo are -Inf (no lag that slow: nothing is masked, numpy.argmax of an all-false array being 0: librosa's quirk, kept).
+ *     The result is bpm[argmax_l(log1p(1e6 g[l]) + logprior[l])], the first index on a tie. A g that holds a non-finite value, or
+ *     one below -1e-6 (log1p's domain), is refused with VSYN_ERR_INVALID.
+ *  6. Checks: W in [2, 2048]; hop_length >= 1; ac_size finite and > 0 when win_length is 0; start_bpm and std_bpm finite and > 0;
+ *     max_tempo finite and >= 0 (0: no cap).
+ *  7. Not built: aggregate = None (a tempo per frame), a caller's prior, beat_track, the Fourier tempogram, other windows and norms.
+ *
+ * Order in the pipeline: ..., STFT and filterbank, HPSS, PCEN, onset strength, then peak picking or tempogram and tempo.
+ * Precision and order. No atomics; every accumulation order above is a function of the stage's parameters and the segment's row
+ * count alone, so the same rows give the same bits anywhere in a batch and under any launch geometry. The entry points read rows
+ * and envelopes only: they touch neither stream state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM. One handle's
+ * rhythm entry points share its rhythm workspace. */
+enum { VSYN_ONSET_CENTER = 1u };                          /* vsyn_onset_spec.options */
+enum { VSYN_PEAKS_NORMALIZE = 1u };                       /* vsyn_onset_peaks.options */
+enum { VSYN_TG_CENTER = 1u, VSYN_TG_NORM_INF = 2u };      /* vsyn_tempogram_spec.options */
+
+typedef struct vsyn_onset_spec { /* 20 bytes */
+  uint32_t lag;        /* 1 .. 64; librosa's default is 1 */
+  uint32_t max_size;   /* 1 .. 64; 1 */
+  uint32_t n_fft;      /* of the rows' spectral spec: only p = n_fft / (2 hop_length) is used */
+  uint32_t hop_length;
+  uint32_t options;    /* VSYN_ONSET_CENTER */
+} vsyn_onset_spec;
+
+typedef struct vsyn_onset_peaks { /* 56 bytes */
+  double pre_max, post_max, pre_avg, post_avg, wait; /* seconds; 0.03, 0.0, 0.10, 0.10, 0.03 */
+  double delta;                                      /* 0.07 */
+  uint32_t hop_length;
+  uint32_t options; /* VSYN_PEAKS_NORMALIZE */
+} vsyn_onset_peaks;
+
+typedef struct vsyn_tempogram_spec { /* 24 bytes */
+  uint32_t win_length; /* 2 .. 2048 (librosa.feature.tempogram's default is 384), or 0: from ac_size and each segment's rate */
+  uint32_t hop_length;
+  uint32_t options;    /* VSYN_TG_CENTER, VSYN_TG_NORM_INF */
+  uint32_t reserved;   /* 0 */
+  double ac_size;      /* seconds, read when win_length is 0; librosa.feature.tempo's default is 8.0 */
+} vsyn_tempogram_spec;
+
+typedef struct vsyn_tempo_spec { /* 24 bytes */
+  double start_bpm; /* 120 */
+  double std_bpm;   /* 1.0 */
+  double max_tempo; /* 320; 0: no cap */
+} vsyn_tempo_spec;
+
+/* B.1: out[0 .. 4] = pre_max, post_max, pre_avg, post_avg, wait in frames for one rate. Pure host arithmetic; VSYN_ERR_INVALID as B.6. */
+int vsyn_onset_peak_windows(const vsyn_onset_peaks* peaks, uint32_t sample_rate, uint32_t* out, const char** err);
+/* C: W for one rate (0: the spec or the rate is refused), and the rows per tile of C.4 for a W (0: W outside [2, 2048]). */
+uint32_t vsyn_tempogram_win_length(const vsyn_tempogram_spec* spec, uint32_t sample_rate);
+uint32_t vsyn_tempogram_tile(uint32_t win_length);
+/* C.5 for one segment's mean g[W]. Pure host arithmetic. lag_out may be NULL. */
+int vsyn_tempo_from_mean(const vsyn_tempo_spec* tempo, const double* g, uint32_t win_length, uint32_t sample_rate, uint32_t hop_length,
+                         double* bpm_out, uint32_t* lag_out, const char** err);
+
+/* A on rows the caller has on the device: d_rows holds the segments' rows back to back, dim columns; seg_rows[S] is a HOST array of
+ * each segment's row count. Writes d_env, one float per row, and nothing past them. Asynchronous on hip_stream. */
+int vsyn_onset_strength_device(vsyn_handle* h, const vsyn_onset_spec* onset, uint32_t dim, uint32_t num_segments, const uint64_t* seg_rows,
+                               const float* d_rows, float* d_env, void* hip_stream, const char** err);
+
+/* B on envelopes the caller has on the device, back to back; seg_rows[S] and sample_rates[S] are HOST arrays. Segment g's accepted
+ * frames go to d_onsets at the offset of its envelope (a segment never has more onsets than frames; the words behind its count are
+ * left as they are), its count to d_counts[g], its refusal word to d_refused[g] (may be NULL). Asynchronous on hip_stream. */
+int vsyn_onset_peaks_device(vsyn_handle* h, const vsyn_onset_peaks* peaks, uint32_t num_segments, const uint64_t* seg_rows,
+                            const uint32_t* sample_rates, const float* d_env, uint32_t* d_onsets, uint32_t* d_counts, uint32_t* d_refused,
+                            void* hip_stream, const char** err);
+
+/* C on envelopes the caller has on the device, back to back; seg_rows[S] and sample_rates[S] (read only when win_length is 0; may be
+ * NULL otherwise) are HOST arrays. d_rows (may be NULL): the segments' (F', W) matrices back to back. d_mean (may be NULL): the
+ * segments' g[W] back to back, float64. Both NULL is refused. A W outside [2, 2048] for any segment is VSYN_ERR_INVALID; with
+ * win_length 0 a rate of 0 skips its segment, which then has neither rows nor mean values.
+ * Asynchronous on hip_stream. */
+int vsyn_tempogram_device(vsyn_handle* h, const vsyn_tempogram_spec* spec, uint32_t num_segments, const uint64_t* seg_rows,
+                          const uint32_t* sample_rates, const float* d_env, float* d_rows, double* d_mean, void* hip_stream,
+                          const char** err);
+
+/* What a host chain returns behind the onset stage (vsyn_rhythm_spec.output), as 32-bit words in its rows buffer; seg_rows[g] counts
+ * the rows of segment g's output:
+ *   ENVELOPE    F rows of 1 column: the envelope, float32;
+ *   ONSETS      count rows of 1 column: the accepted frames, uint32 (peaks is read);
+ *   TEMPOGRAM   F' rows of win_length columns, float32 (tempogram is read; its win_length must not be 0);
+ *   TEMPO_MEAN  W + 1 rows of 2 columns, each row one float64: g[0 .. W-1], then the rate the rows were computed at (tempogram is
+ *               read; W per segment). vsyn_tempo_from_mean turns g into the tempo. A segment without frames has no rows. */
+enum { VSYN_RHYTHM_ENVELOPE = 0, VSYN_RHYTHM_ONSETS = 1, VSYN_RHYTHM_TEMPOGRAM = 2, VSYN_RHYTHM_TEMPO_MEAN = 3 };
+
+typedef struct vsyn_rhythm_spec { /* 112 bytes */
+  uint32_t output;   /* VSYN_RHYTHM_* */
+  uint32_t reserved; /* 0 */
+  vsyn_onset_spec onset; /* n_fft, hop_length and VSYN_ONSET_CENTER as the spectral spec has them */
+  vsyn_onset_peaks peaks;
+  vsyn_tempogram_spec tempogram;
+} vsyn_rhythm_spec;
+
+/* vsyn_pcm_chain_hpss_host with the rhythm stages behind pcen, through the same chain body, without rows, envelope or PCM leaving
+ * the device: the onset stage takes the place of delta / normalisation, and a post spec that is on is refused together with it, by
+ * name. rhythm = NULL is that entry, bit for bit (refused_out is then left alone). With rhythm != NULL: the kind's rows must have 1
+ * to 256 columns; rows receives the selected output as words and rows_capacity counts WORDS, not rows (F words a segment suffice
+ * for ENVELOPE and ONSETS, F win_length for TEMPOGRAM, 4098 for TEMPO_MEAN); seg_rows as above; refused_out[S] (may be NULL) is 1
+ * for a segment whose envelope holds an Inf or a NaN (ONSETS: no frames) and 2 for one whose window length falls outside [2, 2048]
+ * (TEMPO_MEAN: no rows); a rows of NULL only counts the spectral rows into seg_rows, as every chain entry does. Synchronous. */
+int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                               const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                               const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post,
+                               const vsyn_rhythm_spec* rhythm, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                               uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
+                               uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                               vsyn_loudness_record* records_out, uint32_t* refused_out, vsyn_status* status, const char** err);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,28 @@ class SpectralHpss(C.Structure):  # vsyn_spectral_hpss
                 ("margin_h", C.c_double), ("margin_p", C.c_double)]
 
 
+class OnsetSpec(C.Structure):  # vsyn_onset_spec
+    _fields_ = [("lag", C.c_uint32), ("max_size", C.c_uint32), ("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32)]
+
+
+class OnsetPeaks(C.Structure):  # vsyn_onset_peaks
+    _fields_ = [("pre_max", C.c_double), ("post_max", C.c_double), ("pre_avg", C.c_double), ("post_avg", C.c_double), ("wait", C.c_double),
+                ("delta", C.c_double), ("hop_length", C.c_uint32), ("options", C.c_uint32)]
+
+
+class TempogramSpec(C.Structure):  # vsyn_tempogram_spec
+    _fields_ = [("win_length", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32), ("reserved", C.c_uint32),
+                ("ac_size", C.c_double)]
+
+
+class RhythmSpec(C.Structure):  # vsyn_rhythm_spec
+    _fields_ = [("output", C.c_uint32), ("reserved", C.c_uint32), ("onset", OnsetSpec), ("peaks", OnsetPeaks), ("tempogram", TempogramSpec)]
+
+
+class TempoSpec(C.Structure):  # vsyn_tempo_spec
+    _fields_ = [("start_bpm", C.c_double), ("std_bpm", C.c_double), ("max_tempo", C.c_double)]
+
+
 class PcmCond(C.Structure):  # vsyn_pcm_cond
     _fields_ = [("options", C.c_uint32), ("reserved", C.c_uint32), ("preemphasis", C.c_double)]
 
@@ -263,6 +285,8 @@ _SYMBOLS = [
     "vsyn_spectral_chroma_dim", "vsyn_chroma_filterbank", "vsyn_spectral_chroma_tile", "vsyn_spectral_chroma_device",
     "vsyn_pcm_chain_chroma_host",
     "vsyn_spectral_hpss_device", "vsyn_pcm_chain_hpss_host",
+    "vsyn_onset_peak_windows", "vsyn_tempogram_win_length", "vsyn_tempogram_tile", "vsyn_tempo_from_mean",
+    "vsyn_onset_strength_device", "vsyn_onset_peaks_device", "vsyn_tempogram_device", "vsyn_pcm_chain_rhythm_host",
 ]
 
 
@@ -406,11 +430,39 @@ def load():
                                              C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralHpss),
                                              C.POINTER(SpectralPcen), C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64,
                                              vp, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_onset_peak_windows.argtypes = [C.POINTER(OnsetPeaks), u32, vp, cpp]
+    lib.vsyn_tempogram_win_length.argtypes = [C.POINTER(TempogramSpec), u32]
+    lib.vsyn_tempogram_win_length.restype = u32
+    lib.vsyn_tempogram_tile.argtypes = [u32]
+    lib.vsyn_tempogram_tile.restype = u32
+    lib.vsyn_tempo_from_mean.argtypes = [C.POINTER(TempoSpec), vp, u32, u32, u32, C.POINTER(C.c_double), C.POINTER(u32), cpp]
+    lib.vsyn_onset_strength_device.argtypes = [vp, C.POINTER(OnsetSpec), u32, u32, vp, vp, vp, vp, cpp]
+    lib.vsyn_onset_peaks_device.argtypes = [vp, C.POINTER(OnsetPeaks), u32, vp, vp, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_tempogram_device.argtypes = [vp, C.POINTER(TempogramSpec), u32, vp, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_chain_rhythm_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
+                                               C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralHpss),
+                                               C.POINTER(SpectralPcen), C.POINTER(SpectralPost), C.POINTER(RhythmSpec), u32, vp, u32, vp, u64, vp,
+                                               vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
     _lib = lib
     return lib
+
+
+def onset_peak_windows(peaks, sample_rate):
+    """vsyn_onset_peak_windows: (pre_max, post_max, pre_avg, post_avg, wait) in frames for one rate. Host arithmetic, no GPU."""
+    out, err = np.zeros(5, np.uint32), C.c_char_p()
+    _check(load().vsyn_onset_peak_windows(C.byref(peaks), sample_rate, _ptr(out), C.byref(err)), err)
+    return tuple(int(v) for v in out)
+
+
+def tempo_from_mean(tempo, g, sample_rate, hop_length):
+    """vsyn_tempo_from_mean of one mean tempogram g (float64, W values): (bpm, lag). Host arithmetic, no GPU."""
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    bpm, lag, err = C.c_double(), C.c_uint32(), C.c_char_p()
+    _check(load().vsyn_tempo_from_mean(C.byref(tempo), _ptr(g), len(g), sample_rate, hop_length, C.byref(bpm), C.byref(lag), C.byref(err)), err)
+    return bpm.value, lag.value
 
 
 class VsynError(RuntimeError):
@@ -661,6 +713,27 @@ class Synth:
         err = C.c_char_p()
         _check(self.lib.vsyn_spectral_hpss_device(self.h, _ref(hpss), dim, len(nrows), _ptr(nrows), d_in, d_out, stream, C.byref(err)), err)
 
+    def onset_strength_device(self, onset, dim, seg_rows, d_rows, d_env, stream=None):
+        """vsyn_onset_strength_device on device pointers (ints); seg_rows is a host sequence of each segment's row count."""
+        nrows = np.ascontiguousarray(seg_rows, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_onset_strength_device(self.h, _ref(onset), dim, len(nrows), _ptr(nrows), d_rows, d_env, stream, C.byref(err)), err)
+
+    def onset_peaks_device(self, peaks, seg_rows, sample_rates, d_env, d_onsets, d_counts, d_refused=None, stream=None):
+        """vsyn_onset_peaks_device on device pointers (ints); seg_rows and sample_rates are host sequences."""
+        nrows, rates = np.ascontiguousarray(seg_rows, dtype=np.uint64), _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_onset_peaks_device(self.h, _ref(peaks), len(nrows), _ptr(nrows), _ptr(rates), d_env, d_onsets, d_counts, d_refused, stream,
+                                                C.byref(err)), err)
+
+    def tempogram_device(self, spec, seg_rows, sample_rates, d_env, d_rows=None, d_mean=None, stream=None):
+        """vsyn_tempogram_device on device pointers (ints; d_rows or d_mean may be None); seg_rows and sample_rates (None: NULL) are host
+        sequences."""
+        nrows, rates = np.ascontiguousarray(seg_rows, dtype=np.uint64), _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_tempogram_device(self.h, _ref(spec), len(nrows), _ptr(nrows), _ptr(rates), d_env, d_rows, d_mean, stream, C.byref(err)),
+               err)
+
     def pcm_trim_spectral_pcen_host(self, trim, cond, spec, pcen, post, in_rates, out_rate=0):
         """vsyn_pcm_trim_spectral_pcen_host over the last submit's segments (trim / cond / pcen / post may be None): returns what
         pcm_trim_spectral_host returns."""
@@ -839,6 +912,34 @@ class Synth:
         pcm_chain_spectral_host returns."""
         return self._chain_rows_host(self.lib.vsyn_pcm_chain_hpss_host, gate, gate_is_split, loud, cond, spec, chroma, (hpss, pcen), post,
                                      in_rates, out_rate)
+
+    def pcm_chain_rhythm_host(self, gate, gate_is_split, loud, cond, spec, chroma, hpss, pcen, post, rhythm, in_rates, out_rate=0):
+        """vsyn_pcm_chain_rhythm_host over the last submit's segments (every spec but spec may be None). rhythm None: what
+        pcm_chain_hpss_host returns. Otherwise rows holds the selected output's words as float32 [rows][columns] (1 column for the
+        envelope and, to be viewed as uint32, the onsets; win_length for the tempogram; 2 for the mean's float64 values and the rate
+        behind them), seg_rows its rows per segment, and refused [S] the refusal words."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "frames", "bounds", "counts", "peaks", "refs", "refused")
+        rec = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE)
+        ivs = self._split_sizes(gate, S, rates if out_rate else None, out_rate)[1] if gate is not None and gate_is_split else 1
+        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
+        fn = self.lib.vsyn_pcm_chain_rhythm_host
+        head = (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), C.byref(spec), _ref(chroma), _ref(hpss), _ref(pcen), _ref(post),
+                _ref(rhythm), S, _ptr(rates), out_rate)
+        outs = [o["frames"], o["bounds"], o["counts"], iv, ivs, o["peaks"], o["refs"], rec, o["refused"]]
+        if rhythm is None:
+            r = self._rows_host(fn, head, S, _post_dim(spec, post, chroma), outs, o)
+        else:
+            cols = {2: rhythm.tempogram.win_length, 3: 2}.get(rhythm.output, 1)
+            seg_rows, st = np.zeros(max(1, S), np.uint64), Status()
+
+            def alloc():  # the first call counted the spectral rows: F words a segment (F win_length for the tempogram), 4098 for a mean
+                words = int(seg_rows[:S].sum()) * max(cols, 1) + 4098 * S + 1
+                return np.zeros(words, np.float32), words, outs
+            rc, buf = self._sized_call(fn, head, seg_rows, alloc, st, (VSYN_OK, VSYN_ERR_STREAM))
+            n = int(seg_rows[:S].sum())
+            r = dict(rc=rc, rows=buf[:n * cols].reshape(n, cols), seg_rows=seg_rows[:S], flags=st.flags, **{k: v[:S] for k, v in o.items()})
+        return dict(r, intervals=self._intervals(o["counts"], iv, S), records=rec[:S])
 
     def attach_vq(self, vq_spec):
         """vsyn_attach_vq: codebook value tables + residue descriptions for the device VQ stage."""

@@ -26,6 +26,7 @@
 #include "vsyn_spectral_post.h"
 #include "vsyn_pcen.h"
 #include "vsyn_hpss.h"
+#include "vsyn_rhythm.h"
 #include "vsyn_loudness.h"
 #include "vsyn_resample.h"
 #include "vsyn_condition.h"
@@ -132,6 +133,7 @@ struct vsyn_handle {
   PostWs pp;                           // vsyn_spectral_post.h
   PcenWs pc;                           // vsyn_pcen.h
   HpssWs hp;                           // vsyn_hpss.h
+  RhythmWs rh;                         // vsyn_rhythm.h
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
   TrimWs tr;                           // vsyn_trim.h
@@ -1338,6 +1340,65 @@ int vsyn_spectral_hpss_device(vsyn_handle* h, const vsyn_spectral_hpss* hpss, ui
   return hpss_launch_any(h->hp, h->device, hpss, dim, S, seg_rows, d_in, d_out, (hipStream_t)hip_stream, err);
 }
 
+int vsyn_onset_peak_windows(const vsyn_onset_peaks* peaks, uint32_t sample_rate, uint32_t* out, const char** err) {
+  if (int rc = peaks_check(peaks, err)) return rc;
+  if (!out || !sample_rate) return fail(err, VSYN_ERR_INVALID, "peaks: out is NULL or the rate is 0");
+  uint32_t w[5];
+  if (int rc = peaks_windows(peaks, sample_rate, w, err)) return rc;
+  memcpy(out, w, sizeof(w));
+  return VSYN_OK;
+}
+
+uint32_t vsyn_tempogram_win_length(const vsyn_tempogram_spec* spec, uint32_t sample_rate) {
+  if (tg_check(spec, nullptr) != VSYN_OK) return 0;
+  return tg_win_length(spec, sample_rate);
+}
+
+uint32_t vsyn_tempogram_tile(uint32_t win_length) { return win_length < TG_MIN_W || win_length > TG_MAX_W ? 0u : tg_tile(win_length); }
+
+int vsyn_tempo_from_mean(const vsyn_tempo_spec* tempo, const double* g, uint32_t win_length, uint32_t sample_rate, uint32_t hop_length,
+                         double* bpm_out, uint32_t* lag_out, const char** err) {
+  return tempo_from_mean(tempo, g, win_length, sample_rate, hop_length, bpm_out, lag_out, err);
+}
+
+int vsyn_onset_strength_device(vsyn_handle* h, const vsyn_onset_spec* onset, uint32_t dim, uint32_t S, const uint64_t* seg_rows,
+                               const float* d_rows, float* d_env, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = onset_check_call(onset, dim, S, seg_rows, err)) return rc;
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  if (total == 0) return VSYN_OK;
+  if (!d_rows || !d_env) return fail(err, VSYN_ERR_INVALID, "NULL row or envelope pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return onset_launch(h->rh, h->device, onset, dim, S, seg_rows, d_rows, d_env, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_onset_peaks_device(vsyn_handle* h, const vsyn_onset_peaks* peaks, uint32_t S, const uint64_t* seg_rows, const uint32_t* sample_rates,
+                            const float* d_env, uint32_t* d_onsets, uint32_t* d_counts, uint32_t* d_refused, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = peaks_check_call(peaks, S, seg_rows, sample_rates, err)) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_counts) return fail(err, VSYN_ERR_INVALID, "d_counts is NULL");
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  if (total && (!d_env || !d_onsets)) return fail(err, VSYN_ERR_INVALID, "NULL envelope or onset pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return peaks_launch(h->rh, h->device, peaks, S, seg_rows, sample_rates, d_env, d_onsets, d_counts, d_refused, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_tempogram_device(vsyn_handle* h, const vsyn_tempogram_spec* spec, uint32_t S, const uint64_t* seg_rows, const uint32_t* sample_rates,
+                          const float* d_env, float* d_rows, double* d_mean, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = tg_check_call(spec, S, seg_rows, sample_rates, err)) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_rows && !d_mean) return fail(err, VSYN_ERR_INVALID, "tempogram: neither rows nor mean asked for");
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  if (total && !d_env) return fail(err, VSYN_ERR_INVALID, "NULL envelope pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return tg_launch(h->rh, h->device, spec, S, seg_rows, sample_rates, d_env, d_rows, d_mean, (hipStream_t)hip_stream, err);
+}
+
 }  // extern "C"
 
 // The stages chained behind the last host submit. The PCM the next stage reads: planar [S][C][plane]; each segment's frames from d_frames, else from si.
@@ -1594,7 +1655,9 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
 static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S,
                              const uint32_t* spec_rates,
                              const PcmView& v, const uint64_t* seg_rows, uint64_t f_max, uint64_t total, float* rows, vsyn_status* status,
-                             const char** err, const vsyn_spectral_chroma* chroma, const vsyn_spectral_hpss* hpss) {
+                             const char** err, const vsyn_spectral_chroma* chroma, const vsyn_spectral_hpss* hpss,
+                             const vsyn_rhythm_spec* rhythm = nullptr, uint64_t rows_capacity = 0, uint64_t* seg_rows_out = nullptr,
+                             uint32_t* refused_out = nullptr) {
   hipStream_t hs = h->host_stream;
   const uint64_t D = spec_dim(spec, chroma);
   if (hpss)
@@ -1613,6 +1676,11 @@ static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   if (pcen) {
     rc = pcen_launch(h->pc, h->device, pcen, (uint32_t)D, S, seg_rows, spec_rates, spec->hop_length, cur, cur, hs, err);
     if (rc) return rc;
+  }
+  if (rhythm) {  // the rows stay where they are: the selected rhythm output goes to the host in their place
+    rc = rhythm_rows_out(h->rh, h->device, rhythm, (uint32_t)D, S, spec_rates, seg_rows_out, total, cur, rows, rows_capacity, refused_out, hs, err);
+    if (rc) return rc;
+    return sync_status_into(h, status, err);
   }
   if (post) {
     const uint64_t Dout = D * (1u + post->order);
@@ -1635,7 +1703,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
                          uint64_t* seg_rows,
                          uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err, const vsyn_loudness_spec* loud = nullptr,
                          vsyn_loudness_record* records_out = nullptr, const vsyn_spectral_chroma* chroma = nullptr,
-                         const vsyn_spectral_hpss* hpss = nullptr) {
+                         const vsyn_spectral_hpss* hpss = nullptr, const vsyn_rhythm_spec* rhythm = nullptr, uint32_t* refused_out = nullptr) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   if (loud)  // (first: a refused loudness spec writes nothing, the status included)
     if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
@@ -1663,6 +1731,11 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
   if (post) {
     if (int rc = spec_post_check(spec, post, err, chroma)) return rc;
     if (!post_on(post)) post = nullptr;  // off: the rows of the spectral pass, bit for bit
+  }
+  if (rhythm) {
+    if (post) return fail(err, VSYN_ERR_INVALID, "delta / normalize are not available with the rhythm stages: the onset stage takes their place");
+    if (int rc = rhythm_check(rhythm, spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, spec_dim(spec, chroma), err)) return rc;
+    if (refused_out && S) memset(refused_out, 0, sizeof(uint32_t) * S);
   }
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
@@ -1710,7 +1783,7 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
     if (int rc = post_check_rows(post, S, seg_rows, err)) return rc;
   }
   if (!rows || total == 0) return VSYN_OK;
-  if (total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (!rhythm && total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
   if (!gate && out_rate) {
     if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
     if (int rc = step_resample(h, S, rates, out_rate, t_max, false, &v, err)) return rc;
@@ -1719,7 +1792,8 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
     if (int rc = step_loudness(h, S, loud, sp_rates.data(), T.data(), t_max, false, records_out, &v, err)) return rc;
   if (cond)
     if (int rc = step_condition(h, S, cond, t_max, t_max, false, peaks_out, &v, err)) return rc;
-  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err, chroma, hpss);
+  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err, chroma, hpss, rhythm, rows_capacity,
+                           seg_rows, refused_out);
 }
 
 // vsyn_pcm_split_intervals_host: the chain up to the split stage's marks; nothing but the frames in front of the stage, the
@@ -2047,6 +2121,26 @@ int vsyn_pcm_chain_hpss_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate
                        : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
   return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
                        gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma, hpss);
+}
+
+// vsyn_pcm_chain_hpss_host with the rhythm stages behind pcen: the same chain body, and the same choice of the outputs it is given.
+int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                               const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                               const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post,
+                               const vsyn_rhythm_spec* rhythm, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                               uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
+                               uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                               vsyn_loudness_record* records_out, uint32_t* refused_out, vsyn_status* status, const char** err) {
+  if (!rhythm || !spec || !h)  // the entry without the stages (which also words the refusal of a NULL handle or spec)
+    return vsyn_pcm_chain_hpss_host(h, gate, gate_is_split, loud, cond, spec, chroma, hpss, pcen, post, S, in_rates, out_rate, rows, rows_capacity,
+                                    seg_rows, frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out,
+                                    status, err);
+  const bool split = gate && gate_is_split;
+  const Gate g = split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                       : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
+                       gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma, hpss, rhythm,
+                       refused_out);
 }
 
 // ---- pitch (vsyn_pitch.h) ----

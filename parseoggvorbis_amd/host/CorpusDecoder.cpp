@@ -84,6 +84,8 @@ bool loudness_run(const CorpusOptions& o) { return o.loudness; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
 uint32_t spectral_dim(const CorpusOptions& o) {
+  if (o.rhythm)  // the words of a row of the selected rhythm output
+    return o.rhythm_spec.output == VSYN_RHYTHM_TEMPOGRAM ? o.rhythm_spec.tempogram.win_length : o.rhythm_spec.output == VSYN_RHYTHM_TEMPO_MEAN ? 2u : 1u;
   return vsyn_spectral_chroma_dim(&o.spectral, o.chroma_entry && o.chroma_given ? &o.chroma_spec : nullptr) * (1u + o.post.order);
 }
 bool feature_needs_residue(const CorpusOptions& o) {
@@ -629,10 +631,12 @@ struct Feeder {
       rates[s] = o.err[s].empty() ? r.header.audio_sample_rate : 0;
       spec_rows += F;
     }
-    CHECK_ERR(g.rows.ensure(spec_rows * spectral_dim(opts) + 1));
+    const uint64_t rhythm_words = opts.rhythm ? spec_rows * spectral_dim(opts) + 4098u * (uint64_t)S : 0;  // (the mean: 2 (W + 1) a file)
+    CHECK_ERR(g.rows.ensure(opts.rhythm ? rhythm_words + 1 : spec_rows * spectral_dim(opts) + 1));
     CHECK_ERR(g.seg_rows.ensure(S));
     vsyn_status st;
     const char* err = nullptr;
+    std::vector<uint32_t> rhythm_refused(S, 0u);
     std::vector<float> peaks(S);
     std::vector<double> refs(S);
     if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);  // spec_rows, from the untrimmed frames, bounds the trimmed rows
@@ -643,7 +647,15 @@ struct Feeder {
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
     const vsyn_spectral_post* post = post_run(opts) ? &opts.post : nullptr;
     int rc;
-    if (opts.hpss) {  // the chroma form with the HPSS stage in it
+    if (opts.rhythm) {  // the HPSS form with the rhythm stages behind it
+      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+      rc = vsyn_pcm_chain_rhythm_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
+                                      cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, opts.hpss ? &opts.hpss_spec : nullptr,
+                                      opts.pcen ? &opts.pcen_spec : nullptr, post, &opts.rhythm_spec, S, rates.data(), opts.resample_rate, g.rows.p,
+                                      rhythm_words, g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr,
+                                      opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(),
+                                      refs.data(), opts.loudness_norm ? o.loud.data() : nullptr, rhythm_refused.data(), &st, &err);
+    } else if (opts.hpss) {  // the chroma form with the HPSS stage in it
       if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
       rc = vsyn_pcm_chain_hpss_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
                                     cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, &opts.hpss_spec,
@@ -700,6 +712,10 @@ struct Feeder {
       }
     }
     if (opts.condition) refuse_peaks(peaks, o);
+    for (uint32_t s = 0; s < S && rc == VSYN_OK; ++s)
+      if (o.err[s].empty() && rhythm_refused[s])
+        o.err[s] = rhythm_refused[s] == 1u ? "rhythm: the onset envelope holds a value that is not finite"
+                                           : "rhythm: floor(ac_size * rate / hop_length) is outside [2, 2048]";
     if (opts.loudness_norm && rc == VSYN_OK) refuse_loud(o, true, rates);
     return OkOrError();
   }
@@ -1288,7 +1304,7 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
                     const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr, const vsyn_pcm_trim* split = nullptr,
                     const SplitOuts* so = nullptr, const vsyn_spectral_pcen* pcen = nullptr, const vsyn_loudness_spec* loud = nullptr,
                     vsyn_loudness_record* records_out = nullptr, bool chroma_entry = false, const vsyn_spectral_chroma* chroma = nullptr,
-                    const vsyn_spectral_hpss* hpss = nullptr) {
+                    const vsyn_spectral_hpss* hpss = nullptr, const vsyn_rhythm_spec* rhythm = nullptr) {
   if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
   if (post && !vsyn_spectral_post_dim(spec, post))
     return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
@@ -1310,6 +1326,13 @@ int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* l
   if (hpss) {
     opts.hpss = true;
     opts.hpss_spec = *hpss;
+  }
+  if (rhythm) {
+    if (post_run(opts)) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": delta / normalize are not available with the rhythm stages", error_out);
+    if (rhythm->output > VSYN_RHYTHM_TEMPO_MEAN || (rhythm->output == VSYN_RHYTHM_TEMPOGRAM && !vsyn_tempogram_tile(rhythm->tempogram.win_length)))
+      return refuse_call((void**)rows_out, num_files, std::string(fn) + ": unknown rhythm output, or tempogram rows without a win_length in [2, 2048]", error_out);
+    opts.rhythm = true;
+    opts.rhythm_spec = *rhythm;
   }
   if (cond) {
     opts.condition = true;
@@ -1632,6 +1655,27 @@ extern "C" int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, cons
   return spectral_corpus("ogg_vorbis_spectral_corpus_hpss", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
                          post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
                          split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma, hpss);
+}
+
+extern "C" int ogg_vorbis_rhythm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                        uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                                        uint32_t target_rate, const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen,
+                                        const vsyn_spectral_post* post, const vsyn_rhythm_spec* rhythm, const vsyn_pcm_cond* cond,
+                                        const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, float** rows_out,
+                                        uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
+                                        uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                        const char** error_out_per_file, double* stats_out, const char** error_out) {
+  if (!rhythm) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_rhythm_corpus: no rhythm spec", error_out);
+  SplitOuts so;
+  so.frames_out = frames_out;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  so.begin(num_files);
+  const bool split = gate && gate_is_split;
+  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
+  return spectral_corpus("ogg_vorbis_rhythm_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate, post,
+                         rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
+                         split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma, hpss, rhythm);
 }
 
 extern "C" int ogg_vorbis_loudness_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

@@ -145,6 +145,12 @@ struct CorpusOptions {
   // kind, or PCEN on the mask or the median) is every file's error. The default is off: today's rows and today's entry points.
   bool hpss = false;
   vsyn_spectral_hpss hpss_spec = {31u, 31u, VSYN_HPSS_HARMONIC, VSYN_HPSS_OUT_COMPONENT, 2.0, 1.0, 1.0};
+  // rhythm (a spectral run of a kind with 1 to 256 columns): the rows stay on the device and go through the onset stage and what
+  // rhythm_spec.output selects behind it (include/vorbis_synth_hip.h, "rhythm"), through vsyn_pcm_chain_rhythm_host; a file's "rows"
+  // are then that output's words (1 column, win_length columns, or 2 for the mean's float64 values). A spec the stages refuse is
+  // every file's error; an envelope that is not finite, or a window length outside [2, 2048], is that file's. The default is off.
+  bool rhythm = false;
+  vsyn_rhythm_spec rhythm_spec = {};
 };
 
 struct CorpusStats {
@@ -315,6 +321,16 @@ int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, const size_t* l
                                     uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
                                     vsyn_loudness_record* records_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
                                     const char** error_out);
+// ogg_vorbis_spectral_corpus_hpss with the rhythm stages behind PCEN (CorpusOptions::rhythm_spec = *rhythm, which must not be
+// NULL), one entry for the four outputs rhythm->output selects: rows_out receives per file that output's words (see
+// vsyn_rhythm_spec in include/vorbis_synth_hip.h) and rows_count_out its rows. A post spec that is on refuses the call.
+int ogg_vorbis_rhythm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                             uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                             uint32_t target_rate, const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen,
+                             const vsyn_spectral_post* post, const vsyn_rhythm_spec* rhythm, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* gate,
+                             int gate_is_split, const vsyn_loudness_spec* loud, float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out,
+                             uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out,
+                             uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out);
 // The intervals alone (CorpusOptions::intervals_only): decode, resample (target_rate != 0), frame energies, intervals; no PCM comes
 // back from the device. frames_out / rate_out: each file's (resampled) length and rate; intervals_out / intervals_count_out as above.
 int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

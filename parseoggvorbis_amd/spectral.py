@@ -252,6 +252,52 @@ def hpss_spec(component="harmonic", kernel_size=31, power=2.0, margin=1.0, outpu
     return SpectralHpss(ks[0], ks[1], HPSS_COMPONENTS[component], HPSS_OUTPUTS[output], float(power), ms[0], ms[1])
 
 
+# the arguments of get_spectral_batch that checked_specs reads, in the order it unpacks them
+_CHECKED = ("errors", "sr", "kind", "n_fft", "hop_length", "win_length", "n_mels", "fmin", "fmax", "htk", "norm", "center",
+            "power", "log_floor", "amin", "top_db", "n_mfcc", "n_chroma", "tuning", "chroma_norm", "ctroct", "octwidth", "base_c",
+            "delta", "delta_width", "normalize", "std_floor", "pcen_gain", "pcen_bias", "pcen_power", "pcen_time_constant",
+            "pcen_eps", "pcen_b", "pcen_scale", "pcen", "hpss", "hpss_kernel_size", "hpss_power", "hpss_margin", "hpss_output",
+            "peak_normalize", "preemphasis", "trim_db", "trim_frame_length", "trim_hop_length", "trim_index", "split_db",
+            "split_frame_length", "split_hop_length", "split_index", "loudness_normalize", "loudness")
+
+
+def checked_specs(a):
+    """Every check of get_spectral_batch's arguments, a being the dict of them (its locals()), before anything is loaded: the C specs of
+    the stages and the width of the rows. Shared with rhythm.py, whose entries forward the same arguments."""
+    from types import SimpleNamespace
+    (errors, sr, kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
+     n_mfcc, n_chroma, tuning, chroma_norm, ctroct, octwidth, base_c, delta, delta_width, normalize, std_floor, pcen_gain,
+     pcen_bias, pcen_power, pcen_time_constant, pcen_eps, pcen_b, pcen_scale, pcen, hpss, hpss_kernel_size, hpss_power,
+     hpss_margin, hpss_output, peak_normalize, preemphasis, trim_db, trim_frame_length, trim_hop_length, trim_index, split_db,
+     split_frame_length, split_hop_length, split_index, loudness_normalize, loudness) = (a[k] for k in _CHECKED)
+    _corpus.check_errors(errors)
+    from .pcm import check_sr, cond_spec, loudness_args, split_spec, trim_spec
+    target = check_sr(sr, SpectralError)
+    spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
+                         n_mfcc)
+    chroma = chroma_spec(n_chroma, tuning, chroma_norm, ctroct, octwidth, base_c)
+    post, dim, keep = post_spec(spec_dim(spec, chroma), delta, delta_width, normalize, std_floor)
+    if post is not None and spec.kind in LINEAR_KINDS:
+        raise SpectralError("delta / normalize are not available for the linear kind %r (rows of %d columns; the post stage holds 256)"
+                            % (kind, dim))
+    pc = pcen_spec(pcen_gain, pcen_bias, pcen_power, pcen_time_constant, pcen_eps, pcen_b, pcen_scale)
+    if not isinstance(pcen, (bool, np.bool_)):
+        raise SpectralError("pcen must be True or False, got %r" % (pcen,))
+    if pcen and kind not in PCEN_KINDS:
+        raise SpectralError("pcen is not available for kind %r: it takes the rows of %s" % (kind, " or ".join(PCEN_KINDS)))
+    hp = hpss_spec("harmonic" if hpss is None else hpss, hpss_kernel_size, hpss_power, hpss_margin, hpss_output)
+    if hpss is not None and kind not in HPSS_KINDS:
+        raise SpectralError("hpss is not available for kind %r: it takes the rows of %s" % (kind, " or ".join(HPSS_KINDS)))
+    if hpss is not None and pcen and hpss_output != "component":
+        raise SpectralError("pcen takes the hpss component, not hpss_output=%r" % (hpss_output,))
+    cond = cond_spec(peak_normalize, preemphasis, SpectralError)
+    trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index, SpectralError)
+    split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
+    loud = loudness_args(loudness_normalize, loudness, cond, SpectralError)
+    return SimpleNamespace(target=target, spec=spec, chroma=chroma, post=post, dim=dim, keep=keep, pc=pc, hp=hp, cond=cond, trim=trim, split=split,
+                           loud=loud)
+
+
 _load = _corpus.load
 
 
@@ -308,30 +354,10 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     "median" the median-filtered rows themselves (along time for "harmonic", along bins for "percussive"); pcen takes neither of
     those two. With hpss=None the hpss_* arguments are still checked, nothing is launched and the call takes the entry points it took
     without them."""
-    _corpus.check_errors(errors)
-    from .pcm import check_sr, cond_spec, give_loudness, give_split_index, give_trim_index, loudness_args, split_spec, trim_spec
-    target = check_sr(sr, SpectralError)
-    spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
-                         n_mfcc)
-    chroma = chroma_spec(n_chroma, tuning, chroma_norm, ctroct, octwidth, base_c)
-    post, dim, keep = post_spec(spec_dim(spec, chroma), delta, delta_width, normalize, std_floor)
-    if post is not None and spec.kind in LINEAR_KINDS:
-        raise SpectralError("delta / normalize are not available for the linear kind %r (rows of %d columns; the post stage holds 256)"
-                            % (kind, dim))
-    pc = pcen_spec(pcen_gain, pcen_bias, pcen_power, pcen_time_constant, pcen_eps, pcen_b, pcen_scale)
-    if not isinstance(pcen, (bool, np.bool_)):
-        raise SpectralError("pcen must be True or False, got %r" % (pcen,))
-    if pcen and kind not in PCEN_KINDS:
-        raise SpectralError("pcen is not available for kind %r: it takes the rows of %s" % (kind, " or ".join(PCEN_KINDS)))
-    hp = hpss_spec("harmonic" if hpss is None else hpss, hpss_kernel_size, hpss_power, hpss_margin, hpss_output)
-    if hpss is not None and kind not in HPSS_KINDS:
-        raise SpectralError("hpss is not available for kind %r: it takes the rows of %s" % (kind, " or ".join(HPSS_KINDS)))
-    if hpss is not None and pcen and hpss_output != "component":
-        raise SpectralError("pcen takes the hpss component, not hpss_output=%r" % (hpss_output,))
-    cond = cond_spec(peak_normalize, preemphasis, SpectralError)
-    trim = trim_spec(trim_db, trim_frame_length, trim_hop_length, trim_index, SpectralError)
-    split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
-    loud = loudness_args(loudness_normalize, loudness, cond, SpectralError)
+    from .pcm import give_loudness, give_split_index, give_trim_index
+    c = checked_specs(dict(locals()))
+    target, spec, chroma, post, dim, pc, hp = c.target, c.spec, c.chroma, c.post, c.dim, c.pc, c.hp
+    cond, trim, split, loud = c.cond, c.trim, c.split, c.loud
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
     is_chroma = kind in CHROMA_KINDS
