@@ -1399,8 +1399,9 @@ int vsyn_pcm_chain_chroma_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
  *  5. Checks (VSYN_ERR_INVALID before anything runs, the output untouched): kh, kp odd and in [1, 63]; component and output known;
  *     margins finite and >= 1; power > 0, finite or +Inf; dim >= 1. Through the spectral entry points a kind other than
  *     VSYN_SPEC_MEL_POWER or VSYN_SPEC_LIN_POWER is refused by name, and so is PCEN together with the mask or the median output.
- *  6. Not built: even kernel sizes; the residual X - (harmonic + percussive); complex input with phase; both components from one
- *     call; HPSS in front of the chroma kinds, whose bins never leave the FFT workgroup.
+ *  6. Not built: even kernel sizes; the residual X - (harmonic + percussive); complex components as rows (the mask output applied
+ *     to complex bins is the "inverse STFT" stage's mask argument, and "PCM effects" returns the component as PCM); both components
+ *     from one call; HPSS in front of the chroma kinds, whose bins never leave the FFT workgroup.
  *
  * Precision and order. Step 1 selects out of LDS on order-preserving integer images of the floats, so denormals are neither flushed
  * nor reordered. Steps 2 and 3 are per element. Nothing is accumulated and no atomics are used: the result depends on neither the
@@ -1600,6 +1601,104 @@ int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
                                uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
                                uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                vsyn_loudness_record* records_out, uint32_t* refused_out, vsyn_status* status, const char** err);
+
+/* ---- inverse STFT: complex rows, with or without a real mask on them, back to PCM, computed where the rows are ----
+ *
+ * Input: one segment's rows X[f][k], F rows (time) of n_fft / 2 + 1 complex64 bins, the layout VSYN_SPEC_STFT writes; optionally a
+ * float32 mask m[f][k] of the same shape, the layout of VSYN_HPSS_OUT_MASK on VSYN_SPEC_LIN_POWER rows. Output: `length` float32
+ * samples. This is librosa.istft(X.T, hop_length=hop_length, win_length=win_length, n_fft=n_fft, window="hann", center=..., length=
+ * length) of m * X. librosa is not among the test dependencies and parity with it is not claimed: the contract is the arithmetic
+ * below, the device is compared against a float64 model of it (tests/istft_model.py), and the model against torch.istft and a direct
+ * inverse DFT (tests/test_istft_cpu.py).
+ *
+ *  1. Y[f][k] = m[f][k] * X[f][k], one float32 product per component; Y = X without a mask.
+ *  2. x_f = irfft(Y_f, n_fft), the 1 / n_fft included; the imaginary parts of bins 0 and n_fft / 2 are not read, as numpy does not
+ *     read them. In float32: with M = n_fft / 2, a = Y[k], b = Y[M - k] and (c, s) = (cos, sin)(2 pi k / n_fft) rounded to float32,
+ *     Z[k] = (er - (c di + s dr), ei + (c dr - s di)), er = a.re + b.re, ei = a.im - b.im, dr = a.re - b.re, di = a.im + b.im, for
+ *     k < M; then log2 M radix-2 Stockham passes over Z (butterfly j of pass Ns: a = in[j], b = in[j + M/2], t = (c b.re - s b.im,
+ *     c b.im + s b.re) with (c, s) of angle 2 pi (j mod Ns) / (2 Ns), out[j0] = a + t, out[j0 + Ns] = a - t, j0 = 2 (j - j mod Ns) +
+ *     j mod Ns), the forward kernel's passes with conjugated twiddles; z[m] then holds n_fft x_f[2m] and n_fft x_f[2m + 1], and each
+ *     is multiplied by 1 / n_fft (exact). Plain products and sums in the order written; nothing is contracted.
+ *  3. v_f[j] = w[j] * x_f[j] on the window's support, one float32 product; w is the forward table's window (periodic Hann of
+ *     win_length, built in double, rounded to float32, centred in n_fft). Outside the support a frame contributes nothing.
+ *  4. y[t] = (sum_f v_f[t + pad - f hop_length]) / W[t], W[t] = sum_f w[t + pad - f hop_length]^2, pad = n_fft / 2 with
+ *     VSYN_SPEC_CENTER, else 0, both over the frames whose window support holds t. Both sums are float64, from 0.0, in ascending f
+ *     (their terms: the float32 v, and the exact float64 square of the float32 w); the quotient is float64 and is rounded once to
+ *     float32. Where W[t] <= FLT_MIN the sum is left undivided (librosa's `tiny` rule). A sample that no frame covers is 0. `length`
+ *     shorter than what the frames cover cuts the signal, a longer one appends zeros.
+ *  5. Non-finite values. A NaN or an Inf in bin k of row f (the imaginary parts of bins 0 and n_fft / 2 excepted: they are not
+ *     read), or in its mask, makes every x_f[j] non-finite and with it exactly the samples under frame f's window support, w[j] = 0
+ *     included. Every other sample, segment, length word and byte behind a segment's length keeps its bits.
+ *  6. Checks (VSYN_ERR_INVALID before anything runs, the outputs untouched): the spec's n_fft, hop_length and win_length as the
+ *     spectral entry points check them (the spec's other fields but VSYN_SPEC_CENTER are not read); n_fft a power of two, any other
+ *     refused by name; NULL seg_rows, rows or output; a length above out_plane_stride; out_plane_stride >= 2^32.
+ *  7. Not built: the inverse of the direct-DFT path (an n_fft that is no power of two); other windows; a fused single kernel in
+ *     which a workgroup owns an output span and recomputes its edge frames; phase-vocoder time stretch, Griffin-Lim and spectral
+ *     gating, each of which is one kernel on top of this stage.
+ *
+ * Precision and order. Every frame's arithmetic is its own: nothing of one frame enters another's transform, and step 4 adds in
+ * ascending f whatever the grid. No atomics: the result depends on neither the launch geometry nor the segment's place in the batch,
+ * the same rows give the same bits. The entry points read rows and mask only: they touch neither stream state, the overlap buffers
+ * nor the PCM kept by VSYN_SUBMIT_KEEP_PCM. One handle's inverse-STFT entry points share its frame workspace (rows * n_fft floats,
+ * grown on demand). */
+
+/* Samples that `rows` rows cover: hop_length (rows - 1), plus n_fft without VSYN_SPEC_CENTER; 0 for no rows or a refused spec. */
+uint64_t vsyn_istft_num_samples(const vsyn_spectral_spec* spec, uint64_t rows);
+
+/* The stage on rows the caller has on the device: d_rows holds the segments' rows back to back, n_fft / 2 + 1 complex64 bins each
+ * (8-byte aligned); d_mask (may be NULL) the masks in the same order, one float32 per bin; seg_rows[S] is a HOST array of each
+ * segment's row count, lengths[S] a HOST array of each segment's output length (NULL: vsyn_istft_num_samples of its rows). Segment
+ * g's samples go to d_pcm_out + g * out_plane_stride, exactly lengths[g] of them and nothing behind them; d_out_frames[g] (may be
+ * NULL) receives lengths[g]. Asynchronous on hip_stream. */
+int vsyn_istft_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t num_segments, const uint64_t* seg_rows, const float* d_rows,
+                      const float* d_mask, const uint64_t* lengths, float* d_pcm_out, uint64_t out_plane_stride, uint32_t* d_out_frames,
+                      void* hip_stream, const char** err);
+
+/* ---- PCM effects: the harmonic or the percussive component of the decoded PCM as PCM, computed where the PCM is ----
+ *
+ * librosa.effects.harmonic(y) / percussive(y) for one segment: y_c = istft(m_c * stft(y)), m_c the soft mask of
+ * librosa.decompose.hpss on |stft(y)|. Parity with librosa is not claimed; the contract is the composition below, of stages whose
+ * arithmetic their own sections pin, and the stage equals that composition through the public device entry points bit for bit
+ * (tests/test_gpu_pcm_effects.py).
+ *
+ *  1. S = the VSYN_SPEC_LIN_POWER rows, power 1, of the segment's mono downmix ("linear spectra"), with n_fft, hop_length, win_length
+ *     of the effect and always centred: 1 + T / hop_length rows for T > 0 samples.
+ *  2. m = the VSYN_HPSS_OUT_MASK output of the HPSS stage on S ("HPSS") under effect->hpss (its kernel sizes, component, power and
+ *     margins).
+ *  3. y_c = the inverse STFT ("inverse STFT") of X = the VSYN_SPEC_STFT rows of the same signal, under the mask m, centred, to
+ *     length T. X is computed in the workgroup that inverts it and is never stored; its bits are those VSYN_SPEC_STFT stores.
+ *  4. Order in the pipeline: resampler, trim / split, this stage, loudness, peak normalisation and pre-emphasis: those act on the
+ *     component, as they would on librosa.effects.harmonic(y). Output: a mono signal of the same frame count.
+ *  5. Non-finite samples flow through as the three stages' rules say: a NaN or an Inf sample makes the frames that hold it non-finite,
+ *     a NaN in S makes the masks of its median windows NaN, and those make the samples under their frames' supports non-finite.
+ *  6. Checks (VSYN_ERR_INVALID before anything runs, outputs untouched): n_fft a power of two in [16, 8192], any other refused by
+ *     name; hop_length >= 1; win_length in [1, n_fft]; the hpss spec as the HPSS stage checks it, and its output must be
+ *     VSYN_HPSS_OUT_COMPONENT: the mask and the median are not signals.
+ *  7. Not built: the effect in front of the spectral, pitch, descriptor and loudness row entries (the steps are shared, so this is
+ *     the natural follow-up); both components from one call; the residual; time stretch and pitch shift.
+ * The entry points read PCM only, and share the handle's spectral, HPSS and inverse-STFT workspaces with those stages' entries. */
+typedef struct vsyn_pcm_effect { /* 56 bytes */
+  uint32_t n_fft;      /* a power of two in [16, 8192]; librosa's default is 2048 */
+  uint32_t hop_length; /* >= 1; n_fft / 4 */
+  uint32_t win_length; /* 1 .. n_fft; n_fft */
+  uint32_t reserved;   /* 0 */
+  vsyn_spectral_hpss hpss; /* output must be VSYN_HPSS_OUT_COMPONENT */
+} vsyn_pcm_effect;
+
+/* The stage alone on PCM the caller has on the device: d_pcm planar [S][channels][plane_stride] float32, frames[S] a HOST array of
+ * each segment's frame count (at most both strides). Segment g's component goes to d_pcm_out + g * out_plane_stride, exactly
+ * frames[g] samples and nothing behind them; d_out_frames[g] (may be NULL) receives frames[g]. Asynchronous on hip_stream. */
+int vsyn_pcm_hpss_device(vsyn_handle* h, const vsyn_pcm_effect* effect, uint32_t num_segments, const uint64_t* frames, const float* d_pcm,
+                         uint64_t plane_stride, uint32_t channels, float* d_pcm_out, uint64_t out_plane_stride, uint32_t* d_out_frames,
+                         void* hip_stream, const char** err);
+
+/* vsyn_pcm_chain_host with the effect between the gate and the loudness step, through the same chain body, without PCM or rows
+ * leaving the device: out receives ONE plane per segment. effect = NULL is that entry, bit for bit. Synchronous. */
+int vsyn_pcm_chain_effects_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
+                                const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t num_segments, const uint32_t* in_rates,
+                                uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
+                                uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                vsyn_loudness_record* records_out, const char** err);
 
 #ifdef __cplusplus
 }

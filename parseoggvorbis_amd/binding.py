@@ -94,6 +94,10 @@ class SpectralHpss(C.Structure):  # vsyn_spectral_hpss
                 ("margin_h", C.c_double), ("margin_p", C.c_double)]
 
 
+class PcmEffect(C.Structure):  # vsyn_pcm_effect
+    _fields_ = [("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("win_length", C.c_uint32), ("reserved", C.c_uint32), ("hpss", SpectralHpss)]
+
+
 class OnsetSpec(C.Structure):  # vsyn_onset_spec
     _fields_ = [("lag", C.c_uint32), ("max_size", C.c_uint32), ("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32)]
 
@@ -287,6 +291,7 @@ _SYMBOLS = [
     "vsyn_spectral_hpss_device", "vsyn_pcm_chain_hpss_host",
     "vsyn_onset_peak_windows", "vsyn_tempogram_win_length", "vsyn_tempogram_tile", "vsyn_tempo_from_mean",
     "vsyn_onset_strength_device", "vsyn_onset_peaks_device", "vsyn_tempogram_device", "vsyn_pcm_chain_rhythm_host",
+    "vsyn_istft_num_samples", "vsyn_istft_device", "vsyn_pcm_hpss_device", "vsyn_pcm_chain_effects_host",
 ]
 
 
@@ -426,6 +431,12 @@ def load():
                                                C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp,
                                                C.POINTER(Status), cpp]
     lib.vsyn_spectral_hpss_device.argtypes = [vp, C.POINTER(SpectralHpss), u32, u32, vp, vp, vp, vp, cpp]
+    lib.vsyn_istft_num_samples.argtypes = [C.POINTER(SpectralSpec), u64]
+    lib.vsyn_istft_num_samples.restype = u64
+    lib.vsyn_istft_device.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, vp, vp, vp, u64, vp, vp, cpp]
+    lib.vsyn_pcm_hpss_device.argtypes = [vp, C.POINTER(PcmEffect), u32, vp, vp, u64, u32, vp, u64, vp, vp, cpp]
+    lib.vsyn_pcm_chain_effects_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(PcmEffect), C.POINTER(LoudnessSpec), C.POINTER(PcmCond), u32,
+                                                vp, u32, C.c_int, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, cpp]
     lib.vsyn_pcm_chain_hpss_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
                                              C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralHpss),
                                              C.POINTER(SpectralPcen), C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64,
@@ -713,6 +724,23 @@ class Synth:
         err = C.c_char_p()
         _check(self.lib.vsyn_spectral_hpss_device(self.h, _ref(hpss), dim, len(nrows), _ptr(nrows), d_in, d_out, stream, C.byref(err)), err)
 
+    def istft_device(self, spec, seg_rows, d_rows, d_mask, lengths, d_pcm_out, out_plane_stride, d_out_frames=None, stream=None):
+        """vsyn_istft_device on device pointers (ints; d_mask and d_out_frames may be None); seg_rows and lengths (None: what each
+        segment's rows cover) are host sequences."""
+        nrows = np.ascontiguousarray(seg_rows, dtype=np.uint64)
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_istft_device(self.h, _ref(spec), len(nrows), _ptr(nrows), d_rows, d_mask, _ptr(lens), d_pcm_out, out_plane_stride,
+                                          d_out_frames, stream, C.byref(err)), err)
+
+    def pcm_hpss_device(self, effect, frames, d_pcm, plane_stride, channels, d_pcm_out, out_plane_stride, d_out_frames=None, stream=None):
+        """vsyn_pcm_hpss_device on device pointers (ints; d_out_frames may be None); frames is a host sequence of each segment's frame
+        count."""
+        fr = np.ascontiguousarray(frames, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_pcm_hpss_device(self.h, _ref(effect), len(fr), _ptr(fr), d_pcm, plane_stride, channels, d_pcm_out, out_plane_stride,
+                                             d_out_frames, stream, C.byref(err)), err)
+
     def onset_strength_device(self, onset, dim, seg_rows, d_rows, d_env, stream=None):
         """vsyn_onset_strength_device on device pointers (ints); seg_rows is a host sequence of each segment's row count."""
         nrows = np.ascontiguousarray(seg_rows, dtype=np.uint64)
@@ -874,6 +902,21 @@ class Synth:
             return [o["bounds"], o["counts"], iv[0], ivs, o["peaks"], o["refs"], rec]
         out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_host,
                                      (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), S, _ptr(rates), out_rate, fmt), S, fmt, None, outs)
+        return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
+
+    def pcm_chain_effects_host(self, gate, gate_is_split, effect, loud, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_chain_effects_host over the last submit's segments (every spec may be None, but not all four): returns what
+        pcm_chain_host returns."""
+        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "bounds", "counts", "peaks", "refs")
+        rec, iv = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), []
+
+        def outs(t_max):
+            ivs = self._max_intervals(gate, t_max) if gate is not None and gate_is_split else 1
+            iv.append(np.zeros((max(1, S), ivs, 2), np.uint32))
+            return [o["bounds"], o["counts"], iv[0], ivs, o["peaks"], o["refs"], rec]
+        out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_effects_host,
+                                     (_ref(gate), 1 if gate_is_split else 0, _ref(effect), _ref(loud), _ref(cond), S, _ptr(rates), out_rate, fmt), S,
+                                     fmt, None, outs)
         return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
 
     def pcm_chain_spectral_host(self, gate, gate_is_split, loud, cond, spec, pcen, post, in_rates, out_rate=0):

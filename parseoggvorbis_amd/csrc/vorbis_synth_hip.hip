@@ -26,6 +26,8 @@
 #include "vsyn_spectral_post.h"
 #include "vsyn_pcen.h"
 #include "vsyn_hpss.h"
+#include "vsyn_istft.h"
+#include "vsyn_effects.h"
 #include "vsyn_rhythm.h"
 #include "vsyn_loudness.h"
 #include "vsyn_resample.h"
@@ -133,6 +135,8 @@ struct vsyn_handle {
   PostWs pp;                           // vsyn_spectral_post.h
   PcenWs pc;                           // vsyn_pcen.h
   HpssWs hp;                           // vsyn_hpss.h
+  IstftWs is;                          // vsyn_istft.h
+  EffectWs ef;                         // vsyn_effects.h
   RhythmWs rh;                         // vsyn_rhythm.h
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
@@ -1340,6 +1344,37 @@ int vsyn_spectral_hpss_device(vsyn_handle* h, const vsyn_spectral_hpss* hpss, ui
   return hpss_launch_any(h->hp, h->device, hpss, dim, S, seg_rows, d_in, d_out, (hipStream_t)hip_stream, err);
 }
 
+uint64_t vsyn_istft_num_samples(const vsyn_spectral_spec* spec, uint64_t rows) {
+  if (istft_check(spec, nullptr) != VSYN_OK) return 0;
+  return istft_num_samples(spec, rows);
+}
+
+int vsyn_istft_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint64_t* seg_rows, const float* d_rows, const float* d_mask,
+                      const uint64_t* lengths, float* d_pcm_out, uint64_t out_plane_stride, uint32_t* d_out_frames, void* hip_stream,
+                      const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  std::vector<uint64_t> len;
+  uint64_t total, f_max, len_max;
+  if (int rc = istft_check_call(spec, S, seg_rows, lengths, out_plane_stride, len, &total, &f_max, &len_max, err)) return rc;
+  if (total && !d_rows) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
+  if (len_max && !d_pcm_out) return fail(err, VSYN_ERR_INVALID, "NULL output pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return istft_launch(h->is, h->device, spec, S, seg_rows, len.data(), total, f_max, len_max, d_rows, d_mask, d_pcm_out, out_plane_stride,
+                      d_out_frames, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_hpss_device(vsyn_handle* h, const vsyn_pcm_effect* effect, uint32_t S, const uint64_t* frames, const float* d_pcm, uint64_t plane_stride,
+                         uint32_t channels, float* d_pcm_out, uint64_t out_plane_stride, uint32_t* d_out_frames, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = effect_check(effect, err)) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!frames || !d_pcm || !d_pcm_out || plane_stride == 0 || out_plane_stride == 0 || channels == 0 || channels > 255)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return effect_launch(h->sp, h->hp, h->is, h->ef, h->device, effect, S, frames, nullptr, d_pcm, plane_stride, channels, d_pcm_out, out_plane_stride,
+                       d_out_frames, (hipStream_t)hip_stream, err);
+}
+
 int vsyn_onset_peak_windows(const vsyn_onset_peaks* peaks, uint32_t sample_rate, uint32_t* out, const char** err) {
   if (int rc = peaks_check(peaks, err)) return rc;
   if (!out || !sample_rate) return fail(err, VSYN_ERR_INVALID, "peaks: out is NULL or the rate is 0");
@@ -1542,6 +1577,22 @@ static int step_condition(vsyn_handle* h, uint32_t S, const vsyn_pcm_cond* cond,
   return VSYN_OK;
 }
 
+// the component of the view's mono downmix (T[g] frames, host; rates: 0 skips a segment, may be NULL) into h->ef's mono plane; read
+// on as the gate's plane is, with the same frames
+static int step_effects(vsyn_handle* h, uint32_t S, const vsyn_pcm_effect* effect, const uint32_t* rates, const uint64_t* T, uint64_t plane, bool clear,
+                        PcmView* v, const char** err) {
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * plane;
+  HIPCHK(h->ef.pcm.ensure(n + 1));
+  HIPCHK(h->ef.frames.ensure(S));
+  if (clear) HIPCHK(hipMemsetAsync(h->ef.pcm.p, 0, sizeof(float) * n, hs));
+  if (int rc = effect_launch(h->sp, h->hp, h->is, h->ef, h->device, effect, S, T, rates, v->pcm, v->plane, v->C, h->ef.pcm.p, plane, h->ef.frames.p, hs,
+                             err))
+    return rc;
+  *v = PcmView{h->ef.pcm.p, plane, 1u, nullptr, h->ef.frames.p};
+  return VSYN_OK;
+}
+
 // The normaliser of a chain (loud != NULL): what the chain forms ask of its spec beyond loud_check, before anything is written.
 static int chain_loud_check(const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, const char** err) {
   if (int rc = loud_check(loud, err)) return rc;
@@ -1591,7 +1642,10 @@ static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format
 // as long as the longest segment; that plane to out, and the frames behind the gate to frames_out.
 static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, uint32_t out_rate, int format,
                         void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err,
-                        const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr) {
+                        const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr,
+                        const vsyn_pcm_effect* effect = nullptr) {
+  if (effect)
+    if (int rc = effect_check(effect, err)) return rc;
   if (loud)
     if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
   if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
@@ -1621,17 +1675,27 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   PcmView v = last_submit_view(h);
   DevBuf<int16_t>* s16 = &h->rs.s16;  // the last stage's
   if (out_rate)
-    if (int rc = step_resample(h, S, rates, out_rate, gate || cond || loud ? inner : out_stride_frames, f32 && !gate && !cond && !loud, &v, err)) return rc;
+    if (int rc = step_resample(h, S, rates, out_rate, gate || effect || cond || loud ? inner : out_stride_frames,
+                               f32 && !gate && !effect && !cond && !loud, &v, err))
+      return rc;
   if (gate) {
-    if (int rc = step_gate(h, S, g, cond || loud ? inner : out_stride_frames, t_max, f32 && !cond && !loud, &v, err)) return rc;
+    if (int rc = step_gate(h, S, g, effect || cond || loud ? inner : out_stride_frames, t_max, f32 && !effect && !cond && !loud, &v, err)) return rc;
     s16 = g.split ? &h->sl.e.s16 : &h->tr.s16;
   }
-  if (loud) {  // the stage's table needs each segment's frames: behind a gate the chain waits here for the gate's read-backs
-    std::vector<uint64_t> T(frames_out, frames_out + S);
+  // the effect's and the loudness stage's tables need each segment's frames: behind a gate the chain waits here for the gate's read-backs
+  std::vector<uint64_t> T;
+  if (effect || loud) {
+    T.assign(frames_out, frames_out + S);
     if (gate) {
       HIPCHK(hipStreamSynchronize(h->host_stream));
       for (uint32_t s = 0; s < S; ++s) T[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
     }
+  }
+  if (effect) {
+    if (int rc = step_effects(h, S, effect, rates, T.data(), cond || loud ? inner : out_stride_frames, f32 && !cond && !loud, &v, err)) return rc;
+    s16 = &h->ef.s16;
+  }
+  if (loud) {
     const std::vector<uint32_t> ld_rates = stage_rates(S, rates, out_rate);
     if (int rc = step_loudness(h, S, loud, ld_rates.data(), T.data(), cond ? inner : out_stride_frames, f32 && !cond, records_out, &v, err)) return rc;
     s16 = &h->ld.s16;
@@ -2065,6 +2129,22 @@ int vsyn_pcm_chain_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_s
                                : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
   return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
                       records_out);
+}
+
+// vsyn_pcm_chain_host with the effect stage: the same chain body.
+int vsyn_pcm_chain_effects_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
+                                const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
+                                int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
+                                uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                vsyn_loudness_record* records_out, const char** err) {
+  if (!effect)
+    return vsyn_pcm_chain_host(h, gate, gate_is_split, loud, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, bounds_out,
+                               counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, err);
+  if (!h) return cond_no_handle(err);
+  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
+                      loud ? records_out : nullptr, effect);
 }
 
 int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,

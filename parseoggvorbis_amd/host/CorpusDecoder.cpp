@@ -549,7 +549,29 @@ struct Feeder {
     std::vector<float> peaks(S, 0.f);
     const int fmt = opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32;
     void* out = opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p;
-    if (opts.loudness_norm) {  // the one form with every stage's spec: a gate or none, the normaliser, conditioning or none
+    if (opts.effect) {  // the chain form with the effect stage: a gate or none, the effect, the normaliser or none, conditioning or none
+      std::vector<double> refs(S);
+      const bool gated = opts.split || opts.trim;
+      if (opts.split) size_intervals(S, o);
+      if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);
+      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+      const int rc = vsyn_pcm_chain_effects_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.effect_spec,
+                                                 opts.loudness_norm ? &opts.loudness_spec : nullptr, trim_cond(), S, rates.data(),
+                                                 opts.resample_rate, fmt, out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr,
+                                                 opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride,
+                                                 peaks.data(), refs.data(), opts.loudness_norm ? o.loud.data() : nullptr, &err);
+      if (rc != VSYN_OK) return OkOrError(std::string("GPU effects layer: ") + (err ? err : "effect failed"));
+      if (gated) {
+        for (uint32_t s = 0; s < S; ++s) {
+          CHECK(got[s] <= o.frames[s]);
+          o.frames[s] = got[s];
+        }
+        refuse_refs(refs, o);
+      } else {
+        CHECK(got == o.frames);
+      }
+      if (opts.loudness_norm) refuse_loud(o, true, rates);
+    } else if (opts.loudness_norm) {  // the one form with every stage's spec: a gate or none, the normaliser, conditioning or none
       std::vector<double> refs(S);
       const bool gated = opts.split || opts.trim;
       if (opts.split) size_intervals(S, o);
@@ -1296,6 +1318,15 @@ bool loud_norm_spec_ok(const vsyn_loudness_spec* l, const vsyn_pcm_cond* cond) {
          !(cond && (cond->options & VSYN_COND_PEAK));
 }
 
+// What a run with the effect stage asks of its spec (include/vorbis_synth_hip.h, "PCM effects", step 6).
+bool effect_spec_ok(const vsyn_pcm_effect* e) {
+  const vsyn_spectral_hpss& p = e->hpss;
+  return e->n_fft >= 16 && e->n_fft <= 8192 && !(e->n_fft & (e->n_fft - 1u)) && e->hop_length >= 1 && e->win_length >= 1 &&
+         e->win_length <= e->n_fft && (p.kh & 1u) && p.kh <= 63 && (p.kp & 1u) && p.kp <= 63 && p.component <= VSYN_HPSS_PERCUSSIVE &&
+         p.output == VSYN_HPSS_OUT_COMPONENT && p.power > 0.0 && std::isfinite(p.margin_h) && p.margin_h >= 1.0 && std::isfinite(p.margin_p) &&
+         p.margin_p >= 1.0;
+}
+
 // ogg_vorbis_spectral_corpus (target_rate 0) and ogg_vorbis_spectral_corpus_sr; fn: the entry point, for its refusal text.
 int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
@@ -1426,7 +1457,8 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
                uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
                uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                double* stats_out, const char** error_out, const vsyn_pcm_trim* split = nullptr, bool intervals_only = false,
-               const SplitOuts* so = nullptr, const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr);
+               const SplitOuts* so = nullptr, const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr,
+               const vsyn_pcm_effect* effect = nullptr);
 
 }  // namespace
 
@@ -1505,7 +1537,7 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
                uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
                uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                double* stats_out, const char** error_out, const vsyn_pcm_trim* split, bool intervals_only, const SplitOuts* so,
-               const vsyn_loudness_spec* loud, vsyn_loudness_record* records_out) {
+               const vsyn_loudness_spec* loud, vsyn_loudness_record* records_out, const vsyn_pcm_effect* effect) {
   if (so) so->begin(num_files);
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
     return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
@@ -1533,6 +1565,15 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
                          error_out);
     opts.condition = opts.loudness_norm = true;  // one mono plane per file
     opts.loudness_spec = *loud;
+  }
+  if (effect) {
+    if (!effect_spec_ok(effect) || intervals_only)
+      return refuse_call(pcm_out, num_files,
+                         "ogg_vorbis_pcm_corpus_effects: invalid effect spec (n_fft a power of two in [16, 8192], hop_length >= 1, win_length in "
+                         "[1, n_fft], odd kernel sizes up to 63, the component as output)",
+                         error_out);
+    opts.condition = opts.effect = true;  // one mono plane per file
+    opts.effect_spec = *effect;
   }
   const int rc = malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
                                [&](size_t i, const CorpusFileResult& res, bool bad) {
@@ -1596,6 +1637,22 @@ extern "C" int ogg_vorbis_pcm_corpus_loud(const uint8_t* const* datas, const siz
   return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
                     frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
                     &so, loud, records_out);
+}
+
+extern "C" int ogg_vorbis_pcm_corpus_effects(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                             uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                             const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
+                                             const vsyn_loudness_spec* loud, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out,
+                                             uint32_t* rate_out, uint64_t* bounds_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
+                                             vsyn_loudness_record* records_out, uint8_t* ok_out, const char** error_out_per_file,
+                                             double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  const bool split = gate && gate_is_split;
+  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
+                    frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
+                    &so, loud, records_out, effect);
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

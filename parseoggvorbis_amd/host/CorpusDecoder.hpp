@@ -145,6 +145,11 @@ struct CorpusOptions {
   // kind, or PCEN on the mask or the median) is every file's error. The default is off: today's rows and today's entry points.
   bool hpss = false;
   vsyn_spectral_hpss hpss_spec = {31u, 31u, VSYN_HPSS_HARMONIC, VSYN_HPSS_OUT_COMPONENT, 2.0, 1.0, 1.0};
+  // effect (a PCM run with condition): each file's mono plane is replaced by its harmonic or percussive component on the device
+  // between the gate and the loudness normaliser (include/vorbis_synth_hip.h, "PCM effects"), through vsyn_pcm_chain_effects_host.
+  // The default is off: today's output and today's entry points.
+  bool effect = false;
+  vsyn_pcm_effect effect_spec = {2048u, 512u, 2048u, 0u, {31u, 31u, VSYN_HPSS_HARMONIC, VSYN_HPSS_OUT_COMPONENT, 2.0, 1.0, 1.0}};
   // rhythm (a spectral run of a kind with 1 to 256 columns): the rows stay on the device and go through the onset stage and what
   // rhythm_spec.output selects behind it (include/vorbis_synth_hip.h, "rhythm"), through vsyn_pcm_chain_rhythm_host; a file's "rows"
   // are then that output's words (1 column, win_length columns, or 2 for the mean's float64 values). A spec the stages refuse is
@@ -293,6 +298,15 @@ int ogg_vorbis_pcm_corpus_loud(const uint8_t* const* datas, const size_t* lens, 
                                uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint32_t** intervals_out,
                                uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                const char** error_out_per_file, double* stats_out, const char** error_out);
+// ogg_vorbis_pcm_corpus_loud with the effect stage between the gate and the normaliser (effect != NULL: CorpusOptions::effect): one
+// mono plane per file, the harmonic or the percussive component of its (resampled, gated) mono signal. effect = NULL is
+// ogg_vorbis_pcm_corpus_loud, and with loud = NULL as well the entry that one is without a normaliser.
+int ogg_vorbis_pcm_corpus_effects(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                  uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                  const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect, const vsyn_loudness_spec* loud,
+                                  void** pcm_out, uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out,
+                                  uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                  const char** error_out_per_file, double* stats_out, const char** error_out);
 int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                                     const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_pcm_cond* cond,

@@ -148,13 +148,36 @@ def give_split_index(split_index, buffers, results):
         split_index[:] = [None if buffers is None or isinstance(r, Exception) else buffers.take(i) for i, r in enumerate(results)]
 
 
+def effect_spec(hpss=None, hpss_kernel_size=31, hpss_power=2.0, hpss_margin=1.0, hpss_n_fft=2048, hpss_hop_length=None, hpss_win_length=None,
+                error=PcmError):
+    """Checks the effect arguments (include/vorbis_synth_hip.h, "PCM effects", step 6) through spectral.hpss_spec and
+    spectral.spectral_spec and returns the C spec (binding.PcmEffect), or None for hpss=None: the stage is off and its other
+    arguments are not looked at. hpss "harmonic" or "percussive"; hpss_n_fft a power of two in [16, 8192]; hpss_hop_length (None:
+    hpss_n_fft // 4) >= 1; hpss_win_length (None: hpss_n_fft) in [1, hpss_n_fft]."""
+    if hpss is None:
+        return None
+    from . import spectral
+    from .binding import PcmEffect
+    try:
+        hp = spectral.hpss_spec(hpss, hpss_kernel_size, hpss_power, hpss_margin, "component")
+        n_fft = spectral._int("hpss_n_fft", hpss_n_fft)
+        if not (16 <= n_fft <= spectral.MAX_N_FFT and n_fft & (n_fft - 1) == 0):
+            raise error("hpss_n_fft must be a power of two in [16, %d], got %d" % (spectral.MAX_N_FFT, n_fft))
+        fr = spectral.spectral_spec("stft", n_fft, n_fft // 4 if hpss_hop_length is None else hpss_hop_length, hpss_win_length)
+    except spectral.SpectralError as e:
+        msg = str(e)  # (spectral_spec names its own arguments: hop_length, win_length)
+        raise error(msg if msg.startswith("hpss") else "hpss_" + msg) from None
+    return PcmEffect(fr.n_fft, fr.hop_length, fr.win_length, 0, hp)
+
+
 _load = _corpus.load
 
 
 def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0, device=0, errors="raise", files_per_submit=64,
                   stats=None, mono=False, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048, trim_hop_length=512,
                   trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None, loudness_normalize=None,
-                  loudness=None):
+                  loudness=None, hpss=None, hpss_kernel_size=31, hpss_power=2.0, hpss_margin=1.0, hpss_n_fft=2048, hpss_hop_length=None,
+                  hpss_win_length=None):
     """PCM of many Ogg Vorbis files in one corpus run: a list of (pcm, sr) tuples. pcm is float32 (channels, frames), or int16
     (frames, channels) with ov_read's conversion; sr is the rate of the returned PCM. sr=None keeps each file's own rate (the
     PCM is bit for bit that of ogg_vorbis_decode_corpus); an integer resamples every file to it on the GPU. errors="raise": the
@@ -178,7 +201,14 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     BS.1770-4, as get_loudness_batch(channels="mono") measures it on that signal) is L; it is not clipped. loudness (optional list)
     receives the measured LUFS per file, in front of the gain (None for a failed file, and for every file with the stage off). A
     file that is shorter than 400 ms, silent (nothing above -70 LUFS), not finite or below 4000 Hz fails alone, by name. With
-    loudness_normalize=None nothing is launched and the call takes the entry points it took without the argument."""
+    loudness_normalize=None nothing is launched and the call takes the entry points it took without the argument.
+    hpss="harmonic" or "percussive" (needs mono=True): the mono signal, behind the resampler and trim_db / split_db and in front of
+    the loudness normaliser, the peak and the pre-emphasis, is replaced by that component of it, as librosa.effects.harmonic(y,
+    kernel_size=hpss_kernel_size, power=hpss_power, margin=hpss_margin, n_fft=hpss_n_fft, hop_length=hpss_hop_length,
+    win_length=hpss_win_length) computes it (percussive likewise): STFT, the soft mask of decompose.hpss on its magnitude, the masked
+    inverse STFT to the signal's own length, all on the device. hpss_n_fft is a power of two in [16, 8192]; hpss_hop_length defaults
+    to hpss_n_fft // 4 and hpss_win_length to hpss_n_fft; hpss_kernel_size and hpss_margin are one value or a (harmonic, percussive)
+    pair. With hpss=None nothing is launched and the call takes the entry points it took without the argument."""
     _corpus.check_errors(errors)
     target = check_sr(sr)
     name = _format(dtype)
@@ -196,6 +226,9 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     loud = loudness_args(loudness_normalize, loudness, cond)
     if not mono and loud is not None:
         raise PcmError("loudness_normalize acts on the mono signal: pass mono=True")
+    effect = effect_spec(hpss, hpss_kernel_size, hpss_power, hpss_margin, hpss_n_fft, hpss_hop_length, hpss_win_length)
+    if not mono and effect is not None:
+        raise PcmError("hpss acts on the mono signal: pass mono=True")
     lib = _load()
     n = len(list_of_bytes)
     frames = np.zeros(n, np.uint64)
@@ -211,21 +244,24 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
         return _corpus.copy_into(a, p), int(rates[i])
 
     args = (threads, feeders, files_per_submit, device, target, FORMATS[name])
-    if loud is not None:  # the one entry with every stage's spec (NULL: off)
+    if loud is not None or effect is not None:  # the entries with every stage's spec (NULL: off); the effect has one of its own
         from .binding import LOUDNESS_RECORD_DTYPE
         ib = _corpus.IntervalBuffers(lib, n)
         bounds, records = np.zeros((max(n, 1), 2), np.uint64), np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
         gate = split if split is not None else trim
+        head = (C.byref(cond) if cond.options else None, None if gate is None else C.byref(gate), int(split is not None))
+        if effect is None:
+            fn, specs = lib.ogg_vorbis_pcm_corpus_loud, (C.byref(loud),)
+        else:
+            fn, specs = lib.ogg_vorbis_pcm_corpus_effects, (C.byref(effect), None if loud is None else C.byref(loud))
         try:
-            res = _corpus.run(lib, lib.ogg_vorbis_pcm_corpus_loud, list_of_bytes,
-                              args + (C.byref(cond) if cond.options else None, None if gate is None else C.byref(gate), int(split is not None),
-                                      C.byref(loud)), (frames, chans, rates, bounds, ib.ptrs, ib.counts, records), build, PcmError, errors, "pcm",
-                              stats)
+            res = _corpus.run(lib, fn, list_of_bytes, args + head + specs, (frames, chans, rates, bounds, ib.ptrs, ib.counts, records), build,
+                              PcmError, errors, "pcm", stats)
             give_split_index(split_index, ib if split is not None else None, res)
         finally:
             ib.free()
         give_trim_index(trim_index, bounds[:n] if trim is not None else None, res)
-        give_loudness(loudness, records, res)
+        give_loudness(loudness, records if loud is not None else None, res)
         return res
     give_loudness(loudness, None, [None] * n)
     if split is not None:
