@@ -1633,8 +1633,8 @@ int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
  *     spectral entry points check them (the spec's other fields but VSYN_SPEC_CENTER are not read); n_fft a power of two, any other
  *     refused by name; NULL seg_rows, rows or output; a length above out_plane_stride; out_plane_stride >= 2^32.
  *  7. Not built: the inverse of the direct-DFT path (an n_fft that is no power of two); other windows; a fused single kernel in
- *     which a workgroup owns an output span and recomputes its edge frames; phase-vocoder time stretch, Griffin-Lim and spectral
- *     gating, each of which is one kernel on top of this stage.
+ *     which a workgroup owns an output span and recomputes its edge frames; Griffin-Lim and spectral gating, each of which is
+ *     one kernel on top of this stage (the phase-vocoder time stretch is built: "phase vocoder").
  *
  * Precision and order. Every frame's arithmetic is its own: nothing of one frame enters another's transform, and step 4 adds in
  * ascending f whatever the grid. No atomics: the result depends on neither the launch geometry nor the segment's place in the batch,
@@ -1675,7 +1675,8 @@ int vsyn_istft_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t n
  *     name; hop_length >= 1; win_length in [1, n_fft]; the hpss spec as the HPSS stage checks it, and its output must be
  *     VSYN_HPSS_OUT_COMPONENT: the mask and the median are not signals.
  *  7. Not built: the effect in front of the spectral, pitch, descriptor and loudness row entries (the steps are shared, so this is
- *     the natural follow-up); both components from one call; the residual; time stretch and pitch shift.
+ *     the natural follow-up); both components from one call; the residual (time stretch and pitch shift are built: "PCM
+ *     stretch").
  * The entry points read PCM only, and share the handle's spectral, HPSS and inverse-STFT workspaces with those stages' entries. */
 typedef struct vsyn_pcm_effect { /* 56 bytes */
   uint32_t n_fft;      /* a power of two in [16, 8192]; librosa's default is 2048 */
@@ -1695,6 +1696,115 @@ int vsyn_pcm_hpss_device(vsyn_handle* h, const vsyn_pcm_effect* effect, uint32_t
 /* vsyn_pcm_chain_host with the effect between the gate and the loudness step, through the same chain body, without PCM or rows
  * leaving the device: out receives ONE plane per segment. effect = NULL is that entry, bit for bit. Synchronous. */
 int vsyn_pcm_chain_effects_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
+                                const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t num_segments, const uint32_t* in_rates,
+                                uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
+                                uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                vsyn_loudness_record* records_out, const char** err);
+
+/* ---- phase vocoder: complex rows to the complex rows of the time-stretched signal, computed where the rows are ----
+ *
+ * Input: one segment's rows X[f][k], F rows (time) of nb = n_fft / 2 + 1 complex64 bins, the layout VSYN_SPEC_STFT writes, and a rate
+ * per SEGMENT, a finite double above 0 (above 1 shortens). Output: F_out rows of the same layout. This is librosa.phase_vocoder(X.T,
+ * rate=rate, hop_length=hop_length, n_fft=n_fft). librosa is not among the test dependencies and parity with it is not claimed: the
+ * contract is the arithmetic below, the device is compared against a float64 model of it fed the same float32 rows
+ * (tests/pv_model.py), and the model against a literal transcription of librosa's sequential loop (tests/test_pv_cpu.py).
+ *
+ *  1. F_out = ceil(F / rate), one float64 quotient: len(numpy.arange(0, F, rate)); F = 0 gives no rows. Output row t sits at s_t =
+ *     t * rate (one float64 product), i_t = floor(s_t), alpha_t = s_t - i_t. Rows of index >= F read as +0 + 0i (librosa pads two).
+ *  2. Per input row and bin, in float64 from the float32 components: A = atan2((double)im, (double)re), G = sqrt(re * re + im * im).
+ *     C99's signed zeros are part of the contract: atan2(+0, -0) = pi, atan2(-0, -0) = -pi, atan2(+-0, +0) = +-0, so that a silent
+ *     stretch in the middle of a file leaves the phase of what follows where it was.
+ *  3. phi_k = hop_length * (k * (1.0 / (n_fft * (1.0 / (2 pi))))), float64 on the host (numpy's rfftfreq expression); d = A[i_t + 1][k]
+ *     - A[i_t][k] - phi_k; inc_t = phi_k + (d - 2 pi * rint(d / (2 pi))), rint to even, 2 pi the double nearest it.
+ *  4. acc_0 = A[0][k] and acc_{t+1} = acc_t + inc_t, in a FIXED blocked order: output rows go in blocks of VSYN_PV_BLOCK = 64 rows of
+ *     the segment. A block's sum is ((0.0 + inc_b0) + inc_b0+1) + ...; the carry of block b is ((A[0][k] + sum_0) + sum_1) + ... +
+ *     sum_{b-1}; inside a block acc starts at the carry and adds inc_t in ascending t. The block size is a constant of the contract:
+ *     nothing depends on the grid, the tile of bins or the segment's place in the batch.
+ *  5. out[t][k] = ((float)(m cos(acc_t)), (float)(m sin(acc_t))), m = (1 - alpha_t) G[i_t][k] + alpha_t G[i_t + 1][k], everything in
+ *     float64 with one rounding per component. Plain products and sums in the order written; nothing is contracted.
+ *  6. Non-finite values, per bin k (other bins, and other segments, keep their bits). A NaN component in X[f][k] makes A and G of
+ *     that row NaN: m_t is NaN for i_t in {f - 1, f} (alpha_t = 0 included: 0 * NaN), inc_t is NaN for the same t, and acc stays NaN
+ *     behind the first of them. So with t0 the first t whose i_t is f - 1 or f, out[t][k] is NaN for every t >= t0; f = 0 has t0 = 0
+ *     (acc_0 itself). At a rate above 2 the walk can step over both f - 1 and f: then no t0 exists and nothing changes. An Inf
+ *     component has a finite angle and G = Inf: exactly the rows with i_t in {f - 1, f} are non-finite (+-Inf, or NaN from 0 * Inf
+ *     where alpha_t = 0). The rows in front of t0 keep their bits; the rows behind the last of them are finite, but carry the
+ *     phase that the angle of the Inf (a multiple of pi / 4) left in acc, so their bits may differ from the clean run's.
+ *  7. Checks (VSYN_ERR_INVALID before anything runs, the outputs untouched): n_fft a power of two in [16, 8192] and hop_length >= 1
+ *     as the inverse STFT checks them (win_length and the spec's other fields are not read); a rate that is not finite or <= 0; a
+ *     segment of more than 2^30 - 1 rows in or out; NULL seg_rows, rates, rows or output; more than 65535 segments.
+ *  8. Not built: fusing the emit kernel into the inverse STFT's frame kernel (the stretched rows pass through memory); phase locking
+ *     and other vocoder variants; an n_fft that is no power of two.
+ *
+ * Precision and order: no atomics, the same rows and rate give the same bits whatever the batch. The entry reads the rows only. One
+ * handle's calls share its block-sum workspace (F_out / 64 rows of nb float64, grown on demand). */
+#define VSYN_PV_BLOCK 64u
+
+/* F_out of step 1: host arithmetic, no device. 0 for a rate the stage refuses. */
+uint64_t vsyn_pv_num_rows(uint64_t rows, double rate);
+
+/* The stage on rows the caller has on the device: d_rows holds the segments' rows back to back, nb complex64 bins each (8-byte
+ * aligned); seg_rows[S] and rates[S] are HOST arrays. Segment g's F_out rows go to d_rows_out back to back in the same order (the
+ * caller sizes it from vsyn_pv_num_rows; it must not overlap d_rows); seg_rows_out[S] (HOST, may be NULL) receives each F_out.
+ * Of spec only n_fft and hop_length are read. Asynchronous on hip_stream. */
+int vsyn_phase_vocoder_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t num_segments, const uint64_t* seg_rows, const double* rates,
+                              const float* d_rows, float* d_rows_out, uint64_t* seg_rows_out, void* hip_stream, const char** err);
+
+/* ---- PCM stretch: the decoded PCM time-stretched, or pitch-shifted, as PCM, computed where the PCM is ----
+ *
+ * librosa.effects.time_stretch(y, rate=rate) for one segment, and with a resampling behind it librosa.effects.pitch_shift. Parity
+ * with librosa is not claimed; the contract is the composition below, of stages whose arithmetic their own sections pin, and the
+ * stage equals that composition through the public device entry points bit for bit (tests/test_gpu_pcm_stretch.py). Per segment of
+ * T frames, always centred, on the mono downmix:
+ *
+ *  1. X = the VSYN_SPEC_STFT rows ("linear spectra") with the stage's n_fft, hop_length, win_length.
+ *  2. Y = the phase vocoder's rows ("phase vocoder") of X at the segment's rate.
+ *  3. y = the inverse STFT ("inverse STFT") of Y without a mask, to length L = vsyn_stretch_num_samples(T, rate) = nearbyint(T /
+ *     rate), ties to even: Python's int(round(T / rate)).
+ *  4. With shift_to_hz != 0: y resampled from shift_from_hz[g] to shift_to_hz ("resampling"), vsyn_resample_num_frames of L frames.
+ *  5. With VSYN_STRETCH_FIX_LENGTH: exactly T samples, the first T of what step 3 or 4 left, or all of it followed by zeros.
+ *  6. pitch_shift by n_steps of bins_per_octave is this stage with rate = 2^(-n_steps / bins_per_octave), shift_to_hz = sr,
+ *     shift_from_hz = rint(sr / rate) and the length fixed. ONE DIVERGENCE from librosa: it resamples from the non-integer sr / rate,
+ *     this stage from that rate rounded to whole Hz, because its resampler is resample_poly's arithmetic on integer rates. That moves
+ *     the pitch by at most 0.5 / (sr / rate) relative. The pair must pass the resampler's check max(up, down) <= VSYN_RESAMPLE_MAX_M.
+ *  7. Order in the pipeline: resampler, trim / split, this stage, loudness, peak normalisation and pre-emphasis. This is the one
+ *     stage behind the gate that changes the frame count: the steps behind it see the stage's frames.
+ *  8. Non-finite samples flow through as the stages' rules say.
+ *  9. Checks (VSYN_ERR_INVALID before anything runs, outputs untouched): the framing as "PCM effects" checks it; unknown options; a
+ *     non-zero reserved; a rate that is not finite or <= 0; with a shift a NULL shift_from_hz, a from-rate of 0 or a pair the
+ *     resampler refuses, by name; an out_plane_stride below a segment's delivered frames.
+ * 10. Not built: the stretch in front of the spectral, pitch, descriptor and rhythm row entries; the stretch composed with the HPSS
+ *     effect; librosa's non-integer resampling rate; fusing the vocoder into the inverse frame kernel.
+ * The entry points read PCM only, and share the handle's spectral, phase-vocoder and inverse-STFT workspaces with those stages'
+ * entries; the resampler's workspace is the stage's own. */
+#define VSYN_STRETCH_FIX_LENGTH 1u /* cut or zero-pad each output to its input's frames */
+typedef struct vsyn_pcm_stretch { /* 24 bytes */
+  uint32_t n_fft;       /* a power of two in [16, 8192]; librosa's default is 2048 */
+  uint32_t hop_length;  /* >= 1; n_fft / 4 */
+  uint32_t win_length;  /* 1 .. n_fft; n_fft */
+  uint32_t options;     /* VSYN_STRETCH_FIX_LENGTH */
+  uint32_t shift_to_hz; /* 0: time stretch only. Else: behind the stretch, each segment is resampled from shift_from_hz[g] to this rate */
+  uint32_t reserved;    /* 0 */
+} vsyn_pcm_stretch;
+
+/* L of step 3: host arithmetic, no device. 0 for a rate the stage refuses. */
+uint64_t vsyn_stretch_num_samples(uint64_t frames, double rate);
+
+/* The stage alone on PCM the caller has on the device: d_pcm planar [S][channels][plane_stride] float32; frames[S], rates[S] and
+ * shift_from_hz[S] (NULL without a shift) are HOST arrays. Segment g's samples go to d_pcm_out + g * out_plane_stride, exactly its
+ * delivered frames (step 3, 4 or 5) and nothing behind them; d_out_frames[g] (may be NULL) receives that count. Asynchronous on
+ * hip_stream. */
+int vsyn_pcm_stretch_device(vsyn_handle* h, const vsyn_pcm_stretch* stretch, uint32_t num_segments, const uint64_t* frames, const double* rates,
+                            const uint32_t* shift_from_hz, const float* d_pcm, uint64_t plane_stride, uint32_t channels, float* d_pcm_out,
+                            uint64_t out_plane_stride, uint32_t* d_out_frames, void* hip_stream, const char** err);
+
+/* vsyn_pcm_chain_effects_host with the stretch stage in the effect's slot, through the same chain body: stretch_rates[S] and
+ * shift_from_hz[S] (NULL without a shift) are HOST arrays per segment. stretch = NULL is that entry, bit for bit; a stretch and an
+ * effect in one call are refused by name. frames_out[g] receives the stage's delivered frames, and the loudness and conditioning
+ * steps see those. out_stride_frames must hold the largest of each segment's frames in front of the gate, stretched, resampled and
+ * delivered (a gate only shortens, and every one of them is monotone in the frames): a call with out = NULL returns that need in
+ * frames_out instead, as every chain entry's size query does. Synchronous. */
+int vsyn_pcm_chain_stretch_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
+                                const vsyn_pcm_stretch* stretch, const double* stretch_rates, const uint32_t* shift_from_hz,
                                 const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t num_segments, const uint32_t* in_rates,
                                 uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
                                 uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,

@@ -51,6 +51,9 @@ def load():
                        ("ogg_vorbis_pcm_corpus_effects", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
                                                           C.POINTER(binding.PcmEffect), C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp,
                                                           vp, vp, vp]),
+                       ("ogg_vorbis_pcm_corpus_stretch", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
+                                                          C.POINTER(binding.PcmEffect), C.POINTER(binding.PcmStretch), vp, vp,
+                                                          C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_spectral_corpus_loud", [C.POINTER(binding.SpectralSpec), u32, C.POINTER(binding.SpectralPcen),
                                                             C.POINTER(binding.SpectralPost), C.POINTER(binding.PcmCond),
                                                             C.POINTER(binding.PcmTrim), C.c_int, C.POINTER(binding.LoudnessSpec), vp, vp, vp,

@@ -98,6 +98,14 @@ class PcmEffect(C.Structure):  # vsyn_pcm_effect
     _fields_ = [("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("win_length", C.c_uint32), ("reserved", C.c_uint32), ("hpss", SpectralHpss)]
 
 
+class PcmStretch(C.Structure):  # vsyn_pcm_stretch
+    _fields_ = [("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("win_length", C.c_uint32), ("options", C.c_uint32),
+                ("shift_to_hz", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+VSYN_STRETCH_FIX_LENGTH = 1
+
+
 class OnsetSpec(C.Structure):  # vsyn_onset_spec
     _fields_ = [("lag", C.c_uint32), ("max_size", C.c_uint32), ("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32)]
 
@@ -292,6 +300,7 @@ _SYMBOLS = [
     "vsyn_onset_peak_windows", "vsyn_tempogram_win_length", "vsyn_tempogram_tile", "vsyn_tempo_from_mean",
     "vsyn_onset_strength_device", "vsyn_onset_peaks_device", "vsyn_tempogram_device", "vsyn_pcm_chain_rhythm_host",
     "vsyn_istft_num_samples", "vsyn_istft_device", "vsyn_pcm_hpss_device", "vsyn_pcm_chain_effects_host",
+    "vsyn_pv_num_rows", "vsyn_phase_vocoder_device", "vsyn_stretch_num_samples", "vsyn_pcm_stretch_device", "vsyn_pcm_chain_stretch_host",
 ]
 
 
@@ -437,6 +446,15 @@ def load():
     lib.vsyn_pcm_hpss_device.argtypes = [vp, C.POINTER(PcmEffect), u32, vp, vp, u64, u32, vp, u64, vp, vp, cpp]
     lib.vsyn_pcm_chain_effects_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(PcmEffect), C.POINTER(LoudnessSpec), C.POINTER(PcmCond), u32,
                                                 vp, u32, C.c_int, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, cpp]
+    lib.vsyn_pv_num_rows.argtypes = [u64, C.c_double]
+    lib.vsyn_pv_num_rows.restype = u64
+    lib.vsyn_phase_vocoder_device.argtypes = [vp, C.POINTER(SpectralSpec), u32, vp, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_stretch_num_samples.argtypes = [u64, C.c_double]
+    lib.vsyn_stretch_num_samples.restype = u64
+    lib.vsyn_pcm_stretch_device.argtypes = [vp, C.POINTER(PcmStretch), u32, vp, vp, vp, vp, u64, u32, vp, u64, vp, vp, cpp]
+    lib.vsyn_pcm_chain_stretch_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(PcmEffect), C.POINTER(PcmStretch), vp, vp,
+                                                C.POINTER(LoudnessSpec), C.POINTER(PcmCond), u32, vp, u32, C.c_int, vp, u64, vp, vp, vp, vp, u64, vp,
+                                                vp, vp, cpp]
     lib.vsyn_pcm_chain_hpss_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
                                              C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralHpss),
                                              C.POINTER(SpectralPcen), C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64,
@@ -741,6 +759,26 @@ class Synth:
         _check(self.lib.vsyn_pcm_hpss_device(self.h, _ref(effect), len(fr), _ptr(fr), d_pcm, plane_stride, channels, d_pcm_out, out_plane_stride,
                                              d_out_frames, stream, C.byref(err)), err)
 
+    def phase_vocoder_device(self, spec, seg_rows, rates, d_rows, d_rows_out, stream=None):
+        """vsyn_phase_vocoder_device on device pointers (ints); seg_rows and rates are host sequences. Returns each segment's rows
+        out (uint64 [S])."""
+        nrows, r = np.ascontiguousarray(seg_rows, dtype=np.uint64), np.ascontiguousarray(rates, dtype=np.float64)
+        out = np.zeros(max(1, len(nrows)), np.uint64)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_phase_vocoder_device(self.h, _ref(spec), len(nrows), _ptr(nrows), _ptr(r), d_rows, d_rows_out, _ptr(out), stream,
+                                                  C.byref(err)), err)
+        return out[:len(nrows)]
+
+    def pcm_stretch_device(self, stretch, frames, rates, shift_from_hz, d_pcm, plane_stride, channels, d_pcm_out, out_plane_stride, d_out_frames=None,
+                           stream=None):
+        """vsyn_pcm_stretch_device on device pointers (ints; d_out_frames may be None); frames, rates and shift_from_hz (None without
+        a shift) are host sequences."""
+        fr, r = np.ascontiguousarray(frames, dtype=np.uint64), np.ascontiguousarray(rates, dtype=np.float64)
+        hz = None if shift_from_hz is None else np.ascontiguousarray(shift_from_hz, dtype=np.uint32)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_pcm_stretch_device(self.h, _ref(stretch), len(fr), _ptr(fr), _ptr(r), _ptr(hz), d_pcm, plane_stride, channels, d_pcm_out,
+                                                out_plane_stride, d_out_frames, stream, C.byref(err)), err)
+
     def onset_strength_device(self, onset, dim, seg_rows, d_rows, d_env, stream=None):
         """vsyn_onset_strength_device on device pointers (ints); seg_rows is a host sequence of each segment's row count."""
         nrows = np.ascontiguousarray(seg_rows, dtype=np.uint64)
@@ -917,6 +955,25 @@ class Synth:
         out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_effects_host,
                                      (_ref(gate), 1 if gate_is_split else 0, _ref(effect), _ref(loud), _ref(cond), S, _ptr(rates), out_rate, fmt), S,
                                      fmt, None, outs)
+        return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
+
+    def pcm_chain_stretch_host(self, gate, gate_is_split, effect, stretch, stretch_rates, shift_from_hz, loud, cond, num_segments, in_rates=None,
+                               out_rate=0, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_chain_stretch_host over the last submit's segments (stretch_rates: one float per segment; shift_from_hz: None
+        without a shift): returns what pcm_chain_host returns, frames being what the stretch delivers and the stride the largest
+        length on the way."""
+        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "bounds", "counts", "peaks", "refs")
+        rec, iv = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), []
+        sr = None if stretch_rates is None else np.ascontiguousarray(stretch_rates, dtype=np.float64)
+        hz = None if shift_from_hz is None else np.ascontiguousarray(shift_from_hz, dtype=np.uint32)
+
+        def outs(t_max):
+            ivs = self._max_intervals(gate, t_max) if gate is not None and gate_is_split else 1
+            iv.append(np.zeros((max(1, S), ivs, 2), np.uint32))
+            return [o["bounds"], o["counts"], iv[0], ivs, o["peaks"], o["refs"], rec]
+        out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_stretch_host,
+                                     (_ref(gate), 1 if gate_is_split else 0, _ref(effect), _ref(stretch), _ptr(sr), _ptr(hz), _ref(loud), _ref(cond),
+                                      S, _ptr(rates), out_rate, fmt), S, fmt, None, outs)
         return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
 
     def pcm_chain_spectral_host(self, gate, gate_is_split, loud, cond, spec, pcen, post, in_rates, out_rate=0):

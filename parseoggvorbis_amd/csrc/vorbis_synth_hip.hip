@@ -28,9 +28,11 @@
 #include "vsyn_hpss.h"
 #include "vsyn_istft.h"
 #include "vsyn_effects.h"
+#include "vsyn_pv.h"
 #include "vsyn_rhythm.h"
 #include "vsyn_loudness.h"
 #include "vsyn_resample.h"
+#include "vsyn_stretch.h"
 #include "vsyn_condition.h"
 #include "vsyn_trim.h"
 #include "vsyn_split.h"
@@ -137,6 +139,8 @@ struct vsyn_handle {
   HpssWs hp;                           // vsyn_hpss.h
   IstftWs is;                          // vsyn_istft.h
   EffectWs ef;                         // vsyn_effects.h
+  PvWs pv;                             // vsyn_pv.h
+  StretchWs st;                        // vsyn_stretch.h
   RhythmWs rh;                         // vsyn_rhythm.h
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
@@ -1375,6 +1379,36 @@ int vsyn_pcm_hpss_device(vsyn_handle* h, const vsyn_pcm_effect* effect, uint32_t
                        d_out_frames, (hipStream_t)hip_stream, err);
 }
 
+uint64_t vsyn_pv_num_rows(uint64_t rows, double rate) { return pv_num_rows(rows, rate); }
+
+int vsyn_phase_vocoder_device(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint64_t* seg_rows, const double* rates,
+                              const float* d_rows, float* d_rows_out, uint64_t* seg_rows_out, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  std::vector<uint64_t> f_out;
+  uint64_t total, total_out;
+  if (int rc = pv_check_call(spec, S, seg_rows, rates, f_out, &total, &total_out, err)) return rc;
+  if (total && !d_rows) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
+  if (total_out && !d_rows_out) return fail(err, VSYN_ERR_INVALID, "NULL output pointer");
+  for (uint32_t g = 0; g < S && seg_rows_out; ++g) seg_rows_out[g] = f_out[g];
+  std::lock_guard<std::mutex> lk(h->mu);
+  return pv_launch(h->pv, h->device, spec, S, seg_rows, rates, f_out.data(), d_rows, d_rows_out, (hipStream_t)hip_stream, err);
+}
+
+uint64_t vsyn_stretch_num_samples(uint64_t frames, double rate) { return stretch_num_samples(frames, rate); }
+
+int vsyn_pcm_stretch_device(vsyn_handle* h, const vsyn_pcm_stretch* stretch, uint32_t S, const uint64_t* frames, const double* rates,
+                            const uint32_t* shift_from_hz, const float* d_pcm, uint64_t plane_stride, uint32_t channels, float* d_pcm_out,
+                            uint64_t out_plane_stride, uint32_t* d_out_frames, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = stretch_check_call(stretch, S, rates, shift_from_hz, err)) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!frames || !d_pcm || !d_pcm_out || plane_stride == 0 || out_plane_stride == 0 || channels == 0 || channels > 255)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return stretch_launch(h->sp, h->pv, h->is, h->st, h->device, stretch, S, frames, rates, shift_from_hz, d_pcm, plane_stride, channels, d_pcm_out,
+                        out_plane_stride, d_out_frames, (hipStream_t)hip_stream, err);
+}
+
 int vsyn_onset_peak_windows(const vsyn_onset_peaks* peaks, uint32_t sample_rate, uint32_t* out, const char** err) {
   if (int rc = peaks_check(peaks, err)) return rc;
   if (!out || !sample_rate) return fail(err, VSYN_ERR_INVALID, "peaks: out is NULL or the rate is 0");
@@ -1593,6 +1627,32 @@ static int step_effects(vsyn_handle* h, uint32_t S, const vsyn_pcm_effect* effec
   return VSYN_OK;
 }
 
+// The stretch stage in a chain.
+struct Stretch {
+  const vsyn_pcm_stretch* spec;
+  const double* rates;       // [S]
+  const uint32_t* from_hz;   // [S], NULL without a shift
+};
+
+// the stretched (and shifted) mono downmix of the view (T[g] frames, host) into h->st's mono plane, T[g] replaced by what the stage
+// delivers; read on as the gate's plane is, with those frames
+static int step_stretch(vsyn_handle* h, uint32_t S, const Stretch& x, uint64_t* T, uint64_t plane, bool clear, PcmView* v, const char** err) {
+  hipStream_t hs = h->host_stream;
+  const size_t n = (size_t)S * plane;
+  HIPCHK(h->st.pcm.ensure(n + 1));
+  HIPCHK(h->st.frames.ensure(S));
+  if (clear) HIPCHK(hipMemsetAsync(h->st.pcm.p, 0, sizeof(float) * n, hs));
+  if (int rc = stretch_launch(h->sp, h->pv, h->is, h->st, h->device, x.spec, S, T, x.rates, x.from_hz, v->pcm, v->plane, v->C, h->st.pcm.p, plane,
+                              h->st.frames.p, hs, err))
+    return rc;
+  for (uint32_t g = 0; g < S; ++g) {
+    uint64_t len, res;
+    T[g] = stretch_frames(x.spec, T[g], x.rates[g], x.from_hz ? x.from_hz[g] : 0u, &len, &res);
+  }
+  *v = PcmView{h->st.pcm.p, plane, 1u, nullptr, h->st.frames.p};
+  return VSYN_OK;
+}
+
 // The normaliser of a chain (loud != NULL): what the chain forms ask of its spec beyond loud_check, before anything is written.
 static int chain_loud_check(const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, const char** err) {
   if (int rc = loud_check(loud, err)) return rc;
@@ -1643,9 +1703,13 @@ static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format
 static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, uint32_t out_rate, int format,
                         void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err,
                         const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr,
-                        const vsyn_pcm_effect* effect = nullptr) {
+                        const vsyn_pcm_effect* effect = nullptr, const Stretch* stretch = nullptr) {
   if (effect)
     if (int rc = effect_check(effect, err)) return rc;
+  if (stretch) {
+    if (effect) return fail(err, VSYN_ERR_INVALID, "a stretch and an hpss effect in one chain call: their composition is not built");
+    if (int rc = stretch_check_call(stretch->spec, S, stretch->rates, stretch->from_hz, err)) return rc;
+  }
   if (loud)
     if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
   if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
@@ -1657,6 +1721,14 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   std::lock_guard<std::mutex> lk(h->mu);
   uint64_t t_max;
   if (int rc = last_submit_frames(h, S, rates, out_rate, frames_out, &t_max, err)) return rc;
+  const uint64_t t_in = t_max;  // the longest segment in front of the stretch; t_max: the longest anywhere in the chain
+  std::vector<uint64_t> T_in(frames_out, frames_out + S);
+  if (stretch) {  // every plane holds the largest of the input, the stretched, the resampled and the delivered lengths
+    for (uint32_t g = 0; g < S; ++g) {
+      frames_out[g] = stretch_span(stretch->spec, T_in[g], stretch->rates[g], stretch->from_hz ? stretch->from_hz[g] : 0u);
+      t_max = std::max(t_max, frames_out[g]);
+    }
+  }
   if (!out || S == 0) return VSYN_OK;
   if (t_max > out_stride_frames) return fail(err, VSYN_ERR_INVALID, "out_stride_frames %llu below %llu frames",
                                              (unsigned long long)out_stride_frames, (unsigned long long)t_max);
@@ -1666,7 +1738,7 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   if (gate) {
     g = *gate;
     if (g.split)
-      if (int rc = split_check_stride(g, t_max, err)) return rc;
+      if (int rc = split_check_stride(g, t_in, err)) return rc;
     g.frames = joined.data();
     g.bounds = bounds.data();
   }
@@ -1675,17 +1747,19 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   PcmView v = last_submit_view(h);
   DevBuf<int16_t>* s16 = &h->rs.s16;  // the last stage's
   if (out_rate)
-    if (int rc = step_resample(h, S, rates, out_rate, gate || effect || cond || loud ? inner : out_stride_frames,
-                               f32 && !gate && !effect && !cond && !loud, &v, err))
+    if (int rc = step_resample(h, S, rates, out_rate, gate || effect || stretch || cond || loud ? inner : out_stride_frames,
+                               f32 && !gate && !effect && !stretch && !cond && !loud, &v, err))
       return rc;
   if (gate) {
-    if (int rc = step_gate(h, S, g, effect || cond || loud ? inner : out_stride_frames, t_max, f32 && !effect && !cond && !loud, &v, err)) return rc;
+    if (int rc = step_gate(h, S, g, effect || stretch || cond || loud ? inner : out_stride_frames, t_in, f32 && !effect && !stretch && !cond && !loud,
+                           &v, err))
+      return rc;
     s16 = g.split ? &h->sl.e.s16 : &h->tr.s16;
   }
   // the effect's and the loudness stage's tables need each segment's frames: behind a gate the chain waits here for the gate's read-backs
   std::vector<uint64_t> T;
-  if (effect || loud) {
-    T.assign(frames_out, frames_out + S);
+  if (effect || stretch || loud) {
+    T = T_in;
     if (gate) {
       HIPCHK(hipStreamSynchronize(h->host_stream));
       for (uint32_t s = 0; s < S; ++s) T[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
@@ -1694,6 +1768,11 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   if (effect) {
     if (int rc = step_effects(h, S, effect, rates, T.data(), cond || loud ? inner : out_stride_frames, f32 && !cond && !loud, &v, err)) return rc;
     s16 = &h->ef.s16;
+  }
+  if (stretch) {  // T becomes the stage's frames: the steps behind it see those
+    const Stretch& x = *stretch;
+    if (int rc = step_stretch(h, S, x, T.data(), cond || loud ? inner : out_stride_frames, f32 && !cond && !loud, &v, err)) return rc;
+    s16 = &h->st.s16;
   }
   if (loud) {
     const std::vector<uint32_t> ld_rates = stage_rates(S, rates, out_rate);
@@ -1709,6 +1788,7 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
     for (uint32_t s = 0; s < S; ++s) frames_out[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
     if (gate->bounds) memcpy(gate->bounds, bounds.data(), sizeof(uint32_t) * bounds.size());
   }
+  for (uint32_t s = 0; s < S && stretch; ++s) frames_out[s] = T[s];
   return VSYN_OK;
 }
 
@@ -2145,6 +2225,24 @@ int vsyn_pcm_chain_effects_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int g
                                : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
   return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
                       loud ? records_out : nullptr, effect);
+}
+
+// vsyn_pcm_chain_effects_host with the stretch stage in the effect's slot: the same chain body.
+int vsyn_pcm_chain_stretch_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
+                                const vsyn_pcm_stretch* stretch, const double* stretch_rates, const uint32_t* shift_from_hz,
+                                const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
+                                int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
+                                uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                vsyn_loudness_record* records_out, const char** err) {
+  if (!stretch)
+    return vsyn_pcm_chain_effects_host(h, gate, gate_is_split, effect, loud, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out,
+                                       bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, err);
+  if (!h) return cond_no_handle(err);
+  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+  const Stretch x{stretch, stretch_rates, stretch->shift_to_hz ? shift_from_hz : nullptr};
+  return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
+                      loud ? records_out : nullptr, effect, &x);
 }
 
 int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,

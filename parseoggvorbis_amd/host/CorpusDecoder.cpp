@@ -542,6 +542,20 @@ struct Feeder {
       rates[s] = o.err[s].empty() ? g.pending[s]->header.audio_sample_rate : 0;
       pl = std::max(pl, o.frames[s]);
     }
+    // a stretch run: each file's rate and from-rate by its index in the call, and a plane that holds the longest of what a file has
+    // on its way through the stage (include/vorbis_synth_hip.h, vsyn_pcm_chain_stretch_host)
+    std::vector<double> st_rates(opts.stretch ? S : 0);
+    std::vector<uint32_t> st_from(opts.stretch && opts.stretch_spec.shift_to_hz ? S : 0);
+    for (uint32_t s = 0; s < S && opts.stretch; ++s) {
+      const size_t i = g.pending[s]->index;
+      st_rates[s] = opts.stretch_rates[i];
+      uint64_t len = vsyn_stretch_num_samples(o.frames[s], st_rates[s]);
+      pl = std::max(pl, len);
+      if (!st_from.empty()) {
+        st_from[s] = opts.stretch_from_hz[i];
+        pl = std::max(pl, vsyn_resample_num_frames(st_from[s], opts.stretch_spec.shift_to_hz, len));
+      }
+    }
     if (opts.pcm_s16) CHECK_ERR(g.pcm16.ensure((size_t)S * pl));
     else if (!opts.intervals_only) CHECK_ERR(g.pcm.ensure((size_t)S * pl));  // (intervals_only: no PCM comes back)
     const char* err = nullptr;
@@ -549,19 +563,33 @@ struct Feeder {
     std::vector<float> peaks(S, 0.f);
     const int fmt = opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32;
     void* out = opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p;
-    if (opts.effect) {  // the chain form with the effect stage: a gate or none, the effect, the normaliser or none, conditioning or none
+    if (opts.effect || opts.stretch) {  // the chain form with the effect or the stretch stage: a gate or none, the stage, the normaliser or none, conditioning or none
       std::vector<double> refs(S);
       const bool gated = opts.split || opts.trim;
       if (opts.split) size_intervals(S, o);
       if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);
       if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
-      const int rc = vsyn_pcm_chain_effects_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.effect_spec,
-                                                 opts.loudness_norm ? &opts.loudness_spec : nullptr, trim_cond(), S, rates.data(),
-                                                 opts.resample_rate, fmt, out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr,
-                                                 opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride,
-                                                 peaks.data(), refs.data(), opts.loudness_norm ? o.loud.data() : nullptr, &err);
-      if (rc != VSYN_OK) return OkOrError(std::string("GPU effects layer: ") + (err ? err : "effect failed"));
-      if (gated) {
+      const int rc =
+          opts.stretch
+              ? vsyn_pcm_chain_stretch_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.effect ? &opts.effect_spec : nullptr,
+                                            &opts.stretch_spec, st_rates.data(), st_from.empty() ? nullptr : st_from.data(),
+                                            opts.loudness_norm ? &opts.loudness_spec : nullptr, trim_cond(), S, rates.data(), opts.resample_rate, fmt,
+                                            out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
+                                            opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
+                                            opts.loudness_norm ? o.loud.data() : nullptr, &err)
+              : vsyn_pcm_chain_effects_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.effect_spec,
+                                            opts.loudness_norm ? &opts.loudness_spec : nullptr, trim_cond(), S, rates.data(), opts.resample_rate, fmt,
+                                            out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
+                                            opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
+                                            opts.loudness_norm ? o.loud.data() : nullptr, &err);
+      if (rc != VSYN_OK) return OkOrError(std::string(opts.stretch ? "GPU stretch layer: " : "GPU effects layer: ") + (err ? err : "effect failed"));
+      if (opts.stretch) {  // the stage's frames: the one step behind the gate that changes the count
+        for (uint32_t s = 0; s < S; ++s) {
+          CHECK(got[s] <= pl);
+          o.frames[s] = got[s];
+        }
+        if (gated) refuse_refs(refs, o);
+      } else if (gated) {
         for (uint32_t s = 0; s < S; ++s) {
           CHECK(got[s] <= o.frames[s]);
           o.frames[s] = got[s];
@@ -1327,6 +1355,22 @@ bool effect_spec_ok(const vsyn_pcm_effect* e) {
          p.margin_p >= 1.0;
 }
 
+// What a run with the stretch stage asks of its spec and its per-file arrays (include/vorbis_synth_hip.h, "PCM stretch", step 9):
+// empty, or why the call is refused.
+std::string stretch_refusal(const vsyn_pcm_stretch* e, size_t num_files, const double* rates, const uint32_t* from_hz) {
+  if (!(e->n_fft >= 16 && e->n_fft <= 8192 && !(e->n_fft & (e->n_fft - 1u)) && e->hop_length >= 1 && e->win_length >= 1 && e->win_length <= e->n_fft &&
+        !(e->options & ~VSYN_STRETCH_FIX_LENGTH) && !e->reserved))
+    return "invalid stretch spec (n_fft a power of two in [16, 8192], hop_length >= 1, win_length in [1, n_fft], known options)";
+  if (num_files && (!rates || (e->shift_to_hz && !from_hz))) return "NULL per-file rates";
+  for (size_t i = 0; i < num_files; ++i) {
+    if (!std::isfinite(rates[i]) || !(rates[i] > 0.0)) return "file " + std::to_string(i) + ": the rate is not a finite number above 0";
+    if (e->shift_to_hz && vsyn_resample_num_frames(from_hz[i], e->shift_to_hz, 1) == 0)
+      return "file " + std::to_string(i) + ": resample: " + std::to_string(from_hz[i]) + " -> " + std::to_string(e->shift_to_hz) +
+             " Hz is a pair the resampler refuses (a rate of 0, or max(up, down) above " + std::to_string(VSYN_RESAMPLE_MAX_M) + ")";
+  }
+  return std::string();
+}
+
 // ogg_vorbis_spectral_corpus (target_rate 0) and ogg_vorbis_spectral_corpus_sr; fn: the entry point, for its refusal text.
 int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
@@ -1458,7 +1502,8 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
                uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                double* stats_out, const char** error_out, const vsyn_pcm_trim* split = nullptr, bool intervals_only = false,
                const SplitOuts* so = nullptr, const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr,
-               const vsyn_pcm_effect* effect = nullptr);
+               const vsyn_pcm_effect* effect = nullptr, const vsyn_pcm_stretch* stretch = nullptr, const double* stretch_rates = nullptr,
+               const uint32_t* shift_from_hz = nullptr);
 
 }  // namespace
 
@@ -1537,7 +1582,8 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
                uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
                uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                double* stats_out, const char** error_out, const vsyn_pcm_trim* split, bool intervals_only, const SplitOuts* so,
-               const vsyn_loudness_spec* loud, vsyn_loudness_record* records_out, const vsyn_pcm_effect* effect) {
+               const vsyn_loudness_spec* loud, vsyn_loudness_record* records_out, const vsyn_pcm_effect* effect, const vsyn_pcm_stretch* stretch,
+               const double* stretch_rates, const uint32_t* shift_from_hz) {
   if (so) so->begin(num_files);
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
     return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
@@ -1574,6 +1620,16 @@ int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files
                          error_out);
     opts.condition = opts.effect = true;  // one mono plane per file
     opts.effect_spec = *effect;
+  }
+  if (stretch) {
+    if (std::string why = stretch_refusal(stretch, num_files, stretch_rates, shift_from_hz); !why.empty() || intervals_only || effect)
+      return refuse_call(pcm_out, num_files,
+                         "ogg_vorbis_pcm_corpus_stretch: " + (effect ? std::string("a stretch and an hpss effect in one call are not built") : why),
+                         error_out);
+    opts.condition = opts.stretch = true;  // one mono plane per file
+    opts.stretch_spec = *stretch;
+    opts.stretch_rates = stretch_rates;
+    opts.stretch_from_hz = shift_from_hz;
   }
   const int rc = malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
                                [&](size_t i, const CorpusFileResult& res, bool bad) {
@@ -1653,6 +1709,23 @@ extern "C" int ogg_vorbis_pcm_corpus_effects(const uint8_t* const* datas, const 
   return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
                     frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
                     &so, loud, records_out, effect);
+}
+
+extern "C" int ogg_vorbis_pcm_corpus_stretch(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                             uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                             const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
+                                             const vsyn_pcm_stretch* stretch, const double* stretch_rates, const uint32_t* shift_from_hz,
+                                             const vsyn_loudness_spec* loud, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out,
+                                             uint32_t* rate_out, uint64_t* bounds_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
+                                             vsyn_loudness_record* records_out, uint8_t* ok_out, const char** error_out_per_file,
+                                             double* stats_out, const char** error_out) {
+  SplitOuts so;
+  so.intervals_out = intervals_out;
+  so.intervals_count_out = intervals_count_out;
+  const bool split = gate && gate_is_split;
+  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
+                    frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
+                    &so, loud, records_out, effect, stretch, stretch_rates, shift_from_hz);
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,

@@ -150,6 +150,14 @@ struct CorpusOptions {
   // The default is off: today's output and today's entry points.
   bool effect = false;
   vsyn_pcm_effect effect_spec = {2048u, 512u, 2048u, 0u, {31u, 31u, VSYN_HPSS_HARMONIC, VSYN_HPSS_OUT_COMPONENT, 2.0, 1.0, 1.0}};
+  // stretch (a PCM run with condition): each file's mono plane is time-stretched at its own rate, and with stretch_spec.shift_to_hz
+  // resampled behind that (a pitch shift), in the effect's slot (include/vorbis_synth_hip.h, "PCM stretch"), through
+  // vsyn_pcm_chain_stretch_host. stretch_rates and stretch_from_hz (the latter only with a shift) hold one value per FILE of the
+  // call, indexed by the file's index, and must outlive the run. The default is off: today's output and today's entry points.
+  bool stretch = false;
+  vsyn_pcm_stretch stretch_spec = {2048u, 512u, 2048u, 0u, 0u, 0u};
+  const double* stretch_rates = nullptr;
+  const uint32_t* stretch_from_hz = nullptr;
   // rhythm (a spectral run of a kind with 1 to 256 columns): the rows stay on the device and go through the onset stage and what
   // rhythm_spec.output selects behind it (include/vorbis_synth_hip.h, "rhythm"), through vsyn_pcm_chain_rhythm_host; a file's "rows"
   // are then that output's words (1 column, win_length columns, or 2 for the mean's float64 values). A spec the stages refuse is
@@ -306,6 +314,18 @@ int ogg_vorbis_pcm_corpus_effects(const uint8_t* const* datas, const size_t* len
                                   const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect, const vsyn_loudness_spec* loud,
                                   void** pcm_out, uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out,
                                   uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                                  const char** error_out_per_file, double* stats_out, const char** error_out);
+// ogg_vorbis_pcm_corpus_effects with the stretch stage in the effect's slot (stretch != NULL: CorpusOptions::stretch): one mono plane
+// per file, time-stretched at stretch_rates[i] and, with stretch->shift_to_hz, resampled behind that from shift_from_hz[i] (both
+// arrays hold one value per file of the call; shift_from_hz may be NULL without a shift). frames_out[i] is what the stage delivers.
+// A spec, a rate or a resampling pair the stage refuses refuses the call by name before anything runs, as does an effect beside
+// the stretch. stretch = NULL is ogg_vorbis_pcm_corpus_effects.
+int ogg_vorbis_pcm_corpus_stretch(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                  uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
+                                  const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect, const vsyn_pcm_stretch* stretch,
+                                  const double* stretch_rates, const uint32_t* shift_from_hz, const vsyn_loudness_spec* loud, void** pcm_out,
+                                  uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint32_t** intervals_out,
+                                  uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                   const char** error_out_per_file, double* stats_out, const char** error_out);
 int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,

@@ -170,6 +170,76 @@ def effect_spec(hpss=None, hpss_kernel_size=31, hpss_power=2.0, hpss_margin=1.0,
     return PcmEffect(fr.n_fft, fr.hop_length, fr.win_length, 0, hp)
 
 
+STRETCH_FIX_LENGTH = 1        # VSYN_STRETCH_FIX_LENGTH
+RESAMPLE_MAX_M = 65536        # VSYN_RESAMPLE_MAX_M
+
+
+def _per_file(name, v, n, error):
+    """v, one real number or a sequence of n of them, as a float64 array [n]."""
+    if isinstance(v, (bool, np.bool_)):
+        raise error("%s must be a number or one number per file, got %r" % (name, v))
+    if isinstance(v, (int, float, np.integer, np.floating)):
+        return np.full(n, float(v), np.float64)
+    try:
+        vals = list(v)
+    except TypeError:
+        raise error("%s must be a number or one number per file, got %r" % (name, v)) from None
+    if len(vals) != n:
+        raise error("%s has %d values for %d files" % (name, len(vals), n))
+    for x in vals:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise error("%s must hold numbers, got %r" % (name, x))
+    return np.array([float(x) for x in vals], np.float64)
+
+
+def stretch_args(n_files, time_stretch=None, pitch_shift=None, pitch_bins_per_octave=12, stretch_n_fft=2048, stretch_hop_length=None,
+                 stretch_win_length=None, sr=None, error=PcmError):
+    """Checks the stretch arguments (include/vorbis_synth_hip.h, "PCM stretch", steps 6 and 9) and returns (binding.PcmStretch, rates
+    float64 [n_files], shift_from_hz uint32 [n_files] or None), or None with both time_stretch and pitch_shift None: the stage is off
+    and its other arguments are not looked at. time_stretch: a finite rate above 0, or one per file (above 1 shortens). pitch_shift:
+    finite semitone steps of pitch_bins_per_octave, or one per file; needs sr (an integer: every file at one rate), keeps each
+    file's length, and the pair (rint(sr / rate), sr) must be one the resampler takes. The two exclude each other."""
+    if time_stretch is None and pitch_shift is None:
+        return None
+    if time_stretch is not None and pitch_shift is not None:
+        raise error("time_stretch and pitch_shift exclude each other in one call")
+    from . import spectral
+    from .binding import PcmStretch
+    try:
+        n_fft = spectral._int("stretch_n_fft", stretch_n_fft)
+        if not (16 <= n_fft <= spectral.MAX_N_FFT and n_fft & (n_fft - 1) == 0):
+            raise error("stretch_n_fft must be a power of two in [16, %d], got %d" % (spectral.MAX_N_FFT, n_fft))
+        fr = spectral.spectral_spec("stft", n_fft, n_fft // 4 if stretch_hop_length is None else stretch_hop_length, stretch_win_length)
+    except spectral.SpectralError as e:
+        msg = str(e)  # (spectral_spec names its own arguments: hop_length, win_length)
+        raise error(msg if msg.startswith("stretch") else "stretch_" + msg) from None
+    if time_stretch is not None:
+        rates = _per_file("time_stretch", time_stretch, n_files, error)
+        for r in rates:
+            if not (math.isfinite(r) and r > 0.0):
+                raise error("time_stretch must be a finite rate above 0, got %r" % (float(r),))
+        return PcmStretch(fr.n_fft, fr.hop_length, fr.win_length, 0, 0, 0), rates, None
+    steps = _per_file("pitch_shift", pitch_shift, n_files, error)
+    if isinstance(pitch_bins_per_octave, (bool, np.bool_)) or not isinstance(pitch_bins_per_octave, (int, np.integer)) or pitch_bins_per_octave < 1:
+        raise error("pitch_bins_per_octave must be an integer >= 1, got %r" % (pitch_bins_per_octave,))
+    if sr is None:
+        raise error("pitch_shift needs sr=: every file is resampled to one rate first, and back to it behind the stretch")
+    rates, from_hz = np.zeros(n_files, np.float64), np.zeros(n_files, np.uint32)
+    for i, st in enumerate(steps):
+        r = 2.0 ** (-float(st) / int(pitch_bins_per_octave)) if math.isfinite(st) else float("nan")
+        if not (math.isfinite(r) and r > 0.0):
+            raise error("pitch_shift must be a finite number of steps whose rate 2^(-steps / bins) is a finite rate above 0, got %r" % (float(st),))
+        hz = float(np.rint(int(sr) / r))
+        if not 1.0 <= hz <= MAX_RATE:
+            raise error("pitch_shift %r: the rate %g Hz to resample from is outside [1, %d]" % (float(st), hz, MAX_RATE))
+        g = math.gcd(int(hz), int(sr))
+        if max(int(hz), int(sr)) // g > RESAMPLE_MAX_M:
+            raise error("pitch_shift %r: resample: %d -> %d Hz reduces to %d / %d, above the limit max(up, down) <= %d"
+                        % (float(st), int(hz), int(sr), int(sr) // g, int(hz) // g, RESAMPLE_MAX_M))
+        rates[i], from_hz[i] = r, int(hz)
+    return PcmStretch(fr.n_fft, fr.hop_length, fr.win_length, STRETCH_FIX_LENGTH, int(sr), 0), rates, from_hz
+
+
 _load = _corpus.load
 
 
@@ -177,7 +247,8 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
                   stats=None, mono=False, peak_normalize=False, preemphasis=None, trim_db=None, trim_frame_length=2048, trim_hop_length=512,
                   trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None, loudness_normalize=None,
                   loudness=None, hpss=None, hpss_kernel_size=31, hpss_power=2.0, hpss_margin=1.0, hpss_n_fft=2048, hpss_hop_length=None,
-                  hpss_win_length=None):
+                  hpss_win_length=None, time_stretch=None, pitch_shift=None, pitch_bins_per_octave=12, stretch_n_fft=2048, stretch_hop_length=None,
+                  stretch_win_length=None):
     """PCM of many Ogg Vorbis files in one corpus run: a list of (pcm, sr) tuples. pcm is float32 (channels, frames), or int16
     (frames, channels) with ov_read's conversion; sr is the rate of the returned PCM. sr=None keeps each file's own rate (the
     PCM is bit for bit that of ogg_vorbis_decode_corpus); an integer resamples every file to it on the GPU. errors="raise": the
@@ -208,7 +279,16 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     win_length=hpss_win_length) computes it (percussive likewise): STFT, the soft mask of decompose.hpss on its magnitude, the masked
     inverse STFT to the signal's own length, all on the device. hpss_n_fft is a power of two in [16, 8192]; hpss_hop_length defaults
     to hpss_n_fft // 4 and hpss_win_length to hpss_n_fft; hpss_kernel_size and hpss_margin are one value or a (harmonic, percussive)
-    pair. With hpss=None nothing is launched and the call takes the entry points it took without the argument."""
+    pair. With hpss=None nothing is launched and the call takes the entry points it took without the argument.
+    time_stretch=r (a finite rate above 0, or one per file; needs mono=True, excludes hpss): in the same place the mono signal is
+    time-stretched as librosa.effects.time_stretch(y, rate=r, n_fft=stretch_n_fft, hop_length=stretch_hop_length,
+    win_length=stretch_win_length) does: STFT, phase vocoder, inverse STFT to round(len(y) / r) samples, all on the device. r above 1
+    shortens. pitch_shift=s (semitone steps of pitch_bins_per_octave, or one per file; needs mono=True and sr=, excludes
+    time_stretch and hpss) shifts the pitch and keeps the length, as librosa.effects.pitch_shift(y, sr=sr, n_steps=s,
+    bins_per_octave=pitch_bins_per_octave) does: the stretch at rate 2^(-s / bins), then resampled from rint(sr / rate) Hz back to sr
+    and cut or zero-padded to len(y). librosa resamples from the unrounded sr / rate; the whole-Hz rate moves the pitch by at most
+    0.5 / (sr / rate) relative. A pair of rates the resampler refuses raises by name before anything runs. With both None nothing is
+    launched and the call takes the entry points it took without the arguments."""
     _corpus.check_errors(errors)
     target = check_sr(sr)
     name = _format(dtype)
@@ -229,8 +309,13 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
     effect = effect_spec(hpss, hpss_kernel_size, hpss_power, hpss_margin, hpss_n_fft, hpss_hop_length, hpss_win_length)
     if not mono and effect is not None:
         raise PcmError("hpss acts on the mono signal: pass mono=True")
-    lib = _load()
     n = len(list_of_bytes)
+    stretch = stretch_args(n, time_stretch, pitch_shift, pitch_bins_per_octave, stretch_n_fft, stretch_hop_length, stretch_win_length, sr)
+    if stretch is not None and not mono:
+        raise PcmError("time_stretch and pitch_shift act on the mono signal: pass mono=True")
+    if stretch is not None and effect is not None:
+        raise PcmError("time_stretch / pitch_shift and hpss exclude each other: their composition is not built")
+    lib = _load()
     frames = np.zeros(n, np.uint64)
     chans = np.zeros(n, np.uint32)
     rates = np.zeros(n, np.uint32)
@@ -244,13 +329,18 @@ def get_pcm_batch(list_of_bytes, sr=None, dtype="float32", threads=0, feeders=0,
         return _corpus.copy_into(a, p), int(rates[i])
 
     args = (threads, feeders, files_per_submit, device, target, FORMATS[name])
-    if loud is not None or effect is not None:  # the entries with every stage's spec (NULL: off); the effect has one of its own
+    if loud is not None or effect is not None or stretch is not None:  # the entries with every stage's spec (NULL: off); the effect and the stretch have their own
         from .binding import LOUDNESS_RECORD_DTYPE
         ib = _corpus.IntervalBuffers(lib, n)
         bounds, records = np.zeros((max(n, 1), 2), np.uint64), np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
         gate = split if split is not None else trim
         head = (C.byref(cond) if cond.options else None, None if gate is None else C.byref(gate), int(split is not None))
-        if effect is None:
+        if stretch is not None:
+            st_spec, st_rates, st_from = stretch
+            fn, specs = lib.ogg_vorbis_pcm_corpus_stretch, (None, C.byref(st_spec), st_rates.ctypes.data,
+                                                            None if st_from is None else st_from.ctypes.data,
+                                                            None if loud is None else C.byref(loud))
+        elif effect is None:
             fn, specs = lib.ogg_vorbis_pcm_corpus_loud, (C.byref(loud),)
         else:
             fn, specs = lib.ogg_vorbis_pcm_corpus_effects, (C.byref(effect), None if loud is None else C.byref(loud))
