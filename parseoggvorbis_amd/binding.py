@@ -928,9 +928,8 @@ class Synth:
         _check(rc, err, (VSYN_OK, VSYN_ERR_STREAM))
         return dict(rc=rc, records=rec[:S], seg_blocks=nb[:S], z=None if z is None else z[:int(nb[:S].sum())], flags=st.flags)
 
-    def pcm_chain_host(self, gate, gate_is_split, loud, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
-        """vsyn_pcm_chain_host over the last submit's segments (gate / loud / cond may be None, but not all three): returns dict(pcm
-        [S][stride], frames [S], bounds [S][2], counts [S], intervals, peaks [S], refs [S], records [S])."""
+    def _chain_pcm_host(self, fn, gate, gate_is_split, stages, cond, num_segments, in_rates, out_rate, fmt):
+        """The PCM chain entries: stages are the arguments between gate_is_split and cond, as fn takes them."""
         S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "bounds", "counts", "peaks", "refs")
         rec, iv = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), []
 
@@ -938,43 +937,29 @@ class Synth:
             ivs = self._max_intervals(gate, t_max) if gate is not None and gate_is_split else 1
             iv.append(np.zeros((max(1, S), ivs, 2), np.uint32))
             return [o["bounds"], o["counts"], iv[0], ivs, o["peaks"], o["refs"], rec]
-        out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_host,
-                                     (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), S, _ptr(rates), out_rate, fmt), S, fmt, None, outs)
+        out, frames = self._pcm_host(fn, (_ref(gate), 1 if gate_is_split else 0, *stages, _ref(cond), S, _ptr(rates), out_rate, fmt), S, fmt, None, outs)
         return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
+
+    def pcm_chain_host(self, gate, gate_is_split, loud, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
+        """vsyn_pcm_chain_host over the last submit's segments (gate / loud / cond may be None, but not all three): returns dict(pcm
+        [S][stride], frames [S], bounds [S][2], counts [S], intervals, peaks [S], refs [S], records [S])."""
+        return self._chain_pcm_host(self.lib.vsyn_pcm_chain_host, gate, gate_is_split, (_ref(loud),), cond, num_segments, in_rates, out_rate, fmt)
 
     def pcm_chain_effects_host(self, gate, gate_is_split, effect, loud, cond, num_segments, in_rates=None, out_rate=0, fmt=VSYN_PCM_F32):
         """vsyn_pcm_chain_effects_host over the last submit's segments (every spec may be None, but not all four): returns what
         pcm_chain_host returns."""
-        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "bounds", "counts", "peaks", "refs")
-        rec, iv = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), []
-
-        def outs(t_max):
-            ivs = self._max_intervals(gate, t_max) if gate is not None and gate_is_split else 1
-            iv.append(np.zeros((max(1, S), ivs, 2), np.uint32))
-            return [o["bounds"], o["counts"], iv[0], ivs, o["peaks"], o["refs"], rec]
-        out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_effects_host,
-                                     (_ref(gate), 1 if gate_is_split else 0, _ref(effect), _ref(loud), _ref(cond), S, _ptr(rates), out_rate, fmt), S,
-                                     fmt, None, outs)
-        return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
+        return self._chain_pcm_host(self.lib.vsyn_pcm_chain_effects_host, gate, gate_is_split, (_ref(effect), _ref(loud)), cond, num_segments,
+                                    in_rates, out_rate, fmt)
 
     def pcm_chain_stretch_host(self, gate, gate_is_split, effect, stretch, stretch_rates, shift_from_hz, loud, cond, num_segments, in_rates=None,
                                out_rate=0, fmt=VSYN_PCM_F32):
         """vsyn_pcm_chain_stretch_host over the last submit's segments (stretch_rates: one float per segment; shift_from_hz: None
         without a shift): returns what pcm_chain_host returns, frames being what the stretch delivers and the stride the largest
         length on the way."""
-        S, rates, o = num_segments, _rates(in_rates), _per_segment(num_segments, "bounds", "counts", "peaks", "refs")
-        rec, iv = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), []
         sr = None if stretch_rates is None else np.ascontiguousarray(stretch_rates, dtype=np.float64)
         hz = None if shift_from_hz is None else np.ascontiguousarray(shift_from_hz, dtype=np.uint32)
-
-        def outs(t_max):
-            ivs = self._max_intervals(gate, t_max) if gate is not None and gate_is_split else 1
-            iv.append(np.zeros((max(1, S), ivs, 2), np.uint32))
-            return [o["bounds"], o["counts"], iv[0], ivs, o["peaks"], o["refs"], rec]
-        out, frames = self._pcm_host(self.lib.vsyn_pcm_chain_stretch_host,
-                                     (_ref(gate), 1 if gate_is_split else 0, _ref(effect), _ref(stretch), _ptr(sr), _ptr(hz), _ref(loud), _ref(cond),
-                                      S, _ptr(rates), out_rate, fmt), S, fmt, None, outs)
-        return dict(pcm=out, frames=frames, intervals=self._intervals(o["counts"], iv[0], S), records=rec[:S], **{k: v[:S] for k, v in o.items()})
+        return self._chain_pcm_host(self.lib.vsyn_pcm_chain_stretch_host, gate, gate_is_split,
+                                    (_ref(effect), _ref(stretch), _ptr(sr), _ptr(hz), _ref(loud)), cond, num_segments, in_rates, out_rate, fmt)
 
     def pcm_chain_spectral_host(self, gate, gate_is_split, loud, cond, spec, pcen, post, in_rates, out_rate=0):
         """vsyn_pcm_chain_spectral_host over the last submit's segments (gate / loud / cond / pcen / post may be None): returns what

@@ -1513,6 +1513,14 @@ struct Gate {
   double* refs;
 };
 
+// The gate as the exported entries name it: a trim with its bounds, or a split (joined) with its counts and intervals. gate = NULL:
+// a chain without a gate.
+static Gate make_gate(const vsyn_pcm_trim* gate, bool gate_is_split, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out,
+                      uint64_t intervals_stride, double* refs_out) {
+  return gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
+                       : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
+}
+
 // The specs of the stages a chain has (gate, cond: NULL, out_rate: 0 when it has none), in the order every entry checks them.
 static int chain_check(const Gate* gate, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, uint32_t out_rate, const char** err) {
   if (gate)
@@ -1634,6 +1642,29 @@ struct Stretch {
   const uint32_t* from_hz;   // [S], NULL without a shift
 };
 
+// One chain behind the last host submit, as both chain bodies (pcm_out_host, spectral_host) take it. A stage whose spec is NULL is
+// off, out_rate 0 is no resampling, and an output that is NULL is not wanted.
+struct Chain {
+  uint32_t S;             // the call: the last submit's segments, their rates, and the rate they are resampled to first
+  const uint32_t* rates;
+  uint32_t out_rate;
+  Gate gate;              // the PCM stages, in the order they run
+  const vsyn_pcm_effect* effect;
+  Stretch stretch;
+  const vsyn_loudness_spec* loud;
+  const vsyn_pcm_cond* cond;
+  const vsyn_spectral_spec* spec;  // the row stages of spectral_host, in the order they run (post and rhythm exclude each other)
+  const vsyn_spectral_chroma* chroma;
+  const vsyn_spectral_hpss* hpss;
+  const vsyn_spectral_pcen* pcen;
+  const vsyn_spectral_post* post;
+  const vsyn_rhythm_spec* rhythm;
+  uint64_t* frames_out;   // the per-segment outputs [S]: the frames behind the gate (and the stretch), conditioning's peaks, the
+  float* peaks_out;       // normaliser's records, the rhythm stages' refusal words
+  vsyn_loudness_record* records_out;
+  uint32_t* refused_out;
+};
+
 // the stretched (and shifted) mono downmix of the view (T[g] frames, host) into h->st's mono plane, T[g] replaced by what the stage
 // delivers; read on as the gate's plane is, with those frames
 static int step_stretch(vsyn_handle* h, uint32_t S, const Stretch& x, uint64_t* T, uint64_t plane, bool clear, PcmView* v, const char** err) {
@@ -1697,30 +1728,31 @@ static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format
   return VSYN_OK;
 }
 
-// The PCM host forms (vsyn_pcm_resample_host, vsyn_pcm_condition_host, vsyn_pcm_trim_host, vsyn_pcm_split_host): the stages present
-// (gate, cond: NULL, out_rate: 0 for none), the last one into a plane of the caller's stride, the ones in front of it into planes
-// as long as the longest segment; that plane to out, and the frames behind the gate to frames_out.
-static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* rates, uint32_t out_rate, int format,
-                        void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err,
-                        const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr,
-                        const vsyn_pcm_effect* effect = nullptr, const Stretch* stretch = nullptr) {
-  if (effect)
-    if (int rc = effect_check(effect, err)) return rc;
+// The PCM host forms: the steps of c that are present, in the one order they run in; the last of them into a plane of the caller's
+// stride, the ones in front of it into planes as long as the longest segment; that plane to out, and the frames behind the gate
+// (and the stretch) to c.frames_out.
+static int pcm_out_host(vsyn_handle* h, const Chain& c, int format, void* out, uint64_t out_stride_frames, const char** err) {
+  const uint32_t S = c.S;
+  uint64_t* frames_out = c.frames_out;
+  const Gate* gate = c.gate.spec ? &c.gate : nullptr;
+  const Stretch* stretch = c.stretch.spec ? &c.stretch : nullptr;
+  if (c.effect)
+    if (int rc = effect_check(c.effect, err)) return rc;
   if (stretch) {
-    if (effect) return fail(err, VSYN_ERR_INVALID, "a stretch and an hpss effect in one chain call: their composition is not built");
+    if (c.effect) return fail(err, VSYN_ERR_INVALID, "a stretch and an hpss effect in one chain call: their composition is not built");
     if (int rc = stretch_check_call(stretch->spec, S, stretch->rates, stretch->from_hz, err)) return rc;
   }
-  if (loud)
-    if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
-  if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
+  if (c.loud)
+    if (int rc = chain_loud_check(c.loud, c.cond, S, c.rates, err)) return rc;
+  if (int rc = chain_check(gate, c.cond, S, c.rates, c.out_rate, err)) return rc;
   if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return fail(err, VSYN_ERR_INVALID, "unknown PCM format %d", format);
   if (S && !frames_out) return fail(err, VSYN_ERR_INVALID, "frames_out is NULL");
-  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
-  if (records_out) memset(records_out, 0, sizeof(vsyn_loudness_record) * S);
+  if (c.peaks_out) memset(c.peaks_out, 0, sizeof(float) * S);
+  if (c.records_out) memset(c.records_out, 0, sizeof(vsyn_loudness_record) * S);
   // the lock covers the whole call: the stages' workspaces are the handle's, and the PCM must stay that of the last submit
   std::lock_guard<std::mutex> lk(h->mu);
   uint64_t t_max;
-  if (int rc = last_submit_frames(h, S, rates, out_rate, frames_out, &t_max, err)) return rc;
+  if (int rc = last_submit_frames(h, S, c.rates, c.out_rate, frames_out, &t_max, err)) return rc;
   const uint64_t t_in = t_max;  // the longest segment in front of the stretch; t_max: the longest anywhere in the chain
   std::vector<uint64_t> T_in(frames_out, frames_out + S);
   if (stretch) {  // every plane holds the largest of the input, the stretched, the resampled and the delivered lengths
@@ -1742,45 +1774,49 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
     g.frames = joined.data();
     g.bounds = bounds.data();
   }
+  // The steps in the order they run in. The last one present delivers: it alone writes a plane of the caller's stride, cleared
+  // first when that plane goes out as float32, and its int16 scratch is the call's. A new stage is a name here, at its place.
+  enum { RESAMPLE, GATE, EFFECT, STRETCH, LOUDNESS, CONDITION, STEPS };
+  const bool present[STEPS] = {c.out_rate != 0, gate != nullptr, c.effect != nullptr, stretch != nullptr, c.loud != nullptr, c.cond != nullptr};
+  int last = 0;
+  for (int step = 0; step < STEPS; ++step)
+    if (present[step]) last = step;
   const bool f32 = format == VSYN_PCM_F32;
   const uint64_t inner = std::max<uint64_t>(t_max, 1);
+  const auto plane = [&](int step) { return step == last ? out_stride_frames : inner; };
+  const auto clear = [&](int step) { return f32 && step == last; };
   PcmView v = last_submit_view(h);
-  DevBuf<int16_t>* s16 = &h->rs.s16;  // the last stage's
-  if (out_rate)
-    if (int rc = step_resample(h, S, rates, out_rate, gate || effect || stretch || cond || loud ? inner : out_stride_frames,
-                               f32 && !gate && !effect && !stretch && !cond && !loud, &v, err))
-      return rc;
+  DevBuf<int16_t>* s16 = &h->rs.s16;
+  if (c.out_rate)
+    if (int rc = step_resample(h, S, c.rates, c.out_rate, plane(RESAMPLE), clear(RESAMPLE), &v, err)) return rc;
   if (gate) {
-    if (int rc = step_gate(h, S, g, effect || stretch || cond || loud ? inner : out_stride_frames, t_in, f32 && !effect && !stretch && !cond && !loud,
-                           &v, err))
-      return rc;
+    if (int rc = step_gate(h, S, g, plane(GATE), t_in, clear(GATE), &v, err)) return rc;
     s16 = g.split ? &h->sl.e.s16 : &h->tr.s16;
   }
   // the effect's and the loudness stage's tables need each segment's frames: behind a gate the chain waits here for the gate's read-backs
   std::vector<uint64_t> T;
-  if (effect || stretch || loud) {
+  if (c.effect || stretch || c.loud) {
     T = T_in;
     if (gate) {
       HIPCHK(hipStreamSynchronize(h->host_stream));
       for (uint32_t s = 0; s < S; ++s) T[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
     }
   }
-  if (effect) {
-    if (int rc = step_effects(h, S, effect, rates, T.data(), cond || loud ? inner : out_stride_frames, f32 && !cond && !loud, &v, err)) return rc;
+  if (c.effect) {
+    if (int rc = step_effects(h, S, c.effect, c.rates, T.data(), plane(EFFECT), clear(EFFECT), &v, err)) return rc;
     s16 = &h->ef.s16;
   }
   if (stretch) {  // T becomes the stage's frames: the steps behind it see those
-    const Stretch& x = *stretch;
-    if (int rc = step_stretch(h, S, x, T.data(), cond || loud ? inner : out_stride_frames, f32 && !cond && !loud, &v, err)) return rc;
+    if (int rc = step_stretch(h, S, *stretch, T.data(), plane(STRETCH), clear(STRETCH), &v, err)) return rc;
     s16 = &h->st.s16;
   }
-  if (loud) {
-    const std::vector<uint32_t> ld_rates = stage_rates(S, rates, out_rate);
-    if (int rc = step_loudness(h, S, loud, ld_rates.data(), T.data(), cond ? inner : out_stride_frames, f32 && !cond, records_out, &v, err)) return rc;
+  if (c.loud) {
+    const std::vector<uint32_t> ld_rates = stage_rates(S, c.rates, c.out_rate);
+    if (int rc = step_loudness(h, S, c.loud, ld_rates.data(), T.data(), plane(LOUDNESS), clear(LOUDNESS), c.records_out, &v, err)) return rc;
     s16 = &h->ld.s16;
   }
-  if (cond) {
-    if (int rc = step_condition(h, S, cond, out_stride_frames, t_max, f32, peaks_out, &v, err)) return rc;
+  if (c.cond) {
+    if (int rc = step_condition(h, S, c.cond, plane(CONDITION), t_max, clear(CONDITION), c.peaks_out, &v, err)) return rc;
     s16 = &h->cd.s16;
   }
   if (int rc = pcm_copy_out(h, v, S, format, *s16, out, err)) return rc;
@@ -1792,41 +1828,39 @@ static int pcm_out_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* c
   return VSYN_OK;
 }
 
-// The end of a spectral host form: the rows of the view's PCM on the host stream (hpss != NULL: through the HPSS stage into its
-// workspace, where the later stages find them; pcen != NULL: through the PCEN stage in place;
-// post != NULL: on to the post stage in their place, and its wider rows come back), copied to rows, then the call's wait and
-// status. seg_rows, f_max and total are the host's row counts. Caller holds h->mu.
-static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S,
-                             const uint32_t* spec_rates,
-                             const PcmView& v, const uint64_t* seg_rows, uint64_t f_max, uint64_t total, float* rows, vsyn_status* status,
-                             const char** err, const vsyn_spectral_chroma* chroma, const vsyn_spectral_hpss* hpss,
-                             const vsyn_rhythm_spec* rhythm = nullptr, uint64_t rows_capacity = 0, uint64_t* seg_rows_out = nullptr,
-                             uint32_t* refused_out = nullptr) {
+// The end of a spectral host form: the rows of the view's PCM on the host stream, through the row stages of c (hpss: through the
+// HPSS stage into its workspace, where the later stages find them; pcen: through the PCEN stage in place; rhythm: the rows stay on
+// the device, and seg_rows becomes the selected output's; post, which the caller has set to NULL when it is off: on to the post
+// stage in their place, and its wider rows come back), copied to rows, then the call's wait and status. spec_rates are the rates
+// the rows are computed at (0 skips a segment); seg_rows, f_max and total are the host's row counts. Caller holds h->mu.
+static int spectral_rows_out(vsyn_handle* h, const Chain& c, const uint32_t* spec_rates, const PcmView& v, uint64_t* seg_rows, uint64_t f_max,
+                             uint64_t total, float* rows, uint64_t rows_capacity, vsyn_status* status, const char** err) {
   hipStream_t hs = h->host_stream;
-  const uint64_t D = spec_dim(spec, chroma);
-  if (hpss)
-    if (int rc = hpss_check_call(hpss, (uint32_t)D, S, seg_rows, err)) return rc;
+  const uint32_t S = c.S;
+  const uint64_t D = spec_dim(c.spec, c.chroma);
+  if (c.hpss)
+    if (int rc = hpss_check_call(c.hpss, (uint32_t)D, S, seg_rows, err)) return rc;
   HIPCHK(h->sp.rows.ensure(total * D + 1));
-  int rc = spec_launch(h->sp, h->device, spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err,
-                       chroma);
+  int rc = spec_launch(h->sp, h->device, c.spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err,
+                       c.chroma);
   if (rc) return rc;
   float* cur = h->sp.rows.p;  // where the rows are
-  if (hpss) {
+  if (c.hpss) {
     HIPCHK(h->hp.rows.ensure(total * D + 1));
-    rc = hpss_launch(h->hp, h->device, hpss, (uint32_t)D, S, seg_rows, spec_rates, cur, h->hp.rows.p, hs, err);
+    rc = hpss_launch(h->hp, h->device, c.hpss, (uint32_t)D, S, seg_rows, spec_rates, cur, h->hp.rows.p, hs, err);
     if (rc) return rc;
     cur = h->hp.rows.p;
   }
-  if (pcen) {
-    rc = pcen_launch(h->pc, h->device, pcen, (uint32_t)D, S, seg_rows, spec_rates, spec->hop_length, cur, cur, hs, err);
+  if (c.pcen) {
+    rc = pcen_launch(h->pc, h->device, c.pcen, (uint32_t)D, S, seg_rows, spec_rates, c.spec->hop_length, cur, cur, hs, err);
     if (rc) return rc;
   }
-  if (rhythm) {  // the rows stay where they are: the selected rhythm output goes to the host in their place
-    rc = rhythm_rows_out(h->rh, h->device, rhythm, (uint32_t)D, S, spec_rates, seg_rows_out, total, cur, rows, rows_capacity, refused_out, hs, err);
+  if (c.rhythm) {  // the rows stay where they are: the selected rhythm output goes to the host in their place
+    rc = rhythm_rows_out(h->rh, h->device, c.rhythm, (uint32_t)D, S, spec_rates, seg_rows, total, cur, rows, rows_capacity, c.refused_out, hs, err);
     if (rc) return rc;
     return sync_status_into(h, status, err);
   }
-  if (post) {
+  if (const vsyn_spectral_post* post = c.post) {
     const uint64_t Dout = D * (1u + post->order);
     HIPCHK(h->pp.rows.ensure(total * Dout + 1));
     rc = post_launch(h->pp, h->device, post, (uint32_t)D, S, seg_rows, cur, h->pp.rows.p, hs, err);
@@ -1838,53 +1872,52 @@ static int spectral_rows_out(vsyn_handle* h, const vsyn_spectral_spec* spec, con
   return sync_status_into(h, status, err);
 }
 
-// The spectral host forms: the rows of the last host submit's PCM behind the stages present (gate, cond, pcen, post: NULL, out_rate: 0
-// for none). Without a gate the rows are counted on the host and nothing runs for a NULL rows. With one the chain runs up to the
-// gated plane and waits once for the gate's read-backs, the row counts come from those (frames_out: the frames behind the gate),
-// and conditioning, spectral rows and the post stage follow on the gated plane.
-static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_pcen* pcen,
-                         const vsyn_spectral_post* post, uint32_t S, const uint32_t* rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
-                         uint64_t* seg_rows,
-                         uint64_t* frames_out, float* peaks_out, vsyn_status* status, const char** err, const vsyn_loudness_spec* loud = nullptr,
-                         vsyn_loudness_record* records_out = nullptr, const vsyn_spectral_chroma* chroma = nullptr,
-                         const vsyn_spectral_hpss* hpss = nullptr, const vsyn_rhythm_spec* rhythm = nullptr, uint32_t* refused_out = nullptr) {
+// The spectral host forms: the rows of the last host submit's PCM behind the stages of c that are present. Without a gate the rows
+// are counted on the host and nothing runs for a NULL rows. With one the chain runs up to the gated plane and waits once for the
+// gate's read-backs, the row counts come from those (c.frames_out: the frames behind the gate), and the loudness step, conditioning,
+// spectral rows and the row stages follow on the gated plane. (c by value: a post stage that is off is dropped from it.)
+static int spectral_host(vsyn_handle* h, Chain c, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
+  const uint32_t S = c.S, out_rate = c.out_rate;
+  const uint32_t* rates = c.rates;
+  const Gate* gate = c.gate.spec ? &c.gate : nullptr;
+  const vsyn_spectral_spec* spec = c.spec;
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
-  if (loud)  // (first: a refused loudness spec writes nothing, the status included)
-    if (int rc = chain_loud_check(loud, cond, S, rates, err)) return rc;
+  if (c.loud)  // (first: a refused loudness spec writes nothing, the status included)
+    if (int rc = chain_loud_check(c.loud, c.cond, S, rates, err)) return rc;
   status_reset(status);
-  if (int rc = chain_check(gate, cond, S, rates, out_rate, err)) return rc;
+  if (int rc = chain_check(gate, c.cond, S, rates, out_rate, err)) return rc;
   std::vector<uint32_t> sp_rates = stage_rates(S, rates, out_rate);
   // (NULL rates without a gate are spec_check's to refuse; behind a gate they skip every segment)
-  if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err, chroma)) return rc;
-  if (hpss) {
-    if (int rc = hpss_check(hpss, err)) return rc;
+  if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err, c.chroma)) return rc;
+  if (c.hpss) {
+    if (int rc = hpss_check(c.hpss, err)) return rc;
     if (spec->kind != VSYN_SPEC_MEL_POWER && spec->kind != VSYN_SPEC_LIN_POWER)
       return fail(err, VSYN_ERR_INVALID, "hpss takes the rows of mel_power or lin_power, not of kind %u", spec->kind);
-    if (pcen && hpss->output != VSYN_HPSS_OUT_COMPONENT)
-      return fail(err, VSYN_ERR_INVALID, "pcen takes the hpss component, not its %s", hpss->output == VSYN_HPSS_OUT_MASK ? "mask" : "median");
+    if (c.pcen && c.hpss->output != VSYN_HPSS_OUT_COMPONENT)
+      return fail(err, VSYN_ERR_INVALID, "pcen takes the hpss component, not its %s", c.hpss->output == VSYN_HPSS_OUT_MASK ? "mask" : "median");
   }
-  if (pcen) {
-    if (int rc = pcen_check(pcen, err)) return rc;
+  if (c.pcen) {
+    if (int rc = pcen_check(c.pcen, err)) return rc;
     if (spec->kind != VSYN_SPEC_MEL_POWER && spec->kind != VSYN_SPEC_LIN_POWER)
       return fail(err, VSYN_ERR_INVALID, "pcen takes the rows of mel_power or lin_power, not of kind %u (they can be negative)", spec->kind);
     for (uint32_t g = 0; g < S; ++g)
-      if (sp_rates[g] && pcen_b(pcen, sp_rates[g], spec->hop_length) == 0.0)
+      if (sp_rates[g] && pcen_b(c.pcen, sp_rates[g], spec->hop_length) == 0.0)
         return fail(err, VSYN_ERR_INVALID, "segment %u: pcen: no coefficient in (0, 1] from time_constant %g at rate %u, hop %u", g,
-                    pcen->time_constant, sp_rates[g], spec->hop_length);
+                    c.pcen->time_constant, sp_rates[g], spec->hop_length);
   }
-  if (post) {
-    if (int rc = spec_post_check(spec, post, err, chroma)) return rc;
-    if (!post_on(post)) post = nullptr;  // off: the rows of the spectral pass, bit for bit
+  if (c.post) {
+    if (int rc = spec_post_check(spec, c.post, err, c.chroma)) return rc;
+    if (!post_on(c.post)) c.post = nullptr;  // off: the rows of the spectral pass, bit for bit
   }
-  if (rhythm) {
-    if (post) return fail(err, VSYN_ERR_INVALID, "delta / normalize are not available with the rhythm stages: the onset stage takes their place");
-    if (int rc = rhythm_check(rhythm, spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, spec_dim(spec, chroma), err)) return rc;
-    if (refused_out && S) memset(refused_out, 0, sizeof(uint32_t) * S);
+  if (c.rhythm) {
+    if (c.post) return fail(err, VSYN_ERR_INVALID, "delta / normalize are not available with the rhythm stages: the onset stage takes their place");
+    if (int rc = rhythm_check(c.rhythm, spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, spec_dim(spec, c.chroma), err)) return rc;
+    if (c.refused_out && S) memset(c.refused_out, 0, sizeof(uint32_t) * S);
   }
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
-  if (peaks_out) memset(peaks_out, 0, sizeof(float) * S);
-  if (records_out) memset(records_out, 0, sizeof(vsyn_loudness_record) * S);
+  if (c.peaks_out) memset(c.peaks_out, 0, sizeof(float) * S);
+  if (c.records_out) memset(c.records_out, 0, sizeof(vsyn_loudness_record) * S);
   if (gate && gate->bounds) memset(gate->bounds, 0, sizeof(uint32_t) * 2u * S);
   if (gate && gate->refs) memset(gate->refs, 0, sizeof(double) * S);
   // the lock covers the whole call: the stages' workspaces are the handle's, and the PCM must stay that of the last submit
@@ -1911,33 +1944,32 @@ static int spectral_host(vsyn_handle* h, const Gate* gate, const vsyn_pcm_cond* 
     HIPCHK(hipStreamSynchronize(h->host_stream));  // the one read-back of a gated form: the bounds or the joined frames, with the refs (counts, intervals)
     for (uint32_t s = 0; s < S; ++s) {
       T[s] = g.split ? joined[s] : bounds[2u * s + 1u] - bounds[2u * s];
-      if (frames_out) frames_out[s] = T[s];
+      if (c.frames_out) c.frames_out[s] = T[s];
       if (!std::isfinite(refs[s])) sp_rates[s] = 0u;
     }
     if (gate->bounds) memcpy(gate->bounds, bounds.data(), sizeof(uint32_t) * bounds.size());
     if (gate->refs) memcpy(gate->refs, refs.data(), sizeof(double) * S);
   }
   const bool center = (spec->options & VSYN_SPEC_CENTER) != 0;
-  count_rows(spec->n_fft, spec->hop_length, center, S, sp_rates.data(), T.data(), gate && post && post->order ? post->width : 0u, seg_rows, &total,
+  count_rows(spec->n_fft, spec->hop_length, center, S, sp_rates.data(), T.data(), gate && c.post && c.post->order ? c.post->width : 0u, seg_rows, &total,
              &f_max);
   if (gate) {  // gated to nothing, or below the delta width: that segment fails alone
     for (uint32_t s = 0; s < S; ++s)
       if (!seg_rows[s]) sp_rates[s] = 0u;
-  } else if (post) {  // ungated, a segment below the delta width refuses the call
-    if (int rc = post_check_rows(post, S, seg_rows, err)) return rc;
+  } else if (c.post) {  // ungated, a segment below the delta width refuses the call
+    if (int rc = post_check_rows(c.post, S, seg_rows, err)) return rc;
   }
   if (!rows || total == 0) return VSYN_OK;
-  if (!rhythm && total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (!c.rhythm && total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
   if (!gate && out_rate) {
     if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
     if (int rc = step_resample(h, S, rates, out_rate, t_max, false, &v, err)) return rc;
   }
-  if (loud)
-    if (int rc = step_loudness(h, S, loud, sp_rates.data(), T.data(), t_max, false, records_out, &v, err)) return rc;
-  if (cond)
-    if (int rc = step_condition(h, S, cond, t_max, t_max, false, peaks_out, &v, err)) return rc;
-  return spectral_rows_out(h, spec, pcen, post, S, sp_rates.data(), v, seg_rows, f_max, total, rows, status, err, chroma, hpss, rhythm, rows_capacity,
-                           seg_rows, refused_out);
+  if (c.loud)
+    if (int rc = step_loudness(h, S, c.loud, sp_rates.data(), T.data(), t_max, false, c.records_out, &v, err)) return rc;
+  if (c.cond)
+    if (int rc = step_condition(h, S, c.cond, t_max, t_max, false, c.peaks_out, &v, err)) return rc;
+  return spectral_rows_out(h, c, sp_rates.data(), v, seg_rows, f_max, total, rows, rows_capacity, status, err);
 }
 
 // vsyn_pcm_split_intervals_host: the chain up to the split stage's marks; nothing but the frames in front of the stage, the
@@ -2032,19 +2064,26 @@ int vsyn_pcm_resample_host(vsyn_handle* h, uint32_t S, const uint32_t* in_rates,
                            uint64_t out_stride_frames, uint64_t* frames_out, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   if (!out_rate) return rs_check(S, in_rates, out_rate, err);  // (0 would mean no resampling to the shared body)
-  return pcm_out_host(h, nullptr, nullptr, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, nullptr, err);
+  Chain c{S, in_rates, out_rate};
+  c.frames_out = frames_out;
+  return pcm_out_host(h, c, format, out, out_stride_frames, err);
 }
 
 int vsyn_pcm_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* sample_rates, float* rows,
                            uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err) {
-  return spectral_host(h, nullptr, nullptr, spec, nullptr, nullptr, S, sample_rates, 0, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
+  Chain c{S, sample_rates, 0};
+  c.spec = spec;
+  return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
 }
 
 int vsyn_pcm_spectral_post_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post, uint32_t S,
                                 const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
                                 vsyn_status* status, const char** err) {
   if (!post) return fail(err, VSYN_ERR_INVALID, "spectral post spec is NULL");
-  return spectral_host(h, nullptr, nullptr, spec, nullptr, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
+  Chain c{S, in_rates, out_rate};
+  c.spec = spec;
+  c.post = post;
+  return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
 }
 
 int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
@@ -2053,14 +2092,21 @@ int vsyn_pcm_resample_spectral_host(vsyn_handle* h, const vsyn_spectral_spec* sp
     status_reset(status);
     return rs_check(S, in_rates, out_rate, err);
   }
-  return spectral_host(h, nullptr, nullptr, spec, nullptr, nullptr, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, nullptr, status, err);
+  Chain c{S, in_rates, out_rate};
+  c.spec = spec;
+  return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
 }
 
 int vsyn_pcm_cond_spectral_host(vsyn_handle* h, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_post* post,
                                 uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
                                 uint64_t* seg_rows, float* peaks_out, vsyn_status* status, const char** err) {
   if (!h) return cond_no_handle(err);
-  return spectral_host(h, nullptr, cond, spec, nullptr, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status, err);
+  Chain c{S, in_rates, out_rate};
+  c.cond = cond;
+  c.spec = spec;
+  c.post = post;
+  c.peaks_out = peaks_out;
+  return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
 }
 
 int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t S, const float* d_pcm, uint64_t plane_stride,
@@ -2079,12 +2125,24 @@ int vsyn_pcm_condition_device(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_
                      (hipStream_t)hip_stream, err);
 }
 
-// A PCM host form without a gate is vsyn_pcm_condition_host, which needs its spec.
+}  // extern "C"
+
+// The PCM host forms behind vsyn_pcm_resample_host. A chain without a stage is vsyn_pcm_condition_host, which needs its spec.
+static int pcm_form_host(vsyn_handle* h, const Chain& c, int format, void* out, uint64_t out_stride_frames, const char** err) {
+  if (!h) return cond_no_handle(err);
+  if (!c.gate.spec && !c.effect && !c.stretch.spec && !c.loud && !c.cond) return cond_check(c.cond, err);
+  return pcm_out_host(h, c, format, out, out_stride_frames, err);
+}
+
+extern "C" {
+
 int vsyn_pcm_condition_host(vsyn_handle* h, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, int format,
                             void* out, uint64_t out_stride_frames, uint64_t* frames_out, float* peaks_out, const char** err) {
-  if (!h) return cond_no_handle(err);
-  if (!cond) return cond_check(cond, err);
-  return pcm_out_host(h, nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
+  Chain c{S, in_rates, out_rate};
+  c.cond = cond;
+  c.frames_out = frames_out;
+  c.peaks_out = peaks_out;
+  return pcm_form_host(h, c, format, out, out_stride_frames, err);
 }
 
 uint64_t vsyn_pcm_trim_num_frames(const vsyn_pcm_trim* trim, uint64_t frames) {
@@ -2111,10 +2169,8 @@ int vsyn_pcm_trim_device(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t S, 
 int vsyn_pcm_trim_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
                        uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out,
                        float* peaks_out, double* refs_out, const char** err) {
-  if (!trim) return vsyn_pcm_condition_host(h, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
-  if (!h) return cond_no_handle(err);
-  const Gate g{trim, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return pcm_out_host(h, &g, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
+  return vsyn_pcm_chain_host(h, trim, 0, nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, bounds_out, nullptr, nullptr,
+                             0, peaks_out, refs_out, nullptr, err);
 }
 
 int vsyn_pcm_trim_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
@@ -2129,10 +2185,8 @@ int vsyn_pcm_trim_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim, 
                                      const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates,
                                      uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* bounds_out,
                                      float* peaks_out, double* refs_out, vsyn_status* status, const char** err) {
-  if (!h) return cond_no_handle(err);
-  const Gate g{trim, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return spectral_host(h, trim ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr, peaks_out, status,
-                       err);
+  return vsyn_pcm_chain_spectral_host(h, trim, 0, nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, nullptr,
+                                      bounds_out, nullptr, nullptr, 0, peaks_out, refs_out, nullptr, status, err);
 }
 
 uint64_t vsyn_pcm_split_max_intervals(const vsyn_pcm_trim* trim, uint64_t frames) {
@@ -2160,18 +2214,17 @@ int vsyn_pcm_split_device(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t S,
 int vsyn_pcm_split_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates,
                         uint32_t out_rate, int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* counts_out,
                         uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out, const char** err) {
-  if (!trim) return vsyn_pcm_condition_host(h, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
-  if (!h) return cond_no_handle(err);
-  const Gate g{trim, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out};
-  return pcm_out_host(h, &g, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err);
+  return vsyn_pcm_chain_host(h, trim, 1, nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, nullptr, counts_out,
+                             intervals_out, intervals_stride, peaks_out, refs_out, nullptr, err);
 }
 
 int vsyn_pcm_split_intervals_host(vsyn_handle* h, const vsyn_pcm_trim* trim, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
                                   uint64_t* frames_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
                                   double* refs_out, const char** err) {
   if (!h) return cond_no_handle(err);
-  return split_intervals_host(h, Gate{trim, true, false, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}, S, in_rates, out_rate,
-                              frames_out, err);
+  Gate g = make_gate(trim, true, nullptr, counts_out, intervals_out, intervals_stride, refs_out);
+  g.gather = false;
+  return split_intervals_host(h, g, S, in_rates, out_rate, frames_out, err);
 }
 
 int vsyn_pcm_split_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* trim, const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec,
@@ -2187,62 +2240,49 @@ int vsyn_pcm_split_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim,
                                       uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out,
                                       uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                       vsyn_status* status, const char** err) {
-  if (!h) return cond_no_handle(err);
-  const Gate g{trim, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out};
-  return spectral_host(h, trim ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, trim ? frames_out : nullptr,
-                       peaks_out, status, err);
+  return vsyn_pcm_chain_spectral_host(h, trim, 1, nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, frames_out,
+                                      nullptr, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, nullptr, status, err);
 }
 
 // The most general PCM and spectral host forms: every stage's spec, NULL for a stage that is off; the gate is a trim, or with
-// gate_is_split != 0 a split. With loud = NULL they are the entries without the argument.
+// gate_is_split != 0 a split. An entry with a stage passed as NULL is the entry without that argument: each narrower entry is the
+// widest one, vsyn_pcm_chain_stretch_host or vsyn_pcm_chain_rhythm_host, with NULL for what it does not take.
 int vsyn_pcm_chain_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond,
                         uint32_t S, const uint32_t* in_rates, uint32_t out_rate, int format, void* out, uint64_t out_stride_frames,
                         uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
                         float* peaks_out, double* refs_out, vsyn_loudness_record* records_out, const char** err) {
-  if (!loud)
-    return gate && gate_is_split ? vsyn_pcm_split_host(h, gate, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, counts_out,
-                                                       intervals_out, intervals_stride, peaks_out, refs_out, err)
-                                 : vsyn_pcm_trim_host(h, gate, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, bounds_out,
-                                                      peaks_out, refs_out, err);
-  if (!h) return cond_no_handle(err);
-  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
-                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
-                      records_out);
+  return vsyn_pcm_chain_stretch_host(h, gate, gate_is_split, nullptr, nullptr, nullptr, nullptr, loud, cond, S, in_rates, out_rate, format, out,
+                                     out_stride_frames, frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out,
+                                     records_out, err);
 }
 
-// vsyn_pcm_chain_host with the effect stage: the same chain body.
 int vsyn_pcm_chain_effects_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
                                 const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
                                 int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
                                 uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                 vsyn_loudness_record* records_out, const char** err) {
-  if (!effect)
-    return vsyn_pcm_chain_host(h, gate, gate_is_split, loud, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, bounds_out,
-                               counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, err);
-  if (!h) return cond_no_handle(err);
-  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
-                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
-                      loud ? records_out : nullptr, effect);
+  return vsyn_pcm_chain_stretch_host(h, gate, gate_is_split, effect, nullptr, nullptr, nullptr, loud, cond, S, in_rates, out_rate, format, out,
+                                     out_stride_frames, frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out,
+                                     records_out, err);
 }
 
-// vsyn_pcm_chain_effects_host with the stretch stage in the effect's slot: the same chain body.
+// The widest PCM form. The outputs of the gate that is off, and the records without a normaliser, are not written.
 int vsyn_pcm_chain_stretch_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_pcm_effect* effect,
                                 const vsyn_pcm_stretch* stretch, const double* stretch_rates, const uint32_t* shift_from_hz,
                                 const vsyn_loudness_spec* loud, const vsyn_pcm_cond* cond, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
                                 int format, void* out, uint64_t out_stride_frames, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
                                 uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                 vsyn_loudness_record* records_out, const char** err) {
-  if (!stretch)
-    return vsyn_pcm_chain_effects_host(h, gate, gate_is_split, effect, loud, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out,
-                                       bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, err);
-  if (!h) return cond_no_handle(err);
-  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
-                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  const Stretch x{stretch, stretch_rates, stretch->shift_to_hz ? shift_from_hz : nullptr};
-  return pcm_out_host(h, gate ? &g : nullptr, cond, S, in_rates, out_rate, format, out, out_stride_frames, frames_out, peaks_out, err, loud,
-                      loud ? records_out : nullptr, effect, &x);
+  Chain c{S, in_rates, out_rate};
+  c.gate = make_gate(gate, gate && gate_is_split, bounds_out, counts_out, intervals_out, intervals_stride, refs_out);
+  c.effect = effect;
+  c.stretch = Stretch{stretch, stretch_rates, stretch && stretch->shift_to_hz ? shift_from_hz : nullptr};
+  c.loud = loud;
+  c.cond = cond;
+  c.frames_out = frames_out;
+  c.peaks_out = peaks_out;
+  c.records_out = loud ? records_out : nullptr;
+  return pcm_form_host(h, c, format, out, out_stride_frames, err);
 }
 
 int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
@@ -2251,57 +2291,36 @@ int vsyn_pcm_chain_spectral_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int 
                                  uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
                                  uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                  vsyn_loudness_record* records_out, vsyn_status* status, const char** err) {
-  if (!loud)
-    return gate && gate_is_split
-               ? vsyn_pcm_split_spectral_pcen_host(h, gate, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, frames_out,
-                                                   counts_out, intervals_out, intervals_stride, peaks_out, refs_out, status, err)
-               : vsyn_pcm_trim_spectral_pcen_host(h, gate, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows, bounds_out,
-                                                  peaks_out, refs_out, status, err);
-  if (!h) return cond_no_handle(err);
-  const Gate g = gate_is_split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
-                               : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
-                       gate ? frames_out : nullptr, peaks_out, status, err, loud, records_out);
+  return vsyn_pcm_chain_rhythm_host(h, gate, gate_is_split, loud, cond, spec, nullptr, nullptr, pcen, post, nullptr, S, in_rates, out_rate, rows,
+                                    rows_capacity, seg_rows, frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out,
+                                    records_out, nullptr, status, err);
 }
 
-// vsyn_pcm_chain_spectral_host with the chroma parameters: the same chain body. Without a loudness spec the gate decides, as there, which
-// of frames_out and the outputs of the other gate the body is given.
 int vsyn_pcm_chain_chroma_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
                                const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
                                const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S, const uint32_t* in_rates,
                                uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out,
                                uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out,
                                double* refs_out, vsyn_loudness_record* records_out, vsyn_status* status, const char** err) {
-  if (!spec || !spec_is_chroma(spec) || !h)  // chroma is not read: the entry without it (which also words the refusal of a NULL handle)
-    return vsyn_pcm_chain_spectral_host(h, gate, gate_is_split, loud, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
-                                        frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, status,
-                                        err);
-  const bool split = gate && gate_is_split;
-  const Gate g = split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
-                       : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
-                       gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma);
+  return vsyn_pcm_chain_rhythm_host(h, gate, gate_is_split, loud, cond, spec, chroma, nullptr, pcen, post, nullptr, S, in_rates, out_rate, rows,
+                                    rows_capacity, seg_rows, frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out,
+                                    records_out, nullptr, status, err);
 }
 
-// vsyn_pcm_chain_chroma_host with the HPSS stage: the same chain body, and the same choice of the outputs it is given.
 int vsyn_pcm_chain_hpss_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
                              const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
                              const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, uint32_t S,
                              const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
                              uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride,
                              float* peaks_out, double* refs_out, vsyn_loudness_record* records_out, vsyn_status* status, const char** err) {
-  if (!hpss || !spec || !h)  // the entry without the stage (which also words the refusal of a NULL handle or spec)
-    return vsyn_pcm_chain_chroma_host(h, gate, gate_is_split, loud, cond, spec, chroma, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
-                                      frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out, status,
-                                      err);
-  const bool split = gate && gate_is_split;
-  const Gate g = split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
-                       : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
-                       gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma, hpss);
+  return vsyn_pcm_chain_rhythm_host(h, gate, gate_is_split, loud, cond, spec, chroma, hpss, pcen, post, nullptr, S, in_rates, out_rate, rows,
+                                    rows_capacity, seg_rows, frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out,
+                                    records_out, nullptr, status, err);
 }
 
-// vsyn_pcm_chain_hpss_host with the rhythm stages behind pcen: the same chain body, and the same choice of the outputs it is given.
+// The widest spectral form. What the narrower entries fixed by handing a NULL stage down, written out: a NULL handle is refused in
+// the words of the conditioning entries; the chroma parameters are read for a chroma kind only; the body is given frames_out behind
+// a split, or behind any gate with the normaliser, and records_out with the normaliser.
 int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
                                const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
                                const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post,
@@ -2309,16 +2328,23 @@ int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
                                uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
                                uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                vsyn_loudness_record* records_out, uint32_t* refused_out, vsyn_status* status, const char** err) {
-  if (!rhythm || !spec || !h)  // the entry without the stages (which also words the refusal of a NULL handle or spec)
-    return vsyn_pcm_chain_hpss_host(h, gate, gate_is_split, loud, cond, spec, chroma, hpss, pcen, post, S, in_rates, out_rate, rows, rows_capacity,
-                                    seg_rows, frames_out, bounds_out, counts_out, intervals_out, intervals_stride, peaks_out, refs_out, records_out,
-                                    status, err);
+  if (!h) return cond_no_handle(err);
   const bool split = gate && gate_is_split;
-  const Gate g = split ? Gate{gate, true, true, nullptr, nullptr, counts_out, intervals_out, intervals_stride, refs_out}
-                       : Gate{gate, false, false, nullptr, bounds_out, nullptr, nullptr, 0, refs_out};
-  return spectral_host(h, gate ? &g : nullptr, cond, spec, pcen, post, S, in_rates, out_rate, rows, rows_capacity, seg_rows,
-                       gate && (loud || split) ? frames_out : nullptr, peaks_out, status, err, loud, loud ? records_out : nullptr, chroma, hpss, rhythm,
-                       refused_out);
+  Chain c{S, in_rates, out_rate};
+  c.gate = make_gate(gate, split, bounds_out, counts_out, intervals_out, intervals_stride, refs_out);
+  c.loud = loud;
+  c.cond = cond;
+  c.spec = spec;
+  c.chroma = spec && spec_is_chroma(spec) ? chroma : nullptr;
+  c.hpss = hpss;
+  c.pcen = pcen;
+  c.post = post;
+  c.rhythm = rhythm;
+  c.frames_out = gate && (loud || split) ? frames_out : nullptr;
+  c.peaks_out = peaks_out;
+  c.records_out = loud ? records_out : nullptr;
+  c.refused_out = refused_out;
+  return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
 }
 
 // ---- pitch (vsyn_pitch.h) ----

@@ -76,6 +76,9 @@ struct CollectSink : SynthSink {
 
 struct NullCallbacks : ParseCallbacks {};
 
+// The loudness record of a file that has none: the stage is off, or the file failed.
+const vsyn_loudness_record NO_LOUDNESS_RECORD = vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u};
+
 bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
 bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
 bool pitch_run(const CorpusOptions& o) { return o.pitch.frame_length != 0; }
@@ -86,7 +89,7 @@ bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm 
 uint32_t spectral_dim(const CorpusOptions& o) {
   if (o.rhythm)  // the words of a row of the selected rhythm output
     return o.rhythm_spec.output == VSYN_RHYTHM_TEMPOGRAM ? o.rhythm_spec.tempogram.win_length : o.rhythm_spec.output == VSYN_RHYTHM_TEMPO_MEAN ? 2u : 1u;
-  return vsyn_spectral_chroma_dim(&o.spectral, o.chroma_entry && o.chroma_given ? &o.chroma_spec : nullptr) * (1u + o.post.order);
+  return vsyn_spectral_chroma_dim(&o.spectral, o.chroma_given ? &o.chroma_spec : nullptr) * (1u + o.post.order);
 }
 bool feature_needs_residue(const CorpusOptions& o) {
   return o.features.kind == VSYN_FEAT_RESIDUE_YS || o.features.kind == VSYN_FEAT_RESIDUE_YS_WITH_FLOOR;
@@ -448,7 +451,7 @@ struct Feeder {
   }
 
   // Resampled run: each file's PCM resampled on the device from its own rate to resample_rate (vsyn_pcm_resample_host, or for a
-  // spectral run vsyn_pcm_resample_spectral_host in spectral_stage); a file whose ratio the contract refuses gets no output and an error
+  // spectral run vsyn_pcm_chain_rhythm_host in spectral_stage); a file whose ratio the contract refuses gets no output and an error
   // of its own.
   OkOrError resample_stage(Group& g, bool spectral, Outcome& o) {
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size(), out_rate = opts.resample_rate;
@@ -533,7 +536,7 @@ struct Feeder {
   const vsyn_pcm_cond* trim_cond() const { return opts.cond.options ? &opts.cond : nullptr; }
 
   // Conditioned PCM run: each file's PCM, resampled first in a resampled run (resample_stage has set the frames and refused what
-  // the resampler refuses), through vsyn_pcm_condition_host: one mono plane per file comes back.
+  // the resampler refuses), through the PCM stages that are on (vsyn_pcm_chain_stretch_host): one mono plane per file comes back.
   OkOrError condition_stage(Group& g, Outcome& o) {
     const uint32_t S = (uint32_t)g.pending.size();
     std::vector<uint32_t> rates(S);
@@ -563,96 +566,56 @@ struct Feeder {
     std::vector<float> peaks(S, 0.f);
     const int fmt = opts.pcm_s16 ? VSYN_PCM_S16 : VSYN_PCM_F32;
     void* out = opts.pcm_s16 ? (void*)g.pcm16.p : (void*)g.pcm.p;
-    if (opts.effect || opts.stretch) {  // the chain form with the effect or the stretch stage: a gate or none, the stage, the normaliser or none, conditioning or none
-      std::vector<double> refs(S);
-      const bool gated = opts.split || opts.trim;
-      if (opts.split) size_intervals(S, o);
-      if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);
-      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
-      const int rc =
-          opts.stretch
-              ? vsyn_pcm_chain_stretch_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.effect ? &opts.effect_spec : nullptr,
-                                            &opts.stretch_spec, st_rates.data(), st_from.empty() ? nullptr : st_from.data(),
-                                            opts.loudness_norm ? &opts.loudness_spec : nullptr, trim_cond(), S, rates.data(), opts.resample_rate, fmt,
-                                            out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
-                                            opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
-                                            opts.loudness_norm ? o.loud.data() : nullptr, &err)
-              : vsyn_pcm_chain_effects_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.effect_spec,
-                                            opts.loudness_norm ? &opts.loudness_spec : nullptr, trim_cond(), S, rates.data(), opts.resample_rate, fmt,
-                                            out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
-                                            opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
-                                            opts.loudness_norm ? o.loud.data() : nullptr, &err);
-      if (rc != VSYN_OK) return OkOrError(std::string(opts.stretch ? "GPU stretch layer: " : "GPU effects layer: ") + (err ? err : "effect failed"));
-      if (opts.stretch) {  // the stage's frames: the one step behind the gate that changes the count
-        for (uint32_t s = 0; s < S; ++s) {
-          CHECK(got[s] <= pl);
-          o.frames[s] = got[s];
-        }
-        if (gated) refuse_refs(refs, o);
-      } else if (gated) {
-        for (uint32_t s = 0; s < S; ++s) {
-          CHECK(got[s] <= o.frames[s]);
-          o.frames[s] = got[s];
-        }
-        refuse_refs(refs, o);
-      } else {
-        CHECK(got == o.frames);
+    // One call for every run: the widest chain entry, a NULL spec for each stage that is off (the library makes that the entry
+    // without the stage, bit for bit). Only the marks of intervals_only have an entry of their own: no PCM comes back from it.
+    const bool gated = opts.split || opts.trim, staged = opts.effect || opts.stretch || opts.loudness_norm;
+    const bool marks_only = opts.split && opts.intervals_only && !staged;
+    // conditioning alone is the mono downmix, whatever its options; behind another stage, options 0 is no conditioning step
+    const vsyn_pcm_cond* cond = gated || staged ? trim_cond() : &opts.cond;
+    std::vector<double> refs(S);
+    if (opts.split) size_intervals(S, o);
+    if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);
+    if (opts.loudness_norm) o.loud.assign(S, NO_LOUDNESS_RECORD);
+    const int rc =
+        marks_only
+            ? vsyn_pcm_split_intervals_host(g.handle, &opts.trim_spec, S, rates.data(), opts.resample_rate, got.data(), o.counts.data(), o.iv.data(),
+                                            o.iv_stride, refs.data(), &err)
+            : vsyn_pcm_chain_stretch_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.effect ? &opts.effect_spec : nullptr,
+                                          opts.stretch ? &opts.stretch_spec : nullptr, opts.stretch ? st_rates.data() : nullptr,
+                                          st_from.empty() ? nullptr : st_from.data(), opts.loudness_norm ? &opts.loudness_spec : nullptr, cond, S,
+                                          rates.data(), opts.resample_rate, fmt, out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr,
+                                          opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(),
+                                          refs.data(), opts.loudness_norm ? o.loud.data() : nullptr, &err);
+    if (rc != VSYN_OK) {  // the run's error, named after the outermost stage that is on
+      const char *layer = "GPU conditioning layer: ", *what = "conditioning failed";
+      if (opts.trim) layer = "GPU trim layer: ", what = "trim failed";
+      if (opts.split) layer = "GPU split layer: ", what = "split failed";
+      if (opts.loudness_norm) layer = "GPU loudness layer: ", what = "normalisation failed";
+      if (opts.effect) layer = "GPU effects layer: ", what = "effect failed";
+      if (opts.stretch) layer = "GPU stretch layer: ", what = "effect failed";
+      return OkOrError(std::string(layer) + (err ? err : what));
+    }
+    if (opts.stretch) {  // the stage's frames: the one step behind the gate that changes the count
+      for (uint32_t s = 0; s < S; ++s) {
+        CHECK(got[s] <= pl);
+        o.frames[s] = got[s];
       }
-      if (opts.loudness_norm) refuse_loud(o, true, rates);
-    } else if (opts.loudness_norm) {  // the one form with every stage's spec: a gate or none, the normaliser, conditioning or none
-      std::vector<double> refs(S);
-      const bool gated = opts.split || opts.trim;
-      if (opts.split) size_intervals(S, o);
-      if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);
-      o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
-      const int rc = vsyn_pcm_chain_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.loudness_spec, trim_cond(), S,
-                                         rates.data(), opts.resample_rate, fmt, out, pl, got.data(), opts.trim ? o.bounds.data() : nullptr,
-                                         opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(),
-                                         refs.data(), o.loud.data(), &err);
-      if (rc != VSYN_OK) return OkOrError(std::string("GPU loudness layer: ") + (err ? err : "normalisation failed"));
-      if (gated) {
-        for (uint32_t s = 0; s < S; ++s) {
-          CHECK(got[s] <= o.frames[s]);
-          o.frames[s] = got[s];
-        }
-        refuse_refs(refs, o);
-      } else {
-        CHECK(got == o.frames);
-      }
-      refuse_loud(o, true, rates);
-    } else if (opts.split || opts.trim) {  // a gate in front: the frames delivered are the joined or trimmed ones, or with intervals_only nothing is
-      std::vector<double> refs(S);
-      int rc;
-      if (opts.split) {
-        size_intervals(S, o);
-        rc = opts.intervals_only
-                 ? vsyn_pcm_split_intervals_host(g.handle, &opts.trim_spec, S, rates.data(), opts.resample_rate, got.data(), o.counts.data(),
-                                                 o.iv.data(), o.iv_stride, refs.data(), &err)
-                 : vsyn_pcm_split_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate, fmt, out, pl, got.data(),
-                                       o.counts.data(), o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &err);
-        if (rc != VSYN_OK) return OkOrError(std::string("GPU split layer: ") + (err ? err : "split failed"));
-      } else {
-        o.bounds.assign(2u * (size_t)S, 0u);
-        rc = vsyn_pcm_trim_host(g.handle, &opts.trim_spec, trim_cond(), S, rates.data(), opts.resample_rate, fmt, out, pl, got.data(),
-                                o.bounds.data(), peaks.data(), refs.data(), &err);
-        if (rc != VSYN_OK) return OkOrError(std::string("GPU trim layer: ") + (err ? err : "trim failed"));
-      }
+    } else if (gated) {  // the frames delivered are the joined or trimmed ones (marks_only: the unsplit ones)
       for (uint32_t s = 0; s < S; ++s) {
         CHECK(got[s] <= o.frames[s]);
         o.frames[s] = got[s];
       }
-      refuse_refs(refs, o);
     } else {
-      const int rc = vsyn_pcm_condition_host(g.handle, &opts.cond, S, rates.data(), opts.resample_rate, fmt, out, pl, got.data(), peaks.data(), &err);
-      if (rc != VSYN_OK) return OkOrError(std::string("GPU conditioning layer: ") + (err ? err : "conditioning failed"));
       CHECK(got == o.frames);
     }
+    if (gated) refuse_refs(refs, o);
+    if (opts.loudness_norm) refuse_loud(o, true, rates);
     refuse_peaks(peaks, o);
     o.plane = pl;
     return OkOrError();
   }
 
-  // Spectral run: each file's rows from the PCM still on the device (vsyn_pcm_spectral_host, or resampled first); a file whose rate
+  // Spectral run: each file's rows from the PCM still on the device, through the stages that are on (vsyn_pcm_chain_rhythm_host); a file whose rate
   // the spec does not fit (fmax above its sr / 2) gets no rows and an error of its own, unless it has one already.
   OkOrError spectral_stage(Group& g, Outcome& o) {
     const uint32_t S = (uint32_t)g.pending.size();
@@ -692,55 +655,18 @@ struct Feeder {
     if (opts.trim) o.bounds.assign(2u * (size_t)S, 0u);  // spec_rows, from the untrimmed frames, bounds the trimmed rows
     std::vector<uint64_t> joined(S, 0);
     if (opts.split) size_intervals(S, o);
-    // one entry per gate: a stage that is off is a NULL spec, and the entry then gives the bits of the entry without that stage
+    // One call for every run: the widest chain entry, a NULL spec for each stage that is off (the library makes that the entry
+    // without the stage, bit for bit), and the outputs of the gate that is on.
     const bool gated = opts.trim || opts.split;
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
-    const vsyn_spectral_post* post = post_run(opts) ? &opts.post : nullptr;
-    int rc;
-    if (opts.rhythm) {  // the HPSS form with the rhythm stages behind it
-      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
-      rc = vsyn_pcm_chain_rhythm_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
-                                      cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, opts.hpss ? &opts.hpss_spec : nullptr,
-                                      opts.pcen ? &opts.pcen_spec : nullptr, post, &opts.rhythm_spec, S, rates.data(), opts.resample_rate, g.rows.p,
-                                      rhythm_words, g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr,
-                                      opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(),
-                                      refs.data(), opts.loudness_norm ? o.loud.data() : nullptr, rhythm_refused.data(), &st, &err);
-    } else if (opts.hpss) {  // the chroma form with the HPSS stage in it
-      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
-      rc = vsyn_pcm_chain_hpss_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
-                                    cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, &opts.hpss_spec,
-                                    opts.pcen ? &opts.pcen_spec : nullptr, post, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
-                                    g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
-                                    opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
-                                    opts.loudness_norm ? o.loud.data() : nullptr, &st, &err);
-    } else if (opts.chroma_entry) {  // the form with every stage's spec and the chroma parameters; a NULL spec is a stage that is off
-      if (opts.loudness_norm) o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
-      rc = vsyn_pcm_chain_chroma_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr,
-                                      cond, &opts.spectral, opts.chroma_given ? &opts.chroma_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr, post,
-                                      S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(),
-                                      opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
-                                      opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
-                                      opts.loudness_norm ? o.loud.data() : nullptr, &st, &err);
-    } else if (opts.loudness_norm) {  // the one form with every stage's spec
-      o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
-      rc = vsyn_pcm_chain_spectral_host(g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, &opts.loudness_spec, cond, &opts.spectral,
-                                        opts.pcen ? &opts.pcen_spec : nullptr, post, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
-                                        g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
-                                        opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(), o.loud.data(), &st, &err);
-    } else if (opts.pcen)  // the two forms with the PCEN stage in them; off, today's entries
-      rc = opts.split ? vsyn_pcm_split_spectral_pcen_host(g.handle, &opts.trim_spec, cond, &opts.spectral, &opts.pcen_spec, post, S, rates.data(),
-                                                          opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(), o.counts.data(),
-                                                          o.iv.data(), o.iv_stride, peaks.data(), refs.data(), &st, &err)
-                      : vsyn_pcm_trim_spectral_pcen_host(g.handle, opts.trim ? &opts.trim_spec : nullptr, cond, &opts.spectral, &opts.pcen_spec, post, S,
-                                                         rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(),
-                                                         peaks.data(), refs.data(), &st, &err);
-    else
-      rc = opts.split ? vsyn_pcm_split_spectral_host(g.handle, &opts.trim_spec, cond, &opts.spectral, post, S, rates.data(), opts.resample_rate,
-                                                     g.rows.p, spec_rows, g.seg_rows.p, joined.data(), o.counts.data(), o.iv.data(), o.iv_stride,
-                                                     peaks.data(), refs.data(), &st, &err)
-                      : vsyn_pcm_trim_spectral_host(g.handle, opts.trim ? &opts.trim_spec : nullptr, cond, &opts.spectral, post, S, rates.data(),
-                                                    opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, o.bounds.data(), peaks.data(),
-                                                    refs.data(), &st, &err);
+    if (opts.loudness_norm) o.loud.assign(S, NO_LOUDNESS_RECORD);
+    const int rc = vsyn_pcm_chain_rhythm_host(
+        g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr, cond, &opts.spectral,
+        opts.chroma_given ? &opts.chroma_spec : nullptr, opts.hpss ? &opts.hpss_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr,
+        post_run(opts) ? &opts.post : nullptr, opts.rhythm ? &opts.rhythm_spec : nullptr, S, rates.data(), opts.resample_rate, g.rows.p,
+        opts.rhythm ? rhythm_words : spec_rows, g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr,
+        opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
+        opts.loudness_norm ? o.loud.data() : nullptr, rhythm_refused.data(), &st, &err);
     if (rc == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
       for (uint32_t s = 0; s < S; ++s) o.err[s] = std::string("spectral: ") + (err ? err : "refused");
       for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
@@ -834,7 +760,7 @@ struct Feeder {
     const uint32_t S = (uint32_t)g.pending.size();
     std::vector<uint32_t> rates(S);
     for (uint32_t s = 0; s < S; ++s) rates[s] = o.err[s].empty() ? g.pending[s]->header.audio_sample_rate : 0;
-    o.loud.assign(S, vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u});
+    o.loud.assign(S, NO_LOUDNESS_RECORD);
     o.loud_nb.assign(S, 0);
     vsyn_status st;
     const char* err = nullptr;
@@ -1309,37 +1235,6 @@ struct SplitOuts {
   }
 };
 
-// A rows run (features or spectral, as set in opts).
-int rows_corpus(const char* name, const uint8_t* const* datas, const size_t* lens, size_t num_files, const CorpusOptions& opts, float** rows_out,
-                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out,
-                uint64_t* bounds_out = nullptr, const SplitOuts* so = nullptr, vsyn_loudness_record* records_out = nullptr) {
-  if (so) so->begin(num_files);
-  const int rc = malloc_corpus(name, datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
-                               [&](size_t i, const CorpusFileResult& res, bool bad) {
-                                 if (rows_count_out) rows_count_out[i] = res.feature_rows;
-                                 if (records_out) records_out[i] = bad ? vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u} : res.loudness;
-                                 give_bounds(bounds_out, i, res, bad);
-                                 if (so && so->frames_out) so->frames_out[i] = bad ? 0 : res.frames;
-                                 if (so) give_intervals(so->intervals_out, so->intervals_count_out, i, res, bad);
-                               });
-  if (rc && so) so->clear(num_files);
-  return rc;
-}
-
-}  // namespace
-
-extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
-                                          uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
-                                          uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
-                                          double* stats_out, const char** error_out) {
-  if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_features_corpus: no feature kind", error_out);
-  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
-  opts.features = *spec;
-  return rows_corpus("features", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
-}
-
-namespace {
-
 // What a run with the normaliser asks of its spec (include/vorbis_synth_hip.h, "loudness", step 7).
 bool loud_norm_spec_ok(const vsyn_loudness_spec* l, const vsyn_pcm_cond* cond) {
   return l->options == VSYN_LOUD_NORMALIZE && l->channel_mode == VSYN_LOUD_MONO && l->target >= -70.0 && l->target <= 0.0 &&
@@ -1371,84 +1266,192 @@ std::string stretch_refusal(const vsyn_pcm_stretch* e, size_t num_files, const d
   return std::string();
 }
 
-// ogg_vorbis_spectral_corpus (target_rate 0) and ogg_vorbis_spectral_corpus_sr; fn: the entry point, for its refusal text.
-int spectral_corpus(const char* fn, const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
-                    uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
-                    const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
-                    const char** error_out_per_file, double* stats_out, const char** error_out, const vsyn_pcm_cond* cond = nullptr,
-                    const vsyn_pcm_trim* trim = nullptr, uint64_t* bounds_out = nullptr, const vsyn_pcm_trim* split = nullptr,
-                    const SplitOuts* so = nullptr, const vsyn_spectral_pcen* pcen = nullptr, const vsyn_loudness_spec* loud = nullptr,
-                    vsyn_loudness_record* records_out = nullptr, bool chroma_entry = false, const vsyn_spectral_chroma* chroma = nullptr,
-                    const vsyn_spectral_hpss* hpss = nullptr, const vsyn_rhythm_spec* rhythm = nullptr) {
-  if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": no spectral kind", error_out);
-  if (post && !vsyn_spectral_post_dim(spec, post))
-    return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or post spec", error_out);
-  if (chroma_entry && !vsyn_spectral_chroma_dim(spec, chroma))
-    return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid spectral or chroma spec", error_out);
-  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
-  opts.spectral = *spec;
-  opts.chroma_entry = chroma_entry;
-  if (chroma) {
-    opts.chroma_given = true;
-    opts.chroma_spec = *chroma;
+// One exported rows or PCM corpus call: its files, the options its entry fills through the setters below, and where its per-file
+// results go (any output may be NULL). An entry names its outputs, calls the setters of the stages it takes in the order the call's
+// refusals are checked in, and ends in rows() or pcm(); the first refusal stands and is the call's answer there. fn is the entry's
+// name for the refusal texts of a rows call, and NULL for a PCM call, whose refusals carry fixed names whichever entry was called.
+struct CorpusCall {
+  const char* fn;
+  const uint8_t* const* datas;
+  const size_t* lens;
+  size_t num_files;
+  CorpusOptions opts;
+  void** out;                             // per file: the rows, or the PCM
+  uint8_t* ok_out;
+  const char** error_out_per_file;
+  double* stats_out;
+  const char** error_out;
+  uint64_t* rows_count_out = nullptr;
+  uint64_t* frames_out = nullptr;         // a PCM call's frames (a rows call's joined frames are split.frames_out)
+  uint32_t* channels_out = nullptr;
+  uint32_t* rate_out = nullptr;
+  uint64_t* bounds_out = nullptr;
+  SplitOuts split;
+  vsyn_loudness_record* records_out = nullptr;
+  std::string refusal;
+
+  CorpusCall(const char* fn_, const uint8_t* const* datas_, const size_t* lens_, size_t num_files_, int threads, int feeders,
+             uint32_t files_per_submit, int device, void** out_, uint8_t* ok_out_, const char** error_out_per_file_, double* stats_out_,
+             const char** error_out_)
+      : fn(fn_), datas(datas_), lens(lens_), num_files(num_files_), opts(call_options(threads, feeders, files_per_submit, device)), out(out_),
+        ok_out(ok_out_), error_out_per_file(error_out_per_file_), stats_out(stats_out_), error_out(error_out_) {}
+
+  void refuse(const char* pcm_entry, const std::string& why) {
+    if (refusal.empty()) refusal = std::string(fn ? fn : pcm_entry) + ": " + why;
   }
-  opts.resample_rate = target_rate;
-  if (post) opts.post = *post;
-  if (pcen) {
-    opts.pcen = true;
-    opts.pcen_spec = *pcen;
+
+  // The outputs of a split, nulled before anything else. The joined frames are written by a split run alone: a call that takes a
+  // gate which is no split (split_run = false) has them zeroed here.
+  void split_outputs(uint64_t* joined_frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out, bool split_run) {
+    split.frames_out = joined_frames_out;
+    split.intervals_out = intervals_out;
+    split.intervals_count_out = intervals_count_out;
+    split.begin(num_files);
+    for (size_t i = 0; !split_run && joined_frames_out && i < num_files; ++i) joined_frames_out[i] = 0;
   }
-  if (hpss) {
+
+  void spectral(const vsyn_spectral_spec* spec, uint32_t target_rate, const vsyn_spectral_post* post) {
+    if (!spec || spec->kind == 0) return refuse(fn, "no spectral kind");
+    if (post && !vsyn_spectral_post_dim(spec, post)) return refuse(fn, "invalid spectral or post spec");
+    opts.spectral = *spec;
+    opts.resample_rate = target_rate;
+    if (post) opts.post = *post;
+  }
+  // the chroma parameters of the entries that take them (NULL: the defaults): they refuse a spec the chroma dimension has no answer for
+  void chroma(const vsyn_spectral_chroma* chroma) {
+    if (!vsyn_spectral_chroma_dim(&opts.spectral, chroma)) return refuse(fn, "invalid spectral or chroma spec");
+    if (chroma) {
+      opts.chroma_given = true;
+      opts.chroma_spec = *chroma;
+    }
+  }
+  void hpss(const vsyn_spectral_hpss* hpss) {
+    if (!hpss) return;
     opts.hpss = true;
     opts.hpss_spec = *hpss;
   }
-  if (rhythm) {
-    if (post_run(opts)) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": delta / normalize are not available with the rhythm stages", error_out);
+  void pcen(const vsyn_spectral_pcen* pcen) {
+    if (!pcen) return;
+    opts.pcen = true;
+    opts.pcen_spec = *pcen;
+  }
+  void rhythm(const vsyn_rhythm_spec* rhythm) {
+    if (post_run(opts)) return refuse(fn, "delta / normalize are not available with the rhythm stages");
     if (rhythm->output > VSYN_RHYTHM_TEMPO_MEAN || (rhythm->output == VSYN_RHYTHM_TEMPOGRAM && !vsyn_tempogram_tile(rhythm->tempogram.win_length)))
-      return refuse_call((void**)rows_out, num_files, std::string(fn) + ": unknown rhythm output, or tempogram rows without a win_length in [2, 2048]", error_out);
+      return refuse(fn, "unknown rhythm output, or tempogram rows without a win_length in [2, 2048]");
     opts.rhythm = true;
     opts.rhythm_spec = *rhythm;
   }
-  if (cond) {
+  void pcm_format(int format, uint32_t target_rate) {
+    if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return refuse("ogg_vorbis_pcm_corpus", "unknown PCM format " + std::to_string(format));
+    opts.pcm_s16 = format == VSYN_PCM_S16;
+    opts.resample_rate = target_rate;
+  }
+  void cond(const vsyn_pcm_cond* cond) {
+    if (!cond) return;
     opts.condition = true;
     opts.cond = *cond;
   }
-  if (trim) {
-    if (!vsyn_pcm_trim_num_frames(trim, 1)) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid trim spec", error_out);
-    opts.condition = opts.trim = true;  // the rows come from the trimmed mono plane
-    opts.trim_spec = *trim;
+  // the gate: a trim, or with is_split a split in its place; the output is then the trimmed or the joined mono plane
+  void gate(const vsyn_pcm_trim* gate, bool is_split) {
+    if (!gate) return;
+    if (!vsyn_pcm_trim_num_frames(gate, 1))
+      return is_split ? refuse("ogg_vorbis_pcm_corpus_split", "invalid split spec") : refuse("ogg_vorbis_pcm_corpus_trim", "invalid trim spec");
+    opts.condition = true;
+    (is_split ? opts.split : opts.trim) = true;
+    opts.trim_spec = *gate;
   }
-  if (split) {
-    if (!vsyn_pcm_trim_num_frames(split, 1)) return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid split spec", error_out);
-    opts.condition = opts.split = true;  // the rows come from the joined mono plane
-    opts.trim_spec = *split;
-  }
-  if (loud) {
+  // the stages behind the gate; each makes a PCM call deliver one mono plane per file
+  void loud(const vsyn_loudness_spec* loud) {
+    if (!loud) return;
     if (!loud_norm_spec_ok(loud, opts.condition ? &opts.cond : nullptr))
-      return refuse_call((void**)rows_out, num_files, std::string(fn) + ": invalid loudness spec (a target in [-70, 0], the mono downmix, no peak)", error_out);
+      return refuse("ogg_vorbis_pcm_corpus_loud", "invalid loudness spec (a target in [-70, 0], the mono downmix, no peak)");
+    if (!fn) opts.condition = true;
     opts.loudness_norm = true;
     opts.loudness_spec = *loud;
   }
-  return rows_corpus("spectral", datas, lens, num_files, opts, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out,
-                     bounds_out, split ? so : nullptr, records_out);
-}
+  void effect(const vsyn_pcm_effect* effect) {
+    if (!effect) return;
+    if (!effect_spec_ok(effect))
+      return refuse("ogg_vorbis_pcm_corpus_effects",
+                    "invalid effect spec (n_fft a power of two in [16, 8192], hop_length >= 1, win_length in [1, n_fft], odd kernel sizes up to 63, "
+                    "the component as output)");
+    opts.condition = opts.effect = true;
+    opts.effect_spec = *effect;
+  }
+  void stretch(const vsyn_pcm_stretch* stretch, const double* stretch_rates, const uint32_t* shift_from_hz) {
+    if (!stretch) return;
+    if (std::string why = stretch_refusal(stretch, num_files, stretch_rates, shift_from_hz); !why.empty() || opts.effect)
+      return refuse("ogg_vorbis_pcm_corpus_stretch", opts.effect ? std::string("a stretch and an hpss effect in one call are not built") : why);
+    opts.condition = opts.stretch = true;
+    opts.stretch_spec = *stretch;
+    opts.stretch_rates = stretch_rates;
+    opts.stretch_from_hz = shift_from_hz;
+  }
+
+  // The run, or the refusal, and what both leave in the outputs. The joined frames and the intervals are a split run's.
+  template <typename PerFile>
+  int run(const char* name, PerFile per_file) {
+    if (!refusal.empty()) return refuse_call(out, num_files, refusal, error_out);
+    const int rc = malloc_corpus(name, datas, lens, num_files, opts, out, ok_out, error_out_per_file, stats_out, error_out,
+                                 [&](size_t i, const CorpusFileResult& res, bool bad) {
+                                   per_file(i, res, bad);
+                                   if (records_out) records_out[i] = bad ? NO_LOUDNESS_RECORD : res.loudness;
+                                   give_bounds(bounds_out, i, res, bad);
+                                   if (opts.split) give_intervals(split.intervals_out, split.intervals_count_out, i, res, bad);
+                                 });
+    if (rc) split.clear(num_files);
+    return rc;
+  }
+  int rows(const char* name = "spectral") {  // a rows run (features or spectral, as set in opts)
+    return run(name, [&](size_t i, const CorpusFileResult& res, bool bad) {
+      if (rows_count_out) rows_count_out[i] = res.feature_rows;
+      if (opts.split && split.frames_out) split.frames_out[i] = bad ? 0 : res.frames;
+    });
+  }
+  int pcm() {
+    return run("pcm", [&](size_t i, const CorpusFileResult& res, bool bad) {
+      if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+      if (channels_out) channels_out[i] = res.channels;
+      if (rate_out) rate_out[i] = res.sample_rate;
+    });
+  }
+};
 
 }  // namespace
+
+extern "C" int ogg_vorbis_features_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, const vsyn_feature_spec* spec, float** rows_out,
+                                          uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
+                                          double* stats_out, const char** error_out) {
+  if (!spec || spec->kind == 0) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_features_corpus: no feature kind", error_out);
+  CorpusCall c("ogg_vorbis_features_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  c.rows_count_out = rows_count_out;
+  c.opts.features = *spec;
+  return c.rows("features");
+}
 
 extern "C" int ogg_vorbis_spectral_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                           uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, float** rows_out,
                                           uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                           double* stats_out, const char** error_out) {
-  return spectral_corpus("ogg_vorbis_spectral_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, 0, nullptr,
-                         rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+  CorpusCall c("ogg_vorbis_spectral_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  c.rows_count_out = rows_count_out;
+  c.spectral(spec, 0, nullptr);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_sr(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                              uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, uint32_t target_rate,
                                              float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                              double* stats_out, const char** error_out) {
-  return spectral_corpus("ogg_vorbis_spectral_corpus_sr", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
-                         nullptr, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+  CorpusCall c("ogg_vorbis_spectral_corpus_sr", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  c.rows_count_out = rows_count_out;
+  c.spectral(spec, target_rate, nullptr);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_post(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1456,8 +1459,11 @@ extern "C" int ogg_vorbis_spectral_corpus_post(const uint8_t* const* datas, cons
                                                const vsyn_spectral_post* post, float** rows_out, uint64_t* rows_count_out, uint8_t* ok_out,
                                                const char** error_out_per_file, double* stats_out, const char** error_out) {
   if (!post) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_spectral_corpus_post: no post spec", error_out);
-  return spectral_corpus("ogg_vorbis_spectral_corpus_post", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
-                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out);
+  CorpusCall c("ogg_vorbis_spectral_corpus_post", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  c.rows_count_out = rows_count_out;
+  c.spectral(spec, target_rate, post);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_cond(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1465,8 +1471,12 @@ extern "C" int ogg_vorbis_spectral_corpus_cond(const uint8_t* const* datas, cons
                                                const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, float** rows_out,
                                                uint64_t* rows_count_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
                                                const char** error_out) {
-  return spectral_corpus("ogg_vorbis_spectral_corpus_cond", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
-                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond);
+  CorpusCall c("ogg_vorbis_spectral_corpus_cond", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  c.rows_count_out = rows_count_out;
+  c.spectral(spec, target_rate, post);
+  c.cond(cond);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_trim(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1474,8 +1484,14 @@ extern "C" int ogg_vorbis_spectral_corpus_trim(const uint8_t* const* datas, cons
                                                const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim,
                                                float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out, uint8_t* ok_out,
                                                const char** error_out_per_file, double* stats_out, const char** error_out) {
-  return spectral_corpus("ogg_vorbis_spectral_corpus_trim", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
-                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, trim, bounds_out);
+  CorpusCall c("ogg_vorbis_spectral_corpus_trim", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.spectral(spec, target_rate, post);
+  c.cond(cond);
+  c.gate(trim, false);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1494,26 +1510,20 @@ extern "C" int ogg_vorbis_pcm_corpus_cond(const uint8_t* const* datas, const siz
                                     pcm_out, frames_out, channels_out, rate_out, nullptr, ok_out, error_out_per_file, stats_out, error_out);
 }
 
-namespace {
-
-// ogg_vorbis_pcm_corpus_trim, and with split != NULL ogg_vorbis_pcm_corpus_split (intervals_only: ogg_vorbis_intervals_corpus).
-int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders, uint32_t files_per_submit, int device,
-               uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
-               uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
-               double* stats_out, const char** error_out, const vsyn_pcm_trim* split = nullptr, bool intervals_only = false,
-               const SplitOuts* so = nullptr, const vsyn_loudness_spec* loud = nullptr, vsyn_loudness_record* records_out = nullptr,
-               const vsyn_pcm_effect* effect = nullptr, const vsyn_pcm_stretch* stretch = nullptr, const double* stretch_rates = nullptr,
-               const uint32_t* shift_from_hz = nullptr);
-
-}  // namespace
-
 extern "C" int ogg_vorbis_pcm_corpus_trim(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                           uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
                                           const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out,
                                           uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
                                           double* stats_out, const char** error_out) {
-  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, trim, pcm_out, frames_out,
-                    channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out);
+  CorpusCall c(nullptr, datas, lens, num_files, threads, feeders, files_per_submit, device, pcm_out, ok_out, error_out_per_file, stats_out, error_out);
+  c.frames_out = frames_out;
+  c.channels_out = channels_out;
+  c.rate_out = rate_out;
+  c.bounds_out = bounds_out;
+  c.pcm_format(format, target_rate);
+  c.cond(cond);
+  c.gate(trim, false);
+  return c.pcm();
 }
 
 extern "C" int ogg_vorbis_pcm_corpus_split(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1521,11 +1531,15 @@ extern "C" int ogg_vorbis_pcm_corpus_split(const uint8_t* const* datas, const si
                                            const vsyn_pcm_trim* split, void** pcm_out, uint64_t* frames_out, uint32_t* channels_out,
                                            uint32_t* rate_out, uint32_t** intervals_out, uint64_t* intervals_count_out, uint8_t* ok_out,
                                            const char** error_out_per_file, double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, nullptr, pcm_out, frames_out,
-                    channels_out, rate_out, nullptr, ok_out, error_out_per_file, stats_out, error_out, split, false, &so);
+  CorpusCall c(nullptr, datas, lens, num_files, threads, feeders, files_per_submit, device, pcm_out, ok_out, error_out_per_file, stats_out, error_out);
+  c.frames_out = frames_out;
+  c.channels_out = channels_out;
+  c.rate_out = rate_out;
+  c.split_outputs(nullptr, intervals_out, intervals_count_out, true);
+  c.pcm_format(format, target_rate);
+  c.cond(cond);
+  c.gate(split, true);
+  return c.pcm();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_split(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1534,14 +1548,14 @@ extern "C" int ogg_vorbis_spectral_corpus_split(const uint8_t* const* datas, con
                                                 float** rows_out, uint64_t* rows_count_out, uint64_t* frames_out, uint32_t** intervals_out,
                                                 uint64_t* intervals_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                                 double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.frames_out = frames_out;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  so.begin(num_files);
-  return spectral_corpus("ogg_vorbis_spectral_corpus_split", datas, lens, num_files, threads, feeders, files_per_submit, device, spec,
-                         target_rate, post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, nullptr, nullptr,
-                         split, &so);
+  CorpusCall c("ogg_vorbis_spectral_corpus_split", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  c.rows_count_out = rows_count_out;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, true);  // (split = NULL: frames_out keeps the caller's bytes)
+  c.spectral(spec, target_rate, post);
+  c.cond(cond);
+  c.gate(split, true);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_pcen(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1551,100 +1565,33 @@ extern "C" int ogg_vorbis_spectral_corpus_pcen(const uint8_t* const* datas, cons
                                                uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
                                                uint64_t* intervals_count_out, uint8_t* ok_out, const char** error_out_per_file,
                                                double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.frames_out = frames_out;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  so.begin(num_files);
+  CorpusCall c("ogg_vorbis_spectral_corpus_pcen", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
   const bool split = gate && gate_is_split;
-  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
-  return spectral_corpus("ogg_vorbis_spectral_corpus_pcen", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
-                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
-                         split ? gate : nullptr, &so, pcen);
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
+  c.spectral(spec, target_rate, post);
+  c.pcen(pcen);
+  c.cond(cond);
+  c.gate(gate, split);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_intervals_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                            uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pcm_trim* split,
                                            uint32_t** intervals_out, uint64_t* intervals_count_out, uint64_t* frames_out, uint32_t* rate_out,
                                            uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  so.begin(num_files);
-  if (!split) return refuse_call(nullptr, num_files, "ogg_vorbis_intervals_corpus: no split spec", error_out);
-  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, VSYN_PCM_F32, nullptr, nullptr, nullptr,
-                    frames_out, nullptr, rate_out, nullptr, ok_out, error_out_per_file, stats_out, error_out, split, true, &so);
+  CorpusCall c(nullptr, datas, lens, num_files, threads, feeders, files_per_submit, device, nullptr, ok_out, error_out_per_file, stats_out, error_out);
+  c.frames_out = frames_out;
+  c.rate_out = rate_out;
+  c.split_outputs(nullptr, intervals_out, intervals_count_out, true);
+  if (!split) c.refuse("ogg_vorbis_intervals_corpus", "no split spec");
+  c.pcm_format(VSYN_PCM_F32, target_rate);
+  c.gate(split, true);
+  c.opts.intervals_only = true;  // no joined plane is made, and no PCM is delivered
+  return c.pcm();
 }
-
-namespace {
-
-int pcm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders, uint32_t files_per_submit, int device,
-               uint32_t target_rate, int format, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* trim, void** pcm_out, uint64_t* frames_out,
-               uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out, uint8_t* ok_out, const char** error_out_per_file,
-               double* stats_out, const char** error_out, const vsyn_pcm_trim* split, bool intervals_only, const SplitOuts* so,
-               const vsyn_loudness_spec* loud, vsyn_loudness_record* records_out, const vsyn_pcm_effect* effect, const vsyn_pcm_stretch* stretch,
-               const double* stretch_rates, const uint32_t* shift_from_hz) {
-  if (so) so->begin(num_files);
-  if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16)
-    return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus: unknown PCM format " + std::to_string(format), error_out);
-  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
-  opts.pcm_s16 = format == VSYN_PCM_S16;
-  opts.resample_rate = target_rate;
-  if (cond) {
-    opts.condition = true;
-    opts.cond = *cond;
-  }
-  if (trim) {
-    if (!vsyn_pcm_trim_num_frames(trim, 1)) return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus_trim: invalid trim spec", error_out);
-    opts.condition = opts.trim = true;  // one mono plane per file
-    opts.trim_spec = *trim;
-  }
-  if (split) {
-    if (!vsyn_pcm_trim_num_frames(split, 1)) return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus_split: invalid split spec", error_out);
-    opts.condition = opts.split = true;  // one mono plane per file, or with intervals_only none
-    opts.intervals_only = intervals_only;
-    opts.trim_spec = *split;
-  }
-  if (loud) {
-    if (!loud_norm_spec_ok(loud, cond) || intervals_only)
-      return refuse_call(pcm_out, num_files, "ogg_vorbis_pcm_corpus_loud: invalid loudness spec (a target in [-70, 0], the mono downmix, no peak)",
-                         error_out);
-    opts.condition = opts.loudness_norm = true;  // one mono plane per file
-    opts.loudness_spec = *loud;
-  }
-  if (effect) {
-    if (!effect_spec_ok(effect) || intervals_only)
-      return refuse_call(pcm_out, num_files,
-                         "ogg_vorbis_pcm_corpus_effects: invalid effect spec (n_fft a power of two in [16, 8192], hop_length >= 1, win_length in "
-                         "[1, n_fft], odd kernel sizes up to 63, the component as output)",
-                         error_out);
-    opts.condition = opts.effect = true;  // one mono plane per file
-    opts.effect_spec = *effect;
-  }
-  if (stretch) {
-    if (std::string why = stretch_refusal(stretch, num_files, stretch_rates, shift_from_hz); !why.empty() || intervals_only || effect)
-      return refuse_call(pcm_out, num_files,
-                         "ogg_vorbis_pcm_corpus_stretch: " + (effect ? std::string("a stretch and an hpss effect in one call are not built") : why),
-                         error_out);
-    opts.condition = opts.stretch = true;  // one mono plane per file
-    opts.stretch_spec = *stretch;
-    opts.stretch_rates = stretch_rates;
-    opts.stretch_from_hz = shift_from_hz;
-  }
-  const int rc = malloc_corpus("pcm", datas, lens, num_files, opts, pcm_out, ok_out, error_out_per_file, stats_out, error_out,
-                               [&](size_t i, const CorpusFileResult& res, bool bad) {
-                                 if (frames_out) frames_out[i] = bad ? 0 : res.frames;
-                                 if (records_out) records_out[i] = bad ? vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u} : res.loudness;
-                                 if (channels_out) channels_out[i] = res.channels;
-                                 if (rate_out) rate_out[i] = res.sample_rate;
-                                 give_bounds(bounds_out, i, res, bad);
-                                 if (so && split) give_intervals(so->intervals_out, so->intervals_count_out, i, res, bad);
-                               });
-  if (rc && so) so->clear(num_files);
-  return rc;
-}
-
-}  // namespace
 
 extern "C" int ogg_vorbis_pitch_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                        uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pitch_spec* spec, float** rows_out,
@@ -1686,13 +1633,9 @@ extern "C" int ogg_vorbis_pcm_corpus_loud(const uint8_t* const* datas, const siz
                                           uint64_t* frames_out, uint32_t* channels_out, uint32_t* rate_out, uint64_t* bounds_out,
                                           uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out,
                                           uint8_t* ok_out, const char** error_out_per_file, double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  const bool split = gate && gate_is_split;
-  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
-                    frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
-                    &so, loud, records_out);
+  return ogg_vorbis_pcm_corpus_effects(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, gate, gate_is_split,
+                                       nullptr, loud, pcm_out, frames_out, channels_out, rate_out, bounds_out, intervals_out, intervals_count_out,
+                                       records_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
 extern "C" int ogg_vorbis_pcm_corpus_effects(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1702,13 +1645,9 @@ extern "C" int ogg_vorbis_pcm_corpus_effects(const uint8_t* const* datas, const 
                                              uint32_t* rate_out, uint64_t* bounds_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
                                              vsyn_loudness_record* records_out, uint8_t* ok_out, const char** error_out_per_file,
                                              double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  const bool split = gate && gate_is_split;
-  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
-                    frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
-                    &so, loud, records_out, effect);
+  return ogg_vorbis_pcm_corpus_stretch(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, gate, gate_is_split,
+                                       effect, nullptr, nullptr, nullptr, loud, pcm_out, frames_out, channels_out, rate_out, bounds_out, intervals_out,
+                                       intervals_count_out, records_out, ok_out, error_out_per_file, stats_out, error_out);
 }
 
 extern "C" int ogg_vorbis_pcm_corpus_stretch(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1719,13 +1658,21 @@ extern "C" int ogg_vorbis_pcm_corpus_stretch(const uint8_t* const* datas, const 
                                              uint32_t* rate_out, uint64_t* bounds_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
                                              vsyn_loudness_record* records_out, uint8_t* ok_out, const char** error_out_per_file,
                                              double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
+  CorpusCall c(nullptr, datas, lens, num_files, threads, feeders, files_per_submit, device, pcm_out, ok_out, error_out_per_file, stats_out, error_out);
   const bool split = gate && gate_is_split;
-  return pcm_corpus(datas, lens, num_files, threads, feeders, files_per_submit, device, target_rate, format, cond, split ? nullptr : gate, pcm_out,
-                    frames_out, channels_out, rate_out, bounds_out, ok_out, error_out_per_file, stats_out, error_out, split ? gate : nullptr, false,
-                    &so, loud, records_out, effect, stretch, stretch_rates, shift_from_hz);
+  c.frames_out = frames_out;
+  c.channels_out = channels_out;
+  c.rate_out = rate_out;
+  c.bounds_out = bounds_out;
+  c.records_out = records_out;
+  c.split_outputs(nullptr, intervals_out, intervals_count_out, split);
+  c.pcm_format(format, target_rate);
+  c.cond(cond);
+  c.gate(gate, split);
+  c.loud(loud);
+  c.effect(effect);
+  c.stretch(stretch, stretch_rates, shift_from_hz);
+  return c.pcm();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1735,16 +1682,19 @@ extern "C" int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, cons
                                                uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
                                                uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                                const char** error_out_per_file, double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.frames_out = frames_out;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  so.begin(num_files);
+  CorpusCall c("ogg_vorbis_spectral_corpus_loud", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
   const bool split = gate && gate_is_split;
-  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
-  return spectral_corpus("ogg_vorbis_spectral_corpus_loud", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
-                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
-                         split ? gate : nullptr, &so, pcen, loud, records_out);
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.records_out = records_out;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
+  c.spectral(spec, target_rate, post);
+  c.pcen(pcen);
+  c.cond(cond);
+  c.gate(gate, split);
+  c.loud(loud);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1755,16 +1705,20 @@ extern "C" int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, co
                                                  uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
                                                  uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                                  const char** error_out_per_file, double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.frames_out = frames_out;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  so.begin(num_files);
+  CorpusCall c("ogg_vorbis_spectral_corpus_chroma", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
   const bool split = gate && gate_is_split;
-  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
-  return spectral_corpus("ogg_vorbis_spectral_corpus_chroma", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
-                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
-                         split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma);
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.records_out = records_out;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
+  c.spectral(spec, target_rate, post);
+  c.chroma(chroma);
+  c.pcen(pcen);
+  c.cond(cond);
+  c.gate(gate, split);
+  c.loud(loud);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1775,16 +1729,21 @@ extern "C" int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, cons
                                                uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out, uint32_t** intervals_out,
                                                uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                                const char** error_out_per_file, double* stats_out, const char** error_out) {
-  SplitOuts so;
-  so.frames_out = frames_out;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  so.begin(num_files);
+  CorpusCall c("ogg_vorbis_spectral_corpus_hpss", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
   const bool split = gate && gate_is_split;
-  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
-  return spectral_corpus("ogg_vorbis_spectral_corpus_hpss", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate,
-                         post, rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
-                         split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma, hpss);
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.records_out = records_out;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
+  c.spectral(spec, target_rate, post);
+  c.chroma(chroma);
+  c.pcen(pcen);
+  c.hpss(hpss);
+  c.cond(cond);
+  c.gate(gate, split);
+  c.loud(loud);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_rhythm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1796,16 +1755,22 @@ extern "C" int ogg_vorbis_rhythm_corpus(const uint8_t* const* datas, const size_
                                         uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                         const char** error_out_per_file, double* stats_out, const char** error_out) {
   if (!rhythm) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_rhythm_corpus: no rhythm spec", error_out);
-  SplitOuts so;
-  so.frames_out = frames_out;
-  so.intervals_out = intervals_out;
-  so.intervals_count_out = intervals_count_out;
-  so.begin(num_files);
+  CorpusCall c("ogg_vorbis_rhythm_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
   const bool split = gate && gate_is_split;
-  for (size_t i = 0; !split && frames_out && i < num_files; ++i) frames_out[i] = 0;
-  return spectral_corpus("ogg_vorbis_rhythm_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, spec, target_rate, post,
-                         rows_out, rows_count_out, ok_out, error_out_per_file, stats_out, error_out, cond, split ? nullptr : gate, bounds_out,
-                         split ? gate : nullptr, &so, pcen, loud, records_out, true, chroma, hpss, rhythm);
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.records_out = records_out;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
+  c.spectral(spec, target_rate, post);
+  c.chroma(chroma);
+  c.pcen(pcen);
+  c.hpss(hpss);
+  c.rhythm(rhythm);
+  c.cond(cond);
+  c.gate(gate, split);
+  c.loud(loud);
+  return c.rows();
 }
 
 extern "C" int ogg_vorbis_loudness_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -1824,7 +1789,7 @@ extern "C" int ogg_vorbis_loudness_corpus(const uint8_t* const* datas, const siz
   opts.resample_rate = target_rate;
   return malloc_corpus("loudness", datas, lens, num_files, opts, (void**)blocks_out, ok_out, error_out_per_file, stats_out, error_out,
                        [&](size_t i, const CorpusFileResult& res, bool bad) {
-                         if (records_out) records_out[i] = bad ? vsyn_loudness_record{0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u} : res.loudness;
+                         if (records_out) records_out[i] = bad ? NO_LOUDNESS_RECORD : res.loudness;
                          if (frames_out) frames_out[i] = bad ? 0 : res.frames;
                          if (rate_out) rate_out[i] = res.sample_rate;
                          const size_t n = bad || !want_blocks ? 0 : res.loudness_blocks.size();

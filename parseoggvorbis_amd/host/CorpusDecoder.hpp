@@ -79,7 +79,7 @@ struct CorpusOptions {
   // Residue kinds make the workers ship float residue (the VQ stage is off for them).
   vsyn_feature_spec features = {0, 0, 0, 0, 1.0, 1.0f, 0.0f, 1.0f, 0};
   // spectral run (spectral.kind != 0): synthesis as usual but VSYN_SUBMIT_KEEP_PCM, then each file's spectral rows from the PCM on
-  // the device (vsyn_pcm_spectral_host), delivered through gotFileFeatures; no PCM crosses the bus. Excludes features / pcm_s16.
+  // the device (vsyn_pcm_chain_rhythm_host), delivered through gotFileFeatures; no PCM crosses the bus. Excludes features / pcm_s16.
   vsyn_spectral_spec spectral = {0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
   // resample_rate != 0: the PCM (f32 or pcm_s16) and the spectral rows are those of each file's PCM resampled on the device from
   // its own rate to resample_rate (include/vorbis_synth_hip.h, "resampling"); frames and sample_rate in the results are the
@@ -112,7 +112,7 @@ struct CorpusOptions {
   // pcen (a spectral run of kind mel_power or lin_power): each file's rows go through the PCEN stage on the device between the
   // spectral rows and the post stage (include/vorbis_synth_hip.h, "PCEN"); with pcen_spec.b = 0 the coefficient comes from the rate
   // the rows are computed at (resample_rate, else the file's own) and spectral.hop_length. A spec the stage refuses (another kind
-  // among them) is every file's error. The default is off: today's rows and today's entry points.
+  // among them) is every file's error. The default is off: the rows without the stage.
   bool pcen = false;
   vsyn_spectral_pcen pcen_spec = {0.98, 2.0, 0.5, 0.4, 1e-6, 0.0, 1.0};
   // pitch run (pitch.frame_length != 0): synthesis as usual but VSYN_SUBMIT_KEEP_PCM, then each file's (f0, normalised difference)
@@ -132,34 +132,33 @@ struct CorpusOptions {
   // loudness_norm (a PCM run with condition, or a spectral run): each file's mono plane is normalised to loudness_spec.target on
   // the device between the gate and conditioning ("loudness", step 7: VSYN_LOUD_NORMALIZE, VSYN_LOUD_MONO; excludes VSYN_COND_PEAK);
   // the record goes to CorpusFileResult::loudness. A file the stage refuses, a silent one included, fails alone, by name. The
-  // default is off: today's output and today's entry points.
+  // default is off: the output without the stage.
   bool loudness = false, loudness_blocks = false, loudness_norm = false;
   vsyn_loudness_spec loudness_spec = {0u, VSYN_LOUD_SUM, 0.0};
-  // chroma_entry (a spectral run): the rows come through vsyn_pcm_chain_chroma_host, whatever stages are on, with chroma_spec
-  // (chroma_given) or NULL for the defaults (include/vorbis_synth_hip.h, "chroma"). The kinds VSYN_SPEC_CHROMA and VSYN_SPEC_TONNETZ
-  // without it run with the default chroma parameters through today's entry points, as every spectral entry point serves them.
-  bool chroma_entry = false, chroma_given = false;
+  // chroma_given (a spectral run of kind VSYN_SPEC_CHROMA or VSYN_SPEC_TONNETZ): the rows are computed with chroma_spec, else with
+  // the default chroma parameters (include/vorbis_synth_hip.h, "chroma"). Another kind does not read them.
+  bool chroma_given = false;
   vsyn_spectral_chroma chroma_spec = {12u, VSYN_CHROMA_NORM_MAX, VSYN_CHROMA_BASE_C, 0u, 0.0, 5.0, 2.0};
   // hpss (a spectral run of kind mel_power or lin_power): each file's rows go through the HPSS stage on the device between the
-  // spectral rows and PCEN (include/vorbis_synth_hip.h, "HPSS"), through vsyn_pcm_chain_hpss_host. A spec the stage refuses (another
-  // kind, or PCEN on the mask or the median) is every file's error. The default is off: today's rows and today's entry points.
+  // spectral rows and PCEN (include/vorbis_synth_hip.h, "HPSS"). A spec the stage refuses (another kind, or PCEN on the mask or the
+  // median) is every file's error. The default is off: the rows without the stage.
   bool hpss = false;
   vsyn_spectral_hpss hpss_spec = {31u, 31u, VSYN_HPSS_HARMONIC, VSYN_HPSS_OUT_COMPONENT, 2.0, 1.0, 1.0};
   // effect (a PCM run with condition): each file's mono plane is replaced by its harmonic or percussive component on the device
-  // between the gate and the loudness normaliser (include/vorbis_synth_hip.h, "PCM effects"), through vsyn_pcm_chain_effects_host.
-  // The default is off: today's output and today's entry points.
+  // between the gate and the loudness normaliser (include/vorbis_synth_hip.h, "PCM effects"). The default is off: the output
+  // without the stage.
   bool effect = false;
   vsyn_pcm_effect effect_spec = {2048u, 512u, 2048u, 0u, {31u, 31u, VSYN_HPSS_HARMONIC, VSYN_HPSS_OUT_COMPONENT, 2.0, 1.0, 1.0}};
   // stretch (a PCM run with condition): each file's mono plane is time-stretched at its own rate, and with stretch_spec.shift_to_hz
-  // resampled behind that (a pitch shift), in the effect's slot (include/vorbis_synth_hip.h, "PCM stretch"), through
-  // vsyn_pcm_chain_stretch_host. stretch_rates and stretch_from_hz (the latter only with a shift) hold one value per FILE of the
-  // call, indexed by the file's index, and must outlive the run. The default is off: today's output and today's entry points.
+  // resampled behind that (a pitch shift), in the effect's slot (include/vorbis_synth_hip.h, "PCM stretch"). stretch_rates and
+  // stretch_from_hz (the latter only with a shift) hold one value per FILE of the call, indexed by the file's index, and must
+  // outlive the run. The default is off: the output without the stage.
   bool stretch = false;
   vsyn_pcm_stretch stretch_spec = {2048u, 512u, 2048u, 0u, 0u, 0u};
   const double* stretch_rates = nullptr;
   const uint32_t* stretch_from_hz = nullptr;
   // rhythm (a spectral run of a kind with 1 to 256 columns): the rows stay on the device and go through the onset stage and what
-  // rhythm_spec.output selects behind it (include/vorbis_synth_hip.h, "rhythm"), through vsyn_pcm_chain_rhythm_host; a file's "rows"
+  // rhythm_spec.output selects behind it (include/vorbis_synth_hip.h, "rhythm"); a file's "rows"
   // are then that output's words (1 column, win_length columns, or 2 for the mean's float64 values). A spec the stages refuse is
   // every file's error; an envelope that is not finite, or a window length outside [2, 2048], is that file's. The default is off.
   bool rhythm = false;
@@ -336,7 +335,7 @@ int ogg_vorbis_spectral_corpus_loud(const uint8_t* const* datas, const size_t* l
                                     const char** error_out_per_file, double* stats_out, const char** error_out);
 // ogg_vorbis_spectral_corpus_loud with every stage's spec NULL-able (loud = NULL: no normaliser, records_out zeroed) and the chroma
 // parameters of the kinds VSYN_SPEC_CHROMA and VSYN_SPEC_TONNETZ (chroma = NULL: the defaults; not read for another kind): the rows
-// come through vsyn_pcm_chain_chroma_host (CorpusOptions::chroma_entry), dim = vsyn_spectral_chroma_dim(spec, chroma), times
+// are computed with them (CorpusOptions::chroma_given, chroma_spec), dim = vsyn_spectral_chroma_dim(spec, chroma), times
 // 1 + post->order with the post stage. A chroma spec the stage refuses refuses the call. Same output contract.
 int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                       uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,

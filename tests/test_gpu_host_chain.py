@@ -259,7 +259,8 @@ def test_refusals_at_every_host_entry(chain):
 
 def test_nested_forms_agree_bit_for_bit(chain, mods):  # noqa: F811
     """A NULL gate, a NULL conditioning spec and a post stage that is off: the rows, row counts, PCM, frames and peaks of the entry
-    without them, natively and resampled, float32 and int16."""
+    without them, natively and resampled, float32 and int16. Then the chain entries, stage by stage (_chain_entries_nest; the
+    loudness records of the fixture's short segments all carry status 2, VSYN_LOUD_TOO_SHORT)."""
     from parseoggvorbis_amd.binding import SpectralPost
     c, _ = chain
     g, s, S = c.g, c.spec, c.S
@@ -286,6 +287,66 @@ def test_nested_forms_agree_bit_for_bit(chain, mods):  # noqa: F811
                     assert f["pcm"].dtype == out.dtype and np.array_equal(f["pcm"].view(np.uint8), out.view(np.uint8)), (q, fmt)
                     assert np.array_equal(f["frames"], frames) and np.array_equal(f["peaks"].view(np.uint32), peaks.view(np.uint32)), (q, fmt)
                     assert not f["refs"].any()
+    _chain_entries_nest(c, mods[1])
+
+
+def _agree(wide, narrow, what):
+    """The arrays two Synth methods returned (dicts, or pcm_condition_host's tuple), byte for byte: every one both have (of the
+    intervals what the counts cover, which is what the methods return), and zeros in what the wider entry alone has."""
+    if isinstance(narrow, tuple):
+        narrow = dict(zip(("pcm", "frames", "peaks"), narrow))
+    arrays = 0
+    for k, v in wide.items():
+        if k == "intervals":
+            assert all(np.array_equal(p, q) for p, q in zip(v, narrow.get(k, [np.zeros((0, 2))] * len(v)))), (what, k)
+        elif not isinstance(v, np.ndarray):
+            assert k not in narrow or v == narrow[k], (what, k)
+        elif k in narrow:
+            assert v.dtype == narrow[k].dtype and np.array_equal(v.view(np.uint8), narrow[k].view(np.uint8)), (what, k)
+            arrays += 1
+        else:
+            assert not v.view(np.uint8).any(), (what, k)
+    assert not set(narrow) - set(wide) and arrays >= 2, what
+
+
+def _chain_entries_nest(c, spectral):
+    """The chain entries, each with its newest stage passed as NULL, against the entry without that stage, down to the gated
+    entries: out_rate 0 and OUT, no gate, a trim and a split, float32 and int16 for the PCM forms, the stages that stay on in both
+    calls of a pair at the smallest specs they accept. The fixture's segments are a fraction of a second: the normaliser reports
+    every one VSYN_LOUD_TOO_SHORT (record status 2), so the pairs bind the plumbing and not the stage."""
+    from parseoggvorbis_amd.binding import LoudnessSpec, PcmEffect, SpectralHpss, VSYN_LOUD_MONO, VSYN_LOUD_NORMALIZE, VSYN_LOUD_TOO_SHORT
+    g, S = c.g, c.S
+    rates = [RATE] * S
+    loud = LoudnessSpec(VSYN_LOUD_NORMALIZE, VSYN_LOUD_MONO, -23.0)
+    hpss = SpectralHpss(5, 5, 0, 0, 2.0, 1.0, 1.0)
+    effect = PcmEffect(256, 64, 256, 0, hpss)
+    pre = _cond(False, A)  # (the normaliser excludes the peak)
+    power = spectral.spectral_spec(kind="mel_power", n_fft=400, hop_length=160, n_mels=40)  # (what HPSS and PCEN take)
+    pcen = spectral.pcen_spec()
+    for q in (0, OUT):
+        for name, gate, split in (("none", None, 0), ("trim", c.gate, 0), ("split", c.gate, 1)):
+            for fmt in (2, 1):
+                w = (q, name, fmt)
+                eff = g.pcm_chain_effects_host(gate, split, effect, loud, pre, S, rates, q, fmt)
+                assert (eff["records"]["status"] == VSYN_LOUD_TOO_SHORT).all(), (w, eff["records"]["status"])
+                _agree(g.pcm_chain_stretch_host(gate, split, effect, None, None, None, loud, pre, S, rates, q, fmt), eff, (w, "stretch"))
+                _agree(g.pcm_chain_effects_host(gate, split, None, loud, pre, S, rates, q, fmt),
+                       g.pcm_chain_host(gate, split, loud, pre, S, rates, q, fmt), (w, "effect"))
+                gated = (g.pcm_condition_host(c.cond, S, rates, q, fmt) if gate is None else
+                         g.pcm_split_host(gate, c.cond, S, rates, q, fmt) if split else g.pcm_trim_host(gate, c.cond, S, rates, q, fmt))
+                _agree(g.pcm_chain_host(gate, split, None, c.cond, S, rates, q, fmt), gated, (w, "loud"))
+            w = (q, name)
+            _agree(g.pcm_chain_rhythm_host(gate, split, loud, pre, power, None, hpss, pcen, None, None, rates, q),
+                   g.pcm_chain_hpss_host(gate, split, loud, pre, power, None, hpss, pcen, None, rates, q), (w, "rhythm"))
+            _agree(g.pcm_chain_hpss_host(gate, split, loud, pre, power, None, None, pcen, None, rates, q),
+                   g.pcm_chain_chroma_host(gate, split, loud, pre, power, None, pcen, None, rates, q), (w, "hpss"))
+            _agree(g.pcm_chain_chroma_host(gate, split, loud, pre, c.spec, None, None, c.post, rates, q),
+                   g.pcm_chain_spectral_host(gate, split, loud, pre, c.spec, None, c.post, rates, q), (w, "chroma"))
+            pcen_form = g.pcm_split_spectral_pcen_host if split else g.pcm_trim_spectral_pcen_host
+            _agree(g.pcm_chain_spectral_host(gate, split, None, c.cond, power, pcen, None, rates, q),
+                   pcen_form(gate, c.cond, power, pcen, None, rates, q), (w, "loud, rows"))
+            _agree(pcen_form(gate, c.cond, c.spec, None, c.post, rates, q),
+                   (g.pcm_split_spectral_host if split else g.pcm_trim_spectral_host)(gate, c.cond, c.spec, c.post, rates, q), (w, "pcen"))
 
 
 # the middle segment at eight times the others' rate: resampled to OUT it is a sixteenth of its frames long
