@@ -1439,9 +1439,9 @@ int vsyn_pcm_chain_hpss_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate
                              uint64_t intervals_stride, float* peaks_out, double* refs_out, vsyn_loudness_record* records_out,
                              vsyn_status* status, const char** err);
 
-/* ---- rhythm: onset strength, onset frames, tempogram and tempo, computed where the rows are ----
+/* ---- rhythm: onset strength, onset frames, tempogram, tempo and beats, computed where the rows are ----
  *
- * Three stages behind the spectral rows: librosa.onset.onset_strength (aggregate = mean), librosa.onset.onset_detect through
+ * Three stages behind the spectral rows, and the beat tracker (D) behind the first of them: librosa.onset.onset_strength (aggregate = mean), librosa.onset.onset_detect through
  * util.peak_pick (backtrack = False), librosa.feature.tempogram (autocorrelation, window = "hann") and, on its mean,
  * librosa.feature.tempo (aggregate = mean, log-normal prior). librosa is not among the test dependencies and parity with it is not
  * claimed: the contract is the arithmetic below, the device is compared against a float64 model of it (tests/rhythm_model.py), and
@@ -1500,9 +1500,42 @@ int vsyn_pcm_chain_hpss_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate
  *     one below -1e-6 (log1p's domain), is refused with VSYN_ERR_INVALID.
  *  6. Checks: W in [2, 2048]; hop_length >= 1; ac_size finite and > 0 when win_length is 0; start_bpm and std_bpm finite and > 0;
  *     max_tempo finite and >= 0 (0: no cap).
- *  7. Not built: aggregate = None (a tempo per frame), a caller's prior, beat_track, the Fourier tempogram, other windows and norms.
+ *  7. Not built: aggregate = None (a tempo per frame), a caller's prior, the Fourier tempogram, other windows and norms.
  *
- * Order in the pipeline: ..., STFT and filterbank, HPSS, PCEN, onset strength, then peak picking or tempogram and tempo.
+ * D. Beat tracking: librosa >= 0.10.2's static-tempo beat tracker (librosa.beat.beat_track, units = "frames", sparse = True),
+ *    restated. Input per segment: an envelope x of F float32 values and a period P in frames. Output: the ascending beat frames
+ *    (uint32), their count and a refusal word. e = 2^-53; every sum is float64 in the stated order; no atomics on floating-point
+ *    values. Model: tests/beat_model.py, with the bounds and the decision bands the device is gated on.
+ *  0. Period, on the host in double (vsyn_beat_period): P = rint(60 (rate / hop_length) / bpm), half to even. bpm is the caller's, or
+ *     the segment's tempo from C.5 with librosa.beat.beat_track's own defaults: ac_size 8 s, std_bpm 1, max_tempo 320 and the beat
+ *     spec's start_bpm. P outside [1, 2048] refuses the segment with word 3; words 1 and 2 are a non-finite envelope and a tempo
+ *     window length outside [2, 2048]. A segment with F < 2, or whose envelope has no non-zero value, is not refused: it has 0 beats
+ *     and the chain reports bpm 0.0 (librosa's (0.0, [])).
+ *  1. Normalise. m = (sum x) / F, sd = sqrt(sum (x - m)^2 / (F - 1)), u[n] = double(x[n]) / (sd + FLT_MIN). Order of both sums, a
+ *     function of F alone: 256 partials, partial t adding its terms n = t, t + 256, .. in that order to 0.0 (a square is rounded
+ *     before it is added); in each group of 64 consecutive partials six rounds o = 32, .., 1 in which partial i becomes partial i +
+ *     partial (i xor o); then the four groups' sums in ascending order to 0.0.
+ *  2. Local score. w[k] = exp(-0.5 (32 k / P)^2), k = -P .. P, built on the host in double. ls[i] = sum_k w[k] u[i - k] over the k
+ *     with 0 <= i - k < F: one fma chain from 0.0 with k ascending. thr = 0.01 max_i ls[i]; i0 is the first i with ls[i] >= thr.
+ *  3. Dynamic programme. h = rint(P / 2), half to even; lo = max(h, 1). tx[d] = -tightness (log d - log P)^2, d in [lo, 2P], a host
+ *     table in double. For i ascending the candidates are loc = i - d, d = lo .. 2P, loc >= 0, with score s = cum[loc] + tx[d]; the
+ *     best is the largest s, on a tie the smallest d. cum[i] = ls[i] + s_best, or ls[i] without a candidate. back[i] = loc_best
+ *     (-1 without one) for i >= i0, and -1 for i < i0.
+ *  4. Last beat. Frame i is a local maximum when cum[i] > cum[max(i - 1, 0)] and cum[i] >= cum[min(i + 1, F - 1)]. med is the
+ *     median of cum over the local maxima (the mean of the two middle values for an even count). tail is the largest local maximum
+ *     with cum >= 0.5 med, F - 1 if none qualifies. The beats are tail, back[tail], back[back[tail]], .. until -1, reversed. No local
+ *     maximum: no beats.
+ *  5. Trim (VSYN_BEAT_TRIM). With the beats b[0 .. B), v[j] = ls[b[j]], sm[j] = (0.5 v[j-1] + v[j]) + 0.5 v[j+1] with zeros outside,
+ *     t = 0.5 sqrt((sum sm^2) / B), the sum ascending from 0.0, each square rounded first. Without the flag t = 0. The beats inside
+ *     [n0, n1] are kept, n0 and n1 the first and the last frame with ls > t; no such frame: none.
+ *  6. Checks (VSYN_ERR_INVALID before anything runs, outputs untouched): tightness and start_bpm finite and > 0; bpm finite and >= 0
+ *     (0: estimated per segment; vsyn_beat_period wants one > 0); hop_length >= 1; no unknown option bit; segment sizes as everywhere
+ *     in this section.
+ *  7. Not built: the median aggregate of onset_strength that beat_track(y = ..) feeds itself (the envelope is A's mean aggregate),
+ *     time-varying bpm, a caller's prior, units other than frames, sparse = False, plp.
+ *
+ * Order in the pipeline: ..., STFT and filterbank, HPSS, PCEN, onset strength, then peak picking, or tempogram and tempo, or
+ * (tempogram mean, tempo and) beats.
  * Precision and order. No atomics; every accumulation order above is a function of the stage's parameters and the segment's row
  * count alone, so the same rows give the same bits anywhere in a batch and under any launch geometry. The entry points read rows
  * and envelopes only: they touch neither stream state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM. One handle's
@@ -1601,6 +1634,45 @@ int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
                                uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
                                uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
                                vsyn_loudness_record* records_out, uint32_t* refused_out, vsyn_status* status, const char** err);
+
+enum { VSYN_BEAT_TRIM = 1u }; /* vsyn_beat_spec.options */
+
+typedef struct vsyn_beat_spec { /* 32 bytes */
+  double tightness;    /* 100 */
+  double start_bpm;    /* 120: the prior of the tempo estimate */
+  double bpm;          /* > 0: the caller's tempo for every segment; 0: estimated per segment (D.0) */
+  uint32_t hop_length;
+  uint32_t options;    /* VSYN_BEAT_TRIM */
+} vsyn_beat_spec;
+
+/* D.0 for one tempo and rate: *period_out = P, or 0 for a period outside [1, 2048]. Pure host arithmetic; VSYN_ERR_INVALID as D.6,
+ * and for a bpm that is not finite and > 0, a rate of 0 or a NULL period_out. */
+int vsyn_beat_period(const vsyn_beat_spec* beat, double bpm, uint32_t sample_rate, uint32_t* period_out, const char** err);
+
+/* D.1 to D.5 on envelopes the caller has on the device, back to back; seg_rows[S] and periods[S] are HOST arrays. A period of 0
+ * skips its segment: nothing of it is written. One above 2048 refuses it with word 3. Segment g's beats go to d_beats at the offset of
+ * its envelope (never more beats than frames; the words behind its count are left as they are), its count to d_counts[g], its
+ * refusal word (0, 1 or 3; count 0 with it) to d_refused[g] (may be NULL). d_localscore, d_cumscore (float64) and d_backlink (int32)
+ * (each may be NULL) receive ls, cum and back at the envelope's offsets, for a segment that has a score (F >= 2, finite, not all
+ * zero). The beat spec's bpm and start_bpm are checked and not read. Asynchronous on hip_stream. */
+int vsyn_beat_track_device(vsyn_handle* h, const vsyn_beat_spec* beat, uint32_t num_segments, const uint64_t* seg_rows,
+                           const uint32_t* periods, const float* d_env, uint32_t* d_beats, uint32_t* d_counts, uint32_t* d_refused,
+                           double* d_localscore, double* d_cumscore, int32_t* d_backlink, void* hip_stream, const char** err);
+
+/* vsyn_pcm_chain_rhythm_host's chain with the beat tracker behind the onset stage, through the same chain body: the envelope (onset,
+ * which must agree with the spectral spec as vsyn_rhythm_spec.onset must), then with beat->bpm == 0 the tempogram mean for ac_size 8 s,
+ * a copy of the means to the host, vsyn_tempo_from_mean and P per segment, then D.1 to D.5. rows receives the beat frames as uint32
+ * words (rows_capacity counts words; F a segment suffice) and seg_rows their counts; bpm_out[S] the tempo the period came from (0.0
+ * for a segment without beats by D.0, a refused or a skipped one), rate_out[S] the rate the rows were computed at, refused_out[S] the
+ * words of D.0 (each may be NULL). beat = NULL or onset = NULL is refused: the other entries are not rerouted. Synchronous. */
+int vsyn_pcm_chain_beats_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                              const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                              const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post,
+                              const vsyn_onset_spec* onset, const vsyn_beat_spec* beat, uint32_t num_segments, const uint32_t* in_rates,
+                              uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out,
+                              uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out,
+                              double* refs_out, vsyn_loudness_record* records_out, double* bpm_out, uint32_t* rate_out,
+                              uint32_t* refused_out, vsyn_status* status, const char** err);
 
 /* ---- inverse STFT: complex rows, with or without a real mask on them, back to PCM, computed where the rows are ----
  *

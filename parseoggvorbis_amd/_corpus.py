@@ -72,6 +72,11 @@ def load():
                                                      C.POINTER(binding.SpectralPost), C.POINTER(binding.RhythmSpec), C.POINTER(binding.PcmCond),
                                                      C.POINTER(binding.PcmTrim), C.c_int, C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp,
                                                      vp, vp, vp, vp]),
+                       ("ogg_vorbis_beats_corpus", [C.POINTER(binding.SpectralSpec), C.POINTER(binding.SpectralChroma), u32,
+                                                    C.POINTER(binding.SpectralHpss), C.POINTER(binding.SpectralPcen),
+                                                    C.POINTER(binding.SpectralPost), C.POINTER(binding.OnsetSpec), C.POINTER(binding.BeatSpec),
+                                                    C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
+                                                    C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_loudness_corpus", [u32, C.POINTER(binding.LoudnessSpec), C.c_int, vp, vp, vp, vp, vp, vp])):
         fn = getattr(lib, name)
         fn.argtypes = head + args + tail

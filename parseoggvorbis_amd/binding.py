@@ -128,6 +128,13 @@ class TempoSpec(C.Structure):  # vsyn_tempo_spec
     _fields_ = [("start_bpm", C.c_double), ("std_bpm", C.c_double), ("max_tempo", C.c_double)]
 
 
+VSYN_BEAT_TRIM = 1
+
+
+class BeatSpec(C.Structure):  # vsyn_beat_spec, 32 bytes
+    _fields_ = [("tightness", C.c_double), ("start_bpm", C.c_double), ("bpm", C.c_double), ("hop_length", C.c_uint32), ("options", C.c_uint32)]
+
+
 class PcmCond(C.Structure):  # vsyn_pcm_cond
     _fields_ = [("options", C.c_uint32), ("reserved", C.c_uint32), ("preemphasis", C.c_double)]
 
@@ -299,6 +306,7 @@ _SYMBOLS = [
     "vsyn_spectral_hpss_device", "vsyn_pcm_chain_hpss_host",
     "vsyn_onset_peak_windows", "vsyn_tempogram_win_length", "vsyn_tempogram_tile", "vsyn_tempo_from_mean",
     "vsyn_onset_strength_device", "vsyn_onset_peaks_device", "vsyn_tempogram_device", "vsyn_pcm_chain_rhythm_host",
+    "vsyn_beat_period", "vsyn_beat_track_device", "vsyn_pcm_chain_beats_host",
     "vsyn_istft_num_samples", "vsyn_istft_device", "vsyn_pcm_hpss_device", "vsyn_pcm_chain_effects_host",
     "vsyn_pv_num_rows", "vsyn_phase_vocoder_device", "vsyn_stretch_num_samples", "vsyn_pcm_stretch_device", "vsyn_pcm_chain_stretch_host",
 ]
@@ -472,6 +480,12 @@ def load():
                                                C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralHpss),
                                                C.POINTER(SpectralPcen), C.POINTER(SpectralPost), C.POINTER(RhythmSpec), u32, vp, u32, vp, u64, vp,
                                                vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_beat_period.argtypes = [C.POINTER(BeatSpec), C.c_double, u32, C.POINTER(u32), cpp]
+    lib.vsyn_beat_track_device.argtypes = [vp, C.POINTER(BeatSpec), u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_chain_beats_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
+                                              C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralHpss),
+                                              C.POINTER(SpectralPcen), C.POINTER(SpectralPost), C.POINTER(OnsetSpec), C.POINTER(BeatSpec), u32, vp,
+                                              u32, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp), cpp]
     lib.vsyn_host_free.argtypes = [vp]
     lib.vsyn_host_free.restype = None
@@ -492,6 +506,13 @@ def tempo_from_mean(tempo, g, sample_rate, hop_length):
     bpm, lag, err = C.c_double(), C.c_uint32(), C.c_char_p()
     _check(load().vsyn_tempo_from_mean(C.byref(tempo), _ptr(g), len(g), sample_rate, hop_length, C.byref(bpm), C.byref(lag), C.byref(err)), err)
     return bpm.value, lag.value
+
+
+def beat_period(beat, bpm, sample_rate):
+    """vsyn_beat_period: the beat period in frames for one tempo and rate, 0 for one outside [1, 2048]. Host arithmetic, no GPU."""
+    P, err = C.c_uint32(), C.c_char_p()
+    _check(load().vsyn_beat_period(C.byref(beat), float(bpm), int(sample_rate), C.byref(P), C.byref(err)), err)
+    return P.value
 
 
 class VsynError(RuntimeError):
@@ -791,6 +812,14 @@ class Synth:
         err = C.c_char_p()
         _check(self.lib.vsyn_onset_peaks_device(self.h, _ref(peaks), len(nrows), _ptr(nrows), _ptr(rates), d_env, d_onsets, d_counts, d_refused, stream,
                                                 C.byref(err)), err)
+
+    def beat_track_device(self, beat, seg_rows, periods, d_env, d_beats, d_counts, d_refused=None, d_localscore=None, d_cumscore=None,
+                          d_backlink=None, stream=None):
+        """vsyn_beat_track_device on device pointers (ints; the last four may be None); seg_rows and periods are host sequences."""
+        nrows, per = np.ascontiguousarray(seg_rows, dtype=np.uint64), np.ascontiguousarray(periods, dtype=np.uint32)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_beat_track_device(self.h, _ref(beat), len(nrows), _ptr(nrows), _ptr(per), d_env, d_beats, d_counts, d_refused,
+                                               d_localscore, d_cumscore, d_backlink, stream, C.byref(err)), err)
 
     def tempogram_device(self, spec, seg_rows, sample_rates, d_env, d_rows=None, d_mean=None, stream=None):
         """vsyn_tempogram_device on device pointers (ints; d_rows or d_mean may be None); seg_rows and sample_rates (None: NULL) are host

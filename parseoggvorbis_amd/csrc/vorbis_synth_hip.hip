@@ -30,6 +30,7 @@
 #include "vsyn_effects.h"
 #include "vsyn_pv.h"
 #include "vsyn_rhythm.h"
+#include "vsyn_beat.h"
 #include "vsyn_loudness.h"
 #include "vsyn_resample.h"
 #include "vsyn_stretch.h"
@@ -142,6 +143,7 @@ struct vsyn_handle {
   PvWs pv;                             // vsyn_pv.h
   StretchWs st;                        // vsyn_stretch.h
   RhythmWs rh;                         // vsyn_rhythm.h
+  BeatWs bt;                           // vsyn_beat.h
   ResampleWs rs;                       // vsyn_resample.h
   CondWs cd;                           // vsyn_condition.h
   TrimWs tr;                           // vsyn_trim.h
@@ -1468,6 +1470,29 @@ int vsyn_tempogram_device(vsyn_handle* h, const vsyn_tempogram_spec* spec, uint3
   return tg_launch(h->rh, h->device, spec, S, seg_rows, sample_rates, d_env, d_rows, d_mean, (hipStream_t)hip_stream, err);
 }
 
+int vsyn_beat_period(const vsyn_beat_spec* beat, double bpm, uint32_t sample_rate, uint32_t* period_out, const char** err) {
+  if (int rc = beat_check(beat, err)) return rc;
+  if (!period_out || !sample_rate || !std::isfinite(bpm) || !(bpm > 0.0))
+    return fail(err, VSYN_ERR_INVALID, "beat period: period_out is NULL, the rate is 0, or the bpm is not finite and > 0");
+  *period_out = beat_period(beat, bpm, sample_rate);
+  return VSYN_OK;
+}
+
+int vsyn_beat_track_device(vsyn_handle* h, const vsyn_beat_spec* beat, uint32_t S, const uint64_t* seg_rows, const uint32_t* periods,
+                           const float* d_env, uint32_t* d_beats, uint32_t* d_counts, uint32_t* d_refused, double* d_localscore,
+                           double* d_cumscore, int32_t* d_backlink, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = beat_check_call(beat, S, seg_rows, periods, err)) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_counts) return fail(err, VSYN_ERR_INVALID, "d_counts is NULL");
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  if (total && (!d_env || !d_beats)) return fail(err, VSYN_ERR_INVALID, "NULL envelope or beat pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return beat_launch(h->bt, h->device, beat, S, seg_rows, periods, d_env, d_beats, d_counts, d_refused, d_localscore, d_cumscore, d_backlink,
+                     (hipStream_t)hip_stream, err);
+}
+
 }  // extern "C"
 
 // The stages chained behind the last host submit. The PCM the next stage reads: planar [S][C][plane]; each segment's frames from d_frames, else from si.
@@ -1659,6 +1684,10 @@ struct Chain {
   const vsyn_spectral_pcen* pcen;
   const vsyn_spectral_post* post;
   const vsyn_rhythm_spec* rhythm;
+  const vsyn_onset_spec* beat_onset;  // the beat tracker behind the onset stage (vsyn_beat.h), in the rhythm stages' place
+  const vsyn_beat_spec* beat;
+  double* bpm_out;        // its tempo and the rows' rate per segment [S]
+  uint32_t* rate_out;
   uint64_t* frames_out;   // the per-segment outputs [S]: the frames behind the gate (and the stretch), conditioning's peaks, the
   float* peaks_out;       // normaliser's records, the rhythm stages' refusal words
   vsyn_loudness_record* records_out;
@@ -1860,6 +1889,12 @@ static int spectral_rows_out(vsyn_handle* h, const Chain& c, const uint32_t* spe
     if (rc) return rc;
     return sync_status_into(h, status, err);
   }
+  if (c.beat) {  // as the rhythm stages: the rows stay where they are, the beat frames go to the host in their place
+    rc = beat_rows_out(h->rh, h->bt, h->device, c.beat_onset, c.beat, (uint32_t)D, S, spec_rates, seg_rows, total, cur, rows, rows_capacity,
+                       c.bpm_out, c.rate_out, c.refused_out, hs, err);
+    if (rc) return rc;
+    return sync_status_into(h, status, err);
+  }
   if (const vsyn_spectral_post* post = c.post) {
     const uint64_t Dout = D * (1u + post->order);
     HIPCHK(h->pp.rows.ensure(total * Dout + 1));
@@ -1914,6 +1949,14 @@ static int spectral_host(vsyn_handle* h, Chain c, float* rows, uint64_t rows_cap
     if (int rc = rhythm_check(c.rhythm, spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, spec_dim(spec, c.chroma), err)) return rc;
     if (c.refused_out && S) memset(c.refused_out, 0, sizeof(uint32_t) * S);
   }
+  if (c.beat) {
+    if (c.post) return fail(err, VSYN_ERR_INVALID, "delta / normalize are not available with the beat tracker: the onset stage takes their place");
+    if (int rc = beat_chain_check(c.beat_onset, c.beat, spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, spec_dim(spec, c.chroma), err))
+      return rc;
+    if (c.refused_out && S) memset(c.refused_out, 0, sizeof(uint32_t) * S);
+    if (c.bpm_out && S) memset(c.bpm_out, 0, sizeof(double) * S);
+    if (c.rate_out && S) memset(c.rate_out, 0, sizeof(uint32_t) * S);
+  }
   if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
   for (uint32_t g = 0; g < S; ++g) seg_rows[g] = 0;
   if (c.peaks_out) memset(c.peaks_out, 0, sizeof(float) * S);
@@ -1960,7 +2003,7 @@ static int spectral_host(vsyn_handle* h, Chain c, float* rows, uint64_t rows_cap
     if (int rc = post_check_rows(c.post, S, seg_rows, err)) return rc;
   }
   if (!rows || total == 0) return VSYN_OK;
-  if (!c.rhythm && total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (!c.rhythm && !c.beat && total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
   if (!gate && out_rate) {
     if (t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
     if (int rc = step_resample(h, S, rates, out_rate, t_max, false, &v, err)) return rc;
@@ -2340,6 +2383,38 @@ int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
   c.pcen = pcen;
   c.post = post;
   c.rhythm = rhythm;
+  c.frames_out = gate && (loud || split) ? frames_out : nullptr;
+  c.peaks_out = peaks_out;
+  c.records_out = loud ? records_out : nullptr;
+  c.refused_out = refused_out;
+  return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
+}
+
+// vsyn_pcm_chain_rhythm_host's chain with the beat tracker in the rhythm stages' place (vsyn_beat.h).
+int vsyn_pcm_chain_beats_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                              const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                              const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post,
+                              const vsyn_onset_spec* onset, const vsyn_beat_spec* beat, uint32_t S, const uint32_t* in_rates, uint32_t out_rate,
+                              float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out,
+                              uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                              vsyn_loudness_record* records_out, double* bpm_out, uint32_t* rate_out, uint32_t* refused_out, vsyn_status* status,
+                              const char** err) {
+  if (!h) return cond_no_handle(err);
+  if (!beat || !onset) return fail(err, VSYN_ERR_INVALID, "vsyn_pcm_chain_beats_host needs a beat spec and an onset spec");
+  const bool split = gate && gate_is_split;
+  Chain c{S, in_rates, out_rate};
+  c.gate = make_gate(gate, split, bounds_out, counts_out, intervals_out, intervals_stride, refs_out);
+  c.loud = loud;
+  c.cond = cond;
+  c.spec = spec;
+  c.chroma = spec && spec_is_chroma(spec) ? chroma : nullptr;
+  c.hpss = hpss;
+  c.pcen = pcen;
+  c.post = post;
+  c.beat_onset = onset;
+  c.beat = beat;
+  c.bpm_out = bpm_out;
+  c.rate_out = rate_out;
   c.frames_out = gate && (loud || split) ? frames_out : nullptr;
   c.peaks_out = peaks_out;
   c.records_out = loud ? records_out : nullptr;

@@ -87,6 +87,7 @@ bool loudness_run(const CorpusOptions& o) { return o.loudness; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
 uint32_t spectral_dim(const CorpusOptions& o) {
+  if (o.beat) return 1u;  // a beat frame a row
   if (o.rhythm)  // the words of a row of the selected rhythm output
     return o.rhythm_spec.output == VSYN_RHYTHM_TEMPOGRAM ? o.rhythm_spec.tempogram.win_length : o.rhythm_spec.output == VSYN_RHYTHM_TEMPO_MEAN ? 2u : 1u;
   return vsyn_spectral_chroma_dim(&o.spectral, o.chroma_given ? &o.chroma_spec : nullptr) * (1u + o.post.order);
@@ -416,6 +417,7 @@ struct Feeder {
     std::vector<vsyn_loudness_record> loud;  // loudness run: per file its record,
     std::vector<uint64_t> loud_nb;           // its blocks
     std::vector<double> loud_z;              // and with loudness_blocks the block means of all files back to back
+    std::vector<double> bpm;                 // beat run: per file the tempo its period came from
   };
 
   // Synthesis of the packed batch. The PCM comes back as f32 planes unless a later stage reads it on the device (VSYN_SUBMIT_KEEP_PCM).
@@ -645,7 +647,7 @@ struct Feeder {
       spec_rows += F;
     }
     const uint64_t rhythm_words = opts.rhythm ? spec_rows * spectral_dim(opts) + 4098u * (uint64_t)S : 0;  // (the mean: 2 (W + 1) a file)
-    CHECK_ERR(g.rows.ensure(opts.rhythm ? rhythm_words + 1 : spec_rows * spectral_dim(opts) + 1));
+    CHECK_ERR(g.rows.ensure(opts.rhythm ? rhythm_words + 1 : spec_rows * spectral_dim(opts) + 1));  // (a beat run: a word a frame at most)
     CHECK_ERR(g.seg_rows.ensure(S));
     vsyn_status st;
     const char* err = nullptr;
@@ -660,13 +662,25 @@ struct Feeder {
     const bool gated = opts.trim || opts.split;
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
     if (opts.loudness_norm) o.loud.assign(S, NO_LOUDNESS_RECORD);
-    const int rc = vsyn_pcm_chain_rhythm_host(
-        g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr, cond, &opts.spectral,
-        opts.chroma_given ? &opts.chroma_spec : nullptr, opts.hpss ? &opts.hpss_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr,
-        post_run(opts) ? &opts.post : nullptr, opts.rhythm ? &opts.rhythm_spec : nullptr, S, rates.data(), opts.resample_rate, g.rows.p,
-        opts.rhythm ? rhythm_words : spec_rows, g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr,
-        opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
-        opts.loudness_norm ? o.loud.data() : nullptr, rhythm_refused.data(), &st, &err);
+    int rc;
+    if (opts.beat) {  // the beat tracker in the rhythm stages' place: the same chain, the tempo per file beside the refusal words
+      o.bpm.assign(S, 0.0);
+      rc = vsyn_pcm_chain_beats_host(
+          g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr, cond, &opts.spectral,
+          opts.chroma_given ? &opts.chroma_spec : nullptr, opts.hpss ? &opts.hpss_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr,
+          post_run(opts) ? &opts.post : nullptr, &opts.beat_onset, &opts.beat_spec, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows,
+          g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr,
+          opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(), opts.loudness_norm ? o.loud.data() : nullptr, o.bpm.data(),
+          nullptr, rhythm_refused.data(), &st, &err);
+    } else {
+      rc = vsyn_pcm_chain_rhythm_host(
+          g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr, cond, &opts.spectral,
+          opts.chroma_given ? &opts.chroma_spec : nullptr, opts.hpss ? &opts.hpss_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr,
+          post_run(opts) ? &opts.post : nullptr, opts.rhythm ? &opts.rhythm_spec : nullptr, S, rates.data(), opts.resample_rate, g.rows.p,
+          opts.rhythm ? rhythm_words : spec_rows, g.seg_rows.p, joined.data(), opts.trim ? o.bounds.data() : nullptr,
+          opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride, peaks.data(), refs.data(),
+          opts.loudness_norm ? o.loud.data() : nullptr, rhythm_refused.data(), &st, &err);
+    }
     if (rc == VSYN_ERR_INVALID) {  // the spec itself is refused: every file's problem alike
       for (uint32_t s = 0; s < S; ++s) o.err[s] = std::string("spectral: ") + (err ? err : "refused");
       for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;
@@ -690,8 +704,9 @@ struct Feeder {
     if (opts.condition) refuse_peaks(peaks, o);
     for (uint32_t s = 0; s < S && rc == VSYN_OK; ++s)
       if (o.err[s].empty() && rhythm_refused[s])
-        o.err[s] = rhythm_refused[s] == 1u ? "rhythm: the onset envelope holds a value that is not finite"
-                                           : "rhythm: floor(ac_size * rate / hop_length) is outside [2, 2048]";
+        o.err[s] = rhythm_refused[s] == 1u   ? "rhythm: the onset envelope holds a value that is not finite"
+                   : rhythm_refused[s] == 2u ? "rhythm: floor(ac_size * rate / hop_length) is outside [2, 2048]"
+                                             : "rhythm: the beat period is outside [1, 2048] frames";
     if (opts.loudness_norm && rc == VSYN_OK) refuse_loud(o, true, rates);
     return OkOrError();
   }
@@ -809,6 +824,7 @@ struct Feeder {
     if (opts.resample_rate) out.sample_rate = opts.resample_rate;
     stats.frames += frames;
     if (o.err[s].empty() && s < o.loud.size()) out.loudness = o.loud[s];
+    if (o.err[s].empty() && s < o.bpm.size()) out.bpm = o.bpm[s];
     if (loudness_run(opts)) {  // the record and the block means: nothing goes to the callbacks; row0 counts the blocks in front
       if (o.err[s].empty() && s < o.loud.size()) {
         if (opts.loudness_blocks) out.loudness_blocks.assign(o.loud_z.begin() + row0, o.loud_z.begin() + row0 + o.loud_nb[s]);
@@ -1285,6 +1301,7 @@ struct CorpusCall {
   uint64_t* frames_out = nullptr;         // a PCM call's frames (a rows call's joined frames are split.frames_out)
   uint32_t* channels_out = nullptr;
   uint32_t* rate_out = nullptr;
+  double* bpm_out = nullptr;              // a beat run's tempo per file
   uint64_t* bounds_out = nullptr;
   SplitOuts split;
   vsyn_loudness_record* records_out = nullptr;
@@ -1341,6 +1358,12 @@ struct CorpusCall {
       return refuse(fn, "unknown rhythm output, or tempogram rows without a win_length in [2, 2048]");
     opts.rhythm = true;
     opts.rhythm_spec = *rhythm;
+  }
+  void beat(const vsyn_onset_spec* onset, const vsyn_beat_spec* beat) {
+    if (post_run(opts)) return refuse(fn, "delta / normalize are not available with the beat tracker");
+    opts.beat = true;
+    opts.beat_onset = *onset;
+    opts.beat_spec = *beat;
   }
   void pcm_format(int format, uint32_t target_rate) {
     if (format != VSYN_PCM_F32 && format != VSYN_PCM_S16) return refuse("ogg_vorbis_pcm_corpus", "unknown PCM format " + std::to_string(format));
@@ -1407,6 +1430,8 @@ struct CorpusCall {
     return run(name, [&](size_t i, const CorpusFileResult& res, bool bad) {
       if (rows_count_out) rows_count_out[i] = res.feature_rows;
       if (opts.split && split.frames_out) split.frames_out[i] = bad ? 0 : res.frames;
+      if (opts.beat && bpm_out) bpm_out[i] = bad ? 0.0 : res.bpm;
+      if (opts.beat && rate_out) rate_out[i] = res.sample_rate;
     });
   }
   int pcm() {
@@ -1767,6 +1792,36 @@ extern "C" int ogg_vorbis_rhythm_corpus(const uint8_t* const* datas, const size_
   c.pcen(pcen);
   c.hpss(hpss);
   c.rhythm(rhythm);
+  c.cond(cond);
+  c.gate(gate, split);
+  c.loud(loud);
+  return c.rows();
+}
+
+extern "C" int ogg_vorbis_beats_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                       uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                                       uint32_t target_rate, const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen,
+                                       const vsyn_spectral_post* post, const vsyn_onset_spec* onset, const vsyn_beat_spec* beat,
+                                       const vsyn_pcm_cond* cond, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                                       float** rows_out, uint64_t* rows_count_out, double* bpm_out, uint32_t* rate_out, uint64_t* bounds_out,
+                                       uint64_t* frames_out, uint32_t** intervals_out, uint64_t* intervals_count_out,
+                                       vsyn_loudness_record* records_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                                       const char** error_out) {
+  if (!onset || !beat) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_beats_corpus: no onset or no beat spec", error_out);
+  CorpusCall c("ogg_vorbis_beats_corpus", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out, ok_out,
+               error_out_per_file, stats_out, error_out);
+  const bool split = gate && gate_is_split;
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.records_out = records_out;
+  c.bpm_out = bpm_out;
+  c.rate_out = rate_out;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
+  c.spectral(spec, target_rate, post);
+  c.chroma(chroma);
+  c.pcen(pcen);
+  c.hpss(hpss);
+  c.beat(onset, beat);
   c.cond(cond);
   c.gate(gate, split);
   c.loud(loud);

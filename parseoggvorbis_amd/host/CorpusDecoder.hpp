@@ -42,6 +42,7 @@ struct CorpusFileResult {
   std::vector<uint32_t> intervals;        // CorpusOptions::split: (start, end) of every non-silent interval, in samples of that signal
   vsyn_loudness_record loudness = {0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u};  // CorpusOptions::loudness: the file's record
   std::vector<double> loudness_blocks;    // ... and with loudness_blocks its block means z_j
+  double bpm = 0;                         // CorpusOptions::beat: the tempo the beat period came from (0.0: no beats to take one from)
 };
 
 struct CorpusCallbacks {
@@ -163,6 +164,13 @@ struct CorpusOptions {
   // every file's error; an envelope that is not finite, or a window length outside [2, 2048], is that file's. The default is off.
   bool rhythm = false;
   vsyn_rhythm_spec rhythm_spec = {};
+  // beat (a spectral run as for rhythm, which it excludes): the rows stay on the device and go through the onset stage (beat_onset)
+  // and the beat tracker (include/vorbis_synth_hip.h, "rhythm", D; vsyn_pcm_chain_beats_host); a file's "rows" are its beat frames,
+  // one uint32 word each. A non-finite envelope, a tempo window length outside [2, 2048] and a beat period outside [1, 2048] frames
+  // are that file's errors. The default is off.
+  bool beat = false;
+  vsyn_onset_spec beat_onset = {};
+  vsyn_beat_spec beat_spec = {};
 };
 
 struct CorpusStats {
@@ -357,6 +365,18 @@ int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, const size_t* l
 // ogg_vorbis_spectral_corpus_hpss with the rhythm stages behind PCEN (CorpusOptions::rhythm_spec = *rhythm, which must not be
 // NULL), one entry for the four outputs rhythm->output selects: rows_out receives per file that output's words (see
 // vsyn_rhythm_spec in include/vorbis_synth_hip.h) and rows_count_out its rows. A post spec that is on refuses the call.
+// ogg_vorbis_rhythm_corpus with the beat tracker in the rhythm stages' place (CorpusOptions::beat_onset = *onset, beat_spec = *beat;
+// neither may be NULL): rows_out receives per file its beat frames, uint32 words, rows_count_out their count, bpm_out (may be NULL)
+// the tempo the period came from (beat->bpm, or the file's own estimate; 0.0 for a file without beats to take one from) and rate_out
+// (may be NULL) the rate the rows were computed at. A post spec that is on refuses the call.
+int ogg_vorbis_beats_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                            uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                            uint32_t target_rate, const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen,
+                            const vsyn_spectral_post* post, const vsyn_onset_spec* onset, const vsyn_beat_spec* beat, const vsyn_pcm_cond* cond,
+                            const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, float** rows_out,
+                            uint64_t* rows_count_out, double* bpm_out, uint32_t* rate_out, uint64_t* bounds_out, uint64_t* frames_out,
+                            uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
+                            const char** error_out_per_file, double* stats_out, const char** error_out);
 int ogg_vorbis_rhythm_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                              uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
                              uint32_t target_rate, const vsyn_spectral_hpss* hpss, const vsyn_spectral_pcen* pcen,

@@ -1,5 +1,5 @@
-"""Rhythm features of Ogg Vorbis files on the GPU: onset strength, onset frames, tempogram and tempo (include/vorbis_synth_hip.h,
-"rhythm"; model: tests/rhythm_model.py). The spectral rows never leave the device: the onset stage reads them where the spectral
+"""Rhythm features of Ogg Vorbis files on the GPU: onset strength, onset frames, tempogram, tempo and beats (include/vorbis_synth_hip.h,
+"rhythm"; models: tests/rhythm_model.py, tests/beat_model.py). The spectral rows never leave the device: the onset stage reads them where the spectral
 kernels (and HPSS, PCEN) left them, and only the selected output comes back.
 
 Every entry forwards the arguments of spectral.get_spectral_batch that shape the rows or the PCM in front of them (kind and the STFT /
@@ -82,6 +82,14 @@ def tempo_spec(start_bpm=120.0, std_bpm=1.0, max_tempo=320.0):
     from .binding import TempoSpec
     return TempoSpec(_number("start_bpm", start_bpm, positive=True), _number("std_bpm", std_bpm, positive=True),
                      0.0 if max_tempo is None else _number("max_tempo", max_tempo, positive=True))
+
+
+def beat_spec(tightness=100.0, start_bpm=120.0, bpm=None, trim=True, hop_length=512):
+    """binding.BeatSpec of checked arguments: tightness and start_bpm finite and > 0; bpm None (estimated per file) or finite and > 0."""
+    from .binding import BeatSpec
+    return BeatSpec(_number("tightness", tightness, positive=True), _number("start_bpm", start_bpm, positive=True),
+                    0.0 if bpm is None else _number("bpm", bpm, positive=True), _int("hop_length", hop_length, 1, 2 ** 31 - 1),
+                    1 if _flag("trim", trim) else 0)
 
 
 def _spectral_args(kw):
@@ -222,6 +230,80 @@ def get_tempo_batch(list_of_bytes, lag=1, max_size=1, ac_size=8.0, start_bpm=120
     return out
 
 
+def _run_beats(list_of_bytes, onset, beat, c, a):
+    """One corpus run through ogg_vorbis_beats_corpus: per file (bpm, beats int64, sr), or the RhythmError."""
+    from .binding import LOUDNESS_RECORD_DTYPE
+    from .pcm import give_loudness, give_split_index, give_trim_index
+    lib = _corpus.load()
+    n = len(list_of_bytes)
+    counts = np.zeros(max(n, 1), np.uint64)
+    bpm, rate = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.uint32)
+    ib = _corpus.IntervalBuffers(lib, n)
+    joined, bounds = np.zeros(max(n, 1), np.uint64), np.zeros((max(n, 1), 2), np.uint64)
+    records = np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
+    gate = c.split if c.split is not None else c.trim
+    try:
+        res = _corpus.run(lib, lib.ogg_vorbis_beats_corpus, list_of_bytes,
+                          (a["threads"], a["feeders"], a["files_per_submit"], a["device"], C.byref(c.spec),
+                           C.byref(c.chroma) if a["kind"] in CHROMA_KINDS else None, c.target,
+                           C.byref(c.hp) if a["hpss"] is not None else None, C.byref(c.pc) if a["pcen"] else None, None, C.byref(onset),
+                           C.byref(beat), C.byref(c.cond) if c.cond.options else None, None if gate is None else C.byref(gate),
+                           int(c.split is not None), None if c.loud is None else C.byref(c.loud)),
+                          (counts, bpm, rate, bounds, joined, ib.ptrs, ib.counts, records),
+                          lambda i, p: (float(bpm[i]), _corpus.copy_into(np.zeros(int(counts[i]), np.uint32), p).astype(np.int64), int(rate[i])),
+                          RhythmError, a["errors"], "beats", a["stats"])
+        give_split_index(a["split_index"], ib if c.split is not None else None, res)
+    finally:
+        ib.free()
+    give_trim_index(a["trim_index"], bounds[:n] if c.trim is not None else None, res)
+    give_loudness(a["loudness"], records if c.loud is not None else None, res)
+    return res
+
+
+def get_beats_batch(list_of_bytes, lag=1, max_size=1, start_bpm=120.0, tightness=100.0, trim=True, bpm=None, envelope=None, **spectral):
+    """librosa.beat.beat_track(onset_envelope=that envelope, sr=sr, hop_length=hop_length, start_bpm=start_bpm, tightness=tightness,
+    trim=trim, bpm=bpm, units="frames") with the envelope of get_onset_strength_batch (its mean aggregate): a list of (bpm, beats
+    int64, sr), sr the rate the rows were computed at. bpm None: each file's own tempo, as get_tempo_batch(ac_size=8.0) gives it; a
+    number: that tempo for every file; a list: one entry per file (files of one tempo share a run). A file without beats to take a
+    tempo from (fewer than two frames, an all-zero envelope) returns (0.0, no beats, sr). A file whose envelope is not finite, whose
+    tempo window length falls outside [2, 2048] or whose beat period falls outside [1, 2048] frames fails alone. envelope (optional
+    list) receives each file's envelope (None for a failed file), from a second run of the same arithmetic."""
+    c, a = _spectral_args(spectral)
+    hop, n_fft, center = c.spec.hop_length, c.spec.n_fft, bool(c.spec.options & 1)
+    onset = onset_spec(lag, max_size, n_fft, hop, center)
+    n = len(list_of_bytes)
+    if isinstance(bpm, (list, tuple, np.ndarray)):
+        if len(bpm) != n:
+            raise RhythmError("bpm must be a number, None or a list with one entry per file, got %d entries for %d files" % (len(bpm), n))
+        per_file = [_number("bpm", v, positive=True) for v in bpm]
+    else:
+        per_file = [None if bpm is None else _number("bpm", bpm, positive=True)] * n
+    specs = {v: beat_spec(tightness, start_bpm, v, trim, hop) for v in set(per_file)} or {None: beat_spec(tightness, start_bpm, None, trim, hop)}
+    if envelope is not None and not isinstance(envelope, list):
+        raise RhythmError("envelope must be a list or None")
+    _corpus.check_errors(a["errors"])
+    if len(specs) == 1:
+        res = _run_beats(list_of_bytes, onset, next(iter(specs.values())), c, a)
+    else:  # one run per tempo, each over its files; the per-file side outputs are not split across runs
+        if a["trim_index"] is not None or a["split_index"] is not None or a["loudness"] is not None or a["stats"] is not None:
+            raise RhythmError("trim_index, split_index, loudness and stats are not available with a list of bpm")
+        res = [None] * n
+        for v, bs in specs.items():
+            idx = [i for i in range(n) if per_file[i] == v]
+            part = _run_beats([list_of_bytes[i] for i in idx], onset, bs, c, dict(a, errors="return"))
+            for i, r in zip(idx, part):
+                res[i] = RhythmError(str(r).replace("file %d:" % idx.index(i), "file %d:" % i, 1)) if isinstance(r, Exception) else r
+        if a["errors"] == "raise":
+            for r in res:
+                if isinstance(r, Exception):
+                    raise r
+    if envelope is not None:
+        quiet = dict(spectral, errors="return", stats=None, trim_index=None, split_index=None, loudness=None)
+        env = get_onset_strength_batch(list_of_bytes, lag, max_size, **quiet)
+        envelope[:] = [e if isinstance(e, np.ndarray) and isinstance(o, tuple) else None for e, o in zip(env, res)]
+    return res
+
+
 def _single(fn, raw_bytes, kwargs):
     kwargs.setdefault("threads", 1)
     kwargs.setdefault("feeders", 1)
@@ -241,6 +323,11 @@ def get_onsets_from_raw_bytes(raw_bytes, **kwargs):
 def get_tempogram_from_raw_bytes(raw_bytes, **kwargs):
     """One file's tempogram, float32 (frames', win_length)."""
     return _single(get_tempogram_batch, raw_bytes, kwargs)
+
+
+def get_beats_from_raw_bytes(raw_bytes, **kwargs):
+    """One file's (bpm, beats int64, sr)."""
+    return _single(get_beats_batch, raw_bytes, kwargs)
 
 
 def get_tempo_from_raw_bytes(raw_bytes, **kwargs):
