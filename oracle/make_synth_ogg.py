@@ -37,6 +37,15 @@ always writes rangebits = log2(n/2)); one stream of 20 packets with both block s
                                                                           up to the long one, the rest in 20000..32767
 
 The committed synth_16 is `--geometry beyond2 16 9` (stereo, 256/2048), synth_17 is `--geometry shared15 17 11` (stereo, 128/1024).
+
+With --floors per_mode the setup leaves "floor 0 for short blocks, floor 1 for long blocks": two short modes and two or three long
+ones, a mapping per mode, a floor of its own per (mapping, submap), and at least one mapping with two submaps, so that the channels
+of one packet use different floors; short packets draw their mode at random as long ones do. One stream of 18 packets in which every
+mode occurs, with the channel count and block sizes given, written as tests/golden/synth_NN (the residue limits above still hold):
+
+    python oracle/make_synth_ogg.py --floors per_mode NN CHANNELS BS0/BS1 [first_seed]
+
+The committed synth_18 is `--floors per_mode 18 2 256/2048 1`, synth_19 is `--floors per_mode 19 3 128/1024 1`.
 """
 import os
 import struct
@@ -207,7 +216,8 @@ class Setup:
     pass
 
 
-def make_setup(rng, geometry=None):
+def make_setup(rng, geometry=None, per_mode=None):
+    """per_mode: (channels, bs0, bs1) of a --floors per_mode stream"""
     s = Setup()
     s.channels = int(rng.choice([1, 2, 2, 2, 3, 3, 4, 6]))
     if os.environ.get("SYNTH_CHANNELS"):  # stress knobs (one-off runs; the committed set uses none)
@@ -215,6 +225,9 @@ def make_setup(rng, geometry=None):
     s.bs0, s.bs1 = [(64, 256), (128, 1024), (256, 2048), (256, 2048), (512, 512), (64, 64), (128, 512), (256, 2048), (512, 4096)][int(rng.integers(0, 9))]
     if os.environ.get("SYNTH_BLOCKS"):
         s.bs0, s.bs1 = (int(v) for v in os.environ["SYNTH_BLOCKS"].split("/"))
+    if per_mode:
+        s.channels, s.bs0, s.bs1 = per_mode
+        assert s.channels >= 2 and s.bs0 < s.bs1
     s.rate = 44100
     if geometry and s.bs0 == s.bs1:  # a geometry stream has both block sizes: the caller tries the next seed
         return None
@@ -224,9 +237,10 @@ def make_setup(rng, geometry=None):
         books.append(b)
         return len(books) - 1
 
-    # ---- floors: one per block size ----
+    # ---- floors: one per block size (--floors per_mode: one per (mapping, submap), made where the mappings are) ----
     s.floors = []
-    for n in ((s.bs1,) if geometry == "shared15" else (s.bs0, s.bs1)):
+
+    def make_floor(n):
         f = Setup()
         n2 = n // 2
         # x[1] = 1 << rangebits, whatever the block size (hpp:447-450): log2(n/2) by default, one more for beyond2, 15 for shared15
@@ -277,6 +291,11 @@ def make_setup(rng, geometry=None):
         assert len(set(f.xs)) == posts and max(f.xs) == x1
         f.range = rng_y
         s.floors.append(f)
+        return len(s.floors) - 1
+
+    if not per_mode:
+        for n in ((s.bs1,) if geometry == "shared15" else (s.bs0, s.bs1)):
+            make_floor(n)
 
     # ---- residues: one per block size (plus sometimes a second pair for a second submap) ----
     def make_residue(n, nch_for_type2):
@@ -321,11 +340,16 @@ def make_setup(rng, geometry=None):
     s.mappings = []
     blocks = [(0, s.bs0), (1, s.bs1)]
     floor_of = (lambda blk: 0) if geometry == "shared15" else (lambda blk: blk)
-    if rng.random() < 0.35:
+    if per_mode:  # two short modes and two or three long ones, in an order that keeps mode numbers and block flags apart
+        blocks = [(1, s.bs1), (0, s.bs0), (1, s.bs1), (0, s.bs0)] + ([(1, s.bs1)] if rng.random() < 0.5 else [])
+        two_submaps = int(rng.integers(0, len(blocks)))  # this mapping has two submaps whatever the draw below says
+    elif rng.random() < 0.35:
         blocks.append((1, s.bs1))  # a second long-block mode with its own mapping (other coupling / submaps / residue)
     for blk, n in blocks:
         m = Setup()
         m.submaps = 2 if (s.channels >= 2 and rng.random() < 0.3) else 1
+        if per_mode and len(s.mappings) == two_submaps:
+            m.submaps = 2
         m.mux = [0] * s.channels
         if m.submaps > 1:  # every submap gets a channel (the reference dereferences an empty submap's first channel, hpp:1191-1200)
             while len(set(m.mux)) < m.submaps:
@@ -339,8 +363,9 @@ def make_setup(rng, geometry=None):
         m.sub = []
         for sm in range(m.submaps):
             nch = sum(1 for c in range(s.channels) if m.mux[c] == sm)
+            fl = make_floor(n) if per_mode else floor_of(blk)
             s.residues.append(make_residue(n, max(1, nch)))
-            m.sub.append((floor_of(blk), len(s.residues) - 1))  # (floor, residue)
+            m.sub.append((fl, len(s.residues) - 1))  # (floor, residue)
         s.mappings.append(m)
     s.modes = [(blk, k) for k, (blk, _) in enumerate(blocks)]  # (blockflag, mapping)
     s.books = books
@@ -580,9 +605,9 @@ def window_flag_override(flags, rng, kind):
     return (prev, nxt) if cls == {"B", "C", "D"} else None
 
 
-def make_stream(seed, winflags=None, geometry=None):
+def make_stream(seed, winflags=None, geometry=None, per_mode=None):
     rng = np.random.default_rng(seed)
-    s = make_setup(rng, geometry)
+    s = make_setup(rng, geometry, per_mode)
     if s is None:
         return None, s, 0
     ident = b"\x01vorbis" + struct.pack("<IBIiiiB", 0, s.channels, s.rate, 0, 128000, 0, (ilog(s.bs0) - 1) | ((ilog(s.bs1) - 1) << 4)) + b"\x01"
@@ -593,9 +618,12 @@ def make_stream(seed, winflags=None, geometry=None):
     npk = int(os.environ.get("SYNTH_PACKETS", 0)) or int(rng.integers(8, 20) if not winflags else rng.integers(24, 40))
     if geometry:
         npk = 20
+    if per_mode:
+        npk = 18
     flags = [int(rng.random() < 0.55) for _ in range(npk)]
     if geometry and len(set(flags)) < 2:  # packets of both block sizes
         return None, s, npk
+    modes_seen = set()
     override = None
     if winflags:
         override = window_flag_override(flags, rng, winflags) if s.bs0 < s.bs1 else None
@@ -611,6 +639,10 @@ def make_stream(seed, winflags=None, geometry=None):
             prev_long, next_long = override[0][q], override[1][q]
         long_modes = [k for k, (bf, _) in enumerate(s.modes) if bf]
         mode = long_modes[int(rng.integers(0, len(long_modes)))] if lng else 0
+        if per_mode and not lng:
+            short_modes = [k for k, (bf, _) in enumerate(s.modes) if not bf]
+            mode = short_modes[int(rng.integers(0, len(short_modes)))]
+        modes_seen.add(mode)
         pkt = write_audio(s, rng, mode, prev_long, next_long)
         assert len(pkt) < 255 * 200
         n = s.bs1 if lng else s.bs0
@@ -625,6 +657,8 @@ def make_stream(seed, winflags=None, geometry=None):
             pages.append(ogg_page(77, seq, granule, batch, eos=last))
             seq += 1
             batch = []
+    if per_mode and len(modes_seen) < len(s.modes):  # every mode occurs
+        return None, s, npk
     if override:
         s.win_flags = (np.asarray(flags, np.uint8), np.asarray(override[0], np.uint8), np.asarray(override[1], np.uint8))
     return b"".join(pages), s, npk
@@ -692,14 +726,19 @@ def main():
         geometry, index = argv[1], int(argv[2])
         assert geometry in ("beyond2", "shared15"), geometry
         argv = ["1"] + argv[3:]
+    per_mode = None
+    if argv[:2] == ["--floors", "per_mode"]:
+        index = int(argv[2])
+        per_mode = (int(argv[3]),) + tuple(int(v) for v in argv[4].split("/"))
+        argv = ["1"] + argv[5:]
     count = int(argv[0]) if len(argv) > 0 else 12
     seed = int(argv[1]) if len(argv) > 1 else 1
     made = 0
     while made < count:
-        data, s, npk = make_stream(seed, winflags, geometry)
+        data, s, npk = make_stream(seed, winflags, geometry, per_mode)
         if data is None:
             print("seed %d skipped: %s" % (seed, ("the block sequence cannot carry --winflags %s" % winflags) if winflags else
-                                           "equal block sizes, or packets of one size only"))
+                                           "equal block sizes, packets of one size only, or a mode that no packet uses"))
             seed += 1
             continue
         path = os.path.join(OUT, ("winflags_%s.ogg" % winflags) if winflags else ("synth_%02d.ogg" % (index + made)))

@@ -255,10 +255,11 @@ def make_spec(geom, bs0, bs1, channels=2, coupled=True):
     return SetupSpec(channels, bs0, bs1, floors, mappings, modes)
 
 
-def mode_floor(spec, mode):
-    """-> (multiplier, xs, block size) of a mode (every channel of a mapping uses one floor here)"""
+def mode_floor(spec, mode, c=0):
+    """-> (multiplier, xs, block size) of channel c of a mode: the floor spec.floors[spec.mappings[mapping][1][c]] (every channel
+    of a mapping uses one floor in this module's setups; multimode_cases.py has mappings whose channels differ)"""
     bf, mp = spec.modes[mode]
-    mult, xs = spec.floors[spec.mappings[mp][1][0]]
+    mult, xs = spec.floors[spec.mappings[mp][1][c]]
     return mult, xs, spec.blocksize1 if bf else spec.blocksize0
 
 
@@ -338,7 +339,8 @@ def make_batch(spec, kind, seed=1):
 
 def model_taps(spec, b):
     """The integer model's floor_final [P * C * ys_stride] and floor_curve [residue.size] of a batch, in the layout of the
-    vsyn_taps of the same names: final_y * multiplier | step2_flag << 15 per post; the curve per bin, packed like the residue."""
+    vsyn_taps of the same names: final_y * multiplier | step2_flag << 15 per post; the curve per bin, packed like the residue.
+    Every row takes the floor of its own channel; a channel whose floor_used bit is clear leaves both taps at zero."""
     from tests.workloads import packet_blocks
     C, stride = spec.channels, spec.ys_stride
     n_of, off = packet_blocks(spec, b["packets"], b["segments"])
@@ -347,11 +349,14 @@ def model_taps(spec, b):
     memo = {}
     for p in range(len(b["packets"])):
         mode = int(b["packets"]["mode"][p])
-        mult, xs, n = mode_floor(spec, mode)
-        assert n == n_of[p]
+        used = int(b["packets"]["floor_used"][p])
         for c in range(C):
+            mult, xs, n = mode_floor(spec, mode, c)
+            assert n == n_of[p]
+            if not (used >> c) & 1:
+                continue
             row = tuple(int(v) for v in b["ys"][p, c, :len(xs)])
-            key = (mode, row)
+            key = (spec.mappings[spec.modes[mode][1]][1][c], n, row)
             if key not in memo:
                 fy, fl = unwrap(xs, mult, row)
                 memo[key] = (np.array([v * mult | (int(f) << 15) for v, f in zip(fy, fl)], np.uint16), curve(xs, mult, fy, fl, n // 2))

@@ -1,7 +1,7 @@
 """The float64 synthesis model of synth_model.py and its per-packet gate, settled on the CPU: the FFT IMDCT against the oracle's
 closed form, the model's frame counts against the oracle's, and the oracle itself (the reference's float32 arithmetic, pinned bit
 for bit) inside the gate G on every synthetic shape of the parity suite, the loudness profiles of the precision suite, the
-reference's two fixtures and the 18 synth_NN fixtures. Also: synth_batch's defaults give the batches they gave before its
+reference's two fixtures and the 20 synth_NN fixtures. Also: synth_batch's defaults give the batches they gave before its
 precision probes were added."""
 import hashlib
 
@@ -161,12 +161,13 @@ def test_reference_fixtures_in_gate(name):
 
 
 def _synth_names():
-    return ["synth_%02d" % i for i in range(18)]
+    return ["synth_%02d" % i for i in range(20)]
 
 
 @pytest.mark.parametrize("name", _synth_names())
 def test_synthetic_stream_fixtures_in_gate(name, tmp_path_factory):
-    """The 18 synth_NN streams (synth_16 / 17: floors whose x[1] is not half the block size), fed as test_oracle_golden feeds them (fixture setup + the host entropy probe)."""
+    """The 20 synth_NN streams (synth_16 / 17: floors whose x[1] is not half the block size; synth_18 / 19: a floor per (mapping, submap)
+    and several modes per block size), fed as test_oracle_golden feeds them (fixture setup + the host entropy probe)."""
     from tests.test_oracle_golden import _oracle_on_stream
     from tests.workloads import fixture_setup
     res, z, d = _oracle_on_stream(name, tmp_path_factory)

@@ -96,7 +96,7 @@ LOUD_YS = (150, 250)   # floor range of loud packets: peak |pcm| about 150
 
 def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, ylo=28, yhi=88, unused_frac=0.0,
                 granule_last=False, roll=True, prev_long=None, next_long=None, residue="laplace", residue_scale=1.0,
-                floor_ranges=None, alternate=0):
+                floor_ranges=None, alternate=0, modes=None):
     """Synthetic batch in the shape of BASELINE configs 3/4:
     residue = round(Laplace(b=1.5)) with 60 % zeros; floor amplitudes a random walk in [ylo,yhi] (step +-6)
     over the setup's X list, wrapped into coded ys.  pattern: 'long', 'short', 'mixed' (L L L S*8 repeating, rotated per
@@ -108,6 +108,9 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
     times residue_scale; floor_ranges: one (ylo, yhi) per stream instead of (ylo, yhi); alternate=k: packets alternate between
     k quiet packets (floor range QUIET_YS) and k loud ones (LOUD_YS) within each segment, loud first, so that overlap carries run
     from loud blocks into quiet ones.
+    modes: the mode number of every packet, [streams * packets_per_stream] or a callable (stream, q) -> mode, instead of the setup's
+    first long and first short mode laid out by `pattern` (which is then ignored): the block flag, the window flags, the residue
+    length and the floor of each channel follow from the packet's mode (None leaves the batch unchanged, byte for byte).
     Returns dict(packets, segments, ys, residue, plane_stride)."""
     assert residue in ("laplace", "gauss"), residue
     rng = np.random.default_rng(seed)
@@ -123,9 +126,18 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
     else:
         unit = [1, 1, 1] + [0] * 8
         flags1 = np.array((unit * (packets_per_stream // len(unit) + 1))[:packets_per_stream], np.uint8)
-    long_mode = [i for i, (bf, _) in enumerate(spec.modes) if bf][0]
-    short_mode = [i for i, (bf, _) in enumerate(spec.modes) if not bf][0]
     P = streams * packets_per_stream
+    if modes is None:
+        long_mode = [i for i, (bf, _) in enumerate(spec.modes) if bf][0]
+        short_mode = [i for i, (bf, _) in enumerate(spec.modes) if not bf][0]
+        stream_flags = [flags1 if (not roll or pattern != "mixed") else np.roll(flags1, s % 11) for s in range(streams)]
+        stream_modes = [np.where(f, long_mode, short_mode) for f in stream_flags]
+    else:
+        if callable(modes):
+            modes = [modes(s, q) for s in range(streams) for q in range(packets_per_stream)]
+        stream_modes = np.asarray(modes, np.int64).reshape(streams, packets_per_stream)
+        assert 0 <= stream_modes.min() and stream_modes.max() < len(spec.modes)
+        stream_flags = [np.array([1 if spec.modes[int(m)][0] else 0 for m in row], np.uint8) for row in stream_modes]
     pk = np.zeros(P, PACKET_DTYPE)
     seg = np.zeros(streams, SEGMENT_DTYPE)
     stride = spec.ys_stride
@@ -133,12 +145,12 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
     res_parts = []
     off = 0
     for s in range(streams):
-        flags = flags1 if (not roll or pattern != "mixed") else np.roll(flags1, s % 11)
+        flags = stream_flags[s]
         seg[s] = (s, s * packets_per_stream, packets_per_stream, VSYN_SEG_RESET, off)
         for q in range(packets_per_stream):
             p = s * packets_per_stream + q
             lng = int(flags[q])
-            mode = long_mode if lng else short_mode
+            mode = int(stream_modes[s][q])
             n = spec.blocksize1 if lng else spec.blocksize0
             pk[p]["mode"] = mode
             if lng:
@@ -175,8 +187,7 @@ def synth_batch(spec, streams, packets_per_stream, pattern="long", seed=1234, yl
         pk["next_long"] = np.asarray(next_long, np.uint8)
     if granule_last:
         for s in range(streams):
-            fl = flags1 if (not roll or pattern != "mixed") else np.roll(flags1, s % 11)
-            sizes = np.where(fl, spec.blocksize1, spec.blocksize0)
+            sizes = np.where(stream_flags[s], spec.blocksize1, spec.blocksize0)
             total = int(sum(sizes[i - 1] // 4 + sizes[i] // 4 for i in range(1, packets_per_stream)))
             last_l = int(sizes[-2] // 4 + sizes[-1] // 4) if packets_per_stream > 1 else 0
             pk[s * packets_per_stream + packets_per_stream - 1]["granule"] = total - min(37, last_l // 2)  # clipped last packet
