@@ -7,11 +7,14 @@
 // one workgroup of 256 threads (4 waves) per (segment, tile of frames), by n_fft alone:
 //   vsyn_chroma_fft_kernel         n_fft a power of two: spec_lin_fft_tile_run (vsyn_spectral_lin.h), then S[f][k] = |X[k]|^power into
 //                                  the spare ping-pong buffer instead of a store of the bins.
-//   vsyn_chroma_direct_kernel<FT>  any other n_fft: the loop of vsyn_spec_stft_kernel in chunks of 256 bins, S of a chunk in LDS.
+//   vsyn_chroma_direct_kernel<FT>  any other n_fft: frames_stage_direct, then frames_dft_bin and frames_power_store (vsyn_frames.h) in chunks
+//                                  of 256 bins, S of a chunk in LDS, as the mel kernel (vsyn_spectral.h) runs them.
 // Both project with chroma_dot, one wave per (frame, c): lane l runs one fma chain over the bins l, l + 64, ... (ascending) of the
 // whole row (FFT kernel) or of the chunk (direct kernel, the chunks' sums added to R[f][c] in ascending order), W read from global
 // memory along k, S from LDS, then an xor-shuffle tree over lane distances 32 ... 1. chroma_finish then takes each frame's norm, the
 // non-finite rule and, for tonnetz, the 6 x n_chroma product, one wave per frame. No atomics; S and R never leave the workgroup.
+// The last of the spectral kinds' headers: behind the chroma kinds' share of the host side stands spec_launch, the one preamble of
+// every spectral kind, which sees all three.
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include <cfloat>
@@ -27,11 +30,17 @@ struct ChromaHeader {
 
 __device__ __forceinline__ const ChromaHeader* chroma_hdr(const uint8_t* t) { return (const ChromaHeader*)(t + spec_hdr(t)->pad); }
 
-// LDS images in floats: the FFT kernel's of vsyn_spectral_lin.h | R [ft][CHROMA_MAX]; the direct kernel's twiddles [2n] | window [n] |
-// span [(ft-1) hop + n] | S [ft][256] | R [ft][CHROMA_MAX]
+// LDS images in floats: the FFT kernel's of vsyn_spectral_lin.h | R [ft][CHROMA_MAX]; the direct kernel's FramesDirect head (twiddles [2n] |
+// window [n] | span [(ft-1) hop + n]) | S [ft][256] | R [ft][CHROMA_MAX]
 __host__ __device__ __forceinline__ uint64_t chroma_fft_lds_floats(uint32_t ft, uint32_t n) { return spec_lin_fft_lds_floats(ft, n) + (uint64_t)ft * CHROMA_MAX; }
 __host__ __device__ __forceinline__ uint64_t chroma_direct_lds_floats(uint32_t ft, uint32_t n, uint32_t hop) {
   return 3ull * n + spec_span_len(ft, n, hop) + (uint64_t)ft * SPEC_THREADS + (uint64_t)ft * CHROMA_MAX;
+}
+
+// the xor-shuffle tree over lane distances 32 ... 1: every lane returns the wave's sum
+__device__ __forceinline__ float chroma_tree_sum(float v) {
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
 }
 
 // sum_k w[k] s[k] over k < cnt by one wave: lane l's fma chain over k = l, l + 64, ... ascending, then the tree; every lane returns the sum.
@@ -49,13 +58,7 @@ __device__ __forceinline__ float chroma_dot(const float* __restrict__ w, const f
     for (uint32_t u = 0; u < 6u; ++u)
       if (k0 + 64u * u < cnt) acc = fmaf(wv[u], sv[u], acc);
   }
-  for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
-  return acc;
-}
-
-__device__ __forceinline__ float chroma_tree_sum(float v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+  return chroma_tree_sum(acc);
 }
 
 // Rows f0 .. f0 + nf - 1 from R [nf][NC] in LDS, one wave per frame: the norm, the division, the non-finite rule, and for tonnetz the
@@ -84,7 +87,7 @@ __device__ __forceinline__ void chroma_finish(const SpecHeader* H, const ChromaH
         s = s + a;
       }
       bad = __any(bad) != 0;
-      for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+      mx = frames_wave_max(mx);
       float N = mx;
       if (norm == VSYN_CHROMA_NORM_L1) {
         N = chroma_tree_sum(s);
@@ -174,31 +177,12 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_chroma_direct_kernel(const 
   const uint32_t F = A.segF[g];
   const uint32_t f0 = blockIdx.x * FT;
   if (f0 >= F) return;
-  const uint32_t n = H->n, hop = H->hop, nb = H->nbins, win = H->win, woff = H->woff, NC = CH->n_chroma;
+  const uint32_t nb = H->nbins, NC = CH->n_chroma;
   const uint32_t nf = min((uint32_t)FT, F - f0);
-  float2* s_tw = (float2*)lds;
-  float* s_win = lds + 2u * n;
-  float* s_span = s_win + n;
-  const uint32_t span = (uint32_t)spec_span_len(FT, n, hop);
-  float* s_S = s_span + span;             // [FT][256]
+  const FramesDirect D = frames_stage_direct(A, lds, (const float2*)(A.tab + H->off_tw), (const float*)(A.tab + H->off_win), H->n, H->hop,
+                                             (uint32_t)spec_span_len(FT, H->n, H->hop), H->win, H->woff, (H->opts & VSYN_SPEC_CENTER) != 0, g, f0);
+  float* s_S = D.rest;                   // [FT][256]
   float* s_R = s_S + FT * SPEC_THREADS;  // [nf][NC]
-  const float2* g_tw = (const float2*)(A.tab + H->off_tw);
-  const float* g_win = (const float*)(A.tab + H->off_win);
-  for (uint32_t i = tid; i < n; i += SPEC_THREADS) {
-    s_tw[i] = g_tw[i];
-    s_win[i] = g_win[i];
-  }
-  // the tile's span of the padded mono signal, as in vsyn_spec_stft_kernel
-  const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
-  const int64_t pad = (H->opts & VSYN_SPEC_CENTER) ? (int64_t)(n / 2u) : 0;
-  const int64_t p0 = (int64_t)f0 * hop - pad;
-  const uint32_t C = A.C;
-  const float invC = 1.0f / (float)C;
-  const float* x = A.pcm + (size_t)g * C * A.plane;
-  for (uint32_t i = tid; i < span; i += SPEC_THREADS) {
-    const int64_t t = p0 + (int64_t)i;
-    s_span[i] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, invC, (uint64_t)t) : 0.f;
-  }
   for (uint32_t i = tid; i < nf * NC; i += SPEC_THREADS) s_R[i] = 0.f;
   __syncthreads();
   const uint32_t ri = ((const uint32_t*)(A.tab + H->off_rate))[g];
@@ -206,31 +190,9 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_chroma_direct_kernel(const 
   const uint32_t wave = tid >> 6, lane = tid & 63u;
   for (uint32_t k0 = 0; k0 < nb; k0 += SPEC_THREADS) {
     const uint32_t k = k0 + tid;
-    float re[FT], im[FT];
-#pragma unroll
-    for (int f = 0; f < FT; ++f) re[f] = im[f] = 0.f;
-    if (k < nb) {
-      uint32_t idx = (uint32_t)(((uint64_t)woff * k) % n);
-      for (uint32_t j = woff; j < woff + win; ++j) {
-        const float2 tw = s_tw[idx];
-        const float w = s_win[j];
-        const float a = w * tw.x, b = w * tw.y;
-        const float* sp = s_span + j;
-#pragma unroll
-        for (int f = 0; f < FT; ++f) {
-          const float v = sp[f * hop];
-          re[f] = fmaf(v, a, re[f]);
-          im[f] = fmaf(v, b, im[f]);
-        }
-        idx += k;
-        if (idx >= n) idx -= n;
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < FT; ++f) {
-      const float p = fmaf(re[f], re[f], im[f] * im[f]);
-      s_S[f * SPEC_THREADS + tid] = H->power == 1 ? sqrtf(p) : p;
-    }
+    float re[FT] = {}, im[FT] = {};
+    if (k < nb) frames_dft_bin<FT>(D, k, re, im);
+    frames_power_store<FT>(re, im, H->power, s_S);
     __syncthreads();
     const uint32_t cnt = min((uint32_t)SPEC_THREADS, nb - k0);
     for (uint32_t p = wave; p < nf * NC; p += SPEC_THREADS / 64u) {  // (pair p stays with its wave over the chunks)
@@ -304,55 +266,93 @@ static inline uint32_t spec_chroma_tile(const vsyn_spectral_spec* sp) {
   return 0;
 }
 
-// spec_launch for the chroma kinds (it dispatches here): the linear kinds' table with the chroma block behind it, offsets, and the
-// FFT or direct kernel.
-static inline int spec_chroma_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, const vsyn_spectral_chroma* ch, uint32_t S,
-                                     const uint32_t* rates, const float* d_pcm, uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si,
-                                     uint64_t f_max, float* d_rows, uint64_t* d_segoff, hipStream_t s, const char** err) {
-  ch = spec_chroma_or_defaults(ch);
-  const uint32_t ft = spec_chroma_tile(sp), n = sp->n_fft, nb = n / 2u + 1u, NC = ch->n_chroma;
-  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", n, sp->hop_length);
+// The chroma block behind tab (the linear kinds' table of sp): one filterbank per rate of distinct (spec_build_table's list, in the
+// order of the table's rate indices) and phi. ch is checked.
+static inline int spec_chroma_table(SpectralWs& ws, const vsyn_spectral_spec* sp, const vsyn_spectral_chroma* ch, const std::vector<uint32_t>& distinct,
+                                    std::vector<uint8_t>& tab, const char** err) {
+  const uint32_t n = sp->n_fft, nb = n / 2u + 1u, NC = ch->n_chroma;
+  SpecHeader T;
+  memcpy(&T, tab.data(), sizeof(T));
+  const size_t off_ch = (tab.size() + 15) & ~(size_t)15;
+  const size_t off_w = off_ch + sizeof(ChromaHeader);
+  const size_t off_phi = off_w + 4ull * distinct.size() * NC * nb;
+  const size_t total = off_phi + 4ull * 6u * NC + 16;
+  if (total > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too many distinct sample rates (%zu) for one chroma table", distinct.size());
+  tab.resize(total, 0);
+  T.pad = (uint32_t)off_ch;
+  T.dim = spec_dim(sp, ch);
+  memcpy(tab.data(), &T, sizeof(T));
+  const ChromaHeader CH = {NC, ch->norm, (uint32_t)off_w, (uint32_t)off_phi};
+  memcpy(tab.data() + off_ch, &CH, sizeof(CH));
+  // the filterbanks of the last call are kept: a corpus run asks for the same ones submit after submit
+  std::vector<double> key = {(double)n, (double)NC, (double)ch->options, ch->tuning, ch->ctroct, ch->octwidth};
+  for (uint32_t r : distinct) key.push_back((double)r);
+  if (key != ws.chroma_key) {
+    ws.chroma_key.clear();  // (a throw below leaves no stale bank behind a matching key)
+    ws.chroma_bank.resize(distinct.size() * NC * nb);
+    for (size_t r = 0; r < distinct.size(); ++r) chroma_filterbank(distinct[r], n, ch, ws.chroma_bank.data() + r * NC * nb);
+    ws.chroma_key = key;
+  }
+  if (!ws.chroma_bank.empty()) memcpy(tab.data() + off_w, ws.chroma_bank.data(), 4 * ws.chroma_bank.size());
+  chroma_phi(NC, (float*)(tab.data() + off_phi));
+  return VSYN_OK;
+}
+
+// The chroma kinds' kernel behind the offsets kernel: FFT or direct on grid with ft frames per workgroup.
+static inline int spec_chroma_run(const SpecCtx& A, const vsyn_spectral_spec* sp, uint32_t ft, dim3 grid, hipStream_t s, const char** err) {
+  const uint32_t n = sp->n_fft;
+  if (spec_lin_pow2(n)) {
+    hipLaunchKernelGGL(vsyn_chroma_fft_kernel, grid, dim3(SPEC_THREADS), chroma_fft_lds_floats(ft, n) * 4u, s, A, ft, spec_lin_lgm(n));
+  } else {
+    const size_t lds = chroma_direct_lds_floats(ft, n, sp->hop_length) * 4u;
+    if (ft == CHROMA_DIRECT_FT) hipLaunchKernelGGL(vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
+    else hipLaunchKernelGGL(vsyn_chroma_direct_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
+  }
+  HIPCHK(hipGetLastError());
+  return VSYN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// every spectral kind: the launch
+// ------------------------------------------------------------------------------------------------
+// The dynamic-LDS limit of every kind's tile kernels, once per handle (the device is selected).
+static inline int spec_raise_lds(SpectralWs& ws, const char** err) {
+  if (ws.lds_set) return VSYN_OK;
+  const void* const kernels[9] = {(const void*)vsyn_spec_stft_kernel<16>,
+                                  (const void*)vsyn_spec_stft_kernel<4>,
+                                  (const void*)vsyn_spec_stft_kernel<1>,
+                                  (const void*)vsyn_spec_lin_fft_kernel,
+                                  (const void*)vsyn_spec_lin_direct_kernel<SPEC_LIN_DIRECT_FT>,
+                                  (const void*)vsyn_spec_lin_direct_kernel<1>,
+                                  (const void*)vsyn_chroma_fft_kernel,
+                                  (const void*)vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>,
+                                  (const void*)vsyn_chroma_direct_kernel<1>};
+  for (const void* k : kernels) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
+  ws.lds_set = true;
+  return VSYN_OK;
+}
+
+// The kernels of a spectral kind on stream s: the offsets kernel, then the kind's own (spec_mel_run, spec_lin_run, spec_chroma_run; ch,
+// NULL for the defaults, is read for a chroma kind only); frames from d_frames, else from si. f_max bounds every segment's STFT frames,
+// rows_bound the total rows. Caller holds the handle's lock and has run spec_check.
+static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
+                              uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
+                              uint64_t* d_segoff, hipStream_t s, const char** err, const vsyn_spectral_chroma* ch = nullptr) {
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  const bool lin = spec_is_lin(sp), chroma = spec_is_chroma(sp), mfcc = sp->kind == VSYN_SPEC_MFCC;
+  const uint32_t ft = lin ? spec_lin_tile(sp) : chroma ? spec_chroma_tile(sp) : spec_tile(sp);
+  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", sp->n_fft, sp->hop_length);
   std::vector<uint8_t> tab;
-  spec_build_table(sp, S, rates, tab);
-  {  // the chroma block: one filterbank per distinct rate, in the order of the table's rate indices (first appearance)
-    SpecHeader T;
-    memcpy(&T, tab.data(), sizeof(T));
-    std::vector<uint32_t> distinct;
-    for (uint32_t g = 0; g < S; ++g)
-      if (rates[g] && std::find(distinct.begin(), distinct.end(), rates[g]) == distinct.end()) distinct.push_back(rates[g]);
-    const size_t off_ch = (tab.size() + 15) & ~(size_t)15;
-    const size_t off_w = off_ch + sizeof(ChromaHeader);
-    const size_t off_phi = off_w + 4ull * distinct.size() * NC * nb;
-    const size_t total = off_phi + 4ull * 6u * NC + 16;
-    if (total > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too many distinct sample rates (%zu) for one chroma table", distinct.size());
-    tab.resize(total, 0);
-    T.pad = (uint32_t)off_ch;
-    T.dim = spec_dim(sp, ch);
-    memcpy(tab.data(), &T, sizeof(T));
-    const ChromaHeader CH = {NC, ch->norm, (uint32_t)off_w, (uint32_t)off_phi};
-    memcpy(tab.data() + off_ch, &CH, sizeof(CH));
-    // the filterbanks of the last call are kept: a corpus run asks for the same ones submit after submit
-    std::vector<double> key = {(double)n, (double)NC, (double)ch->options, ch->tuning, ch->ctroct, ch->octwidth};
-    for (uint32_t r : distinct) key.push_back((double)r);
-    if (key != ws.chroma_key) {
-      ws.chroma_key.clear();  // (a throw below leaves no stale bank behind a matching key)
-      ws.chroma_bank.resize(distinct.size() * NC * nb);
-      for (size_t r = 0; r < distinct.size(); ++r) chroma_filterbank(distinct[r], n, ch, ws.chroma_bank.data() + r * NC * nb);
-      ws.chroma_key = key;
-    }
-    if (!ws.chroma_bank.empty()) memcpy(tab.data() + off_w, ws.chroma_bank.data(), 4 * ws.chroma_bank.size());
-    chroma_phi(NC, (float*)(tab.data() + off_phi));
-  }
+  std::vector<uint32_t> distinct;
+  spec_build_table(sp, S, rates, tab, &distinct);
+  if (chroma)
+    if (int rc = spec_chroma_table(ws, sp, spec_chroma_or_defaults(ch), distinct, tab, err)) return rc;
   HIPCHK(hipSetDevice(device));
-  if (!ws.chroma_lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_chroma_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_chroma_direct_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    ws.chroma_lds_set = true;
-  }
+  if (int rc = spec_raise_lds(ws, err)) return rc;
   HIPCHK(ws.segF.ensure(S));
   HIPCHK(ws.segmax.ensure(S));
   HIPCHK(ws.segoff.ensure((size_t)S + 1));
+  if (mfcc) HIPCHK(ws.db.ensure(rows_bound * sp->n_mels + 1));
   if (int rc = ws.tab.upload(tab, s, err)) return rc;
   SpecCtx A;
   A.tab = ws.tab.dev.p;
@@ -366,22 +366,14 @@ static inline int spec_chroma_launch(SpectralWs& ws, int device, const vsyn_spec
   A.segoff = d_segoff ? d_segoff : ws.segoff.p;
   A.segmax = ws.segmax.p;
   A.rows = d_rows;
-  A.db = nullptr;
+  A.db = mfcc ? ws.db.p : nullptr;
   hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
   HIPCHK(hipGetLastError());
   if (f_max == 0 || S == 0) return VSYN_OK;
   const uint64_t gx = (f_max + ft - 1) / ft;
   if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
   const dim3 grid((uint32_t)gx, S);
-  if (spec_lin_pow2(n)) {
-    uint32_t lgM = 0;
-    while ((2u << lgM) < n) ++lgM;
-    hipLaunchKernelGGL(vsyn_chroma_fft_kernel, grid, dim3(SPEC_THREADS), chroma_fft_lds_floats(ft, n) * 4u, s, A, ft, lgM);
-  } else {
-    const size_t lds = chroma_direct_lds_floats(ft, n, sp->hop_length) * 4u;
-    if (ft == CHROMA_DIRECT_FT) hipLaunchKernelGGL(vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
-    else hipLaunchKernelGGL(vsyn_chroma_direct_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
-  }
-  HIPCHK(hipGetLastError());
-  return VSYN_OK;
+  if (lin) return spec_lin_run(A, sp, ft, grid, f_max, s, err);
+  if (chroma) return spec_chroma_run(A, sp, ft, grid, s, err);
+  return spec_mel_run(A, sp, ft, grid, f_max, s, err);
 }

@@ -7,6 +7,7 @@
 //   3. vsyn_istft_masked_kernel on the same PCM under that mask, and vsyn_istft_ola_kernel to each segment's own length (vsyn_istft.h).
 // The complex bins are never stored: step 3 recomputes the forward transform in the workgroup that inverts it.
 #pragma once
+#include "vsyn_chroma.h"  // spec_launch
 #include "vsyn_hpss.h"
 #include "vsyn_istft.h"
 

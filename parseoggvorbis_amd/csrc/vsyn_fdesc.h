@@ -2,15 +2,16 @@
 // planar float32 PCM already on the device. Semantics: include/vorbis_synth_hip.h, "frame descriptors".
 //
 // Three kernels on one stream (the table — per-segment rates, float64 twiddles, float32 window — is built on the host per call):
-//   1. vsyn_fdesc_offsets_kernel  one workgroup: per segment its frame count (spec_num_frames) and the exclusive row scan seg_off[S+1]
-//                                 (the pitch stage's offsets kernel).
+//   1. vsyn_fdesc_offsets_kernel  one workgroup: per segment its frame count (spec_num_frames) and the exclusive row scan seg_off[S+1]:
+//                                 frames_offsets (vsyn_frames.h).
 //   2. vsyn_fdesc_kernel<TWL>     grid (tile of FT frames, segment), 256 threads. Dynamic LDS, declared 16-byte aligned, in this order:
 //                                   twiddles (cos, sin)[n_fft] float64, TWL only
 //                                   S[FT][NB] float64, NB = n_fft / 2 + 1: the magnitudes of the tile's frames
 //                                   26 words of 8 bytes for the reductions
 //                                   window[n_fft] float32
 //                                   the tile's span of the mono signal as float32 (the downmix is done while loading, zeros outside
-//                                   [0, T); hop > n_fft: the frames back to back, as the pitch and trim stages stage them).
+//                                   [0, T); hop > n_fft: the frames back to back): frames_tile_head / frames_tile_derive / frames_tile_stage
+//                                   (vsyn_frames.h), which also write the tile's flag word.
 //                                 DFT: the tile's frames are taken in groups of FDESC_ILP, and the (group, bin) items are dealt to
 //                                 the threads in order, bin fastest. A thread owns its bin k for the frames of its group and walks
 //                                 j = 0 .. n_fft - 1: window[j] and each frame's y[j] are one address per wave (broadcast reads),
@@ -26,7 +27,7 @@
 //                                 The workgroup also looks at every sample of its share of the segment for an Inf or a NaN
 //                                 (trim_not_finite) and stores one flag word per tile.
 //   3. vsyn_fdesc_finish_kernel   one workgroup per segment: a segment with a flagged tile is refused: its rows become NaN and its
-//                                 word of the refused array 1.
+//                                 word of the refused array 1 (frames_finish).
 // Order of the sums over the bins: with K = ceil(NB / 256), thread t owns the bins t K .. min((t + 1) K, NB) - 1 and adds its terms in
 // ascending order from 0.0 (its total). The totals are scanned inside each wave by Hillis-Steele over the lane offsets 1, 2, .. 32; a
 // wave's offset is the sum of the earlier waves' totals in ascending order; a sum over all bins is ((w0 + w1) + w2) + w3 of the four
@@ -39,12 +40,13 @@
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_frames.h"
 #include "vsyn_host.h"
-#include "vsyn_pitch.h"
-#include "vsyn_spectral.h"
+#include "vsyn_pitch.h"  // pitch_wg_min, PITCH_NONE
 #include "vsyn_trim.h"
 
 #define FDESC_THREADS 256
+static_assert(FDESC_THREADS == FRAMES_THREADS, "the shared framing helpers stride by the workgroup's size");
 #define FDESC_WAVES (FDESC_THREADS / 64)
 #define FDESC_ILP 4u                         // frames per thread and twiddle read: 8 independent fma chains
 #define FDESC_FT_MAX 64u                     // frames per workgroup, at most
@@ -76,15 +78,8 @@ struct FdescCtx {  // launch arguments
   float* rows;             // [segoff[S]][6]
 };
 
-__device__ __forceinline__ uint64_t fdesc_frames(const FdescCtx& A, uint32_t g) {
-  return trim_min64(A.frames ? A.frames[g] : A.si[g].total_emit, A.plane);
-}
-
 __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_offsets_kernel(const FdescCtx A) {
-  wg_exclusive_scan<FDESC_THREADS, 1>(A.S, A.segoff, [&](uint32_t g, uint64_t* v) {
-    v[0] = A.sr[g] != 0.0 ? spec_num_frames(A.N, A.H, A.center != 0, fdesc_frames(A, g)) : 0ull;
-    A.segF[g] = (uint32_t)v[0];
-  });
+  frames_offsets(A, A.N, [&](uint32_t g) { return A.sr[g] == 0.0; });
 }
 
 // M sums over the workgroup in the order of the header: v = this thread's totals; exc = the sum of the totals of the threads in front
@@ -156,24 +151,10 @@ __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCt
   extern __shared__ __attribute__((aligned(16))) double s_fdesc[];
   const uint32_t g = blockIdx.y, tid = threadIdx.x;
   const double sr = A.sr[g];
-  uint32_t* flag = A.flags + (size_t)g * A.tiles + blockIdx.x;
-  const uint64_t F = A.segF[g];
-  const uint64_t f0 = (uint64_t)blockIdx.x * A.FT;
-  if (sr == 0.0 || (f0 >= F && blockIdx.x != 0u)) {  // (workgroup-uniform) nothing here: the flag word is still this workgroup's to write
-    if (tid == 0) *flag = 0u;
-    return;
-  }
-  const uint64_t T = fdesc_frames(A, g);
+  FramesTile t;
+  if (frames_tile_head(A, sr == 0.0, t)) return frames_tile_idle(t);
+  frames_tile_derive(A, A.N, t);
   const uint32_t N = A.N, H = A.H, NB = N / 2u + 1u;
-  const uint32_t nf = f0 < F ? (uint32_t)trim_min64(A.FT, F - f0) : 0u;  // (F = 0, T > 0: tile 0 still looks at the samples)
-  const bool last = f0 + A.FT >= F;
-  const uint32_t C = A.C;
-  const float inv_c = 1.0f / (float)C;
-  const float* x = A.pcm + (size_t)g * C * A.plane;
-  const int64_t pad = A.center ? (int64_t)(N / 2u) : 0;
-  const bool apart = H > N;  // frames that do not touch: staged back to back
-  const uint32_t fstep = apart ? N : H, staged = nf ? (nf - 1u) * fstep + N : 0u;
-  const int64_t base = (int64_t)(f0 * H) - pad;  // sample index of the first staged float
   const double2* s_tw = (const double2*)s_fdesc;  // (first: the image is declared 16-byte aligned, for the 16-byte twiddle reads)
   double* s_S = s_fdesc + (TWL ? 2u * (size_t)N : 0u);
   double* s_w = s_S + (size_t)A.FT * NB;  // the reductions' words
@@ -181,42 +162,29 @@ __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCt
   uint64_t* s_r = (uint64_t*)(s_a + 1);
   float* s_win = (float*)(s_w + FDESC_WORDS);
   float* s_y = s_win + N;
-  if (nf) {
+  if (t.nf) {
     if (TWL)
       for (uint32_t u = tid; u < N; u += FDESC_THREADS) ((double2*)s_tw)[u] = A.tw[u];
     for (uint32_t u = tid; u < N; u += FDESC_THREADS) s_win[u] = A.win[u];
   }
-  for (uint32_t u = tid; u < staged; u += FDESC_THREADS) {
-    const int64_t t = apart ? base + (int64_t)(u / N) * H + (u % N) : base + u;
-    s_y[u] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t) : 0.f;
-  }
-  // the workgroup's share of the segment, [its first frame's start, the next tile's), the first tile from 0 and the last up to T
-  {
-    const int64_t lo = blockIdx.x == 0u ? 0 : (base > 0 ? base : 0);
-    int64_t hi = last ? (int64_t)T : (int64_t)((f0 + A.FT) * H) - pad;
-    if (hi > (int64_t)T) hi = (int64_t)T;
-    bool bad = false;
-    for (int64_t t = lo + tid; t < hi; t += FDESC_THREADS) bad |= trim_not_finite(pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t));
-    const int any = __syncthreads_or(bad ? 1 : 0);  // (also the barrier behind the staging)
-    if (tid == 0) *flag = any ? 1u : 0u;
-  }
-  if (nf == 0u) return;
+  frames_tile_stage(A, t, s_y);
+  if (t.nf == 0u) return;
 
   // S[f][k]: one fma chain per component of (f, k), j ascending. An item is (group of up to FDESC_ILP frames, bin); a wave without one
   // skips the pass (the CU's other workgroup has the SIMD meanwhile).
-  const uint32_t items = ((nf + FDESC_ILP - 1u) / FDESC_ILP) * NB;
+  const uint32_t items = ((t.nf + FDESC_ILP - 1u) / FDESC_ILP) * NB;
   for (uint32_t q0 = 0; q0 < items; q0 += FDESC_THREADS) {
     if (q0 + (tid & ~63u) >= items) continue;  // (wave-uniform; no barrier inside the loop)
     const uint32_t q = q0 + tid;
     if (q >= items) continue;
     const uint32_t grp = q / NB, k = q - grp * NB, fa = grp * FDESC_ILP;
-    const float* z0 = s_y + (size_t)fa * fstep;
+    const float* z0 = s_y + (size_t)fa * t.fstep;
     double* out = s_S + (size_t)fa * NB + k;
-    switch (nf - fa) {
-      case 1u: fdesc_dft<TWL, 1u>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
-      case 2u: fdesc_dft<TWL, 2u>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
-      case 3u: fdesc_dft<TWL, 3u>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
-      default: fdesc_dft<TWL, FDESC_ILP>(s_tw, A.tw, s_win, z0, fstep, N, k, out, NB); break;
+    switch (t.nf - fa) {
+      case 1u: fdesc_dft<TWL, 1u>(s_tw, A.tw, s_win, z0, t.fstep, N, k, out, NB); break;
+      case 2u: fdesc_dft<TWL, 2u>(s_tw, A.tw, s_win, z0, t.fstep, N, k, out, NB); break;
+      case 3u: fdesc_dft<TWL, 3u>(s_tw, A.tw, s_win, z0, t.fstep, N, k, out, NB); break;
+      default: fdesc_dft<TWL, FDESC_ILP>(s_tw, A.tw, s_win, z0, t.fstep, N, k, out, NB); break;
     }
   }
   __syncthreads();
@@ -225,14 +193,14 @@ __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCt
   const uint32_t b0 = tid * K < NB ? tid * K : NB, b1 = b0 + K < NB ? b0 + K : NB;  // this thread's bins
   const uint32_t KJ = (N + FDESC_THREADS - 1u) / FDESC_THREADS;
   const uint32_t j0 = tid * KJ < N ? tid * KJ : N, j1 = j0 + KJ < N ? j0 + KJ : N;  // this thread's samples
-  const double y_first = (double)pcm_downmix(x, A.plane, C, inv_c, 0ull);           // (F > 0: T > 0) zcr's edge padding
-  const double y_last = (double)pcm_downmix(x, A.plane, C, inv_c, T - 1u);
+  const double y_first = (double)pcm_downmix(t.x, A.plane, t.C, t.inv_c, 0ull);  // (F > 0: T > 0) zcr's edge padding
+  const double y_last = (double)pcm_downmix(t.x, A.plane, t.C, t.inv_c, t.T - 1u);
   const double dn = (double)N, dnb = (double)NB;
-  const uint64_t r0 = A.segoff[g] + f0;
-  for (uint32_t f = 0; f < nf; ++f) {
+  const uint64_t r0 = A.segoff[g] + t.f0;
+  for (uint32_t f = 0; f < t.nf; ++f) {
     const double* S = s_S + (size_t)f * NB;
-    const float* z = s_y + (size_t)f * fstep;
-    const int64_t t0 = (int64_t)((f0 + f) * H) - pad;  // the frame's first sample
+    const float* z = s_y + (size_t)f * t.fstep;
+    const int64_t t0 = (int64_t)((t.f0 + f) * H) - t.pad;  // the frame's first sample
     // the sums of the first pass, and the zero crossings of this thread's samples
     double v[FDESC_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0}, exc[FDESC_SUMS], tot[FDESC_SUMS];
     for (uint32_t kk = b0; kk < b1; ++kk) {
@@ -248,8 +216,8 @@ __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCt
       v[4] = fma(y, y, v[4]);
       if (j == 0u) continue;
       const int64_t ta = t0 + (int64_t)j - 1, tb = ta + 1;
-      const double ya = ta < 0 ? y_first : (uint64_t)ta >= T ? y_last : (double)z[j - 1u];
-      const double yb = tb < 0 ? y_first : (uint64_t)tb >= T ? y_last : y;
+      const double ya = ta < 0 ? y_first : (uint64_t)ta >= t.T ? y_last : (double)z[j - 1u];
+      const double yb = tb < 0 ? y_first : (uint64_t)tb >= t.T ? y_last : y;
       const bool sa = ya < 0.0 && fabs(ya) > A.zthr, sb = yb < 0.0 && fabs(yb) > A.zthr;
       cross += sa != sb ? 1u : 0u;
     }
@@ -295,17 +263,7 @@ __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCt
   }
 }
 
-__global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_finish_kernel(const FdescCtx A) {
-  const uint32_t g = blockIdx.x, tid = threadIdx.x;
-  bool bad = false;
-  for (uint32_t i = tid; i < A.tiles; i += FDESC_THREADS) bad |= A.flags[(size_t)g * A.tiles + i] != 0u;
-  const int refused = __syncthreads_or(bad ? 1 : 0);
-  if (tid == 0 && A.refused) A.refused[g] = refused ? 1u : 0u;
-  if (!refused) return;
-  float* rows = A.rows + (size_t)FDESC_COLS * A.segoff[g];
-  const uint64_t nv = (uint64_t)FDESC_COLS * A.segF[g];
-  for (uint64_t i = tid; i < nv; i += FDESC_THREADS) rows[i] = __uint_as_float(0x7FC00000u);
-}
+__global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_finish_kernel(const FdescCtx A) { frames_finish(A, FDESC_COLS); }
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -356,23 +314,14 @@ static inline uint32_t fdesc_tile(uint32_t n, uint32_t h, bool twl) {
 static inline int fdesc_launch(FdescWs& ws, int device, const vsyn_fdesc_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
                                uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
                                uint64_t* d_segoff, uint32_t* d_refused, hipStream_t s, const char** err) {
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_rows & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM and row pointers must be 4-byte aligned");
-  if (plane > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
+  if (int rc = frames_check_call(S, d_pcm, d_rows, plane, err)) return rc;
   const uint32_t n = sp->n_fft, h = sp->hop_length;
   // the table: (cos, sin)[n] as double | window [n] as float (rebuilt only when n_fft or win_length change) | rates [S] as double
   const size_t off_win = 16u * (size_t)n, off_sr = align_up(off_win + 4u * (size_t)n, 16);
   if (ws.fixed_n != n || ws.fixed_win != sp->win_length) {
     ws.fixed.assign(off_sr, 0);
-    double* tw = (double*)ws.fixed.data();
-    for (uint32_t m = 0; m < n; ++m) {
-      const double a = 2.0 * M_PI * (double)m / (double)n;
-      tw[2u * m] = cos(a);
-      tw[2u * m + 1u] = sin(a);
-    }
-    float* wn = (float*)(ws.fixed.data() + off_win);  // the spectral stage's window: periodic Hann of win_length, centred in n_fft
-    const uint32_t woff = (n - sp->win_length) / 2u;
-    for (uint32_t i = 0; i < sp->win_length; ++i) wn[woff + i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)sp->win_length));
+    twiddle_table(n, (double*)ws.fixed.data());
+    hann_centred(n, sp->win_length, (float*)(ws.fixed.data() + off_win));  // the spectral stage's window
     ws.fixed_n = n;
     ws.fixed_win = sp->win_length;
   }
@@ -382,48 +331,24 @@ static inline int fdesc_launch(FdescWs& ws, int device, const vsyn_fdesc_spec* s
   for (uint32_t g = 0; g < S; ++g) sr[g] = (double)rates[g];
   const bool twl = fdesc_twiddles_in_lds(n, h);
   const uint32_t ft = fdesc_tile(n, h, twl);
-  const uint64_t tiles = std::max<uint64_t>((f_max + ft - 1u) / ft, 1);
-  if (tiles > 0x7FFFFFFFull || f_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  HIPCHK(hipSetDevice(device));
-  if (!ws.lds_set) {
+  const auto raise_lds = [&]() -> int {
+    if (ws.lds_set) return VSYN_OK;
     HIPCHK(hipFuncSetAttribute((const void*)vsyn_fdesc_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FDESC_LDS_BUDGET));
     HIPCHK(hipFuncSetAttribute((const void*)vsyn_fdesc_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FDESC_LDS_WIDE));
     ws.lds_set = true;
-  }
-  HIPCHK(ws.segF.ensure(S));
-  HIPCHK(ws.segoff.ensure((size_t)S + 1));
-  HIPCHK(ws.flags.ensure((size_t)S * tiles));
-  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+    return VSYN_OK;
+  };
   FdescCtx A;
+  if (int rc = frames_begin(ws, device, tab, ft, h, (sp->options & VSYN_FDESC_CENTER) != 0, S, d_pcm, plane, C, d_frames, si, f_max, d_rows, d_segoff,
+                            d_refused, s, err, raise_lds, A))
+    return rc;
   A.sr = (const double*)(ws.tab.dev.p + off_sr);
   A.tw = (const double2*)ws.tab.dev.p;
   A.win = (const float*)(ws.tab.dev.p + off_win);
-  A.pcm = d_pcm;
-  A.plane = plane;
-  A.C = C;
-  A.S = S;
-  A.frames = d_frames;
-  A.si = si;
   A.N = n;
-  A.H = h;
-  A.FT = ft;
-  A.center = (sp->options & VSYN_FDESC_CENTER) ? 1u : 0u;
-  A.tiles = (uint32_t)tiles;
   A.roll = sp->roll_percent;
   A.zthr = sp->zcr_threshold;
   A.amin = sp->amin;
-  A.segF = ws.segF.p;
-  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
-  A.flags = ws.flags.p;
-  A.refused = d_refused;
-  A.rows = d_rows;
-  hipLaunchKernelGGL(vsyn_fdesc_offsets_kernel, dim3(1), dim3(FDESC_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  const size_t lds = fdesc_lds_bytes(ft, n, h, twl);
-  if (twl) hipLaunchKernelGGL(vsyn_fdesc_kernel<true>, dim3((uint32_t)tiles, S), dim3(FDESC_THREADS), lds, s, A);
-  else hipLaunchKernelGGL(vsyn_fdesc_kernel<false>, dim3((uint32_t)tiles, S), dim3(FDESC_THREADS), lds, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_fdesc_finish_kernel, dim3(S), dim3(FDESC_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  return VSYN_OK;
+  return frames_launch(A, vsyn_fdesc_offsets_kernel, twl ? vsyn_fdesc_kernel<true> : vsyn_fdesc_kernel<false>, fdesc_lds_bytes(ft, n, h, twl),
+                       vsyn_fdesc_finish_kernel, s, err);
 }

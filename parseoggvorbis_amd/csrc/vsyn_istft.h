@@ -7,7 +7,8 @@
 //                             kernel's LDS image (spec_lin_fft_lds_floats). Per frame the inverse of vsyn_spec_lin_fft_kernel, pass
 //                             for pass: the tangling pass builds the half-size spectrum Z[k] from Y[k] and conj Y[M - k] (Y = m X, one
 //                             float32 product per component), the same radix-2 Stockham passes run with conjugated twiddles
-//                             between the same two LDS buffers (per-pass twiddle runs read at stride 1), and z[m] = x[2m] + i x[2m+1]
+//                             (frames_stockham<true> behind frames_stockham_twiddles, vsyn_frames.h: the one pass loop of both
+//                             directions) between the same two LDS buffers, and z[m] = x[2m] + i x[2m+1]
 //                             leaves as v[j] = w[j] * (x[j] / n_fft) into the frame workspace, [rows][n_fft] float32. A frame owns
 //                             its M complex words: nothing of one frame enters another's sums.
 //   vsyn_istft_masked_kernel  the frame kernel for a chain (vsyn_effects.h): the forward transform of the PCM by spec_lin_fft_tile_run, the
@@ -55,39 +56,6 @@ __device__ __forceinline__ float2 istft_tangle(float2 a, float2 b, float2 w, uin
   return make_float2(er - (w.x * di + w.y * dr), ei + (w.x * dr - w.y * di));
 }
 
-// The per-pass twiddle runs of spec_lin_fft_tile_run into its place of the LDS image. No barrier behind it.
-__device__ __forceinline__ void istft_twiddles(const float2* g_tw, float2* s_st, uint32_t M, uint32_t lgM) {
-  for (uint32_t e = threadIdx.x; e + 1u < M; e += SPEC_THREADS) {
-    const uint32_t lv = 31u - (uint32_t)__clz((int)(e + 1u)), Ns = 1u << lv, k = e + 1u - Ns;
-    s_st[e] = g_tw[k << (lgM - lv)];
-  }
-}
-
-// The Stockham passes of spec_lin_fft_tile_run with conjugated twiddles: src [ft][M] (filled, no barrier needed in front) to the
-// unnormalised inverse transform, natural order in and out. Returns the buffer that holds it; ends behind a barrier.
-__device__ __forceinline__ const float2* istft_passes(const float2* s_st, float2* src, float2* dst, uint32_t ft, uint32_t lgM) {
-  const uint32_t M = 1u << lgM, half = M >> 1, tot = ft * half;
-  for (uint32_t Ns = 1; Ns < M; Ns <<= 1) {
-    __syncthreads();
-    for (uint32_t q = threadIdx.x; q < tot; q += SPEC_THREADS) {
-      const uint32_t f = q >> (lgM - 1u), j = q & (half - 1u), k = j & (Ns - 1u);
-      const float2 w = s_st[Ns - 1u + k];
-      const float2* in = src + (size_t)f * M;
-      const float2 a = in[j], b = in[j + half];
-      const float tr = w.x * b.x - w.y * b.y;
-      const float ti = w.x * b.y + w.y * b.x;
-      float2* out = dst + (size_t)f * M + (((j - k) << 1) + k);
-      out[0] = make_float2(a.x + tr, a.y + ti);
-      out[Ns] = make_float2(a.x - tr, a.y - ti);
-    }
-    float2* sw = src;
-    src = dst;
-    dst = sw;
-  }
-  __syncthreads();
-  return src;
-}
-
 // v[2m], v[2m+1] = w * (z / n_fft) of the tile's nf frames into the workspace rows r0 ..; 0 outside the window's support.
 __device__ __forceinline__ void istft_store(const SpecHeader* H, const float* g_win, const float2* z, float* frames, uint64_t r0, uint32_t nf,
                                             uint32_t lgM) {
@@ -115,7 +83,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_istft_frames_kernel(const I
   float2* src = s_st + 2u * M + 1u;  // behind the forward image's untangling twiddles, which this kernel reads from the table
   float2* dst = src + (size_t)ft * M;
   const float2* g_tw = (const float2*)(A.tab + H->off_tw);
-  istft_twiddles(g_tw, s_st, M, lgM);
+  frames_stockham_twiddles(g_tw, s_st, M, lgM);
   // the tangling pass reads its twiddle from the table, once per bin and at stride 1 along k
   const uint64_t r0 = sg.off + f0;
   for (uint32_t q = threadIdx.x; q < ft * M; q += SPEC_THREADS) {
@@ -128,8 +96,8 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_istft_frames_kernel(const I
     }
     src[q] = Z;
   }
-  const float2* z = istft_passes(s_st, src, dst, ft, lgM);
-  istft_store(H, (const float*)(A.tab + H->off_win), z, A.frames, r0, nf, lgM);
+  frames_stockham<true>(s_st, src, dst, ft, 1u << lgM, lgM);
+  istft_store(H, (const float*)(A.tab + H->off_win), src, A.frames, r0, nf, lgM);
 }
 
 // The frame kernel from the PCM, for a chain: the forward transform of vsyn_spec_lin_fft_kernel (spec_lin_fft_tile_run on P's PCM), the
@@ -160,8 +128,9 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_istft_masked_kernel(const S
     }
     T.spare[q] = Z;
   }
-  const float2* z = istft_passes((const float2*)lds, T.spare, (float2*)T.Z, ft, lgM);
-  istft_store(H, (const float*)(A.tab + H->off_win), z, A.frames, r0, nf, lgM);
+  float2 *src = T.spare, *dst = (float2*)T.Z;  // (Z is read out: its buffer is the passes' other one)
+  frames_stockham<true>((const float2*)lds, src, dst, ft, 1u << lgM, lgM);
+  istft_store(H, (const float*)(A.tab + H->off_win), src, A.frames, r0, nf, lgM);
 }
 
 // y[t] = (sum_f v_f[t + pad - f hop]) / W[t], W[t] = sum_f w[t + pad - f hop]^2 over the frames whose window support holds t, f
@@ -287,8 +256,7 @@ static inline int istft_launch(IstftWs& ws, int device, const vsyn_spectral_spec
   A.plane = plane;
   A.out_frames = d_out_frames;
   if (f_max && len_max) {
-    uint32_t lgM = 0;
-    while ((2u << lgM) < n) ++lgM;
+    const uint32_t lgM = spec_lin_lgm(n);
     const size_t lds = spec_lin_fft_lds_floats(ft, n) * 4u;
     if (fwd) {
       SpecCtx P = *fwd;

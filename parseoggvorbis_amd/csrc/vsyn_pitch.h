@@ -3,10 +3,10 @@
 //
 // Three kernels on one stream (the per-segment periods are built on the host in double, pitch_periods):
 //   1. vsyn_pitch_offsets_kernel  one workgroup: per segment its PCM frames, its frame count (spec_num_frames), the exclusive row
-//                                 scan seg_off[S+1] (the spectral stage's offsets kernel, without its dB maxima).
+//                                 scan seg_off[S+1]: frames_offsets (vsyn_frames.h).
 //   2. vsyn_pitch_kernel          grid (tile of FT frames, segment). LDS: the tile's span of the mono signal as float32 (the downmix
-//                                 is done while loading, zeros outside [0, T); H > L: the frames back to back, as the trim stage
-//                                 stages them), then d[FT][p_max] as float64.
+//                                 is done while loading, zeros outside [0, T); H > L: the frames back to back), staged by
+//                                 frames_tile_head / frames_tile_derive / frames_tile_stage (vsyn_frames.h), then d[FT][p_max] as float64.
 //                                 Difference function: the (frame, lag) pairs of the tile are dealt to the threads in order, lag
 //                                 fastest, PITCH_ILP pairs per thread PITCH_THREADS apart. A thread owns its lag tau and walks j =
 //                                 1 .. W: z[j] is one address per frame (a broadcast read), z[j + tau] consecutive across the lanes
@@ -18,9 +18,9 @@
 //                                 the first trough below the threshold and the first minimum by 64-bit integer minima through the
 //                                 wave (__shfl_xor) and the four waves (LDS), and thread 0 writes the row. No atomics.
 //                                 The workgroup also looks at every sample of its share of the segment for an Inf or a NaN
-//                                 (trim_not_finite, the trim stage's test) and stores one flag word per tile.
+//                                 (trim_not_finite, the trim stage's test) and stores one flag word per tile (frames_tile_stage).
 //   3. vsyn_pitch_finish_kernel   one workgroup per segment: a segment with a flagged tile is refused: its rows become NaN and its
-//                                 word of the refused array 1.
+//                                 word of the refused array 1 (frames_finish).
 // Order of S: with K = ceil(p_max / PITCH_THREADS), thread t owns the lags t K + 1 .. (t + 1) K. It adds its d in ascending order
 // (its total), the totals are scanned inside each wave by Hillis-Steele over the lane offsets 1, 2, .. 32, a wave's offset is the sum
 // of the earlier waves' totals in ascending order, and S[tau] = (wave offset + the exclusive lane prefix) + d[first] + .. + d[tau],
@@ -28,11 +28,12 @@
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_frames.h"
 #include "vsyn_host.h"
-#include "vsyn_spectral.h"
 #include "vsyn_trim.h"
 
 #define PITCH_THREADS 256
+static_assert(PITCH_THREADS == FRAMES_THREADS, "the shared framing helpers stride by the workgroup's size");
 #define PITCH_WAVES (PITCH_THREADS / 64)
 #define PITCH_ILP 4u                        // independent fma chains per thread
 #define PITCH_FT_MAX 64u                    // frames per workgroup, at most
@@ -63,15 +64,8 @@ struct PitchCtx {  // launch arguments
   float* rows;             // [segoff[S]][2]
 };
 
-__device__ __forceinline__ uint64_t pitch_frames(const PitchCtx& A, uint32_t g) {
-  return trim_min64(A.frames ? A.frames[g] : A.si[g].total_emit, A.plane);
-}
-
 __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_offsets_kernel(const PitchCtx A) {
-  wg_exclusive_scan<PITCH_THREADS, 1>(A.S, A.segoff, [&](uint32_t g, uint64_t* v) {
-    v[0] = A.seg[g].p_max ? spec_num_frames(A.L, A.H, A.center != 0, pitch_frames(A, g)) : 0ull;
-    A.segF[g] = (uint32_t)v[0];
-  });
+  frames_offsets(A, A.L, [&](uint32_t g) { return A.seg[g].p_max == 0u; });
 }
 
 // the minimum of v over the workgroup, for every thread (s_r: PITCH_WAVES words of LDS, free again on return)
@@ -90,40 +84,15 @@ __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCt
   __shared__ double s_w[PITCH_WAVES];
   const uint32_t g = blockIdx.y, tid = threadIdx.x;
   const PitchSeg sg = A.seg[g];
-  uint32_t* flag = A.flags + (size_t)g * A.tiles + blockIdx.x;
-  const uint64_t F = A.segF[g];
-  const uint64_t f0 = (uint64_t)blockIdx.x * A.FT;
-  if (sg.p_max == 0u || (f0 >= F && blockIdx.x != 0u)) {  // (workgroup-uniform) nothing here: the flag word is still this workgroup's to write
-    if (tid == 0) *flag = 0u;
-    return;
-  }
-  const uint64_t T = pitch_frames(A, g);
-  const uint32_t L = A.L, H = A.H, W = L / 2u, PL = sg.p_max;
-  const uint32_t nf = f0 < F ? (uint32_t)trim_min64(A.FT, F - f0) : 0u;  // (F = 0, T > 0: tile 0 still looks at the samples)
-  const bool last = f0 + A.FT >= F;
-  const uint32_t C = A.C;
-  const float inv_c = 1.0f / (float)C;
-  const float* x = A.pcm + (size_t)g * C * A.plane;
-  const int64_t pad = A.center ? (int64_t)W : 0;
-  const bool apart = H > L;  // frames that do not touch: staged back to back
-  const uint32_t fstep = apart ? L : H, staged = nf ? (nf - 1u) * fstep + L : 0u;
-  const int64_t base = (int64_t)(f0 * H) - pad;  // sample index of the first staged float
+  FramesTile t;
+  if (frames_tile_head(A, sg.p_max == 0u, t)) return frames_tile_idle(t);
+  frames_tile_derive(A, A.L, t);
+  const uint32_t L = A.L, W = L / 2u, PL = sg.p_max;
+  const uint32_t nf = t.nf, fstep = t.fstep;
+  const uint64_t f0 = t.f0;
   float* s_y = (float*)s_pitch;
   double* s_d = s_pitch + (((size_t)(A.FT - 1u) * fstep + L + 1u) >> 1);
-  for (uint32_t u = tid; u < staged; u += PITCH_THREADS) {
-    const int64_t t = apart ? base + (int64_t)(u / L) * H + (u % L) : base + u;
-    s_y[u] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t) : 0.f;
-  }
-  // the workgroup's share of the segment, [its first frame's start, the next tile's), the first tile from 0 and the last up to T
-  {
-    const int64_t lo = blockIdx.x == 0u ? 0 : (base > 0 ? base : 0);
-    int64_t hi = last ? (int64_t)T : (int64_t)((f0 + A.FT) * H) - pad;
-    if (hi > (int64_t)T) hi = (int64_t)T;
-    bool bad = false;
-    for (int64_t t = lo + tid; t < hi; t += PITCH_THREADS) bad |= trim_not_finite(pcm_downmix(x, A.plane, C, inv_c, (uint64_t)t));
-    const int any = __syncthreads_or(bad ? 1 : 0);  // (also the barrier behind the staging)
-    if (tid == 0) *flag = any ? 1u : 0u;
-  }
+  frames_tile_stage(A, t, s_y);
   if (nf == 0u) return;
 
   // d[f][tau - 1], tau = 1 .. PL: one fma chain per (f, tau), j ascending
@@ -217,17 +186,7 @@ __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCt
   }
 }
 
-__global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_finish_kernel(const PitchCtx A) {
-  const uint32_t g = blockIdx.x, tid = threadIdx.x;
-  bool bad = false;
-  for (uint32_t i = tid; i < A.tiles; i += PITCH_THREADS) bad |= A.flags[(size_t)g * A.tiles + i] != 0u;
-  const int refused = __syncthreads_or(bad ? 1 : 0);
-  if (tid == 0 && A.refused) A.refused[g] = refused ? 1u : 0u;
-  if (!refused) return;
-  float* rows = A.rows + 2u * A.segoff[g];
-  const uint64_t nv = 2ull * A.segF[g];
-  for (uint64_t i = tid; i < nv; i += PITCH_THREADS) rows[i] = __uint_as_float(0x7FC00000u);
-}
+__global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_finish_kernel(const PitchCtx A) { frames_finish(A, 2u); }
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -289,9 +248,7 @@ static inline uint32_t pitch_tile(uint32_t L, uint32_t H, uint32_t pl) {
 static inline int pitch_launch(PitchWs& ws, int device, const vsyn_pitch_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
                                uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
                                uint64_t* d_segoff, uint32_t* d_refused, hipStream_t s, const char** err) {
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  if (((uintptr_t)d_pcm & 3u) || ((uintptr_t)d_rows & 3u)) return fail(err, VSYN_ERR_INVALID, "PCM and row pointers must be 4-byte aligned");
-  if (plane > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "plane_stride must be below 2^32");
+  if (int rc = frames_check_call(S, d_pcm, d_rows, plane, err)) return rc;
   const uint32_t L = sp->frame_length, H = sp->hop_length;
   std::vector<uint8_t> tab(sizeof(PitchSeg) * (size_t)S);
   PitchSeg* seg = (PitchSeg*)tab.data();
@@ -302,41 +259,18 @@ static inline int pitch_launch(PitchWs& ws, int device, const vsyn_pitch_spec* s
     pl = std::max(pl, seg[g].p_max);
   }
   const uint32_t ft = pitch_tile(L, H, pl);
-  const uint64_t tiles = std::max<uint64_t>((f_max + ft - 1u) / ft, 1);
-  if (tiles > 0x7FFFFFFFull || f_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  HIPCHK(hipSetDevice(device));
-  if (!ws.lds_set) {
+  const auto raise_lds = [&]() -> int {
+    if (ws.lds_set) return VSYN_OK;
     HIPCHK(hipFuncSetAttribute((const void*)vsyn_pitch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PITCH_LDS_BUDGET));
     ws.lds_set = true;
-  }
-  HIPCHK(ws.segF.ensure(S));
-  HIPCHK(ws.segoff.ensure((size_t)S + 1));
-  HIPCHK(ws.flags.ensure((size_t)S * tiles));
-  if (int rc = ws.tab.upload(tab, s, err)) return rc;
+    return VSYN_OK;
+  };
   PitchCtx A;
+  if (int rc = frames_begin(ws, device, tab, ft, H, (sp->options & VSYN_PITCH_CENTER) != 0, S, d_pcm, plane, C, d_frames, si, f_max, d_rows, d_segoff,
+                            d_refused, s, err, raise_lds, A))
+    return rc;
   A.seg = (const PitchSeg*)ws.tab.dev.p;
-  A.pcm = d_pcm;
-  A.plane = plane;
-  A.C = C;
-  A.S = S;
-  A.frames = d_frames;
-  A.si = si;
   A.L = L;
-  A.H = H;
-  A.FT = ft;
-  A.center = (sp->options & VSYN_PITCH_CENTER) ? 1u : 0u;
-  A.tiles = (uint32_t)tiles;
   A.thr = sp->trough_threshold;
-  A.segF = ws.segF.p;
-  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
-  A.flags = ws.flags.p;
-  A.refused = d_refused;
-  A.rows = d_rows;
-  hipLaunchKernelGGL(vsyn_pitch_offsets_kernel, dim3(1), dim3(PITCH_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_pitch_kernel, dim3((uint32_t)tiles, S), dim3(PITCH_THREADS), pitch_lds_bytes(ft, L, H, pl), s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_pitch_finish_kernel, dim3(S), dim3(PITCH_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  return VSYN_OK;
+  return frames_launch(A, vsyn_pitch_offsets_kernel, vsyn_pitch_kernel, pitch_lds_bytes(ft, L, H, pl), vsyn_pitch_finish_kernel, s, err);
 }

@@ -5,17 +5,20 @@
 //   1. vsyn_spec_offsets_kernel  one workgroup: per segment its PCM frames (the caller's d_frames, or the last submit's SegInfo),
 //                                its STFT frame count, the exclusive row scan seg_off[S+1]; clears the per-segment dB maxima.
 //   2. vsyn_spec_stft_kernel<FT> one workgroup per (segment, tile of FT frames). LDS holds the twiddles cos/sin(2 pi m / n_fft)
-//                                (m < n_fft), the window, and the tile's span of the mono signal (the downmix is done while
-//                                loading it). A thread owns one bin k of a 256-bin chunk and accumulates the FT frames' real DFT
-//                                sums, walking the twiddle index by (j * k) mod n_fft; the chunk's |X|^power goes to LDS and the
+//                                (m < n_fft), the window, and the tile's span of the mono signal (frames_stage_direct, vsyn_frames.h).
+//                                A thread owns one bin k of a 256-bin chunk and accumulates the FT frames' real DFT sums
+//                                (frames_dft_bin); the chunk's |X|^power goes to LDS (frames_power_store) and the
 //                                mel bands that overlap the chunk take their share from it (sparse per-band weights). The last
 //                                chunk ends in the kind's output: M, log10, or 10 log10 (with a per-segment max by atomicMax on
 //                                order-preserving integer keys).
 //   3. vsyn_spec_finish_kernel   MEL_DB / MFCC only, after 2: the top_db clamp against the segment's max, and for MFCC the
 //                                orthonormal DCT-II (host-built matrix) of the clamped dB rows.
+// The host side here is the mel kinds' share of a launch: tile, table, kernel pick and finish. spec_launch itself, the one preamble
+// of every spectral kind, stands behind the last kind's header (vsyn_chroma.h).
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
 #include "vsyn_device.h"
+#include "vsyn_frames.h"
 #include "vsyn_host.h"
 
 struct SpecHeader {
@@ -45,15 +48,10 @@ struct SpecCtx {  // launch arguments
 };
 
 #define SPEC_THREADS 256
+static_assert(SPEC_THREADS == FRAMES_THREADS, "the shared framing helpers stride by the workgroup's size");
 #define SPEC_FIN_ROWS 16
 
 __device__ __forceinline__ const SpecHeader* spec_hdr(const uint8_t* t) { return (const SpecHeader*)t; }
-
-__host__ __device__ __forceinline__ uint64_t spec_num_frames(uint32_t n, uint32_t hop, bool center, uint64_t T) {
-  if (T == 0) return 0;
-  const uint64_t tp = T + (center ? 2ull * (n / 2u) : 0ull);
-  return tp < n ? 0ull : 1ull + (tp - n) / hop;
-}
 
 // max(x, floor) that keeps a NaN: fmaxf(NaN, floor) is floor, which would turn a frame that holds a NaN sample into a silent one
 __device__ __forceinline__ float spec_floor(float x, float floor) { return x < floor ? floor : x; }
@@ -71,14 +69,15 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_offsets_kernel(const S
   const SpecHeader* H = spec_hdr(A.tab);
   const uint32_t* rate = (const uint32_t*)(A.tab + H->off_rate);
   wg_exclusive_scan<SPEC_THREADS, 1>(A.S, A.segoff, [&](uint32_t g, uint64_t* v) {
-    const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
+    const uint64_t T = frames_len(A, g);
     v[0] = rate[g] == SPEC_SKIP ? 0ull : spec_num_frames(H->n, H->hop, (H->opts & VSYN_SPEC_CENTER) != 0, T);
     A.segF[g] = (uint32_t)v[0];
     A.segmax[g] = 0u;  // below every key
   });
 }
 
-// LDS image of the STFT kernel, in floats: twiddles [2n] | window [n] | span [(FT-1) hop + n] | |X|^power [FT][256] | M [FT][n_mels]
+// LDS image of the STFT kernel, in floats: FramesDirect's head (twiddles [2n] | window [n] | span [(FT-1) hop + n]) | |X|^power [FT][256] |
+// M [FT][n_mels]
 __host__ __device__ __forceinline__ uint64_t spec_span_len(uint32_t ft, uint32_t n, uint32_t hop) { return (uint64_t)(ft - 1u) * hop + n; }
 __host__ __device__ __forceinline__ uint64_t spec_lds_floats(uint32_t ft, uint32_t n, uint32_t hop, uint32_t n_mels) {
   return 3ull * n + spec_span_len(ft, n, hop) + (uint64_t)ft * SPEC_THREADS + (uint64_t)ft * n_mels;
@@ -92,65 +91,23 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_stft_kernel(const Spec
   const uint32_t F = A.segF[g];
   const uint32_t f0 = blockIdx.x * FT;
   if (f0 >= F) return;
-  const uint32_t n = H->n, hop = H->hop, nb = H->nbins, NM = H->n_mels, win = H->win, woff = H->woff;
+  const uint32_t nb = H->nbins, NM = H->n_mels;
   const uint32_t nf = min((uint32_t)FT, F - f0);
   const uint32_t ri = ((const uint32_t*)(A.tab + H->off_rate))[g];
   const SpecBand* band = (const SpecBand*)(A.tab + H->off_band) + (size_t)ri * NM;
   const float* wts = (const float*)(A.tab + H->off_w);
-  float2* s_tw = (float2*)lds;
-  float* s_win = lds + 2u * n;
-  float* s_span = s_win + n;
-  const uint32_t span = (uint32_t)spec_span_len(FT, n, hop);
-  float* s_S = s_span + span;
+  const FramesDirect D = frames_stage_direct(A, lds, (const float2*)(A.tab + H->off_tw), (const float*)(A.tab + H->off_win), H->n, H->hop,
+                                             (uint32_t)spec_span_len(FT, H->n, H->hop), H->win, H->woff, (H->opts & VSYN_SPEC_CENTER) != 0, g, f0);
+  float* s_S = D.rest;
   float* s_M = s_S + FT * SPEC_THREADS;
-  const float2* g_tw = (const float2*)(A.tab + H->off_tw);
-  const float* g_win = (const float*)(A.tab + H->off_win);
-  for (uint32_t i = tid; i < n; i += SPEC_THREADS) {
-    s_tw[i] = g_tw[i];
-    s_win[i] = g_win[i];
-  }
-  // the tile's span of the padded mono signal: padded index p = f0 * hop + i is PCM frame p - pad (zero outside [0, T));
-  // frames of the tile past nf read the zero-filled rest and are never stored
-  const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
-  const int64_t pad = (H->opts & VSYN_SPEC_CENTER) ? (int64_t)(n / 2u) : 0;
-  const int64_t p0 = (int64_t)f0 * hop - pad;
-  const uint32_t C = A.C;
-  const float invC = 1.0f / (float)C;
-  const float* x = A.pcm + (size_t)g * C * A.plane;
-  for (uint32_t i = tid; i < span; i += SPEC_THREADS) {
-    const int64_t t = p0 + (int64_t)i;
-    s_span[i] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, invC, (uint64_t)t) : 0.f;
-  }
   for (uint32_t i = tid; i < FT * NM; i += SPEC_THREADS) s_M[i] = 0.f;
   __syncthreads();
 
   for (uint32_t k0 = 0; k0 < nb; k0 += SPEC_THREADS) {
     const uint32_t k = k0 + tid;
-    float re[FT], im[FT];
-#pragma unroll
-    for (int f = 0; f < FT; ++f) re[f] = im[f] = 0.f;
-    if (k < nb) {
-      uint32_t idx = (uint32_t)(((uint64_t)woff * k) % n);
-      for (uint32_t j = woff; j < woff + win; ++j) {
-        const float2 tw = s_tw[idx];
-        const float w = s_win[j];
-        const float a = w * tw.x, b = w * tw.y;
-        const float* sp = s_span + j;
-#pragma unroll
-        for (int f = 0; f < FT; ++f) {
-          const float v = sp[f * hop];
-          re[f] = fmaf(v, a, re[f]);
-          im[f] = fmaf(v, b, im[f]);
-        }
-        idx += k;
-        if (idx >= n) idx -= n;
-      }
-    }
-#pragma unroll
-    for (int f = 0; f < FT; ++f) {
-      const float p = fmaf(re[f], re[f], im[f] * im[f]);
-      s_S[f * SPEC_THREADS + tid] = H->power == 1 ? sqrtf(p) : p;
-    }
+    float re[FT] = {}, im[FT] = {};
+    if (k < nb) frames_dft_bin<FT>(D, k, re, im);
+    frames_power_store<FT>(re, im, H->power, s_S);
     __syncthreads();
     const uint32_t kend = min(k0 + SPEC_THREADS, nb);
     for (uint32_t q = tid; q < nf * NM; q += SPEC_THREADS) {
@@ -183,7 +140,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_stft_kernel(const Spec
     }
   }
   if (kind >= VSYN_SPEC_MEL_DB) {
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = frames_wave_max(mx);
     if ((tid & 63u) == 0 && mx > -INFINITY) atomicMax(A.segmax + g, spec_key(mx));
   }
 }
@@ -227,9 +184,7 @@ static const uint32_t SPEC_LDS_BUDGET = 160u * 1024u;  // gfx950: 160 KiB of LDS
 
 struct SpectralWs {  // the stage's buffers: its own; the PCM is only read
   TableUpload tab;
-  bool lds_set = false;                // the STFT kernels' dynamic-LDS limit is raised on this handle's device
-  bool lin_lds_set = false;            // and that of the linear kinds' kernels (vsyn_spectral_lin.h)
-  bool chroma_lds_set = false;         // and that of the chroma kernels (vsyn_chroma.h)
+  bool lds_set = false;                // the dynamic-LDS limit of every kind's kernels is raised on this handle's device (spec_raise_lds)
   std::vector<double> chroma_key;      // what the kept chroma filterbanks were built from (n_fft, the chroma parameters, the distinct rates)
   std::vector<float> chroma_bank;      // [rate][n_chroma][NB]
   DevBuf<uint32_t> segF, segmax;
@@ -321,8 +276,10 @@ static inline uint32_t spec_tile(const vsyn_spectral_spec* sp) {  // frames per 
   return 0;
 }
 
-// SpecHeader, twiddles, window, per-rate bands and weights, DCT matrix, per-segment rate index. Call after spec_check.
-static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, std::vector<uint8_t>& out) {
+// SpecHeader, twiddles, window, per-rate bands and weights, DCT matrix, per-segment rate index. Call after spec_check. rates_out, where
+// given, takes the distinct rates in the order of the table's rate indices (first appearance).
+static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, std::vector<uint8_t>& out,
+                                    std::vector<uint32_t>* rates_out = nullptr) {
   const uint32_t n = sp->n_fft, NM = spec_is_lin(sp) || spec_is_chroma(sp) ? 0u : sp->n_mels, nb = n / 2u + 1u;  // a linear or chroma kind: no mel table
   const bool htk = (sp->options & VSYN_SPEC_HTK) != 0, norm = !(sp->options & VSYN_SPEC_NO_NORM);
   std::vector<uint32_t> distinct, seg_rate(S, SPEC_SKIP);
@@ -381,14 +338,8 @@ static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, co
   T.off_rate = al(T.off_dct + 4ull * T.n_mfcc * NM);
   out.assign(T.off_rate + 4ull * S + 16, 0);
   memcpy(out.data(), &T, sizeof(T));
-  float* tw = (float*)(out.data() + T.off_tw);
-  for (uint32_t m = 0; m < n; ++m) {
-    const double a = 2.0 * M_PI * (double)m / (double)n;
-    tw[2 * m] = (float)cos(a);
-    tw[2 * m + 1] = (float)sin(a);
-  }
-  float* wn = (float*)(out.data() + T.off_win);
-  for (uint32_t i = 0; i < sp->win_length; ++i) wn[T.woff + i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)sp->win_length));
+  twiddle_table(n, (float*)(out.data() + T.off_tw));
+  hann_centred(n, sp->win_length, (float*)(out.data() + T.off_win));
   if (!bands.empty()) memcpy(out.data() + T.off_band, bands.data(), sizeof(SpecBand) * bands.size());
   if (!w.empty()) memcpy(out.data() + T.off_w, w.data(), 4 * w.size());
   float* dct = (float*)(out.data() + T.off_dct);
@@ -396,65 +347,18 @@ static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, co
     for (uint32_t m = 0; m < NM; ++m)
       dct[(size_t)i * NM + m] = (float)(sqrt((i ? 2.0 : 1.0) / NM) * cos(M_PI * (double)i * (2.0 * m + 1.0) / (2.0 * NM)));
   if (S) memcpy(out.data() + T.off_rate, seg_rate.data(), 4ull * S);
+  if (rates_out) rates_out->swap(distinct);
 }
 
-static inline int spec_lin_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
-                                  uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
-                                  uint64_t* d_segoff, hipStream_t s, const char** err);  // vsyn_spectral_lin.h
-static inline int spec_chroma_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, const vsyn_spectral_chroma* ch, uint32_t S,
-                                     const uint32_t* rates, const float* d_pcm, uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si,
-                                     uint64_t f_max, float* d_rows, uint64_t* d_segoff, hipStream_t s, const char** err);  // vsyn_chroma.h
-
-// Offsets, STFT / mel, and (MEL_DB, MFCC) finishing kernels on stream s (a linear kind: spec_lin_launch; a chroma kind: spec_chroma_launch with ch, NULL for the defaults); frames from d_frames, else from si. f_max bounds every
-// segment's STFT frames, rows_bound the total rows. Caller holds the handle's lock and has run spec_check.
-static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
-                       uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
-                       uint64_t* d_segoff, hipStream_t s, const char** err, const vsyn_spectral_chroma* ch = nullptr) {
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  if (spec_is_lin(sp)) return spec_lin_launch(ws, device, sp, S, rates, d_pcm, plane, C, d_frames, si, f_max, d_rows, d_segoff, s, err);
-  if (spec_is_chroma(sp)) return spec_chroma_launch(ws, device, sp, ch, S, rates, d_pcm, plane, C, d_frames, si, f_max, d_rows, d_segoff, s, err);
-  const uint32_t ft = spec_tile(sp);
-  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", sp->n_fft, sp->hop_length);
-  std::vector<uint8_t> tab;
-  spec_build_table(sp, S, rates, tab);
-  HIPCHK(hipSetDevice(device));
-  if (!ws.lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_stft_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    ws.lds_set = true;
-  }
-  HIPCHK(ws.segF.ensure(S));
-  HIPCHK(ws.segmax.ensure(S));
-  HIPCHK(ws.segoff.ensure((size_t)S + 1));
-  if (sp->kind == VSYN_SPEC_MFCC) HIPCHK(ws.db.ensure(rows_bound * sp->n_mels + 1));
-  if (int rc = ws.tab.upload(tab, s, err)) return rc;
-  SpecCtx A;
-  A.tab = ws.tab.dev.p;
-  A.pcm = d_pcm;
-  A.plane = plane;
-  A.C = C;
-  A.S = S;
-  A.frames = d_frames;
-  A.si = si;
-  A.segF = ws.segF.p;
-  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
-  A.segmax = ws.segmax.p;
-  A.rows = d_rows;
-  A.db = sp->kind == VSYN_SPEC_MFCC ? ws.db.p : nullptr;
-  hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  if (f_max == 0 || S == 0) return VSYN_OK;
-  const uint64_t gx = (f_max + ft - 1) / ft;
-  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
+// The mel kinds' kernels behind the offsets kernel: STFT / mel on grid with ft frames per workgroup, and the (MEL_DB, MFCC) finish.
+static inline int spec_mel_run(const SpecCtx& A, const vsyn_spectral_spec* sp, uint32_t ft, dim3 grid, uint64_t f_max, hipStream_t s, const char** err) {
   const size_t lds = spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u;
-  const dim3 grid((uint32_t)gx, S);
   if (ft == 16) hipLaunchKernelGGL(vsyn_spec_stft_kernel<16>, grid, dim3(SPEC_THREADS), lds, s, A);
   else if (ft == 4) hipLaunchKernelGGL(vsyn_spec_stft_kernel<4>, grid, dim3(SPEC_THREADS), lds, s, A);
   else hipLaunchKernelGGL(vsyn_spec_stft_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
   HIPCHK(hipGetLastError());
   if (sp->kind >= VSYN_SPEC_MEL_DB) {
-    hipLaunchKernelGGL(vsyn_spec_finish_kernel, dim3((uint32_t)((f_max + SPEC_FIN_ROWS - 1) / SPEC_FIN_ROWS), S), dim3(SPEC_THREADS), 0, s, A);
+    hipLaunchKernelGGL(vsyn_spec_finish_kernel, dim3((uint32_t)((f_max + SPEC_FIN_ROWS - 1) / SPEC_FIN_ROWS), grid.y), dim3(SPEC_THREADS), 0, s, A);
     HIPCHK(hipGetLastError());
   }
   return VSYN_OK;

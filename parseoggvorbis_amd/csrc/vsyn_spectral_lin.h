@@ -12,8 +12,11 @@
 //                                    the n_fft / 2 + 1 entries of the untangling pass. The tile's transforms and one bin's
 //                                    untangling are the __device__ helpers spec_lin_fft_tile_run and spec_lin_untangle, which
 //                                    the chroma kernel (vsyn_chroma.h) calls as well.
-//   vsyn_spec_lin_direct_kernel<FT>  any other n_fft: the loop of vsyn_spec_stft_kernel (twiddle index walked by (j k) mod n_fft, one
-//                                    fma chain per component, j ascending over the window's support), its sums stored as bins.
+//                                    The per-pass twiddle runs and the passes are frames_stockham_twiddles and frames_stockham<false>
+//                                    (vsyn_frames.h), which the inverse (vsyn_istft.h) runs with INVERSE = true.
+//   vsyn_spec_lin_direct_kernel<FT>  any other n_fft: frames_stage_direct and frames_dft_bin (vsyn_frames.h: twiddle index walked by
+//                                    (j k) mod n_fft, one fma chain per component, j ascending over the window's support), its sums
+//                                    stored as bins.
 //   vsyn_spec_lin_clamp_kernel       LIN_DB with top_db > 0, after either: the clamp against the segment's maximum, elementwise.
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
@@ -27,7 +30,7 @@ __host__ __device__ __forceinline__ uint32_t spec_lin_fft_tile(uint32_t n) { ret
 // LDS image of the FFT kernel, in floats (M = n / 2): pass twiddles [M] float2 | untangling twiddles [M + 1] float2 | two buffers
 // of [ft][M] float2
 __host__ __device__ __forceinline__ uint64_t spec_lin_fft_lds_floats(uint32_t ft, uint32_t n) { return 2ull * n + 2ull + 2ull * ft * n; }
-// LDS image of the direct kernel, in floats: twiddles [2n] | window [n] | span [(ft-1) hop + n]
+// LDS image of the direct kernel, in floats: FramesDirect's head alone, twiddles [2n] | window [n] | span [(ft-1) hop + n]
 __host__ __device__ __forceinline__ uint64_t spec_lin_direct_lds_floats(uint32_t ft, uint32_t n, uint32_t hop) { return 3ull * n + spec_span_len(ft, n, hop); }
 
 // One bin of row r into the kind's layout; returns the dB value of LIN_DB where it is finite (for the segment's maximum), -inf
@@ -52,7 +55,7 @@ __device__ __forceinline__ float spec_lin_emit(const SpecHeader* H, float* rows,
 }
 
 __device__ __forceinline__ void spec_lin_seg_max(const SpecCtx& A, uint32_t g, float mx) {
-  for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  mx = frames_wave_max(mx);
   if ((threadIdx.x & 63u) == 0 && mx > -INFINITY) atomicMax(A.segmax + g, spec_key(mx));
 }
 
@@ -87,21 +90,18 @@ __device__ __forceinline__ SpecLinFft spec_lin_fft_tile_run(const SpecCtx& A, co
                                                             uint32_t f0, uint32_t nf) {
   const uint32_t tid = threadIdx.x;
   const uint32_t n = H->n, hop = H->hop, win = H->win, woff = H->woff;
-  const uint32_t M = n >> 1, half = M >> 1;
-  float2* s_st = (float2*)lds;  // pass Ns reads s_st[Ns - 1 + k] = exp(-2 pi i k / (2 Ns)) as (cos, sin), k < Ns
+  const uint32_t M = n >> 1;
+  float2* s_st = (float2*)lds;  // the per-pass twiddle runs
   float2* s_un = s_st + M;      // s_un[k] = (cos, sin)(2 pi k / n), k <= M
   float2* src = s_un + M + 1u;
   float2* dst = src + (size_t)ft * M;
   const float2* g_tw = (const float2*)(A.tab + H->off_tw);
   const float* g_win = (const float*)(A.tab + H->off_win);
-  for (uint32_t e = tid; e + 1u < M; e += SPEC_THREADS) {
-    const uint32_t lv = 31u - (uint32_t)__clz((int)(e + 1u)), Ns = 1u << lv, k = e + 1u - Ns;
-    s_st[e] = g_tw[k << (lgM - lv)];  // k * n / (2 Ns)
-  }
+  frames_stockham_twiddles(g_tw, s_st, M, lgM);
   for (uint32_t k = tid; k < M; k += SPEC_THREADS) s_un[k] = g_tw[k];
   // z[m] = v[2m] + i v[2m+1], v[j] = w[j] * y_pad[f hop + j] on the window's support and inside the signal, 0 elsewhere; padded
   // index p is PCM frame p - pad. Frames of the tile past nf are zeros and are never stored.
-  const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
+  const uint64_t T = frames_len(A, g);
   const int64_t pad = (H->opts & VSYN_SPEC_CENTER) ? (int64_t)(n / 2u) : 0;
   const uint32_t C = A.C;
   const float invC = 1.0f / (float)C;
@@ -120,27 +120,7 @@ __device__ __forceinline__ SpecLinFft spec_lin_fft_tile_run(const SpecCtx& A, co
     }
     src[q] = make_float2(v[0], v[1]);
   }
-  // Stockham radix-2 passes: butterfly j of a frame reads a = src[j], b = src[j + M/2] and writes a + w b, a - w b to
-  // dst[j0], dst[j0 + Ns], j0 = 2 (j - k) + k, k = j mod Ns, w = exp(-2 pi i k / (2 Ns))
-  const uint32_t tot = ft * half;
-  for (uint32_t Ns = 1; Ns < M; Ns <<= 1) {
-    __syncthreads();
-    for (uint32_t q = tid; q < tot; q += SPEC_THREADS) {
-      const uint32_t f = q >> (lgM - 1u), j = q & (half - 1u), k = j & (Ns - 1u);
-      const float2 w = s_st[Ns - 1u + k];
-      const float2* in = src + (size_t)f * M;
-      const float2 a = in[j], b = in[j + half];
-      const float tr = w.x * b.x + w.y * b.y;
-      const float ti = w.x * b.y - w.y * b.x;
-      float2* out = dst + (size_t)f * M + (((j - k) << 1) + k);
-      out[0] = make_float2(a.x + tr, a.y + ti);
-      out[Ns] = make_float2(a.x - tr, a.y - ti);
-    }
-    float2* sw = src;
-    src = dst;
-    dst = sw;
-  }
-  __syncthreads();
+  frames_stockham<false>(s_st, src, dst, ft, M, lgM);
   return SpecLinFft{src, s_un, dst};
 }
 
@@ -173,51 +153,16 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_lin_direct_kernel(cons
   const uint32_t F = A.segF[g];
   const uint32_t f0 = blockIdx.x * FT;
   if (f0 >= F) return;
-  const uint32_t n = H->n, hop = H->hop, nb = H->nbins, win = H->win, woff = H->woff;
+  const uint32_t nb = H->nbins;
   const uint32_t nf = min((uint32_t)FT, F - f0);
-  float2* s_tw = (float2*)lds;
-  float* s_win = lds + 2u * n;
-  float* s_span = s_win + n;
-  const uint32_t span = (uint32_t)spec_span_len(FT, n, hop);
-  const float2* g_tw = (const float2*)(A.tab + H->off_tw);
-  const float* g_win = (const float*)(A.tab + H->off_win);
-  for (uint32_t i = tid; i < n; i += SPEC_THREADS) {
-    s_tw[i] = g_tw[i];
-    s_win[i] = g_win[i];
-  }
-  // the tile's span of the padded mono signal, as in vsyn_spec_stft_kernel
-  const uint64_t T = min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
-  const int64_t pad = (H->opts & VSYN_SPEC_CENTER) ? (int64_t)(n / 2u) : 0;
-  const int64_t p0 = (int64_t)f0 * hop - pad;
-  const uint32_t C = A.C;
-  const float invC = 1.0f / (float)C;
-  const float* x = A.pcm + (size_t)g * C * A.plane;
-  for (uint32_t i = tid; i < span; i += SPEC_THREADS) {
-    const int64_t t = p0 + (int64_t)i;
-    s_span[i] = (t >= 0 && (uint64_t)t < T) ? pcm_downmix(x, A.plane, C, invC, (uint64_t)t) : 0.f;
-  }
+  const FramesDirect D = frames_stage_direct(A, lds, (const float2*)(A.tab + H->off_tw), (const float*)(A.tab + H->off_win), H->n, H->hop,
+                                             (uint32_t)spec_span_len(FT, H->n, H->hop), H->win, H->woff, (H->opts & VSYN_SPEC_CENTER) != 0, g, f0);
   __syncthreads();
   const uint64_t r0 = A.segoff[g] + f0;
   float mx = -INFINITY;
   for (uint32_t k = tid; k < nb; k += SPEC_THREADS) {
-    float re[FT], im[FT];
-#pragma unroll
-    for (int f = 0; f < FT; ++f) re[f] = im[f] = 0.f;
-    uint32_t idx = (uint32_t)(((uint64_t)woff * k) % n);
-    for (uint32_t j = woff; j < woff + win; ++j) {
-      const float2 tw = s_tw[idx];
-      const float w = s_win[j];
-      const float a = w * tw.x, b = w * tw.y;
-      const float* sp = s_span + j;
-#pragma unroll
-      for (int f = 0; f < FT; ++f) {
-        const float v = sp[f * hop];
-        re[f] = fmaf(v, a, re[f]);
-        im[f] = fmaf(v, b, im[f]);
-      }
-      idx += k;
-      if (idx >= n) idx -= n;
-    }
+    float re[FT] = {}, im[FT] = {};
+    frames_dft_bin<FT>(D, k, re, im);
 #pragma unroll
     for (int f = 0; f < FT; ++f)
       if ((uint32_t)f < nf) mx = fmaxf(mx, spec_lin_emit(H, A.rows, r0 + f, k, re[f], -im[f]));
@@ -250,48 +195,18 @@ static inline uint32_t spec_lin_tile(const vsyn_spectral_spec* sp) {
   return 0;
 }
 
-// spec_launch for the linear kinds (it dispatches here): offsets, FFT or direct kernel, and the LIN_DB clamp.
-static inline int spec_lin_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm,
-                                  uint64_t plane, uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows,
-                                  uint64_t* d_segoff, hipStream_t s, const char** err) {
-  const uint32_t ft = spec_lin_tile(sp), n = sp->n_fft;
-  if (!ft) return fail(err, VSYN_ERR_INVALID, "n_fft %u / hop_length %u do not fit the LDS", n, sp->hop_length);
-  std::vector<uint8_t> tab;
-  spec_build_table(sp, S, rates, tab);
-  HIPCHK(hipSetDevice(device));
-  if (!ws.lin_lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_lin_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_lin_direct_kernel<SPEC_LIN_DIRECT_FT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_spec_lin_direct_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    ws.lin_lds_set = true;
-  }
-  HIPCHK(ws.segF.ensure(S));
-  HIPCHK(ws.segmax.ensure(S));
-  HIPCHK(ws.segoff.ensure((size_t)S + 1));
-  if (int rc = ws.tab.upload(tab, s, err)) return rc;
-  SpecCtx A;
-  A.tab = ws.tab.dev.p;
-  A.pcm = d_pcm;
-  A.plane = plane;
-  A.C = C;
-  A.S = S;
-  A.frames = d_frames;
-  A.si = si;
-  A.segF = ws.segF.p;
-  A.segoff = d_segoff ? d_segoff : ws.segoff.p;
-  A.segmax = ws.segmax.p;
-  A.rows = d_rows;
-  A.db = nullptr;
-  hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  if (f_max == 0 || S == 0) return VSYN_OK;
-  const uint64_t gx = (f_max + ft - 1) / ft;
-  if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  const dim3 grid((uint32_t)gx, S);
+// log2 (n_fft / 2) of a power-of-two n_fft: the FFT kernels' lgM
+static inline uint32_t spec_lin_lgm(uint32_t n) {
+  uint32_t lgM = 0;
+  while ((2u << lgM) < n) ++lgM;
+  return lgM;
+}
+
+// The linear kinds' kernels behind the offsets kernel: FFT or direct on grid with ft frames per workgroup, and the LIN_DB clamp.
+static inline int spec_lin_run(const SpecCtx& A, const vsyn_spectral_spec* sp, uint32_t ft, dim3 grid, uint64_t f_max, hipStream_t s, const char** err) {
+  const uint32_t n = sp->n_fft;
   if (spec_lin_pow2(n)) {
-    uint32_t lgM = 0;
-    while ((2u << lgM) < n) ++lgM;
-    hipLaunchKernelGGL(vsyn_spec_lin_fft_kernel, grid, dim3(SPEC_THREADS), spec_lin_fft_lds_floats(ft, n) * 4u, s, A, ft, lgM);
+    hipLaunchKernelGGL(vsyn_spec_lin_fft_kernel, grid, dim3(SPEC_THREADS), spec_lin_fft_lds_floats(ft, n) * 4u, s, A, ft, spec_lin_lgm(n));
   } else {
     const size_t lds = spec_lin_direct_lds_floats(ft, n, sp->hop_length) * 4u;
     if (ft == SPEC_LIN_DIRECT_FT) hipLaunchKernelGGL(vsyn_spec_lin_direct_kernel<SPEC_LIN_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
@@ -300,7 +215,7 @@ static inline int spec_lin_launch(SpectralWs& ws, int device, const vsyn_spectra
   HIPCHK(hipGetLastError());
   if (sp->kind == VSYN_SPEC_LIN_DB && sp->top_db > 0.0) {
     const uint64_t cx = std::min<uint64_t>((f_max * (n / 2u + 1u) + SPEC_THREADS - 1) / SPEC_THREADS, 4096);
-    hipLaunchKernelGGL(vsyn_spec_lin_clamp_kernel, dim3((uint32_t)cx, S), dim3(SPEC_THREADS), 0, s, A);
+    hipLaunchKernelGGL(vsyn_spec_lin_clamp_kernel, dim3((uint32_t)cx, grid.y), dim3(SPEC_THREADS), 0, s, A);
     HIPCHK(hipGetLastError());
   }
   return VSYN_OK;

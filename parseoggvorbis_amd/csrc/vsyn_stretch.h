@@ -9,6 +9,7 @@
 // and, with VSYN_STRETCH_FIX_LENGTH, vsyn_stretch_deliver_kernel: each segment's first T samples, or all of them and zeros up to T.
 // Both sets of rows pass through memory.
 #pragma once
+#include "vsyn_chroma.h"  // spec_launch
 #include "vsyn_istft.h"
 #include "vsyn_pv.h"
 #include "vsyn_resample.h"
