@@ -91,3 +91,45 @@ def resample(x, r_in, r_out, h=None):
         v = np.where(ok, xx[ch][np.clip(idx, 0, max(T - 1, 0))] if T else 0.0, 0.0)
         out[ch] = (w * v).sum(axis=1)
     return out[0] if x.ndim == 1 else out
+
+
+def resample_at(x, r_in, r_out, j, P=None, block=1 << 22):
+    """resample(x, r_in, r_out)[..., j] for a 1-D array of output indices j, by the same arithmetic (the same products, summed over
+    the K axis in the same order), a block of rows at a time: for inputs and filters too long for the (T_out, K) arrays. P: the
+    pair's polyphase(up, down), when the caller keeps it."""
+    x = np.asarray(x)
+    j = np.asarray(j, np.int64)
+    up, down = ratio(r_in, r_out)
+    if up == down:
+        return x[..., j].astype(np.float64)
+    xx = np.atleast_2d(x)
+    T = xx.shape[-1]
+    assert j.ndim == 1 and (not j.size or (j.min() >= 0 and j.max() < num_frames(r_in, r_out, T)))
+    P = polyphase(up, down) if P is None else P
+    K = P.shape[1]
+    H = 10 * max(up, down)
+    t = np.arange(K)[None, :]
+    rows = max(1, block // K)
+    out = np.zeros((xx.shape[0], j.size))
+    for a in range(0, j.size, rows):
+        c = j[a:a + rows] * down + H
+        phi, i0_ = c % up, c // up
+        idx = i0_[:, None] - t
+        ok = (idx >= 0) & (idx < T)
+        idx = np.clip(idx, 0, max(T - 1, 0))
+        w = P[phi]
+        for ch in range(xx.shape[0]):
+            v = np.where(ok, xx[ch][idx].astype(np.float64) if T else 0.0, 0.0)
+            out[ch, a:a + rows] = (w * v).sum(axis=1)
+    return out[0] if x.ndim == 1 else out
+
+
+def tap_index(r_in, r_out, j, p):
+    """The index n = phi_j + (i0_j - p) up of the tap h[n] that output j applies to input sample p (step 3: y[j] = sum_t h[phi + t up]
+    x[i0 - t], so t = i0 - p), or -1 where there is none: n outside [0, N). j and p broadcast; int64. Not for up == down."""
+    up, down = ratio(r_in, r_out)
+    M = max(up, down)
+    H, N = 10 * M, 20 * M + 1
+    c = np.asarray(j, np.int64) * down + H
+    n = c % up + (c // up - np.asarray(p, np.int64)) * up
+    return np.where((n >= 0) & (n < N), n, -1)
