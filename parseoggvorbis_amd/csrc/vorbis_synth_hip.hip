@@ -1032,10 +1032,9 @@ int vsyn_pcm_interleave_device(vsyn_handle* h, int format, const float* d_pcm, u
   const dim3 grid((uint32_t)((cap + 1023) / 1024), h->last_S);
   const SegInfo* si = h->ws_seg[h->last_wb].p;
   if (format == VSYN_PCM_S16)
-    vsyn_pcm_interleave_kernel<VSYN_PCM_S16><<<grid, 256, 0, s>>>(h->d_const, si, h->last_S, d_pcm, plane_stride, d_out, out_stride_frames, d_frames);
+    VSYN_LAUNCH(vsyn_pcm_interleave_kernel<VSYN_PCM_S16>, grid, dim3(256), 0, s, h->d_const, si, h->last_S, d_pcm, plane_stride, d_out, out_stride_frames, d_frames);
   else
-    vsyn_pcm_interleave_kernel<VSYN_PCM_F32><<<grid, 256, 0, s>>>(h->d_const, si, h->last_S, d_pcm, plane_stride, d_out, out_stride_frames, d_frames);
-  HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_pcm_interleave_kernel<VSYN_PCM_F32>, grid, dim3(256), 0, s, h->d_const, si, h->last_S, d_pcm, plane_stride, d_out, out_stride_frames, d_frames);
   return VSYN_OK;
 }
 
@@ -1056,12 +1055,11 @@ int vsyn_pcm_fetch_host(vsyn_handle* h, int format, void* out, uint64_t out_stri
   const dim3 grid((uint32_t)((cap + 1023) / 1024), h->last_S);
   const SegInfo* si = h->ws_seg[h->last_wb].p;
   if (format == VSYN_PCM_S16)
-    vsyn_pcm_interleave_kernel<VSYN_PCM_S16><<<grid, 256, 0, s>>>(h->d_const, si, h->last_S, h->st_pcm.p, h->last_host_plane, h->st_conv.p, out_stride_frames,
-                                                                 h->st_frames.p);
+    VSYN_LAUNCH(vsyn_pcm_interleave_kernel<VSYN_PCM_S16>, grid, dim3(256), 0, s, h->d_const, si, h->last_S, h->st_pcm.p, h->last_host_plane, h->st_conv.p,
+                out_stride_frames, h->st_frames.p);
   else
-    vsyn_pcm_interleave_kernel<VSYN_PCM_F32><<<grid, 256, 0, s>>>(h->d_const, si, h->last_S, h->st_pcm.p, h->last_host_plane, h->st_conv.p, out_stride_frames,
-                                                                 h->st_frames.p);
-  HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_pcm_interleave_kernel<VSYN_PCM_F32>, grid, dim3(256), 0, s, h->d_const, si, h->last_S, h->st_pcm.p, h->last_host_plane, h->st_conv.p,
+                out_stride_frames, h->st_frames.p);
   HIPCHK(hipMemcpyAsync(out, h->st_conv.p, bytes, hipMemcpyDeviceToHost, s));
   if (frames_out) HIPCHK(hipMemcpyAsync(frames_out, h->st_frames.p, sizeof(uint32_t) * h->last_S, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -1076,9 +1074,8 @@ int vsyn_pcm_abs_sum_host(vsyn_handle* h, double* out, const char** err) {
   HIPCHK(hipSetDevice(h->device));
   const uint32_t units = h->last_S * h->H.channels;
   HIPCHK(h->st_sum.ensure(units));
-  vsyn_pcm_abs_sum_kernel<<<units, 256, 0, h->host_stream>>>(h->d_const, h->ws_seg[h->last_wb].p, h->last_S, h->st_pcm.p, h->last_host_plane,
-                                                              h->st_sum.p);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_pcm_abs_sum_kernel, dim3(units), dim3(256), 0, h->host_stream, h->d_const, h->ws_seg[h->last_wb].p, h->last_S, h->st_pcm.p,
+              h->last_host_plane, h->st_sum.p);
   HIPCHK(hipMemcpyAsync(out, h->st_sum.p, sizeof(double) * units, hipMemcpyDeviceToHost, h->host_stream));
   HIPCHK(hipStreamSynchronize(h->host_stream));
   return VSYN_OK;
@@ -1306,8 +1303,7 @@ int vsyn_spectral_post_device(vsyn_handle* h, const vsyn_spectral_post* post, ui
   if (rc) return rc;
   rc = post_check_rows(post, S, seg_rows, err);
   if (rc) return rc;
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   if (total == 0) return VSYN_OK;
   if (!d_in || !d_out) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
   if (d_in == d_out && post->order) return fail(err, VSYN_ERR_INVALID, "d_out may be d_in only when order = 0");
@@ -1330,8 +1326,7 @@ int vsyn_spectral_pcen_device(vsyn_handle* h, const vsyn_spectral_pcen* pcen, ui
                               const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   if (int rc = pcen_check_call(pcen, dim, S, seg_rows, sample_rates, hop_length, err)) return rc;
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   if (total == 0) return VSYN_OK;
   if (!d_in || !d_out) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
   std::lock_guard<std::mutex> lk(h->mu);
@@ -1342,8 +1337,7 @@ int vsyn_spectral_hpss_device(vsyn_handle* h, const vsyn_spectral_hpss* hpss, ui
                               float* d_out, void* hip_stream, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   if (int rc = hpss_check_call(hpss, dim, S, seg_rows, err)) return rc;
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   if (total == 0) return VSYN_OK;
   if (!d_in || !d_out) return fail(err, VSYN_ERR_INVALID, "NULL row pointer");
   std::lock_guard<std::mutex> lk(h->mu);
@@ -1436,8 +1430,7 @@ int vsyn_onset_strength_device(vsyn_handle* h, const vsyn_onset_spec* onset, uin
                                const float* d_rows, float* d_env, void* hip_stream, const char** err) {
   if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
   if (int rc = onset_check_call(onset, dim, S, seg_rows, err)) return rc;
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   if (total == 0) return VSYN_OK;
   if (!d_rows || !d_env) return fail(err, VSYN_ERR_INVALID, "NULL row or envelope pointer");
   std::lock_guard<std::mutex> lk(h->mu);
@@ -1450,8 +1443,7 @@ int vsyn_onset_peaks_device(vsyn_handle* h, const vsyn_onset_peaks* peaks, uint3
   if (int rc = peaks_check_call(peaks, S, seg_rows, sample_rates, err)) return rc;
   if (S == 0) return VSYN_OK;
   if (!d_counts) return fail(err, VSYN_ERR_INVALID, "d_counts is NULL");
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   if (total && (!d_env || !d_onsets)) return fail(err, VSYN_ERR_INVALID, "NULL envelope or onset pointer");
   std::lock_guard<std::mutex> lk(h->mu);
   return peaks_launch(h->rh, h->device, peaks, S, seg_rows, sample_rates, d_env, d_onsets, d_counts, d_refused, (hipStream_t)hip_stream, err);
@@ -1463,8 +1455,7 @@ int vsyn_tempogram_device(vsyn_handle* h, const vsyn_tempogram_spec* spec, uint3
   if (int rc = tg_check_call(spec, S, seg_rows, sample_rates, err)) return rc;
   if (S == 0) return VSYN_OK;
   if (!d_rows && !d_mean) return fail(err, VSYN_ERR_INVALID, "tempogram: neither rows nor mean asked for");
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   if (total && !d_env) return fail(err, VSYN_ERR_INVALID, "NULL envelope pointer");
   std::lock_guard<std::mutex> lk(h->mu);
   return tg_launch(h->rh, h->device, spec, S, seg_rows, sample_rates, d_env, d_rows, d_mean, (hipStream_t)hip_stream, err);
@@ -1485,8 +1476,7 @@ int vsyn_beat_track_device(vsyn_handle* h, const vsyn_beat_spec* beat, uint32_t 
   if (int rc = beat_check_call(beat, S, seg_rows, periods, err)) return rc;
   if (S == 0) return VSYN_OK;
   if (!d_counts) return fail(err, VSYN_ERR_INVALID, "d_counts is NULL");
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   if (total && (!d_env || !d_beats)) return fail(err, VSYN_ERR_INVALID, "NULL envelope or beat pointer");
   std::lock_guard<std::mutex> lk(h->mu);
   return beat_launch(h->bt, h->device, beat, S, seg_rows, periods, d_env, d_beats, d_counts, d_refused, d_localscore, d_cumscore, d_backlink,
@@ -1749,8 +1739,7 @@ static int pcm_copy_out(vsyn_handle* h, const PcmView& v, uint32_t S, int format
   } else {
     HIPCHK(s16.ensure(n + 1));
     const dim3 grid((uint32_t)((v.plane + 255) / 256), S);
-    hipLaunchKernelGGL(vsyn_rs_s16_kernel, grid, dim3(256), 0, hs, v.pcm, v.plane, v.C, v.d_frames, s16.p, v.plane);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_rs_s16_kernel, grid, dim3(256), 0, hs, v.pcm, v.plane, v.C, v.d_frames, s16.p, v.plane);
     HIPCHK(hipMemcpyAsync(out, s16.p, sizeof(int16_t) * n, hipMemcpyDeviceToHost, hs));
   }
   HIPCHK(hipStreamSynchronize(hs));

@@ -2,8 +2,8 @@
 // "rhythm", D; model: tests/beat_model.py.
 //
 // Four kernels, one workgroup per segment wherever a step is sequential; the batch is the parallelism there:
-//   vsyn_beat_norm_kernel   one workgroup per segment: the two sums of D.1 in their documented order (256 lane-strided partials, xor
-//                           rounds in each wave, the four waves' sums in ascending order), whether a value is not finite, whether
+//   vsyn_beat_norm_kernel   one workgroup per segment: the two sums of D.1 in their documented order (256 lane-strided partials, then
+//                           wave_sum and the waves ascending: DESIGN.md 6t), whether a value is not finite, whether
 //                           one is not zero. Leaves sd + FLT_MIN and the segment's flags; a segment without a score (refused, F < 2,
 //                           all zero) gets its count and refusal word here and is skipped by the kernels behind.
 //   vsyn_beat_score_kernel  grid (tile of 256 frames, segment), a thread per frame: the window (2P + 1 doubles) and the tile's u with
@@ -28,6 +28,7 @@
 // writes stream state, the overlap carry or any synthesis buffer.
 #pragma once
 #include "vsyn_rhythm.h"
+#include "vsyn_wave.h"
 
 #define BEAT_THREADS 256
 #define BEAT_WAVES (BEAT_THREADS / 64)
@@ -76,38 +77,6 @@ __device__ __forceinline__ uint64_t beat_key(double v) {
 __device__ __forceinline__ double beat_unkey(uint64_t k) {
   return __longlong_as_double((long long)((k >> 63) ? k & 0x7FFFFFFFFFFFFFFFull : ~k));
 }
-__device__ __forceinline__ uint64_t beat_shfl_xor64(uint64_t v, int o) {
-  return ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o);
-}
-
-// Block reductions of integers over nw waves through scratch[nw] (order-independent); every thread gets the result. Two barriers.
-__device__ __forceinline__ uint32_t beat_block_sum(uint32_t v, uint32_t* scratch, uint32_t nw) {
-  for (int o = 32; o >= 1; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  __syncthreads();  // (scratch is free)
-  if ((threadIdx.x & 63u) == 0u) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t r = 0u;
-  for (uint32_t w = 0; w < nw; ++w) r += scratch[w];
-  return r;
-}
-__device__ __forceinline__ uint32_t beat_block_min(uint32_t v, uint32_t* scratch, uint32_t nw) {
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-  __syncthreads();
-  if ((threadIdx.x & 63u) == 0u) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t r = 0xFFFFFFFFu;
-  for (uint32_t w = 0; w < nw; ++w) r = min(r, scratch[w]);
-  return r;
-}
-__device__ __forceinline__ uint32_t beat_block_max(uint32_t v, uint32_t* scratch, uint32_t nw) {
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  __syncthreads();
-  if ((threadIdx.x & 63u) == 0u) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint32_t r = 0u;
-  for (uint32_t w = 0; w < nw; ++w) r = max(r, scratch[w]);
-  return r;
-}
 
 // ------------------------------------------------------------------------------------------------
 // D.1: the sums, the flags
@@ -135,11 +104,9 @@ __global__ void __launch_bounds__(BEAT_THREADS) vsyn_beat_norm_kernel(const Beat
     nz |= v != 0.f;
     part += (double)v;
   }
-  for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o);
-  if ((tid & 63u) == 0u) s_part[tid >> 6] = part;
+  wg_put(part, s_part, WaveSum());  // (the barrier is the flags' __syncthreads_or: the two halves of wg_reduce_all apart)
   const int any_bad = __syncthreads_or(bad ? 1 : 0);
-  double sum = 0.0;
-  for (uint32_t w = 0; w < BEAT_WAVES; ++w) sum += s_part[w];
+  double sum = wg_get<BEAT_WAVES>(s_part, WaveSum(), 0.0);
   const double m = sum / (double)F;
   const int any_nz = __syncthreads_or(nz ? 1 : 0);  // (and s_part is free)
   part = 0.0;
@@ -148,12 +115,8 @@ __global__ void __launch_bounds__(BEAT_THREADS) vsyn_beat_norm_kernel(const Beat
     const double q = d * d;  // (rounded before it is added: the build contracts nothing)
     part += q;
   }
-  for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o);
-  if ((tid & 63u) == 0u) s_part[tid >> 6] = part;
-  __syncthreads();
+  sum = wg_reduce_t0<BEAT_WAVES>(part, s_part, WaveSum(), 0.0);
   if (tid == 0u) {
-    sum = 0.0;
-    for (uint32_t w = 0; w < BEAT_WAVES; ++w) sum += s_part[w];
     const bool scored = !any_bad && any_nz && F >= 2u;
     const double sd = scored ? sqrt(sum / (double)(F - 1u)) : 0.0;
     A.stat[g] = BeatStat{sd + (double)RHY_FLT_MIN, (any_bad ? BEAT_BAD : 0u) | (scored ? BEAT_SCORED : 0u), 0u};
@@ -195,16 +158,8 @@ __global__ void __launch_bounds__(BEAT_THREADS) vsyn_beat_score_kernel(const Bea
     A.ls[sg.off + i] = acc;
     key = beat_key(acc);
   }
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t other = beat_shfl_xor64(key, o);
-    key = other > key ? other : key;
-  }
-  if ((tid & 63u) == 0u) s_r[tid >> 6] = key;
-  __syncthreads();
-  if (tid == 0u) {
-    for (uint32_t k = 1; k < BEAT_WAVES; ++k) key = s_r[k] > key ? s_r[k] : key;
-    A.tmax[sg.mx_off + blockIdx.x] = key;
-  }
+  key = wg_reduce_t0<BEAT_WAVES>(key, s_r, WaveMax(), 0ull);
+  if (tid == 0u) A.tmax[sg.mx_off + blockIdx.x] = key;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -239,20 +194,15 @@ __global__ void __launch_bounds__(BEAT_DP_THREADS) vsyn_beat_dp_kernel(const Bea
     const uint64_t k = A.tmax[sg.mx_off + t];
     key = k > key ? k : key;
   }
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t other = beat_shfl_xor64(key, o);
-    key = other > key ? other : key;
-  }
-  if (lane == 0u) s_r[wave] = key;
+  wg_put(key, s_r, WaveMax());  // (one barrier: s_r is not written again)
   __syncthreads();
-  for (uint32_t k = 0; k < BEAT_DP_WAVES; ++k) key = s_r[k] > key ? s_r[k] : key;
+  key = wg_get<BEAT_DP_WAVES>(s_r, WaveMax(), 0ull);
   const double thr = 0.01 * beat_unkey(key);
   // i0: the first frame that reaches thr (the maximum does)
   uint32_t first = 0xFFFFFFFFu;
   for (uint32_t i = tid; i < F && first == 0xFFFFFFFFu; i += BEAT_DP_THREADS)
     if (ls[i] >= thr) first = i;
-  const uint32_t i0 = beat_block_min(first, s_r32, BEAT_DP_WAVES);
-  __syncthreads();  // (s_tx is written)
+  const uint32_t i0 = wg_reduce_all<BEAT_DP_WAVES>(first, s_r32, WaveMin(), 0xFFFFFFFFu);  // (behind its barriers s_tx is written too)
   const double ninf = -__longlong_as_double(0x7FF0000000000000ll);
   for (uint32_t base = 0; base < F; base += lo) {
     const uint32_t nf = min(lo, F - base);
@@ -268,9 +218,9 @@ __global__ void __launch_bounds__(BEAT_DP_THREADS) vsyn_beat_dp_kernel(const Bea
           best_d = d;
         }
       }
-      for (int o = 32; o >= 1; o >>= 1) {
-        const double os = __shfl_xor(best_s, o);
-        const uint32_t od = (uint32_t)__shfl_xor((int)best_d, o);
+      for (int o = 32; o >= 1; o >>= 1) {  // (an arg-max on the pair (s, d): the butterfly of wave_reduce with a rule of its own)
+        const double os = wave_xor(best_s, o);
+        const uint32_t od = wave_xor(best_d, o);
         if (os > best_s || (os == best_s && od < best_d)) {
           best_s = os;
           best_d = od;
@@ -341,7 +291,7 @@ __global__ void __launch_bounds__(BEAT_THREADS) vsyn_beat_tail_kernel(const Beat
   double* sq = A.sq + sg.off;
   uint32_t n = 0u;
   for (uint32_t i = tid; i < F; i += BEAT_THREADS) n += beat_is_max(cum, F, i) ? 1u : 0u;
-  const uint32_t M = beat_block_sum(n, s_r32, BEAT_WAVES);
+  const uint32_t M = wg_reduce_all<BEAT_WAVES>(n, s_r32, WaveSum(), 0u);
   if (M == 0u) {  // (workgroup-uniform) no local maximum: no beats
     if (tid == 0u) A.counts[g] = 0u;
     return;
@@ -352,7 +302,7 @@ __global__ void __launch_bounds__(BEAT_THREADS) vsyn_beat_tail_kernel(const Beat
   uint32_t last = 0u;  // (frame + 1 of the last local maximum that reaches 0.5 med)
   for (uint32_t i = tid; i < F; i += BEAT_THREADS)
     if (beat_is_max(cum, F, i) && cum[i] >= need) last = i + 1u;
-  last = beat_block_max(last, s_r32, BEAT_WAVES);
+  last = wg_reduce_all<BEAT_WAVES>(last, s_r32, WaveMax(), 0u);
   const uint32_t tail = last ? last - 1u : F - 1u;
   if (tid == 0u) {  // the walk: back[b] < b, at most ceil(F / lo) frames
     uint32_t B = 0u;
@@ -385,8 +335,8 @@ __global__ void __launch_bounds__(BEAT_THREADS) vsyn_beat_tail_kernel(const Beat
       n0 = min(n0, i);
       n1 = i + 1u;
     }
-  n0 = beat_block_min(n0, s_r32, BEAT_WAVES);
-  n1 = beat_block_max(n1, s_r32, BEAT_WAVES);
+  n0 = wg_reduce_all<BEAT_WAVES>(n0, s_r32, WaveMin(), 0xFFFFFFFFu);
+  n1 = wg_reduce_all<BEAT_WAVES>(n1, s_r32, WaveMax(), 0u);
   if (n1 == 0u) {  // (workgroup-uniform) no frame above t: none is kept
     if (tid == 0u) A.counts[g] = 0u;
     return;
@@ -397,8 +347,8 @@ __global__ void __launch_bounds__(BEAT_THREADS) vsyn_beat_tail_kernel(const Beat
     below += b < n0 ? 1u : 0u;
     kept += b >= n0 && b < n1 ? 1u : 0u;
   }
-  below = beat_block_sum(below, s_r32, BEAT_WAVES);
-  kept = beat_block_sum(kept, s_r32, BEAT_WAVES);
+  below = wg_reduce_all<BEAT_WAVES>(below, s_r32, WaveSum(), 0u);
+  kept = wg_reduce_all<BEAT_WAVES>(kept, s_r32, WaveSum(), 0u);
   uint32_t* out = A.beats + sg.off;
   for (uint32_t j = tid; j < kept; j += BEAT_THREADS) out[j] = chain[B - 1u - (below + j)];  // (ascending: the kept ones are consecutive)
   if (tid == 0u) A.counts[g] = kept;
@@ -470,13 +420,7 @@ static inline int beat_launch(BeatWs& ws, int device, const vsyn_beat_spec* p, u
       sg.lo = std::max(h, 1u);
       sg.ring = beat_ring(sg.P, sg.lo);
       sg.tiles = (sg.F + BEAT_THREADS - 1u) / BEAT_THREADS;
-      size_t k = 0;
-      while (k < tabs.size() && tabs[k].first != sg.P) ++k;
-      if (k == tabs.size()) {
-        tabs.push_back(std::make_pair(sg.P, tab_doubles));
-        tab_doubles += 2u * (2u * sg.P + 1u);
-      }
-      sg.tab_off = tabs[k].second;
+      sg.tab_off = table_slot(tabs, sg.P, &tab_doubles, 2u * (2u * sg.P + 1u));
       mx_off += sg.tiles;
       tiles_max = std::max(tiles_max, sg.tiles);
       lds_score = std::max(lds_score, beat_score_lds(sg.P));
@@ -503,12 +447,11 @@ static inline int beat_launch(BeatWs& ws, int device, const vsyn_beat_spec* p, u
     }
   }
   HIPCHK(hipSetDevice(device));
-  if (!ws.lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_beat_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)beat_score_lds(BEAT_MAX_P)));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_beat_dp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)beat_dp_lds(BEAT_MAX_P, beat_ring(BEAT_MAX_P, BEAT_MAX_P / 2u))));
-    ws.lds_set = true;
-  }
+  if (int rc = raise_lds_once(ws.lds_set,
+                              {{(const void*)vsyn_beat_score_kernel, beat_score_lds(BEAT_MAX_P)},
+                               {(const void*)vsyn_beat_dp_kernel, beat_dp_lds(BEAT_MAX_P, beat_ring(BEAT_MAX_P, BEAT_MAX_P / 2u))}},
+                              err))
+    return rc;
   HIPCHK(ws.stat.ensure(S));
   HIPCHK(ws.tmax.ensure(mx_off + 1u));
   HIPCHK(ws.chain.ensure(off + 1u));
@@ -532,15 +475,11 @@ static inline int beat_launch(BeatWs& ws, int device, const vsyn_beat_spec* p, u
   A.counts = d_counts;
   A.refused = d_refused;
   A.trim = (p->options & VSYN_BEAT_TRIM) ? 1u : 0u;
-  hipLaunchKernelGGL(vsyn_beat_norm_kernel, dim3(S), dim3(BEAT_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_beat_norm_kernel, dim3(S), dim3(BEAT_THREADS), 0, s, A);
   if (tiles_max) {
-    hipLaunchKernelGGL(vsyn_beat_score_kernel, dim3(tiles_max, S), dim3(BEAT_THREADS), lds_score, s, A);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(vsyn_beat_dp_kernel, dim3(S), dim3(BEAT_DP_THREADS), lds_dp, s, A);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(vsyn_beat_tail_kernel, dim3(S), dim3(BEAT_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_beat_score_kernel, dim3(tiles_max, S), dim3(BEAT_THREADS), lds_score, s, A);
+    VSYN_LAUNCH(vsyn_beat_dp_kernel, dim3(S), dim3(BEAT_DP_THREADS), lds_dp, s, A);
+    VSYN_LAUNCH(vsyn_beat_tail_kernel, dim3(S), dim3(BEAT_THREADS), 0, s, A);
   }
   return VSYN_OK;
 }

@@ -11,7 +11,7 @@
 //                                  of 256 bins, S of a chunk in LDS, as the mel kernel (vsyn_spectral.h) runs them.
 // Both project with chroma_dot, one wave per (frame, c): lane l runs one fma chain over the bins l, l + 64, ... (ascending) of the
 // whole row (FFT kernel) or of the chunk (direct kernel, the chunks' sums added to R[f][c] in ascending order), W read from global
-// memory along k, S from LDS, then an xor-shuffle tree over lane distances 32 ... 1. chroma_finish then takes each frame's norm, the
+// memory along k, S from LDS, then wave_sum (the butterfly of DESIGN.md 6t). chroma_finish then takes each frame's norm, the
 // non-finite rule and, for tonnetz, the 6 x n_chroma product, one wave per frame. No atomics; S and R never leave the workgroup.
 // The last of the spectral kinds' headers: behind the chroma kinds' share of the host side stands spec_launch, the one preamble of
 // every spectral kind, which sees all three.
@@ -37,13 +37,7 @@ __host__ __device__ __forceinline__ uint64_t chroma_direct_lds_floats(uint32_t f
   return 3ull * n + spec_span_len(ft, n, hop) + (uint64_t)ft * SPEC_THREADS + (uint64_t)ft * CHROMA_MAX;
 }
 
-// the xor-shuffle tree over lane distances 32 ... 1: every lane returns the wave's sum
-__device__ __forceinline__ float chroma_tree_sum(float v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// sum_k w[k] s[k] over k < cnt by one wave: lane l's fma chain over k = l, l + 64, ... ascending, then the tree; every lane returns the sum.
+// sum_k w[k] s[k] over k < cnt by one wave: lane l's fma chain over k = l, l + 64, ... ascending, then wave_sum; every lane returns the sum.
 __device__ __forceinline__ float chroma_dot(const float* __restrict__ w, const float* s, uint32_t cnt, uint32_t lane) {
   float acc = 0.f;
   for (uint32_t k0 = lane; k0 < cnt; k0 += 64u * 6u) {  // six loads of each operand in flight, then their fmas in the chain's order
@@ -58,7 +52,7 @@ __device__ __forceinline__ float chroma_dot(const float* __restrict__ w, const f
     for (uint32_t u = 0; u < 6u; ++u)
       if (k0 + 64u * u < cnt) acc = fmaf(wv[u], sv[u], acc);
   }
-  return chroma_tree_sum(acc);
+  return wave_sum(acc);
 }
 
 // Rows f0 .. f0 + nf - 1 from R [nf][NC] in LDS, one wave per frame: the norm, the division, the non-finite rule, and for tonnetz the
@@ -87,10 +81,10 @@ __device__ __forceinline__ void chroma_finish(const SpecHeader* H, const ChromaH
         s = s + a;
       }
       bad = __any(bad) != 0;
-      mx = frames_wave_max(mx);
+      mx = wave_max(mx);
       float N = mx;
       if (norm == VSYN_CHROMA_NORM_L1) {
-        N = chroma_tree_sum(s);
+        N = wave_sum(s);
       } else if (norm == VSYN_CHROMA_NORM_L2 && !(mx < FLT_MIN)) {  // mx sqrt(sum (R / mx)^2): the squares neither overflow nor vanish
         s = 0.f;
 #pragma unroll
@@ -98,7 +92,7 @@ __device__ __forceinline__ void chroma_finish(const SpecHeader* H, const ChromaH
           const float t = v[j] / mx;
           s = fmaf(t, t, s);
         }
-        N = mx * sqrtf(chroma_tree_sum(s));
+        N = mx * sqrtf(wave_sum(s));
       }
       if (norm != VSYN_CHROMA_NORM_NONE && !bad && !(N < FLT_MIN)) {
 #pragma unroll
@@ -108,7 +102,7 @@ __device__ __forceinline__ void chroma_finish(const SpecHeader* H, const ChromaH
         float s1 = 0.f;
 #pragma unroll
         for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) s1 = s1 + fabsf(v[j]);
-        s1 = chroma_tree_sum(s1);
+        s1 = wave_sum(s1);
         if (!(s1 < FLT_MIN)) {
 #pragma unroll
           for (uint32_t j = 0; j < CHROMA_MAX / 64; ++j) v[j] = v[j] / s1;
@@ -302,13 +296,12 @@ static inline int spec_chroma_table(SpectralWs& ws, const vsyn_spectral_spec* sp
 static inline int spec_chroma_run(const SpecCtx& A, const vsyn_spectral_spec* sp, uint32_t ft, dim3 grid, hipStream_t s, const char** err) {
   const uint32_t n = sp->n_fft;
   if (spec_lin_pow2(n)) {
-    hipLaunchKernelGGL(vsyn_chroma_fft_kernel, grid, dim3(SPEC_THREADS), chroma_fft_lds_floats(ft, n) * 4u, s, A, ft, spec_lin_lgm(n));
+    VSYN_LAUNCH(vsyn_chroma_fft_kernel, grid, dim3(SPEC_THREADS), chroma_fft_lds_floats(ft, n) * 4u, s, A, ft, spec_lin_lgm(n));
   } else {
     const size_t lds = chroma_direct_lds_floats(ft, n, sp->hop_length) * 4u;
-    if (ft == CHROMA_DIRECT_FT) hipLaunchKernelGGL(vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
-    else hipLaunchKernelGGL(vsyn_chroma_direct_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
+    if (ft == CHROMA_DIRECT_FT) VSYN_LAUNCH(vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
+    else VSYN_LAUNCH(vsyn_chroma_direct_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
   }
-  HIPCHK(hipGetLastError());
   return VSYN_OK;
 }
 
@@ -367,8 +360,7 @@ static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_sp
   A.segmax = ws.segmax.p;
   A.rows = d_rows;
   A.db = mfcc ? ws.db.p : nullptr;
-  hipLaunchKernelGGL(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_spec_offsets_kernel, dim3(1), dim3(SPEC_THREADS), 0, s, A);
   if (f_max == 0 || S == 0) return VSYN_OK;
   const uint64_t gx = (f_max + ft - 1) / ft;
   if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");

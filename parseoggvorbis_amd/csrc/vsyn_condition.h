@@ -3,8 +3,8 @@
 //
 // Two kernels on one stream, both on a grid of (tile of COND_TILE frames, segment):
 //   1. vsyn_cond_peak_kernel   VSYN_COND_PEAK only. Every thread downmixes its frames (pcm_downmix, vsyn_device.h) and keeps the
-//                              largest |bits| as an unsigned integer; the maximum goes through the wave (__shfl_xor), the
-//                              workgroup's four waves (LDS) and one atomicMax per workgroup into the segment's word, which the
+//                              largest |bits| as an unsigned integer; the maximum goes through the wave, the
+//                              workgroup's four waves (vsyn_wave.h) and one atomicMax per workgroup into the segment's word, which the
 //                              host side clears first. A maximum does not depend on the order: the same PCM gives the same bits.
 //   2. vsyn_cond_apply_kernel  downmix again, y / p (__fdiv_rn, the IEEE division) when the word holds a finite p > 0, then
 //                              z[t] = fmaf(-a, y1[t-1], y1[t]): each thread recomputes y1[t-1] from one more frame on its left, so
@@ -19,6 +19,7 @@
 #pragma once
 #include "vsyn_device.h"
 #include "vsyn_host.h"
+#include "vsyn_wave.h"
 
 #define COND_THREADS 256
 #define COND_PER_THREAD 4
@@ -98,11 +99,8 @@ __global__ void __launch_bounds__(COND_THREADS) vsyn_cond_peak_kernel(const Cond
       if (t < T) mx = max(mx, cond_abs_bits(pcm_downmix(x, A.plane, C, inv_c, t)));
     }
   }
-  for (int o = 32; o; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
-  if ((tid & 63u) == 0) s_wave[tid >> 6] = mx;
-  __syncthreads();
+  mx = wg_reduce_t0<COND_THREADS / 64>(mx, s_wave, WaveMax(), 0u);
   if (tid == 0) {
-    mx = max(max(s_wave[0], s_wave[1]), max(s_wave[2], s_wave[3]));
     if (mx) atomicMax(A.peak + g, mx);  // (the word was cleared: silence leaves it 0)
   }
 }
@@ -239,11 +237,9 @@ static inline int cond_launch(CondWs& ws, int device, const vsyn_pcm_cond* c, ui
   const dim3 grid((uint32_t)gx, S);
   if (peak) {
     HIPCHK(hipMemsetAsync(d_peak, 0, sizeof(uint32_t) * S, s));
-    hipLaunchKernelGGL(vsyn_cond_peak_kernel, grid, dim3(COND_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_cond_peak_kernel, grid, dim3(COND_THREADS), 0, s, A);
   }
-  hipLaunchKernelGGL(vsyn_cond_apply_kernel, grid, dim3(COND_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_cond_apply_kernel, grid, dim3(COND_THREADS), 0, s, A);
   return VSYN_OK;
 }
 

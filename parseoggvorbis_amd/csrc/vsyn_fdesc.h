@@ -22,16 +22,16 @@
 //                                 TWL = true reads the twiddles from LDS, TWL = false from the table in global memory (every workgroup
 //                                 re-reads the same 16 n_fft bytes: L2). Both read the same table: the bits do not depend on the path.
 //                                 Then per frame, by the whole workgroup: the ordered sums below, the roll-off bin by an integer
-//                                 minimum through the wave (__shfl_xor) and the four waves (LDS), the zero-crossing count by an integer
+//                                 minimum through the wave and the four waves (vsyn_wave.h), the zero-crossing count by an integer
 //                                 sum, and thread 0 writes the row. No atomics.
 //                                 The workgroup also looks at every sample of its share of the segment for an Inf or a NaN
 //                                 (trim_not_finite) and stores one flag word per tile.
 //   3. vsyn_fdesc_finish_kernel   one workgroup per segment: a segment with a flagged tile is refused: its rows become NaN and its
 //                                 word of the refused array 1 (frames_finish).
 // Order of the sums over the bins: with K = ceil(NB / 256), thread t owns the bins t K .. min((t + 1) K, NB) - 1 and adds its terms in
-// ascending order from 0.0 (its total). The totals are scanned inside each wave by Hillis-Steele over the lane offsets 1, 2, .. 32; a
-// wave's offset is the sum of the earlier waves' totals in ascending order; a sum over all bins is ((w0 + w1) + w2) + w3 of the four
-// waves' totals; and c_k = (wave offset + the exclusive lane prefix) + S[first] + .. + S[k], added left to right. A = c_(NB-1). The
+// ascending order from 0.0 (its total). The totals go through wg_sum_scan (vsyn_wave.h; the order is DESIGN.md 6t: the wave scan over
+// the lane offsets 1, 2, .. 32, a wave's offset the earlier waves' totals in ascending order, a sum over all bins ((w0 + w1) + w2) + w3 of
+// the four waves' totals); and c_k = (wave offset + the exclusive lane prefix) + S[first] + .. + S[k], added left to right. A = c_(NB-1). The
 // frame's energy (rms) is summed the same way over the samples, K = ceil(n_fft / 256). A function of n_fft alone.
 // LDS budget: FDESC_LDS_BUDGET = 79 KiB (80,896 B) of dynamic LDS, so that two workgroups share a CU's 160 KiB beside the
 // static LDS of __syncthreads_or; with the twiddles in LDS one frame takes 28 n_fft + 216 bytes, which fits up to n_fft = 2881. Above that the twiddles
@@ -80,44 +80,6 @@ struct FdescCtx {  // launch arguments
 
 __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_offsets_kernel(const FdescCtx A) {
   frames_offsets(A, A.N, [&](uint32_t g) { return A.sr[g] == 0.0; });
-}
-
-// M sums over the workgroup in the order of the header: v = this thread's totals; exc = the sum of the totals of the threads in front
-// of it, tot = the sum of all of them, for every thread (s_w: M * FDESC_WAVES doubles of LDS, free again on return)
-template <uint32_t M>
-__device__ __forceinline__ void fdesc_scan(const double (&v)[M], double (&exc)[M], double (&tot)[M], double* s_w) {
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t m = 0; m < M; ++m) {
-    double inc = v[m];
-    for (int o = 1; o < 64; o <<= 1) {
-      const double up = __shfl_up(inc, o);
-      if ((int)lane >= o) inc += up;
-    }
-    if (lane == 63u) s_w[m * FDESC_WAVES + wave] = inc;
-    const double e = __shfl_up(inc, 1);
-    exc[m] = lane == 0u ? 0.0 : e;
-  }
-  __syncthreads();
-#pragma unroll
-  for (uint32_t m = 0; m < M; ++m) {
-    const double* w = s_w + m * FDESC_WAVES;
-    double woff = 0.0;
-    for (uint32_t i = 0; i < wave; ++i) woff += w[i];
-    exc[m] = woff + exc[m];
-    tot[m] = ((w[0] + w[1]) + w[2]) + w[3];
-  }
-  __syncthreads();
-}
-
-// the sum of v over the workgroup, for every thread (s_r: FDESC_WAVES words of LDS, free again on return)
-__device__ __forceinline__ uint32_t fdesc_wg_count(uint32_t v, uint64_t* s_r) {
-  for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  if ((threadIdx.x & 63u) == 0) s_r[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (uint32_t)(s_r[0] + s_r[1] + s_r[2] + s_r[3]);
-  __syncthreads();
-  return v;
 }
 
 // Bin k of NR frames a tile step apart (z0: the first one's samples): S into out[0], out[NB], .. One twiddle read serves the NR
@@ -221,8 +183,8 @@ __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCt
       const bool sa = ya < 0.0 && fabs(ya) > A.zthr, sb = yb < 0.0 && fabs(yb) > A.zthr;
       cross += sa != sb ? 1u : 0u;
     }
-    fdesc_scan<FDESC_SUMS>(v, exc, tot, s_w);
-    cross = fdesc_wg_count(cross, s_r);
+    wg_sum_scan<FDESC_SUMS>(v, exc, tot, s_w);
+    cross = wg_reduce_all<FDESC_WAVES>(cross, (uint32_t*)s_r, WaveSum(), 0u);
     // A = c_(NB-1), from the thread that owns the last bin
     {
       double run = exc[0];
@@ -250,7 +212,7 @@ __global__ void __launch_bounds__(FDESC_THREADS) vsyn_fdesc_kernel(const FdescCt
       const double d = (double)kk * sr / dn - cent;
       v2[0] = fma(S[kk] * d, d, v2[0]);
     }
-    fdesc_scan<1>(v2, e2, t2, s_w);
+    wg_sum_scan<1>(v2, e2, t2, s_w);
     if (tid == 0) {
       float* row = A.rows + (size_t)FDESC_COLS * (r0 + f);
       row[0] = (float)sqrt(tot[4] / dn);

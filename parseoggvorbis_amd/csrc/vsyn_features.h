@@ -433,17 +433,15 @@ static inline int feat_launch(FeatureWs& ws, int device, const ConstHeader& H, c
   A.P = P;
   A.S = S;
   A.max_seg = max_seg;
-  hipLaunchKernelGGL(vsyn_feat_count_kernel, dim3(S), dim3(FEAT_THREADS), 0, s, A);
-  hipLaunchKernelGGL(vsyn_feat_offsets_kernel, dim3(1), dim3(FEAT_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_feat_count_kernel, dim3(S), dim3(FEAT_THREADS), 0, s, A);
+  VSYN_LAUNCH(vsyn_feat_offsets_kernel, dim3(1), dim3(FEAT_THREADS), 0, s, A);
   if (!d_rows || P == 0 || max_seg == 0) return VSYN_OK;  // (no packet: every segment is empty or flagged by the count kernel)
   const uint32_t rows = P * C;
-  hipLaunchKernelGGL(vsyn_floor_unwrap_kernel, dim3(std::min<uint32_t>((rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, 65535u)), dim3(UNWRAP_THREADS), unwrap_lds_bytes, s,
-                     d_const, P, (const PktInfo*)ws.info.p, d_ys, ws.fy.p, d_status);
+  VSYN_LAUNCH(vsyn_floor_unwrap_kernel, dim3(std::min<uint32_t>((rows + UNWRAP_THREADS - 1) / UNWRAP_THREADS, 65535u)), dim3(UNWRAP_THREADS), unwrap_lds_bytes, s,
+              d_const, P, (const PktInfo*)ws.info.p, d_ys, ws.fy.p, d_status);
   const uint64_t slots = (uint64_t)max_seg * C;
   const uint64_t gx = (slots + FEAT_ROW_WAVES - 1) / FEAT_ROW_WAVES;
   if (gx > 0x7FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment too long");
-  hipLaunchKernelGGL(vsyn_feat_rows_kernel, dim3((uint32_t)gx, S), dim3(FEAT_ROW_WAVES * 64), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_feat_rows_kernel, dim3((uint32_t)gx, S), dim3(FEAT_ROW_WAVES * 64), 0, s, A);
   return VSYN_OK;
 }

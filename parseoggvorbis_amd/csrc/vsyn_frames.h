@@ -11,7 +11,6 @@
 //   frames_tile_head / _derive /  a (tile, segment) workgroup of the pitch and descriptor kernels: its derived quantities, the staged
 //   _stage, frames_offsets,       frames, the non-finite flag word; the offsets and finishing kernels' bodies
 //   frames_finish
-//   frames_wave_max               fmaxf through a wave
 // A Ctx template parameter is a stage's launch-argument struct; the helpers read the fields that all of them name alike (pcm, plane, C,
 // frames, si; for the pitch and descriptor stages also S, H, FT, center, tiles, segF, segoff, flags, refused, rows).
 // The host side holds the window and twiddle generators and the launch sequence of the pitch and descriptor stages.
@@ -19,6 +18,7 @@
 #include "vsyn_device.h"
 #include "vsyn_host.h"
 #include "vsyn_trim.h"
+#include "vsyn_wave.h"
 
 #define FRAMES_THREADS 256  // the workgroup of every kernel here
 
@@ -32,11 +32,6 @@ __host__ __device__ __forceinline__ uint64_t spec_num_frames(uint32_t n, uint32_
 template <class Ctx>
 __device__ __forceinline__ uint64_t frames_len(const Ctx& A, uint32_t g) {
   return min((uint64_t)(A.frames ? A.frames[g] : A.si[g].total_emit), A.plane);
-}
-
-__device__ __forceinline__ float frames_wave_max(float v) {
-  for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -309,11 +304,8 @@ static inline int frames_begin(Ws& ws, int device, const std::vector<uint8_t>& t
 // The stage's three kernels on stream s: offsets, one workgroup per (tile, segment) with lds bytes of dynamic LDS, finish.
 template <class Ctx>
 static inline int frames_launch(const Ctx& A, void (*offsets)(Ctx), void (*tile)(Ctx), size_t lds, void (*finish)(Ctx), hipStream_t s, const char** err) {
-  hipLaunchKernelGGL(offsets, dim3(1), dim3(FRAMES_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(tile, dim3(A.tiles, A.S), dim3(FRAMES_THREADS), lds, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(finish, dim3(A.S), dim3(FRAMES_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(offsets, dim3(1), dim3(FRAMES_THREADS), 0, s, A);
+  VSYN_LAUNCH(tile, dim3(A.tiles, A.S), dim3(FRAMES_THREADS), lds, s, A);
+  VSYN_LAUNCH(finish, dim3(A.S), dim3(FRAMES_THREADS), 0, s, A);
   return VSYN_OK;
 }

@@ -9,7 +9,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <numeric>
+#include <utility>
 #include <vector>
 
 #include "vsyn_device.h"
@@ -91,6 +93,95 @@ struct TableUpload {
     if (host) (void)hipHostFree(host);
   }
 };
+
+// Launch and return the launch's error from the calling function (the text names the file and line of the site).
+#define VSYN_LAUNCH(kernel, grid, block, lds, stream, ...)              \
+  do {                                                                  \
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);  \
+    HIPCHK(hipGetLastError());                                          \
+  } while (0)
+
+// Raise the dynamic-LDS limits of a stage's kernels, once per handle (flag: the workspace's word for it; the device is selected).
+struct LdsLimit {
+  const void* kernel;
+  size_t bytes;
+};
+static inline int raise_lds_once(bool& flag, std::initializer_list<LdsLimit> limits, const char** err) {
+  if (flag) return VSYN_OK;
+  for (const LdsLimit& l : limits) HIPCHK(hipFuncSetAttribute(l.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.bytes));
+  flag = true;
+  return VSYN_OK;
+}
+
+// The per-segment records of the stages that walk rows [rows][D] segment by segment: the segment's first row and its rows, and for
+// the stages that cut a segment into blocks of rows its first block. A stage whose record carries more derives from one of them (the
+// kernels read the same bytes) or keeps a record and a loop of its own.
+struct RowSeg {
+  uint64_t off;  // first row of the segment in the row buffers
+  uint32_t F, pad;
+};
+struct RowBlkSeg {
+  uint64_t off;  // first row of the segment in the row buffers
+  uint64_t blk;  // first block of the segment in the stage's per-block buffers
+  uint32_t F, pad;
+};
+// Thread layout of a workgroup of THREADS over rows of D columns: wd lanes along the columns, G = THREADS / wd row groups; this thread
+// is lane tx of group ty (a thread with ty >= G has no group).
+struct RowLane {
+  uint32_t wd, G, ty, tx;
+};
+template <uint32_t THREADS>
+__device__ __forceinline__ RowLane row_lane(uint32_t D) {
+  RowLane L;
+  L.wd = min(D, THREADS);
+  L.G = THREADS / L.wd;
+  L.ty = threadIdx.x / L.wd;
+  L.tx = threadIdx.x - L.ty * L.wd;
+  return L;
+}
+struct RowTotals {
+  uint64_t rows = 0, blocks = 0, f_max = 0;  // all rows (skipped segments' too), the live segments' blocks, the longest live segment
+};
+static inline void row_seg_set(RowSeg& r, const RowTotals& t, uint32_t F) { r.off = t.rows, r.F = F, r.pad = 0u; }
+static inline void row_seg_set(RowBlkSeg& r, const RowTotals& t, uint32_t F) { r.off = t.rows, r.blk = t.blocks, r.F = F, r.pad = 0u; }
+// seg[g] for g < S from seg_rows; live (may be NULL): a segment with live[g] = 0 keeps its place but has F = 0. blk_len: rows a block.
+template <class Seg>
+static inline RowTotals row_segs_fill(Seg* seg, uint32_t S, const uint64_t* seg_rows, const uint32_t* live, uint32_t blk_len) {
+  RowTotals t;
+  for (uint32_t g = 0; g < S; ++g) {
+    const uint64_t F = live && !live[g] ? 0u : seg_rows[g];
+    row_seg_set(seg[g], t, (uint32_t)F);
+    t.rows += seg_rows[g];
+    t.blocks += (F + blk_len - 1u) / blk_len;
+    t.f_max = std::max(t.f_max, F);
+  }
+  return t;
+}
+
+static inline uint64_t seg_total(uint32_t S, const uint64_t* seg_rows) {
+  uint64_t total = 0;
+  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  return total;
+}
+
+// The refusals every call over seg_rows[S] shares, in this order.
+static inline int rows_check_segs(uint32_t S, const uint64_t* seg_rows, uint64_t max_rows, const char** err) {
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  for (uint32_t g = 0; g < S; ++g)
+    if (seg_rows[g] > max_rows) return fail(err, VSYN_ERR_INVALID, "segment %u: too many rows", g);
+  return VSYN_OK;
+}
+
+// Tables shared by the segments of one key, laid out back to back: the offset of key's table among those already placed (key,
+// offset), else it is placed at *next, which grows by len.
+static inline uint32_t table_slot(std::vector<std::pair<uint32_t, uint32_t>>& placed, uint32_t key, uint32_t* next, uint32_t len) {
+  for (const auto& p : placed)
+    if (p.first == key) return p.second;
+  placed.push_back(std::make_pair(key, *next));
+  *next += len;
+  return placed.back().second;
+}
 
 static inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1)); }
 static inline uint32_t ilog2(uint32_t v) {

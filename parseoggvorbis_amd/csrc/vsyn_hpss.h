@@ -38,10 +38,7 @@
 #define HPSS_NAN_KEY 0xFFFFFFFFu
 #define HPSS_MAX_DIM 0x3FFFFFFFu  // rows per segment, and columns: twice the count is an int32 in the reflection
 
-struct HpssSeg {
-  uint64_t off;  // first row of the segment in the row buffers
-  uint32_t F, pad;
-};
+typedef RowSeg HpssSeg;
 
 struct HpssCtx {  // launch arguments
   const HpssSeg* seg;
@@ -230,11 +227,10 @@ static inline int hpss_check_call(const vsyn_spectral_hpss* p, uint32_t D, uint3
   if (int rc = hpss_check(p, err)) return rc;
   if (D < 1) return fail(err, VSYN_ERR_INVALID, "hpss: dim must be >= 1");
   if (D > HPSS_MAX_DIM) return fail(err, VSYN_ERR_INVALID, "hpss: dim too large");
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
+  if (int rc = rows_check_segs(S, seg_rows, HPSS_MAX_DIM, err)) return rc;
   const uint64_t ntd = (D + HPSS_TD - 1u) / HPSS_TD;
-  for (uint32_t g = 0; g < S; ++g)
-    if (seg_rows[g] > HPSS_MAX_DIM || (seg_rows[g] + HPSS_TF - 1u) / HPSS_TF * ntd > 0x7FFFFFFFull)
+  for (uint32_t g = 0; g < S; ++g)  // the tiles of a segment are one grid dimension
+    if ((seg_rows[g] + HPSS_TF - 1u) / HPSS_TF * ntd > 0x7FFFFFFFull)
       return fail(err, VSYN_ERR_INVALID, "segment %u: too many rows", g);
   return VSYN_OK;
 }
@@ -246,13 +242,7 @@ static inline int hpss_launch(HpssWs& ws, int device, const vsyn_spectral_hpss* 
                               const float* d_in, float* d_out, hipStream_t s, const char** err) {
   std::vector<uint8_t> tab(sizeof(HpssSeg) * (size_t)S);
   HpssSeg* seg = (HpssSeg*)tab.data();
-  uint64_t rows = 0, f_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    const uint64_t F = skip && !skip[g] ? 0u : seg_rows[g];
-    seg[g] = HpssSeg{rows, (uint32_t)F, 0u};
-    rows += seg_rows[g];
-    f_max = std::max(f_max, F);
-  }
+  const uint64_t f_max = row_segs_fill(seg, S, seg_rows, skip, 1u).f_max;
   if (f_max == 0) return VSYN_OK;
   HIPCHK(hipSetDevice(device));
   if (int rc = ws.tab.upload(tab, s, err)) return rc;
@@ -272,8 +262,7 @@ static inline int hpss_launch(HpssWs& ws, int device, const vsyn_spectral_hpss* 
   A.margin_h = p->margin_h;
   A.margin_p = p->margin_p;
   const dim3 grid((uint32_t)((f_max + HPSS_TF - 1u) / HPSS_TF * A.ntd), S);
-  hipLaunchKernelGGL(vsyn_hpss_kernel, grid, dim3(HPSS_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_hpss_kernel, grid, dim3(HPSS_THREADS), 0, s, A);
   return VSYN_OK;
 }
 
@@ -281,8 +270,7 @@ static inline int hpss_launch(HpssWs& ws, int device, const vsyn_spectral_hpss* 
 static inline int hpss_launch_any(HpssWs& ws, int device, const vsyn_spectral_hpss* p, uint32_t D, uint32_t S, const uint64_t* seg_rows,
                                   const float* d_in, float* d_out, hipStream_t s, const char** err) {
   if (d_out != d_in) return hpss_launch(ws, device, p, D, S, seg_rows, nullptr, d_in, d_out, s, err);
-  uint64_t total = 0;
-  for (uint32_t g = 0; g < S; ++g) total += seg_rows[g];
+  const uint64_t total = seg_total(S, seg_rows);
   HIPCHK(hipSetDevice(device));
   HIPCHK(ws.rows.ensure(total * D));
   if (int rc = hpss_launch(ws, device, p, D, S, seg_rows, nullptr, d_in, ws.rows.p, s, err)) return rc;

@@ -239,11 +239,8 @@ static inline int istft_launch(IstftWs& ws, int device, const vsyn_spectral_spec
     rows += seg_rows[g];
   }
   HIPCHK(hipSetDevice(device));
-  if (!ws.lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_istft_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_istft_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    ws.lds_set = true;
-  }
+  if (int rc = raise_lds_once(ws.lds_set, {{(const void*)vsyn_istft_frames_kernel, SPEC_LDS_BUDGET}, {(const void*)vsyn_istft_masked_kernel, SPEC_LDS_BUDGET}}, err))
+    return rc;
   HIPCHK(ws.frames.ensure(total_rows * n + 1));
   if (int rc = ws.tab.upload(tab, s, err)) return rc;
   IstftCtx A;
@@ -261,14 +258,12 @@ static inline int istft_launch(IstftWs& ws, int device, const vsyn_spectral_spec
     if (fwd) {
       SpecCtx P = *fwd;
       P.tab = A.tab;
-      hipLaunchKernelGGL(vsyn_istft_masked_kernel, dim3((uint32_t)gx, S), dim3(SPEC_THREADS), lds, s, P, A, ft, lgM);
+      VSYN_LAUNCH(vsyn_istft_masked_kernel, dim3((uint32_t)gx, S), dim3(SPEC_THREADS), lds, s, P, A, ft, lgM);
     } else {
-      hipLaunchKernelGGL(vsyn_istft_frames_kernel, dim3((uint32_t)gx, S), dim3(SPEC_THREADS), lds, s, A, ft, lgM);
+      VSYN_LAUNCH(vsyn_istft_frames_kernel, dim3((uint32_t)gx, S), dim3(SPEC_THREADS), lds, s, A, ft, lgM);
     }
-    HIPCHK(hipGetLastError());
   }
   const uint64_t ox = std::max<uint64_t>((len_max + SPEC_THREADS - 1) / SPEC_THREADS, 1);
-  hipLaunchKernelGGL(vsyn_istft_ola_kernel, dim3((uint32_t)ox, S), dim3(SPEC_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_istft_ola_kernel, dim3((uint32_t)ox, S), dim3(SPEC_THREADS), 0, s, A);
   return VSYN_OK;
 }

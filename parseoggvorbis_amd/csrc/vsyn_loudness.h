@@ -27,6 +27,7 @@
 #pragma once
 #include "vsyn_device.h"
 #include "vsyn_host.h"
+#include "vsyn_wave.h"
 
 #define LOUD_LANES 256u
 #define LOUD_SUB 32u                       // samples per lane chunk
@@ -290,7 +291,7 @@ __global__ void __launch_bounds__(256) vsyn_loud_hops_kernel(const LoudCtx A) {
     const uint64_t nsub = (uint64_t)sg->tiles * LOUD_LANES;
     for (uint64_t l = l_lo + lane; l <= l_hi; l += 64u) s += sub[l == l_lo && behind ? nsub + l : l];
   }
-  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (lane == 0) A.hops[sg->hop_off * A.Cs + (uint64_t)c * (sg->Nh + 1u) + i] = s;
 }
 
@@ -583,23 +584,17 @@ static inline int loud_launch(LoudWs& ws, int device, const vsyn_loudness_spec* 
   A.z_abs = pow(10.0, (LOUD_ABS_GATE_LUFS + 0.691) / 10.0);
   A.z_target = (p->options & VSYN_LOUD_NORMALIZE) ? pow(10.0, (p->target + 0.691) / 10.0) : 0.0;
   if (tiles_max > 1u) {
-    hipLaunchKernelGGL(vsyn_loud_part_kernel, dim3((uint32_t)tiles_max - 1u, Cs, S), dim3(LOUD_LANES), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_loud_part_kernel, dim3((uint32_t)tiles_max - 1u, Cs, S), dim3(LOUD_LANES), 0, s, A);
   }
   if (tiles_max > 0u) {
-    hipLaunchKernelGGL(vsyn_loud_carry_kernel, dim3(S), dim3(LOUD_LANES), 0, s, A);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(vsyn_loud_apply_kernel, dim3((uint32_t)tiles_max, Cs, S), dim3(LOUD_LANES), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_loud_carry_kernel, dim3(S), dim3(LOUD_LANES), 0, s, A);
+    VSYN_LAUNCH(vsyn_loud_apply_kernel, dim3((uint32_t)tiles_max, Cs, S), dim3(LOUD_LANES), 0, s, A);
   }
-  hipLaunchKernelGGL(vsyn_loud_hops_kernel, dim3((uint32_t)((nh_max + 1u + 3u) / 4u), Cs, S), dim3(256), 0, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_loud_gate_kernel, dim3(S), dim3(256), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_loud_hops_kernel, dim3((uint32_t)((nh_max + 1u + 3u) / 4u), Cs, S), dim3(256), 0, s, A);
+  VSYN_LAUNCH(vsyn_loud_gate_kernel, dim3(S), dim3(256), 0, s, A);
   if (d_scaled && std::min(f_max, splane) > 0u) {
     const uint64_t gx = (std::min(f_max, splane) + 1023u) / 1024u;
-    hipLaunchKernelGGL(vsyn_loud_scale_kernel, dim3((uint32_t)gx, Cs, S), dim3(256), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_loud_scale_kernel, dim3((uint32_t)gx, Cs, S), dim3(256), 0, s, A);
   }
   return VSYN_OK;
 }

@@ -21,10 +21,7 @@
 #define PCEN_THREADS 256
 #define PCEN_BLK 64u  // rows per block of the scan
 
-struct PcenSeg {
-  uint64_t off;  // first row of the segment in the row buffers
-  uint64_t blk;  // first block of the segment in part / carry
-  uint32_t F, pad;
+struct PcenSeg : RowBlkSeg {  // blk: the segment's first block in part / carry
   double b, q, qblk;  // the coefficient, 1 - b, q^PCEN_BLK
 };
 
@@ -39,19 +36,7 @@ struct PcenCtx {  // launch arguments
   double gain, bias, power, eps, log_eps, bias_pow;  // log(eps) and bias^power from the host
 };
 
-// Thread layout: wd lanes along the columns, G = PCEN_THREADS / wd row groups; group ty of workgroup x takes block x G + ty.
-struct PcenLane {
-  uint32_t wd, G, ty, tx;
-};
-__device__ __forceinline__ PcenLane pcen_lane(uint32_t D) {
-  PcenLane L;
-  L.wd = min(D, (uint32_t)PCEN_THREADS);
-  L.G = PCEN_THREADS / L.wd;
-  L.ty = threadIdx.x / L.wd;
-  L.tx = threadIdx.x - L.ty * L.wd;
-  return L;
-}
-
+// Thread layout (row_lane): group ty of workgroup x takes block x G + ty.
 // S = float32(X * float32(scale)), one rounding; then one step of the smoother. Both kernels that walk rows go through these two.
 __device__ __forceinline__ float pcen_scaled(float x, float scale) { return x * scale; }
 __device__ __forceinline__ double pcen_step(double m, double b, double q, float s) { return b * (double)s + q * m; }
@@ -71,7 +56,7 @@ __device__ __forceinline__ float pcen_value(const PcenCtx& A, float s, double m)
 
 __global__ void __launch_bounds__(PCEN_THREADS) vsyn_pcen_part_kernel(const PcenCtx A) {
   const PcenSeg sg = A.seg[blockIdx.y];
-  const PcenLane L = pcen_lane(A.D);
+  const RowLane L = row_lane<PCEN_THREADS>(A.D);
   if (L.ty >= L.G) return;
   const uint32_t nblk = (sg.F + PCEN_BLK - 1u) / PCEN_BLK;
   const uint64_t k = (uint64_t)blockIdx.x * L.G + L.ty;
@@ -102,7 +87,7 @@ __global__ void __launch_bounds__(PCEN_THREADS) vsyn_pcen_carry_kernel(const Pce
 
 __global__ void __launch_bounds__(PCEN_THREADS) vsyn_pcen_apply_kernel(const PcenCtx A) {
   const PcenSeg sg = A.seg[blockIdx.y];
-  const PcenLane L = pcen_lane(A.D);
+  const RowLane L = row_lane<PCEN_THREADS>(A.D);
   if (L.ty >= L.G) return;
   const uint64_t k = (uint64_t)blockIdx.x * L.G + L.ty;
   if (k * PCEN_BLK >= sg.F) return;
@@ -177,15 +162,13 @@ static inline int pcen_launch(PcenWs& ws, int device, const vsyn_spectral_pcen* 
   if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
   std::vector<uint8_t> tab(sizeof(PcenSeg) * (size_t)S);
   PcenSeg* seg = (PcenSeg*)tab.data();
-  uint64_t rows = 0, blocks = 0, f_max = 0;
+  const RowTotals t = row_segs_fill(seg, S, seg_rows, rates, PCEN_BLK);
   for (uint32_t g = 0; g < S; ++g) {
-    const uint64_t F = rates && !rates[g] ? 0u : seg_rows[g];
-    const double b = F ? pcen_b(p, rates ? rates[g] : 0u, hop) : 1.0, q = 1.0 - b;
-    seg[g] = PcenSeg{rows, blocks, (uint32_t)F, 0u, b, q, pow(q, (double)PCEN_BLK)};
-    rows += seg_rows[g];
-    blocks += (F + PCEN_BLK - 1u) / PCEN_BLK;
-    f_max = std::max(f_max, F);
+    seg[g].b = seg[g].F ? pcen_b(p, rates ? rates[g] : 0u, hop) : 1.0;
+    seg[g].q = 1.0 - seg[g].b;
+    seg[g].qblk = pow(seg[g].q, (double)PCEN_BLK);
   }
+  const uint64_t blocks = t.blocks, f_max = t.f_max;
   if (f_max == 0) return VSYN_OK;
   HIPCHK(hipSetDevice(device));
   HIPCHK(ws.part.ensure(blocks * D));
@@ -209,11 +192,8 @@ static inline int pcen_launch(PcenWs& ws, int device, const vsyn_spectral_pcen* 
   const uint32_t G = PCEN_THREADS / std::min<uint32_t>(D, PCEN_THREADS);
   const uint64_t nblk = (f_max + PCEN_BLK - 1u) / PCEN_BLK;
   const dim3 grid((uint32_t)((nblk + G - 1u) / G), S), cgrid((D + PCEN_THREADS - 1u) / PCEN_THREADS, S);
-  hipLaunchKernelGGL(vsyn_pcen_part_kernel, grid, dim3(PCEN_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_pcen_carry_kernel, cgrid, dim3(PCEN_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_pcen_apply_kernel, grid, dim3(PCEN_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_pcen_part_kernel, grid, dim3(PCEN_THREADS), 0, s, A);
+  VSYN_LAUNCH(vsyn_pcen_carry_kernel, cgrid, dim3(PCEN_THREADS), 0, s, A);
+  VSYN_LAUNCH(vsyn_pcen_apply_kernel, grid, dim3(PCEN_THREADS), 0, s, A);
   return VSYN_OK;
 }

@@ -16,14 +16,14 @@
 //                                 wave per SIMD, two workgroups per CU at the LDS budget).
 //                                 Then per frame, by the whole workgroup: the cumulative sum S (order below), c in place of d,
 //                                 the first trough below the threshold and the first minimum by 64-bit integer minima through the
-//                                 wave (__shfl_xor) and the four waves (LDS), and thread 0 writes the row. No atomics.
+//                                 wave and the four waves (vsyn_wave.h), and thread 0 writes the row. No atomics.
 //                                 The workgroup also looks at every sample of its share of the segment for an Inf or a NaN
 //                                 (trim_not_finite, the trim stage's test) and stores one flag word per tile (frames_tile_stage).
 //   3. vsyn_pitch_finish_kernel   one workgroup per segment: a segment with a flagged tile is refused: its rows become NaN and its
 //                                 word of the refused array 1 (frames_finish).
 // Order of S: with K = ceil(p_max / PITCH_THREADS), thread t owns the lags t K + 1 .. (t + 1) K. It adds its d in ascending order
-// (its total), the totals are scanned inside each wave by Hillis-Steele over the lane offsets 1, 2, .. 32, a wave's offset is the sum
-// of the earlier waves' totals in ascending order, and S[tau] = (wave offset + the exclusive lane prefix) + d[first] + .. + d[tau],
+// (its total), the totals go through wg_sum_scan<1> (vsyn_wave.h; DESIGN.md 6t: the wave scan over the lane offsets 1, 2, .. 32, a wave's
+// offset the sum of the earlier waves' totals in ascending order), and S[tau] = (wave offset + the exclusive lane prefix) + d[first] + .. + d[tau],
 // added left to right. A function of p_max alone. Every term is >= 0: the relative error is at most (terms) * 2^-53.
 // Nothing here reads or writes stream state, the overlap carry or any synthesis buffer; the PCM is only read.
 #pragma once
@@ -70,12 +70,7 @@ __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_offsets_kernel(const
 
 // the minimum of v over the workgroup, for every thread (s_r: PITCH_WAVES words of LDS, free again on return)
 __device__ __forceinline__ uint64_t pitch_wg_min(uint64_t v, uint64_t* s_r) {
-  v = trim_wave_min(v);
-  if ((threadIdx.x & 63u) == 0) s_r[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = trim_min64(trim_min64(s_r[0], s_r[1]), trim_min64(s_r[2], s_r[3]));
-  __syncthreads();
-  return v;
+  return wg_reduce_all<PITCH_WAVES>(v, s_r, WaveMin(), PITCH_NONE);
 }
 
 __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCtx A) {
@@ -128,25 +123,14 @@ __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCt
   const uint32_t p_min = sg.p_min, n = PL - p_min + 1u;
   const uint32_t K = (PL + PITCH_THREADS - 1u) / PITCH_THREADS;
   const uint32_t b0 = tid * K < PL ? tid * K : PL, b1 = b0 + K < PL ? b0 + K : PL;  // this thread's lags, as indices tau - 1
-  const uint32_t wave = tid >> 6, lane = tid & 63u;
   const uint64_t r0 = A.segoff[g] + f0;
   for (uint32_t f = 0; f < nf; ++f) {
     double* d = s_d + (size_t)f * PL;
     // S, and c in place of d from p_min on
-    double tot = 0.0;
-    for (uint32_t k = b0; k < b1; ++k) tot += d[k];
-    double inc = tot;
-    for (int o = 1; o < 64; o <<= 1) {
-      const double up = __shfl_up(inc, o);
-      if ((int)lane >= o) inc += up;
-    }
-    if (lane == 63u) s_w[wave] = inc;
-    double exc = __shfl_up(inc, 1);
-    if (lane == 0u) exc = 0.0;
-    __syncthreads();
-    double woff = 0.0;
-    for (uint32_t w = 0; w < wave; ++w) woff += s_w[w];
-    double run = woff + exc;
+    double tot[1] = {0.0}, exc[1], all[1];
+    for (uint32_t k = b0; k < b1; ++k) tot[0] += d[k];
+    wg_sum_scan<1>(tot, exc, all, s_w);
+    double run = exc[0];
     for (uint32_t k = b0; k < b1; ++k) {
       const double dk = d[k];
       run += dk;

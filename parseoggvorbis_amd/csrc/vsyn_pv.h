@@ -197,11 +197,8 @@ static inline int pv_launch(PvWs& ws, int device, const vsyn_spectral_spec* sp, 
   P.nb = nb;
   const uint32_t kt = (nb + PV_THREADS - 1u) / PV_THREADS;
   const dim3 grid((uint32_t)bx, kt, S);  // bx <= 2^24: ISTFT_MAX_ROWS / VSYN_PV_BLOCK
-  hipLaunchKernelGGL(vsyn_pv_kernel<false>, grid, dim3(PV_THREADS), 0, s, P);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_pv_carry_kernel, dim3(kt, S), dim3(PV_THREADS), 0, s, P);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_pv_kernel<true>, grid, dim3(PV_THREADS), 0, s, P);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_pv_kernel<false>, grid, dim3(PV_THREADS), 0, s, P);
+  VSYN_LAUNCH(vsyn_pv_carry_kernel, dim3(kt, S), dim3(PV_THREADS), 0, s, P);
+  VSYN_LAUNCH(vsyn_pv_kernel<true>, grid, dim3(PV_THREADS), 0, s, P);
   return VSYN_OK;
 }

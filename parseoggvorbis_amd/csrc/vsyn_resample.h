@@ -361,15 +361,12 @@ static inline int rs_launch(ResampleWs& ws, int device, uint32_t S, const uint32
   A.in_frames = ws.inF.p;
   A.out_frames = d_out_frames ? d_out_frames : ws.outF.p;
   A.off = ws.off.p;
-  hipLaunchKernelGGL(vsyn_rs_offsets_kernel, dim3(1), dim3(RS_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_rs_offsets_kernel, dim3(1), dim3(RS_THREADS), 0, s, A);
   if (plan.chunks[0]) {
-    hipLaunchKernelGGL(vsyn_rs_kernel<true>, dim3((uint32_t)plan.chunks[0]), dim3(RS_THREADS), plan.lds_bytes, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_rs_kernel<true>, dim3((uint32_t)plan.chunks[0]), dim3(RS_THREADS), plan.lds_bytes, s, A);
   }
   if (plan.chunks[1]) {
-    hipLaunchKernelGGL(vsyn_rs_kernel<false>, dim3((uint32_t)plan.chunks[1]), dim3(RS_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_rs_kernel<false>, dim3((uint32_t)plan.chunks[1]), dim3(RS_THREADS), 0, s, A);
   }
   return VSYN_OK;
 }

@@ -5,7 +5,7 @@
 //   A. vsyn_onset_kernel           grid (tile of ONS_FT frames, segment), a wave per frame. The reference row g - lag goes to the wave's
 //                                  LDS line as order keys (vsyn_hpss.h: NaN the largest key), lane i takes the bins i, i + 64, ..: the
 //                                  bin maximum out of LDS, the difference and its clamp in float64, its partial sum; the 64 partials
-//                                  are folded by __shfl_xor over 32 .. 1, which leaves the same sum in every lane. Rows are read
+//                                  are folded by wave_sum, which leaves the same sum in every lane. Rows are read
 //                                  coalesced and once (twice with max_size = 1), nothing is accumulated across frames.
 //   B. vsyn_peaks_minmax_kernel    one workgroup per segment: float32 minimum and maximum (order keys again: the order of the reads
 //                                  cannot show) and whether a value is not finite.
@@ -31,6 +31,7 @@
 #include "vsyn_device.h"
 #include "vsyn_host.h"
 #include "vsyn_hpss.h"
+#include "vsyn_wave.h"
 
 #define RHY_THREADS 256
 #define RHY_WAVES (RHY_THREADS / 64)
@@ -49,10 +50,7 @@
 // ------------------------------------------------------------------------------------------------
 // A. onset strength
 // ------------------------------------------------------------------------------------------------
-struct OnsSeg {
-  uint64_t off;  // first row of the segment
-  uint32_t F, pad;
-};
+typedef RowSeg OnsSeg;
 
 struct OnsCtx {  // launch arguments
   const OnsSeg* seg;
@@ -90,7 +88,7 @@ __global__ void __launch_bounds__(RHY_THREADS) vsyn_onset_kernel(const OnsCtx A)
         const double d = (double)cur[j] - (double)r;
         part += d > 0.0 ? d : (d != d ? d : 0.0);
       }
-      for (int o = 32; o >= 1; o >>= 1) part += __shfl_xor(part, o);
+      part = wave_sum(part);
     }
     if (f < F && lane == 0u) A.env[sg.off + f] = live ? (float)(part / (double)D) : 0.f;
     __syncthreads();  // the line is free for the next frame
@@ -133,20 +131,12 @@ __global__ void __launch_bounds__(RHY_THREADS) vsyn_peaks_minmax_kernel(const Pe
     lo = min(lo, k);
     hi = max(hi, k);
   }
-  for (int o = 32; o >= 1; o >>= 1) {
-    lo = min(lo, (uint32_t)__shfl_xor((int)lo, o));
-    hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
-  }
-  if ((tid & 63u) == 0u) {
-    s_lo[tid >> 6] = lo;
-    s_hi[tid >> 6] = hi;
-  }
+  wg_put(lo, s_lo, WaveMin());  // (one barrier for the two, and it is the flag's __syncthreads_or)
+  wg_put(hi, s_hi, WaveMax());
   const int any = __syncthreads_or(bad ? 1 : 0);
   if (tid == 0u) {
-    for (uint32_t w = 1; w < RHY_WAVES; ++w) {
-      lo = min(lo, s_lo[w]);
-      hi = max(hi, s_hi[w]);
-    }
+    lo = wg_get<RHY_WAVES>(s_lo, WaveMin(), 0xFFFFFFFFu);
+    hi = wg_get<RHY_WAVES>(s_hi, WaveMax(), 0u);
     A.mm[2u * g] = sg.F ? hpss_unkey(lo) : 0.f;
     A.mm[2u * g + 1u] = sg.F ? hpss_unkey(hi) : 0.f;
     A.bad[g] = any ? 1u : 0u;
@@ -192,7 +182,7 @@ __global__ void __launch_bounds__(64) vsyn_peaks_walk_kernel(const PeakCtx A) {
       if (__ballot(mine != 0ull) == 0ull) continue;  // (wave-uniform)
       const uint32_t nw = min(64u, words - w0);
       for (uint32_t w = 0; w < nw; ++w) {
-        uint64_t word = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(mine >> 32), (int)w) << 32) | (uint32_t)__shfl((int)(uint32_t)mine, (int)w);
+        uint64_t word = shfl64(mine, (int)w);
         while (word) {  // (wave-uniform)
           const uint32_t n = ((w0 + w) << 6) + (uint32_t)__ffsll((unsigned long long)word) - 1u;
           word &= word - 1ull;
@@ -315,16 +305,8 @@ __global__ void __launch_bounds__(RHY_THREADS) vsyn_tempogram_kernel(const TgCtx
           const uint64_t b = (uint64_t)__double_as_longlong(s_ac[(size_t)f * W + l]) & 0x7FFFFFFFFFFFFFFFull;
           mx = b > mx ? b : mx;
         }
-        for (int o = 32; o >= 1; o >>= 1) {
-          const uint64_t other = ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(mx >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)mx, o);
-          mx = other > mx ? other : mx;
-        }
-        if ((tid & 63u) == 0u) s_r[tid >> 6] = mx;
-        __syncthreads();
-        if (tid == 0u) {
-          for (uint32_t k = 1; k < RHY_WAVES; ++k) mx = s_r[k] > mx ? s_r[k] : mx;
-          s_mx[f] = __longlong_as_double((long long)mx);
-        }
+        mx = wg_reduce_t0<RHY_WAVES>(mx, s_r, WaveMax(), 0ull);
+        if (tid == 0u) s_mx[f] = __longlong_as_double((long long)mx);
         __syncthreads();
       }
     }
@@ -383,13 +365,7 @@ static inline int onset_check(const vsyn_onset_spec* p, const char** err) {
   return VSYN_OK;
 }
 
-static inline int rhythm_check_segs(uint32_t S, const uint64_t* seg_rows, const char** err) {
-  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
-  if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
-  for (uint32_t g = 0; g < S; ++g)
-    if (seg_rows[g] > 0x3FFFFFFFull) return fail(err, VSYN_ERR_INVALID, "segment %u: too many rows", g);
-  return VSYN_OK;
-}
+static inline int rhythm_check_segs(uint32_t S, const uint64_t* seg_rows, const char** err) { return rows_check_segs(S, seg_rows, 0x3FFFFFFFull, err); }
 
 static inline int onset_check_call(const vsyn_onset_spec* p, uint32_t D, uint32_t S, const uint64_t* seg_rows, const char** err) {
   if (int rc = onset_check(p, err)) return rc;
@@ -402,12 +378,7 @@ static inline int onset_launch(RhythmWs& ws, int device, const vsyn_onset_spec* 
                                const float* d_rows, float* d_env, hipStream_t s, const char** err) {
   std::vector<uint8_t> tab(sizeof(OnsSeg) * (size_t)S);
   OnsSeg* seg = (OnsSeg*)tab.data();
-  uint64_t rows = 0, f_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    seg[g] = OnsSeg{rows, (uint32_t)seg_rows[g], 0u};
-    rows += seg_rows[g];
-    f_max = std::max(f_max, seg_rows[g]);
-  }
+  const uint64_t f_max = row_segs_fill(seg, S, seg_rows, nullptr, 1u).f_max;
   if (f_max == 0) return VSYN_OK;
   HIPCHK(hipSetDevice(device));
   if (int rc = ws.tab_onset.upload(tab, s, err)) return rc;
@@ -419,8 +390,7 @@ static inline int onset_launch(RhythmWs& ws, int device, const vsyn_onset_spec* 
   A.lag = p->lag;
   A.m = p->max_size;
   A.p = (p->options & VSYN_ONSET_CENTER) ? (uint32_t)(p->n_fft / (2ull * p->hop_length)) : 0u;
-  hipLaunchKernelGGL(vsyn_onset_kernel, dim3((uint32_t)((f_max + ONS_FT - 1u) / ONS_FT), S), dim3(RHY_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_onset_kernel, dim3((uint32_t)((f_max + ONS_FT - 1u) / ONS_FT), S), dim3(RHY_THREADS), 0, s, A);
   return VSYN_OK;
 }
 
@@ -496,14 +466,11 @@ static inline int peaks_launch(RhythmWs& ws, int device, const vsyn_onset_peaks*
   A.refused = d_refused;
   A.delta = p->delta;
   A.normalize = (p->options & VSYN_PEAKS_NORMALIZE) ? 1u : 0u;
-  hipLaunchKernelGGL(vsyn_peaks_minmax_kernel, dim3(S), dim3(RHY_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_peaks_minmax_kernel, dim3(S), dim3(RHY_THREADS), 0, s, A);
   if (f_max) {
-    hipLaunchKernelGGL(vsyn_peaks_cand_kernel, dim3((uint32_t)((f_max + RHY_THREADS - 1u) / RHY_THREADS), S), dim3(RHY_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_peaks_cand_kernel, dim3((uint32_t)((f_max + RHY_THREADS - 1u) / RHY_THREADS), S), dim3(RHY_THREADS), 0, s, A);
   }
-  hipLaunchKernelGGL(vsyn_peaks_walk_kernel, dim3(S), dim3(64), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_peaks_walk_kernel, dim3(S), dim3(64), 0, s, A);
   return VSYN_OK;
 }
 
@@ -566,13 +533,7 @@ static inline int tg_launch(RhythmWs& ws, int device, const vsyn_tempogram_spec*
     sg.row_off = row_off;
     sg.part_off = part_off;
     sg.mean_off = mean_off;
-    size_t k = 0;
-    while (k < wins.size() && wins[k].first != sg.W) ++k;
-    if (k == wins.size()) {
-      wins.push_back(std::make_pair(sg.W, win_floats));
-      win_floats += sg.W;
-    }
-    sg.win_off = wins[k].second;
+    sg.win_off = table_slot(wins, sg.W, &win_floats, sg.W);
     memcpy(tab.data() + sizeof(TgSeg) * (size_t)g, &sg, sizeof(sg));
     off += seg_rows[g];
     row_off += (uint64_t)sg.Fp * sg.W;
@@ -587,10 +548,7 @@ static inline int tg_launch(RhythmWs& ws, int device, const vsyn_tempogram_spec*
   for (const auto& wk : wins)
     for (uint32_t n = 0; n < wk.first; ++n) win[wk.second + n] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)n / (double)wk.first));
   HIPCHK(hipSetDevice(device));
-  if (!ws.lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_tempogram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tg_lds_bytes(TG_ILP, TG_MAX_W)));
-    ws.lds_set = true;
-  }
+  if (int rc = raise_lds_once(ws.lds_set, {{(const void*)vsyn_tempogram_kernel, tg_lds_bytes(TG_ILP, TG_MAX_W)}}, err)) return rc;
   if (d_mean) HIPCHK(ws.part.ensure(part_off + 1u));
   if (int rc = ws.tab_tg.upload(tab, s, err)) return rc;
   TgCtx A;
@@ -603,12 +561,10 @@ static inline int tg_launch(RhythmWs& ws, int device, const vsyn_tempogram_spec*
   A.center = center ? 1u : 0u;
   A.norm = (p->options & VSYN_TG_NORM_INF) ? 1u : 0u;
   if (nb_max) {
-    hipLaunchKernelGGL(vsyn_tempogram_kernel, dim3(nb_max, S), dim3(RHY_THREADS), lds, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_tempogram_kernel, dim3(nb_max, S), dim3(RHY_THREADS), lds, s, A);
   }
   if (d_mean && w_max) {  // (w_max = 0: every segment is skipped)
-    hipLaunchKernelGGL(vsyn_tempogram_mean_kernel, dim3((w_max + RHY_THREADS - 1u) / RHY_THREADS, S), dim3(RHY_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_tempogram_mean_kernel, dim3((w_max + RHY_THREADS - 1u) / RHY_THREADS, S), dim3(RHY_THREADS), 0, s, A);
   }
   return VSYN_OK;
 }

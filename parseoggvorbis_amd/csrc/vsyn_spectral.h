@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_spec_stft_kernel(const Spec
     }
   }
   if (kind >= VSYN_SPEC_MEL_DB) {
-    mx = frames_wave_max(mx);
+    mx = wave_max(mx);
     if ((tid & 63u) == 0 && mx > -INFINITY) atomicMax(A.segmax + g, spec_key(mx));
   }
 }
@@ -353,13 +353,11 @@ static inline void spec_build_table(const vsyn_spectral_spec* sp, uint32_t S, co
 // The mel kinds' kernels behind the offsets kernel: STFT / mel on grid with ft frames per workgroup, and the (MEL_DB, MFCC) finish.
 static inline int spec_mel_run(const SpecCtx& A, const vsyn_spectral_spec* sp, uint32_t ft, dim3 grid, uint64_t f_max, hipStream_t s, const char** err) {
   const size_t lds = spec_lds_floats(ft, sp->n_fft, sp->hop_length, sp->n_mels) * 4u;
-  if (ft == 16) hipLaunchKernelGGL(vsyn_spec_stft_kernel<16>, grid, dim3(SPEC_THREADS), lds, s, A);
-  else if (ft == 4) hipLaunchKernelGGL(vsyn_spec_stft_kernel<4>, grid, dim3(SPEC_THREADS), lds, s, A);
-  else hipLaunchKernelGGL(vsyn_spec_stft_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
-  HIPCHK(hipGetLastError());
+  if (ft == 16) VSYN_LAUNCH(vsyn_spec_stft_kernel<16>, grid, dim3(SPEC_THREADS), lds, s, A);
+  else if (ft == 4) VSYN_LAUNCH(vsyn_spec_stft_kernel<4>, grid, dim3(SPEC_THREADS), lds, s, A);
+  else VSYN_LAUNCH(vsyn_spec_stft_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
   if (sp->kind >= VSYN_SPEC_MEL_DB) {
-    hipLaunchKernelGGL(vsyn_spec_finish_kernel, dim3((uint32_t)((f_max + SPEC_FIN_ROWS - 1) / SPEC_FIN_ROWS), grid.y), dim3(SPEC_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_spec_finish_kernel, dim3((uint32_t)((f_max + SPEC_FIN_ROWS - 1) / SPEC_FIN_ROWS), grid.y), dim3(SPEC_THREADS), 0, s, A);
   }
   return VSYN_OK;
 }

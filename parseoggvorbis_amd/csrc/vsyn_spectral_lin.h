@@ -55,7 +55,7 @@ __device__ __forceinline__ float spec_lin_emit(const SpecHeader* H, float* rows,
 }
 
 __device__ __forceinline__ void spec_lin_seg_max(const SpecCtx& A, uint32_t g, float mx) {
-  mx = frames_wave_max(mx);
+  mx = wave_max(mx);
   if ((threadIdx.x & 63u) == 0 && mx > -INFINITY) atomicMax(A.segmax + g, spec_key(mx));
 }
 
@@ -206,17 +206,15 @@ static inline uint32_t spec_lin_lgm(uint32_t n) {
 static inline int spec_lin_run(const SpecCtx& A, const vsyn_spectral_spec* sp, uint32_t ft, dim3 grid, uint64_t f_max, hipStream_t s, const char** err) {
   const uint32_t n = sp->n_fft;
   if (spec_lin_pow2(n)) {
-    hipLaunchKernelGGL(vsyn_spec_lin_fft_kernel, grid, dim3(SPEC_THREADS), spec_lin_fft_lds_floats(ft, n) * 4u, s, A, ft, spec_lin_lgm(n));
+    VSYN_LAUNCH(vsyn_spec_lin_fft_kernel, grid, dim3(SPEC_THREADS), spec_lin_fft_lds_floats(ft, n) * 4u, s, A, ft, spec_lin_lgm(n));
   } else {
     const size_t lds = spec_lin_direct_lds_floats(ft, n, sp->hop_length) * 4u;
-    if (ft == SPEC_LIN_DIRECT_FT) hipLaunchKernelGGL(vsyn_spec_lin_direct_kernel<SPEC_LIN_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
-    else hipLaunchKernelGGL(vsyn_spec_lin_direct_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
+    if (ft == SPEC_LIN_DIRECT_FT) VSYN_LAUNCH(vsyn_spec_lin_direct_kernel<SPEC_LIN_DIRECT_FT>, grid, dim3(SPEC_THREADS), lds, s, A);
+    else VSYN_LAUNCH(vsyn_spec_lin_direct_kernel<1>, grid, dim3(SPEC_THREADS), lds, s, A);
   }
-  HIPCHK(hipGetLastError());
   if (sp->kind == VSYN_SPEC_LIN_DB && sp->top_db > 0.0) {
     const uint64_t cx = std::min<uint64_t>((f_max * (n / 2u + 1u) + SPEC_THREADS - 1) / SPEC_THREADS, 4096);
-    hipLaunchKernelGGL(vsyn_spec_lin_clamp_kernel, dim3((uint32_t)cx, grid.y), dim3(SPEC_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_spec_lin_clamp_kernel, dim3((uint32_t)cx, grid.y), dim3(SPEC_THREADS), 0, s, A);
   }
   return VSYN_OK;
 }

@@ -29,11 +29,7 @@
 #define POST_RED_COLS 16u    // ... and columns per workgroup (POST_RED_CHAINS * POST_RED_COLS = POST_THREADS)
 #define POST_COEF_FLOATS 132u  // LDS floats in front of the tile's rows: two coefficient vectors of up to 65
 
-struct PostSeg {
-  uint64_t off;  // first row of the segment in the row buffers
-  uint64_t blk;  // first block of the segment in the partials
-  uint32_t F, pad;
-};
+typedef RowBlkSeg PostSeg;  // blk: the segment's first block in the partials
 
 struct PostCtx {  // launch arguments
   const PostSeg* seg;
@@ -48,18 +44,7 @@ struct PostCtx {  // launch arguments
   double std_floor;
 };
 
-// Thread layout over a tile: wd lanes along the columns, G = POST_THREADS / wd row groups; group ty takes blocks ty, ty + G, ...
-struct PostLane {
-  uint32_t wd, G, ty, tx;
-};
-__device__ __forceinline__ PostLane post_lane(uint32_t Dout) {
-  PostLane L;
-  L.wd = min(Dout, (uint32_t)POST_THREADS);
-  L.G = POST_THREADS / L.wd;
-  L.ty = threadIdx.x / L.wd;
-  L.tx = threadIdx.x - L.ty * L.wd;
-  return L;
-}
+// Thread layout over a tile (row_lane): group ty takes blocks ty, ty + G, ...
 __device__ __forceinline__ uint32_t post_clamp(uint32_t f, uint32_t lo, uint32_t hi) { return min(max(f, lo), hi); }
 
 __global__ void __launch_bounds__(POST_THREADS) vsyn_post_delta_kernel(const PostCtx A) {
@@ -78,7 +63,7 @@ __global__ void __launch_bounds__(POST_THREADS) vsyn_post_delta_kernel(const Pos
   if (A.order)
     for (uint32_t i = tid; i < A.order * W; i += POST_THREADS) s_c[i] = A.coef[i];
   __syncthreads();
-  const PostLane L = post_lane(Dout);
+  const RowLane L = row_lane<POST_THREADS>(Dout);
   if (L.ty >= L.G) return;
   const uint32_t nblk = (nrows + POST_BLK - 1u) / POST_BLK;
   for (uint32_t b = L.ty; b < nblk; b += L.G) {
@@ -111,7 +96,7 @@ __global__ void __launch_bounds__(POST_THREADS) vsyn_post_moment_kernel(const Po
   const uint32_t F = sg.F, f0 = blockIdx.x * A.tile, Dout = A.Dout;
   if (f0 >= F) return;
   const uint32_t nrows = min(A.tile, F - f0);
-  const PostLane L = post_lane(Dout);
+  const RowLane L = row_lane<POST_THREADS>(Dout);
   if (L.ty >= L.G) return;
   const double* mu = A.mu + (size_t)blockIdx.y * A.stat_stride;
   const uint32_t nblk = (nrows + POST_BLK - 1u) / POST_BLK;
@@ -165,7 +150,7 @@ __global__ void __launch_bounds__(POST_THREADS) vsyn_post_norm_kernel(const Post
   const uint32_t F = sg.F, f0 = blockIdx.x * A.tile, Dout = A.Dout;
   if (f0 >= F) return;
   const uint32_t nrows = min(A.tile, F - f0);
-  const PostLane L = post_lane(Dout);
+  const RowLane L = row_lane<POST_THREADS>(Dout);
   if (L.ty >= L.G) return;
   const size_t s0 = (size_t)blockIdx.y * A.stat_stride;
   const uint32_t nblk = (nrows + POST_BLK - 1u) / POST_BLK;
@@ -243,13 +228,8 @@ static inline int post_launch(PostWs& ws, int device, const vsyn_spectral_post* 
   const size_t off_stat = sizeof(PostSeg) * S, off_coef = off_stat + (given ? 16ull * Dout : 0ull);
   std::vector<uint8_t> tab(off_coef + 8ull * W);
   PostSeg* seg = (PostSeg*)tab.data();
-  uint64_t rows = 0, blocks = 0, f_max = 0;
-  for (uint32_t g = 0; g < S; ++g) {
-    seg[g] = PostSeg{rows, blocks, (uint32_t)seg_rows[g], 0u};
-    rows += seg_rows[g];
-    blocks += (seg_rows[g] + POST_BLK - 1u) / POST_BLK;
-    f_max = std::max(f_max, seg_rows[g]);
-  }
+  const RowTotals t = row_segs_fill(seg, S, seg_rows, nullptr, POST_BLK);
+  const uint64_t blocks = t.blocks, f_max = t.f_max;
   if (f_max == 0) return VSYN_OK;
   if (given) {
     double* st = (double*)(tab.data() + off_stat);
@@ -277,10 +257,7 @@ static inline int post_launch(PostWs& ws, int device, const vsyn_spectral_post* 
   const uint32_t tile = nb * POST_BLK;
   const size_t lds = lds_of(nb);
   HIPCHK(hipSetDevice(device));
-  if (!ws.lds_set) {
-    HIPCHK(hipFuncSetAttribute((const void*)vsyn_post_delta_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
-    ws.lds_set = true;
-  }
+  if (int rc = raise_lds_once(ws.lds_set, {{(const void*)vsyn_post_delta_kernel, SPEC_LDS_BUDGET}}, err)) return rc;
   const bool seg_stats = norm && !given;
   if (seg_stats) {
     HIPCHK(ws.part.ensure(blocks * Dout));
@@ -304,21 +281,16 @@ static inline int post_launch(PostWs& ws, int device, const vsyn_spectral_post* 
   A.std_floor = p->std_floor;
   const uint64_t gx = (f_max + tile - 1u) / tile;
   const dim3 grid((uint32_t)gx, S), rgrid((Dout + POST_RED_COLS - 1u) / POST_RED_COLS, S);
-  hipLaunchKernelGGL(vsyn_post_delta_kernel, grid, dim3(POST_THREADS), lds, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_post_delta_kernel, grid, dim3(POST_THREADS), lds, s, A);
   if (seg_stats) {
-    hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 0u);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 0u);
     if (var) {
-      hipLaunchKernelGGL(vsyn_post_moment_kernel, grid, dim3(POST_THREADS), 0, s, A);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 1u);
-      HIPCHK(hipGetLastError());
+      VSYN_LAUNCH(vsyn_post_moment_kernel, grid, dim3(POST_THREADS), 0, s, A);
+      VSYN_LAUNCH(vsyn_post_reduce_kernel, rgrid, dim3(POST_THREADS), 0, s, A, 1u);
     }
   }
   if (norm) {
-    hipLaunchKernelGGL(vsyn_post_norm_kernel, grid, dim3(POST_THREADS), 0, s, A);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_post_norm_kernel, grid, dim3(POST_THREADS), 0, s, A);
   }
   return VSYN_OK;
 }

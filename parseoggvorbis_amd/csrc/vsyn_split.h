@@ -10,7 +10,7 @@
 //                               positions f = 0 .. F (F itself stands for the silent frame behind the last one), SPLIT_CHUNK
 //                               positions at a time: a thread owns SPLIT_PER consecutive positions, evaluates the predicate for
 //                               f - 1 and each of them (no exchange for the edges), and counts its edges (loud(f) != loud(f - 1))
-//                               and its non-silent frames; the two counts go through an inclusive wave scan (__shfl_up), the four
+//                               and its non-silent frames; the two counts go through an inclusive wave scan (wave_scan), the four
 //                               waves' totals through LDS, and a carry runs from chunk to chunk in a register every thread keeps.
 //                               Edges alternate rising, falling, from a rising one: the edge with e edges in front of it is word e
 //                               of the segment's interval array, (start_0, end_0, start_1, ...), and holds min(f H, T). The
@@ -81,15 +81,7 @@ __global__ void __launch_bounds__(TRIM_THREADS) vsyn_split_mark_kernel(const Spl
       nl += loud[i] ? 1u : 0u;
       prev = loud[i];
     }
-    uint32_t se = ne, sl = nl;  // inclusive scan through the wave
-#pragma unroll
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-      const uint32_t ue = __shfl_up(se, o), ul = __shfl_up(sl, o);
-      if (lane >= o) {
-        se += ue;
-        sl += ul;
-      }
-    }
+    const uint32_t se = wave_scan(ne), sl = wave_scan(nl);  // inclusive
     if (lane == 63u) {
       s_e[set][wave] = se;
       s_l[set][wave] = sl;
@@ -208,12 +200,10 @@ static inline int split_launch(SplitWs& ws, int device, const vsyn_pcm_trim* tr,
   B.iv = d_iv;
   B.iv_stride = iv_stride;
   B.hops = ws.hops.p;
-  hipLaunchKernelGGL(vsyn_split_mark_kernel, dim3(S), dim3(TRIM_THREADS), 0, s, B);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_split_mark_kernel, dim3(S), dim3(TRIM_THREADS), 0, s, B);
   if (d_out) {
     const uint64_t gx = (B.t.t_cap + 3u + SPLIT_TILE - 1u) / SPLIT_TILE;
-    hipLaunchKernelGGL(vsyn_split_gather_kernel, dim3((uint32_t)gx, S), dim3(TRIM_THREADS), 0, s, B);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_split_gather_kernel, dim3((uint32_t)gx, S), dim3(TRIM_THREADS), 0, s, B);
   }
   return VSYN_OK;
 }

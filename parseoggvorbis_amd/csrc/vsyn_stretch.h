@@ -171,8 +171,7 @@ static inline int stretch_launch(SpectralWs& sp, PvWs& pv, IstftWs& is, StretchW
   }
   if (fix && (out_max || d_out_frames)) {
     const dim3 grid((uint32_t)std::max<uint64_t>((out_max + 255u) / 256u, 1), S);
-    hipLaunchKernelGGL(vsyn_stretch_deliver_kernel, grid, dim3(256), 0, s, last, last_plane, d_frames + S, S, d_out, out_plane, d_out_frames);
-    HIPCHK(hipGetLastError());
+    VSYN_LAUNCH(vsyn_stretch_deliver_kernel, grid, dim3(256), 0, s, last, last_plane, d_frames + S, S, d_out, out_plane, d_out_frames);
   }
   return VSYN_OK;
 }

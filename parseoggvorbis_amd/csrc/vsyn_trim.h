@@ -7,7 +7,7 @@
 //                               from HBM. H <= L: one contiguous span of (FT - 1) H + L samples; H > L (frames that do not touch):
 //                               the FT frames back to back, L samples each. The four waves take the tile's frames in turn; lane l
 //                               of a wave adds the squares of the frame's samples l, l + 64, ... in float64, in ascending order,
-//                               and a fixed __shfl_xor butterfly (offsets 32, 16, .. 1) makes the frame's sum: its order is a
+//                               and wave_sum (the butterfly of DESIGN.md 6t) makes the frame's sum: its order is a
 //                               function of L alone, whatever the tile, the grid and the segment's slot. ms[f] = sum / L goes to
 //                               the workspace and to the caller's d_ms. The workgroup also looks at every sample of its share of
 //                               the segment (the hops of its frames; the last tile up to T) for an Inf or a NaN, also where no
@@ -15,7 +15,7 @@
 //   2. vsyn_trim_bounds_kernel  one workgroup per segment, behind a finished ms array: the maximum of ms[g][0 .. F) on the doubles'
 //                               bit patterns with the sign masked (a maximum has no order; NaN > Inf > finite), the tiles' flags,
 //                               then the first and last frame with E = max(ms, 1e-10) > R k (or E >= R) by integer min / max through the wave
-//                               (__shfl_xor) and the four waves (LDS). Writes (start, end), out_frames and R. No atomics.
+//                               and the four waves (vsyn_wave.h). Writes (start, end), out_frames and R. No atomics.
 //   3. vsyn_trim_cut_kernel     grid (tile of TRIM_CUT_TILE frames, segment): out[t] = downmix(start + t) for t < end - start.
 // Memory access of the cut kernel: a thread owns four output frames that start at a 16-byte boundary of the OUTPUT plane (a
 // scalar head and tail around them). start is a multiple of H and otherwise arbitrary, so whether the four input frames of every
@@ -27,6 +27,7 @@
 #include "vsyn_condition.h"
 #include "vsyn_device.h"
 #include "vsyn_host.h"
+#include "vsyn_wave.h"
 
 #define TRIM_THREADS 256
 #define TRIM_WAVES (TRIM_THREADS / 64)
@@ -126,7 +127,7 @@ __global__ void __launch_bounds__(TRIM_THREADS) vsyn_trim_energy_kernel(const Tr
       const double v = (double)fr[i];
       acc += v * v;
     }
-    for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum(acc);
     if (lane == 0) {
       const double m = acc / (double)L;
       A.ms[(size_t)g * A.F_max + f0 + j] = m;
@@ -135,15 +136,6 @@ __global__ void __launch_bounds__(TRIM_THREADS) vsyn_trim_energy_kernel(const Tr
   }
   __syncthreads();
   if (tid == 0) A.flags[(size_t)g * A.tiles + blockIdx.x] = s_bad;
-}
-
-__device__ __forceinline__ uint64_t trim_wave_max(uint64_t v) {
-  for (int o = 32; o; o >>= 1) v = trim_max64(v, (uint64_t)__shfl_xor((unsigned long long)v, o));
-  return v;
-}
-__device__ __forceinline__ uint64_t trim_wave_min(uint64_t v) {
-  for (int o = 32; o; o >>= 1) v = trim_min64(v, (uint64_t)__shfl_xor((unsigned long long)v, o));
-  return v;
 }
 
 // The reference of segment g behind its finished ms array, for a whole workgroup of TRIM_THREADS (s_a: TRIM_WAVES words of LDS, free
@@ -156,12 +148,7 @@ __device__ __forceinline__ uint64_t trim_segment_max(const TrimCtx& A, uint32_t 
   for (uint64_t f = tid; f < F; f += TRIM_THREADS) mx = trim_max64(mx, (uint64_t)__double_as_longlong(ms[f]) & TRIM_ABS64);
   for (uint32_t i = tid; i < tiles; i += TRIM_THREADS)
     if (A.flags[(size_t)g * A.tiles + i]) mx = trim_max64(mx, TRIM_NOT_FINITE64 | 0x0008000000000000ull);
-  mx = trim_wave_max(mx);
-  if ((tid & 63u) == 0) s_a[tid >> 6] = mx;
-  __syncthreads();
-  mx = trim_max64(trim_max64(s_a[0], s_a[1]), trim_max64(s_a[2], s_a[3]));
-  __syncthreads();
-  return mx;
+  return wg_reduce_all<TRIM_WAVES>(mx, s_a, WaveMax(), 0ull);
 }
 __device__ __forceinline__ bool trim_refused(uint64_t mx) { return mx >= TRIM_NOT_FINITE64; }
 __device__ __forceinline__ double trim_ref(uint64_t mx) {
@@ -192,16 +179,12 @@ __global__ void __launch_bounds__(TRIM_THREADS) vsyn_trim_bounds_kernel(const Tr
       }
     }
   }
-  first = trim_wave_min(first);
-  lastf = trim_wave_max(lastf);
-  if ((tid & 63u) == 0) {
-    s_a[tid >> 6] = first;
-    s_b[tid >> 6] = lastf;
-  }
+  wg_put(first, s_a, WaveMin());  // (one barrier for the two)
+  wg_put(lastf, s_b, WaveMax());
   __syncthreads();
   if (tid == 0) {
-    first = trim_min64(trim_min64(s_a[0], s_a[1]), trim_min64(s_a[2], s_a[3]));
-    lastf = trim_max64(trim_max64(s_b[0], s_b[1]), trim_max64(s_b[2], s_b[3]));
+    first = wg_get<TRIM_WAVES>(s_a, WaveMin(), ~0ull);
+    lastf = wg_get<TRIM_WAVES>(s_b, WaveMax(), 0ull);
     uint64_t start = 0, end = 0;
     if (lastf) {  // (F >= 1 and not refused: the frame that holds the maximum is there)
       start = first * A.H;
@@ -326,8 +309,7 @@ static inline int trim_energy_launch(TrimWs& ws, int device, const vsyn_pcm_trim
   A.ref = d_ref;
   const uint32_t fstep = std::min(L, H);
   const size_t lds = sizeof(float) * ((size_t)(ft - 1u) * fstep + L);
-  hipLaunchKernelGGL(vsyn_trim_energy_kernel, dim3((uint32_t)tiles, S), dim3(TRIM_THREADS), lds, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_trim_energy_kernel, dim3((uint32_t)tiles, S), dim3(TRIM_THREADS), lds, s, A);
   return VSYN_OK;
 }
 
@@ -347,10 +329,8 @@ static inline int trim_launch(TrimWs& ws, int device, const vsyn_pcm_trim* tr, u
                                   ms_stride, s, &A, err))
     return rc;
   const uint64_t gx = (A.t_cap + 3u + TRIM_CUT_TILE - 1u) / TRIM_CUT_TILE;
-  hipLaunchKernelGGL(vsyn_trim_bounds_kernel, dim3(S), dim3(TRIM_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(vsyn_trim_cut_kernel, dim3((uint32_t)gx, S), dim3(TRIM_THREADS), 0, s, A);
-  HIPCHK(hipGetLastError());
+  VSYN_LAUNCH(vsyn_trim_bounds_kernel, dim3(S), dim3(TRIM_THREADS), 0, s, A);
+  VSYN_LAUNCH(vsyn_trim_cut_kernel, dim3((uint32_t)gx, S), dim3(TRIM_THREADS), 0, s, A);
   return VSYN_OK;
 }
 
