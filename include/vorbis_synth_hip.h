@@ -1110,7 +1110,7 @@ int vsyn_pcm_split_spectral_pcen_host(vsyn_handle* h, const vsyn_pcm_trim* trim,
  *     trough_threshold finite; 0 < fmin < fmax <= sr / 2 and n >= 2 for every segment's rate; 0 < trough_threshold <= 1. A rate
  *     of 0 skips the segment (0 rows).
  *
- * Not built: pYIN, a win_length other than L / 2, composition with the trim, split and conditioning stages. The same PCM gives the
+ * Not built: a win_length other than L / 2, composition with the trim, split and conditioning stages. The same PCM gives the
  * same bits, alone, in any slot of a batch and at any alignment. The pitch entry points read PCM only: they touch neither stream
  * state, the overlap buffers nor the PCM kept by VSYN_SUBMIT_KEEP_PCM, and a later vsyn_pcm_fetch_host returns the same PCM. One
  * handle's pitch entry points share its pitch workspace, which is no other stage's. */
@@ -1146,6 +1146,109 @@ int vsyn_pitch_device(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t num_
 int vsyn_pcm_pitch_host(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
                         float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
                         const char** err);
+
+/* ---- pyin: voiced flags, voicing probabilities and a Viterbi-decoded fundamental frequency (pYIN), computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, and its sample rate sr. Parameters: frame_length L,
+ * hop_length H, fmin, fmax, n_thresholds N, the caller's table beta_probs[N], boltzmann_parameter lam, resolution,
+ * max_transition_rate, switch_prob s, no_trough_prob, VSYN_PYIN_CENTER. Output: a float32 matrix (F, 3), one row per frame: f0 in
+ * Hz (the decoded pitch bin's frequency, written for unvoiced frames too), voiced (1.0 or 0.0) and voiced_prob. This is
+ * librosa.pyin(y, fmin, fmax, sr, frame_length=L, win_length=L / 2, hop_length=H, n_thresholds, beta_parameters,
+ * boltzmann_parameter, resolution, max_transition_rate, switch_prob, no_trough_prob, center, pad_mode="constant") (librosa >= 0.10)
+ * on the mono signal, before fill_na, which the caller applies. librosa is not among the test dependencies and parity with it is
+ * not claimed: the device is compared against a float64 model of the arithmetic below (tests/pyin_model.py), and the model against
+ * a restatement in librosa's own words (tests/test_pyin_cpu.py). tiny = 2.2250738585072014e-308 throughout.
+ *
+ *  1. Shared steps. Mono, framing, the periods p_min .. p_max, the difference function d and c[i], i < n, are steps 1 to 5 of
+ *     "pitch", bit for bit: one device function, called by both kernels.
+ *  2. Troughs: trough[i] of "pitch" step 6, its end rules included. The troughs in ascending lag are i_0 < i_1 < .. < i_(K-1), with
+ *     heights h_k = c[i_k]. A frame without a trough has no voiced observation.
+ *  3. Thresholds: t_m = m * (1.0 / N) for 1 <= m < N and t_N = 1 (numpy.linspace(0, 1, N + 1)[1:] bit for bit; m / N is not).
+ *     beta_probs[m], m = 1 .. N, are the differences of the Beta(a, b) distribution function at 0, t_1, .. t_N: the caller's table
+ *     of N doubles (threshold_probs); this library has no incomplete-beta routine.
+ *  4. Trough probabilities. below(k, m) = h_k < t_m; n_m = #{k : below(k, m)}; pos(k, m) = #{k' <= k : below(k', m)} - 1;
+ *     prior(k, m) = ((1 - e^-lam) / (1 - e^(-lam n_m))) * e^(-lam pos(k, m)) (scipy.stats.boltzmann.pmf, in this order);
+ *     P_k = sum_m below(k, m) * (prior(k, m) * beta_probs[m]): one float64 chain with m ascending. With g the first index of the
+ *     minimum of h: P_g += no_trough_prob * (sum of beta_probs[m] over the m with not below(g, m), m ascending). No atomics: the
+ *     same PCM gives the same bits. The work is O(K N).
+ *  5. Candidates. Every trough with P_k > 0 gives period = p_min + i_k + shift(i_k) (shift: "pitch" step 7), f0 = sr / period,
+ *     bin = clip(rint(12 bps log2(f0 / fmin)), 0, B), round half even, with bps = ceil(1 / resolution) and B = floor(12 bps
+ *     log2(fmax / fmin)) + 1 computed in double on the host (vsyn_pyin_num_bins). A candidate at bin == B is dropped (librosa's
+ *     clip to n_pitch_bins, whose slot its unvoiced fill overwrites). Of several candidates in one bin the one with the LARGEST lag
+ *     gives the bin's value (numpy's last assignment). obs[f][b], b < B, is that value, else 0.
+ *     vp[f] = clip(sum_b obs[f][b], 0, 1), b ascending in float64. Every unvoiced state observes (1 - vp[f]) / B.
+ *  6. Transitions. msf = round(max_transition_rate * 12 * H / sr) (half even, Python's round) per segment rate; w = msf bps + 1.
+ *     An EVEN w is refused (VSYN_ERR_INVALID): librosa's pad_center and roll make that case asymmetric and dependent on the parity
+ *     of B; a stated divergence, which needs a resolution other than the default. With h = w / 2: loc[i][j] = ((w + 1) / 2 - |j - i|)
+ *     / ((w + 1) / 2) for |j - i| <= h and 0 <= j < B, else 0 (scipy.signal.get_window("triangle", w, fftbins=False)); each row is
+ *     divided by its sum, added from the outside in, the two entries of a distance first (sum += loc[i][i-d] + loc[i][i+d] for
+ *     d = h .. 1, then loc[i][i]), so that the mirror rows i and B - 1 - i hold the same bits. The state of voicing v (0 voiced, 1 unvoiced) and bin i has index v B + i.
+ *     trans = kron([[1 - s, s], [s, 1 - s]], loc), and the Viterbi uses log(trans + tiny): outside the band that is log(tiny), about
+ *     -708.4, NOT -inf, and it is evaluated: a clean tone has vp == 1 exactly, so its unvoiced observations are log(tiny) too, and
+ *     its back pointers do leave the band. The out-of-band term of a target is the maximum of value + log(tiny) over the states
+ *     outside its band, taken from prefix and suffix maxima per frame, not from a dense (2B)^2 sweep. Interior rows (h <= i < B - h)
+ *     are translates of one row; the log table is built on the host in double. vsyn_pyin_transition returns it without a device.
+ *  7. Viterbi (librosa.sequence.viterbi). value[0][s] = log(obs[0][s] + tiny) + log(1 / (2B) + tiny);
+ *     value[t][s'] = log(obs[t][s'] + tiny) + max_s (value[t-1][s] + log_trans[s][s']); the back pointer is the LOWEST s that
+ *     attains the maximum (np.argmax); the last state is the lowest arg-max of the last frame's values; then the back pointers are
+ *     walked. Every maximum is taken under the total order "greater value, then lower state", so no grouping changes it. One
+ *     workgroup per segment, frames in sequence; value ping-pongs in LDS as float64. 2B <= VSYN_PYIN_MAX_STATES.
+ *  8. Row f: column 0 = float32(fmin * 2^((state mod B) / (12 bps))) from a host table in double; column 1 = state < B;
+ *     column 2 = float32(vp[f]).
+ *  9. Not finite and skipped segments: as "pitch" step 9, a segment with an Inf or NaN sample is refused alone (its F rows NaN,
+ *     its refused word 1; its observations are not decoded). A rate of 0 or T = 0 gives 0 rows.
+ * 10. Checks (VSYN_ERR_INVALID before anything runs): those of "pitch" step 10 without the threshold; 1 <= N <= 1024; threshold_probs
+ *     not NULL, every entry finite and >= 0; lam > 0 and finite; 0 < resolution < 1; max_transition_rate > 0 and finite;
+ *     0 < switch_prob < 1; 0 <= no_trough_prob <= 1; 2B <= VSYN_PYIN_MAX_STATES; w odd for every segment's rate.
+ *
+ * Memory. Between the two kernels the observations are a dense float64 matrix (F, B) per segment in the stage's own workspace, and
+ * the back pointers take 2 bytes per state and frame: 8 F B + 4 F B bytes a segment (and 8 F for vp), about 3 MB for 10 s at the
+ * defaults (F = 431, B = 601). Not built: a sparse form of the observations; an even w; a win_length other than L / 2. The same PCM
+ * gives the same bits, alone, in any slot of a batch and at any alignment. The entry points read PCM only, as the pitch stage's do,
+ * and share the handle's pyin workspace, which is no other stage's. */
+#define VSYN_PYIN_CENTER 1u /* pad frame_length/2 zeros on both sides (librosa's center=True) */
+#define VSYN_PYIN_MAX_STATES 4096u
+
+typedef struct vsyn_pyin_spec {
+  uint32_t frame_length; /* L */
+  uint32_t hop_length;   /* H */
+  uint32_t options;      /* VSYN_PYIN_* bits */
+  uint32_t n_thresholds; /* N */
+  double fmin, fmax;     /* Hz */
+  double boltzmann_parameter, resolution, max_transition_rate, switch_prob, no_trough_prob;
+  const double* threshold_probs; /* beta_probs[N] of step 3 (host) */
+} vsyn_pyin_spec;
+
+/* F of step 1 for a segment of `frames` PCM frames, 0 for an invalid spec (the checks of step 10 that need no rate). */
+uint64_t vsyn_pyin_num_frames(const vsyn_pyin_spec* spec, uint64_t frames);
+
+/* B of step 5, 0 for an invalid spec. */
+uint32_t vsyn_pyin_num_bins(const vsyn_pyin_spec* spec);
+
+/* Host only, no device and no handle: w of step 6 at rate sample_rate into *width_out and B into *bins_out (either may be NULL), and,
+ * when table is not NULL, the log table of step 6: table[(i * w + k) * 2 + x] for the source bin i < B, the target bin j = i + k - h,
+ * k < w, and x = 0 for the same voicing (log((1 - s) loc[i][j] + tiny)), 1 for the other (log(s loc[i][j] + tiny)); log(tiny) where
+ * j is outside [0, B). table_capacity counts doubles: VSYN_ERR_INVALID (with w and B filled) below B * w * 2. */
+int vsyn_pyin_transition(const vsyn_pyin_spec* spec, uint32_t sample_rate, uint32_t* width_out, uint32_t* bins_out, double* table,
+                         uint64_t table_capacity, const char** err);
+
+/* The caller's planar PCM, as for vsyn_pitch_device; d_rows holds rows of 3 columns. */
+int vsyn_pyin_device(vsyn_handle* h, const vsyn_pyin_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
+                     const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows,
+                     uint64_t* d_seg_row_off, uint32_t* d_refused, void* hip_stream, const char** err);
+
+/* The Viterbi of steps 6 and 7 alone, the second kernel of vsyn_pyin_device: d_obs (device, float64) holds the caller's dense
+ * observation rows (seg_rows[g], B) of the segments back to back, every value finite and in [0, 1] (other values give states in
+ * range that mean nothing); vp of a frame is step 5's clipped sum of its row. seg_rows[S] and sample_rates[S] are HOST arrays; a
+ * rate of 0 skips the segment (its rows are still counted in the offsets). Writes d_states (device, uint32): the state of every
+ * frame, back to back as the rows are. Asynchronous on hip_stream. */
+int vsyn_pyin_decode_device(vsyn_handle* h, const vsyn_pyin_spec* spec, uint32_t num_segments, const uint32_t* sample_rates,
+                            const double* d_obs, const uint64_t* seg_rows, uint32_t* d_states, void* hip_stream, const char** err);
+
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle, as for vsyn_pcm_pitch_host; rows of 3 columns. */
+int vsyn_pcm_pyin_host(vsyn_handle* h, const vsyn_pyin_spec* spec, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                       float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
+                       const char** err);
 
 /* ---- frame descriptors: energy, zero-crossing rate and spectral shape of the decoded PCM per frame, computed where the PCM is ----
  *

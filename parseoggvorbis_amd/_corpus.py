@@ -45,6 +45,7 @@ def load():
                                                             C.POINTER(binding.PcmTrim), C.c_int, vp, vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_intervals_corpus", [u32, C.POINTER(binding.PcmTrim), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pitch_corpus", [u32, C.POINTER(binding.PitchSpec), vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_pyin_corpus", [u32, C.POINTER(binding.PyinSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_fdesc_corpus", [u32, C.POINTER(binding.FdescSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus_loud", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
                                                        C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -148,6 +148,13 @@ class PitchSpec(C.Structure):  # vsyn_pitch_spec
                 ("fmin", C.c_double), ("fmax", C.c_double), ("trough_threshold", C.c_double)]
 
 
+class PyinSpec(C.Structure):  # vsyn_pyin_spec; threshold_probs points into the caller's float64 array, which must outlive the spec's use
+    _fields_ = [("frame_length", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32), ("n_thresholds", C.c_uint32),
+                ("fmin", C.c_double), ("fmax", C.c_double), ("boltzmann_parameter", C.c_double), ("resolution", C.c_double),
+                ("max_transition_rate", C.c_double), ("switch_prob", C.c_double), ("no_trough_prob", C.c_double),
+                ("threshold_probs", C.c_void_p)]
+
+
 class FdescSpec(C.Structure):  # vsyn_fdesc_spec
     _fields_ = [("n_fft", C.c_uint32), ("hop_length", C.c_uint32), ("win_length", C.c_uint32), ("options", C.c_uint32),
                 ("roll_percent", C.c_double), ("zcr_threshold", C.c_double), ("amin", C.c_double)]
@@ -298,6 +305,7 @@ _SYMBOLS = [
     "vsyn_pcm_split_spectral_host",
     "vsyn_spectral_pcen_b", "vsyn_spectral_pcen_device", "vsyn_pcm_trim_spectral_pcen_host", "vsyn_pcm_split_spectral_pcen_host",
     "vsyn_pitch_num_frames", "vsyn_pitch_device", "vsyn_pcm_pitch_host",
+    "vsyn_pyin_num_frames", "vsyn_pyin_num_bins", "vsyn_pyin_transition", "vsyn_pyin_device", "vsyn_pyin_decode_device", "vsyn_pcm_pyin_host",
     "vsyn_fdesc_num_frames", "vsyn_fdesc_device", "vsyn_pcm_fdesc_host",
     "vsyn_loudness_num_blocks", "vsyn_loudness_coefficients", "vsyn_loudness_powers", "vsyn_loudness_device", "vsyn_pcm_loudness_host",
     "vsyn_pcm_chain_host", "vsyn_pcm_chain_spectral_host",
@@ -422,6 +430,14 @@ def load():
     lib.vsyn_pitch_num_frames.restype = u64
     lib.vsyn_pitch_device.argtypes = [vp, C.POINTER(PitchSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_pitch_host.argtypes = [vp, C.POINTER(PitchSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_pyin_num_frames.argtypes = [C.POINTER(PyinSpec), u64]
+    lib.vsyn_pyin_num_frames.restype = u64
+    lib.vsyn_pyin_num_bins.argtypes = [C.POINTER(PyinSpec)]
+    lib.vsyn_pyin_num_bins.restype = u32
+    lib.vsyn_pyin_transition.argtypes = [C.POINTER(PyinSpec), u32, vp, vp, vp, u64, cpp]
+    lib.vsyn_pyin_device.argtypes = [vp, C.POINTER(PyinSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_pyin_decode_device.argtypes = [vp, C.POINTER(PyinSpec), u32, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_pyin_host.argtypes = [vp, C.POINTER(PyinSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_fdesc_num_frames.argtypes = [C.POINTER(FdescSpec), u64]
     lib.vsyn_fdesc_num_frames.restype = u64
     lib.vsyn_fdesc_device.argtypes = [vp, C.POINTER(FdescSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
@@ -919,6 +935,25 @@ class Synth:
         rates = _rates(in_rates)
         S, o = len(rates), _per_segment(len(rates), "refused")
         return self._rows_host(self.lib.vsyn_pcm_pitch_host, (C.byref(spec), S, _ptr(rates), out_rate), S, 2, [o["refused"]], o)
+
+    def pyin_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, d_refused=None, stream=None):
+        """vsyn_pyin_device on device pointers (ints); sample_rates is a host sequence."""
+        rates = _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_pyin_device(self.h, _ref(spec), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames, d_rows,
+                                         d_seg_row_off, d_refused, stream, C.byref(err)), err)
+
+    def pyin_decode_device(self, spec, sample_rates, d_obs, seg_rows, d_states, stream=None):
+        """vsyn_pyin_decode_device on device pointers (ints); sample_rates and seg_rows are host sequences."""
+        rates, rows = _rates(sample_rates), np.ascontiguousarray(seg_rows, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_pyin_decode_device(self.h, _ref(spec), len(rates), _ptr(rates), d_obs, _ptr(rows), d_states, stream, C.byref(err)), err)
+
+    def pcm_pyin_host(self, spec, in_rates, out_rate=0):
+        """vsyn_pcm_pyin_host over the last submit's segments: returns dict(rc, rows [total][3], seg_rows [S], refused [S], flags)."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "refused")
+        return self._rows_host(self.lib.vsyn_pcm_pyin_host, (C.byref(spec), S, _ptr(rates), out_rate), S, 3, [o["refused"]], o)
 
     def fdesc_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, d_refused=None, stream=None):
         """vsyn_fdesc_device on device pointers (ints); sample_rates is a host sequence (None: NULL)."""

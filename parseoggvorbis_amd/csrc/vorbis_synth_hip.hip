@@ -38,6 +38,7 @@
 #include "vsyn_trim.h"
 #include "vsyn_split.h"
 #include "vsyn_pitch.h"
+#include "vsyn_pyin.h"
 #include "vsyn_fdesc.h"
 
 static const uint32_t k_inverse_db_bits[256] = {
@@ -149,6 +150,7 @@ struct vsyn_handle {
   TrimWs tr;                           // vsyn_trim.h
   SplitWs sl;                          // vsyn_split.h
   PitchWs pt;                          // vsyn_pitch.h
+  PyinWs py;                           // vsyn_pyin.h
   FdescWs fd;                          // vsyn_fdesc.h
   LoudWs ld;                           // vsyn_loudness.h
   // profiling
@@ -2445,6 +2447,73 @@ int vsyn_pcm_pitch_host(vsyn_handle* h, const vsyn_pitch_spec* spec, uint32_t S,
       h, spec->frame_length, spec->hop_length, pitch_center(spec), 2u, h->pt.rows, h->pt.refused,
       [&](const PcmView& v, uint64_t f_max, hipStream_t hs) {
         return pitch_launch(h->pt, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->pt.rows.p, nullptr, h->pt.refused.p, hs, err);
+      },
+      S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
+}
+
+// ---- pyin (vsyn_pyin.h) ----
+
+uint64_t vsyn_pyin_num_frames(const vsyn_pyin_spec* spec, uint64_t frames) {
+  if (pyin_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
+  return spec_num_frames(spec->frame_length, spec->hop_length, pyin_center(spec), frames);
+}
+
+uint32_t vsyn_pyin_num_bins(const vsyn_pyin_spec* spec) { return pyin_check(spec, 0, nullptr, nullptr) == VSYN_OK ? pyin_bins(spec) : 0u; }
+
+int vsyn_pyin_transition(const vsyn_pyin_spec* spec, uint32_t sample_rate, uint32_t* width_out, uint32_t* bins_out, double* table,
+                         uint64_t table_capacity, const char** err) {
+  if (!sample_rate) return fail(err, VSYN_ERR_INVALID, "sample_rate is 0");
+  if (int rc = pyin_check(spec, 1, &sample_rate, err)) return rc;
+  const uint32_t B = pyin_bins(spec), w = pyin_width(spec, sample_rate);
+  if (width_out) *width_out = w;
+  if (bins_out) *bins_out = B;
+  if (!table) return VSYN_OK;
+  if (table_capacity < (uint64_t)B * w * 2u)
+    return fail(err, VSYN_ERR_INVALID, "transition table too small: %llu doubles needed", (unsigned long long)B * w * 2u);
+  for (uint32_t i = 0; i < B; ++i) pyin_log_row(spec, B, w / 2u, i, table + (size_t)i * w * 2u);
+  return VSYN_OK;
+}
+
+int vsyn_pyin_device(vsyn_handle* h, const vsyn_pyin_spec* spec, uint32_t S, const uint32_t* sample_rates, const float* d_pcm,
+                     uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off,
+                     uint32_t* d_refused, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = pyin_check(spec, S, sample_rates, err);
+  if (rc) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_rows || plane_stride == 0 || channels == 0 || channels > 255)
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  const uint64_t f_max = spec_num_frames(spec->frame_length, spec->hop_length, pyin_center(spec), plane_stride);
+  std::lock_guard<std::mutex> lk(h->mu);
+  return pyin_launch(h->py, h->device, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, f_max * S, d_rows,
+                     d_seg_row_off, d_refused, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pyin_decode_device(vsyn_handle* h, const vsyn_pyin_spec* spec, uint32_t S, const uint32_t* sample_rates, const double* d_obs,
+                            const uint64_t* seg_rows, uint32_t* d_states, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = pyin_check(spec, S, sample_rates, err)) return rc;
+  if (int rc = rows_check_segs(S, seg_rows, 0xFFFFFFFFull, err)) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_obs || !d_states || ((uintptr_t)d_obs & 7u) || ((uintptr_t)d_states & 3u))
+    return fail(err, VSYN_ERR_INVALID, "NULL or misaligned observation or state pointer");
+  std::lock_guard<std::mutex> lk(h->mu);
+  return pyin_decode_launch(h->py, h->device, spec, S, sample_rates, d_obs, seg_rows, d_states, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_pyin_host(vsyn_handle* h, const vsyn_pyin_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                       uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  status_reset(status);
+  if (int rc = chain_check(nullptr, nullptr, S, in_rates, out_rate, err)) return rc;
+  const std::vector<uint32_t> py_rates = stage_rates(S, in_rates, out_rate);
+  const uint32_t* rates = out_rate ? py_rates.data() : in_rates;
+  if (int rc = pyin_check(spec, S, rates, err)) return rc;
+  return framed_rows_host(
+      h, spec->frame_length, spec->hop_length, pyin_center(spec), 3u, h->py.rows, h->py.refused,
+      [&](const PcmView& v, uint64_t f_max, hipStream_t hs) {
+        return pyin_launch(h->py, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, f_max * S, h->py.rows.p, nullptr,
+                           h->py.refused.p, hs, err);
       },
       S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
 }

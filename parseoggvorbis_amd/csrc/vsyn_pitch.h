@@ -19,6 +19,8 @@
 //                                 wave and the four waves (vsyn_wave.h), and thread 0 writes the row. No atomics.
 //                                 The workgroup also looks at every sample of its share of the segment for an Inf or a NaN
 //                                 (trim_not_finite, the trim stage's test) and stores one flag word per tile (frames_tile_stage).
+//                                 The difference function, S, c, the trough test and the parabolic shift are the device functions of
+//                                 vsyn_yin.h, which the pYIN kernel (vsyn_pyin.h) calls too.
 //   3. vsyn_pitch_finish_kernel   one workgroup per segment: a segment with a flagged tile is refused: its rows become NaN and its
 //                                 word of the refused array 1 (frames_finish).
 // Order of S: with K = ceil(p_max / PITCH_THREADS), thread t owns the lags t K + 1 .. (t + 1) K. It adds its d in ascending order
@@ -31,20 +33,10 @@
 #include "vsyn_frames.h"
 #include "vsyn_host.h"
 #include "vsyn_trim.h"
+#include "vsyn_yin.h"
 
-#define PITCH_THREADS 256
-static_assert(PITCH_THREADS == FRAMES_THREADS, "the shared framing helpers stride by the workgroup's size");
-#define PITCH_WAVES (PITCH_THREADS / 64)
-#define PITCH_ILP 4u                        // independent fma chains per thread
 #define PITCH_FT_MAX 64u                    // frames per workgroup, at most
 #define PITCH_LDS_BUDGET (79u * 1024u)      // dynamic LDS of a workgroup: two fit a CU's 160 KiB beside their static words
-#define PITCH_TINY 2.2250738585072014e-308  // numpy.finfo(float64).tiny
-#define PITCH_NONE 0xFFFFFFFFFFFFFFFFull
-
-struct PitchSeg {  // one segment's periods (host, double): p_max = 0 skips the segment
-  double sr;
-  uint32_t p_min, p_max;
-};
 
 struct PitchCtx {  // launch arguments
   const PitchSeg* seg;
@@ -68,11 +60,6 @@ __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_offsets_kernel(const
   frames_offsets(A, A.L, [&](uint32_t g) { return A.seg[g].p_max == 0u; });
 }
 
-// the minimum of v over the workgroup, for every thread (s_r: PITCH_WAVES words of LDS, free again on return)
-__device__ __forceinline__ uint64_t pitch_wg_min(uint64_t v, uint64_t* s_r) {
-  return wg_reduce_all<PITCH_WAVES>(v, s_r, WaveMin(), PITCH_NONE);
-}
-
 __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCtx A) {
   extern __shared__ double s_pitch[];
   __shared__ uint64_t s_r[PITCH_WAVES];
@@ -90,60 +77,19 @@ __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCt
   frames_tile_stage(A, t, s_y);
   if (nf == 0u) return;
 
-  // d[f][tau - 1], tau = 1 .. PL: one fma chain per (f, tau), j ascending
-  const uint32_t items = nf * PL;
-  for (uint32_t q0 = 0; q0 < items; q0 += PITCH_ILP * PITCH_THREADS) {
-    const float* zf[PITCH_ILP];
-    uint32_t tau[PITCH_ILP];
-    double acc[PITCH_ILP];
-#pragma unroll
-    for (uint32_t r = 0; r < PITCH_ILP; ++r) {
-      const uint32_t q = q0 + r * PITCH_THREADS + tid;
-      const uint32_t qq = q < items ? q : 0u;  // (an idle chain repeats pair 0 and is not stored)
-      const uint32_t f = qq / PL;
-      tau[r] = qq - f * PL + 1u;
-      zf[r] = s_y + (size_t)f * fstep;
-      acc[r] = 0.0;
-    }
-    for (uint32_t j = 1; j <= W; ++j) {
-#pragma unroll
-      for (uint32_t r = 0; r < PITCH_ILP; ++r) {
-        const double df = (double)zf[r][j] - (double)zf[r][j + tau[r]];  // (j + tau <= W + p_max <= L - 1)
-        acc[r] = fma(df, df, acc[r]);
-      }
-    }
-#pragma unroll
-    for (uint32_t r = 0; r < PITCH_ILP; ++r) {
-      const uint32_t q = q0 + r * PITCH_THREADS + tid;
-      if (q < items) s_d[q] = acc[r];
-    }
-  }
-  __syncthreads();
+  yin_difference(s_y, s_d, nf, fstep, W, PL);  // d[f][tau - 1], tau = 1 .. PL
 
   const uint32_t p_min = sg.p_min, n = PL - p_min + 1u;
-  const uint32_t K = (PL + PITCH_THREADS - 1u) / PITCH_THREADS;
-  const uint32_t b0 = tid * K < PL ? tid * K : PL, b1 = b0 + K < PL ? b0 + K : PL;  // this thread's lags, as indices tau - 1
   const uint64_t r0 = A.segoff[g] + f0;
   for (uint32_t f = 0; f < nf; ++f) {
     double* d = s_d + (size_t)f * PL;
-    // S, and c in place of d from p_min on
-    double tot[1] = {0.0}, exc[1], all[1];
-    for (uint32_t k = b0; k < b1; ++k) tot[0] += d[k];
-    wg_sum_scan<1>(tot, exc, all, s_w);
-    double run = exc[0];
-    for (uint32_t k = b0; k < b1; ++k) {
-      const double dk = d[k];
-      run += dk;
-      if (k + 1u >= p_min) d[k] = dk / (run / (double)(k + 1u) + PITCH_TINY);
-    }
-    __syncthreads();
+    yin_normalise(d, PL, p_min, s_w);  // S, and c in place of d from p_min on
     // i*: the first trough below the threshold, else the first minimum (c >= 0: its bit pattern orders as its value)
     const double* c = d + (p_min - 1u);
     uint64_t first = PITCH_NONE, low = PITCH_NONE;
     for (uint32_t i = tid; i < n; i += PITCH_THREADS) {
       const double ci = c[i];
-      const bool tr = i == 0u ? ci < c[1] : i == n - 1u ? ci < c[i - 1u] : (ci < c[i - 1u] && ci <= c[i + 1u]);
-      if (tr && ci < A.thr) first = trim_min64(first, i);
+      if (yin_trough(c, i, n) && ci < A.thr) first = trim_min64(first, i);
       low = trim_min64(low, (uint64_t)__double_as_longlong(ci));
     }
     first = pitch_wg_min(first, s_r);
@@ -156,12 +102,7 @@ __global__ void __launch_bounds__(PITCH_THREADS) vsyn_pitch_kernel(const PitchCt
     }
     if (tid == 0) {
       const uint32_t is = (uint32_t)first;
-      double shift = 0.0;
-      if (is > 0u && is < n - 1u) {
-        const double a = (c[is + 1u] + c[is - 1u]) - 2.0 * c[is];
-        const double b = (c[is + 1u] - c[is - 1u]) * 0.5;
-        if (fabs(b) < fabs(a)) shift = -b / a;
-      }
+      const double shift = yin_shift(c, is, n);
       float* row = A.rows + 2u * (r0 + f);
       row[0] = (float)(sg.sr / ((double)(p_min + is) + shift));
       row[1] = (float)c[is];

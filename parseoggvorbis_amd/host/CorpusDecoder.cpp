@@ -82,6 +82,7 @@ const vsyn_loudness_record NO_LOUDNESS_RECORD = vsyn_loudness_record{0.0, 0.0, 0
 bool feature_run(const CorpusOptions& o) { return o.features.kind != 0; }
 bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
 bool pitch_run(const CorpusOptions& o) { return o.pitch.frame_length != 0; }
+bool pyin_run(const CorpusOptions& o) { return o.pyin.frame_length != 0; }
 bool fdesc_run(const CorpusOptions& o) { return o.fdesc.n_fft != 0; }
 bool loudness_run(const CorpusOptions& o) { return o.loudness; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
@@ -753,6 +754,29 @@ struct Feeder {
     });
   }
 
+  // pYIN run: each file's (f0, voiced, voiced_prob) rows (vsyn_pcm_pyin_host), as a pitch run; whether a file's rate fits the spec
+  // (fmax <= sr/2, two lags or more, an odd transition width) is vsyn_pyin_transition's answer for that rate, its text the file's error.
+  OkOrError pyin_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size();
+    std::vector<uint32_t> rates(S);
+    uint64_t rows = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      const uint32_t in = g.pending[s]->header.audio_sample_rate;
+      const uint32_t sr = opts.resample_rate ? opts.resample_rate : in;  // the rate the rows are computed at
+      const char* why = nullptr;
+      if (o.err[s].empty() && vsyn_pyin_transition(&opts.pyin, sr, nullptr, nullptr, nullptr, 0, &why) != VSYN_OK) {
+        char buf[400];
+        snprintf(buf, sizeof(buf), "pyin: the spec does not fit sample rate %u: %s", sr, why ? why : "refused");
+        o.err[s] = buf;
+      }
+      rates[s] = o.err[s].empty() ? in : 0;
+      if (rates[s]) rows += vsyn_pyin_num_frames(&opts.pyin, std::min<uint64_t>(o.frames[s], o.plane));
+    }
+    return framed_rows(g, o, rows, 3u, "pyin", "pyin", [&](uint32_t* refused, vsyn_status* st, const char** err) {
+      return vsyn_pcm_pyin_host(g.handle, &opts.pyin, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused, st, err);
+    });
+  }
+
   // Frame descriptor run: each file's (rms, zcr, centroid, bandwidth, rolloff, flatness) rows from the PCM still on the device
   // (vsyn_pcm_fdesc_host, resampled first in a resampled run); a file the stage refuses (a sample that is not finite) gets an error
   // of its own.
@@ -797,7 +821,7 @@ struct Feeder {
   // A synthesis run's file: its PCM (or, for a spectral, pitch or frame descriptor run, its rows) to the callbacks.
   OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
     const uint32_t C = opts.condition ? 1u : g.channels;  // channels delivered
-    const bool spectral = spectral_run(opts) || pitch_run(opts) || fdesc_run(opts) || loudness_run(opts);
+    const bool spectral = spectral_run(opts) || pitch_run(opts) || pyin_run(opts) || fdesc_run(opts) || loudness_run(opts);
     const uint64_t frames = o.frames[s], pl = o.plane;
     if (opts.condition) out.channels = 1;
     std::vector<DataRange<const float>> chans(C);
@@ -832,7 +856,7 @@ struct Feeder {
       if (s < o.loud_nb.size()) row0 += o.loud_nb[s];
       return OkOrError();
     }
-    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : fdesc_run(opts) ? 6u : spectral_dim(opts));
+    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : pyin_run(opts) ? 3u : fdesc_run(opts) ? 6u : spectral_dim(opts));
     if (!callbacks || !o.err[s].empty() || opts.intervals_only) return OkOrError();
     std::lock_guard<std::mutex> lk(callbacks_mu);
     if (opts.pcm_s16) {
@@ -847,8 +871,8 @@ struct Feeder {
     if (g.pending.empty()) return OkOrError();
     if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
-    const bool pitch = pitch_run(opts), fdesc = fdesc_run(opts), loud = loudness_run(opts);
-    const bool spectral = spectral_run(opts) || pitch || fdesc || loud;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
+    const bool pitch = pitch_run(opts), pyin = pyin_run(opts), fdesc = fdesc_run(opts), loud = loudness_run(opts);
+    const bool spectral = spectral_run(opts) || pitch || pyin || fdesc || loud;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
     const bool cond = opts.condition;               // ... and until it is conditioned
     double t0 = now_s();
@@ -880,6 +904,7 @@ struct Feeder {
       if (cond && !spectral) CHECK_ERR(condition_stage(g, o));
       if (loud) CHECK_ERR(loudness_stage(g, o));
       else if (pitch) CHECK_ERR(pitch_stage(g, o));
+      else if (pyin) CHECK_ERR(pyin_stage(g, o));
       else if (fdesc) CHECK_ERR(fdesc_stage(g, o));
       else if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
@@ -1628,6 +1653,23 @@ extern "C" int ogg_vorbis_pitch_corpus(const uint8_t* const* datas, const size_t
   opts.pitch = *spec;
   opts.resample_rate = target_rate;
   return malloc_corpus("pitch", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                       });
+}
+
+extern "C" int ogg_vorbis_pyin_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                      uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pyin_spec* spec, float** rows_out,
+                                      uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                                      const char** error_out_per_file, double* stats_out, const char** error_out) {
+  if (!spec || !vsyn_pyin_num_frames(spec, 0x7FFFFFFFu))
+    return refuse_call((void**)rows_out, num_files, "ogg_vorbis_pyin_corpus: invalid pyin spec", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  opts.pyin = *spec;
+  opts.resample_rate = target_rate;
+  return malloc_corpus("pyin", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
                        [&](size_t i, const CorpusFileResult& res, bool bad) {
                          if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
                          if (frames_out) frames_out[i] = bad ? 0 : res.frames;

@@ -121,6 +121,11 @@ struct CorpusOptions {
   // delivered through gotFileFeatures with dim 2; no PCM crosses the bus. A file whose rate the spec does not fit, and a file with
   // a sample that is not finite, fails alone. Excludes features, spectral, pcm_s16 and the conditioning, trim and split stages.
   vsyn_pitch_spec pitch = {0, 0, 0, 0, 0.0, 0.0, 0.0};
+  // pYIN run (pyin.frame_length != 0): as a pitch run, but each file's (f0, voiced, voiced_prob) rows (include/vorbis_synth_hip.h,
+  // "pyin": vsyn_pcm_pyin_host), delivered through gotFileFeatures with dim 3; pyin.threshold_probs must stay valid for the run. A
+  // file whose rate the spec does not fit (an even transition width among the reasons) fails alone. Excludes what a pitch run
+  // excludes, and pitch.
+  vsyn_pyin_spec pyin = {0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, nullptr};
   // frame descriptor run (fdesc.n_fft != 0): as a pitch run, but each file's (rms, zcr, centroid, bandwidth, rolloff, flatness) rows
   // (include/vorbis_synth_hip.h, "frame descriptors": vsyn_pcm_fdesc_host), delivered through gotFileFeatures with dim 6. A file with
   // a sample that is not finite fails alone. Excludes what a pitch run excludes, and pitch.
@@ -397,6 +402,13 @@ int ogg_vorbis_pitch_corpus(const uint8_t* const* datas, const size_t* lens, siz
                             uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pitch_spec* spec, float** rows_out,
                             uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
                             const char** error_out_per_file, double* stats_out, const char** error_out);
+// pYIN run (CorpusOptions::pyin = *spec; target_rate as for ogg_vorbis_pitch_corpus): rows_out receives per file NULL (failed, or
+// no rows) or a buffer of rows_count_out[i] * 3 floats, (f0 in Hz, voiced, voiced_prob) per frame, released with
+// ogg_vorbis_features_free. An invalid spec refuses the call before any file is touched.
+int ogg_vorbis_pyin_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                           uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_pyin_spec* spec, float** rows_out,
+                           uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                           const char** error_out_per_file, double* stats_out, const char** error_out);
 // frame descriptor run (CorpusOptions::fdesc = *spec; target_rate as for ogg_vorbis_pitch_corpus): rows_out receives per file NULL
 // (failed, or no rows) or a buffer of rows_count_out[i] * 6 floats, (rms, zcr, centroid, bandwidth, rolloff, flatness) per frame,
 // released with ogg_vorbis_features_free. An invalid spec refuses the call before any file is touched.
