@@ -195,28 +195,47 @@ def _transition(lib, spec, sr):
     return rc, w.value, B.value, tab, err.value
 
 
-# (sr, H, fmin, fmax, resolution): w in {1, 3, 101, 71, 31, 281}, B below, equal to and above w
+# (sr, H, fmin, fmax, resolution): w in {1, 3, 101, 71, 31, 281}, B below, equal to and above w; then the sizes of
+# tests/pyin_regime_cases.py: (B, w) = (1201, 201), (2048, 341), (59, 141), (36, 71), (37, 71)
 TABLES = [(22050, 16, 1000.0, 1400.0, 0.5), (8000, 16, 400.0, 550.0, 0.5), (22050, 512, yc.C2, yc.C7, 0.1), (8000, 128, 200.0, 280.0, 0.1),
-          (8000, 128, 200.0, 300.5, 0.1), (16000, 128, 200.0, 280.0, 0.1), (8000, 512, yc.C2, yc.C7, 0.1), (22050, 512, 30.0, 60.0, 0.5)]
+          (8000, 128, 200.0, 300.5, 0.1), (16000, 128, 200.0, 280.0, 0.1), (8000, 512, yc.C2, yc.C7, 0.1), (22050, 512, 30.0, 60.0, 0.5),
+          (22050, 512, yc.C2, yc.C7, 0.05), (22050, 512, yc.C2, yc.C2 * 2.0 ** (2047.5 / 408.0), 0.03), (8000, 256, 200.0, 280.0, 0.1),
+          (8000, 128, 200.0, 245.0, 0.1), (8000, 128, 200.0, 247.0, 0.1)]
+# (sr, H, fmin, fmax, resolution, max_transition_rate, switch_prob): (601, 1) needs another rate; the other switch probabilities
+TABLES_MORE = [(22050, 512, yc.C2, yc.C7, 0.1, 1.0, 0.01), (8000, 128, 200.0, 302.0, 0.1, 35.92, 0.3), (8000, 16, 400.0, 550.0, 0.5, 35.92, 0.49),
+               (16000, 128, 200.0, 302.0, 0.1, 35.92, 0.3)]
 
 
-@pytest.mark.parametrize("sr,H,fmin,fmax,res", TABLES)
-def test_the_transition_table_against_the_model(lib, sr, H, fmin, fmax, res):
-    """Relative 2^-50 inside the band, log(tiny) exactly outside it, w and B equal. (This test fails without the feature: the symbol
-    does not exist.)"""
-    spec = pitch.pyin_spec(fmin, fmax, 2048 if H == 512 else 512 if H == 128 else 64, H, resolution=res)
+def _check_table(lib, sr, H, fmin, fmax, res, mtr=35.92, sw=0.01):
+    spec = pitch.pyin_spec(fmin, fmax, 2048 if H == 512 else 512 if H in (128, 256) else 64, H, resolution=res, max_transition_rate=mtr, switch_prob=sw)
     rc, w, B, tab, err = _transition(lib, spec, sr)
     assert rc == 0, err
     bps, Bm = ym.num_bins(fmin, fmax, res)
-    wm = ym.width(sr, H, 35.92, bps)
+    wm = ym.width(sr, H, mtr, bps)
     assert (w, B) == (wm, Bm) and B == lib.vsyn_pyin_num_bins(ctypes.byref(spec))
-    want = ym.band_table(ym.log_transition(B, w, 0.01), B, w)
+    want = ym.band_table(ym.log_transition(B, w, sw), B, w)
     inside = want != ym.LT
     h = w // 2
     j = np.arange(B)[:, None] + np.arange(w)[None, :] - h
     assert np.array_equal(inside[:, :, 0], (j >= 0) & (j < B)) and np.array_equal(inside[:, :, 0], inside[:, :, 1])
     assert (tab[~inside] == ym.LT).all()
     assert (np.abs(tab[inside] - want[inside]) <= 2.0 ** -50 * np.abs(want[inside])).all()
+    return B, w
+
+
+@pytest.mark.parametrize("sr,H,fmin,fmax,res", TABLES)
+def test_the_transition_table_against_the_model(lib, sr, H, fmin, fmax, res):
+    """Relative 2^-50 inside the band, log(tiny) exactly outside it, w and B equal. (This test fails without the feature: the symbol
+    does not exist.)"""
+    _check_table(lib, sr, H, fmin, fmax, res)
+
+
+@pytest.mark.parametrize("sr,H,fmin,fmax,res,mtr,sw", TABLES_MORE)
+def test_the_transition_table_at_other_rates_and_switch_probabilities(lib, sr, H, fmin, fmax, res, mtr, sw):
+    """The same comparison where max_transition_rate and switch_prob are not the defaults: w = 1 at B = 601, and the stay and switch
+    entries at 0.3 and 0.49, which differ from each other by less than at 0.01."""
+    B, w = _check_table(lib, sr, H, fmin, fmax, res, mtr, sw)
+    assert (B, w) in ((601, 1), (72, 71), (12, 3), (72, 31))
 
 
 def test_the_widths_and_sizes_of_the_tables_cover_the_section():
@@ -315,6 +334,7 @@ BAD_SPECS = [dict(L=3), dict(L=8193), dict(H=0), dict(options=2), dict(fmin=0.0)
              dict(res=math.nan), dict(mtr=0.0), dict(mtr=math.nan), dict(mtr=math.inf), dict(sw=0.0), dict(sw=1.0), dict(sw=math.nan), dict(ntp=-0.1),
              dict(ntp=1.1), dict(ntp=math.nan), dict(fmin=20.0, fmax=8000.0, res=0.01), dict(res=0.34, H=128, L=512, fmin=200.0, fmax=280.0)]
 # (the last at 8000 Hz: w = 22, even)
+BAD_SPECS.append(dict(res=0.03, fmax=yc.C2 * 2.0 ** (2048.5 / 408.0), fmin=yc.C2))  # B = 2049: one pair of states above the cap (B = 2048 passes)
 
 
 @pytest.mark.parametrize("kw", BAD_SPECS, ids=lambda kw: ",".join("%s" % k for k in kw))
