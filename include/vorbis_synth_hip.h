@@ -1330,6 +1330,136 @@ int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t nu
                         float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
                         const char** err);
 
+/* ---- constant-Q: the constant-Q / variable-Q transform of the decoded PCM and the chroma_cqt rows folded from it, computed where the PCM is ----
+ *
+ * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, and its sample rate sr. Parameters: n_bins,
+ * bins_per_octave (bpo), hop_length, fmin, tuning, filter_scale, gamma, norm, VSYN_CQT_SCALE, an output selector and, for the chroma
+ * outputs, n_chroma, chroma_norm and VSYN_CQT_BASE_C. This is the quantity librosa.cqt / librosa.vqt (window="hann",
+ * pad_mode="constant") and librosa.feature.chroma_cqt approximate, in DIRECT TIME-DOMAIN FORM: every coefficient is the plain
+ * sum of step 5 over the whole support of its wavelet. A stated divergence: librosa multiplies an STFT by a sparsified FFT basis
+ * (its `sparsity`), octave by octave on a recursively decimated signal (its `res_type`, its early downsampling); none of the three
+ * exists here, and none of their approximation errors. librosa is not among the test dependencies and parity with it is not
+ * claimed: the device is compared against a float64 model of the arithmetic below (tests/cqt_model.py), and the model against closed
+ * forms and a restatement as a correlation (tests/test_cqt_cpu.py).
+ *
+ *  1. Frequencies. f_k = (fmin * exp2(tuning / bpo)) * exp2(k / bpo), k < n_bins, in double in this order (the C library's exp2).
+ *  2. Lengths. r = exp2(1 / bpo), alpha = (r r - 1) / (r r + 1), Q = filter_scale / alpha, N_k = (Q * sr) / (f_k + gamma / alpha), a
+ *     double. gamma = 0 is the CQT, gamma > 0 the VQT; it costs nothing beyond the host table. N_k falls with k: bin 0 is the longest.
+ *  3. Support and window. With h_k = ceil(N_k / 2), the support is the integers m in [-h_k, floor(N_k / 2)); their count L_k =
+ *     h_k + floor(N_k / 2) is odd unless N_k / 2 is an integer, and h_k = ceil(L_k / 2). The window is the periodic Hann over the
+ *     support: w_k[j] = 0.5 - 0.5 cos(2 pi j / L_k), j = m + h_k.
+ *  4. Wavelet. b_k[m] = w_k[j] * exp(-2 pi i f_k m / sr) / n_k: re = w cos(p) / n_k, im = -(w sin(p)) / n_k with
+ *     p = ((2 pi f_k) m) / sr; n_k = sum_j w_k[j] for norm 1 (the default), sqrt(sum_j w_k[j]^2) for norm 2, 1 for norm 0 (none),
+ *     the sums added in ascending j. Built in double on the host, once per distinct rate, and stored as float32 pairs.
+ *  5. Transform. y[t] is step 1 of the conditioning stage (the float32 downmix, the one device function every stage uses).
+ *     C[t][k] = s_k * sum_m y[t hop + m] b_k[m], samples outside [0, T) taken as zero (librosa's pad_mode="constant", always
+ *     centred); s_k = sqrt(N_k) with VSYN_CQT_SCALE (librosa's scale=True, the default), else N_k, stored as float32.
+ *     F = 1 + T / hop (integer division; vsyn_cqt_num_frames) and T = 0 gives 0 rows. Row t is centred on sample t hop: where row t
+ *     of every centred spectral kind with an even n_fft, and frame t of the centred pitch and descriptor stages, are centred.
+ *     Order of one (t, k) sum, float32 throughout: the offsets m are cut into chunks [c K - K/2, (c + 1) K - K/2) of K =
+ *     VSYN_CQT_CHUNK samples, the same grid for every bin, rate and batch; inside a chunk lane l of 64 runs one fma chain per
+ *     component over the bin's offsets first + l, first + l + 64, .. (ascending; first = the larger of the chunk's and the support's
+ *     first offset), the 64 chains go through the xor butterfly (offsets 32 .. 1), and the chunks' sums are added in ascending
+ *     order onto 0.0. A fixed function of (L_k, K). No atomics.
+ *  6. Outputs. VSYN_CQT_MAG: |C|^power, power 1 or 2 (sqrtf(fma(re, re, im im)) or the argument of the root), float32 (F, n_bins).
+ *     VSYN_CQT_COMPLEX: re and im interleaved, (F, 2 n_bins), a complex64 matrix (F, n_bins) as the spectral kind "stft" is.
+ *     VSYN_CQT_CHROMA: step 7, (F, n_chroma). VSYN_CQT_TONNETZ: step 8, (F, 6). vsyn_cqt_dim gives the columns.
+ *  7. Chroma (librosa.feature.chroma_cqt with threshold=None, cqt_mode="full", window=None). R[c] = sum_k M[c][k] |C[t][k]|, the
+ *     magnitudes (power is not read), added in ascending k in float32. M is librosa.filters.cq_to_chroma's 0/1 matrix: with
+ *     n_merge = bpo / n_chroma (an integer), M[c][k] = 1 exactly for
+ *       c = ((((k mod bpo) + n_merge / 2) mod bpo) / n_merge + roll) mod n_chroma        (integer divisions),
+ *     roll = rint((n_chroma / 12.0) * m0) with VSYN_CQT_BASE_C and rint((n_chroma / 12.0) * (m0 - 9)) without, rint to even, reduced
+ *     mod n_chroma to 0 .. n_chroma - 1, m0 = fmod(12 (log2(fmin) - log2(440)) + 69, 12) made non-negative (hz_to_midi of the
+ *     UNTUNED fmin, as librosa has it). This is numpy's construction read out: repeat(eye(n_chroma), n_merge, axis=1) puts column j
+ *     in class j / n_merge; roll(.., -(n_merge / 2), axis=1) makes column j the old column j + n_merge / 2; tile repeats the bpo
+ *     columns; roll(.., roll, axis=0) moves class c to row c + roll. At fmin = C1 bin 0 is row 0 with VSYN_CQT_BASE_C and row 3
+ *     (A = 0) without. Then the per-frame norm chroma_norm (VSYN_CHROMA_NORM_*), its FLT_MIN rule and the non-finite rule of
+ *     "chroma" step 3: the same device function.
+ *  8. Tonnetz. Step 4 of "chroma" applied to the rows of step 7: the same device function.
+ *  9. Not finite. A segment with an Inf or NaN sample among its T frames is refused alone: every value of its F rows is NaN and its
+ *     entry of the refused array is VSYN_CQT_NOT_FINITE (1): the descriptor stage's rule.
+ * 10. Rate. A segment whose top bin's pass band leaves the Nyquist band, f_(n_bins-1) * (1 + 0.5 * 1.50018310546875 / Q) > sr / 2
+ *     (the Hann window's bandwidth in bins, librosa's rule), is refused alone: its F rows are NaN and its entry of the refused array
+ *     is VSYN_CQT_RATE (2); nothing of it is read, so this entry wins over step 9's. A rate of 0 skips the segment (0 rows).
+ * 11. Checks (VSYN_ERR_INVALID before anything runs): 1 <= n_bins <= 256; 1 <= bpo <= 256; hop_length >= 1; fmin finite and > 0;
+ *     filter_scale finite and > 0; gamma finite and >= 0; tuning finite; power 1 or 2; norm 0, 1 or 2; a known output; for the
+ *     chroma outputs 1 <= n_chroma <= 256, bpo a multiple of n_chroma and a known chroma_norm; unknown option bits; channels >= 1;
+ *     and for every rate of the call that step 10 does not refuse: L_0 <= VSYN_CQT_MAX_LENGTH (2^17) and sum_k L_k <=
+ *     VSYN_CQT_MAX_TABLE (2^23 pairs, 64 MB).
+ *
+ * Deliberately not built: librosa's FFT-basis route and its sparsity; hybrid_cqt, pseudo_cqt, icqt, griffinlim_cqt; chroma_cens;
+ * chroma_cqt's threshold and smoothing window; windows other than Hann; tuning=None (estimation); dB output; composition with the
+ * trim, split, conditioning, delta, normalisation and HPSS stages; MFMA. The same PCM gives the same bits, alone, in any slot of a
+ * batch and at any alignment. The entry points read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept
+ * by VSYN_SUBMIT_KEEP_PCM. One handle's constant-Q entry points share its constant-Q workspace, which is no other stage's; the
+ * wavelet tables of the last call's (spec, rates) stay there, on the host and on the device. */
+#define VSYN_CQT_SCALE 1u  /* s_k = sqrt(N_k) (librosa's scale=True) */
+#define VSYN_CQT_BASE_C 2u /* chroma outputs: row 0 is C, else A */
+#define VSYN_CQT_MAG 1u
+#define VSYN_CQT_COMPLEX 2u
+#define VSYN_CQT_CHROMA 3u
+#define VSYN_CQT_TONNETZ 4u
+#define VSYN_CQT_NOT_FINITE 1u /* refused[g], step 9 */
+#define VSYN_CQT_RATE 2u       /* refused[g], step 10 */
+#define VSYN_CQT_CHUNK 1024u
+#define VSYN_CQT_MAX_LENGTH (1u << 17)
+#define VSYN_CQT_MAX_TABLE (1u << 23)
+#define VSYN_CQT_RATE_REFUSED 100 /* vsyn_cqt_lengths: the rate is refused under step 10 */
+
+typedef struct vsyn_cqt_spec {
+  uint32_t n_bins;
+  uint32_t bins_per_octave;
+  uint32_t hop_length;
+  uint32_t options;     /* VSYN_CQT_SCALE, VSYN_CQT_BASE_C */
+  uint32_t output;      /* VSYN_CQT_MAG .. VSYN_CQT_TONNETZ */
+  uint32_t power;       /* 1 or 2 (VSYN_CQT_MAG) */
+  uint32_t norm;        /* 0 (none), 1 or 2: step 4 */
+  uint32_t n_chroma;    /* chroma outputs */
+  uint32_t chroma_norm; /* VSYN_CHROMA_NORM_*, chroma outputs */
+  uint32_t reserved;    /* 0 */
+  double fmin, tuning, filter_scale, gamma;
+} vsyn_cqt_spec;
+
+/* Columns of a row (step 6), 0 for an invalid spec (the checks of step 11 that need no rate). */
+uint32_t vsyn_cqt_dim(const vsyn_cqt_spec* spec);
+
+/* F of step 5 for a segment of `frames` PCM frames, 0 for an invalid spec. */
+uint64_t vsyn_cqt_num_frames(const vsyn_cqt_spec* spec, uint64_t frames);
+
+/* Host only, no device and no handle: N_k and L_k of steps 2 and 3 at rate sample_rate into N[n_bins] and L[n_bins] (either may be
+ * NULL). VSYN_ERR_INVALID for an invalid spec or a rate of 0 (nothing written); VSYN_CQT_RATE_REFUSED where step 10 refuses the
+ * rate and VSYN_ERR_INVALID where L_0 or sum_k L_k exceed their caps, both with N and L filled; else VSYN_OK. */
+int vsyn_cqt_lengths(uint32_t sample_rate, const vsyn_cqt_spec* spec, double* N, uint32_t* L);
+
+/* Host only: the float32 pairs of bin k at rate sample_rate (step 4) into re_im[2 L_k], index 2 j and 2 j + 1, j = m + h_k: what
+ * the device's table holds. The return values of vsyn_cqt_lengths; nothing is written unless VSYN_OK. */
+int vsyn_cqt_basis(uint32_t sample_rate, const vsyn_cqt_spec* spec, uint32_t k, float* re_im);
+
+/* Host only: M of step 7 into out[c * n_bins + k], n_chroma rows. VSYN_ERR_INVALID unless spec is valid with a chroma output. */
+int vsyn_cq_to_chroma(const vsyn_cqt_spec* spec, float* out);
+
+/* Host only, tuning facts for tests: out[0] frames per workgroup, out[1] samples per chunk (VSYN_CQT_CHUNK), out[2] bins per
+ * workgroup (consecutive k, so of similar length: one wave per bin). Functions of the spec alone today; the rate is taken so that
+ * they may depend on it. VSYN_ERR_INVALID for an invalid spec. */
+int vsyn_cqt_tile(const vsyn_cqt_spec* spec, uint32_t sample_rate, uint32_t out[3]);
+
+/* The caller's planar PCM, as for vsyn_fdesc_device: d_pcm[(g * channels + c) * plane_stride + t], d_frames[S] (device) PCM frames
+ * per segment (clamped to plane_stride), sample_rates[S] a HOST array (0 skips the segment). Writes d_seg_row_off[S+1] (uint64, may
+ * be NULL) and d_rows, which must hold sum_g vsyn_cqt_num_frames(spec, frames_g) rows of vsyn_cqt_dim(spec) columns; d_refused[S]
+ * (device, uint32, may be NULL): 0, VSYN_CQT_NOT_FINITE or VSYN_CQT_RATE. Asynchronous on hip_stream. */
+int vsyn_cqt_device(vsyn_handle* h, const vsyn_cqt_spec* spec, uint32_t num_segments, const uint32_t* sample_rates, const float* d_pcm,
+                    uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off,
+                    uint32_t* d_refused, void* hip_stream, const char** err);
+
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle, as for vsyn_pcm_fdesc_host: each segment resampled from in_rates[g]
+ * to out_rate first when out_rate != 0 (the wavelets are then those of out_rate). seg_rows[S] receives each segment's row count;
+ * rows (may be NULL when only the counts are wanted: nothing is launched) receives the rows of all segments back to back, at most
+ * rows_capacity rows (VSYN_ERR_INVALID with the counts filled if it is too small); refused_out[S] (uint32, may be NULL) as
+ * d_refused. status as for vsyn_pcm_spectral_host. Synchronous. */
+int vsyn_pcm_cqt_host(vsyn_handle* h, const vsyn_cqt_spec* spec, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
+                      float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
+                      const char** err);
+
 /* ---- loudness: the integrated loudness of the decoded PCM (ITU-R BS.1770-4 / EBU R 128) and the gain to a target, computed where the PCM is ----
  *
  * Input: one segment's planar float32 PCM x[c][t], C channels, T frames, at rate fs. The measured signal is the C planes

@@ -1,4 +1,4 @@
-"""ctypes plumbing of the corpus front-ends (features.py, spectral.py, pcm.py, pitch.py, frame_descriptors.py, loudness.py): the corpus entry points of libparseoggvorbis_amd.so
+"""ctypes plumbing of the corpus front-ends (features.py, spectral.py, pcm.py, pitch.py, frame_descriptors.py, cqt.py, loudness.py): the corpus entry points of libparseoggvorbis_amd.so
 and the per-file loop over the buffers they hand back (include/vorbis_synth_hip.h documents what they compute)."""
 import ctypes as C
 import os
@@ -47,6 +47,7 @@ def load():
                        ("ogg_vorbis_pitch_corpus", [u32, C.POINTER(binding.PitchSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pyin_corpus", [u32, C.POINTER(binding.PyinSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_fdesc_corpus", [u32, C.POINTER(binding.FdescSpec), vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_cqt_corpus", [u32, C.POINTER(binding.CqtSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus_loud", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
                                                        C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus_effects", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,

@@ -160,6 +160,20 @@ class FdescSpec(C.Structure):  # vsyn_fdesc_spec
                 ("roll_percent", C.c_double), ("zcr_threshold", C.c_double), ("amin", C.c_double)]
 
 
+class CqtSpec(C.Structure):  # vsyn_cqt_spec
+    _fields_ = [("n_bins", C.c_uint32), ("bins_per_octave", C.c_uint32), ("hop_length", C.c_uint32), ("options", C.c_uint32),
+                ("output", C.c_uint32), ("power", C.c_uint32), ("norm", C.c_uint32), ("n_chroma", C.c_uint32),
+                ("chroma_norm", C.c_uint32), ("reserved", C.c_uint32),
+                ("fmin", C.c_double), ("tuning", C.c_double), ("filter_scale", C.c_double), ("gamma", C.c_double)]
+
+
+VSYN_CQT_SCALE, VSYN_CQT_BASE_C = 1, 2
+VSYN_CQT_MAG, VSYN_CQT_COMPLEX, VSYN_CQT_CHROMA, VSYN_CQT_TONNETZ = 1, 2, 3, 4
+VSYN_CQT_NOT_FINITE, VSYN_CQT_RATE = 1, 2
+VSYN_CQT_RATE_REFUSED = 100  # vsyn_cqt_lengths / vsyn_cqt_basis: step 10 refuses the rate
+VSYN_CQT_MAX_LENGTH, VSYN_CQT_MAX_TABLE = 1 << 17, 1 << 23
+
+
 class LoudnessSpec(C.Structure):  # vsyn_loudness_spec
     _fields_ = [("options", C.c_uint32), ("channel_mode", C.c_uint32), ("target", C.c_double)]
 
@@ -307,6 +321,8 @@ _SYMBOLS = [
     "vsyn_pitch_num_frames", "vsyn_pitch_device", "vsyn_pcm_pitch_host",
     "vsyn_pyin_num_frames", "vsyn_pyin_num_bins", "vsyn_pyin_transition", "vsyn_pyin_device", "vsyn_pyin_decode_device", "vsyn_pcm_pyin_host",
     "vsyn_fdesc_num_frames", "vsyn_fdesc_device", "vsyn_pcm_fdesc_host",
+    "vsyn_cqt_dim", "vsyn_cqt_num_frames", "vsyn_cqt_lengths", "vsyn_cqt_basis", "vsyn_cq_to_chroma", "vsyn_cqt_tile", "vsyn_cqt_device",
+    "vsyn_pcm_cqt_host",
     "vsyn_loudness_num_blocks", "vsyn_loudness_coefficients", "vsyn_loudness_powers", "vsyn_loudness_device", "vsyn_pcm_loudness_host",
     "vsyn_pcm_chain_host", "vsyn_pcm_chain_spectral_host",
     "vsyn_spectral_chroma_dim", "vsyn_chroma_filterbank", "vsyn_spectral_chroma_tile", "vsyn_spectral_chroma_device",
@@ -442,6 +458,16 @@ def load():
     lib.vsyn_fdesc_num_frames.restype = u64
     lib.vsyn_fdesc_device.argtypes = [vp, C.POINTER(FdescSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_fdesc_host.argtypes = [vp, C.POINTER(FdescSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_cqt_dim.argtypes = [C.POINTER(CqtSpec)]
+    lib.vsyn_cqt_dim.restype = u32
+    lib.vsyn_cqt_num_frames.argtypes = [C.POINTER(CqtSpec), u64]
+    lib.vsyn_cqt_num_frames.restype = u64
+    lib.vsyn_cqt_lengths.argtypes = [u32, C.POINTER(CqtSpec), vp, vp]
+    lib.vsyn_cqt_basis.argtypes = [u32, C.POINTER(CqtSpec), u32, vp]
+    lib.vsyn_cq_to_chroma.argtypes = [C.POINTER(CqtSpec), vp]
+    lib.vsyn_cqt_tile.argtypes = [C.POINTER(CqtSpec), u32, vp]
+    lib.vsyn_cqt_device.argtypes = [vp, C.POINTER(CqtSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_cqt_host.argtypes = [vp, C.POINTER(CqtSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_loudness_num_blocks.argtypes = [u32, u64]
     lib.vsyn_loudness_num_blocks.restype = u64
     lib.vsyn_loudness_coefficients.argtypes = [u32, vp]
@@ -552,6 +578,47 @@ def _ref(x):
 
 def _rates(r):
     return None if r is None else np.ascontiguousarray(r, dtype=np.uint32)
+
+
+def cqt_lengths(spec, sample_rate):
+    """vsyn_cqt_lengths (host only, no device): (rc, N float64 [n_bins], L uint32 [n_bins]); rc is VSYN_OK, VSYN_CQT_RATE_REFUSED
+    (step 10) or VSYN_ERR_INVALID (the spec, a rate of 0: N and L zeros; or a cap of step 11: N and L filled)."""
+    n = max(1, min(int(spec.n_bins), 256))
+    N, L = np.zeros(n, np.float64), np.zeros(n, np.uint32)
+    rc = load().vsyn_cqt_lengths(sample_rate, C.byref(spec), _ptr(N), _ptr(L))
+    return rc, N, L
+
+
+def cqt_basis(spec, sample_rate, k):
+    """vsyn_cqt_basis (host only): bin k's wavelet as complex64 [L_k], what the device's table holds. Raises VsynError unless VSYN_OK."""
+    rc, _, L = cqt_lengths(spec, sample_rate)
+    if rc != VSYN_OK or not 0 <= k < spec.n_bins:
+        raise VsynError(rc or VSYN_ERR_INVALID, "vsyn_cqt_lengths refuses the spec, the rate or the bin")
+    out = np.zeros(2 * int(L[k]), np.float32)
+    rc = load().vsyn_cqt_basis(sample_rate, C.byref(spec), k, _ptr(out))
+    if rc != VSYN_OK:
+        raise VsynError(rc, "vsyn_cqt_basis")
+    return out.view(np.complex64)
+
+
+def cq_to_chroma(spec):
+    """vsyn_cq_to_chroma (host only): the 0/1 fold matrix float32 (n_chroma, n_bins). Raises VsynError for an invalid spec."""
+    if not (1 <= spec.n_bins <= 256 and 1 <= spec.n_chroma <= 256):
+        raise VsynError(VSYN_ERR_INVALID, "n_bins or n_chroma outside [1, 256]")
+    out = np.zeros((int(spec.n_chroma), int(spec.n_bins)), np.float32)
+    rc = load().vsyn_cq_to_chroma(C.byref(spec), _ptr(out))
+    if rc != VSYN_OK:
+        raise VsynError(rc, "vsyn_cq_to_chroma")
+    return out
+
+
+def cqt_tile(spec, sample_rate):
+    """vsyn_cqt_tile (host only): (frames per workgroup, samples per chunk, bins per workgroup)."""
+    out = np.zeros(3, np.uint32)
+    rc = load().vsyn_cqt_tile(C.byref(spec), sample_rate, _ptr(out))
+    if rc != VSYN_OK:
+        raise VsynError(rc, "vsyn_cqt_tile")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 _PER_SEGMENT = dict(frames=(np.uint64,), seg_rows=(np.uint64,), peaks=(np.float32,), refs=(np.float64,), counts=(np.uint32,),
@@ -967,6 +1034,20 @@ class Synth:
         rates = _rates(in_rates)
         S, o = len(rates), _per_segment(len(rates), "refused")
         return self._rows_host(self.lib.vsyn_pcm_fdesc_host, (C.byref(spec), S, _ptr(rates), out_rate), S, 6, [o["refused"]], o)
+
+    def cqt_device(self, spec, sample_rates, d_pcm, plane_stride, channels, d_frames, d_rows, d_seg_row_off=None, d_refused=None, stream=None):
+        """vsyn_cqt_device on device pointers (ints); sample_rates is a host sequence (None: NULL)."""
+        rates = _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_cqt_device(self.h, _ref(spec), 0 if rates is None else len(rates), _ptr(rates), d_pcm, plane_stride, channels,
+                                        d_frames, d_rows, d_seg_row_off, d_refused, stream, C.byref(err)), err)
+
+    def pcm_cqt_host(self, spec, in_rates, out_rate=0):
+        """vsyn_pcm_cqt_host over the last submit's segments: returns dict(rc, rows [total][dim], seg_rows [S], refused [S], flags)."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "refused")
+        dim = int(self.lib.vsyn_cqt_dim(C.byref(spec)))
+        return self._rows_host(self.lib.vsyn_pcm_cqt_host, (C.byref(spec), S, _ptr(rates), out_rate), S, max(dim, 1), [o["refused"]], o)
 
     def loudness_device(self, spec, sample_rates, frames, d_pcm, plane_stride, channels, d_records, d_z=None, d_weighted=None,
                         weighted_plane_stride=0, d_scaled=None, scaled_plane_stride=0, stream=None):

@@ -40,6 +40,7 @@
 #include "vsyn_pitch.h"
 #include "vsyn_pyin.h"
 #include "vsyn_fdesc.h"
+#include "vsyn_cqt.h"
 
 static const uint32_t k_inverse_db_bits[256] = {
 #include "vorbis_floor1_inverse_db.inc"
@@ -152,6 +153,7 @@ struct vsyn_handle {
   PitchWs pt;                          // vsyn_pitch.h
   PyinWs py;                           // vsyn_pyin.h
   FdescWs fd;                          // vsyn_fdesc.h
+  CqtWs cq;                            // vsyn_cqt.h
   LoudWs ld;                           // vsyn_loudness.h
   // profiling
   bool profile = false;
@@ -2552,6 +2554,83 @@ int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t S,
       h, spec->n_fft, spec->hop_length, fdesc_center(spec), FDESC_COLS, h->fd.rows, h->fd.refused,
       [&](const PcmView& v, uint64_t f_max, hipStream_t hs) {
         return fdesc_launch(h->fd, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->fd.rows.p, nullptr, h->fd.refused.p, hs, err);
+      },
+      S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
+}
+
+// ---- constant-Q (vsyn_cqt.h) ----
+
+uint32_t vsyn_cqt_dim(const vsyn_cqt_spec* spec) { return cqt_check(spec, 0, nullptr, nullptr) == VSYN_OK ? cqt_dim(spec) : 0u; }
+
+uint64_t vsyn_cqt_num_frames(const vsyn_cqt_spec* spec, uint64_t frames) {
+  if (cqt_check(spec, 0, nullptr, nullptr) != VSYN_OK) return 0;
+  return spec_num_frames(0u, spec->hop_length, true, frames);
+}
+
+int vsyn_cqt_lengths(uint32_t sample_rate, const vsyn_cqt_spec* spec, double* N, uint32_t* L) {
+  if (!sample_rate || cqt_check(spec, 0, nullptr, nullptr) != VSYN_OK) return VSYN_ERR_INVALID;
+  const CqtLengths len = cqt_lengths(spec, sample_rate);
+  for (uint32_t k = 0; k < spec->n_bins; ++k) {
+    if (N) N[k] = len.N[k];
+    if (L) L[k] = len.L[k];
+  }
+  return len.refused ? VSYN_CQT_RATE_REFUSED : cqt_check_caps(len, sample_rate, nullptr);
+}
+
+int vsyn_cqt_basis(uint32_t sample_rate, const vsyn_cqt_spec* spec, uint32_t k, float* re_im) {
+  if (!sample_rate || !re_im || cqt_check(spec, 0, nullptr, nullptr) != VSYN_OK || k >= spec->n_bins) return VSYN_ERR_INVALID;
+  const CqtLengths len = cqt_lengths(spec, sample_rate);
+  if (len.refused) return VSYN_CQT_RATE_REFUSED;
+  if (int rc = cqt_check_caps(len, sample_rate, nullptr)) return rc;
+  cqt_wavelet(spec, sample_rate, len, k, re_im);
+  return VSYN_OK;
+}
+
+int vsyn_cq_to_chroma(const vsyn_cqt_spec* spec, float* out) {
+  if (!out || cqt_check(spec, 0, nullptr, nullptr) != VSYN_OK || !cqt_chroma_out(spec)) return VSYN_ERR_INVALID;
+  std::vector<uint32_t> cls(spec->n_bins);
+  cqt_classes(spec, cls.data());
+  for (uint32_t c = 0; c < spec->n_chroma; ++c)
+    for (uint32_t k = 0; k < spec->n_bins; ++k) out[(size_t)c * spec->n_bins + k] = cls[k] == c ? 1.f : 0.f;
+  return VSYN_OK;
+}
+
+int vsyn_cqt_tile(const vsyn_cqt_spec* spec, uint32_t sample_rate, uint32_t out[3]) {
+  (void)sample_rate;
+  if (!out || cqt_check(spec, 0, nullptr, nullptr) != VSYN_OK) return VSYN_ERR_INVALID;
+  out[0] = CQT_FT;
+  out[1] = VSYN_CQT_CHUNK;
+  out[2] = CQT_BPW;
+  return VSYN_OK;
+}
+
+int vsyn_cqt_device(vsyn_handle* h, const vsyn_cqt_spec* spec, uint32_t S, const uint32_t* sample_rates, const float* d_pcm, uint64_t plane_stride,
+                    uint32_t channels, const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off, uint32_t* d_refused, void* hip_stream,
+                    const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  int rc = cqt_check(spec, S, sample_rates, err);
+  if (rc) return rc;
+  if (channels == 0 || channels > 255) return fail(err, VSYN_ERR_INVALID, "channels %u outside [1, 255]", channels);
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || !d_rows || plane_stride == 0) return fail(err, VSYN_ERR_INVALID, "NULL pointer or zero stride");
+  const uint64_t f_max = spec_num_frames(0u, spec->hop_length, true, plane_stride);
+  std::lock_guard<std::mutex> lk(h->mu);
+  return cqt_launch(h->cq, h->device, spec, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, d_rows, d_seg_row_off,
+                    d_refused, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_pcm_cqt_host(vsyn_handle* h, const vsyn_cqt_spec* spec, uint32_t S, const uint32_t* in_rates, uint32_t out_rate, float* rows,
+                      uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = cqt_check(spec, S, in_rates, err)) return rc;  // (first: an invalid spec writes nothing, the status included)
+  status_reset(status);
+  if (int rc = chain_check(nullptr, nullptr, S, in_rates, out_rate, err)) return rc;
+  const std::vector<uint32_t> cq_rates = stage_rates(S, in_rates, out_rate);
+  const uint32_t* rates = out_rate ? cq_rates.data() : in_rates;
+  return framed_rows_host(
+      h, 0u, spec->hop_length, true, cqt_dim(spec), h->cq.rows, h->cq.refused,
+      [&](const PcmView& v, uint64_t f_max, hipStream_t hs) {
+        return cqt_launch(h->cq, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->cq.rows.p, nullptr, h->cq.refused.p, hs, err);
       },
       S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
 }

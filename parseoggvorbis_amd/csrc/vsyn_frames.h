@@ -1,5 +1,5 @@
 // vsyn_frames.h — what the kernels that cut PCM into frames share: the STFT family (vsyn_spectral.h, vsyn_spectral_lin.h, vsyn_chroma.h,
-// vsyn_istft.h) and the pitch and descriptor stages (vsyn_pitch.h, vsyn_fdesc.h). Every piece exists once, so that a correction to an
+// vsyn_istft.h) and the pitch, descriptor and constant-Q stages (vsyn_pitch.h, vsyn_fdesc.h, vsyn_cqt.h). Every piece exists once, so that a correction to an
 // order of operations reaches every kernel that promises it. All device helpers are inlined into their kernels: no kernel, no launch.
 //   frames_len, spec_num_frames   a segment's PCM frames and the frames a framing cuts from them
 //   frames_stage_direct           a direct-DFT tile's LDS image head: twiddles, window, the tile's padded mono span (downmix while loading)
@@ -9,8 +9,8 @@
 //   frames_stockham_twiddles,     the per-pass twiddle runs and the radix-2 Stockham passes between two LDS buffers, forward and
 //   frames_stockham<INVERSE>      inverse (conjugated twiddles)
 //   frames_tile_head / _derive /  a (tile, segment) workgroup of the pitch and descriptor kernels: its derived quantities, the staged
-//   _stage, frames_offsets,       frames, the non-finite flag word; the offsets and finishing kernels' bodies
-//   frames_finish
+//   _flag / _stage,               frames, the non-finite flag word; the offsets and finishing kernels' bodies
+//   frames_offsets, frames_finish
 // A Ctx template parameter is a stage's launch-argument struct; the helpers read the fields that all of them name alike (pcm, plane, C,
 // frames, si; for the pitch and descriptor stages also S, H, FT, center, tiles, segF, segoff, flags, refused, rows).
 // The host side holds the window and twiddle generators and the launch sequence of the pitch and descriptor stages.
@@ -196,6 +196,20 @@ __device__ __forceinline__ void frames_tile_derive(const Ctx& A, uint32_t L, Fra
   t.base = (int64_t)(t.f0 * A.H) - t.pad;
 }
 
+// The tile's flag word: whether a sample of the workgroup's share of the segment, [its first frame's start, the next tile's), the
+// first tile from 0 and the last up to T, is an Inf or a NaN. Called by the whole workgroup; holds one barrier.
+template <class Ctx>
+__device__ __forceinline__ void frames_tile_flag(const Ctx& A, const FramesTile& t) {
+  const uint32_t tid = threadIdx.x;
+  const int64_t lo = blockIdx.x == 0u ? 0 : (t.base > 0 ? t.base : 0);
+  int64_t hi = t.last ? (int64_t)t.T : (int64_t)((t.f0 + A.FT) * A.H) - t.pad;
+  if (hi > (int64_t)t.T) hi = (int64_t)t.T;
+  bool bad = false;
+  for (int64_t s = lo + tid; s < hi; s += FRAMES_THREADS) bad |= trim_not_finite(pcm_downmix(t.x, A.plane, t.C, t.inv_c, (uint64_t)s));
+  const int any = __syncthreads_or(bad ? 1 : 0);
+  if (tid == 0) *t.flag = any ? 1u : 0u;
+}
+
 // The tile's frames as float32 into s_y (the downmix is done while loading, zeros outside [0, T)), and the flag word: whether a sample
 // of the workgroup's share of the segment, [its first frame's start, the next tile's), the first tile from 0 and the last up to T, is
 // an Inf or a NaN. Ends behind a barrier.
@@ -208,13 +222,7 @@ __device__ __forceinline__ void frames_tile_stage(const Ctx& A, const FramesTile
     const int64_t s = apart ? base + (int64_t)(u / L) * H + (u % L) : base + u;
     s_y[u] = (s >= 0 && (uint64_t)s < t.T) ? pcm_downmix(t.x, A.plane, t.C, t.inv_c, (uint64_t)s) : 0.f;
   }
-  const int64_t lo = blockIdx.x == 0u ? 0 : (base > 0 ? base : 0);
-  int64_t hi = t.last ? (int64_t)t.T : (int64_t)((t.f0 + A.FT) * H) - t.pad;
-  if (hi > (int64_t)t.T) hi = (int64_t)t.T;
-  bool bad = false;
-  for (int64_t s = lo + tid; s < hi; s += FRAMES_THREADS) bad |= trim_not_finite(pcm_downmix(t.x, A.plane, t.C, t.inv_c, (uint64_t)s));
-  const int any = __syncthreads_or(bad ? 1 : 0);  // (also the barrier behind the staging)
-  if (tid == 0) *t.flag = any ? 1u : 0u;
+  frames_tile_flag(A, t);  // (also the barrier behind the staging)
 }
 
 // One workgroup: per segment its frame count under frames of L samples (0 where skip(g)) and the exclusive row scan segoff[S+1].
@@ -301,11 +309,15 @@ static inline int frames_begin(Ws& ws, int device, const std::vector<uint8_t>& t
   return VSYN_OK;
 }
 
-// The stage's three kernels on stream s: offsets, one workgroup per (tile, segment) with lds bytes of dynamic LDS, finish.
+// The stage's three kernels on stream s: offsets, one workgroup per (tile, segment) with lds bytes of dynamic LDS, finish. The
+// constant-Q stage (vsyn_cqt.h) runs gz workgroups per (tile, segment), one per group of bins (blockIdx.z), and for its chroma
+// outputs a fold kernel per (tile, segment) in front of the finishing one.
 template <class Ctx>
-static inline int frames_launch(const Ctx& A, void (*offsets)(Ctx), void (*tile)(Ctx), size_t lds, void (*finish)(Ctx), hipStream_t s, const char** err) {
+static inline int frames_launch(const Ctx& A, void (*offsets)(Ctx), void (*tile)(Ctx), size_t lds, void (*finish)(Ctx), hipStream_t s, const char** err,
+                                uint32_t gz = 1u, void (*fold)(Ctx) = nullptr) {
   VSYN_LAUNCH(offsets, dim3(1), dim3(FRAMES_THREADS), 0, s, A);
-  VSYN_LAUNCH(tile, dim3(A.tiles, A.S), dim3(FRAMES_THREADS), lds, s, A);
+  VSYN_LAUNCH(tile, dim3(A.tiles, A.S, gz), dim3(FRAMES_THREADS), lds, s, A);
+  if (fold) VSYN_LAUNCH(fold, dim3(A.tiles, A.S), dim3(FRAMES_THREADS), 0, s, A);
   VSYN_LAUNCH(finish, dim3(A.S), dim3(FRAMES_THREADS), 0, s, A);
   return VSYN_OK;
 }

@@ -84,6 +84,7 @@ bool spectral_run(const CorpusOptions& o) { return o.spectral.kind != 0; }
 bool pitch_run(const CorpusOptions& o) { return o.pitch.frame_length != 0; }
 bool pyin_run(const CorpusOptions& o) { return o.pyin.frame_length != 0; }
 bool fdesc_run(const CorpusOptions& o) { return o.fdesc.n_fft != 0; }
+bool cqt_run(const CorpusOptions& o) { return o.cqt.n_bins != 0; }
 bool loudness_run(const CorpusOptions& o) { return o.loudness; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
@@ -793,6 +794,45 @@ struct Feeder {
     });
   }
 
+  // Constant-Q run: each file's rows from the PCM still on the device (vsyn_pcm_cqt_host, resampled first in a resampled run). A file
+  // whose rate makes a wavelet or the table longer than the stage's caps gets no rows and an error of its own; so does a file the
+  // stage refuses, and the error says whether a sample is not finite or the top bin leaves the Nyquist band at its rate.
+  OkOrError cqt_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size(), cols = vsyn_cqt_dim(&opts.cqt);
+    std::vector<uint32_t> rates(S), srs(S);
+    uint64_t rows = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      const uint32_t in = g.pending[s]->header.audio_sample_rate;
+      srs[s] = opts.resample_rate ? opts.resample_rate : in;  // the rate the rows are computed at
+      if (o.err[s].empty() && srs[s] && vsyn_cqt_lengths(srs[s], &opts.cqt, nullptr, nullptr) == VSYN_ERR_INVALID) {
+        char buf[200];
+        snprintf(buf, sizeof(buf), "constant-Q: at sample rate %u the wavelets are longer than the stage's caps (one of %u, all of %u samples)", srs[s],
+                 VSYN_CQT_MAX_LENGTH, VSYN_CQT_MAX_TABLE);
+        o.err[s] = buf;
+      }
+      rates[s] = o.err[s].empty() ? in : 0;
+      if (rates[s]) rows += vsyn_cqt_num_frames(&opts.cqt, std::min<uint64_t>(o.frames[s], o.plane));
+    }
+    CHECK_ERR(g.rows.ensure(rows * cols + 1));
+    CHECK_ERR(g.seg_rows.ensure(S));
+    std::vector<uint32_t> refused(S, 0u);
+    vsyn_status st;
+    const char* err = nullptr;
+    if (vsyn_pcm_cqt_host(g.handle, &opts.cqt, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused.data(), &st, &err) != VSYN_OK)
+      return OkOrError(std::string("GPU constant-Q layer: ") + (err ? err : "constant-Q failed"));
+    for (uint32_t s = 0; s < S; ++s) {
+      if (!o.err[s].empty() || !refused[s]) continue;
+      if (refused[s] == VSYN_CQT_RATE) {
+        char buf[200];
+        snprintf(buf, sizeof(buf), "constant-Q: the top bin's pass band leaves the Nyquist band at sample rate %u", srs[s]);
+        o.err[s] = buf;
+      } else {
+        o.err[s] = "constant-Q: the PCM holds a sample that is not finite";
+      }
+    }
+    return OkOrError();
+  }
+
   // Loudness run: each file's record (and block means) from the PCM still on the device (vsyn_pcm_loudness_host, resampled first in
   // a resampled run). A silent file is measured; a file the stage refuses gets an error of its own, by name.
   OkOrError loudness_stage(Group& g, Outcome& o) {
@@ -821,7 +861,7 @@ struct Feeder {
   // A synthesis run's file: its PCM (or, for a spectral, pitch or frame descriptor run, its rows) to the callbacks.
   OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
     const uint32_t C = opts.condition ? 1u : g.channels;  // channels delivered
-    const bool spectral = spectral_run(opts) || pitch_run(opts) || pyin_run(opts) || fdesc_run(opts) || loudness_run(opts);
+    const bool spectral = spectral_run(opts) || pitch_run(opts) || pyin_run(opts) || fdesc_run(opts) || cqt_run(opts) || loudness_run(opts);
     const uint64_t frames = o.frames[s], pl = o.plane;
     if (opts.condition) out.channels = 1;
     std::vector<DataRange<const float>> chans(C);
@@ -856,7 +896,7 @@ struct Feeder {
       if (s < o.loud_nb.size()) row0 += o.loud_nb[s];
       return OkOrError();
     }
-    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : pyin_run(opts) ? 3u : fdesc_run(opts) ? 6u : spectral_dim(opts));
+    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : pyin_run(opts) ? 3u : fdesc_run(opts) ? 6u : cqt_run(opts) ? vsyn_cqt_dim(&opts.cqt) : spectral_dim(opts));
     if (!callbacks || !o.err[s].empty() || opts.intervals_only) return OkOrError();
     std::lock_guard<std::mutex> lk(callbacks_mu);
     if (opts.pcm_s16) {
@@ -871,8 +911,8 @@ struct Feeder {
     if (g.pending.empty()) return OkOrError();
     if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
-    const bool pitch = pitch_run(opts), pyin = pyin_run(opts), fdesc = fdesc_run(opts), loud = loudness_run(opts);
-    const bool spectral = spectral_run(opts) || pitch || pyin || fdesc || loud;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
+    const bool pitch = pitch_run(opts), pyin = pyin_run(opts), fdesc = fdesc_run(opts), cqt = cqt_run(opts), loud = loudness_run(opts);
+    const bool spectral = spectral_run(opts) || pitch || pyin || fdesc || cqt || loud;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
     const bool cond = opts.condition;               // ... and until it is conditioned
     double t0 = now_s();
@@ -906,6 +946,7 @@ struct Feeder {
       else if (pitch) CHECK_ERR(pitch_stage(g, o));
       else if (pyin) CHECK_ERR(pyin_stage(g, o));
       else if (fdesc) CHECK_ERR(fdesc_stage(g, o));
+      else if (cqt) CHECK_ERR(cqt_stage(g, o));
       else if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
     double t2 = now_s();
@@ -1687,6 +1728,22 @@ extern "C" int ogg_vorbis_fdesc_corpus(const uint8_t* const* datas, const size_t
   opts.fdesc = *spec;
   opts.resample_rate = target_rate;
   return malloc_corpus("fdesc", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                       });
+}
+
+extern "C" int ogg_vorbis_cqt_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                     uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_cqt_spec* spec, float** rows_out,
+                                     uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                                     const char** error_out_per_file, double* stats_out, const char** error_out) {
+  if (!spec || !vsyn_cqt_dim(spec)) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_cqt_corpus: invalid constant-Q spec", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  opts.cqt = *spec;
+  opts.resample_rate = target_rate;
+  return malloc_corpus("cqt", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
                        [&](size_t i, const CorpusFileResult& res, bool bad) {
                          if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
                          if (frames_out) frames_out[i] = bad ? 0 : res.frames;

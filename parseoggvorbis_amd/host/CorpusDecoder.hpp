@@ -130,6 +130,11 @@ struct CorpusOptions {
   // (include/vorbis_synth_hip.h, "frame descriptors": vsyn_pcm_fdesc_host), delivered through gotFileFeatures with dim 6. A file with
   // a sample that is not finite fails alone. Excludes what a pitch run excludes, and pitch.
   vsyn_fdesc_spec fdesc = {0, 0, 0, 0, 0.0, 0.0, 0.0};
+  // constant-Q run (cqt.n_bins != 0): as a pitch run, but each file's constant-Q, chroma_cqt or tonnetz rows (include/vorbis_synth_hip.h,
+  // "constant-Q": vsyn_pcm_cqt_host), delivered through gotFileFeatures with dim vsyn_cqt_dim(&cqt). A file with a sample that is not
+  // finite, a file at whose rate the top bin leaves the Nyquist band and a file whose rate makes the wavelets longer than the stage's
+  // caps fail alone, by name. Excludes what a pitch run excludes, pitch and fdesc.
+  vsyn_cqt_spec cqt = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
   // loudness run (loudness): as a pitch run, but each file's integrated loudness record (include/vorbis_synth_hip.h, "loudness":
   // vsyn_pcm_loudness_host, resampled first with resample_rate; loudness_spec.channel_mode picks the planes or their downmix) into
   // CorpusFileResult::loudness, and with loudness_blocks the block means into CorpusFileResult::loudness_blocks; nothing goes to the
@@ -416,6 +421,13 @@ int ogg_vorbis_fdesc_corpus(const uint8_t* const* datas, const size_t* lens, siz
                             uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_fdesc_spec* spec, float** rows_out,
                             uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
                             const char** error_out_per_file, double* stats_out, const char** error_out);
+// constant-Q run (CorpusOptions::cqt = *spec; target_rate as for ogg_vorbis_pitch_corpus): rows_out receives per file NULL (failed,
+// or no rows) or a buffer of rows_count_out[i] * vsyn_cqt_dim(spec) floats, released with ogg_vorbis_features_free. An invalid spec
+// refuses the call before any file is touched.
+int ogg_vorbis_cqt_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                          uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_cqt_spec* spec, float** rows_out,
+                          uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
+                          const char** error_out_per_file, double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
 }
 
