@@ -588,7 +588,9 @@ uint32_t vsyn_spectral_lin_tile(const vsyn_spectral_spec* spec);
  *  6. Checked (VSYN_ERR_INVALID before anything runs): the option bits, n_fft, hop_length, win_length and power as for "linear
  *     spectra"; 1 <= n_chroma <= 256; norm in 0 .. 3; no unknown chroma option bits; tuning and ctroct finite; octwidth finite and
  *     > 0 unless VSYN_CHROMA_NO_OCT. Not read and not checked: the mel fields, amin, top_db, log_floor. A rate of 0 skips its
- *     segment. tuning is always a number: librosa's tuning = None (estimate_tuning) is not built.
+ *     segment. tuning is a number here: the estimate that librosa's tuning = None runs first is a stage of its own ("tuning
+ *     estimation"), which vsyn_pcm_chain_chroma_est_host runs in front of the filterbank per segment and a caller of the
+ *     asynchronous entry chains in front himself (vsyn_tuning_device).
  *  7. PCEN is refused for both kinds. The post stage ("spectral post-processing") is accepted for both: their rows are at most 256
  *     columns wide.
  *
@@ -637,6 +639,99 @@ uint32_t vsyn_spectral_chroma_tile(const vsyn_spectral_spec* spec);
 int vsyn_spectral_chroma_device(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma, uint32_t num_segments,
                                 const uint32_t* sample_rates, const float* d_pcm, uint64_t plane_stride, uint32_t channels,
                                 const uint32_t* d_frames, float* d_rows, uint64_t* d_seg_row_off, void* hip_stream, const char** err);
+
+/* ---- tuning estimation: spectral peaks (librosa.piptrack) and the tuning taken from them (librosa.estimate_tuning), where the PCM is ----
+ *
+ * librosa is not among the test dependencies and parity with it is not claimed: the contract is the arithmetic below and a float64
+ * model of it (tests/tuning_model.py). The result is the number that vsyn_spectral_chroma.tuning (with n_chroma = bins_per_octave)
+ * and vsyn_cqt_spec.tuning take: a deviation from A440 in fractions of a bin of bins_per_octave.
+ *
+ *  1. Spectrum. Per segment and frame f, S[k], k < NB = n_fft / 2 + 1, is the float32 value of VSYN_SPEC_LIN_POWER ("linear
+ *     spectra") at the same n_fft, hop_length, win_length, centring and power (1 or 2), bit for bit. It stays in LDS.
+ *  2. Searched bins, on the host in double, per distinct rate sr: fmin' = max(fmin, 0), fmax' = min(fmax, sr / 2); [k_lo, k_hi) holds
+ *     the bins k < NB with fmin' <= k sr / n_fft < fmax' (vsyn_piptrack_bins; k_lo = k_hi = 0 when there is none).
+ *  3. Peaks, in float32 unless stated. ref = threshold32 * max_k S[k], the maximum over all NB bins and threshold32 the threshold
+ *     rounded to float32; Z[k] = S[k] > ref ? S[k] : 0. Bin k is a peak when k_lo <= k < k_hi, Z[k] > Z[k-1] and Z[k] >= Z[k+1], with
+ *     replicated edges Z[-1] = Z[0], Z[NB] = Z[NB-1]: bin 0 is never a peak, the last bin can be one.
+ *  4. Interpolation at a peak. For 1 <= k <= NB - 2: a = 0.5f * (S[k+1] - S[k-1]), b = (2 S[k] - S[k+1]) - S[k-1], and b = b + 1 if
+ *     |b| < FLT_MIN; s = a / b. At k = 0 and k = NB - 1, a = s = 0. pitch = float32(((double)k + (double)s) * ((double)sr / n_fft)),
+ *     mag = S[k] + (0.5f * a) * s. Every bin that is no peak holds 0 in both outputs. The library is built without fused contraction.
+ *  5. A frame with any S[k] that is not finite (an Inf or NaN sample inside it, or an overflow) has NaN in every value of both its
+ *     rows and contributes no peak to the tuning; other frames are not touched.
+ *  6. Tuning, per segment over all its frames. P = the entries with pitch > 0, n = |P|. n = 0: the tuning is 0.0. Else the threshold
+ *     is the median of mag over P: n odd, the middle element of the ascending float32 order; n even, (lo + hi) / 2 of the two middle
+ *     ones rounded in float32 (numpy.median of a float32 array). Selected are the entries of P with mag >= threshold.
+ *  7. Residual of a selected entry, in double: r = fmod(bins_per_octave * log2((double)pitch / 27.5), 1.0), and r = r - 1 if r >= 0.5.
+ *     librosa takes this residual in float32; double is chosen here because every platform's double log2 agrees to an ulp or two,
+ *     which the histogram's edges absorb, while a float32 chain would tie the result to one libm. fmod keeps the sign of its first
+ *     argument: a pitch below 27.5 Hz can give r < -0.5, and such an entry is selected and counted nowhere.
+ *  8. Histogram. nbin = ceil(1 / resolution); edges e_i = -0.5 + i * (1.0 / nbin), i = 0 .. nbin, built on the host in double. An entry
+ *     counts in the bin i with e_i <= r < e_{i+1}: floor((r + 0.5) nbin), corrected by at most one against the table. The tuning is e_i
+ *     of the FIRST bin with the largest count, a double. counts = {n, number selected}.
+ *  9. Checked (VSYN_ERR_INVALID before anything runs): the spectral spec as for "linear spectra", and its kind must be
+ *     VSYN_SPEC_LIN_POWER (power 1 or 2); fmin and fmax finite with fmax > fmin'; threshold finite and >= 0; resolution finite with
+ *     0 < resolution < 1 and nbin <= 4096; 1 <= bins_per_octave <= 256; reserved 0. A call in which a segment could hold more than
+ *     2^31 peaks (frames times half the searched bins) is refused. A rate of 0 skips its segment: no rows, tuning 0.0, counts 0.
+ *
+ * Arithmetic: no floating-point atomics anywhere. One wave per frame takes the maximum in an xor-shuffle tree and walks the bins 64
+ * at a time in ascending order, one lane per bin; a frame's peaks are compacted in ascending k by ballot and prefix count into the
+ * frame's own run of the workspace. The median is an exact selection on the float32 bit patterns by integer counting (8 bits a pass),
+ * the histogram's counts are integers. The same PCM gives the same bits alone, in any slot of a batch and wherever a frame falls in
+ * its workgroup's tile.
+ *
+ * Workspace: the entries of this section use the handle's spectral table and frame counts, as every spectral and chroma entry does:
+ * calls of these entries on one handle must be ordered on one stream (or by the caller) among themselves and with those. The peak
+ * records are sized from plane_stride (frames it could hold times cap), not from the segments' actual lengths, and a call that
+ * needs more room than the last frees and allocates, which waits for the device.
+ *
+ * In front of the pitch-class features: vsyn_pcm_chain_chroma_est_host ("chroma") and vsyn_pcm_cqt_est_host ("constant-Q") run the
+ * estimate per segment and build their tables per (rate, tuning) pair. Deliberately not built: piptrack's ref callable (ref is
+ * always threshold * the frame's maximum); windows other than Hann; librosa's float32 residual (step 7); the estimate inside the
+ * asynchronous vsyn_spectral_chroma_device and vsyn_cqt_device, which keep taking a number: the tables are built on the host from
+ * numbers the device has yet to compute, so a caller chains vsyn_tuning_device in front and passes each tuning on. */
+#define VSYN_TUNING_ONLY 0u /* vsyn_pcm_tuning_host: the tuning and the counts */
+#define VSYN_TUNING_ROWS 1u /* ... and the dense piptrack rows */
+
+typedef struct vsyn_tuning_spec { /* 40 bytes */
+  double fmin, fmax;        /* the searched band in Hz (librosa: 150, 4000) */
+  double threshold;         /* of the frame's maximum (librosa: 0.1) */
+  double resolution;        /* the histogram's bin width in fractions of a bin (librosa: 0.01) */
+  uint32_t bins_per_octave; /* 1 .. 256 (librosa: 12) */
+  uint32_t reserved;        /* 0 */
+} vsyn_tuning_spec;
+
+/* Host only, no device and no handle: step 9 on (spec, tun), VSYN_OK or VSYN_ERR_INVALID with *err (may be NULL) naming the refusal. */
+int vsyn_tuning_check(const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, const char** err);
+/* Host only: out = {k_lo, k_hi} of step 2 at sample_rate. VSYN_ERR_INVALID for a NULL out, a rate of 0 or what step 9 refuses. */
+int vsyn_piptrack_bins(uint32_t sample_rate, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t out[2]);
+/* Host only: steps 6 to 8 on host arrays freqs[n] and mags[n] (librosa.pitch_tuning behind estimate_tuning's median threshold). With
+ * mags NULL every entry with freqs > 0 is selected, which is plain pitch_tuning. *tuning and counts = {n of step 6, selected} are
+ * written. VSYN_ERR_INVALID (nothing written) for a NULL output, a resolution or bins_per_octave that step 9 refuses, or more than
+ * 2^31 entries with freqs > 0. */
+int vsyn_pitch_tuning(const float* freqs, const float* mags, uint64_t n, double resolution, uint32_t bins_per_octave, double* tuning,
+                      uint64_t counts[2]);
+/* Frames that one workgroup of the piptrack kernels computes under spec (a tuning fact, exposed for tests that place frame counts
+ * around it); 0 for an invalid spec or a kind other than VSYN_SPEC_LIN_POWER. */
+uint32_t vsyn_piptrack_tile(const vsyn_spectral_spec* spec);
+/* The caller's planar PCM, as for vsyn_spectral_device. vsyn_piptrack_device writes d_seg_row_off[S+1] (uint64, may be NULL) and the
+ * dense rows of steps 3 to 5 into d_pitches and d_mags, each sum_g vsyn_spectral_num_frames(spec, frames_g) rows of NB float32.
+ * vsyn_tuning_device writes d_tuning[S] (double) and d_counts[S][2] (uint64: n, selected) of steps 6 to 8; the peaks go through the
+ * handle's workspace, never through dense rows. Both asynchronous on hip_stream. */
+int vsyn_piptrack_device(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t num_segments,
+                         const uint32_t* sample_rates, const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames,
+                         float* d_pitches, float* d_mags, uint64_t* d_seg_row_off, void* hip_stream, const char** err);
+int vsyn_tuning_device(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t num_segments,
+                       const uint32_t* sample_rates, const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames,
+                       double* d_tuning, uint64_t* d_counts, void* hip_stream, const char** err);
+/* The PCM of the MOST RECENT vsyn_submit_host* on this handle, as for vsyn_pcm_cqt_host: each segment resampled from in_rates[g] to
+ * out_rate first when out_rate != 0. seg_rows[S] always receives each segment's frame count. what = VSYN_TUNING_ONLY: tuning[S] and
+ * counts[S][2] (counts may be NULL); with a NULL tuning nothing is launched. what = VSYN_TUNING_ROWS: the dense rows of all segments
+ * back to back into rows, 2 NB float32 a row (its NB pitches, then its NB magnitudes), at most rows_capacity rows (VSYN_ERR_INVALID
+ * with seg_rows filled if that is too small; with a NULL rows nothing is launched), and the tuning as well where tuning is not NULL.
+ * status as for vsyn_pcm_spectral_host. Synchronous. */
+int vsyn_pcm_tuning_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t num_segments,
+                         const uint32_t* in_rates, uint32_t out_rate, uint32_t what, double* tuning, uint64_t* counts, float* rows,
+                         uint64_t rows_capacity, uint64_t* seg_rows, vsyn_status* status, const char** err);
 
 /* ---- resampling: polyphase resampling of the decoded PCM to a target sample rate, computed where the PCM is ----
  *
@@ -1388,11 +1483,11 @@ int vsyn_pcm_fdesc_host(vsyn_handle* h, const vsyn_fdesc_spec* spec, uint32_t nu
  *     VSYN_CQT_MAX_TABLE (2^23 pairs, 64 MB).
  *
  * Deliberately not built: librosa's FFT-basis route and its sparsity; hybrid_cqt, pseudo_cqt, icqt, griffinlim_cqt; chroma_cens;
- * chroma_cqt's threshold and smoothing window; windows other than Hann; tuning=None (estimation); dB output; composition with the
- * trim, split, conditioning, delta, normalisation and HPSS stages; MFMA. The same PCM gives the same bits, alone, in any slot of a
+ * chroma_cqt's threshold and smoothing window; windows other than Hann; tuning = None inside vsyn_cqt_device (vsyn_pcm_cqt_est_host
+ * below estimates first); dB output; composition with the trim, split, conditioning, delta, normalisation and HPSS stages; MFMA. The same PCM gives the same bits, alone, in any slot of a
  * batch and at any alignment. The entry points read PCM only: they touch neither stream state, the overlap buffers nor the PCM kept
  * by VSYN_SUBMIT_KEEP_PCM. One handle's constant-Q entry points share its constant-Q workspace, which is no other stage's; the
- * wavelet tables of the last call's (spec, rates) stay there, on the host and on the device. */
+ * wavelet tables of the last call's spec and (rate, tuning) pairs stay there, on the host and on the device. */
 #define VSYN_CQT_SCALE 1u  /* s_k = sqrt(N_k) (librosa's scale=True) */
 #define VSYN_CQT_BASE_C 2u /* chroma outputs: row 0 is C, else A */
 #define VSYN_CQT_MAG 1u
@@ -1459,6 +1554,19 @@ int vsyn_cqt_device(vsyn_handle* h, const vsyn_cqt_spec* spec, uint32_t num_segm
 int vsyn_pcm_cqt_host(vsyn_handle* h, const vsyn_cqt_spec* spec, uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate,
                       float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, vsyn_status* status,
                       const char** err);
+
+/* vsyn_pcm_cqt_host with each segment's tuning estimated first ("tuning estimation"; librosa's tuning = None). estimate NULL: that
+ * entry, tuning_out not written. Otherwise estimate->bins_per_octave must equal spec->bins_per_octave; spec->tuning is still checked
+ * and is not used. The estimate runs on the mono signal the transform sees (after the resampler) with librosa.cqt's own framing of
+ * it: n_fft 2048, hop 512, Hann, centred, power 1. The tunings are read back (one more wait), the wavelets are built on the host by
+ * the one builder for the distinct (rate, tuning) pairs of the call, and a segment's table entry indexes the pairs: segment g's rows
+ * are, bit for bit, those of vsyn_pcm_cqt_host called with spec->tuning = tuning_out[g]. The handle keeps ONE wavelet table, the
+ * last call's: a tuning is a multiple of 1 / nbin, so a call holds at most nbin = ceil(1 / resolution) sets of wavelets per rate,
+ * each under the caps of step 11, and a call whose sets exceed the table's 4 GiB is refused by name. tuning_out[S] receives the
+ * estimates (0.0 for a segment of rate 0). */
+int vsyn_pcm_cqt_est_host(vsyn_handle* h, const vsyn_cqt_spec* spec, const vsyn_tuning_spec* estimate, uint32_t num_segments,
+                          const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                          uint32_t* refused_out, double* tuning_out, vsyn_status* status, const char** err);
 
 /* ---- loudness: the integrated loudness of the decoded PCM (ITU-R BS.1770-4 / EBU R 128) and the gain to a target, computed where the PCM is ----
  *
@@ -1605,6 +1713,24 @@ int vsyn_pcm_chain_chroma_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
                                uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint64_t* frames_out,
                                uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out,
                                double* refs_out, vsyn_loudness_record* records_out, vsyn_status* status, const char** err);
+
+/* vsyn_pcm_chain_chroma_host with each segment's tuning estimated first ("tuning estimation"; librosa's tuning = None). estimate NULL:
+ * that entry, and tuning_out is not written. Otherwise spec->kind must be CHROMA or TONNETZ and estimate->bins_per_octave must equal
+ * n_chroma (the unit of the tuning); chroma->tuning is still checked and is not used. The estimate runs on the PCM the chroma kernel
+ * sees (after resample, trim or split, loudness and conditioning) at the call's own n_fft, hop_length, win_length, centring and
+ * POWER: librosa's chroma_stft hands its power spectrogram to the estimator, and that quirk is kept. The tunings are read back (one
+ * more wait; the entry is synchronous already), the filterbanks are built on the host by the one builder for the distinct
+ * (rate, tuning) pairs of the call and kept for the next call with the same pairs, and the chroma kernels read a per-segment bank
+ * index where they read the rate index otherwise: segment g's rows are, bit for bit, those of vsyn_pcm_chain_chroma_host called with
+ * chroma->tuning = tuning_out[g]. tuning_out[S] receives the estimates (0.0 for a segment without rows). A call whose filterbanks
+ * would exceed the table's 4 GiB is refused by name. */
+int vsyn_pcm_chain_chroma_est_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                                   const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                                   const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_tuning_spec* estimate,
+                                   uint32_t num_segments, const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity,
+                                   uint64_t* seg_rows, uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out,
+                                   uint32_t* intervals_out, uint64_t intervals_stride, float* peaks_out, double* refs_out,
+                                   vsyn_loudness_record* records_out, double* tuning_out, vsyn_status* status, const char** err);
 
 /* ---- HPSS: harmonic-percussive separation of spectral rows by median filtering, computed where the rows are ----
  *

@@ -1,4 +1,4 @@
-"""ctypes plumbing of the corpus front-ends (features.py, spectral.py, pcm.py, pitch.py, frame_descriptors.py, cqt.py, loudness.py): the corpus entry points of libparseoggvorbis_amd.so
+"""ctypes plumbing of the corpus front-ends (features.py, spectral.py, pcm.py, pitch.py, frame_descriptors.py, cqt.py, tuning.py, loudness.py): the corpus entry points of libparseoggvorbis_amd.so
 and the per-file loop over the buffers they hand back (include/vorbis_synth_hip.h documents what they compute)."""
 import ctypes as C
 import os
@@ -48,6 +48,9 @@ def load():
                        ("ogg_vorbis_pyin_corpus", [u32, C.POINTER(binding.PyinSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_fdesc_corpus", [u32, C.POINTER(binding.FdescSpec), vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_cqt_corpus", [u32, C.POINTER(binding.CqtSpec), vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_cqt_corpus_est", [u32, C.POINTER(binding.CqtSpec), C.POINTER(binding.TuningSpec), vp, vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_tuning_corpus", [u32, C.POINTER(binding.SpectralSpec), C.POINTER(binding.TuningSpec), C.c_int, vp, vp, vp,
+                                                     vp, vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus_loud", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
                                                        C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_pcm_corpus_effects", [u32, C.c_int, C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
@@ -64,6 +67,11 @@ def load():
                                                               C.POINTER(binding.SpectralPcen), C.POINTER(binding.SpectralPost),
                                                               C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
                                                               C.POINTER(binding.LoudnessSpec), vp, vp, vp, vp, vp, vp, vp, vp]),
+                       ("ogg_vorbis_spectral_corpus_chroma_est", [C.POINTER(binding.SpectralSpec), C.POINTER(binding.SpectralChroma), u32,
+                                                                  C.POINTER(binding.SpectralPcen), C.POINTER(binding.SpectralPost),
+                                                                  C.POINTER(binding.PcmCond), C.POINTER(binding.PcmTrim), C.c_int,
+                                                                  C.POINTER(binding.LoudnessSpec), C.POINTER(binding.TuningSpec), vp, vp, vp,
+                                                                  vp, vp, vp, vp, vp, vp]),
                        ("ogg_vorbis_spectral_corpus_hpss", [C.POINTER(binding.SpectralSpec), C.POINTER(binding.SpectralChroma), u32,
                                                             C.POINTER(binding.SpectralHpss), C.POINTER(binding.SpectralPcen),
                                                             C.POINTER(binding.SpectralPost), C.POINTER(binding.PcmCond),

@@ -174,6 +174,14 @@ VSYN_CQT_RATE_REFUSED = 100  # vsyn_cqt_lengths / vsyn_cqt_basis: step 10 refuse
 VSYN_CQT_MAX_LENGTH, VSYN_CQT_MAX_TABLE = 1 << 17, 1 << 23
 
 
+class TuningSpec(C.Structure):  # vsyn_tuning_spec, 40 bytes
+    _fields_ = [("fmin", C.c_double), ("fmax", C.c_double), ("threshold", C.c_double), ("resolution", C.c_double),
+                ("bins_per_octave", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+VSYN_TUNING_ONLY, VSYN_TUNING_ROWS = 0, 1
+
+
 class LoudnessSpec(C.Structure):  # vsyn_loudness_spec
     _fields_ = [("options", C.c_uint32), ("channel_mode", C.c_uint32), ("target", C.c_double)]
 
@@ -327,6 +335,8 @@ _SYMBOLS = [
     "vsyn_pcm_chain_host", "vsyn_pcm_chain_spectral_host",
     "vsyn_spectral_chroma_dim", "vsyn_chroma_filterbank", "vsyn_spectral_chroma_tile", "vsyn_spectral_chroma_device",
     "vsyn_pcm_chain_chroma_host",
+    "vsyn_tuning_check", "vsyn_piptrack_bins", "vsyn_pitch_tuning", "vsyn_piptrack_tile", "vsyn_piptrack_device", "vsyn_tuning_device",
+    "vsyn_pcm_tuning_host", "vsyn_pcm_chain_chroma_est_host", "vsyn_pcm_cqt_est_host",
     "vsyn_spectral_hpss_device", "vsyn_pcm_chain_hpss_host",
     "vsyn_onset_peak_windows", "vsyn_tempogram_win_length", "vsyn_tempogram_tile", "vsyn_tempo_from_mean",
     "vsyn_onset_strength_device", "vsyn_onset_peaks_device", "vsyn_tempogram_device", "vsyn_pcm_chain_rhythm_host",
@@ -468,6 +478,7 @@ def load():
     lib.vsyn_cqt_tile.argtypes = [C.POINTER(CqtSpec), u32, vp]
     lib.vsyn_cqt_device.argtypes = [vp, C.POINTER(CqtSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
     lib.vsyn_pcm_cqt_host.argtypes = [vp, C.POINTER(CqtSpec), u32, vp, u32, vp, u64, vp, vp, C.POINTER(Status), cpp]
+    lib.vsyn_pcm_cqt_est_host.argtypes = [vp, C.POINTER(CqtSpec), C.POINTER(TuningSpec), u32, vp, u32, vp, u64, vp, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_loudness_num_blocks.argtypes = [u32, u64]
     lib.vsyn_loudness_num_blocks.restype = u64
     lib.vsyn_loudness_coefficients.argtypes = [u32, vp]
@@ -489,6 +500,19 @@ def load():
                                                C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralPcen),
                                                C.POINTER(SpectralPost), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp,
                                                C.POINTER(Status), cpp]
+    lib.vsyn_tuning_check.argtypes = [C.POINTER(SpectralSpec), C.POINTER(TuningSpec), cpp]
+    lib.vsyn_piptrack_bins.argtypes = [u32, C.POINTER(SpectralSpec), C.POINTER(TuningSpec), vp]
+    lib.vsyn_pitch_tuning.argtypes = [vp, vp, u64, C.c_double, u32, vp, vp]
+    lib.vsyn_piptrack_tile.argtypes = [C.POINTER(SpectralSpec)]
+    lib.vsyn_piptrack_tile.restype = u32
+    lib.vsyn_piptrack_device.argtypes = [vp, C.POINTER(SpectralSpec), C.POINTER(TuningSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, vp, cpp]
+    lib.vsyn_tuning_device.argtypes = [vp, C.POINTER(SpectralSpec), C.POINTER(TuningSpec), u32, vp, vp, u64, u32, vp, vp, vp, vp, cpp]
+    lib.vsyn_pcm_tuning_host.argtypes = [vp, C.POINTER(SpectralSpec), C.POINTER(TuningSpec), u32, vp, u32, u32, vp, vp, vp, u64, vp,
+                                         C.POINTER(Status), cpp]
+    lib.vsyn_pcm_chain_chroma_est_host.argtypes = [vp, C.POINTER(PcmTrim), C.c_int, C.POINTER(LoudnessSpec), C.POINTER(PcmCond),
+                                                   C.POINTER(SpectralSpec), C.POINTER(SpectralChroma), C.POINTER(SpectralPcen),
+                                                   C.POINTER(SpectralPost), C.POINTER(TuningSpec), u32, vp, u32, vp, u64, vp, vp, vp, vp, vp,
+                                                   u64, vp, vp, vp, vp, C.POINTER(Status), cpp]
     lib.vsyn_spectral_hpss_device.argtypes = [vp, C.POINTER(SpectralHpss), u32, u32, vp, vp, vp, vp, cpp]
     lib.vsyn_istft_num_samples.argtypes = [C.POINTER(SpectralSpec), u64]
     lib.vsyn_istft_num_samples.restype = u64
@@ -610,6 +634,35 @@ def cq_to_chroma(spec):
     if rc != VSYN_OK:
         raise VsynError(rc, "vsyn_cq_to_chroma")
     return out
+
+
+def tuning_check(spec, tun):
+    """vsyn_tuning_check (host only): raises VsynError naming what "tuning estimation" step 9 refuses."""
+    err = C.c_char_p()
+    _check(load().vsyn_tuning_check(C.byref(spec), C.byref(tun), C.byref(err)), err)
+
+
+def piptrack_bins(sample_rate, spec, tun):
+    """vsyn_piptrack_bins (host only): (k_lo, k_hi) of the searched band at sample_rate."""
+    out = np.zeros(2, np.uint32)
+    rc = load().vsyn_piptrack_bins(int(sample_rate), C.byref(spec), C.byref(tun), _ptr(out))
+    if rc != VSYN_OK:
+        raise VsynError(rc, "vsyn_piptrack_bins refuses the rate, the spec or the tuning spec")
+    return int(out[0]), int(out[1])
+
+
+def pitch_tuning(freqs, mags=None, resolution=0.01, bins_per_octave=12):
+    """vsyn_pitch_tuning (host only): (tuning, n, selected) of float32 freqs (and mags, or None: every freqs > 0 is selected)."""
+    f = np.ascontiguousarray(freqs, np.float32).reshape(-1)
+    m = None if mags is None else np.ascontiguousarray(mags, np.float32).reshape(-1)
+    if m is not None and m.size != f.size:
+        raise ValueError("freqs and mags differ in size")
+    t, cnt = np.zeros(1, np.float64), np.zeros(2, np.uint64)
+    rc = load().vsyn_pitch_tuning(_ptr(f) if f.size else None, _ptr(m) if m is not None and m.size else None, f.size, float(resolution),
+                                  int(bins_per_octave), _ptr(t), _ptr(cnt))
+    if rc != VSYN_OK:
+        raise VsynError(rc, "vsyn_pitch_tuning refuses resolution %r or bins_per_octave %r" % (resolution, bins_per_octave))
+    return float(t[0]), int(cnt[0]), int(cnt[1])
 
 
 def cqt_tile(spec, sample_rate):
@@ -758,6 +811,42 @@ class Synth:
         err = C.c_char_p()
         _check(self.lib.vsyn_spectral_chroma_device(self.h, C.byref(spec), _ref(chroma), len(rates), _ptr(rates), d_pcm, plane_stride, channels,
                                                     d_frames, d_rows, d_seg_row_off, stream, C.byref(err)), err)
+
+    def piptrack_device(self, spec, tun, sample_rates, d_pcm, plane_stride, channels, d_frames, d_pitches, d_mags, d_seg_row_off=None, stream=None):
+        """vsyn_piptrack_device on device pointers (ints); spec is a lin_power SpectralSpec, tun a TuningSpec."""
+        rates = _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_piptrack_device(self.h, C.byref(spec), C.byref(tun), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames,
+                                             d_pitches, d_mags, d_seg_row_off, stream, C.byref(err)), err)
+
+    def tuning_device(self, spec, tun, sample_rates, d_pcm, plane_stride, channels, d_frames, d_tuning, d_counts, stream=None):
+        """vsyn_tuning_device on device pointers (ints): d_tuning [S] float64, d_counts [S][2] uint64."""
+        rates = _rates(sample_rates)
+        err = C.c_char_p()
+        _check(self.lib.vsyn_tuning_device(self.h, C.byref(spec), C.byref(tun), len(rates), _ptr(rates), d_pcm, plane_stride, channels, d_frames,
+                                           d_tuning, d_counts, stream, C.byref(err)), err)
+
+    def pcm_tuning_host(self, spec, tun, in_rates, out_rate=0, rows=False):
+        """vsyn_pcm_tuning_host over the last submit's segments: dict(rc, tuning [S] float64, counts [S][2] uint64, seg_rows [S], flags)
+        and with rows=True pitches and mags, float32 [total][NB]."""
+        rates = _rates(in_rates)
+        S, nb = len(rates), int(spec.n_fft) // 2 + 1
+        tuning, counts, seg_rows = np.zeros(max(1, S), np.float64), np.zeros((max(1, S), 2), np.uint64), np.zeros(max(1, S), np.uint64)
+        st, err = Status(), C.c_char_p()
+        head = (self.h, C.byref(spec), C.byref(tun), S, _ptr(rates), out_rate)
+        out = {}
+        if rows:
+            _check(self.lib.vsyn_pcm_tuning_host(*head, VSYN_TUNING_ROWS, None, None, None, 0, _ptr(seg_rows), C.byref(st), C.byref(err)), err)
+            total = int(seg_rows[:S].sum())
+            r = np.zeros((max(1, total), 2 * nb), np.float32)
+            rc = self.lib.vsyn_pcm_tuning_host(*head, VSYN_TUNING_ROWS, _ptr(tuning), _ptr(counts), _ptr(r), total, _ptr(seg_rows), C.byref(st),
+                                               C.byref(err))
+            out = dict(pitches=r[:total, :nb], mags=r[:total, nb:])
+        else:
+            rc = self.lib.vsyn_pcm_tuning_host(*head, VSYN_TUNING_ONLY, _ptr(tuning), _ptr(counts), None, 0, _ptr(seg_rows), C.byref(st),
+                                               C.byref(err))
+        _check(rc, err, (VSYN_OK, VSYN_ERR_STREAM))
+        return dict(rc=rc, tuning=tuning[:S], counts=counts[:S], seg_rows=seg_rows[:S], flags=st.flags, **out)
 
     def spectral_post_device(self, post, dim, seg_rows, d_in, d_out, stream=None):
         """vsyn_spectral_post_device on device pointers (ints); seg_rows is a host sequence of each segment's row count."""
@@ -1049,6 +1138,16 @@ class Synth:
         dim = int(self.lib.vsyn_cqt_dim(C.byref(spec)))
         return self._rows_host(self.lib.vsyn_pcm_cqt_host, (C.byref(spec), S, _ptr(rates), out_rate), S, max(dim, 1), [o["refused"]], o)
 
+    def pcm_cqt_est_host(self, spec, estimate, in_rates, out_rate=0):
+        """vsyn_pcm_cqt_est_host over the last submit's segments: what pcm_cqt_host returns and tuning [S] float64 (estimate: a
+        TuningSpec, or None for pcm_cqt_host itself: tuning stays zeros)."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "refused")
+        dim, tun = int(self.lib.vsyn_cqt_dim(C.byref(spec))), np.zeros(max(1, len(rates)), np.float64)
+        r = self._rows_host(self.lib.vsyn_pcm_cqt_est_host, (C.byref(spec), _ref(estimate), S, _ptr(rates), out_rate), S, max(dim, 1),
+                            [o["refused"], tun], o)
+        return dict(r, tuning=tun[:S])
+
     def loudness_device(self, spec, sample_rates, frames, d_pcm, plane_stride, channels, d_records, d_z=None, d_weighted=None,
                         weighted_plane_stride=0, d_scaled=None, scaled_plane_stride=0, stream=None):
         """vsyn_loudness_device on device pointers (ints); sample_rates and frames are host sequences."""
@@ -1130,6 +1229,20 @@ class Synth:
                             tuple(_ref(st) for st in stages) + (_ref(post), S, _ptr(rates), out_rate), S, _post_dim(spec, post, chroma),
                             [o["frames"], o["bounds"], o["counts"], iv, ivs, o["peaks"], o["refs"], rec], o)
         return dict(r, intervals=self._intervals(o["counts"], iv, S), records=rec[:S])
+
+    def pcm_chain_chroma_est_host(self, gate, gate_is_split, loud, cond, spec, chroma, pcen, post, estimate, in_rates, out_rate=0):
+        """vsyn_pcm_chain_chroma_est_host over the last submit's segments: what pcm_chain_chroma_host returns and tuning [S] float64, each
+        segment's estimate (estimate: a TuningSpec, or None for pcm_chain_chroma_host itself: tuning stays zeros)."""
+        rates = _rates(in_rates)
+        S, o = len(rates), _per_segment(len(rates), "frames", "bounds", "counts", "peaks", "refs")
+        rec, tun = np.zeros(max(1, S), LOUDNESS_RECORD_DTYPE), np.zeros(max(1, S), np.float64)
+        ivs = self._split_sizes(gate, S, rates if out_rate else None, out_rate)[1] if gate is not None and gate_is_split else 1
+        iv = np.zeros((max(1, S), ivs, 2), np.uint32)
+        r = self._rows_host(self.lib.vsyn_pcm_chain_chroma_est_host,
+                            (_ref(gate), 1 if gate_is_split else 0, _ref(loud), _ref(cond), C.byref(spec), _ref(chroma), _ref(pcen), _ref(post),
+                             _ref(estimate), S, _ptr(rates), out_rate), S, _post_dim(spec, post, chroma),
+                            [o["frames"], o["bounds"], o["counts"], iv, ivs, o["peaks"], o["refs"], rec, tun], o)
+        return dict(r, intervals=self._intervals(o["counts"], iv, S), records=rec[:S], tuning=tun[:S])
 
     def pcm_chain_chroma_host(self, gate, gate_is_split, loud, cond, spec, chroma, pcen, post, in_rates, out_rate=0):
         """vsyn_pcm_chain_chroma_host over the last submit's segments (every spec but spec may be None): returns what

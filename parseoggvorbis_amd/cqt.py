@@ -71,6 +71,8 @@ def cqt_spec(hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, tuning=0.
     f = C1 if fmin is None else _real("fmin", fmin)
     if not f > 0.0:
         raise CqtError("fmin must be > 0, got %r" % (fmin,))
+    if tuning is None:
+        raise CqtError("tuning must be a number, got None (librosa's tuning=None is tuning=\"estimate\" in the batch functions)")
     fs, gm, tu = _real("filter_scale", filter_scale), _real("gamma", gamma), _real("tuning", tuning)
     if not fs > 0.0:
         raise CqtError("filter_scale must be > 0, got %r" % (filter_scale,))
@@ -93,7 +95,19 @@ def cqt_spec(hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, tuning=0.
 _load = _corpus.load
 
 
-def _run(list_of_bytes, spec, sr, threads, feeders, device, errors, files_per_submit, stats):
+def _estimate(tuning, bins_per_octave, resolution, fmin, fmax, threshold):
+    """(the number cqt_spec gets, the estimator's C spec or None): tuning="estimate" is librosa's tuning=None, each file's own estimate
+    first (parseoggvorbis_amd/tuning.py); None itself and every other string stay refused by cqt_spec."""
+    if not (isinstance(tuning, str) and tuning == "estimate"):
+        return tuning, None
+    from .tuning import TuningError, tuning_spec
+    try:
+        return 0.0, tuning_spec(fmin, fmax, threshold, resolution, _int("bins_per_octave", bins_per_octave, 1, 256))
+    except TuningError as e:
+        raise CqtError("tuning='estimate': tuning_%s" % e) from None
+
+
+def _run(list_of_bytes, spec, sr, threads, feeders, device, errors, files_per_submit, stats, est=None):
     if errors not in ("raise", "return"):
         raise CqtError("errors must be 'raise' or 'return', got %r" % (errors,))
     target = check_sr(sr, CqtError)
@@ -107,44 +121,56 @@ def _run(list_of_bytes, spec, sr, threads, feeders, device, errors, files_per_su
     nb = int(spec.n_bins)
     dim = {1: nb, 2: 2 * nb, 3: int(spec.n_chroma), 4: 6}[int(spec.output)]
 
+    tunings = np.zeros(max(n, 1), np.float64)
+
     def build(i, p):
         rows = _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p)
         if spec.output == OUTPUTS["complex"]:
             rows = rows.view(np.complex64)
-        return rows, int(rates[i])
+        return (rows, int(rates[i])) if est is None else (rows, int(rates[i]), float(tunings[i]))
 
+    if est is not None:
+        return _corpus.run(lib, lib.ogg_vorbis_cqt_corpus_est, list_of_bytes,
+                           (threads, feeders, files_per_submit, device, target, C.byref(spec), C.byref(est)), (counts, frames, rates, tunings), build,
+                           CqtError, errors, "constant-Q", stats)
     return _corpus.run(lib, lib.ogg_vorbis_cqt_corpus, list_of_bytes, (threads, feeders, files_per_submit, device, target, C.byref(spec)),
                        (counts, frames, rates), build, CqtError, errors, "constant-Q", stats)
 
 
 def get_cqt_batch(list_of_bytes, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, tuning=0.0, filter_scale=1.0, gamma=0.0, norm=1,
                   scale=True, output="magnitude", power=1, sr=None, threads=0, feeders=0, device=0, errors="raise", files_per_submit=64,
-                  stats=None):
+                  stats=None, tuning_resolution=0.01, tuning_fmin=150.0, tuning_fmax=4000.0, tuning_threshold=0.1):
     """The constant-Q (gamma = 0) or variable-Q (gamma > 0) rows of many Ogg Vorbis files in one corpus run: a list of (rows, sr)
     tuples. rows is float32 (F, n_bins), |C|^power, for output="magnitude" and complex64 (F, n_bins) for output="complex",
     F = 1 + T // hop_length; sr is the rate they were computed at. fmin=None means C1. sr, threads, feeders, errors and stats as for
     get_pcm_batch. A file with an Inf or NaN sample, and a file at whose rate the top bin's pass band leaves the Nyquist band, fails
     alone: errors="raise" raises CqtError naming the first such file and which of the two it was, errors="return" puts the CqtError in
-    its slot."""
+    its slot. tuning="estimate" (librosa's tuning=None; None itself stays refused): each file's tuning is estimated first on the device
+    from a magnitude STFT (n_fft 2048, hop 512) of the signal the transform sees, with tuning_fmin, tuning_fmax, tuning_threshold,
+    tuning_resolution and the transform's bins_per_octave; the entries are then (rows, sr, tuning), the rows those of the same call with
+    that number, bit for bit."""
     if output not in ("magnitude", "complex"):
         raise CqtError("output must be 'magnitude' or 'complex', got %r" % (output,))
+    tuning, est = _estimate(tuning, bins_per_octave, tuning_resolution, tuning_fmin, tuning_fmax, tuning_threshold)
     spec = cqt_spec(hop_length, fmin, n_bins, bins_per_octave, tuning, filter_scale, gamma, norm, scale, output, power)
-    return _run(list_of_bytes, spec, sr, threads, feeders, device, errors, files_per_submit, stats)
+    return _run(list_of_bytes, spec, sr, threads, feeders, device, errors, files_per_submit, stats, est)
 
 
 def get_chroma_cqt_batch(list_of_bytes, hop_length=512, fmin=None, n_chroma=12, n_octaves=7, bins_per_octave=36, tuning=0.0, filter_scale=1.0,
                          gamma=0.0, norm=1, scale=True, chroma_norm=np.inf, base_c=True, tonnetz=False, sr=None, threads=0, feeders=0,
-                         device=0, errors="raise", files_per_submit=64, stats=None):
+                         device=0, errors="raise", files_per_submit=64, stats=None, tuning_resolution=0.01, tuning_fmin=150.0,
+                         tuning_fmax=4000.0, tuning_threshold=0.1):
     """librosa.feature.chroma_cqt's rows (threshold=None, cqt_mode="full", window=None) of many files: a list of (rows, sr), rows
     float32 (F, n_chroma), or with tonnetz=True the (F, 6) tonnetz rows computed from them. The transform has
-    n_bins = n_octaves * bins_per_octave bins (at most 256). The rest as get_cqt_batch."""
+    n_bins = n_octaves * bins_per_octave bins (at most 256). The rest as get_cqt_batch, tuning="estimate" included."""
     no = _int("n_octaves", n_octaves, 1, MAX_BINS)
     bpo = _int("bins_per_octave", bins_per_octave, 1, 256)
     if no * bpo > MAX_BINS:
         raise CqtError("n_octaves * bins_per_octave = %d exceeds %d bins" % (no * bpo, MAX_BINS))
+    tuning, est = _estimate(tuning, bpo, tuning_resolution, tuning_fmin, tuning_fmax, tuning_threshold)
     spec = cqt_spec(hop_length, fmin, no * bpo, bpo, tuning, filter_scale, gamma, norm, scale, "tonnetz" if _bool("tonnetz", tonnetz) else "chroma",
                     1, n_chroma, chroma_norm, base_c)
-    return _run(list_of_bytes, spec, sr, threads, feeders, device, errors, files_per_submit, stats)
+    return _run(list_of_bytes, spec, sr, threads, feeders, device, errors, files_per_submit, stats, est)
 
 
 def get_cqt_from_raw_bytes(raw_bytes, **kwargs):

@@ -137,6 +137,8 @@ struct vsyn_handle {
   // the stages behind synthesis: each owns its workspace, and its launch code sees nothing else of the handle
   FeatureWs ft;                        // vsyn_features.h
   SpectralWs sp;                       // vsyn_spectral.h
+  TuningWs tu;                         // vsyn_tuning.h (beside sp: the table and the offsets are the spectral stage's)
+  DevBuf<float> tu_rows;               // vsyn_pcm_tuning_host: rows of NB pitches and NB magnitudes
   PostWs pp;                           // vsyn_spectral_post.h
   PcenWs pc;                           // vsyn_pcen.h
   HpssWs hp;                           // vsyn_hpss.h
@@ -1686,6 +1688,8 @@ struct Chain {
   float* peaks_out;       // normaliser's records, the rhythm stages' refusal words
   vsyn_loudness_record* records_out;
   uint32_t* refused_out;
+  const vsyn_tuning_spec* estimate;  // a chroma kind with each segment's tuning estimated first (vsyn_tuning.h): chroma->tuning is
+  double* tuning_out;                // checked and not used; the estimates [S] go here
 };
 
 // the stretched (and shifted) mono downmix of the view (T[g] frames, host) into h->st's mono plane, T[g] replaced by what the stage
@@ -1863,8 +1867,20 @@ static int spectral_rows_out(vsyn_handle* h, const Chain& c, const uint32_t* spe
   if (c.hpss)
     if (int rc = hpss_check_call(c.hpss, (uint32_t)D, S, seg_rows, err)) return rc;
   HIPCHK(h->sp.rows.ensure(total * D + 1));
-  int rc = spec_launch(h->sp, h->device, c.spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err,
-                       c.chroma);
+  int rc;
+  if (c.estimate) {  // the estimate on the PCM the chroma kernel is about to see, at its framing and power; the one extra wait of the form
+    vsyn_spectral_spec lin = *c.spec;
+    lin.kind = VSYN_SPEC_LIN_POWER;
+    HIPCHK(h->tu.tuning.ensure(S));
+    HIPCHK(h->tu.counts.ensure(2ull * S));
+    rc = pip_launch(h->sp, h->tu, h->device, &lin, c.estimate, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, nullptr, nullptr, 0, nullptr,
+                    h->tu.tuning.p, h->tu.counts.p, hs, err);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(c.tuning_out, h->tu.tuning.p, sizeof(double) * S, hipMemcpyDeviceToHost, hs));
+    HIPCHK(hipStreamSynchronize(hs));
+  }
+  rc = spec_launch(h->sp, h->device, c.spec, S, spec_rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, total, h->sp.rows.p, nullptr, hs, err,
+                   c.chroma, c.estimate ? c.tuning_out : nullptr);
   if (rc) return rc;
   float* cur = h->sp.rows.p;  // where the rows are
   if (c.hpss) {
@@ -1917,6 +1933,17 @@ static int spectral_host(vsyn_handle* h, Chain c, float* rows, uint64_t rows_cap
   std::vector<uint32_t> sp_rates = stage_rates(S, rates, out_rate);
   // (NULL rates without a gate are spec_check's to refuse; behind a gate they skip every segment)
   if (int rc = spec_check(spec, S, gate || rates ? sp_rates.data() : nullptr, err, c.chroma)) return rc;
+  if (c.estimate) {
+    if (!spec_is_chroma(spec)) return fail(err, VSYN_ERR_INVALID, "a tuning estimate is for the chroma kinds, not for kind %u", spec->kind);
+    vsyn_spectral_spec lin = *spec;
+    lin.kind = VSYN_SPEC_LIN_POWER;
+    if (int rc = tuning_check(&lin, c.estimate, 0, nullptr, err)) return rc;
+    if (c.estimate->bins_per_octave != spec_chroma_or_defaults(c.chroma)->n_chroma)
+      return fail(err, VSYN_ERR_INVALID, "the estimate's bins_per_octave %u is not n_chroma %u: the tuning would be in another unit",
+                  c.estimate->bins_per_octave, spec_chroma_or_defaults(c.chroma)->n_chroma);
+    if (S && rows && !c.tuning_out) return fail(err, VSYN_ERR_INVALID, "tuning_out is NULL");
+    for (uint32_t g = 0; g < S && c.tuning_out; ++g) c.tuning_out[g] = 0.0;
+  }
   if (c.hpss) {
     if (int rc = hpss_check(c.hpss, err)) return rc;
     if (spec->kind != VSYN_SPEC_MEL_POWER && spec->kind != VSYN_SPEC_LIN_POWER)
@@ -2383,6 +2410,32 @@ int vsyn_pcm_chain_rhythm_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int ga
   return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
 }
 
+// vsyn_pcm_chain_chroma_host with each segment's tuning estimated first (estimate NULL: that entry, tuning_out not written).
+int vsyn_pcm_chain_chroma_est_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
+                                   const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
+                                   const vsyn_spectral_pcen* pcen, const vsyn_spectral_post* post, const vsyn_tuning_spec* estimate, uint32_t S,
+                                   const uint32_t* in_rates, uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows,
+                                   uint64_t* frames_out, uint32_t* bounds_out, uint32_t* counts_out, uint32_t* intervals_out,
+                                   uint64_t intervals_stride, float* peaks_out, double* refs_out, vsyn_loudness_record* records_out,
+                                   double* tuning_out, vsyn_status* status, const char** err) {
+  if (!h) return cond_no_handle(err);
+  const bool split = gate && gate_is_split;
+  Chain c{S, in_rates, out_rate};
+  c.gate = make_gate(gate, split, bounds_out, counts_out, intervals_out, intervals_stride, refs_out);
+  c.loud = loud;
+  c.cond = cond;
+  c.spec = spec;
+  c.chroma = spec && spec_is_chroma(spec) ? chroma : nullptr;
+  c.pcen = pcen;
+  c.post = post;
+  c.frames_out = gate && (loud || split) ? frames_out : nullptr;
+  c.peaks_out = peaks_out;
+  c.records_out = loud ? records_out : nullptr;
+  c.estimate = estimate;
+  c.tuning_out = estimate ? tuning_out : nullptr;
+  return spectral_host(h, c, rows, rows_capacity, seg_rows, status, err);
+}
+
 // vsyn_pcm_chain_rhythm_host's chain with the beat tracker in the rhythm stages' place (vsyn_beat.h).
 int vsyn_pcm_chain_beats_host(vsyn_handle* h, const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud,
                               const vsyn_pcm_cond* cond, const vsyn_spectral_spec* spec, const vsyn_spectral_chroma* chroma,
@@ -2633,6 +2686,139 @@ int vsyn_pcm_cqt_host(vsyn_handle* h, const vsyn_cqt_spec* spec, uint32_t S, con
         return cqt_launch(h->cq, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->cq.rows.p, nullptr, h->cq.refused.p, hs, err);
       },
       S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
+}
+
+// vsyn_pcm_cqt_host with each segment's tuning estimated first: a magnitude STFT of n_fft 2048, hop 512, Hann, centred (librosa.cqt's
+// call of estimate_tuning) on the mono signal the transform sees, the estimates read back, then the transform on wavelets per
+// distinct (rate, tuning) pair.
+int vsyn_pcm_cqt_est_host(vsyn_handle* h, const vsyn_cqt_spec* spec, const vsyn_tuning_spec* estimate, uint32_t S, const uint32_t* in_rates,
+                          uint32_t out_rate, float* rows, uint64_t rows_capacity, uint64_t* seg_rows, uint32_t* refused_out, double* tuning_out,
+                          vsyn_status* status, const char** err) {
+  if (!estimate) return vsyn_pcm_cqt_host(h, spec, S, in_rates, out_rate, rows, rows_capacity, seg_rows, refused_out, status, err);
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = cqt_check(spec, S, in_rates, err)) return rc;  // (first: an invalid spec writes nothing, the status included)
+  const vsyn_spectral_spec lin = {VSYN_SPEC_LIN_POWER, VSYN_SPEC_CENTER, 2048u, 512u, 2048u, 0u, 0u, 1u, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (int rc = tuning_check(&lin, estimate, 0, nullptr, err)) return rc;
+  if (estimate->bins_per_octave != spec->bins_per_octave)
+    return fail(err, VSYN_ERR_INVALID, "the estimate's bins_per_octave %u is not the transform's %u: the tuning would be in another unit",
+                estimate->bins_per_octave, spec->bins_per_octave);
+  if (S && rows && !tuning_out) return fail(err, VSYN_ERR_INVALID, "tuning_out is NULL");
+  for (uint32_t g = 0; g < S && tuning_out; ++g) tuning_out[g] = 0.0;
+  status_reset(status);
+  if (int rc = chain_check(nullptr, nullptr, S, in_rates, out_rate, err)) return rc;
+  const std::vector<uint32_t> cq_rates = stage_rates(S, in_rates, out_rate);
+  const uint32_t* rates = out_rate ? cq_rates.data() : in_rates;
+  return framed_rows_host(
+      h, 0u, spec->hop_length, true, cqt_dim(spec), h->cq.rows, h->cq.refused,
+      [&](const PcmView& v, uint64_t f_max, hipStream_t hs) {
+        HIPCHK(h->tu.tuning.ensure(S));
+        HIPCHK(h->tu.counts.ensure(2ull * S));
+        if (int rc = pip_launch(h->sp, h->tu, h->device, &lin, estimate, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si,
+                                spec_num_frames(lin.n_fft, lin.hop_length, true, v.plane), nullptr, nullptr, 0, nullptr, h->tu.tuning.p, h->tu.counts.p,
+                                hs, err))
+          return rc;
+        HIPCHK(hipMemcpyAsync(tuning_out, h->tu.tuning.p, sizeof(double) * S, hipMemcpyDeviceToHost, hs));
+        HIPCHK(hipStreamSynchronize(hs));  // the one extra wait of the form: the wavelets need the numbers
+        return cqt_launch(h->cq, h->device, spec, S, rates, v.pcm, v.plane, v.C, v.d_frames, v.si, f_max, h->cq.rows.p, nullptr, h->cq.refused.p, hs, err,
+                          tuning_out);
+      },
+      S, in_rates, out_rate, rates, rows, rows_capacity, seg_rows, refused_out, status, err);
+}
+
+// ---- tuning estimation (vsyn_tuning.h) ----
+
+int vsyn_tuning_check(const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, const char** err) { return tuning_check(spec, tun, 0, nullptr, err); }
+
+int vsyn_piptrack_bins(uint32_t sample_rate, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t out[2]) {
+  if (!out || !sample_rate || tuning_check(spec, tun, 0, nullptr, nullptr) != VSYN_OK) return VSYN_ERR_INVALID;
+  pip_bins(sample_rate, spec->n_fft, tun, out);
+  return VSYN_OK;
+}
+
+int vsyn_pitch_tuning(const float* freqs, const float* mags, uint64_t n, double resolution, uint32_t bins_per_octave, double* tuning,
+                      uint64_t counts[2]) {
+  if ((n && !freqs) || !tuning || !counts) return VSYN_ERR_INVALID;
+  if (!std::isfinite(resolution) || !(resolution > 0.0 && resolution < 1.0) || ceil(1.0 / resolution) > (double)TUNE_MAX_BINS) return VSYN_ERR_INVALID;
+  if (bins_per_octave < 1 || bins_per_octave > 256) return VSYN_ERR_INVALID;
+  return tune_host(freqs, mags, n, resolution, bins_per_octave, tuning, counts);
+}
+
+uint32_t vsyn_piptrack_tile(const vsyn_spectral_spec* spec) {
+  if (spec_check(spec, 0, nullptr, nullptr) != VSYN_OK || spec->kind != VSYN_SPEC_LIN_POWER) return 0;
+  return pip_tile(spec);
+}
+
+// what the two device entries share: the checks, then pip_launch with the outputs of one of them
+static int tuning_device_call(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t S, const uint32_t* sample_rates,
+                              const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_pitches, float* d_mags,
+                              uint64_t* d_seg_row_off, double* d_tuning, uint64_t* d_counts, void* hip_stream, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = tuning_check(spec, tun, S, sample_rates, err)) return rc;
+  if (S == 0) return VSYN_OK;
+  if (!d_pcm || !d_frames || plane_stride == 0 || channels == 0 || channels > 255 || (!d_tuning && (!d_pitches || !d_mags)) || (d_tuning && !d_counts))
+    return fail(err, VSYN_ERR_INVALID, "NULL pointer, zero stride or channels outside [1, 255]");
+  const uint64_t f_max = spec_num_frames(spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, plane_stride);
+  std::lock_guard<std::mutex> lk(h->mu);
+  return pip_launch(h->sp, h->tu, h->device, spec, tun, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, f_max, d_pitches, d_mags,
+                    spec->n_fft / 2u + 1u, d_seg_row_off, d_tuning, d_counts, (hipStream_t)hip_stream, err);
+}
+
+int vsyn_piptrack_device(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t S, const uint32_t* sample_rates,
+                         const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, float* d_pitches, float* d_mags,
+                         uint64_t* d_seg_row_off, void* hip_stream, const char** err) {
+  return tuning_device_call(h, spec, tun, S, sample_rates, d_pcm, plane_stride, channels, d_frames, d_pitches, d_mags, d_seg_row_off, nullptr, nullptr,
+                            hip_stream, err);
+}
+
+int vsyn_tuning_device(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t S, const uint32_t* sample_rates,
+                       const float* d_pcm, uint64_t plane_stride, uint32_t channels, const uint32_t* d_frames, double* d_tuning, uint64_t* d_counts,
+                       void* hip_stream, const char** err) {
+  if (h && !d_tuning && S) return fail(err, VSYN_ERR_INVALID, "d_tuning is NULL");
+  return tuning_device_call(h, spec, tun, S, sample_rates, d_pcm, plane_stride, channels, d_frames, nullptr, nullptr, nullptr, d_tuning, d_counts,
+                            hip_stream, err);
+}
+
+int vsyn_pcm_tuning_host(vsyn_handle* h, const vsyn_spectral_spec* spec, const vsyn_tuning_spec* tun, uint32_t S, const uint32_t* in_rates,
+                         uint32_t out_rate, uint32_t what, double* tuning, uint64_t* counts, float* rows, uint64_t rows_capacity,
+                         uint64_t* seg_rows, vsyn_status* status, const char** err) {
+  if (!h) return fail(err, VSYN_ERR_INVALID, "handle is NULL");
+  if (int rc = tuning_check(spec, tun, S, in_rates, err)) return rc;  // (first: an invalid spec writes nothing, the status included)
+  if (what > VSYN_TUNING_ROWS) return fail(err, VSYN_ERR_INVALID, "unknown tuning output selector %u", what);
+  if (S && !seg_rows) return fail(err, VSYN_ERR_INVALID, "seg_rows is NULL");
+  status_reset(status);
+  if (int rc = chain_check(nullptr, nullptr, S, in_rates, out_rate, err)) return rc;
+  const std::vector<uint32_t> rates = stage_rates(S, in_rates, out_rate);
+  const bool dense = what == VSYN_TUNING_ROWS;
+  // the lock covers the whole call: the resample workspace and the stage's are the handle's, and the PCM must stay that of the last submit
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<uint64_t> T(S);
+  uint64_t total, f_max, t_max;
+  if (int rc = last_submit_frames(h, S, in_rates, out_rate, T.data(), &t_max, err)) return rc;
+  t_max = std::max<uint64_t>(t_max, 1);
+  count_rows(spec->n_fft, spec->hop_length, (spec->options & VSYN_SPEC_CENTER) != 0, S, rates.data(), T.data(), 0, seg_rows, &total, &f_max);
+  if (S == 0 || (dense ? !rows : !tuning)) return VSYN_OK;  // the size query
+  if (dense && total > rows_capacity) return fail(err, VSYN_ERR_INVALID, "rows buffer too small: %llu rows needed", (unsigned long long)total);
+  if (out_rate && t_max > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "resampled segment too long");
+  hipStream_t hs = h->host_stream;
+  PcmView v = last_submit_view(h);
+  if (out_rate)
+    if (int rc = step_resample(h, S, in_rates, out_rate, t_max, false, &v, err)) return rc;
+  const uint64_t nb = spec->n_fft / 2u + 1u, nv = total * 2u * nb;  // a row: its NB pitches, then its NB magnitudes
+  if (dense) HIPCHK(h->tu_rows.ensure(nv + 1));
+  if (tuning) {
+    HIPCHK(h->tu.tuning.ensure(S));
+    HIPCHK(h->tu.counts.ensure(2ull * S));
+  }
+  if (int rc = pip_launch(h->sp, h->tu, h->device, spec, tun, S, rates.data(), v.pcm, v.plane, v.C, v.d_frames, v.si, f_max,
+                          dense ? h->tu_rows.p : nullptr, dense ? h->tu_rows.p + nb : nullptr, 2u * nb, nullptr, tuning ? h->tu.tuning.p : nullptr,
+                          tuning ? h->tu.counts.p : nullptr, hs, err))
+    return rc;
+  if (dense && nv) HIPCHK(hipMemcpyAsync(rows, h->tu_rows.p, sizeof(float) * nv, hipMemcpyDeviceToHost, hs));
+  if (tuning) {
+    HIPCHK(hipMemcpyAsync(tuning, h->tu.tuning.p, sizeof(double) * S, hipMemcpyDeviceToHost, hs));
+    if (counts) HIPCHK(hipMemcpyAsync(counts, h->tu.counts.p, sizeof(uint64_t) * 2u * S, hipMemcpyDeviceToHost, hs));
+  }
+  return sync_status_into(h, status, err);
 }
 
 // ---- loudness (vsyn_loudness.h) ----

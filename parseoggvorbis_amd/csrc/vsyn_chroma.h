@@ -3,7 +3,8 @@
 //
 // The offsets kernel, the table of the linear kinds (header, twiddles, window, per-segment rate index) and the workspace are those of
 // vsyn_spectral.h; behind the rate index the table carries a ChromaHeader, the dense float32 filterbank [rate][n_chroma][NB] and
-// phi [6][n_chroma] (SpecHeader.pad holds the ChromaHeader's offset; it is 0 in every other kind's table). Behind the offsets kernel,
+// phi [6][n_chroma] (SpecHeader.pad holds the ChromaHeader's offset; it is 0 in every other kind's table). With estimated tunings
+// (spec_launch's seg_tuning) there is one filterbank per distinct (rate, tuning) pair and a per-segment bank index behind phi. Behind the offsets kernel,
 // one workgroup of 256 threads (4 waves) per (segment, tile of frames), by n_fft alone:
 //   vsyn_chroma_fft_kernel         n_fft a power of two: spec_lin_fft_tile_run (vsyn_spectral_lin.h), then S[f][k] = |X[k]|^power into
 //                                  the spare ping-pong buffer instead of a store of the bins.
@@ -20,12 +21,14 @@
 #include <cfloat>
 
 #include "vsyn_spectral_lin.h"
+#include "vsyn_tuning.h"  // its tile kernels stand in spec_raise_lds' list
 
 #define CHROMA_DIRECT_FT 8
 #define CHROMA_MAX 256  // n_chroma's limit; the LDS images reserve a row of it per frame, so that the tile depends on the spec alone
 
 struct ChromaHeader {
   uint32_t n_chroma, norm, off_w, off_phi;  // byte offsets into the table
+  uint32_t off_bank, pad[3];                // the per-segment filterbank index [S]: the rate index itself unless tunings were estimated
 };
 
 __device__ __forceinline__ const ChromaHeader* chroma_hdr(const uint8_t* t) { return (const ChromaHeader*)(t + spec_hdr(t)->pad); }
@@ -150,7 +153,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_chroma_fft_kernel(const Spe
     s_S[q] = H->power == 1 ? sqrtf(p) : p;
   }
   __syncthreads();
-  const uint32_t ri = ((const uint32_t*)(A.tab + H->off_rate))[g];
+  const uint32_t ri = ((const uint32_t*)(A.tab + CH->off_bank))[g];
   const float* W = (const float*)(A.tab + CH->off_w) + (size_t)ri * NC * nb;
   const uint32_t wave = tid >> 6, lane = tid & 63u;
   for (uint32_t p = wave; p < nf * NC; p += SPEC_THREADS / 64u) {
@@ -179,7 +182,7 @@ __global__ void __launch_bounds__(SPEC_THREADS) vsyn_chroma_direct_kernel(const 
   float* s_R = s_S + FT * SPEC_THREADS;  // [nf][NC]
   for (uint32_t i = tid; i < nf * NC; i += SPEC_THREADS) s_R[i] = 0.f;
   __syncthreads();
-  const uint32_t ri = ((const uint32_t*)(A.tab + H->off_rate))[g];
+  const uint32_t ri = ((const uint32_t*)(A.tab + CH->off_bank))[g];
   const float* W = (const float*)(A.tab + CH->off_w) + (size_t)ri * NC * nb;
   const uint32_t wave = tid >> 6, lane = tid & 63u;
   for (uint32_t k0 = 0; k0 < nb; k0 += SPEC_THREADS) {
@@ -260,31 +263,59 @@ static inline uint32_t spec_chroma_tile(const vsyn_spectral_spec* sp) {
   return 0;
 }
 
-// The chroma block behind tab (the linear kinds' table of sp): one filterbank per rate of distinct (spec_build_table's list, in the
-// order of the table's rate indices) and phi. ch is checked.
+// The chroma block behind tab (the linear kinds' table of sp): one filterbank per bank and phi. Without seg_tuning a bank is a rate of
+// distinct (spec_build_table's list, in the order of the table's rate indices) at ch->tuning, and a segment's bank index is its rate
+// index. With seg_tuning [S] (estimated tunings) a bank is a distinct (rate, tuning) pair in the order of first appearance, and the
+// per-segment bank index stands behind phi. ch is checked.
 static inline int spec_chroma_table(SpectralWs& ws, const vsyn_spectral_spec* sp, const vsyn_spectral_chroma* ch, const std::vector<uint32_t>& distinct,
-                                    std::vector<uint8_t>& tab, const char** err) {
+                                    std::vector<uint8_t>& tab, const char** err, const double* seg_tuning = nullptr) {
   const uint32_t n = sp->n_fft, nb = n / 2u + 1u, NC = ch->n_chroma;
   SpecHeader T;
   memcpy(&T, tab.data(), sizeof(T));
+  std::vector<std::pair<uint32_t, double>> banks;
+  std::vector<uint32_t> seg_bank;
+  if (seg_tuning) {
+    std::vector<uint32_t> seg_rate(T.S);
+    if (T.S) memcpy(seg_rate.data(), tab.data() + T.off_rate, 4ull * T.S);
+    seg_bank.assign(T.S, SPEC_SKIP);
+    for (uint32_t g = 0; g < T.S; ++g) {
+      if (seg_rate[g] == SPEC_SKIP) continue;
+      const std::pair<uint32_t, double> want(distinct[seg_rate[g]], seg_tuning[g]);
+      auto it = std::find(banks.begin(), banks.end(), want);
+      seg_bank[g] = (uint32_t)(it - banks.begin());
+      if (it == banks.end()) banks.push_back(want);
+    }
+  } else {
+    for (uint32_t r : distinct) banks.push_back(std::make_pair(r, ch->tuning));
+  }
   const size_t off_ch = (tab.size() + 15) & ~(size_t)15;
   const size_t off_w = off_ch + sizeof(ChromaHeader);
-  const size_t off_phi = off_w + 4ull * distinct.size() * NC * nb;
-  const size_t total = off_phi + 4ull * 6u * NC + 16;
-  if (total > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too many distinct sample rates (%zu) for one chroma table", distinct.size());
+  const size_t off_phi = off_w + 4ull * banks.size() * NC * nb;
+  const size_t off_bank = off_phi + 4ull * 6u * NC;
+  const size_t total = off_bank + 4ull * seg_bank.size() + 16;
+  if (total > 0xFFFFFFFFull)
+    return fail(err, VSYN_ERR_INVALID, "too many distinct (sample rate, tuning) pairs (%zu) for one chroma table", banks.size());
   tab.resize(total, 0);
   T.pad = (uint32_t)off_ch;
   T.dim = spec_dim(sp, ch);
   memcpy(tab.data(), &T, sizeof(T));
-  const ChromaHeader CH = {NC, ch->norm, (uint32_t)off_w, (uint32_t)off_phi};
+  const ChromaHeader CH = {NC, ch->norm, (uint32_t)off_w, (uint32_t)off_phi, seg_tuning ? (uint32_t)off_bank : T.off_rate, {0u, 0u, 0u}};
   memcpy(tab.data() + off_ch, &CH, sizeof(CH));
+  if (!seg_bank.empty()) memcpy(tab.data() + off_bank, seg_bank.data(), 4 * seg_bank.size());
   // the filterbanks of the last call are kept: a corpus run asks for the same ones submit after submit
-  std::vector<double> key = {(double)n, (double)NC, (double)ch->options, ch->tuning, ch->ctroct, ch->octwidth};
-  for (uint32_t r : distinct) key.push_back((double)r);
+  std::vector<double> key = {(double)n, (double)NC, (double)ch->options, ch->ctroct, ch->octwidth};
+  for (const auto& b : banks) {
+    key.push_back((double)b.first);
+    key.push_back(b.second);
+  }
   if (key != ws.chroma_key) {
     ws.chroma_key.clear();  // (a throw below leaves no stale bank behind a matching key)
-    ws.chroma_bank.resize(distinct.size() * NC * nb);
-    for (size_t r = 0; r < distinct.size(); ++r) chroma_filterbank(distinct[r], n, ch, ws.chroma_bank.data() + r * NC * nb);
+    ws.chroma_bank.resize(banks.size() * NC * nb);
+    vsyn_spectral_chroma cb = *ch;
+    for (size_t r = 0; r < banks.size(); ++r) {
+      cb.tuning = banks[r].second;
+      chroma_filterbank(banks[r].first, n, &cb, ws.chroma_bank.data() + r * NC * nb);
+    }
     ws.chroma_key = key;
   }
   if (!ws.chroma_bank.empty()) memcpy(tab.data() + off_w, ws.chroma_bank.data(), 4 * ws.chroma_bank.size());
@@ -311,7 +342,7 @@ static inline int spec_chroma_run(const SpecCtx& A, const vsyn_spectral_spec* sp
 // The dynamic-LDS limit of every kind's tile kernels, once per handle (the device is selected).
 static inline int spec_raise_lds(SpectralWs& ws, const char** err) {
   if (ws.lds_set) return VSYN_OK;
-  const void* const kernels[9] = {(const void*)vsyn_spec_stft_kernel<16>,
+  const void* const kernels[12] = {(const void*)vsyn_spec_stft_kernel<16>,
                                   (const void*)vsyn_spec_stft_kernel<4>,
                                   (const void*)vsyn_spec_stft_kernel<1>,
                                   (const void*)vsyn_spec_lin_fft_kernel,
@@ -319,7 +350,10 @@ static inline int spec_raise_lds(SpectralWs& ws, const char** err) {
                                   (const void*)vsyn_spec_lin_direct_kernel<1>,
                                   (const void*)vsyn_chroma_fft_kernel,
                                   (const void*)vsyn_chroma_direct_kernel<CHROMA_DIRECT_FT>,
-                                  (const void*)vsyn_chroma_direct_kernel<1>};
+                                  (const void*)vsyn_chroma_direct_kernel<1>,
+                                  (const void*)vsyn_piptrack_fft_kernel,
+                                  (const void*)vsyn_piptrack_direct_kernel<PIP_DIRECT_FT>,
+                                  (const void*)vsyn_piptrack_direct_kernel<1>};
   for (const void* k : kernels) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_BUDGET));
   ws.lds_set = true;
   return VSYN_OK;
@@ -327,10 +361,12 @@ static inline int spec_raise_lds(SpectralWs& ws, const char** err) {
 
 // The kernels of a spectral kind on stream s: the offsets kernel, then the kind's own (spec_mel_run, spec_lin_run, spec_chroma_run; ch,
 // NULL for the defaults, is read for a chroma kind only); frames from d_frames, else from si. f_max bounds every segment's STFT frames,
-// rows_bound the total rows. Caller holds the handle's lock and has run spec_check.
+// rows_bound the total rows. seg_tuning [S] (a chroma kind only; NULL: ch->tuning for all): each segment's own tuning, the
+// filterbanks then per (rate, tuning) pair. Caller holds the handle's lock and has run spec_check.
 static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
                               uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, uint64_t rows_bound, float* d_rows,
-                              uint64_t* d_segoff, hipStream_t s, const char** err, const vsyn_spectral_chroma* ch = nullptr) {
+                              uint64_t* d_segoff, hipStream_t s, const char** err, const vsyn_spectral_chroma* ch = nullptr,
+                              const double* seg_tuning = nullptr) {
   if (S > 65535u) return fail(err, VSYN_ERR_INVALID, "too many segments (%u > 65535)", S);
   const bool lin = spec_is_lin(sp), chroma = spec_is_chroma(sp), mfcc = sp->kind == VSYN_SPEC_MFCC;
   const uint32_t ft = lin ? spec_lin_tile(sp) : chroma ? spec_chroma_tile(sp) : spec_tile(sp);
@@ -339,7 +375,7 @@ static inline int spec_launch(SpectralWs& ws, int device, const vsyn_spectral_sp
   std::vector<uint32_t> distinct;
   spec_build_table(sp, S, rates, tab, &distinct);
   if (chroma)
-    if (int rc = spec_chroma_table(ws, sp, spec_chroma_or_defaults(ch), distinct, tab, err)) return rc;
+    if (int rc = spec_chroma_table(ws, sp, spec_chroma_or_defaults(ch), distinct, tab, err, seg_tuning)) return rc;
   HIPCHK(hipSetDevice(device));
   if (int rc = spec_raise_lds(ws, err)) return rc;
   HIPCHK(ws.segF.ensure(S));

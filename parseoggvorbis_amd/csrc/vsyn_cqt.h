@@ -2,7 +2,7 @@
 // planar float32 PCM already on the device. Semantics: include/vorbis_synth_hip.h, "constant-Q". Design, bound and measurements:
 // DESIGN.md 6v.
 //
-// Two tables. The wavelets (ws.basis) are built on the host per (spec, distinct rates), kept there and on the device from call to
+// Two tables. The wavelets (ws.basis) are built on the host per (spec, distinct (rate, tuning) pairs), kept there and on the device from call to
 // call, and uploaded only when that key changes:
 //   CqtBin [rate][n_bins] (L_k, h_k, the first pair's index, s_k) | class index [n_bins] (chroma outputs) | float32 pairs (re, im)
 // The per-call table (ws.tab) is small: a SpecHeader and a ChromaHeader for chroma_finish (vsyn_chroma.h), phi, and per segment its
@@ -322,54 +322,63 @@ static inline void cqt_classes(const vsyn_cqt_spec* sp, uint32_t* cls) {
 }
 
 // Offsets, transform, fold and finishing kernels on stream s; frames from d_frames, else from si. f_max bounds every segment's rows.
-// d_refused [S] may be NULL. Caller holds the handle's lock and has run cqt_check.
+// d_refused [S] may be NULL. seg_tuning [S] (NULL: sp->tuning for all): each segment's own tuning; the wavelet table then holds one
+// set of bins per distinct (rate, tuning) pair where it holds one per rate otherwise, and a segment's entry indexes the pairs: the
+// kernels read it as they read a rate index. Caller holds the handle's lock and has run cqt_check.
 static inline int cqt_launch(CqtWs& ws, int device, const vsyn_cqt_spec* sp, uint32_t S, const uint32_t* rates, const float* d_pcm, uint64_t plane,
                              uint32_t C, const uint32_t* d_frames, const SegInfo* si, uint64_t f_max, float* d_rows, uint64_t* d_segoff,
-                             uint32_t* d_refused, hipStream_t s, const char** err) {
+                             uint32_t* d_refused, hipStream_t s, const char** err, const double* seg_tuning = nullptr) {
   if (int rc = frames_check_call(S, d_pcm, d_rows, plane, err)) return rc;
   const uint32_t nb = sp->n_bins, cols = cqt_dim(sp);
   const bool chroma = cqt_chroma_out(sp);
-  // the rates the call computes at, in order of first appearance, and each segment's entry
-  std::vector<uint32_t> distinct, seg(S);
+  // the (rate, tuning) pairs the call computes at, in order of first appearance, and each segment's entry
+  typedef std::pair<uint32_t, double> Pair;
+  std::vector<Pair> distinct, refused_pairs;
+  std::vector<uint32_t> seg(S);
   std::vector<CqtLengths> lens;
-  std::vector<uint32_t> refused_rates;
+  vsyn_cqt_spec sq = *sp;  // the spec at a pair's tuning
   for (uint32_t g = 0; g < S; ++g) {
-    const uint32_t r = rates[g];
-    if (!r) {
+    if (!rates[g]) {
       seg[g] = CQT_SKIP;
       continue;
     }
-    if (std::find(refused_rates.begin(), refused_rates.end(), r) != refused_rates.end()) {
+    const Pair p(rates[g], seg_tuning ? seg_tuning[g] : sp->tuning);
+    if (std::find(refused_pairs.begin(), refused_pairs.end(), p) != refused_pairs.end()) {
       seg[g] = CQT_REFUSED;
       continue;
     }
-    const auto it = std::find(distinct.begin(), distinct.end(), r);
+    const auto it = std::find(distinct.begin(), distinct.end(), p);
     if (it != distinct.end()) {
       seg[g] = (uint32_t)(it - distinct.begin());
       continue;
     }
-    CqtLengths len = cqt_lengths(sp, r);
+    sq.tuning = p.second;
+    CqtLengths len = cqt_lengths(&sq, p.first);
     if (len.refused) {
-      refused_rates.push_back(r);
+      refused_pairs.push_back(p);
       seg[g] = CQT_REFUSED;
       continue;
     }
-    if (int rc = cqt_check_caps(len, r, err)) return rc;
+    if (int rc = cqt_check_caps(len, p.first, err)) return rc;
     seg[g] = (uint32_t)distinct.size();
-    distinct.push_back(r);
+    distinct.push_back(p);
     lens.push_back(std::move(len));
   }
-  // the wavelet table: rebuilt when the spec or the rates change
+  // the wavelet table: rebuilt when the spec or the pairs change
   std::vector<double> key = {(double)nb, (double)sp->bins_per_octave, (double)sp->options, (double)sp->norm, (double)(chroma ? sp->n_chroma : 0u),
-                             sp->fmin, sp->tuning, sp->filter_scale, sp->gamma};
-  for (uint32_t r : distinct) key.push_back((double)r);
+                             sp->fmin, sp->filter_scale, sp->gamma};
+  for (const Pair& p : distinct) {
+    key.push_back((double)p.first);
+    key.push_back(p.second);
+  }
   const bool rebuild = key != ws.basis_key;
   if (rebuild) {
     ws.basis_key.clear();  // (a throw below leaves no stale table behind a matching key)
     const size_t off_cls = sizeof(CqtBin) * distinct.size() * nb, off_pairs = align_up(off_cls + 4u * (size_t)nb, 16);
     uint64_t pairs = 0;
     for (const CqtLengths& l : lens) pairs += l.total;
-    if (off_pairs + 8u * pairs > 0xFFFFFFFFull) return fail(err, VSYN_ERR_INVALID, "too many distinct sample rates (%zu) for one constant-Q table", distinct.size());
+    if (off_pairs + 8u * pairs > 0xFFFFFFFFull)
+      return fail(err, VSYN_ERR_INVALID, "too many distinct (sample rate, tuning) pairs (%zu) for one constant-Q table", distinct.size());
     ws.basis_host.assign(off_pairs + 8u * (size_t)pairs + 16u, 0);
     CqtBin* bins = (CqtBin*)ws.basis_host.data();
     float* pr = (float*)(ws.basis_host.data() + off_pairs);
@@ -378,7 +387,7 @@ static inline int cqt_launch(CqtWs& ws, int device, const vsyn_cqt_spec* sp, uin
       for (uint32_t k = 0; k < nb; ++k) {
         const CqtLengths& l = lens[r];
         bins[r * nb + k] = CqtBin{l.L[k], l.h[k], at, (float)((sp->options & VSYN_CQT_SCALE) ? sqrt(l.N[k]) : l.N[k])};
-        cqt_wavelet(sp, distinct[r], l, k, pr + 2u * (size_t)at);
+        cqt_wavelet(sp, distinct[r].first, l, k, pr + 2u * (size_t)at);  // (reads the bin's frequency from l, not the spec's tuning)
         at += l.L[k];
       }
     if (chroma) cqt_classes(sp, (uint32_t*)(ws.basis_host.data() + off_cls));

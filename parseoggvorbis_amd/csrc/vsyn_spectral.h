@@ -185,8 +185,8 @@ static const uint32_t SPEC_LDS_BUDGET = 160u * 1024u;  // gfx950: 160 KiB of LDS
 struct SpectralWs {  // the stage's buffers: its own; the PCM is only read
   TableUpload tab;
   bool lds_set = false;                // the dynamic-LDS limit of every kind's kernels is raised on this handle's device (spec_raise_lds)
-  std::vector<double> chroma_key;      // what the kept chroma filterbanks were built from (n_fft, the chroma parameters, the distinct rates)
-  std::vector<float> chroma_bank;      // [rate][n_chroma][NB]
+  std::vector<double> chroma_key;      // what the kept chroma filterbanks were built from (n_fft, the chroma parameters, the (rate, tuning) pairs)
+  std::vector<float> chroma_bank;      // [bank][n_chroma][NB]
   DevBuf<uint32_t> segF, segmax;
   DevBuf<uint64_t> segoff;
   DevBuf<float> db, rows;

@@ -85,6 +85,7 @@ bool pitch_run(const CorpusOptions& o) { return o.pitch.frame_length != 0; }
 bool pyin_run(const CorpusOptions& o) { return o.pyin.frame_length != 0; }
 bool fdesc_run(const CorpusOptions& o) { return o.fdesc.n_fft != 0; }
 bool cqt_run(const CorpusOptions& o) { return o.cqt.n_bins != 0; }
+bool tuning_run(const CorpusOptions& o) { return o.tuning.bins_per_octave != 0; }
 bool loudness_run(const CorpusOptions& o) { return o.loudness; }
 bool post_run(const CorpusOptions& o) { return o.post.order != 0 || o.post.norm != VSYN_POST_NORM_NONE; }
 // columns of a spectral run's rows: the kind's dim, times 1 + the delta orders
@@ -420,6 +421,8 @@ struct Feeder {
     std::vector<uint64_t> loud_nb;           // its blocks
     std::vector<double> loud_z;              // and with loudness_blocks the block means of all files back to back
     std::vector<double> bpm;                 // beat run: per file the tempo its period came from
+    std::vector<double> tuning;              // tuning run: per file the estimate
+    std::vector<uint64_t> tuning_counts;     // and its two counts
   };
 
   // Synthesis of the packed batch. The PCM comes back as f32 planes unless a later stage reads it on the device (VSYN_SUBMIT_KEEP_PCM).
@@ -665,7 +668,16 @@ struct Feeder {
     const vsyn_pcm_cond* cond = gated ? trim_cond() : opts.condition ? &opts.cond : nullptr;
     if (opts.loudness_norm) o.loud.assign(S, NO_LOUDNESS_RECORD);
     int rc;
-    if (opts.beat) {  // the beat tracker in the rhythm stages' place: the same chain, the tempo per file beside the refusal words
+    if (opts.chroma_estimate) {  // each file's tuning estimated first (the entry refuses the stages it does not take)
+      o.tuning.assign(S, 0.0);
+      o.tuning_counts.assign(2u * (size_t)S, 0);
+      rc = vsyn_pcm_chain_chroma_est_host(
+          g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr, cond, &opts.spectral,
+          opts.chroma_given ? &opts.chroma_spec : nullptr, opts.pcen ? &opts.pcen_spec : nullptr, post_run(opts) ? &opts.post : nullptr,
+          &opts.chroma_estimate_spec, S, rates.data(), opts.resample_rate, g.rows.p, spec_rows, g.seg_rows.p, joined.data(),
+          opts.trim ? o.bounds.data() : nullptr, opts.split ? o.counts.data() : nullptr, opts.split ? o.iv.data() : nullptr, o.iv_stride,
+          peaks.data(), refs.data(), opts.loudness_norm ? o.loud.data() : nullptr, o.tuning.data(), &st, &err);
+    } else if (opts.beat) {  // the beat tracker in the rhythm stages' place: the same chain, the tempo per file beside the refusal words
       o.bpm.assign(S, 0.0);
       rc = vsyn_pcm_chain_beats_host(
           g.handle, gated ? &opts.trim_spec : nullptr, opts.split ? 1 : 0, opts.loudness_norm ? &opts.loudness_spec : nullptr, cond, &opts.spectral,
@@ -818,7 +830,12 @@ struct Feeder {
     std::vector<uint32_t> refused(S, 0u);
     vsyn_status st;
     const char* err = nullptr;
-    if (vsyn_pcm_cqt_host(g.handle, &opts.cqt, S, rates.data(), opts.resample_rate, g.rows.p, rows, g.seg_rows.p, refused.data(), &st, &err) != VSYN_OK)
+    if (opts.cqt_estimate) {
+      o.tuning.assign(S, 0.0);
+      o.tuning_counts.assign(2u * (size_t)S, 0);
+    }
+    if (vsyn_pcm_cqt_est_host(g.handle, &opts.cqt, opts.cqt_estimate ? &opts.cqt_estimate_spec : nullptr, S, rates.data(), opts.resample_rate, g.rows.p,
+                              rows, g.seg_rows.p, refused.data(), opts.cqt_estimate ? o.tuning.data() : nullptr, &st, &err) != VSYN_OK)
       return OkOrError(std::string("GPU constant-Q layer: ") + (err ? err : "constant-Q failed"));
     for (uint32_t s = 0; s < S; ++s) {
       if (!o.err[s].empty() || !refused[s]) continue;
@@ -830,6 +847,41 @@ struct Feeder {
         o.err[s] = "constant-Q: the PCM holds a sample that is not finite";
       }
     }
+    return OkOrError();
+  }
+
+  // Tuning run: each file's estimate, and with tuning_rows its piptrack rows, from the PCM still on the device (vsyn_pcm_tuning_host,
+  // resampled first in a resampled run). A frame with a sample that is not finite is NaN in the rows and gives the estimate no peak.
+  OkOrError tuning_stage(Group& g, Outcome& o) {
+    const uint32_t S = (uint32_t)g.pending.size(), cols = 2u * (opts.tuning_framing.n_fft / 2u + 1u);
+    std::vector<uint32_t> rates(S);
+    uint64_t rows = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+      rates[s] = o.err[s].empty() ? g.pending[s]->header.audio_sample_rate : 0;
+      if (rates[s] && opts.tuning_rows) rows += vsyn_spectral_num_frames(&opts.tuning_framing, std::min<uint64_t>(o.frames[s], o.plane));
+    }
+    if (opts.resample_rate && opts.tuning_rows) {  // the rows are those of the resampled frames: the stage's own count
+      vsyn_status st0;
+      const char* err0 = nullptr;
+      CHECK_ERR(g.seg_rows.ensure(S));
+      if (vsyn_pcm_tuning_host(g.handle, &opts.tuning_framing, &opts.tuning, S, rates.data(), opts.resample_rate, VSYN_TUNING_ROWS, nullptr, nullptr,
+                               nullptr, 0, g.seg_rows.p, &st0, &err0) != VSYN_OK)
+        return OkOrError(std::string("GPU tuning layer: ") + (err0 ? err0 : "tuning failed"));
+      rows = 0;
+      for (uint32_t s = 0; s < S && opts.tuning_rows; ++s) rows += g.seg_rows[s];
+    }
+    CHECK_ERR(g.rows.ensure(rows * cols + 1));
+    CHECK_ERR(g.seg_rows.ensure(S));
+    o.tuning.assign(S, 0.0);
+    o.tuning_counts.assign(2u * (size_t)S, 0);
+    vsyn_status st;
+    const char* err = nullptr;
+    if (vsyn_pcm_tuning_host(g.handle, &opts.tuning_framing, &opts.tuning, S, rates.data(), opts.resample_rate,
+                             opts.tuning_rows ? VSYN_TUNING_ROWS : VSYN_TUNING_ONLY, o.tuning.data(), o.tuning_counts.data(),
+                             opts.tuning_rows ? g.rows.p : nullptr, rows, g.seg_rows.p, &st, &err) != VSYN_OK)
+      return OkOrError(std::string("GPU tuning layer: ") + (err ? err : "tuning failed"));
+    if (!opts.tuning_rows)
+      for (uint32_t s = 0; s < S; ++s) g.seg_rows[s] = 0;  // nothing to deliver
     return OkOrError();
   }
 
@@ -861,7 +913,7 @@ struct Feeder {
   // A synthesis run's file: its PCM (or, for a spectral, pitch or frame descriptor run, its rows) to the callbacks.
   OkOrError deliver_pcm(Group& g, uint32_t s, const FileRecord& r, CorpusFileResult& out, const Outcome& o, uint64_t& row0) {
     const uint32_t C = opts.condition ? 1u : g.channels;  // channels delivered
-    const bool spectral = spectral_run(opts) || pitch_run(opts) || pyin_run(opts) || fdesc_run(opts) || cqt_run(opts) || loudness_run(opts);
+    const bool spectral = spectral_run(opts) || pitch_run(opts) || pyin_run(opts) || fdesc_run(opts) || cqt_run(opts) || tuning_run(opts) || loudness_run(opts);
     const uint64_t frames = o.frames[s], pl = o.plane;
     if (opts.condition) out.channels = 1;
     std::vector<DataRange<const float>> chans(C);
@@ -889,6 +941,11 @@ struct Feeder {
     stats.frames += frames;
     if (o.err[s].empty() && s < o.loud.size()) out.loudness = o.loud[s];
     if (o.err[s].empty() && s < o.bpm.size()) out.bpm = o.bpm[s];
+    if (o.err[s].empty() && s < o.tuning.size()) {
+      out.tuning = o.tuning[s];
+      out.tuning_counts[0] = o.tuning_counts[2u * s];
+      out.tuning_counts[1] = o.tuning_counts[2u * s + 1u];
+    }
     if (loudness_run(opts)) {  // the record and the block means: nothing goes to the callbacks; row0 counts the blocks in front
       if (o.err[s].empty() && s < o.loud.size()) {
         if (opts.loudness_blocks) out.loudness_blocks.assign(o.loud_z.begin() + row0, o.loud_z.begin() + row0 + o.loud_nb[s]);
@@ -896,7 +953,7 @@ struct Feeder {
       if (s < o.loud_nb.size()) row0 += o.loud_nb[s];
       return OkOrError();
     }
-    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : pyin_run(opts) ? 3u : fdesc_run(opts) ? 6u : cqt_run(opts) ? vsyn_cqt_dim(&opts.cqt) : spectral_dim(opts));
+    if (spectral) return deliver_rows(g, r, out, row0, g.seg_rows[s], pitch_run(opts) ? 2u : pyin_run(opts) ? 3u : fdesc_run(opts) ? 6u : cqt_run(opts) ? vsyn_cqt_dim(&opts.cqt) : tuning_run(opts) ? 2u * (opts.tuning_framing.n_fft / 2u + 1u) : spectral_dim(opts));
     if (!callbacks || !o.err[s].empty() || opts.intervals_only) return OkOrError();
     std::lock_guard<std::mutex> lk(callbacks_mu);
     if (opts.pcm_s16) {
@@ -912,7 +969,8 @@ struct Feeder {
     if (feature_run(opts)) return submit_features(g);
     const uint32_t C = g.channels, S = (uint32_t)g.pending.size();
     const bool pitch = pitch_run(opts), pyin = pyin_run(opts), fdesc = fdesc_run(opts), cqt = cqt_run(opts), loud = loudness_run(opts);
-    const bool spectral = spectral_run(opts) || pitch || pyin || fdesc || cqt || loud;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
+    const bool tune = tuning_run(opts);
+    const bool spectral = spectral_run(opts) || pitch || pyin || fdesc || cqt || tune || loud;  // the PCM stays on the device: only the spectral (pitch, descriptor) rows come back
     const bool resample = opts.resample_rate != 0;  // the PCM stays on the device until it is resampled
     const bool cond = opts.condition;               // ... and until it is conditioned
     double t0 = now_s();
@@ -947,6 +1005,7 @@ struct Feeder {
       else if (pyin) CHECK_ERR(pyin_stage(g, o));
       else if (fdesc) CHECK_ERR(fdesc_stage(g, o));
       else if (cqt) CHECK_ERR(cqt_stage(g, o));
+      else if (tune) CHECK_ERR(tuning_stage(g, o));
       else if (spectral) CHECK_ERR(spectral_stage(g, o));
     }
     double t2 = now_s();
@@ -1368,6 +1427,7 @@ struct CorpusCall {
   uint32_t* channels_out = nullptr;
   uint32_t* rate_out = nullptr;
   double* bpm_out = nullptr;              // a beat run's tempo per file
+  double* tuning_out = nullptr;           // a chroma run's estimated tuning per file
   uint64_t* bounds_out = nullptr;
   SplitOuts split;
   vsyn_loudness_record* records_out = nullptr;
@@ -1407,6 +1467,16 @@ struct CorpusCall {
       opts.chroma_given = true;
       opts.chroma_spec = *chroma;
     }
+  }
+  void chroma_estimate(const vsyn_tuning_spec* estimate) {
+    if (!estimate) return;
+    vsyn_spectral_spec lin = opts.spectral;
+    lin.kind = VSYN_SPEC_LIN_POWER;
+    const char* why = nullptr;
+    if (opts.spectral.kind != VSYN_SPEC_CHROMA && opts.spectral.kind != VSYN_SPEC_TONNETZ) return refuse(fn, "a tuning estimate is for the chroma kinds");
+    if (vsyn_tuning_check(&lin, estimate, &why) != VSYN_OK) return refuse(fn, why ? why : "invalid tuning spec");
+    opts.chroma_estimate = true;
+    opts.chroma_estimate_spec = *estimate;
   }
   void hpss(const vsyn_spectral_hpss* hpss) {
     if (!hpss) return;
@@ -1498,6 +1568,7 @@ struct CorpusCall {
       if (opts.split && split.frames_out) split.frames_out[i] = bad ? 0 : res.frames;
       if (opts.beat && bpm_out) bpm_out[i] = bad ? 0.0 : res.bpm;
       if (opts.beat && rate_out) rate_out[i] = res.sample_rate;
+      if (tuning_out) tuning_out[i] = bad ? 0.0 : res.tuning;
     });
   }
   int pcm() {
@@ -1751,6 +1822,60 @@ extern "C" int ogg_vorbis_cqt_corpus(const uint8_t* const* datas, const size_t* 
                        });
 }
 
+extern "C" int ogg_vorbis_cqt_corpus_est(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                         uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_cqt_spec* spec,
+                                         const vsyn_tuning_spec* estimate, float** rows_out, uint64_t* rows_count_out, uint64_t* frames_out,
+                                         uint32_t* rate_out, double* tuning_out, uint8_t* ok_out, const char** error_out_per_file,
+                                         double* stats_out, const char** error_out) {
+  if (!spec || !vsyn_cqt_dim(spec)) return refuse_call((void**)rows_out, num_files, "ogg_vorbis_cqt_corpus_est: invalid constant-Q spec", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  if (estimate) {
+    const vsyn_spectral_spec lin = {VSYN_SPEC_LIN_POWER, VSYN_SPEC_CENTER, 2048u, 512u, 2048u, 0u, 0u, 1u, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const char* why = nullptr;
+    if (vsyn_tuning_check(&lin, estimate, &why) != VSYN_OK || estimate->bins_per_octave != spec->bins_per_octave)
+      return refuse_call((void**)rows_out, num_files,
+                         std::string("ogg_vorbis_cqt_corpus_est: ") + (why ? why : "the estimate's bins_per_octave is not the transform's"), error_out);
+    opts.cqt_estimate = true;
+    opts.cqt_estimate_spec = *estimate;
+  }
+  opts.cqt = *spec;
+  opts.resample_rate = target_rate;
+  return malloc_corpus("cqt", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                         if (estimate && tuning_out) tuning_out[i] = bad ? 0.0 : res.tuning;
+                       });
+}
+
+extern "C" int ogg_vorbis_tuning_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                        uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_spectral_spec* spec,
+                                        const vsyn_tuning_spec* tun, int want_rows, float** rows_out, uint64_t* rows_count_out,
+                                        uint64_t* frames_out, uint32_t* rate_out, double* tuning_out, uint64_t* counts_out, uint8_t* ok_out,
+                                        const char** error_out_per_file, double* stats_out, const char** error_out) {
+  const char* why = nullptr;
+  if (!spec || !tun || vsyn_tuning_check(spec, tun, &why) != VSYN_OK)
+    return refuse_call((void**)rows_out, num_files, std::string("ogg_vorbis_tuning_corpus: ") + (why ? why : "invalid spec"), error_out);
+  if (want_rows && !rows_out) return refuse_call(nullptr, num_files, "ogg_vorbis_tuning_corpus: rows wanted, rows_out NULL", error_out);
+  CorpusOptions opts = call_options(threads, feeders, files_per_submit, device);
+  opts.tuning_framing = *spec;
+  opts.tuning = *tun;
+  opts.tuning_rows = want_rows != 0;
+  opts.resample_rate = target_rate;
+  return malloc_corpus("tuning", datas, lens, num_files, opts, (void**)rows_out, ok_out, error_out_per_file, stats_out, error_out,
+                       [&](size_t i, const CorpusFileResult& res, bool bad) {
+                         if (rows_count_out) rows_count_out[i] = bad ? 0 : res.feature_rows;
+                         if (frames_out) frames_out[i] = bad ? 0 : res.frames;
+                         if (rate_out) rate_out[i] = res.sample_rate;
+                         if (tuning_out) tuning_out[i] = bad ? 0.0 : res.tuning;
+                         if (counts_out) {
+                           counts_out[2 * i] = bad ? 0 : res.tuning_counts[0];
+                           counts_out[2 * i + 1] = bad ? 0 : res.tuning_counts[1];
+                         }
+                       });
+}
+
 extern "C" int ogg_vorbis_pcm_corpus_loud(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
                                           uint32_t files_per_submit, int device, uint32_t target_rate, int format, const vsyn_pcm_cond* cond,
                                           const vsyn_pcm_trim* gate, int gate_is_split, const vsyn_loudness_spec* loud, void** pcm_out,
@@ -1838,6 +1963,33 @@ extern "C" int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, co
   c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
   c.spectral(spec, target_rate, post);
   c.chroma(chroma);
+  c.pcen(pcen);
+  c.cond(cond);
+  c.gate(gate, split);
+  c.loud(loud);
+  return c.rows();
+}
+
+extern "C" int ogg_vorbis_spectral_corpus_chroma_est(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                                     uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec,
+                                                     const vsyn_spectral_chroma* chroma, uint32_t target_rate, const vsyn_spectral_pcen* pcen,
+                                                     const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* gate,
+                                                     int gate_is_split, const vsyn_loudness_spec* loud, const vsyn_tuning_spec* estimate,
+                                                     float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out,
+                                                     uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out,
+                                                     double* tuning_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                                                     const char** error_out) {
+  CorpusCall c("ogg_vorbis_spectral_corpus_chroma_est", datas, lens, num_files, threads, feeders, files_per_submit, device, (void**)rows_out,
+               ok_out, error_out_per_file, stats_out, error_out);
+  const bool split = gate && gate_is_split;
+  c.rows_count_out = rows_count_out;
+  c.bounds_out = bounds_out;
+  c.records_out = records_out;
+  c.tuning_out = estimate ? tuning_out : nullptr;
+  c.split_outputs(frames_out, intervals_out, intervals_count_out, split);
+  c.spectral(spec, target_rate, post);
+  c.chroma(chroma);
+  c.chroma_estimate(estimate);
   c.pcen(pcen);
   c.cond(cond);
   c.gate(gate, split);

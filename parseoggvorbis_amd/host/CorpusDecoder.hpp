@@ -43,6 +43,8 @@ struct CorpusFileResult {
   vsyn_loudness_record loudness = {0.0, 0.0, 0u, 0u, 0u, 0.0f, 0u, 0u};  // CorpusOptions::loudness: the file's record
   std::vector<double> loudness_blocks;    // ... and with loudness_blocks its block means z_j
   double bpm = 0;                         // CorpusOptions::beat: the tempo the beat period came from (0.0: no beats to take one from)
+  double tuning = 0;                      // a tuning run: the estimate, in fractions of a bin of tuning.bins_per_octave
+  uint64_t tuning_counts[2] = {0, 0};     // ... the peaks it was taken from, and those at or above their median magnitude
 };
 
 struct CorpusCallbacks {
@@ -135,6 +137,17 @@ struct CorpusOptions {
   // finite, a file at whose rate the top bin leaves the Nyquist band and a file whose rate makes the wavelets longer than the stage's
   // caps fail alone, by name. Excludes what a pitch run excludes, pitch and fdesc.
   vsyn_cqt_spec cqt = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
+  // cqt_estimate (a constant-Q run): each file's tuning is estimated first (vsyn_pcm_cqt_est_host with cqt_estimate_spec) and goes to
+  // CorpusFileResult::tuning; cqt.tuning is not used.
+  bool cqt_estimate = false;
+  vsyn_tuning_spec cqt_estimate_spec = {0.0, 0.0, 0.0, 0.0, 0u, 0u};
+  // tuning run (tuning.bins_per_octave != 0): as a pitch run, but each file's tuning estimate (include/vorbis_synth_hip.h, "tuning
+  // estimation": vsyn_pcm_tuning_host on the STFT of tuning_framing, a lin_power spec) into CorpusFileResult::tuning and
+  // tuning_counts; with tuning_rows also the file's piptrack rows, delivered through gotFileFeatures with dim 2 (n_fft / 2 + 1): a
+  // row's pitches, then its magnitudes. Excludes what a pitch run excludes, pitch, fdesc and cqt.
+  vsyn_spectral_spec tuning_framing = {0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  vsyn_tuning_spec tuning = {0.0, 0.0, 0.0, 0.0, 0u, 0u};
+  bool tuning_rows = false;
   // loudness run (loudness): as a pitch run, but each file's integrated loudness record (include/vorbis_synth_hip.h, "loudness":
   // vsyn_pcm_loudness_host, resampled first with resample_rate; loudness_spec.channel_mode picks the planes or their downmix) into
   // CorpusFileResult::loudness, and with loudness_blocks the block means into CorpusFileResult::loudness_blocks; nothing goes to the
@@ -150,6 +163,10 @@ struct CorpusOptions {
   // the default chroma parameters (include/vorbis_synth_hip.h, "chroma"). Another kind does not read them.
   bool chroma_given = false;
   vsyn_spectral_chroma chroma_spec = {12u, VSYN_CHROMA_NORM_MAX, VSYN_CHROMA_BASE_C, 0u, 0.0, 5.0, 2.0};
+  // chroma_estimate (a spectral run of a chroma kind without hpss, rhythm or beat): each file's tuning is estimated first on the PCM
+  // the chroma kernel sees (vsyn_pcm_chain_chroma_est_host) and goes to CorpusFileResult::tuning; chroma_spec.tuning is not used.
+  bool chroma_estimate = false;
+  vsyn_tuning_spec chroma_estimate_spec = {0.0, 0.0, 0.0, 0.0, 0u, 0u};
   // hpss (a spectral run of kind mel_power or lin_power): each file's rows go through the HPSS stage on the device between the
   // spectral rows and PCEN (include/vorbis_synth_hip.h, "HPSS"). A spec the stage refuses (another kind, or PCEN on the mask or the
   // median) is every file's error. The default is off: the rows without the stage.
@@ -362,6 +379,19 @@ int ogg_vorbis_spectral_corpus_chroma(const uint8_t* const* datas, const size_t*
                                       float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out,
                                       uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out, uint8_t* ok_out,
                                       const char** error_out_per_file, double* stats_out, const char** error_out);
+// ogg_vorbis_spectral_corpus_chroma with each file's tuning estimated first (estimate != NULL: CorpusOptions::chroma_estimate,
+// chroma_estimate_spec; spec must be a chroma kind and estimate->bins_per_octave the chroma parameters' n_chroma): the rows are those
+// of that entry called with the file's own estimate, which goes to tuning_out[i] (0.0 for a failed file); estimate = NULL is that
+// entry and tuning_out is not written. A spec pair the estimator refuses refuses the call. Same output contract.
+int ogg_vorbis_spectral_corpus_chroma_est(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                                          uint32_t files_per_submit, int device, const vsyn_spectral_spec* spec,
+                                          const vsyn_spectral_chroma* chroma, uint32_t target_rate, const vsyn_spectral_pcen* pcen,
+                                          const vsyn_spectral_post* post, const vsyn_pcm_cond* cond, const vsyn_pcm_trim* gate,
+                                          int gate_is_split, const vsyn_loudness_spec* loud, const vsyn_tuning_spec* estimate,
+                                          float** rows_out, uint64_t* rows_count_out, uint64_t* bounds_out, uint64_t* frames_out,
+                                          uint32_t** intervals_out, uint64_t* intervals_count_out, vsyn_loudness_record* records_out,
+                                          double* tuning_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                                          const char** error_out);
 // ogg_vorbis_spectral_corpus_chroma with the HPSS stage (hpss != NULL: CorpusOptions::hpss_spec = *hpss) between the spectral rows
 // and PCEN; hpss = NULL is that entry. An HPSS spec the stage refuses is every file's error. Same output contract.
 int ogg_vorbis_spectral_corpus_hpss(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
@@ -428,6 +458,23 @@ int ogg_vorbis_cqt_corpus(const uint8_t* const* datas, const size_t* lens, size_
                           uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_cqt_spec* spec, float** rows_out,
                           uint64_t* rows_count_out, uint64_t* frames_out, uint32_t* rate_out, uint8_t* ok_out,
                           const char** error_out_per_file, double* stats_out, const char** error_out);
+// ogg_vorbis_cqt_corpus with each file's tuning estimated first (estimate != NULL: CorpusOptions::cqt_estimate, cqt_estimate_spec;
+// estimate->bins_per_octave must be spec's): the rows are those of that entry called with the file's own estimate, which goes to
+// tuning_out[i] (0.0 for a failed file); estimate = NULL is that entry and tuning_out is not written.
+int ogg_vorbis_cqt_corpus_est(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                              uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_cqt_spec* spec,
+                              const vsyn_tuning_spec* estimate, float** rows_out, uint64_t* rows_count_out, uint64_t* frames_out,
+                              uint32_t* rate_out, double* tuning_out, uint8_t* ok_out, const char** error_out_per_file, double* stats_out,
+                              const char** error_out);
+// tuning run (CorpusOptions::tuning_framing = *spec, tuning = *tun, tuning_rows = want_rows != 0; target_rate as for
+// ogg_vorbis_pitch_corpus): tuning_out[i] and counts_out[i][2] per file (0 for a failed file; either may be NULL), and with want_rows
+// rows_out receives per file NULL or a buffer of rows_count_out[i] * 2 * (n_fft / 2 + 1) floats, released with
+// ogg_vorbis_features_free. An invalid spec pair refuses the call.
+int ogg_vorbis_tuning_corpus(const uint8_t* const* datas, const size_t* lens, size_t num_files, int threads, int feeders,
+                             uint32_t files_per_submit, int device, uint32_t target_rate, const vsyn_spectral_spec* spec,
+                             const vsyn_tuning_spec* tun, int want_rows, float** rows_out, uint64_t* rows_count_out, uint64_t* frames_out,
+                             uint32_t* rate_out, double* tuning_out, uint64_t* counts_out, uint8_t* ok_out, const char** error_out_per_file,
+                             double* stats_out, const char** error_out);
 void ogg_vorbis_features_free(float* rows);
 }
 

@@ -96,8 +96,8 @@ def spectral_spec(kind="log_mel", n_fft=2048, hop_length=512, win_length=None, n
 
 def chroma_spec(n_chroma=12, tuning=0.0, chroma_norm=math.inf, ctroct=5.0, octwidth=2.0, base_c=True):
     """Checks the chroma arguments (include/vorbis_synth_hip.h, "chroma", step 6) and returns the C struct (binding.SpectralChroma).
-    chroma_norm: numpy.inf (max), 1, 2 or None; octwidth=None: no octave weighting. tuning is a number: librosa's tuning=None
-    (estimate_tuning) is not available."""
+    chroma_norm: numpy.inf (max), 1, 2 or None; octwidth=None: no octave weighting. tuning is a number here; librosa's tuning=None
+    (estimate_tuning first) is get_spectral_batch(tuning="estimate"), and None itself stays refused."""
     from .binding import SpectralChroma
     n_chroma = _int("n_chroma", n_chroma)
     if not 1 <= n_chroma <= MAX_N_CHROMA:
@@ -107,6 +107,8 @@ def chroma_spec(n_chroma=12, tuning=0.0, chroma_norm=math.inf, ctroct=5.0, octwi
         raise SpectralError("chroma_norm must be numpy.inf, 1, 2 or None, got %r" % (chroma_norm,))
     norm = CHROMA_NORMS[None if chroma_norm is None else (math.inf if chroma_norm == math.inf else int(chroma_norm))]
     vals = {}
+    if tuning is None:
+        raise SpectralError("tuning must be a finite number, got None (librosa's tuning=None is tuning=\"estimate\" in get_spectral_batch)")
     for name, v in (("tuning", tuning), ("ctroct", ctroct), ("octwidth", octwidth)):
         if name == "octwidth" and v is None:
             vals[name] = 0.0
@@ -275,6 +277,21 @@ def checked_specs(a):
     target = check_sr(sr, SpectralError)
     spec = spectral_spec(kind, n_fft, hop_length, win_length, n_mels, fmin, fmax, htk, norm, center, power, log_floor, amin, top_db,
                          n_mfcc)
+    est = None
+    if isinstance(tuning, str) and tuning == "estimate":  # librosa's tuning=None: each file's own estimate first (tuning.py)
+        if "tuning_resolution" not in a:
+            raise SpectralError("tuning='estimate' is available in get_spectral_batch only")
+        if kind not in CHROMA_KINDS:
+            raise SpectralError("tuning='estimate' is for kind %s, not %r" % (" or ".join(repr(k) for k in CHROMA_KINDS), kind))
+        if hpss is not None:
+            raise SpectralError("tuning='estimate' is not available with hpss")
+        from .tuning import TuningError, tuning_spec
+        try:
+            est = tuning_spec(a["tuning_fmin"], a["tuning_fmax"], a["tuning_threshold"], a["tuning_resolution"],
+                              n_chroma if isinstance(n_chroma, (int, np.integer)) and not isinstance(n_chroma, bool) and 1 <= n_chroma <= 256 else 12)
+        except TuningError as e:
+            raise SpectralError("tuning='estimate': tuning_%s" % e) from None
+        tuning = 0.0
     chroma = chroma_spec(n_chroma, tuning, chroma_norm, ctroct, octwidth, base_c)
     post, dim, keep = post_spec(spec_dim(spec, chroma), delta, delta_width, normalize, std_floor)
     if post is not None and spec.kind in LINEAR_KINDS:
@@ -295,7 +312,7 @@ def checked_specs(a):
     split = split_spec(split_db, split_frame_length, split_hop_length, split_index, trim, SpectralError)
     loud = loudness_args(loudness_normalize, loudness, cond, SpectralError)
     return SimpleNamespace(target=target, spec=spec, chroma=chroma, post=post, dim=dim, keep=keep, pc=pc, hp=hp, cond=cond, trim=trim, split=split,
-                           loud=loud)
+                           loud=loud, est=est)
 
 
 _load = _corpus.load
@@ -308,7 +325,8 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                        trim_hop_length=512, trim_index=None, split_db=None, split_frame_length=2048, split_hop_length=512, split_index=None,
                        pcen=False, pcen_gain=0.98, pcen_bias=2.0, pcen_power=0.5, pcen_time_constant=0.4, pcen_eps=1e-6, pcen_b=None,
                        pcen_scale=1.0, loudness_normalize=None, loudness=None, n_chroma=12, tuning=0.0, chroma_norm=math.inf, ctroct=5.0,
-                       octwidth=2.0, base_c=True, hpss=None, hpss_kernel_size=31, hpss_power=2.0, hpss_margin=1.0, hpss_output="component"):
+                       octwidth=2.0, base_c=True, hpss=None, hpss_kernel_size=31, hpss_power=2.0, hpss_margin=1.0, hpss_output="component",
+                       tuning_resolution=0.01, tuning_fmin=150.0, tuning_fmax=4000.0, tuning_threshold=0.1, tunings=None):
     """Spectral matrices of many Ogg Vorbis files in one corpus run: a list of float32 arrays (frames, dim), dim = n_mfcc for
     "mfcc", n_mels for the other mel kinds. The linear kinds have no filterbank: "lin_power" is |X|^power and "lin_db" its dB image
     (amin, top_db as for "mel_db"; librosa.amplitude_to_db(|X|, amin=a) is power=2, amin=a*a), both (frames, n_fft / 2 + 1);
@@ -343,7 +361,11 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     kind="chroma" gives librosa.feature.chroma_stft's arithmetic (include/vorbis_synth_hip.h, "chroma"; model: tests/chroma_model.py):
     (frames, n_chroma) rows of the |X|^power spectrum (power=2 is chroma_stft's) projected on librosa.filters.chroma(sr, n_fft,
     n_chroma, tuning, ctroct, octwidth, base_c) and normalised per frame by chroma_norm (numpy.inf, 1, 2 or None); octwidth=None turns
-    the octave weighting off. tuning must be a number (librosa's tuning=None estimation is not available). kind="tonnetz" gives
+    the octave weighting off. tuning is a number, or "estimate" (librosa's tuning=None; None itself stays refused): each file's tuning is
+    estimated first on the device (parseoggvorbis_amd/tuning.py, "tuning estimation" in the header) from the signal the chroma kernel
+    sees, at this call's n_fft, hop_length, win_length, center and power, with tuning_fmin, tuning_fmax, tuning_threshold,
+    tuning_resolution and bins_per_octave = n_chroma; the rows are those of the same call with that number, bit for bit, and tunings
+    (optional list) receives it per file, None for a failed file and for every file when tuning is a number. kind="tonnetz" gives
     librosa.feature.tonnetz(chroma=those rows): (frames, 6). A frame that holds an Inf or NaN sample is all NaN. Both take delta /
     normalize and every PCM stage like the mel kinds, and refuse pcen. The chroma arguments are checked for every kind.
     hpss="harmonic" / "percussive" (kind "mel_power" or "lin_power" only; SpectralError before anything is loaded otherwise) replaces
@@ -358,6 +380,8 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
     c = checked_specs(dict(locals()))
     target, spec, chroma, post, dim, pc, hp = c.target, c.spec, c.chroma, c.post, c.dim, c.pc, c.hp
     cond, trim, split, loud = c.cond, c.trim, c.split, c.loud
+    if tunings is not None and not isinstance(tunings, list):
+        raise SpectralError("tunings must be a list (or None), got %r" % (tunings,))
     lib = _load()
     counts = np.zeros(len(list_of_bytes), np.uint64)
     is_chroma = kind in CHROMA_KINDS
@@ -368,9 +392,13 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
         joined, bounds = np.zeros(max(n, 1), np.uint64), np.zeros((max(n, 1), 2), np.uint64)
         records = np.zeros(max(n, 1), LOUDNESS_RECORD_DTYPE)
         gate = split if split is not None else trim
+        tail, est_out = (), ()
         try:
             if hpss is not None:  # the chroma entry with the HPSS spec behind the rate (its kinds read no chroma parameters)
                 fn, head, mid = lib.ogg_vorbis_spectral_corpus_hpss, (None,), (C.byref(hp),)
+            elif is_chroma and c.est is not None:
+                fn, head, mid = lib.ogg_vorbis_spectral_corpus_chroma_est, (C.byref(chroma),), ()
+                tail, est_out = (C.byref(c.est),), (np.zeros(max(n, 1), np.float64),)
             elif is_chroma:
                 fn, head, mid = lib.ogg_vorbis_spectral_corpus_chroma, (C.byref(chroma),), ()
             else:
@@ -379,8 +407,8 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
                               (threads, feeders, files_per_submit, device, C.byref(spec)) + head + (target,) + mid +
                               (C.byref(pc) if pcen else None,
                                None if post is None else C.byref(post), C.byref(cond) if cond.options else None,
-                               None if gate is None else C.byref(gate), int(split is not None), None if loud is None else C.byref(loud)),
-                              (counts, bounds, joined, ib.ptrs, ib.counts, records),
+                               None if gate is None else C.byref(gate), int(split is not None), None if loud is None else C.byref(loud)) + tail,
+                              (counts, bounds, joined, ib.ptrs, ib.counts, records) + est_out,
                               lambda i, p: _corpus.copy_into(np.zeros((int(counts[i]), dim), np.float32), p), SpectralError, errors,
                               "spectral", stats)
             give_split_index(split_index, ib if split is not None else None, res)
@@ -388,7 +416,11 @@ def get_spectral_batch(list_of_bytes, kind="log_mel", n_fft=2048, hop_length=512
             ib.free()
         give_trim_index(trim_index, bounds[:n] if trim is not None else None, res)
         give_loudness(loudness, records if loud is not None else None, res)
+        if tunings is not None:
+            tunings[:] = [float(est_out[0][i]) if est_out and isinstance(r, np.ndarray) else None for i, r in enumerate(res)]
         return _finish(spec, res)
+    if tunings is not None:
+        tunings[:] = [None] * len(list_of_bytes)
     give_loudness(loudness, None, [None] * len(list_of_bytes))
     if pcen:  # the one entry with every stage's spec (NULL: off)
         n = len(list_of_bytes)
